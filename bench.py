@@ -7,7 +7,7 @@ holds the N x 256-scan batch and fans the shards out over RCCL (grouped isend / 
 matches its shard, the result records are gathered to rank 0 (weak scaling; no collective on the data path).
 `--config C5`: BASELINE.json configs[4] per GPU -- multi-hypothesis relocalisation, 512 seed poses x one 10k-point
 scan against the 5M-point map (x 8 GPUs = the 4096 seeds of configs[4]); the scan is broadcast, the seeds are
-sharded, the best hypothesis is an arg-max over all ranks.  The default run reports C5 as a side figure
+sharded, the best hypothesis is an arg-max over all ranks.  A `--full` run reports C5 as a side figure
 (`multi_hypothesis`), configs[1] (one scan) as `single_scan_ms`.
 
 One step = the whole hot path over one batch with inputs resident in HBM: voxel normal-distributions build of the
@@ -22,6 +22,11 @@ have left.  `roofline.kernel_ms` is always the duration of ONE launch (HIP event
 `python bench.py --gpus N` is one command: without WORLD_SIZE in the environment the process starts the N ranks itself
 (`python -m torch.distributed.run`, one rank per GPU) before it has touched the GPU, relays rank 0's line and exits with
 the ranks' status; under a launcher (WORLD_SIZE set) it is a rank.
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, the K timed steps, the JSON line.  `--full` adds
+everything else behind the timed region: the map build timed alone (`roofline.map_build`), the steady-state and
+moving-local-map legs, the single-scan, reference-call-pattern, configs[4], front-end and local-map figures, and the CPU
+baseline with its parity check.  `--dump-outputs DIR` writes the result records of the last timed step as .npy files.
 
 Layout of this file: parse_args / spawn_ranks (the launcher) -- init_env, make_inputs, Pipeline (set-up) -- run_timed,
 kernel_figures (the timed region and what the library's events say about it) -- leg_* (side figures behind the timed
@@ -133,6 +138,10 @@ def parse_args(argv=None):
     ap.add_argument("--no-single-scan", action="store_true", help="skip the side figures (configs[1] latency, C5 leg, rows f1-f3)")
     ap.add_argument("--cpu-sample", type=int, default=256, help="matches timed on the host cores")
     ap.add_argument("--cpu-reps", type=int, default=5, help="times the CPU sample is run (median reported)")
+    ap.add_argument("--full", action="store_true", help="also every figure behind the timed region (module docstring); the "
+                    "options above that switch a side leg off act within --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result records of the last timed step to DIR/<field>.npy (float32 / float64)")
     return ap.parse_args(argv)
 
 
@@ -371,7 +380,7 @@ class Pipeline:
         self.gmap = self.gmaps[0]
         torch.cuda.synchronize()
         self.solo_build_ms = []
-        for _ in range(3):                                      # the build alone, nothing else on the GPU
+        for _ in range(3 if args.full else 0):                  # the build alone, nothing else on the GPU
             self.gmaps[-1].rebuild(dev_ptr=self.d_map.data_ptr(), n=len(I.map_xy), stride=8)
             self.solo_build_ms.append(self.bctx.last_timing()[0])
         torch.cuda.synchronize()
@@ -546,6 +555,47 @@ def kernel_figures(pipe, env, args):
     return F
 
 
+def last_step_outputs(pipe, env, F):
+    """What the timed path hands its caller in the last timed step, on rank 0, and where the records come from.
+    configs[2] / [3]: the result records -- at N > 1 those gathered from every rank, in rank order; if that gather failed
+    (comm.gather_error) rank 0's own shard, and the source says so.  configs[4]: rank 0's records (the path gathers
+    no records) and, at N > 1, the arg-max over all ranks (best_trans_prob / best_seed)."""
+    res, extra, source = F.res, {}, "rank 0" if env.world > 1 else "all ranks"
+    last = (pipe.args.warmup + pipe.args.steps - 1) % pipe.nbuf
+    if env.world > 1 and not pipe.I.c5:
+        if "gather_error" in env.comm:
+            source = "rank 0 only: the gather of the records failed (comm.gather_error)"
+        else:
+            res = np.frombuffer(b"".join(t.cpu().numpy().tobytes() for t in pipe.gathered[last]), dtype=pipe.capi.RESULT_DTYPE)
+            source = "all ranks"
+    if pipe.best_log:
+        extra = {"best_trans_prob": np.array([float(pipe.best_log[-1][0].item())]),
+                 "best_seed": np.array([float(pipe.best_log[-1][1].item())])}
+        source += " + arg-max over all ranks"
+    return res, extra, source
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res, extra, max_bytes=DUMP_MAX_BYTES):
+    """DIR/<field>.npy for every field of the result records (record i = match i; floating-point fields as they are,
+    integer fields as float64, exact) and every array of `extra`.  The inputs are seeded, so two runs with the same
+    arguments compare output for output.  Above max_bytes a fixed sample of the records is written, with their indices
+    (record_index.npy).  Returns the number of records written."""
+    cols = {n: res[n] if res.dtype[n].base.kind == "f" else res[n].astype(np.float64) for n in res.dtype.names}
+    per_record = sum(c.nbytes for c in cols.values()) / max(1, len(res))
+    keep = int((max_bytes - sum(a.nbytes for a in extra.values())) // (per_record + 8))
+    if len(res) > keep:
+        idx = np.sort(np.random.default_rng(0).choice(len(res), keep, replace=False))
+        cols = {n: c[idx] for n, c in cols.items()}
+        cols["record_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in list(cols.items()) + list(extra.items()):
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(a))
+    return min(len(res), keep)
+
+
 # ------------------------------------------------------------------------------------------------ side legs (N = 1)
 def leg_steady(pipe, args, first):
     """The same pipelined step for >= 200 more steps -- the driver's 20 timed steps are 10 ms, about the length of the
@@ -649,9 +699,9 @@ def leg_reference_faithful(pipe, out):
 
 
 def leg_multi_hypothesis(pipe, env):
-    """configs[4] as a side figure of the default run, on every rank: 512 seeds x one scan vs a 5M-point map (map
+    """configs[4] as a side figure of a --full run, on every rank: 512 seeds x one scan vs a 5M-point map (map
     rebuild + matches).  At N > 1 this is the whole configs[4] pattern -- the scan broadcast from rank 0, the 4096-seed
-    lattice cut into strided shards, the arg-max of the scores over all ranks -- so that the driver's multi-GPU run
+    lattice cut into strided shards, the arg-max of the scores over all ranks -- so that a multi-GPU --full run
     executes it too; a failure here is reported in the line, it does not take the headline figure down."""
     import torch
     import torch.distributed as dist
@@ -911,16 +961,18 @@ def headline(env, args, I, pipe, F, elapsed, rebuilt_timed, legs):
             "8 x 512 = 4096-seed lattice)" % (B, n_scan, cfg["n_map"], world)) if c5 else (
             "BASELINE configs[2]: batch of %d scans x %d pts vs shared %d-pt map, 0.5 m voxels, per GPU (configs[3] sharding "
             "at N>1)" % (B, n_scan, cfg["n_map"]))
-    v_cells = int(pipe.gmaps[0].info().n_cells)              # voxels of the search set (>= min_pts points)
-    mb_bytes = len(I.map_xy) * 8.0 + v_cells * 24.0
-    mb_ms = float(np.median(pipe.solo_build_ms))
-    mb_traffic, mb_src = side_traffic("c5_build" if c5 else "build")
     ft_traffic, ft_src = side_traffic("c5_fitness" if c5 else "fitness")
-    map_build_roofline = {"kernels": "the chain of ndt_map_build_dev (DESIGN.md 4.1), alone on the GPU", "ms": mb_ms,
-                          "map_points": int(len(I.map_xy)), "voxels": v_cells, "algorithmic_bytes_per_build": mb_bytes,
-                          "achieved_GBps": mb_bytes / (mb_ms * 1e-3) / 1e9, "frac": mb_bytes / (mb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          "traffic": mb_traffic, "traffic_source": mb_src,
-                          "note": "SURVEY 8d: M x 8 B read + V x 24 B written"}
+    mb_ms = map_build_roofline = None
+    if pipe.solo_build_ms:                                   # --full: the build timed alone (Pipeline)
+        v_cells = int(pipe.gmaps[0].info().n_cells)          # voxels of the search set (>= min_pts points)
+        mb_bytes = len(I.map_xy) * 8.0 + v_cells * 24.0
+        mb_ms = float(np.median(pipe.solo_build_ms))
+        mb_traffic, mb_src = side_traffic("c5_build" if c5 else "build")
+        map_build_roofline = {"kernels": "the chain of ndt_map_build_dev (DESIGN.md 4.1), alone on the GPU", "ms": mb_ms,
+                              "map_points": int(len(I.map_xy)), "voxels": v_cells, "algorithmic_bytes_per_build": mb_bytes,
+                              "achieved_GBps": mb_bytes / (mb_ms * 1e-3) / 1e9, "frac": mb_bytes / (mb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "traffic": mb_traffic, "traffic_source": mb_src,
+                              "note": "SURVEY 8d: M x 8 B read + V x 24 B written"}
     out = {
         "metric": "scan-matches/sec (10k-pt scan vs 1M-pt NDT map)" if not c5 else "scan-matches/sec (seed poses of one 10k-pt scan vs 5M-pt NDT map)",
         "value": world * B * args.steps / elapsed,
@@ -1011,12 +1063,16 @@ def main(argv=None):
     rank, world, c5 = env.rank, env.world, I.c5
 
     nst = args.steps + args.warmup
-    side_legs = world == 1 and not args.no_single_scan and not c5      # steady-state and moving-map legs behind the timed region
+    side_legs = args.full and world == 1 and not args.no_single_scan and not c5      # steady-state and moving-map legs behind the timed region
     n_extra = (max(0, args.steady_steps) + 2 * max(0, args.moving_steps)) if side_legs else 0
     pipe = Pipeline(env, args, I, nst + n_extra)
 
     elapsed, rebuilt_timed = run_timed(pipe, env, args)
     F = kernel_figures(pipe, env, args)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        res, extra, source = last_step_outputs(pipe, env, F)
+        dumped = {"dir": args.dump_outputs, "records": dump_outputs(args.dump_outputs, res, extra), "records_from": source}
 
     legs, nxt = {}, nst
     if side_legs and args.steady_steps > 0:
@@ -1033,19 +1089,21 @@ def main(argv=None):
         nxt += args.moving_steps
 
     out = headline(env, args, I, pipe, F, elapsed, rebuilt_timed, legs) if rank == 0 else None
+    if dumped:
+        out["dump_outputs"] = dumped
 
-    side_figures = rank == 0 and world == 1 and not args.no_single_scan
+    side_figures = args.full and rank == 0 and world == 1 and not args.no_single_scan
     if side_figures and not c5:
         leg_single_scan(pipe, out)
         leg_reference_faithful(pipe, out)
-    if not c5 and not args.no_single_scan and (world > 1 or rank == 0):
+    if args.full and not c5 and not args.no_single_scan and (world > 1 or rank == 0):
         mh = leg_multi_hypothesis(pipe, env)
         if rank == 0:
             out["multi_hypothesis"] = mh
     if side_figures and not c5:
         leg_front_end(pipe, out)
         leg_local_map(pipe, args, out)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         leg_cpu_baseline(args, I, F.res, out)
 
     if rank == 0:

@@ -66,3 +66,38 @@ def test_a_rank_under_a_launcher_of_the_wrong_size_says_so(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.init_env(bench.parse_args(["--gpus", "4"]))
     assert "WORLD_SIZE 2 != --gpus 4" in str(e.value)
+
+
+def test_plain_run_is_the_default_and_dumps_are_off():
+    a = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 4 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_every_record_field_as_float(tmp_path):
+    from ndt_slam_amd import capi
+    res = np.zeros(5, dtype=capi.RESULT_DTYPE)
+    res["pose"] = np.arange(15.0).reshape(5, 3); res["T00"] = 0.5; res["iters"] = [1, 2, 3, 4, 5]; res["H"][:, 4] = -1.0
+    assert bench.dump_outputs(str(tmp_path / "d"), res, {"best_seed": np.array([17.0])}) == 5
+    got = {f.name[:-4]: np.load(f) for f in (tmp_path / "d").iterdir()}
+    assert set(got) == set(capi.RESULT_DTYPE.names) | {"best_seed"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["T00"].dtype == np.float32 and got["iters"].dtype == np.float64
+    assert got["pose"].tobytes() == res["pose"].tobytes() and got["iters"].tolist() == [1, 2, 3, 4, 5]
+    assert got["H"].shape == (5, 9) and got["best_seed"].tolist() == [17.0]
+
+
+def test_dump_outputs_samples_a_fixed_subset_above_the_size_cap(tmp_path):
+    from ndt_slam_amd import capi
+    res = np.zeros(1000, dtype=capi.RESULT_DTYPE)
+    res["iters"] = np.arange(1000)
+    cap = 100 * 256
+    written = [bench.dump_outputs(str(tmp_path / run), res, {}, max_bytes=cap) for run in ("a", "b")]
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert sum(x.nbytes for x in a.values()) <= cap
+    idx = a["record_index.npy"]
+    assert 0 < len(idx) < 1000 and np.all(np.diff(idx) > 0) and a["iters.npy"].tolist() == idx.tolist()
+    assert written == [len(idx), len(idx)]
+    assert all(a[n].tobytes() == b[n].tobytes() for n in a)

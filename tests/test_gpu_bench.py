@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "8",
-                          "--cpu-reps", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--cpu-reps", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -55,14 +56,43 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert d["steady_state"]["steps"] == 200 and d["steady_state"]["value"] > 0
 
 
-def test_two_rank_path_walks_through_on_one_gpu():
+def test_plain_run_times_the_steps_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline figure and no side figure; --dump-outputs writes the last timed step's
+    records, and two runs with the same arguments write the same bytes (seeded inputs, deterministic matches)."""
+    from ndt_slam_amd import capi
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / ("run%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(d_out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "matches/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["metric"].startswith("scan-matches/sec")
+        assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+        for k in ("cpu_baseline", "parity", "steady_state", "moving_map", "multi_hypothesis", "single_scan_ms", "local_map"):
+            assert k not in d, k
+        assert d["map_build_ms"] is None and d["roofline"]["map_build"] is None and 0 < d["roofline"]["frac"] < 1
+        files = {f.name: np.load(f) for f in d_out.iterdir()}
+        assert set(files) == {n + ".npy" for n in capi.RESULT_DTYPE.names}
+        assert all(a.dtype in (np.float32, np.float64) and len(a) == 256 for a in files.values())
+        assert np.all(files["status.npy"] == 0) and d["converged"] == int(files["converged.npy"].sum())
+        assert d["dump_outputs"] == {"dir": str(d_out), "records": 256, "records_from": "all ranks"}
+        dumps.append(files)
+    assert all(dumps[0][n].tobytes() == dumps[1][n].tobytes() for n in dumps[0])
+
+
+def test_two_rank_path_walks_through_on_one_gpu(tmp_path):
     """N > 1 code path (sharded scans, gather of the result records on a side stream, MAX over ranks, rank 0
-    prints) rehearsed with both ranks on device 0 over gloo; the real run uses RCCL, one rank per GPU."""
+    prints and dumps the records of both ranks) rehearsed with both ranks on device 0 over gloo; the real run uses RCCL,
+    one rank per GPU."""
     env = dict(os.environ, NDT_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     # ONE command, as the driver types it at N = 1: bench.py starts the two ranks itself (bench.spawn_ranks)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
-                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+                          "--dump-outputs", str(tmp_path / "d")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{")          # the launcher relays rank 0's line and nothing else
@@ -77,27 +107,35 @@ def test_two_rank_path_walks_through_on_one_gpu():
     mh = d["multi_hypothesis"]                         # the configs[4] leg of the default run, both ranks
     assert "error" not in mh, mh
     assert mh["broadcast_scan_ms"] > 0 and 0 <= mh["best_over_all_ranks"]["seed"] < 4096 and mh["seeds_per_s"] > 0
+    # the dump holds what the caller on rank 0 receives: the gathered records of both ranks, rank 0's first
+    assert d["dump_outputs"]["records"] == 512 and d["dump_outputs"]["records_from"] == "all ranks"
+    conv = np.load(tmp_path / "d" / "converged.npy")
+    assert len(conv) == 512 and np.all(np.load(tmp_path / "d" / "status.npy") == 0) and int(conv[:256].sum()) == d["converged"]
 
 
-def test_two_rank_multi_hypothesis_path_walks_through_on_one_gpu():
+def test_two_rank_multi_hypothesis_path_walks_through_on_one_gpu(tmp_path):
     """configs[4] at N > 1 (scan broadcast, seeds sharded by stride, arg-max of the scores over the ranks) rehearsed
     with both ranks on device 0 over gloo."""
     env = dict(os.environ, NDT_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--config", "C5"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                          "--config", "C5", "--dump-outputs", str(tmp_path / "d")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["config"]["matches_per_gpu"] == 512 and d["config"]["map_points"] == 5_000_000
     g = d["best_hypothesis"]["global"]
     assert g["trans_prob"] >= d["best_hypothesis"]["trans_prob"] and 0 <= g["seed"] < 4096
+    # configs[4] gathers no records: rank 0's seeds and the arg-max over both ranks
+    assert d["dump_outputs"]["records"] == 512 and d["dump_outputs"]["records_from"] == "rank 0 + arg-max over all ranks"
+    assert np.load(tmp_path / "d" / "best_seed.npy").tolist() == [float(g["seed"])]
+    assert np.load(tmp_path / "d" / "best_trans_prob.npy").tolist() == [g["trans_prob"]]
 
 
 def test_bench_c5_and_two_launches_in_flight():
     """`--config C5` at N = 1 and `--inflight 2` (alternating contexts) keep the contract and the results."""
     for extra in (["--config", "C5"], ["--inflight", "2"]):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "8",
-                              "--cpu-reps", "1", "--no-single-scan"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                              "--cpu-reps", "1", "--no-single-scan", "--full"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
         assert d["parity"]["max_dpos_m"] <= 1e-4 and d["parity"]["max_dyaw_rad"] <= 1e-4 and d["parity"]["same_iters"]

@@ -11,8 +11,8 @@ TAG=${1:-prof}; shift || true
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="bench.py --no-single-scan --no-cpu-baseline $*"
-python3 bench.py $* > $OUT/bench.log 2> $OUT/bench.err
+B="bench.py --full --no-single-scan --no-cpu-baseline $*"
+python3 bench.py --full $* > $OUT/bench.log 2> $OUT/bench.err
 echo "bench done"; tail -c 300 $OUT/bench.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 $B > $OUT/stats.log 2>&1
 echo "stats done"
@@ -32,10 +32,10 @@ echo "build done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/alone_stats -o run -- python3 tools/prof_single.py 256 12 > $OUT/alone_stats.log 2>&1
 echo "alone done"
 # (iii) configs[4]
-python3 bench.py --config C5 --no-cpu-baseline > $OUT/c5_bench.log 2> $OUT/c5_bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_stats -o run -- python3 bench.py --config C5 --no-cpu-baseline --no-single-scan > $OUT/c5_stats.log 2>&1
-rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_THREAD_CYCLES_VALU --output-format csv -d $OUT/c5_valu -o run -- python3 bench.py --config C5 --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_valu.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c5_fetch -o run -- python3 bench.py --config C5 --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/c5_write -o run -- python3 bench.py --config C5 --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_write.log 2>&1
+python3 bench.py --config C5 --full --no-cpu-baseline > $OUT/c5_bench.log 2> $OUT/c5_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_stats -o run -- python3 bench.py --config C5 --full --no-cpu-baseline --no-single-scan > $OUT/c5_stats.log 2>&1
+rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_THREAD_CYCLES_VALU --output-format csv -d $OUT/c5_valu -o run -- python3 bench.py --config C5 --full --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_valu.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c5_fetch -o run -- python3 bench.py --config C5 --full --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/c5_write -o run -- python3 bench.py --config C5 --full --no-cpu-baseline --no-single-scan --steps 6 > $OUT/c5_write.log 2>&1
 echo "c5 done"
 ls $OUT | head -60
