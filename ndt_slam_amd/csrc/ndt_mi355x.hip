@@ -55,6 +55,80 @@ thread_local std::string g_last_error;
 // host side
 // ==========================================================================================
 
+namespace {
+
+std::set<ndt_ctx *> g_live_ctx;                // contexts that exist (a map may outlive a context that only READ it)
+std::mutex g_live_mu;                          // (contexts may be created / destroyed from different host threads)
+
+int fail(ndt_ctx *ctx, int code, const std::string &msg);
+
+#define HIP_TRY(ctx, expr)                                                                   \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess)                                                                    \
+      return fail((ctx), NDT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+// A device (or pinned host) allocation of T, freed by its owner's destructor: a context or map frees its buffers when it is
+// deleted (after it has drained its streams and made its device current).
+template <typename T, bool Pinned = false>
+struct DevBuf {
+  T *p = nullptr;
+  size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept { release(); std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+  ~DevBuf() { release(); }
+  size_t cap() const { return bytes / sizeof(T); }
+  void release() { if (p) { hipError_t e = Pinned ? hipHostFree(p) : hipFree(p); (void)e; } p = nullptr; bytes = 0; }
+  // exactly `want` bytes; the old allocation is freed first (no two at once)
+  int alloc(ndt_ctx *ctx, size_t want) {
+    release();
+    void *q = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&q, want, hipHostMallocDefault) : hipMalloc(&q, want);
+    if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string(Pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
+    p = static_cast<T *>(q); bytes = want;
+    return NDT_OK;
+  }
+  // at least n elements, grow-only (need + need / 4 + 256 bytes); *grown: a new allocation was made (contents undefined)
+  int ensure(ndt_ctx *ctx, size_t n, bool *grown = nullptr) {
+    const bool grow = !p || n > cap();
+    if (grown) *grown = grow;
+    return grow ? alloc(ctx, n * sizeof(T) + n * sizeof(T) / 4 + 256) : NDT_OK;
+  }
+};
+template <typename T> using PinnedBuf = DevBuf<T, true>;
+
+// Timing events of the last kLen match launches of a context, attached to the dispatches: match kernel start / stop, end of
+// the launch (fitness_reduce_kernel stop).  Launch k of the context is entry k % kLen.
+struct LaunchRing {
+  static constexpr int kLen = 64;
+  hipEvent_t ev[3 * kLen] = {};
+  bool deferred_[kLen] = {};           // NDT_OPT_DEFER_FITNESS: the launch's fitness kernels are on the context's own stream
+  unsigned long long launches = 0;     // launches entered so far (read and written under g_live_mu)
+
+  hipEvent_t *events(unsigned long long k) { return ev + 3 * (k % kLen); }
+  // A launch that has left the ring is covered by the latest one: a context queues its launches in order (its fitness stream
+  // is in order, a launch that leaves the deferred mode waits for the last deferred one, the scratch bracket orders a call
+  // on another stream behind the previous one), so the latest launch's end is reached after every earlier one's.
+  unsigned long long covering(unsigned long long k) const { return launches - 1 - k >= (unsigned long long)kLen ? launches - 1 : k; }
+  hipEvent_t end(unsigned long long k) { return events(covering(k))[2]; }
+  bool deferred(unsigned long long k) const { return deferred_[covering(k) % kLen]; }
+  // the events of the launch `b` launches before the latest (0: the latest); nullptr if it is not in the ring
+  hipEvent_t *back(int b) { return b < 0 || b >= kLen || (unsigned long long)b >= launches ? nullptr : events(launches - 1 - b); }
+  // Enters the next launch of context `self` as the latest one of that context that reads a map (`readers`: ndt_map::readers).
+  // Under g_live_mu: launches and builds on several contexts may come from several host threads.
+  void enter(ndt_ctx *self, std::vector<std::pair<ndt_ctx *, unsigned long long>> &readers, bool deferred) {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    deferred_[launches % kLen] = deferred;
+    auto it = std::find_if(readers.begin(), readers.end(), [&](const auto &r) { return r.first == self; });
+    if (it != readers.end()) it->second = launches; else readers.emplace_back(self, launches);
+    launches++;
+  }
+};
+
+}  // namespace
+
 struct ndt_ctx {
   int device = 0;
   hipStream_t stream = nullptr;       // the stream all work is ordered on
@@ -66,28 +140,22 @@ struct ndt_ctx {
   hipStream_t side = nullptr;                // map build: bounding box + centroid fill beside the bucketing chain
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool map_ms_pending = false;
-  unsigned *h_bounds = nullptr;              // pinned: bounding box read-back of the map build
+  PinnedBuf<unsigned> h_bounds;              // bounding box read-back of the map build
   std::string err;
   float map_ms = 0.f, align_ms = 0.f;
   // grow-only staging for the host-pointer entry points
-  void *d_scan = nullptr; size_t d_scan_cap = 0;
-  void *d_off = nullptr; size_t d_off_cap = 0;
-  void *d_init = nullptr; size_t d_init_cap = 0;
-  void *d_res = nullptr; size_t d_res_cap = 0;
-  void *d_tmp = nullptr; size_t d_tmp_cap = 0;
-  void *d_trace = nullptr; size_t d_trace_cap = 0;
-  void *d_rows = nullptr; size_t d_rows_cap = 0;
-  void *d_sorted = nullptr; size_t d_sorted_cap = 0;   // cell-ordered copy of the scans
-  void *d_sorted_x[2] = {nullptr, nullptr}; size_t d_sorted_x_cap[2] = {0, 0};   // NDT_OPT_DEFER_FITNESS: the copies of the launches in between (the last ones' are still read by their fitness kernels)
-  void *d_fit = nullptr; size_t d_fit_cap = 0;         // squared distance to the nearest map point, per scan point (shared_scan launches)
-  void *d_fit_part = nullptr; size_t d_fit_part_cap = 0;   // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
-  void *d_far = nullptr; size_t d_far_cap = 0;         // deferred far phase of the fitness search: per match two counts, then the lists
-  void *d_ws = nullptr; size_t d_ws_cap = 0;           // WsHeader + ScanCtl[B] + chunk totals
-  void *d_ws_x[2] = {nullptr, nullptr}; size_t d_ws_x_cap[2] = {0, 0};       // NDT_OPT_DEFER_FITNESS: the control words of the launches in between
-  void *d_pf = nullptr; size_t d_pf_cap = 0;           // pre-filter: filtered points at the raw offsets + counts
-  void *d_rn = nullptr; size_t d_rn_cap = 0;           // neighbour removal: block offsets + keep flags
-  void *d_mm = nullptr; size_t d_mm_cap = 0;           // local-map assembly: jobs, pieces, voxel sets, lists
-  void *h_mm = nullptr; size_t h_mm_cap = 0;           // pinned staging of the job table
+  DevBuf<unsigned char> d_scan, d_tmp;
+  DevBuf<uint64_t> d_off;
+  DevBuf<double> d_init, d_trace;
+  DevBuf<ndt_result> d_res;
+  DevBuf<int> d_rows;
+  DevBuf<float> d_fit;                                 // squared distance to the nearest map point, per scan point (shared_scan launches)
+  DevBuf<FitPart> d_fit_part;                          // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
+  DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
+  DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
+  DevBuf<unsigned char> d_rn;                          // neighbour removal: block offsets + keep flags
+  DevBuf<unsigned char> d_mm;                          // local-map assembly: jobs, pieces, voxel sets, lists
+  PinnedBuf<unsigned char> h_mm;                       // staging of the job table
   hipEvent_t ev_mm = nullptr; bool mm_pending = false; // job table upload of the previous call
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
@@ -97,9 +165,9 @@ struct ndt_ctx {
   // belong to no scratch bracket: set s is written by the prepare call for batch i + 1 while the launch of batch i, which reads
   // the other set, is still running; the prepare call orders itself behind the last launch that read ITS set.
   struct PrepSet {
-    void *sorted = nullptr; size_t sorted_cap = 0;
-    void *recs = nullptr; size_t recs_cap = 0;
-    void *maps = nullptr; size_t maps_cap = 0;
+    DevBuf<float2> sorted;
+    DevBuf<PrepRec> recs;
+    DevBuf<unsigned char> maps;
     hipEvent_t ev0 = nullptr, ready = nullptr;         // around ndt_order_kernel (on its dispatch)
     bool valid = false, timed = false;
     // what the set was prepared for
@@ -113,23 +181,23 @@ struct ndt_ctx {
   // The grow-only scratch above belongs to the context, not to a stream: a call on another stream than the
   // previous one first waits for the previous user (ev_scratch).
   hipEvent_t ev_scratch = nullptr; hipStream_t scratch_stream = nullptr; bool scratch_used = false, scratch_recorded = false;
-  size_t ws_clean = 0;                                 // leading bytes of d_ws known to be zero (cleared by the previous launch's last kernel)
-  size_t ws_clean_x[2] = {0, 0};                       // the same of d_ws_x
-  // ring of timing events of the last kTimeRing match launches: match kernel start / stop, fitness_reduce_kernel stop (attached to the dispatches)
-  static constexpr int kTimeRing = 64;
-  hipEvent_t ev_ring[3 * kTimeRing] = {};
+  // A match launch's WsHeader + ScanCtl[B] + chunk totals + bitmaps (ws), cell-ordered copy of the scans (sorted) and leading
+  // bytes of ws known to be zero (cleared by the previous launch's last kernel).  Set 0 is the one every entry point uses;
+  // NDT_OPT_DEFER_FITNESS launches take turns on all of them (the fitness kernels of the launches in between read theirs).
+  struct LaunchSet { DevBuf<unsigned char> ws; DevBuf<float2> sorted; size_t ws_clean = 0; };
+  static constexpr int kDeferSets = 2;                 // launches whose fitness kernels may be outstanding behind a new launch's match kernel, + 1
+  LaunchSet sets[kDeferSets];
+  LaunchRing ring;
   // NDT_OPT_DEFER_FITNESS: the fitness kernels of ndt_align_batch_dev on a stream of the context's own, beside whatever the
   // caller's stream runs next (the next launch's match kernel: its idle workgroups' CUs)
   int defer_fitness = 0;
   hipStream_t fit_stream = nullptr;
-  bool ring_deferred[kTimeRing] = {};                  // per launch of the ring
   struct FitJob {                                      // the fitness kernels of one launch: what queue_fitness needs
     MapView V; const float *scans = nullptr; const unsigned long long *offsets = nullptr; int B = 0, shared_scan = 0;
     size_t total_points = 0; float2 *sorted = nullptr; ndt_result *out = nullptr; unsigned char *ws = nullptr;
-    size_t zero_bytes = 0, far_cnt_bytes = 0; bool sse = false; unsigned slot = 0;
+    size_t zero_bytes = 0, far_cnt_bytes = 0; bool sse = false; hipEvent_t end = nullptr;
   };
   bool deferred_pending = false;                       // the last launch's fitness kernels may still be running beside the caller's stream
-  unsigned long long launches = 0;
 };
 
 struct ndt_map {
@@ -140,33 +208,30 @@ struct ndt_map {
   MapView view;
   size_t n = 0, ng = 0, npad = 0;
   // device buffers (grow-only across rebuilds)
-  int *count = nullptr, *start = nullptr, *npts_grid = nullptr;
-  size_t count_cap = 0, start_cap = 0, npts_cap = 0;
-  unsigned long long *scan_state = nullptr; size_t scan_state_cap = 0;   // scan_onepass_kernel: two tagged words per tile
-  unsigned scan_seq = 0;                                                  // tag of the last build's words
-  bool count_clean = false;                   // count[0 .. count_cap) is all zero (a complete build leaves it so: the scatter takes back what the count added)
-  int *perm = nullptr, *perm_sorted = nullptr; float2 *pts = nullptr;
-  size_t perm_cap = 0, perm_sorted_cap = 0, pts_cap = 0;
-  float2 *cent = nullptr; double *rec = nullptr; size_t cent_cap = 0, rec_cap = 0;
-  unsigned *bounds = nullptr; int *counters = nullptr; int *total = nullptr;   // counters: n_cells, n_valid, n_big
-  int *big = nullptr; size_t big_cap = 0;
-  unsigned *occ = nullptr; size_t occ_cap = 0;
-  unsigned long long *tiles = nullptr; size_t tiles_cap = 0;   // MapView::tiles
+  DevBuf<int> count, start, npts_grid;
+  DevBuf<unsigned long long> scan_state;      // scan_onepass_kernel: two tagged words per tile
+  unsigned scan_seq = 0;                      // tag of the last build's words
+  bool count_clean = false;                   // count is all zero (a complete build leaves it so: the scatter takes back what the count added)
+  DevBuf<int> perm;
+  DevBuf<float2> pts, cent;
+  DevBuf<double> rec;
+  DevBuf<unsigned> bounds; DevBuf<int> counters;   // counters: n_cells, n_valid, n_big
+  DevBuf<int> big;
+  DevBuf<unsigned> occ;
+  DevBuf<unsigned long long> tiles;           // MapView::tiles
   bool pending = false, pend_queued = false;  // between ndt_map_rebuild_begin and _end
   const float *pend_xy = nullptr; size_t pend_stride = 0;
   GridDims grid; bool have_grid = false;      // voxel grid of the last build (queued ahead of the next one's bounding box)
-  void *d_xy_stage = nullptr; size_t d_xy_cap = 0;
+  DevBuf<unsigned char> xy_stage;             // ndt_map_build: the host cloud's copy
   // Launches that read this map since its last build_begin, one entry per reading context: (context, number of that launch
-  // in the context's event ring).  A build that has to be queued AGAIN (build_end: the speculative grid was wrong) rewrites
+  // in the context's ring).  A build that has to be queued AGAIN (build_end: the speculative grid was wrong) rewrites
   // the tables those launches read -- on another stream when the caller builds and matches on different contexts -- and
-  // must wait for them first (round 4: a fitness kernel walking bucket offsets that were being rebuilt ran 236 ms).
+  // must wait for them first (round 4: a fitness kernel walking bucket offsets that were being rebuilt ran 236 ms); so must
+  // every build for the deferred ones (build_begin).
   std::vector<std::pair<ndt_ctx *, unsigned long long>> readers;
 };
 
 namespace {
-
-std::set<ndt_ctx *> g_live_ctx;                // contexts that exist (a map may outlive a context that only READ it)
-std::mutex g_live_mu;                          // (contexts may be created / destroyed from different host threads)
 
 int fail(ndt_ctx *ctx, int code, const std::string &msg) {
   g_last_error = msg;
@@ -174,70 +239,44 @@ int fail(ndt_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail((ctx), NDT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-int ensure(ndt_ctx *ctx, void **p, size_t *cap, size_t need) {
-  if (need <= *cap && *p) return NDT_OK;
-  if (*p) { hipError_t e = hipFree(*p); (void)e; *p = nullptr; *cap = 0; }
-  size_t want = need + need / 4 + 256;
-  HIP_TRY(ctx, hipMalloc(p, want));
-  *cap = want;
-  return NDT_OK;
-}
-
-template <typename T>
-int ensure_t(ndt_ctx *ctx, T **p, size_t *cap_elems, size_t need_elems) {
-  size_t cap_bytes = *cap_elems * sizeof(T);
-  void *vp = *p;
-  int rc = ensure(ctx, &vp, &cap_bytes, need_elems * sizeof(T));
-  *p = static_cast<T *>(vp);
-  *cap_elems = cap_bytes / sizeof(T);
-  return rc;
-}
-
-// Scratch hand-over between streams (see ndt_ctx): call before the first and after the last use in an entry point.
+// The scratch bracket (ndt_ctx::ev_scratch): every entry point that uses the context's scratch opens it before the first and
+// closes it after the last use.
 // (An event record is a barrier packet between kernels: a call on the context's own / registered stream -- which lives
 // as long as the registration -- records nothing; the event is recorded on that stream when a call on ANOTHER stream
 // arrives.  A call on a foreign stream records at once: the stream may be gone by the time the next call comes.)
-int scratch_begin(ndt_ctx *ctx, hipStream_t st, bool deferred_launch = false) {
-  // (NDT_OPT_DEFER_FITNESS) whatever uses the context's scratch next waits for the fitness kernels still running on the
-  // context's own stream -- except the next deferred launch, which orders itself (launch_align)
-  if (ctx->deferred_pending && !deferred_launch && ctx->launches > 0) {
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_ring[3 * ((ctx->launches - 1) % ndt_ctx::kTimeRing) + 2], 0));
-    ctx->deferred_pending = false;
-  }
-  if (ctx->scratch_used && st != ctx->scratch_stream) {
-    if (!ctx->scratch_recorded) HIP_TRY(ctx, hipEventRecord(ctx->ev_scratch, ctx->scratch_stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_scratch, 0));
-  }
-  return NDT_OK;
-}
-int scratch_end(ndt_ctx *ctx, hipStream_t st) {
-  ctx->scratch_recorded = false;
-  if (st != ctx->stream) { HIP_TRY(ctx, hipEventRecord(ctx->ev_scratch, st)); ctx->scratch_recorded = true; }
-  ctx->scratch_stream = st; ctx->scratch_used = true;
-  return NDT_OK;
-}
-
-// scratch_end on EVERY way out of an entry point once its bracket is open: an error return behind the first queued kernel or
+// The bracket is closed on EVERY way out of an entry point once it is open: an error return behind the first queued kernel or
 // copy still leaves work on `st` that uses the context's scratch, and a later call on another stream must be ordered behind it
-// (round 5; VERDICT r04: launch_align failing after the match kernel was queued returned without it).  The quiet form keeps the
-// error message of the failure that is being returned.
+// (round 5; VERDICT r04: launch_align failing after the match kernel was queued returned without it).  The quiet form (the
+// destructor) keeps the error message of the failure that is being returned.
 struct ScratchScope {
-  ndt_ctx *ctx; hipStream_t st; bool open;
-  ScratchScope(ndt_ctx *c, hipStream_t s) : ctx(c), st(s), open(true) {}
+  ndt_ctx *ctx; hipStream_t st; bool is_open = false;
+  ScratchScope(ndt_ctx *c, hipStream_t s) : ctx(c), st(s) {}
   ScratchScope(const ScratchScope &) = delete;
   ScratchScope &operator=(const ScratchScope &) = delete;
-  int close() { open = false; return scratch_end(ctx, st); }
+  int open(bool deferred_launch = false) {
+    // (NDT_OPT_DEFER_FITNESS) whatever uses the context's scratch next waits for the fitness kernels still running on the
+    // context's own stream -- except the next deferred launch, which orders itself (launch_align)
+    if (ctx->deferred_pending && !deferred_launch && ctx->ring.launches > 0) {
+      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ring.end(ctx->ring.launches - 1), 0));
+      ctx->deferred_pending = false;
+    }
+    if (ctx->scratch_used && st != ctx->scratch_stream) {
+      if (!ctx->scratch_recorded) HIP_TRY(ctx, hipEventRecord(ctx->ev_scratch, ctx->scratch_stream));
+      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_scratch, 0));
+    }
+    is_open = true;
+    return NDT_OK;
+  }
+  int close() {
+    is_open = false; ctx->scratch_recorded = false;
+    if (st != ctx->stream) { HIP_TRY(ctx, hipEventRecord(ctx->ev_scratch, st)); ctx->scratch_recorded = true; }
+    ctx->scratch_stream = st; ctx->scratch_used = true;
+    return NDT_OK;
+  }
   ~ScratchScope() {
-    if (!open) return;
+    if (!is_open) return;
     const std::string keep = ctx->err, keep_tl = g_last_error;
-    (void)scratch_end(ctx, st);
+    (void)close();
     ctx->err = keep; g_last_error = keep_tl;
   }
 };
@@ -288,9 +327,8 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   const int B = J.B, shared_scan = J.shared_scan; const size_t total_points = J.total_points;
   float2 *sorted = J.sorted; ndt_result *out = J.out; unsigned char *ws = J.ws;
   const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes; const bool sse = J.sse;
-  hipEvent_t *evr = ctx->ev_ring + 3 * J.slot;
-  float *fit = (float *)ctx->d_fit;
-  FitPart *parts = (FitPart *)ctx->d_fit_part;
+  float *fit = ctx->d_fit.p;
+  FitPart *parts = ctx->d_fit_part.p;
   {
     const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
     const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
@@ -300,13 +338,13 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
       // hypothesis scoring: most seeds end far from the map -- the far phase of the search as a pass of its own over the
       // queries that need it (ndt_fitness.hip.h)
       const size_t cnt_bytes = far_cnt_bytes;
-      unsigned *far_n = (unsigned *)ctx->d_far, *far_idx = (unsigned *)((unsigned char *)ctx->d_far + cnt_bytes);
+      unsigned *far_n = (unsigned *)ctx->d_far.p, *far_idx = (unsigned *)(ctx->d_far.p + cnt_bytes);
       { hipError_t e = hipMemsetAsync(far_n, 0, cnt_bytes, fs); if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("queue_fitness: hipMemsetAsync: ") + hipGetErrorString(e)); }
       if (sse) fitness_points_kernel<true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
       else     fitness_points_kernel<false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
       if (sse) fitness_far_kernel<true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
       else     fitness_far_kernel<false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
-      hipExtLaunchKernelGGL(fitness_reduce_kernel<true>, dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, evr[2], 0,
+      hipExtLaunchKernelGGL(fitness_reduce_kernel<true>, dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
                             offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16));
     } else {
       // scans of their own: the search kernel leaves a {sum, count} per chunk of 64 points instead of a distance per point
@@ -315,7 +353,7 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
       // (a wave per match; at least as many workgroups as clear the control words with one store per thread, a CU each at most)
       const size_t close_wgs = std::max<size_t>(((size_t)B + kFitBlock / 64 - 1) / (kFitBlock / 64),
                                                 std::min<size_t>((size_t)ctx->num_cus, (zero_bytes / 16 + kFitBlock - 1) / kFitBlock));
-      hipExtLaunchKernelGGL(fitness_reduce_kernel<false>, dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, evr[2], 0,
+      hipExtLaunchKernelGGL(fitness_reduce_kernel<false>, dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
                             offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16));
     }
   }
@@ -324,62 +362,50 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   return NDT_OK;
 }
 
-#ifndef NDT_DEFER_SETS
-#define NDT_DEFER_SETS 2
-#endif
-constexpr int kDeferSets = NDT_DEFER_SETS;      // NDT_OPT_DEFER_FITNESS: launches whose fitness kernels may be outstanding behind a new launch's match kernel, + 1
-static_assert(kDeferSets >= 2 && kDeferSets <= 3, "two spare sets of control words and ordered copies");
 int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scans,
                  const unsigned long long *offsets, int B, int shared_scan, size_t total_points, const double *inits,
                  ndt_result *out, double *trace, int trace_cap, int *trace_rows, unsigned long long *prof,
                  ndt_ctx::PrepSet *pset = nullptr, bool defer = false) {
   const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
-  // NDT_OPT_DEFER_FITNESS: launches take turns on two sets of control words and ordered copies -- the fitness kernels of
-  // launch i (the context's own stream) read set i & 1 while the match kernel of launch i + 1 (the caller's stream) fills the other
-  const int set = defer ? (int)(ctx->launches % (unsigned long long)kDeferSets) : 0;      // (0: the buffers every other entry point uses)
-  void **p_ws = set ? &ctx->d_ws_x[set - 1] : &ctx->d_ws; size_t *p_ws_cap = set ? &ctx->d_ws_x_cap[set - 1] : &ctx->d_ws_cap;
-  size_t *p_clean = set ? &ctx->ws_clean_x[set - 1] : &ctx->ws_clean;
-  void **p_sorted = set ? &ctx->d_sorted_x[set - 1] : &ctx->d_sorted; size_t *p_sorted_cap = set ? &ctx->d_sorted_x_cap[set - 1] : &ctx->d_sorted_cap;
-  {
-    const unsigned long long L = ctx->launches;
-    auto end_of = [&](unsigned long long k) { return ctx->ev_ring[3 * (k % ndt_ctx::kTimeRing) + 2]; };
-    // leaving the deferred mode: behind the last launch's fitness kernels; in it: behind those of the launch before last (whose
-    // control words, ordered copies -- and, the caller alternating two of them, result records -- this launch takes over)
-    if (!defer && L >= 1 && ctx->ring_deferred[(L - 1) % ndt_ctx::kTimeRing]) HIP_TRY(ctx, hipStreamWaitEvent(st, end_of(L - 1), 0));   // (the fitness stream is in order: the last launch's end is everybody's)
-    if (defer && L >= (unsigned long long)kDeferSets && ctx->ring_deferred[(L - kDeferSets) % ndt_ctx::kTimeRing]) HIP_TRY(ctx, hipStreamWaitEvent(st, end_of(L - kDeferSets), 0));
-    // (the caller's priority class: below it these kernels starve behind every match kernel -- 0.49 against 0.37 ms per bench step)
-    if (defer && !ctx->fit_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->fit_stream, hipStreamNonBlocking));
-  }
+  LaunchRing &R = ctx->ring;
+  const unsigned long long L = R.launches;
+  // NDT_OPT_DEFER_FITNESS: launches take turns on the sets -- the fitness kernels of launch i (the context's own stream) read
+  // set i & 1 while the match kernel of launch i + 1 (the caller's stream) fills the other
+  ndt_ctx::LaunchSet &set = ctx->sets[defer ? L % ndt_ctx::kDeferSets : 0];
+  // leaving the deferred mode: behind the last launch's fitness kernels; in it: behind those of the launch before last (whose
+  // control words, ordered copies -- and, the caller alternating two of them, result records -- this launch takes over)
+  if (!defer && L >= 1 && R.deferred(L - 1)) HIP_TRY(ctx, hipStreamWaitEvent(st, R.end(L - 1), 0));   // (the fitness stream is in order: the last launch's end is everybody's)
+  if (defer && L >= (unsigned long long)ndt_ctx::kDeferSets && R.deferred(L - ndt_ctx::kDeferSets)) HIP_TRY(ctx, hipStreamWaitEvent(st, R.end(L - ndt_ctx::kDeferSets), 0));
+  // (the caller's priority class: below it these kernels starve behind every match kernel -- 0.49 against 0.37 ms per bench step)
+  if (defer && !ctx->fit_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->fit_stream, hipStreamNonBlocking));
   const MapView &V = map->view;
   const OptParams O = opt_of(map->prm);
   // workspace: header + one control line per scan (zeroed every launch) + chunk totals
   // control words, epoch-tagged pose halves and unit totals (zero at kernel start), then the marked-cell bitmaps
   const size_t zero_bytes = sizeof(WsHeader) + (size_t)B * sizeof(ScanCtl) + (size_t)B * kUnits * kUnitWords * sizeof(u64);
   const size_t ws_bytes = zero_bytes + (size_t)B * (kRegionCells / 8);
-  const size_t ws_cap_before = *p_ws_cap;
-  int rc = ensure(ctx, p_ws, p_ws_cap, ws_bytes);
+  bool grown = false;
+  int rc = set.ws.ensure(ctx, ws_bytes, &grown);
   if (rc) return rc;
-  if (*p_ws_cap != ws_cap_before) *p_clean = 0;                // a new allocation
+  if (grown) set.ws_clean = 0;
   // ordered copy of every scan (what the passes and the fitness kernel read) and one float per point for the
   // fitness score; when every match uses scan 0 each match has its own slot of the scan's size
   const size_t slots = (shared_scan ? (size_t)B : (size_t)1) * total_points;
-  if ((rc = ensure(ctx, p_sorted, p_sorted_cap, slots * sizeof(float2) + 16))) return rc;
-  if (shared_scan && (rc = ensure(ctx, &ctx->d_fit, &ctx->d_fit_cap, slots * sizeof(float) + 16))) return rc;   // (scans of their own: chunk sums only, d_fit_part)
-  float2 *sorted = pset ? (float2 *)pset->sorted : (float2 *)*p_sorted;      // (a prepared batch: its ordered copies are in its own set)
-  const PrepRec *prep = pset ? (const PrepRec *)pset->recs : nullptr;
-  const unsigned *prep_map = pset ? (const unsigned *)pset->maps : nullptr;
-  float *fit = (float *)ctx->d_fit;
+  if ((rc = set.sorted.ensure(ctx, slots + 2))) return rc;
+  if (shared_scan && (rc = ctx->d_fit.ensure(ctx, slots + 4))) return rc;   // (scans of their own: chunk sums only, d_fit_part)
+  float2 *sorted = pset ? pset->sorted.p : set.sorted.p;      // (a prepared batch: its ordered copies are in its own set)
+  const PrepRec *prep = pset ? pset->recs.p : nullptr;
+  const unsigned *prep_map = pset ? (const unsigned *)pset->maps.p : nullptr;
   // (every allocation of the launch in front of its first kernel: nothing below can fail for want of memory once work is queued)
   const size_t far_cnt_bytes = ((size_t)B * 2 * sizeof(unsigned) + 15) & ~(size_t)15;
-  if (shared_scan && (rc = ensure(ctx, &ctx->d_far, &ctx->d_far_cap, far_cnt_bytes + slots * sizeof(unsigned) + 16))) return rc;
+  if (shared_scan && (rc = ctx->d_far.ensure(ctx, far_cnt_bytes + slots * sizeof(unsigned) + 16))) return rc;
   // the chunk sums of the fitness kernels (FitPart, a chunk = 64 points; a match's chunks start at fit_part_of)
-  if ((rc = ensure(ctx, &ctx->d_fit_part, &ctx->d_fit_part_cap, (slots / 64 + (size_t)B + 1) * sizeof(FitPart)))) return rc;
-  FitPart *parts = (FitPart *)ctx->d_fit_part;
+  if ((rc = ctx->d_fit_part.ensure(ctx, slots / 64 + (size_t)B + 1))) return rc;
   // control words: zero before every launch -- by the last kernel of the previous launch of this context
   // (fitness_reduce_kernel), or by a memset when that did not cover enough
-  if (*p_clean < zero_bytes) HIP_TRY(ctx, hipMemsetAsync(*p_ws, 0, zero_bytes, st));
-  *p_clean = 0;
-  unsigned char *ws = (unsigned char *)*p_ws;
+  if (set.ws_clean < zero_bytes) HIP_TRY(ctx, hipMemsetAsync(set.ws.p, 0, zero_bytes, st));
+  set.ws_clean = 0;
+  unsigned char *ws = set.ws.p;
   // helper limit: 8 while a launch has fewer scans than workgroups (one scan at a time: everybody helps), 2 for whole-GPU
   // batches -- there the match kernel is as fast with 2 as with 15, and workgroups that find nothing to join leave their
   // CUs to the next step's map build earlier (round 4, after the repeated line-search passes went: LOG R4.9)
@@ -389,10 +415,9 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const int grid = helpers ? ncu : (B < ncu ? B : ncu);
   // timing: the events ride on the kernels' own dispatch packets (hipExtLaunchKernelGGL: start / stop of that kernel) -- an
   // event RECORD is a packet of its own between two kernels, three of them per launch cost the stream 6-10 us
-  hipEvent_t *evr = ctx->ev_ring + 3 * (ctx->launches % ndt_ctx::kTimeRing);
+  hipEvent_t *evr = R.events(L);
   // (the pair check left out where it cannot fire -- accumulate_pair -- in the preset's own instantiation only)
   const bool chk = !(V.e_hi > 1.0 + 1e-6);
-  ctx->ring_deferred[ctx->launches % ndt_ctx::kTimeRing] = defer;
 #define NDT_LAUNCH(S_, I_, C_)                                                                                          \
   hipExtLaunchKernelGGL((ndt_align_kernel<S_, I_, C_>), dim3(grid), dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, \
                         offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, prep, prep_map)
@@ -404,18 +429,11 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
 #undef NDT_LAUNCH
   // From here on a kernel that reads the map and the context's scratch is queued: whatever happens below, the launch is
   // entered in the context's ring (its last event recorded) and in the map's list of readers, so that a later call on another
-  // stream and a re-queued build of this map are ordered behind it.
+  // stream and a build of this map that must wait for it (re-queued, or behind a deferred launch) are ordered behind it.
   auto entered = [&](int code) {
     if (code != NDT_OK) { hipError_t e = hipEventRecord(evr[2], st); (void)e; }      // (the dispatch that would have carried it was not made)
-    {                                         // this launch reads the map: a re-queued build must wait for it (ndt_map::readers)
-      auto &rd = const_cast<ndt_map *>(map)->readers;
-      std::lock_guard<std::mutex> lk(g_live_mu);           // (launches on several contexts may come from several host threads)
-      bool found = false;
-      for (auto &r : rd) if (r.first == ctx) { r.second = ctx->launches; found = true; }
-      if (!found) rd.emplace_back(ctx, ctx->launches);
-      if (pset) pset->reader = (long long)ctx->launches;
-      ctx->launches++;
-    }
+    R.enter(ctx, const_cast<ndt_map *>(map)->readers, defer);   // this launch reads the map: a build must wait for it (ndt_map::readers)
+    if (pset) pset->reader = (long long)L;
     return code;
   };
   if (ctx->inject_fault > 0 && --ctx->inject_fault == 0)      // NDT_OPT_INJECT_FAULT (tests): fail with the match kernel queued
@@ -429,19 +447,13 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
     hipError_t e = hipStreamWaitEvent(fs, evr[1], 0);
     if (e != hipSuccess) return entered(fail(ctx, NDT_E_HIP, std::string("launch_align: hipStreamWaitEvent: ") + hipGetErrorString(e)));
   }
-  {
-    ndt_ctx::FitJob J;
-    J.V = V; J.scans = scans; J.offsets = offsets; J.B = B; J.shared_scan = shared_scan; J.total_points = total_points;
-    J.sorted = sorted; J.out = out; J.ws = ws; J.zero_bytes = zero_bytes; J.far_cnt_bytes = far_cnt_bytes; J.sse = sse;
-    J.slot = (unsigned)(ctx->launches % ndt_ctx::kTimeRing);
-    int qrc = queue_fitness(ctx, J, fs);
-    if (qrc != NDT_OK) return entered(qrc);
-  }
+  const int qrc = queue_fitness(ctx, {V, scans, offsets, B, shared_scan, total_points, sorted, out, ws, zero_bytes, far_cnt_bytes, sse, evr[2]}, fs);
+  if (qrc != NDT_OK) return entered(qrc);
   {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return entered(fail(ctx, NDT_E_HIP, std::string("launch_align: ") + hipGetErrorString(e)));
   }
-  *p_clean = zero_bytes;
+  set.ws_clean = zero_bytes;
   if (defer) ctx->deferred_pending = true;
   return entered(NDT_OK);
 }
@@ -511,8 +523,8 @@ static int ctx_init(ndt_ctx *c, int device) {
   HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mm, hipEventDisableTiming));
   HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scratch, hipEventDisableTiming));
-  for (hipEvent_t &e : c->ev_ring) HIP_TRY(c, hipEventCreate(&e));
-  HIP_TRY(c, hipHostMalloc((void **)&c->h_bounds, 64, hipHostMallocDefault));
+  for (hipEvent_t &e : c->ring.ev) HIP_TRY(c, hipEventCreate(&e));
+  { int rc = c->h_bounds.alloc(c, 64); if (rc) return rc; }
   { int rc = upload_exp_table(c); if (rc) return rc; }
   hipDeviceProp_t prop;
   HIP_TRY(c, hipGetDeviceProperties(&prop, device));
@@ -572,23 +584,16 @@ int ndt_ctx_destroy(ndt_ctx *c) {
   if (c->side) { e = hipStreamSynchronize(c->side); e = hipStreamDestroy(c->side); }
   if (c->ev_fork) e = hipEventDestroy(c->ev_fork);
   if (c->ev_join) e = hipEventDestroy(c->ev_join);
-  if (c->h_bounds) e = hipHostFree(c->h_bounds);
   if (c->ev_mm) e = hipEventDestroy(c->ev_mm);
   if (c->ev_scratch) e = hipEventDestroy(c->ev_scratch);
-  for (hipEvent_t r : c->ev_ring) if (r) e = hipEventDestroy(r);
+  for (hipEvent_t r : c->ring.ev) if (r) e = hipEventDestroy(r);
   for (ndt_ctx::PrepSet &S : c->prep) {
     if (S.ready && S.scans) e = hipEventSynchronize(S.ready);      // (its kernel may have been queued on another stream than the context's)
     if (S.ev0) e = hipEventDestroy(S.ev0);
     if (S.ready) e = hipEventDestroy(S.ready);
-    if (S.sorted) e = hipFree(S.sorted);
-    if (S.recs) e = hipFree(S.recs);
-    if (S.maps) e = hipFree(S.maps);
   }
-  if (c->h_mm) e = hipHostFree(c->h_mm);
-  void *bufs[] = {c->d_scan, c->d_off, c->d_init, c->d_res, c->d_tmp, c->d_trace, c->d_rows, c->d_sorted, c->d_sorted_x[0], c->d_sorted_x[1], c->d_ws_x[0], c->d_ws_x[1], c->d_fit, c->d_far, c->d_fit_part, c->d_ws, c->d_pf, c->d_rn, c->d_mm};
-  for (void *b : bufs) if (b) e = hipFree(b);
   (void)e;
-  delete c;
+  delete c;                                     // (its buffers: on this device, after the work above has drained)
   return NDT_OK;
 }
 
@@ -619,9 +624,8 @@ int ndt_last_timing(const ndt_ctx *cc, float *map_ms, float *align_ms) {
 }
 
 int ndt_kernel_timing(ndt_ctx *c, int back, float *match_ms, float *fitness_ms) {
-  if (!c || back < 0 || back >= ndt_ctx::kTimeRing || (unsigned long long)back >= c->launches)
-    return fail(c, NDT_E_ARG, "ndt_kernel_timing: no such launch in the ring");
-  hipEvent_t *evr = c->ev_ring + 3 * ((c->launches - 1 - (unsigned long long)back) % ndt_ctx::kTimeRing);
+  hipEvent_t *evr = c ? c->ring.back(back) : nullptr;
+  if (!evr) return fail(c, NDT_E_ARG, "ndt_kernel_timing: no such launch in the ring");
   HIP_TRY(c, hipEventSynchronize(evr[2]));
   float a = 0.f, f = 0.f;
   HIP_TRY(c, hipEventElapsedTime(&a, evr[0], evr[1]));
@@ -632,20 +636,17 @@ int ndt_kernel_timing(ndt_ctx *c, int back, float *match_ms, float *fitness_ms) 
 }
 
 int ndt_launch_interval(ndt_ctx *c, int back, float *interval_ms) {
-  if (!c || !interval_ms || back < 0 || back + 1 >= ndt_ctx::kTimeRing || (unsigned long long)(back + 1) >= c->launches)
-    return fail(c, NDT_E_ARG, "ndt_launch_interval: no such pair of launches in the ring");
-  hipEvent_t *e1 = c->ev_ring + 3 * ((c->launches - 1 - (unsigned long long)back) % ndt_ctx::kTimeRing);
-  hipEvent_t *e0 = c->ev_ring + 3 * ((c->launches - 2 - (unsigned long long)back) % ndt_ctx::kTimeRing);
+  hipEvent_t *e1 = c && interval_ms ? c->ring.back(back) : nullptr, *e0 = e1 ? c->ring.back(back + 1) : nullptr;
+  if (!e0) return fail(c, NDT_E_ARG, "ndt_launch_interval: no such pair of launches in the ring");
   HIP_TRY(c, hipEventSynchronize(e1[0]));
   HIP_TRY(c, hipEventElapsedTime(interval_ms, e0[0], e1[0]));
   return NDT_OK;
 }
 
 int ndt_ctx_wait_launch(ndt_ctx *c, int back, void *stream) {
-  if (!c || back < 0 || back >= ndt_ctx::kTimeRing || (unsigned long long)back >= c->launches)
-    return fail(c, NDT_E_ARG, "ndt_ctx_wait_launch: no such launch in the ring");
+  hipEvent_t *evr = c ? c->ring.back(back) : nullptr;
+  if (!evr) return fail(c, NDT_E_ARG, "ndt_ctx_wait_launch: no such launch in the ring");
   HIP_TRY(c, hipSetDevice(c->device));
-  hipEvent_t *evr = c->ev_ring + 3 * ((c->launches - 1 - (unsigned long long)back) % ndt_ctx::kTimeRing);
   HIP_TRY(c, hipStreamWaitEvent(stream ? (hipStream_t)stream : c->stream, evr[2], 0));
   return NDT_OK;
 }
@@ -659,11 +660,8 @@ int ndt_map_destroy(ndt_map *m) {
   }
   e = hipStreamSynchronize(m->ctx->stream);
   if (m->ctx->side) e = hipStreamSynchronize(m->ctx->side);
-  void *bufs[] = {m->occ, m->tiles, m->big, m->count, m->start, m->scan_state, m->npts_grid, m->perm, m->perm_sorted, m->pts,
-                  m->cent, m->rec, m->bounds, m->counters, m->total, m->d_xy_stage};
-  for (void *b : bufs) if (b) e = hipFree(b);
   (void)e;
-  delete m;
+  delete m;                                     // (its buffers: on this device, after the work above has drained)
   return NDT_OK;
 }
 
@@ -680,30 +678,28 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
 
   // 2. buffers (grow-only across rebuilds)
   {
-    int rc;
+    int rc; bool grown = false;
     const size_t ntiles_ = (ng + kScanTile - 1) / kScanTile;
-    const size_t count_cap_before = m->count_cap;
-    if ((rc = ensure_t(ctx, &m->count, &m->count_cap, ng + 1))) return rc;
-    if (m->count_cap != count_cap_before) m->count_clean = false;      // a new allocation
-    if ((rc = ensure_t(ctx, &m->start, &m->start_cap, ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
-    if ((rc = ensure_t(ctx, &m->npts_grid, &m->npts_cap, ng + 1))) return rc;
-    const size_t state_cap_before = m->scan_state_cap;
-    if ((rc = ensure_t(ctx, &m->scan_state, &m->scan_state_cap, 2 * ntiles_ + 2))) return rc;
-    if (m->scan_state_cap != state_cap_before)      // a new allocation: no word may carry a tag by accident
-      HIP_TRY(ctx, hipMemsetAsync(m->scan_state, 0, m->scan_state_cap * sizeof(unsigned long long), st));
-    if ((rc = ensure_t(ctx, &m->perm, &m->perm_cap, n + 4))) return rc;       // + 4: map_order_kernel reads four numbers at a time
-    if ((rc = ensure_t(ctx, &m->big, &m->big_cap, n / kBigVoxel + 1))) return rc;   // voxels with > kBigVoxel points
-    if ((rc = ensure_t(ctx, &m->occ, &m->occ_cap, (ng + 31) / 32 + 2))) return rc;
-    if ((rc = ensure_t(ctx, &m->tiles, &m->tiles_cap, ntile8))) return rc;
-    if ((rc = ensure_t(ctx, &m->pts, &m->pts_cap, n))) return rc;
-    if ((rc = ensure_t(ctx, &m->cent, &m->cent_cap, npad))) return rc;
-    if ((rc = ensure_t(ctx, &m->rec, &m->rec_cap, npad * 8))) return rc;
+    if ((rc = m->count.ensure(ctx, ng + 1, &grown))) return rc;
+    if (grown) m->count_clean = false;
+    if ((rc = m->start.ensure(ctx, ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
+    if ((rc = m->npts_grid.ensure(ctx, ng + 1))) return rc;
+    if ((rc = m->scan_state.ensure(ctx, 2 * ntiles_ + 2, &grown))) return rc;
+    if (grown)      // no word may carry a tag by accident
+      HIP_TRY(ctx, hipMemsetAsync(m->scan_state.p, 0, m->scan_state.cap() * sizeof(unsigned long long), st));
+    if ((rc = m->perm.ensure(ctx, n + 4))) return rc;       // + 4: map_order_kernel reads four numbers at a time
+    if ((rc = m->big.ensure(ctx, n / kBigVoxel + 1))) return rc;   // voxels with > kBigVoxel points
+    if ((rc = m->occ.ensure(ctx, (ng + 31) / 32 + 2))) return rc;
+    if ((rc = m->tiles.ensure(ctx, ntile8))) return rc;
+    if ((rc = m->pts.ensure(ctx, n))) return rc;
+    if ((rc = m->cent.ensure(ctx, npad))) return rc;
+    if ((rc = m->rec.ensure(ctx, npad * 8))) return rc;
   }
   // No clearing in the steady state (every memset is a kernel of its own between the build's kernels): the per-voxel
   // counters are zero again after a complete build (map_scatter_kernel takes back what map_count_kernel added), the
   // four small counters are cleared by map_count_kernel, the scan's words carry the build's tag, the readable ints in
   // front of `start` are written by scan_onepass_kernel.
-  if (!m->count_clean) HIP_TRY(ctx, hipMemsetAsync(m->count, 0, m->count_cap * sizeof(int), st));
+  if (!m->count_clean) HIP_TRY(ctx, hipMemsetAsync(m->count.p, 0, m->count.cap() * sizeof(int), st));
   m->count_clean = false;
   // (records of voxels outside the search set are never read: no clearing of m->rec)
   // (the centroid grid is reset on the side stream, beside the bucketing chain; joined in front of the statistics)
@@ -715,23 +711,23 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   }
-  fill_f2_kernel<<<grid_for(npad, 256), 256, 0, ctx->side>>>(m->cent, npad, INFINITY, m->tiles, ntile8);
+  fill_f2_kernel<<<grid_for(npad, 256), 256, 0, ctx->side>>>(m->cent.p, npad, INFINITY, m->tiles.p, ntile8);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->side));
 
   // 3. bucket the points by voxel, cloud order kept inside a bucket
-  map_count_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, m->count, m->counters);
+  map_count_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, m->count.p, m->counters.p);
   const int ntiles = (int)((ng + kScanTile - 1) / kScanTile);
-  int *const start = m->start + 4;
+  int *const start = m->start.p + 4;
   const int big_cap = (int)(n / kBigVoxel + 1);
   m->scan_seq = (m->scan_seq + 1u) & 0x3fffffffu;
   if (m->scan_seq == 0u) m->scan_seq = 1u;
-  scan_onepass_kernel<<<ntiles, kScanBlock, 0, st>>>(m->count, ng, m->scan_state, m->scan_seq, ntiles, m->counters + 3, start,
-                                                     m->big, m->counters + 2, big_cap);
-  map_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, start, m->count, m->perm);
+  scan_onepass_kernel<<<ntiles, kScanBlock, 0, st>>>(m->count.p, ng, m->scan_state.p, m->scan_seq, ntiles, m->counters.p + 3, start,
+                                                     m->big.p, m->counters.p + 2, big_cap);
+  map_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, start, m->count.p, m->perm.p);
   HIP_TRY(ctx, hipGetLastError());
   m->count_clean = true;
   const unsigned small_blocks = (unsigned)((ng + kOrderVoxPerBlock - 1) / kOrderVoxPerBlock);
-  map_order_kernel<<<small_blocks + kBigBlocks, 256, 0, st>>>(start, ng, small_blocks, m->big, m->counters + 2, big_cap, m->perm, xy, stride, m->pts);
+  map_order_kernel<<<small_blocks + kBigBlocks, 256, 0, st>>>(start, ng, small_blocks, m->big.p, m->counters.p + 2, big_cap, m->perm.p, xy, stride, m->pts.p);
   HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
 
   // 4. per-voxel statistics -> centroid grid + cell records + bucketed raw points
@@ -741,7 +737,7 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   // evm1 -- the end of the build, for ndt_kernel timing and for launches on other streams -- rides on this kernel's own
   // dispatch (an hipEventRecord is a packet of its own: ~6 us between two kernels, tools/launch_gap.py)
   hipExtLaunchKernelGGL(map_finalize_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, nullptr, ctx->evm1, 0, G, L, start,
-                        m->pts, m->cent, m->rec, m->npts_grid, m->counters, m->occ, m->tiles, tiles_w);
+                        m->pts.p, m->cent.p, m->rec.p, m->npts_grid.p, m->counters.p, m->occ.p, m->tiles.p, tiles_w);
   HIP_TRY(ctx, hipGetLastError());
 
   MapView &V = m->view;
@@ -749,11 +745,30 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   V.r2 = (float)((double)prm->resolution * (double)prm->resolution);
   V.radius_inclusive = prm->radius_inclusive; V.transform_sse = prm->transform_sse;
   V.min_bx = G.min_bx; V.min_by = G.min_by; V.div_x = G.div_x; V.div_y = G.div_y; V.gw = G.gw; V.gh = G.gh;
-  V.cent = m->cent; V.rec = m->rec; V.occ = m->occ; V.tiles = m->tiles; V.tiles_w = tiles_w; V.pt_start = start; V.pts = m->pts;
+  V.cent = m->cent.p; V.rec = m->rec.p; V.occ = m->occ.p; V.tiles = m->tiles.p; V.tiles_w = tiles_w; V.pt_start = start; V.pts = m->pts.p;
   gauss_constants(*prm, &V.d1, &V.d2);
   V.e_hi = pair_check_threshold(V.d2);
   m->info.min_bx = G.min_bx; m->info.min_by = G.min_by; m->info.div_x = G.div_x; m->info.div_y = G.div_y;
   m->info.n_points = n;
+  return NDT_OK;
+}
+
+// Makes `st` wait for the ends of the launches that read map m (ndt_map::readers): all, or only the unfinished deferred ones.
+// The alive check, the read of the reader's ring and the wait happen under ONE hold of the registry's mutex: a concurrent
+// ndt_ctx_destroy or launch on another host thread cannot slip in between.  (A launch that has left its ring is waited for
+// through the latest one, LaunchRing::end: skipping it would let the build rewrite tables under a launch still running.)
+static int wait_for_readers(ndt_ctx *ctx, const ndt_map *m, hipStream_t st, bool deferred_only) {
+  std::lock_guard<std::mutex> lk(g_live_mu);
+  for (const auto &r : m->readers) {
+    if (g_live_ctx.count(r.first) == 0 || r.first->ring.launches <= r.second) continue;   // gone (it synchronised on the way out) / never launched
+    LaunchRing &R = r.first->ring;
+    const hipEvent_t end = R.end(r.second);
+    if (deferred_only) {
+      if (!R.deferred(r.second) || hipEventQuery(end) == hipSuccess) continue;            // not deferred / finished: no barrier packet
+      (void)hipGetLastError();                     // (hipErrorNotReady is no failure: not left behind for the build's launch checks)
+    }
+    HIP_TRY(ctx, hipStreamWaitEvent(st, end, 0));
+  }
   return NDT_OK;
 }
 
@@ -766,14 +781,17 @@ static int build_begin(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   hipStream_t st = ctx->stream;
   m->prm = *prm; m->n = n; m->info_valid = false;
   m->pend_xy = xy; m->pend_stride = stride; m->pend_queued = false;
-  { std::lock_guard<std::mutex> lk(g_live_mu); m->readers.clear(); }   // whoever read the previous build is the caller's to wait for (stream order / ndt_ctx_wait_launch)
+  // A launch that read the previous build is the caller's to order before this one (stream order / ndt_ctx_wait_launch), except
+  // for deferred fitness kernels (NDT_OPT_DEFER_FITNESS, their context's own stream): waited for here, ahead of the fork below.
+  { int rc = wait_for_readers(ctx, m, st, /*deferred_only=*/true); if (rc) return rc; }
+  { std::lock_guard<std::mutex> lk(g_live_mu); m->readers.clear(); }
   // The bounding box (and the reset of the centroid grid, queue_build) run on a side stream beside the bucketing
   // chain -- a dozen dependent kernels whose launch latencies add up -- and are joined in front of the statistics.
   // (One record serves as the start of the build's timing and as the fork.)
   HIP_TRY(ctx, hipEventRecord(ctx->evm0, st));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->evm0, 0));
-  map_minmax_kernel<<<grid_for(n, 256 * 32, 128), 256, 0, ctx->side>>>(xy, stride, n, m->bounds, m->bounds + 4);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bounds, m->bounds + 4, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side));
+  map_minmax_kernel<<<grid_for(n, 256 * 32, 128), 256, 0, ctx->side>>>(xy, stride, n, m->bounds.p, m->bounds.p + 4);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bounds.p, m->bounds.p + 4, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side));
   HIP_TRY(ctx, hipEventRecord(ctx->evb, ctx->side));
   const float inv_leaf = 1.0f / prm->resolution;
   if (m->have_grid && m->grid.inv_leaf == inv_leaf) {
@@ -792,7 +810,7 @@ static int build_end(ndt_ctx *ctx, ndt_map *m) {
   const ndt_params *prm = &m->prm;
   m->pending = false;
   ctx->pending_map = nullptr;
-  const unsigned *hb = ctx->h_bounds;            // pinned
+  const unsigned *hb = ctx->h_bounds.p;          // pinned
   HIP_TRY(ctx, hipEventSynchronize(ctx->evb));
   if (hb[0] == 0xffffffffu) return fail(ctx, NDT_E_ARG, "ndt_map_build: no finite points");
   const float inv_leaf = 1.0f / prm->resolution;
@@ -825,22 +843,8 @@ static int build_end(ndt_ctx *ctx, ndt_map *m) {
     if (m->pend_queued) {
       // the launches queued since build_begin read the speculative build's tables: the build that replaces them waits
       // for the last of them on every context that issued any (the event on that launch's last kernel)
-      // (alive check, the read of the reader's launch counter and the wait under ONE hold of the registry's mutex: a
-      //  concurrent ndt_ctx_destroy or launch on another host thread cannot slip in between.  A reader whose event ring has
-      //  wrapped since that launch -- 64 or more launches later -- is waited for through its MOST RECENT launch: a context
-      //  queues its launches in order, so the latest event covers the earlier one; skipping it would let this build rewrite
-      //  tables under a launch that may still be running.)
-      {
-        std::lock_guard<std::mutex> lk(g_live_mu);
-        for (auto &r : m->readers) {
-          ndt_ctx *rc_ = r.first;
-          if (g_live_ctx.count(rc_) == 0 || rc_->launches <= r.second) continue;      // gone (it synchronised on the way out) / never launched
-          const bool wrapped = rc_->launches - 1 - r.second >= (unsigned long long)ndt_ctx::kTimeRing;
-          const unsigned long long which = wrapped ? rc_->launches - 1 : r.second;
-          hipEvent_t *evr = rc_->ev_ring + 3 * (which % ndt_ctx::kTimeRing);
-          HIP_TRY(ctx, hipStreamWaitEvent(st, evr[2], 0));
-        }
-      }
+      int rc = wait_for_readers(ctx, m, st, /*deferred_only=*/false);
+      if (rc) return rc;
     }
     int rc = queue_build(ctx, m, m->pend_xy, m->n, m->pend_stride, prm, G, /*requeue=*/m->pend_queued);
     if (rc) return rc;
@@ -873,12 +877,12 @@ int ndt_map_build_dev(ndt_ctx *ctx, const float *xy, size_t n, size_t stride, co
     m = new (std::nothrow) ndt_map();
     if (!m) return NDT_E_NOMEM;
     m->ctx = ctx;
-    hipError_t e = hipMalloc(&m->bounds, 16 * sizeof(unsigned));
     const unsigned init_b[16] = {0xffffffffu, 0xffffffffu, 0u, 0u};     // running bounding box, result, done-counter (map_minmax_kernel)
-    if (e == hipSuccess) e = hipMemcpy(m->bounds, init_b, sizeof(init_b), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&m->counters, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&m->total, sizeof(int));
-    if (e != hipSuccess) { ndt_map_destroy(m); return fail(ctx, NDT_E_HIP, std::string("ndt_map_build: hipMalloc: ") + hipGetErrorString(e)); }
+    int rc = m->bounds.alloc(ctx, sizeof(init_b));
+    const hipError_t e = rc ? hipSuccess : hipMemcpy(m->bounds.p, init_b, sizeof(init_b), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, std::string("ndt_map_build: hipMemcpy: ") + hipGetErrorString(e));
+    if (rc == NDT_OK) rc = m->counters.alloc(ctx, 4 * sizeof(int));
+    if (rc) { ndt_map_destroy(m); return rc; }
   }
   const int rc = map_build_impl(ctx, m, xy, n, stride, prm);
   if (rc) {
@@ -921,15 +925,14 @@ int ndt_map_build(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, c
   if (!xy_host || n == 0 || !pmap || stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, "ndt_map_build: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // stage through a buffer owned by the map once it exists; first build uses a temporary
-  void *stage = nullptr; size_t cap = 0;
-  if (*pmap) { stage = (*pmap)->d_xy_stage; cap = (*pmap)->d_xy_cap; }
-  int rc = ensure(ctx, &stage, &cap, n * stride);
+  DevBuf<unsigned char> stage;
+  if (*pmap) stage = std::move((*pmap)->xy_stage);
+  int rc = stage.ensure(ctx, n * stride);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(stage, xy_host, n * stride, hipMemcpyHostToDevice, ctx->stream));
-  rc = ndt_map_build_dev(ctx, (const float *)stage, n, stride, prm, pmap);
+  HIP_TRY(ctx, hipMemcpyAsync(stage.p, xy_host, n * stride, hipMemcpyHostToDevice, ctx->stream));
+  rc = ndt_map_build_dev(ctx, (const float *)stage.p, n, stride, prm, pmap);
   if (rc == NDT_OK) { hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }   // host-pointer form: synchronous
-  if (*pmap) { (*pmap)->d_xy_stage = stage; (*pmap)->d_xy_cap = cap; }
-  else { hipError_t e = hipFree(stage); (void)e; }
+  if (*pmap) (*pmap)->xy_stage = std::move(stage);
   return rc;
 }
 
@@ -940,7 +943,7 @@ int ndt_map_info_get(const ndt_map *cm, ndt_map_info *out) {
     // per-voxel flags: 0 not in the search set, n accepted, -n rejected covariance
     std::vector<int> flags(m->ng);
     HIP_TRY(m->ctx, hipSetDevice(m->ctx->device));
-    HIP_TRY(m->ctx, hipMemcpyAsync(flags.data(), m->npts_grid, m->ng * sizeof(int), hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(m->ctx, hipMemcpyAsync(flags.data(), m->npts_grid.p, m->ng * sizeof(int), hipMemcpyDeviceToHost, m->ctx->stream));
     HIP_TRY(m->ctx, hipStreamSynchronize(m->ctx->stream));
     int cells = 0, valid = 0;
     for (int f : flags) { cells += f != 0; valid += f > 0; }
@@ -962,9 +965,9 @@ int ndt_map_export(const ndt_map *cm, int *cell_idx, float *cent_xy, double *mea
   float2 *hc = (float2 *)malloc(npad * sizeof(float2));
   double *hr = (double *)malloc(npad * 8 * sizeof(double));
   if (!hn || !hc || !hr) { free(hn); free(hc); free(hr); return NDT_E_NOMEM; }
-  hipError_t e1 = hipMemcpyAsync(hn, m->npts_grid, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e2 = hipMemcpyAsync(hc, m->cent, npad * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e3 = hipMemcpyAsync(hr, m->rec, npad * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e1 = hipMemcpyAsync(hn, m->npts_grid.p, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e2 = hipMemcpyAsync(hc, m->cent.p, npad * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e3 = hipMemcpyAsync(hr, m->rec.p, npad * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   hipError_t e4 = hipStreamSynchronize(ctx->stream);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
     free(hn); free(hc); free(hr);
@@ -1001,28 +1004,25 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   S.valid = false;
   const size_t slots = (shared_scan ? (size_t)B : (size_t)1) * total_points;
   int rc;
-  if ((rc = ensure(ctx, &S.sorted, &S.sorted_cap, slots * sizeof(float2) + 16))) return rc;
-  if ((rc = ensure(ctx, &S.recs, &S.recs_cap, (size_t)B * sizeof(PrepRec)))) return rc;
-  if ((rc = ensure(ctx, &S.maps, &S.maps_cap, (size_t)B * (kRegionCells / 8)))) return rc;
+  if ((rc = S.sorted.ensure(ctx, slots + 2))) return rc;
+  if ((rc = S.recs.ensure(ctx, (size_t)B))) return rc;
+  if ((rc = S.maps.ensure(ctx, (size_t)B * (kRegionCells / 8)))) return rc;
   if (!S.ready) { HIP_TRY(ctx, hipEventCreate(&S.ev0)); HIP_TRY(ctx, hipEventCreate(&S.ready)); }
   // Of the map it takes the grid's geometry (by value, now) and reads nothing on the device: no wait for a build that may be
   // queued or running -- a two-phase rebuild that ends with another grid simply leaves this set unused.  It is ordered behind
   // the last launch that read this set (its fitness kernels walk the set's ordered copies).
-  if (S.reader >= 0 && (unsigned long long)S.reader < ctx->launches) {
-    const bool wrapped = ctx->launches - 1 - (unsigned long long)S.reader >= (unsigned long long)ndt_ctx::kTimeRing;
-    const unsigned long long which = wrapped ? ctx->launches - 1 : (unsigned long long)S.reader;
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_ring[3 * (which % ndt_ctx::kTimeRing) + 2], 0));
-  }
+  if (S.reader >= 0 && (unsigned long long)S.reader < ctx->ring.launches)
+    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ring.end((unsigned long long)S.reader), 0));
   const MapView &V = map->view;
   const OptParams O = opt_of(map->prm);
   const int ncu = ctx->workgroups > 0 ? ctx->workgroups : ctx->num_cus;
   const int grid = B < ncu ? B : ncu;
   if (map->prm.transform_sse)
     hipExtLaunchKernelGGL((ndt_order_kernel<true>), dim3(grid), dim3(kBlock), 0, st, S.ev0, S.ready, 0, V, O, scans,
-                          (const unsigned long long *)offsets, B, shared_scan, inits, (float2 *)S.sorted, (PrepRec *)S.recs, (unsigned *)S.maps);
+                          (const unsigned long long *)offsets, B, shared_scan, inits, S.sorted.p, S.recs.p, (unsigned *)S.maps.p);
   else
     hipExtLaunchKernelGGL((ndt_order_kernel<false>), dim3(grid), dim3(kBlock), 0, st, S.ev0, S.ready, 0, V, O, scans,
-                          (const unsigned long long *)offsets, B, shared_scan, inits, (float2 *)S.sorted, (PrepRec *)S.recs, (unsigned *)S.maps);
+                          (const unsigned long long *)offsets, B, shared_scan, inits, S.sorted.p, S.recs.p, (unsigned *)S.maps.p);
   HIP_TRY(ctx, hipGetLastError());
   S.scans = scans; S.offsets = offsets; S.inits = inits; S.map = map; S.B = B; S.shared_scan = shared_scan; S.total_points = total_points;
   S.min_bx = V.min_bx; S.min_by = V.min_by; S.div_x = V.div_x; S.div_y = V.div_y; S.inv_leaf = V.inv_leaf;
@@ -1059,11 +1059,11 @@ int ndt_align_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans, co
   }
   int rc;
   const bool defer = ctx->defer_fitness != 0;
-  if ((rc = scratch_begin(ctx, st, defer))) return rc;
   ScratchScope scope(ctx, st);
+  if ((rc = scope.open(defer))) return rc;
   if ((rc = launch_align(ctx, map, st, scans, (const unsigned long long *)offsets, B, shared_scan, total_points, inits,
                          out, nullptr, 0, nullptr, nullptr, pset, defer)))
-    return rc;                                     // (scope: scratch_end all the same -- kernels may have been queued)
+    return rc;                                     // (scope: closed all the same -- kernels may have been queued)
   return scope.close();
 }
 
@@ -1136,38 +1136,40 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
     if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch: offsets not monotone");
   int rc;
   if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
-  if ((rc = scratch_begin(ctx, st))) return rc;
-  ScratchScope scope(ctx, st);                     // (every return below goes through scratch_end)
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
   const size_t ntot = (size_t)offsets[nscan];
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, ntot * 8))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_off, &ctx->d_off_cap, (nscan + 1) * 8))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_init, &ctx->d_init_cap, (size_t)B * 24))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_res, &ctx->d_res_cap, (size_t)B * sizeof(ndt_result)))) return rc;
+  if ((rc = ctx->d_scan.ensure(ctx, ntot * 8))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, nscan + 1))) return rc;
+  if ((rc = ctx->d_init.ensure(ctx, (size_t)B * 3))) return rc;
+  if ((rc = ctx->d_res.ensure(ctx, (size_t)B))) return rc;
   double *d_trace = nullptr; int *d_rows = nullptr;
   if (trace && trace_cap > 0 && trace_rows) {
-    if ((rc = ensure(ctx, &ctx->d_trace, &ctx->d_trace_cap, (size_t)B * trace_cap * 64))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_rows, &ctx->d_rows_cap, (size_t)B * 4))) return rc;
-    d_trace = (double *)ctx->d_trace; d_rows = (int *)ctx->d_rows;
+    if ((rc = ctx->d_trace.ensure(ctx, (size_t)B * trace_cap * 8))) return rc;
+    if ((rc = ctx->d_rows.ensure(ctx, (size_t)B))) return rc;
+    d_trace = ctx->d_trace.p; d_rows = ctx->d_rows.p;
     HIP_TRY(ctx, hipMemsetAsync(d_trace, 0, (size_t)B * trace_cap * 64, st));
   }
   if (stride == 8) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan, scans, ntot * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scans, ntot * 8, hipMemcpyHostToDevice, st));
   } else {                                     // e.g. pcl::PointXYZ (16 bytes): strided upload, packed on the device
-    if ((rc = ensure(ctx, &ctx->d_tmp, &ctx->d_tmp_cap, ntot * stride))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp, scans, ntot * stride, hipMemcpyHostToDevice, st));
-    repack_f2_kernel<<<grid_for(ntot, 256), 256, 0, st>>>((const float *)ctx->d_tmp, stride, ntot, (float2 *)ctx->d_scan);
+    if ((rc = ctx->d_tmp.ensure(ctx, ntot * stride))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp.p, scans, ntot * stride, hipMemcpyHostToDevice, st));
+    repack_f2_kernel<<<grid_for(ntot, 256), 256, 0, st>>>((const float *)ctx->d_tmp.p, stride, ntot, (float2 *)ctx->d_scan.p);
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init.p, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
   unsigned long long *d_prof = nullptr;
 #ifdef NDT_DIAG
   const bool want_prof = getenv("NDT_PROF") != nullptr;
   const size_t prof_bytes = (size_t)B * (256 + kProfTimeline * 8);      // phase timers, then the shared-pass timelines
-  if (want_prof) { HIP_TRY(ctx, hipMalloc(&d_prof, prof_bytes)); HIP_TRY(ctx, hipMemsetAsync(d_prof, 0, prof_bytes, st)); }
+  DevBuf<unsigned long long> prof_buf;
+  if (want_prof && (rc = prof_buf.alloc(ctx, prof_bytes))) return rc;
+  if (want_prof) { d_prof = prof_buf.p; HIP_TRY(ctx, hipMemsetAsync(d_prof, 0, prof_bytes, st)); }
 #endif
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  if ((rc = launch_align(ctx, map, st, (const float *)ctx->d_scan, (const unsigned long long *)ctx->d_off, B,
-                         shared_scan, ntot, (const double *)ctx->d_init, (ndt_result *)ctx->d_res, d_trace, trace_cap,
+  if ((rc = launch_align(ctx, map, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B,
+                         shared_scan, ntot, ctx->d_init.p, ctx->d_res.p, d_trace, trace_cap,
                          d_rows, d_prof)))
     return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
@@ -1177,10 +1179,9 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
     HIP_TRY(ctx, hipStreamSynchronize(st));
     HIP_TRY(ctx, hipMemcpy(hp.data(), d_prof, prof_bytes, hipMemcpyDeviceToHost));
     prof_report(hp.data(), B);
-    hipError_t e = hipFree(d_prof); (void)e;
   }
 #endif
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_res, (size_t)B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_res.p, (size_t)B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
   if (d_trace) {
     HIP_TRY(ctx, hipMemcpyAsync(trace, d_trace, (size_t)B * trace_cap * 64, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(trace_rows, d_rows, (size_t)B * 4, hipMemcpyDeviceToHost, st));
@@ -1278,8 +1279,9 @@ int ndt_selftest_libm_f32(ndt_ctx *ctx, const float *yaw, size_t n, float *cos_o
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!yaw || n == 0) return fail(ctx, NDT_E_ARG, "ndt_selftest_libm_f32: bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  float *d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void **)&d, 4 * n * sizeof(float)));
+  DevBuf<float> buf;
+  { int rc = buf.alloc(ctx, 4 * n * sizeof(float)); if (rc) return rc; }
+  float *d = buf.p;
   hipError_t e = hipMemcpyAsync(d, yaw, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     selftest_libm_f32_kernel<<<grid_for(n, 256), 256, 0, ctx->stream>>>(d, n, d + n, d + 2 * n, d + 3 * n);
@@ -1289,7 +1291,6 @@ int ndt_selftest_libm_f32(ndt_ctx *ctx, const float *yaw, size_t n, float *cos_o
   if (e == hipSuccess && sin_out) e = hipMemcpyAsync(sin_out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && init_yaw_out) e = hipMemcpyAsync(init_yaw_out, d + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipError_t e2 = hipFree(d); (void)e2;
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_selftest_libm_f32: ") + hipGetErrorString(e));
   return NDT_OK;
 }
@@ -1310,13 +1311,13 @@ int ndt_eval_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, s
   hipStream_t st = ctx->stream;
   int rc;
   const int grid = grid_for(n, 256, 1024);
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, n * stride))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_tmp, &ctx->d_tmp_cap, (size_t)grid * kAcc * 8))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan, scan, n * stride, hipMemcpyHostToDevice, st));
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
+  if ((rc = ctx->d_tmp.ensure(ctx, (size_t)grid * kAcc * 8))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
   {
     const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
     const MapView &V = map->view; const double sn = map->prm.snap_thresh;
-    const float *ds = (const float *)ctx->d_scan; double *dt = (double *)ctx->d_tmp;
+    const float *ds = (const float *)ctx->d_scan.p; double *dt = (double *)ctx->d_tmp.p;
     if (sse && incl)       ndt_eval_kernel<true, true><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
     else if (sse)          ndt_eval_kernel<true, false><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
     else if (incl)         ndt_eval_kernel<false, true><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
@@ -1325,7 +1326,7 @@ int ndt_eval_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, s
   HIP_TRY(ctx, hipGetLastError());
   double *hp = (double *)malloc((size_t)grid * kAcc * 8);
   if (!hp) return NDT_E_NOMEM;
-  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp, (size_t)grid * kAcc * 8, hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp.p, (size_t)grid * kAcc * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { free(hp); return fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }
   double t[kAcc] = {0};
@@ -1350,16 +1351,16 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n
   hipStream_t st = ctx->stream;
   int rc;
   const int grid = grid_for(n, 256, 1024);
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, n * stride))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_tmp, &ctx->d_tmp_cap, (size_t)grid * 16))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan, scan, n * stride, hipMemcpyHostToDevice, st));
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
+  if ((rc = ctx->d_tmp.ensure(ctx, (size_t)grid * 16))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
   Tf32 T = {c, s, tx, ty};
-  ndt_fitness_kernel<<<grid, 256, 0, st>>>(map->view, (const float *)ctx->d_scan, stride, (int)n, T,
-                                           (double *)ctx->d_tmp);
+  ndt_fitness_kernel<<<grid, 256, 0, st>>>(map->view, (const float *)ctx->d_scan.p, stride, (int)n, T,
+                                           (double *)ctx->d_tmp.p);
   HIP_TRY(ctx, hipGetLastError());
   double *hp = (double *)malloc((size_t)grid * 16);
   if (!hp) return NDT_E_NOMEM;
-  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp, (size_t)grid * 16, hipMemcpyDeviceToHost, st);
+  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp.p, (size_t)grid * 16, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { free(hp); return fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }
   double sum = 0, cnt = 0;
@@ -1378,14 +1379,14 @@ int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy, size_t stride, co
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   int rc;
-  if ((rc = scratch_begin(ctx, st))) return rc;
   ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
   // filtered points at the raw offsets, then the per-scan counts
   const size_t tmp_bytes = total_raw_points * sizeof(float2);
-  if ((rc = ensure(ctx, &ctx->d_pf, &ctx->d_pf_cap, 2 * tmp_bytes + (size_t)B * sizeof(unsigned)))) return rc;
-  float2 *tmp = (float2 *)ctx->d_pf;                                   // dense result at the raw offsets
-  float2 *sparse = (float2 *)((char *)ctx->d_pf + tmp_bytes);          // step-by-step kernel: flushes at the index of their cause
-  unsigned *counts = (unsigned *)((char *)ctx->d_pf + 2 * tmp_bytes);
+  if ((rc = ctx->d_pf.ensure(ctx, 2 * tmp_bytes + (size_t)B * sizeof(unsigned)))) return rc;
+  float2 *tmp = (float2 *)ctx->d_pf.p;                                   // dense result at the raw offsets
+  float2 *sparse = (float2 *)((char *)ctx->d_pf.p + tmp_bytes);          // step-by-step kernel: flushes at the index of their cause
+  unsigned *counts = (unsigned *)((char *)ctx->d_pf.p + 2 * tmp_bytes);
   const int grid = B < 8 * ctx->num_cus ? B : 8 * ctx->num_cus;
   // scans of up to kPfSortMax points: ordered by slot, one thread per slot; longer ones: the step-by-step replay
   prefilter_sorted_kernel<<<grid, kPfSortThreads, 0, st>>>(raw_xy, stride, (const unsigned long long *)raw_offsets, B, leaf,
@@ -1408,11 +1409,11 @@ int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, f
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   int rc;
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, n * stride + n * sizeof(float2)))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_off, &ctx->d_off_cap, 4 * sizeof(uint64_t)))) return rc;
-  float *d_in = (float *)ctx->d_scan;
-  float *d_out = (float *)((char *)ctx->d_scan + n * stride);
-  uint64_t *d_offs = (uint64_t *)ctx->d_off;                  // [0..1] raw, [2..3] filtered
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride + n * sizeof(float2)))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
+  float *d_in = (float *)ctx->d_scan.p;
+  float *d_out = (float *)((char *)ctx->d_scan.p + n * stride);
+  uint64_t *d_offs = ctx->d_off.p;                              // [0..1] raw, [2..3] filtered
   const uint64_t raw[2] = {0, (uint64_t)n};
   HIP_TRY(ctx, hipMemcpyAsync(d_in, xy_host, n * stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_offs, raw, sizeof(raw), hipMemcpyHostToDevice, st));
@@ -1471,11 +1472,11 @@ int ndt_remove_neighbors_dev(ndt_ctx *ctx, const float *base_xy, size_t base_str
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   const int nblocks = (int)((n_base + kRnBlock - 1) / kRnBlock);
   int rc;
-  if ((rc = scratch_begin(ctx, st))) return rc;
   ScratchScope scope(ctx, st);
-  if ((rc = ensure(ctx, &ctx->d_rn, &ctx->d_rn_cap, n_base + (size_t)nblocks * sizeof(int) + 16))) return rc;
-  int *block_count = (int *)ctx->d_rn;
-  unsigned char *keep = (unsigned char *)ctx->d_rn + (size_t)nblocks * sizeof(int);
+  if ((rc = scope.open())) return rc;
+  if ((rc = ctx->d_rn.ensure(ctx, n_base + (size_t)nblocks * sizeof(int) + 16))) return rc;
+  int *block_count = (int *)ctx->d_rn.p;
+  unsigned char *keep = (unsigned char *)ctx->d_rn.p + (size_t)nblocks * sizeof(int);
   remove_neighbors_flag_kernel<<<nblocks, kRnBlock, 0, st>>>(base_xy, base_stride, (int)n_base, list_xy, list_stride,
                                                              (int)n_list, rn_cutoff(thre_neighbor), keep, block_count);
   remove_neighbors_scan_kernel<<<1, 1024, 0, st>>>(block_count, nblocks, (unsigned long long *)n_out);
@@ -1495,17 +1496,17 @@ int ndt_remove_neighbors(ndt_ctx *ctx, const float *base_xy_host, size_t base_st
   hipStream_t st = ctx->stream;
   int rc;
   const size_t bb = n_base * base_stride, lb = n_list * list_stride, ob = n_base * sizeof(float2);
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, bb + lb + ob + 64))) return rc;
-  char *d = (char *)ctx->d_scan;
+  if ((rc = ctx->d_scan.ensure(ctx, bb + lb + ob + 64))) return rc;
+  char *d = (char *)ctx->d_scan.p;
   float *d_base = (float *)d, *d_list = (float *)(d + bb), *d_out = (float *)(d + bb + ((lb + 15) & ~(size_t)15));
-  if ((rc = ensure(ctx, &ctx->d_off, &ctx->d_off_cap, 4 * sizeof(uint64_t)))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(d_base, base_xy_host, bb, hipMemcpyHostToDevice, st));
   if (n_list) HIP_TRY(ctx, hipMemcpyAsync(d_list, list_xy_host, lb, hipMemcpyHostToDevice, st));
   if ((rc = ndt_remove_neighbors_dev(ctx, d_base, base_stride, n_base, n_list ? d_list : nullptr, n_list ? list_stride : 8,
-                                     n_list, thre_neighbor, d_out, (uint64_t *)ctx->d_off, st)))
+                                     n_list, thre_neighbor, d_out, ctx->d_off.p, st)))
     return rc;
   uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   *n_out = (size_t)cnt;
   HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)cnt * sizeof(float2), hipMemcpyDeviceToHost, st));
@@ -1550,14 +1551,10 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t
   L.o_diff = L.o_tab + tab_words * 8;
   const size_t total = L.o_diff + list_pts * 8 + 64;
   int rc;                                            // (the scratch bracket around mm_prepare + mm_run is the caller's: ScratchScope)
-  if ((rc = ensure(ctx, &ctx->d_mm, &ctx->d_mm_cap, total))) return rc;
+  if ((rc = ctx->d_mm.ensure(ctx, total))) return rc;
   if (ctx->mm_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_mm)); ctx->mm_pending = false; }
-  if (L.o_ucnt > ctx->h_mm_cap) {
-    if (ctx->h_mm) { hipError_t e = hipHostFree(ctx->h_mm); (void)e; ctx->h_mm = nullptr; ctx->h_mm_cap = 0; }
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_mm, 2 * L.o_ucnt + 256, hipHostMallocDefault));
-    ctx->h_mm_cap = 2 * L.o_ucnt + 256;
-  }
-  char *d = (char *)ctx->d_mm, *h = (char *)ctx->h_mm;
+  if (L.o_ucnt > ctx->h_mm.cap() && (rc = ctx->h_mm.alloc(ctx, 2 * L.o_ucnt + 256))) return rc;
+  char *d = (char *)ctx->d_mm.p, *h = (char *)ctx->h_mm.p;
   L.jobs = (MmJob *)h;
   L.units = (MmUnit *)(h + L.o_units);
   unsigned long long *d_cnt = (unsigned long long *)(d + L.o_cnt);
@@ -1583,10 +1580,10 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t
 // uploads jobs + units and queues the kernels; out/n_out are only used when there are units
 int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, double thre, float *out_xy,
            uint64_t *n_out, hipStream_t st) {
-  char *d = (char *)ctx->d_mm;
+  char *d = (char *)ctx->d_mm.p;
   const size_t bytes = nu ? L.o_units + nu * sizeof(MmUnit) : nj * sizeof(MmJob);
   if (bytes) {
-    HIP_TRY(ctx, hipMemcpyAsync(d, ctx->h_mm, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d, ctx->h_mm.p, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mm, st));
     ctx->mm_pending = true;
   }
@@ -1623,8 +1620,8 @@ int ndt_difference_extraction_dev(ndt_ctx *ctx, const float *base_xy, size_t bas
   MmLayout L;
   int rc;
   // the difference list is written straight to the caller's buffer, its count to the caller's counter
-  if ((rc = scratch_begin(ctx, st))) return rc;
   ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
   if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, st, &L))) return rc;
   L.jobs[0].n_diff = (unsigned long long *)n_out;
   if ((rc = mm_run(ctx, L, 1, 0, resol, 0.0, nullptr, nullptr, st))) return rc;
@@ -1643,17 +1640,17 @@ int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t ba
   hipStream_t st = ctx->stream;
   int rc;
   const size_t bb = (n_base * base_stride + 15) & ~(size_t)15, tb = (n_test * test_stride + 15) & ~(size_t)15;
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, bb + tb + n_test * sizeof(float2) + 64))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_off, &ctx->d_off_cap, 4 * sizeof(uint64_t)))) return rc;
-  char *d = (char *)ctx->d_scan;
+  if ((rc = ctx->d_scan.ensure(ctx, bb + tb + n_test * sizeof(float2) + 64))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
+  char *d = (char *)ctx->d_scan.p;
   float *d_base = (float *)d, *d_test = (float *)(d + bb), *d_out = (float *)(d + bb + tb);
   if (n_base) HIP_TRY(ctx, hipMemcpyAsync(d_base, base_xy_host, n_base * base_stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_test, test_xy_host, n_test * test_stride, hipMemcpyHostToDevice, st));
   if ((rc = ndt_difference_extraction_dev(ctx, d_base, base_stride, n_base, d_test, test_stride, n_test, resol, d_out,
-                                          (uint64_t *)ctx->d_off, st)))
+                                          ctx->d_off.p, st)))
     return rc;
   uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (cnt == ~0ull) return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: the clouds span more than 2^30 voxels");
   *n_out = (size_t)cnt;
@@ -1697,8 +1694,8 @@ int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy, size_t stride, const u
   P.unit_room = nu;
   MmLayout L;
   int rc;
-  if ((rc = scratch_begin(ctx, st))) return rc;
   ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
   if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
   size_t u = 0;
   for (const auto &pc : pieces) {
@@ -1725,19 +1722,19 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
   int rc;
   const size_t ib = (total * stride + 15) & ~(size_t)15;
   const size_t out_pts = n_scans == 1 ? 2 * total : total;      // a lone scan is appended twice (first + newest)
-  if ((rc = ensure(ctx, &ctx->d_scan, &ctx->d_scan_cap, ib + out_pts * sizeof(float2) + 64))) return rc;
-  if ((rc = ensure(ctx, &ctx->d_off, &ctx->d_off_cap, 4 * sizeof(uint64_t)))) return rc;
-  char *d = (char *)ctx->d_scan;
+  if ((rc = ctx->d_scan.ensure(ctx, ib + out_pts * sizeof(float2) + 64))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
+  char *d = (char *)ctx->d_scan.p;
   float *d_in = (float *)d, *d_out = (float *)(d + ib);
   HIP_TRY(ctx, hipMemcpyAsync(d_in, (const char *)scans_xy_host + (size_t)offsets[0] * stride, total * stride,
                               hipMemcpyHostToDevice, st));
   std::vector<uint64_t> rel((size_t)n_scans + 1);
   for (int i = 0; i <= n_scans; ++i) rel[i] = offsets[i] - offsets[0];
   if ((rc = ndt_make_map_dev(ctx, d_in, stride, rel.data(), n_scans, first_submap, newest, remove_moving, resol,
-                             thre_neighbor, d_out, (uint64_t *)ctx->d_off, st)))
+                             thre_neighbor, d_out, ctx->d_off.p, st)))
     return rc;
   uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (cnt == ~0ull) return fail(ctx, NDT_E_ARG, "ndt_make_map: a scan triple spans more than 2^30 voxels");
   *n_out = (size_t)cnt;

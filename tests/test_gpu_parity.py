@@ -967,7 +967,8 @@ def test_deferred_fitness_gives_the_same_records(gpu):
     runs next.  A stream of launches with alternating result arrays and two batches that take turns -- a whole-GPU one and a
     ragged one with an empty scan --, read at the launches' ends (ndt_ctx_wait_launch), equals the same stream without the option
     byte for byte; the caller's stream alone does NOT cover a deferred launch's fitness; entry points that are not deferred
-    launches (a host-pointer match, a launch after the option is switched off) wait for the deferred work by themselves."""
+    launches (a host-pointer match, a launch after the option is switched off, an in-place rebuild of the map the launch
+    reads, queued at once behind it) wait for the deferred work by themselves."""
     import torch
     capi, _ = gpu
     from ndt_slam_amd import synth
@@ -983,6 +984,7 @@ def test_deferred_fitness_gives_the_same_records(gpu):
     batches = []
     for sc, of, ini in ((scans, off, inits), (r_scans, r_off, inits[:40])):
         batches.append((torch.from_numpy(sc).to(dev), torch.from_numpy(of.astype(np.int64)).to(dev), torch.from_numpy(ini).to(dev), len(ini), len(sc)))
+    moved = [torch.from_numpy(np.ascontiguousarray(m + np.float32(d), dtype=np.float32)).to(dev) for d in (0.37, -1.3)]
 
     def stream_of_launches(defer):
         ctx = capi.Context(0)
@@ -1016,16 +1018,70 @@ def test_deferred_fitness_gives_the_same_records(gpu):
         gm.align_batch_dev(d_sc.data_ptr(), d_of.data_ptr(), B, npts, d_in.data_ptr(), outs[0][1].data_ptr(), stream=st.cuda_stream, ctx=ctx)
         st.synchronize()                                           # (not deferred: the stream's order covers it -- and the launch before it)
         tail = [np.frombuffer(o.cpu().numpy().tobytes(), dtype=capi.RESULT_DTYPE).copy() for o in outs[0]]
-        return got, one, tail
+        # a launch, then at once -- same stream, no wait_launch -- an in-place rebuild of its map from a moved cloud
+        # (ndt_map_build_dev, then rebuild_begin / _end): the rebuild waits for the deferred fitness kernels that read the tables
+        if defer:
+            ctx.set_option(capi.OPT_DEFER_FITNESS, 1)
+        rebuilt = []
+        for k, cloud in enumerate(moved):
+            gm.align_batch_dev(d_sc.data_ptr(), d_of.data_ptr(), B, npts, d_in.data_ptr(), outs[0][k % 2].data_ptr(), stream=st.cuda_stream, ctx=ctx)
+            if k == 0:
+                gm.rebuild(dev_ptr=cloud.data_ptr(), n=len(cloud))
+            else:
+                gm.rebuild_begin(cloud.data_ptr(), len(cloud))
+                gm.rebuild_end()
+            ctx.wait_launch(0, st.cuda_stream)
+            st.synchronize()
+            rebuilt.append(np.frombuffer(outs[0][k % 2].cpu().numpy().tobytes(), dtype=capi.RESULT_DTYPE).copy())
+        return got, one, tail, rebuilt
 
-    plain, one_p, tail_p = stream_of_launches(False)
-    deferred, one_d, tail_d = stream_of_launches(True)
+    plain, one_p, tail_p, rebuilt_p = stream_of_launches(False)
+    deferred, one_d, tail_d, rebuilt_d = stream_of_launches(True)
     assert np.all(plain[0]["status"] == 0) and np.all(plain[0]["fitness"] < 1e30)
     for a, b in zip(plain, deferred):
         assert a.tobytes() == b.tobytes()
     assert one_p.tobytes() == one_d.tobytes()
     for a, b in zip(tail_p, tail_d):
         assert a.tobytes() == b.tobytes() and a.tobytes() == plain[0].tobytes()
+    assert rebuilt_p[0].tobytes() == plain[0].tobytes()                # (the first read the map as built at the start)
+    for a, b in zip(rebuilt_p, rebuilt_d):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_contexts_and_maps_release_their_device_memory(gpu):
+    """Every device buffer of a context and of a map -- the scratch of the host-pointer and device-pointer entry points, the
+    prepared sets, the deferred launches' sets, the map's tables -- is released when they are destroyed: twenty rounds of
+    create, prepared batch, deferred launch, destroy leave the device's free memory where it was after the second."""
+    import torch
+    capi, _ = gpu
+    from ndt_slam_amd import synth
+    cfg = synth.CONFIGS["C3"]
+    m = synth.make_map(cfg["n_map"], cfg["half"])
+    sf = synth.ScanFactory(m, cfg["half"], cfg["n_scan"])
+    prm = capi.default_params(resolution=cfg["resolution"])
+    dev = torch.device("cuda", 0)
+    scans, off, truths, inits = sf.batch(0, 256)
+    d_sc, d_of, d_in = (torch.from_numpy(a).to(dev) for a in (scans, off.astype(np.int64), inits))
+    outs = [torch.zeros(256 * capi.RESULT_BYTES, dtype=torch.uint8, device=dev) for _ in range(2)]
+    args = (d_sc.data_ptr(), d_of.data_ptr(), 256, len(scans), d_in.data_ptr())
+    torch.cuda.synchronize()
+    free = []
+    for rnd in range(20):
+        ctx = capi.Context(0)
+        gm = capi.Map(ctx, m, prm)
+        gm.prepare_batch_dev(*args)
+        gm.align_batch_dev(*args, outs[0].data_ptr())
+        ctx.set_option(capi.OPT_DEFER_FITNESS, 1)
+        gm.align_batch_dev(*args, outs[1].data_ptr())
+        ctx.wait_launch(0)
+        torch.cuda.synchronize()
+        assert np.all(np.frombuffer(outs[1].cpu().numpy().tobytes(), dtype=capi.RESULT_DTYPE)["status"] == 0)
+        gm.close()
+        ctx.close()
+        if rnd in (1, 19):
+            torch.cuda.synchronize()
+            free.append(torch.cuda.mem_get_info(0)[0])
+    assert abs(free[1] - free[0]) <= 16 << 20, free
 
 
 def test_a_batch_prepared_ahead_gives_the_same_records(gpu, c1_world):
