@@ -288,6 +288,45 @@ int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy_dev, size_t stride
                             const uint64_t *raw_offsets_dev, int B, size_t total_raw_points, float leaf,
                             float *out_xy_dev, uint64_t *out_offsets_dev, void *stream);
 
+/* The two ends of ScanMatcher::matchScan for a batch: the resampler before the match and growMap's
+ * transform after it (src/ScanMatcher.cpp:6, :92-107).  Raw scans are LPoint2D x, y doubles
+ * (include/ndt_slam/LPoint2D.h:17-18) at stride_bytes (>= 16, a multiple of 8).
+ *
+ * Output bound of ndt_resample*: *capacity = total_points * k_max, where k_max = 1 if
+ * space_thre <= space, else floor(space_thre / space) + 2 (the most points one input point can
+ * emit).  Needs no context and no device.  NDT_E_ARG for a negative or non-finite parameter, for
+ * space == 0 < space_thre (the reference interpolates at distance 0 forever there) and when the
+ * product overflows. */
+int ndt_resample_capacity(size_t total_points, double space, double space_thre, size_t *capacity);
+/* Replaces ScanPointResampler::resamplePoints (src/ScanPointResampler.cpp:4-62, called at
+ * src/ScanMatcher.cpp:6) for a batch of B raw scans in device memory (raw_offsets[B+1] in points),
+ * bit for bit.  Writes the packed results: out_xy64_dev as double2 and/or out_xy32_dev as float2
+ * (the double -> float32 conversion of setScanPair, include/ndt_slam/PoseEstimator.h:91-104: exactly
+ * the input of ndt_prefilter_batch_dev); either may be NULL, not both; each needs room for
+ * ndt_resample_capacity(total_raw_points) points.  out_offsets_dev[B+1] in points.  status_dev: B
+ * ints or NULL; NDT_E_ARG marks a scan that holds a non-finite coordinate (its output range is then
+ * empty), NDT_OK the others.  Parameters are checked as ndt_resample_capacity checks them.
+ * growMap's ISOLATE skip (src/ScanMatcher.cpp:98) never fires on a resampled scan: every point is
+ * created anew with type UNKNOWN (include/ndt_slam/LPoint2D.h:28-42), so no type array is taken.
+ * Asynchronous on `stream` (NULL = the context's stream). */
+int ndt_resample_batch_dev(ndt_ctx *ctx, const double *raw_xy_dev, size_t stride_bytes,
+                           const uint64_t *raw_offsets_dev, int B, size_t total_raw_points, double space,
+                           double space_thre, double *out_xy64_dev, float *out_xy32_dev,
+                           uint64_t *out_offsets_dev, int *status_dev, void *stream);
+/* The same for one scan of n points in host memory; out_xy_host needs room for
+ * ndt_resample_capacity(n) points (double2); *n_out = points written.  Synchronous, like
+ * ndt_prefilter.  NDT_E_ARG for a non-finite coordinate. */
+int ndt_resample(ndt_ctx *ctx, const double *xy_host, size_t n, size_t stride_bytes, double space,
+                 double space_thre, double *out_xy_host, size_t *n_out);
+/* Replaces ScanMatcher::growMap's transform (src/ScanMatcher.cpp:96-101), followed by
+ * PointCloudMap::addPoints' conversion to float32 with z = 0: the resampled scans (doubles at
+ * stride_bytes, offsets_dev[B+1]) with B poses (tx, ty, th[deg]; Rmat as Pose2D::calRmat,
+ * include/ndt_slam/Pose2D.h:43-47) -> map-frame float2 points at the same offsets in out_xy_dev,
+ * ready for ndt_make_map_dev.  Asynchronous on `stream` (NULL = the context's stream). */
+int ndt_scan_to_map_batch_dev(ndt_ctx *ctx, const double *xy_dev, size_t stride_bytes,
+                              const uint64_t *offsets_dev, int B, size_t total_points,
+                              const double *poses_dev, float *out_xy_dev, void *stream);
+
 /* SURVEY.md 8f row f2 -- the steps either side of the match, for a batch resident in device
  * memory.  Poses are (tx, ty, th) triples of doubles with th in DEGREES (include/ndt_slam/Pose2D.h:14);
  * covariances are row-major 3x3 in (m, m, rad). */

@@ -62,7 +62,7 @@ EXPORTS = [
     "ndt_fuse_default_params", "ndt_predict_batch_dev", "ndt_fuse_batch_dev",
     "ndt_remove_neighbors", "ndt_remove_neighbors_dev",
     "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
-    "ndt_selftest_libm_f32",
+    "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
 ]
 
 
@@ -119,6 +119,10 @@ def lib():
     L.ndt_make_map.argtypes = [vp, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp,
                                C.POINTER(sz)]
     L.ndt_make_map_dev.argtypes = [vp, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
+    L.ndt_resample_capacity.argtypes = [sz, C.c_double, C.c_double, C.POINTER(sz)]
+    L.ndt_resample_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.ndt_resample.argtypes = [vp, vp, sz, sz, C.c_double, C.c_double, vp, C.POINTER(sz)]
+    L.ndt_scan_to_map_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -160,6 +164,16 @@ def align_batch_sharded(maps, scans, offsets, inits, shared_scan=False, partial=
     if rc:
         raise NdtError("ndt_align_batch_sharded -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
     return res
+
+
+def resample_capacity(total_points, space, space_thre):
+    """ndt_resample_capacity: the output bound (in points) of the resampler for total_points raw points.  Needs no
+    context and no device; raises NdtError on refused parameters."""
+    cap = C.c_size_t()
+    rc = lib().ndt_resample_capacity(int(total_points), float(space), float(space_thre), C.byref(cap))
+    if rc:
+        raise NdtError("ndt_resample_capacity -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+    return cap.value
 
 
 def default_fuse_params(**kw):
@@ -224,6 +238,27 @@ class Context:
         """Device pointers in and out (see include/ndt_mi355x.h); asynchronous."""
         self.check(lib().ndt_prefilter_batch_dev(self.h, raw_ptr, stride, raw_offsets_ptr, B, total_raw_points, leaf,
                                                  out_ptr, out_offsets_ptr, stream), "ndt_prefilter_batch_dev")
+
+    def resample(self, xy, space, space_thre):
+        """ScanPointResampler::resamplePoints on one scan ([n, 2] float64) -> resampled [m, 2] float64."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((resample_capacity(len(xy), space, space_thre), 2), dtype=np.float64)
+        m = C.c_size_t()
+        self.check(lib().ndt_resample(self.h, xy.ctypes.data if len(xy) else None, len(xy), 16, space, space_thre,
+                                      out.ctypes.data if len(out) else None, C.byref(m)), "ndt_resample")
+        return out[:m.value].copy()
+
+    def resample_batch_dev(self, raw_ptr, stride, raw_offsets_ptr, B, total_raw_points, space, space_thre, out64_ptr,
+                           out32_ptr, out_offsets_ptr, status_ptr=None, stream=None):
+        """Device pointers in and out (see include/ndt_mi355x.h; outputs sized by resample_capacity); asynchronous."""
+        self.check(lib().ndt_resample_batch_dev(self.h, raw_ptr, stride, raw_offsets_ptr, B, total_raw_points, space,
+                                                space_thre, out64_ptr, out32_ptr, out_offsets_ptr, status_ptr, stream),
+                   "ndt_resample_batch_dev")
+
+    def scan_to_map_batch_dev(self, xy_ptr, stride, offsets_ptr, B, total_points, poses_ptr, out_ptr, stream=None):
+        """growMap's transform for a batch: device pointers (doubles in, B x 3 poses in degrees, float2 out); asynchronous."""
+        self.check(lib().ndt_scan_to_map_batch_dev(self.h, xy_ptr, stride, offsets_ptr, B, total_points, poses_ptr,
+                                                   out_ptr, stream), "ndt_scan_to_map_batch_dev")
 
     def remove_neighbors(self, base, point_list, thre_neighbor):
         """PCFilter::remove_neighborPoint: base points with no list point within thre_neighbor, in order."""

@@ -48,6 +48,7 @@ thread_local std::string g_last_error;
 #include "ndt_map_build.hip.h"
 #include "ndt_front.hip.h"
 #include "ndt_localmap.hip.h"
+#include "ndt_resample.hip.h"
 
 }  // namespace
 
@@ -153,6 +154,7 @@ struct ndt_ctx {
   DevBuf<FitPart> d_fit_part;                          // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
+  DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
   DevBuf<unsigned char> d_rn;                          // neighbour removal: block offsets + keep flags
   DevBuf<unsigned char> d_mm;                          // local-map assembly: jobs, pieces, voxel sets, lists
   PinnedBuf<unsigned char> h_mm;                       // staging of the job table
@@ -1424,6 +1426,116 @@ int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, f
   *n_out = (size_t)fo[1];
   HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)fo[1] * sizeof(float2), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+namespace {
+// k_max of ndt_resample_capacity: the most points one input point can emit; 0 = refused parameters
+size_t resample_k_max(double space, double space_thre) {
+  if (!std::isfinite(space) || !std::isfinite(space_thre) || space < 0 || space_thre < 0) return 0;
+  if (space == 0 && space_thre > 0) return 0;        // the reference interpolates at distance 0 forever there
+  if (space_thre <= space) return 1;                 // dis + L >= space implies >= space_thre: kept, never interpolated
+  const double k = std::floor(space_thre / space) + 2;
+  return k < 9.0e18 ? (size_t)k : 0;
+}
+}  // namespace
+
+int ndt_resample_capacity(size_t total_points, double space, double space_thre, size_t *capacity) {
+  const size_t k = resample_k_max(space, space_thre);
+  if (!capacity || k == 0) return fail(nullptr, NDT_E_ARG, "ndt_resample_capacity: bad arguments");
+  if (total_points && k > SIZE_MAX / total_points) return fail(nullptr, NDT_E_ARG, "ndt_resample_capacity: overflow");
+  *capacity = total_points * k;
+  return NDT_OK;
+}
+
+int ndt_resample_batch_dev(ndt_ctx *ctx, const double *raw_xy, size_t stride, const uint64_t *raw_offsets, int B,
+                           size_t total_raw_points, double space, double space_thre, double *out_xy64, float *out_xy32,
+                           uint64_t *out_offsets, int *status, void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  size_t cap = 0;
+  if (!raw_xy || !raw_offsets || (!out_xy64 && !out_xy32) || !out_offsets || B <= 0 || total_raw_points == 0 ||
+      stride < 16 || (stride & 7) || ndt_resample_capacity(total_raw_points, space, space_thre, &cap))
+    return fail(ctx, NDT_E_ARG, "ndt_resample_batch: bad arguments");
+  const size_t k_max = cap / total_raw_points, N = total_raw_points;
+  if (cap > SIZE_MAX / sizeof(double2) / 2) return fail(ctx, NDT_E_NOMEM, "ndt_resample_batch: scratch too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  int rc;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
+  // scratch: walk outputs (k_max slots per raw point) | L | cnt | pos | tot | dist | bad
+  const size_t scr_b = cap * sizeof(double2), l_b = N * sizeof(double), c_b = N * sizeof(unsigned long long),
+               t_b = (size_t)B * sizeof(unsigned long long), d_b = (N * sizeof(unsigned) + 7) & ~(size_t)7;
+  if ((rc = ctx->d_rs.ensure(ctx, scr_b + l_b + 2 * c_b + t_b + d_b + (size_t)B * sizeof(int)))) return rc;
+  char *p = (char *)ctx->d_rs.p;
+  double2 *scr = (double2 *)p;                           p += scr_b;
+  double *L = (double *)p;                               p += l_b;
+  unsigned long long *cnt = (unsigned long long *)p;     p += c_b;
+  unsigned long long *pos = (unsigned long long *)p;     p += c_b;
+  unsigned long long *tot = (unsigned long long *)p;     p += t_b;
+  unsigned *dist = (unsigned *)p;                        p += d_b;
+  int *bad = (int *)p;
+  const unsigned long long *offs = (const unsigned long long *)raw_offsets;
+  const double resync = std::max(space, space_thre);
+  const unsigned gx = (unsigned)std::min<size_t>(64, (N / (size_t)B + 255) / 256 + 1), gy = (unsigned)std::min(B, 65535);
+  HIP_TRY(ctx, hipMemsetAsync(bad, 0, (size_t)B * sizeof(int), st));
+  resample_prepass_kernel<<<dim3(gx, gy), 256, 0, st>>>(raw_xy, stride, offs, B, N, L, bad);
+  resample_walk_kernel<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(raw_xy, stride, offs, B, N, L, space, space_thre, resync,
+                                                                     k_max, bad, scr, cnt, dist);
+  resample_segscan_kernel<<<std::min(B, 8 * ctx->num_cus), kRsScanThreads, 0, st>>>(offs, B, N, L, resync, bad, cnt, pos, tot);
+  resample_offsets_kernel<<<1, kRsScanThreads, 0, st>>>(tot, bad, B, (unsigned long long *)out_offsets, status);
+  resample_pack_kernel<<<dim3(gx, gy), 256, 0, st>>>(offs, B, N, bad, scr, k_max, cnt, pos, dist,
+                                                      (const unsigned long long *)out_offsets, (double2 *)out_xy64,
+                                                      (float2 *)out_xy32);
+  HIP_TRY(ctx, hipGetLastError());
+  return scope.close();
+}
+
+int ndt_resample(ndt_ctx *ctx, const double *xy_host, size_t n, size_t stride, double space, double space_thre,
+                 double *out_xy_host, size_t *n_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  size_t cap = 0;
+  if ((n && (!xy_host || !out_xy_host)) || !n_out || stride < 16 || (stride & 7) ||
+      ndt_resample_capacity(n, space, space_thre, &cap))
+    return fail(ctx, NDT_E_ARG, "ndt_resample: bad arguments");
+  if (n == 0) { *n_out = 0; return NDT_OK; }           // an empty scan stays empty (src/ScanPointResampler.cpp:7-8)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  int rc;
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride + 15 + cap * sizeof(double2)))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 5))) return rc;
+  double *d_in = (double *)ctx->d_scan.p;
+  double *d_out = (double *)((char *)ctx->d_scan.p + ((n * stride + 15) & ~(size_t)15));
+  uint64_t *d_offs = ctx->d_off.p;                              // [0..1] raw, [2..3] resampled, [4] status
+  const uint64_t raw[2] = {0, (uint64_t)n};
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, xy_host, n * stride, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_offs, raw, sizeof(raw), hipMemcpyHostToDevice, st));
+  if ((rc = ndt_resample_batch_dev(ctx, d_in, stride, d_offs, 1, n, space, space_thre, d_out, nullptr, d_offs + 2,
+                                   (int *)(d_offs + 4), st)))
+    return rc;
+  uint64_t fo[3] = {0, 0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(fo, d_offs + 2, sizeof(fo), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  int scan_status = 0;
+  memcpy(&scan_status, &fo[2], sizeof(int));
+  if (scan_status != NDT_OK) return fail(ctx, NDT_E_ARG, "ndt_resample: the scan holds a non-finite coordinate");
+  *n_out = (size_t)fo[1];
+  HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)fo[1] * sizeof(double2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+int ndt_scan_to_map_batch_dev(ndt_ctx *ctx, const double *xy, size_t stride, const uint64_t *offsets, int B,
+                              size_t total_points, const double *poses, float *out_xy, void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!xy || !offsets || !poses || !out_xy || B <= 0 || total_points == 0 || stride < 16 || (stride & 7))
+    return fail(ctx, NDT_E_ARG, "ndt_scan_to_map_batch: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const unsigned gx = (unsigned)std::min<size_t>(64, (total_points / (size_t)B + 255) / 256 + 1), gy = (unsigned)std::min(B, 65535);
+  scan_to_map_kernel<<<dim3(gx, gy), 256, 0, st>>>(xy, stride, (const unsigned long long *)offsets, B, total_points, poses,
+                                                    (float2 *)out_xy);
+  HIP_TRY(ctx, hipGetLastError());
   return NDT_OK;
 }
 

@@ -15,8 +15,9 @@ Host-side mirrors, same names and argument meaning as the reference:
 
 What runs on the MI355X: the source pre-filter and NDT match (PoseEstimator -> ndt_prefilter, ndt_map_build,
 ndt_align), Submap::makeMap (ndt_make_map: octree change detection + moving-object removal) and
-Submap::filterPoints (ndt_prefilter).  `ops` is the object that provides them (capi.Context); the bookkeeping
-and the 3x3 filter algebra stay on the host as in the reference.  ROS publishing (tf, PoseArray, RViz clouds)
+Submap::filterPoints (ndt_prefilter); with SlamLauncher(device_resample=True) also ScanPointResampler (ndt_resample,
+bit-identical to resample_points).  `ops` is the object that provides them (capi.Context); the bookkeeping and the
+3x3 filter algebra stay on the host as in the reference.  ROS publishing (tf, PoseArray, RViz clouds)
 is left out: it does not feed back into the estimate.
 """
 import math
@@ -337,8 +338,9 @@ class PointCloudMap:
 class ScanMatcher:
     """src/ScanMatcher.cpp:4-116; default score threshold 0.0 (ScanMatcher.h:49)."""
 
-    def __init__(self, estim, pcmap, pfu, scthre=0.0, space=0.0, space_thre=0.0):
+    def __init__(self, estim, pcmap, pfu, scthre=0.0, space=0.0, space_thre=0.0, resample=resample_points):
         self.estim, self.pcmap, self.pfu = estim, pcmap, pfu
+        self.resample = resample             # resample_points, or a device resampler with its arguments (ops.resample)
         self.scthre, self.space, self.space_thre = scthre, space, space_thre
         self.cnt = 0
         self.prevScan = None
@@ -347,7 +349,7 @@ class ScanMatcher:
         self.costs, self.accepted = [], []
 
     def matchScan(self, curScan):
-        curScan.lps = resample_points(curScan.lps, self.space, self.space_thre)         # :6
+        curScan.lps = self.resample(curScan.lps, self.space, self.space_thre)           # :6
         if self.cnt == 0:                                                               # :9-22
             self.growMap(curScan, curScan.pose)
             self.savePose(curScan.pose, np.zeros((3, 3)))
@@ -412,9 +414,10 @@ class FrontEnd:
 class SlamLauncher:
     """Wires the pipeline as SlamLauncher::init does (src/SlamLauncher.cpp:7-28) and runs the replay loop
     (:107-141).  `ops` provides prefilter / make_map (a capi.Context); `estim` defaults to the device
-    PoseEstimator on the same context."""
+    PoseEstimator on the same context.  device_resample: the scans are resampled by ops.resample (on the device)
+    instead of the host mirror resample_points -- the same points, bit for bit."""
 
-    def __init__(self, ops, estim=None, **params):
+    def __init__(self, ops, estim=None, device_resample=False, **params):
         p = dict(LAUNCH_PARAMS)
         p.update(params)
         self.p = p
@@ -425,7 +428,7 @@ class SlamLauncher:
                                    resol=p["resol"], thre_neighbor=p["thre_neighbor"])
         self.pfu = PoseFuser(p["coeVel"], p["coeOmega"], p["delTime"])
         self.smat = ScanMatcher(self.estim, self.pcmap, self.pfu, scthre=p["score_thre"], space=p["space"],
-                                space_thre=p["space_thre"])
+                                space_thre=p["space_thre"], resample=ops.resample if device_resample else resample_points)
         self.frontEnd = FrontEnd(self.smat, self.pcmap, keyframeSkip=p["keyframe_skip"], startFrame=p["start_frame"])
 
     def run(self, scans, poses_name=None, map_name=None, separated_map_name=None):

@@ -1,0 +1,346 @@
+"""GPU tests of the two ends of ScanMatcher::matchScan on the device: the resampler
+(ScanPointResampler::resamplePoints, src/ScanPointResampler.cpp:4-62) against its host mirror
+replay.resample_points, bit for bit, and growMap's scan-to-map transform (src/ScanMatcher.cpp:96-101) against
+replay.ScanMatcher.growMap within one float32 ulp (device cos / sin in double may differ from libm by one ulp)."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from ndt_slam_amd import replay, synth
+from ndt_slam_amd.pose_estimator import Pose2D, Scan2D
+from test_resample_capacity import adversarial_scans
+
+pytestmark = pytest.mark.gpu
+LAUNCH = (0.05, 0.25)                      # ndt_mapping.launch: space, space_thre
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
+    from ndt_slam_amd import capi
+    return capi, capi.Context(0)
+
+
+def to_dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def resample_on_device(capi, ctx, scans, space, space_thre):
+    """resample_batch_dev on a list of [n_i, 2] float64 scans -> (list of float64 results, list of float32 results,
+    out offsets, statuses)."""
+    import torch
+    scans = [np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in scans]
+    B = len(scans)
+    raw = np.concatenate(scans)
+    off = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+    cap = capi.resample_capacity(len(raw), space, space_thre)
+    d_raw, d_off = to_dev(raw), to_dev(off)
+    d64 = torch.full((cap, 2), -1.0, dtype=torch.float64, device="cuda:0")
+    d32 = torch.full((cap, 2), -1.0, dtype=torch.float32, device="cuda:0")
+    d_oo = torch.full((B + 1,), -1, dtype=torch.int64, device="cuda:0")
+    d_st = torch.full((B,), 7, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    ctx.resample_batch_dev(d_raw.data_ptr(), 16, d_off.data_ptr(), B, len(raw), space, space_thre, d64.data_ptr(),
+                           d32.data_ptr(), d_oo.data_ptr(), d_st.data_ptr())
+    torch.cuda.synchronize()
+    o64, o32, oo, st = d64.cpu().numpy(), d32.cpu().numpy(), d_oo.cpu().numpy(), d_st.cpu().numpy()
+    assert oo[0] == 0 and np.all(np.diff(oo) >= 0) and oo[-1] <= cap
+    return [o64[oo[b]:oo[b + 1]] for b in range(B)], [o32[oo[b]:oo[b + 1]] for b in range(B)], oo, st
+
+
+def assert_bit_equal(capi, ctx, scans, space, space_thre):
+    r64, r32, oo, st = resample_on_device(capi, ctx, scans, space, space_thre)
+    assert np.all(st == capi.NDT_OK)
+    n_ref = 0
+    for b, s in enumerate(scans):
+        ref = replay.resample_points(s, space, space_thre)
+        assert oo[b] == n_ref, b
+        n_ref += len(ref)
+        assert r64[b].shape == ref.shape, (b, r64[b].shape, ref.shape)
+        assert np.array_equal(r64[b].view(np.uint64), ref.view(np.uint64)), b
+        assert np.array_equal(r32[b].view(np.uint32), ref.astype(np.float32).view(np.uint32)), b
+    assert oo[-1] == n_ref
+
+
+def synthetic_scans(n):
+    recs, _ = synth.replay_records(n_frames=n, n_beams=1081)
+    return [r["front"] for r in recs]
+
+
+def test_batch_of_256_synthetic_scans_is_bit_equal(gpu):
+    capi, ctx = gpu
+    assert_bit_equal(capi, ctx, synthetic_scans(256), *LAUNCH)
+
+
+def test_mixed_batch_with_empty_and_tiny_scans(gpu):
+    capi, ctx = gpu
+    s = synthetic_scans(3)
+    scans = [np.zeros((0, 2)), s[0], np.array([[1.0, 2.0]]), s[1], np.array([[0.0, 0.0], [0.3, 0.0]]),
+             np.zeros((0, 2)), np.array([[0.0, 0.0], [0.01, 0.0]]), s[2], np.zeros((0, 2))]
+    assert_bit_equal(capi, ctx, scans, *LAUNCH)
+
+
+@pytest.mark.parametrize("space,space_thre", [(0.05, 0.25), (0.05, 0.05), (0.1, 0.05), (0.0, 0.0), (0.03, 0.2)])
+def test_adversarial_sets(gpu, space, space_thre):
+    capi, ctx = gpu
+    scans = adversarial_scans(space, space_thre, np.random.default_rng(11))
+    assert_bit_equal(capi, ctx, scans, space, space_thre)
+
+
+def test_zero_parameters_return_the_input(gpu):
+    capi, ctx = gpu
+    scans = synthetic_scans(4) + [np.repeat(np.arange(10.0).reshape(5, 2), 3, axis=0)]
+    r64, _, _, st = resample_on_device(capi, ctx, scans, 0.0, 0.0)
+    assert np.all(st == 0)
+    for a, b in zip(r64, scans):
+        assert np.array_equal(a, b)
+
+
+def test_space_thre_not_above_space(gpu):
+    capi, ctx = gpu
+    scans = synthetic_scans(8)
+    assert_bit_equal(capi, ctx, scans, 0.05, 0.05)
+    assert_bit_equal(capi, ctx, scans, 0.08, 0.02)
+
+
+def test_one_long_scan_without_a_resync_point(gpu):
+    """The worst case for the walk: 120k points in one piece (no step reaches max(space, space_thre))."""
+    capi, ctx = gpu
+    rng = np.random.default_rng(3)
+    steps = rng.normal(0, 0.02, (120000, 2))
+    steps *= np.minimum(1.0, 0.2 / np.maximum(np.hypot(steps[:, 0], steps[:, 1]), 1e-12))[:, None]
+    scan = steps.cumsum(0)
+    assert np.hypot(*np.diff(scan, axis=0).T).max() < 0.25
+    assert_bit_equal(capi, ctx, [scan], *LAUNCH)
+
+
+def test_host_entry_matches_the_batch(gpu):
+    capi, ctx = gpu
+    scans = synthetic_scans(6) + adversarial_scans(*LAUNCH, np.random.default_rng(2))[:4] + [np.zeros((0, 2))]
+    r64, _, _, _ = resample_on_device(capi, ctx, scans, *LAUNCH)
+    for s, b in zip(scans, r64):
+        h = ctx.resample(s, *LAUNCH)
+        assert h.dtype == np.float64 and h.shape == b.shape
+        assert np.array_equal(h.view(np.uint64), b.view(np.uint64))
+
+
+def test_non_finite_scan_is_refused_and_its_neighbours_are_unchanged(gpu):
+    """Defined behaviour for a NaN / inf coordinate: the scan's status is NDT_E_ARG and its range is empty (the walk
+    is capped at k_max emissions per input point, so no input can make it loop)."""
+    capi, ctx = gpu
+    s = synthetic_scans(5)
+    nan_scan = s[2].copy(); nan_scan[500, 1] = np.nan
+    inf_scan = s[3].copy(); inf_scan[7, 0] = np.inf
+    scans = [s[0], s[1], nan_scan, s[4], inf_scan, s[1]]
+    r64, r32, oo, st = resample_on_device(capi, ctx, scans, *LAUNCH)
+    assert list(st) == [0, 0, capi.NDT_E_ARG, 0, capi.NDT_E_ARG, 0]
+    assert oo[3] == oo[2] and oo[5] == oo[4]
+    for b in (0, 1, 3, 5):
+        ref = replay.resample_points(scans[b], *LAUNCH)
+        assert np.array_equal(r64[b].view(np.uint64), ref.view(np.uint64))
+        assert np.array_equal(r32[b], ref.astype(np.float32))
+    with pytest.raises(capi.NdtError):
+        ctx.resample(nan_scan, *LAUNCH)
+
+
+def test_bad_arguments_are_refused_synchronously(gpu):
+    import torch
+    capi, ctx = gpu
+    L = capi.lib()
+    d = torch.zeros((64, 2), dtype=torch.float64, device="cuda:0")
+    off = to_dev(np.array([0, 64], np.int64))
+    o64 = torch.zeros((64 * 7, 2), dtype=torch.float64, device="cuda:0")
+    oo = torch.zeros(2, dtype=torch.int64, device="cuda:0")
+    p, po, p64, poo = d.data_ptr(), off.data_ptr(), o64.data_ptr(), oo.data_ptr()
+    ok = L.ndt_resample_batch_dev(ctx.h, p, 16, po, 1, 64, 0.05, 0.25, p64, None, poo, None, None)
+    torch.cuda.synchronize()
+    assert ok == capi.NDT_OK
+    bad = [
+        (ctx.h, p, 16, po, 1, 64, 0.05, 0.25, None, None, poo, None, None),     # no output at all
+        (ctx.h, None, 16, po, 1, 64, 0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, None, 1, 64, 0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 1, 64, 0.05, 0.25, p64, None, None, None, None),
+        (ctx.h, p, 8, po, 1, 64, 0.05, 0.25, p64, None, poo, None, None),       # stride below one point
+        (ctx.h, p, 20, po, 1, 64, 0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 0, 64, 0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 1, 0, 0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 1, 64, -0.05, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 1, 64, 0.0, 0.25, p64, None, poo, None, None),       # the reference never ends there
+        (ctx.h, p, 16, po, 1, 64, math.nan, 0.25, p64, None, poo, None, None),
+        (ctx.h, p, 16, po, 1, 64, 0.05, math.inf, p64, None, poo, None, None),
+        (None, p, 16, po, 1, 64, 0.05, 0.25, p64, None, poo, None, None),
+    ]
+    for a in bad:
+        assert L.ndt_resample_batch_dev(*a) == capi.NDT_E_ARG, a
+    n = ctypes.c_size_t()
+    host = np.zeros((4, 2))
+    out = np.zeros((28, 2))
+    assert L.ndt_resample(ctx.h, host.ctypes.data, 4, 16, 0.0, 0.25, out.ctypes.data, ctypes.byref(n)) == capi.NDT_E_ARG
+    assert L.ndt_resample(ctx.h, host.ctypes.data, 4, 8, 0.05, 0.25, out.ctypes.data, ctypes.byref(n)) == capi.NDT_E_ARG
+    assert L.ndt_resample(ctx.h, host.ctypes.data, 4, 16, 0.05, 0.25, None, ctypes.byref(n)) == capi.NDT_E_ARG
+    pose = to_dev(np.zeros(3))
+    o32 = torch.zeros((64, 2), dtype=torch.float32, device="cuda:0")
+    for a in [(ctx.h, p, 16, po, 1, 64, pose.data_ptr(), None, None), (ctx.h, p, 16, po, 0, 64, pose.data_ptr(), o32.data_ptr(), None),
+              (ctx.h, p, 8, po, 1, 64, pose.data_ptr(), o32.data_ptr(), None), (ctx.h, p, 16, po, 1, 64, None, o32.data_ptr(), None),
+              (ctx.h, p, 16, po, 1, 0, pose.data_ptr(), o32.data_ptr(), None)]:
+        assert L.ndt_scan_to_map_batch_dev(*a) == capi.NDT_E_ARG, a
+    torch.cuda.synchronize()
+
+
+class _Capture:
+    """Stands in for PointCloudMap in growMap: keeps the float32 cloud addPoints makes (PointCloudMap.cpp:59-60)."""
+
+    def addPose(self, p):
+        pass
+
+    def addPoints(self, lps):
+        self.cloud = np.ascontiguousarray(lps, dtype=np.float32).reshape(-1, 2)
+
+    def setLastPose(self, p):
+        pass
+
+    def setLastScan(self, s):
+        pass
+
+    def makeLocalMap(self):
+        pass
+
+
+def grow_map_points(lps, pose):
+    cap = _Capture()
+    replay.ScanMatcher(None, cap, None).growMap(Scan2D(lps), Pose2D(*pose))
+    return cap.cloud
+
+
+def ulp_distance(a, b):
+    """Distance in float32 ulps (monotone integer map of the bit patterns)."""
+    def key(x):
+        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7fffffff), i)
+    return np.abs(key(a) - key(b))
+
+
+def scan_to_map_on_device(capi, ctx, scans, poses):
+    import torch
+    off = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+    xy = np.concatenate(scans).astype(np.float64)
+    d_out = torch.full((len(xy), 2), np.nan, dtype=torch.float32, device="cuda:0")
+    d_xy, d_off, d_p = to_dev(xy), to_dev(off), to_dev(np.asarray(poses, np.float64).reshape(-1, 3))
+    torch.cuda.synchronize()
+    ctx.scan_to_map_batch_dev(d_xy.data_ptr(), 16, d_off.data_ptr(), len(scans), len(xy), d_p.data_ptr(), d_out.data_ptr())
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    return [out[off[b]:off[b + 1]] for b in range(len(scans))]
+
+
+def test_scan_to_map_matches_grow_map(gpu):
+    capi, ctx = gpu
+    rng = np.random.default_rng(4)
+    scans = [replay.resample_points(s, *LAUNCH) for s in synthetic_scans(64)]
+    scans.insert(5, np.zeros((0, 2)))
+    poses = np.column_stack([rng.uniform(-30, 30, (len(scans), 2)), rng.uniform(-180, 180, len(scans))])
+    poses[0] = (0.0, 0.0, 0.0); poses[1] = (1.5, -2.0, 90.0); poses[2] = (0.0, 0.0, -180.0)
+    got = scan_to_map_on_device(capi, ctx, scans, poses)
+    differ = total = 0
+    for s, p, g in zip(scans, poses, got):
+        ref = grow_map_points(s, p)
+        assert g.shape == ref.shape
+        d = ulp_distance(g, ref)
+        assert d.max(initial=0) <= 1
+        differ += int((d != 0).sum()); total += d.size
+    print("scan_to_map: %d of %d coordinates not bit-equal to growMap (all within 1 ulp)" % (differ, total))
+    assert differ <= total // 100
+
+
+def test_whole_matchscan_chain_on_the_device(gpu, oracle, c1_world):
+    """resample -> pre-filter -> predict -> match -> fuse -> scan-to-map for a batch without leaving the device,
+    against the host chain resample_points -> approx_voxel_filter -> align -> fuse -> growMap (ScanMatcher::matchScan,
+    src/ScanMatcher.cpp:4-107).  Extends test_gpu_fuse.py::test_whole_front_end_step_on_the_device at both ends."""
+    import torch
+    capi, ctx = gpu
+    m, sf, cfg = c1_world
+    B = 32
+    space, space_thre = LAUNCH
+    prm = capi.default_params(resolution=cfg["resolution"])
+    gm = capi.Map(ctx, m, prm)
+    om = oracle.Map(m, oracle.default_params(resolution=cfg["resolution"]))
+    rng = np.random.default_rng(9)
+    raws, lasts, prevs, curs = [], [], [], []
+    for b in range(B):
+        scan, truth, init = sf.make(b % 16)
+        # raw doubles: every return twice, with noise, as a denser lidar would see the same walls
+        raws.append(np.repeat(scan.astype(np.float64), 2, axis=0) + rng.normal(0, 0.003, (2 * len(scan), 2)))
+        last = np.array([init[0] - 0.3, init[1] + 0.1, np.rad2deg(init[2]) - 2.0])
+        prev = np.array([rng.uniform(-5, 5), rng.uniform(-5, 5), rng.uniform(-180, 180)])
+        a, al = np.deg2rad(prev[2]), np.deg2rad(last[2])
+        d = np.array([[np.cos(al), np.sin(al)], [-np.sin(al), np.cos(al)]]) @ (np.array(init[:2]) - last[:2])
+        cur = np.array([*(prev[:2] + np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]) @ d), prev[2] + 2.0])
+        lasts.append(last); prevs.append(prev); curs.append(cur)
+    raw_all = np.concatenate(raws)
+    raw_off = np.concatenate([[0], np.cumsum([len(r) for r in raws])]).astype(np.int64)
+    cap = capi.resample_capacity(len(raw_all), space, space_thre)
+    last_cov = np.tile(np.eye(3) * 1e-4, (B, 1, 1))
+    dev = "cuda:0"
+    d_raw, d_roff = to_dev(raw_all), to_dev(raw_off)
+    d_r64 = torch.zeros((cap, 2), dtype=torch.float64, device=dev); d_r32 = torch.zeros((cap, 2), dtype=torch.float32, device=dev)
+    d_roo = torch.zeros(B + 1, dtype=torch.int64, device=dev); d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+    d_f = torch.zeros((cap, 2), dtype=torch.float32, device=dev); d_foff = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    d_cur, d_prev, d_last = to_dev(np.array(curs)), to_dev(np.array(prevs)), to_dev(np.array(lasts))
+    d_lc = to_dev(last_cov.reshape(B, 9))
+    d_mo = torch.zeros(B, 3, dtype=torch.float64, device=dev); d_pred = torch.zeros_like(d_mo); d_init = torch.zeros_like(d_mo)
+    d_res = torch.zeros(B * capi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+    d_fused = torch.zeros_like(d_mo); d_cov = torch.zeros(B, 9, dtype=torch.float64, device=dev)
+    d_ok = torch.zeros(B, dtype=torch.int32, device=dev)
+    d_map = torch.zeros((cap, 2), dtype=torch.float32, device=dev)
+    fp = capi.default_fuse_params(score_thre=0.5)
+    torch.cuda.synchronize()
+    ctx.resample_batch_dev(d_raw.data_ptr(), 16, d_roff.data_ptr(), B, len(raw_all), space, space_thre, d_r64.data_ptr(),
+                           d_r32.data_ptr(), d_roo.data_ptr(), d_st.data_ptr())
+    ctx.prefilter_batch_dev(d_r32.data_ptr(), 8, d_roo.data_ptr(), B, cap, 0.05, d_f.data_ptr(), d_foff.data_ptr())
+    ctx.predict_batch_dev(d_cur.data_ptr(), d_prev.data_ptr(), d_last.data_ptr(), B, d_mo.data_ptr(), d_pred.data_ptr(),
+                          d_init.data_ptr())
+    gm.align_batch_dev(d_f.data_ptr(), d_foff.data_ptr(), B, cap, d_init.data_ptr(), d_res.data_ptr())
+    ctx.fuse_batch_dev(d_res.data_ptr(), d_pred.data_ptr(), d_mo.data_ptr(), d_last.data_ptr(), d_lc.data_ptr(), B, fp,
+                       d_fused.data_ptr(), d_cov.data_ptr(), d_ok.data_ptr())
+    ctx.scan_to_map_batch_dev(d_r64.data_ptr(), 16, d_roo.data_ptr(), B, cap, d_fused.data_ptr(), d_map.data_ptr())
+    torch.cuda.synchronize()
+    fused, ok, st = d_fused.cpu().numpy(), d_ok.cpu().numpy(), d_st.cpu().numpy()
+    roo, r64, mp = d_roo.cpu().numpy(), d_r64.cpu().numpy(), d_map.cpu().numpy()
+    assert np.all(st == 0)
+    fo = oracle.default_fuse_params(score_thre=0.5)
+    for b in range(B):
+        res = replay.resample_points(raws[b], space, space_thre)
+        assert np.array_equal(r64[roo[b]:roo[b + 1]], res)
+        mo_ref, pred_ref = oracle.predict(curs[b], prevs[b], lasts[b])
+        filt = oracle.approx_voxel_filter(res.astype(np.float32), 0.05)
+        r_ref = om.align(filt, [pred_ref[0], pred_ref[1], np.deg2rad(pred_ref[2])])
+        ok_ref, f_ref, _ = oracle.fuse(r_ref, pred_ref, mo_ref, lasts[b], last_cov[b], fo)
+        assert ok[b] == ok_ref
+        assert fused[b, :2] == pytest.approx(f_ref[:2], abs=1e-4) and abs(fused[b, 2] - f_ref[2]) < np.rad2deg(1e-4)
+        # growMap with the pose this chain fused: the map-frame points ndt_make_map_dev takes
+        ref_map = grow_map_points(res, fused[b])
+        assert ulp_distance(mp[roo[b]:roo[b + 1]], ref_map).max(initial=0) <= 1
+    assert ok.sum() >= B // 2
+
+
+def test_replay_with_device_resampling_writes_the_same_files(gpu, tmp_path):
+    capi, ctx = gpu
+    recs, _ = synth.replay_records(n_frames=30, n_beams=361, step=0.5)
+    replay.write_log(tmp_path / "log.txt", recs)
+    params = dict(replay.LAUNCH_PARAMS, end_frame=30, sepThre=5.0)
+    outs = {}
+    for tag, flag in (("host", False), ("dev", True)):
+        sl = replay.SlamLauncher(ctx, device_resample=flag, **params)
+        sl.run(replay.read_log(tmp_path / "log.txt", sidelidar=False), poses_name=tmp_path / (tag + ".txt"),
+               map_name=str(tmp_path / (tag + ".pcd")), separated_map_name=str(tmp_path / (tag + "_sep")))
+        outs[tag] = sl
+    assert outs["dev"].smat.resample == ctx.resample and outs["host"].smat.resample is replay.resample_points
+    assert len(outs["dev"].pcmap.maps) == len(outs["host"].pcmap.maps) >= 2
+    assert open(tmp_path / "dev.txt", "rb").read() == open(tmp_path / "host.txt", "rb").read()
+    assert open(tmp_path / "dev.pcd", "rb").read() == open(tmp_path / "host.pcd", "rb").read()
+    for i in range(len(outs["dev"].pcmap.maps)):
+        assert open(tmp_path / ("dev_sep%d.pcd" % i), "rb").read() == open(tmp_path / ("host_sep%d.pcd" % i), "rb").read()

@@ -1,6 +1,8 @@
 """End-to-end replay: synthetic log -> poses file + PCD maps, every heavy step on the device;
 prints the time per scan next to the same replay with the oracle on one host core.
-Usage: python tools/replay_demo.py [n_frames] [n_beams] [--no-oracle]"""
+Usage: python tools/replay_demo.py [n_frames] [n_beams] [--profile] [--device-resample] [--no-oracle]
+--device-resample: the scans are resampled on the device (ndt_resample) instead of by the host mirror;
+--profile then reports the resampler's host time per scan next to the other steps."""
 import os
 import sys
 import tempfile
@@ -36,8 +38,9 @@ def main():
             setattr(obj, name, g)
         for name in ("prefilter", "make_map"):
             timed(ctx, name)
-    sl = replay.SlamLauncher(ctx, **params)
+    sl = replay.SlamLauncher(ctx, device_resample="--device-resample" in sys.argv, **params)
     if "--profile" in sys.argv:
+        timed(sl.smat, "resample")
         timed(sl.estim, "estimatePose")
         timed(sl.smat, "matchScan")
     scans = replay.read_log(log, sidelidar=False)
@@ -49,15 +52,16 @@ def main():
     est = np.array([[p.tx, p.ty] for p in poses])
     err = np.linalg.norm(est - truth[:len(est), :2], axis=1)
     odo = np.array([[r["x"], r["y"]] for r in recs])
-    print("replay of %d scans (%d returns each, ~%d points after resampling): %.1f ms per scan on the device path "
+    print("replay of %d scans (%d returns each, ~%d points after resampling on the %s): %.1f ms per scan on the device path "
           "(host bookkeeping in Python included); accepted %d; max position error %.3f m (odometry alone: %.3f m); "
           "submaps %d; local map %d points" % (
-              len(poses), n_raw, int(np.mean([len(s.lps) for s in scans])), 1e3 * t_dev / len(poses),
+              len(poses), n_raw, int(np.mean([len(s.lps) for s in scans])),
+              "device" if "--device-resample" in sys.argv else "host", 1e3 * t_dev / len(poses),
               sum(sl.smat.accepted), err.max(), np.linalg.norm(odo - truth[:, :2], axis=1).max(), len(sl.pcmap.submaps),
               len(sl.pcmap.localMap_cloud)))
     if spent:
         print("host time per scan [ms]:", {k: round(1e3 * v / len(poses), 3) for k, v in spent.items()},
-              "(estimatePose contains one prefilter; matchScan contains everything)")
+              "(estimatePose contains one prefilter; matchScan contains everything, resample included)")
     if "--no-oracle" not in sys.argv:
         from oracle import ndt_oracle as O                 # checker / CPU figure only
         from replay_helpers import OracleEstimator, OracleOps
