@@ -239,6 +239,35 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
  * none was used.  Blocks until that kernel has run. */
 int ndt_prepare_timing(ndt_ctx *ctx, float *order_ms);
 
+/* B independent matches, match b against maps[map_of[b]] (map_of == NULL: match b against maps[b], n_maps == B): one launch
+ * for many SLAM sessions, each with its own local map (src/ScanMatcher.cpp:40, src/PointCloudMap.cpp:119-131), or one scan
+ * against several candidate submaps.  Scans, offsets, inits, out, total_points and stream as for ndt_align_batch_dev;
+ * map_of_dev holds B ints in device memory (ndt_align_batch_multi: map_of_host, host memory; the call is synchronous).
+ *   Records: every record is byte-identical to the one ndt_align_batch_dev gives for the same scan, init and map -- flags,
+ *     kbar, evals and ref_evals included -- whatever the other maps of the launch, the helper count or the work sharing.
+ *   shared_scan != 0: scan 0 is matched from B seeds, each seed against its own map (relocalisation of one scan against K
+ *     candidate submaps: B = K x seeds).
+ *   Refusals (NDT_E_ARG, synchronous, nothing queued): n_maps < 1, a NULL maps array or map, a map that was never built, a map
+ *     on another device than ctx, map_of == NULL with n_maps != B, maps whose match parameters differ -- the optimiser
+ *     settings, transform_sse, radius_inclusive, resolution and the Gaussian constants d1 / d2 / e_hi, compared bit for bit
+ *     (the launch's kernel instance depends on them); build-only fields such as grid_margin or the covariance switches may
+ *     differ.  The error text names the first map that differs.
+ *   A map_of[b] outside [0, n_maps): record b alone gets status = NDT_E_ARG, zeroed, converged = 0, fitness = DBL_MAX (as a
+ *     failed shard's records, ndt_align_batch_sharded); no kernel reads through that index, the other records are unaffected.
+ *   Maps may belong to other contexts of the same device.  The launch is entered as a reader of every distinct map it reads:
+ *     a rebuild of any of them (re-queued by ndt_map_rebuild_end, or behind a deferred launch) waits for it; a map between
+ *     ndt_map_rebuild_begin and _end is matched with the grid its view holds at the call.
+ *   NDT_OPT_DEFER_FITNESS, NDT_OPT_MAX_HELPERS and NDT_OPT_WORKGROUPS apply as for ndt_align_batch_dev.  A multi-map call never
+ *     uses a batch prepared by ndt_align_batch_prepare_dev and leaves the prepared batches as they are.
+ *   The table of the maps' views is copied to the device once per call from pinned staging; the call waits on the host for
+ *     the previous multi-map call's copy of it before it rewrites the staging. */
+int ndt_align_batch_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_dev,
+                              const float *scans_xy_dev, const uint64_t *offsets_dev, int B, size_t total_points,
+                              int shared_scan, const double *inits_dev, ndt_result *out_dev, void *stream);
+int ndt_align_batch_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_host,
+                          const float *scans_xy_host, const uint64_t *offsets_host, int B, int shared_scan,
+                          const double *inits_host, ndt_result *out_host);
+
 /* Many matches over several GPUs from ONE process (north_star: "batch across the 8 GPUs of one node"; SURVEY.md 8b's
  * indicative multi-device context): `ctxs[r]` / `maps[r]` are a context of device r and a map built there from the same
  * cloud.  The batch is cut into n_shards contiguous, balanced shards (matches [r B / n, (r + 1) B / n), the first B % n

@@ -63,6 +63,7 @@ EXPORTS = [
     "ndt_remove_neighbors", "ndt_remove_neighbors_dev",
     "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
     "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
+    "ndt_align_batch_multi", "ndt_align_batch_multi_dev",
 ]
 
 
@@ -123,6 +124,8 @@ def lib():
     L.ndt_resample_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.ndt_resample.argtypes = [vp, vp, sz, sz, C.c_double, C.c_double, vp, C.POINTER(sz)]
     L.ndt_scan_to_map_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, vp, vp, vp]
+    L.ndt_align_batch_multi.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp]
+    L.ndt_align_batch_multi_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, i, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -163,6 +166,31 @@ def align_batch_sharded(maps, scans, offsets, inits, shared_scan=False, partial=
         return rc, res
     if rc:
         raise NdtError("ndt_align_batch_sharded -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+    return res
+
+
+def _map_handles(maps):
+    """(ndt_map *)[n] of a list of Map objects (None entries pass as NULL)."""
+    n = len(maps)
+    return (C.c_void_p * max(n, 1))(*[(m.h if m is not None else None) for m in maps]), n
+
+
+def align_batch_multi(ctx, maps, scans, offsets, inits, map_of=None, shared_scan=False):
+    """ndt_align_batch_multi: match b against maps[map_of[b]] (map_of None: maps[b], one map per match) in one launch on
+    `ctx`; records in the format of Map.align_batch.  A map_of entry outside [0, len(maps)) gives that record alone
+    status NDT_E_ARG (zeroed, fitness DBL_MAX)."""
+    scans = _f32c(scans)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    inits = np.ascontiguousarray(inits, dtype=np.float64).reshape(-1, 3)
+    B = len(inits)
+    res = np.zeros(B, dtype=RESULT_DTYPE)
+    mp, n = _map_handles(maps)
+    mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+    if mo is not None and len(mo) != B:
+        raise ValueError("map_of needs one entry per match")
+    ctx.check(lib().ndt_align_batch_multi(ctx.h, mp, n, None if mo is None else mo.ctypes.data, scans.ctypes.data,
+                                          offsets.ctypes.data, B, int(shared_scan), inits.ctypes.data, res.ctypes.data),
+              "ndt_align_batch_multi")
     return res
 
 
@@ -315,6 +343,15 @@ class Context:
         self.check(lib().ndt_fuse_batch_dev(self.h, results_ptr, pred_ptr, motion_ptr, last_pose_ptr, last_cov_ptr, B,
                                             C.byref(prm), fused_ptr, cov_ptr, successful_ptr, stream),
                    "ndt_fuse_batch_dev")
+
+    def align_batch_multi_dev(self, maps, map_of_ptr, scans_ptr, offsets_ptr, B, total_points, inits_ptr, out_ptr,
+                              shared_scan=False, stream=None):
+        """ndt_align_batch_multi_dev: `maps` a list of Map objects (of any context of this device), map_of_ptr a device
+        array of B int32 or None (match b against maps[b]); every other pointer a device address; asynchronous."""
+        mp, n = _map_handles(maps)
+        self.check(lib().ndt_align_batch_multi_dev(self.h, mp, n, map_of_ptr, scans_ptr, offsets_ptr, B, total_points,
+                                                   int(shared_scan), inits_ptr, out_ptr, stream),
+                   "ndt_align_batch_multi_dev")
 
     def selftest_libm_f32(self, yaws):
         """Device cosf / sinf / initial yaw (ndt_libm_f32.hip.h) for an array of float32 yaws -> (cos, sin, init_yaw)."""

@@ -398,15 +398,27 @@ __device__ __forceinline__ bool fit_block_of(int gx, int B, int &b, int &x) {
   return b < B;
 }
 
-template <bool SSE, bool DEFER>
+// MULTI launches (ndt_align_batch_multi_dev): the map of match b is views[map_of[b]] (map_of null: views[b]); a match whose
+// index is out of range has no map -- its workgroups return before reading anything through it, and its record keeps the
+// match kernel's fitness (DBL_MAX).  -1 for such a match.
+__device__ __forceinline__ int fit_map_index(const int *__restrict__ map_of, int n_maps, int b) {
+  const int mi = map_of ? map_of[b] : b;
+  return (mi >= 0 && mi < n_maps) ? mi : -1;
+}
+
+template <bool SSE, bool DEFER, bool MULTI = false>
 __global__ void __launch_bounds__(256, NDT_FIT_OCC)
-fitness_points_kernel(MapView M, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
+fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
                       int shared_scan, const float2 *__restrict__ sorted, const ndt_result *__restrict__ results,
                       float *__restrict__ fit, unsigned *__restrict__ far_idx, unsigned *__restrict__ far_n, int gx,
-                      FitPart *__restrict__ parts) {
+                      FitPart *__restrict__ parts, const MapView *__restrict__ views = nullptr,
+                      const int *__restrict__ map_of = nullptr, int n_maps = 0) {
   __shared__ RingLds ring[256 / 64];
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
+  int mi = 0;
+  if (MULTI && (mi = fit_map_index(map_of, n_maps, b)) < 0) return;
+  const MapView M = MULTI ? views[mi] : M_arg;
   {
     const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
     const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
@@ -465,14 +477,18 @@ fitness_points_kernel(MapView M, const float *__restrict__ scans, const unsigned
 #ifndef NDT_FAR_OCC
 #define NDT_FAR_OCC 5
 #endif
-template <bool SSE>
+template <bool SSE, bool MULTI = false>
 __global__ void __launch_bounds__(256, NDT_FAR_OCC)
-fitness_far_kernel(MapView M, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
+fitness_far_kernel(MapView M_arg, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
                    int shared_scan, const float2 *__restrict__ sorted, const ndt_result *__restrict__ results,
-                   float *__restrict__ fit, const unsigned *__restrict__ far_idx, const unsigned *__restrict__ far_n, int gx) {
+                   float *__restrict__ fit, const unsigned *__restrict__ far_idx, const unsigned *__restrict__ far_n, int gx,
+                   const MapView *__restrict__ views = nullptr, const int *__restrict__ map_of = nullptr, int n_maps = 0) {
   __shared__ FarLds far_lds;
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
+  int mi = 0;
+  if (MULTI && (mi = fit_map_index(map_of, n_maps, b)) < 0) return;
+  const MapView M = MULTI ? views[mi] : M_arg;
   {
     const unsigned na = far_n[2 * (size_t)b], nb = far_n[2 * (size_t)b + 1];
     if (na + nb == 0u) return;
@@ -510,17 +526,19 @@ fitness_far_kernel(MapView M, const float *__restrict__ scans, const unsigned lo
 // workgroup per match sums them into the match's chunks, and its first wave closes the match.  !SUM: the chunks are there
 // (fitness_points_kernel), a wave per match closes it.
 constexpr int kFitBlock = 1024;
-template <bool SUM>
+template <bool SUM, bool MULTI = false>
 __global__ void __launch_bounds__(kFitBlock)
 fitness_reduce_kernel(const unsigned long long *__restrict__ offsets, int B, int shared_scan,
                       const float *__restrict__ fit, ndt_result *__restrict__ results, FitPart *parts,
-                      uint4 *__restrict__ ws_words, unsigned n_ws_words) {
+                      uint4 *__restrict__ ws_words, unsigned n_ws_words,
+                      const int *__restrict__ map_of = nullptr, int n_maps = 0) {
   // it also clears the match kernel's control words and epoch-tagged words for the next launch (one kernel fewer between
   // two launches than a memset in front of each)
   for (unsigned i = blockIdx.x * kFitBlock + threadIdx.x; i < n_ws_words; i += gridDim.x * kFitBlock) ws_words[i] = uint4{0u, 0u, 0u, 0u};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (!SUM) {
     for (int b = blockIdx.x * (kFitBlock / 64) + wave; b < B; b += gridDim.x * (kFitBlock / 64)) {
+      if (MULTI && fit_map_index(map_of, n_maps, b) < 0) continue;      // (no map: the record keeps fitness DBL_MAX)
       const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
       const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
       const int n = (int)(o1 - o0);
@@ -529,6 +547,7 @@ fitness_reduce_kernel(const unsigned long long *__restrict__ offsets, int B, int
     return;
   }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    if (MULTI && fit_map_index(map_of, n_maps, b) < 0) continue;        // (workgroup-uniform)
     const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
     const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
     const int n = (int)(o1 - o0), nch = (n + 63) >> 6;

@@ -1107,7 +1107,21 @@ ndt_order_kernel(MapView M, OptParams P, const float *__restrict__ scans, const 
   }
 }
 
-template <bool SSE, bool INCL, bool CHK>
+// MULTI launches (ndt_align_batch_multi_dev): match b reads the map views[map_of[b]] (map_of null: views[b]); the index of a
+// match is checked before anything is read through it.  -1: outside [0, n_maps).
+__device__ __forceinline__ int map_index_of(const int *__restrict__ map_of, int n_maps, int b) {
+  const int mi = map_of ? map_of[b] : b;
+  return (mi >= 0 && mi < n_maps) ? mi : -1;
+}
+// The view into L.M, one word per lane of wave 1 (as the prepared records' optimiser state: a MapView held by value in
+// registers went through scratch memory).  The readers take it from there into SGPRs (pass_units: uniform_*).
+static_assert(sizeof(MapView) % 4 == 0 && sizeof(MapView) / 4 <= 64, "a word of the view per lane of one wave");
+__device__ __forceinline__ void load_view(Lds &L, const MapView *__restrict__ views, int mi) {
+  const unsigned t = threadIdx.x - 64u;
+  if (t < sizeof(MapView) / 4) reinterpret_cast<u32 *>(&L.M)[t] = reinterpret_cast<const u32 *>(views + mi)[t];
+}
+
+template <bool SSE, bool INCL, bool CHK, bool MULTI = false>
 __global__ void __launch_bounds__(kBlock)
 ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
                  const unsigned long long *__restrict__ offsets, int B, int shared_scan,
@@ -1118,7 +1132,9 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
                  int allow_helpers /* 0: none; else max helper workgroups per scan */,
                  unsigned long long *__restrict__ prof /* diagnostic: 8 words per scan */,
                  const PrepRec *__restrict__ prep /* batch prepared ahead (ndt_order_kernel), or null */,
-                 const unsigned *__restrict__ prep_map) {
+                 const unsigned *__restrict__ prep_map,
+                 const MapView *__restrict__ views = nullptr /* MULTI: n_maps views; M is not read then */,
+                 const int *__restrict__ map_of = nullptr, int n_maps = 0) {
   Lds &L = g_L;
   uint4 *const pool = g_pool;
   WsHeader *hdr = reinterpret_cast<WsHeader *>(ws);
@@ -1151,18 +1167,26 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
   if (allow_helpers && B > 0 && B < (int)gridDim.x && blockIdx.x < 4u * (unsigned)B)
     b0 = (int)((blockIdx.x % (unsigned)B + blockIdx.x / (unsigned)B) % (unsigned)B);
   for (int b = b0; b < B && !aborted;) {
+    // MULTI: the scan's own map, in L.M before the barrier behind the claim (its first reader is the scan's set-up below);
+    // a match whose map index is out of range reads no map: it runs as an empty scan and gets a zeroed NDT_E_ARG record
+    int mi = 0;
+    if (MULTI) {
+      mi = map_index_of(map_of, n_maps, (int)uniform_u((unsigned)b));
+      mi = (int)uniform_u((unsigned)mi);
+    }
     const u64 o0 = shared_scan ? offsets[0] : offsets[b];
     const u64 o1 = shared_scan ? offsets[1] : offsets[b + 1];
-    const int n = (int)(o1 - o0);
+    const int n = (MULTI && mi < 0) ? 0 : (int)(o1 - o0);
     const float2 *scan = reinterpret_cast<const float2 *>(scans) + o0;
     double *tr = trace ? trace + (size_t)b * trace_cap * 8 : nullptr;
     ScanCtl *C = ctl + b;
     u64 *mytot = utot + (size_t)b * kUnits * kUnitWords;
     __syncthreads();
+    if (MULTI && mi >= 0) load_view(L, views, mi);
     // scans that fit the register-resident set-up (order_scan_regs) get their optimiser state set up in there, under the
     // latency of the scan's first touch
     const bool reg_path = n > 0 && sorted != nullptr && n <= kSortRegs;
-    const bool prepared = reg_path && prep != nullptr && prep[b].ok != 0;        // (uniform: one word per scan)
+    const bool prepared = !MULTI && reg_path && prep != nullptr && prep[b].ok != 0;        // (uniform: one word per scan)
     // fewer scans than workgroups: idle workgroups from the start -- the scan is opened to them in the middle of its ordering
     const bool early_open = allow_helpers != 0 && reg_path && !prepared && B < (int)gridDim.x;
     if (threadIdx.x == 0) {
@@ -1447,9 +1471,15 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
       R_.flags = n > 0 ? ((L.RG.nspill > 0 ? NDT_FLAG_WINDOW_SPILL : 0) | (L.clipped ? NDT_FLAG_REGION_CLIPPED : 0) |
                           (pts == scan ? NDT_FLAG_UNSORTED : 0)) : 0;      // (an empty scan has no window: nothing left over from the scan before it)
       R_.kbar = (S.evals > 0 && n > 0) ? S.pairs / ((double)S.evals * (double)n) : 0.0;
+      if (MULTI && mi < 0) {                 // no map: zeroed, NDT_E_ARG, not converged, fitness DBL_MAX (the fitness kernels skip it)
+        memset(&R_, 0, sizeof(R_));
+        R_.status = NDT_E_ARG; R_.fitness = DBL_MAX;
+      }
       results[b] = R_;
       if (allow_helpers) {
         st64(&C->ticket, (u64)kEpochDone << 32);
+        // (MULTI: a score per point compared across scans of different maps -- best_spp only ranks scans for the helpers'
+        //  choice of whom to join, and no record depends on who helps whom)
         const float spp = n > 0 ? (float)(S.score / (double)n) : 0.f;
         if (S.converged && spp > 0.f) __hip_atomic_fetch_max(&hdr->best_spp, __float_as_uint(spp), NDT_RLX, NDT_AGENT);   // (positive floats order like their bits)
         __hip_atomic_fetch_add(&hdr->done, 1u, NDT_RLX, NDT_AGENT);
@@ -1565,6 +1595,11 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
     const u64 o0 = shared_scan ? offsets[0] : offsets[vb];
     const u64 o1 = shared_scan ? offsets[1] : offsets[vb + 1];
     const int n = (int)(o1 - o0);
+    if (MULTI) {                              // the joined scan's map, in L.M before the barrier in front of fill_window
+      // (a scan is opened to helpers only once its owner has found its map index in range; checked again all the same)
+      const int hm = (int)uniform_u((unsigned)map_index_of(map_of, n_maps, (int)uniform_u((unsigned)vb)));
+      if (hm >= 0) load_view(L, views, hm);
+    }
     if (threadIdx.x == 0) L.sflag[1] = (int)C->use_sorted;
     if (threadIdx.x == 0) {
       Region r; r.x0 = C->region[0]; r.y0 = C->region[1]; r.rw = C->region[2]; r.rh = C->region[3];

@@ -117,13 +117,18 @@ struct LaunchRing {
   bool deferred(unsigned long long k) const { return deferred_[covering(k) % kLen]; }
   // the events of the launch `b` launches before the latest (0: the latest); nullptr if it is not in the ring
   hipEvent_t *back(int b) { return b < 0 || b >= kLen || (unsigned long long)b >= launches ? nullptr : events(launches - 1 - b); }
-  // Enters the next launch of context `self` as the latest one of that context that reads a map (`readers`: ndt_map::readers).
+  // Enters the next launch of context `self` as the latest one of that context that reads the maps whose lists of readers
+  // are lists[0 .. n) (ndt_map::readers; one list per distinct map).
   // Under g_live_mu: launches and builds on several contexts may come from several host threads.
-  void enter(ndt_ctx *self, std::vector<std::pair<ndt_ctx *, unsigned long long>> &readers, bool deferred) {
+  using Readers = std::vector<std::pair<ndt_ctx *, unsigned long long>>;
+  void enter(ndt_ctx *self, Readers *const *lists, int n, bool deferred) {
     std::lock_guard<std::mutex> lk(g_live_mu);
     deferred_[launches % kLen] = deferred;
-    auto it = std::find_if(readers.begin(), readers.end(), [&](const auto &r) { return r.first == self; });
-    if (it != readers.end()) it->second = launches; else readers.emplace_back(self, launches);
+    for (int i = 0; i < n; ++i) {
+      Readers &readers = *lists[i];
+      auto it = std::find_if(readers.begin(), readers.end(), [&](const auto &r) { return r.first == self; });
+      if (it != readers.end()) it->second = launches; else readers.emplace_back(self, launches);
+    }
     launches++;
   }
 };
@@ -150,6 +155,7 @@ struct ndt_ctx {
   DevBuf<double> d_init, d_trace;
   DevBuf<ndt_result> d_res;
   DevBuf<int> d_rows;
+  DevBuf<int> d_map_of;                                // ndt_align_batch_multi: the host map_of's copy
   DevBuf<float> d_fit;                                 // squared distance to the nearest map point, per scan point (shared_scan launches)
   DevBuf<FitPart> d_fit_part;                          // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
@@ -159,6 +165,8 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_mm;                          // local-map assembly: jobs, pieces, voxel sets, lists
   PinnedBuf<unsigned char> h_mm;                       // staging of the job table
   hipEvent_t ev_mm = nullptr; bool mm_pending = false; // job table upload of the previous call
+  PinnedBuf<MapView> h_views;                          // ndt_align_batch_multi_dev: staging of the launch's table of map views
+  hipEvent_t ev_views = nullptr; bool views_pending = false;   // its upload by the previous multi-map launch (created on first use)
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
@@ -198,12 +206,14 @@ struct ndt_ctx {
     MapView V; const float *scans = nullptr; const unsigned long long *offsets = nullptr; int B = 0, shared_scan = 0;
     size_t total_points = 0; float2 *sorted = nullptr; ndt_result *out = nullptr; unsigned char *ws = nullptr;
     size_t zero_bytes = 0, far_cnt_bytes = 0; bool sse = false; hipEvent_t end = nullptr;
+    const MapView *views = nullptr; const int *map_of = nullptr; int n_maps = 0;   // multi-map launch: the device table (else V)
   };
   bool deferred_pending = false;                       // the last launch's fitness kernels may still be running beside the caller's stream
 };
 
 struct ndt_map {
   ndt_ctx *ctx = nullptr;
+  int device = 0;                             // ctx->device, kept for a destroy after the context's (ndt_map_destroy)
   ndt_params prm;
   ndt_map_info info;
   bool info_valid = false;
@@ -328,7 +338,7 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   const float *scans = J.scans; const unsigned long long *offsets = J.offsets;
   const int B = J.B, shared_scan = J.shared_scan; const size_t total_points = J.total_points;
   float2 *sorted = J.sorted; ndt_result *out = J.out; unsigned char *ws = J.ws;
-  const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes; const bool sse = J.sse;
+  const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes; const bool sse = J.sse, multi = J.views != nullptr;
   float *fit = ctx->d_fit.p;
   FitPart *parts = ctx->d_fit_part.p;
   {
@@ -342,21 +352,37 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
       const size_t cnt_bytes = far_cnt_bytes;
       unsigned *far_n = (unsigned *)ctx->d_far.p, *far_idx = (unsigned *)(ctx->d_far.p + cnt_bytes);
       { hipError_t e = hipMemsetAsync(far_n, 0, cnt_bytes, fs); if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("queue_fitness: hipMemsetAsync: ") + hipGetErrorString(e)); }
+      if (multi) {
+        if (sse) fitness_points_kernel<true, true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr, J.views, J.map_of, J.n_maps);
+        else     fitness_points_kernel<false, true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr, J.views, J.map_of, J.n_maps);
+        if (sse) fitness_far_kernel<true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, J.views, J.map_of, J.n_maps);
+        else     fitness_far_kernel<false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, J.views, J.map_of, J.n_maps);
+        hipExtLaunchKernelGGL((fitness_reduce_kernel<true, true>), dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
+                              offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), J.map_of, J.n_maps);
+      } else {
       if (sse) fitness_points_kernel<true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
       else     fitness_points_kernel<false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
       if (sse) fitness_far_kernel<true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
       else     fitness_far_kernel<false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
       hipExtLaunchKernelGGL(fitness_reduce_kernel<true>, dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                            offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16));
+                            offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), nullptr, 0);
+      }
     } else {
       // scans of their own: the search kernel leaves a {sum, count} per chunk of 64 points instead of a distance per point
-      if (sse) fitness_points_kernel<true, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
-      else     fitness_points_kernel<false, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
+      if (multi && sse) fitness_points_kernel<true, false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts, J.views, J.map_of, J.n_maps);
+      else if (multi)   fitness_points_kernel<false, false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts, J.views, J.map_of, J.n_maps);
+      else if (sse) fitness_points_kernel<true, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
+      else          fitness_points_kernel<false, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
       // (a wave per match; at least as many workgroups as clear the control words with one store per thread, a CU each at most)
       const size_t close_wgs = std::max<size_t>(((size_t)B + kFitBlock / 64 - 1) / (kFitBlock / 64),
                                                 std::min<size_t>((size_t)ctx->num_cus, (zero_bytes / 16 + kFitBlock - 1) / kFitBlock));
-      hipExtLaunchKernelGGL(fitness_reduce_kernel<false>, dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                            offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16));
+      if (multi)
+        hipExtLaunchKernelGGL((fitness_reduce_kernel<false, true>), dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
+                              offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), J.map_of, J.n_maps);
+      else
+        hipExtLaunchKernelGGL(fitness_reduce_kernel<false>, dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
+                              offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16),
+                              nullptr, 0);
     }
   }
   hipError_t e = hipGetLastError();
@@ -364,10 +390,18 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   return NDT_OK;
 }
 
+// The maps of a multi-map launch (ndt_align_batch_multi_dev): match b reads maps[map_of[b]] (map_of null: maps[b]).
+// The launch's parameters and template instance are those of maps[0] -- every map has the same ones (checked by the caller).
+struct MultiMaps {
+  const ndt_map *const *maps; int n_maps;
+  const int *map_of;                          // device, B entries, or null
+  std::vector<const ndt_map *> distinct;      // each map once: the launch enters itself in the readers of every one
+};
+
 int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scans,
                  const unsigned long long *offsets, int B, int shared_scan, size_t total_points, const double *inits,
                  ndt_result *out, double *trace, int trace_cap, int *trace_rows, unsigned long long *prof,
-                 ndt_ctx::PrepSet *pset = nullptr, bool defer = false) {
+                 ndt_ctx::PrepSet *pset = nullptr, bool defer = false, const MultiMaps *mm = nullptr) {
   const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
   LaunchRing &R = ctx->ring;
   const unsigned long long L = R.launches;
@@ -385,7 +419,11 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   // workspace: header + one control line per scan (zeroed every launch) + chunk totals
   // control words, epoch-tagged pose halves and unit totals (zero at kernel start), then the marked-cell bitmaps
   const size_t zero_bytes = sizeof(WsHeader) + (size_t)B * sizeof(ScanCtl) + (size_t)B * kUnits * kUnitWords * sizeof(u64);
-  const size_t ws_bytes = zero_bytes + (size_t)B * (kRegionCells / 8);
+  // a multi-map launch: its table of MapViews behind the bitmaps, outside the zeroed part -- in the launch's own set, so that
+  // it lives as long as the launch's fitness kernels, which read it (NDT_OPT_DEFER_FITNESS: the set is not taken over before
+  // they have finished; see below)
+  const size_t tab_off = (zero_bytes + (size_t)B * (kRegionCells / 8) + 255) & ~(size_t)255;
+  const size_t ws_bytes = mm ? tab_off + (size_t)mm->n_maps * sizeof(MapView) : zero_bytes + (size_t)B * (kRegionCells / 8);
   bool grown = false;
   int rc = set.ws.ensure(ctx, ws_bytes, &grown);
   if (rc) return rc;
@@ -405,9 +443,25 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   if ((rc = ctx->d_fit_part.ensure(ctx, slots / 64 + (size_t)B + 1))) return rc;
   // control words: zero before every launch -- by the last kernel of the previous launch of this context
   // (fitness_reduce_kernel), or by a memset when that did not cover enough
+  if (mm && !ctx->ev_views) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_views, hipEventDisableTiming));
+  if (mm && (size_t)mm->n_maps > ctx->h_views.cap()) {
+    if (ctx->views_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_views)); ctx->views_pending = false; }
+    if ((rc = ctx->h_views.ensure(ctx, (size_t)mm->n_maps))) return rc;
+  }
   if (set.ws_clean < zero_bytes) HIP_TRY(ctx, hipMemsetAsync(set.ws.p, 0, zero_bytes, st));
   set.ws_clean = 0;
   unsigned char *ws = set.ws.p;
+  // The table: the views as they are now (a map between ndt_map_rebuild_begin and _end is matched with the grid its view
+  // holds at the call), staged in pinned memory that the previous multi-map launch's copy may still be reading, then one copy
+  const MapView *views = nullptr;
+  if (mm) {
+    if (ctx->views_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_views)); ctx->views_pending = false; }
+    for (int i = 0; i < mm->n_maps; ++i) ctx->h_views.p[i] = mm->maps[i]->view;
+    HIP_TRY(ctx, hipMemcpyAsync(ws + tab_off, ctx->h_views.p, (size_t)mm->n_maps * sizeof(MapView), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_views, st));
+    ctx->views_pending = true;
+    views = reinterpret_cast<const MapView *>(ws + tab_off);
+  }
   // helper limit: 8 while a launch has fewer scans than workgroups (one scan at a time: everybody helps), 2 for whole-GPU
   // batches -- there the match kernel is as fast with 2 as with 15, and workgroups that find nothing to join leave their
   // CUs to the next step's map build earlier (round 4, after the repeated line-search passes went: LOG R4.9)
@@ -422,19 +476,40 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const bool chk = !(V.e_hi > 1.0 + 1e-6);
 #define NDT_LAUNCH(S_, I_, C_)                                                                                          \
   hipExtLaunchKernelGGL((ndt_align_kernel<S_, I_, C_>), dim3(grid), dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, \
-                        offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, prep, prep_map)
-  if (sse && incl)      NDT_LAUNCH(true, true, true);
+                        offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, prep, prep_map, \
+                        nullptr, nullptr, 0)
+#define NDT_LAUNCH_MULTI(S_, I_, C_)                                                                                          \
+  hipExtLaunchKernelGGL((ndt_align_kernel<S_, I_, C_, true>), dim3(grid), dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, \
+                        offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, nullptr, nullptr, \
+                        views, mm->map_of, mm->n_maps)
+  if (mm) {
+    if (sse && incl)      NDT_LAUNCH_MULTI(true, true, true);
+    else if (sse && !chk) NDT_LAUNCH_MULTI(true, false, false);
+    else if (sse)         NDT_LAUNCH_MULTI(true, false, true);
+    else if (incl)        NDT_LAUNCH_MULTI(false, true, true);
+    else                  NDT_LAUNCH_MULTI(false, false, true);
+  }
+  else if (sse && incl) NDT_LAUNCH(true, true, true);
   else if (sse && !chk) NDT_LAUNCH(true, false, false);
   else if (sse)         NDT_LAUNCH(true, false, true);
   else if (incl)        NDT_LAUNCH(false, true, true);
   else                  NDT_LAUNCH(false, false, true);
+#undef NDT_LAUNCH_MULTI
 #undef NDT_LAUNCH
   // From here on a kernel that reads the map and the context's scratch is queued: whatever happens below, the launch is
   // entered in the context's ring (its last event recorded) and in the map's list of readers, so that a later call on another
   // stream and a build of this map that must wait for it (re-queued, or behind a deferred launch) are ordered behind it.
   auto entered = [&](int code) {
     if (code != NDT_OK) { hipError_t e = hipEventRecord(evr[2], st); (void)e; }      // (the dispatch that would have carried it was not made)
-    R.enter(ctx, const_cast<ndt_map *>(map)->readers, defer);   // this launch reads the map: a build must wait for it (ndt_map::readers)
+    // this launch reads the map(s): a build must wait for it (ndt_map::readers)
+    if (mm) {
+      std::vector<LaunchRing::Readers *> lists;
+      for (const ndt_map *m : mm->distinct) lists.push_back(&const_cast<ndt_map *>(m)->readers);
+      R.enter(ctx, lists.data(), (int)lists.size(), defer);
+    } else {
+      LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
+      R.enter(ctx, &list, 1, defer);
+    }
     if (pset) pset->reader = (long long)L;
     return code;
   };
@@ -449,7 +524,8 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
     hipError_t e = hipStreamWaitEvent(fs, evr[1], 0);
     if (e != hipSuccess) return entered(fail(ctx, NDT_E_HIP, std::string("launch_align: hipStreamWaitEvent: ") + hipGetErrorString(e)));
   }
-  const int qrc = queue_fitness(ctx, {V, scans, offsets, B, shared_scan, total_points, sorted, out, ws, zero_bytes, far_cnt_bytes, sse, evr[2]}, fs);
+  const int qrc = queue_fitness(ctx, {V, scans, offsets, B, shared_scan, total_points, sorted, out, ws, zero_bytes, far_cnt_bytes, sse, evr[2],
+                                      views, mm ? mm->map_of : nullptr, mm ? mm->n_maps : 0}, fs);
   if (qrc != NDT_OK) return entered(qrc);
   {
     hipError_t e = hipGetLastError();
@@ -587,6 +663,7 @@ int ndt_ctx_destroy(ndt_ctx *c) {
   if (c->ev_fork) e = hipEventDestroy(c->ev_fork);
   if (c->ev_join) e = hipEventDestroy(c->ev_join);
   if (c->ev_mm) e = hipEventDestroy(c->ev_mm);
+  if (c->ev_views) e = hipEventDestroy(c->ev_views);
   if (c->ev_scratch) e = hipEventDestroy(c->ev_scratch);
   for (hipEvent_t r : c->ring.ev) if (r) e = hipEventDestroy(r);
   for (ndt_ctx::PrepSet &S : c->prep) {
@@ -655,13 +732,20 @@ int ndt_ctx_wait_launch(ndt_ctx *c, int back, void *stream) {
 
 int ndt_map_destroy(ndt_map *m) {
   if (!m) return NDT_E_ARG;
-  hipError_t e = hipSetDevice(m->ctx->device);
-  if (m->ctx->pending_map == m) {               // an open ndt_map_rebuild_begin dies with its map
+  bool ctx_live;
+  { std::lock_guard<std::mutex> lk(g_live_mu); ctx_live = g_live_ctx.count(m->ctx) != 0; }
+  hipError_t e = hipSetDevice(m->device);
+  // A context destroyed before its map (the header asks for the other order; a garbage collector that frees both
+  // together, such as Python's for objects on a reference cycle, may not keep it) has drained its streams already and
+  // is gone: nothing of it is touched then.
+  if (ctx_live) {
+    if (m->ctx->pending_map == m) {             // an open ndt_map_rebuild_begin dies with its map
+      if (m->ctx->side) e = hipStreamSynchronize(m->ctx->side);
+      m->ctx->pending_map = nullptr;
+    }
+    e = hipStreamSynchronize(m->ctx->stream);
     if (m->ctx->side) e = hipStreamSynchronize(m->ctx->side);
-    m->ctx->pending_map = nullptr;
   }
-  e = hipStreamSynchronize(m->ctx->stream);
-  if (m->ctx->side) e = hipStreamSynchronize(m->ctx->side);
   (void)e;
   delete m;                                     // (its buffers: on this device, after the work above has drained)
   return NDT_OK;
@@ -879,6 +963,7 @@ int ndt_map_build_dev(ndt_ctx *ctx, const float *xy, size_t n, size_t stride, co
     m = new (std::nothrow) ndt_map();
     if (!m) return NDT_E_NOMEM;
     m->ctx = ctx;
+    m->device = ctx->device;
     const unsigned init_b[16] = {0xffffffffu, 0xffffffffu, 0u, 0u};     // running bounding box, result, done-counter (map_minmax_kernel)
     int rc = m->bounds.alloc(ctx, sizeof(init_b));
     const hipError_t e = rc ? hipSuccess : hipMemcpy(m->bounds.p, init_b, sizeof(init_b), hipMemcpyHostToDevice);
@@ -1204,9 +1289,118 @@ int align_host(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_t stri
   return rc ? rc : align_host_finish(ctx);
 }
 
+// ---- multi-map launches (ndt_align_batch_multi_dev / ndt_align_batch_multi) ----
+
+bool same_bits(const void *a, const void *b, size_t n) { return memcmp(a, b, n) == 0; }
+
+// The refusals of a multi-map call (synchronous, nothing queued); fills mm on success.  The launch's template instance and
+// optimiser parameters are those of maps[0], so every field a match reads besides the grid must be the same in every map.
+int check_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_map_of, int B, const char *fn, MultiMaps *mm) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!maps || n_maps < 1) return fail(ctx, NDT_E_ARG, std::string(fn) + ": no maps (maps == NULL or n_maps < 1)");
+  if (!have_map_of && n_maps != B) return fail(ctx, NDT_E_ARG, std::string(fn) + ": map_of == NULL needs n_maps == B");
+  for (int i = 0; i < n_maps; ++i) {
+    const ndt_map *m = maps[i];
+    const std::string which = std::string(fn) + ": map " + std::to_string(i);
+    if (!m) return fail(ctx, NDT_E_ARG, which + " is NULL");
+    if (!m->ctx || !m->view.cent) return fail(ctx, NDT_E_ARG, which + " was never built");
+    if (m->ctx->device != ctx->device) return fail(ctx, NDT_E_ARG, which + " was built on another device");
+  }
+  const ndt_map *m0 = maps[0];
+  const OptParams o0 = opt_of(m0->prm);
+  for (int i = 1; i < n_maps; ++i) {
+    const ndt_map *m = maps[i];
+    const OptParams o = opt_of(m->prm);
+    const bool same = same_bits(&o.step_size, &o0.step_size, sizeof(double)) && same_bits(&o.trans_eps, &o0.trans_eps, sizeof(double)) &&
+                      same_bits(&o.snap_thresh, &o0.snap_thresh, sizeof(double)) && same_bits(&o.mt_mu, &o0.mt_mu, sizeof(double)) &&
+                      same_bits(&o.mt_nu, &o0.mt_nu, sizeof(double)) && o.max_iter == o0.max_iter && o.conv_ge == o0.conv_ge &&
+                      o.stale_h_ang == o0.stale_h_ang && o.mt_max_iter == o0.mt_max_iter && o.libm_f32 == o0.libm_f32 &&
+                      m->prm.transform_sse == m0->prm.transform_sse && m->prm.radius_inclusive == m0->prm.radius_inclusive &&
+                      same_bits(&m->prm.resolution, &m0->prm.resolution, sizeof(m0->prm.resolution)) &&
+                      same_bits(&m->view.d1, &m0->view.d1, sizeof(double)) && same_bits(&m->view.d2, &m0->view.d2, sizeof(double)) &&
+                      same_bits(&m->view.e_hi, &m0->view.e_hi, sizeof(double));
+    if (!same)
+      return fail(ctx, NDT_E_ARG, std::string(fn) + ": map " + std::to_string(i) +
+                  " has other match parameters than map 0 (optimiser settings, transform_sse, radius_inclusive, resolution or the Gaussian constants)");
+  }
+  mm->maps = maps; mm->n_maps = n_maps;
+  mm->distinct.assign(maps, maps + n_maps);
+  std::sort(mm->distinct.begin(), mm->distinct.end());
+  mm->distinct.erase(std::unique(mm->distinct.begin(), mm->distinct.end()), mm->distinct.end());
+  return NDT_OK;
+}
+
+// Stream order behind the builds of the maps (each on the stream of the context that built it), then the launch.
+int queue_multi(ndt_ctx *ctx, MultiMaps &mm, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
+                size_t total_points, int shared_scan, const double *inits, ndt_result *out, bool defer) {
+  std::vector<const ndt_ctx *> waited;
+  for (const ndt_map *m : mm.distinct) {
+    if (st == m->ctx->stream || std::find(waited.begin(), waited.end(), m->ctx) != waited.end()) continue;
+    HIP_TRY(ctx, hipStreamWaitEvent(st, m->ctx->evm1, 0));
+    waited.push_back(m->ctx);
+  }
+  return launch_align(ctx, mm.maps[0], st, scans, offsets, B, shared_scan, total_points, inits, out, nullptr, 0, nullptr, nullptr,
+                      nullptr, defer, &mm);
+}
+
 }  // namespace
 
 extern "C" {
+
+int ndt_align_batch_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_dev,
+                              const float *scans, const uint64_t *offsets, int B, size_t total_points, int shared_scan,
+                              const double *inits, ndt_result *out, void *stream) {
+  MultiMaps mm;
+  int rc = check_multi(ctx, maps, n_maps, map_of_dev != nullptr, B, "ndt_align_batch_multi_dev", &mm);
+  if (rc) return rc;
+  if (!scans || !offsets || !inits || !out || B <= 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi_dev: bad arguments");
+  if (total_points == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi_dev: total_points = 0");
+  mm.map_of = map_of_dev;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const bool defer = ctx->defer_fitness != 0;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open(defer))) return rc;
+  if ((rc = queue_multi(ctx, mm, st, scans, (const unsigned long long *)offsets, B, total_points, shared_scan, inits, out, defer)))
+    return rc;                                     // (scope: closed all the same -- kernels may have been queued)
+  return scope.close();
+}
+
+int ndt_align_batch_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_host,
+                          const float *scans, const uint64_t *offsets, int B, int shared_scan, const double *inits,
+                          ndt_result *out) {
+  MultiMaps mm;
+  int rc = check_multi(ctx, maps, n_maps, map_of_host != nullptr, B, "ndt_align_batch_multi", &mm);
+  if (rc) return rc;
+  if (!scans || !offsets || !inits || !out || B <= 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: bad arguments");
+  const size_t nscan = shared_scan ? 1 : (size_t)B;
+  for (size_t b = 0; b < nscan; ++b)
+    if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: offsets not monotone");
+  const size_t ntot = (size_t)offsets[nscan];
+  if (offsets[nscan] == offsets[0]) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: empty scans");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  if ((rc = ctx->d_scan.ensure(ctx, ntot * 8))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, nscan + 1))) return rc;
+  if ((rc = ctx->d_init.ensure(ctx, (size_t)B * 3))) return rc;
+  if ((rc = ctx->d_res.ensure(ctx, (size_t)B))) return rc;
+  if (map_of_host && (rc = ctx->d_map_of.ensure(ctx, (size_t)B))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scans, ntot * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init.p, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
+  if (map_of_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map_of.p, map_of_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  mm.map_of = map_of_host ? ctx->d_map_of.p : nullptr;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
+  if ((rc = queue_multi(ctx, mm, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B, ntot, shared_scan,
+                        ctx->d_init.p, ctx->d_res.p, false)))
+    return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_res.p, (size_t)B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  return align_host_finish(ctx);
+}
 
 int ndt_align_batch_trace(ndt_ctx *ctx, const ndt_map *map, const float *scans, const uint64_t *offsets,
                           int B, int shared_scan, const double *inits, ndt_result *out, double *trace,

@@ -127,6 +127,15 @@ class PoseEstimator:
 
     def estimatePose(self, initPose):
         """src/PoseEstimator.cpp:4-69.  Returns (cost, estPose, cov)."""
+        filtered = self.prepareEstimate()
+        try:
+            r = self._map.align(filtered, [initPose.tx, initPose.ty, DEG2RAD(initPose.th)])   # :22-28
+        except capi.NdtError:
+            return NOT_CONVERGED_COST, Pose2D(), np.full((3, 3), np.nan)
+        return self.finishEstimate(r)
+
+    def prepareEstimate(self):
+        """First half of estimatePose: the source pre-filter and the target's rebuild.  Returns the filtered scan."""
         filtered = self.ctx.prefilter(self.source_cloud, self.LeafSize)             # :6-10, on the device (f1)
         # :17-19 -- the target is rebuilt on every call, as the reference does (the local map is
         # refilled in place each scan, src/PointCloudMap.cpp:119-131)
@@ -135,12 +144,11 @@ class PoseEstimator:
         else:
             self._map.params = self.params
             self._map.rebuild(xy=self.target_cloud)
+        return filtered
+
+    def finishEstimate(self, r):
+        """Second half of estimatePose: one match record -> (cost, estPose, cov)."""
         est = Pose2D()
-        cov = np.full((3, 3), np.nan)
-        try:
-            r = self._map.align(filtered, [initPose.tx, initPose.ty, DEG2RAD(initPose.th)])   # :22-28
-        except capi.NdtError:
-            return NOT_CONVERGED_COST, est, cov
         self.last_result = r
         est.setPose(float(r["T03"]), float(r["T13"]), RAD2DEG(yaw_from_T_platform(r["T00"], r["T10"])))   # :29-36
         cost = float(r["fitness"])                                                  # :43
@@ -153,3 +161,36 @@ class PoseEstimator:
             except np.linalg.LinAlgError:
                 cov = np.full((3, 3), np.inf)
         return cost, est, cov
+
+
+def estimate_poses(estims, initPoses):
+    """estimatePose of several estimators -- independent sessions, each with its own local map -- with ONE multi-map
+    launch (capi.align_batch_multi): each estimator's first half, the launch over their maps, each one's second half.
+    Returns the list of (cost, estPose, cov), in the order of `estims`; the same values as estimatePose one by one.
+    The estimators must share one context and the match parameters of their maps (Resolution, StepSize,
+    TransformationEpsilon, MaximumIterations and the preset's switches): a launch refuses maps that differ in them, and
+    that refusal is raised (capi.NdtError), as every other one.  A parameter sweep over match parameters makes one call
+    per parameter set."""
+    estims = list(estims)
+    if not estims:
+        return []
+    ctx = estims[0].ctx
+    if any(e.ctx is not ctx for e in estims):
+        raise ValueError("estimate_poses: the estimators do not share one context")
+    filtered = [np.ascontiguousarray(e.prepareEstimate(), dtype=np.float32).reshape(-1, 2) for e in estims]
+    offsets = np.zeros(len(estims) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(f) for f in filtered])
+    inits = np.array([[p.tx, p.ty, DEG2RAD(p.th)] for p in initPoses], dtype=np.float64).reshape(-1, 3)
+    # An empty filtered scan is what makes estimatePose's match refuse (ndt_align: NDT_E_ARG) and return the
+    # not-converged sentinel.  In the batch it gets an NDT_E_ARG record; when every scan is empty there is nothing to launch.
+    if int(offsets[-1]) > 0:
+        recs = capi.align_batch_multi(ctx, [e._map for e in estims], np.concatenate(filtered), offsets, inits)
+    else:
+        recs = [None] * len(estims)
+    out = []
+    for e, f, r in zip(estims, filtered, recs):
+        if len(f) == 0:
+            out.append((NOT_CONVERGED_COST, Pose2D(), np.full((3, 3), np.nan)))
+        else:
+            out.append(e.finishEstimate(r))
+    return out

@@ -24,7 +24,7 @@ import math
 
 import numpy as np
 
-from .pose_estimator import DEG2RAD, RAD2DEG, Pose2D, PoseEstimator, Scan2D
+from .pose_estimator import DEG2RAD, RAD2DEG, Pose2D, PoseEstimator, Scan2D, estimate_poses
 
 # launch-file parameters (ndt_mapping.launch:8-36); constructor defaults differ and are noted at their classes
 LAUNCH_PARAMS = dict(
@@ -349,18 +349,33 @@ class ScanMatcher:
         self.costs, self.accepted = [], []
 
     def matchScan(self, curScan):
+        predPose = self.matchScanBegin(curScan)
+        if predPose is None:
+            return True
+        cost, estPose, Qmat = self.estim.estimatePose(predPose)                         # :45
+        return self.matchScanEnd(cost, estPose, Qmat)
+
+    def matchScanBegin(self, curScan):
+        """matchScan up to setScanPair.  Returns the predicted pose the match starts from, or None when the scan is the
+        first one (taken as it is: nothing to match)."""
         curScan.lps = self.resample(curScan.lps, self.space, self.space_thre)           # :6
         if self.cnt == 0:                                                               # :9-22
             self.growMap(curScan, curScan.pose)
             self.savePose(curScan.pose, np.zeros((3, 3)))
             self.prevScan = curScan
             self.cnt += 1
-            return True
+            return None
         odoMotion = calMotion(curScan.pose, self.prevScan.pose)                         # :27-28
         lastPose = self.pcmap.getLastPose()
         predPose = calPredPose(odoMotion, lastPose)                                     # :30-32
         self.estim.setScanPair(curScan, self.pcmap.localMap_cloud)                      # :40
-        cost, estPose, Qmat = self.estim.estimatePose(predPose)                         # :45
+        self._pending = (curScan, odoMotion, lastPose, predPose)
+        return predPose
+
+    def matchScanEnd(self, cost, estPose, Qmat):
+        """matchScan from the accept test on, with the estimate of the scan matchScanBegin set up."""
+        curScan, odoMotion, lastPose, predPose = self._pending
+        self._pending = None
         successful = cost <= self.scthre                                                # :49-53
         if successful:                                                                  # :58-65
             fusedPose, cov = self.pfu.fusePose(predPose, estPose, odoMotion, lastPose, self.lastCov, Qmat)
@@ -403,6 +418,10 @@ class FrontEnd:
         if scan.sid < self.startFrame:
             return
         self.smat.matchScan(scan)
+        self.processEnd()
+
+    def processEnd(self):
+        """process() behind the match: the keyframe bookkeeping."""
         if self.cnt % self.keyframeSkip == 0:
             self.pcmap.makeGlobalMap()
         self.cnt += 1
@@ -444,3 +463,49 @@ class SlamLauncher:
         if map_name:
             self.pcmap.saveGlobalMap(map_name, separated_map_name or (map_name + "_sep"))
         return poses
+
+
+def run_sessions(ops, logs, poses_names=None, map_names=None, separated_map_names=None, estimate=estimate_poses,
+                 launchers=None, **params):
+    """Independent SLAM sessions in lockstep: one SlamLauncher stack per log (`launchers`, or built from ops and
+    params), all stepped together.  At step k every session that still has a scan (at most end_frame of them) runs
+    matchScan's first half; the sessions that need a match are estimated together by ONE call of
+    `estimate(estimators, initPoses)` -- estimate_poses: one multi-map launch over the sessions' local maps -- then
+    each session runs the second half and FrontEnd's bookkeeping (start_frame, keyframe_skip).  A session that has
+    run out of scans drops out of the batch.  Writes per session what SlamLauncher.run writes (names may be None)
+    and returns the list of every session's fused poses; each is the same as its own SlamLauncher.run."""
+    logs = [list(l) for l in logs]
+    S = len(logs)
+    if launchers is None:
+        launchers = [SlamLauncher(ops, **params) for _ in range(S)]
+    if len(launchers) != S:
+        raise ValueError("run_sessions: one launcher per log")
+    lengths = [min(len(l), L.p["end_frame"]) for l, L in zip(logs, launchers)]
+    for k in range(max(lengths, default=0)):
+        stepped, need = [], []
+        for i in range(S):
+            if k >= lengths[i]:
+                continue
+            fe, scan = launchers[i].frontEnd, logs[i][k]
+            if scan.sid < fe.startFrame:
+                continue
+            stepped.append(i)
+            pred = fe.smat.matchScanBegin(scan)
+            if pred is not None:
+                need.append((i, pred))
+        if need:
+            res = estimate([launchers[i].smat.estim for i, _ in need], [p for _, p in need])
+            for (i, _), (cost, est, cov) in zip(need, res):
+                launchers[i].smat.matchScanEnd(cost, est, cov)
+        for i in stepped:
+            launchers[i].frontEnd.processEnd()
+    out = []
+    for i, L in enumerate(launchers):
+        poses = L.frontEnd.get_poses()
+        if poses_names and poses_names[i]:
+            write_poses(poses_names[i], poses)
+        if map_names and map_names[i]:
+            sep = separated_map_names[i] if separated_map_names and separated_map_names[i] else None
+            L.pcmap.saveGlobalMap(map_names[i], sep or (map_names[i] + "_sep"))
+        out.append(poses)
+    return out
