@@ -7,6 +7,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "ndt_mi355x.hip")
 OUT = os.path.join(HERE, "libndt_mi355x.so")
+# the test build whose set-up puts every scan's points in place by counting (order_scan_regs; tests/test_gpu_setup.py)
+FORCE_REPAIR_OUT = os.path.join(HERE, "libndt_mi355x_force_repair.so")
+FORCE_REPAIR_FLAGS = ["-DNDT_FORCE_ORDER_REPAIR"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
@@ -16,10 +19,10 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
          "-I" + os.path.join(ROOT, "include")]
 
 
-def needs_build():
-    if not os.path.exists(OUT):
+def needs_build(out=OUT):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
+    t = os.path.getmtime(out)
     csrc = os.path.dirname(SRC)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
     deps += [os.path.join(ROOT, "include", "ndt_mi355x.h"), __file__]

@@ -408,7 +408,10 @@ class Map:
         self.h = C.c_void_p()
         self.rebuild(xy=xy, dev_ptr=dev_ptr, n=n, stride=stride)
 
-    def rebuild(self, xy=None, dev_ptr=None, n=None, stride=8):
+    def rebuild(self, xy=None, dev_ptr=None, n=None, stride=8, params=None):
+        """Build the map again in place; `params`: other ndt_params from now on (the resolution may not change)."""
+        if params is not None:
+            self.params = params
         if dev_ptr is not None:
             rc = lib().ndt_map_build_dev(self.ctx.h, dev_ptr, n, stride, C.byref(self.params), C.byref(self.h))
         else:

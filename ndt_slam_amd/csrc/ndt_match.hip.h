@@ -616,7 +616,8 @@ __device__ __noinline__ bool sort_points(const MapView &M, const Tf32 &T0, const
 // executes one wave's instructions in order; between the lanes of ONE instruction that hit the same counter the LDS serialises
 // -- in lane order on this hardware, which the ISA does not promise, so every entry carries its sequence number and the order
 // that came out is checked (one comparison per entry: the entries of the whole array must ascend); if it ever does not, the
-// places are found by counting after all.  The turns are sixteen LDS-only barriers, 3.3 us (a token in LDS that the waves
+// places are found by counting after all (-DNDT_FORCE_ORDER_REPAIR takes that branch on every scan: the build
+// libndt_mi355x_force_repair.so, tests/test_gpu_setup.py).  The turns are sixteen LDS-only barriers, 3.3 us (a token in LDS that the waves
 // poll for their turn: 6 us).  Results differ from rounds 3-4 in the last bits of the sums (other order inside the cells), not
 // in the float32 transforms or the iteration counts (every parity test, all configurations).
 // The barriers of these phases order LDS traffic only (sync_lds): the ordered copy's stores to memory drain behind them.
@@ -780,6 +781,9 @@ __device__ NDT_ORDER_INLINE void order_scan_regs(const MapView &M, const OptPara
 #pragma unroll
     for (int u = 0; u < PER; ++u) bad |= ((int)threadIdx.x + u * kBlock + 1 < n) && !(va[u] < vb[u]);
     if (__ballot(bad) != 0ull && ln == 0) L.sflag[0] = 1;              // (raised by any wave)
+#ifdef NDT_FORCE_ORDER_REPAIR
+    if (threadIdx.x == 0) L.sflag[0] = 1;                              // (test build: the repair below on every scan)
+#endif
   }
   sync_lds();
   NDT_STAMP(stamps, t0s, 11);

@@ -173,17 +173,21 @@ struct ndt_ctx {
   int inject_fault = 0;                                // NDT_OPT_INJECT_FAULT (tests): the k-th next match launch fails behind its first kernel
   // Batches prepared ahead (ndt_align_batch_prepare_dev): two sets of buffers in turn -- ordered copies, records, bitmaps -- that
   // belong to no scratch bracket: set s is written by the prepare call for batch i + 1 while the launch of batch i, which reads
-  // the other set, is still running; the prepare call orders itself behind the last launch that read ITS set.
+  // the other set, is still running; the prepare call orders itself behind the last launch that read ITS set and behind the
+  // set's own previous ndt_order_kernel (which may still run on another stream).
   struct PrepSet {
     DevBuf<float2> sorted;
     DevBuf<PrepRec> recs;
     DevBuf<unsigned char> maps;
     hipEvent_t ev0 = nullptr, ready = nullptr;         // around ndt_order_kernel (on its dispatch)
     bool valid = false, timed = false;
-    // what the set was prepared for
+    // what the set was prepared for: the batch, and by value everything of the map ndt_order_kernel reads -- the optimiser's
+    // parameters (init_state: libm_f32, snap_thresh), the kernel instance (transform_sse) and the grid's origin and leaf
+    // (the cells at the first pose; div_x / div_y besides: the grid as a whole)
     const void *scans = nullptr, *offsets = nullptr, *inits = nullptr, *map = nullptr;
     int B = 0, shared_scan = 0; size_t total_points = 0;
     int min_bx = 0, min_by = 0, div_x = 0, div_y = 0; float inv_leaf = 0.f;
+    OptParams P{}; int transform_sse = 0;
     long long reader = -1;                             // number of the last launch of this context that read the set (-1: none)
   } prep[2];
   int prep_last = 1;                                   // set of the most recent prepare call
@@ -299,6 +303,16 @@ OptParams opt_of(const ndt_params &p) {
   o.mt_mu = p.mt_mu; o.mt_nu = p.mt_nu; o.max_iter = p.max_iter; o.conv_ge = p.conv_ge;
   o.stale_h_ang = p.stale_h_ang; o.mt_max_iter = p.mt_max_iter; o.libm_f32 = p.libm_f32;
   return o;
+}
+
+bool same_bits(const void *a, const void *b, size_t n) { return memcmp(a, b, n) == 0; }
+
+// Every field of two OptParams, the doubles bit for bit (not the struct as a whole: its padding is not defined).
+bool same_opt(const OptParams &o, const OptParams &o0) {
+  return same_bits(&o.step_size, &o0.step_size, sizeof(double)) && same_bits(&o.trans_eps, &o0.trans_eps, sizeof(double)) &&
+         same_bits(&o.snap_thresh, &o0.snap_thresh, sizeof(double)) && same_bits(&o.mt_mu, &o0.mt_mu, sizeof(double)) &&
+         same_bits(&o.mt_nu, &o0.mt_nu, sizeof(double)) && o.max_iter == o0.max_iter && o.conv_ge == o0.conv_ge &&
+         o.stale_h_ang == o0.stale_h_ang && o.mt_max_iter == o0.mt_max_iter && o.libm_f32 == o0.libm_f32;
 }
 
 // a3: Gaussian constants (Magnusson 2009 eq 6.8), host libm, once per map.
@@ -1100,6 +1114,9 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   // the last launch that read this set (its fitness kernels walk the set's ordered copies).
   if (S.reader >= 0 && (unsigned long long)S.reader < ctx->ring.launches)
     HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ring.end((unsigned long long)S.reader), 0));
+  // ... and behind the set's own previous order kernel, which no launch may have read (a third prepare call before any launch,
+  // the earlier one on another stream)
+  if (S.scans) HIP_TRY(ctx, hipStreamWaitEvent(st, S.ready, 0));
   const MapView &V = map->view;
   const OptParams O = opt_of(map->prm);
   const int ncu = ctx->workgroups > 0 ? ctx->workgroups : ctx->num_cus;
@@ -1113,6 +1130,7 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   HIP_TRY(ctx, hipGetLastError());
   S.scans = scans; S.offsets = offsets; S.inits = inits; S.map = map; S.B = B; S.shared_scan = shared_scan; S.total_points = total_points;
   S.min_bx = V.min_bx; S.min_by = V.min_by; S.div_x = V.div_x; S.div_y = V.div_y; S.inv_leaf = V.inv_leaf;
+  S.P = O; S.transform_sse = map->prm.transform_sse;
   S.valid = true; S.timed = false;
   ctx->prep_last ^= 1;
   return NDT_OK;
@@ -1129,15 +1147,18 @@ int ndt_align_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans, co
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   // the map build may still be running on the stream of the context that built the map
   if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
-  // a set prepared for exactly this batch against exactly this grid?  (A map whose speculative grid turned out wrong has been
-  // queued again with another origin -- ndt_map_rebuild_end: NDT_REBUILT -- and the set no longer fits: the owners order their
-  // scans themselves, as without it.)
+  // a set prepared for exactly this batch against exactly this grid and these parameters?  (A map whose speculative grid turned
+  // out wrong has been queued again with another origin -- ndt_map_rebuild_end: NDT_REBUILT --, or a rebuild changed the
+  // parameters, or another map took the old one's address, and the set no longer fits: the owners order their scans
+  // themselves, as without it.)
   ndt_ctx::PrepSet *pset = nullptr;
+  const OptParams O = opt_of(map->prm);
   for (ndt_ctx::PrepSet &S : ctx->prep) {
     const MapView &V = map->view;
     if (S.valid && S.scans == scans && S.offsets == offsets && S.inits == inits && S.map == map && S.B == B &&
         S.shared_scan == shared_scan && S.total_points == total_points && S.min_bx == V.min_bx && S.min_by == V.min_by &&
-        S.div_x == V.div_x && S.div_y == V.div_y && S.inv_leaf == V.inv_leaf)
+        S.div_x == V.div_x && S.div_y == V.div_y && same_bits(&S.inv_leaf, &V.inv_leaf, sizeof(float)) &&
+        S.transform_sse == map->prm.transform_sse && same_opt(S.P, O))
       pset = &S;
   }
   if (pset) {
@@ -1291,8 +1312,6 @@ int align_host(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_t stri
 
 // ---- multi-map launches (ndt_align_batch_multi_dev / ndt_align_batch_multi) ----
 
-bool same_bits(const void *a, const void *b, size_t n) { return memcmp(a, b, n) == 0; }
-
 // The refusals of a multi-map call (synchronous, nothing queued); fills mm on success.  The launch's template instance and
 // optimiser parameters are those of maps[0], so every field a match reads besides the grid must be the same in every map.
 int check_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_map_of, int B, const char *fn, MultiMaps *mm) {
@@ -1311,11 +1330,7 @@ int check_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_
   for (int i = 1; i < n_maps; ++i) {
     const ndt_map *m = maps[i];
     const OptParams o = opt_of(m->prm);
-    const bool same = same_bits(&o.step_size, &o0.step_size, sizeof(double)) && same_bits(&o.trans_eps, &o0.trans_eps, sizeof(double)) &&
-                      same_bits(&o.snap_thresh, &o0.snap_thresh, sizeof(double)) && same_bits(&o.mt_mu, &o0.mt_mu, sizeof(double)) &&
-                      same_bits(&o.mt_nu, &o0.mt_nu, sizeof(double)) && o.max_iter == o0.max_iter && o.conv_ge == o0.conv_ge &&
-                      o.stale_h_ang == o0.stale_h_ang && o.mt_max_iter == o0.mt_max_iter && o.libm_f32 == o0.libm_f32 &&
-                      m->prm.transform_sse == m0->prm.transform_sse && m->prm.radius_inclusive == m0->prm.radius_inclusive &&
+    const bool same = same_opt(o, o0) && m->prm.transform_sse == m0->prm.transform_sse && m->prm.radius_inclusive == m0->prm.radius_inclusive &&
                       same_bits(&m->prm.resolution, &m0->prm.resolution, sizeof(m0->prm.resolution)) &&
                       same_bits(&m->view.d1, &m0->view.d1, sizeof(double)) && same_bits(&m->view.d2, &m0->view.d2, sizeof(double)) &&
                       same_bits(&m->view.e_hi, &m0->view.e_hi, sizeof(double));
