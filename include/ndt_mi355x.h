@@ -191,6 +191,30 @@ int ndt_map_build_dev(ndt_ctx *ctx, const float *xy_dev, size_t n, size_t stride
 int ndt_map_rebuild_begin(ndt_ctx *ctx, const float *xy_dev, size_t n, size_t stride_bytes,
                           const ndt_params *prm, ndt_map *map);
 int ndt_map_rebuild_end(ndt_ctx *ctx, ndt_map *map);
+/* Many maps in one set of launches: replaces ndt.setInputTarget (src/PoseEstimator.cpp:19) for every session of a lockstep
+ * step (one ndt_map_build_dev per session before).  Map s is built from n[s] points at xy[s] (stride_bytes as for
+ * ndt_map_build) with parameters prm[s]; maps[s] == NULL: a new map is created and stored there, else maps[s] is rebuilt in
+ * place.  xy, n, prm and maps are host arrays of n_maps entries; _dev takes device cloud pointers, the host form copies
+ * the clouds to a staging buffer of the context first and is synchronous.
+ *   Result: each map is what ndt_map_build_dev gives for that map with its history -- the same voxel grid (grid_margin's
+ *     rule against the map's previous grid), ndt_map_info, ndt_map_export, raw-point buckets and match view -- so every
+ *     other entry point treats it as before.
+ *   The call reads back all the bounding boxes with one copy and waits for it once, then queues the rest of the build
+ *     (each kernel once for all maps).  No two-phase form.  _dev returns before the build ends (stream order, as
+ *     ndt_map_build_dev): xy[s] must stay valid until the build has run on the context's stream.
+ *   Refusals (NDT_E_ARG, synchronous, no map changed or created; the text names the first offending index): a NULL
+ *     context, n_maps < 1, NULL arrays, xy[s] == NULL, n[s] == 0 or > INT32_MAX, a bad stride, prm[s].resolution <= 0, a
+ *     map of another context, the same map twice, an open ndt_map_rebuild_begin on the context.  Behind the box read-back,
+ *     also changing nothing: a cloud with no finite point (NDT_E_ARG), a grid beyond 2^28 cells (NDT_E_GRID), grids that
+ *     together need more than 2^32 work-items in one kernel (NDT_E_GRID).
+ *   A HIP or allocation failure after that leaves the batch's existing maps unusable until they are rebuilt and destroys
+ *     the maps the call created (as ndt_map_build_dev for one map).
+ *   Ordering: as ndt_map_build_dev, per map (a deferred launch's fitness kernels that read it are waited for);
+ *     ndt_last_timing reports the whole call as the build time. */
+int ndt_map_build_batch_dev(ndt_ctx *ctx, const float *const *xy_dev, const size_t *n, size_t stride_bytes,
+                            int n_maps, const ndt_params *prm, ndt_map **maps);
+int ndt_map_build_batch(ndt_ctx *ctx, const float *const *xy_host, const size_t *n, size_t stride_bytes,
+                        int n_maps, const ndt_params *prm, ndt_map **maps);
 int ndt_map_destroy(ndt_map *map);
 int ndt_map_info_get(const ndt_map *map, ndt_map_info *out);
 /* Cell table in ascending voxel-index order, arrays sized n_cells (parity tests). */

@@ -63,7 +63,7 @@ EXPORTS = [
     "ndt_remove_neighbors", "ndt_remove_neighbors_dev",
     "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
     "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
-    "ndt_align_batch_multi", "ndt_align_batch_multi_dev",
+    "ndt_align_batch_multi", "ndt_align_batch_multi_dev", "ndt_map_build_batch", "ndt_map_build_batch_dev",
 ]
 
 
@@ -126,6 +126,8 @@ def lib():
     L.ndt_scan_to_map_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, vp, vp, vp]
     L.ndt_align_batch_multi.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp]
     L.ndt_align_batch_multi_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, i, vp, vp, vp]
+    L.ndt_map_build_batch.argtypes = [vp, vp, vp, sz, i, vp, vp]
+    L.ndt_map_build_batch_dev.argtypes = [vp, vp, vp, sz, i, vp, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -192,6 +194,38 @@ def align_batch_multi(ctx, maps, scans, offsets, inits, map_of=None, shared_scan
                                           offsets.ctypes.data, B, int(shared_scan), inits.ctypes.data, res.ctypes.data),
               "ndt_align_batch_multi")
     return res
+
+
+def _build_batch(ctx, fn, ptrs, ns, stride, params, maps):
+    """ndt_map_build_batch{,_dev}: the call's arrays from Python lists; existing maps rebuilt in place, new ones adopted."""
+    S = len(ptrs)
+    prms = list(params) if isinstance(params, (list, tuple)) else [params] * S
+    maps = list(maps) if maps is not None else [None] * S
+    if len(prms) != S or len(maps) != S:
+        raise ValueError("build_maps: one Params (or one for all) and one map slot per cloud")
+    k = max(S, 1)
+    xy = (C.c_void_p * k)(*ptrs)
+    n = (C.c_size_t * k)(*ns)
+    P = (Params * k)(*prms)
+    mp = (C.c_void_p * k)(*[(m.h if m is not None else None) for m in maps])
+    ctx.check(getattr(lib(), fn)(ctx.h, xy, n, stride, S, P, mp), fn)
+    out = []
+    for s in range(S):
+        if maps[s] is None:
+            out.append(Map.adopt(ctx, mp[s], prms[s]))
+        else:
+            maps[s].params = prms[s]
+            out.append(maps[s])
+    return out
+
+
+def build_maps(ctx, clouds, params, maps=None):
+    """ndt_map_build_batch: map s from clouds[s] ([n, 2] float32) with params (one Params for all, or a list), in one set
+    of launches on `ctx`.  `maps`: a list of Map or None per cloud (None: all new); existing maps are rebuilt in place, new
+    ones created.  Returns the list of Map, in the order of `clouds`."""
+    clouds = [_f32c(c) for c in clouds]
+    return _build_batch(ctx, "ndt_map_build_batch", [c.ctypes.data if len(c) else None for c in clouds],
+                        [len(c) for c in clouds], 8, params, maps)
 
 
 def resample_capacity(total_points, space, space_thre):
@@ -353,6 +387,11 @@ class Context:
                                                    int(shared_scan), inits_ptr, out_ptr, stream),
                    "ndt_align_batch_multi_dev")
 
+    def build_maps_dev(self, xy_ptrs, ns, params, maps=None, stride=8):
+        """ndt_map_build_batch_dev: capi.build_maps with device cloud pointers (xy_ptrs[s], ns[s] points at `stride` bytes);
+        asynchronous on this context's stream (the clouds must stay as they are until it has run)."""
+        return _build_batch(self, "ndt_map_build_batch_dev", list(xy_ptrs), list(ns), stride, params, maps)
+
     def selftest_libm_f32(self, yaws):
         """Device cosf / sinf / initial yaw (ndt_libm_f32.hip.h) for an array of float32 yaws -> (cos, sin, init_yaw)."""
         y = np.ascontiguousarray(yaws, dtype=np.float32).ravel()
@@ -407,6 +446,13 @@ class Map:
         self.params = params if params is not None else default_params()
         self.h = C.c_void_p()
         self.rebuild(xy=xy, dev_ptr=dev_ptr, n=n, stride=stride)
+
+    @classmethod
+    def adopt(cls, ctx, handle, params):
+        """A Map that owns `handle`, an ndt_map * a C call created on ctx (ndt_map_build_batch) with `params`."""
+        m = cls.__new__(cls)
+        m.ctx, m.params, m.h = ctx, params, C.c_void_p(handle)
+        return m
 
     def rebuild(self, xy=None, dev_ptr=None, n=None, stride=8, params=None):
         """Build the map again in place; `params`: other ndt_params from now on (the resolution may not change)."""

@@ -22,16 +22,67 @@ __host__ __device__ inline float ord2f(unsigned u) {
   return f;
 }
 
+struct GridDims { float inv_leaf; int min_bx, min_by, div_x, div_y, gw, gh; };
+struct LeafParams { int min_pts, cov_unbiased, cov_init_identity; double eig_mult; };
+
+// Batched builds (ndt_map_build_batch_dev): every kernel below has a BATCH instance that runs once per call for ALL maps
+// of the call.  Its prologue finds the workgroup's map in the block prefixes of that kernel (map s owns workgroups
+// [pre[s], pre[s + 1])) by binary search, takes that map's arguments from its job and its workgroup index inside the map;
+// the rest of the kernel is the single-map kernel's own code.  The scan takes its tiles from ONE ticket across the batch,
+// in map order: a tile's look-back only waits on tiles of its own map in front of it, which hold smaller tickets and so
+// belong to workgroups that are running or done, whatever the order in which workgroups are dispatched.
+enum { kBbMinmax = 0, kBbFill, kBbCount, kBbScan, kBbScatter, kBbOrder, kBbFinalize, kBbKernels };
+
+struct BoxJob { const float *xy; size_t n; };          // what map_minmax needs, ahead of the grids
+
+struct BuildJob {                                      // one map of the batch, with the grid its bounding box gave
+  const float *xy; size_t n;
+  GridDims G; LeafParams L;
+  int *count, *start /* the map's start.p + 4 */, *perm, *big, *npts_grid, *counters;
+  unsigned long long *scan_state; unsigned tag; int ntiles, big_cap; unsigned small_blocks;
+  float2 *pts, *cent; double *rec; unsigned *occ; u64 *tiles; int tiles_w;
+  size_t ng, npad, ntile8;
+  size_t zero_count, zero_state;                       // ints of count / words of scan_state to clear first (0: clean)
+};
+
+struct BuildBatch {                                    // the header of the job table, in device memory
+  const BoxJob *box_jobs; const BuildJob *jobs;
+  const unsigned *pre[kBbKernels];                     // per kernel: n_maps + 1 block prefixes
+  unsigned *boxes;                                     // 16 words per map: map_minmax's running box, result, done-counter
+  int *ticket;                                         // scan_onepass's tickets (cleared by map_count's batched instance)
+  int n_maps;
+};
+
+// The map of workgroup `blk` of batched kernel k; blk becomes the workgroup's index inside the map, nblk the map's number
+// of workgroups of that kernel.
+__device__ __forceinline__ int bb_map(const BuildBatch *bb, int k, unsigned &blk, unsigned &nblk) {
+  const unsigned *P = bb->pre[k];
+  int lo = 0, hi = bb->n_maps;                         // P[lo] <= blk < P[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (P[mid] <= blk) lo = mid; else hi = mid;
+  }
+  blk -= P[lo]; nblk = P[lo + 1] - P[lo];
+  return lo;
+}
+
 // getMinMax3D: out[0..3] = ord(min x), ord(min y), ord(max x), ord(max y).  bounds[0..3] is the running result and
 // bounds[8] counts the workgroups that are done; the last one hands the result over and puts both back to their
 // start values ({~0, ~0, 0, 0}, 0 -- set once when the map is created): no initialising copy in front of every build.
+// BATCH: the map's cloud; its box in the context's table (same layout), one table for the batch.
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256)
 map_minmax_kernel(const float *__restrict__ xy, size_t stride, size_t n, unsigned *__restrict__ bounds,
-                  unsigned *__restrict__ out) {
+                  unsigned *__restrict__ out, const BuildBatch *__restrict__ bb = nullptr) {
+  unsigned blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (BATCH) {
+    const int s = bb_map(bb, kBbMinmax, blk, nblk);
+    xy = bb->box_jobs[s].xy; n = bb->box_jobs[s].n; bounds = bb->boxes + 16 * (size_t)s; out = bounds + 4;
+  }
   __shared__ float sh[4][4];
   float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
-  const size_t step = (size_t)gridDim.x * blockDim.x;
-  for (size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i0 < n; i0 += 16 * step) {   // 16 loads in flight
+  const size_t step = (size_t)nblk * blockDim.x;
+  for (size_t i0 = blk * (size_t)blockDim.x + threadIdx.x; i0 < n; i0 += 16 * step) {   // 16 loads in flight
     float2 p[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) { const size_t i = i0 + u * step; p[u] = load_pt(xy, stride, i < n ? i : i0); }
@@ -60,7 +111,7 @@ map_minmax_kernel(const float *__restrict__ xy, size_t stride, size_t n, unsigne
       atomicMax(&bounds[2], f2ord(mxx)); atomicMax(&bounds[3], f2ord(mxy));
     }
     __threadfence();
-    if (atomicAdd(&bounds[8], 1u) == gridDim.x - 1u) {      // the last workgroup: every other one's atomics are in
+    if (atomicAdd(&bounds[8], 1u) == nblk - 1u) {           // the last workgroup: every other one's atomics are in
       __threadfence();
       out[0] = atomicExch(&bounds[0], 0xffffffffu); out[1] = atomicExch(&bounds[1], 0xffffffffu);
       out[2] = atomicExch(&bounds[2], 0u);          out[3] = atomicExch(&bounds[3], 0u);
@@ -68,8 +119,6 @@ map_minmax_kernel(const float *__restrict__ xy, size_t stride, size_t n, unsigne
     }
   }
 }
-
-struct GridDims { float inv_leaf; int min_bx, min_by, div_x, div_y, gw, gh; };
 
 __device__ __forceinline__ int voxel_of(const GridDims &G, float2 p) {
   if (!finite2(p.x, p.y)) return -1;
@@ -94,13 +143,21 @@ __device__ __forceinline__ void wave_runs(int v, int lane, int &head, int &len) 
   len = above ? (lane + 1 + __builtin_ctzll(above)) - lane : 64 - lane;  // valid in head lanes
 }
 
+// BATCH: the first workgroup of the call also clears the batch's scan ticket.
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256)
 map_count_kernel(const float *__restrict__ xy, size_t stride, size_t n, GridDims G, int *__restrict__ count,
-                 int *__restrict__ counters) {
-  if (blockIdx.x == 0 && threadIdx.x < 4) counters[threadIdx.x] = 0;     // the build's small counters (cells, valid, big voxels, scan ticket), for the kernels behind this one
+                 int *__restrict__ counters, const BuildBatch *__restrict__ bb = nullptr) {
+  unsigned blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (BATCH) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *bb->ticket = 0;
+    const BuildJob &J = bb->jobs[bb_map(bb, kBbCount, blk, nblk)];
+    xy = J.xy; n = J.n; G = J.G; count = J.count; counters = J.counters;
+  }
+  if (blk == 0 && threadIdx.x < 4) counters[threadIdx.x] = 0;     // the build's small counters (cells, valid, big voxels, scan ticket), for the kernels behind this one
   const int lane = threadIdx.x & 63;
   const size_t nround = (n + 63) / 64 * 64;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nround; i += (size_t)gridDim.x * blockDim.x) {
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < nround; i += (size_t)nblk * blockDim.x) {
     const int v = i < n ? voxel_of(G, load_pt(xy, stride, i)) : -2;
     int head, len;
     wave_runs(v, lane, head, len);
@@ -124,15 +181,26 @@ constexpr int kScanBlock = 1024, kScanPer = 8, kScanTile = kScanBlock * kScanPer
 constexpr int kBigVoxel = 16;        // voxels with more points are handled by a whole wave (order, statistics)
 constexpr unsigned long long kScanAgg = 1ull << 62, kScanPre = 2ull << 62;
 
+// BATCH: the ticket is the batch's; the ticket's map gives the arguments and the tile number inside the map.
+template <bool BATCH = false>
 __global__ void __launch_bounds__(kScanBlock)
 scan_onepass_kernel(const int *__restrict__ in, size_t n, unsigned long long *__restrict__ state /* 2 words per tile */, unsigned tag,
                     int ntiles, int *__restrict__ ticket, int *__restrict__ out /* n + 1 (+ 3 copies; 4 readable ints in front) */,
-                    int *__restrict__ big /* voxels with more than kBigVoxel points, in voxel order */, int *__restrict__ nbig, int big_cap) {
+                    int *__restrict__ big /* voxels with more than kBigVoxel points, in voxel order */, int *__restrict__ nbig, int big_cap,
+                    const BuildBatch *__restrict__ bb = nullptr) {
   __shared__ int sh_s[kScanBlock / 64], sh_b[kScanBlock / 64];
   __shared__ int s_tile, s_base_s, s_base_b;
+  if constexpr (BATCH) ticket = bb->ticket;
   if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1);
   __syncthreads();
-  const int tile = s_tile, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int tile = s_tile;
+  if constexpr (BATCH) {
+    unsigned t = (unsigned)__builtin_amdgcn_readfirstlane(tile), nt;
+    const BuildJob &J = bb->jobs[bb_map(bb, kBbScan, t, nt)];
+    tile = (int)t; in = J.count; n = J.ng; state = J.scan_state; tag = J.tag; ntiles = J.ntiles;
+    out = J.start; big = J.big; nbig = J.counters + 2; big_cap = J.big_cap;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t base = (size_t)tile * kScanTile + (size_t)threadIdx.x * kScanPer;
   int v[kScanPer]; int s = 0; unsigned bigmask = 0;
 #pragma unroll
@@ -207,13 +275,19 @@ scan_onepass_kernel(const int *__restrict__ in, size_t n, unsigned long long *__
   if (tile == 0 && threadIdx.x < 4) out[(int)threadIdx.x - 4] = 0;                        // the four readable ints in front of out[0] (ndt_fitness.hip.h)
 }
 
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256)
 map_scatter_kernel(const float *__restrict__ xy, size_t stride, size_t n, GridDims G,
                    const int *__restrict__ start, int *__restrict__ count /* in: points per voxel; out: zero */,
-                   int *__restrict__ perm) {
+                   int *__restrict__ perm, const BuildBatch *__restrict__ bb = nullptr) {
+  unsigned blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (BATCH) {
+    const BuildJob &J = bb->jobs[bb_map(bb, kBbScatter, blk, nblk)];
+    xy = J.xy; n = J.n; G = J.G; start = J.start; count = J.count; perm = J.perm;
+  }
   const int lane = threadIdx.x & 63;
   const size_t nround = (n + 63) / 64 * 64;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nround; i += (size_t)gridDim.x * blockDim.x) {
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < nround; i += (size_t)nblk * blockDim.x) {
     const int v = i < n ? voxel_of(G, load_pt(xy, stride, i)) : -2;
     int head, len;
     wave_runs(v, lane, head, len);
@@ -276,7 +350,8 @@ __device__ __forceinline__ void order_small_voxels(unsigned block, const int *__
 constexpr int kBigWavesPerBlock = 4, kBigBlocks = 4096, kBigStage = 512;   // LDS staging: point numbers per wave
 constexpr int kBigRuns = 64;                 // runs of consecutive point numbers per voxel the merge handles (else: rank by counting)
 // One launch for both kinds (they do not depend on each other): workgroups [0, small_blocks) take the small voxels,
-// the kBigBlocks behind them the listed big ones.
+// the kBigBlocks behind them the listed big ones (BATCH: per map, its small-voxel workgroups, then big-voxel ones sized by
+// its list's capacity).
 //
 // Big voxels (round 4): a voxel's segment of `perm` is a handful of RUNS of consecutive point numbers -- map_scatter_kernel
 // places every wave-run as a block, and a cloud is appended scan by scan, wall by wall (bench map: 2.5 runs per voxel,
@@ -284,14 +359,21 @@ constexpr int kBigRuns = 64;                 // runs of consecutive point number
 // an element's place is (lengths of the runs that start before its run) + (its offset in its run): O(n + runs * n / 64)
 // per voxel instead of the n^2 / 64 comparisons of rank counting (n = 25: the typical wall voxel).  A voxel in more than
 // kBigRuns runs (a cloud in random order) keeps rank counting.
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256)
 map_order_kernel(const int *__restrict__ start, size_t ng, unsigned small_blocks, const int *__restrict__ big,
                  const int *__restrict__ nbig, int big_cap, const int *__restrict__ perm, const float *__restrict__ xy,
-                 size_t stride, float2 *__restrict__ pts) {
+                 size_t stride, float2 *__restrict__ pts, const BuildBatch *__restrict__ bb = nullptr) {
+  unsigned blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (BATCH) {
+    const BuildJob &J = bb->jobs[bb_map(bb, kBbOrder, blk, nblk)];
+    start = J.start; ng = J.ng; small_blocks = J.small_blocks; big = J.big; nbig = J.counters + 2; big_cap = J.big_cap;
+    perm = J.perm; xy = J.xy; pts = J.pts;
+  }
   __shared__ int stage[kBigWavesPerBlock][kBigStage];
   __shared__ int run_first[kBigWavesPerBlock][kBigRuns], run_pos[kBigWavesPerBlock][kBigRuns + 1];
-  if (blockIdx.x < small_blocks) { order_small_voxels(blockIdx.x, start, ng, perm, xy, stride, pts); return; }
-  const unsigned bblock = blockIdx.x - small_blocks, bblocks = gridDim.x - small_blocks;
+  if (blk < small_blocks) { order_small_voxels(blk, start, ng, perm, xy, stride, pts); return; }
+  const unsigned bblock = blk - small_blocks, bblocks = nblk - small_blocks;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const u64 lt = (1ull << lane) - 1ull;
   const int count = min(*nbig, big_cap);
@@ -348,8 +430,6 @@ map_order_kernel(const int *__restrict__ start, size_t ng, unsigned small_blocks
     }
   }
 }
-
-struct LeafParams { int min_pts, cov_unbiased, cov_init_identity; double eig_mult; };
 
 // Mean, regularised covariance and its inverse of one z = 0 voxel (second loop of
 // VoxelGridCovariance::applyFilter); closed-form 2x2 eigen-decomposition, the z eigenpair is
@@ -433,16 +513,25 @@ __device__ __forceinline__ int write_voxel(const GridDims &G, const LeafParams &
 // voxel from memory eight points at a time, and the kernel lasted as long as its fullest voxel's chain of load round
 // trips (128 points: sixteen of them).  Same additions in the same order: the sums are unchanged bit for bit.
 constexpr int kFinStage = 1536;               // points per wave in LDS (12 KiB; a wave whose voxels hold more streams from memory)
+template <bool BATCH = false>
 __global__ void __launch_bounds__(256)
 map_finalize_kernel(GridDims G, LeafParams L,
                           const int *__restrict__ start,
                           const float2 *__restrict__ pts, float2 *__restrict__ cent, double *__restrict__ rec,
                           int *__restrict__ npts_grid, int *__restrict__ counters /* unused */,
                           unsigned *__restrict__ occ /* (ng + 31) / 32 words: voxel in the search set */,
-                          u64 *__restrict__ tiles, int tiles_w /* voxels with raw points, 8 x 8 per word (MapView::tiles) */) {
+                          u64 *__restrict__ tiles, int tiles_w /* voxels with raw points, 8 x 8 per word (MapView::tiles) */,
+                          const BuildBatch *__restrict__ bb = nullptr) {
+  unsigned blk = blockIdx.x;
+  if constexpr (BATCH) {
+    unsigned nblk;
+    const BuildJob &J = bb->jobs[bb_map(bb, kBbFinalize, blk, nblk)];
+    G = J.G; L = J.L; start = J.start; pts = J.pts; cent = J.cent; rec = J.rec; npts_grid = J.npts_grid; counters = J.counters;
+    occ = J.occ; tiles = J.tiles; tiles_w = J.tiles_w;
+  }
   __shared__ float2 lp[4][kFinStage];
   const size_t ng = (size_t)G.div_x * G.div_y;
-  size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  size_t g = blk * (size_t)blockDim.x + threadIdx.x;
   const bool live = g < ng;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int s0 = 0, s1 = 0;
@@ -515,10 +604,23 @@ map_finalize_kernel(GridDims G, LeafParams L,
   }
 }
 
-// reset of the centroid grid and of the occupancy tiles (side stream, beside the bucketing chain)
-__global__ void fill_f2_kernel(float2 *p, size_t n, float v, u64 *tiles, size_t ntiles) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+// reset of the centroid grid and of the occupancy tiles (side stream, beside the bucketing chain).  BATCH (on the build's
+// stream, in front of map_count): also the clearing of a count buffer that is not clean (grown, or left by a failed build)
+// and of grown scan words -- no memset per map.
+template <bool BATCH = false>
+__global__ void fill_f2_kernel(float2 *p, size_t n, float v, u64 *tiles, size_t ntiles, const BuildBatch *bb = nullptr) {
+  unsigned blk = blockIdx.x, nblk = gridDim.x;
+  const BuildJob *J = nullptr;
+  if constexpr (BATCH) {
+    J = &bb->jobs[bb_map(bb, kBbFill, blk, nblk)];
+    p = J->cent; n = J->npad; tiles = J->tiles; ntiles = J->ntile8;
+  }
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)nblk * blockDim.x)
     p[i] = make_float2(v, v);
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < ntiles; i += (size_t)gridDim.x * blockDim.x)
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < ntiles; i += (size_t)nblk * blockDim.x)
     tiles[i] = 0ull;
+  if constexpr (BATCH) {
+    for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < J->zero_count; i += (size_t)nblk * blockDim.x) J->count[i] = 0;
+    for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < J->zero_state; i += (size_t)nblk * blockDim.x) J->scan_state[i] = 0ull;
+  }
 }

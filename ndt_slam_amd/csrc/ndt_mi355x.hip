@@ -167,6 +167,14 @@ struct ndt_ctx {
   hipEvent_t ev_mm = nullptr; bool mm_pending = false; // job table upload of the previous call
   PinnedBuf<MapView> h_views;                          // ndt_align_batch_multi_dev: staging of the launch's table of map views
   hipEvent_t ev_views = nullptr; bool views_pending = false;   // its upload by the previous multi-map launch (created on first use)
+  // ndt_map_build_batch_dev: the scan's ticket (word 0) and 16 words per map from word 16 (map_minmax's running box, result and
+  // done-counter, set to their start values when the table grows), their read-back, the job table and its pinned staging
+  DevBuf<unsigned> d_boxes;
+  PinnedBuf<unsigned> h_boxes;
+  DevBuf<unsigned char> d_bb;
+  PinnedBuf<unsigned char> h_bb;
+  hipEvent_t ev_bb = nullptr; bool bb_pending = false; // the job table's upload by the previous batched build (created on first use)
+  DevBuf<unsigned char> d_bstage;                      // ndt_map_build_batch: the host clouds' copies
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
@@ -678,6 +686,7 @@ int ndt_ctx_destroy(ndt_ctx *c) {
   if (c->ev_join) e = hipEventDestroy(c->ev_join);
   if (c->ev_mm) e = hipEventDestroy(c->ev_mm);
   if (c->ev_views) e = hipEventDestroy(c->ev_views);
+  if (c->ev_bb) e = hipEventDestroy(c->ev_bb);
   if (c->ev_scratch) e = hipEventDestroy(c->ev_scratch);
   for (hipEvent_t r : c->ring.ev) if (r) e = hipEventDestroy(r);
   for (ndt_ctx::PrepSet &S : c->prep) {
@@ -765,35 +774,77 @@ int ndt_map_destroy(ndt_map *m) {
   return NDT_OK;
 }
 
+// The geometry of the occupancy tiles of a grid (MapView::tiles: 8 x 8 voxels per word, a border of one word).
+static int tiles_w_of(const GridDims &G) { return (G.div_x + 7) / 8 + 2; }
+static size_t ntile8_of(const GridDims &G) { return (size_t)tiles_w_of(G) * ((G.div_y + 7) / 8 + 2); }
+
+// Step 2 of the map build: the map's buffers for n points on a grid of ng voxels (npad with the border), grow-only across
+// rebuilds.  A grown count buffer is marked not clean; *state_grown: the scan's words were reallocated -- the caller clears
+// them (no word may carry a tag by accident).
+static int ensure_build_buffers(ndt_ctx *ctx, ndt_map *m, size_t n, size_t ng, size_t npad, size_t ntile8, bool *state_grown) {
+  int rc; bool grown = false;
+  const size_t ntiles_ = (ng + kScanTile - 1) / kScanTile;
+  if ((rc = m->count.ensure(ctx, ng + 1, &grown))) return rc;
+  if (grown) m->count_clean = false;
+  if ((rc = m->start.ensure(ctx, ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
+  if ((rc = m->npts_grid.ensure(ctx, ng + 1))) return rc;
+  if ((rc = m->scan_state.ensure(ctx, 2 * ntiles_ + 2, state_grown))) return rc;
+  if ((rc = m->perm.ensure(ctx, n + 4))) return rc;       // + 4: map_order_kernel reads four numbers at a time
+  if ((rc = m->big.ensure(ctx, n / kBigVoxel + 1))) return rc;   // voxels with > kBigVoxel points
+  if ((rc = m->occ.ensure(ctx, (ng + 31) / 32 + 2))) return rc;
+  if ((rc = m->tiles.ensure(ctx, ntile8))) return rc;
+  if ((rc = m->pts.ensure(ctx, n))) return rc;
+  if ((rc = m->cent.ensure(ctx, npad))) return rc;
+  if ((rc = m->rec.ensure(ctx, npad * 8))) return rc;
+  return NDT_OK;
+}
+
+// The tag of a build's scan words (never 0: cleared words carry no tag).
+static unsigned next_scan_tag(ndt_map *m) {
+  m->scan_seq = (m->scan_seq + 1u) & 0x3fffffffu;
+  if (m->scan_seq == 0u) m->scan_seq = 1u;
+  return m->scan_seq;
+}
+
+static LeafParams leaf_of(const ndt_params *prm) {
+  LeafParams L;
+  L.min_pts = prm->min_pts; L.cov_unbiased = prm->cov_unbiased; L.cov_init_identity = prm->cov_init_identity;
+  L.eig_mult = prm->eig_mult;
+  return L;
+}
+
+// What a build of n points on grid G leaves on the host: the map's view (what the match and fitness kernels read) and info.
+static void set_view(ndt_map *m, size_t n, const ndt_params *prm, const GridDims &G) {
+  MapView &V = m->view;
+  V.inv_leaf = G.inv_leaf; V.leaf = prm->resolution;
+  V.r2 = (float)((double)prm->resolution * (double)prm->resolution);
+  V.radius_inclusive = prm->radius_inclusive; V.transform_sse = prm->transform_sse;
+  V.min_bx = G.min_bx; V.min_by = G.min_by; V.div_x = G.div_x; V.div_y = G.div_y; V.gw = G.gw; V.gh = G.gh;
+  V.cent = m->cent.p; V.rec = m->rec.p; V.occ = m->occ.p; V.tiles = m->tiles.p; V.tiles_w = tiles_w_of(G); V.pt_start = m->start.p + 4;
+  V.pts = m->pts.p;
+  gauss_constants(*prm, &V.d1, &V.d2);
+  V.e_hi = pair_check_threshold(V.d2);
+  m->info.min_bx = G.min_bx; m->info.min_by = G.min_by; m->info.div_x = G.div_x; m->info.div_y = G.div_y;
+  m->info.n_points = n;
+}
+
 // Steps 2-4 of the map build for a given voxel grid: everything after the bounding box, queued on
 // the context's stream.
 static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size_t stride, const ndt_params *prm,
                        const GridDims &G, bool requeue = false) {
   hipStream_t st = ctx->stream;
-  const float inv_leaf = G.inv_leaf;
   const size_t ng = (size_t)G.div_x * G.div_y, npad = (size_t)G.gw * G.gh;
   m->ng = ng; m->npad = npad;
-  const int tiles_w = (G.div_x + 7) / 8 + 2, tiles_h = (G.div_y + 7) / 8 + 2;
-  const size_t ntile8 = (size_t)tiles_w * tiles_h;
+  const int tiles_w = tiles_w_of(G);
+  const size_t ntile8 = ntile8_of(G);
 
   // 2. buffers (grow-only across rebuilds)
   {
-    int rc; bool grown = false;
-    const size_t ntiles_ = (ng + kScanTile - 1) / kScanTile;
-    if ((rc = m->count.ensure(ctx, ng + 1, &grown))) return rc;
-    if (grown) m->count_clean = false;
-    if ((rc = m->start.ensure(ctx, ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
-    if ((rc = m->npts_grid.ensure(ctx, ng + 1))) return rc;
-    if ((rc = m->scan_state.ensure(ctx, 2 * ntiles_ + 2, &grown))) return rc;
+    bool grown = false;
+    const int rc = ensure_build_buffers(ctx, m, n, ng, npad, ntile8, &grown);
+    if (rc) return rc;
     if (grown)      // no word may carry a tag by accident
       HIP_TRY(ctx, hipMemsetAsync(m->scan_state.p, 0, m->scan_state.cap() * sizeof(unsigned long long), st));
-    if ((rc = m->perm.ensure(ctx, n + 4))) return rc;       // + 4: map_order_kernel reads four numbers at a time
-    if ((rc = m->big.ensure(ctx, n / kBigVoxel + 1))) return rc;   // voxels with > kBigVoxel points
-    if ((rc = m->occ.ensure(ctx, (ng + 31) / 32 + 2))) return rc;
-    if ((rc = m->tiles.ensure(ctx, ntile8))) return rc;
-    if ((rc = m->pts.ensure(ctx, n))) return rc;
-    if ((rc = m->cent.ensure(ctx, npad))) return rc;
-    if ((rc = m->rec.ensure(ctx, npad * 8))) return rc;
   }
   // No clearing in the steady state (every memset is a kernel of its own between the build's kernels): the per-voxel
   // counters are zero again after a complete build (map_scatter_kernel takes back what map_count_kernel added), the
@@ -819,9 +870,8 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   const int ntiles = (int)((ng + kScanTile - 1) / kScanTile);
   int *const start = m->start.p + 4;
   const int big_cap = (int)(n / kBigVoxel + 1);
-  m->scan_seq = (m->scan_seq + 1u) & 0x3fffffffu;
-  if (m->scan_seq == 0u) m->scan_seq = 1u;
-  scan_onepass_kernel<<<ntiles, kScanBlock, 0, st>>>(m->count.p, ng, m->scan_state.p, m->scan_seq, ntiles, m->counters.p + 3, start,
+  const unsigned tag = next_scan_tag(m);
+  scan_onepass_kernel<<<ntiles, kScanBlock, 0, st>>>(m->count.p, ng, m->scan_state.p, tag, ntiles, m->counters.p + 3, start,
                                                      m->big.p, m->counters.p + 2, big_cap);
   map_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, start, m->count.p, m->perm.p);
   HIP_TRY(ctx, hipGetLastError());
@@ -831,25 +881,14 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
 
   // 4. per-voxel statistics -> centroid grid + cell records + bucketed raw points
-  LeafParams L;
-  L.min_pts = prm->min_pts; L.cov_unbiased = prm->cov_unbiased; L.cov_init_identity = prm->cov_init_identity;
-  L.eig_mult = prm->eig_mult;
+  const LeafParams L = leaf_of(prm);
   // evm1 -- the end of the build, for ndt_kernel timing and for launches on other streams -- rides on this kernel's own
   // dispatch (an hipEventRecord is a packet of its own: ~6 us between two kernels, tools/launch_gap.py)
-  hipExtLaunchKernelGGL(map_finalize_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, nullptr, ctx->evm1, 0, G, L, start,
-                        m->pts.p, m->cent.p, m->rec.p, m->npts_grid.p, m->counters.p, m->occ.p, m->tiles.p, tiles_w);
+  hipExtLaunchKernelGGL(map_finalize_kernel<false>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, nullptr, ctx->evm1, 0, G, L, start,
+                        m->pts.p, m->cent.p, m->rec.p, m->npts_grid.p, m->counters.p, m->occ.p, m->tiles.p, tiles_w,
+                        (const BuildBatch *)nullptr);
   HIP_TRY(ctx, hipGetLastError());
-
-  MapView &V = m->view;
-  V.inv_leaf = inv_leaf; V.leaf = prm->resolution;
-  V.r2 = (float)((double)prm->resolution * (double)prm->resolution);
-  V.radius_inclusive = prm->radius_inclusive; V.transform_sse = prm->transform_sse;
-  V.min_bx = G.min_bx; V.min_by = G.min_by; V.div_x = G.div_x; V.div_y = G.div_y; V.gw = G.gw; V.gh = G.gh;
-  V.cent = m->cent.p; V.rec = m->rec.p; V.occ = m->occ.p; V.tiles = m->tiles.p; V.tiles_w = tiles_w; V.pt_start = start; V.pts = m->pts.p;
-  gauss_constants(*prm, &V.d1, &V.d2);
-  V.e_hi = pair_check_threshold(V.d2);
-  m->info.min_bx = G.min_bx; m->info.min_by = G.min_by; m->info.div_x = G.div_x; m->info.div_y = G.div_y;
-  m->info.n_points = n;
+  set_view(m, n, prm, G);
   return NDT_OK;
 }
 
@@ -904,15 +943,12 @@ static int build_begin(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
   return NDT_OK;
 }
 
-// Returns NDT_OK, or 1 if a build queued by build_begin used a grid that turned out wrong and has been queued again.
-static int build_end(ndt_ctx *ctx, ndt_map *m) {
-  hipStream_t st = ctx->stream;
-  const ndt_params *prm = &m->prm;
-  m->pending = false;
-  ctx->pending_map = nullptr;
-  const unsigned *hb = ctx->h_bounds.p;          // pinned
-  HIP_TRY(ctx, hipEventSynchronize(ctx->evb));
-  if (hb[0] == 0xffffffffu) return fail(ctx, NDT_E_ARG, "ndt_map_build: no finite points");
+// The voxel grid of a build from its cloud's bounding box hb (min x, min y, max x, max y, order-encoded: map_minmax_kernel)
+// -- the rule of both build paths.  prev: the grid of the map's previous build at this leaf size (what ndt_map_rebuild_begin
+// queued ahead), or nullptr.  ndt_params::grid_margin: prev is kept (*same) if it contains the cloud's box and is not much
+// wider; otherwise the grid is the box widened by the margin.  NDT_E_GRID (text: `who`: ...) beyond 2^28 cells.
+static int grid_of_box(ndt_ctx *ctx, const unsigned *hb, const ndt_params *prm, const GridDims *prev, GridDims *out, bool *same_out,
+                       const std::string &who) {
   const float inv_leaf = 1.0f / prm->resolution;
   const float mnx = ord2f(hb[0]), mny = ord2f(hb[1]), mxx = ord2f(hb[2]), mxy = ord2f(hb[3]);
   GridDims G;
@@ -924,20 +960,35 @@ static int build_end(ndt_ctx *ctx, ndt_map *m) {
   // ndt_params::grid_margin: the grid queued ahead is good if it contains the cloud's box and is not much wider
   const int mg = prm->grid_margin > 0 ? (prm->grid_margin < 4096 ? prm->grid_margin : 4096) : 0;
   bool same = false;
-  if (m->pend_queued) {
-    const GridDims &S = m->grid;
+  if (prev) {
+    const GridDims &S = *prev;
     const long long lo_x = (long long)G.min_bx - S.min_bx, lo_y = (long long)G.min_by - S.min_by;       // slack on the low sides
     const long long hi_x = ((long long)S.min_bx + S.div_x) - ((long long)G.min_bx + dx);
     const long long hi_y = ((long long)S.min_by + S.div_y) - ((long long)G.min_by + dy);
     same = lo_x >= 0 && lo_y >= 0 && hi_x >= 0 && hi_y >= 0 && lo_x <= 2 * mg && lo_y <= 2 * mg && hi_x <= 2 * mg && hi_y <= 2 * mg;
   }
-  if (same) G = m->grid;
+  if (same) G = *prev;
   else {
     G.min_bx -= mg; G.min_by -= mg; dx += 2 * mg; dy += 2 * mg;
     if (dx > (1LL << 28) || dy > (1LL << 28) || dx * dy > (1LL << 28))      // (each factor first: the product of two 2^32s overflows)
-      return fail(ctx, NDT_E_GRID, "ndt_map_build: voxel grid larger than 2^28 cells");
+      return fail(ctx, NDT_E_GRID, who + ": voxel grid larger than 2^28 cells");
     G.div_x = (int)dx; G.div_y = (int)dy; G.gw = G.div_x + 4; G.gh = G.div_y + 4;
   }
+  *out = G; *same_out = same;
+  return NDT_OK;
+}
+
+// Returns NDT_OK, or 1 if a build queued by build_begin used a grid that turned out wrong and has been queued again.
+static int build_end(ndt_ctx *ctx, ndt_map *m) {
+  hipStream_t st = ctx->stream;
+  const ndt_params *prm = &m->prm;
+  m->pending = false;
+  ctx->pending_map = nullptr;
+  const unsigned *hb = ctx->h_bounds.p;          // pinned
+  HIP_TRY(ctx, hipEventSynchronize(ctx->evb));
+  if (hb[0] == 0xffffffffu) return fail(ctx, NDT_E_ARG, "ndt_map_build: no finite points");
+  GridDims G; bool same = false;
+  { const int rc = grid_of_box(ctx, hb, prm, m->pend_queued ? &m->grid : nullptr, &G, &same, "ndt_map_build"); if (rc) return rc; }
   int redone = 0;
   if (!same) {
     if (m->pend_queued) {
@@ -963,6 +1014,23 @@ static int map_build_impl(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, s
   return rc < 0 ? rc : NDT_OK;
 }
 
+// A new map of ctx with the buffers every build path expects: map_minmax_kernel's running box at its start values, the
+// build's small counters.
+static int new_map(ndt_ctx *ctx, ndt_map **out) {
+  ndt_map *m = new (std::nothrow) ndt_map();
+  if (!m) return NDT_E_NOMEM;
+  m->ctx = ctx;
+  m->device = ctx->device;
+  const unsigned init_b[16] = {0xffffffffu, 0xffffffffu, 0u, 0u};     // running bounding box, result, done-counter (map_minmax_kernel)
+  int rc = m->bounds.alloc(ctx, sizeof(init_b));
+  const hipError_t e = rc ? hipSuccess : hipMemcpy(m->bounds.p, init_b, sizeof(init_b), hipMemcpyHostToDevice);
+  if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, std::string("ndt_map_build: hipMemcpy: ") + hipGetErrorString(e));
+  if (rc == NDT_OK) rc = m->counters.alloc(ctx, 4 * sizeof(int));
+  if (rc) { ndt_map_destroy(m); return rc; }
+  *out = m;
+  return NDT_OK;
+}
+
 int ndt_map_build_dev(ndt_ctx *ctx, const float *xy, size_t n, size_t stride, const ndt_params *prm,
                       ndt_map **pmap) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
@@ -974,16 +1042,8 @@ int ndt_map_build_dev(ndt_ctx *ctx, const float *xy, size_t n, size_t stride, co
   ndt_map *m = *pmap;
   const bool fresh = (m == nullptr);
   if (fresh) {
-    m = new (std::nothrow) ndt_map();
-    if (!m) return NDT_E_NOMEM;
-    m->ctx = ctx;
-    m->device = ctx->device;
-    const unsigned init_b[16] = {0xffffffffu, 0xffffffffu, 0u, 0u};     // running bounding box, result, done-counter (map_minmax_kernel)
-    int rc = m->bounds.alloc(ctx, sizeof(init_b));
-    const hipError_t e = rc ? hipSuccess : hipMemcpy(m->bounds.p, init_b, sizeof(init_b), hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, std::string("ndt_map_build: hipMemcpy: ") + hipGetErrorString(e));
-    if (rc == NDT_OK) rc = m->counters.alloc(ctx, 4 * sizeof(int));
-    if (rc) { ndt_map_destroy(m); return rc; }
+    const int rc = new_map(ctx, &m);
+    if (rc) return rc;
   }
   const int rc = map_build_impl(ctx, m, xy, n, stride, prm);
   if (rc) {
@@ -1034,6 +1094,225 @@ int ndt_map_build(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, c
   rc = ndt_map_build_dev(ctx, (const float *)stage.p, n, stride, prm, pmap);
   if (rc == NDT_OK) { hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }   // host-pointer form: synchronous
   if (*pmap) (*pmap)->xy_stage = std::move(stage);
+  return rc;
+}
+
+// ---- batched builds (ndt_map_build_batch_dev / ndt_map_build_batch) ----
+
+// The synchronous refusals of a batched build: nothing changed, nothing created, nothing queued.
+static int check_build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, size_t stride, int n_maps, const ndt_params *prm,
+                             ndt_map **maps, const std::string &fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (n_maps < 1) return fail(ctx, NDT_E_ARG, fn + ": n_maps < 1");
+  if (!xy || !n || !prm || !maps) return fail(ctx, NDT_E_ARG, fn + ": NULL array (xy, n, prm or maps)");
+  if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, fn + ": bad stride (need stride_bytes >= 8 and % 8 == 0)");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, fn + ": ndt_map_rebuild_end is still owed for a map of this context");
+  std::vector<std::pair<const ndt_map *, int>> seen;
+  for (int s = 0; s < n_maps; ++s) {
+    const std::string which = fn + ": map " + std::to_string(s);
+    if (!xy[s]) return fail(ctx, NDT_E_ARG, which + ": NULL cloud");
+    if (n[s] == 0) return fail(ctx, NDT_E_ARG, which + ": no points (n == 0)");
+    if (n[s] > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, which + ": more than 2^31 points");
+    if (!(prm[s].resolution > 0)) return fail(ctx, NDT_E_ARG, which + ": resolution <= 0");
+    if (!maps[s]) continue;
+    if (maps[s]->ctx != ctx) return fail(ctx, NDT_E_ARG, which + " belongs to another context");
+    seen.emplace_back(maps[s], s);
+  }
+  std::sort(seen.begin(), seen.end());
+  int dup = -1, first = -1;                             // the first index that repeats an earlier map, and that map's first index
+  for (size_t k = 1; k < seen.size(); ++k)             // (sorted: a map's indices in ascending order; k the second of its map)
+    if (seen[k].first == seen[k - 1].first && (k < 2 || seen[k - 2].first != seen[k].first) && (dup < 0 || seen[k].second < dup)) {
+      dup = seen[k].second;
+      first = seen[k - 1].second;
+    }
+  if (dup >= 0)
+    return fail(ctx, NDT_E_ARG, fn + ": map " + std::to_string(dup) + " is map " + std::to_string(first) + " again");
+  return NDT_OK;
+}
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// One set of launches for every map: the bounding boxes (one kernel, ONE read-back and host wait), the grids by the rule of
+// the single-map path (grid_of_box, with each map's previous grid), one job-table upload, then each kernel of the chain once.
+// Each map comes out as ndt_map_build_dev would leave it.
+static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, size_t stride, int n_maps, const ndt_params *prm,
+                       ndt_map **maps, const std::string &fn) {
+  hipStream_t st = ctx->stream;
+  const size_t S = (size_t)n_maps, npre = S + 1;
+  // staging / device table: [BuildBatch | BoxJob x S | minmax prefixes] [BuildJob x S | prefixes of the other kernels]; the
+  // first part goes up ahead of the boxes, the second (the job table proper) once the grids are known
+  const size_t o_box = align256(sizeof(BuildBatch)), o_pre0 = o_box + S * sizeof(BoxJob), o_jobs = align256(o_pre0 + npre * sizeof(unsigned));
+  const size_t o_pre = o_jobs + align256(S * sizeof(BuildJob)), bytes = o_pre + (kBbKernels - 1) * npre * sizeof(unsigned);
+  int rc;
+  if (!ctx->ev_bb) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_bb, hipEventDisableTiming));
+  if (ctx->bb_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_bb)); ctx->bb_pending = false; }
+  if ((rc = ctx->h_bb.ensure(ctx, bytes))) return rc;
+  if ((rc = ctx->d_bb.ensure(ctx, bytes))) return rc;
+  if ((rc = ctx->h_boxes.ensure(ctx, 16 * S))) return rc;
+  {
+    bool grown = false;
+    if ((rc = ctx->d_boxes.ensure(ctx, 16 * (S + 1), &grown))) return rc;
+    if (grown) {                                       // every map's running box at its start values (map_minmax_kernel)
+      std::vector<unsigned> init(ctx->d_boxes.cap(), 0u);
+      for (size_t w = 16; w + 16 <= init.size(); w += 16) init[w] = init[w + 1] = 0xffffffffu;
+      HIP_TRY(ctx, hipMemcpy(ctx->d_boxes.p, init.data(), init.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    }
+  }
+  unsigned char *h = ctx->h_bb.p, *d = ctx->d_bb.p;
+  BuildBatch &BB = *(BuildBatch *)h;
+  const BuildBatch *dbb = (const BuildBatch *)d;
+  BoxJob *hbox = (BoxJob *)(h + o_box);
+  BuildJob *hjob = (BuildJob *)(h + o_jobs);
+  unsigned *hpre[kBbKernels];
+  BB.box_jobs = (const BoxJob *)(d + o_box); BB.jobs = (const BuildJob *)(d + o_jobs);
+  hpre[kBbMinmax] = (unsigned *)(h + o_pre0); BB.pre[kBbMinmax] = (const unsigned *)(d + o_pre0);
+  for (int k = 1; k < kBbKernels; ++k) {
+    hpre[k] = (unsigned *)(h + o_pre) + (k - 1) * npre;
+    BB.pre[k] = (const unsigned *)(d + o_pre) + (k - 1) * npre;
+  }
+  BB.boxes = ctx->d_boxes.p + 16; BB.ticket = (int *)ctx->d_boxes.p; BB.n_maps = n_maps;
+  // a launch's work-items fit in 32 bits (blocks x block size, summed over the maps)
+  auto prefixes = [&](int k, int block, auto &&blocks_of) -> int {
+    unsigned long long tot = 0;
+    for (size_t s = 0; s < S; ++s) {
+      hpre[k][s] = (unsigned)tot;
+      tot += (unsigned long long)blocks_of(s);
+      if (tot * (unsigned long long)block > 0xffffffffull)
+        return fail(ctx, k <= kBbCount || k == kBbScatter ? NDT_E_ARG : NDT_E_GRID, fn + ": the maps of the call need more than 2^32 work-items in one kernel");
+    }
+    hpre[k][S] = (unsigned)tot;
+    return NDT_OK;
+  };
+  if ((rc = prefixes(kBbMinmax, 256, [&](size_t s) { return grid_for(n[s], 256 * 32, 128); }))) return rc;
+  if ((rc = prefixes(kBbCount, 256, [&](size_t s) { return grid_for(n[s], 256); }))) return rc;
+  if ((rc = prefixes(kBbScatter, 256, [&](size_t s) { return grid_for(n[s], 256); }))) return rc;
+
+  // 1. the bounding boxes of all clouds, read back with one copy and one wait
+  for (size_t s = 0; s < S; ++s) { hbox[s].xy = xy[s]; hbox[s].n = n[s]; }
+  HIP_TRY(ctx, hipEventRecord(ctx->evm0, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d, h, o_jobs, hipMemcpyHostToDevice, st));
+  map_minmax_kernel<true><<<hpre[kBbMinmax][S], 256, 0, st>>>(nullptr, stride, 0, nullptr, nullptr, dbb);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_boxes.p, ctx->d_boxes.p + 16, 16 * S * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipEventRecord(ctx->evb, st));
+  HIP_TRY(ctx, hipEventSynchronize(ctx->evb));
+
+  // 2. the grids; the refusals that need the boxes change nothing either
+  std::vector<GridDims> grids(S);
+  for (size_t s = 0; s < S; ++s) {
+    const std::string which = fn + ": map " + std::to_string(s);
+    const unsigned *hb = ctx->h_boxes.p + 16 * s + 4;
+    if (hb[0] == 0xffffffffu) return fail(ctx, NDT_E_ARG, which + ": no finite points");
+    const ndt_map *m = maps[s];
+    const bool prev = m && m->have_grid && m->grid.inv_leaf == 1.0f / prm[s].resolution;   // (what ndt_map_rebuild_begin would queue ahead)
+    bool same = false;
+    if ((rc = grid_of_box(ctx, hb, &prm[s], prev ? &m->grid : nullptr, &grids[s], &same, which))) return rc;
+  }
+  auto ng_of = [&](size_t s) { return (size_t)grids[s].div_x * grids[s].div_y; };
+  auto big_cap_of = [&](size_t s) { return (int)(n[s] / kBigVoxel + 1); };
+  auto small_of = [&](size_t s) { return (unsigned)((ng_of(s) + kOrderVoxPerBlock - 1) / kOrderVoxPerBlock); };
+  if ((rc = prefixes(kBbScan, kScanBlock, [&](size_t s) { return (ng_of(s) + kScanTile - 1) / kScanTile; }))) return rc;
+  if ((rc = prefixes(kBbOrder, 256, [&](size_t s) {
+         return (size_t)small_of(s) + std::min<size_t>(kBigBlocks, ((size_t)big_cap_of(s) + kBigWavesPerBlock - 1) / kBigWavesPerBlock); })))
+    return rc;
+  if ((rc = prefixes(kBbFinalize, 256, [&](size_t s) { return (ng_of(s) + 255) / 256; }))) return rc;
+
+  // 3. the maps: new ones created, every one's readers waited for as build_begin does, buffers, jobs
+  std::vector<ndt_map *> mp(S, nullptr), made;
+  auto failed = [&](int code) {                        // a HIP / allocation failure from here on: as ndt_map_build_dev
+    for (size_t s = 0; s < S; ++s)
+      if (maps[s]) { mp[s]->have_grid = false; mp[s]->count_clean = false; }
+    for (ndt_map *m : made) ndt_map_destroy(m);
+    return code;
+  };
+  for (size_t s = 0; s < S; ++s) {
+    if (maps[s]) { mp[s] = maps[s]; continue; }
+    if ((rc = new_map(ctx, &mp[s]))) return failed(rc);
+    made.push_back(mp[s]);
+  }
+  for (size_t s = 0; s < S; ++s) {
+    ndt_map *m = mp[s];
+    const GridDims &G = grids[s];
+    if ((rc = wait_for_readers(ctx, m, st, /*deferred_only=*/true))) return failed(rc);
+    { std::lock_guard<std::mutex> lk(g_live_mu); m->readers.clear(); }
+    const size_t ng = ng_of(s), npad = (size_t)G.gw * G.gh, ntile8 = ntile8_of(G);
+    bool state_grown = false;
+    if ((rc = ensure_build_buffers(ctx, m, n[s], ng, npad, ntile8, &state_grown))) return failed(rc);
+    BuildJob &J = hjob[s];
+    J.xy = xy[s]; J.n = n[s]; J.G = G; J.L = leaf_of(&prm[s]);
+    J.count = m->count.p; J.start = m->start.p + 4; J.perm = m->perm.p; J.big = m->big.p; J.npts_grid = m->npts_grid.p;
+    J.counters = m->counters.p; J.scan_state = m->scan_state.p; J.tag = next_scan_tag(m);
+    J.ntiles = (int)((ng + kScanTile - 1) / kScanTile); J.big_cap = big_cap_of(s); J.small_blocks = small_of(s);
+    J.pts = m->pts.p; J.cent = m->cent.p; J.rec = m->rec.p; J.occ = m->occ.p; J.tiles = m->tiles.p; J.tiles_w = tiles_w_of(G);
+    J.ng = ng; J.npad = npad; J.ntile8 = ntile8;
+    J.zero_count = m->count_clean ? 0 : m->count.cap();
+    J.zero_state = state_grown ? m->scan_state.cap() : 0;
+    m->count_clean = false;
+  }
+  if ((rc = prefixes(kBbFill, 256, [&](size_t s) {
+         const BuildJob &J = hjob[s];
+         return grid_for(std::max(std::max(J.npad, J.ntile8), std::max(J.zero_count, J.zero_state)), 256); })))
+    return failed(rc);
+
+  // 4. one upload of the jobs, then each kernel of the chain once (evm1 on the last one's dispatch, as queue_build)
+  {
+    hipError_t e = hipMemcpyAsync(d + o_jobs, h + o_jobs, bytes - o_jobs, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev_bb, st);
+    if (e != hipSuccess) return failed(fail(ctx, NDT_E_HIP, fn + ": job table upload: " + hipGetErrorString(e)));
+  }
+  ctx->bb_pending = true;
+  // (the batched instances take every other argument from their map's job)
+  const GridDims G0{}; const LeafParams L0{};
+  fill_f2_kernel<true><<<hpre[kBbFill][S], 256, 0, st>>>(nullptr, 0, INFINITY, nullptr, 0, dbb);
+  map_count_kernel<true><<<hpre[kBbCount][S], 256, 0, st>>>(nullptr, stride, 0, G0, nullptr, nullptr, dbb);
+  scan_onepass_kernel<true><<<hpre[kBbScan][S], kScanBlock, 0, st>>>(nullptr, 0, nullptr, 0u, 0, nullptr, nullptr, nullptr, nullptr, 0, dbb);
+  map_scatter_kernel<true><<<hpre[kBbScatter][S], 256, 0, st>>>(nullptr, stride, 0, G0, nullptr, nullptr, nullptr, dbb);
+  map_order_kernel<true><<<hpre[kBbOrder][S], 256, 0, st>>>(nullptr, 0, 0u, nullptr, nullptr, 0, nullptr, nullptr, stride, nullptr, dbb);
+  hipExtLaunchKernelGGL(map_finalize_kernel<true>, dim3(hpre[kBbFinalize][S]), dim3(256), 0, st, nullptr, ctx->evm1, 0, G0, L0,
+                        (const int *)nullptr, (const float2 *)nullptr, (float2 *)nullptr, (double *)nullptr, (int *)nullptr, (int *)nullptr,
+                        (unsigned *)nullptr, (u64 *)nullptr, 0, dbb);
+  { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return failed(fail(ctx, NDT_E_HIP, fn + ": launch: " + hipGetErrorString(e))); }
+
+  // 5. the host side of every map: as queue_build / build_end leave it
+  for (size_t s = 0; s < S; ++s) {
+    ndt_map *m = mp[s];
+    m->prm = prm[s]; m->n = n[s]; m->info_valid = false;
+    m->pend_xy = xy[s]; m->pend_stride = stride; m->pend_queued = false;
+    m->ng = ng_of(s); m->npad = (size_t)grids[s].gw * grids[s].gh;
+    set_view(m, n[s], &prm[s], grids[s]);
+    m->grid = grids[s]; m->have_grid = true;
+    m->count_clean = true;                             // (map_scatter takes back what map_count added)
+    maps[s] = m;
+  }
+  ctx->map_ms_pending = true;
+  return NDT_OK;
+}
+
+int ndt_map_build_batch_dev(ndt_ctx *ctx, const float *const *xy_dev, const size_t *n, size_t stride, int n_maps,
+                            const ndt_params *prm, ndt_map **maps) {
+  int rc = check_build_batch(ctx, xy_dev, n, stride, n_maps, prm, maps, "ndt_map_build_batch_dev");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return build_batch(ctx, xy_dev, n, stride, n_maps, prm, maps, "ndt_map_build_batch_dev");
+}
+
+int ndt_map_build_batch(ndt_ctx *ctx, const float *const *xy_host, const size_t *n, size_t stride, int n_maps,
+                        const ndt_params *prm, ndt_map **maps) {
+  int rc = check_build_batch(ctx, xy_host, n, stride, n_maps, prm, maps, "ndt_map_build_batch");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the clouds, one after another in the context's staging (each at a 256-byte boundary)
+  std::vector<size_t> off((size_t)n_maps);
+  size_t tot = 0;
+  for (int s = 0; s < n_maps; ++s) { off[s] = tot; tot += align256(n[s] * stride); }
+  if ((rc = ctx->d_bstage.ensure(ctx, tot))) return rc;
+  std::vector<const float *> dxy((size_t)n_maps);
+  for (int s = 0; s < n_maps; ++s) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bstage.p + off[s], xy_host[s], n[s] * stride, hipMemcpyHostToDevice, ctx->stream));
+    dxy[s] = (const float *)(ctx->d_bstage.p + off[s]);
+  }
+  rc = build_batch(ctx, dxy.data(), n, stride, n_maps, prm, maps, "ndt_map_build_batch");
+  if (rc == NDT_OK) { const hipError_t e = hipStreamSynchronize(ctx->stream); if (e != hipSuccess) rc = fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }
   return rc;
 }
 

@@ -136,15 +136,22 @@ class PoseEstimator:
 
     def prepareEstimate(self):
         """First half of estimatePose: the source pre-filter and the target's rebuild.  Returns the filtered scan."""
-        filtered = self.ctx.prefilter(self.source_cloud, self.LeafSize)             # :6-10, on the device (f1)
-        # :17-19 -- the target is rebuilt on every call, as the reference does (the local map is
-        # refilled in place each scan, src/PointCloudMap.cpp:119-131)
+        filtered = self.prefilterSource()
+        self.rebuildTarget()
+        return filtered
+
+    def prefilterSource(self):
+        """src/PoseEstimator.cpp:6-10 on the device (f1): the filtered scan."""
+        return self.ctx.prefilter(self.source_cloud, self.LeafSize)
+
+    def rebuildTarget(self):
+        """src/PoseEstimator.cpp:17-19 -- the target is rebuilt on every call, as the reference does (the local map is
+        refilled in place each scan, src/PointCloudMap.cpp:119-131)."""
         if self._map is None:
             self._map = capi.Map(self.ctx, self.target_cloud, self.params)
         else:
             self._map.params = self.params
             self._map.rebuild(xy=self.target_cloud)
-        return filtered
 
     def finishEstimate(self, r):
         """Second half of estimatePose: one match record -> (cost, estPose, cov)."""
@@ -164,8 +171,9 @@ class PoseEstimator:
 
 
 def estimate_poses(estims, initPoses):
-    """estimatePose of several estimators -- independent sessions, each with its own local map -- with ONE multi-map
-    launch (capi.align_batch_multi): each estimator's first half, the launch over their maps, each one's second half.
+    """estimatePose of several estimators -- independent sessions, each with its own local map -- with ONE batched map
+    build (capi.build_maps) and ONE multi-map launch (capi.align_batch_multi): each estimator's pre-filter, the build of
+    all their targets, the launch over their maps, each one's second half.
     Returns the list of (cost, estPose, cov), in the order of `estims`; the same values as estimatePose one by one.
     The estimators must share one context and the match parameters of their maps (Resolution, StepSize,
     TransformationEpsilon, MaximumIterations and the preset's switches): a launch refuses maps that differ in them, and
@@ -177,7 +185,12 @@ def estimate_poses(estims, initPoses):
     ctx = estims[0].ctx
     if any(e.ctx is not ctx for e in estims):
         raise ValueError("estimate_poses: the estimators do not share one context")
-    filtered = [np.ascontiguousarray(e.prepareEstimate(), dtype=np.float32).reshape(-1, 2) for e in estims]
+    filtered = [np.ascontiguousarray(e.prefilterSource(), dtype=np.float32).reshape(-1, 2) for e in estims]
+    # every estimator's target in ONE batched build (ndt_map_build_batch): each map as its own rebuild would leave it
+    uniq = list({id(e): e for e in estims}.values())
+    maps = capi.build_maps(ctx, [e.target_cloud for e in uniq], [e.params for e in uniq], [e._map for e in uniq])
+    for e, m in zip(uniq, maps):
+        e._map = m
     offsets = np.zeros(len(estims) + 1, dtype=np.uint64)
     offsets[1:] = np.cumsum([len(f) for f in filtered])
     inits = np.array([[p.tx, p.ty, DEG2RAD(p.th)] for p in initPoses], dtype=np.float64).reshape(-1, 3)

@@ -1,0 +1,368 @@
+"""ndt_map_build_batch{,_dev}: many maps in one set of launches.  Every map equals its twin -- the same cloud built by
+ndt_map_build_dev (capi.Map) on its own, with the same history -- in ndt_map_info, ndt_map_export and the records of a
+multi-map launch over it, byte for byte."""
+import ctypes
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
+    from ndt_slam_amd import capi
+    return capi, capi.Context(0)
+
+
+def C1():
+    from ndt_slam_amd import synth
+    return synth.CONFIGS["C1"]
+
+
+def assert_same_map(a, b, what=""):
+    ia, ib = a.info(), b.info()
+    assert bytes(ia) == bytes(ib), (what, [getattr(ia, f) for f, _ in ia._fields_], [getattr(ib, f) for f, _ in ib._fields_])
+    ea, eb = a.export(), b.export()
+    for k in ea:
+        assert ea[k].tobytes() == eb[k].tobytes(), (what, k)
+
+
+def scans_for(n_maps, seed=0):
+    """One C1 scan per map (the scan of a C1 world from its own seed, with its initial guess)."""
+    from ndt_slam_amd import synth
+    cfg = C1()
+    parts, inits = [], []
+    for s in range(n_maps):
+        w = synth.make_map(cfg["n_map"], cfg["half"], seed=7000 + seed + s % 5)
+        scan, truth, init = synth.ScanFactory(w, cfg["half"], cfg["n_scan"]).make(s)
+        parts.append(scan); inits.append(init)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
+    return np.concatenate(parts), off, np.array(inits)
+
+
+def records(capi, ctx, maps, scans):
+    sc, off, inits = scans
+    return capi.align_batch_multi(ctx, maps, sc, off, inits).tobytes()
+
+
+def new_map_clouds():
+    from ndt_slam_amd import synth
+    cfg = C1()
+    rng = np.random.default_rng(11)
+    clouds = [synth.make_map(n, cfg["half"] * f, seed=300 + k)
+              for k, (n, f) in enumerate([(5000, 1.0), (2000, 0.5), (8000, 1.3), (12000, 2.0), (3000, 0.8), (6500, 1.7)])]
+    a = synth.make_map(4000, 10.0, seed=320)
+    clouds.append(np.concatenate([a, a + np.float32([50.0, 0.0])]))                   # two clusters 50 m apart
+    clouds.append(synth.make_map(1_000_000, 60.0, seed=321))                           # many scan tiles and big voxels
+    dense = rng.uniform(0.31, 0.59, size=(900, 2)).astype(np.float32)                  # one voxel with 900 points
+    clouds.append(np.concatenate([dense, synth.make_map(2000, 8.0, seed=322)]))
+    clouds.append(np.float32([[1.234, -5.678]]))                                       # one point
+    nanc = synth.make_map(5000, cfg["half"], seed=323).copy()
+    nanc[rng.choice(len(nanc), 300, replace=False)] = np.nan                           # NaN points mixed in
+    nanc[7] = [np.inf, 1.0]
+    clouds.append(nanc)
+    clouds.append(synth.make_map(5000, cfg["half"], seed=324) + np.float32([-200.0, 75.0]))
+    return clouds
+
+
+@pytest.fixture(scope="module")
+def new_batch(gpu):
+    capi, ctx = gpu
+    prm = capi.default_params(resolution=C1()["resolution"])
+    clouds = new_map_clouds()
+    maps = capi.build_maps(ctx, clouds, prm)
+    twins = [capi.Map(ctx, c, prm) for c in clouds]
+    return clouds, prm, maps, twins
+
+
+def test_new_maps_equal_their_twins_and_the_oracle(gpu, new_batch):
+    capi, ctx = gpu
+    from oracle import ndt_oracle as O
+    clouds, prm, maps, twins = new_batch
+    assert len(maps) == len(clouds) >= 12 and all(isinstance(m, capi.Map) and m.h for m in maps)
+    for s, (m, t) in enumerate(zip(maps, twins)):
+        assert_same_map(m, t, s)
+    assert maps[7].info().div_x * maps[7].info().div_y > 8 * 8192        # the 1M-point map spans many scan tiles
+    for s in (0, 9):                                                     # as test_map_build_matches_oracle_bit_for_bit
+        om = O.Map(clouds[s], O.default_params(resolution=C1()["resolution"]))
+        gi, oi = maps[s].info(), om.info()
+        assert (gi.min_bx, gi.min_by, gi.div_x, gi.div_y, gi.n_cells, gi.n_valid) == \
+               (oi.min_bx, oi.min_by, oi.div_x, oi.div_y, oi.n_cells, oi.n_valid)
+        g, o = maps[s].export(), om.export()
+        for k in ("idx", "npts", "cent", "mean"):
+            assert np.array_equal(g[k], o[k]), (s, k)
+        assert g["icov"] == pytest.approx(o["icov"], rel=1e-12, abs=1e-300)
+
+
+def test_records_of_a_multi_map_launch_equal_the_twins(gpu, new_batch):
+    capi, ctx = gpu
+    clouds, prm, maps, twins = new_batch
+    sc = scans_for(len(maps))
+    a, b = records(capi, ctx, maps, sc), records(capi, ctx, twins, sc)
+    assert a == b
+    recs = np.frombuffer(a, dtype=capi.RESULT_DTYPE)
+    assert np.all(recs["status"] == 0) and np.all(np.isfinite(recs["fitness"]))
+
+
+@pytest.mark.parametrize("margin", [0, 8])
+def test_history_of_sliding_clouds(gpu, margin):
+    """Twin sets through 10 steps of sliding clouds: one created (all slots NULL) and rebuilt by the batch, one by
+    ndt_map_build_dev; grids, exports and records equal at every step; then a two-phase rebuild of a batch-built map."""
+    import torch
+    capi, ctx = gpu
+    from ndt_slam_amd import synth
+    cfg = C1()
+    prm = capi.default_params(resolution=cfg["resolution"], grid_margin=margin)
+    base = [synth.make_map(cfg["n_map"], cfg["half"], seed=400 + k) for k in range(5)]
+    sc = scans_for(5, seed=50)
+    batch, twins, grids = [None] * 5, None, []
+    for step in range(10):
+        clouds = [c + np.float32([0.37 * step * (1 + k % 2), -0.21 * step * (k % 3)]) for k, c in enumerate(base)]
+        batch = capi.build_maps(ctx, clouds, prm, batch)
+        if twins is None:
+            twins = [capi.Map(ctx, c, prm) for c in clouds]
+        else:
+            for t, c in zip(twins, clouds):
+                t.rebuild(xy=c)
+        for s in range(5):
+            assert_same_map(batch[s], twins[s], (step, s))
+        assert records(capi, ctx, batch, sc) == records(capi, ctx, twins, sc), step
+        grids.append(tuple((m.info().min_bx, m.info().div_x) for m in batch))
+    moved = sum(g1 != g0 for g0, g1 in zip(grids, grids[1:]))
+    if margin:
+        assert 0 < moved < len(grids) - 1                 # some steps cross the margin, some keep the grid
+    else:
+        assert moved == len(grids) - 1
+    dev = torch.device("cuda", 0)
+    nxt = torch.from_numpy(np.ascontiguousarray(base[1] + np.float32([4.1, 0.3]))).to(dev)
+    torch.cuda.synchronize()
+    for m in (batch[1], twins[1]):
+        m.rebuild_begin(nxt.data_ptr(), len(nxt))
+        m.rebuild_end()
+    assert_same_map(batch[1], twins[1], "two-phase")
+    assert records(capi, ctx, batch, sc) == records(capi, ctx, twins, sc)
+
+
+def test_mixed_call_with_per_map_parameters(gpu):
+    capi, ctx = gpu
+    from ndt_slam_amd import synth
+    cfg = C1()
+    r = cfg["resolution"]
+    prms = [capi.default_params(resolution=r), capi.default_params(resolution=0.5),
+            capi.default_params(resolution=r, min_pts=3), capi.default_params(resolution=0.5, min_pts=10),
+            capi.default_params(resolution=r, cov_unbiased=1), capi.default_params(resolution=r, cov_init_identity=0),
+            capi.default_params("pcl110", resolution=r), capi.default_params("pcl18", resolution=0.5),
+            capi.default_params("pcl_new", resolution=r, grid_margin=4)]
+    old = [synth.make_map(cfg["n_map"], cfg["half"], seed=500 + k) for k in range(len(prms))]
+    new = [c + np.float32([0.9, -0.4]) for c in old]
+    existing = {0, 2, 3, 6, 8}
+    slots, twins = [], []
+    for s, p in enumerate(prms):
+        if s in existing:                                 # built before, by either path
+            m = capi.Map(ctx, old[s], p) if s % 2 == 0 else capi.build_maps(ctx, [old[s]], p)[0]
+            t = capi.Map(ctx, old[s], p)
+            t.rebuild(xy=new[s])
+            slots.append(m)
+        else:
+            t = capi.Map(ctx, new[s], p)
+            slots.append(None)
+        twins.append(t)
+    got = capi.build_maps(ctx, new, prms, slots)
+    for s in range(len(prms)):
+        if s in existing:
+            assert got[s] is slots[s]
+        assert_same_map(got[s], twins[s], s)
+        assert got[s].params is prms[s]
+
+
+def call_raw(capi, ctx_h, xys, ns, stride, prms, maps, n_maps=None):
+    k = max(len(ns), 1)
+    xy = (ctypes.c_void_p * k)(*xys)
+    n = (ctypes.c_size_t * k)(*ns)
+    P = (capi.Params * k)(*prms)
+    mp = (ctypes.c_void_p * k)(*[(m.h.value if m is not None else None) for m in maps])
+    rc = capi.lib().ndt_map_build_batch(ctx_h, xy, n, stride, len(ns) if n_maps is None else n_maps, P, mp)
+    return rc, capi.lib().ndt_last_error(ctx_h).decode(), list(mp)
+
+
+def test_refusals(gpu):
+    import torch
+    capi, ctx = gpu
+    from ndt_slam_amd import synth
+    cfg = C1()
+    prm = capi.default_params(resolution=cfg["resolution"])
+    clouds = [synth.make_map(cfg["n_map"], cfg["half"], seed=600 + k) for k in range(4)]
+    have = capi.build_maps(ctx, clouds[:2], prm)
+    before = [m.export() for m in have]
+    ptr = [c.ctypes.data for c in clouds]
+    ns = [len(c) for c in clouds]
+    P = [prm] * 4
+    slots = [have[0], None, have[1], None]
+
+    def refused(code, text, xys=ptr, n=ns, stride=8, prms=P, maps=slots, n_maps=None, ctx_h=ctx.h):
+        rc, err, out = call_raw(capi, ctx_h, xys, n, stride, prms, maps, n_maps)
+        assert rc == code and text in err, (rc, err)
+        assert all(out[s] is None for s, m in enumerate(maps) if m is None)      # no map created
+        return err
+
+    refused(capi.NDT_E_ARG, "null context", ctx_h=None)
+    refused(capi.NDT_E_ARG, "n_maps < 1", n_maps=0)
+    rc = capi.lib().ndt_map_build_batch(ctx.h, None, (ctypes.c_size_t * 1)(5), 8, 1, None, None)
+    assert rc == capi.NDT_E_ARG and "NULL array" in capi.lib().ndt_last_error(ctx.h).decode()
+    refused(capi.NDT_E_ARG, "map 2: NULL cloud", xys=[ptr[0], ptr[1], None, None])
+    refused(capi.NDT_E_ARG, "map 1: no points", n=[ns[0], 0, ns[2], 0])
+    refused(capi.NDT_E_ARG, "map 3: more than 2^31 points", n=ns[:3] + [2 ** 31])
+    refused(capi.NDT_E_ARG, "bad stride", stride=12)
+    refused(capi.NDT_E_ARG, "map 2: resolution <= 0", prms=[prm, prm, capi.default_params(resolution=0.0), prm])
+    ctx2 = capi.Context(0)
+    other = capi.Map(ctx2, clouds[3], prm)
+    refused(capi.NDT_E_ARG, "map 1 belongs to another context", maps=[have[0], other, have[1], None])
+    refused(capi.NDT_E_ARG, "map 2 is map 0 again", maps=[have[0], None, have[0], None])
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(clouds[0]).to(dev)
+    torch.cuda.synchronize()
+    have[0].rebuild_begin(d.data_ptr(), len(d))
+    refused(capi.NDT_E_ARG, "ndt_map_rebuild_end is still owed")
+    have[0].rebuild_end()
+    before[0] = have[0].export()                                     # (rebuilt from the same cloud)
+    # behind the box read-back: nothing changed either
+    allnan = np.full((100, 2), np.nan, np.float32)
+    refused(capi.NDT_E_ARG, "map 2: no finite points", xys=[ptr[0], ptr[1], allnan.ctypes.data, ptr[3]], n=ns[:2] + [100, ns[3]])
+    far = np.float32([[0.0, 0.0], [1.0e4, 1.0e4]])
+    refused(capi.NDT_E_GRID, "map 1: voxel grid larger than 2^28 cells", xys=[ptr[0], far.ctypes.data, ptr[2], ptr[3]],
+            n=[ns[0], 2, ns[2], ns[3]])
+    for m, e in zip(have, before):
+        got = m.export()
+        assert all(got[k].tobytes() == e[k].tobytes() for k in e)
+    # the context still builds and matches
+    maps = capi.build_maps(ctx, clouds, prm, slots)
+    twins = [capi.Map(ctx, c, prm) for c in clouds]
+    for m, t in zip(maps, twins):
+        assert_same_map(m, t)
+    sc = scans_for(4, seed=60)
+    assert records(capi, ctx, maps, sc) == records(capi, ctx, twins, sc)
+
+
+def test_deferred_fitness_and_a_batched_rebuild_behind_the_launch(gpu):
+    """NDT_OPT_DEFER_FITNESS: maps 1 and 2 rebuilt by one batched call right behind a multi-map launch over them; the
+    records equal the plain launch's."""
+    import torch
+    capi, _ = gpu
+    from ndt_slam_amd import synth
+    cfg = C1()
+    prm = capi.default_params(resolution=cfg["resolution"])
+    clouds = [synth.make_map(cfg["n_map"], cfg["half"], seed=900 + k) for k in range(3)]
+    parts, inits = [], []
+    map_of = np.array([b % 3 for b in range(48)], np.int32)
+    for b in range(48):
+        scan, truth, init = synth.ScanFactory(clouds[map_of[b]], cfg["half"], cfg["n_scan"]).make(b)
+        parts.append(scan); inits.append(init)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
+    scans, inits = np.concatenate(parts), np.array(inits)
+    dev = torch.device("cuda", 0)
+    moved = [torch.from_numpy(np.ascontiguousarray(clouds[k] + np.float32(0.7 * k), dtype=np.float32)).to(dev) for k in (1, 2)]
+
+    def run(defer):
+        ctx = capi.Context(0)
+        if defer:
+            ctx.set_option(capi.OPT_DEFER_FITNESS, 1)
+        maps = capi.build_maps(ctx, clouds, prm)
+        d_sc = torch.from_numpy(scans).to(dev)
+        d_of = torch.from_numpy(off.astype(np.int64)).to(dev)
+        d_in = torch.from_numpy(inits).to(dev)
+        d_mo = torch.from_numpy(map_of).to(dev)
+        out = torch.zeros(48 * capi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ctx.align_batch_multi_dev(maps, d_mo.data_ptr(), d_sc.data_ptr(), d_of.data_ptr(), 48, len(scans),
+                                  d_in.data_ptr(), out.data_ptr())
+        ctx.build_maps_dev([t.data_ptr() for t in moved], [len(t) for t in moved], prm, maps[1:])   # at once, no wait
+        ctx.wait_launch(0, None)
+        torch.cuda.ExternalStream(ctx.stream).synchronize()
+        return np.frombuffer(out.cpu().numpy().tobytes(), dtype=capi.RESULT_DTYPE).copy()
+
+    plain, deferred = run(False), run(True)
+    assert np.all(plain["status"] == 0)
+    assert plain.tobytes() == deferred.tobytes()
+
+
+def test_256_maps_in_one_call(gpu):
+    import torch
+    capi, ctx = gpu
+    from ndt_slam_amd import synth
+    cfg = C1()
+    prm = capi.default_params(resolution=cfg["resolution"])
+    clouds = [synth.make_map(cfg["n_map"], cfg["half"], seed=10_000 + s) for s in range(256)]
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(c).to(dev) for c in clouds]
+    torch.cuda.synchronize()
+    maps = ctx.build_maps_dev([t.data_ptr() for t in d], [len(t) for t in d], prm)
+    torch.cuda.ExternalStream(ctx.stream).synchronize()
+    map_ms, _ = ctx.last_timing()
+    assert map_ms > 0
+    for s, c in enumerate(clouds):
+        assert_same_map(maps[s], capi.Map(ctx, c, prm), s)
+
+
+def test_estimate_poses_builds_once_and_equals_estimate_pose(gpu, monkeypatch):
+    capi, ctx = gpu
+    from ndt_slam_amd import synth
+    from ndt_slam_amd.pose_estimator import Pose2D, PoseEstimator, Scan2D, estimate_poses, RAD2DEG
+    cfg = C1()
+    setups = []
+    for k in range(4):
+        c = synth.make_map(cfg["n_map"], cfg["half"], seed=1300 + k)
+        scan, truth, init = synth.ScanFactory(c, cfg["half"], cfg["n_scan"]).make(k)
+        setups.append((Scan2D(scan.astype(np.float64)), c, Pose2D(init[0], init[1], RAD2DEG(init[2]))))
+    calls = []
+    real = capi.build_maps
+
+    def counted(*a, **k):
+        calls.append(len(a[1]))
+        return real(*a, **k)
+
+    monkeypatch.setattr(capi, "build_maps", counted)
+    es = []
+    for sc, c, _ in setups:
+        e = PoseEstimator(ctx=ctx, Resolution=cfg["resolution"], LeafSize=0.05)
+        e.setScanPair(sc, c)
+        es.append(e)
+    for rnd in range(2):                                  # round 0: every map new; round 1: every map rebuilt in place
+        got = estimate_poses(es, [p for _, _, p in setups])
+        assert calls == [4] * (rnd + 1)
+        for e, (_, _, p), (cost, est, cov) in zip(es, setups, got):
+            c1, e1, v1 = e.estimatePose(p)
+            assert cost == c1 and (est.tx, est.ty, est.th) == (e1.tx, e1.ty, e1.th)
+            assert np.array_equal(cov, v1, equal_nan=True)
+
+
+def test_lockstep_replay_builds_once_per_step(gpu, tmp_path, monkeypatch):
+    capi, ctx = gpu
+    from ndt_slam_amd import replay, synth
+    logs = []
+    for i, (seed, n) in enumerate(((33, 14), (34, 9), (35, 12), (36, 6))):
+        recs, _ = synth.replay_records(n_frames=n, n_beams=181, step=0.6, seed=seed)
+        replay.write_log(tmp_path / ("log%d.txt" % i), recs)
+        logs.append(replay.read_log(tmp_path / ("log%d.txt" % i), sidelidar=False))
+    params = dict(replay.LAUNCH_PARAMS, end_frame=20, sepThre=5.0)
+    for i, log in enumerate(logs):
+        replay.SlamLauncher(ctx, **params).run(log, poses_name=tmp_path / ("solo%d.txt" % i),
+                                               map_name=str(tmp_path / ("solo%d.pcd" % i)))
+    logs = [replay.read_log(tmp_path / ("log%d.txt" % i), sidelidar=False) for i in range(4)]
+    calls = []
+    real = capi.build_maps
+
+    def counted(*a, **k):
+        calls.append(len(a[1]))
+        return real(*a, **k)
+
+    monkeypatch.setattr(capi, "build_maps", counted)
+    replay.run_sessions(ctx, logs, poses_names=[tmp_path / ("multi%d.txt" % i) for i in range(4)],
+                        map_names=[str(tmp_path / ("multi%d.pcd" % i)) for i in range(4)], **params)
+    for i in range(4):
+        assert open(tmp_path / ("multi%d.txt" % i)).read() == open(tmp_path / ("solo%d.txt" % i)).read()
+        assert open(tmp_path / ("multi%d.pcd" % i)).read() == open(tmp_path / ("solo%d.pcd" % i)).read()
+    # steps 1 .. 13 need a match: one batched build each, over the sessions still running
+    assert calls == [sum(1 for n in (14, 9, 12, 6) if k < n) for k in range(1, 14)]
