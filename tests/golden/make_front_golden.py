@@ -5,6 +5,13 @@ As for c1_golden.npz the reference ships nothing to compare with and its own sou
 ROS / Eigen, so the vectors come from this repo's CPU restatement (oracle/ndt_oracle.c, ndt_oracle_octree.c) and
 pin it -- and the HIP path -- against silent drift; they are NOT outputs of the reference.
 
+Since then three of these rows have been pinned by the reference's own code in a file of their own,
+front_ref_golden.npz (make_front_ref_golden.{cpp,py}): odometry prediction and EKF fusion (f2), the scan resampler (f4)
+and growMap's scan-to-map transform -- their sources compile without PCL.  Still restatement-only, here and
+everywhere: f1 (the source pre-filter, PCL's ApproximateVoxelGrid) and f3 (the local-map assembly: PCL's octree change
+detector, remove_neighborPoint through PCFilter.h).  The prediction / fusion vectors below stay as they are (the oracle
+that makes them is itself held to the reference's build now).
+
 Contents: a submap of registered scans with a moving object -> PCFilter::difference_extraction of one triple
 (indices in the octree's leaf order), Submap::makeMap for three flag combinations, Submap::filterPoints of the
 result; odometry prediction + EKF fusion vectors; and the poses of a short replay of a synthetic log.

@@ -16,6 +16,30 @@ def rot(deg):
     return np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
 
 
+def numpy_odometry_covariance(del_time, coe_vel, coe_omega, motion, last, lc):
+    """PoseFuser::calOdometryCovariance (src/PoseFuser.cpp:38-61) written with numpy matrices: the independent twin of
+    the oracle's f2_odo_cov.  (tests/test_front_ref_pins.py holds it against the reference's own build.)"""
+    dt = del_time
+    v = np.hypot(motion[0], motion[1]) / dt; om = np.deg2rad(motion[2] / dt)
+    th = np.deg2rad(last[2])
+    F = np.array([[1, 0, -v * dt * np.sin(th)], [0, 1, v * dt * np.cos(th)], [0, 0, 1]])
+    Am = np.array([[dt * np.cos(th), 0], [dt * np.sin(th), 0], [0, dt]])
+    M = np.diag([coe_vel * v * v, coe_omega * om * om])
+    return F @ lc @ F.T + Am @ M @ Am.T
+
+
+def numpy_kalman_update(del_time, coe_vel, coe_omega, coe_ndt_cov, est_rad, H, pred, motion, last, lc):
+    """PoseFuser::fusePose (src/PoseFuser.cpp:3-36) behind Qmat = (-H)^-1 * coeNDTCov (src/PoseEstimator.cpp:57-64),
+    with numpy: -> (mu = (x, y, yaw in RADIANS), cov)."""
+    ch = numpy_odometry_covariance(del_time, coe_vel, coe_omega, motion, last, lc)
+    Q = np.linalg.inv(-np.asarray(H, float).reshape(3, 3)) * coe_ndt_cov
+    K = ch @ np.linalg.inv(Q + ch)
+    dth = (np.rad2deg(est_rad[2]) - pred[2] + 180) % 360 - 180
+    mu = K @ np.array([est_rad[0] - pred[0], est_rad[1] - pred[1], np.deg2rad(dth)]) + \
+        np.array([pred[0], pred[1], np.deg2rad(pred[2])])
+    return mu, (np.eye(3) - K) @ ch
+
+
 def test_prediction_is_the_odometry_increment_applied_to_the_last_pose(oracle):
     rng = np.random.default_rng(1)
     for _ in range(50):
@@ -50,19 +74,8 @@ def test_fusion_matches_a_numpy_kalman_update(oracle):
         est_rad[2] = (est_rad[2] + np.pi) % (2 * np.pi) - np.pi
         ok, fused, cov = oracle.fuse(result_record(oracle, est_rad, H), pred, motion, last, lc, prm)
         assert ok == 1
-        dt = prm.del_time
-        v = np.hypot(motion[0], motion[1]) / dt; om = np.deg2rad(motion[2] / dt)
-        th = np.deg2rad(last[2])
-        F = np.array([[1, 0, -v * dt * np.sin(th)], [0, 1, v * dt * np.cos(th)], [0, 0, 1]])
-        Am = np.array([[dt * np.cos(th), 0], [dt * np.sin(th), 0], [0, dt]])
-        M = np.diag([prm.coe_vel * v * v, prm.coe_omega * om * om])
-        ch = F @ lc @ F.T + Am @ M @ Am.T
-        Q = np.linalg.inv(-H) * prm.coe_ndt_cov
-        K = ch @ np.linalg.inv(Q + ch)
-        dth = (np.rad2deg(est_rad[2]) - pred[2] + 180) % 360 - 180
-        mu = K @ np.array([est_rad[0] - pred[0], est_rad[1] - pred[1], np.deg2rad(dth)]) + \
-            np.array([pred[0], pred[1], np.deg2rad(pred[2])])
-        assert cov == pytest.approx((np.eye(3) - K) @ ch, rel=1e-9, abs=1e-15)
+        mu, cov_np = numpy_kalman_update(prm.del_time, prm.coe_vel, prm.coe_omega, prm.coe_ndt_cov, est_rad, H, pred, motion, last, lc)
+        assert cov == pytest.approx(cov_np, rel=1e-9, abs=1e-15)
         assert fused[:2] == pytest.approx(mu[:2], abs=1e-10)
         assert fused[2] == pytest.approx(np.rad2deg(mu[2]), abs=1e-8)
 
