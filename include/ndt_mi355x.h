@@ -463,6 +463,65 @@ int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy_dev, size_t stride_byte
                      int n_scans, int first_submap, int newest, int remove_moving, double resol,
                      double thre_neighbor, float *out_xy_dev, uint64_t *n_out_dev, void *stream);
 
+/* The same pre-filter for B scans in host memory (scan b = points [raw_offsets[b], raw_offsets[b+1]) of raw_xy_host at
+ * stride_bytes): one upload, one ndt_prefilter_batch_dev, the offsets read back, one copy of the result.  Scan b's filtered
+ * points are [out_offsets_host[b], out_offsets_host[b+1]) of out_xy_host (packed float2; room for every input point), each
+ * byte-identical to ndt_prefilter of that scan; an empty scan stays empty (a call whose scans are all empty is valid).
+ * Synchronous.  NDT_E_ARG (nothing changed): a NULL context ("null context"), B < 1, a NULL array, a bad stride,
+ * leaf <= 0, offsets that decrease (the text names the scan). */
+int ndt_prefilter_batch(ndt_ctx *ctx, const float *raw_xy_host, size_t stride_bytes, const uint64_t *raw_offsets_host,
+                        int B, float leaf, float *out_xy_host, uint64_t *out_offsets_host);
+
+/* SURVEY.md 8f row f3 for many submaps at once -- Submap::makeMap (src/PointCloudMap.cpp:15-39) and the local map that
+ * PointCloudMap::makeLocalMap (:119-134) makes of it, for n_subs independent submaps (one per SLAM session) in ONE set of
+ * launches: the number of kernels, copies and host waits of a call does not depend on n_subs.
+ *
+ * One entry of the HOST array `subs` per submap: */
+typedef struct ndt_submap_desc {
+  const float    *scans_xy;      /* the submap's scans, already in the map frame (as ndt_make_map), points at stride_bytes */
+  const uint64_t *offsets;       /* HOST array, n_scans + 1 entries, in points of scans_xy                                 */
+  int             n_scans;
+  int             first_submap, newest, remove_moving;   /* as ndt_make_map                                                */
+  double          resol, thre_neighbor;                  /* PCFilter's, per submap                                         */
+  const float    *prev_xy;       /* p_cloud of the submap before this one (makeLocalMap :123-126) at stride_bytes, or NULL */
+  size_t          n_prev;
+} ndt_submap_desc;
+/* For submap s the call writes
+ *   cloud[s]  = points [cloud_off[s], cloud_off[s+1]) of cloud_xy: what ndt_make_map_dev gives for that submap, byte for
+ *               byte (Submap::p_cloud after makeMap);
+ *   target[s] = points [target_off[s], target_off[s+1]) of target_xy: prev[s] (n_prev points) followed by
+ *               Submap::filterPoints of cloud[s] at leaf size `leaf` -- makeLocalMap's localMap_cloud, and what
+ *               ndt_map_build_batch_dev takes as xy[s] once target_off has been read back.  The part behind the first n_prev
+ *               points is byte-identical to ndt_prefilter(cloud[s], leaf); an empty cloud[s] gives an empty filtered part;
+ *   status[s] = NDT_OK, or NDT_E_ARG when one of the submap's scan triples spans more than 2^30 voxels: that submap alone
+ *               gets empty ranges in both outputs (the single call reports this as *n_out = UINT64_MAX).
+ * Both outputs are packed float2.  With target_xy_dev == NULL (then target_off_dev must be NULL too) the call is a batched
+ * ndt_make_map_dev: leaf, prev_xy and n_prev are ignored.  One leaf per call; resol and thre_neighbor per submap.
+ *
+ * Buffer sizes, computable without a device:
+ *   cloud capacity  (points) = the sum over the submaps of their input points, offsets[n_scans] - offsets[0], counting a
+ *                              submap of a single scan TWICE (ndt_make_map appends a lone scan as the first and as the newest);
+ *   target capacity (points) = the cloud capacity + the sum of n_prev;
+ *   cloud_off, target_off: n_subs + 1 uint64 each; status: n_subs ints.
+ * The inputs (scans and previous clouds; not `subs` and the offsets, which are read before the call returns) must stay
+ * valid until the call has run on its stream; the outputs must not overlap the inputs.  Asynchronous on `stream`
+ * (NULL = the context's stream).
+ *
+ * Refusals (NDT_E_ARG, synchronous, nothing written or queued; the text names the first offending submap): a NULL context
+ * ("null context", checked first), n_subs < 1, a NULL array (subs, cloud_xy, cloud_off, status; target_xy without
+ * target_off or the reverse), a submap with n_scans < 1 or NULL scans_xy / offsets, offsets that decrease or a scan above
+ * 2^29 points, a bad stride, remove_moving with a resol that is not positive and finite, n_prev > 0 with NULL prev_xy, a
+ * target with leaf <= 0.  A call in which every submap is empty is valid and gives all-zero offsets. */
+int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride_bytes, float leaf,
+                            float *cloud_xy_dev, uint64_t *cloud_off_dev, float *target_xy_dev, uint64_t *target_off_dev,
+                            int *status_dev, void *stream);
+/* The same with every point pointer (scans_xy, prev_xy, cloud_xy, target_xy) and every result in HOST memory: one upload of
+ * all scans and previous clouds, one ndt_local_map_batch_dev, one read-back of the offsets and status, one copy of each
+ * result.  Synchronous; same capacities, same refusals. */
+int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride_bytes, float leaf,
+                        float *cloud_xy_host, uint64_t *cloud_off_host, float *target_xy_host, uint64_t *target_off_host,
+                        int *status_host);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

@@ -37,6 +37,13 @@ class FuseParams(C.Structure):
                 ("del_time", C.c_double), ("score_thre", C.c_double)]
 
 
+class SubmapDesc(C.Structure):
+    """ndt_submap_desc (include/ndt_mi355x.h): one submap of ndt_local_map_batch{,_dev}."""
+    _fields_ = [("scans_xy", C.c_void_p), ("offsets", C.c_void_p), ("n_scans", C.c_int), ("first_submap", C.c_int),
+                ("newest", C.c_int), ("remove_moving", C.c_int), ("resol", C.c_double), ("thre_neighbor", C.c_double),
+                ("prev_xy", C.c_void_p), ("n_prev", C.c_size_t)]
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -64,6 +71,7 @@ EXPORTS = [
     "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
     "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
     "ndt_align_batch_multi", "ndt_align_batch_multi_dev", "ndt_map_build_batch", "ndt_map_build_batch_dev",
+    "ndt_local_map_batch", "ndt_local_map_batch_dev", "ndt_prefilter_batch",
 ]
 
 
@@ -128,6 +136,9 @@ def lib():
     L.ndt_align_batch_multi_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, i, vp, vp, vp]
     L.ndt_map_build_batch.argtypes = [vp, vp, vp, sz, i, vp, vp]
     L.ndt_map_build_batch_dev.argtypes = [vp, vp, vp, sz, i, vp, vp]
+    L.ndt_local_map_batch.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp]
+    L.ndt_local_map_batch_dev.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.ndt_prefilter_batch.argtypes = [vp, vp, sz, vp, i, C.c_float, vp, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -301,6 +312,22 @@ class Context:
         self.check(lib().ndt_prefilter_batch_dev(self.h, raw_ptr, stride, raw_offsets_ptr, B, total_raw_points, leaf,
                                                  out_ptr, out_offsets_ptr, stream), "ndt_prefilter_batch_dev")
 
+    def prefilter_batch(self, scans, leaf):
+        """ndt_prefilter_batch: the pre-filter of every scan of a list ([n_b, 2] float32 each, empty ones allowed) in one
+        call -> the list of filtered scans, each what prefilter gives for it."""
+        scans = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in scans]
+        if not scans:
+            return []
+        B = len(scans)
+        off = np.zeros(B + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in scans])
+        allp = np.ascontiguousarray(np.concatenate(scans))
+        out = np.empty((len(allp) + 1, 2), dtype=np.float32)
+        ooff = np.zeros(B + 1, dtype=np.uint64)
+        self.check(lib().ndt_prefilter_batch(self.h, allp.ctypes.data if len(allp) else None, 8, off.ctypes.data, B, leaf,
+                                             out.ctypes.data, ooff.ctypes.data), "ndt_prefilter_batch")
+        return [out[int(ooff[b]):int(ooff[b + 1])].copy() for b in range(B)]
+
     def resample(self, xy, space, space_thre):
         """ScanPointResampler::resamplePoints on one scan ([n, 2] float64) -> resampled [m, 2] float64."""
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
@@ -364,6 +391,57 @@ class Context:
         self.check(lib().ndt_make_map_dev(self.h, scans_ptr, stride, off.ctypes.data, len(off) - 1, int(first_submap),
                                           int(newest), int(remove_moving), resol, thre_neighbor, out_ptr, n_out_ptr,
                                           stream), "ndt_make_map_dev")
+
+    def local_maps(self, items, leaf):
+        """ndt_local_map_batch: Submap::makeMap and makeLocalMap's cloud for many submaps in one call.  An item is
+        (scans, first_submap, newest, remove_moving, resol, thre_neighbor, prev_cloud): `scans` as make_map takes them,
+        prev_cloud the p_cloud of the submap before it ([n, 2] float32) or None.  Returns per item (p_cloud, target,
+        n_prev): p_cloud what make_map gives, target = prev_cloud followed by prefilter(p_cloud, leaf) (its first n_prev
+        points are prev_cloud).  Raises NdtError for a failed item (a scan triple beyond 2^30 voxels), as make_map does."""
+        items = list(items)
+        if not items:
+            return []
+        S = len(items)
+        descs = (SubmapDesc * S)()
+        keep = []                                            # the arrays the descriptors point into
+        cap_cloud = cap_prev = 0
+        for s, (scans, first, newest, remove, resol, thre, prev) in enumerate(items):
+            scans = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in scans]
+            off = np.zeros(len(scans) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x) for x in scans])
+            allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2), np.float32)
+            if len(allp) == 0:
+                allp = np.zeros((1, 2), np.float32)          # (a non-NULL address for a submap without points)
+            pv = np.zeros((0, 2), np.float32) if prev is None else np.ascontiguousarray(prev, dtype=np.float32).reshape(-1, 2)
+            keep.append((allp, off, pv))
+            descs[s] = SubmapDesc(allp.ctypes.data, off.ctypes.data, len(scans), int(first), int(newest), int(remove),
+                                  float(resol), float(thre), pv.ctypes.data if len(pv) else None, len(pv))
+            cap_cloud += (2 if len(scans) == 1 else 1) * int(off[-1])
+            cap_prev += len(pv)
+        cloud = np.empty((cap_cloud + 1, 2), dtype=np.float32)
+        target = np.empty((cap_cloud + cap_prev + 1, 2), dtype=np.float32)
+        coff, toff = np.zeros(S + 1, dtype=np.uint64), np.zeros(S + 1, dtype=np.uint64)
+        status = np.zeros(S, dtype=np.int32)
+        self.check(lib().ndt_local_map_batch(self.h, descs, S, 8, leaf, cloud.ctypes.data, coff.ctypes.data,
+                                             target.ctypes.data, toff.ctypes.data, status.ctypes.data),
+                   "ndt_local_map_batch")
+        bad = np.flatnonzero(status)
+        if len(bad):
+            raise NdtError("ndt_local_map_batch -> %d: submap %d: a scan triple spans more than 2^30 voxels"
+                           % (int(status[bad[0]]), int(bad[0])))
+        return [(cloud[int(coff[s]):int(coff[s + 1])].copy(), target[int(toff[s]):int(toff[s + 1])].copy(), len(keep[s][2]))
+                for s in range(S)]
+
+    def local_maps_dev(self, descs, leaf, cloud_ptr, cloud_off_ptr, target_ptr, target_off_ptr, status_ptr, stride=8,
+                       stream=None):
+        """ndt_local_map_batch_dev: `descs` a list of SubmapDesc (or a ctypes array of them) whose scans_xy / prev_xy are
+        device addresses and whose offsets are host arrays; every other pointer a device address (target_ptr and
+        target_off_ptr may both be None: the clouds alone); asynchronous."""
+        n = len(descs)
+        if isinstance(descs, (list, tuple)):
+            descs = (SubmapDesc * max(n, 1))(*descs)
+        self.check(lib().ndt_local_map_batch_dev(self.h, descs, n, stride, leaf, cloud_ptr, cloud_off_ptr, target_ptr,
+                                                 target_off_ptr, status_ptr, stream), "ndt_local_map_batch_dev")
 
     def predict_batch_dev(self, odo_cur_ptr, odo_prev_ptr, last_pose_ptr, B, motion_ptr, pred_ptr, init_ptr=None,
                           stream=None):

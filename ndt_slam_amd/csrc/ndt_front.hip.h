@@ -398,16 +398,24 @@ prefilter_sorted_kernel(const float *__restrict__ xy, size_t stride, const unsig
   }
 }
 
-// offsets of the filtered scans: exclusive scan of the counts (one workgroup)
+// ndt_local_map_batch_dev: the cloud that goes in front of scan b's filtered points in the output (makeLocalMap's
+// previous submap, src/PointCloudMap.cpp:123-126)
+struct PfPrev { const float *xy; unsigned long long n; };
+
+// offsets of the filtered scans: exclusive scan of the counts (one workgroup).  kTarget: of prev[b].n + count b, and
+// of nothing for a scan whose status is not NDT_OK (a failed submap: empty in every output)
+template <bool kTarget>
 __global__ void __launch_bounds__(1024)
-prefilter_offsets_kernel(const unsigned *__restrict__ counts, int B, unsigned long long *__restrict__ out_offsets) {
+prefilter_offsets_kernel(const unsigned *__restrict__ counts, int B, unsigned long long *__restrict__ out_offsets,
+                         const PfPrev *__restrict__ prev, const int *__restrict__ status) {
   __shared__ unsigned long long sh[1024];
   __shared__ unsigned long long carry;
   if (threadIdx.x == 0) carry = 0;
   __syncthreads();
   for (int base = 0; base < B; base += 1024) {
     const int i = base + threadIdx.x;
-    const unsigned long long v = i < B ? counts[i] : 0ull;
+    unsigned long long v = i < B ? counts[i] : 0ull;
+    if (kTarget) v = (i < B && status[i] == 0) ? v + prev[i].n : 0ull;
     sh[threadIdx.x] = v;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {
@@ -424,12 +432,23 @@ prefilter_offsets_kernel(const unsigned *__restrict__ counts, int B, unsigned lo
   if (threadIdx.x == 0) out_offsets[B] = carry;
 }
 
-// filtered points from their raw offsets to the packed output
+// filtered points from their raw offsets to the packed output.  kTarget: behind prev[b], which is copied in front of them
+template <bool kTarget>
 __global__ void __launch_bounds__(256)
 prefilter_pack_kernel(const float2 *__restrict__ tmp, const unsigned long long *__restrict__ raw_offsets,
-                      const unsigned long long *__restrict__ out_offsets, int B, float2 *__restrict__ out) {
+                      const unsigned long long *__restrict__ out_offsets, int B, float2 *__restrict__ out,
+                      const PfPrev *__restrict__ prev, size_t prev_stride, const int *__restrict__ status) {
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const unsigned long long r0 = raw_offsets[b], q0 = out_offsets[b];
+    const unsigned long long r0 = raw_offsets[b];
+    unsigned long long q0 = out_offsets[b];
+    if (kTarget) {
+      if (status[b] != 0) continue;
+      const PfPrev P = prev[b];
+      for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < P.n;
+           j += (unsigned long long)gridDim.x * blockDim.x)
+        out[q0 + j] = load_pt(P.xy, prev_stride, (size_t)j);
+      q0 += P.n;
+    }
     const unsigned long long n = out_offsets[b + 1] - q0;
     for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < n;
          j += (unsigned long long)gridDim.x * blockDim.x)

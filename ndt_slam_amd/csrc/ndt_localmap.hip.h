@@ -39,13 +39,17 @@ struct MmJob {
   unsigned long long *tab;             // preset to kMmEmpty
   float2 *diff;                        // points of b in new voxels, input order (room for nb)
   unsigned long long *n_diff;          // their count; ~0 when the clouds span more than 2^30 voxels
+  double res;                          // batched calls (ndt_local_map_batch_dev): the submap's resol ...
+  float cut;                           // ... and its rn_cutoff(thre_neighbor); the single calls pass both as kernel arguments
 };
 
 struct MmUnit {                        // at most kMmUnit consecutive points of the concatenated result
   const float *src; unsigned stride; unsigned n;
   int job;                             // >= 0: points of that triple's middle scan, to be filtered; < 0: copied whole
-  unsigned pad_;
+  unsigned sub;                        // batched calls: the submap the unit belongs to
 };
+
+struct MmSub { unsigned u0, u1; };     // batched calls: the units of a submap are [u0, u1) of the unit table
 
 struct MmFrame {
   double minx, miny, maxx, maxy, minz;
@@ -125,13 +129,16 @@ __device__ inline int mm_append4(const bool flag[kMmPer], const float2 p[kMmPer]
   return run;
 }
 
+// kBatch: the triples of every submap of a batched call, each with its own resol (MmJob::res)
+template <bool kBatch>
 __global__ void __launch_bounds__(kMmBlock)
-make_map_diff_kernel(const MmJob *__restrict__ jobs, double res) {
+make_map_diff_kernel(const MmJob *__restrict__ jobs, double res_arg) {
   __shared__ MmFrame F;
   __shared__ int wcnt[kMmPer][kMmWaves];
   __shared__ unsigned long long ltab[kMmLdsTab];
   __shared__ int lfill, lover;
   const MmJob J = jobs[blockIdx.x];
+  const double res = kBatch ? J.res : res_arg;
   const int tid = threadIdx.x, lane = tid & 63;
   const int nA = (int)(J.n0 + J.n1), N = nA + (int)J.nb;
   if (tid == 0) { F.defined = 0; F.nev = 0; F.err = 0; F.from = 0; F.depth = 0; F.first = 0x7fffffff; }
@@ -341,8 +348,10 @@ make_map_diff_kernel(const MmJob *__restrict__ jobs, double res) {
 // ---- remove_neighborPoint(test, diff) and the concatenation, spread over the chip: the result is cut into
 // units of at most 256 points -- stretches of a scan that is appended whole, or of a middle scan whose points
 // are tested against their triple's difference list (all pairs, float32 distance, strict <; rn_cutoff).
+// kBatch: the units of every submap of a batched call in one grid, the cut-off per submap (MmJob::cut)
+template <bool kBatch>
 __global__ void __launch_bounds__(kMmUnit)
-make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ units, float cut,
+make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ units, float cut_arg,
                      unsigned long long *__restrict__ keepbits, unsigned *__restrict__ unit_cnt) {
   __shared__ float2 tile[kMmTile];
   __shared__ int wsum[kMmUnit / 64];
@@ -353,6 +362,7 @@ make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ 
   const unsigned long long ndl = *J.n_diff;
   if (ndl == kMmEmpty) { if (tid == 0) unit_cnt[blockIdx.x] = 0xffffffffu; return; }
   const int nd = (int)ndl;
+  const float cut = kBatch ? J.cut : cut_arg;
   float2 p = make_float2(0.f, 0.f);
   if (tid < (int)U.n) p = load_pt(U.src, U.stride, (size_t)tid);
   bool keep = tid < (int)U.n;
@@ -402,14 +412,84 @@ make_map_offsets_kernel(const unsigned *__restrict__ unit_cnt, int nu, unsigned 
   if (threadIdx.x == 0) *n_out = bad ? kMmEmpty : carry;
 }
 
+// Batched calls, first level of the offsets: one workgroup per submap scans the counts of that submap's units
+// (unit_off: relative to the submap's start) and leaves the submap's total in cloud_off[s + 1] -- 0 and
+// status NDT_E_ARG when one of its triples failed.  Second level: make_map_sub_scan_kernel.
+__global__ void __launch_bounds__(1024)
+make_map_sub_offsets_kernel(const unsigned *__restrict__ unit_cnt, const MmSub *__restrict__ subs,
+                            unsigned long long *__restrict__ unit_off, unsigned long long *__restrict__ cloud_off,
+                            int *__restrict__ status) {
+  __shared__ unsigned long long sh[1024];
+  __shared__ unsigned long long carry;
+  __shared__ int bad;
+  const MmSub S = subs[blockIdx.x];
+  if (threadIdx.x == 0) { carry = 0ull; bad = 0; }
+  __syncthreads();
+  for (unsigned base = S.u0; base < S.u1; base += 1024u) {
+    const unsigned i = base + threadIdx.x;
+    unsigned c = i < S.u1 ? unit_cnt[i] : 0u;
+    if (c == 0xffffffffu) { bad = 1; c = 0u; }
+    sh[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const unsigned long long t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
+      __syncthreads();
+      sh[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (i < S.u1) unit_off[i] = carry + sh[threadIdx.x] - c;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry += sh[1023];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    cloud_off[blockIdx.x + 1] = bad ? 0ull : carry;
+    status[blockIdx.x] = bad ? (int)NDT_E_ARG : (int)NDT_OK;
+    if (blockIdx.x == 0) cloud_off[0] = 0ull;
+  }
+}
+
+// second level: the submaps' totals in cloud_off[1 .. n_subs] to their running sum, in place (one workgroup;
+// a round reads its 1024 entries before it writes them, and the next round's entries lie behind those)
+__global__ void __launch_bounds__(1024)
+make_map_sub_scan_kernel(unsigned long long *__restrict__ cloud_off, int n_subs) {
+  __shared__ unsigned long long sh[1024];
+  __shared__ unsigned long long carry;
+  if (threadIdx.x == 0) carry = 0ull;
+  __syncthreads();
+  for (int base = 0; base < n_subs; base += 1024) {
+    const int i = base + threadIdx.x;
+    sh[threadIdx.x] = i < n_subs ? cloud_off[i + 1] : 0ull;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const unsigned long long t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
+      __syncthreads();
+      sh[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (i < n_subs) cloud_off[i + 1] = carry + sh[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 1023) carry += sh[1023];
+    __syncthreads();
+  }
+}
+
+// kBatch: a unit's place is its submap's start (cloud_off) + its offset in the submap; a unit of a failed
+// submap writes nothing (n_out is not read)
+template <bool kBatch>
 __global__ void __launch_bounds__(kMmUnit)
 make_map_copy_kernel(const MmUnit *__restrict__ units, const unsigned long long *__restrict__ keepbits,
                      const unsigned long long *__restrict__ unit_off, const unsigned long long *__restrict__ n_out,
-                     float2 *__restrict__ out) {
-  if (*n_out == kMmEmpty) return;
+                     float2 *__restrict__ out, const unsigned long long *__restrict__ cloud_off,
+                     const int *__restrict__ status) {
+  if (!kBatch) { if (*n_out == kMmEmpty) return; }
   const MmUnit U = units[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   unsigned long long off = unit_off[blockIdx.x];
+  if (kBatch) {
+    if (status[U.sub] != (int)NDT_OK) return;
+    off += cloud_off[U.sub];
+  }
   if (U.job < 0) {
     if (tid < (int)U.n) out[off + tid] = load_pt(U.src, U.stride, (size_t)tid);
     return;

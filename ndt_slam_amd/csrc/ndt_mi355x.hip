@@ -1860,17 +1860,18 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n
   return NDT_OK;
 }
 
-int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy, size_t stride, const uint64_t *raw_offsets, int B,
-                            size_t total_raw_points, float leaf, float *out_xy, uint64_t *out_offsets, void *stream) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!raw_xy || !raw_offsets || !out_xy || !out_offsets || B <= 0 || total_raw_points == 0 || !(leaf > 0) ||
-      stride < 8 || (stride & 7))
-    return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+}  // extern "C"
+
+namespace {
+// The kernels of the pre-filter over B scans, inside the caller's scratch bracket (ScratchScope).  kTarget
+// (ndt_local_map_batch_dev): scan b's filtered points go behind prev[b] (device table, points at prev_stride), which
+// is copied in front of them, and out_offsets is the scan of prev[b].n + count b (of 0 where status[b] != NDT_OK);
+// total_prev_points: the sum of prev[b].n.
+template <bool kTarget>
+int pf_run(ndt_ctx *ctx, const float *raw_xy, size_t stride, const uint64_t *raw_offsets, int B, size_t total_raw_points,
+           float leaf, float *out_xy, uint64_t *out_offsets, const PfPrev *prev, size_t prev_stride,
+           size_t total_prev_points, const int *status, hipStream_t st) {
   int rc;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
   // filtered points at the raw offsets, then the per-scan counts
   const size_t tmp_bytes = total_raw_points * sizeof(float2);
   if ((rc = ctx->d_pf.ensure(ctx, 2 * tmp_bytes + (size_t)B * sizeof(unsigned)))) return rc;
@@ -1883,12 +1884,68 @@ int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy, size_t stride, co
                                                            tmp, counts);
   prefilter_mw_kernel<<<grid, 64 * kPfWaves, 0, st>>>(raw_xy, stride, (const unsigned long long *)raw_offsets, B, leaf,
                                                       sparse, tmp, counts, NDT_PF_SORTED ? kPfSortMax : -1);
-  prefilter_offsets_kernel<<<1, 1024, 0, st>>>(counts, B, (unsigned long long *)out_offsets);
-  const int gx = (int)std::min<size_t>(64, (total_raw_points / (size_t)B + 255) / 256 + 1);
-  prefilter_pack_kernel<<<dim3((unsigned)gx, (unsigned)std::min(B, 65535)), 256, 0, st>>>(
-      tmp, (const unsigned long long *)raw_offsets, (const unsigned long long *)out_offsets, B, (float2 *)out_xy);
+  prefilter_offsets_kernel<kTarget><<<1, 1024, 0, st>>>(counts, B, (unsigned long long *)out_offsets, prev, status);
+  const int gx = (int)std::min<size_t>(64, ((total_raw_points + total_prev_points) / (size_t)B + 255) / 256 + 1);
+  prefilter_pack_kernel<kTarget><<<dim3((unsigned)gx, (unsigned)std::min(B, 65535)), 256, 0, st>>>(
+      tmp, (const unsigned long long *)raw_offsets, (const unsigned long long *)out_offsets, B, (float2 *)out_xy, prev,
+      prev_stride, status);
   HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy, size_t stride, const uint64_t *raw_offsets, int B,
+                            size_t total_raw_points, float leaf, float *out_xy, uint64_t *out_offsets, void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!raw_xy || !raw_offsets || !out_xy || !out_offsets || B <= 0 || total_raw_points == 0 || !(leaf > 0) ||
+      stride < 8 || (stride & 7))
+    return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  int rc;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
+  if ((rc = pf_run<false>(ctx, raw_xy, stride, raw_offsets, B, total_raw_points, leaf, out_xy, out_offsets, nullptr, 0, 0, nullptr, st)))
+    return rc;
   return scope.close();
+}
+
+// B scans in host memory (raw_offsets[B + 1] in points of raw_xy_host): one upload, ndt_prefilter_batch_dev, the offsets
+// read back, one copy of the result.  out_xy_host needs room for every input point.  Empty scans stay empty.
+int ndt_prefilter_batch(ndt_ctx *ctx, const float *raw_xy_host, size_t stride, const uint64_t *raw_offsets, int B,
+                        float leaf, float *out_xy_host, uint64_t *out_offsets_host) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (B < 1) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: B < 1");
+  if (!raw_offsets || !out_offsets_host) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: NULL array (raw_offsets or out_offsets)");
+  if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: bad stride (need stride_bytes >= 8 and % 8 == 0)");
+  if (!(leaf > 0)) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: leaf <= 0");
+  for (int b = 0; b < B; ++b)
+    if (raw_offsets[b + 1] < raw_offsets[b])
+      return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: scan " + std::to_string(b) + ": offsets decrease");
+  const size_t n = (size_t)(raw_offsets[B] - raw_offsets[0]);
+  if (n && (!raw_xy_host || !out_xy_host)) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: NULL array (raw_xy or out_xy)");
+  if (n == 0) { for (int b = 0; b <= B; ++b) out_offsets_host[b] = 0; return NDT_OK; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  int rc;
+  const size_t ib = (n * stride + 15) & ~(size_t)15;
+  if ((rc = ctx->d_scan.ensure(ctx, ib + n * sizeof(float2)))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 2 * ((size_t)B + 1)))) return rc;
+  float *d_in = (float *)ctx->d_scan.p, *d_out = (float *)((char *)ctx->d_scan.p + ib);
+  uint64_t *d_offs = ctx->d_off.p;                              // [0 .. B] raw, [B + 1 .. 2 B + 1] filtered
+  std::vector<uint64_t> rel((size_t)B + 1);
+  for (int b = 0; b <= B; ++b) rel[b] = raw_offsets[b] - raw_offsets[0];
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, (const char *)raw_xy_host + (size_t)raw_offsets[0] * stride, n * stride, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_offs, rel.data(), rel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if ((rc = ndt_prefilter_batch_dev(ctx, d_in, stride, d_offs, B, n, leaf, d_out, d_offs + B + 1, st))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_offsets_host, d_offs + B + 1, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  const size_t m = (size_t)out_offsets_host[B];
+  if (m) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, m * sizeof(float2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
 }
 
 int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, float leaf, float *out_xy_host,
@@ -2121,29 +2178,35 @@ namespace {
 // Local-map assembly: the job table (one entry per scan triple) and the unit table (256-point stretches of the
 // result) are written into pinned memory, uploaded with one copy and consumed by the kernels of
 // ndt_localmap.hip.h.  Device scratch (ctx->d_mm):
-// [jobs][units][unit counts][unit offsets][keep bits][diff counts][voxel sets][diff lists].
+// [jobs][units][submaps][previous clouds][unit counts][unit offsets][keep bits][diff counts][voxel sets][diff lists]
+// (the submap and previous-cloud tables only in a batched call, ndt_local_map_batch_dev: the upload ends behind them).
 struct MmPlan {
-  struct Pair { const float *a0, *a1, *b; size_t n0, n1, nb; };
+  struct Pair { const float *a0, *a1, *b; size_t n0, n1, nb; double res = 0.0; float cut = 0.f; };   // res, cut: batched calls
   std::vector<Pair> pairs;
   size_t sa = 8, sb = 8;
   size_t unit_room = 0;
+  size_t n_subs = 0;         // batched calls: submaps (the tables of MmSub and PfPrev follow the units)
 };
 struct MmLayout {
-  size_t o_units = 0, o_ucnt = 0, o_uoff = 0, o_keep = 0, o_cnt = 0, o_tab = 0, o_diff = 0;
+  size_t o_units = 0, o_subs = 0, o_prev = 0, o_ucnt = 0, o_uoff = 0, o_keep = 0, o_cnt = 0, o_tab = 0, o_diff = 0;
   MmJob *jobs = nullptr;     // pinned, valid until the next call on this context
   MmUnit *units = nullptr;   // pinned
+  MmSub *subs = nullptr;     // pinned (batched calls)
+  PfPrev *prevs = nullptr;   // pinned (batched calls)
 };
 
 size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
 size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t st, MmLayout *Lo) {
-  const size_t nj = P.pairs.size(), nu = P.unit_room;
+  const size_t nj = P.pairs.size(), nu = P.unit_room, ns = P.n_subs;
   size_t tab_words = 0, list_pts = 0;
   for (const auto &q : P.pairs) { tab_words += pow2_at_least(2 * (q.n0 + q.n1) + 2); list_pts += q.nb; }
   MmLayout L;
   L.o_units = up64(nj * sizeof(MmJob));
-  L.o_ucnt = L.o_units + up64(nu * sizeof(MmUnit));
+  L.o_subs = L.o_units + up64(nu * sizeof(MmUnit));
+  L.o_prev = L.o_subs + up64(ns * sizeof(MmSub));
+  L.o_ucnt = L.o_prev + up64(ns * sizeof(PfPrev));
   L.o_uoff = L.o_ucnt + up64(nu * 4);
   L.o_keep = L.o_uoff + up64(nu * 8);
   L.o_cnt = L.o_keep + up64(nu * (kMmUnit / 64) * 8);
@@ -2157,6 +2220,8 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t
   char *d = (char *)ctx->d_mm.p, *h = (char *)ctx->h_mm.p;
   L.jobs = (MmJob *)h;
   L.units = (MmUnit *)(h + L.o_units);
+  L.subs = (MmSub *)(h + L.o_subs);
+  L.prevs = (PfPrev *)(h + L.o_prev);
   unsigned long long *d_cnt = (unsigned long long *)(d + L.o_cnt);
   size_t tw = 0, lp = 0;
   for (size_t j = 0; j < nj; ++j) {
@@ -2170,6 +2235,7 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t
     J.tab = (unsigned long long *)(d + L.o_tab) + tw;
     J.diff = diff_override ? diff_override : (float2 *)(d + L.o_diff) + lp;
     J.n_diff = d_cnt + j;
+    J.res = q.res; J.cut = q.cut;
     tw += cap; lp += q.nb;
   }
   if (tab_words) HIP_TRY(ctx, hipMemsetAsync(d + L.o_tab, 0xff, tab_words * 8, st));
@@ -2187,16 +2253,38 @@ int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, 
     HIP_TRY(ctx, hipEventRecord(ctx->ev_mm, st));
     ctx->mm_pending = true;
   }
-  if (nj) make_map_diff_kernel<<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, resol);
+  if (nj) make_map_diff_kernel<false><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, resol);
   if (nu) {
     const MmUnit *units = (const MmUnit *)(d + L.o_units);
     unsigned *ucnt = (unsigned *)(d + L.o_ucnt);
     unsigned long long *uoff = (unsigned long long *)(d + L.o_uoff), *keep = (unsigned long long *)(d + L.o_keep);
-    make_map_flag_kernel<<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, rn_cutoff(thre), keep, ucnt);
+    make_map_flag_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, rn_cutoff(thre), keep, ucnt);
     make_map_offsets_kernel<<<1, 1024, 0, st>>>(ucnt, (int)nu, uoff, (unsigned long long *)n_out);
-    make_map_copy_kernel<<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, (const unsigned long long *)n_out,
-                                                          (float2 *)out_xy);
+    make_map_copy_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, (const unsigned long long *)n_out,
+                                                                 (float2 *)out_xy, nullptr, nullptr);
   }
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+// The batched form (ndt_local_map_batch_dev): ONE upload of jobs + units + the submap tables, then the same chain over all
+// submaps at once, with the offsets in two levels (per submap, then over the submaps) and a status per submap.
+int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, size_t ns, float *cloud_xy, uint64_t *cloud_off,
+                 int *status, hipStream_t st) {
+  char *d = (char *)ctx->d_mm.p;
+  HIP_TRY(ctx, hipMemcpyAsync(d, ctx->h_mm.p, L.o_prev + ns * sizeof(PfPrev), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev_mm, st));
+  ctx->mm_pending = true;
+  const MmUnit *units = (const MmUnit *)(d + L.o_units);
+  unsigned *ucnt = (unsigned *)(d + L.o_ucnt);
+  unsigned long long *uoff = (unsigned long long *)(d + L.o_uoff), *keep = (unsigned long long *)(d + L.o_keep);
+  if (nj) make_map_diff_kernel<true><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, 0.0);
+  if (nu) make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, 0.f, keep, ucnt);
+  make_map_sub_offsets_kernel<<<(unsigned)ns, 1024, 0, st>>>(ucnt, (const MmSub *)(d + L.o_subs), uoff,
+                                                            (unsigned long long *)cloud_off, status);
+  make_map_sub_scan_kernel<<<1, 1024, 0, st>>>((unsigned long long *)cloud_off, (int)ns);
+  if (nu) make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, (float2 *)cloud_xy,
+                                                                      (const unsigned long long *)cloud_off, status);
   HIP_TRY(ctx, hipGetLastError());
   return NDT_OK;
 }
@@ -2339,6 +2427,180 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
   if (cnt == ~0ull) return fail(ctx, NDT_E_ARG, "ndt_make_map: a scan triple spans more than 2^30 voxels");
   *n_out = (size_t)cnt;
   if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)cnt * sizeof(float2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+}  // extern "C"
+
+// ---- batched local-map assembly (ndt_local_map_batch_dev / ndt_local_map_batch) ----
+
+namespace {
+
+size_t submap_points(const ndt_submap_desc &D) {        // points the submap's cloud may hold (the header's capacity rule)
+  const size_t total = (size_t)(D.offsets[D.n_scans] - D.offsets[0]);
+  return D.n_scans == 1 ? 2 * total : total;
+}
+
+// The synchronous refusals of a batched assembly: nothing changed, nothing queued.
+int check_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf, const void *cloud_xy,
+                          const void *cloud_off, const void *target_xy, const void *target_off, const void *status,
+                          const std::string &fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (n_subs < 1) return fail(ctx, NDT_E_ARG, fn + ": n_subs < 1");
+  if (!subs || !cloud_xy || !cloud_off || !status || (!target_xy) != (!target_off))
+    return fail(ctx, NDT_E_ARG, fn + ": NULL array (subs, cloud_xy, cloud_off, status, or one of target_xy / target_off alone)");
+  for (int s = 0; s < n_subs; ++s) {
+    const ndt_submap_desc &D = subs[s];
+    const std::string which = fn + ": submap " + std::to_string(s);
+    if (D.n_scans < 1 || D.n_scans > (1 << 20)) return fail(ctx, NDT_E_ARG, which + ": n_scans < 1 (or above 2^20)");
+    if (!D.scans_xy || !D.offsets) return fail(ctx, NDT_E_ARG, which + ": NULL scans_xy or offsets");
+    for (int i = 0; i < D.n_scans; ++i)
+      if (D.offsets[i + 1] < D.offsets[i] || D.offsets[i + 1] - D.offsets[i] > (uint64_t)(1u << 29))
+        return fail(ctx, NDT_E_ARG, which + ": offsets must be non-decreasing, scans below 2^29 points");
+  }
+  if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, fn + ": bad stride (need stride_bytes >= 8 and % 8 == 0)");
+  for (int s = 0; s < n_subs; ++s) {
+    const ndt_submap_desc &D = subs[s];
+    const std::string which = fn + ": submap " + std::to_string(s);
+    if (D.remove_moving && (!(D.resol > 0.0) || !std::isfinite(D.resol) || !std::isfinite(D.thre_neighbor)))
+      return fail(ctx, NDT_E_ARG, which + ": remove_moving needs a positive finite resol (and a finite thre_neighbor)");
+    if (D.n_prev > 0 && !D.prev_xy) return fail(ctx, NDT_E_ARG, which + ": n_prev > 0 with NULL prev_xy");
+    if (D.n_prev > (size_t)1 << 40) return fail(ctx, NDT_E_ARG, which + ": n_prev above 2^40 points");
+  }
+  if (target_xy && !(leaf > 0)) return fail(ctx, NDT_E_ARG, fn + ": a target needs leaf > 0");
+  return NDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
+                            float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status,
+                            void *stream) {
+  int rc = check_local_map_batch(ctx, subs, n_subs, stride, leaf, cloud_xy, cloud_off, target_xy, target_off, status,
+                                 "ndt_local_map_batch_dev");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  // the triples (jobs) and the pieces of every submap's cloud, in the order ndt_make_map_dev lists them for one submap
+  struct Piece { const float *p; size_t n; int job; };
+  MmPlan P;
+  P.sa = P.sb = stride;
+  P.n_subs = (size_t)n_subs;
+  std::vector<Piece> pieces;
+  std::vector<size_t> piece_end((size_t)n_subs);       // pieces of submap s: [piece_end[s - 1], piece_end[s])
+  size_t nu = 0, cap_cloud = 0, total_prev = 0;
+  double cut_of = 0.0; float cut = 0.f; bool have_cut = false;
+  for (int s = 0; s < n_subs; ++s) {
+    const ndt_submap_desc &D = subs[s];
+    auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
+    auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
+    auto piece = [&](int i, int job) { pieces.push_back({scan_ptr(i), scan_n(i), job}); nu += (scan_n(i) + kMmUnit - 1) / kMmUnit; };
+    if (D.remove_moving) {
+      if (!have_cut || !same_bits(&cut_of, &D.thre_neighbor, sizeof(double))) {
+        cut = rn_cutoff(D.thre_neighbor); cut_of = D.thre_neighbor; have_cut = true;
+      }
+      if (D.first_submap) piece(0, -1);
+      for (int i = 0; i + 2 < D.n_scans; ++i)
+        if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
+          piece(i + 1, (int)P.pairs.size());
+          P.pairs.push_back({scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut});
+        }
+      if (D.newest) piece(D.n_scans - 1, -1);
+    } else {
+      for (int i = D.first_submap ? 0 : 2; i < D.n_scans; ++i) piece(i, -1);
+    }
+    piece_end[s] = pieces.size();
+    cap_cloud += submap_points(D);
+    total_prev += D.n_prev;
+  }
+  if (nu > (size_t)INT32_MAX || P.pairs.size() > (size_t)INT32_MAX)
+    return fail(ctx, NDT_E_ARG, "ndt_local_map_batch_dev: more than 2^31 units of 256 points or scan triples in one call");
+  P.unit_room = nu;
+  MmLayout L;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
+  if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
+  size_t u = 0, pc = 0;
+  for (int s = 0; s < n_subs; ++s) {
+    L.subs[s].u0 = (unsigned)u;
+    for (; pc < piece_end[s]; ++pc)
+      for (size_t o = 0; o < pieces[pc].n; o += kMmUnit)
+        L.units[u++] = MmUnit{(const float *)((const char *)pieces[pc].p + o * stride), (unsigned)stride,
+                              (unsigned)std::min<size_t>(kMmUnit, pieces[pc].n - o), pieces[pc].job, (unsigned)s};
+    L.subs[s].u1 = (unsigned)u;
+    L.prevs[s] = PfPrev{subs[s].n_prev ? subs[s].prev_xy : nullptr, (unsigned long long)subs[s].n_prev};
+  }
+  if ((rc = mm_run_batch(ctx, L, P.pairs.size(), nu, (size_t)n_subs, cloud_xy, cloud_off, status, st))) return rc;
+  if (target_xy) {
+    // Submap::filterPoints of every cloud, behind its previous submap's cloud: cloud_xy / cloud_off are the filter's input form
+    const PfPrev *d_prev = (const PfPrev *)((const char *)ctx->d_mm.p + L.o_prev);
+    if ((rc = pf_run<true>(ctx, cloud_xy, sizeof(float2), cloud_off, n_subs, cap_cloud, leaf, target_xy, target_off, d_prev,
+                           stride, total_prev, status, st)))
+      return rc;
+  }
+  return scope.close();
+}
+
+int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
+                        float *cloud_xy_host, uint64_t *cloud_off_host, float *target_xy_host, uint64_t *target_off_host,
+                        int *status_host) {
+  int rc = check_local_map_batch(ctx, subs, n_subs, stride, leaf, cloud_xy_host, cloud_off_host, target_xy_host,
+                                 target_off_host, status_host, "ndt_local_map_batch");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const bool want_target = target_xy_host != nullptr;
+  // every submap's scans and previous cloud into one host block (each at a 16-byte boundary), uploaded with ONE copy
+  const size_t S = (size_t)n_subs;
+  std::vector<size_t> o_scan(S), o_prev(S);
+  size_t in_bytes = 0, cap_cloud = 0, total_prev = 0;
+  for (size_t s = 0; s < S; ++s) {
+    const ndt_submap_desc &D = subs[s];
+    o_scan[s] = in_bytes; in_bytes += ((size_t)(D.offsets[D.n_scans] - D.offsets[0]) * stride + 15) & ~(size_t)15;
+    o_prev[s] = in_bytes; in_bytes += (want_target ? (D.n_prev * stride + 15) & ~(size_t)15 : 0);
+    cap_cloud += submap_points(D);
+    total_prev += D.n_prev;
+  }
+  const size_t cap_target = want_target ? cap_cloud + total_prev : 0;
+  const size_t o_cloud = in_bytes + 64, o_target = o_cloud + cap_cloud * sizeof(float2) + 64;
+  if ((rc = ctx->d_scan.ensure(ctx, o_target + cap_target * sizeof(float2) + 64))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 3 * (S + 1)))) return rc;   // cloud_off | target_off | status (ints)
+  std::vector<unsigned char> stage(in_bytes);
+  std::vector<ndt_submap_desc> dsubs(subs, subs + S);
+  std::vector<std::vector<uint64_t>> rel(S);
+  char *d = (char *)ctx->d_scan.p;
+  for (size_t s = 0; s < S; ++s) {
+    const ndt_submap_desc &D = subs[s];
+    const size_t nb = (size_t)(D.offsets[D.n_scans] - D.offsets[0]) * stride;
+    if (nb) memcpy(stage.data() + o_scan[s], (const char *)D.scans_xy + (size_t)D.offsets[0] * stride, nb);
+    if (want_target && D.n_prev) memcpy(stage.data() + o_prev[s], D.prev_xy, D.n_prev * stride);
+    rel[s].resize((size_t)D.n_scans + 1);
+    for (int i = 0; i <= D.n_scans; ++i) rel[s][i] = D.offsets[i] - D.offsets[0];
+    dsubs[s].scans_xy = (const float *)(d + o_scan[s]);
+    dsubs[s].offsets = rel[s].data();
+    dsubs[s].prev_xy = want_target && D.n_prev ? (const float *)(d + o_prev[s]) : nullptr;
+    if (!want_target) dsubs[s].n_prev = 0;
+  }
+  if (in_bytes) HIP_TRY(ctx, hipMemcpyAsync(d, stage.data(), in_bytes, hipMemcpyHostToDevice, st));
+  uint64_t *d_coff = ctx->d_off.p, *d_toff = d_coff + S + 1;
+  int *d_status = (int *)(d_toff + S + 1);
+  if ((rc = ndt_local_map_batch_dev(ctx, dsubs.data(), n_subs, stride, leaf, (float *)(d + o_cloud), d_coff,
+                                    want_target ? (float *)(d + o_target) : nullptr, want_target ? d_toff : nullptr, d_status, st))) {
+    hipError_t e = hipStreamSynchronize(st); (void)e;          // (the staged block is read by the copy queued above)
+    return rc;
+  }
+  std::vector<uint64_t> back(3 * (S + 1));
+  HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_coff, back.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  memcpy(cloud_off_host, back.data(), (S + 1) * sizeof(uint64_t));
+  if (want_target) memcpy(target_off_host, back.data() + S + 1, (S + 1) * sizeof(uint64_t));
+  memcpy(status_host, back.data() + 2 * (S + 1), S * sizeof(int));
+  const size_t nc = (size_t)back[S], nt = want_target ? (size_t)back[2 * S + 1] : 0;
+  if (nc) HIP_TRY(ctx, hipMemcpyAsync(cloud_xy_host, d + o_cloud, nc * sizeof(float2), hipMemcpyDeviceToHost, st));
+  if (nt) HIP_TRY(ctx, hipMemcpyAsync(target_xy_host, d + o_target, nt * sizeof(float2), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return NDT_OK;
 }

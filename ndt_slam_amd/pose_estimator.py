@@ -172,7 +172,8 @@ class PoseEstimator:
 
 def estimate_poses(estims, initPoses):
     """estimatePose of several estimators -- independent sessions, each with its own local map -- with ONE batched map
-    build (capi.build_maps) and ONE multi-map launch (capi.align_batch_multi): each estimator's pre-filter, the build of
+    build (capi.build_maps) and ONE multi-map launch (capi.align_batch_multi): the pre-filter of all their scans (one
+    ctx.prefilter_batch per distinct LeafSize), the build of
     all their targets, the launch over their maps, each one's second half.
     Returns the list of (cost, estPose, cov), in the order of `estims`; the same values as estimatePose one by one.
     The estimators must share one context and the match parameters of their maps (Resolution, StepSize,
@@ -185,7 +186,20 @@ def estimate_poses(estims, initPoses):
     ctx = estims[0].ctx
     if any(e.ctx is not ctx for e in estims):
         raise ValueError("estimate_poses: the estimators do not share one context")
-    filtered = [np.ascontiguousarray(e.prefilterSource(), dtype=np.float32).reshape(-1, 2) for e in estims]
+    # the source pre-filters: ONE ctx.prefilter_batch per distinct LeafSize.  (An estimator whose own prefilterSource
+    # refuses -- no scan pair set, an empty scan, a leaf size that is not positive -- makes that call, in its turn, and
+    # so raises what it raised before.)
+    filtered = [None] * len(estims)
+    by_leaf = {}
+    for k, e in enumerate(estims):
+        if e.source_cloud is None or len(e.source_cloud) == 0 or not e.LeafSize > 0:
+            filtered[k] = e.prefilterSource()
+        else:
+            by_leaf.setdefault(e.LeafSize, []).append(k)
+    for leaf, idx in by_leaf.items():
+        for k, f in zip(idx, ctx.prefilter_batch([estims[k].source_cloud for k in idx], leaf)):
+            filtered[k] = f
+    filtered = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 2) for f in filtered]
     # every estimator's target in ONE batched build (ndt_map_build_batch): each map as its own rebuild would leave it
     uniq = list({id(e): e for e in estims}.values())
     maps = capi.build_maps(ctx, [e.target_cloud for e in uniq], [e.params for e in uniq], [e._map for e in uniq])

@@ -15,7 +15,7 @@ Host-side mirrors, same names and argument meaning as the reference:
 
 What runs on the MI355X: the source pre-filter and NDT match (PoseEstimator -> ndt_prefilter, ndt_map_build,
 ndt_align), Submap::makeMap (ndt_make_map: octree change detection + moving-object removal) and
-Submap::filterPoints (ndt_prefilter); with SlamLauncher(device_resample=True) also ScanPointResampler (ndt_resample,
+Submap::filterPoints (ndt_prefilter) -- in run_sessions both for all sessions at once (ndt_local_map_batch); with SlamLauncher(device_resample=True) also ScanPointResampler (ndt_resample,
 bit-identical to resample_points).  `ops` is the object that provides them (capi.Context); the bookkeeping and the
 3x3 filter algebra stay on the host as in the reference.  ROS publishing (tf, PoseArray, RViz clouds)
 is left out: it does not feed back into the estimate.
@@ -250,18 +250,29 @@ class Submap:
         self.resol, self.thre_neighbor = resol, thre_neighbor          # PCFilter.h:20-23
         self.scans = []
         self.p_cloud = _EMPTY
+        self.filtered = None            # filterPoints() of the current p_cloud, when a batched call has already made it
 
     def addPoints(self, cloud):
         self.scans.append(cloud)
 
     def filterPoints(self):                                             # src/PointCloudMap.cpp:4-13
+        if self.filtered is not None:
+            return self.filtered
         if len(self.p_cloud) == 0:
             return _EMPTY
         return self.ops.prefilter(self.p_cloud, self.LeafSize)
 
+    def makeMapArgs(self):
+        """makeMap's arguments, as ops.make_map takes them and as an item of ops.local_maps starts."""
+        return (self.scans, self.cntS == 0, self.newest, self.removeMoving, self.resol, self.thre_neighbor)
+
     def makeMap(self):                                                  # src/PointCloudMap.cpp:15-39
-        self.p_cloud = self.ops.make_map(self.scans, self.cntS == 0, self.newest, self.removeMoving, self.resol,
-                                         self.thre_neighbor)
+        self.p_cloud = self.ops.make_map(*self.makeMapArgs())
+        self.filtered = None
+
+    def setMap(self, p_cloud, filtered):
+        """What makeMap and the filterPoints calls behind it give, from one batched call (ops.local_maps)."""
+        self.p_cloud, self.filtered = p_cloud, filtered
 
 
 class PointCloudMap:
@@ -277,6 +288,9 @@ class PointCloudMap:
         self.localMap_cloud = _EMPTY
         self.maps = []
         self.submaps = [Submap(ops, **submap_kw)]
+        # run_sessions' batched path: addPoints does its bookkeeping only, and the makeMap it ends in and makeLocalMap
+        # are left to ONE ops.local_maps call over every session of the step (localMapItem / setLocalMap)
+        self.deferred = False
 
     def setLastPose(self, p):
         self.lastPose = p
@@ -296,23 +310,30 @@ class PointCloudMap:
         self.poses.append(p)
 
     def addPoints(self, lps):                                           # :59-96
+        sub = self.addPointsBookkeeping(lps)
+        if not self.deferred:
+            sub.makeMap()
+
+    def addPointsBookkeeping(self, lps):
+        """addPoints without the makeMap it ends in: the scan goes to the current submap, or -- past sepThre of travelled
+        distance -- the current submap closes (:72-90) and a new one takes it.  Returns the submap whose map is to be made."""
         cloud = np.ascontiguousarray(lps, dtype=np.float32).reshape(-1, 2)   # double -> PointXYZ floats, z = 0
         cur = self.submaps[-1]
         if self.atd - cur.atdS >= self.sepThre:
             size = len(self.poses)
             cur.cntE = size - 2
-            cur.p_cloud = cur.filterPoints()
+            cur.p_cloud = cur.filterPoints()                            # (p_cloud has not changed since the last step's filter)
+            cur.filtered = None
             cur.newest = False
             sub = Submap(self.ops, self.atd, size - 1, **self.submap_kw)
             if len(cur.scans) >= 2:                                     # two scans of overlap for the triple test
                 sub.addPoints(cur.scans[-2])
                 sub.addPoints(cur.scans[-1])
             sub.addPoints(cloud)
-            sub.makeMap()
             self.submaps.append(sub)
-        else:
-            cur.addPoints(cloud)
-            cur.makeMap()
+            return sub
+        cur.addPoints(cloud)
+        return cur
 
     def makeGlobalMap(self):                                            # :101-117
         self.maps = [s.p_cloud for s in self.submaps[:-1]]
@@ -320,11 +341,23 @@ class PointCloudMap:
         self.globalMap_cloud = np.concatenate(self.maps) if self.maps else _EMPTY
 
     def makeLocalMap(self):                                             # :119-134
+        if self.deferred:
+            return
         parts = []
         if len(self.submaps) >= 2:
             parts.append(self.submaps[-2].p_cloud)
         parts.append(self.submaps[-1].filterPoints())
         self.localMap_cloud = np.concatenate(parts)
+
+    def localMapItem(self):
+        """The current submap's makeMap + makeLocalMap as an item of ops.local_maps."""
+        prev = self.submaps[-2].p_cloud if len(self.submaps) >= 2 else None
+        return self.submaps[-1].makeMapArgs() + (prev,)
+
+    def setLocalMap(self, p_cloud, target, n_prev):
+        """The result of that item: the submap's cloud, and the local map = previous submap's cloud + filtered cloud."""
+        self.submaps[-1].setMap(p_cloud, target[n_prev:])
+        self.localMap_cloud = target
 
     def saveGlobalMap(self, map_name, separated_map_name):              # PointCloudMap.h:124-136
         save_pcd_ascii(map_name, self.globalMap_cloud)
@@ -473,7 +506,11 @@ def run_sessions(ops, logs, poses_names=None, map_names=None, separated_map_name
     `estimate(estimators, initPoses)` -- estimate_poses: one multi-map launch over the sessions' local maps -- then
     each session runs the second half and FrontEnd's bookkeeping (start_frame, keyframe_skip).  A session that has
     run out of scans drops out of the batch.  Writes per session what SlamLauncher.run writes (names may be None)
-    and returns the list of every session's fused poses; each is the same as its own SlamLauncher.run."""
+    and returns the list of every session's fused poses; each is the same as its own SlamLauncher.run.
+    When all sessions share one `ops` object that provides local_maps (a capi.Context), the map part of every growMap
+    of a step -- Submap::makeMap, filterPoints and makeLocalMap -- is done by ONE ops.local_maps call per step (one per
+    distinct LeafSize), between the second halves of matchScan and the bookkeeping; the sessions then make no
+    ops.make_map and no ops.prefilter call.  Otherwise every session makes its own calls, as SlamLauncher.run does."""
     logs = [list(l) for l in logs]
     S = len(logs)
     if launchers is None:
@@ -481,24 +518,42 @@ def run_sessions(ops, logs, poses_names=None, map_names=None, separated_map_name
     if len(launchers) != S:
         raise ValueError("run_sessions: one launcher per log")
     lengths = [min(len(l), L.p["end_frame"]) for l, L in zip(logs, launchers)]
-    for k in range(max(lengths, default=0)):
-        stepped, need = [], []
-        for i in range(S):
-            if k >= lengths[i]:
-                continue
-            fe, scan = launchers[i].frontEnd, logs[i][k]
-            if scan.sid < fe.startFrame:
-                continue
-            stepped.append(i)
-            pred = fe.smat.matchScanBegin(scan)
-            if pred is not None:
-                need.append((i, pred))
-        if need:
-            res = estimate([launchers[i].smat.estim for i, _ in need], [p for _, p in need])
-            for (i, _), (cost, est, cov) in zip(need, res):
-                launchers[i].smat.matchScanEnd(cost, est, cov)
-        for i in stepped:
-            launchers[i].frontEnd.processEnd()
+    ops0 = launchers[0].pcmap.ops if launchers else None
+    batched = ops0 is not None and hasattr(ops0, "local_maps") and all(L.pcmap.ops is ops0 for L in launchers)
+    for L in launchers:
+        L.pcmap.deferred = batched
+    try:
+        for k in range(max(lengths, default=0)):
+            stepped, need = [], []
+            for i in range(S):
+                if k >= lengths[i]:
+                    continue
+                fe, scan = launchers[i].frontEnd, logs[i][k]
+                if scan.sid < fe.startFrame:
+                    continue
+                stepped.append(i)
+                pred = fe.smat.matchScanBegin(scan)
+                if pred is not None:
+                    need.append((i, pred))
+            if need:
+                res = estimate([launchers[i].smat.estim for i, _ in need], [p for _, p in need])
+                for (i, _), (cost, est, cov) in zip(need, res):
+                    launchers[i].smat.matchScanEnd(cost, est, cov)
+            if batched and stepped:
+                # every stepped session has grown its map by one scan (matchScanBegin for a first scan, matchScanEnd for the
+                # others): their local maps in one call per LeafSize
+                by_leaf = {}
+                for i in stepped:
+                    by_leaf.setdefault(launchers[i].pcmap.submaps[-1].LeafSize, []).append(i)
+                for leaf, idx in by_leaf.items():
+                    res = ops0.local_maps([launchers[i].pcmap.localMapItem() for i in idx], leaf)
+                    for i, (p_cloud, target, n_prev) in zip(idx, res):
+                        launchers[i].pcmap.setLocalMap(p_cloud, target, n_prev)
+            for i in stepped:
+                launchers[i].frontEnd.processEnd()
+    finally:
+        for L in launchers:
+            L.pcmap.deferred = False
     out = []
     for i, L in enumerate(launchers):
         poses = L.frontEnd.get_poses()
