@@ -9,6 +9,8 @@ import pytest
 
 from oracle import ndt_numpy as NP
 
+import fitness_workloads as FW
+
 
 @pytest.fixture(scope="module")
 def c1(oracle, c1_world):
@@ -174,3 +176,54 @@ def test_version_switches_are_live(oracle, c1_world):
         r = oracle.Map(m, oracle.default_params(resolution=0.3, **kw)).align(scan, init)
         assert r["status"] == 0
         assert abs(r["score"] - base["score"]) > 0 or kw == dict(stale_h_ang=1)
+
+
+# ------------------------------------------------------------------------------------------ away from the origin
+@pytest.mark.parametrize("off", FW.MATCH_OFFSETS)
+@pytest.mark.parametrize("leaf", FW.MATCH_LEAVES)
+def test_c_vs_numpy_at_an_offset_and_other_leaves(oracle, leaf, off):
+    """The C1 world moved 1.2 km and 2.5 km from the origin, at leaves 0.1, 0.3 and 1 m: the C oracle against the NumPy
+    restatement, as the tests above do at the origin at 0.3 m.  Everything discrete or float32 is equal: the voxel of every
+    point, counts, float32 centroids, the neighbour pairs of an evaluation, iterations, evaluations, the final float32 matrix.
+    The fp64 quantities meet a cancellation both sides share with the reference: the covariance is sum(x x^T) / n - mu mu^T,
+    two numbers of size |x|^2 whose difference is of size sigma^2.  The two sides add the n products in different orders, each
+    rounding by up to half an ulp of the running sum, so a covariance entry may differ by n ulp(|x|^2) and an inverse
+    covariance by the relative amount  tol_c = n ulp(|x|^2) max|icov_c|  (first order), per voxel c.  That, beside the
+    tolerance of the test at the origin, is the bound for icov; for the score and its derivatives -- sums over the pairs of
+    smooth functions of icov, a relative change e of icov moving a term by at most about 2 e of its size -- it is twice the
+    largest tol_c over the voxels the evaluation pairs with, relative to the largest entry."""
+    m, make = FW.shifted_world(off)
+    prm = oracle.default_params(resolution=leaf)
+    M, cells = oracle.Map(m, prm), NP.Cells(m, leaf)
+    t = M.export()
+    assert np.array_equal(t["idx"], cells.idx)
+    assert np.array_equal(t["npts"], cells.npts)
+    assert np.array_equal(t["cent"], cells.cent)
+    assert t["mean"] == pytest.approx(cells.mean, rel=1e-13, abs=1e-13)
+    r2 = float((m.astype(np.float64) ** 2).sum(axis=1).max())
+    tol_c = np.abs(cells.npts) * np.spacing(r2) * np.abs(cells.icov).max(axis=1)
+    bound = (1e-8 + tol_c)[:, None] * np.abs(cells.icov).max(axis=1, keepdims=True) + 1e-8
+    assert np.all(np.abs(t["icov"] - cells.icov) <= bound)
+    d1, d2 = oracle.gauss(prm)
+    for k in range(3):
+        scan, truth, init = make(k)
+        for p in (init, truth, truth + [0.02, -0.01, 0.003]):
+            s, g, H, pairs = M.eval_at(scan, p)
+            tr, _ = NP.transform32(scan, p)
+            s2, g2, H2, n2 = NP.score_grad_hess(cells, scan, tr, p[2], d1, d2)
+            assert pairs == n2
+            used = cells.neighbours(tr)[1]
+            e = 2.0 * float(tol_c[used].max()) if len(used) else 0.0
+            assert s == pytest.approx(s2, rel=1e-9 + e)
+            assert g == pytest.approx(g2, rel=1e-8, abs=(1e-9 + e) * np.abs(g2).max())
+            assert H == pytest.approx(H2, rel=1e-8, abs=(1e-9 + e) * np.abs(H2).max())
+    for k in (0, 3, 4, 5):
+        scan, truth, init = make(k)
+        r, tr = M.align(scan, init, trace_cap=600)
+        n = NP.align(cells, scan, init, leaf)
+        assert int(r["iters"]) == n["iters"] and bool(r["converged"]) == n["converged"]
+        assert len(tr) == len(n["log"])
+        assert (r["T00"], r["T10"], r["T03"], r["T13"]) == tuple(n["T"])
+        assert r["pose"] == pytest.approx(n["pose"], abs=1e-12)
+        assert int(r["ref_evals"]) == n["evals"]
+        assert M.fitness(scan, *[float(v) for v in n["T"]]) == pytest.approx(NP.fitness(m, scan, n["T"]), rel=FW.loose_rel(len(scan)))
