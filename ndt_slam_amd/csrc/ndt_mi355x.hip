@@ -26,6 +26,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -100,15 +101,60 @@ struct DevBuf {
 };
 template <typename T> using PinnedBuf = DevBuf<T, true>;
 
+// An event or a stream that its owner's destructor destroys, as DevBuf frees: the owner has drained its work first.
+template <typename H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle &&o) noexcept { std::swap(h, o.h); }
+  Handle &operator=(Handle &&o) noexcept { release(); std::swap(h, o.h); return *this; }
+  ~Handle() { release(); }
+  void release() { if (h) { hipError_t e = Destroy(h); (void)e; } h = nullptr; }
+  H get() const { return h; }
+  operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+  int create(ndt_ctx *ctx, unsigned flags = hipEventDefault) { release(); HIP_TRY(ctx, hipEventCreateWithFlags(&h, flags)); return NDT_OK; }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+  int create(ndt_ctx *ctx, unsigned flags) { release(); HIP_TRY(ctx, hipStreamCreateWithFlags(&h, flags)); return NDT_OK; }
+  int create(ndt_ctx *ctx, unsigned flags, int priority) { release(); HIP_TRY(ctx, hipStreamCreateWithPriority(&h, flags, priority)); return NDT_OK; }
+};
+
+// A table that the host writes into pinned memory and one copy per call uploads: the previous call's copy may still be reading
+// the staging when the next call comes to rewrite (or reallocate) it.
+template <typename T>
+struct StagedUpload {
+  PinnedBuf<T> h;
+  Event ev;                           // behind the last upload (created on first use)
+  bool pending = false;               // ... which has not been waited for yet
+  // the staging is the host's to rewrite, with room for n elements
+  int reserve(ndt_ctx *ctx, size_t n) {
+    if (!ev) { const int rc = ev.create(ctx, hipEventDisableTiming); if (rc) return rc; }
+    if (pending) { HIP_TRY(ctx, hipEventSynchronize(ev)); pending = false; }
+    return h.ensure(ctx, n);
+  }
+  // elements [first, first + n) of the staging to dst, on st
+  hipError_t upload(void *dst, size_t first, size_t n, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(dst, h.p + first, n * sizeof(T), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(ev, st);
+    if (e == hipSuccess) pending = true;
+    return e;
+  }
+};
+
+// Run-time booleans as compile-time ones, to pick a kernel's template instance: f(std::true_type / std::false_type).
+template <typename F> void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
 // Timing events of the last kLen match launches of a context, attached to the dispatches: match kernel start / stop, end of
 // the launch (fitness_reduce_kernel stop).  Launch k of the context is entry k % kLen.
 struct LaunchRing {
   static constexpr int kLen = 64;
-  hipEvent_t ev[3 * kLen] = {};
+  Event ev[3 * kLen];
   bool deferred_[kLen] = {};           // NDT_OPT_DEFER_FITNESS: the launch's fitness kernels are on the context's own stream
   unsigned long long launches = 0;     // launches entered so far (read and written under g_live_mu)
 
-  hipEvent_t *events(unsigned long long k) { return ev + 3 * (k % kLen); }
+  Event *events(unsigned long long k) { return ev + 3 * (k % kLen); }
   // A launch that has left the ring is covered by the latest one: a context queues its launches in order (its fitness stream
   // is in order, a launch that leaves the deferred mode waits for the last deferred one, the scratch bracket orders a call
   // on another stream behind the previous one), so the latest launch's end is reached after every earlier one's.
@@ -116,7 +162,7 @@ struct LaunchRing {
   hipEvent_t end(unsigned long long k) { return events(covering(k))[2]; }
   bool deferred(unsigned long long k) const { return deferred_[covering(k) % kLen]; }
   // the events of the launch `b` launches before the latest (0: the latest); nullptr if it is not in the ring
-  hipEvent_t *back(int b) { return b < 0 || b >= kLen || (unsigned long long)b >= launches ? nullptr : events(launches - 1 - b); }
+  Event *back(int b) { return b < 0 || b >= kLen || (unsigned long long)b >= launches ? nullptr : events(launches - 1 - b); }
   // Enters the next launch of context `self` as the latest one of that context that reads the maps whose lists of readers
   // are lists[0 .. n) (ndt_map::readers; one list per distinct map).
   // Under g_live_mu: launches and builds on several contexts may come from several host threads.
@@ -137,14 +183,8 @@ struct LaunchRing {
 
 struct ndt_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;       // the stream all work is ordered on
-  hipStream_t own_stream = nullptr;   // created by ndt_ctx_create
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last match launch
-  hipEvent_t evm0 = nullptr, evm1 = nullptr; // around the last map build
-  hipEvent_t evb = nullptr;                  // bounding box of the map build read back
+  hipStream_t stream = nullptr;       // the stream all work is ordered on (own_stream, or the caller's: not owned)
   ndt_map *pending_map = nullptr;            // ndt_map_rebuild_begin without its _end (one at a time: the read-back buffer is the context's)
-  hipStream_t side = nullptr;                // map build: bounding box + centroid fill beside the bucketing chain
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool map_ms_pending = false;
   PinnedBuf<unsigned> h_bounds;              // bounding box read-back of the map build
   std::string err;
@@ -163,17 +203,14 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
   DevBuf<unsigned char> d_rn;                          // neighbour removal: block offsets + keep flags
   DevBuf<unsigned char> d_mm;                          // local-map assembly: jobs, pieces, voxel sets, lists
-  PinnedBuf<unsigned char> h_mm;                       // staging of the job table
-  hipEvent_t ev_mm = nullptr; bool mm_pending = false; // job table upload of the previous call
-  PinnedBuf<MapView> h_views;                          // ndt_align_batch_multi_dev: staging of the launch's table of map views
-  hipEvent_t ev_views = nullptr; bool views_pending = false;   // its upload by the previous multi-map launch (created on first use)
+  StagedUpload<unsigned char> mm_tab;                  // its job table
+  StagedUpload<MapView> views_tab;                     // ndt_align_batch_multi_dev: the launch's table of map views
   // ndt_map_build_batch_dev: the scan's ticket (word 0) and 16 words per map from word 16 (map_minmax's running box, result and
-  // done-counter, set to their start values when the table grows), their read-back, the job table and its pinned staging
+  // done-counter, set to their start values when the table grows), their read-back, the job table and its staging
   DevBuf<unsigned> d_boxes;
   PinnedBuf<unsigned> h_boxes;
   DevBuf<unsigned char> d_bb;
-  PinnedBuf<unsigned char> h_bb;
-  hipEvent_t ev_bb = nullptr; bool bb_pending = false; // the job table's upload by the previous batched build (created on first use)
+  StagedUpload<unsigned char> bb_tab;
   DevBuf<unsigned char> d_bstage;                      // ndt_map_build_batch: the host clouds' copies
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
@@ -187,7 +224,7 @@ struct ndt_ctx {
     DevBuf<float2> sorted;
     DevBuf<PrepRec> recs;
     DevBuf<unsigned char> maps;
-    hipEvent_t ev0 = nullptr, ready = nullptr;         // around ndt_order_kernel (on its dispatch)
+    Event ev0, ready;                                  // around ndt_order_kernel (on its dispatch)
     bool valid = false, timed = false;
     // what the set was prepared for: the batch, and by value everything of the map ndt_order_kernel reads -- the optimiser's
     // parameters (init_state: libm_f32, snap_thresh), the kernel instance (transform_sse) and the grid's origin and leaf
@@ -202,18 +239,16 @@ struct ndt_ctx {
   float order_ms = 0.f;                                // ndt_order_kernel of the prepared batch the last launch used
   // The grow-only scratch above belongs to the context, not to a stream: a call on another stream than the
   // previous one first waits for the previous user (ev_scratch).
-  hipEvent_t ev_scratch = nullptr; hipStream_t scratch_stream = nullptr; bool scratch_used = false, scratch_recorded = false;
+  hipStream_t scratch_stream = nullptr; bool scratch_used = false, scratch_recorded = false;
   // A match launch's WsHeader + ScanCtl[B] + chunk totals + bitmaps (ws), cell-ordered copy of the scans (sorted) and leading
   // bytes of ws known to be zero (cleared by the previous launch's last kernel).  Set 0 is the one every entry point uses;
   // NDT_OPT_DEFER_FITNESS launches take turns on all of them (the fitness kernels of the launches in between read theirs).
   struct LaunchSet { DevBuf<unsigned char> ws; DevBuf<float2> sorted; size_t ws_clean = 0; };
   static constexpr int kDeferSets = 2;                 // launches whose fitness kernels may be outstanding behind a new launch's match kernel, + 1
   LaunchSet sets[kDeferSets];
-  LaunchRing ring;
   // NDT_OPT_DEFER_FITNESS: the fitness kernels of ndt_align_batch_dev on a stream of the context's own, beside whatever the
   // caller's stream runs next (the next launch's match kernel: its idle workgroups' CUs)
   int defer_fitness = 0;
-  hipStream_t fit_stream = nullptr;
   struct FitJob {                                      // the fitness kernels of one launch: what queue_fitness needs
     MapView V; const float *scans = nullptr; const unsigned long long *offsets = nullptr; int B = 0, shared_scan = 0;
     size_t total_points = 0; float2 *sorted = nullptr; ndt_result *out = nullptr; unsigned char *ws = nullptr;
@@ -221,6 +256,17 @@ struct ndt_ctx {
     const MapView *views = nullptr; const int *map_of = nullptr; int n_maps = 0;   // multi-map launch: the device table (else V)
   };
   bool deferred_pending = false;                       // the last launch's fitness kernels may still be running beside the caller's stream
+  // The events and streams the context owns, declared behind the buffers above: `delete` destroys them first, the buffers after
+  // them (ndt_ctx_destroy has drained every stream before; a staged table's and a prepared set's events go with their buffers).
+  Stream own_stream;                  // created by ndt_ctx_create
+  Event ev0, ev1;                     // around the last match launch
+  Event evm0, evm1;                   // around the last map build
+  Event evb;                          // bounding box of the map build read back
+  Stream side;                        // map build: bounding box + centroid fill beside the bucketing chain
+  Event ev_fork, ev_join;
+  Event ev_scratch;                   // the scratch bracket (ScratchScope)
+  Stream fit_stream;                  // NDT_OPT_DEFER_FITNESS (created on first use)
+  LaunchRing ring;
 };
 
 struct ndt_map {
@@ -360,53 +406,34 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   const float *scans = J.scans; const unsigned long long *offsets = J.offsets;
   const int B = J.B, shared_scan = J.shared_scan; const size_t total_points = J.total_points;
   float2 *sorted = J.sorted; ndt_result *out = J.out; unsigned char *ws = J.ws;
-  const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes; const bool sse = J.sse, multi = J.views != nullptr;
+  const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes;
   float *fit = ctx->d_fit.p;
   FitPart *parts = ctx->d_fit_part.p;
-  {
-    const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
-    const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
-    // one-dimensional, XCD-aware: workgroup w -> (match, block of the match) in fit_block_of (ndt_fitness.hip.h)
-    const dim3 grid(gx * (unsigned)(((size_t)B + 7) / 8 * 8));
-    if (shared_scan) {
-      // hypothesis scoring: most seeds end far from the map -- the far phase of the search as a pass of its own over the
-      // queries that need it (ndt_fitness.hip.h)
-      const size_t cnt_bytes = far_cnt_bytes;
-      unsigned *far_n = (unsigned *)ctx->d_far.p, *far_idx = (unsigned *)(ctx->d_far.p + cnt_bytes);
-      { hipError_t e = hipMemsetAsync(far_n, 0, cnt_bytes, fs); if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("queue_fitness: hipMemsetAsync: ") + hipGetErrorString(e)); }
-      if (multi) {
-        if (sse) fitness_points_kernel<true, true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr, J.views, J.map_of, J.n_maps);
-        else     fitness_points_kernel<false, true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr, J.views, J.map_of, J.n_maps);
-        if (sse) fitness_far_kernel<true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, J.views, J.map_of, J.n_maps);
-        else     fitness_far_kernel<false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, J.views, J.map_of, J.n_maps);
-        hipExtLaunchKernelGGL((fitness_reduce_kernel<true, true>), dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                              offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), J.map_of, J.n_maps);
-      } else {
-      if (sse) fitness_points_kernel<true, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
-      else     fitness_points_kernel<false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, nullptr);
-      if (sse) fitness_far_kernel<true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
-      else     fitness_far_kernel<false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx);
-      hipExtLaunchKernelGGL(fitness_reduce_kernel<true>, dim3(std::min(B, 4 * ctx->num_cus)), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                            offsets, B, shared_scan, (const float *)fit, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), nullptr, 0);
-      }
-    } else {
-      // scans of their own: the search kernel leaves a {sum, count} per chunk of 64 points instead of a distance per point
-      if (multi && sse) fitness_points_kernel<true, false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts, J.views, J.map_of, J.n_maps);
-      else if (multi)   fitness_points_kernel<false, false, true><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts, J.views, J.map_of, J.n_maps);
-      else if (sse) fitness_points_kernel<true, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
-      else          fitness_points_kernel<false, false><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, nullptr, nullptr, (int)gx, parts);
-      // (a wave per match; at least as many workgroups as clear the control words with one store per thread, a CU each at most)
-      const size_t close_wgs = std::max<size_t>(((size_t)B + kFitBlock / 64 - 1) / (kFitBlock / 64),
-                                                std::min<size_t>((size_t)ctx->num_cus, (zero_bytes / 16 + kFitBlock - 1) / kFitBlock));
-      if (multi)
-        hipExtLaunchKernelGGL((fitness_reduce_kernel<false, true>), dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                              offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16), J.map_of, J.n_maps);
-      else
-        hipExtLaunchKernelGGL(fitness_reduce_kernel<false>, dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
-                              offsets, B, shared_scan, (const float *)nullptr, out, parts, (uint4 *)ws, (unsigned)(zero_bytes / 16),
-                              nullptr, 0);
-    }
-  }
+  const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
+  const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
+  // one-dimensional, XCD-aware: workgroup w -> (match, block of the match) in fit_block_of (ndt_fitness.hip.h)
+  const dim3 grid(gx * (unsigned)(((size_t)B + 7) / 8 * 8));
+  // hypothesis scoring (shared_scan): most seeds end far from the map -- the far phase of the search as a pass of its own over
+  // the queries that need it (ndt_fitness.hip.h); scans of their own: the search kernel leaves a {sum, count} per chunk of 64
+  // points instead of a distance per point
+  unsigned *far_n = shared_scan ? (unsigned *)ctx->d_far.p : nullptr, *far_idx = shared_scan ? (unsigned *)(ctx->d_far.p + far_cnt_bytes) : nullptr;
+  if (shared_scan) { hipError_t e = hipMemsetAsync(far_n, 0, far_cnt_bytes, fs); if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("queue_fitness: hipMemsetAsync: ") + hipGetErrorString(e)); }
+  // the closing kernel, shared_scan: a workgroup per match; else a wave per match, and at least as many workgroups as clear the
+  // control words with one store per thread, a CU each at most
+  const size_t close_wgs = shared_scan ? (size_t)std::min(B, 4 * ctx->num_cus)
+                                       : std::max<size_t>(((size_t)B + kFitBlock / 64 - 1) / (kFitBlock / 64),
+                                                          std::min<size_t>((size_t)ctx->num_cus, (zero_bytes / 16 + kFitBlock - 1) / kFitBlock));
+  // (a single-map launch: views, map_of null and n_maps 0, the kernels' defaults)
+  with_bool(J.sse, [&](auto S) { with_bool(J.views != nullptr, [&](auto M) { with_bool(shared_scan != 0, [&](auto D) {
+    constexpr bool sse = decltype(S)::value, multi = decltype(M)::value, shared = decltype(D)::value;
+    fitness_points_kernel<sse, shared, multi><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx,
+                                                                    shared ? nullptr : parts, J.views, J.map_of, J.n_maps);
+    if constexpr (shared)
+      fitness_far_kernel<sse, multi><<<grid, 256, 0, fs>>>(V, scans, offsets, B, shared_scan, sorted, out, fit, far_idx, far_n, (int)gx, J.views, J.map_of, J.n_maps);
+    hipExtLaunchKernelGGL((fitness_reduce_kernel<shared, multi>), dim3((unsigned)close_wgs), dim3(kFitBlock), 0, fs, nullptr, J.end, 0,
+                          offsets, B, shared_scan, shared ? (const float *)fit : (const float *)nullptr, out, parts, (uint4 *)ws,
+                          (unsigned)(zero_bytes / 16), J.map_of, J.n_maps);
+  }); }); });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("queue_fitness: ") + hipGetErrorString(e));
   return NDT_OK;
@@ -435,7 +462,7 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   if (!defer && L >= 1 && R.deferred(L - 1)) HIP_TRY(ctx, hipStreamWaitEvent(st, R.end(L - 1), 0));   // (the fitness stream is in order: the last launch's end is everybody's)
   if (defer && L >= (unsigned long long)ndt_ctx::kDeferSets && R.deferred(L - ndt_ctx::kDeferSets)) HIP_TRY(ctx, hipStreamWaitEvent(st, R.end(L - ndt_ctx::kDeferSets), 0));
   // (the caller's priority class: below it these kernels starve behind every match kernel -- 0.49 against 0.37 ms per bench step)
-  if (defer && !ctx->fit_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->fit_stream, hipStreamNonBlocking));
+  if (defer && !ctx->fit_stream) { const int rc = ctx->fit_stream.create(ctx, hipStreamNonBlocking); if (rc) return rc; }
   const MapView &V = map->view;
   const OptParams O = opt_of(map->prm);
   // workspace: header + one control line per scan (zeroed every launch) + chunk totals
@@ -465,23 +492,16 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   if ((rc = ctx->d_fit_part.ensure(ctx, slots / 64 + (size_t)B + 1))) return rc;
   // control words: zero before every launch -- by the last kernel of the previous launch of this context
   // (fitness_reduce_kernel), or by a memset when that did not cover enough
-  if (mm && !ctx->ev_views) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_views, hipEventDisableTiming));
-  if (mm && (size_t)mm->n_maps > ctx->h_views.cap()) {
-    if (ctx->views_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_views)); ctx->views_pending = false; }
-    if ((rc = ctx->h_views.ensure(ctx, (size_t)mm->n_maps))) return rc;
-  }
+  if (mm && (rc = ctx->views_tab.reserve(ctx, (size_t)mm->n_maps))) return rc;   // (waits for the previous multi-map launch's copy)
   if (set.ws_clean < zero_bytes) HIP_TRY(ctx, hipMemsetAsync(set.ws.p, 0, zero_bytes, st));
   set.ws_clean = 0;
   unsigned char *ws = set.ws.p;
   // The table: the views as they are now (a map between ndt_map_rebuild_begin and _end is matched with the grid its view
-  // holds at the call), staged in pinned memory that the previous multi-map launch's copy may still be reading, then one copy
+  // holds at the call), staged in pinned memory, then one copy
   const MapView *views = nullptr;
   if (mm) {
-    if (ctx->views_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_views)); ctx->views_pending = false; }
-    for (int i = 0; i < mm->n_maps; ++i) ctx->h_views.p[i] = mm->maps[i]->view;
-    HIP_TRY(ctx, hipMemcpyAsync(ws + tab_off, ctx->h_views.p, (size_t)mm->n_maps * sizeof(MapView), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_views, st));
-    ctx->views_pending = true;
+    for (int i = 0; i < mm->n_maps; ++i) ctx->views_tab.h.p[i] = mm->maps[i]->view;
+    HIP_TRY(ctx, ctx->views_tab.upload(ws + tab_off, 0, (size_t)mm->n_maps, st));
     views = reinterpret_cast<const MapView *>(ws + tab_off);
   }
   // helper limit: 8 while a launch has fewer scans than workgroups (one scan at a time: everybody helps), 2 for whole-GPU
@@ -493,31 +513,25 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const int grid = helpers ? ncu : (B < ncu ? B : ncu);
   // timing: the events ride on the kernels' own dispatch packets (hipExtLaunchKernelGGL: start / stop of that kernel) -- an
   // event RECORD is a packet of its own between two kernels, three of them per launch cost the stream 6-10 us
-  hipEvent_t *evr = R.events(L);
+  Event *evr = R.events(L);
   // (the pair check left out where it cannot fire -- accumulate_pair -- in the preset's own instantiation only)
   const bool chk = !(V.e_hi > 1.0 + 1e-6);
-#define NDT_LAUNCH(S_, I_, C_)                                                                                          \
-  hipExtLaunchKernelGGL((ndt_align_kernel<S_, I_, C_>), dim3(grid), dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, \
-                        offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, prep, prep_map, \
-                        nullptr, nullptr, 0)
-#define NDT_LAUNCH_MULTI(S_, I_, C_)                                                                                          \
-  hipExtLaunchKernelGGL((ndt_align_kernel<S_, I_, C_, true>), dim3(grid), dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, \
-                        offsets, B, shared_scan, inits, out, trace, trace_cap, trace_rows, sorted, ws, helpers, prof, nullptr, nullptr, \
-                        views, mm->map_of, mm->n_maps)
-  if (mm) {
-    if (sse && incl)      NDT_LAUNCH_MULTI(true, true, true);
-    else if (sse && !chk) NDT_LAUNCH_MULTI(true, false, false);
-    else if (sse)         NDT_LAUNCH_MULTI(true, false, true);
-    else if (incl)        NDT_LAUNCH_MULTI(false, true, true);
-    else                  NDT_LAUNCH_MULTI(false, false, true);
-  }
-  else if (sse && incl) NDT_LAUNCH(true, true, true);
-  else if (sse && !chk) NDT_LAUNCH(true, false, false);
-  else if (sse)         NDT_LAUNCH(true, false, true);
-  else if (incl)        NDT_LAUNCH(false, true, true);
-  else                  NDT_LAUNCH(false, false, true);
-#undef NDT_LAUNCH_MULTI
-#undef NDT_LAUNCH
+  // The kernel exists in five <SSE, INCL, CHK> instances per MULTI (not eight: it is the largest in the object); a single-map
+  // launch has no table (views, map_of null), a multi-map one no prepared set (prep, prep_map null).
+  const int *map_of = mm ? mm->map_of : nullptr; const int n_maps = mm ? mm->n_maps : 0;
+  auto match = [&](auto S, auto I, auto C) {
+    with_bool(mm != nullptr, [&](auto M) {
+      hipExtLaunchKernelGGL((ndt_align_kernel<decltype(S)::value, decltype(I)::value, decltype(C)::value, decltype(M)::value>), dim3(grid),
+                            dim3(kBlock), 0, st, evr[0], evr[1], 0, V, O, scans, offsets, B, shared_scan, inits, out, trace, trace_cap,
+                            trace_rows, sorted, ws, helpers, prof, prep, prep_map, views, map_of, n_maps);
+    });
+  };
+  const std::true_type yes; const std::false_type no;
+  if (sse && incl)      match(yes, yes, yes);
+  else if (sse && !chk) match(yes, no, no);
+  else if (sse)         match(yes, no, yes);
+  else if (incl)        match(no, yes, yes);
+  else                  match(no, no, yes);
   // From here on a kernel that reads the map and the context's scratch is queued: whatever happens below, the launch is
   // entered in the context's ring (its last event recorded) and in the map's list of readers, so that a later call on another
   // stream and a build of this map that must wait for it (re-queued, or behind a deferred launch) are ordered behind it.
@@ -547,7 +561,7 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
     if (e != hipSuccess) return entered(fail(ctx, NDT_E_HIP, std::string("launch_align: hipStreamWaitEvent: ") + hipGetErrorString(e)));
   }
   const int qrc = queue_fitness(ctx, {V, scans, offsets, B, shared_scan, total_points, sorted, out, ws, zero_bytes, far_cnt_bytes, sse, evr[2],
-                                      views, mm ? mm->map_of : nullptr, mm ? mm->n_maps : 0}, fs);
+                                      views, map_of, n_maps}, fs);
   if (qrc != NDT_OK) return entered(qrc);
   {
     hipError_t e = hipGetLastError();
@@ -607,25 +621,19 @@ const char *ndt_last_error(const ndt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 static int ctx_init(ndt_ctx *c, int device) {
   c->device = device;
   HIP_TRY(c, hipSetDevice(device));
-  HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-  c->stream = c->own_stream;
-  HIP_TRY(c, hipEventCreate(&c->ev0));
-  HIP_TRY(c, hipEventCreate(&c->ev1));
-  HIP_TRY(c, hipEventCreate(&c->evm0));
-  HIP_TRY(c, hipEventCreate(&c->evm1));
-  HIP_TRY(c, hipEventCreateWithFlags(&c->evb, hipEventDisableTiming));
+  int rc;
+  if ((rc = c->own_stream.create(c, hipStreamNonBlocking))) return rc;
+  c->stream = c->own_stream.get();
+  for (Event *e : {&c->ev0, &c->ev1, &c->evm0, &c->evm1}) if ((rc = e->create(c))) return rc;
   {
     int lo = 0, hi = 0;
     HIP_TRY(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIP_TRY(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, hi));
+    if ((rc = c->side.create(c, hipStreamNonBlocking, hi))) return rc;
   }
-  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mm, hipEventDisableTiming));
-  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scratch, hipEventDisableTiming));
-  for (hipEvent_t &e : c->ring.ev) HIP_TRY(c, hipEventCreate(&e));
-  { int rc = c->h_bounds.alloc(c, 64); if (rc) return rc; }
-  { int rc = upload_exp_table(c); if (rc) return rc; }
+  for (Event *e : {&c->evb, &c->ev_fork, &c->ev_join, &c->ev_scratch}) if ((rc = e->create(c, hipEventDisableTiming))) return rc;
+  for (Event &e : c->ring.ev) if ((rc = e.create(c))) return rc;
+  if ((rc = c->h_bounds.alloc(c, 64))) return rc;
+  if ((rc = upload_exp_table(c))) return rc;
   hipDeviceProp_t prop;
   HIP_TRY(c, hipGetDeviceProperties(&prop, device));
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
@@ -673,29 +681,14 @@ int ndt_ctx_destroy(ndt_ctx *c) {
   { std::lock_guard<std::mutex> lk(g_live_mu); g_live_ctx.erase(c); }
   hipError_t e;
   e = hipSetDevice(c->device);
+  // Ordering, not ownership: everything the context queued has finished before any of its events, streams and buffers goes.
   if (c->stream) e = hipStreamSynchronize(c->stream);
-  if (c->fit_stream) { e = hipStreamSynchronize(c->fit_stream); e = hipStreamDestroy(c->fit_stream); }
-  if (c->own_stream) e = hipStreamDestroy(c->own_stream);
-  if (c->ev0) e = hipEventDestroy(c->ev0);
-  if (c->ev1) e = hipEventDestroy(c->ev1);
-  if (c->evm0) e = hipEventDestroy(c->evm0);
-  if (c->evm1) e = hipEventDestroy(c->evm1);
-  if (c->evb) e = hipEventDestroy(c->evb);
-  if (c->side) { e = hipStreamSynchronize(c->side); e = hipStreamDestroy(c->side); }
-  if (c->ev_fork) e = hipEventDestroy(c->ev_fork);
-  if (c->ev_join) e = hipEventDestroy(c->ev_join);
-  if (c->ev_mm) e = hipEventDestroy(c->ev_mm);
-  if (c->ev_views) e = hipEventDestroy(c->ev_views);
-  if (c->ev_bb) e = hipEventDestroy(c->ev_bb);
-  if (c->ev_scratch) e = hipEventDestroy(c->ev_scratch);
-  for (hipEvent_t r : c->ring.ev) if (r) e = hipEventDestroy(r);
-  for (ndt_ctx::PrepSet &S : c->prep) {
+  if (c->fit_stream) e = hipStreamSynchronize(c->fit_stream);
+  if (c->side) e = hipStreamSynchronize(c->side);
+  for (ndt_ctx::PrepSet &S : c->prep)
     if (S.ready && S.scans) e = hipEventSynchronize(S.ready);      // (its kernel may have been queued on another stream than the context's)
-    if (S.ev0) e = hipEventDestroy(S.ev0);
-    if (S.ready) e = hipEventDestroy(S.ready);
-  }
   (void)e;
-  delete c;                                     // (its buffers: on this device, after the work above has drained)
+  delete c;                                     // (its events and streams, then its buffers: on this device, after the work above has drained)
   return NDT_OK;
 }
 
@@ -708,7 +701,7 @@ int ndt_ctx_set_stream(ndt_ctx *c, void *stream) {
   // the last user of the scratch may have been a *_dev call on a foreign stream (its event was recorded then)
   if (c->scratch_used && c->scratch_recorded) HIP_TRY(c, hipEventSynchronize(c->ev_scratch));
   c->scratch_used = false; c->scratch_recorded = false;   // (everything queued so far has finished)
-  c->stream = stream ? (hipStream_t)stream : c->own_stream;
+  c->stream = stream ? (hipStream_t)stream : c->own_stream.get();
   return NDT_OK;
 }
 
@@ -726,7 +719,7 @@ int ndt_last_timing(const ndt_ctx *cc, float *map_ms, float *align_ms) {
 }
 
 int ndt_kernel_timing(ndt_ctx *c, int back, float *match_ms, float *fitness_ms) {
-  hipEvent_t *evr = c ? c->ring.back(back) : nullptr;
+  Event *evr = c ? c->ring.back(back) : nullptr;
   if (!evr) return fail(c, NDT_E_ARG, "ndt_kernel_timing: no such launch in the ring");
   HIP_TRY(c, hipEventSynchronize(evr[2]));
   float a = 0.f, f = 0.f;
@@ -738,7 +731,7 @@ int ndt_kernel_timing(ndt_ctx *c, int back, float *match_ms, float *fitness_ms) 
 }
 
 int ndt_launch_interval(ndt_ctx *c, int back, float *interval_ms) {
-  hipEvent_t *e1 = c && interval_ms ? c->ring.back(back) : nullptr, *e0 = e1 ? c->ring.back(back + 1) : nullptr;
+  Event *e1 = c && interval_ms ? c->ring.back(back) : nullptr, *e0 = e1 ? c->ring.back(back + 1) : nullptr;
   if (!e0) return fail(c, NDT_E_ARG, "ndt_launch_interval: no such pair of launches in the ring");
   HIP_TRY(c, hipEventSynchronize(e1[0]));
   HIP_TRY(c, hipEventElapsedTime(interval_ms, e0[0], e1[0]));
@@ -746,7 +739,7 @@ int ndt_launch_interval(ndt_ctx *c, int back, float *interval_ms) {
 }
 
 int ndt_ctx_wait_launch(ndt_ctx *c, int back, void *stream) {
-  hipEvent_t *evr = c ? c->ring.back(back) : nullptr;
+  Event *evr = c ? c->ring.back(back) : nullptr;
   if (!evr) return fail(c, NDT_E_ARG, "ndt_ctx_wait_launch: no such launch in the ring");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamWaitEvent(stream ? (hipStream_t)stream : c->stream, evr[2], 0));
@@ -774,28 +767,39 @@ int ndt_map_destroy(ndt_map *m) {
   return NDT_OK;
 }
 
-// The geometry of the occupancy tiles of a grid (MapView::tiles: 8 x 8 voxels per word, a border of one word).
-static int tiles_w_of(const GridDims &G) { return (G.div_x + 7) / 8 + 2; }
-static size_t ntile8_of(const GridDims &G) { return (size_t)tiles_w_of(G) * ((G.div_y + 7) / 8 + 2); }
+// The launch geometry of a build of n points on grid G -- the rule of both build paths: queue_build launches with it,
+// build_batch puts it into its BuildJobs and prefix sums.  (tiles: MapView::tiles, 8 x 8 voxels per word, a border of one word.)
+struct BuildGeom {
+  size_t ng, npad, ntile8;            // voxels, voxels with the border, occupancy words
+  int tiles_w, ntiles, big_cap;       // occupancy words per row; tiles of the scan; room for voxels with > kBigVoxel points
+  unsigned small_blocks, finalize_blocks;   // map_order's blocks of small voxels; map_finalize
+  BuildGeom(size_t n, const GridDims &G)
+      : ng((size_t)G.div_x * G.div_y), npad((size_t)G.gw * G.gh), ntile8((size_t)((G.div_x + 7) / 8 + 2) * ((G.div_y + 7) / 8 + 2)),
+        tiles_w((G.div_x + 7) / 8 + 2), ntiles((int)((ng + kScanTile - 1) / kScanTile)), big_cap((int)(n / kBigVoxel + 1)),
+        small_blocks((unsigned)((ng + kOrderVoxPerBlock - 1) / kOrderVoxPerBlock)),
+        finalize_blocks((unsigned)((ng + 255) / 256)) {}
+};
+// ... and of the kernels over the points alone (map_minmax_kernel; map_count_kernel and map_scatter_kernel)
+static int minmax_blocks(size_t n) { return grid_for(n, 256 * 32, 128); }
+static int point_blocks(size_t n) { return grid_for(n, 256); }
 
 // Step 2 of the map build: the map's buffers for n points on a grid of ng voxels (npad with the border), grow-only across
 // rebuilds.  A grown count buffer is marked not clean; *state_grown: the scan's words were reallocated -- the caller clears
 // them (no word may carry a tag by accident).
-static int ensure_build_buffers(ndt_ctx *ctx, ndt_map *m, size_t n, size_t ng, size_t npad, size_t ntile8, bool *state_grown) {
+static int ensure_build_buffers(ndt_ctx *ctx, ndt_map *m, size_t n, const BuildGeom &g, bool *state_grown) {
   int rc; bool grown = false;
-  const size_t ntiles_ = (ng + kScanTile - 1) / kScanTile;
-  if ((rc = m->count.ensure(ctx, ng + 1, &grown))) return rc;
+  if ((rc = m->count.ensure(ctx, g.ng + 1, &grown))) return rc;
   if (grown) m->count_clean = false;
-  if ((rc = m->start.ensure(ctx, ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
-  if ((rc = m->npts_grid.ensure(ctx, ng + 1))) return rc;
-  if ((rc = m->scan_state.ensure(ctx, 2 * ntiles_ + 2, state_grown))) return rc;
+  if ((rc = m->start.ensure(ctx, g.ng + 1 + 8))) return rc;   // 4 readable ints before, 3 after (nearest_sq)
+  if ((rc = m->npts_grid.ensure(ctx, g.ng + 1))) return rc;
+  if ((rc = m->scan_state.ensure(ctx, 2 * (size_t)g.ntiles + 2, state_grown))) return rc;
   if ((rc = m->perm.ensure(ctx, n + 4))) return rc;       // + 4: map_order_kernel reads four numbers at a time
-  if ((rc = m->big.ensure(ctx, n / kBigVoxel + 1))) return rc;   // voxels with > kBigVoxel points
-  if ((rc = m->occ.ensure(ctx, (ng + 31) / 32 + 2))) return rc;
-  if ((rc = m->tiles.ensure(ctx, ntile8))) return rc;
+  if ((rc = m->big.ensure(ctx, (size_t)g.big_cap))) return rc;   // voxels with > kBigVoxel points
+  if ((rc = m->occ.ensure(ctx, (g.ng + 31) / 32 + 2))) return rc;
+  if ((rc = m->tiles.ensure(ctx, g.ntile8))) return rc;
   if ((rc = m->pts.ensure(ctx, n))) return rc;
-  if ((rc = m->cent.ensure(ctx, npad))) return rc;
-  if ((rc = m->rec.ensure(ctx, npad * 8))) return rc;
+  if ((rc = m->cent.ensure(ctx, g.npad))) return rc;
+  if ((rc = m->rec.ensure(ctx, g.npad * 8))) return rc;
   return NDT_OK;
 }
 
@@ -813,35 +817,43 @@ static LeafParams leaf_of(const ndt_params *prm) {
   return L;
 }
 
-// What a build of n points on grid G leaves on the host: the map's view (what the match and fitness kernels read) and info.
-static void set_view(ndt_map *m, size_t n, const ndt_params *prm, const GridDims &G) {
+// The host side of a build, in two steps -- the rule of both build paths.  build_requested: what is to be built, before
+// anything is queued (the two-phase build's second half reads it back).  build_queued: what the build's kernels, once queued
+// on grid G, leave -- the map's view (what the match and fitness kernels read), its info and the grid kept for the next build.
+static void build_requested(ndt_map *m, const float *xy, size_t n, size_t stride, const ndt_params *prm) {
+  m->prm = *prm; m->n = n; m->info_valid = false;
+  m->pend_xy = xy; m->pend_stride = stride; m->pend_queued = false;
+}
+static void build_queued(ndt_map *m, const GridDims &G) {
+  const BuildGeom g(m->n, G);
+  const ndt_params *prm = &m->prm;
+  m->ng = g.ng; m->npad = g.npad;
   MapView &V = m->view;
   V.inv_leaf = G.inv_leaf; V.leaf = prm->resolution;
   V.r2 = (float)((double)prm->resolution * (double)prm->resolution);
   V.radius_inclusive = prm->radius_inclusive; V.transform_sse = prm->transform_sse;
   V.min_bx = G.min_bx; V.min_by = G.min_by; V.div_x = G.div_x; V.div_y = G.div_y; V.gw = G.gw; V.gh = G.gh;
-  V.cent = m->cent.p; V.rec = m->rec.p; V.occ = m->occ.p; V.tiles = m->tiles.p; V.tiles_w = tiles_w_of(G); V.pt_start = m->start.p + 4;
+  V.cent = m->cent.p; V.rec = m->rec.p; V.occ = m->occ.p; V.tiles = m->tiles.p; V.tiles_w = g.tiles_w; V.pt_start = m->start.p + 4;
   V.pts = m->pts.p;
   gauss_constants(*prm, &V.d1, &V.d2);
   V.e_hi = pair_check_threshold(V.d2);
   m->info.min_bx = G.min_bx; m->info.min_by = G.min_by; m->info.div_x = G.div_x; m->info.div_y = G.div_y;
-  m->info.n_points = n;
+  m->info.n_points = m->n;
+  m->grid = G; m->have_grid = true;
+  m->count_clean = true;                // (a complete build: map_scatter_kernel takes back what map_count_kernel added)
 }
 
 // Steps 2-4 of the map build for a given voxel grid: everything after the bounding box, queued on
-// the context's stream.
-static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size_t stride, const ndt_params *prm,
-                       const GridDims &G, bool requeue = false) {
+// the context's stream.  The cloud, its parameters and n are the map's (build_requested).
+static int queue_build(ndt_ctx *ctx, ndt_map *m, const GridDims &G, bool requeue = false) {
   hipStream_t st = ctx->stream;
-  const size_t ng = (size_t)G.div_x * G.div_y, npad = (size_t)G.gw * G.gh;
-  m->ng = ng; m->npad = npad;
-  const int tiles_w = tiles_w_of(G);
-  const size_t ntile8 = ntile8_of(G);
+  const float *xy = m->pend_xy; const size_t n = m->n, stride = m->pend_stride;
+  const BuildGeom g(n, G);
 
   // 2. buffers (grow-only across rebuilds)
   {
     bool grown = false;
-    const int rc = ensure_build_buffers(ctx, m, n, ng, npad, ntile8, &grown);
+    const int rc = ensure_build_buffers(ctx, m, n, g, &grown);
     if (rc) return rc;
     if (grown)      // no word may carry a tag by accident
       HIP_TRY(ctx, hipMemsetAsync(m->scan_state.p, 0, m->scan_state.cap() * sizeof(unsigned long long), st));
@@ -862,33 +874,30 @@ static int queue_build(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   }
-  fill_f2_kernel<<<grid_for(npad, 256), 256, 0, ctx->side>>>(m->cent.p, npad, INFINITY, m->tiles.p, ntile8);
+  fill_f2_kernel<<<grid_for(g.npad, 256), 256, 0, ctx->side>>>(m->cent.p, g.npad, INFINITY, m->tiles.p, g.ntile8);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->side));
 
   // 3. bucket the points by voxel, cloud order kept inside a bucket
-  map_count_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, m->count.p, m->counters.p);
-  const int ntiles = (int)((ng + kScanTile - 1) / kScanTile);
+  map_count_kernel<<<point_blocks(n), 256, 0, st>>>(xy, stride, n, G, m->count.p, m->counters.p);
   int *const start = m->start.p + 4;
-  const int big_cap = (int)(n / kBigVoxel + 1);
   const unsigned tag = next_scan_tag(m);
-  scan_onepass_kernel<<<ntiles, kScanBlock, 0, st>>>(m->count.p, ng, m->scan_state.p, tag, ntiles, m->counters.p + 3, start,
-                                                     m->big.p, m->counters.p + 2, big_cap);
-  map_scatter_kernel<<<grid_for(n, 256), 256, 0, st>>>(xy, stride, n, G, start, m->count.p, m->perm.p);
+  scan_onepass_kernel<<<g.ntiles, kScanBlock, 0, st>>>(m->count.p, g.ng, m->scan_state.p, tag, g.ntiles, m->counters.p + 3, start,
+                                                       m->big.p, m->counters.p + 2, g.big_cap);
+  map_scatter_kernel<<<point_blocks(n), 256, 0, st>>>(xy, stride, n, G, start, m->count.p, m->perm.p);
   HIP_TRY(ctx, hipGetLastError());
   m->count_clean = true;
-  const unsigned small_blocks = (unsigned)((ng + kOrderVoxPerBlock - 1) / kOrderVoxPerBlock);
-  map_order_kernel<<<small_blocks + kBigBlocks, 256, 0, st>>>(start, ng, small_blocks, m->big.p, m->counters.p + 2, big_cap, m->perm.p, xy, stride, m->pts.p);
+  map_order_kernel<<<g.small_blocks + kBigBlocks, 256, 0, st>>>(start, g.ng, g.small_blocks, m->big.p, m->counters.p + 2, g.big_cap, m->perm.p, xy, stride, m->pts.p);
   HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
 
   // 4. per-voxel statistics -> centroid grid + cell records + bucketed raw points
-  const LeafParams L = leaf_of(prm);
+  const LeafParams L = leaf_of(&m->prm);
   // evm1 -- the end of the build, for ndt_kernel timing and for launches on other streams -- rides on this kernel's own
   // dispatch (an hipEventRecord is a packet of its own: ~6 us between two kernels, tools/launch_gap.py)
-  hipExtLaunchKernelGGL(map_finalize_kernel<false>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, nullptr, ctx->evm1, 0, G, L, start,
-                        m->pts.p, m->cent.p, m->rec.p, m->npts_grid.p, m->counters.p, m->occ.p, m->tiles.p, tiles_w,
+  hipExtLaunchKernelGGL(map_finalize_kernel<false>, dim3(g.finalize_blocks), dim3(256), 0, st, nullptr, ctx->evm1, 0, G, L, start,
+                        m->pts.p, m->cent.p, m->rec.p, m->npts_grid.p, m->counters.p, m->occ.p, m->tiles.p, g.tiles_w,
                         (const BuildBatch *)nullptr);
   HIP_TRY(ctx, hipGetLastError());
-  set_view(m, n, prm, G);
+  build_queued(m, G);
   return NDT_OK;
 }
 
@@ -911,6 +920,17 @@ static int wait_for_readers(ndt_ctx *ctx, const ndt_map *m, hipStream_t st, bool
   return NDT_OK;
 }
 
+// A build takes the map over from the launches that read its previous one.  Those are the caller's to order before the build
+// (stream order / ndt_ctx_wait_launch), except for deferred fitness kernels (NDT_OPT_DEFER_FITNESS, their context's own stream):
+// waited for here.  The list starts again with the launches that read the new build.
+static int take_over_from_readers(ndt_ctx *ctx, ndt_map *m, hipStream_t st) {
+  const int rc = wait_for_readers(ctx, m, st, /*deferred_only=*/true);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(g_live_mu);
+  m->readers.clear();
+  return NDT_OK;
+}
+
 // The build in two halves.  build_begin queues everything: the bounding box of the cloud (getMinMax3D) with its
 // read-back on the side stream, and -- instead of idling the GPU during that round trip -- the rest of the build with
 // the voxel grid of the previous build of this map (a SLAM local map keeps its voxel bounding box for many scans).
@@ -918,23 +938,19 @@ static int wait_for_readers(ndt_ctx *ctx, const ndt_map *m, hipStream_t st, bool
 // Any failure leaves the map without a speculative grid.
 static int build_begin(ndt_ctx *ctx, ndt_map *m, const float *xy, size_t n, size_t stride, const ndt_params *prm) {
   hipStream_t st = ctx->stream;
-  m->prm = *prm; m->n = n; m->info_valid = false;
-  m->pend_xy = xy; m->pend_stride = stride; m->pend_queued = false;
-  // A launch that read the previous build is the caller's to order before this one (stream order / ndt_ctx_wait_launch), except
-  // for deferred fitness kernels (NDT_OPT_DEFER_FITNESS, their context's own stream): waited for here, ahead of the fork below.
-  { int rc = wait_for_readers(ctx, m, st, /*deferred_only=*/true); if (rc) return rc; }
-  { std::lock_guard<std::mutex> lk(g_live_mu); m->readers.clear(); }
+  build_requested(m, xy, n, stride, prm);
+  { const int rc = take_over_from_readers(ctx, m, st); if (rc) return rc; }      // (ahead of the fork below)
   // The bounding box (and the reset of the centroid grid, queue_build) run on a side stream beside the bucketing
   // chain -- a dozen dependent kernels whose launch latencies add up -- and are joined in front of the statistics.
   // (One record serves as the start of the build's timing and as the fork.)
   HIP_TRY(ctx, hipEventRecord(ctx->evm0, st));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->evm0, 0));
-  map_minmax_kernel<<<grid_for(n, 256 * 32, 128), 256, 0, ctx->side>>>(xy, stride, n, m->bounds.p, m->bounds.p + 4);
+  map_minmax_kernel<<<minmax_blocks(n), 256, 0, ctx->side>>>(xy, stride, n, m->bounds.p, m->bounds.p + 4);
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_bounds.p, m->bounds.p + 4, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->side));
   HIP_TRY(ctx, hipEventRecord(ctx->evb, ctx->side));
   const float inv_leaf = 1.0f / prm->resolution;
   if (m->have_grid && m->grid.inv_leaf == inv_leaf) {
-    int rc = queue_build(ctx, m, xy, n, stride, prm, m->grid);
+    int rc = queue_build(ctx, m, m->grid);
     if (rc) return rc;
     m->pend_queued = true;                                 // (evm1, what launches queued before build_end wait for: queue_build)
   }
@@ -997,11 +1013,11 @@ static int build_end(ndt_ctx *ctx, ndt_map *m) {
       int rc = wait_for_readers(ctx, m, st, /*deferred_only=*/false);
       if (rc) return rc;
     }
-    int rc = queue_build(ctx, m, m->pend_xy, m->n, m->pend_stride, prm, G, /*requeue=*/m->pend_queued);
+    int rc = queue_build(ctx, m, G, /*requeue=*/m->pend_queued);
     if (rc) return rc;
     redone = m->pend_queued ? 1 : 0;
   }
-  m->grid = G; m->have_grid = true;
+  m->grid = G; m->have_grid = true;            // (again: a refused build between begin and end has withdrawn the grid, ndt_map_build_dev)
   ctx->map_ms_pending = true;
   return redone;                               // asynchronous from here on (stream order)
 }
@@ -1144,9 +1160,7 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
   const size_t o_box = align256(sizeof(BuildBatch)), o_pre0 = o_box + S * sizeof(BoxJob), o_jobs = align256(o_pre0 + npre * sizeof(unsigned));
   const size_t o_pre = o_jobs + align256(S * sizeof(BuildJob)), bytes = o_pre + (kBbKernels - 1) * npre * sizeof(unsigned);
   int rc;
-  if (!ctx->ev_bb) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_bb, hipEventDisableTiming));
-  if (ctx->bb_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_bb)); ctx->bb_pending = false; }
-  if ((rc = ctx->h_bb.ensure(ctx, bytes))) return rc;
+  if ((rc = ctx->bb_tab.reserve(ctx, bytes))) return rc;           // (waits for the previous batched build's upload)
   if ((rc = ctx->d_bb.ensure(ctx, bytes))) return rc;
   if ((rc = ctx->h_boxes.ensure(ctx, 16 * S))) return rc;
   {
@@ -1158,7 +1172,7 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
       HIP_TRY(ctx, hipMemcpy(ctx->d_boxes.p, init.data(), init.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     }
   }
-  unsigned char *h = ctx->h_bb.p, *d = ctx->d_bb.p;
+  unsigned char *h = ctx->bb_tab.h.p, *d = ctx->d_bb.p;
   BuildBatch &BB = *(BuildBatch *)h;
   const BuildBatch *dbb = (const BuildBatch *)d;
   BoxJob *hbox = (BoxJob *)(h + o_box);
@@ -1183,9 +1197,9 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
     hpre[k][S] = (unsigned)tot;
     return NDT_OK;
   };
-  if ((rc = prefixes(kBbMinmax, 256, [&](size_t s) { return grid_for(n[s], 256 * 32, 128); }))) return rc;
-  if ((rc = prefixes(kBbCount, 256, [&](size_t s) { return grid_for(n[s], 256); }))) return rc;
-  if ((rc = prefixes(kBbScatter, 256, [&](size_t s) { return grid_for(n[s], 256); }))) return rc;
+  if ((rc = prefixes(kBbMinmax, 256, [&](size_t s) { return minmax_blocks(n[s]); }))) return rc;
+  if ((rc = prefixes(kBbCount, 256, [&](size_t s) { return point_blocks(n[s]); }))) return rc;
+  if ((rc = prefixes(kBbScatter, 256, [&](size_t s) { return point_blocks(n[s]); }))) return rc;
 
   // 1. the bounding boxes of all clouds, read back with one copy and one wait
   for (size_t s = 0; s < S; ++s) { hbox[s].xy = xy[s]; hbox[s].n = n[s]; }
@@ -1199,6 +1213,8 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
 
   // 2. the grids; the refusals that need the boxes change nothing either
   std::vector<GridDims> grids(S);
+  std::vector<BuildGeom> geom;
+  geom.reserve(S);
   for (size_t s = 0; s < S; ++s) {
     const std::string which = fn + ": map " + std::to_string(s);
     const unsigned *hb = ctx->h_boxes.p + 16 * s + 4;
@@ -1207,15 +1223,13 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
     const bool prev = m && m->have_grid && m->grid.inv_leaf == 1.0f / prm[s].resolution;   // (what ndt_map_rebuild_begin would queue ahead)
     bool same = false;
     if ((rc = grid_of_box(ctx, hb, &prm[s], prev ? &m->grid : nullptr, &grids[s], &same, which))) return rc;
+    geom.emplace_back(n[s], grids[s]);
   }
-  auto ng_of = [&](size_t s) { return (size_t)grids[s].div_x * grids[s].div_y; };
-  auto big_cap_of = [&](size_t s) { return (int)(n[s] / kBigVoxel + 1); };
-  auto small_of = [&](size_t s) { return (unsigned)((ng_of(s) + kOrderVoxPerBlock - 1) / kOrderVoxPerBlock); };
-  if ((rc = prefixes(kBbScan, kScanBlock, [&](size_t s) { return (ng_of(s) + kScanTile - 1) / kScanTile; }))) return rc;
-  if ((rc = prefixes(kBbOrder, 256, [&](size_t s) {
-         return (size_t)small_of(s) + std::min<size_t>(kBigBlocks, ((size_t)big_cap_of(s) + kBigWavesPerBlock - 1) / kBigWavesPerBlock); })))
+  if ((rc = prefixes(kBbScan, kScanBlock, [&](size_t s) { return geom[s].ntiles; }))) return rc;
+  if ((rc = prefixes(kBbOrder, 256, [&](size_t s) {      // (the big voxels' blocks: no more than the map can need, not kBigBlocks for each)
+         return (size_t)geom[s].small_blocks + std::min<size_t>(kBigBlocks, ((size_t)geom[s].big_cap + kBigWavesPerBlock - 1) / kBigWavesPerBlock); })))
     return rc;
-  if ((rc = prefixes(kBbFinalize, 256, [&](size_t s) { return (ng_of(s) + 255) / 256; }))) return rc;
+  if ((rc = prefixes(kBbFinalize, 256, [&](size_t s) { return geom[s].finalize_blocks; }))) return rc;
 
   // 3. the maps: new ones created, every one's readers waited for as build_begin does, buffers, jobs
   std::vector<ndt_map *> mp(S, nullptr), made;
@@ -1232,19 +1246,17 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
   }
   for (size_t s = 0; s < S; ++s) {
     ndt_map *m = mp[s];
-    const GridDims &G = grids[s];
-    if ((rc = wait_for_readers(ctx, m, st, /*deferred_only=*/true))) return failed(rc);
-    { std::lock_guard<std::mutex> lk(g_live_mu); m->readers.clear(); }
-    const size_t ng = ng_of(s), npad = (size_t)G.gw * G.gh, ntile8 = ntile8_of(G);
+    const BuildGeom &g = geom[s];
+    if ((rc = take_over_from_readers(ctx, m, st))) return failed(rc);
     bool state_grown = false;
-    if ((rc = ensure_build_buffers(ctx, m, n[s], ng, npad, ntile8, &state_grown))) return failed(rc);
+    if ((rc = ensure_build_buffers(ctx, m, n[s], g, &state_grown))) return failed(rc);
     BuildJob &J = hjob[s];
-    J.xy = xy[s]; J.n = n[s]; J.G = G; J.L = leaf_of(&prm[s]);
+    J.xy = xy[s]; J.n = n[s]; J.G = grids[s]; J.L = leaf_of(&prm[s]);
     J.count = m->count.p; J.start = m->start.p + 4; J.perm = m->perm.p; J.big = m->big.p; J.npts_grid = m->npts_grid.p;
     J.counters = m->counters.p; J.scan_state = m->scan_state.p; J.tag = next_scan_tag(m);
-    J.ntiles = (int)((ng + kScanTile - 1) / kScanTile); J.big_cap = big_cap_of(s); J.small_blocks = small_of(s);
-    J.pts = m->pts.p; J.cent = m->cent.p; J.rec = m->rec.p; J.occ = m->occ.p; J.tiles = m->tiles.p; J.tiles_w = tiles_w_of(G);
-    J.ng = ng; J.npad = npad; J.ntile8 = ntile8;
+    J.ntiles = g.ntiles; J.big_cap = g.big_cap; J.small_blocks = g.small_blocks;
+    J.pts = m->pts.p; J.cent = m->cent.p; J.rec = m->rec.p; J.occ = m->occ.p; J.tiles = m->tiles.p; J.tiles_w = g.tiles_w;
+    J.ng = g.ng; J.npad = g.npad; J.ntile8 = g.ntile8;
     J.zero_count = m->count_clean ? 0 : m->count.cap();
     J.zero_state = state_grown ? m->scan_state.cap() : 0;
     m->count_clean = false;
@@ -1256,11 +1268,9 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
 
   // 4. one upload of the jobs, then each kernel of the chain once (evm1 on the last one's dispatch, as queue_build)
   {
-    hipError_t e = hipMemcpyAsync(d + o_jobs, h + o_jobs, bytes - o_jobs, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_bb, st);
+    const hipError_t e = ctx->bb_tab.upload(d + o_jobs, o_jobs, bytes - o_jobs, st);
     if (e != hipSuccess) return failed(fail(ctx, NDT_E_HIP, fn + ": job table upload: " + hipGetErrorString(e)));
   }
-  ctx->bb_pending = true;
   // (the batched instances take every other argument from their map's job)
   const GridDims G0{}; const LeafParams L0{};
   fill_f2_kernel<true><<<hpre[kBbFill][S], 256, 0, st>>>(nullptr, 0, INFINITY, nullptr, 0, dbb);
@@ -1273,16 +1283,11 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
                         (unsigned *)nullptr, (u64 *)nullptr, 0, dbb);
   { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return failed(fail(ctx, NDT_E_HIP, fn + ": launch: " + hipGetErrorString(e))); }
 
-  // 5. the host side of every map: as queue_build / build_end leave it
+  // 5. the host side of every map
   for (size_t s = 0; s < S; ++s) {
-    ndt_map *m = mp[s];
-    m->prm = prm[s]; m->n = n[s]; m->info_valid = false;
-    m->pend_xy = xy[s]; m->pend_stride = stride; m->pend_queued = false;
-    m->ng = ng_of(s); m->npad = (size_t)grids[s].gw * grids[s].gh;
-    set_view(m, n[s], &prm[s], grids[s]);
-    m->grid = grids[s]; m->have_grid = true;
-    m->count_clean = true;                             // (map_scatter takes back what map_count added)
-    maps[s] = m;
+    build_requested(mp[s], xy[s], n[s], stride, &prm[s]);
+    build_queued(mp[s], grids[s]);
+    maps[s] = mp[s];
   }
   ctx->map_ms_pending = true;
   return NDT_OK;
@@ -1341,18 +1346,15 @@ int ndt_map_export(const ndt_map *cm, int *cell_idx, float *cent_xy, double *mea
   ndt_ctx *ctx = m->ctx;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t ng = m->ng, npad = m->npad;
-  int *hn = (int *)malloc(ng * sizeof(int));
-  float2 *hc = (float2 *)malloc(npad * sizeof(float2));
-  double *hr = (double *)malloc(npad * 8 * sizeof(double));
-  if (!hn || !hc || !hr) { free(hn); free(hc); free(hr); return NDT_E_NOMEM; }
-  hipError_t e1 = hipMemcpyAsync(hn, m->npts_grid.p, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e2 = hipMemcpyAsync(hc, m->cent.p, npad * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e3 = hipMemcpyAsync(hr, m->rec.p, npad * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  std::vector<int> hn(ng);
+  std::vector<float2> hc(npad);
+  std::vector<double> hr(npad * 8);
+  hipError_t e1 = hipMemcpyAsync(hn.data(), m->npts_grid.p, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e2 = hipMemcpyAsync(hc.data(), m->cent.p, npad * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e3 = hipMemcpyAsync(hr.data(), m->rec.p, npad * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   hipError_t e4 = hipStreamSynchronize(ctx->stream);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-    free(hn); free(hc); free(hr);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess)
     return fail(ctx, NDT_E_HIP, "ndt_map_export: copy failed");
-  }
   size_t k = 0;
   const int gw = m->view.gw, dx = m->view.div_x;
   for (size_t g = 0; g < ng; ++g) {
@@ -1364,7 +1366,6 @@ int ndt_map_export(const ndt_map *cm, int *cell_idx, float *cent_xy, double *mea
     icov[3 * k] = hr[pg * 8 + 2]; icov[3 * k + 1] = hr[pg * 8 + 3]; icov[3 * k + 2] = hr[pg * 8 + 4];
     ++k;
   }
-  free(hn); free(hc); free(hr);
   return NDT_OK;
 }
 
@@ -1387,7 +1388,7 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   if ((rc = S.sorted.ensure(ctx, slots + 2))) return rc;
   if ((rc = S.recs.ensure(ctx, (size_t)B))) return rc;
   if ((rc = S.maps.ensure(ctx, (size_t)B * (kRegionCells / 8)))) return rc;
-  if (!S.ready) { HIP_TRY(ctx, hipEventCreate(&S.ev0)); HIP_TRY(ctx, hipEventCreate(&S.ready)); }
+  if (!S.ready && ((rc = S.ev0.create(ctx)) || (rc = S.ready.create(ctx)))) return rc;
   // Of the map it takes the grid's geometry (by value, now) and reads nothing on the device: no wait for a build that may be
   // queued or running -- a two-phase rebuild that ends with another grid simply leaves this set unused.  It is ordered behind
   // the last launch that read this set (its fitness kernels walk the set's ordered copies).
@@ -1400,12 +1401,10 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   const OptParams O = opt_of(map->prm);
   const int ncu = ctx->workgroups > 0 ? ctx->workgroups : ctx->num_cus;
   const int grid = B < ncu ? B : ncu;
-  if (map->prm.transform_sse)
-    hipExtLaunchKernelGGL((ndt_order_kernel<true>), dim3(grid), dim3(kBlock), 0, st, S.ev0, S.ready, 0, V, O, scans,
+  with_bool(map->prm.transform_sse != 0, [&](auto Sse) {
+    hipExtLaunchKernelGGL((ndt_order_kernel<decltype(Sse)::value>), dim3(grid), dim3(kBlock), 0, st, S.ev0, S.ready, 0, V, O, scans,
                           (const unsigned long long *)offsets, B, shared_scan, inits, S.sorted.p, S.recs.p, (unsigned *)S.maps.p);
-  else
-    hipExtLaunchKernelGGL((ndt_order_kernel<false>), dim3(grid), dim3(kBlock), 0, st, S.ev0, S.ready, 0, V, O, scans,
-                          (const unsigned long long *)offsets, B, shared_scan, inits, S.sorted.p, S.recs.p, (unsigned *)S.maps.p);
+  });
   HIP_TRY(ctx, hipGetLastError());
   S.scans = scans; S.offsets = offsets; S.inits = inits; S.map = map; S.B = B; S.shared_scan = shared_scan; S.total_points = total_points;
   S.min_bx = V.min_bx; S.min_by = V.min_by; S.div_x = V.div_x; S.div_y = V.div_y; S.inv_leaf = V.inv_leaf;
@@ -1506,26 +1505,18 @@ void prof_report(const unsigned long long *hp, int B) {
 }
 #endif
 
-// Host-pointer matches: stage scans (records of `stride` bytes, repacked to float2 on the device when stride != 8),
-// offsets and initial guesses, run the batch, copy the records back; synchronous.
-int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_t stride, const uint64_t *offsets, int B,
-                     int shared_scan, const double *inits, ndt_result *out, double *trace, int trace_cap, int *trace_rows) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!map || !scans || !offsets || !inits || !out || B <= 0 || stride < 8 || (stride & 3))
-    return fail(ctx, NDT_E_ARG, "ndt_align_batch: bad arguments");
-  if (map->ctx->device != ctx->device) return fail(ctx, NDT_E_ARG, "ndt_align_batch: the map was built on another device");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t nscan = shared_scan ? 1 : (size_t)B;
-  const size_t npts = (size_t)(offsets[nscan] - offsets[0]);
-  if (npts == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: empty scans");
-  for (size_t b = 0; b < nscan; ++b)
-    if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch: offsets not monotone");
+// The staged part of a host-pointer match call, from where the scratch bracket opens to where it closes -- the same for
+// one map and for many: scans (records of `stride` bytes, repacked to float2 on the device when stride != 8), offsets, initial
+// guesses and (multi-map calls) map_of go up, `launch(d_map_of, d_trace, d_rows, d_prof)` queues the batch between ev0 and
+// ev1, the records and the trace come back.  Asynchronous: align_host_finish waits.
+template <typename Launch>
+int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t stride, const uint64_t *offsets, int B,
+                      int shared_scan, const double *inits, const int *map_of, ndt_result *out, double *trace, int trace_cap,
+                      int *trace_rows, Launch &&launch) {
   int rc;
-  if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
   ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
   if ((rc = scope.open())) return rc;
-  const size_t ntot = (size_t)offsets[nscan];
+  const size_t nscan = shared_scan ? 1 : (size_t)B, ntot = (size_t)offsets[nscan];
   if ((rc = ctx->d_scan.ensure(ctx, ntot * 8))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, nscan + 1))) return rc;
   if ((rc = ctx->d_init.ensure(ctx, (size_t)B * 3))) return rc;
@@ -1537,6 +1528,7 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
     d_trace = ctx->d_trace.p; d_rows = ctx->d_rows.p;
     HIP_TRY(ctx, hipMemsetAsync(d_trace, 0, (size_t)B * trace_cap * 64, st));
   }
+  if (map_of && (rc = ctx->d_map_of.ensure(ctx, (size_t)B))) return rc;
   if (stride == 8) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scans, ntot * 8, hipMemcpyHostToDevice, st));
   } else {                                     // e.g. pcl::PointXYZ (16 bytes): strided upload, packed on the device
@@ -1546,6 +1538,7 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
   }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init.p, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
+  if (map_of) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map_of.p, map_of, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
   unsigned long long *d_prof = nullptr;
 #ifdef NDT_DIAG
   const bool want_prof = getenv("NDT_PROF") != nullptr;
@@ -1555,10 +1548,7 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
   if (want_prof) { d_prof = prof_buf.p; HIP_TRY(ctx, hipMemsetAsync(d_prof, 0, prof_bytes, st)); }
 #endif
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  if ((rc = launch_align(ctx, map, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B,
-                         shared_scan, ntot, ctx->d_init.p, ctx->d_res.p, d_trace, trace_cap,
-                         d_rows, d_prof)))
-    return rc;
+  if ((rc = launch(map_of ? ctx->d_map_of.p : nullptr, d_trace, d_rows, d_prof))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
 #ifdef NDT_DIAG
   if (want_prof) {
@@ -1575,6 +1565,47 @@ int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_
   }
   return scope.close();
 }
+
+// Host-pointer matches against one map: the refusals, the wait for the map's build, then the staged part.
+int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_t stride, const uint64_t *offsets, int B,
+                     int shared_scan, const double *inits, ndt_result *out, double *trace, int trace_cap, int *trace_rows) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!map || !scans || !offsets || !inits || !out || B <= 0 || stride < 8 || (stride & 3))
+    return fail(ctx, NDT_E_ARG, "ndt_align_batch: bad arguments");
+  if (map->ctx->device != ctx->device) return fail(ctx, NDT_E_ARG, "ndt_align_batch: the map was built on another device");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t nscan = shared_scan ? 1 : (size_t)B;
+  const size_t npts = (size_t)(offsets[nscan] - offsets[0]);
+  if (npts == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: empty scans");
+  for (size_t b = 0; b < nscan; ++b)
+    if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch: offsets not monotone");
+  if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  return align_host_staged(ctx, st, scans, stride, offsets, B, shared_scan, inits, nullptr, out, trace, trace_cap, trace_rows,
+                           [&](const int *, double *d_trace, int *d_rows, unsigned long long *d_prof) {
+                             return launch_align(ctx, map, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B,
+                                                 shared_scan, (size_t)offsets[nscan], ctx->d_init.p, ctx->d_res.p, d_trace, trace_cap,
+                                                 d_rows, d_prof);
+                           });
+}
+
+// The end of a host-pointer wrapper whose result has a length only the device knows: W words come back (w[1]: the count when
+// W > 1, else w[0]), the stream is synchronised, `check(w)` -- the wrapper's own refusal, an NDT code -- looks at them, then
+// that many elements of `elem` bytes are copied and the stream is synchronised again.
+template <size_t W, typename Check>
+int read_back_counted(ndt_ctx *ctx, hipStream_t st, const uint64_t *d_words, const void *d_out, size_t elem, void *out_host, size_t *n_out,
+                      Check &&check) {
+  uint64_t w[W] = {};
+  HIP_TRY(ctx, hipMemcpyAsync(w, d_words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (const int rc = check(w)) return rc;
+  const size_t cnt = (size_t)w[W > 1];
+  *n_out = cnt;
+  if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_host, d_out, cnt * elem, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+int no_check(const uint64_t *) { return NDT_OK; }
 
 int align_host_finish(ndt_ctx *ctx) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1626,14 +1657,15 @@ int check_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_
 
 // Stream order behind the builds of the maps (each on the stream of the context that built it), then the launch.
 int queue_multi(ndt_ctx *ctx, MultiMaps &mm, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
-                size_t total_points, int shared_scan, const double *inits, ndt_result *out, bool defer) {
+                size_t total_points, int shared_scan, const double *inits, ndt_result *out, bool defer,
+                unsigned long long *prof = nullptr) {
   std::vector<const ndt_ctx *> waited;
   for (const ndt_map *m : mm.distinct) {
     if (st == m->ctx->stream || std::find(waited.begin(), waited.end(), m->ctx) != waited.end()) continue;
     HIP_TRY(ctx, hipStreamWaitEvent(st, m->ctx->evm1, 0));
     waited.push_back(m->ctx);
   }
-  return launch_align(ctx, mm.maps[0], st, scans, offsets, B, shared_scan, total_points, inits, out, nullptr, 0, nullptr, nullptr,
+  return launch_align(ctx, mm.maps[0], st, scans, offsets, B, shared_scan, total_points, inits, out, nullptr, 0, nullptr, prof,
                       nullptr, defer, &mm);
 }
 
@@ -1674,26 +1706,13 @@ int ndt_align_batch_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, 
   if (offsets[nscan] == offsets[0]) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: empty scans");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
-  if ((rc = ctx->d_scan.ensure(ctx, ntot * 8))) return rc;
-  if ((rc = ctx->d_off.ensure(ctx, nscan + 1))) return rc;
-  if ((rc = ctx->d_init.ensure(ctx, (size_t)B * 3))) return rc;
-  if ((rc = ctx->d_res.ensure(ctx, (size_t)B))) return rc;
-  if (map_of_host && (rc = ctx->d_map_of.ensure(ctx, (size_t)B))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scans, ntot * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init.p, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
-  if (map_of_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map_of.p, map_of_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-  mm.map_of = map_of_host ? ctx->d_map_of.p : nullptr;
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  if ((rc = queue_multi(ctx, mm, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B, ntot, shared_scan,
-                        ctx->d_init.p, ctx->d_res.p, false)))
-    return rc;
-  HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_res.p, (size_t)B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  return align_host_finish(ctx);
+  rc = align_host_staged(ctx, st, scans, 8, offsets, B, shared_scan, inits, map_of_host, out, nullptr, 0, nullptr,
+                         [&](const int *d_map_of, double *, int *, unsigned long long *d_prof) {
+                           mm.map_of = d_map_of;
+                           return queue_multi(ctx, mm, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B, ntot,
+                                              shared_scan, ctx->d_init.p, ctx->d_res.p, false, d_prof);
+                         });
+  return rc ? rc : align_host_finish(ctx);
 }
 
 int ndt_align_batch_trace(ndt_ctx *ctx, const ndt_map *map, const float *scans, const uint64_t *offsets,
@@ -1805,23 +1824,19 @@ int ndt_eval_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, s
   if ((rc = ctx->d_tmp.ensure(ctx, (size_t)grid * kAcc * 8))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
   {
-    const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
     const MapView &V = map->view; const double sn = map->prm.snap_thresh;
     const float *ds = (const float *)ctx->d_scan.p; double *dt = (double *)ctx->d_tmp.p;
-    if (sse && incl)       ndt_eval_kernel<true, true><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
-    else if (sse)          ndt_eval_kernel<true, false><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
-    else if (incl)         ndt_eval_kernel<false, true><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
-    else                   ndt_eval_kernel<false, false><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
+    with_bool(map->prm.transform_sse != 0, [&](auto Sse) { with_bool(map->prm.radius_inclusive != 0, [&](auto Incl) {
+      ndt_eval_kernel<decltype(Sse)::value, decltype(Incl)::value><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
+    }); });
   }
   HIP_TRY(ctx, hipGetLastError());
-  double *hp = (double *)malloc((size_t)grid * kAcc * 8);
-  if (!hp) return NDT_E_NOMEM;
-  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp.p, (size_t)grid * kAcc * 8, hipMemcpyDeviceToHost, st);
+  std::vector<double> hp((size_t)grid * kAcc);
+  hipError_t e = hipMemcpyAsync(hp.data(), ctx->d_tmp.p, hp.size() * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { free(hp); return fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, hipGetErrorString(e));
   double t[kAcc] = {0};
   for (int b = 0; b < grid; ++b) for (int k = 0; k < kAcc; ++k) t[k] += hp[b * kAcc + k];
-  free(hp);
   const double w = map->view.d1 * map->view.d2;
   if (score) *score = -map->view.d1 * t[0];
   if (g) { g[0] = w * t[1]; g[1] = w * t[2]; g[2] = w * t[3]; }
@@ -1848,14 +1863,12 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n
   ndt_fitness_kernel<<<grid, 256, 0, st>>>(map->view, (const float *)ctx->d_scan.p, stride, (int)n, T,
                                            (double *)ctx->d_tmp.p);
   HIP_TRY(ctx, hipGetLastError());
-  double *hp = (double *)malloc((size_t)grid * 16);
-  if (!hp) return NDT_E_NOMEM;
-  hipError_t e = hipMemcpyAsync(hp, ctx->d_tmp.p, (size_t)grid * 16, hipMemcpyDeviceToHost, st);
+  std::vector<double> hp((size_t)grid * 2);
+  hipError_t e = hipMemcpyAsync(hp.data(), ctx->d_tmp.p, hp.size() * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { free(hp); return fail(ctx, NDT_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, hipGetErrorString(e));
   double sum = 0, cnt = 0;
   for (int b = 0; b < grid; ++b) { sum += hp[2 * b]; cnt += hp[2 * b + 1]; }
-  free(hp);
   *fitness = cnt > 0 ? sum / cnt : DBL_MAX;
   return NDT_OK;
 }
@@ -1965,13 +1978,7 @@ int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, f
   HIP_TRY(ctx, hipMemcpyAsync(d_in, xy_host, n * stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_offs, raw, sizeof(raw), hipMemcpyHostToDevice, st));
   if ((rc = ndt_prefilter_batch_dev(ctx, d_in, stride, d_offs, 1, n, leaf, d_out, d_offs + 2, st))) return rc;
-  uint64_t fo[2] = {0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(fo, d_offs + 2, sizeof(fo), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  *n_out = (size_t)fo[1];
-  HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)fo[1] * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return read_back_counted<2>(ctx, st, d_offs + 2, d_out, sizeof(float2), out_xy_host, n_out, no_check);
 }
 
 namespace {
@@ -2058,16 +2065,11 @@ int ndt_resample(ndt_ctx *ctx, const double *xy_host, size_t n, size_t stride, d
   if ((rc = ndt_resample_batch_dev(ctx, d_in, stride, d_offs, 1, n, space, space_thre, d_out, nullptr, d_offs + 2,
                                    (int *)(d_offs + 4), st)))
     return rc;
-  uint64_t fo[3] = {0, 0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(fo, d_offs + 2, sizeof(fo), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  int scan_status = 0;
-  memcpy(&scan_status, &fo[2], sizeof(int));
-  if (scan_status != NDT_OK) return fail(ctx, NDT_E_ARG, "ndt_resample: the scan holds a non-finite coordinate");
-  *n_out = (size_t)fo[1];
-  HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)fo[1] * sizeof(double2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return read_back_counted<3>(ctx, st, d_offs + 2, d_out, sizeof(double2), out_xy_host, n_out, [&](const uint64_t *fo) {
+    int scan_status = 0;
+    memcpy(&scan_status, &fo[2], sizeof(int));
+    return scan_status != NDT_OK ? fail(ctx, NDT_E_ARG, "ndt_resample: the scan holds a non-finite coordinate") : NDT_OK;
+  });
 }
 
 int ndt_scan_to_map_batch_dev(ndt_ctx *ctx, const double *xy, size_t stride, const uint64_t *offsets, int B,
@@ -2162,13 +2164,7 @@ int ndt_remove_neighbors(ndt_ctx *ctx, const float *base_xy_host, size_t base_st
   if ((rc = ndt_remove_neighbors_dev(ctx, d_base, base_stride, n_base, n_list ? d_list : nullptr, n_list ? list_stride : 8,
                                      n_list, thre_neighbor, d_out, ctx->d_off.p, st)))
     return rc;
-  uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  *n_out = (size_t)cnt;
-  HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)cnt * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, no_check);
 }
 
 }  // extern "C"
@@ -2195,6 +2191,38 @@ struct MmLayout {
   PfPrev *prevs = nullptr;   // pinned (batched calls)
 };
 
+// One submap's scan triples (appended to P.pairs) and the pieces of its cloud (appended to `pieces`) in the order
+// Submap::makeMap appends them -- the rule of the single and the batched assembly.  cut: rn_cutoff(D.thre_neighbor).
+// Returns the units (stretches of kMmUnit points) the pieces take.
+struct MmPiece { const float *p; size_t n; int job; };      // job: the piece's triple in P.pairs, or -1
+size_t submap_pieces(const ndt_submap_desc &D, size_t stride, float cut, MmPlan *P, std::vector<MmPiece> *pieces) {
+  auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
+  auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
+  size_t nu = 0;
+  auto piece = [&](int i, int job) { pieces->push_back({scan_ptr(i), scan_n(i), job}); nu += (scan_n(i) + kMmUnit - 1) / kMmUnit; };
+  if (D.remove_moving) {
+    if (D.first_submap) piece(0, -1);
+    for (int i = 0; i + 2 < D.n_scans; ++i)
+      if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
+        piece(i + 1, (int)P->pairs.size());
+        P->pairs.push_back({scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut});
+      }
+    if (D.newest) piece(D.n_scans - 1, -1);
+  } else {
+    for (int i = D.first_submap ? 0 : 2; i < D.n_scans; ++i) piece(i, -1);
+  }
+  return nu;
+}
+
+// The units of pieces [first, last), which belong to submap `sub`, written from `units` on; returns the end.
+MmUnit *fill_units(MmUnit *units, const MmPiece *first, const MmPiece *last, size_t stride, unsigned sub) {
+  for (const MmPiece *pc = first; pc != last; ++pc)
+    for (size_t o = 0; o < pc->n; o += kMmUnit)
+      *units++ = MmUnit{(const float *)((const char *)pc->p + o * stride), (unsigned)stride,
+                        (unsigned)std::min<size_t>(kMmUnit, pc->n - o), pc->job, sub};
+  return units;
+}
+
 size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
 size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
@@ -2215,9 +2243,8 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t
   const size_t total = L.o_diff + list_pts * 8 + 64;
   int rc;                                            // (the scratch bracket around mm_prepare + mm_run is the caller's: ScratchScope)
   if ((rc = ctx->d_mm.ensure(ctx, total))) return rc;
-  if (ctx->mm_pending) { HIP_TRY(ctx, hipEventSynchronize(ctx->ev_mm)); ctx->mm_pending = false; }
-  if (L.o_ucnt > ctx->h_mm.cap() && (rc = ctx->h_mm.alloc(ctx, 2 * L.o_ucnt + 256))) return rc;
-  char *d = (char *)ctx->d_mm.p, *h = (char *)ctx->h_mm.p;
+  if ((rc = ctx->mm_tab.reserve(ctx, L.o_ucnt))) return rc;      // (waits for the previous call's upload)
+  char *d = (char *)ctx->d_mm.p, *h = (char *)ctx->mm_tab.h.p;
   L.jobs = (MmJob *)h;
   L.units = (MmUnit *)(h + L.o_units);
   L.subs = (MmSub *)(h + L.o_subs);
@@ -2248,11 +2275,7 @@ int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, 
            uint64_t *n_out, hipStream_t st) {
   char *d = (char *)ctx->d_mm.p;
   const size_t bytes = nu ? L.o_units + nu * sizeof(MmUnit) : nj * sizeof(MmJob);
-  if (bytes) {
-    HIP_TRY(ctx, hipMemcpyAsync(d, ctx->h_mm.p, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_mm, st));
-    ctx->mm_pending = true;
-  }
+  if (bytes) HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, bytes, st));
   if (nj) make_map_diff_kernel<false><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, resol);
   if (nu) {
     const MmUnit *units = (const MmUnit *)(d + L.o_units);
@@ -2272,9 +2295,7 @@ int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, 
 int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, size_t ns, float *cloud_xy, uint64_t *cloud_off,
                  int *status, hipStream_t st) {
   char *d = (char *)ctx->d_mm.p;
-  HIP_TRY(ctx, hipMemcpyAsync(d, ctx->h_mm.p, L.o_prev + ns * sizeof(PfPrev), hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev_mm, st));
-  ctx->mm_pending = true;
+  HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, L.o_prev + ns * sizeof(PfPrev), st));
   const MmUnit *units = (const MmUnit *)(d + L.o_units);
   unsigned *ucnt = (unsigned *)(d + L.o_ucnt);
   unsigned long long *uoff = (unsigned long long *)(d + L.o_uoff), *keep = (unsigned long long *)(d + L.o_keep);
@@ -2337,14 +2358,9 @@ int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t ba
   if ((rc = ndt_difference_extraction_dev(ctx, d_base, base_stride, n_base, d_test, test_stride, n_test, resol, d_out,
                                           ctx->d_off.p, st)))
     return rc;
-  uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (cnt == ~0ull) return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: the clouds span more than 2^30 voxels");
-  *n_out = (size_t)cnt;
-  if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)cnt * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
+    return *cnt == ~0ull ? fail(ctx, NDT_E_ARG, "ndt_difference_extraction: the clouds span more than 2^30 voxels") : NDT_OK;
+  });
 }
 
 int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans,
@@ -2359,39 +2375,19 @@ int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy, size_t stride, const u
       return fail(ctx, NDT_E_ARG, "ndt_make_map: offsets must be non-decreasing, scans below 2^29 points");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  auto scan_ptr = [&](int i) { return (const float *)((const char *)scans_xy + (size_t)offsets[i] * stride); };
-  auto scan_n = [&](int i) { return (size_t)(offsets[i + 1] - offsets[i]); };
   MmPlan P;
   P.sa = P.sb = stride;
-  if (remove_moving)
-    for (int i = 0; i + 2 < n_scans; ++i)
-      if (scan_n(i + 1))     // an empty middle scan contributes nothing
-        P.pairs.push_back({scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1)});
-  // the pieces of p_cloud in the order Submap::makeMap appends them: (scan, triple or -1)
-  std::vector<std::pair<int, int>> pieces;
-  if (remove_moving) {
-    if (first_submap) pieces.push_back({0, -1});
-    int j = 0;
-    for (int i = 0; i + 2 < n_scans; ++i) if (scan_n(i + 1)) pieces.push_back({i + 1, j++});
-    if (newest) pieces.push_back({n_scans - 1, -1});
-  } else {
-    for (int i = first_submap ? 0 : 2; i < n_scans; ++i) pieces.push_back({i, -1});
-  }
-  size_t nu = 0;
-  for (const auto &pc : pieces) nu += (scan_n(pc.first) + kMmUnit - 1) / kMmUnit;
+  // (one submap; its resol and thre_neighbor reach the kernels as arguments, mm_run: the jobs' own copies stay unset)
+  const ndt_submap_desc D = {scans_xy, offsets, n_scans, first_submap, newest, remove_moving, 0.0, 0.0, nullptr, 0};
+  std::vector<MmPiece> pieces;
+  const size_t nu = submap_pieces(D, stride, 0.f, &P, &pieces);
   P.unit_room = nu;
   MmLayout L;
   int rc;
   ScratchScope scope(ctx, st);
   if ((rc = scope.open())) return rc;
   if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
-  size_t u = 0;
-  for (const auto &pc : pieces) {
-    const size_t n = scan_n(pc.first);
-    for (size_t o = 0; o < n; o += kMmUnit)
-      L.units[u++] = MmUnit{(const float *)((const char *)scan_ptr(pc.first) + o * stride), (unsigned)stride,
-                            (unsigned)std::min<size_t>(kMmUnit, n - o), pc.second, 0u};
-  }
+  fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
   if (nu == 0) HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(uint64_t), st));
   if ((rc = mm_run(ctx, L, P.pairs.size(), nu, resol, thre_neighbor, out_xy, n_out, st))) return rc;
   return scope.close();
@@ -2421,14 +2417,9 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
   if ((rc = ndt_make_map_dev(ctx, d_in, stride, rel.data(), n_scans, first_submap, newest, remove_moving, resol,
                              thre_neighbor, d_out, ctx->d_off.p, st)))
     return rc;
-  uint64_t cnt = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->d_off.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (cnt == ~0ull) return fail(ctx, NDT_E_ARG, "ndt_make_map: a scan triple spans more than 2^30 voxels");
-  *n_out = (size_t)cnt;
-  if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, (size_t)cnt * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
+    return *cnt == ~0ull ? fail(ctx, NDT_E_ARG, "ndt_make_map: a scan triple spans more than 2^30 voxels") : NDT_OK;
+  });
 }
 
 }  // extern "C"
@@ -2484,34 +2475,20 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  // the triples (jobs) and the pieces of every submap's cloud, in the order ndt_make_map_dev lists them for one submap
-  struct Piece { const float *p; size_t n; int job; };
+  // the triples (jobs) and the pieces of every submap's cloud
   MmPlan P;
   P.sa = P.sb = stride;
   P.n_subs = (size_t)n_subs;
-  std::vector<Piece> pieces;
+  std::vector<MmPiece> pieces;
   std::vector<size_t> piece_end((size_t)n_subs);       // pieces of submap s: [piece_end[s - 1], piece_end[s])
   size_t nu = 0, cap_cloud = 0, total_prev = 0;
   double cut_of = 0.0; float cut = 0.f; bool have_cut = false;
   for (int s = 0; s < n_subs; ++s) {
     const ndt_submap_desc &D = subs[s];
-    auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
-    auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
-    auto piece = [&](int i, int job) { pieces.push_back({scan_ptr(i), scan_n(i), job}); nu += (scan_n(i) + kMmUnit - 1) / kMmUnit; };
-    if (D.remove_moving) {
-      if (!have_cut || !same_bits(&cut_of, &D.thre_neighbor, sizeof(double))) {
-        cut = rn_cutoff(D.thre_neighbor); cut_of = D.thre_neighbor; have_cut = true;
-      }
-      if (D.first_submap) piece(0, -1);
-      for (int i = 0; i + 2 < D.n_scans; ++i)
-        if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
-          piece(i + 1, (int)P.pairs.size());
-          P.pairs.push_back({scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut});
-        }
-      if (D.newest) piece(D.n_scans - 1, -1);
-    } else {
-      for (int i = D.first_submap ? 0 : 2; i < D.n_scans; ++i) piece(i, -1);
+    if (D.remove_moving && (!have_cut || !same_bits(&cut_of, &D.thre_neighbor, sizeof(double)))) {
+      cut = rn_cutoff(D.thre_neighbor); cut_of = D.thre_neighbor; have_cut = true;      // (a search over float bits: once per distinct bound)
     }
+    nu += submap_pieces(D, stride, cut, &P, &pieces);
     piece_end[s] = pieces.size();
     cap_cloud += submap_points(D);
     total_prev += D.n_prev;
@@ -2523,14 +2500,11 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
   ScratchScope scope(ctx, st);
   if ((rc = scope.open())) return rc;
   if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
-  size_t u = 0, pc = 0;
+  MmUnit *u = L.units;
   for (int s = 0; s < n_subs; ++s) {
-    L.subs[s].u0 = (unsigned)u;
-    for (; pc < piece_end[s]; ++pc)
-      for (size_t o = 0; o < pieces[pc].n; o += kMmUnit)
-        L.units[u++] = MmUnit{(const float *)((const char *)pieces[pc].p + o * stride), (unsigned)stride,
-                              (unsigned)std::min<size_t>(kMmUnit, pieces[pc].n - o), pieces[pc].job, (unsigned)s};
-    L.subs[s].u1 = (unsigned)u;
+    L.subs[s].u0 = (unsigned)(u - L.units);
+    u = fill_units(u, pieces.data() + (s ? piece_end[s - 1] : 0), pieces.data() + piece_end[s], stride, (unsigned)s);
+    L.subs[s].u1 = (unsigned)(u - L.units);
     L.prevs[s] = PfPrev{subs[s].n_prev ? subs[s].prev_xy : nullptr, (unsigned long long)subs[s].n_prev};
   }
   if ((rc = mm_run_batch(ctx, L, P.pairs.size(), nu, (size_t)n_subs, cloud_xy, cloud_off, status, st))) return rc;
