@@ -522,6 +522,83 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
                         float *cloud_xy_host, uint64_t *cloud_off_host, float *target_xy_host, uint64_t *target_off_host,
                         int *status_host);
 
+/* Device-resident lockstep sessions: replaces, for n_sessions independent SLAM sessions stepped together, the whole of
+ * ScanMatcher::matchScan + growMap (src/ScanMatcher.cpp:4-116), PointCloudMap::addPose / addPoints / makeLocalMap /
+ * makeGlobalMap (src/PointCloudMap.cpp:44-134) and the part of FrontEnd::process that drives them (src/FrontEnd.cpp), with
+ * every session's scans, submap clouds, local map, NDT map, last pose and covariance kept in device memory from step to
+ * step.  One ndt_sessions_step takes the new raw scans and odometry up and brings the fused poses down (DESIGN.md 4.10;
+ * the call sequence in INTEGRATION.md 5.3).  A step is the step of the chain ndt_resample_batch_dev ->
+ * ndt_prefilter_batch_dev -> ndt_predict_batch_dev -> ndt_align_batch_multi_dev -> ndt_fuse_batch_dev ->
+ * ndt_scan_to_map_batch_dev -> ndt_local_map_batch_dev -> ndt_map_build_batch_dev with PointCloudMap's bookkeeping on the
+ * host, byte for byte, except that of a submap's scan triples only the newest is computed (the survivors of the earlier ones
+ * are kept), and that nothing but the records below crosses the bus.  The number of kernels, copies and host waits (three)
+ * of a step does not depend on n_sessions or on the length of a submap. */
+typedef struct ndt_session_params {   /* one set of parameters per session set; a sweep uses several sets */
+  ndt_params      match;              /* PoseEstimator's (include/ndt_slam/PoseEstimator.h:63-84); grid_margin as given (the shims use 8) */
+  ndt_fuse_params fuse;               /* coeNDTCov, coeVel, coeOmega, delTime, score_thre */
+  double space, space_thre;           /* ScanPointResampler (src/ScanPointResampler.cpp:4-62) */
+  float  leaf;                        /* LeafSize: source pre-filter (src/PoseEstimator.cpp:6-10) and Submap::filterPoints (src/PointCloudMap.cpp:4-13) */
+  double resol, thre_neighbor;        /* PCFilter (include/ndt_slam/PCFilter.h:20-23) */
+  double sep_thre;                    /* PointCloudMap sepThre (src/PointCloudMap.cpp:72) */
+  int    remove_moving;
+} ndt_session_params;
+typedef struct ndt_sessions ndt_sessions;
+typedef struct ndt_session_step {     /* one per session and step, HOST memory */
+  double pose[3];                     /* fused pose (tx, ty, th[deg]) = what savePose stores (src/ScanMatcher.cpp:76-80) */
+  double cov[9];
+  double cost;                        /* fitness with the 1e7 sentinel (src/PoseEstimator.cpp:43-46); 0 for a first scan */
+  int    stepped;                     /* 0: inactive or skipped this step, state untouched */
+  int    matched;                     /* 0: first scan, taken as it is at its odometry pose (src/ScanMatcher.cpp:9-22) */
+  int    successful;                  /* matchScan's return value (1 for a first scan) */
+  int    status;                      /* NDT_OK, or NDT_E_ARG for a raw scan with a non-finite coordinate: that session alone
+                                         skips the step; also NDT_E_ARG (stepped = 1) when the newest scan triple spans more
+                                         than 2^30 voxels: that session's clouds of this step are empty and its map is kept */
+  int    submap;                      /* index of the session's current submap after the step */
+  int    split;                       /* 1: this step closed a submap (src/PointCloudMap.cpp:72-90) */
+} ndt_session_step;
+typedef struct ndt_sessions_stats {   /* of the most recent step */
+  uint64_t h2d_bytes, d2h_bytes;      /* bytes the step copied to and from the device */
+  int host_waits;                     /* times the step waited for the device on the host */
+  int triples_run;                    /* scan triples the step computed (at most one per stepped session) */
+  int sessions_stepped;
+} ndt_sessions_stats;
+
+/* ndt_default_params (grid_margin 8, as the shims set it) + ndt_fuse_default_params + the values of ndt_mapping.launch:8-36. */
+int ndt_session_default_params(ndt_session_params *p);
+/* Refusals of every call below (NDT_E_ARG, synchronous, nothing changed, the text names the first offending index): a NULL
+ * context or set, checked first ("null context" / "null session set"); n_sessions < 1; parameters the single entry points
+ * refuse (leaf <= 0, resolution <= 0, del_time <= 0, a bad stride, resol not positive and finite with remove_moving, the
+ * resampler's parameter rules, ndt_resample_capacity); NULL arrays; offsets that decrease; an open ndt_map_rebuild_begin on the
+ * context.  A HIP failure inside a step leaves the SET unusable (every later call on it returns NDT_E_HIP; destroy it) and
+ * the context usable.  The set works on the context's stream and is bound to the context's host thread; destroy it before
+ * the context.  The maps are owned by the set and destroyed with it. */
+int ndt_sessions_create(ndt_ctx *ctx, int n_sessions, const ndt_session_params *prm, ndt_sessions **out);
+int ndt_sessions_destroy(ndt_sessions *s);
+/* One lockstep step (src/FrontEnd.cpp:20-33 for every session at once).  raw scans: LPoint2D x, y doubles
+ * (include/ndt_slam/LPoint2D.h:17-18) at stride_bytes (>= 16, a multiple of 8), session i's scan = points
+ * [raw_offsets[i], raw_offsets[i+1]) (raw_offsets[S+1] in points; an empty range is legal: the scan then has no points, and
+ * a matched session gets the not-converged cost as ndt_align_batch_multi's NDT_E_ARG record gives it).  odo: S x 3
+ * (tx, ty, th[deg]), the scan's odometry pose.  active: S bytes or NULL (= all); a session with active[i] == 0 is not touched
+ * (start_frame, end_frame, logs of different lengths).  out_host: S records.  Synchronous. */
+int ndt_sessions_step(ndt_sessions *s, const double *raw_xy_host, size_t stride_bytes,
+                      const uint64_t *raw_offsets_host, const double *odo_host,
+                      const unsigned char *active, ndt_session_step *out_host);
+/* the same with raw_xy and odo in DEVICE memory; offsets, active and out stay on the host */
+int ndt_sessions_step_dev(ndt_sessions *s, const double *raw_xy_dev, size_t stride_bytes,
+                          const uint64_t *raw_offsets_host, const double *odo_dev,
+                          const unsigned char *active, ndt_session_step *out_host);
+/* Views of the resident state of session i, valid until the next step: the local map (PointCloudMap::localMap_cloud,
+ * src/PointCloudMap.cpp:119-134; packed float2 in device memory) with the NDT map built from it, and the current submap's
+ * cloud (Submap::p_cloud after makeMap, src/PointCloudMap.cpp:15-39).  Before the session's first step: no points, no map. */
+int ndt_sessions_local_map(const ndt_sessions *s, int i, const float **xy_dev, size_t *n, const ndt_map **map);
+int ndt_sessions_submap_cloud(const ndt_sessions *s, int i, const float **xy_dev, size_t *n);
+/* makeGlobalMap as of now (src/PointCloudMap.cpp:101-117): every closed submap's p_cloud, then filterPoints of the current
+ * one, to HOST memory (packed float2).  sub_offsets: n_submaps + 1 entries, in points.  A call with out_xy_host == NULL
+ * returns the sizes (*n_out, *n_submaps); capacity in points. */
+int ndt_sessions_global_map(ndt_sessions *s, int i, float *out_xy_host, size_t capacity, size_t *n_out,
+                            uint64_t *sub_offsets, int *n_submaps);
+int ndt_sessions_get_stats(const ndt_sessions *s, ndt_sessions_stats *out);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

@@ -44,6 +44,30 @@ class SubmapDesc(C.Structure):
                 ("prev_xy", C.c_void_p), ("n_prev", C.c_size_t)]
 
 
+class SessionParams(C.Structure):
+    """ndt_session_params (include/ndt_mi355x.h): the parameters of one session set."""
+    _fields_ = [("match", Params), ("fuse", FuseParams), ("space", C.c_double), ("space_thre", C.c_double),
+                ("leaf", C.c_float), ("resol", C.c_double), ("thre_neighbor", C.c_double), ("sep_thre", C.c_double),
+                ("remove_moving", C.c_int)]
+
+
+class SessionStep(C.Structure):
+    """ndt_session_step (include/ndt_mi355x.h): one session's record of one lockstep step."""
+    _fields_ = [("pose", C.c_double * 3), ("cov", C.c_double * 9), ("cost", C.c_double), ("stepped", C.c_int),
+                ("matched", C.c_int), ("successful", C.c_int), ("status", C.c_int), ("submap", C.c_int),
+                ("split", C.c_int)]
+
+
+class SessionsStats(C.Structure):
+    """ndt_sessions_stats (include/ndt_mi355x.h): transfers and host waits of the most recent step."""
+    _fields_ = [("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("host_waits", C.c_int),
+                ("triples_run", C.c_int), ("sessions_stepped", C.c_int)]
+
+
+SESSION_STEP_DTYPE = np.dtype([("pose", "f8", 3), ("cov", "f8", 9), ("cost", "f8"), ("stepped", "i4"), ("matched", "i4"),
+                               ("successful", "i4"), ("status", "i4"), ("submap", "i4"), ("split", "i4")], align=True)
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -72,6 +96,8 @@ EXPORTS = [
     "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
     "ndt_align_batch_multi", "ndt_align_batch_multi_dev", "ndt_map_build_batch", "ndt_map_build_batch_dev",
     "ndt_local_map_batch", "ndt_local_map_batch_dev", "ndt_prefilter_batch",
+    "ndt_session_default_params", "ndt_sessions_create", "ndt_sessions_destroy", "ndt_sessions_step", "ndt_sessions_step_dev",
+    "ndt_sessions_local_map", "ndt_sessions_submap_cloud", "ndt_sessions_global_map", "ndt_sessions_get_stats",
 ]
 
 
@@ -139,6 +165,15 @@ def lib():
     L.ndt_local_map_batch.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp]
     L.ndt_local_map_batch_dev.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp, vp]
     L.ndt_prefilter_batch.argtypes = [vp, vp, sz, vp, i, C.c_float, vp, vp]
+    L.ndt_session_default_params.argtypes = [C.POINTER(SessionParams)]
+    L.ndt_sessions_create.argtypes = [vp, i, C.POINTER(SessionParams), C.POINTER(vp)]
+    L.ndt_sessions_destroy.argtypes = [vp]
+    L.ndt_sessions_step.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.ndt_sessions_step_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.ndt_sessions_local_map.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
+    L.ndt_sessions_submap_cloud.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz)]
+    L.ndt_sessions_global_map.argtypes = [vp, i, vp, sz, C.POINTER(sz), vp, C.POINTER(i)]
+    L.ndt_sessions_get_stats.argtypes = [vp, C.POINTER(SessionsStats)]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -257,6 +292,34 @@ def default_fuse_params(**kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_session_params(**kw):
+    """ndt_session_default_params (the launch file's values), fields overridden by keyword; match_* and fuse_* reach the
+    nested ndt_params / ndt_fuse_params (match_resolution=0.5, fuse_score_thre=1.0)."""
+    p = SessionParams()
+    lib().ndt_session_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k.startswith("match_") and hasattr(p.match, k[6:]):
+            setattr(p.match, k[6:], v)
+        elif k.startswith("fuse_") and hasattr(p.fuse, k[5:]):
+            setattr(p.fuse, k[5:], v)
+        elif hasattr(p, k) and k not in ("match", "fuse"):
+            setattr(p, k, v)
+        else:
+            raise AttributeError(k)
+    return p
+
+
+def session_params_from_launch(params):
+    """ndt_session_params of a dict of launch-file parameters (replay.LAUNCH_PARAMS' names)."""
+    q = params
+    return default_session_params(
+        match_resolution=q["Resolution"], match_step_size=q["StepSize"], match_trans_eps=q["TransformationEpsilon"],
+        match_max_iter=q["MaximumIterations"], fuse_coe_ndt_cov=q["coeNDTCov"], fuse_coe_vel=q["coeVel"],
+        fuse_coe_omega=q["coeOmega"], fuse_del_time=q["delTime"], fuse_score_thre=q["score_thre"], space=q["space"],
+        space_thre=q["space_thre"], leaf=q["LeafSize"], resol=q["resol"], thre_neighbor=q["thre_neighbor"],
+        sep_thre=q["sepThre"], remove_moving=int(bool(q["removeMoving"])))
 
 
 def _f32c(a):
@@ -508,6 +571,103 @@ class Context:
 
     def __del__(self):
         # at interpreter shutdown the HIP runtime may already be gone: leave the handles to the OS
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sessions:
+    """ndt_sessions: n device-resident SLAM sessions stepped together (include/ndt_mi355x.h)."""
+
+    def __init__(self, ctx, n_sessions, params=None):
+        self.ctx = ctx
+        self.params = params if params is not None else default_session_params()
+        self.n = int(n_sessions)
+        self.h = C.c_void_p()
+        ctx.check(lib().ndt_sessions_create(ctx.h, self.n, C.byref(self.params), C.byref(self.h)), "ndt_sessions_create")
+
+    def _active(self, active):
+        if active is None:
+            return None
+        a = np.ascontiguousarray(active, dtype=np.uint8)
+        if len(a) != self.n:
+            raise ValueError("active needs one entry per session")
+        return a
+
+    def step(self, scans, odo, active=None):
+        """ndt_sessions_step: scans = one [n_i, 2] float64 raw scan per session (empty ones allowed), odo = [S, 3]
+        (tx, ty, th[deg]) -> the S records as a numpy array of SESSION_STEP_DTYPE."""
+        scans = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2) for x in scans]
+        if len(scans) != self.n:
+            raise ValueError("step needs one scan per session")
+        off = np.zeros(self.n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in scans])
+        allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2))
+        odo = np.ascontiguousarray(odo, dtype=np.float64).reshape(self.n, 3)
+        a = self._active(active)
+        out = np.zeros(self.n, dtype=SESSION_STEP_DTYPE)
+        self.ctx.check(lib().ndt_sessions_step(self.h, allp.ctypes.data if len(allp) else None, 16, off.ctypes.data,
+                                               odo.ctypes.data, None if a is None else a.ctypes.data, out.ctypes.data),
+                       "ndt_sessions_step")
+        return out
+
+    def step_dev(self, raw_ptr, stride, raw_offsets, odo_ptr, active=None):
+        """ndt_sessions_step_dev: device addresses of the raw scans and the odometry; `raw_offsets` a host uint64 array."""
+        off = np.ascontiguousarray(raw_offsets, dtype=np.uint64)
+        a = self._active(active)
+        out = np.zeros(self.n, dtype=SESSION_STEP_DTYPE)
+        self.ctx.check(lib().ndt_sessions_step_dev(self.h, raw_ptr, stride, off.ctypes.data, odo_ptr,
+                                                   None if a is None else a.ctypes.data, out.ctypes.data),
+                       "ndt_sessions_step_dev")
+        return out
+
+    def local_map(self, i):
+        """(device address, points, ndt_map handle or None) of session i's local map; valid until the next step."""
+        p, n, m = C.c_void_p(), C.c_size_t(), C.c_void_p()
+        self.ctx.check(lib().ndt_sessions_local_map(self.h, i, C.byref(p), C.byref(n), C.byref(m)), "ndt_sessions_local_map")
+        return p.value, n.value, m.value
+
+    def submap_cloud(self, i):
+        """(device address, points) of session i's current Submap::p_cloud; valid until the next step."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self.ctx.check(lib().ndt_sessions_submap_cloud(self.h, i, C.byref(p), C.byref(n)), "ndt_sessions_submap_cloud")
+        return p.value, n.value
+
+    def map_export(self, i):
+        """ndt_map_export of session i's map (the set keeps owning it), or None before it has one."""
+        _, _, m = self.local_map(i)
+        if not m:
+            return None
+        view = Map.adopt(self.ctx, m, self.params.match)
+        try:
+            return view.export()
+        finally:
+            view.h = C.c_void_p()                      # not ours to destroy
+
+    def global_map(self, i):
+        """ndt_sessions_global_map: (globalMap_cloud [n, 2] float32, [each submap's cloud]) as makeGlobalMap leaves them."""
+        n, k = C.c_size_t(), C.c_int()
+        self.ctx.check(lib().ndt_sessions_global_map(self.h, i, None, 0, C.byref(n), None, C.byref(k)), "ndt_sessions_global_map")
+        out = np.zeros((n.value, 2), dtype=np.float32)
+        off = np.zeros(k.value + 1, dtype=np.uint64)
+        self.ctx.check(lib().ndt_sessions_global_map(self.h, i, out.ctypes.data if n.value else None, n.value, C.byref(n),
+                                                     off.ctypes.data, C.byref(k)), "ndt_sessions_global_map")
+        return out, [out[int(off[j]):int(off[j + 1])] for j in range(k.value)]
+
+    def stats(self):
+        st = SessionsStats()
+        self.ctx.check(lib().ndt_sessions_get_stats(self.h, C.byref(st)), "ndt_sessions_get_stats")
+        return st
+
+    def close(self):
+        if self.h:
+            lib().ndt_sessions_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
         if sys is None or sys.is_finalizing():
             return
         try:

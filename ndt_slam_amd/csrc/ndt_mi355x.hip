@@ -2580,3 +2580,161 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
 }
 
 }  // extern "C"
+
+// ---- device-resident lockstep sessions (ndt_sessions_*; state, kernels and the step in ndt_sessions.hip.h) ----
+
+#include "ndt_sessions.hip.h"
+
+namespace {
+
+// the refusals every call on a set starts with; `i` < 0: the call names no session
+int check_set(const ndt_sessions *s, int i, bool with_index, const char *fn) {
+  if (!s) return fail(nullptr, NDT_E_ARG, "null session set");
+  if (s->dead) return fail(s->ctx, NDT_E_HIP, std::string(fn) + ": the set is unusable after a HIP failure inside a step");
+  if (with_index && (i < 0 || i >= s->S)) return fail(s->ctx, NDT_E_ARG, std::string(fn) + ": session " + std::to_string(i) + " out of range");
+  return NDT_OK;
+}
+
+int step_entry(ndt_sessions *s, const double *raw_host, const double *raw_dev, size_t stride, const uint64_t *raw_offsets,
+               const double *odo_host, const double *odo_dev, const unsigned char *active, ndt_session_step *out, const char *fn) {
+  int rc = check_set(s, 0, false, fn);
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const std::string f(fn);
+  if (!raw_offsets || !out || (!odo_host && !odo_dev)) return fail(ctx, NDT_E_ARG, f + ": NULL array (raw_offsets, odo or out)");
+  if (stride < 16 || (stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad stride (need stride_bytes >= 16 and % 8 == 0)");
+  for (int i = 0; i < s->S; ++i)
+    if (raw_offsets[i + 1] < raw_offsets[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": offsets decrease");
+  if (raw_offsets[s->S] > raw_offsets[0] && !raw_host && !raw_dev) return fail(ctx, NDT_E_ARG, f + ": NULL array (raw_xy)");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  rc = ss_step(s, raw_host, raw_dev, stride, raw_offsets, odo_host, odo_dev, active, out);
+  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
+    s->dead = true;
+    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;      // (the context stays usable: nothing of the set is in flight)
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_session_default_params(ndt_session_params *p) {
+  if (!p) return NDT_E_ARG;
+  memset(p, 0, sizeof(*p));
+  ndt_default_params(&p->match);
+  p->match.resolution = 0.3f; p->match.step_size = 0.1; p->match.trans_eps = 0.01; p->match.max_iter = 35;
+  p->match.grid_margin = 8;
+  ndt_fuse_default_params(&p->fuse);
+  p->fuse.coe_ndt_cov = 1.0; p->fuse.coe_vel = 0.1; p->fuse.coe_omega = 0.5; p->fuse.del_time = 0.5; p->fuse.score_thre = 0.5;
+  p->space = 0.05; p->space_thre = 0.25; p->leaf = 0.05f; p->resol = 0.05; p->thre_neighbor = 0.2; p->sep_thre = 10.0;
+  p->remove_moving = 1;
+  return NDT_OK;
+}
+
+int ndt_sessions_create(ndt_ctx *ctx, int n_sessions, const ndt_session_params *prm, ndt_sessions **out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (n_sessions < 1) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: n_sessions < 1");
+  if (!prm || !out) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: NULL argument (prm or out)");
+  int rc = ss_check_params(ctx, *prm);
+  if (rc) return rc;
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: an ndt_map_rebuild_begin is open on the context");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ndt_sessions *s = new (std::nothrow) ndt_sessions;
+  if (!s) return fail(ctx, NDT_E_NOMEM, "ndt_sessions_create: out of memory");
+  s->ctx = ctx; s->S = n_sessions; s->prm = *prm;
+  s->ses.resize((size_t)n_sessions);
+  const size_t S = (size_t)n_sessions;
+  auto zeroed = [&](auto &buf, size_t n) {
+    int r = buf.ensure(ctx, n);
+    if (!r && hipMemsetAsync(buf.p, 0, buf.bytes, ctx->stream) != hipSuccess) r = fail(ctx, NDT_E_HIP, "ndt_sessions_create: hipMemsetAsync failed");
+    return r;
+  };
+  if ((rc = zeroed(s->last_pose, 3 * S)) || (rc = zeroed(s->last_cov, 9 * S)) || (rc = zeroed(s->prev_odo, 3 * S)) ||
+      (rc = zeroed(s->plen, S)) || (rc = zeroed(s->motion, 3 * S)) || (rc = zeroed(s->pred, 3 * S)) || (rc = zeroed(s->init, 3 * S)) ||
+      (rc = zeroed(s->fused, 3 * S)) || (rc = zeroed(s->cov, 9 * S)) || (rc = zeroed(s->rs_status, S)) || (rc = zeroed(s->successful, S)) ||
+      (rc = zeroed(s->res, S)) || (rc = zeroed(s->rec, S)) || (rc = zeroed(s->cloud_off, S + 1)) || (rc = zeroed(s->target_off, S + 1)) ||
+      (rc = zeroed(s->status, S)) || (rc = zeroed(s->tri_off, S + 1)) || (rc = zeroed(s->tri_status, S))) {
+    delete s;
+    return rc;
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) { delete s; return fail(ctx, NDT_E_HIP, "ndt_sessions_create: hipStreamSynchronize failed"); }
+  *out = s;
+  return NDT_OK;
+}
+
+int ndt_sessions_destroy(ndt_sessions *s) {
+  if (!s) return fail(nullptr, NDT_E_ARG, "null session set");
+  ndt_ctx *ctx = s->ctx;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)e;
+  for (auto &Q : s->ses)
+    if (Q.map) { ndt_map_destroy(Q.map); Q.map = nullptr; }
+  delete s;
+  return NDT_OK;
+}
+
+int ndt_sessions_step(ndt_sessions *s, const double *raw_xy_host, size_t stride, const uint64_t *raw_offsets, const double *odo_host,
+                      const unsigned char *active, ndt_session_step *out) {
+  return step_entry(s, raw_xy_host, nullptr, stride, raw_offsets, odo_host, nullptr, active, out, "ndt_sessions_step");
+}
+
+int ndt_sessions_step_dev(ndt_sessions *s, const double *raw_xy_dev, size_t stride, const uint64_t *raw_offsets, const double *odo_dev,
+                          const unsigned char *active, ndt_session_step *out) {
+  return step_entry(s, nullptr, raw_xy_dev, stride, raw_offsets, nullptr, odo_dev, active, out, "ndt_sessions_step_dev");
+}
+
+int ndt_sessions_local_map(const ndt_sessions *s, int i, const float **xy_dev, size_t *n, const ndt_map **map) {
+  const int rc = check_set(s, i, true, "ndt_sessions_local_map");
+  if (rc) return rc;
+  const SsSession &Q = s->ses[(size_t)i];
+  if (xy_dev) *xy_dev = Q.has_target && Q.t_n ? (const float *)(s->target[Q.buf].p + Q.t_off) : nullptr;
+  if (n) *n = Q.has_target ? (size_t)Q.t_n : 0;
+  if (map) *map = Q.map;
+  return NDT_OK;
+}
+
+int ndt_sessions_submap_cloud(const ndt_sessions *s, int i, const float **xy_dev, size_t *n) {
+  const int rc = check_set(s, i, true, "ndt_sessions_submap_cloud");
+  if (rc) return rc;
+  const SsSession &Q = s->ses[(size_t)i];
+  if (xy_dev) *xy_dev = Q.has_target && Q.c_n ? (const float *)(s->cloud[Q.buf].p + Q.c_off) : nullptr;
+  if (n) *n = Q.has_target ? (size_t)Q.c_n : 0;
+  return NDT_OK;
+}
+
+int ndt_sessions_global_map(ndt_sessions *s, int i, float *out_xy_host, size_t capacity, size_t *n_out, uint64_t *sub_offsets,
+                            int *n_submaps) {
+  const int rc = check_set(s, i, true, "ndt_sessions_global_map");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const SsSession &Q = s->ses[(size_t)i];
+  const size_t n_closed = (size_t)Q.closed_off.back(), n_tail = Q.has_target ? (size_t)(Q.t_n - Q.n_prev) : 0;
+  if (out_xy_host && capacity < n_closed + n_tail)
+    return fail(ctx, NDT_E_ARG, "ndt_sessions_global_map: session " + std::to_string(i) + ": capacity below the map's " +
+                                    std::to_string(n_closed + n_tail) + " points");
+  if (n_out) *n_out = n_closed + n_tail;
+  if (n_submaps) *n_submaps = Q.n_closed + 1;
+  if (sub_offsets) {
+    for (size_t k = 0; k < Q.closed_off.size(); ++k) sub_offsets[k] = Q.closed_off[k];
+    sub_offsets[Q.closed_off.size()] = n_closed + n_tail;
+  }
+  if (!out_xy_host) return NDT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n_closed) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, Q.closed.p, n_closed * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+  if (n_tail)
+    HIP_TRY(ctx, hipMemcpyAsync(out_xy_host + 2 * n_closed, s->target[Q.buf].p + Q.t_off + Q.n_prev, n_tail * sizeof(float2),
+                                hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return NDT_OK;
+}
+
+int ndt_sessions_get_stats(const ndt_sessions *s, ndt_sessions_stats *out) {
+  if (!s) return fail(nullptr, NDT_E_ARG, "null session set");
+  if (!out) return fail(s->ctx, NDT_E_ARG, "ndt_sessions_get_stats: NULL out");
+  *out = s->stats;
+  return NDT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,605 @@
+// Device-resident lockstep sessions (ndt_sessions_*): the state of S independent SLAM sessions and the
+// step that advances all of them -- ScanMatcher::matchScan + growMap (src/ScanMatcher.cpp:4-116), PointCloudMap's
+// addPose / addPoints / makeLocalMap (src/PointCloudMap.cpp:44-134) as FrontEnd::process drives them (src/FrontEnd.cpp) --
+// without a scan, a cloud or a map leaving the device.  Included at the end of ndt_mi355x.hip: the step is made of the
+// launches of the batched entry points (resampler, pre-filter, prediction, multi-map match, fusion, local-map assembly
+// kernels, target filter, batched map build) on the session set's own resident arrays, plus five small kernels of its own:
+//   session_select_kernel     per session: the odometry pose (first scan), the fused pose (matched) or nothing; carries
+//                             last_pose / last_cov / prev_odo forward and writes the step record
+//   scan_to_map_dst_kernel    growMap's transform, scan b to its own destination (the session's scan store)
+//   session_units_kernel      the 256-point units of every newest triple's middle scan, from one job per session
+//   session_plan_kernel       per session: the cloud's length and offset, the append of the new survivors to the cached
+//                             prefix, and the gather table of prefix ++ survivors ++ newest scan
+//   seg_copy_kernel           every move of a step (carried-over scans, closed clouds, gathers): a table of (src, dst, n)
+
+namespace {
+
+struct SsCopy { const float2 *src; float2 *dst; unsigned long long n; };
+
+// what the host knows of one session's cloud at a step: Submap::makeMap's branches (src/PointCloudMap.cpp:15-39) with the
+// prefix = [scans[0] of a first submap] ++ the survivors of every triple computed so far (remove_moving), or the scans
+// before the newest (otherwise)
+struct SsPlan {
+  float2 *prefix;                  // the session's prefix store
+  const float2 *piece;             // what this step appends to the prefix: a whole scan (tri < 0) ...
+  unsigned long long piece_n;
+  int tri;                         // ... or the survivors of triple `tri`: points [tri_off[tri], tri_off[tri + 1]) of tri_xy
+  int stepped;                     // 0: no cloud this step
+  int reset;                       // 1: a new submap, the prefix starts empty
+  int with_newest;                 // the newest scan closes the cloud
+  const float2 *newest;
+  unsigned long long newest_n;
+};
+
+constexpr int kSsNone = 0, kSsFirst = 1, kSsMatch = 2;      // a session's part in a step (SsMode)
+
+__global__ void __launch_bounds__(256)
+seg_copy_kernel(const SsCopy *__restrict__ tab, int n_seg) {
+  for (int s = blockIdx.y; s < n_seg; s += gridDim.y) {
+    const SsCopy c = tab[s];
+    for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < c.n;
+         j += (unsigned long long)gridDim.x * blockDim.x)
+      c.dst[j] = c.src[j];
+  }
+}
+
+// One lane per session.  mode: kSsNone / kSsFirst / kSsMatch; rs_status: the resampler's (NDT_E_ARG: a non-finite coordinate).
+__global__ void __launch_bounds__(256)
+session_select_kernel(const int *__restrict__ mode, const int *__restrict__ rs_status, const double *__restrict__ odo_cur,
+                      const ndt_result *__restrict__ res, const double *__restrict__ fused, const double *__restrict__ cov,
+                      const int *__restrict__ successful, int S, double *__restrict__ last_pose,
+                      double *__restrict__ last_cov, double *__restrict__ prev_odo, ndt_session_step *__restrict__ rec) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S) return;
+  ndt_session_step r;
+  for (int i = 0; i < 3; ++i) r.pose[i] = 0.0;
+  for (int i = 0; i < 9; ++i) r.cov[i] = 0.0;
+  r.cost = 0.0; r.stepped = 0; r.matched = 0; r.successful = 0; r.status = NDT_OK; r.submap = 0; r.split = 0;
+  const int m = mode[b];
+  if (m != kSsNone && rs_status[b] != NDT_OK) r.status = NDT_E_ARG;
+  else if (m == kSsFirst) {
+    for (int i = 0; i < 3; ++i) r.pose[i] = odo_cur[3 * b + i];
+    r.stepped = 1; r.successful = 1;
+  } else if (m == kSsMatch) {
+    const ndt_result q = res[b];
+    for (int i = 0; i < 3; ++i) r.pose[i] = fused[3 * b + i];
+    for (int i = 0; i < 9; ++i) r.cov[i] = cov[9 * b + i];
+    r.cost = (q.status == NDT_OK && q.converged) ? q.fitness : 10000000.0;
+    r.stepped = 1; r.matched = 1; r.successful = successful[b];
+  }
+  if (r.stepped) {
+    for (int i = 0; i < 3; ++i) { last_pose[3 * b + i] = r.pose[i]; prev_odo[3 * b + i] = odo_cur[3 * b + i]; }
+    for (int i = 0; i < 9; ++i) last_cov[9 * b + i] = r.cov[i];
+  }
+  rec[b] = r;
+}
+
+// scan_to_map_kernel (ndt_resample.hip.h) with a destination per scan: dst[b] == nullptr: scan b is not transformed
+__global__ void __launch_bounds__(256)
+scan_to_map_dst_kernel(const double *__restrict__ xy, size_t stride, const unsigned long long *__restrict__ offsets, int B,
+                       const double *__restrict__ poses, float2 *const *__restrict__ dst) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    float2 *out = dst[b];
+    const unsigned long long r0 = offsets[b], r1 = offsets[b + 1];
+    if (!out || r0 >= r1) continue;
+    const double tx = poses[3 * b], ty = poses[3 * b + 1], a = poses[3 * b + 2] * M_PI / 180;
+    const double c = cos(a), sn = sin(a);
+    const double r00 = c, r01 = -sn, r10 = sn, r11 = c;
+    for (unsigned long long g = r0 + blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; g < r1;
+         g += (unsigned long long)gridDim.x * blockDim.x) {
+      const double *p = rs_point(xy, stride, g);
+      const double lx = p[0], ly = p[1];
+      const double x = r00 * lx + r01 * ly + tx;
+      const double y = r10 * lx + r11 * ly + ty;
+      out[g - r0] = make_float2((float)x, (float)y);
+    }
+  }
+}
+
+// the units of triple t's middle scan (MmUnit, ndt_localmap.hip.h): [subs[t].u0, subs[t].u1), job t, submap t
+__global__ void __launch_bounds__(256)
+session_units_kernel(const MmJob *__restrict__ jobs, const MmSub *__restrict__ subs, MmUnit *__restrict__ units) {
+  const MmJob J = jobs[blockIdx.x];
+  const MmSub U = subs[blockIdx.x];
+  for (unsigned k = threadIdx.x; k < U.u1 - U.u0; k += blockDim.x) {
+    const unsigned first = k * (unsigned)kMmUnit;
+    MmUnit u;
+    u.src = (const float *)((const char *)J.b + (size_t)first * J.sb);
+    u.stride = J.sb;
+    u.n = min((unsigned)kMmUnit, J.nb - first);
+    u.job = (int)blockIdx.x;
+    u.sub = blockIdx.x;
+    units[U.u0 + k] = u;
+  }
+}
+
+// One workgroup: cloud s = prefix s ++ piece s ++ newest scan s.  Writes the exclusive scan of the lengths to cloud_off,
+// the status per session (NDT_E_ARG: its triple failed, the cloud is empty and the prefix is left as it was), the new
+// prefix lengths, and four segments per session for seg_copy_kernel: the append of the piece to the prefix, and the three
+// gathers into the arena.
+__global__ void __launch_bounds__(1024)
+session_plan_kernel(const SsPlan *__restrict__ plan, int S, const float2 *__restrict__ tri_xy,
+                    const unsigned long long *__restrict__ tri_off, const int *__restrict__ tri_status,
+                    unsigned long long *__restrict__ plen, float2 *__restrict__ arena,
+                    unsigned long long *__restrict__ cloud_off, int *__restrict__ status, SsCopy *__restrict__ seg) {
+  __shared__ unsigned long long sh[1024];
+  __shared__ unsigned long long carry;
+  if (threadIdx.x == 0) carry = 0ull;
+  __syncthreads();
+  for (int base = 0; base < S; base += 1024) {
+    const int i = base + threadIdx.x;
+    SsPlan P;
+    unsigned long long pl = 0ull, pn = 0ull, nn = 0ull, len = 0ull;
+    const float2 *piece = nullptr;
+    int st = NDT_OK;
+    bool live = false;
+    if (i < S) {
+      P = plan[i];
+      live = P.stepped != 0;
+      if (live) {
+        pl = P.reset ? 0ull : plen[i];
+        piece = P.piece; pn = P.piece_n;
+        if (P.tri >= 0) {
+          if (tri_status[P.tri] != NDT_OK) st = NDT_E_ARG;
+          piece = tri_xy + tri_off[P.tri];
+          pn = tri_off[P.tri + 1] - tri_off[P.tri];
+        }
+        nn = P.with_newest ? P.newest_n : 0ull;
+        if (st != NDT_OK) { pn = 0ull; nn = 0ull; len = 0ull; }
+        else len = pl + pn + nn;
+      }
+    }
+    sh[threadIdx.x] = len;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const unsigned long long t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
+      __syncthreads();
+      sh[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (i < S) {
+      const unsigned long long off = carry + sh[threadIdx.x] - len;
+      cloud_off[i] = off;
+      status[i] = st;
+      const bool ok = live && st == NDT_OK;
+      seg[4 * i + 0] = SsCopy{piece, ok ? P.prefix + pl : nullptr, ok ? pn : 0ull};
+      seg[4 * i + 1] = SsCopy{ok ? P.prefix : nullptr, arena + off, ok ? pl : 0ull};
+      seg[4 * i + 2] = SsCopy{piece, arena + off + pl, ok ? pn : 0ull};
+      seg[4 * i + 3] = SsCopy{ok ? P.newest : nullptr, arena + off + pl + pn, ok ? nn : 0ull};
+      if (live) plen[i] = st == NDT_OK ? pl + pn : pl;
+    }
+    __syncthreads();
+    if (threadIdx.x == 1023) carry += sh[1023];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) cloud_off[S] = carry;
+}
+
+}  // namespace
+
+// ---- the host side ----
+
+namespace {
+
+// PointCloudMap's bookkeeping of one session (the logic of host/PointCloudMap.cpp addPose / addPoints) and where its
+// resident arrays are
+struct SsSession {
+  // PointCloudMap
+  int n_poses = 0;
+  double atd = 0.0, last_tx = 0.0, last_ty = 0.0;
+  double atdS = 0.0;                        // of the current submap
+  bool first_submap = true;                 // cntS == 0
+  int n_closed = 0;
+  // the current submap's scans (map frame, float2), one behind the other in store[cur]; the other store takes the two
+  // carried-over scans at a split
+  DevBuf<float2> store[2];
+  int cur = 0;
+  std::vector<uint64_t> scan_off{0};        // n_scans + 1 entries
+  DevBuf<float2> prefix;                    // the cached part of p_cloud
+  uint64_t plen = 0;                        // its length as of the last step (read back at host wait 2)
+  DevBuf<float2> closed;                    // every closed submap's p_cloud
+  std::vector<uint64_t> closed_off{0};      // n_closed + 1 entries
+  // the last step's results in the arenas: arena `buf`, p_cloud at [c_off, c_off + c_n) of the cloud arena, the local map at
+  // [t_off, t_off + t_n) of the target arena, its first n_prev points the previous submap's cloud
+  bool has_target = false;
+  int buf = 0;
+  uint64_t c_off = 0, c_n = 0, t_off = 0, t_n = 0, n_prev = 0;
+  ndt_map *map = nullptr;
+  bool started = false;
+};
+
+}  // namespace
+
+struct ndt_sessions {
+  ndt_ctx *ctx = nullptr;
+  int S = 0;
+  ndt_session_params prm{};
+  bool dead = false;                        // a HIP failure inside a step: every later call returns NDT_E_HIP
+  std::vector<SsSession> ses;
+  ndt_sessions_stats stats{};
+  // resident per-session state
+  DevBuf<double> last_pose, last_cov, prev_odo;      // S x 3, S x 9, S x 3
+  DevBuf<unsigned long long> plen;                   // S
+  // a step's arrays
+  DevBuf<unsigned char> raw;                         // the raw scans' copy (host form)
+  DevBuf<double> odo, motion, pred, init, fused, cov;
+  DevBuf<double> rs64; DevBuf<float> rs32, src;      // resampled scans (double2 / float2), filtered source scans
+  DevBuf<uint64_t> raw_off, rs_off, src_off;
+  DevBuf<int> rs_status, mode, map_of, successful;
+  DevBuf<ndt_result> res;
+  DevBuf<ndt_session_step> rec;
+  PinnedBuf<unsigned char> h_back;                   // read-backs
+  StagedUpload<unsigned char> tab_a, tab_b, tab_c;   // the tables of the three phases of a step
+  DevBuf<unsigned char> d_tab_a, d_tab_b, d_tab_c;
+  DevBuf<unsigned char> mm;                          // newest triples: units, counts, keep bits, voxel sets, difference lists
+  DevBuf<float2> tri_xy; DevBuf<uint64_t> tri_off; DevBuf<int> tri_status;
+  DevBuf<float2> cloud[2], target[2];                // the arenas, in turn
+  DevBuf<uint64_t> cloud_off, target_off;            // S + 1 each
+  DevBuf<int> status;
+  int cur = 0;                                       // arena of the most recent step
+};
+
+namespace {
+
+#define SS_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// at least `need` elements with the first `keep` preserved: a growth doubles, copies on the device on the context's stream
+// and frees the old block behind that copy
+template <typename T>
+int ss_grow(ndt_ctx *ctx, DevBuf<T> &b, size_t need, size_t keep) {
+  if (b.p && need <= b.cap()) return NDT_OK;
+  DevBuf<T> nb;
+  SS_TRY(nb.alloc(ctx, std::max(need * 2, (size_t)1024) * sizeof(T)));
+  if (keep && b.p) {
+    HIP_TRY(ctx, hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  b = std::move(nb);
+  return NDT_OK;
+}
+
+int ss_check_params(ndt_ctx *ctx, const ndt_session_params &p) {
+  size_t cap = 0;
+  if (!(p.leaf > 0)) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: leaf <= 0");
+  if (!(p.match.resolution > 0)) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: match.resolution <= 0");
+  if (!(p.fuse.del_time > 0)) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: fuse.del_time <= 0");
+  if (ndt_resample_capacity(1, p.space, p.space_thre, &cap))
+    return fail(ctx, NDT_E_ARG, "ndt_sessions_create: space / space_thre refused (negative, non-finite, or space == 0 < space_thre)");
+  if (p.remove_moving && (!(p.resol > 0.0) || !std::isfinite(p.resol) || !std::isfinite(p.thre_neighbor)))
+    return fail(ctx, NDT_E_ARG, "ndt_sessions_create: remove_moving needs a positive finite resol (and a finite thre_neighbor)");
+  if (!std::isfinite(p.sep_thre)) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: sep_thre is not finite");
+  return NDT_OK;
+}
+
+unsigned ss_gx(size_t total, int B) { return (unsigned)std::min<size_t>(64, (total / (size_t)std::max(B, 1) + 255) / 256 + 1); }
+
+// The step.  raw_dev / odo_dev: the device form (then raw_host / odo_host are NULL).  Every return with a HIP error leaves
+// the set dead (the caller marks it).
+int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, size_t stride, const uint64_t *raw_offsets,
+            const double *odo_host, const double *odo_dev_in, const unsigned char *active, ndt_session_step *out) {
+  ndt_ctx *ctx = s->ctx;
+  const int S = s->S;
+  const ndt_session_params &P = s->prm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ndt_sessions_stats stats{};
+  const size_t N = (size_t)(raw_offsets[S] - raw_offsets[0]);
+
+  // ---- who steps ----
+  std::vector<int> mode((size_t)S, kSsNone), map_of((size_t)S, -1);
+  std::vector<const ndt_map *> maps;
+  int n_active = 0;
+  for (int i = 0; i < S; ++i) {
+    if (active && !active[i]) continue;
+    ++n_active;
+    SsSession &Q = s->ses[(size_t)i];
+    if (!Q.started) mode[(size_t)i] = kSsFirst;
+    else {
+      mode[(size_t)i] = kSsMatch;
+      if (Q.map) { map_of[(size_t)i] = (int)maps.size(); maps.push_back(Q.map); }
+    }
+  }
+  if (n_active == 0) {
+    for (int i = 0; i < S; ++i) { memset(&out[i], 0, sizeof(out[i])); out[i].submap = s->ses[(size_t)i].n_closed; }
+    s->stats = stats;
+    return NDT_OK;
+  }
+
+  // ---- phase A: upload, resample -> pre-filter -> predict -> match -> fuse -> select ----
+  size_t cap_rs = 0;
+  if (ndt_resample_capacity(std::max<size_t>(N, 1), P.space, P.space_thre, &cap_rs))
+    return fail(ctx, NDT_E_ARG, "ndt_sessions_step: the resampled scans' capacity overflows");
+  const size_t S1 = (size_t)S + 1;
+  SS_TRY(s->raw_off.ensure(ctx, S1)); SS_TRY(s->rs_off.ensure(ctx, S1)); SS_TRY(s->src_off.ensure(ctx, S1));
+  SS_TRY(s->rs64.ensure(ctx, 2 * cap_rs)); SS_TRY(s->rs32.ensure(ctx, 2 * cap_rs)); SS_TRY(s->src.ensure(ctx, 2 * cap_rs));
+  // table A: raw offsets (relative) | mode | map_of | odometry (host form)
+  const size_t a_off = 0, a_mode = a_off + S1 * 8, a_mapof = a_mode + up64((size_t)S * 4), a_odo = a_mapof + up64((size_t)S * 4);
+  const size_t a_bytes = a_odo + (odo_host ? (size_t)S * 24 : 0);
+  SS_TRY(s->tab_a.reserve(ctx, a_bytes));
+  SS_TRY(s->d_tab_a.ensure(ctx, a_bytes));
+  {
+    unsigned char *h = s->tab_a.h.p;
+    uint64_t *ro = (uint64_t *)(h + a_off);
+    for (int b = 0; b <= S; ++b) ro[b] = raw_offsets[b] - raw_offsets[0];
+    memcpy(h + a_mode, mode.data(), (size_t)S * 4);
+    memcpy(h + a_mapof, map_of.data(), (size_t)S * 4);
+    if (odo_host) memcpy(h + a_odo, odo_host, (size_t)S * 24);
+  }
+  HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, a_bytes, st));
+  stats.h2d_bytes += a_bytes;
+  const unsigned long long *d_raw_off = (const unsigned long long *)(s->d_tab_a.p + a_off);
+  const int *d_mode = (const int *)(s->d_tab_a.p + a_mode), *d_map_of = (const int *)(s->d_tab_a.p + a_mapof);
+  const double *d_odo = odo_host ? (const double *)(s->d_tab_a.p + a_odo) : odo_dev_in;
+  const double *d_raw = raw_dev_in ? (const double *)((const char *)raw_dev_in + (size_t)raw_offsets[0] * stride) : nullptr;
+  if (raw_host && N) {
+    SS_TRY(s->raw.ensure(ctx, N * stride));
+    HIP_TRY(ctx, hipMemcpyAsync(s->raw.p, (const char *)raw_host + (size_t)raw_offsets[0] * stride, N * stride, hipMemcpyHostToDevice, st));
+    stats.h2d_bytes += N * stride;
+    d_raw = (const double *)s->raw.p;
+  }
+  if (N) {
+    SS_TRY(ndt_resample_batch_dev(ctx, d_raw, stride, (const uint64_t *)d_raw_off, S, N, P.space, P.space_thre, s->rs64.p, s->rs32.p,
+                                  s->rs_off.p, s->rs_status.p, st));
+    SS_TRY(ndt_prefilter_batch_dev(ctx, s->rs32.p, sizeof(float2), s->rs_off.p, S, cap_rs, P.leaf, s->src.p, s->src_off.p, st));
+  } else {
+    HIP_TRY(ctx, hipMemsetAsync(s->rs_off.p, 0, S1 * 8, st));
+    HIP_TRY(ctx, hipMemsetAsync(s->src_off.p, 0, S1 * 8, st));
+    HIP_TRY(ctx, hipMemsetAsync(s->rs_status.p, 0, (size_t)S * 4, st));
+  }
+  SS_TRY(ndt_predict_batch_dev(ctx, d_odo, s->prev_odo.p, s->last_pose.p, S, s->motion.p, s->pred.p, s->init.p, st));
+  if (!maps.empty() && N) {
+    SS_TRY(ndt_align_batch_multi_dev(ctx, maps.data(), (int)maps.size(), d_map_of, s->src.p, s->src_off.p, S, cap_rs, 0, s->init.p,
+                                     s->res.p, st));
+  } else {
+    HIP_TRY(ctx, hipMemsetAsync(s->res.p, 0, (size_t)S * sizeof(ndt_result), st));      // (status 0, converged 0: the sentinel cost)
+  }
+  SS_TRY(ndt_fuse_batch_dev(ctx, s->res.p, s->pred.p, s->motion.p, s->last_pose.p, s->last_cov.p, S, &P.fuse, s->fused.p, s->cov.p,
+                            s->successful.p, st));
+  session_select_kernel<<<(S + 255) / 256, 256, 0, st>>>(d_mode, s->rs_status.p, d_odo, s->res.p, s->fused.p, s->cov.p, s->successful.p,
+                                                         S, s->last_pose.p, s->last_cov.p, s->prev_odo.p, s->rec.p);
+  HIP_TRY(ctx, hipGetLastError());
+  // ---- host wait 1: the resampled counts and the records ----
+  const size_t b_rs = 0, b_rec = up64(S1 * 8), back1 = b_rec + (size_t)S * sizeof(ndt_session_step);
+  const size_t b_toff = 0, b_coff = S1 * 8, b_plen = 2 * S1 * 8, b_stat = b_plen + (size_t)S * 8, back2 = b_stat + (size_t)S * 4;
+  SS_TRY(s->h_back.ensure(ctx, std::max(back1, back2)));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rs, s->rs_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rec, s->rec.p, (size_t)S * sizeof(ndt_session_step), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  stats.d2h_bytes += S1 * 8 + (size_t)S * sizeof(ndt_session_step);
+  stats.host_waits++;
+  std::vector<uint64_t> rs_off(S1);
+  memcpy(rs_off.data(), s->h_back.p + b_rs, S1 * 8);
+  memcpy(out, s->h_back.p + b_rec, (size_t)S * sizeof(ndt_session_step));
+
+  // ---- the bookkeeping: addPose, the split, where the scan lands (PointCloudMap::addPose / addPoints) ----
+  const int cur = s->cur ^ 1;                      // this step's arenas; the last step's are s->cur
+  std::vector<SsCopy> moves;                       // carried-over scans and closed clouds
+  std::vector<float2 *> dst((size_t)S, nullptr);
+  std::vector<SsPlan> plan((size_t)S);
+  std::vector<PfPrev> prevs((size_t)S);
+  std::vector<MmJob> jobs; std::vector<MmSub> subs; std::vector<int> tri_of;
+  size_t nu = 0, cap_cloud = 0, total_prev = 0, tab_words = 0, list_pts = 0, tri_pts = 0, carry_cloud = 0, carry_target = 0;
+  const float cut = P.remove_moving ? rn_cutoff(P.thre_neighbor) : 0.f;
+  for (int i = 0; i < S; ++i) {
+    SsSession &Q = s->ses[(size_t)i];
+    SsPlan &L = plan[(size_t)i];
+    L = SsPlan{nullptr, nullptr, 0ull, -1, 0, 0, 0, nullptr, 0ull};
+    prevs[(size_t)i] = PfPrev{nullptr, 0ull};
+    out[i].submap = Q.n_closed;
+    if (!out[i].stepped) {
+      if (Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
+      continue;
+    }
+    stats.sessions_stepped++;
+    const size_t n_new = (size_t)(rs_off[(size_t)i + 1] - rs_off[(size_t)i]);
+    const double tx = out[i].pose[0], ty = out[i].pose[1];
+    if (Q.n_poses) Q.atd += std::sqrt((tx - Q.last_tx) * (tx - Q.last_tx) + (ty - Q.last_ty) * (ty - Q.last_ty));
+    else Q.atd = 0.0;
+    Q.n_poses++; Q.last_tx = tx; Q.last_ty = ty; Q.started = true;
+    if (Q.atd - Q.atdS >= P.sep_thre) {
+      // the current submap closes (src/PointCloudMap.cpp:72-90): its cloud becomes the filtered part of the last local map
+      const uint64_t n_tail = Q.has_target ? Q.t_n - Q.n_prev : 0;
+      SS_TRY(ss_grow(ctx, Q.closed, (size_t)(Q.closed_off.back() + n_tail), (size_t)Q.closed_off.back()));
+      if (n_tail) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off + Q.n_prev, Q.closed.p + Q.closed_off.back(), n_tail});
+      Q.closed_off.push_back(Q.closed_off.back() + n_tail);
+      Q.n_closed++;
+      Q.atdS = Q.atd; Q.first_submap = Q.n_poses - 1 == 0;
+      const size_t ns = Q.scan_off.size() - 1;
+      const int other = Q.cur ^ 1;
+      std::vector<uint64_t> noff{0};
+      if (ns >= 2) {
+        const uint64_t a = Q.scan_off[ns - 2], n2 = Q.scan_off[ns] - a;
+        SS_TRY(ss_grow(ctx, Q.store[other], (size_t)n2 + n_new, 0));
+        if (n2) moves.push_back(SsCopy{Q.store[Q.cur].p + a, Q.store[other].p, n2});
+        noff.push_back(Q.scan_off[ns - 1] - a); noff.push_back(n2);
+      }
+      Q.scan_off = noff; Q.cur = other;
+      L.reset = 1; Q.plen = 0;
+      out[i].split = 1;
+    }
+    out[i].submap = Q.n_closed;
+    SS_TRY(ss_grow(ctx, Q.store[Q.cur], (size_t)Q.scan_off.back() + n_new, (size_t)Q.scan_off.back()));
+    float2 *base = Q.store[Q.cur].p;
+    dst[(size_t)i] = base + Q.scan_off.back();
+    Q.scan_off.push_back(Q.scan_off.back() + n_new);
+    // Submap::makeMap's branches
+    const size_t n = Q.scan_off.size() - 1;
+    auto scan_p = [&](size_t k) { return base + Q.scan_off[k]; };
+    auto scan_n = [&](size_t k) { return (size_t)(Q.scan_off[k + 1] - Q.scan_off[k]); };
+    L.stepped = 1;
+    L.newest = scan_p(n - 1); L.newest_n = scan_n(n - 1);
+    size_t piece_room = 0;
+    if (P.remove_moving) {
+      L.with_newest = 1;
+      if (n == 1 && Q.first_submap) { L.piece = scan_p(0); L.piece_n = scan_n(0); piece_room = scan_n(0); }
+      else if (n >= 3 && scan_n(n - 2)) {      // the newest triple (an empty middle scan contributes nothing)
+        const size_t n0 = scan_n(n - 3), n1 = scan_n(n - 1), nb = scan_n(n - 2);
+        if (n0 > ((size_t)1 << 29) || n1 > ((size_t)1 << 29) || nb > ((size_t)1 << 29))
+          return fail(ctx, NDT_E_ARG, "ndt_sessions_step: session " + std::to_string(i) + ": a scan above 2^29 points");
+        L.tri = (int)jobs.size();
+        MmJob J{};
+        J.a0 = (const float *)scan_p(n - 3); J.a1 = (const float *)scan_p(n - 1); J.b = (const float *)scan_p(n - 2);
+        J.n0 = (unsigned)n0; J.n1 = (unsigned)n1; J.nb = (unsigned)nb; J.sa = J.sb = (unsigned)sizeof(float2);
+        const size_t capw = pow2_at_least(2 * (n0 + n1) + 2);
+        J.tab_mask = (unsigned)(capw - 1);
+        J.tab = (unsigned long long *)tab_words; J.diff = (float2 *)list_pts;      // offsets for now, pointers below
+        J.res = P.resol; J.cut = cut;
+        jobs.push_back(J);
+        const unsigned u = (unsigned)((nb + kMmUnit - 1) / kMmUnit);
+        subs.push_back(MmSub{(unsigned)nu, (unsigned)nu + u});
+        tri_of.push_back(i);
+        nu += u; tab_words += capw; list_pts += nb; tri_pts += nb; piece_room = nb;
+      }
+    } else {
+      L.with_newest = Q.first_submap || n - 1 >= 2;
+      if (n >= 2 && (Q.first_submap || n - 2 >= 2)) { L.piece = scan_p(n - 2); L.piece_n = scan_n(n - 2); piece_room = scan_n(n - 2); }
+    }
+    SS_TRY(ss_grow(ctx, Q.prefix, (size_t)Q.plen + piece_room, (size_t)Q.plen));
+    L.prefix = Q.prefix.p;
+    cap_cloud += (size_t)Q.plen + piece_room + (L.with_newest ? (size_t)L.newest_n : 0);
+    if (Q.n_closed >= 1) {
+      const uint64_t a = Q.closed_off[(size_t)Q.n_closed - 1], np = Q.closed_off[(size_t)Q.n_closed] - a;
+      prevs[(size_t)i] = PfPrev{np ? (const float *)(Q.closed.p + a) : nullptr, np};
+      total_prev += (size_t)np;
+    }
+  }
+  stats.triples_run = (int)jobs.size();
+  const size_t T = jobs.size();
+  // the stores may have moved when they grew: the pointers above were taken after each session's own growth, and no later
+  // session touches them
+
+  // ---- phase B: growMap's transform, the moves, the newest triples, the clouds, the targets ----
+  const size_t cap_target = cap_cloud + total_prev;
+  SS_TRY(s->cloud[cur].ensure(ctx, cap_cloud + carry_cloud + 64));
+  SS_TRY(s->target[cur].ensure(ctx, cap_target + carry_target + 64));
+  SS_TRY(s->tri_xy.ensure(ctx, tri_pts + 64));
+  // device scratch of the triples: [units][unit counts][unit offsets][keep bits][diff counts][voxel sets][diff lists]
+  const size_t m_ucnt = up64(nu * sizeof(MmUnit)), m_uoff = m_ucnt + up64(nu * 4), m_keep = m_uoff + up64(nu * 8),
+               m_cnt = m_keep + up64(nu * (kMmUnit / 64) * 8), m_tab = m_cnt + up64(T * 8 + 8), m_diff = m_tab + tab_words * 8;
+  SS_TRY(s->mm.ensure(ctx, m_diff + list_pts * 8 + 64));
+  char *dm = (char *)s->mm.p;
+  for (size_t t = 0; t < T; ++t) {
+    jobs[t].tab = (unsigned long long *)(dm + m_tab) + (size_t)jobs[t].tab;
+    jobs[t].diff = (float2 *)(dm + m_diff) + (size_t)jobs[t].diff;
+    jobs[t].n_diff = (unsigned long long *)(dm + m_cnt) + t;
+  }
+  // table B, the same size at every step: dst | plan | prevs | jobs | subs | moves (3 per session at most)
+  const size_t o_dst = 0, o_plan = o_dst + up64((size_t)S * 8), o_prev = o_plan + up64((size_t)S * sizeof(SsPlan)),
+               o_jobs = o_prev + up64((size_t)S * sizeof(PfPrev)), o_subs = o_jobs + up64((size_t)S * sizeof(MmJob)),
+               o_moves = o_subs + up64((size_t)S * sizeof(MmSub)), o_seg = o_moves + up64(3 * (size_t)S * sizeof(SsCopy)),
+               b_bytes = o_seg, b_room = o_seg + 4 * (size_t)S * sizeof(SsCopy);
+  SS_TRY(s->tab_b.reserve(ctx, b_bytes));
+  SS_TRY(s->d_tab_b.ensure(ctx, b_room));
+  {
+    unsigned char *h = s->tab_b.h.p;
+    memset(h, 0, b_bytes);
+    memcpy(h + o_dst, dst.data(), (size_t)S * 8);
+    memcpy(h + o_plan, plan.data(), (size_t)S * sizeof(SsPlan));
+    memcpy(h + o_prev, prevs.data(), (size_t)S * sizeof(PfPrev));
+    if (T) { memcpy(h + o_jobs, jobs.data(), T * sizeof(MmJob)); memcpy(h + o_subs, subs.data(), T * sizeof(MmSub)); }
+    if (!moves.empty()) memcpy(h + o_moves, moves.data(), moves.size() * sizeof(SsCopy));
+  }
+  HIP_TRY(ctx, s->tab_b.upload(s->d_tab_b.p, 0, b_bytes, st));
+  stats.h2d_bytes += b_bytes;
+  unsigned char *db = s->d_tab_b.p;
+  const size_t rs_total = (size_t)rs_off[(size_t)S];
+  if (rs_total)
+    scan_to_map_dst_kernel<<<dim3(ss_gx(rs_total, S), (unsigned)std::min(S, 65535)), 256, 0, st>>>(
+        s->rs64.p, sizeof(double2), (const unsigned long long *)s->rs_off.p, S, s->last_pose.p, (float2 *const *)(db + o_dst));
+  if (!moves.empty())
+    seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(moves.size(), 65535)), 256, 0, st>>>((const SsCopy *)(db + o_moves), (int)moves.size());
+  if (T) {
+    const MmJob *d_jobs = (const MmJob *)(db + o_jobs);
+    const MmSub *d_subs = (const MmSub *)(db + o_subs);
+    MmUnit *units = (MmUnit *)dm;
+    unsigned *ucnt = (unsigned *)(dm + m_ucnt);
+    unsigned long long *uoff = (unsigned long long *)(dm + m_uoff), *keep = (unsigned long long *)(dm + m_keep);
+    SS_TRY(s->tri_off.ensure(ctx, T + 1)); SS_TRY(s->tri_status.ensure(ctx, T));
+    HIP_TRY(ctx, hipMemsetAsync(dm + m_tab, 0xff, tab_words * 8, st));
+    session_units_kernel<<<(unsigned)T, 256, 0, st>>>(d_jobs, d_subs, units);
+    make_map_diff_kernel<true><<<(unsigned)T, kMmBlock, 0, st>>>(d_jobs, 0.0);
+    make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(d_jobs, units, 0.f, keep, ucnt);
+    make_map_sub_offsets_kernel<<<(unsigned)T, 1024, 0, st>>>(ucnt, d_subs, uoff, (unsigned long long *)s->tri_off.p, s->tri_status.p);
+    make_map_sub_scan_kernel<<<1, 1024, 0, st>>>((unsigned long long *)s->tri_off.p, (int)T);
+    make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, s->tri_xy.p,
+                                                                (const unsigned long long *)s->tri_off.p, s->tri_status.p);
+  }
+  session_plan_kernel<<<1, 1024, 0, st>>>((const SsPlan *)(db + o_plan), S, s->tri_xy.p, (const unsigned long long *)s->tri_off.p,
+                                          s->tri_status.p, s->plen.p, s->cloud[cur].p, (unsigned long long *)s->cloud_off.p,
+                                          s->status.p, (SsCopy *)(db + o_seg));
+  seg_copy_kernel<<<dim3(ss_gx(cap_cloud, S), (unsigned)std::min(4 * S, 65535)), 256, 0, st>>>((const SsCopy *)(db + o_seg), 4 * S);
+  HIP_TRY(ctx, hipGetLastError());
+  {
+    ScratchScope scope(ctx, st);                  // (the filter's scratch is the context's)
+    SS_TRY(scope.open());
+    SS_TRY(pf_run<true>(ctx, (const float *)s->cloud[cur].p, sizeof(float2), s->cloud_off.p, S, std::max<size_t>(cap_cloud, 1), P.leaf,
+                        (float *)s->target[cur].p, s->target_off.p, (const PfPrev *)(db + o_prev), sizeof(float2), total_prev,
+                        s->status.p, st));
+    SS_TRY(scope.close());
+  }
+  // ---- host wait 2: the target and cloud offsets, the prefix lengths, the status ----
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->target_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_coff, s->cloud_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_plen, s->plen.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->status.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  stats.d2h_bytes += 2 * S1 * 8 + (size_t)S * 12;
+  stats.host_waits++;
+  const uint64_t *toff = (const uint64_t *)(s->h_back.p + b_toff), *coff = (const uint64_t *)(s->h_back.p + b_coff),
+                 *pl = (const uint64_t *)(s->h_back.p + b_plen);
+  const int *stt = (const int *)(s->h_back.p + b_stat);
+  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<ndt_map *> bmaps; std::vector<int> bwho;
+  std::vector<SsCopy> carry;
+  uint64_t c_end = coff[S], t_end = toff[S];
+  for (int i = 0; i < S; ++i) {
+    SsSession &Q = s->ses[(size_t)i];
+    if (out[i].stepped) {
+      Q.plen = pl[i];
+      if (stt[i] != NDT_OK) {
+        // the newest triple spans more than 2^30 voxels: no cloud and no local map this step; the map stays as it is
+        out[i].status = NDT_E_ARG;
+        Q.has_target = false; Q.c_n = Q.t_n = Q.n_prev = 0; Q.buf = cur;
+        continue;
+      }
+      Q.buf = cur; Q.has_target = true;
+      Q.c_off = coff[i]; Q.c_n = coff[i + 1] - coff[i];
+      Q.t_off = toff[i]; Q.t_n = toff[i + 1] - toff[i];
+      Q.n_prev = prevs[(size_t)i].n;
+      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bmaps.push_back(Q.map); bwho.push_back(i); }
+    } else if (Q.has_target && Q.buf != cur) {
+      // a session that did not step keeps its views and its last local map: they move to this step's arenas
+      if (Q.c_n) carry.push_back(SsCopy{s->cloud[Q.buf].p + Q.c_off, s->cloud[cur].p + c_end, Q.c_n});
+      if (Q.t_n) carry.push_back(SsCopy{s->target[Q.buf].p + Q.t_off, s->target[cur].p + t_end, Q.t_n});
+      Q.c_off = c_end; c_end += Q.c_n; Q.t_off = t_end; t_end += Q.t_n; Q.buf = cur;
+    }
+  }
+  // table C, the same size at every step: two carried ranges per session at most
+  const size_t c_bytes = 2 * (size_t)S * sizeof(SsCopy);
+  SS_TRY(s->tab_c.reserve(ctx, c_bytes));
+  SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
+  memset(s->tab_c.h.p, 0, c_bytes);
+  if (!carry.empty()) memcpy(s->tab_c.h.p, carry.data(), carry.size() * sizeof(SsCopy));
+  HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
+  stats.h2d_bytes += c_bytes;
+  if (!carry.empty())
+    seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(carry.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)carry.size());
+  HIP_TRY(ctx, hipGetLastError());
+  s->cur = cur;
+  // ---- the NDT maps of the new local maps (host wait 3: the bounding boxes) ----
+  if (!bxy.empty()) {
+    std::vector<ndt_params> bp(bxy.size(), P.match);
+    const int rc = ndt_map_build_batch_dev(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data());
+    for (size_t k = 0; k < bwho.size(); ++k) s->ses[(size_t)bwho[k]].map = rc == NDT_OK ? bmaps[k] : s->ses[(size_t)bwho[k]].map;
+    if (rc) return rc;
+  } else {
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  stats.host_waits++;
+  stats.d2h_bytes += bxy.size() * 16 * sizeof(unsigned);
+  s->stats = stats;
+  return NDT_OK;
+}
+
+#undef SS_TRY
+
+}  // namespace

@@ -564,3 +564,61 @@ def run_sessions(ops, logs, poses_names=None, map_names=None, separated_map_name
             L.pcmap.saveGlobalMap(map_names[i], sep or (map_names[i] + "_sep"))
         out.append(poses)
     return out
+
+
+def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated_map_names=None, sessions=None, **params):
+    """run_sessions with every session's state resident on the device: one capi.Sessions set (ndt_sessions_*) over all
+    logs, one `step` per lockstep step -- the raw scans and odometry go up, the fused poses come down; scans, submap
+    clouds, local maps and NDT maps never leave the device.  The same files and return value as run_sessions
+    (start_frame and end_frame reach the set through `active`); the global map is read from the device once per session,
+    at its last keyframe step (cnt % keyframe_skip == 0: what saveGlobalMap writes).  One parameter set for all sessions
+    (a sweep makes one call per set).  `sessions`: an object with capi.Sessions' interface to use instead of a new
+    capi.Sessions(ctx, len(logs), ...) (tests: a host stand-in)."""
+    from . import capi
+    p = dict(LAUNCH_PARAMS)
+    p.update(params)
+    logs = [list(l) for l in logs]
+    S = len(logs)
+    if S == 0:
+        return []
+    own = sessions is None
+    if own:
+        sessions = capi.Sessions(ctx, S, capi.session_params_from_launch(p))
+    lengths = [min(len(l), p["end_frame"]) for l in logs]
+    steps_of = [[k for k in range(lengths[i]) if logs[i][k].sid >= p["start_frame"]] for i in range(S)]
+    # FrontEnd::process makes the global map when cnt % keyframe_skip == 0 (cnt: scans processed so far): the last such step
+    last_key = [(st[((len(st) - 1) // p["keyframe_skip"]) * p["keyframe_skip"]] if st else -1) for st in steps_of]
+    poses = [[] for _ in range(S)]
+    exported = [(_EMPTY, []) for _ in range(S)]
+    empty = np.zeros((0, 2))
+    try:
+        for k in range(max(lengths, default=0)):
+            active = np.array([k < lengths[i] and logs[i][k].sid >= p["start_frame"] for i in range(S)], dtype=np.uint8)
+            if not active.any():
+                continue
+            scans = [logs[i][k].lps if active[i] else empty for i in range(S)]
+            odo = [((logs[i][k].pose.tx, logs[i][k].pose.ty, logs[i][k].pose.th) if active[i] else (0.0, 0.0, 0.0))
+                   for i in range(S)]
+            recs = sessions.step(scans, odo, active)
+            for i in range(S):
+                if not active[i]:
+                    continue
+                if not recs[i]["stepped"]:
+                    raise capi.NdtError("run_sessions_resident: session %d, scan %d: status %d (a non-finite coordinate)"
+                                        % (i, k, int(recs[i]["status"])))
+                poses[i].append(Pose2D(*[float(v) for v in recs[i]["pose"]]))
+                if k == last_key[i]:
+                    g, parts = sessions.global_map(i)
+                    exported[i] = (g.copy(), [m.copy() for m in parts])
+    finally:
+        if own:
+            sessions.close()
+    for i in range(S):
+        if poses_names and poses_names[i]:
+            write_poses(poses_names[i], poses[i])
+        if map_names and map_names[i]:
+            sep = separated_map_names[i] if separated_map_names and separated_map_names[i] else None
+            save_pcd_ascii(map_names[i], exported[i][0])
+            for j, m in enumerate(exported[i][1]):
+                save_pcd_ascii("%s%d.pcd" % (sep or (map_names[i] + "_sep"), j), m)
+    return poses
