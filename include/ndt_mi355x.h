@@ -161,8 +161,12 @@ void *ndt_ctx_stream(ndt_ctx *ctx);               /* hipStream_t the context wor
  *                               synchronisation) before reading them, keep scans / offsets / initial guesses alive until
  *                               then, and give two launches in a row different `out` arrays (a launch waits for the end of
  *                               the launch before last by itself).  Every other entry point of the context waits for a
- *                               deferred launch's end before it touches the context.  Same kernels, same records. */
-enum ndt_option { NDT_OPT_MAX_HELPERS = 1, NDT_OPT_WORKGROUPS = 2, NDT_OPT_INJECT_FAULT = 3, NDT_OPT_DEFER_FITNESS = 4 };
+ *                               deferred launch's end before it touches the context.  Same kernels, same records.
+ *   NDT_OPT_SCORE_STAGE 0 / 1   the score sweep (ndt_score_*) copies a scan of up to 8000 points into LDS once per workgroup
+ *                               (1, the default) or reads every scan from global memory (0), as it does for longer scans.
+ *                               Same scores, bit for bit. */
+enum ndt_option { NDT_OPT_MAX_HELPERS = 1, NDT_OPT_WORKGROUPS = 2, NDT_OPT_INJECT_FAULT = 3, NDT_OPT_DEFER_FITNESS = 4,
+                  NDT_OPT_SCORE_STAGE = 5 };
 int ndt_ctx_set_option(ndt_ctx *ctx, int option, long long value);
 /* Make the context work on a caller-owned hipStream_t (e.g. the stream a host framework already
  * orders its copies on); NULL restores the context's own stream. */
@@ -598,6 +602,75 @@ int ndt_sessions_submap_cloud(const ndt_sessions *s, int i, const float **xy_dev
 int ndt_sessions_global_map(ndt_sessions *s, int i, float *out_xy_host, size_t capacity, size_t *n_out,
                             uint64_t *sub_offsets, int *n_submaps);
 int ndt_sessions_get_stats(const ndt_sessions *s, ndt_sessions_stats *out);
+
+/* ---- Relocalisation: score a pose lattice, pick candidates, refine --------------------------------------------------------
+ * The reference has NO counterpart.  Every match it runs starts from the odometry prediction (src/ScanMatcher.cpp:40,45 ->
+ * src/PoseEstimator.cpp:22-28), and its answer to a failed match is src/ScanMatcher.cpp:60-66: the fused pose falls back to
+ * the prediction and the session stays lost.  These calls are the coarse half of coarse-to-fine for a caller that has no
+ * guess inside the NDT basin (about one voxel and a few degrees wide): the NDT score alone -- eq. 6.9's sum, what
+ * computeDerivatives returns as `score` (src/PoseEstimator.cpp:28 -> ndt.align), without gradient or Hessian -- of one scan
+ * at a very large number of poses in one launch, a deterministic pick of the few poses worth refining, and the existing
+ * shared-scan match from those.  The score of a pose list is also what a particle filter takes as weights. */
+
+/* A regular lattice of poses.  Index = (k * ny + j) * nx + i (yaw-major, x fastest); pose = (x0 + (double)i * step_x,
+ * y0 + (double)j * step_y, yaw0 + (double)k * step_yaw), each component one rounded multiply and one rounded add (no fused
+ * multiply-add).  Yaw in radians, not wrapped.  Steps may be negative or zero. */
+typedef struct ndt_pose_lattice {
+  double x0, y0, yaw0;
+  double step_x, step_y, step_yaw;
+  int nx, ny, nyaw;
+} ndt_pose_lattice;
+/* Number of poses / pose `index` of a lattice.  Host only: no context, no device.  ndt_lattice_pose IS the definition of a
+ * lattice pose: the device forms the same bits.  NDT_E_ARG: a NULL pointer, a dimension below 1, a non-finite origin or
+ * step, more than 2^31 - 1 poses, index out of range. */
+int ndt_lattice_size(const ndt_pose_lattice *lattice, uint64_t *n_poses);
+int ndt_lattice_pose(const ndt_pose_lattice *lattice, uint64_t index, double pose_xyyaw[3]);
+
+/* The score sweep.  For pose p: score[p] = -d1 * (sum of e over every (point, voxel) pair), pairs[p] = the number of pairs --
+ * the pairs and the e of ndt_eval_at at that pose, term for term the same doubles (the float32 transform of the map's
+ * ndt_params, the 3 x 3 neighbourhood with the radius test on float32 centroids, updateDerivatives' check on e).  A
+ * non-finite scan point adds nothing; a pose with a non-finite component gets score 0 and pairs 0.
+ * A pose's score and pairs are a function of the map, the scan and the pose to the last bit: they do not depend on the
+ * pose's place in the list, the other poses, P, lattice or list form, NDT_OPT_WORKGROUPS, NDT_OPT_SCORE_STAGE or the stride
+ * (the order of summation is fixed per pose).
+ * _dev: every pointer a device address (poses_dev: P x 3 doubles; pairs_dev may be NULL); asynchronous on `stream` (NULL = the
+ * context's), behind the map's build; the call is entered among the map's readers as a match launch is, so a rebuild of the
+ * map queued behind it -- on whatever stream -- waits for it.  ndt_score_poses: host pointers, synchronous.
+ * Refusals (NDT_E_ARG, synchronous, nothing queued): a NULL context ("null context"), a NULL map, scan, poses or score, a map
+ * never built or of another device, n == 0 or n > INT32_MAX, P < 1 or P > 2^31 - 1, stride_bytes < 8 or not a multiple of 8
+ * (as ndt_eval_at), a lattice ndt_lattice_size refuses, an open ndt_map_rebuild_begin on the context. */
+int ndt_score_poses_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride_bytes,
+                        const double *poses_dev, uint64_t P, double *score_dev, uint32_t *pairs_dev, void *stream);
+int ndt_score_lattice_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride_bytes,
+                          const ndt_pose_lattice *lattice, double *score_dev, uint32_t *pairs_dev, void *stream);
+int ndt_score_poses(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride_bytes,
+                    const double *poses_host, uint64_t P, double *score_host, uint32_t *pairs_host);
+
+/* The candidate pick over a lattice's score volume (device pointers, asynchronous on `stream`).  A pose is eligible when
+ * pairs > 0 and, with local_max != 0, score > neighbour for each of its up to 26 lattice neighbours of LOWER index and
+ * score >= neighbour for each of HIGHER index (neighbours outside the lattice do not exist, the yaw does not wrap: a plateau
+ * yields exactly its lowest-index pose).  cand_index_dev[0 .. *n_cand_dev) = the min(top_k, eligible) eligible poses of
+ * largest score, in descending score, ties to the lower index.  top_k in 1 .. 1024.  Refusals as above. */
+int ndt_lattice_select_dev(ndt_ctx *ctx, const ndt_pose_lattice *lattice, const double *score_dev, const uint32_t *pairs_dev,
+                           int top_k, int local_max, uint64_t *cand_index_dev, int *n_cand_dev, void *stream);
+
+/* Sweep, pick, one read-back of the number of candidates (the call's one host wait before the match), then
+ * ndt_align_batch_dev's launch with shared_scan = 1 and B = n_cand from the candidates' lattice poses (formed on the device),
+ * and the records back.  Synchronous.  cand_index / cand_score / records need room for top_k entries; the first *n_cand are
+ * written.  records[c] is byte-identical to what ndt_align_batch with shared_scan gives for the same scan, map and those
+ * initial guesses.  A record's cost is `converged ? fitness : 1e7`, the reference shim's sentinel
+ * (src/PoseEstimator.cpp:43-46); *best = the index of the lowest cost, ties to the lower index, or -1 when *n_cand == 0 (the
+ * scan met no voxel anywhere on the lattice; the call still returns NDT_OK).  scores_host: P doubles for the whole volume,
+ * or NULL.  _dev: the scan already in device memory, every other pointer host memory.
+ * Where the reference falls back to odometry after a rejected match (src/ScanMatcher.cpp:60-66), a caller runs this
+ * instead.  Refusals: those of the sweep and the pick, and a NULL params or output pointer. */
+typedef struct ndt_reloc_params { ndt_pose_lattice lattice; int top_k; int local_max; } ndt_reloc_params;
+int ndt_relocalize(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride_bytes,
+                   const ndt_reloc_params *params, uint64_t *cand_index, double *cand_score, ndt_result *records,
+                   int *n_cand, int *best, double *scores_host);
+int ndt_relocalize_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride_bytes,
+                       const ndt_reloc_params *params, uint64_t *cand_index, double *cand_score, ndt_result *records,
+                       int *n_cand, int *best, double *scores_host);
 
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the

@@ -68,6 +68,39 @@ SESSION_STEP_DTYPE = np.dtype([("pose", "f8", 3), ("cov", "f8", 9), ("cost", "f8
                                ("successful", "i4"), ("status", "i4"), ("submap", "i4"), ("split", "i4")], align=True)
 
 
+class PoseLattice(C.Structure):
+    """ndt_pose_lattice (include/ndt_mi355x.h): index = (k * ny + j) * nx + i, pose = origin + (i, j, k) * step."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("yaw0", C.c_double), ("step_x", C.c_double), ("step_y", C.c_double),
+                ("step_yaw", C.c_double), ("nx", C.c_int), ("ny", C.c_int), ("nyaw", C.c_int)]
+
+    @property
+    def size(self):
+        """ndt_lattice_size (host only); raises NdtError for a lattice the library refuses."""
+        n = C.c_uint64()
+        rc = lib().ndt_lattice_size(C.byref(self), C.byref(n))
+        if rc:
+            raise NdtError("ndt_lattice_size -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+        return n.value
+
+    def pose(self, index):
+        """ndt_lattice_pose (host only): the definition of the lattice's poses."""
+        p = (C.c_double * 3)()
+        rc = lib().ndt_lattice_pose(C.byref(self), int(index), p)
+        if rc:
+            raise NdtError("ndt_lattice_pose -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+        return np.array(p[:])
+
+    def poses(self, indices=None):
+        """[len, 3] float64 lattice poses of `indices` (default: all), through ndt_lattice_pose."""
+        idx = range(self.size) if indices is None else indices
+        return np.array([self.pose(i) for i in idx], dtype=np.float64).reshape(-1, 3)
+
+
+class RelocParams(C.Structure):
+    """ndt_reloc_params (include/ndt_mi355x.h)."""
+    _fields_ = [("lattice", PoseLattice), ("top_k", C.c_int), ("local_max", C.c_int)]
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -82,7 +115,8 @@ RESULT_DTYPE = np.dtype([
 RESULT_BYTES = RESULT_DTYPE.itemsize
 FLAG_WINDOW_SPILL, FLAG_REGION_CLIPPED, FLAG_UNSORTED = 1, 2, 4      # ndt_result.flags
 NDT_OK, NDT_E_ARG, NDT_E_HIP, NDT_E_NO_DEVICE, NDT_E_GRID, NDT_E_NOMEM = 0, -1, -2, -3, -4, -5    # ndt_status
-OPT_MAX_HELPERS, OPT_WORKGROUPS, OPT_INJECT_FAULT, OPT_DEFER_FITNESS = 1, 2, 3, 4            # ndt_ctx_set_option
+OPT_MAX_HELPERS, OPT_WORKGROUPS, OPT_INJECT_FAULT, OPT_DEFER_FITNESS, OPT_SCORE_STAGE = 1, 2, 3, 4, 5     # ndt_ctx_set_option
+SCORE_STAGE_POINTS = 8000            # the score sweep stages scans up to this many points in LDS (kScoreStagePts, ndt_score.hip.h)
 
 EXPORTS = [
     "ndt_default_params", "ndt_params_pcl110", "ndt_params_pcl18", "ndt_params_pcl_new", "ndt_ctx_create", "ndt_ctx_destroy", "ndt_last_error", "ndt_ctx_stream",
@@ -98,6 +132,8 @@ EXPORTS = [
     "ndt_local_map_batch", "ndt_local_map_batch_dev", "ndt_prefilter_batch",
     "ndt_session_default_params", "ndt_sessions_create", "ndt_sessions_destroy", "ndt_sessions_step", "ndt_sessions_step_dev",
     "ndt_sessions_local_map", "ndt_sessions_submap_cloud", "ndt_sessions_global_map", "ndt_sessions_get_stats",
+    "ndt_lattice_size", "ndt_lattice_pose", "ndt_score_poses", "ndt_score_poses_dev", "ndt_score_lattice_dev",
+    "ndt_lattice_select_dev", "ndt_relocalize", "ndt_relocalize_dev",
 ]
 
 
@@ -174,6 +210,14 @@ def lib():
     L.ndt_sessions_submap_cloud.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz)]
     L.ndt_sessions_global_map.argtypes = [vp, i, vp, sz, C.POINTER(sz), vp, C.POINTER(i)]
     L.ndt_sessions_get_stats.argtypes = [vp, C.POINTER(SessionsStats)]
+    L.ndt_lattice_size.argtypes = [C.POINTER(PoseLattice), C.POINTER(C.c_uint64)]
+    L.ndt_lattice_pose.argtypes = [C.POINTER(PoseLattice), C.c_uint64, vp]
+    L.ndt_score_poses.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp]
+    L.ndt_score_poses_dev.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp, vp]
+    L.ndt_score_lattice_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(PoseLattice), vp, vp, vp]
+    L.ndt_lattice_select_dev.argtypes = [vp, C.POINTER(PoseLattice), vp, vp, i, i, vp, vp, vp]
+    L.ndt_relocalize.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
+    L.ndt_relocalize_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -786,6 +830,61 @@ class Map:
         self.ctx.check(lib().ndt_fitness_at(self.ctx.h, self.h, scan.ctypes.data, len(scan), 8, c, s, tx, ty,
                                             C.addressof(f)), "ndt_fitness_at")
         return f.value
+
+    def score_poses(self, scan, poses, stride=8):
+        """ndt_score_poses: the NDT score alone of one scan ([n, 2] float32) at every pose of `poses` ([P, 3] float64)
+        -> (score [P] float64, pairs [P] uint32).  `stride` > 8: the scan is handed over in records of that many bytes."""
+        scan = _f32c(scan)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        if stride != 8:
+            wide = np.zeros((len(scan), stride // 4), dtype=np.float32)
+            wide[:, :2] = scan
+            scan = wide
+        P = len(poses)
+        score = np.zeros(P, dtype=np.float64); pairs = np.zeros(P, dtype=np.uint32)
+        self.ctx.check(lib().ndt_score_poses(self.ctx.h, self.h, scan.ctypes.data, len(scan), stride, poses.ctypes.data, P,
+                                             score.ctypes.data, pairs.ctypes.data), "ndt_score_poses")
+        return score, pairs
+
+    def score_poses_dev(self, scan_ptr, n, poses_ptr, P, score_ptr, pairs_ptr=None, stride=8, stream=None, ctx=None):
+        """ndt_score_poses_dev: device addresses; asynchronous.  `ctx`: the context that launches (default: the map's)."""
+        cx = ctx if ctx is not None else self.ctx
+        cx.check(lib().ndt_score_poses_dev(cx.h, self.h, scan_ptr, n, stride, poses_ptr, P, score_ptr, pairs_ptr, stream),
+                 "ndt_score_poses_dev")
+
+    def score_lattice(self, scan_ptr, n, lattice, score_ptr, pairs_ptr=None, stride=8, stream=None, ctx=None):
+        """ndt_score_lattice_dev: the score volume of a PoseLattice; device addresses; asynchronous."""
+        cx = ctx if ctx is not None else self.ctx
+        cx.check(lib().ndt_score_lattice_dev(cx.h, self.h, scan_ptr, n, stride, C.byref(lattice), score_ptr, pairs_ptr, stream),
+                 "ndt_score_lattice_dev")
+
+    def lattice_select(self, lattice, score_ptr, pairs_ptr, top_k, local_max, cand_ptr, n_cand_ptr, stream=None, ctx=None):
+        """ndt_lattice_select_dev: the top_k eligible poses of a score volume (device addresses: uint64 indices, one int32
+        count); asynchronous."""
+        cx = ctx if ctx is not None else self.ctx
+        cx.check(lib().ndt_lattice_select_dev(cx.h, C.byref(lattice), score_ptr, pairs_ptr, int(top_k), int(local_max), cand_ptr,
+                                              n_cand_ptr, stream), "ndt_lattice_select_dev")
+
+    def relocalize(self, scan, lattice, top_k=16, local_max=True, want_scores=False, dev_ptr=None, n=None, stride=8):
+        """ndt_relocalize (or, with dev_ptr / n / stride, ndt_relocalize_dev): sweep the lattice, pick top_k candidates,
+        refine them with the shared-scan match -> dict(cand_index [m] uint64, cand_score [m], records [m] RESULT_DTYPE,
+        best (index of the lowest cost `converged ? fitness : 1e7`, -1 when m == 0), scores (the whole volume or None))."""
+        prm = RelocParams(lattice, int(top_k), int(bool(local_max)))
+        idx = np.zeros(top_k, dtype=np.uint64); cs = np.zeros(top_k, dtype=np.float64)
+        rec = np.zeros(top_k, dtype=RESULT_DTYPE)
+        m, best = C.c_int(), C.c_int()
+        vol = np.zeros(lattice.size, dtype=np.float64) if want_scores else None
+        volp = vol.ctypes.data if vol is not None else None
+        if dev_ptr is not None:
+            rc = lib().ndt_relocalize_dev(self.ctx.h, self.h, dev_ptr, n, stride, C.byref(prm), idx.ctypes.data, cs.ctypes.data,
+                                          rec.ctypes.data, C.byref(m), C.byref(best), volp)
+        else:
+            scan = _f32c(scan)
+            rc = lib().ndt_relocalize(self.ctx.h, self.h, scan.ctypes.data, len(scan), 8, C.byref(prm), idx.ctypes.data,
+                                      cs.ctypes.data, rec.ctypes.data, C.byref(m), C.byref(best), volp)
+        self.ctx.check(rc, "ndt_relocalize")
+        k = m.value
+        return dict(cand_index=idx[:k].copy(), cand_score=cs[:k].copy(), records=rec[:k].copy(), best=best.value, scores=vol)
 
     def close(self):
         if self.h:

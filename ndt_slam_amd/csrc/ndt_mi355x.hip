@@ -50,6 +50,7 @@ thread_local std::string g_last_error;
 #include "ndt_front.hip.h"
 #include "ndt_localmap.hip.h"
 #include "ndt_resample.hip.h"
+#include "ndt_score.hip.h"
 
 }  // namespace
 
@@ -212,10 +213,13 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_bb;
   StagedUpload<unsigned char> bb_tab;
   DevBuf<unsigned char> d_bstage;                      // ndt_map_build_batch: the host clouds' copies
+  DevBuf<unsigned char> d_sel;                         // candidate pick: the sorted lists of the runs, their lengths and heads
+  DevBuf<unsigned char> d_rl;                          // score sweep / relocalisation: poses or score volume, pair counts, candidates, guesses, records
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
   int inject_fault = 0;                                // NDT_OPT_INJECT_FAULT (tests): the k-th next match launch fails behind its first kernel
+  int score_stage = 1;                                 // NDT_OPT_SCORE_STAGE: the score sweep stages scans that fit in LDS (0: every scan is read from global memory)
   // Batches prepared ahead (ndt_align_batch_prepare_dev): two sets of buffers in turn -- ordered copies, records, bitmaps -- that
   // belong to no scratch bracket: set s is written by the prepare call for batch i + 1 while the launch of batch i, which reads
   // the other set, is still running; the prepare call orders itself behind the last launch that read ITS set and behind the
@@ -672,6 +676,9 @@ int ndt_ctx_set_option(ndt_ctx *c, int option, long long value) {
     case NDT_OPT_DEFER_FITNESS:
       if (value != 0 && value != 1) return fail(c, NDT_E_ARG, "NDT_OPT_DEFER_FITNESS: 0 or 1");
       c->defer_fitness = (int)value; return NDT_OK;
+    case NDT_OPT_SCORE_STAGE:
+      if (value != 0 && value != 1) return fail(c, NDT_E_ARG, "NDT_OPT_SCORE_STAGE: 0 or 1");
+      c->score_stage = (int)value; return NDT_OK;
     default: return fail(c, NDT_E_ARG, "ndt_ctx_set_option: unknown option");
   }
 }
@@ -2735,6 +2742,282 @@ int ndt_sessions_get_stats(const ndt_sessions *s, ndt_sessions_stats *out) {
   if (!out) return fail(s->ctx, NDT_E_ARG, "ndt_sessions_get_stats: NULL out");
   *out = s->stats;
   return NDT_OK;
+}
+
+}  // extern "C"
+
+// ---- relocalisation: score sweep, candidate pick, refinement (ndt_score_*, ndt_lattice_*, ndt_relocalize*; kernels in
+//      ndt_score.hip.h) ----
+
+namespace {
+
+// ndt_lattice_size's rule: false for a NULL lattice, a dimension below 1, a non-finite origin or step, more than 2^31 - 1 poses
+bool lattice_count(const ndt_pose_lattice *l, uint64_t *n) {
+  if (!l || l->nx < 1 || l->ny < 1 || l->nyaw < 1) return false;
+  for (double v : {l->x0, l->y0, l->yaw0, l->step_x, l->step_y, l->step_yaw})
+    if (!std::isfinite(v)) return false;
+  const uint64_t xy = (uint64_t)l->nx * (uint64_t)l->ny;                // < 2^62
+  if (xy > (uint64_t)INT32_MAX || xy * (uint64_t)l->nyaw > (uint64_t)INT32_MAX) return false;
+  *n = xy * (uint64_t)l->nyaw;
+  return true;
+}
+
+Lattice lattice_of(const ndt_pose_lattice &l) { return Lattice{l.x0, l.y0, l.yaw0, l.step_x, l.step_y, l.step_yaw, l.nx, l.ny, l.nyaw}; }
+
+// The refusals every score call starts with (synchronous, nothing queued).
+int score_check(ndt_ctx *ctx, const ndt_map *map, const void *scan, size_t n, size_t stride, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!map || !scan) return fail(ctx, NDT_E_ARG, f + ": NULL map or scan");
+  if (!map->ctx || !map->view.cent) return fail(ctx, NDT_E_ARG, f + ": the map was never built");
+  if (map->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the map was built on another device");
+  if (n == 0 || n > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, f + ": need 1 <= n <= 2^31 - 1 scan points");
+  if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad stride (need stride_bytes >= 8 and % 8 == 0)");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return NDT_OK;
+}
+
+// The sweep on st, inside the caller's scratch bracket: behind the map's build, one kernel, entered in the context's ring as a
+// reader of the map.  A sweep on another stream than the one that carries the map's builds is, to a build, what a deferred
+// launch is -- work its stream order does not cover -- and is entered as one: build_begin waits for its end.
+int queue_score(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scan, size_t n, size_t stride, const double *poses,
+                const Lattice &L, uint64_t P, double *score, unsigned *pairs) {
+  const bool foreign = st != map->ctx->stream;
+  if (foreign) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  const MapView &V = map->view;
+  const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
+  const bool chk = !(V.e_hi > 1.0 + 1e-6);            // (launch_align's rule, in the same instances)
+  const int staged = ctx->score_stage && n <= (size_t)kScoreStagePts;
+  const size_t lds = staged ? n * sizeof(float2) : 0;
+  // workgroups: as many as the CUs hold at this LDS size (four of four waves at most: the kernel's registers allow four waves per SIMD), or NDT_OPT_WORKGROUPS
+  const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, (size_t)(150 * 1024) / (lds + 1024)));
+  const uint64_t tiles = (P + kScoreTile - 1) / kScoreTile;
+  const uint64_t want = ctx->workgroups > 0 ? (uint64_t)ctx->workgroups : (uint64_t)ctx->num_cus * per_cu;
+  const unsigned grid = (unsigned)std::min<uint64_t>(tiles, want);
+  LaunchRing &R = ctx->ring;
+  Event *evr = R.events(R.launches);
+  auto sweep = [&](auto S, auto I, auto C) {
+    hipExtLaunchKernelGGL((ndt_score_kernel<decltype(S)::value, decltype(I)::value, decltype(C)::value>), dim3(grid), dim3(kScoreBlock),
+                          lds, st, evr[0], evr[1], 0, V, map->prm.libm_f32, scan, stride, (int)n, staged, poses, L,
+                          (unsigned long long)P, score, pairs);
+  };
+  const std::true_type yes; const std::false_type no;
+  if (sse && incl)      sweep(yes, yes, yes);
+  else if (sse && !chk) sweep(yes, no, no);
+  else if (sse)         sweep(yes, no, yes);
+  else if (incl)        sweep(no, yes, yes);
+  else                  sweep(no, no, yes);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_score: ") + hipGetErrorString(e));
+  // the kernel is queued: whatever happens below, the launch has its place in the ring and in the map's readers
+  const hipError_t e2 = hipEventRecord(evr[2], st);
+  LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
+  R.enter(ctx, &list, 1, foreign);
+  if (e2 != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_score: hipEventRecord: ") + hipGetErrorString(e2));
+  return NDT_OK;
+}
+
+// The pick on st, inside the caller's scratch bracket (d_sel).
+int queue_select(ndt_ctx *ctx, hipStream_t st, const Lattice &L, uint64_t P, const double *score, const unsigned *pairs, int top_k,
+                 int local_max, unsigned long long *cand, int *n_cand) {
+  const size_t tiles = (size_t)((P + kSelTile - 1) / kSelTile);
+  const size_t sorted_bytes = align256(tiles * kSelTile * sizeof(unsigned short)), cnt_bytes = align256(tiles * sizeof(unsigned));
+  int rc;
+  if ((rc = ctx->d_sel.ensure(ctx, sorted_bytes + 2 * cnt_bytes))) return rc;
+  unsigned short *sorted = (unsigned short *)ctx->d_sel.p;
+  unsigned *cnt = (unsigned *)(ctx->d_sel.p + sorted_bytes), *head = (unsigned *)(ctx->d_sel.p + sorted_bytes + cnt_bytes);
+  const unsigned grid = (unsigned)std::min<size_t>(tiles, (size_t)ctx->num_cus * 2);
+  lattice_rank_kernel<<<grid, kSelTile, 0, st>>>(L, (unsigned long long)P, score, pairs, local_max, sorted, cnt, head);
+  lattice_merge_kernel<<<1, kSelTile, 0, st>>>((unsigned long long)P, score, sorted, cnt, head, top_k, cand, n_cand);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_lattice_select_dev: ") + hipGetErrorString(e));
+  return NDT_OK;
+}
+
+// ndt_relocalize / ndt_relocalize_dev: the scan is host memory (scan_host) or device memory (scan_dev).
+int relocalize_impl(ndt_ctx *ctx, const ndt_map *map, const float *scan_host, const float *scan_dev, size_t n, size_t stride,
+                    const ndt_reloc_params *prm, uint64_t *cand_index, double *cand_score, ndt_result *records, int *n_cand, int *best,
+                    double *scores_host, const char *fn) {
+  int rc = score_check(ctx, map, scan_host ? (const void *)scan_host : (const void *)scan_dev, n, stride, fn);
+  if (rc) return rc;
+  const std::string f(fn);
+  if (!prm || !cand_index || !cand_score || !records || !n_cand || !best) return fail(ctx, NDT_E_ARG, f + ": NULL parameters or outputs");
+  uint64_t P = 0;
+  if (!lattice_count(&prm->lattice, &P)) return fail(ctx, NDT_E_ARG, f + ": bad lattice (a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
+  const int K = prm->top_k;
+  if (K < 1 || K > 1024) return fail(ctx, NDT_E_ARG, f + ": top_k must be in 1 .. 1024");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const Lattice L = lattice_of(prm->lattice);
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  // the volume, the candidates, the guesses and the records: one grow-only allocation
+  const size_t o_pairs = align256((size_t)P * 8), o_cand = o_pairs + align256((size_t)P * 4), o_ncand = o_cand + align256((size_t)K * 8),
+               o_init = o_ncand + 256, o_cscore = o_init + align256((size_t)K * 24), o_off = o_cscore + align256((size_t)K * 8),
+               o_res = o_off + 256, total = o_res + align256((size_t)K * sizeof(ndt_result));
+  if ((rc = ctx->d_rl.ensure(ctx, total))) return rc;
+  unsigned char *base = ctx->d_rl.p;
+  double *d_score = (double *)base; unsigned *d_pairs = (unsigned *)(base + o_pairs);
+  unsigned long long *d_cand = (unsigned long long *)(base + o_cand); int *d_ncand = (int *)(base + o_ncand);
+  double *d_init = (double *)(base + o_init), *d_cscore = (double *)(base + o_cscore);
+  unsigned long long *d_off = (unsigned long long *)(base + o_off); ndt_result *d_res = (ndt_result *)(base + o_res);
+  // the scan, packed: what the match reads (the sweep reads the same copy)
+  const float *scan = scan_dev;
+  if (scan_host || stride != 8) {
+    if ((rc = ctx->d_scan.ensure(ctx, n * 8))) return rc;
+    if (scan_host && stride == 8) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan_host, n * 8, hipMemcpyHostToDevice, st));
+    } else {
+      const float *src = scan_dev;
+      if (scan_host) {
+        if ((rc = ctx->d_tmp.ensure(ctx, n * stride))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp.p, scan_host, n * stride, hipMemcpyHostToDevice, st));
+        src = (const float *)ctx->d_tmp.p;
+      }
+      repack_f2_kernel<<<grid_for(n, 256), 256, 0, st>>>(src, stride, n, (float2 *)ctx->d_scan.p);
+    }
+    scan = (const float *)ctx->d_scan.p;
+  }
+  const unsigned long long h_off[2] = {0ull, (unsigned long long)n};
+  HIP_TRY(ctx, hipMemcpyAsync(d_off, h_off, sizeof(h_off), hipMemcpyHostToDevice, st));
+  // sweep, pick, the candidates' poses -- then the call's one host wait before the match: how many there are
+  if ((rc = queue_score(ctx, map, st, scan, n, 8, nullptr, L, P, d_score, d_pairs))) return rc;
+  if ((rc = queue_select(ctx, st, L, P, d_score, d_pairs, K, prm->local_max, d_cand, d_ncand))) return rc;
+  lattice_cand_kernel<<<(K + 255) / 256, 256, 0, st>>>(L, d_cand, d_ncand, K, d_score, d_init, d_cscore);
+  HIP_TRY(ctx, hipGetLastError());
+  int nc = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&nc, d_ncand, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  *n_cand = nc; *best = -1;
+  if (nc > 0) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
+    if ((rc = launch_align(ctx, map, st, scan, d_off, nc, 1, n, d_init, d_res, nullptr, 0, nullptr, nullptr))) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
+    HIP_TRY(ctx, hipMemcpyAsync(records, d_res, (size_t)nc * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(cand_index, d_cand, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(cand_score, d_cscore, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (scores_host) HIP_TRY(ctx, hipMemcpyAsync(scores_host, d_score, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (nc > 0) HIP_TRY(ctx, hipEventElapsedTime(&ctx->align_ms, ctx->ev0, ctx->ev1));
+  // the shim's cost (src/PoseEstimator.cpp:43-46): the fitness of a converged match, else 1e7; lowest first, ties to the lower index
+  double best_cost = 0.0;
+  for (int c = 0; c < nc; ++c) {
+    const double cost = records[c].converged ? records[c].fitness : 1e7;
+    if (*best < 0 || cost < best_cost) { *best = c; best_cost = cost; }
+  }
+  return NDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_lattice_size(const ndt_pose_lattice *l, uint64_t *n_poses) {
+  uint64_t n = 0;
+  if (!n_poses || !lattice_count(l, &n))
+    return fail(nullptr, NDT_E_ARG, "ndt_lattice_size: NULL pointer, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses");
+  *n_poses = n;
+  return NDT_OK;
+}
+
+int ndt_lattice_pose(const ndt_pose_lattice *l, uint64_t index, double pose_xyyaw[3]) {
+#pragma clang fp contract(off)
+  uint64_t n = 0;
+  if (!pose_xyyaw || !lattice_count(l, &n) || index >= n) return fail(nullptr, NDT_E_ARG, "ndt_lattice_pose: NULL pointer, bad lattice or index out of range");
+  const uint64_t row = index / (uint64_t)l->nx;
+  const uint64_t i = index - row * (uint64_t)l->nx, k = row / (uint64_t)l->ny, j = row - k * (uint64_t)l->ny;
+  // one rounded multiply, one rounded add: this IS the definition (lattice_pose on the device gives the same bits)
+  const double mx = (double)i * l->step_x, my = (double)j * l->step_y, mk = (double)k * l->step_yaw;
+  pose_xyyaw[0] = l->x0 + mx; pose_xyyaw[1] = l->y0 + my; pose_xyyaw[2] = l->yaw0 + mk;
+  return NDT_OK;
+}
+
+int ndt_score_poses_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride, const double *poses_dev,
+                        uint64_t P, double *score_dev, uint32_t *pairs_dev, void *stream) {
+  int rc = score_check(ctx, map, scan_xy_dev, n, stride, "ndt_score_poses_dev");
+  if (rc) return rc;
+  if (!poses_dev || !score_dev) return fail(ctx, NDT_E_ARG, "ndt_score_poses_dev: NULL poses or score");
+  if (P < 1 || P > (uint64_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_score_poses_dev: need 1 <= P <= 2^31 - 1 poses");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);                     // (no scratch of its own: the bracket keeps the context's launches in order)
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_score(ctx, map, st, scan_xy_dev, n, stride, poses_dev, Lattice{}, P, score_dev, pairs_dev))) return rc;
+  return scope.close();
+}
+
+int ndt_score_lattice_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride,
+                          const ndt_pose_lattice *lattice, double *score_dev, uint32_t *pairs_dev, void *stream) {
+  int rc = score_check(ctx, map, scan_xy_dev, n, stride, "ndt_score_lattice_dev");
+  if (rc) return rc;
+  if (!score_dev) return fail(ctx, NDT_E_ARG, "ndt_score_lattice_dev: NULL score");
+  uint64_t P = 0;
+  if (!lattice_count(lattice, &P))
+    return fail(ctx, NDT_E_ARG, "ndt_score_lattice_dev: bad lattice (NULL, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_score(ctx, map, st, scan_xy_dev, n, stride, nullptr, lattice_of(*lattice), P, score_dev, pairs_dev))) return rc;
+  return scope.close();
+}
+
+int ndt_score_poses(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride, const double *poses_host,
+                    uint64_t P, double *score_host, uint32_t *pairs_host) {
+  int rc = score_check(ctx, map, scan_xy_host, n, stride, "ndt_score_poses");
+  if (rc) return rc;
+  if (!poses_host || !score_host) return fail(ctx, NDT_E_ARG, "ndt_score_poses: NULL poses or score");
+  if (P < 1 || P > (uint64_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_score_poses: need 1 <= P <= 2^31 - 1 poses");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);
+  if ((rc = scope.open())) return rc;
+  const size_t o_score = align256((size_t)P * 24), o_pairs = o_score + align256((size_t)P * 8);
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
+  if ((rc = ctx->d_rl.ensure(ctx, o_pairs + (size_t)P * 4))) return rc;
+  double *d_poses = (double *)ctx->d_rl.p, *d_score = (double *)(ctx->d_rl.p + o_score);
+  unsigned *d_pairs = (unsigned *)(ctx->d_rl.p + o_pairs);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan_xy_host, n * stride, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_poses, poses_host, (size_t)P * 24, hipMemcpyHostToDevice, st));
+  if ((rc = queue_score(ctx, map, st, (const float *)ctx->d_scan.p, n, stride, d_poses, Lattice{}, P, d_score, d_pairs))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(score_host, d_score, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  if (pairs_host) HIP_TRY(ctx, hipMemcpyAsync(pairs_host, d_pairs, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+int ndt_lattice_select_dev(ndt_ctx *ctx, const ndt_pose_lattice *lattice, const double *score_dev, const uint32_t *pairs_dev, int top_k,
+                           int local_max, uint64_t *cand_index_dev, int *n_cand_dev, void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!score_dev || !pairs_dev || !cand_index_dev || !n_cand_dev) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: NULL array");
+  uint64_t P = 0;
+  if (!lattice_count(lattice, &P))
+    return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: bad lattice (NULL, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
+  if (top_k < 1 || top_k > 1024) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: top_k must be in 1 .. 1024");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: an ndt_map_rebuild_begin is open on the context");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);
+  int rc;
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_select(ctx, st, lattice_of(*lattice), P, score_dev, pairs_dev, top_k, local_max, (unsigned long long *)cand_index_dev, n_cand_dev)))
+    return rc;
+  return scope.close();
+}
+
+int ndt_relocalize(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride, const ndt_reloc_params *prm,
+                   uint64_t *cand_index, double *cand_score, ndt_result *records, int *n_cand, int *best, double *scores_host) {
+  return relocalize_impl(ctx, map, scan_xy_host, nullptr, n, stride, prm, cand_index, cand_score, records, n_cand, best, scores_host,
+                         "ndt_relocalize");
+}
+
+int ndt_relocalize_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride, const ndt_reloc_params *prm,
+                       uint64_t *cand_index, double *cand_score, ndt_result *records, int *n_cand, int *best, double *scores_host) {
+  return relocalize_impl(ctx, map, nullptr, scan_xy_dev, n, stride, prm, cand_index, cand_score, records, n_cand, best, scores_host,
+                         "ndt_relocalize_dev");
 }
 
 }  // extern "C"
