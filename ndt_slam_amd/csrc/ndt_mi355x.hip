@@ -2180,28 +2180,70 @@ namespace {
 
 // Local-map assembly: the job table (one entry per scan triple) and the unit table (256-point stretches of the
 // result) are written into pinned memory, uploaded with one copy and consumed by the kernels of
-// ndt_localmap.hip.h.  Device scratch (ctx->d_mm):
-// [jobs][units][submaps][previous clouds][unit counts][unit offsets][keep bits][diff counts][voxel sets][diff lists]
+// ndt_localmap.hip.h.  Device scratch (ctx->d_mm): [jobs][units][submaps][previous clouds], then the chain's own (MmScratch)
 // (the submap and previous-cloud tables only in a batched call, ndt_local_map_batch_dev: the upload ends behind them).
-struct MmPlan {
-  struct Pair { const float *a0, *a1, *b; size_t n0, n1, nb; double res = 0.0; float cut = 0.f; };   // res, cut: batched calls
-  std::vector<Pair> pairs;
-  size_t sa = 8, sb = 8;
-  size_t unit_room = 0;
-  size_t n_subs = 0;         // batched calls: submaps (the tables of MmSub and PfPrev follow the units)
-};
-struct MmLayout {
-  size_t o_units = 0, o_subs = 0, o_prev = 0, o_ucnt = 0, o_uoff = 0, o_keep = 0, o_cnt = 0, o_tab = 0, o_diff = 0;
-  MmJob *jobs = nullptr;     // pinned, valid until the next call on this context
-  MmUnit *units = nullptr;   // pinned
-  MmSub *subs = nullptr;     // pinned (batched calls)
-  PfPrev *prevs = nullptr;   // pinned (batched calls)
+size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
+size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
+
+// Consecutive regions of one block, each at a multiple of 64 bytes: take() gives the next one's offset, `end` is the block's size
+struct Regions {
+  size_t end = 0;
+  size_t take(size_t bytes) { const size_t o = up64(end); end = o + bytes; return o; }
 };
 
-// One submap's scan triples (appended to P.pairs) and the pieces of its cloud (appended to `pieces`) in the order
-// Submap::makeMap appends them -- the rule of the single and the batched assembly.  cut: rn_cutoff(D.thre_neighbor).
+// The scan triples of a call (of a step of a session set), their jobs still unbound (mm_bind).
+struct MmPlan {
+  std::vector<MmJob> jobs;
+  size_t sa = 8, sb = 8;     // set before the first add()
+  size_t unit_room = 0;
+  size_t n_subs = 0;         // batched calls: submaps (the tables of MmSub and PfPrev follow the units)
+  size_t tab_words = 0, list_pts = 0;      // over the jobs: the voxel sets' words, the difference lists' points
+  // One triple: base cloud a0 ++ a1, test cloud b; res, cut: batched calls.  The one place that sizes a voxel set.
+  void add(const float *a0, const float *a1, const float *b, size_t n0, size_t n1, size_t nb, double res = 0.0, float cut = 0.f) {
+    const size_t cap = pow2_at_least(2 * (n0 + n1) + 2);
+    MmJob J{};
+    J.a0 = a0; J.a1 = a1; J.b = b; J.n0 = (unsigned)n0; J.n1 = (unsigned)n1; J.nb = (unsigned)nb;
+    J.sa = (unsigned)sa; J.sb = (unsigned)sb; J.tab_mask = (unsigned)(cap - 1); J.res = res; J.cut = cut;
+    jobs.push_back(J);
+    tab_words += cap; list_pts += nb;
+  }
+};
+
+// The chain's device-only scratch for P's jobs and P.unit_room units, as offsets into the block the caller lays out (behind the
+// uploaded tables in ctx->d_mm, behind the units in a session set's mm)
+struct MmScratch {
+  size_t ucnt = 0, uoff = 0, keep = 0, cnt = 0, tab = 0, diff = 0, nj = 0, nu = 0, tab_words = 0;
+  MmScratch() = default;
+  MmScratch(Regions &R, const MmPlan &P) : nj(P.jobs.size()), nu(P.unit_room), tab_words(P.tab_words) {
+    ucnt = R.take(nu * 4); uoff = R.take(nu * 8); keep = R.take(nu * (kMmUnit / 64) * 8);      // per unit
+    cnt = R.take(nj * 8 + 8); tab = R.take(tab_words * 8); diff = R.take(P.list_pts * 8 + 64);      // difference counts, voxel sets, lists
+  }
+};
+struct MmLayout {
+  size_t o_units = 0, o_subs = 0, o_prev = 0, o_up = 0;      // o_up: where the uploaded tables end
+  MmScratch x;
+  MmJob *jobs = nullptr; MmUnit *units = nullptr;      // pinned, valid until the next call on this context
+  MmSub *subs = nullptr; PfPrev *prevs = nullptr;      // pinned (batched calls)
+};
+
+// Jobs [0, nj) get their voxel sets, difference lists and counters in scratch X of the block at d, one behind the other.
+// diff_override / n_diff_override: every list / counter is the caller's instead (ndt_difference_extraction_dev: one job).
+void mm_bind(MmJob *jobs, size_t nj, char *d, const MmScratch &X, float2 *diff_override = nullptr, unsigned long long *n_diff_override = nullptr) {
+  size_t tw = 0, lp = 0;
+  for (size_t j = 0; j < nj; ++j) {
+    MmJob &J = jobs[j];
+    J.tab = (unsigned long long *)(d + X.tab) + tw;
+    J.diff = diff_override ? diff_override : (float2 *)(d + X.diff) + lp;
+    J.n_diff = n_diff_override ? n_diff_override : (unsigned long long *)(d + X.cnt) + j;
+    tw += (size_t)J.tab_mask + 1; lp += J.nb;
+  }
+}
+
+// One submap's scan triples (added to P) and the pieces of its cloud (appended to `pieces`) in the order
+// Submap::makeMap appends them -- the rule of the single and the batched assembly, of the whole submap; the sessions' step
+// holds the same branches in their incremental form (SsStep::book, ndt_sessions.hip.h).  cut: rn_cutoff(D.thre_neighbor).
 // Returns the units (stretches of kMmUnit points) the pieces take.
-struct MmPiece { const float *p; size_t n; int job; };      // job: the piece's triple in P.pairs, or -1
+struct MmPiece { const float *p; size_t n; int job; };      // job: the piece's triple in P.jobs, or -1
 size_t submap_pieces(const ndt_submap_desc &D, size_t stride, float cut, MmPlan *P, std::vector<MmPiece> *pieces) {
   auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
   auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
@@ -2211,8 +2253,8 @@ size_t submap_pieces(const ndt_submap_desc &D, size_t stride, float cut, MmPlan 
     if (D.first_submap) piece(0, -1);
     for (int i = 0; i + 2 < D.n_scans; ++i)
       if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
-        piece(i + 1, (int)P->pairs.size());
-        P->pairs.push_back({scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut});
+        piece(i + 1, (int)P->jobs.size());
+        P->add(scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut);
       }
     if (D.newest) piece(D.n_scans - 1, -1);
   } else {
@@ -2230,64 +2272,38 @@ MmUnit *fill_units(MmUnit *units, const MmPiece *first, const MmPiece *last, siz
   return units;
 }
 
-size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
-size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
-
-int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, hipStream_t st, MmLayout *Lo) {
-  const size_t nj = P.pairs.size(), nu = P.unit_room, ns = P.n_subs;
-  size_t tab_words = 0, list_pts = 0;
-  for (const auto &q : P.pairs) { tab_words += pow2_at_least(2 * (q.n0 + q.n1) + 2); list_pts += q.nb; }
+// Lays out ctx->d_mm and the pinned tables, and writes the jobs, bound.  Queues nothing.
+int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, unsigned long long *n_diff_override, MmLayout *Lo) {
+  const size_t nj = P.jobs.size(), nu = P.unit_room, ns = P.n_subs;
   MmLayout L;
-  L.o_units = up64(nj * sizeof(MmJob));
-  L.o_subs = L.o_units + up64(nu * sizeof(MmUnit));
-  L.o_prev = L.o_subs + up64(ns * sizeof(MmSub));
-  L.o_ucnt = L.o_prev + up64(ns * sizeof(PfPrev));
-  L.o_uoff = L.o_ucnt + up64(nu * 4);
-  L.o_keep = L.o_uoff + up64(nu * 8);
-  L.o_cnt = L.o_keep + up64(nu * (kMmUnit / 64) * 8);
-  L.o_tab = L.o_cnt + up64(nj * 8 + 8);
-  L.o_diff = L.o_tab + tab_words * 8;
-  const size_t total = L.o_diff + list_pts * 8 + 64;
+  Regions R;
+  R.take(nj * sizeof(MmJob));
+  L.o_units = R.take(nu * sizeof(MmUnit)); L.o_subs = R.take(ns * sizeof(MmSub)); L.o_prev = R.take(ns * sizeof(PfPrev));
+  L.o_up = up64(R.end);
+  L.x = MmScratch(R, P);
   int rc;                                            // (the scratch bracket around mm_prepare + mm_run is the caller's: ScratchScope)
-  if ((rc = ctx->d_mm.ensure(ctx, total))) return rc;
-  if ((rc = ctx->mm_tab.reserve(ctx, L.o_ucnt))) return rc;      // (waits for the previous call's upload)
-  char *d = (char *)ctx->d_mm.p, *h = (char *)ctx->mm_tab.h.p;
-  L.jobs = (MmJob *)h;
-  L.units = (MmUnit *)(h + L.o_units);
-  L.subs = (MmSub *)(h + L.o_subs);
-  L.prevs = (PfPrev *)(h + L.o_prev);
-  unsigned long long *d_cnt = (unsigned long long *)(d + L.o_cnt);
-  size_t tw = 0, lp = 0;
-  for (size_t j = 0; j < nj; ++j) {
-    const auto &q = P.pairs[j];
-    const size_t cap = pow2_at_least(2 * (q.n0 + q.n1) + 2);
-    MmJob &J = L.jobs[j];
-    J.a0 = q.a0; J.a1 = q.a1; J.b = q.b;
-    J.n0 = (unsigned)q.n0; J.n1 = (unsigned)q.n1; J.nb = (unsigned)q.nb;
-    J.sa = (unsigned)P.sa; J.sb = (unsigned)P.sb;
-    J.tab_mask = (unsigned)(cap - 1);
-    J.tab = (unsigned long long *)(d + L.o_tab) + tw;
-    J.diff = diff_override ? diff_override : (float2 *)(d + L.o_diff) + lp;
-    J.n_diff = d_cnt + j;
-    J.res = q.res; J.cut = q.cut;
-    tw += cap; lp += q.nb;
-  }
-  if (tab_words) HIP_TRY(ctx, hipMemsetAsync(d + L.o_tab, 0xff, tab_words * 8, st));
+  if ((rc = ctx->d_mm.ensure(ctx, R.end))) return rc;
+  if ((rc = ctx->mm_tab.reserve(ctx, L.o_up))) return rc;      // (waits for the previous call's upload)
+  char *h = (char *)ctx->mm_tab.h.p;
+  L.jobs = (MmJob *)h; L.units = (MmUnit *)(h + L.o_units); L.subs = (MmSub *)(h + L.o_subs); L.prevs = (PfPrev *)(h + L.o_prev);
+  if (nj) memcpy(L.jobs, P.jobs.data(), nj * sizeof(MmJob));
+  mm_bind(L.jobs, nj, (char *)ctx->d_mm.p, L.x, diff_override, n_diff_override);
   *Lo = L;
   return NDT_OK;
 }
 
-// uploads jobs + units and queues the kernels; out/n_out are only used when there are units
-int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, double thre, float *out_xy,
-           uint64_t *n_out, hipStream_t st) {
+// fills the voxel sets, uploads jobs + units and queues the kernels; out/n_out are only used when there are units
+int mm_run(ndt_ctx *ctx, const MmLayout &L, double resol, double thre, float *out_xy, uint64_t *n_out, hipStream_t st) {
   char *d = (char *)ctx->d_mm.p;
+  const size_t nj = L.x.nj, nu = L.x.nu;
+  if (L.x.tab_words) HIP_TRY(ctx, hipMemsetAsync(d + L.x.tab, 0xff, L.x.tab_words * 8, st));
   const size_t bytes = nu ? L.o_units + nu * sizeof(MmUnit) : nj * sizeof(MmJob);
   if (bytes) HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, bytes, st));
   if (nj) make_map_diff_kernel<false><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, resol);
   if (nu) {
     const MmUnit *units = (const MmUnit *)(d + L.o_units);
-    unsigned *ucnt = (unsigned *)(d + L.o_ucnt);
-    unsigned long long *uoff = (unsigned long long *)(d + L.o_uoff), *keep = (unsigned long long *)(d + L.o_keep);
+    unsigned *ucnt = (unsigned *)(d + L.x.ucnt);
+    unsigned long long *uoff = (unsigned long long *)(d + L.x.uoff), *keep = (unsigned long long *)(d + L.x.keep);
     make_map_flag_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, rn_cutoff(thre), keep, ucnt);
     make_map_offsets_kernel<<<1, 1024, 0, st>>>(ucnt, (int)nu, uoff, (unsigned long long *)n_out);
     make_map_copy_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, (const unsigned long long *)n_out,
@@ -2297,24 +2313,30 @@ int mm_run(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, double resol, 
   return NDT_OK;
 }
 
-// The batched form (ndt_local_map_batch_dev): ONE upload of jobs + units + the submap tables, then the same chain over all
-// submaps at once, with the offsets in two levels (per submap, then over the submaps) and a status per submap.
-int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t nj, size_t nu, size_t ns, float *cloud_xy, uint64_t *cloud_off,
-                 int *status, hipStream_t st) {
-  char *d = (char *)ctx->d_mm.p;
-  HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, L.o_prev + ns * sizeof(PfPrev), st));
-  const MmUnit *units = (const MmUnit *)(d + L.o_units);
-  unsigned *ucnt = (unsigned *)(d + L.o_ucnt);
-  unsigned long long *uoff = (unsigned long long *)(d + L.o_uoff), *keep = (unsigned long long *)(d + L.o_keep);
-  if (nj) make_map_diff_kernel<true><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, 0.0);
-  if (nu) make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, 0.f, keep, ucnt);
-  make_map_sub_offsets_kernel<<<(unsigned)ns, 1024, 0, st>>>(ucnt, (const MmSub *)(d + L.o_subs), uoff,
-                                                            (unsigned long long *)cloud_off, status);
-  make_map_sub_scan_kernel<<<1, 1024, 0, st>>>((unsigned long long *)cloud_off, (int)ns);
-  if (nu) make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, (float2 *)cloud_xy,
-                                                                      (const unsigned long long *)cloud_off, status);
+// The batched chain over tables that are on the device (jobs, units, subs) and scratch X of the block at d: the fill of
+// the voxel sets, then every kernel once for all submaps, with the offsets in two levels (per submap, then over the
+// submaps) and a status per submap.  The two offset kernels run even with no units.
+int mm_queue_batch(ndt_ctx *ctx, const MmJob *jobs, const MmUnit *units, const MmSub *subs, char *d, const MmScratch &X, size_t ns,
+                   float2 *cloud_xy, unsigned long long *cloud_off, int *status, hipStream_t st) {
+  const size_t nj = X.nj, nu = X.nu;
+  unsigned *ucnt = (unsigned *)(d + X.ucnt);
+  unsigned long long *uoff = (unsigned long long *)(d + X.uoff), *keep = (unsigned long long *)(d + X.keep);
+  if (X.tab_words) HIP_TRY(ctx, hipMemsetAsync(d + X.tab, 0xff, X.tab_words * 8, st));
+  if (nj) make_map_diff_kernel<true><<<(unsigned)nj, kMmBlock, 0, st>>>(jobs, 0.0);
+  if (nu) make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(jobs, units, 0.f, keep, ucnt);
+  make_map_sub_offsets_kernel<<<(unsigned)ns, 1024, 0, st>>>(ucnt, subs, uoff, cloud_off, status);
+  make_map_sub_scan_kernel<<<1, 1024, 0, st>>>(cloud_off, (int)ns);
+  if (nu) make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, cloud_xy, cloud_off, status);
   HIP_TRY(ctx, hipGetLastError());
   return NDT_OK;
+}
+
+// The batched form (ndt_local_map_batch_dev): ONE upload of jobs + units + the submap tables, then the chain.
+int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t ns, float *cloud_xy, uint64_t *cloud_off, int *status, hipStream_t st) {
+  char *d = (char *)ctx->d_mm.p;
+  HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, L.o_prev + ns * sizeof(PfPrev), st));
+  return mm_queue_batch(ctx, (const MmJob *)d, (const MmUnit *)(d + L.o_units), (const MmSub *)(d + L.o_subs), d, L.x, ns,
+                        (float2 *)cloud_xy, (unsigned long long *)cloud_off, status, st);
 }
 
 }  // namespace
@@ -2331,16 +2353,15 @@ int ndt_difference_extraction_dev(ndt_ctx *ctx, const float *base_xy, size_t bas
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   MmPlan P;
-  P.pairs.push_back({base_xy, base_xy, test_xy, n_base, 0, n_test});
   P.sa = base_stride; P.sb = test_stride;
+  P.add(base_xy, base_xy, test_xy, n_base, 0, n_test);
   MmLayout L;
   int rc;
   // the difference list is written straight to the caller's buffer, its count to the caller's counter
   ScratchScope scope(ctx, st);
   if ((rc = scope.open())) return rc;
-  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, st, &L))) return rc;
-  L.jobs[0].n_diff = (unsigned long long *)n_out;
-  if ((rc = mm_run(ctx, L, 1, 0, resol, 0.0, nullptr, nullptr, st))) return rc;
+  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, (unsigned long long *)n_out, &L))) return rc;
+  if ((rc = mm_run(ctx, L, resol, 0.0, nullptr, nullptr, st))) return rc;
   return scope.close();
 }
 
@@ -2393,10 +2414,10 @@ int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy, size_t stride, const u
   int rc;
   ScratchScope scope(ctx, st);
   if ((rc = scope.open())) return rc;
-  if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
+  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
   fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
   if (nu == 0) HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(uint64_t), st));
-  if ((rc = mm_run(ctx, L, P.pairs.size(), nu, resol, thre_neighbor, out_xy, n_out, st))) return rc;
+  if ((rc = mm_run(ctx, L, resol, thre_neighbor, out_xy, n_out, st))) return rc;
   return scope.close();
 }
 
@@ -2500,13 +2521,13 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
     cap_cloud += submap_points(D);
     total_prev += D.n_prev;
   }
-  if (nu > (size_t)INT32_MAX || P.pairs.size() > (size_t)INT32_MAX)
+  if (nu > (size_t)INT32_MAX || P.jobs.size() > (size_t)INT32_MAX)
     return fail(ctx, NDT_E_ARG, "ndt_local_map_batch_dev: more than 2^31 units of 256 points or scan triples in one call");
   P.unit_room = nu;
   MmLayout L;
   ScratchScope scope(ctx, st);
   if ((rc = scope.open())) return rc;
-  if ((rc = mm_prepare(ctx, P, nullptr, st, &L))) return rc;
+  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
   MmUnit *u = L.units;
   for (int s = 0; s < n_subs; ++s) {
     L.subs[s].u0 = (unsigned)(u - L.units);
@@ -2514,7 +2535,7 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
     L.subs[s].u1 = (unsigned)(u - L.units);
     L.prevs[s] = PfPrev{subs[s].n_prev ? subs[s].prev_xy : nullptr, (unsigned long long)subs[s].n_prev};
   }
-  if ((rc = mm_run_batch(ctx, L, P.pairs.size(), nu, (size_t)n_subs, cloud_xy, cloud_off, status, st))) return rc;
+  if ((rc = mm_run_batch(ctx, L, (size_t)n_subs, cloud_xy, cloud_off, status, st))) return rc;
   if (target_xy) {
     // Submap::filterPoints of every cloud, behind its previous submap's cloud: cloud_xy / cloud_off are the filter's input form
     const PfPrev *d_prev = (const PfPrev *)((const char *)ctx->d_mm.p + L.o_prev);

@@ -273,21 +273,29 @@ int ss_check_params(ndt_ctx *ctx, const ndt_session_params &p) {
 
 unsigned ss_gx(size_t total, int B) { return (unsigned)std::min<size_t>(64, (total / (size_t)std::max(B, 1) + 255) / 256 + 1); }
 
-// The step.  raw_dev / odo_dev: the device form (then raw_host / odo_host are NULL).  Every return with a HIP error leaves
-// the set dead (the caller marks it).
-int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, size_t stride, const uint64_t *raw_offsets,
-            const double *odo_host, const double *odo_dev_in, const unsigned char *active, ndt_session_step *out) {
-  ndt_ctx *ctx = s->ctx;
-  const int S = s->S;
-  const ndt_session_params &P = s->prm;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
+// What passes between the parts of one step (DESIGN.md 4.10's list), in the order the parts fill it.
+struct SsStep {
+  // the call; raw_dev / odo_dev: the device form (then raw_host / odo_host are NULL)
+  ndt_sessions *s; const double *raw_host, *raw_dev; size_t stride; const uint64_t *raw_offsets; const double *odo_host, *odo_dev;
+  const unsigned char *active; ndt_session_step *out;
+  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
   ndt_sessions_stats stats{};
-  const size_t N = (size_t)(raw_offsets[S] - raw_offsets[0]);
+  std::vector<int> mode, map_of; std::vector<const ndt_map *> maps;      // who steps
+  std::vector<uint64_t> rs_off;                    // the front part: the resampled scans' offsets
+  // the bookkeeping: table B's contents, the newest triples (unit_room: their units) and the submaps of one triple each
+  int cur = 0;                                     // this step's arenas; the last step's are s->cur
+  std::vector<SsCopy> moves;                       // carried-over scans and closed clouds
+  std::vector<float2 *> dst; std::vector<SsPlan> plan; std::vector<PfPrev> prevs;
+  MmPlan tri; std::vector<MmSub> subs; float cut = 0.f;      // (cut: rn_cutoff of the set's thre_neighbor)
+  size_t cap_cloud = 0, total_prev = 0, carry_cloud = 0, carry_target = 0;
+  size_t b_toff = 0, b_coff = 0, b_plen = 0, b_stat = 0;      // the part behind it: where wait 2's read-back lies in h_back
+  bool who_steps(); int front(); int bookkeeping(); int behind(); int close();      // the parts, in this order
+  int book(int i, size_t n_new);
+};
 
-  // ---- who steps ----
-  std::vector<int> mode((size_t)S, kSsNone), map_of((size_t)S, -1);
-  std::vector<const ndt_map *> maps;
+// ---- who steps; false: nobody (the records and the stats are written) ----
+bool SsStep::who_steps() {
+  mode.assign((size_t)S, kSsNone); map_of.assign((size_t)S, -1);
   int n_active = 0;
   for (int i = 0; i < S; ++i) {
     if (active && !active[i]) continue;
@@ -299,38 +307,36 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
       if (Q.map) { map_of[(size_t)i] = (int)maps.size(); maps.push_back(Q.map); }
     }
   }
-  if (n_active == 0) {
-    for (int i = 0; i < S; ++i) { memset(&out[i], 0, sizeof(out[i])); out[i].submap = s->ses[(size_t)i].n_closed; }
-    s->stats = stats;
-    return NDT_OK;
-  }
+  if (n_active) return true;
+  for (int i = 0; i < S; ++i) { memset(&out[i], 0, sizeof(out[i])); out[i].submap = s->ses[(size_t)i].n_closed; }
+  s->stats = stats;
+  return false;
+}
 
-  // ---- phase A: upload, resample -> pre-filter -> predict -> match -> fuse -> select ----
+// ---- the front part: upload, resample -> pre-filter -> predict -> match -> fuse -> select, host wait 1 ----
+int SsStep::front() {
+  const size_t N = (size_t)(raw_offsets[S] - raw_offsets[0]), S1 = (size_t)S + 1;
   size_t cap_rs = 0;
   if (ndt_resample_capacity(std::max<size_t>(N, 1), P.space, P.space_thre, &cap_rs))
     return fail(ctx, NDT_E_ARG, "ndt_sessions_step: the resampled scans' capacity overflows");
-  const size_t S1 = (size_t)S + 1;
   SS_TRY(s->raw_off.ensure(ctx, S1)); SS_TRY(s->rs_off.ensure(ctx, S1)); SS_TRY(s->src_off.ensure(ctx, S1));
   SS_TRY(s->rs64.ensure(ctx, 2 * cap_rs)); SS_TRY(s->rs32.ensure(ctx, 2 * cap_rs)); SS_TRY(s->src.ensure(ctx, 2 * cap_rs));
   // table A: raw offsets (relative) | mode | map_of | odometry (host form)
-  const size_t a_off = 0, a_mode = a_off + S1 * 8, a_mapof = a_mode + up64((size_t)S * 4), a_odo = a_mapof + up64((size_t)S * 4);
-  const size_t a_bytes = a_odo + (odo_host ? (size_t)S * 24 : 0);
-  SS_TRY(s->tab_a.reserve(ctx, a_bytes));
-  SS_TRY(s->d_tab_a.ensure(ctx, a_bytes));
-  {
-    unsigned char *h = s->tab_a.h.p;
-    uint64_t *ro = (uint64_t *)(h + a_off);
-    for (int b = 0; b <= S; ++b) ro[b] = raw_offsets[b] - raw_offsets[0];
-    memcpy(h + a_mode, mode.data(), (size_t)S * 4);
-    memcpy(h + a_mapof, map_of.data(), (size_t)S * 4);
-    if (odo_host) memcpy(h + a_odo, odo_host, (size_t)S * 24);
-  }
-  HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, a_bytes, st));
-  stats.h2d_bytes += a_bytes;
+  Regions A;
+  const size_t a_off = A.take(S1 * 8), a_mode = A.take((size_t)S * 4), a_mapof = A.take((size_t)S * 4),
+               a_odo = A.take(odo_host ? (size_t)S * 24 : 0);
+  SS_TRY(s->tab_a.reserve(ctx, A.end)); SS_TRY(s->d_tab_a.ensure(ctx, A.end));
+  unsigned char *h = s->tab_a.h.p;
+  uint64_t *ro = (uint64_t *)(h + a_off);
+  for (int b = 0; b <= S; ++b) ro[b] = raw_offsets[b] - raw_offsets[0];
+  memcpy(h + a_mode, mode.data(), (size_t)S * 4); memcpy(h + a_mapof, map_of.data(), (size_t)S * 4);
+  if (odo_host) memcpy(h + a_odo, odo_host, (size_t)S * 24);
+  HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, A.end, st));
+  stats.h2d_bytes += A.end;
   const unsigned long long *d_raw_off = (const unsigned long long *)(s->d_tab_a.p + a_off);
   const int *d_mode = (const int *)(s->d_tab_a.p + a_mode), *d_map_of = (const int *)(s->d_tab_a.p + a_mapof);
-  const double *d_odo = odo_host ? (const double *)(s->d_tab_a.p + a_odo) : odo_dev_in;
-  const double *d_raw = raw_dev_in ? (const double *)((const char *)raw_dev_in + (size_t)raw_offsets[0] * stride) : nullptr;
+  const double *d_odo = odo_host ? (const double *)(s->d_tab_a.p + a_odo) : odo_dev;
+  const double *d_raw = raw_dev ? (const double *)((const char *)raw_dev + (size_t)raw_offsets[0] * stride) : nullptr;
   if (raw_host && N) {
     SS_TRY(s->raw.ensure(ctx, N * stride));
     HIP_TRY(ctx, hipMemcpyAsync(s->raw.p, (const char *)raw_host + (size_t)raw_offsets[0] * stride, N * stride, hipMemcpyHostToDevice, st));
@@ -342,8 +348,7 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
                                   s->rs_off.p, s->rs_status.p, st));
     SS_TRY(ndt_prefilter_batch_dev(ctx, s->rs32.p, sizeof(float2), s->rs_off.p, S, cap_rs, P.leaf, s->src.p, s->src_off.p, st));
   } else {
-    HIP_TRY(ctx, hipMemsetAsync(s->rs_off.p, 0, S1 * 8, st));
-    HIP_TRY(ctx, hipMemsetAsync(s->src_off.p, 0, S1 * 8, st));
+    HIP_TRY(ctx, hipMemsetAsync(s->rs_off.p, 0, S1 * 8, st)); HIP_TRY(ctx, hipMemsetAsync(s->src_off.p, 0, S1 * 8, st));
     HIP_TRY(ctx, hipMemsetAsync(s->rs_status.p, 0, (size_t)S * 4, st));
   }
   SS_TRY(ndt_predict_batch_dev(ctx, d_odo, s->prev_odo.p, s->last_pose.p, S, s->motion.p, s->pred.p, s->init.p, st));
@@ -358,147 +363,136 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
   session_select_kernel<<<(S + 255) / 256, 256, 0, st>>>(d_mode, s->rs_status.p, d_odo, s->res.p, s->fused.p, s->cov.p, s->successful.p,
                                                          S, s->last_pose.p, s->last_cov.p, s->prev_odo.p, s->rec.p);
   HIP_TRY(ctx, hipGetLastError());
-  // ---- host wait 1: the resampled counts and the records ----
-  const size_t b_rs = 0, b_rec = up64(S1 * 8), back1 = b_rec + (size_t)S * sizeof(ndt_session_step);
-  const size_t b_toff = 0, b_coff = S1 * 8, b_plen = 2 * S1 * 8, b_stat = b_plen + (size_t)S * 8, back2 = b_stat + (size_t)S * 4;
-  SS_TRY(s->h_back.ensure(ctx, std::max(back1, back2)));
+  // host wait 1: the resampled counts and the records
+  Regions B;
+  const size_t b_rs = B.take(S1 * 8), b_rec = B.take((size_t)S * sizeof(ndt_session_step));
+  SS_TRY(s->h_back.ensure(ctx, B.end));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rs, s->rs_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rec, s->rec.p, (size_t)S * sizeof(ndt_session_step), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += S1 * 8 + (size_t)S * sizeof(ndt_session_step);
-  stats.host_waits++;
-  std::vector<uint64_t> rs_off(S1);
-  memcpy(rs_off.data(), s->h_back.p + b_rs, S1 * 8);
+  stats.d2h_bytes += S1 * 8 + (size_t)S * sizeof(ndt_session_step); stats.host_waits++;
+  rs_off.assign((const uint64_t *)(s->h_back.p + b_rs), (const uint64_t *)(s->h_back.p + b_rs) + S1);
   memcpy(out, s->h_back.p + b_rec, (size_t)S * sizeof(ndt_session_step));
+  return NDT_OK;
+}
 
-  // ---- the bookkeeping: addPose, the split, where the scan lands (PointCloudMap::addPose / addPoints) ----
-  const int cur = s->cur ^ 1;                      // this step's arenas; the last step's are s->cur
-  std::vector<SsCopy> moves;                       // carried-over scans and closed clouds
-  std::vector<float2 *> dst((size_t)S, nullptr);
-  std::vector<SsPlan> plan((size_t)S);
-  std::vector<PfPrev> prevs((size_t)S);
-  std::vector<MmJob> jobs; std::vector<MmSub> subs; std::vector<int> tri_of;
-  size_t nu = 0, cap_cloud = 0, total_prev = 0, tab_words = 0, list_pts = 0, tri_pts = 0, carry_cloud = 0, carry_target = 0;
-  const float cut = P.remove_moving ? rn_cutoff(P.thre_neighbor) : 0.f;
+// The bookkeeping of session i, which stepped with record out[i] and a new scan of n_new points: addPose, the split, where
+// the scan lands (PointCloudMap::addPose / addPoints) and Submap::makeMap's branches in their incremental form -- the
+// whole-submap form is submap_pieces (ndt_mi355x.hip).  Gives the session's row of table B (plan, dst, prevs), its moves and
+// its newest triple, if any.  The stores may move when they grow: every pointer is taken after the session's own growth,
+// and no other session touches them.
+int SsStep::book(int i, size_t n_new) {
+  SsSession &Q = s->ses[(size_t)i]; SsPlan &L = plan[(size_t)i];
+  stats.sessions_stepped++;
+  const double tx = out[i].pose[0], ty = out[i].pose[1];
+  if (Q.n_poses) Q.atd += std::sqrt((tx - Q.last_tx) * (tx - Q.last_tx) + (ty - Q.last_ty) * (ty - Q.last_ty));
+  else Q.atd = 0.0;
+  Q.n_poses++; Q.last_tx = tx; Q.last_ty = ty; Q.started = true;
+  if (Q.atd - Q.atdS >= P.sep_thre) {
+    // the current submap closes (src/PointCloudMap.cpp:72-90): its cloud becomes the filtered part of the last local map
+    const uint64_t n_tail = Q.has_target ? Q.t_n - Q.n_prev : 0;
+    SS_TRY(ss_grow(ctx, Q.closed, (size_t)(Q.closed_off.back() + n_tail), (size_t)Q.closed_off.back()));
+    if (n_tail) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off + Q.n_prev, Q.closed.p + Q.closed_off.back(), n_tail});
+    Q.closed_off.push_back(Q.closed_off.back() + n_tail);
+    Q.n_closed++;
+    Q.atdS = Q.atd; Q.first_submap = Q.n_poses - 1 == 0;
+    const size_t ns = Q.scan_off.size() - 1;
+    const int other = Q.cur ^ 1;
+    std::vector<uint64_t> noff{0};
+    if (ns >= 2) {
+      const uint64_t a = Q.scan_off[ns - 2], n2 = Q.scan_off[ns] - a;
+      SS_TRY(ss_grow(ctx, Q.store[other], (size_t)n2 + n_new, 0));
+      if (n2) moves.push_back(SsCopy{Q.store[Q.cur].p + a, Q.store[other].p, n2});
+      noff.push_back(Q.scan_off[ns - 1] - a); noff.push_back(n2);
+    }
+    Q.scan_off = noff; Q.cur = other;
+    L.reset = 1; Q.plen = 0;
+    out[i].split = 1;
+  }
+  out[i].submap = Q.n_closed;
+  SS_TRY(ss_grow(ctx, Q.store[Q.cur], (size_t)Q.scan_off.back() + n_new, (size_t)Q.scan_off.back()));
+  float2 *base = Q.store[Q.cur].p;
+  dst[(size_t)i] = base + Q.scan_off.back();
+  Q.scan_off.push_back(Q.scan_off.back() + n_new);
+  // Submap::makeMap's branches
+  const size_t n = Q.scan_off.size() - 1;
+  auto scan_p = [&](size_t k) { return base + Q.scan_off[k]; };
+  auto scan_n = [&](size_t k) { return (size_t)(Q.scan_off[k + 1] - Q.scan_off[k]); };
+  L.stepped = 1;
+  L.newest = scan_p(n - 1); L.newest_n = scan_n(n - 1);
+  size_t piece_room = 0;
+  if (P.remove_moving) {
+    L.with_newest = 1;
+    if (n == 1 && Q.first_submap) { L.piece = scan_p(0); L.piece_n = scan_n(0); piece_room = scan_n(0); }
+    else if (n >= 3 && scan_n(n - 2)) {      // the newest triple (an empty middle scan contributes nothing)
+      const size_t n0 = scan_n(n - 3), n1 = scan_n(n - 1), nb = scan_n(n - 2);
+      if (n0 > ((size_t)1 << 29) || n1 > ((size_t)1 << 29) || nb > ((size_t)1 << 29))
+        return fail(ctx, NDT_E_ARG, "ndt_sessions_step: session " + std::to_string(i) + ": a scan above 2^29 points");
+      L.tri = (int)tri.jobs.size();
+      tri.add((const float *)scan_p(n - 3), (const float *)scan_p(n - 1), (const float *)scan_p(n - 2), n0, n1, nb, P.resol, cut);
+      const size_t u0 = tri.unit_room;
+      tri.unit_room += (nb + kMmUnit - 1) / kMmUnit;
+      subs.push_back(MmSub{(unsigned)u0, (unsigned)tri.unit_room});      // (the triple's own submap: its units)
+      piece_room = nb;
+    }
+  } else {
+    L.with_newest = Q.first_submap || n - 1 >= 2;
+    if (n >= 2 && (Q.first_submap || n - 2 >= 2)) { L.piece = scan_p(n - 2); L.piece_n = scan_n(n - 2); piece_room = scan_n(n - 2); }
+  }
+  SS_TRY(ss_grow(ctx, Q.prefix, (size_t)Q.plen + piece_room, (size_t)Q.plen));
+  L.prefix = Q.prefix.p;
+  cap_cloud += (size_t)Q.plen + piece_room + (L.with_newest ? (size_t)L.newest_n : 0);
+  if (Q.n_closed >= 1) {
+    const uint64_t a = Q.closed_off[(size_t)Q.n_closed - 1], np = Q.closed_off[(size_t)Q.n_closed] - a;
+    prevs[(size_t)i] = PfPrev{np ? (const float *)(Q.closed.p + a) : nullptr, np};
+    total_prev += (size_t)np;
+  }
+  return NDT_OK;
+}
+
+// ---- the host bookkeeping: table B's rows, the moves and the newest triples of the sessions that stepped (book) ----
+int SsStep::bookkeeping() {
+  cur = s->cur ^ 1;
+  dst.assign((size_t)S, nullptr); prevs.assign((size_t)S, PfPrev{nullptr, 0ull});
+  plan.assign((size_t)S, SsPlan{nullptr, nullptr, 0ull, -1, 0, 0, 0, nullptr, 0ull});
+  tri.sa = tri.sb = sizeof(float2);
+  cut = P.remove_moving ? rn_cutoff(P.thre_neighbor) : 0.f;
   for (int i = 0; i < S; ++i) {
-    SsSession &Q = s->ses[(size_t)i];
-    SsPlan &L = plan[(size_t)i];
-    L = SsPlan{nullptr, nullptr, 0ull, -1, 0, 0, 0, nullptr, 0ull};
-    prevs[(size_t)i] = PfPrev{nullptr, 0ull};
+    const SsSession &Q = s->ses[(size_t)i];
     out[i].submap = Q.n_closed;
-    if (!out[i].stepped) {
-      if (Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
-      continue;
-    }
-    stats.sessions_stepped++;
-    const size_t n_new = (size_t)(rs_off[(size_t)i + 1] - rs_off[(size_t)i]);
-    const double tx = out[i].pose[0], ty = out[i].pose[1];
-    if (Q.n_poses) Q.atd += std::sqrt((tx - Q.last_tx) * (tx - Q.last_tx) + (ty - Q.last_ty) * (ty - Q.last_ty));
-    else Q.atd = 0.0;
-    Q.n_poses++; Q.last_tx = tx; Q.last_ty = ty; Q.started = true;
-    if (Q.atd - Q.atdS >= P.sep_thre) {
-      // the current submap closes (src/PointCloudMap.cpp:72-90): its cloud becomes the filtered part of the last local map
-      const uint64_t n_tail = Q.has_target ? Q.t_n - Q.n_prev : 0;
-      SS_TRY(ss_grow(ctx, Q.closed, (size_t)(Q.closed_off.back() + n_tail), (size_t)Q.closed_off.back()));
-      if (n_tail) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off + Q.n_prev, Q.closed.p + Q.closed_off.back(), n_tail});
-      Q.closed_off.push_back(Q.closed_off.back() + n_tail);
-      Q.n_closed++;
-      Q.atdS = Q.atd; Q.first_submap = Q.n_poses - 1 == 0;
-      const size_t ns = Q.scan_off.size() - 1;
-      const int other = Q.cur ^ 1;
-      std::vector<uint64_t> noff{0};
-      if (ns >= 2) {
-        const uint64_t a = Q.scan_off[ns - 2], n2 = Q.scan_off[ns] - a;
-        SS_TRY(ss_grow(ctx, Q.store[other], (size_t)n2 + n_new, 0));
-        if (n2) moves.push_back(SsCopy{Q.store[Q.cur].p + a, Q.store[other].p, n2});
-        noff.push_back(Q.scan_off[ns - 1] - a); noff.push_back(n2);
-      }
-      Q.scan_off = noff; Q.cur = other;
-      L.reset = 1; Q.plen = 0;
-      out[i].split = 1;
-    }
-    out[i].submap = Q.n_closed;
-    SS_TRY(ss_grow(ctx, Q.store[Q.cur], (size_t)Q.scan_off.back() + n_new, (size_t)Q.scan_off.back()));
-    float2 *base = Q.store[Q.cur].p;
-    dst[(size_t)i] = base + Q.scan_off.back();
-    Q.scan_off.push_back(Q.scan_off.back() + n_new);
-    // Submap::makeMap's branches
-    const size_t n = Q.scan_off.size() - 1;
-    auto scan_p = [&](size_t k) { return base + Q.scan_off[k]; };
-    auto scan_n = [&](size_t k) { return (size_t)(Q.scan_off[k + 1] - Q.scan_off[k]); };
-    L.stepped = 1;
-    L.newest = scan_p(n - 1); L.newest_n = scan_n(n - 1);
-    size_t piece_room = 0;
-    if (P.remove_moving) {
-      L.with_newest = 1;
-      if (n == 1 && Q.first_submap) { L.piece = scan_p(0); L.piece_n = scan_n(0); piece_room = scan_n(0); }
-      else if (n >= 3 && scan_n(n - 2)) {      // the newest triple (an empty middle scan contributes nothing)
-        const size_t n0 = scan_n(n - 3), n1 = scan_n(n - 1), nb = scan_n(n - 2);
-        if (n0 > ((size_t)1 << 29) || n1 > ((size_t)1 << 29) || nb > ((size_t)1 << 29))
-          return fail(ctx, NDT_E_ARG, "ndt_sessions_step: session " + std::to_string(i) + ": a scan above 2^29 points");
-        L.tri = (int)jobs.size();
-        MmJob J{};
-        J.a0 = (const float *)scan_p(n - 3); J.a1 = (const float *)scan_p(n - 1); J.b = (const float *)scan_p(n - 2);
-        J.n0 = (unsigned)n0; J.n1 = (unsigned)n1; J.nb = (unsigned)nb; J.sa = J.sb = (unsigned)sizeof(float2);
-        const size_t capw = pow2_at_least(2 * (n0 + n1) + 2);
-        J.tab_mask = (unsigned)(capw - 1);
-        J.tab = (unsigned long long *)tab_words; J.diff = (float2 *)list_pts;      // offsets for now, pointers below
-        J.res = P.resol; J.cut = cut;
-        jobs.push_back(J);
-        const unsigned u = (unsigned)((nb + kMmUnit - 1) / kMmUnit);
-        subs.push_back(MmSub{(unsigned)nu, (unsigned)nu + u});
-        tri_of.push_back(i);
-        nu += u; tab_words += capw; list_pts += nb; tri_pts += nb; piece_room = nb;
-      }
-    } else {
-      L.with_newest = Q.first_submap || n - 1 >= 2;
-      if (n >= 2 && (Q.first_submap || n - 2 >= 2)) { L.piece = scan_p(n - 2); L.piece_n = scan_n(n - 2); piece_room = scan_n(n - 2); }
-    }
-    SS_TRY(ss_grow(ctx, Q.prefix, (size_t)Q.plen + piece_room, (size_t)Q.plen));
-    L.prefix = Q.prefix.p;
-    cap_cloud += (size_t)Q.plen + piece_room + (L.with_newest ? (size_t)L.newest_n : 0);
-    if (Q.n_closed >= 1) {
-      const uint64_t a = Q.closed_off[(size_t)Q.n_closed - 1], np = Q.closed_off[(size_t)Q.n_closed] - a;
-      prevs[(size_t)i] = PfPrev{np ? (const float *)(Q.closed.p + a) : nullptr, np};
-      total_prev += (size_t)np;
-    }
+    if (out[i].stepped) SS_TRY(book(i, (size_t)(rs_off[(size_t)i + 1] - rs_off[(size_t)i])));
+    else if (Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
   }
-  stats.triples_run = (int)jobs.size();
-  const size_t T = jobs.size();
-  // the stores may have moved when they grew: the pointers above were taken after each session's own growth, and no later
-  // session touches them
+  stats.triples_run = (int)tri.jobs.size();
+  return NDT_OK;
+}
 
-  // ---- phase B: growMap's transform, the moves, the newest triples, the clouds, the targets ----
-  const size_t cap_target = cap_cloud + total_prev;
-  SS_TRY(s->cloud[cur].ensure(ctx, cap_cloud + carry_cloud + 64));
-  SS_TRY(s->target[cur].ensure(ctx, cap_target + carry_target + 64));
-  SS_TRY(s->tri_xy.ensure(ctx, tri_pts + 64));
-  // device scratch of the triples: [units][unit counts][unit offsets][keep bits][diff counts][voxel sets][diff lists]
-  const size_t m_ucnt = up64(nu * sizeof(MmUnit)), m_uoff = m_ucnt + up64(nu * 4), m_keep = m_uoff + up64(nu * 8),
-               m_cnt = m_keep + up64(nu * (kMmUnit / 64) * 8), m_tab = m_cnt + up64(T * 8 + 8), m_diff = m_tab + tab_words * 8;
-  SS_TRY(s->mm.ensure(ctx, m_diff + list_pts * 8 + 64));
+// ---- the part behind it: growMap's transform, the moves, the newest triples, the clouds, the targets, host wait 2 ----
+int SsStep::behind() {
+  const size_t S1 = (size_t)S + 1, nt = tri.jobs.size();
+  SS_TRY(s->cloud[cur].ensure(ctx, cap_cloud + carry_cloud + 64)); SS_TRY(s->tri_xy.ensure(ctx, tri.list_pts + 64));
+  SS_TRY(s->target[cur].ensure(ctx, cap_cloud + total_prev + carry_target + 64));
+  // device scratch of the triples: the units (made on the device), then the assembly chain's own
+  Regions M;
+  const size_t m_units = M.take(tri.unit_room * sizeof(MmUnit));
+  const MmScratch X(M, tri);
+  SS_TRY(s->mm.ensure(ctx, M.end));
   char *dm = (char *)s->mm.p;
-  for (size_t t = 0; t < T; ++t) {
-    jobs[t].tab = (unsigned long long *)(dm + m_tab) + (size_t)jobs[t].tab;
-    jobs[t].diff = (float2 *)(dm + m_diff) + (size_t)jobs[t].diff;
-    jobs[t].n_diff = (unsigned long long *)(dm + m_cnt) + t;
-  }
-  // table B, the same size at every step: dst | plan | prevs | jobs | subs | moves (3 per session at most)
-  const size_t o_dst = 0, o_plan = o_dst + up64((size_t)S * 8), o_prev = o_plan + up64((size_t)S * sizeof(SsPlan)),
-               o_jobs = o_prev + up64((size_t)S * sizeof(PfPrev)), o_subs = o_jobs + up64((size_t)S * sizeof(MmJob)),
-               o_moves = o_subs + up64((size_t)S * sizeof(MmSub)), o_seg = o_moves + up64(3 * (size_t)S * sizeof(SsCopy)),
-               b_bytes = o_seg, b_room = o_seg + 4 * (size_t)S * sizeof(SsCopy);
-  SS_TRY(s->tab_b.reserve(ctx, b_bytes));
-  SS_TRY(s->d_tab_b.ensure(ctx, b_room));
-  {
-    unsigned char *h = s->tab_b.h.p;
-    memset(h, 0, b_bytes);
-    memcpy(h + o_dst, dst.data(), (size_t)S * 8);
-    memcpy(h + o_plan, plan.data(), (size_t)S * sizeof(SsPlan));
-    memcpy(h + o_prev, prevs.data(), (size_t)S * sizeof(PfPrev));
-    if (T) { memcpy(h + o_jobs, jobs.data(), T * sizeof(MmJob)); memcpy(h + o_subs, subs.data(), T * sizeof(MmSub)); }
-    if (!moves.empty()) memcpy(h + o_moves, moves.data(), moves.size() * sizeof(SsCopy));
-  }
+  mm_bind(tri.jobs.data(), nt, dm, X);
+  // table B, the same size at every step: dst | plan | prevs | jobs | subs | moves (3 per session at most); the segments
+  // of session_plan_kernel lie behind it on the device
+  Regions B;
+  const size_t o_dst = B.take((size_t)S * 8), o_plan = B.take((size_t)S * sizeof(SsPlan)), o_prev = B.take((size_t)S * sizeof(PfPrev)),
+               o_jobs = B.take((size_t)S * sizeof(MmJob)), o_subs = B.take((size_t)S * sizeof(MmSub)),
+               o_moves = B.take(3 * (size_t)S * sizeof(SsCopy)), o_seg = B.take(4 * (size_t)S * sizeof(SsCopy)), b_bytes = o_seg;
+  SS_TRY(s->tab_b.reserve(ctx, b_bytes)); SS_TRY(s->d_tab_b.ensure(ctx, B.end));
+  unsigned char *h = s->tab_b.h.p;
+  memset(h, 0, b_bytes);
+  memcpy(h + o_dst, dst.data(), (size_t)S * 8);
+  memcpy(h + o_plan, plan.data(), (size_t)S * sizeof(SsPlan));
+  memcpy(h + o_prev, prevs.data(), (size_t)S * sizeof(PfPrev));
+  if (nt) { memcpy(h + o_jobs, tri.jobs.data(), nt * sizeof(MmJob)); memcpy(h + o_subs, subs.data(), nt * sizeof(MmSub)); }
+  if (!moves.empty()) memcpy(h + o_moves, moves.data(), moves.size() * sizeof(SsCopy));
   HIP_TRY(ctx, s->tab_b.upload(s->d_tab_b.p, 0, b_bytes, st));
   stats.h2d_bytes += b_bytes;
   unsigned char *db = s->d_tab_b.p;
@@ -508,21 +502,12 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
         s->rs64.p, sizeof(double2), (const unsigned long long *)s->rs_off.p, S, s->last_pose.p, (float2 *const *)(db + o_dst));
   if (!moves.empty())
     seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(moves.size(), 65535)), 256, 0, st>>>((const SsCopy *)(db + o_moves), (int)moves.size());
-  if (T) {
-    const MmJob *d_jobs = (const MmJob *)(db + o_jobs);
-    const MmSub *d_subs = (const MmSub *)(db + o_subs);
-    MmUnit *units = (MmUnit *)dm;
-    unsigned *ucnt = (unsigned *)(dm + m_ucnt);
-    unsigned long long *uoff = (unsigned long long *)(dm + m_uoff), *keep = (unsigned long long *)(dm + m_keep);
-    SS_TRY(s->tri_off.ensure(ctx, T + 1)); SS_TRY(s->tri_status.ensure(ctx, T));
-    HIP_TRY(ctx, hipMemsetAsync(dm + m_tab, 0xff, tab_words * 8, st));
-    session_units_kernel<<<(unsigned)T, 256, 0, st>>>(d_jobs, d_subs, units);
-    make_map_diff_kernel<true><<<(unsigned)T, kMmBlock, 0, st>>>(d_jobs, 0.0);
-    make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(d_jobs, units, 0.f, keep, ucnt);
-    make_map_sub_offsets_kernel<<<(unsigned)T, 1024, 0, st>>>(ucnt, d_subs, uoff, (unsigned long long *)s->tri_off.p, s->tri_status.p);
-    make_map_sub_scan_kernel<<<1, 1024, 0, st>>>((unsigned long long *)s->tri_off.p, (int)T);
-    make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, s->tri_xy.p,
-                                                                (const unsigned long long *)s->tri_off.p, s->tri_status.p);
+  if (nt) {
+    const MmJob *d_jobs = (const MmJob *)(db + o_jobs); const MmSub *d_subs = (const MmSub *)(db + o_subs);
+    SS_TRY(s->tri_off.ensure(ctx, nt + 1)); SS_TRY(s->tri_status.ensure(ctx, nt));
+    session_units_kernel<<<(unsigned)nt, 256, 0, st>>>(d_jobs, d_subs, (MmUnit *)(dm + m_units));
+    SS_TRY(mm_queue_batch(ctx, d_jobs, (const MmUnit *)(dm + m_units), d_subs, dm, X, nt, s->tri_xy.p,
+                          (unsigned long long *)s->tri_off.p, s->tri_status.p, st));
   }
   session_plan_kernel<<<1, 1024, 0, st>>>((const SsPlan *)(db + o_plan), S, s->tri_xy.p, (const unsigned long long *)s->tri_off.p,
                                           s->tri_status.p, s->plen.p, s->cloud[cur].p, (unsigned long long *)s->cloud_off.p,
@@ -537,14 +522,21 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
                         s->status.p, st));
     SS_TRY(scope.close());
   }
-  // ---- host wait 2: the target and cloud offsets, the prefix lengths, the status ----
+  // host wait 2: the target and cloud offsets, the prefix lengths, the status
+  Regions R;
+  b_toff = R.take(S1 * 8); b_coff = R.take(S1 * 8); b_plen = R.take((size_t)S * 8); b_stat = R.take((size_t)S * 4);
+  SS_TRY(s->h_back.ensure(ctx, R.end));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->target_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_coff, s->cloud_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_plen, s->plen.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->status.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += 2 * S1 * 8 + (size_t)S * 12;
-  stats.host_waits++;
+  stats.d2h_bytes += 2 * S1 * 8 + (size_t)S * 12; stats.host_waits++;
+  return NDT_OK;
+}
+
+// ---- the close: the new views, the carried ranges (table C), the NDT maps of the new local maps (host wait 3) ----
+int SsStep::close() {
   const uint64_t *toff = (const uint64_t *)(s->h_back.p + b_toff), *coff = (const uint64_t *)(s->h_back.p + b_coff),
                  *pl = (const uint64_t *)(s->h_back.p + b_plen);
   const int *stt = (const int *)(s->h_back.p + b_stat);
@@ -575,8 +567,7 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
   }
   // table C, the same size at every step: two carried ranges per session at most
   const size_t c_bytes = 2 * (size_t)S * sizeof(SsCopy);
-  SS_TRY(s->tab_c.reserve(ctx, c_bytes));
-  SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
+  SS_TRY(s->tab_c.reserve(ctx, c_bytes)); SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
   memset(s->tab_c.h.p, 0, c_bytes);
   if (!carry.empty()) memcpy(s->tab_c.h.p, carry.data(), carry.size() * sizeof(SsCopy));
   HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
@@ -585,19 +576,30 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev_in, s
     seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(carry.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)carry.size());
   HIP_TRY(ctx, hipGetLastError());
   s->cur = cur;
-  // ---- the NDT maps of the new local maps (host wait 3: the bounding boxes) ----
+  // the NDT maps of the new local maps (host wait 3: the bounding boxes)
   if (!bxy.empty()) {
-    std::vector<ndt_params> bp(bxy.size(), P.match);
+    std::vector<ndt_params> bp(bxy.size(), s->prm.match);
     const int rc = ndt_map_build_batch_dev(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data());
     for (size_t k = 0; k < bwho.size(); ++k) s->ses[(size_t)bwho[k]].map = rc == NDT_OK ? bmaps[k] : s->ses[(size_t)bwho[k]].map;
     if (rc) return rc;
   } else {
     HIP_TRY(ctx, hipStreamSynchronize(st));
   }
-  stats.host_waits++;
-  stats.d2h_bytes += bxy.size() * 16 * sizeof(unsigned);
+  stats.host_waits++; stats.d2h_bytes += bxy.size() * 16 * sizeof(unsigned);
   s->stats = stats;
   return NDT_OK;
+}
+
+// The step: DESIGN.md 4.10's list.  Every return with a HIP error leaves the set dead (the caller marks it).
+int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev, size_t stride, const uint64_t *raw_offsets,
+            const double *odo_host, const double *odo_dev, const unsigned char *active, ndt_session_step *out) {
+  HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
+  SsStep T{s, raw_host, raw_dev, stride, raw_offsets, odo_host, odo_dev, active, out};
+  if (!T.who_steps()) return NDT_OK;
+  SS_TRY(T.front());
+  SS_TRY(T.bookkeeping());
+  SS_TRY(T.behind());
+  return T.close();
 }
 
 #undef SS_TRY
