@@ -347,9 +347,7 @@ __device__ __forceinline__ float nearest_sq(const MapView &M, float qx, float qy
 // order the passes read the scan: the cell-ordered copy, so that the lanes of a wave share buckets), then per match
 // the sum in the unit order of the passes (lane -> wave butterfly -> units 0..63).
 // ------------------------------------------------------------------------------------------
-#ifndef NDT_FIT_OCC
-#define NDT_FIT_OCC 6
-#endif
+constexpr int kFitOcc = 6;       // workgroups per CU the search kernel is built for (4 .. 8 waves per SIMD measure the same)
 // DEFER (launches whose matches share one scan: hypothesis scoring, configs[4]): the queries that need phase 3 are not
 // finished here but put on their match's list -- those with a point in hand from the front, those without from the back --
 // and fitness_far_kernel finishes them, 64 queries of ONE kind per wave.  With phase 3 inline a wave walks the rings of its
@@ -407,7 +405,7 @@ __device__ __forceinline__ int fit_map_index(const int *__restrict__ map_of, int
 }
 
 template <bool SSE, bool DEFER, bool MULTI = false>
-__global__ void __launch_bounds__(256, NDT_FIT_OCC)
+__global__ void __launch_bounds__(256, kFitOcc)
 fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
                       int shared_scan, const float2 *__restrict__ sorted, const ndt_result *__restrict__ results,
                       float *__restrict__ fit, unsigned *__restrict__ far_idx, unsigned *__restrict__ far_n, int gx,
@@ -474,11 +472,9 @@ fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsi
 
 // Phase 3 of the queries fitness_points_kernel<.., true> has listed: per match the queries with a point in hand, then
 // the ones without (far_n[2b], far_n[2b + 1] of them, from the front / the back of the match's slice of far_idx).
-#ifndef NDT_FAR_OCC
-#define NDT_FAR_OCC 5
-#endif
+constexpr int kFarOcc = 5;       // workgroups per CU the far kernel is built for (4 / 5 / 6 level, 8 slower)
 template <bool SSE, bool MULTI = false>
-__global__ void __launch_bounds__(256, NDT_FAR_OCC)
+__global__ void __launch_bounds__(256, kFarOcc)
 fitness_far_kernel(MapView M_arg, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
                    int shared_scan, const float2 *__restrict__ sorted, const ndt_result *__restrict__ results,
                    float *__restrict__ fit, const unsigned *__restrict__ far_idx, const unsigned *__restrict__ far_n, int gx,

@@ -27,69 +27,56 @@
 // ------------------------------------------------------------------------------------------
 constexpr int kBlock = 1024;
 constexpr int kWaves = kBlock / 64;
-#ifndef NDT_KSUB
-#define NDT_KSUB 4
-#endif
-constexpr int kSub = NDT_KSUB;               // a lane's points are cut into kSub runs -> kSub units per wave
+constexpr int kSub = 4;                      // a lane's points are cut into kSub runs -> kSub units per wave
 constexpr int kUnits = kWaves * kSub;        // units per pass
-#ifndef NDT_MAX_HELPERS_BUILD
-#define NDT_MAX_HELPERS_BUILD 15
-#endif
-constexpr int kMaxHelpers = NDT_MAX_HELPERS_BUILD;   // helper workgroups per scan, hard limit (64 units: 4 each)
+constexpr int kMaxHelpers = 15;              // helper workgroups per scan, hard limit (64 units: 4 each)
 // Default (NDT_OPT_MAX_HELPERS): beyond three helpers a pass hardly gets shorter (one unit on one wave takes 7.5 us),
 // and a workgroup that finds every unfinished scan at its limit leaves -- its CU goes to whatever is queued behind
 // the launch (in the bench: the map build of the next step).  8 against 15: same kernel time, 1.6 % more matches/s.
 constexpr int kDefaultHelpers = 8;
 constexpr int kBatchHelpers = 2;           // launches with a scan for every workgroup (ndt_mi355x.hip: launch_align)
-#ifndef NDT_IDLE_MAX
-#define NDT_IDLE_MAX 800           // idle helper back-off: 4 us doubling up to 8 us (100 MHz ticks)
-#endif
-#ifndef NDT_XCD_BONUS
-#define NDT_XCD_BONUS 6          // passes' worth of preference for scans owned on the helper's own XCD (0: off)
-#endif
-#ifndef NDT_NEED_SLOPE
-#define NDT_NEED_SLOPE 10       // passes still to run per unit of (1 - score per point / best score per point of a finished scan)
-#endif
-#ifndef NDT_HELPER_PENALTY
-#define NDT_HELPER_PENALTY 12    // passes a scan must be ahead by before it gets one more helper than another
-#endif
-#ifndef NDT_BASE_HELPERS
-#define NDT_BASE_HELPERS 7
-#endif
-#ifndef NDT_POLL2
-#define NDT_POLL2 0      // owner: two polls of a unit-total word in flight
-#endif
-#ifndef NDT_POLL2H
-#define NDT_POLL2H 0     // helper: two polls of the epoch line in flight
-#endif
-#ifndef NDT_OWNER_LEAD
-#define NDT_OWNER_LEAD 0
-#endif
-constexpr int kOwnerLead = NDT_OWNER_LEAD;   // units of a shared pass the owner computes on top of its round-robin share
+constexpr unsigned long long kIdleMax = 800; // idle helper back-off: 4 us doubling up to 8 us (100 MHz ticks)
+constexpr int kXcdBonus = 6;                 // passes' worth of preference for scans owned on the helper's own XCD (0: off)
+constexpr int kNeedSlope = 10;               // passes still to run per unit of (1 - score per point / best score per point of a finished scan)
+constexpr int kHelperPenalty = 12;           // passes a scan must be ahead by before it gets one more helper than another
+constexpr int kOwnerLead = 0;                // units of a shared pass the owner computes on top of its round-robin share
                                              // (the helpers' share reaches it a hand-off latency after its own)
-constexpr int kBaseHelpers = NDT_BASE_HELPERS;              // ... while more scans are unfinished than workgroups / 8
+constexpr int kBaseHelpers = 7;              // ... while more scans are unfinished than workgroups / 8
 constexpr unsigned kEpochDone = 0xFFFFFFFFu;
-#ifndef NDT_FIRST_PASS_WAIT
-#define NDT_FIRST_PASS_WAIT 2500
-#endif
-constexpr unsigned long long kFirstPassWait = NDT_FIRST_PASS_WAIT;   // ticks of the 100 MHz wall clock (25 us)
+constexpr unsigned long long kTicketOpen = 1ull << 32;                            // epoch 1: open for joining, nothing to compute (h = 0)
+constexpr unsigned long long kTicketDone = (unsigned long long)kEpochDone << 32;
+constexpr unsigned long long kFirstPassWait = 2500;   // ticks of the 100 MHz wall clock (25 us)
 constexpr unsigned long long kWatchTicks = 400000000ull;   // ~4 s of the 100 MHz wall clock
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-// Phase timers of the match kernel exist only in diagnostic builds (-DNDT_DIAG): a dozen 64-bit running sums live
-// across every loop of the kernel cost registers the pass loop needs.
+// Phase timers exist only in diagnostic builds (-DNDT_DIAG): a dozen 64-bit sums live across the kernel's loops cost registers the pass loop needs.
 #ifdef NDT_DIAG
 constexpr bool kProf = true;
 #else
 constexpr bool kProf = false;
 #endif
-// diagnostic builds: thread 0 of the owner stamps the setup phases of a scan (ticks since the scan was taken)
-// diagnostic builds: timeline of the first kProfPasses shared passes of every scan, 16 words each (absolute ticks):
-// opened, owner's units done, collected, helpers counted in, then (seen, done) of the helpers of rank 0..5
+// The profile buffer of a diagnostic launch of B scans, in 64-bit words -- written by the kernel's kProf code, read by
+// prof_report, dumped as it is for tools/prof_phases.py (NDT_PROF_DUMP).  Four areas, one after the other:
+//   per-scan sums   [B][8]   the ProfScan words
+//   shared passes   [B][8]   the ProfShared words: sums over a scan's shared passes, then its set-up phases (packed)
+//   set-up stamps   [B][16]  thread 0 of the owner stamps the set-up phases of a scan (NDT_STAMP: ticks since the scan was taken)
+//   pass timelines  [B][kProfPasses][16]  the first kProfPasses shared passes of every scan, the ProfPass words (absolute ticks)
 constexpr int kProfPasses = 24;
 constexpr int kProfTimeline = kProfPasses * 16;
+constexpr int kProfRanks = 6;                // helpers (by rank) that stamp a timeline
+enum ProfScan { kPsEval, kPsAdv /* | fitness ticks << 32 | window spilled << 63 */, kPsStart /* first shared pass << 32 | scan taken */,
+                kPsCounts /* passes | shared << 16 | helper units << 32 */, kPsAttached, kPsHelperReady, kPsWait, kPsTotal };
+enum ProfShared { kPhCount, kPhPro, kPhOwn, kPhWait, kPhComb, kPhAdv, kPhSetupA /* region, or the whole ordering << 32 | sort */,
+                  kPhSetupB /* window staged << 32 | the plan's first two phases, 16 bits each */ };
+enum ProfPass { kPpOpened, kPpOwnDone, kPpCollected, kPpHelpers };     // then (seen, done) of the helpers of rank 0 .. kProfRanks - 1:
+__host__ __device__ constexpr int prof_pass_helper(int rank, bool done) { return 4 + 2 * rank + (done ? 1 : 0); }
+__host__ __device__ constexpr size_t prof_scan_at(int b) { return 8 * (size_t)b; }
+__host__ __device__ constexpr size_t prof_shared_at(int B, int b) { return 8 * (size_t)B + 8 * (size_t)b; }
+__host__ __device__ constexpr size_t prof_stamps_at(int B, int b) { return 16 * (size_t)B + 16 * (size_t)b; }
+__host__ __device__ constexpr size_t prof_pass_at(int B, int b, unsigned e) { return 32 * (size_t)B + ((size_t)b * kProfPasses + e) * 16; }
+__host__ __device__ constexpr size_t prof_scan_bytes() { return 256 + kProfTimeline * 8; }   // all four areas, per scan
 #define NDT_STAMP(st_, t0_, k_) do { if (kProf && (st_) && threadIdx.x == 0) (st_)[k_] = wall_clock64() - (t0_); } while (0)
 
 // Per-scan control block: two 128-byte lines, so that the words polled by the helpers (line 0, written by the owner
@@ -110,6 +97,11 @@ constexpr int kProfTimeline = kProfPasses * 16;
 // ubeg + k + j*(h+1).  The assignment is static (no claim atomics: a same-address agent-scope
 // read-modify-write costs ~0.1 us and 128 waves used to queue on it every pass); it is safe because a
 // helper only counts once it has registered in `ready`, after which it does nothing but poll line 0.
+__device__ __forceinline__ u64 ticket_of(unsigned epoch, int h, int uend, int ubeg) { return ((u64)epoch << 32) | ((u64)h << 16) | ((u64)uend << 8) | (u64)ubeg; }
+__device__ __forceinline__ u32 ticket_epoch(u64 w) { return (u32)(w >> 32); }
+__device__ __forceinline__ int ticket_helpers(u64 w) { return (int)((w >> 16) & 0xFFu); }
+__device__ __forceinline__ int ticket_uend(u64 w) { return (int)((w >> 8) & 0xFFu); }
+__device__ __forceinline__ int ticket_ubeg(u64 w) { return (int)(w & 0xFFu); }
 constexpr int kPoseWords = 12;               // Tf32 (4 x float32) + cj, sj, ch, sh (4 x fp64) as 32-bit halves
 constexpr int kUnitWords = 24;               // 12 fp64 sums of a unit as 32-bit halves
 struct alignas(128) ScanCtl {
@@ -130,6 +122,16 @@ static_assert(sizeof(ScanCtl) == 256, "ScanCtl is two 128-byte lines");
 
 struct WsHeader { u32 done; u32 abort; u32 next; u32 best_spp; u32 pad[28]; };   // next: scans handed out beyond the first gridDim.x; best_spp: float bits, best score per point of a finished scan
 static_assert(sizeof(WsHeader) == 128, "WsHeader");
+
+// The workspace of a launch of B scans, in bytes:
+//   WsHeader | ScanCtl[B] | unit totals [B][kUnits][kUnitWords] u64 | marked-cell bitmaps [B][kBitmapWords] | (multi-map) MapView[n_maps]
+// Everything in front of the bitmaps is zero at kernel start (see ScanCtl); the view table starts on a 256-byte boundary.
+constexpr int kBitmapWords = kRegionCells / 32; constexpr size_t kBitmapBytes = (size_t)kBitmapWords * 4;   // a scan's marked-cell bitmap, a bit per window cell
+__host__ __device__ constexpr size_t ws_ctl_off() { return sizeof(WsHeader); }
+__host__ __device__ constexpr size_t ws_utot_off(size_t B) { return ws_ctl_off() + B * sizeof(ScanCtl); }
+__host__ __device__ constexpr size_t ws_bitmap_off(size_t B) { return ws_utot_off(B) + B * kUnits * kUnitWords * sizeof(u64); }   // = the zeroed part
+__host__ __device__ constexpr size_t ws_views_off(size_t B) { return (ws_bitmap_off(B) + B * kBitmapBytes + 255) & ~(size_t)255; }
+__host__ __device__ constexpr size_t ws_bytes(size_t B, size_t n_maps) { return n_maps ? ws_views_off(B) + n_maps * sizeof(MapView) : ws_bitmap_off(B) + B * kBitmapBytes; }
 
 #define NDT_RLX __ATOMIC_RELAXED
 #define NDT_AGENT __HIP_MEMORY_SCOPE_AGENT
@@ -160,6 +162,13 @@ __device__ __forceinline__ void sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// the same for one wave: what its lanes wrote to LDS is visible to its other lanes
+__device__ __forceinline__ void sync_wave() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ __forceinline__ int wave_min_i(int v) {
@@ -204,8 +213,8 @@ struct Lds {
   double etab[64];
 };
 
-// The match kernel's LDS lives at namespace scope so that the routines around the kernel body (pass_units, which can be
-// built as a function of its own) can reach it by name: the window pool (slot table + voxel records of one scan) and the control / scratch block.
+// The match kernel's LDS lives at namespace scope so that the routines around the kernel body (pass_units) can reach it
+// by name: the window pool (slot table + voxel records of one scan) and the control / scratch block.
 __shared__ Lds g_L;
 __shared__ uint4 g_pool[kPoolBytes / 16];
 
@@ -507,7 +516,7 @@ __device__ __noinline__ bool sort_points(const MapView &M, const Tf32 &T0, const
   unsigned *hist = reinterpret_cast<unsigned *>(pool);                 // ncell + 1 counters (last: outside the window)
   unsigned *idx = hist + ((ncell + 1 + 3) & ~3);
   for (int i = threadIdx.x; i <= ncell; i += kBlock) hist[i] = 0u;
-  for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) wmap[i] = 0u;
+  for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) wmap[i] = 0u;
   __syncthreads();
   auto key_of = [&](float2 pt) {
     float xt, yt;
@@ -621,11 +630,8 @@ __device__ __noinline__ bool sort_points(const MapView &M, const Tf32 &T0, const
 // poll for their turn: 6 us).  Results differ from rounds 3-4 in the last bits of the sums (other order inside the cells), not
 // in the float32 transforms or the iteration counts (every parity test, all configurations).
 // The barriers of these phases order LDS traffic only (sync_lds): the ordered copy's stores to memory drain behind them.
-#ifndef NDT_ORDER_INLINE
-#define NDT_ORDER_INLINE __noinline__
-#endif
 template <bool SSE, int PER>
-__device__ NDT_ORDER_INLINE void order_scan_regs(const MapView &M, const OptParams &P, const double *__restrict__ init,
+__device__ __noinline__ void order_scan_regs(const MapView &M, const OptParams &P, const double *__restrict__ init,
                                              const float2 *__restrict__ scan, int n, Lds &L, uint4 *pool,
                                              float2 *__restrict__ sp, u64 *stamps = nullptr, u64 t0s = 0,
                                              ScanCtl *open_ctl = nullptr, unsigned *open_map = nullptr) {
@@ -654,7 +660,7 @@ __device__ NDT_ORDER_INLINE void order_scan_regs(const MapView &M, const OptPara
     const int i = (int)threadIdx.x + k * kBlock;
     if (i < kHistWords / 4) pool[i] = make_uint4(0u, 0u, 0u, 0u);
   }
-  if (threadIdx.x < kRegionCells / 32) wmap[threadIdx.x] = 0u;
+  if (threadIdx.x < kBitmapWords) wmap[threadIdx.x] = 0u;
   if (threadIdx.x == 64) {
     L.sbox[0] = INT_MAX; L.sbox[1] = INT_MAX; L.sbox[2] = INT_MIN; L.sbox[3] = INT_MIN;
     L.sflag[0] = 0;                                                    // raised when the scatter's order has to be repaired
@@ -745,7 +751,7 @@ __device__ NDT_ORDER_INLINE void order_scan_regs(const MapView &M, const OptPara
   // 8 us behind it (the ordered copy is only read once a pass has been opened, behind this workgroup's own staging, whose
   // last barrier drains the copy's stores).  Everything stored write-through and drained before the ticket, as in the kernel.
   if (open_ctl) {
-    for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) st32(&open_map[i], wmap[i]);
+    for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) st32(&open_map[i], wmap[i]);
     if (threadIdx.x == 0) {
       const Region r = L.RG;
       st32((u32 *)&open_ctl->region[0], (u32)r.x0); st32((u32 *)&open_ctl->region[1], (u32)r.y0); st32((u32 *)&open_ctl->region[2], (u32)r.rw);
@@ -754,7 +760,7 @@ __device__ NDT_ORDER_INLINE void order_scan_regs(const MapView &M, const OptPara
     }
     drain_vmem();
     __syncthreads();
-    if (threadIdx.x == 0) st64(&open_ctl->ticket, (u64)1 << 32);       // epoch 1: open for joining, nothing to compute yet
+    if (threadIdx.x == 0) st64(&open_ctl->ticket, kTicketOpen);
   }
   // Places: the waves in turn (see the head of the routine).
   unsigned place[PER];
@@ -933,25 +939,19 @@ __device__ __forceinline__ const T *uniform_p(const T *p) {
   return (const T *)(((u64)uniform_u((unsigned)(b >> 32)) << 32) | uniform_u((unsigned)b));
 }
 
-// The pass loop needs the register file to itself.  In round 1's kernel -- everything inlined into one persistent
-// body, with a dozen 64-bit diagnostic timers alive across every loop -- it inherited what the kernel keeps alive around
-// it and the compiler spilled inside the point loop (a dozen scratch reloads per point, each behind an
-// s_waitcnt vmcnt(0)).  Two things fixed that: the phases AROUND the loop became functions of their own
-// (compute_region, sort_points, fill_window, advance: their registers no longer overlap the loop's), and the loop takes
-// its inputs from LDS (g_L.M, g_L.RG, g_L.PP, g_L.pts), moved to SGPRs once per call, instead of from values that would
-// have to stay live across the whole kernel.  For a while this routine was a function too (-DNDT_PASS_INLINE=__noinline__
-// still builds that): same speed, but every call saved and restored 18 VGPRs per lane through scratch -- 300 MB of
-// write traffic per launch -- so it is inlined again, spill-free now (the kernel's 67 spilled VGPRs are in cold code).
-#ifndef NDT_PASS_INLINE
-#define NDT_PASS_INLINE __forceinline__
-#endif
+// The pass loop needs the register file to itself: the phases AROUND it are functions of their own (compute_region,
+// sort_points, fill_window, advance: their registers do not overlap the loop's), and the loop takes its inputs from LDS
+// (g_L.M, g_L.RG, g_L.PP, g_L.pts), moved to SGPRs once per call, instead of from values that would have to stay live across
+// the whole kernel.  The routine itself is inlined: as a function every call saved and restored 18 VGPRs per lane through
+// scratch (300 MB of write traffic per launch, same speed); inlined it is spill-free (the kernel's 67 spilled VGPRs are in
+// cold code).
 // Two ways of being used (once per wave and pass):
 //   step == 0: solo pass -- wave `first` walks its own kSub units (first, 0..kSub-1) in one go, totals to L.wpart;
 //   step  > 0: shared pass -- the wave takes units (j from the workgroup's LDS counter) 0 .. lead-1, then
 //              first + (j - lead) * step until they reach uend; totals to L.wpart (owner, vtot == nullptr) or, tagged,
 //              straight to the scan's unit totals in HBM (helper; lead = 0).
 template <bool SSE, bool INCL, bool CHK>
-__device__ NDT_PASS_INLINE void pass_units(int first_in, int step_in, int uend_in, u64 *vtot_in, unsigned tag_in, int lead_in) {
+__device__ __forceinline__ void pass_units(int first_in, int step_in, int uend_in, u64 *vtot_in, unsigned tag_in, int lead_in) {
   const int first = (int)uniform_u((unsigned)first_in), step = (int)uniform_u((unsigned)step_in);
   const int uend = (int)uniform_u((unsigned)uend_in), lead = (int)uniform_u((unsigned)lead_in);
   const u64 tag = (u64)uniform_u(tag_in) << 32;
@@ -980,15 +980,10 @@ __device__ NDT_PASS_INLINE void pass_units(int first_in, int step_in, int uend_i
   pp.cj = uniform_d(pp_in.cj); pp.sj = uniform_d(pp_in.sj); pp.ch = uniform_d(pp_in.ch); pp.sh = uniform_d(pp_in.sh);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, last = n - 1;
   const int per_lane = (n + kBlock - 1) / kBlock;          // points of the longest lane
-#ifdef NDT_RUNS_CEIL
-  const int run = (per_lane + kSub - 1) / kSub;              // runs of equal length, the last one short (10 rounds: 3 3 3 1)
-  auto kstart = [&](int q) { return min(per_lane, q * run); };
-#else
   // runs as equal as they get (10 rounds: 3 3 2 2): in a pass shared by two workgroups every wave then walks a long and
   // a short unit -- five rounds -- instead of half the waves two long ones (round 3)
   const int rbase = per_lane / kSub, rextra = per_lane % kSub;
   auto kstart = [&](int q) { return q * rbase + min(q, rextra); };
-#endif
   for (int it = 0; it <= kUnits; ++it) {                   // counted (tools/repro/ticket2.hip)
     int w, q0, q1, dst_stride;
     double *dst;
@@ -1041,6 +1036,14 @@ __device__ NDT_PASS_INLINE void pass_units(int first_in, int step_in, int uend_i
   }
 }
 
+// thread 0: the next scan of the queue behind the first gridDim.x (>= B: the queue is used up)
+__device__ __forceinline__ int next_in_queue(WsHeader *hdr) { return (int)gridDim.x + (int)__hip_atomic_fetch_add(&hdr->next, 1u, NDT_RLX, NDT_AGENT); }
+// a scan belongs to the workgroup that wins this compare-and-swap (see "Claims" in the kernel)
+__device__ __forceinline__ bool try_claim(ScanCtl *C) {
+  u32 expect = 0u;
+  return __hip_atomic_compare_exchange_strong(&C->claimed, &expect, 1u, NDT_RLX, NDT_RLX, NDT_AGENT);
+}
+
 // Bound on every spin, measured from the start of that spin (a launch may legitimately run longer
 // than any bound); looked at once per 64 polls (the abort word is one line shared by the chip).
 __device__ __forceinline__ bool watchdog(WsHeader *hdr, u64 spin_start, unsigned &polls) {
@@ -1076,7 +1079,7 @@ template <bool SSE>
 __global__ void __launch_bounds__(kBlock)
 ndt_order_kernel(MapView M, OptParams P, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets,
                  int B, int shared_scan, const double *__restrict__ inits, float2 *__restrict__ sorted,
-                 PrepRec *__restrict__ prep, unsigned *__restrict__ prep_map /* [B][kRegionCells / 32] */) {
+                 PrepRec *__restrict__ prep, unsigned *__restrict__ prep_map /* [B][kBitmapWords] */) {
   Lds &L = g_L;
   uint4 *const pool = g_pool;
   if (threadIdx.x == 64) { L.M = M; L.P = P; }
@@ -1104,8 +1107,8 @@ ndt_order_kernel(MapView M, OptParams P, const float *__restrict__ scans, const 
       u32 *dst = reinterpret_cast<u32 *>(&R->S);
       if (threadIdx.x < sizeof(AlignState) / 4) dst[threadIdx.x] = src[threadIdx.x];
       const unsigned *wmap = reinterpret_cast<const unsigned *>(L.wpart);
-      unsigned *gm = prep_map + (size_t)b * (kRegionCells / 32);
-      for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) gm[i] = wmap[i];
+      unsigned *gm = prep_map + (size_t)b * kBitmapWords;
+      for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) gm[i] = wmap[i];
     }
     __syncthreads();
   }
@@ -1125,6 +1128,90 @@ __device__ __forceinline__ void load_view(Lds &L, const MapView *__restrict__ vi
   if (t < sizeof(MapView) / 4) reinterpret_cast<u32 *>(&L.M)[t] = reinterpret_cast<const u32 *>(views + mi)[t];
 }
 
+// The parts of the kernel body below that are arithmetic and stores through a pointer used once.  (What polls, takes a
+// barrier or modifies memory through a pointer parameter stays in the body: as a function it reschedules the kernel, LOG R17.1.)
+
+// window geometry as PrepRec and ScanCtl hold it: x0, y0, rw, rh, cap (, nspill)
+__device__ __forceinline__ Region region_of(const int *w, int nspill) { Region r; r.x0 = w[0]; r.y0 = w[1]; r.rw = w[2]; r.rh = w[3]; r.cap = w[4]; r.nspill = nspill; return r; }
+
+// owner, thread 0: open epoch `tag` for h helpers -- the pose halves and the epoch word, all under the tag
+__device__ __forceinline__ void open_epoch(ScanCtl *C, const PassPose &pp, unsigned tag, int h) {
+  const u64 tg = (u64)tag << 32;
+  const u64 dj = (u64)__double_as_longlong(pp.cj), ds = (u64)__double_as_longlong(pp.sj);
+  const u64 eh = (u64)__double_as_longlong(pp.ch), es = (u64)__double_as_longlong(pp.sh);
+  st64(&C->pose[0], tg | (u64)__float_as_uint(pp.T.c));  st64(&C->pose[1], tg | (u64)__float_as_uint(pp.T.s));
+  st64(&C->pose[2], tg | (u64)__float_as_uint(pp.T.tx)); st64(&C->pose[3], tg | (u64)__float_as_uint(pp.T.ty));
+  st64(&C->pose[4], tg | (dj & 0xFFFFFFFFull));  st64(&C->pose[5], tg | (dj >> 32));
+  st64(&C->pose[6], tg | (ds & 0xFFFFFFFFull));  st64(&C->pose[7], tg | (ds >> 32));
+  st64(&C->pose[8], tg | (eh & 0xFFFFFFFFull));  st64(&C->pose[9], tg | (eh >> 32));
+  st64(&C->pose[10], tg | (es & 0xFFFFFFFFull)); st64(&C->pose[11], tg | (es >> 32));
+  st64(&C->ticket, ticket_of(tag, h, kUnits, kOwnerLead));
+}
+
+// owner, thread 0: the record of a scan of n points from the optimiser's last state (filled in place: returned by value it builds another kernel, LOG R17.1)
+__device__ __forceinline__ void fill_result(ndt_result &R_, const AlignState &S, const Lds &L, int n, bool aborted, bool unsorted) {
+  const Tf32 T = S.T;
+  R_.pose[0] = (double)T.tx; R_.pose[1] = (double)T.ty; R_.pose[2] = yaw_from_T(T.c, T.s);
+  R_.T00 = T.c; R_.T10 = T.s; R_.T03 = T.tx; R_.T13 = T.ty;
+  R_.fitness = DBL_MAX;                 // written by fitness_reduce_kernel, queued behind this kernel
+  R_.score = S.score;
+  R_.trans_prob = n > 0 ? S.score / (double)n : 0.0;
+  R_.H[0] = S.H[0]; R_.H[1] = S.H[1]; R_.H[2] = S.H[2];
+  R_.H[3] = S.H[1]; R_.H[4] = S.H[3]; R_.H[5] = S.H[4];
+  R_.H[6] = S.H[2]; R_.H[7] = S.H[4]; R_.H[8] = S.H[5];
+  R_.p[0] = S.p[0]; R_.p[1] = S.p[1]; R_.p[2] = S.p[2];
+  R_.iters = S.iters; R_.evals = S.evals;
+  R_.ref_evals = S.ref_evals + 1;       // + the getHessian pass (src/PoseEstimator.cpp:56)
+  R_.converged = S.converged;
+  R_.status = aborted ? NDT_E_HIP : (n > 0 ? NDT_OK : NDT_E_ARG);
+  R_.flags = n > 0 ? ((L.RG.nspill > 0 ? NDT_FLAG_WINDOW_SPILL : 0) | (L.clipped ? NDT_FLAG_REGION_CLIPPED : 0) |
+                      (unsorted ? NDT_FLAG_UNSORTED : 0)) : 0;      // (an empty scan has no window: nothing left over from the scan before it)
+  R_.kbar = (S.evals > 0 && n > 0) ? S.pairs / ((double)S.evals * (double)n) : 0.0;
+}
+
+// helper: how much an open scan with h helpers attached wants one more.  Which scan has most left to do?  Its score per
+// point says: against the best a FINISHED scan of this launch reached, 1.00 / 0.97 / 0.8 / 0.7 / 0.5 / 0.4 of it go with
+// 1 / 2 / 3 / 4 / 5 / 6-7 passes still to run (bench workload, tools/pass_counts.py: the score alone explains 65-78 % of the
+// variance of what is left; the passes run so far -- the rule until round 4 -- nothing once the repeated passes were gone).
+// In quarter passes; every attached helper counts like kHelperPenalty passes fewer, an owner on this XCD like kXcdBonus more.
+__device__ __forceinline__ int join_score(const ScanCtl *C, float best_spp, u32 h) {
+  int need4;
+  const float spp = __uint_as_float(ld32(&C->spp));
+  if (best_spp > 0.f) need4 = (int)(4.f * fminf(fmaxf(1.f + (float)kNeedSlope * (1.f - spp / best_spp), 0.f), 12.f));
+  else need4 = 4 * (int)min(ld32(&C->passes), 12u);
+  return need4 - 4 * kHelperPenalty * (int)h + ((kXcdBonus && ld32(&C->owner_xcd) == 1u + (blockIdx.x & 7u)) ? 4 * kXcdBonus : 0);
+}
+
+// Diagnostic builds (kProf): thread clocks of the owner over one scan, and how they are packed into the profile buffer
+// (the fitness ticks, the owner's wait and the helper units have no writer: their places hold 0).
+struct PassClock {
+  u64 q0 = 0, q1 = 0, q2 = 0, q3 = 0;                        // set-up: begun, region / order done, plan begun, window staged
+  u64 tt0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, tt1 = 0;           // the open pass: begun, opened, own units done, collected, summed
+  u64 t_eval = 0, t_adv = 0, t_scan0 = 0, t_first_shared = 0;
+  u64 a_n = 0, a_pro = 0, a_own = 0, a_wait = 0, a_comb = 0, a_adv = 0;     // shared passes: their number, sums of their phases
+  unsigned n_shared = 0;
+  __device__ __forceinline__ void setup_end(u64 *prof, int B, int b, const unsigned *diag) const {
+    u64 *p = prof + prof_shared_at(B, b);
+    p[kPhSetupA] = ((q1 - q0) << 32) | ((q2 - q1) & 0xFFFFFFFFull);
+    p[kPhSetupB] = ((q3 - q2) << 32) | ((u64)(diag[0] & 0xFFFFu) << 16) | (u64)(diag[1] & 0xFFFFu);
+  }
+  __device__ __forceinline__ void pass_end(int pass_h) {
+    const u64 te = wall_clock64();
+    if (threadIdx.x >= 64) tt1 = te;          // (only wave 0 stamps the end of the summation)
+    t_eval += tt1 - tt0;
+    t_adv += te - tt1;
+    if (pass_h > 0) { a_pro += ts1 - tt0; a_own += ts2 - ts1; a_wait += ts3 - ts2; a_comb += tt1 - ts3; a_adv += te - tt1; a_n += 1; }
+  }
+  __device__ __forceinline__ void scan_end(u64 *prof, int B, int b, int evals, bool spilled, u64 total) const {
+    u64 *p = prof + prof_scan_at(b);
+    p[kPsEval] = t_eval; p[kPsAdv] = t_adv | ((u64)spilled << 63); p[kPsStart] = (t_first_shared << 32) | (t_scan0 & 0xFFFFFFFFull);
+    p[kPsCounts] = (u64)evals | ((u64)n_shared << 16);
+    p[kPsWait] = 0; p[kPsTotal] = total;
+    u64 *p2 = prof + prof_shared_at(B, b);
+    p2[kPhCount] = a_n; p2[kPhPro] = a_pro; p2[kPhOwn] = a_own; p2[kPhWait] = a_wait; p2[kPhComb] = a_comb; p2[kPhAdv] = a_adv;
+  }
+};
+
 template <bool SSE, bool INCL, bool CHK, bool MULTI = false>
 __global__ void __launch_bounds__(kBlock)
 ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
@@ -1132,9 +1219,9 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
                  const double *__restrict__ inits, ndt_result *__restrict__ results,
                  double *__restrict__ trace, int trace_cap, int *__restrict__ trace_rows,
                  float2 *__restrict__ sorted /* scratch, same offsets as scans; may be null */,
-                 unsigned char *__restrict__ ws /* WsHeader, ScanCtl[B], unit totals[B][kUnits][24], marked-cell bitmaps[B][kRegionCells/32] */,
+                 unsigned char *__restrict__ ws /* the launch's workspace: see ws_bytes */,
                  int allow_helpers /* 0: none; else max helper workgroups per scan */,
-                 unsigned long long *__restrict__ prof /* diagnostic: 8 words per scan */,
+                 unsigned long long *__restrict__ prof /* diagnostic: the profile buffer (see kProfPasses), or null */,
                  const PrepRec *__restrict__ prep /* batch prepared ahead (ndt_order_kernel), or null */,
                  const unsigned *__restrict__ prep_map,
                  const MapView *__restrict__ views = nullptr /* MULTI: n_maps views; M is not read then */,
@@ -1142,10 +1229,9 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
   Lds &L = g_L;
   uint4 *const pool = g_pool;
   WsHeader *hdr = reinterpret_cast<WsHeader *>(ws);
-  ScanCtl *ctl = reinterpret_cast<ScanCtl *>(ws + sizeof(WsHeader));
-  u64 *utot = reinterpret_cast<u64 *>(ws + sizeof(WsHeader) + (size_t)B * sizeof(ScanCtl));
-  unsigned *wantmap = reinterpret_cast<unsigned *>(ws + sizeof(WsHeader) + (size_t)B * sizeof(ScanCtl) +
-                                                  (size_t)B * kUnits * kUnitWords * sizeof(u64));
+  ScanCtl *ctl = reinterpret_cast<ScanCtl *>(ws + ws_ctl_off());
+  u64 *utot = reinterpret_cast<u64 *>(ws + ws_utot_off((size_t)B));
+  unsigned *wantmap = reinterpret_cast<unsigned *>(ws + ws_bitmap_off((size_t)B));
   const u64 t_start = kProf ? wall_clock64() : 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x < 64) L.etab[threadIdx.x] = c_exp2_tab[threadIdx.x];
@@ -1194,12 +1280,10 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
     // fewer scans than workgroups: idle workgroups from the start -- the scan is opened to them in the middle of its ordering
     const bool early_open = allow_helpers != 0 && reg_path && !prepared && B < (int)gridDim.x;
     if (threadIdx.x == 0) {
-      u32 expect = 0u;
-      const bool won = !allow_helpers || b >= (int)gridDim.x || b == preclaimed ||
-                       __hip_atomic_compare_exchange_strong(&C->claimed, &expect, 1u, NDT_RLX, NDT_RLX, NDT_AGENT);
+      const bool won = !allow_helpers || b >= (int)gridDim.x || b == preclaimed || try_claim(C);
       L.sflag[3] = won ? 1 : 0;
       if (won) {
-        if (NDT_XCD_BONUS && allow_helpers) st32(&C->owner_xcd, 1u + (blockIdx.x & 7u));
+        if (kXcdBonus && allow_helpers) st32(&C->owner_xcd, 1u + (blockIdx.x & 7u));
         if (!reg_path) init_state(L.S, L.P, inits + 3 * (size_t)b, (double)n);
         if (trace_rows) trace_rows[b] = 0;
         if (n <= 0) { L.S.phase = PH_DONE; L.S.converged = 0; }
@@ -1208,56 +1292,55 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
     __syncthreads();
     if (!L.sflag[3]) {                        // taken over by another workgroup while this one was not resident: next scan
       __syncthreads();
-      if (threadIdx.x == 0) L.sflag[3] = (int)gridDim.x + (int)__hip_atomic_fetch_add(&hdr->next, 1u, NDT_RLX, NDT_AGENT);
+      if (threadIdx.x == 0) L.sflag[3] = next_in_queue(hdr);
       __syncthreads();
       b = L.sflag[3];
       continue;
     }
     const float2 *pts = scan;
-    u64 *const stamps = (kProf && prof) ? prof + 16 * (size_t)B + 16 * (size_t)b : nullptr;
+    u64 *const stamps = (kProf && prof) ? prof + prof_stamps_at(B, b) : nullptr;
     const u64 t0s = kProf ? wall_clock64() : 0;
+    PassClock clk;                                       // (diagnostic)
     if (n > 0) {
-      const u64 q0 = kProf ? wall_clock64() : 0;
+      if (kProf) clk.q0 = wall_clock64();
       if (!reg_path) NDT_STAMP(stamps, t0s, 0);
       // scratch copy: at the scan's own offsets, or (every match uses scan 0) one slot per match
       float2 *sp = sorted ? (shared_scan ? sorted + (size_t)b * (size_t)n : sorted + o0) : nullptr;
-      u64 q1 = 0;
       if (prepared) {
         // ordered ahead of the launch: the optimiser's start, the geometry and the bitmap come from the record, the copy is in place
         const PrepRec *R = prep + b;
         if (threadIdx.x < sizeof(AlignState) / 4)
           reinterpret_cast<u32 *>(&L.S)[threadIdx.x] = reinterpret_cast<const u32 *>(&R->S)[threadIdx.x];
         if (threadIdx.x == 64) {
-          Region r; r.x0 = R->region[0]; r.y0 = R->region[1]; r.rw = R->region[2]; r.rh = R->region[3]; r.cap = R->region[4]; r.nspill = 0;
-          L.RG = r; L.clipped = R->clipped;
+          L.RG = region_of(R->region, 0); L.clipped = R->clipped;
         }
         unsigned *wmap = reinterpret_cast<unsigned *>(L.wpart);
-        const unsigned *gm = prep_map + (size_t)b * (kRegionCells / 32);
-        for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) wmap[i] = gm[i];
+        const unsigned *gm = prep_map + (size_t)b * kBitmapWords;
+        for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) wmap[i] = gm[i];
         pts = sp;
         __syncthreads();
         NDT_STAMP(stamps, t0s, 0);
       } else if (reg_path) {
         order_scan_regs<SSE, kSortRegs / kBlock>(L.M, L.P, inits + 3 * (size_t)b, scan, n, L, pool, sp, stamps, t0s,
-                                                 early_open ? C : nullptr, early_open ? wantmap + (size_t)b * (kRegionCells / 32) : nullptr);
+                                                 early_open ? C : nullptr, early_open ? wantmap + (size_t)b * kBitmapWords : nullptr);
         pts = sp;
       } else {
         compute_region<SSE>(L.M, L.S.T, scan, n, L);
-        q1 = kProf ? wall_clock64() : 0;
+        if (kProf) clk.q1 = wall_clock64();
         NDT_STAMP(stamps, t0s, 1);
         if (sort_points<SSE>(L.M, L.S.T, scan, n, L, pool, sp, stamps, t0s)) pts = sp;
       }
-      if (kProf && q1 == 0) q1 = wall_clock64();
+      if (kProf && clk.q1 == 0) clk.q1 = wall_clock64();
       NDT_STAMP(stamps, t0s, 5);
-      const u64 q2 = kProf ? wall_clock64() : 0;
+      if (kProf) clk.q2 = wall_clock64();
       // Which voxels get a record (control block only; its loads of the map's occupancy words are in front of the copy's
       // stores: a wait for a load is a wait for every store issued before it), then the ordered copy on its way to memory.
       fill_window_plan(L.M, L, stamps, t0s);
       if (reg_path && !prepared) copy_out_ordered(pool, sp, n);
       if (allow_helpers && !early_open) {          // helpers rebuild the same window from this bitmap
         const unsigned *wmap = reinterpret_cast<const unsigned *>(L.wpart);
-        unsigned *gw = wantmap + (size_t)b * (kRegionCells / 32);
-        for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) st32(&gw[i], wmap[i]);
+        unsigned *gw = wantmap + (size_t)b * kBitmapWords;
+        for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) st32(&gw[i], wmap[i]);
       }
       // Publication: geometry + marked cells + ordered copy.  Everything a helper will read is stored write-through (geometry
       // and marked cells here, the ordered copy above) and drained by every wave before the ticket is written, so
@@ -1283,18 +1366,15 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             drain_vmem();
           }
-          st64(&C->ticket, (u64)1 << 32);                     // epoch 1: open for joining, nothing to compute (h = 0)
+          st64(&C->ticket, kTicketOpen);
         }
       }
       NDT_STAMP(stamps, t0s, 6);
       fill_window_fetch(L.M, L, pool, stamps, t0s);         // (its last barrier waits for every wave's outstanding stores)
-      if (allow_helpers && late_publish && threadIdx.x == 0) st64(&C->ticket, (u64)1 << 32);
+      if (allow_helpers && late_publish && threadIdx.x == 0) st64(&C->ticket, kTicketOpen);
       NDT_STAMP(stamps, t0s, 10);
-      const u64 q3 = kProf ? wall_clock64() : 0;
-      if (kProf && prof && threadIdx.x == 0) {
-        prof[8 * (size_t)B + 8 * (size_t)b + 6] = ((q1 - q0) << 32) | ((q2 - q1) & 0xFFFFFFFFull);
-        prof[8 * (size_t)B + 8 * (size_t)b + 7] = ((q3 - q2) << 32) | ((u64)(L.diag[0] & 0xFFFFu) << 16) | (u64)(L.diag[1] & 0xFFFFu);
-      }
+      if (kProf) clk.q3 = wall_clock64();
+      if (kProf && prof && threadIdx.x == 0) clk.setup_end(prof, B, b, L.diag);
     }
     unsigned epoch = 1;
     if (threadIdx.x == 0) {
@@ -1316,13 +1396,10 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
       L.sflag[1] = ready; L.pts = pts; L.npts = n;       // sflag[1]: registered helpers (refreshed during every advance)
       L.sflag[2] = 0;                                    // set by a thread whose wait ran into the watchdog
     }
-    u64 t_eval = 0, t_adv = 0, tt0 = 0, tt1 = 0, t_wait = 0, t_first_shared = 0, t_fit = 0;
-    u64 ts1 = 0, ts2 = 0, ts3 = 0, a_pro = 0, a_own = 0, a_wait = 0, a_comb = 0, a_adv = 0, a_n = 0;   // shared derivative passes (diagnostic)
-    const u64 t_scan0 = kProf ? wall_clock64() - t_start : 0;
-    unsigned n_shared = 0, n_helped = 0;
+    if (kProf) clk.t_scan0 = wall_clock64() - t_start;
     // ---- derivative passes until the optimiser stops (the fitness score is a kernel of its own: ndt_fitness.hip.h) ----
     while (n > 0 && L.S.phase != PH_DONE) {
-      if (kProf && prof) tt0 = wall_clock64();
+      if (kProf && prof) clk.tt0 = wall_clock64();
       // A pass is solo (one walk per wave) or split over the registered helpers.
       int pass_h = 0;
       if (threadIdx.x == 0) {
@@ -1336,25 +1413,16 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
           const float spp = (float)(L.S.score / (double)n);
           st32(&C->spp, spp > 0.f ? __float_as_uint(spp) : 0u);
         }
-        if (h > 0) {                            // open an epoch: the pose halves and the epoch word, all under its tag
-          const u64 tg = (u64)(epoch + 1) << 32;
-          const u64 dj = (u64)__double_as_longlong(pp.cj), ds = (u64)__double_as_longlong(pp.sj);
-          const u64 eh = (u64)__double_as_longlong(pp.ch), es = (u64)__double_as_longlong(pp.sh);
-          st64(&C->pose[0], tg | (u64)__float_as_uint(pp.T.c));  st64(&C->pose[1], tg | (u64)__float_as_uint(pp.T.s));
-          st64(&C->pose[2], tg | (u64)__float_as_uint(pp.T.tx)); st64(&C->pose[3], tg | (u64)__float_as_uint(pp.T.ty));
-          st64(&C->pose[4], tg | (dj & 0xFFFFFFFFull));  st64(&C->pose[5], tg | (dj >> 32));
-          st64(&C->pose[6], tg | (ds & 0xFFFFFFFFull));  st64(&C->pose[7], tg | (ds >> 32));
-          st64(&C->pose[8], tg | (eh & 0xFFFFFFFFull));  st64(&C->pose[9], tg | (eh >> 32));
-          st64(&C->pose[10], tg | (es & 0xFFFFFFFFull)); st64(&C->pose[11], tg | (es >> 32));
-          st64(&C->ticket, tg | ((u64)h << 16) | ((u64)kUnits << 8) | (u64)kOwnerLead);
+        if (h > 0) {
+          open_epoch(C, pp, epoch + 1, h);
           if (kProf && prof && epoch - 1 < (unsigned)kProfPasses) {
-            u64 *tl = prof + 32 * (size_t)B + ((size_t)b * kProfPasses + (epoch - 1)) * 16;
-            tl[0] = wall_clock64(); tl[3] = (u64)h;
+            u64 *tl = prof + prof_pass_at(B, b, epoch - 1);
+            tl[kPpOpened] = wall_clock64(); tl[kPpHelpers] = (u64)h;
           }
         }
       }
       __syncthreads();
-      if (kProf && prof) ts1 = wall_clock64();
+      if (kProf && prof) clk.ts1 = wall_clock64();
       const int nhelp = L.sflag[0];
       if (nhelp <= 0) {
         // solo pass: wave w computes its own units (w, 0..kSub-1) in one walk
@@ -1364,7 +1432,7 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
         ++epoch;
         pass_h = nhelp;
         pass_units<SSE, INCL, CHK>(kOwnerLead, nhelp + 1, kUnits, nullptr, 0u, kOwnerLead);
-        if (kProf && prof) ts2 = wall_clock64();
+        if (kProf && prof) clk.ts2 = wall_clock64();
         // the helpers' units: every thread polls the words it will copy (24 per unit) until they carry this epoch's
         // tag (every counted helper is polling the epoch word or computing)
         u32 *const wp32 = reinterpret_cast<u32 *>(L.wpart);
@@ -1374,18 +1442,9 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
         for (int wi = threadIdx.x; wi < kUnits * kUnitWords && !bad; wi += kBlock) {
           const int u = wi / kUnitWords;
           if (u < kOwnerLead || (u - kOwnerLead) % (nhelp + 1) == 0) continue;      // own unit
-#if NDT_POLL2
-          u64 w = 0, w_next = ld64(&mytot[wi]);          // two polls in flight: half the time between looks
-#else
           u64 w = 0;
-#endif
           for (unsigned it = 0; it < 0x40000000u; ++it) {
-#if NDT_POLL2
-            w = w_next;
-            w_next = ld64(&mytot[wi]);
-#else
             w = ld64(&mytot[wi]);
-#endif
             if ((u32)(w >> 32) == epoch) break;
             if ((++polls & 63u) == 0u) {           // bound on the spin, as in watchdog(); the clock is read lazily
               if (ld32(&hdr->abort)) { bad = true; break; }
@@ -1397,13 +1456,13 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
           wp32[wi] = (u32)w;
         }
         if (bad) L.sflag[2] = 1;
-        if (kProf && threadIdx.x == 0) { if (n_shared == 0) t_first_shared = ts2 - t_start; n_shared += 1; }
+        if (kProf && threadIdx.x == 0) { if (clk.n_shared == 0) clk.t_first_shared = clk.ts2 - t_start; clk.n_shared += 1; }
       }
       __syncthreads();
-      if (kProf && prof) ts3 = wall_clock64();
+      if (kProf && prof) clk.ts3 = wall_clock64();
       if (kProf && prof && threadIdx.x == 0 && pass_h > 0 && epoch - 2 < (unsigned)kProfPasses) {
-        u64 *tl = prof + 32 * (size_t)B + ((size_t)b * kProfPasses + (epoch - 2)) * 16;
-        tl[1] = ts2; tl[2] = ts3;
+        u64 *tl = prof + prof_pass_at(B, b, epoch - 2);
+        tl[kPpOwnDone] = clk.ts2; tl[kPpCollected] = clk.ts3;
       }
       if (L.sflag[2]) { aborted = true; break; }
       // pass total: the units in kSub groups of 16, each summed in unit order by one lane per value,
@@ -1430,14 +1489,10 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
 #pragma unroll
         for (int g = 1; g < kSub; ++g) total += __shfl(part, j + 12 * g);
         if (lane < 12) L.tot[lane] = total;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (kProf && prof) { tt1 = wall_clock64(); }
+        sync_wave();
+        if (kProf && prof) clk.tt1 = wall_clock64();
         if (lane == 0) advance(L.S, L.P, L.M, L.tot, tr, trace_cap, trace_rows ? trace_rows + b : nullptr);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        sync_wave();
         const int need_tf = L.S.need_tf;                       // (uniform: one LDS word)
         if (need_tf && lane < 2) trial_transforms(L.S, L.P, lane, need_tf);
       }
@@ -1446,59 +1501,31 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
       //  that has just registered must be counted in at once)
       if (threadIdx.x == 64 && allow_helpers) L.sflag[1] = (int)rd32_fresh(&C->ready);
       __syncthreads();
-      if (kProf && prof) {
-        const u64 te = wall_clock64();
-        if (threadIdx.x >= 64) tt1 = te;          // (only wave 0 stamps the end of the summation)
-        t_eval += tt1 - tt0;
-        t_adv += te - tt1;
-        if (pass_h > 0) { a_pro += ts1 - tt0; a_own += ts2 - ts1; a_wait += ts3 - ts2; a_comb += tt1 - ts3; a_adv += te - tt1; a_n += 1; }
-      }
+      if (kProf && prof) clk.pass_end(pass_h);
     }
     // ---- result record; close the scan ----
     if (threadIdx.x == 0) {
       const AlignState &S = L.S;
-      const Tf32 T = S.T;
       ndt_result R_;
-      R_.pose[0] = (double)T.tx; R_.pose[1] = (double)T.ty; R_.pose[2] = yaw_from_T(T.c, T.s);
-      R_.T00 = T.c; R_.T10 = T.s; R_.T03 = T.tx; R_.T13 = T.ty;
-      R_.fitness = DBL_MAX;                 // written by fitness_reduce_kernel, queued behind this kernel
-      R_.score = S.score;
-      R_.trans_prob = n > 0 ? S.score / (double)n : 0.0;
-      R_.H[0] = S.H[0]; R_.H[1] = S.H[1]; R_.H[2] = S.H[2];
-      R_.H[3] = S.H[1]; R_.H[4] = S.H[3]; R_.H[5] = S.H[4];
-      R_.H[6] = S.H[2]; R_.H[7] = S.H[4]; R_.H[8] = S.H[5];
-      R_.p[0] = S.p[0]; R_.p[1] = S.p[1]; R_.p[2] = S.p[2];
-      R_.iters = S.iters; R_.evals = S.evals;
-      R_.ref_evals = S.ref_evals + 1;       // + the getHessian pass (src/PoseEstimator.cpp:56)
-      R_.converged = S.converged;
-      R_.status = aborted ? NDT_E_HIP : (n > 0 ? NDT_OK : NDT_E_ARG);
-      R_.flags = n > 0 ? ((L.RG.nspill > 0 ? NDT_FLAG_WINDOW_SPILL : 0) | (L.clipped ? NDT_FLAG_REGION_CLIPPED : 0) |
-                          (pts == scan ? NDT_FLAG_UNSORTED : 0)) : 0;      // (an empty scan has no window: nothing left over from the scan before it)
-      R_.kbar = (S.evals > 0 && n > 0) ? S.pairs / ((double)S.evals * (double)n) : 0.0;
+      fill_result(R_, S, L, n, aborted, pts == scan);
       if (MULTI && mi < 0) {                 // no map: zeroed, NDT_E_ARG, not converged, fitness DBL_MAX (the fitness kernels skip it)
         memset(&R_, 0, sizeof(R_));
         R_.status = NDT_E_ARG; R_.fitness = DBL_MAX;
       }
       results[b] = R_;
       if (allow_helpers) {
-        st64(&C->ticket, (u64)kEpochDone << 32);
+        st64(&C->ticket, kTicketDone);
         // (MULTI: a score per point compared across scans of different maps -- best_spp only ranks scans for the helpers'
         //  choice of whom to join, and no record depends on who helps whom)
         const float spp = n > 0 ? (float)(S.score / (double)n) : 0.f;
         if (S.converged && spp > 0.f) __hip_atomic_fetch_max(&hdr->best_spp, __float_as_uint(spp), NDT_RLX, NDT_AGENT);   // (positive floats order like their bits)
         __hip_atomic_fetch_add(&hdr->done, 1u, NDT_RLX, NDT_AGENT);
       }
-      if (kProf && prof) {
-        prof[8 * b + 0] = t_eval; prof[8 * b + 1] = t_adv | (t_fit << 32) | ((u64)(L.RG.nspill > 0) << 63); prof[8 * b + 2] = (t_first_shared << 32) | (t_scan0 & 0xFFFFFFFFull);
-        prof[8 * b + 3] = (unsigned long long)S.evals | ((u64)n_shared << 16) | ((u64)n_helped << 32);
-        prof[8 * b + 6] = t_wait; prof[8 * b + 7] = wall_clock64() - t_start;
-        u64 *p2 = prof + 8 * (size_t)B + 8 * (size_t)b;
-        p2[0] = a_n; p2[1] = a_pro; p2[2] = a_own; p2[3] = a_wait; p2[4] = a_comb; p2[5] = a_adv;
-      }
+      if (kProf && prof) clk.scan_end(prof, B, b, S.evals, L.RG.nspill > 0, wall_clock64() - t_start);
     }
       // next scan of the batch, if any: from the queue; once that is used up, a scan nobody has claimed (see "Claims")
     __syncthreads();
-    if (threadIdx.x == 0) { L.sflag[3] = (int)gridDim.x + (int)__hip_atomic_fetch_add(&hdr->next, 1u, NDT_RLX, NDT_AGENT); L.steal = INT_MAX; }
+    if (threadIdx.x == 0) { L.sflag[3] = next_in_queue(hdr); L.steal = INT_MAX; }
     __syncthreads();
     b = L.sflag[3];
     if (b >= B && allow_helpers && !aborted) {
@@ -1509,8 +1536,7 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
       if (threadIdx.x == 0) {
         int got = B;
         for (int tries = 0; tries < 4 && L.steal != INT_MAX && got == B; ++tries) {   // lost a race: the next free one, if any
-          u32 expect = 0u;
-          if (__hip_atomic_compare_exchange_strong(&ctl[L.steal].claimed, &expect, 1u, NDT_RLX, NDT_RLX, NDT_AGENT)) got = L.steal;
+          if (try_claim(&ctl[L.steal])) got = L.steal;
           else {
             int nx = INT_MAX;
             for (int k = L.steal + 1; k < first; ++k) if (ld32(&ctl[k].claimed) == 0u) { nx = k; break; }
@@ -1541,25 +1567,12 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
     const float best_spp = __uint_as_float(ld32(&hdr->best_spp));
     for (int k = threadIdx.x; k < B; k += kBlock) {
       int b = start + k; if (b >= B) b -= B;
-      const u32 ep = (u32)(rd64_fresh(&ctl[b].ticket) >> 32);
+      const u32 ep = (u32)(rd64_fresh(&ctl[b].ticket) >> 32);     // (ticket_epoch here builds another kernel: LOG R17.1)
       if (ep == 0u) { L.sflag[2] = 1; continue; }          // not open yet (its owner is setting up, or a workgroup that runs out of work will claim it): may need help later
       if (ep == kEpochDone) continue;
       const u32 h = rd32_fresh(&ctl[b].helpers);
       if (h >= (u32)room) continue;
-      // Which scan has most left to do?  Its score per point says: against the best a FINISHED scan of this launch reached,
-      // 1.00 / 0.97 / 0.8 / 0.7 / 0.5 / 0.4 of it go with 1 / 2 / 3 / 4 / 5 / 6-7 passes still to run (bench workload,
-      // tools/pass_counts.py: the score alone explains 65-78 % of the variance of what is left; the passes run so far --
-      // the rule until round 4 -- nothing once the repeated passes were gone).  In quarter passes; every attached helper
-      // counts like NDT_HELPER_PENALTY passes fewer, an owner on this XCD like NDT_XCD_BONUS more; then nearest.
-      int need4;
-#ifndef NDT_NO_NEED_POLICY
-      const float spp = __uint_as_float(ld32(&ctl[b].spp));
-      if (best_spp > 0.f) need4 = (int)(4.f * fminf(fmaxf(1.f + (float)NDT_NEED_SLOPE * (1.f - spp / best_spp), 0.f), 12.f));
-      else
-#endif
-        need4 = 4 * (int)min(ld32(&ctl[b].passes), 12u);
-      const int score = need4 - 4 * NDT_HELPER_PENALTY * (int)h +
-                        ((NDT_XCD_BONUS && ld32(&ctl[b].owner_xcd) == 1u + (blockIdx.x & 7u)) ? 4 * NDT_XCD_BONUS : 0);
+      const int score = join_score(&ctl[b], best_spp, h);      // then nearest
       atomicMin(&L.sflag[0], (int)(((u32)(1024 - score) << 20) | (u32)k));
     }
     __syncthreads();
@@ -1577,15 +1590,15 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
         } else {
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // geometry + ordered copy of the owner
           drain_vmem();
-          if (kProf && prof && h == 0) prof[8 * b + 4] = wall_clock64() - t_start;
+          if (kProf && prof && h == 0) prof[prof_scan_at(b) + kPsAttached] = wall_clock64() - t_start;
           code = b;
         }
       }
       L.sflag[3] = code;
-      if (code == -1) {                                    // back off: 4 us, doubling up to NDT_IDLE_MAX ticks
+      if (code == -1) {                                    // back off: 4 us, doubling up to kIdleMax ticks
         const u64 t0 = wall_clock64();
         while (wall_clock64() - t0 < idle_ticks) __builtin_amdgcn_s_sleep(64);
-        if (idle_ticks < NDT_IDLE_MAX) idle_ticks *= 2;
+        if (idle_ticks < kIdleMax) idle_ticks *= 2;
       } else {
         idle_ticks = 400;
       }
@@ -1605,22 +1618,18 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
       if (hm >= 0) load_view(L, views, hm);
     }
     if (threadIdx.x == 0) L.sflag[1] = (int)C->use_sorted;
-    if (threadIdx.x == 0) {
-      Region r; r.x0 = C->region[0]; r.y0 = C->region[1]; r.rw = C->region[2]; r.rh = C->region[3];
-      r.cap = C->region[4]; r.nspill = C->region[5];
-      L.RG = r;
-    }
+    if (threadIdx.x == 0) L.RG = region_of(C->region, C->region[5]);
     {
       unsigned *wmap = reinterpret_cast<unsigned *>(L.wpart);
-      const unsigned *gw = wantmap + (size_t)vb * (kRegionCells / 32);
-      for (int i = threadIdx.x; i < kRegionCells / 32; i += kBlock) wmap[i] = gw[i];
+      const unsigned *gw = wantmap + (size_t)vb * kBitmapWords;
+      for (int i = threadIdx.x; i < kBitmapWords; i += kBlock) wmap[i] = gw[i];
     }
     __syncthreads();
     const float2 *pts = L.sflag[1] ? (shared_scan ? sorted + (size_t)vb * (size_t)n : sorted + o0)
                                    : (reinterpret_cast<const float2 *>(scans) + o0);
     fill_window(L.M, L, pool);
     if (threadIdx.x == 0) { L.pts = pts; L.npts = n; }
-    if (kProf && prof && threadIdx.x == 0 && prof[8 * vb + 5] == 0) prof[8 * vb + 5] = wall_clock64() - t_start;
+    if (kProf && prof && threadIdx.x == 0 && prof[prof_scan_at(vb) + kPsHelperReady] == 0) prof[prof_scan_at(vb) + kPsHelperReady] = wall_clock64() - t_start;
     u64 *vtot = utot + (size_t)vb * kUnits * kUnitWords;
     // register: from now on this workgroup does nothing but watch the scan's epoch word
     if (threadIdx.x == 0) L.hrank = (int)__hip_atomic_fetch_add(&C->ready, 1u, NDT_RLX, NDT_AGENT);
@@ -1634,45 +1643,36 @@ ndt_align_kernel(MapView M, OptParams P, const float *__restrict__ scans,
         u64 word = 0, mine = 0;
         unsigned polls = 0;
         const u64 w0 = wall_clock64();
-#if NDT_POLL2H
-        u64 mine_next = 0;
-        if (lane <= kPoseWords) mine_next = ld64(&C->ticket + lane);   // two polls in flight: half the time between looks
-#endif
         for (unsigned it = 0; it < 0x40000000u; ++it) {
-#if NDT_POLL2H
-          mine = mine_next;
-          if (lane <= kPoseWords) mine_next = ld64(&C->ticket + lane);
-#else
           if (lane <= kPoseWords) mine = ld64(&C->ticket + lane);
-#endif
           word = wave_bcast64(mine);
-          const u32 ep = (u32)(word >> 32);
+          const u32 ep = ticket_epoch(word);
           if (ep != last_ep && ep != 0u) {
-            if (ep == kEpochDone || rank >= (int)((word >> 16) & 0xFFu)) break;
+            if (ep == kEpochDone || rank >= ticket_helpers(word)) break;
             if (__builtin_amdgcn_ballot_w64(lane <= kPoseWords && (u32)(mine >> 32) != ep) == 0ull) break;
           }
-          if (watchdog(hdr, w0, polls)) { word = (u64)kEpochDone << 32; break; }
+          if (watchdog(hdr, w0, polls)) { word = kTicketDone; break; }
           __builtin_amdgcn_s_sleep(1);
         }
-        if ((u32)(word >> 32) != kEpochDone && rank < (int)((word >> 16) & 0xFFu) && lane >= 1 && lane <= kPoseWords)
+        if (ticket_epoch(word) != kEpochDone && rank < ticket_helpers(word) && lane >= 1 && lane <= kPoseWords)
           reinterpret_cast<u32 *>(&L.PP)[lane - 1] = (u32)mine;      // T.c, T.s, T.tx, T.ty, then the halves of cj, sj, ch, sh
         if (lane == 0) { L.hword = word; L.jnext = 0; }
-        if (kProf && prof && lane == 0 && rank < 6 && rank < (int)((word >> 16) & 0xFFu) && (u32)(word >> 32) - 2u < (unsigned)kProfPasses)
-          prof[32 * (size_t)B + ((size_t)vb * kProfPasses + ((u32)(word >> 32) - 2u)) * 16 + 4 + 2 * rank] = wall_clock64();
+        if (kProf && prof && lane == 0 && rank < kProfRanks && rank < ticket_helpers(word) && ticket_epoch(word) - 2u < (unsigned)kProfPasses)
+          prof[prof_pass_at(B, vb, ticket_epoch(word) - 2u) + prof_pass_helper(rank, false)] = wall_clock64();
       }
       __syncthreads();
       const u64 word = L.hword;
-      const u32 ep = (u32)(word >> 32);
+      const u32 ep = ticket_epoch(word);
       if (ep == kEpochDone) break;
       last_ep = ep;
-      const int h = (int)((word >> 16) & 0xFFu), ubeg = (int)(word & 0xFFu), uend = (int)((word >> 8) & 0xFFu);
+      const int h = ticket_helpers(word), ubeg = ticket_ubeg(word), uend = ticket_uend(word);
       if (rank < h) {
         // this workgroup's units ubeg + rank+1 + j*(h+1), handed to its waves from an LDS counter
         pass_units<SSE, INCL, CHK>(ubeg + (rank + 1), h + 1, uend, vtot, ep, 0);
       }
       __syncthreads();                                       // L.jnext / L.PP are rewritten by wave 0 in the next turn
-      if (kProf && prof && threadIdx.x == 0 && rank < 6 && rank < h && ep - 2u < (unsigned)kProfPasses)
-        prof[32 * (size_t)B + ((size_t)vb * kProfPasses + (ep - 2u)) * 16 + 5 + 2 * rank] = wall_clock64();
+      if (kProf && prof && threadIdx.x == 0 && rank < kProfRanks && rank < h && ep - 2u < (unsigned)kProfPasses)
+        prof[prof_pass_at(B, vb, ep - 2u) + prof_pass_helper(rank, true)] = wall_clock64();
     }
   }
 }

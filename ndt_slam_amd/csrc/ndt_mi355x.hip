@@ -469,16 +469,14 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   if (defer && !ctx->fit_stream) { const int rc = ctx->fit_stream.create(ctx, hipStreamNonBlocking); if (rc) return rc; }
   const MapView &V = map->view;
   const OptParams O = opt_of(map->prm);
-  // workspace: header + one control line per scan (zeroed every launch) + chunk totals
-  // control words, epoch-tagged pose halves and unit totals (zero at kernel start), then the marked-cell bitmaps
-  const size_t zero_bytes = sizeof(WsHeader) + (size_t)B * sizeof(ScanCtl) + (size_t)B * kUnits * kUnitWords * sizeof(u64);
+  // workspace (layout: ws_bytes, ndt_match.hip.h): what lies in front of the marked-cell bitmaps is zero at kernel start
+  const size_t zero_bytes = ws_bitmap_off((size_t)B);
   // a multi-map launch: its table of MapViews behind the bitmaps, outside the zeroed part -- in the launch's own set, so that
   // it lives as long as the launch's fitness kernels, which read it (NDT_OPT_DEFER_FITNESS: the set is not taken over before
   // they have finished; see below)
-  const size_t tab_off = (zero_bytes + (size_t)B * (kRegionCells / 8) + 255) & ~(size_t)255;
-  const size_t ws_bytes = mm ? tab_off + (size_t)mm->n_maps * sizeof(MapView) : zero_bytes + (size_t)B * (kRegionCells / 8);
+  const size_t tab_off = ws_views_off((size_t)B);
   bool grown = false;
-  int rc = set.ws.ensure(ctx, ws_bytes, &grown);
+  int rc = set.ws.ensure(ctx, ws_bytes((size_t)B, mm ? (size_t)mm->n_maps : 0), &grown);
   if (rc) return rc;
   if (grown) set.ws_clean = 0;
   // ordered copy of every scan (what the passes and the fitness kernel read) and one float per point for the
@@ -1394,7 +1392,7 @@ int ndt_align_batch_prepare_dev(ndt_ctx *ctx, const ndt_map *map, const float *s
   int rc;
   if ((rc = S.sorted.ensure(ctx, slots + 2))) return rc;
   if ((rc = S.recs.ensure(ctx, (size_t)B))) return rc;
-  if ((rc = S.maps.ensure(ctx, (size_t)B * (kRegionCells / 8)))) return rc;
+  if ((rc = S.maps.ensure(ctx, (size_t)B * kBitmapBytes))) return rc;
   if (!S.ready && ((rc = S.ev0.create(ctx)) || (rc = S.ready.create(ctx)))) return rc;
   // Of the map it takes the grid's geometry (by value, now) and reads nothing on the device: no wait for a build that may be
   // queued or running -- a two-phase rebuild that ends with another grid simply leaves this set unused.  It is ordered behind
@@ -1490,25 +1488,27 @@ repack_f2_kernel(const float *__restrict__ in, size_t stride, size_t n, float2 *
 void prof_report(const unsigned long long *hp, int B) {
   double te = 0, ta = 0, tw = 0, ev = 0, sh = 0, hc = 0, worst = 0;
   std::vector<unsigned long long> seen((size_t)B, 0ull);
+  auto word = [&](int b, ProfScan k) { return hp[prof_scan_at(b) + k]; };
+  auto ticks = [&](int b) { return (word(b, kPsEval) + (word(b, kPsAdv) & 0xFFFFFFFFull)) * 0.01; };
   for (int b = 0; b < B; ++b) {
-    te += hp[8 * b] * 0.01; ta += (hp[8 * b + 1] & 0xFFFFFFFFull) * 0.01; tw += hp[8 * b + 6] * 0.01;
-    ev += (double)(hp[8 * b + 3] & 0xFFFF); sh += (double)((hp[8 * b + 3] >> 16) & 0xFFFF); hc += (double)(hp[8 * b + 3] >> 32);
-    double tot = (hp[8 * b] + (hp[8 * b + 1] & 0xFFFFFFFFull)) * 0.01;
-    if (tot > worst) worst = tot;
+    te += word(b, kPsEval) * 0.01; ta += (word(b, kPsAdv) & 0xFFFFFFFFull) * 0.01; tw += word(b, kPsWait) * 0.01;
+    ev += (double)(word(b, kPsCounts) & 0xFFFF); sh += (double)((word(b, kPsCounts) >> 16) & 0xFFFF); hc += (double)(word(b, kPsCounts) >> 32);
+    if (ticks(b) > worst) worst = ticks(b);
   }
   for (int rep = 0; rep < 6 && rep < B; ++rep) {      // the longest scans
     int best = -1; double bt = -1;
-    for (int b = 0; b < B; ++b) { double tot = (hp[8 * b] + (hp[8 * b + 1] & 0xFFFFFFFFull)) * 0.01; if (tot > bt && !seen[b]) { bt = tot; best = b; } }
+    for (int b = 0; b < B; ++b) if (ticks(b) > bt && !seen[b]) { bt = ticks(b); best = b; }
     if (best < 0) break;
     fprintf(stderr, "[NDT_PROF]   scan %3d: %.0f us (fitness pass %.0f us, window spilled %d), passes %llu, shared %llu, helper units %llu, first shared pass at %.0f us (scan started %.0f, first helper attached %.0f, its window ready %.0f)\n", best, bt,
-            (double)((hp[8 * best + 1] >> 32) & 0x7FFFFFFFull) * 0.01, (int)(hp[8 * best + 1] >> 63),
-            hp[8 * best + 3] & 0xFFFF, (hp[8 * best + 3] >> 16) & 0xFFFF, (hp[8 * best + 3] >> 32) & 0x7FFFFFFF, (double)(hp[8 * best + 2] >> 32) * 0.01, (double)(hp[8 * best + 2] & 0xFFFFFFFFull) * 0.01,
-            (double)hp[8 * best + 4] * 0.01, (double)hp[8 * best + 5] * 0.01);
+            (double)((word(best, kPsAdv) >> 32) & 0x7FFFFFFFull) * 0.01, (int)(word(best, kPsAdv) >> 63),
+            word(best, kPsCounts) & 0xFFFF, (word(best, kPsCounts) >> 16) & 0xFFFF, (word(best, kPsCounts) >> 32) & 0x7FFFFFFF,
+            (double)(word(best, kPsStart) >> 32) * 0.01, (double)(word(best, kPsStart) & 0xFFFFFFFFull) * 0.01,
+            (double)word(best, kPsAttached) * 0.01, (double)word(best, kPsHelperReady) * 0.01);
     seen[best] = 1;
   }
   fprintf(stderr, "[NDT_PROF] B=%d passes=%.0f (+fitness) | per pass: compute+combine %.2f us, advance %.2f us | shared passes %.0f, helper chunks %.0f, owner wait %.2f us per shared pass | slowest scan %.1f us\n",
           B, ev, te / (ev + B), ta / ev, sh, hc, sh > 0 ? tw / sh : 0.0, worst);
-  if (const char *dump = getenv("NDT_PROF_DUMP")) { FILE *f = fopen(dump, "wb"); if (f) { fwrite(hp, 256 + kProfTimeline * 8, (size_t)B, f); fclose(f); } }
+  if (const char *dump = getenv("NDT_PROF_DUMP")) { FILE *f = fopen(dump, "wb"); if (f) { fwrite(hp, prof_scan_bytes(), (size_t)B, f); fclose(f); } }
 }
 #endif
 
@@ -1549,7 +1549,7 @@ int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t s
   unsigned long long *d_prof = nullptr;
 #ifdef NDT_DIAG
   const bool want_prof = getenv("NDT_PROF") != nullptr;
-  const size_t prof_bytes = (size_t)B * (256 + kProfTimeline * 8);      // phase timers, then the shared-pass timelines
+  const size_t prof_bytes = (size_t)B * prof_scan_bytes();
   DevBuf<unsigned long long> prof_buf;
   if (want_prof && (rc = prof_buf.alloc(ctx, prof_bytes))) return rc;
   if (want_prof) { d_prof = prof_buf.p; HIP_TRY(ctx, hipMemsetAsync(d_prof, 0, prof_bytes, st)); }
