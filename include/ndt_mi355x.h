@@ -672,6 +672,66 @@ int ndt_relocalize_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_de
                        const ndt_reloc_params *params, uint64_t *cand_index, double *cand_score, ndt_result *records,
                        int *n_cand, int *best, double *scores_host);
 
+/* ---- Per-point nearest distances and the ranged fitness ------------------------------------------------------------------
+ * ndt_result.fitness is getFitnessScore() as src/PoseEstimator.cpp:43 calls it: PCL's getFitnessScore(max_range) with the
+ * default max_range = DBL_MAX, the mean over EVERY scan point.  These calls give what that one number hides: the float32
+ * squared distance of every point of a scan, at a given transform, to its nearest raw map point, in the caller's order, and
+ * PCL's getFitnessScore(max_range) from them for any range.
+ *
+ * Inputs.  scans_xy / offsets / B / total_points / shared_scan as for ndt_align_batch_dev (packed float2; shared_scan: scan 0
+ * with B transforms).  Transform b is four floats (c, s, tx, ty) at (const char *)tf + b * tf_stride_bytes: the T00, T10,
+ * T03, T13 of an ndt_result, in that order; tf_stride_bytes is a multiple of 4 and at least 16, so sizeof(ndt_result) with
+ * tf = &records[0].T00 takes the transforms straight from a launch's records, on the device, without a copy.  The point
+ * transform is the map's ndt_params::transform_sse form, the one the launch's own fitness kernels apply.
+ *
+ * d2.  The value the launch's search returns: the minimum over all raw map points of F(ex * ex) + F(ey * ey), float32.  A point
+ * without a distance -- a non-finite transformed point, or one every distance of which overflows -- gets +INFINITY.  Output
+ * is in INPUT order, never the launch's internal voxel order: scans of their own, the point's index in scans_xy (d2 has
+ * total_points floats); shared_scan, index b * n + i (d2 has B * n floats).  d2 may be NULL and stats may be NULL, not both.
+ *
+ * Stats.  max_d2 is compared with the SQUARED distance widened to double, `<=`, inclusive: what PCL's
+ * getFitnessScore(max_range) does with its argument.  DBL_MAX reproduces the reference's call (src/PoseEstimator.cpp:43);
+ * 0.0 is legal and counts the exact hits.
+ *
+ * Order of summation, stated once and kept.  Chunk k of a match is its points [64k, 64k + 64) in input order.  A chunk's two
+ * sums (all / in range) are the wave butterfly over the 64 lanes' (double)d2, 0.0 where the predicate fails.  Lane l of ONE
+ * wave adds the chunks l, l + 64, l + 128 ... in ascending order into one accumulator; the butterfly then adds the lanes.
+ * Counts are integers.  fitness = n_in ? S_in / n_in : DBL_MAX, fitness_all likewise with n_dist.  (The launch's own scheme,
+ * over input order instead of its ordered copy.)  A match's ndt_fit_stats and d2 are a function of (map, scan, transform,
+ * max_d2) to the last bit: they do not depend on b, B, the other scans, shared_scan against the own-scan form, or
+ * NDT_OPT_WORKGROUPS.  fitness_all equals ndt_result.fitness of a launch with the same transform within n * 2^-53 relative,
+ * and bit for bit whenever the scan's sum is exact in fp64.
+ * An empty scan: stats {DBL_MAX, DBL_MAX, 0, 0, 0, 0}, no d2 written.
+ *
+ * Ordering.  _dev is asynchronous on `stream` (NULL = the context's) and runs behind the map's build; it is entered among the
+ * map's readers as the score sweep is, so a rebuild of the map queued behind it -- on whatever stream -- waits for it.  Its
+ * scratch (one 32-byte {S_all, S_in, n_dist, n_in} per chunk) lies inside the context's scratch bracket.  ndt_fit_points_batch:
+ * host pointers; one upload, the _dev call, one read-back each of d2 and stats; synchronous.
+ *
+ * Refusals (NDT_E_ARG, synchronous, nothing queued or written): a NULL context ("null context"); a NULL map, scans, offsets
+ * or tf; both outputs NULL; B < 1; a map never built or of another device; tf_stride_bytes below 16 or not a multiple of 4;
+ * max_d2 NaN or below 0; host form: offsets that decrease; an open ndt_map_rebuild_begin on the context. */
+typedef struct ndt_fit_stats {
+  double   fitness;      /* getFitnessScore(max_range) (PCL; src/PoseEstimator.cpp:43 passes none): mean of d2 over the
+                            points with (double)d2 <= max_d2; DBL_MAX when there is none                       */
+  double   fitness_all;  /* the same with no cut (src/PoseEstimator.cpp:43 as it stands): the quantity
+                            ndt_result.fitness holds, summed in THIS call's order                                   */
+  uint32_t n_in;         /* points with (double)d2 <= max_d2                                                        */
+  uint32_t n_dist;       /* points that have a distance at all                                                      */
+  uint32_t n_points;     /* points of the scan                                                                      */
+  uint32_t reserved;     /* 0                                                                                       */
+} ndt_fit_stats;         /* 32 bytes */
+/* getFitnessScore(max_range) of PCL (src/PoseEstimator.cpp:43: without a range) and its per-point terms; device pointers. */
+int ndt_fit_points_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_dev,
+                             const uint64_t *offsets_dev, int B, size_t total_points, int shared_scan,
+                             const float *tf_dev, size_t tf_stride_bytes, double max_d2,
+                             float *d2_dev, ndt_fit_stats *stats_dev, void *stream);
+/* The same from host memory (getFitnessScore(max_range) of PCL; src/PoseEstimator.cpp:43); synchronous. */
+int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_host,
+                         const uint64_t *offsets_host, int B, int shared_scan,
+                         const float *tf_host, size_t tf_stride_bytes, double max_d2,
+                         float *d2_host, ndt_fit_stats *stats_host);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

@@ -101,6 +101,17 @@ class RelocParams(C.Structure):
     _fields_ = [("lattice", PoseLattice), ("top_k", C.c_int), ("local_max", C.c_int)]
 
 
+class FitStats(C.Structure):
+    """ndt_fit_stats (include/ndt_mi355x.h): one match's getFitnessScore(max_range) and its counts."""
+    _fields_ = [("fitness", C.c_double), ("fitness_all", C.c_double), ("n_in", C.c_uint32), ("n_dist", C.c_uint32),
+                ("n_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FIT_STATS_DTYPE = np.dtype([("fitness", "f8"), ("fitness_all", "f8"), ("n_in", "u4"), ("n_dist", "u4"), ("n_points", "u4"),
+                            ("reserved", "u4")], align=True)
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -134,6 +145,7 @@ EXPORTS = [
     "ndt_sessions_local_map", "ndt_sessions_submap_cloud", "ndt_sessions_global_map", "ndt_sessions_get_stats",
     "ndt_lattice_size", "ndt_lattice_pose", "ndt_score_poses", "ndt_score_poses_dev", "ndt_score_lattice_dev",
     "ndt_lattice_select_dev", "ndt_relocalize", "ndt_relocalize_dev",
+    "ndt_fit_points_batch", "ndt_fit_points_batch_dev",
 ]
 
 
@@ -218,6 +230,8 @@ def lib():
     L.ndt_lattice_select_dev.argtypes = [vp, C.POINTER(PoseLattice), vp, vp, i, i, vp, vp, vp]
     L.ndt_relocalize.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
     L.ndt_relocalize_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
+    L.ndt_fit_points_batch_dev.argtypes = [vp, vp, vp, vp, i, sz, i, vp, sz, C.c_double, vp, vp, vp]
+    L.ndt_fit_points_batch.argtypes = [vp, vp, vp, vp, i, i, vp, sz, C.c_double, vp, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -371,6 +385,28 @@ def _f32c(a):
     if a.ndim != 2 or a.shape[1] != 2:
         raise ValueError("expected an [n, 2] float32 array")
     return a
+
+
+def _tf4(tf):
+    """[B, 4] float32 (c, s, tx, ty) of a [B, 4] array or of align_batch's records (T00, T10, T03, T13)."""
+    tf = np.asarray(tf)
+    if tf.dtype.names is not None:
+        tf = np.stack([tf["T00"], tf["T10"], tf["T03"], tf["T13"]], axis=-1)
+    tf = np.ascontiguousarray(tf, dtype=np.float32)
+    if tf.ndim != 2 or tf.shape[1] != 4:
+        raise ValueError("expected a [B, 4] float32 array of (c, s, tx, ty) or a record array")
+    return tf
+
+
+def rerank(records, stats):
+    """Index of the lowest `converged ? ranged fitness : 1e7` over a relocalisation's records and their FIT_STATS_DTYPE of
+    one fit_points call; ties to the higher n_in, then the lower index.  -1 for no records."""
+    best, key = -1, None
+    for c in range(len(records)):
+        k = (float(stats[c]["fitness"]) if records[c]["converged"] else 1e7, -int(stats[c]["n_in"]), c)
+        if key is None or k < key:
+            best, key = c, k
+    return best
 
 
 class Context:
@@ -865,10 +901,43 @@ class Map:
         cx.check(lib().ndt_lattice_select_dev(cx.h, C.byref(lattice), score_ptr, pairs_ptr, int(top_k), int(local_max), cand_ptr,
                                               n_cand_ptr, stream), "ndt_lattice_select_dev")
 
-    def relocalize(self, scan, lattice, top_k=16, local_max=True, want_scores=False, dev_ptr=None, n=None, stride=8):
+    def fit_points(self, scans, offsets, tf, max_d2=DBL_MAX, shared_scan=False, want_d2=True):
+        """ndt_fit_points_batch: the float32 squared distance of every scan point, at transform b of `tf`, to its nearest raw
+        map point, in input order, and getFitnessScore(max_range) per match -> (d2 float32 or None, stats FIT_STATS_DTYPE [B]).
+        `tf`: a [B, 4] float32 array of (c, s, tx, ty), or a record array of align_batch (its T00, T10, T03, T13 are taken).
+        shared_scan: scan 0 with every transform; d2 is then [B * n], row b at b * n."""
+        scans = _f32c(scans)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        tf = _tf4(tf)
+        B = len(tf)
+        nscan = 1 if shared_scan else B
+        if len(offsets) != nscan + 1:
+            raise ValueError("offsets needs one entry per scan and one more")
+        n_d2 = B * int(offsets[1] - offsets[0]) if shared_scan else int(offsets[-1])
+        d2 = np.zeros(n_d2, dtype=np.float32) if want_d2 else None
+        stats = np.zeros(B, dtype=FIT_STATS_DTYPE)
+        self.ctx.check(lib().ndt_fit_points_batch(self.ctx.h, self.h, scans.ctypes.data, offsets.ctypes.data, B, int(shared_scan),
+                                                  tf.ctypes.data, 16, float(max_d2), d2.ctypes.data if want_d2 else None,
+                                                  stats.ctypes.data), "ndt_fit_points_batch")
+        return d2, stats
+
+    def fit_points_dev(self, scans_ptr, offsets_ptr, B, total_points, tf_ptr, tf_stride, max_d2, d2_ptr, stats_ptr,
+                       shared_scan=False, stream=None, ctx=None):
+        """ndt_fit_points_batch_dev: device addresses (d2_ptr or stats_ptr may be None); asynchronous.  tf_ptr = the address of
+        a record's T00 with tf_stride = RESULT_BYTES reads the transforms of a launch's records where they lie."""
+        cx = ctx if ctx is not None else self.ctx
+        cx.check(lib().ndt_fit_points_batch_dev(cx.h, self.h, scans_ptr, offsets_ptr, B, total_points, int(shared_scan), tf_ptr,
+                                                tf_stride, float(max_d2), d2_ptr, stats_ptr, stream), "ndt_fit_points_batch_dev")
+
+    def relocalize(self, scan, lattice, top_k=16, local_max=True, want_scores=False, dev_ptr=None, n=None, stride=8, max_d2=None):
         """ndt_relocalize (or, with dev_ptr / n / stride, ndt_relocalize_dev): sweep the lattice, pick top_k candidates,
         refine them with the shared-scan match -> dict(cand_index [m] uint64, cand_score [m], records [m] RESULT_DTYPE,
-        best (index of the lowest cost `converged ? fitness : 1e7`, -1 when m == 0), scores (the whole volume or None))."""
+        best (index of the lowest cost `converged ? fitness : 1e7`, -1 when m == 0), scores (the whole volume or None)).
+        max_d2 (host scans only): the candidates are ranked again by `converged ? ranged fitness : 1e7` -- getFitnessScore
+        with max_range, from ONE fit_points call with shared_scan on the candidates' records -- ties to the higher n_in, then
+        the lower index; `best` is that ranking's, and the dict also holds fit_stats and best_unbounded (the C call's)."""
+        if max_d2 is not None and dev_ptr is not None:
+            raise ValueError("relocalize: max_d2 needs the scan in host memory")
         prm = RelocParams(lattice, int(top_k), int(bool(local_max)))
         idx = np.zeros(top_k, dtype=np.uint64); cs = np.zeros(top_k, dtype=np.float64)
         rec = np.zeros(top_k, dtype=RESULT_DTYPE)
@@ -884,7 +953,16 @@ class Map:
                                       cs.ctypes.data, rec.ctypes.data, C.byref(m), C.byref(best), volp)
         self.ctx.check(rc, "ndt_relocalize")
         k = m.value
-        return dict(cand_index=idx[:k].copy(), cand_score=cs[:k].copy(), records=rec[:k].copy(), best=best.value, scores=vol)
+        out = dict(cand_index=idx[:k].copy(), cand_score=cs[:k].copy(), records=rec[:k].copy(), best=best.value, scores=vol)
+        if max_d2 is not None:
+            out["best_unbounded"] = out["best"]
+            out["fit_stats"] = np.zeros(0, dtype=FIT_STATS_DTYPE)
+            if k > 0:
+                _, st = self.fit_points(scan, np.array([0, len(scan)], dtype=np.uint64), out["records"], max_d2=max_d2,
+                                        shared_scan=True, want_d2=False)
+                out["fit_stats"] = st
+                out["best"] = rerank(out["records"], st)
+        return out
 
     def close(self):
         if self.h:

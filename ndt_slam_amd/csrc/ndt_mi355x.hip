@@ -45,6 +45,7 @@ thread_local std::string g_last_error;
 #include "ndt_point.hip.h"
 #include "ndt_optimizer.hip.h"
 #include "ndt_fitness.hip.h"
+#include "ndt_fit_points.hip.h"
 #include "ndt_match.hip.h"
 #include "ndt_map_build.hip.h"
 #include "ndt_front.hip.h"
@@ -199,6 +200,8 @@ struct ndt_ctx {
   DevBuf<int> d_map_of;                                // ndt_align_batch_multi: the host map_of's copy
   DevBuf<float> d_fit;                                 // squared distance to the nearest map point, per scan point (shared_scan launches)
   DevBuf<FitPart> d_fit_part;                          // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
+  DevBuf<FitPtsPart> d_fit_pts;                        // ndt_fit_points_batch_dev: FitPtsPart per chunk of 64 scan points in input order (ndt_fit_points.hip.h)
+  StagedUpload<unsigned char> fp_tab;                  // ndt_fit_points_batch: offsets, transforms and scans of the call, one upload
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
   DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
@@ -3039,6 +3042,123 @@ int ndt_relocalize_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_de
                        uint64_t *cand_index, double *cand_score, ndt_result *records, int *n_cand, int *best, double *scores_host) {
   return relocalize_impl(ctx, map, nullptr, scan_xy_dev, n, stride, prm, cand_index, cand_score, records, n_cand, best, scores_host,
                          "ndt_relocalize_dev");
+}
+
+}  // extern "C"
+
+// ---- ndt_fit_points_batch_dev / ndt_fit_points_batch: per-point nearest distances and the ranged fitness ----
+
+namespace {
+
+// The refusals both forms start with (synchronous, nothing queued or written).
+int fit_points_check(ndt_ctx *ctx, const ndt_map *map, const void *scans, const void *offsets, int B, const void *tf,
+                     size_t tf_stride, double max_d2, const void *d2, const void *stats, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!map || !scans || !offsets || !tf) return fail(ctx, NDT_E_ARG, f + ": NULL map, scans, offsets or tf");
+  if (!d2 && !stats) return fail(ctx, NDT_E_ARG, f + ": d2 and stats are both NULL");
+  if (B < 1) return fail(ctx, NDT_E_ARG, f + ": need B >= 1");
+  if (!map->ctx || !map->view.cent) return fail(ctx, NDT_E_ARG, f + ": the map was never built");
+  if (map->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the map was built on another device");
+  if (tf_stride < 16 || (tf_stride & 3)) return fail(ctx, NDT_E_ARG, f + ": bad tf_stride_bytes (need >= 16 and % 4 == 0)");
+  if (!(max_d2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_d2 is NaN or negative");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return NDT_OK;
+}
+
+// The two kernels on st, inside the caller's scratch bracket (d_fit_pts): behind the map's build, entered in the context's
+// ring as a reader of the map the way the score sweep is (queue_score) -- on another stream than the one that carries the
+// map's builds it is, to a build, what a deferred launch is.  The ring's events ride on the search kernel's dispatch.
+int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
+                     size_t total_points, int shared_scan, const void *tf, size_t tf_stride, double max_d2, float *d2,
+                     ndt_fit_stats *stats) {
+  int rc;
+  const size_t n_parts = shared_scan ? (size_t)B * ((total_points + 63) / 64) : total_points / 64 + (size_t)B + 1;
+  if (stats && (rc = ctx->d_fit_pts.ensure(ctx, n_parts))) return rc;        // (the call's one allocation, in front of its first kernel)
+  const bool foreign = st != map->ctx->stream;
+  if (foreign) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  // queue_fitness's grid: workgroup w -> (match, block of the match) in fit_block_of; NDT_OPT_WORKGROUPS bounds it
+  const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
+  const size_t b8 = ((size_t)B + 7) / 8 * 8;
+  size_t gx = std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
+  if (ctx->workgroups > 0) gx = std::max<size_t>(1, std::min<size_t>(gx, (size_t)ctx->workgroups / b8));
+  FitPtsPart *parts = stats ? ctx->d_fit_pts.p : nullptr;
+  LaunchRing &R = ctx->ring;
+  Event *evr = R.events(R.launches);
+  with_bool(map->prm.transform_sse != 0, [&](auto S) {
+    hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value>), dim3((unsigned)(gx * b8)), dim3(256), 0, st, evr[0], evr[1], 0, map->view,
+                          reinterpret_cast<const float2 *>(scans), offsets, B, shared_scan, (const unsigned char *)tf, tf_stride, max_d2, d2,
+                          parts, (int)gx);
+  });
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
+  // the search is queued: whatever happens below, the call has its place in the ring and in the map's readers
+  if (stats) {
+    fit_points_close_kernel<<<dim3((unsigned)(((size_t)B + 3) / 4)), dim3(256), 0, st>>>(offsets, B, shared_scan, parts, stats);
+    e = hipGetLastError();
+  }
+  const hipError_t e2 = hipEventRecord(evr[2], st);
+  LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
+  R.enter(ctx, &list, 1, foreign);
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: hipEventRecord: ") + hipGetErrorString(e2));
+  return NDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_fit_points_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_dev, const uint64_t *offsets_dev, int B,
+                             size_t total_points, int shared_scan, const float *tf_dev, size_t tf_stride_bytes, double max_d2,
+                             float *d2_dev, ndt_fit_stats *stats_dev, void *stream) {
+  int rc = fit_points_check(ctx, map, scans_xy_dev, offsets_dev, B, tf_dev, tf_stride_bytes, max_d2, d2_dev, stats_dev, "ndt_fit_points_batch_dev");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_fit_points(ctx, map, st, scans_xy_dev, (const unsigned long long *)offsets_dev, B, total_points, shared_scan, tf_dev,
+                             tf_stride_bytes, max_d2, d2_dev, stats_dev)))
+    return rc;
+  return scope.close();
+}
+
+int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_host, const uint64_t *offsets_host, int B,
+                         int shared_scan, const float *tf_host, size_t tf_stride_bytes, double max_d2, float *d2_host,
+                         ndt_fit_stats *stats_host) {
+  int rc = fit_points_check(ctx, map, scans_xy_host, offsets_host, B, tf_host, tf_stride_bytes, max_d2, d2_host, stats_host, "ndt_fit_points_batch");
+  if (rc) return rc;
+  const size_t nscan = shared_scan ? 1 : (size_t)B;
+  for (size_t b = 0; b < nscan; ++b)
+    if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, "ndt_fit_points_batch: offsets not monotone");
+  const size_t ntot = (size_t)offsets_host[nscan];
+  const size_t n_d2 = shared_scan ? (size_t)B * (size_t)(offsets_host[1] - offsets_host[0]) : ntot;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  // one upload: the offsets, the transforms (packed: 16 bytes each) and the scans, staged in pinned memory
+  const size_t o_tf = align256((nscan + 1) * 8), o_scan = o_tf + align256((size_t)B * 16), bytes = o_scan + ntot * 8;
+  if ((rc = ctx->fp_tab.reserve(ctx, bytes))) return rc;
+  if ((rc = ctx->d_scan.ensure(ctx, bytes))) return rc;
+  if (d2_host && (rc = ctx->d_fit.ensure(ctx, n_d2 + 4))) return rc;
+  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, (size_t)B * sizeof(ndt_fit_stats)))) return rc;
+  unsigned char *h = ctx->fp_tab.h.p, *d = ctx->d_scan.p;
+  memcpy(h, offsets_host, (nscan + 1) * 8);
+  for (int b = 0; b < B; ++b) memcpy(h + o_tf + (size_t)b * 16, (const unsigned char *)tf_host + (size_t)b * tf_stride_bytes, 16);
+  if (ntot) memcpy(h + o_scan, scans_xy_host, ntot * 8);
+  HIP_TRY(ctx, ctx->fp_tab.upload(d, 0, bytes, st));
+  float *d_d2 = d2_host ? ctx->d_fit.p : nullptr;
+  ndt_fit_stats *d_stats = stats_host ? (ndt_fit_stats *)ctx->d_tmp.p : nullptr;
+  if ((rc = queue_fit_points(ctx, map, st, (const float *)(d + o_scan), (const unsigned long long *)d, B, ntot, shared_scan, d + o_tf, 16,
+                             max_d2, d_d2, d_stats)))
+    return rc;
+  if (d2_host && n_d2) HIP_TRY(ctx, hipMemcpyAsync(d2_host, d_d2, n_d2 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, (size_t)B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
 }
 
 }  // extern "C"

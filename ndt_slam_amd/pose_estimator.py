@@ -169,21 +169,26 @@ class PoseEstimator:
                 cov = np.full((3, 3), np.inf)
         return cost, est, cov
 
-    def relocalize(self, lattice, top_k=16):
+    def relocalize(self, lattice, top_k=16, max_d2=None):
         """What the reference lacks: the pose of the current scan pair without an initial guess (its answer to a failed
         match is the odometry fallback of src/ScanMatcher.cpp:60-66).  Pre-filters the source and rebuilds the target as
         estimatePose does, sweeps `lattice` (capi.PoseLattice, metres / radians in the target's frame), refines the top_k
         local maxima (ndt_relocalize) and returns (estPose, cost) of the lowest cost, in estimatePose's units: degrees,
         and the fitness score or NOT_CONVERGED_COST.  (Pose2D(), NOT_CONVERGED_COST) when the scan meets the map nowhere
-        on the lattice or the library refuses."""
+        on the lattice or the library refuses.
+        max_d2 (m^2): the candidates are ranked by getFitnessScore(max_range) with that SQUARED range instead of the
+        unbounded mean (Map.relocalize), and the cost returned is the ranged fitness; for a map that covers the scan only
+        in part."""
         filtered = self.prepareEstimate()
         try:
-            out = self._map.relocalize(filtered, lattice, top_k=top_k)
+            out = self._map.relocalize(filtered, lattice, top_k=top_k, max_d2=max_d2)
         except capi.NdtError:
             return Pose2D(), NOT_CONVERGED_COST
         if out["best"] < 0:
             return Pose2D(), NOT_CONVERGED_COST
         cost, est, _ = self.finishEstimate(out["records"][out["best"]])
+        if max_d2 is not None and cost != NOT_CONVERGED_COST:
+            cost = float(out["fit_stats"][out["best"]]["fitness"])
         return est, cost
 
 
