@@ -732,6 +732,90 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
                          const float *tf_host, size_t tf_stride_bytes, double max_d2,
                          float *d2_host, ndt_fit_stats *stats_host);
 
+/* ---- Occupancy grids, ray-cast from scans on the device -----------------------------------------------------------------
+ * The reference writes poses and point clouds; it has no counterpart to these calls.  A grid holds, per cell, how many beams
+ * ended in it (hit) and how many passed through it (pass).  Everything is integer addition, so a grid's counters and a
+ * call's stats are a function of (geometry, beams) alone, to the last bit: they do not depend on the order of scans or beams,
+ * on B, on how many calls the beams were spread over, or on NDT_OPT_WORKGROUPS.
+ *
+ * Geometry.  Cell (ix, iy) covers [x0 + ix res, x0 + (ix + 1) res) x [y0 + iy res, y0 + (iy + 1) res); cells are row-major,
+ * index iy * nx + ix.  The cell of a point is ix = floor(((double)x - x0) / res): one rounded fp64 subtraction, one rounded
+ * fp64 division, then floor; iy likewise.  ndt_occ_cell IS the definition (as ndt_lattice_pose is for lattices; host only, no
+ * context): the device forms the same integers.  It saturates at +-2^62 and refuses a non-finite x or y.  Refusals of a
+ * geometry: NDT_E_ARG for a res that is not positive and finite, a non-finite origin, nx or ny below 1; NDT_E_GRID for more
+ * than 2^28 cells.
+ *
+ * Cells.  Two uint32_t counters {hit, pass}, interleaved, 8 bytes per cell; zero after create and after clear.  Counters wrap
+ * modulo 2^32: nothing saturates.
+ *
+ * A beam runs from the origin o (two doubles) to an end point e (one float32 map-frame point, widened to double).  It is
+ * SKIPPED -- nothing written, counted in n_skipped -- when a coordinate of o or e is not finite; when dx dx + dy dy >
+ * max_range2, dx = (double)ex - ox (products and sum each rounded, no fma; max_range2 is the SQUARED range, as max_d2 is in
+ * ndt_fit_points_batch; DBL_MAX = no limit); when a cell index of either endpoint lies outside [-2^30, 2^30]; when its length
+ * in cells L exceeds 65536; when its scan's grid_of entry is out of range.
+ *
+ * The walk, in integers only.  (X0, Y0) = cell of o, (X1, Y1) = cell of e, dx = |X1 - X0|, dy = |Y1 - Y0|, sx, sy the signs,
+ * L = max(dx, dy), m = min(dx, dy).  The beam visits k = 0 .. L - 1: the major coordinate is start + s k, the minor one
+ * start + s floor((2 k m + L - 1) / (2 L)) in 64-bit integers; dx == dy counts as x-major.  Every visited cell inside the grid
+ * gets pass += 1.  The end cell (X1, Y1) is not among the visits: it gets hit += 1 if it lies inside the grid.  L = 0 is a hit
+ * only.  Cells outside the grid are not written; the beam is not otherwise clipped or dropped.  This closed form is the
+ * all-octant integer Bresenham line from (X0, Y0) to (X1, Y1), end cell excluded: x-major, e = 2 dy - dx; dx times: visit;
+ * if e > 0 { y += sy; e -= 2 dx; } e += 2 dy; x += sx (y-major: symmetric).
+ *
+ * Stats of one call (overwritten, not accumulated): n_beams seen, n_hit hits written, n_pass pass increments written,
+ * n_skipped beams skipped.
+ *
+ * Render.  n = (uint64_t)hit + pass; the value is -1 when n < min_obs (min_obs >= 1), else (int8_t)((200 hit + n) / (2 n)):
+ * 100 hit / n rounded half up, 0 .. 100, the convention of ROS's OccupancyGrid.
+ *
+ * ndt_occ_integrate_dev.  Scan b is the packed float2 map-frame points [offsets[b], offsets[b + 1]) -- what
+ * ndt_scan_to_map_batch_dev writes -- and goes into occs[grid_of[b]] (grid_of_dev == NULL: all into occs[0]).  Origin b is two
+ * doubles at (const char *)origins + b * origin_stride_bytes; the stride is a multiple of 8 and at least 16, so 24 takes the
+ * (tx, ty, th) pose triples of ndt_scan_to_map_batch_dev, or a session set's last poses, where they lie.  An empty scan is
+ * legal.  Asynchronous on `stream` (NULL = the context's), no host wait; one table upload (the grids, from pinned staging) and
+ * two launches whatever B and n_occ are; the scratch (table, runs) lies inside the context's scratch bracket.
+ * ndt_occ_integrate: the same from host memory, synchronous: one upload, the _dev call, the stats read back.
+ *
+ * Ordering.  A grid remembers the event behind its last writer (integrate, clear; create returns with the grid zeroed); any call that touches the grid on
+ * another stream waits for that event first.  Calls of one context are otherwise serialised as all its calls are (the scratch
+ * bracket).  Grids are destroyed before their context, like maps.
+ *
+ * Refusals (synchronous, nothing queued or written; the text names the first offender; NDT_E_ARG): a NULL context ("null
+ * context", checked first); NULL arrays; n_occ < 1 or B < 1; a NULL grid, a grid of another context, the same grid twice; an
+ * origin stride below 16 or not a multiple of 8; max_range2 NaN or negative; min_obs < 1; an open ndt_map_rebuild_begin on the
+ * context; host form: offsets that decrease. */
+typedef struct ndt_occ ndt_occ;
+typedef struct ndt_occ_geometry { double x0, y0, res; int nx, ny; } ndt_occ_geometry;            /* 32 bytes */
+typedef struct ndt_occ_stats { uint64_t n_beams, n_hit, n_pass, n_skipped; } ndt_occ_stats;    /* 32 bytes */
+int ndt_occ_cell(const ndt_occ_geometry *geometry, double x, double y, int64_t *ix, int64_t *iy);
+int ndt_occ_create(ndt_ctx *ctx, const ndt_occ_geometry *geometry, ndt_occ **out);
+int ndt_occ_destroy(ndt_occ *occ);
+/* Asynchronous memset on `stream` (NULL = the context's). */
+int ndt_occ_clear(ndt_ctx *ctx, ndt_occ *occ, void *stream);
+int ndt_occ_geometry_get(const ndt_occ *occ, ndt_occ_geometry *out);
+/* The interleaved {hit, pass} device array, 2 * nx * ny uint32_t. */
+int ndt_occ_view(const ndt_occ *occ, const uint32_t **cells_dev);
+int ndt_occ_integrate_dev(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_dev, const float *xy_dev,
+                          const uint64_t *offsets_dev, int B, size_t total_points, const double *origins_dev,
+                          size_t origin_stride_bytes, double max_range2, ndt_occ_stats *stats_dev, void *stream);
+int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_host, const float *xy_host,
+                      const uint64_t *offsets_host, int B, const double *origins_host, size_t origin_stride_bytes,
+                      double max_range2, ndt_occ_stats *stats_host);
+/* out: nx * ny int8_t, row-major.  _dev: asynchronous on `stream`; the host form is synchronous. */
+int ndt_occ_render_dev(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_dev, void *stream);
+int ndt_occ_render(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_host);
+/* Synchronous read-back of the counters, nx * ny uint32_t each; either pointer may be NULL, not both. */
+int ndt_occ_counts(ndt_ctx *ctx, ndt_occ *occ, uint32_t *hit_host, uint32_t *pass_host);
+/* Session i is taken when (which == NULL or which[i] != 0) and it has started: its NEWEST scan -- the resampled scan in the
+ * map frame as the last step that session took part in added it to the map -- goes into occs[i], from the origin at session
+ * i's row of the set's resident last poses.  One table upload and the launches of ndt_occ_integrate_dev on the context's
+ * stream; stats_host (may be NULL) is the call's one read-back, and with it the call waits.  Reads the set's state and
+ * changes none of it.  Pass the step records' `stepped` flags as `which`: a session taken that did not step has its last
+ * scan integrated AGAIN.  NDT_E_ARG: a NULL occs, a NULL or foreign entry of occs for a session that is taken, the same grid
+ * for two of them, max_range2 NaN or negative.  NDT_E_HIP: a dead set. */
+int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, double max_range2,
+                               ndt_occ_stats *stats_host);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

@@ -112,6 +112,27 @@ FIT_STATS_DTYPE = np.dtype([("fitness", "f8"), ("fitness_all", "f8"), ("n_in", "
 DBL_MAX = float(np.finfo(np.float64).max)
 
 
+class OccGeometry(C.Structure):
+    """ndt_occ_geometry (include/ndt_mi355x.h): cell (ix, iy) covers [x0 + ix res, x0 + (ix + 1) res) x [y0 + iy res, ...)."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("res", C.c_double), ("nx", C.c_int), ("ny", C.c_int)]
+
+    def cell(self, x, y):
+        """ndt_occ_cell: the (ix, iy) of a point -- the definition the device follows."""
+        ix, iy = C.c_int64(), C.c_int64()
+        rc = lib().ndt_occ_cell(C.byref(self), float(x), float(y), C.byref(ix), C.byref(iy))
+        if rc != 0:
+            raise NdtError("ndt_occ_cell failed (%d): %s" % (rc, lib().ndt_last_error(None).decode()))
+        return ix.value, iy.value
+
+
+class OccStats(C.Structure):
+    """ndt_occ_stats: one integrate call's counts."""
+    _fields_ = [("n_beams", C.c_uint64), ("n_hit", C.c_uint64), ("n_pass", C.c_uint64), ("n_skipped", C.c_uint64)]
+
+
+OCC_STATS_DTYPE = np.dtype([("n_beams", "u8"), ("n_hit", "u8"), ("n_pass", "u8"), ("n_skipped", "u8")], align=True)
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -146,6 +167,9 @@ EXPORTS = [
     "ndt_lattice_size", "ndt_lattice_pose", "ndt_score_poses", "ndt_score_poses_dev", "ndt_score_lattice_dev",
     "ndt_lattice_select_dev", "ndt_relocalize", "ndt_relocalize_dev",
     "ndt_fit_points_batch", "ndt_fit_points_batch_dev",
+    "ndt_occ_cell", "ndt_occ_create", "ndt_occ_destroy", "ndt_occ_clear", "ndt_occ_geometry_get", "ndt_occ_view",
+    "ndt_occ_integrate_dev", "ndt_occ_integrate", "ndt_occ_render_dev", "ndt_occ_render", "ndt_occ_counts",
+    "ndt_sessions_occ_integrate",
 ]
 
 
@@ -232,6 +256,19 @@ def lib():
     L.ndt_relocalize_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
     L.ndt_fit_points_batch_dev.argtypes = [vp, vp, vp, vp, i, sz, i, vp, sz, C.c_double, vp, vp, vp]
     L.ndt_fit_points_batch.argtypes = [vp, vp, vp, vp, i, i, vp, sz, C.c_double, vp, vp]
+    d = C.c_double
+    L.ndt_occ_cell.argtypes = [C.POINTER(OccGeometry), d, d, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.ndt_occ_create.argtypes = [vp, C.POINTER(OccGeometry), C.POINTER(vp)]
+    L.ndt_occ_destroy.argtypes = [vp]
+    L.ndt_occ_clear.argtypes = [vp, vp, vp]
+    L.ndt_occ_geometry_get.argtypes = [vp, C.POINTER(OccGeometry)]
+    L.ndt_occ_view.argtypes = [vp, C.POINTER(vp)]
+    L.ndt_occ_integrate_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, vp, sz, d, vp, vp]
+    L.ndt_occ_integrate.argtypes = [vp, vp, i, vp, vp, vp, i, vp, sz, d, vp]
+    L.ndt_occ_render_dev.argtypes = [vp, vp, C.c_uint32, vp, vp]
+    L.ndt_occ_render.argtypes = [vp, vp, C.c_uint32, vp]
+    L.ndt_occ_counts.argtypes = [vp, vp, vp, vp]
+    L.ndt_sessions_occ_integrate.argtypes = [vp, vp, vp, d, vp]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -737,6 +774,19 @@ class Sessions:
                                                      off.ctypes.data, C.byref(k)), "ndt_sessions_global_map")
         return out, [out[int(off[j]):int(off[j + 1])] for j in range(k.value)]
 
+    def occ_integrate(self, grids, which=None, max_range2=DBL_MAX):
+        """ndt_sessions_occ_integrate: every taken session's newest map-frame scan into its grid (grids: one OccGrid or None
+        per session), from the session's resident pose -> the call's OCC_STATS_DTYPE record.  Pass the step records' `stepped`
+        as `which`: a session taken that did not step has its last scan integrated again."""
+        if len(grids) != self.n:
+            raise ValueError("occ_integrate needs one grid (or None) per session")
+        hs = (C.c_void_p * self.n)(*[g.h if g is not None else None for g in grids])
+        w = self._active(which)
+        st = np.zeros(1, dtype=OCC_STATS_DTYPE)
+        self.ctx.check(lib().ndt_sessions_occ_integrate(self.h, hs, None if w is None else w.ctypes.data, float(max_range2),
+                                                        st.ctypes.data), "ndt_sessions_occ_integrate")
+        return st[0]
+
     def stats(self):
         st = SessionsStats()
         self.ctx.check(lib().ndt_sessions_get_stats(self.h, C.byref(st)), "ndt_sessions_get_stats")
@@ -967,6 +1017,105 @@ class Map:
     def close(self):
         if self.h:
             lib().ndt_map_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _occ_handles(grids):
+    grids = list(grids)
+    return (C.c_void_p * len(grids))(*[g.h for g in grids]), len(grids)
+
+
+def integrate_occ(ctx, grids, scans, offsets, origins, grid_of=None, max_range2=DBL_MAX):
+    """ndt_occ_integrate: scan b = the float32 map-frame points [offsets[b], offsets[b + 1]) of `scans`, ray-cast from
+    origins[b] (a [B, 2] or [B, 3] float64 array: the first two of each row) into grids[grid_of[b]] (None: all into grids[0])
+    -> the call's OCC_STATS_DTYPE record."""
+    scans = _f32c(scans)
+    if scans.size == 0:
+        scans = np.zeros((1, 2), dtype=np.float32)     # (an address for a batch of empty scans)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    origins = np.ascontiguousarray(origins, dtype=np.float64)
+    B = len(offsets) - 1
+    if origins.ndim != 2 or origins.shape[0] != B or origins.shape[1] < 2:
+        raise ValueError("origins needs one row of at least two doubles per scan")
+    gof = None if grid_of is None else np.ascontiguousarray(grid_of, dtype=np.int32)
+    if gof is not None and len(gof) != B:
+        raise ValueError("grid_of needs one entry per scan")
+    hs, n = _occ_handles(grids)
+    st = np.zeros(1, dtype=OCC_STATS_DTYPE)
+    ctx.check(lib().ndt_occ_integrate(ctx.h, hs, n, None if gof is None else gof.ctypes.data, scans.ctypes.data, offsets.ctypes.data,
+                                      B, origins.ctypes.data, origins.strides[0], float(max_range2), st.ctypes.data),
+              "ndt_occ_integrate")
+    return st[0]
+
+
+def integrate_occ_dev(ctx, grids, grid_of_ptr, xy_ptr, offsets_ptr, B, total_points, origins_ptr, origin_stride=24,
+                      max_range2=DBL_MAX, stats_ptr=None, stream=None):
+    """ndt_occ_integrate_dev: device addresses (grid_of_ptr None: every scan into grids[0]; stats_ptr None: no stats);
+    asynchronous on `stream` (None: the context's)."""
+    hs, n = _occ_handles(grids)
+    ctx.check(lib().ndt_occ_integrate_dev(ctx.h, hs, n, grid_of_ptr, xy_ptr, offsets_ptr, B, total_points, origins_ptr, origin_stride,
+                                          float(max_range2), stats_ptr, stream), "ndt_occ_integrate_dev")
+
+
+class OccGrid:
+    """ndt_occ: an occupancy grid of {hit, pass} counters on the device (include/ndt_mi355x.h)."""
+
+    def __init__(self, ctx, geometry):
+        self.ctx = ctx
+        self.geometry = OccGeometry(geometry.x0, geometry.y0, geometry.res, geometry.nx, geometry.ny)
+        self.h = C.c_void_p()
+        ctx.check(lib().ndt_occ_create(ctx.h, C.byref(self.geometry), C.byref(self.h)), "ndt_occ_create")
+
+    @property
+    def shape(self):
+        return (self.geometry.ny, self.geometry.nx)
+
+    def cells_ptr(self):
+        """ndt_occ_view: the device address of the interleaved {hit, pass} uint32 array."""
+        p = C.c_void_p()
+        self.ctx.check(lib().ndt_occ_view(self.h, C.byref(p)), "ndt_occ_view")
+        return p.value
+
+    def integrate(self, scans, offsets, origins, max_range2=DBL_MAX):
+        """integrate_occ with this grid alone."""
+        return integrate_occ(self.ctx, [self], scans, offsets, origins, None, max_range2)
+
+    def integrate_dev(self, xy_ptr, offsets_ptr, B, total_points, origins_ptr, origin_stride=24, max_range2=DBL_MAX,
+                      stats_ptr=None, stream=None):
+        """integrate_occ_dev with this grid alone: device addresses; asynchronous."""
+        integrate_occ_dev(self.ctx, [self], None, xy_ptr, offsets_ptr, B, total_points, origins_ptr, origin_stride, max_range2,
+                          stats_ptr, stream)
+
+    def render(self, min_obs=1):
+        """ndt_occ_render -> [ny, nx] int8: 100 hit / n rounded half up, -1 below min_obs observations."""
+        out = np.zeros(self.shape, dtype=np.int8)
+        self.ctx.check(lib().ndt_occ_render(self.ctx.h, self.h, int(min_obs), out.ctypes.data), "ndt_occ_render")
+        return out
+
+    def render_dev(self, out_ptr, min_obs=1, stream=None):
+        self.ctx.check(lib().ndt_occ_render_dev(self.ctx.h, self.h, int(min_obs), out_ptr, stream), "ndt_occ_render_dev")
+
+    def counts(self):
+        """ndt_occ_counts -> (hit, pass), [ny, nx] uint32 each."""
+        hit = np.zeros(self.shape, dtype=np.uint32)
+        pas = np.zeros(self.shape, dtype=np.uint32)
+        self.ctx.check(lib().ndt_occ_counts(self.ctx.h, self.h, hit.ctypes.data, pas.ctypes.data), "ndt_occ_counts")
+        return hit, pas
+
+    def clear(self, stream=None):
+        self.ctx.check(lib().ndt_occ_clear(self.ctx.h, self.h, stream), "ndt_occ_clear")
+
+    def close(self):
+        if self.h:
+            lib().ndt_occ_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

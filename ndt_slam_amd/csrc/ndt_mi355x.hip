@@ -52,6 +52,7 @@ thread_local std::string g_last_error;
 #include "ndt_localmap.hip.h"
 #include "ndt_resample.hip.h"
 #include "ndt_score.hip.h"
+#include "ndt_occupancy.hip.h"
 
 }  // namespace
 
@@ -202,6 +203,8 @@ struct ndt_ctx {
   DevBuf<FitPart> d_fit_part;                          // FitPart per chunk of 64 scan points (ndt_fitness.hip.h)
   DevBuf<FitPtsPart> d_fit_pts;                        // ndt_fit_points_batch_dev: FitPtsPart per chunk of 64 scan points in input order (ndt_fit_points.hip.h)
   StagedUpload<unsigned char> fp_tab;                  // ndt_fit_points_batch: offsets, transforms and scans of the call, one upload
+  DevBuf<unsigned char> d_occ;                         // ndt_occ_integrate_dev: the call's table of grids, its count of runs and the runs (ndt_occupancy.hip.h)
+  StagedUpload<unsigned char> occ_tab, occ_up;         // ... the table's staging; ndt_occ_integrate: offsets, grid_of, origins and scans of the call, one upload
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
   DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
@@ -274,6 +277,11 @@ struct ndt_ctx {
   Event ev_scratch;                   // the scratch bracket (ScratchScope)
   Stream fit_stream;                  // NDT_OPT_DEFER_FITNESS (created on first use)
   LaunchRing ring;
+  // Occupancy grids: the event behind each of the last kOccEv calls that wrote a grid (integrate, clear, create), recorded on
+  // that call's stream; call k's is occ_ev[k % kOccEv].  A grid remembers the number of its last writer (ndt_occ::wseq).
+  static constexpr int kOccEv = 8;
+  Event occ_ev[kOccEv];
+  unsigned long long occ_seq = 0;
 };
 
 struct ndt_map {
@@ -3158,6 +3166,355 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, (size_t)B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
   if ((rc = scope.close())) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+}  // extern "C"
+
+// ---- ndt_occ_*: occupancy grids of {hit, pass} counters, ray-cast from scans (kernels in ndt_occupancy.hip.h) ----
+
+struct ndt_occ {
+  ndt_ctx *ctx = nullptr;
+  int device = 0;
+  ndt_occ_geometry g{};
+  size_t n_cells = 0;
+  DevBuf<unsigned> cells;                     // 2 * n_cells: {hit, pass} per cell
+  // the last call that wrote the grid: its number among the context's writers (ndt_ctx::occ_ev) and its stream
+  bool written = false;
+  unsigned long long wseq = 0;
+  hipStream_t wstream = nullptr;
+};
+
+namespace {
+
+int occ_geometry_check(ndt_ctx *ctx, const ndt_occ_geometry *g, const char *fn) {
+  const std::string f(fn);
+  if (!g) return fail(ctx, NDT_E_ARG, f + ": NULL geometry");
+  if (!(g->res > 0.0) || !std::isfinite(g->res)) return fail(ctx, NDT_E_ARG, f + ": res is not positive and finite");
+  if (!std::isfinite(g->x0) || !std::isfinite(g->y0)) return fail(ctx, NDT_E_ARG, f + ": the origin is not finite");
+  if (g->nx < 1 || g->ny < 1) return fail(ctx, NDT_E_ARG, f + ": nx or ny below 1");
+  if ((uint64_t)g->nx * (uint64_t)g->ny > ((uint64_t)1 << 28)) return fail(ctx, NDT_E_GRID, f + ": more than 2^28 cells");
+  return NDT_OK;
+}
+
+// The event of the context's writer number k.  A writer that has left the ring is covered by the latest one: every writer
+// opens the scratch bracket, so each is ordered behind the one before it, on whatever stream.
+hipEvent_t occ_event_of(ndt_ctx *ctx, unsigned long long k) {
+  const unsigned long long last = ctx->occ_seq - 1;
+  return ctx->occ_ev[(last - k >= (unsigned long long)ndt_ctx::kOccEv ? last : k) % ndt_ctx::kOccEv];
+}
+
+// A call on st is about to touch the grid: behind the grid's last writer, if that was on another stream.
+int occ_touch(ndt_ctx *ctx, const ndt_occ *o, hipStream_t st) {
+  if (o->written && o->wstream != st) HIP_TRY(ctx, hipStreamWaitEvent(st, occ_event_of(ctx, o->wseq), 0));
+  return NDT_OK;
+}
+
+// The call on st has queued its writes of occs[0 .. n) (NULL entries: not written): one event for all of them.
+int occ_wrote(ndt_ctx *ctx, ndt_occ *const *occs, int n, hipStream_t st) {
+  Event &ev = ctx->occ_ev[ctx->occ_seq % ndt_ctx::kOccEv];
+  if (!ev) { const int rc = ev.create(ctx, hipEventDisableTiming); if (rc) return rc; }
+  HIP_TRY(ctx, hipEventRecord(ev, st));
+  for (int i = 0; i < n; ++i)
+    if (occs[i]) { occs[i]->written = true; occs[i]->wseq = ctx->occ_seq; occs[i]->wstream = st; }
+  ctx->occ_seq++;
+  return NDT_OK;
+}
+
+// One call's beams: the batch forms (xy, offsets, grid_of: device arrays; rows = the grids) or the sessions form (xy ==
+// nullptr: row b is scan b and its grid).
+struct OccCall {
+  ndt_occ *const *occs; int n_rows;           // NULL entries (sessions form): rows not taken
+  const OccRow *own;                          // sessions form: pts / n per row (host), else nullptr
+  const int *grid_of; const float *xy; const unsigned long long *offsets; int B; size_t total_points;
+  const void *origins; size_t origin_stride; double max_range2; ndt_occ_stats *stats;
+};
+
+// The table's upload and the two kernels on st, inside the caller's scratch bracket (d_occ); the grids are entered as written.
+int queue_occ(ndt_ctx *ctx, hipStream_t st, const OccCall &C) {
+  int rc;
+  const size_t job_cap = std::min<size_t>(C.total_points / (size_t)kOccRun + (size_t)C.B, (size_t)UINT32_MAX);
+  Regions R;
+  const size_t o_tab = R.take((size_t)C.n_rows * sizeof(OccRow)), o_nj = R.take(256), o_jobs = R.take(job_cap * sizeof(OccJob));
+  if ((rc = ctx->occ_tab.reserve(ctx, (size_t)C.n_rows * sizeof(OccRow)))) return rc;      // (waits for the previous call's copy)
+  if ((rc = ctx->d_occ.ensure(ctx, R.end))) return rc;
+  for (int i = 0; i < C.n_rows; ++i)
+    if (C.occs[i] && (rc = occ_touch(ctx, C.occs[i], st))) return rc;
+  OccRow *h = reinterpret_cast<OccRow *>(ctx->occ_tab.h.p);
+  for (int i = 0; i < C.n_rows; ++i) {
+    OccRow r{};
+    if (C.occs[i]) {
+      const ndt_occ &o = *C.occs[i];
+      r.cells = o.cells.p; r.x0 = o.g.x0; r.y0 = o.g.y0; r.res = o.g.res; r.nx = o.g.nx; r.ny = o.g.ny;
+      if (C.own) { r.pts = C.own[i].pts; r.n = C.own[i].n; }
+    }
+    h[i] = r;
+  }
+  unsigned char *d = ctx->d_occ.p;
+  HIP_TRY(ctx, ctx->occ_tab.upload(d + o_tab, 0, (size_t)C.n_rows * sizeof(OccRow), st));
+  const OccRow *tab = reinterpret_cast<const OccRow *>(d + o_tab);
+  OccJob *jobs = reinterpret_cast<OccJob *>(d + o_jobs);
+  unsigned *nj = reinterpret_cast<unsigned *>(d + o_nj);
+  unsigned long long *stats = reinterpret_cast<unsigned long long *>(C.stats);
+  occ_jobs_kernel<<<1, 256, 0, st>>>(tab, C.offsets, C.B, jobs, (unsigned)job_cap, nj, stats);
+  // as many workgroups as there can be runs, eight per CU at most (or NDT_OPT_WORKGROUPS): each takes runs in turn
+  const size_t wgs = std::max<size_t>(1, std::min<size_t>(job_cap, ctx->workgroups > 0 ? (size_t)ctx->workgroups : (size_t)ctx->num_cus * 8));
+  occ_integrate_kernel<<<dim3((unsigned)wgs), dim3(kOccRun), 0, st>>>(tab, C.n_rows, C.grid_of, reinterpret_cast<const float2 *>(C.xy), C.offsets,
+                                                                       (const unsigned char *)C.origins, C.origin_stride, C.max_range2, jobs, nj, stats);
+  const hipError_t e = hipGetLastError();
+  // the kernels are queued (or not): either way the grids count as written behind this point of st
+  rc = occ_wrote(ctx, C.occs, C.n_rows, st);
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_occ_integrate: ") + hipGetErrorString(e));
+  return rc;
+}
+
+// The refusals both batch forms start with (synchronous, nothing queued or written).
+int occ_integrate_check(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const void *xy, const void *offsets, int B, const void *origins,
+                        size_t origin_stride, double max_range2, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!occs || !xy || !offsets || !origins) return fail(ctx, NDT_E_ARG, f + ": NULL array (occs, xy, offsets or origins)");
+  if (n_occ < 1 || B < 1) return fail(ctx, NDT_E_ARG, f + ": need n_occ >= 1 and B >= 1");
+  for (int i = 0; i < n_occ; ++i) {
+    if (!occs[i]) return fail(ctx, NDT_E_ARG, f + ": grid " + std::to_string(i) + " is NULL");
+    if (occs[i]->ctx != ctx || occs[i]->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": grid " + std::to_string(i) + " belongs to another context");
+    for (int k = 0; k < i; ++k)
+      if (occs[k] == occs[i]) return fail(ctx, NDT_E_ARG, f + ": grid " + std::to_string(i) + " is given twice (also as grid " + std::to_string(k) + ")");
+  }
+  if (origin_stride < 16 || (origin_stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad origin_stride_bytes (need >= 16 and % 8 == 0)");
+  if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return NDT_OK;
+}
+
+// ... and those of the calls on one grid
+int occ_one_check(ndt_ctx *ctx, const ndt_occ *occ, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!occ) return fail(ctx, NDT_E_ARG, f + ": NULL grid");
+  if (occ->ctx != ctx || occ->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the grid belongs to another context");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return NDT_OK;
+}
+
+int queue_occ_render(ndt_ctx *ctx, const ndt_occ *occ, unsigned min_obs, signed char *out, hipStream_t st) {
+  int rc = occ_touch(ctx, occ, st);
+  if (rc) return rc;
+  occ_render_kernel<<<dim3((unsigned)grid_for(occ->n_cells, 256, ctx->num_cus * 8)), dim3(256), 0, st>>>(
+      reinterpret_cast<const uint2 *>(occ->cells.p), occ->n_cells, min_obs, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_occ_cell(const ndt_occ_geometry *g, double x, double y, int64_t *ix, int64_t *iy) {
+  const int rc = occ_geometry_check(nullptr, g, "ndt_occ_cell");
+  if (rc) return rc;
+  if (!ix || !iy) return fail(nullptr, NDT_E_ARG, "ndt_occ_cell: NULL output");
+  if (!std::isfinite(x) || !std::isfinite(y)) return fail(nullptr, NDT_E_ARG, "ndt_occ_cell: a coordinate is not finite");
+  const double lim = 4611686018427387904.0;      // 2^62
+  const double fx = occ_axis(x, g->x0, g->res), fy = occ_axis(y, g->y0, g->res);
+  *ix = (int64_t)std::max(-lim, std::min(lim, fx));
+  *iy = (int64_t)std::max(-lim, std::min(lim, fy));
+  return NDT_OK;
+}
+
+int ndt_occ_create(ndt_ctx *ctx, const ndt_occ_geometry *g, ndt_occ **out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!out) return fail(ctx, NDT_E_ARG, "ndt_occ_create: NULL out");
+  int rc = occ_geometry_check(ctx, g, "ndt_occ_create");
+  if (rc) return rc;
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_occ_create: an ndt_map_rebuild_begin is open on the context");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ndt_occ *o = new (std::nothrow) ndt_occ;
+  if (!o) return fail(ctx, NDT_E_NOMEM, "ndt_occ_create: out of memory");
+  o->ctx = ctx; o->device = ctx->device; o->g = *g; o->n_cells = (size_t)g->nx * (size_t)g->ny;
+  if ((rc = o->cells.alloc(ctx, o->n_cells * 2 * sizeof(unsigned)))) { delete o; return rc; }
+  hipError_t e = hipMemsetAsync(o->cells.p, 0, o->cells.bytes, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) { delete o; return fail(ctx, NDT_E_HIP, std::string("ndt_occ_create: ") + hipGetErrorString(e)); }
+  *out = o;
+  return NDT_OK;
+}
+
+int ndt_occ_destroy(ndt_occ *o) {
+  if (!o) return NDT_E_ARG;
+  bool ctx_live;
+  { std::lock_guard<std::mutex> lk(g_live_mu); ctx_live = g_live_ctx.count(o->ctx) != 0; }
+  hipError_t e = hipSetDevice(o->device);
+  if (ctx_live) {                               // (a context destroyed first has drained its streams: ndt_map_destroy's rule)
+    e = hipStreamSynchronize(o->ctx->stream);
+    if (o->written) e = hipEventSynchronize(occ_event_of(o->ctx, o->wseq));      // (the last writer may have been on another stream)
+  }
+  (void)e;
+  delete o;
+  return NDT_OK;
+}
+
+int ndt_occ_geometry_get(const ndt_occ *o, ndt_occ_geometry *out) {
+  if (!o || !out) return fail(o ? o->ctx : nullptr, NDT_E_ARG, "ndt_occ_geometry_get: NULL argument");
+  *out = o->g;
+  return NDT_OK;
+}
+
+int ndt_occ_view(const ndt_occ *o, const uint32_t **cells_dev) {
+  if (!o || !cells_dev) return fail(o ? o->ctx : nullptr, NDT_E_ARG, "ndt_occ_view: NULL argument");
+  *cells_dev = o->cells.p;
+  return NDT_OK;
+}
+
+int ndt_occ_clear(ndt_ctx *ctx, ndt_occ *occ, void *stream) {
+  int rc = occ_one_check(ctx, occ, "ndt_occ_clear");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);                     // (no scratch: the bracket orders the call among the context's)
+  if ((rc = scope.open())) return rc;
+  if ((rc = occ_touch(ctx, occ, st))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(occ->cells.p, 0, occ->cells.bytes, st));
+  if ((rc = occ_wrote(ctx, &occ, 1, st))) return rc;
+  return scope.close();
+}
+
+int ndt_occ_integrate_dev(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_dev, const float *xy_dev,
+                          const uint64_t *offsets_dev, int B, size_t total_points, const double *origins_dev,
+                          size_t origin_stride_bytes, double max_range2, ndt_occ_stats *stats_dev, void *stream) {
+  int rc = occ_integrate_check(ctx, occs, n_occ, xy_dev, offsets_dev, B, origins_dev, origin_stride_bytes, max_range2, "ndt_occ_integrate_dev");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_occ(ctx, st, OccCall{occs, n_occ, nullptr, grid_of_dev, xy_dev, (const unsigned long long *)offsets_dev, B, total_points,
+                                       origins_dev, origin_stride_bytes, max_range2, stats_dev})))
+    return rc;
+  return scope.close();
+}
+
+int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_host, const float *xy_host,
+                      const uint64_t *offsets_host, int B, const double *origins_host, size_t origin_stride_bytes,
+                      double max_range2, ndt_occ_stats *stats_host) {
+  int rc = occ_integrate_check(ctx, occs, n_occ, xy_host, offsets_host, B, origins_host, origin_stride_bytes, max_range2, "ndt_occ_integrate");
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b)
+    if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, "ndt_occ_integrate: scan " + std::to_string(b) + ": offsets decrease");
+  const size_t first = (size_t)offsets_host[0], ntot = (size_t)(offsets_host[B] - offsets_host[0]);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  // one upload: the offsets (relative), grid_of, the origins (packed: 16 bytes each) and the scans, staged in pinned memory
+  Regions U;
+  const size_t o_off = U.take(((size_t)B + 1) * 8), o_gof = U.take(grid_of_host ? (size_t)B * 4 : 0), o_org = U.take((size_t)B * 16),
+               o_xy = U.take(ntot * 8);
+  if ((rc = ctx->occ_up.reserve(ctx, U.end))) return rc;
+  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
+  unsigned char *h = ctx->occ_up.h.p, *d = ctx->d_scan.p;
+  for (int b = 0; b <= B; ++b) { const uint64_t v = offsets_host[b] - offsets_host[0]; memcpy(h + o_off + (size_t)b * 8, &v, 8); }
+  if (grid_of_host) memcpy(h + o_gof, grid_of_host, (size_t)B * 4);
+  for (int b = 0; b < B; ++b) memcpy(h + o_org + (size_t)b * 16, (const unsigned char *)origins_host + (size_t)b * origin_stride_bytes, 16);
+  if (ntot) memcpy(h + o_xy, xy_host + 2 * first, ntot * 8);
+  HIP_TRY(ctx, ctx->occ_up.upload(d, 0, U.end, st));
+  ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
+  if ((rc = queue_occ(ctx, st, OccCall{occs, n_occ, nullptr, grid_of_host ? (const int *)(d + o_gof) : nullptr, (const float *)(d + o_xy),
+                                       (const unsigned long long *)(d + o_off), B, ntot, d + o_org, 16, max_range2, d_stats})))
+    return rc;
+  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+int ndt_occ_render_dev(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_dev, void *stream) {
+  int rc = occ_one_check(ctx, occ, "ndt_occ_render_dev");
+  if (rc) return rc;
+  if (!out_dev) return fail(ctx, NDT_E_ARG, "ndt_occ_render_dev: NULL out");
+  if (min_obs < 1) return fail(ctx, NDT_E_ARG, "ndt_occ_render_dev: min_obs below 1");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  ScratchScope scope(ctx, st);                     // (no scratch: the bracket orders the call among the context's)
+  if ((rc = scope.open())) return rc;
+  if ((rc = queue_occ_render(ctx, occ, min_obs, (signed char *)out_dev, st))) return rc;
+  return scope.close();
+}
+
+int ndt_occ_render(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_host) {
+  int rc = occ_one_check(ctx, occ, "ndt_occ_render");
+  if (rc) return rc;
+  if (!out_host) return fail(ctx, NDT_E_ARG, "ndt_occ_render: NULL out");
+  if (min_obs < 1) return fail(ctx, NDT_E_ARG, "ndt_occ_render: min_obs below 1");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  if ((rc = ctx->d_tmp.ensure(ctx, occ->n_cells))) return rc;
+  if ((rc = queue_occ_render(ctx, occ, min_obs, (signed char *)ctx->d_tmp.p, st))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->d_tmp.p, occ->n_cells, hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+int ndt_occ_counts(ndt_ctx *ctx, ndt_occ *occ, uint32_t *hit_host, uint32_t *pass_host) {
+  int rc = occ_one_check(ctx, occ, "ndt_occ_counts");
+  if (rc) return rc;
+  if (!hit_host && !pass_host) return fail(ctx, NDT_E_ARG, "ndt_occ_counts: hit and pass are both NULL");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  std::vector<uint32_t> both;
+  try { both.resize(occ->n_cells * 2); } catch (const std::bad_alloc &) { return fail(ctx, NDT_E_NOMEM, "ndt_occ_counts: out of memory"); }
+  if ((rc = occ_touch(ctx, occ, st))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(both.data(), occ->cells.p, both.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (size_t i = 0; i < occ->n_cells; ++i) {
+    if (hit_host) hit_host[i] = both[2 * i];
+    if (pass_host) pass_host[i] = both[2 * i + 1];
+  }
+  return NDT_OK;
+}
+
+int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, double max_range2,
+                               ndt_occ_stats *stats_host) {
+  int rc = check_set(s, 0, false, "ndt_sessions_occ_integrate");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const std::string f("ndt_sessions_occ_integrate");
+  if (!occs) return fail(ctx, NDT_E_ARG, f + ": NULL occs");
+  if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  // who is taken: the newest scan is the last range of scan_off in store[cur]
+  const int S = s->S;
+  std::vector<ndt_occ *> taken((size_t)S, nullptr);
+  std::vector<OccRow> own((size_t)S);
+  std::set<const ndt_occ *> seen;
+  size_t total = 0;
+  for (int i = 0; i < S; ++i) {
+    const SsSession &Q = s->ses[(size_t)i];
+    if ((which && !which[i]) || !Q.started || Q.scan_off.size() < 2) continue;
+    if (!occs[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": NULL grid");
+    if (occs[i]->ctx != ctx || occs[i]->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": the grid belongs to another context");
+    if (!seen.insert(occs[i]).second) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": its grid is given twice");
+    const size_t k = Q.scan_off.size() - 2;
+    taken[(size_t)i] = occs[i];
+    own[(size_t)i].pts = Q.store[Q.cur].p + Q.scan_off[k];
+    own[(size_t)i].n = Q.scan_off[k + 1] - Q.scan_off[k];
+    total += (size_t)own[(size_t)i].n;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
+  if ((rc = scope.open())) return rc;
+  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
+  ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
+  if ((rc = queue_occ(ctx, st, OccCall{taken.data(), S, own.data(), nullptr, nullptr, nullptr, S, total, s->last_pose.p, 24, max_range2, d_stats})))
+    return rc;
+  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
+  if ((rc = scope.close())) return rc;
+  if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
   return NDT_OK;
 }
 

@@ -21,6 +21,7 @@ bit-identical to resample_points).  `ops` is the object that provides them (capi
 is left out: it does not feed back into the estimate.
 """
 import math
+import os
 
 import numpy as np
 
@@ -566,14 +567,68 @@ def run_sessions(ops, logs, poses_names=None, map_names=None, separated_map_name
     return out
 
 
-def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated_map_names=None, sessions=None, **params):
+def save_occupancy(stem, values, geometry, occupied_thresh=0.65, free_thresh=0.196):
+    """An occupancy grid in map_server's format: `stem`.pgm and `stem`.yaml.  values: [ny, nx] int8 as OccGrid.render gives
+    them (-1 unknown, else 0 .. 100), row iy at y0 + iy res; geometry: anything with x0, y0, res.  The PGM is P5 with row 0
+    the LARGEST y; a pixel is 0 for value / 100 > occupied_thresh, 254 for value / 100 < free_thresh, 205 otherwise (unknown
+    included).  The YAML holds image, resolution, origin [x0, y0, 0.0], negate 0 and the two thresholds."""
+    v = np.asarray(values, dtype=np.int8)
+    if v.ndim != 2:
+        raise ValueError("save_occupancy: values must be [ny, nx]")
+    known = v >= 0
+    p = v.astype(np.float64) / 100.0
+    pix = np.full(v.shape, 205, dtype=np.uint8)
+    pix[known & (p > occupied_thresh)] = 0
+    pix[known & (p < free_thresh)] = 254
+    stem = str(stem)
+    with open(stem + ".pgm", "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (v.shape[1], v.shape[0]))
+        f.write(np.ascontiguousarray(pix[::-1]).tobytes())
+    with open(stem + ".yaml", "w") as f:
+        f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0.0]\nnegate: 0\noccupied_thresh: %r\nfree_thresh: %r\n"
+                % (os.path.basename(stem) + ".pgm", float(geometry.res), float(geometry.x0), float(geometry.y0),
+                   float(occupied_thresh), float(free_thresh)))
+
+
+def load_occupancy(stem):
+    """The inverse of save_occupancy, for tests -> (pixels [ny, nx] uint8 with row 0 the SMALLEST y again, dict of the YAML:
+    image, resolution, origin [x0, y0, 0.0], negate, occupied_thresh, free_thresh)."""
+    stem = str(stem)
+    with open(stem + ".pgm", "rb") as f:
+        raw = f.read()
+    magic, dims, maxv, body = raw.split(b"\n", 3)
+    if magic != b"P5" or maxv != b"255":
+        raise ValueError("load_occupancy: not a P5 image of 8 bits")
+    nx, ny = (int(t) for t in dims.split())
+    pix = np.frombuffer(body, dtype=np.uint8, count=nx * ny).reshape(ny, nx)[::-1].copy()
+    meta = {}
+    with open(stem + ".yaml") as f:
+        for line in f:
+            key, _, val = line.strip().partition(": ")
+            if key == "image":
+                meta[key] = val
+            elif key == "origin":
+                meta[key] = [float(t) for t in val.strip("[]").split(",")]
+            elif key == "negate":
+                meta[key] = int(val)
+            elif key:
+                meta[key] = float(val)
+    return pix, meta
+
+
+def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated_map_names=None, sessions=None,
+                          occupancy=None, occupancy_names=None, **params):
     """run_sessions with every session's state resident on the device: one capi.Sessions set (ndt_sessions_*) over all
     logs, one `step` per lockstep step -- the raw scans and odometry go up, the fused poses come down; scans, submap
     clouds, local maps and NDT maps never leave the device.  The same files and return value as run_sessions
     (start_frame and end_frame reach the set through `active`); the global map is read from the device once per session,
     at its last keyframe step (cnt % keyframe_skip == 0: what saveGlobalMap writes).  One parameter set for all sessions
     (a sweep makes one call per set).  `sessions`: an object with capi.Sessions' interface to use instead of a new
-    capi.Sessions(ctx, len(logs), ...) (tests: a host stand-in)."""
+    capi.Sessions(ctx, len(logs), ...) (tests: a host stand-in).
+    occupancy: a geometry (x0, y0, res, nx, ny: capi.OccGeometry), or one per log -- one occupancy grid per log
+    (capi.OccGrid, or sessions.occ_grid(geometry) where the stand-in has one), every step's scans ray-cast into them
+    (sessions.occ_integrate with the records' `stepped` flags), rendered at min_obs = 1 and written with save_occupancy to
+    occupancy_names[i] at the end.  None: no grids, nothing else changes."""
     from . import capi
     p = dict(LAUNCH_PARAMS)
     p.update(params)
@@ -591,7 +646,16 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
     poses = [[] for _ in range(S)]
     exported = [(_EMPTY, []) for _ in range(S)]
     empty = np.zeros((0, 2))
+    grids, rendered = None, None
     try:
+        if occupancy is not None:
+            geoms = [occupancy] * S if hasattr(occupancy, "res") else list(occupancy)
+            if len(geoms) != S:
+                raise ValueError("run_sessions_resident: occupancy needs one geometry, or one per log")
+            make = getattr(sessions, "occ_grid", None) or (lambda g: capi.OccGrid(ctx, g))
+            grids = []
+            for g in geoms:
+                grids.append(make(g))
         for k in range(max(lengths, default=0)):
             active = np.array([k < lengths[i] and logs[i][k].sid >= p["start_frame"] for i in range(S)], dtype=np.uint8)
             if not active.any():
@@ -600,6 +664,8 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
             odo = [((logs[i][k].pose.tx, logs[i][k].pose.ty, logs[i][k].pose.th) if active[i] else (0.0, 0.0, 0.0))
                    for i in range(S)]
             recs = sessions.step(scans, odo, active)
+            if grids is not None:
+                sessions.occ_integrate(grids, np.ascontiguousarray(recs["stepped"], dtype=np.uint8))
             for i in range(S):
                 if not active[i]:
                     continue
@@ -610,10 +676,16 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
                 if k == last_key[i]:
                     g, parts = sessions.global_map(i)
                     exported[i] = (g.copy(), [m.copy() for m in parts])
+        if grids is not None:
+            rendered = [g.render(1) for g in grids]
     finally:
+        for g in grids or []:
+            g.close()
         if own:
             sessions.close()
     for i in range(S):
+        if rendered is not None and occupancy_names and occupancy_names[i]:
+            save_occupancy(occupancy_names[i], rendered[i], geoms[i])
         if poses_names and poses_names[i]:
             write_poses(poses_names[i], poses[i])
         if map_names and map_names[i]:
