@@ -228,7 +228,13 @@ int ndt_map_export(const ndt_map *map, int *cell_idx, float *cent_xy, double *me
 /* Replaces ndt.setInputSource + ndt.align + getFinalTransformation + getFitnessScore +
  * hasConverged + getTransformationProbability + getHessian for ONE scan
  * (src/PoseEstimator.cpp:17-56).  scan = the post-filter source cloud (row a1 stays with the
- * caller); init = (tx, ty, yaw[rad]) as src/PoseEstimator.cpp:22-24 builds the guess. */
+ * caller); init = (tx, ty, yaw[rad]) as src/PoseEstimator.cpp:22-24 builds the guess.
+ * A match with nothing to match -- the guess is not finite, every point of the scan is NaN, or no point reaches a voxel --
+ * is legal, here and in every batched form below: the first pass has score 0, a zero gradient and a zero Hessian; the
+ * Newton step is then exactly zero and the match ends at once with status 0, iters = 0, converged = 1, p and the float32
+ * matrix as the prologue forms them from the guess (NaN where the guess is), pose read from that matrix, and fitness
+ * DBL_MAX when no point has a finite image.  Non-finite points are skipped by every pass and never binned: no float is
+ * converted to an integer before it is known to be finite.  The checker (oracle/ndt_oracle.c) follows the same rule. */
 int ndt_align(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n,
               size_t stride_bytes, const double init_xyyaw[3], ndt_result *out);
 
@@ -236,7 +242,8 @@ int ndt_align(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_
  * packed float2, concatenated; offsets[B+1] in points.  shared_scan != 0: every match uses
  * scan 0 (offsets[0..1]) with its own init pose (multi-hypothesis relocalisation).  Such launches keep a scratch
  * slot of the scan's size PER MATCH (ordered copy 8 B, distance 4 B, far-query list 4 B per point: 16 B x n x B)
- * and score the seeds that end far from the map from the map's occupancy words (same `fitness`). */
+ * and score the seeds that end far from the map from the map's occupancy words (same `fitness`).
+ * Each match with nothing to match ends as ndt_align says; it changes nothing for the other matches of the batch. */
 int ndt_align_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_host,
                     const uint64_t *offsets_host, int B, int shared_scan,
                     const double *inits_host /* B x 3 */, ndt_result *out_host /* B */);
@@ -845,6 +852,22 @@ int ndt_last_timing(const ndt_ctx *ctx, float *map_build_ms, float *align_ms);
  * against its own libm with this before trusting bit-level parity (tests/test_gpu_parity.py does, on 2e6 yaws).
  * Any output pointer may be NULL. */
 int ndt_selftest_libm_f32(ndt_ctx *ctx, const float *yaw_host, size_t n, float *cos_out, float *sin_out, float *init_yaw_out);
+
+/* Self-test of the optimiser's device functions (ndt_slam_amd/csrc/ndt_optimizer.hip.h), the functions the match kernel
+ * calls, not copies: one lane per row, host arrays in and out, four independent parts.  A part whose input pointer is
+ * NULL (or whose count is 0) is skipped; a part that runs needs its output pointer.
+ *   solve3:     n x 9 doubles {Hxx, Hxy, Hxt, Hyy, Hyt, Htt, b0, b1, b2}          -> n x 3 doubles x (H x = b, pseudo-inverse)
+ *   mt_trial:   n x 9 doubles {a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t}      -> n doubles, the trial value
+ *   mt_update:  n x 9 doubles, the same layout                                   -> n x 7 doubles {a_l, f_l, g_l, a_u, f_u, g_u
+ *               after the update, return value (1.0: interval converged)}, taken through the match kernel's state record
+ *   yaw_from_T: n x 2 floats {T00, T10}                                           -> n doubles, the a9 yaw
+ * NaN inputs are legal and give what the match gives: solve3 with a NaN entry of H returns NaN, a negative radicand in
+ * mt_trial returns NaN.  (A whole match on non-finite input: see ndt_align.)
+ * At most 2^26 rows per part.  NDT_E_ARG: no part to run, a missing output, too many rows. */
+int ndt_selftest_optimizer(ndt_ctx *ctx, const double *solve3_in, size_t n_solve3, double *solve3_out,
+                           const double *mt_trial_in, size_t n_mt_trial, double *mt_trial_out,
+                           const double *mt_update_in, size_t n_mt_update, double *mt_update_out,
+                           const float *yaw_in, size_t n_yaw, double *yaw_out);
 
 #ifdef __cplusplus
 }

@@ -159,7 +159,7 @@ EXPORTS = [
     "ndt_fuse_default_params", "ndt_predict_batch_dev", "ndt_fuse_batch_dev",
     "ndt_remove_neighbors", "ndt_remove_neighbors_dev",
     "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
-    "ndt_selftest_libm_f32", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
+    "ndt_selftest_libm_f32", "ndt_selftest_optimizer", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
     "ndt_align_batch_multi", "ndt_align_batch_multi_dev", "ndt_map_build_batch", "ndt_map_build_batch_dev",
     "ndt_local_map_batch", "ndt_local_map_batch_dev", "ndt_prefilter_batch",
     "ndt_session_default_params", "ndt_sessions_create", "ndt_sessions_destroy", "ndt_sessions_step", "ndt_sessions_step_dev",
@@ -211,6 +211,7 @@ def lib():
     L.ndt_fitness_at.argtypes = [vp, vp, vp, sz, sz, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     L.ndt_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.ndt_selftest_libm_f32.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    L.ndt_selftest_optimizer.argtypes = [vp] + [vp, C.c_size_t, vp] * 4
     L.ndt_kernel_timing.argtypes = [vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.ndt_launch_interval.argtypes = [vp, i, C.POINTER(C.c_float)]
     L.ndt_align_batch_sharded.argtypes = [vp, vp, i, vp, vp, i, i, vp, vp]
@@ -657,6 +658,23 @@ class Context:
         self.check(lib().ndt_selftest_libm_f32(self.h, y.ctypes.data, len(y), c.ctypes.data, s.ctypes.data, y0.ctypes.data),
                    "ndt_selftest_libm_f32")
         return c, s, y0
+
+    def selftest_optimizer(self, solve3=None, mt_trial=None, mt_update=None, yaw=None):
+        """ndt_selftest_optimizer: rows through the device functions of ndt_optimizer.hip.h.  solve3 [n, 9] (Hxx Hxy Hxt Hyy Hyt
+        Htt b0 b1 b2) -> [n, 3]; mt_trial [n, 9] -> [n]; mt_update [n, 9] -> [n, 7] (the six interval values, the return
+        value); yaw [n, 2] float32 (T00, T10) -> [n].  Returns a dict with the parts that were given."""
+        args, outs = [], {}
+        for name, rows, dt, width, out_shape in (("solve3", solve3, np.float64, 9, (3,)), ("mt_trial", mt_trial, np.float64, 9, ()),
+                                                 ("mt_update", mt_update, np.float64, 9, (7,)), ("yaw", yaw, np.float32, 2, ())):
+            if rows is None or len(rows) == 0:
+                args += [None, 0, None]
+                continue
+            a = np.ascontiguousarray(rows, dtype=dt).reshape(-1, width)
+            o = np.zeros((len(a),) + out_shape, np.float64)
+            outs[name] = (a, o)
+            args += [a.ctypes.data, len(a), o.ctypes.data]
+        self.check(lib().ndt_selftest_optimizer(self.h, *args), "ndt_selftest_optimizer")
+        return {k: v[1] for k, v in outs.items()}
 
     def last_timing(self):
         a, b = C.c_float(), C.c_float()

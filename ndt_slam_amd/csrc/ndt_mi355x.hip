@@ -1822,6 +1822,80 @@ int ndt_selftest_libm_f32(ndt_ctx *ctx, const float *yaw, size_t n, float *cos_o
   return NDT_OK;
 }
 
+namespace {
+// One lane per row through the optimiser's own device functions (ndt_optimizer.hip.h); a part whose input is NULL is skipped.
+__global__ void __launch_bounds__(256)
+selftest_optimizer_kernel(const double *__restrict__ s3_in, size_t n_s3, double *__restrict__ s3_out,
+                          const double *__restrict__ tr_in, size_t n_tr, double *__restrict__ tr_out,
+                          const double *__restrict__ up_in, size_t n_up, double *__restrict__ up_out,
+                          const float *__restrict__ yw_in, size_t n_yw, double *__restrict__ yw_out) {
+  const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  if (s3_in) for (size_t i = i0; i < n_s3; i += step) {
+    const double *r = s3_in + 9 * i;
+    const double Hs[6] = {r[0], r[1], r[2], r[3], r[4], r[5]};
+    double x0, x1, x2;
+    solve3(Hs, r[6], r[7], r[8], x0, x1, x2);
+    s3_out[3 * i] = x0; s3_out[3 * i + 1] = x1; s3_out[3 * i + 2] = x2;
+  }
+  if (tr_in) for (size_t i = i0; i < n_tr; i += step) {
+    const double *r = tr_in + 9 * i;
+    tr_out[i] = mt_trial(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8]);
+  }
+  if (up_in) for (size_t i = i0; i < n_up; i += step) {
+    const double *r = up_in + 9 * i;
+    AlignState S;
+    S.a_l = r[0]; S.f_l = r[1]; S.g_l = r[2]; S.a_u = r[3]; S.f_u = r[4]; S.g_u = r[5];
+    const int rc = mt_update(S, r[6], r[7], r[8]);
+    double *o = up_out + 7 * i;
+    o[0] = S.a_l; o[1] = S.f_l; o[2] = S.g_l; o[3] = S.a_u; o[4] = S.f_u; o[5] = S.g_u; o[6] = (double)rc;
+  }
+  if (yw_in) for (size_t i = i0; i < n_yw; i += step) yw_out[i] = yaw_from_T(yw_in[2 * i], yw_in[2 * i + 1]);
+}
+}  // namespace
+
+int ndt_selftest_optimizer(ndt_ctx *ctx, const double *solve3_in, size_t n_solve3, double *solve3_out,
+                           const double *mt_trial_in, size_t n_mt_trial, double *mt_trial_out,
+                           const double *mt_update_in, size_t n_mt_update, double *mt_update_out,
+                           const float *yaw_in, size_t n_yaw, double *yaw_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!solve3_in) n_solve3 = 0;
+  if (!mt_trial_in) n_mt_trial = 0;
+  if (!mt_update_in) n_mt_update = 0;
+  if (!yaw_in) n_yaw = 0;
+  const size_t n_max = std::max(std::max(n_solve3, n_mt_trial), std::max(n_mt_update, n_yaw));
+  if (n_max == 0 || n_max > ((size_t)1 << 26) || (n_solve3 && !solve3_out) || (n_mt_trial && !mt_trial_out) ||
+      (n_mt_update && !mt_update_out) || (n_yaw && !yaw_out))
+    return fail(ctx, NDT_E_ARG, "ndt_selftest_optimizer: bad arguments");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // one buffer of doubles: [solve3 in 9 | out 3] [mt_trial in 9 | out 1] [mt_update in 9 | out 7] [yaw out 1 | in 2 floats = 1 double]
+  const size_t o_s3 = 0, o_tr = o_s3 + 12 * n_solve3, o_up = o_tr + 10 * n_mt_trial, o_yw = o_up + 16 * n_mt_update,
+               total = o_yw + 2 * n_yaw;
+  DevBuf<double> buf;
+  { int rc = buf.alloc(ctx, total * sizeof(double)); if (rc) return rc; }
+  double *d = buf.p;
+  double *d_s3 = d + o_s3, *d_tr = d + o_tr, *d_up = d + o_up, *d_yw = d + o_yw;
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  if (e == hipSuccess && n_solve3) e = hipMemcpyAsync(d_s3, solve3_in, 9 * n_solve3 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_mt_trial) e = hipMemcpyAsync(d_tr, mt_trial_in, 9 * n_mt_trial * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_mt_update) e = hipMemcpyAsync(d_up, mt_update_in, 9 * n_mt_update * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_yaw) e = hipMemcpyAsync(d_yw + n_yaw, yaw_in, 2 * n_yaw * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    selftest_optimizer_kernel<<<grid_for(n_max, 256), 256, 0, st>>>(
+        n_solve3 ? d_s3 : nullptr, n_solve3, d_s3 + 9 * n_solve3, n_mt_trial ? d_tr : nullptr, n_mt_trial, d_tr + 9 * n_mt_trial,
+        n_mt_update ? d_up : nullptr, n_mt_update, d_up + 9 * n_mt_update,
+        n_yaw ? (const float *)(d_yw + n_yaw) : nullptr, n_yaw, d_yw);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && n_solve3) e = hipMemcpyAsync(solve3_out, d_s3 + 9 * n_solve3, 3 * n_solve3 * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_mt_trial) e = hipMemcpyAsync(mt_trial_out, d_tr + 9 * n_mt_trial, n_mt_trial * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_mt_update) e = hipMemcpyAsync(mt_update_out, d_up + 9 * n_mt_update, 7 * n_mt_update * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_yaw) e = hipMemcpyAsync(yaw_out, d_yw, n_yaw * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_selftest_optimizer: ") + hipGetErrorString(e));
+  return NDT_OK;
+}
+
 int ndt_align(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, size_t stride,
               const double init[3], ndt_result *out) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");

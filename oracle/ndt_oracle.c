@@ -445,13 +445,40 @@ double ndt_oracle_eval_at(const ndt_oracle_map *m, const float *scan, size_t n, 
 /* a6: Newton step + More-Thuente line search                                                  */
 /* ------------------------------------------------------------------------------------------ */
 
+/* Branch census (tests only; ndt_oracle.h): one counter per branch of the optimiser, and a bounded ring of the argument
+ * tuples of every More-Thuente call.  Counting changes no result.  Not thread safe. */
+static int g_census[NDT_CEN_COUNT];
+#define CEN(k) (g_census[NDT_CEN_##k]++)
+void ndt_oracle_census_reset(void) { memset(g_census, 0, sizeof(g_census)); }
+int ndt_oracle_census_get(int *out, int cap) {
+  for (int k = 0; k < NDT_CEN_COUNT && k < cap; ++k) out[k] = g_census[k];
+  return NDT_CEN_COUNT;
+}
+#define RING_ROWS 8192
+static double g_ring[RING_ROWS][10];
+static long g_ring_n = 0;
+static int g_ring_on = 0;
+void ndt_oracle_ring_enable(int on) { g_ring_on = on ? 1 : 0; g_ring_n = 0; }
+int ndt_oracle_ring_get(double *out, int cap_rows) {
+  const long have = g_ring_n < RING_ROWS ? g_ring_n : RING_ROWS, first = g_ring_n - have;
+  int n = 0;
+  for (long r = first; r < g_ring_n && n < cap_rows; ++r, ++n) memcpy(out + 10 * (size_t)n, g_ring[r % RING_ROWS], sizeof(g_ring[0]));
+  return n;
+}
+static void ring_push(int kind, double a_l, double f_l, double g_l, double a_u, double f_u, double g_u, double a_t,
+                      double f_t, double g_t) {
+  if (!g_ring_on) return;
+  double *r = g_ring[g_ring_n++ % RING_ROWS];
+  r[0] = kind; r[1] = a_l; r[2] = f_l; r[3] = g_l; r[4] = a_u; r[5] = f_u; r[6] = g_u; r[7] = a_t; r[8] = f_t; r[9] = g_t;
+}
+
 /* Symmetric 3x3 solve by cyclic Jacobi eigen-decomposition with pseudo-inverse thresholding.
  * Stands in for PCL's JacobiSVD<6x6>(H).solve(-g): for a symmetric matrix the SVD is the
  * eigen-decomposition up to signs and the 6x6 is block diagonal (SURVEY.md 8a note). */
 void ndt_oracle_solve3(const double Hin[9], const double b[3], double x[3]) {
   double A[3][3], V[3][3];
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { A[i][j] = 0.5 * (Hin[3 * i + j] + Hin[3 * j + i]); V[i][j] = (i == j); }
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) if (A[i][j] != A[i][j]) { x[0] = x[1] = x[2] = NAN; return; }
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) if (A[i][j] != A[i][j]) { CEN(S3_NAN); x[0] = x[1] = x[2] = NAN; return; }
   {
     /* well-conditioned case: adjugate / determinant (same answer as the SVD solve up to rounding) */
     double a00 = A[0][0], a01 = A[0][1], a02 = A[0][2], a11 = A[1][1], a12 = A[1][2], a22 = A[2][2];
@@ -460,18 +487,22 @@ void ndt_oracle_solve3(const double Hin[9], const double b[3], double x[3]) {
     double det = a00 * c00 + a01 * c01 + a02 * c02;
     double sc = fmax(fmax(fabs(a00), fabs(a11)), fmax(fabs(a22), fmax(fabs(a01), fmax(fabs(a02), fabs(a12)))));
     if (fabs(det) > 1e-9 * sc * sc * sc && fabs(det) <= DBL_MAX) {
+      CEN(S3_ADJ);
       x[0] = (c00 * b[0] + c01 * b[1] + c02 * b[2]) / det;
       x[1] = (c01 * b[0] + c11 * b[1] + c12 * b[2]) / det;
       x[2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) / det;
       return;
     }
   }
+  CEN(S3_JACOBI);
+  if (A[0][0] != 0 || A[1][1] != 0 || A[2][2] != 0 || A[0][1] != 0 || A[0][2] != 0 || A[1][2] != 0) CEN(S3_JACOBI_NONZERO);
   for (int sweep = 0; sweep < 12; ++sweep) {
     double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
     if (off == 0.0) break;
     for (int p = 0; p < 2; ++p) for (int q = p + 1; q < 3; ++q) {
       double apq = A[p][q];
-      if (apq == 0.0) continue;
+      if (apq == 0.0) { g_census[NDT_CEN_S3_SKIP01 + p + q - 1]++; continue; }
+      g_census[NDT_CEN_S3_ROT01 + p + q - 1]++;
       double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
       double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
       double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
@@ -492,7 +523,7 @@ void ndt_oracle_solve3(const double Hin[9], const double b[3], double x[3]) {
   x[0] = x[1] = x[2] = 0.0;
   for (int k = 0; k < 3; ++k) {
     double l = A[k][k];
-    if (!(fabs(l) > thr) || fabs(l) < DBL_MIN) continue;
+    if (!(fabs(l) > thr) || fabs(l) < DBL_MIN) { g_census[NDT_CEN_S3_DROP0 + k]++; continue; }
     double proj = (V[0][k] * b[0] + V[1][k] * b[1] + V[2][k] * b[2]) / l;
     x[0] += V[0][k] * proj; x[1] += V[1][k] * proj; x[2] += V[2][k] * proj;
   }
@@ -500,47 +531,66 @@ void ndt_oracle_solve3(const double Hin[9], const double b[3], double x[3]) {
 
 /* trialValueSelectionMT: More-Thuente trial value, cases 1-4 with the Sun & Yuan
  * cubic/quadratic/secant minimisers and the 0.66 safeguard. */
-double ndt_oracle_mt_trial(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u,
-                           double a_t, double f_t, double g_t) {
+static double mt_trial_impl(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u,
+                            double a_t, double f_t, double g_t) {
   if (f_t > f_l) {                                          /* case 1 */
     double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
     double w = sqrt(z * z - g_t * g_l);
     double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
     double a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t));
-    if (fabs(a_c - a_l) < fabs(a_q - a_l)) return a_c;
+    if (fabs(a_c - a_l) < fabs(a_q - a_l)) { CEN(MT_C1_CUBIC); return a_c; }
+    CEN(MT_C1_AVG);
     return 0.5 * (a_q + a_c);
   } else if (g_t * g_l < 0) {                               /* case 2 */
     double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
     double w = sqrt(z * z - g_t * g_l);
     double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
     double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
-    if (fabs(a_c - a_t) >= fabs(a_s - a_t)) return a_c;
+    if (fabs(a_c - a_t) >= fabs(a_s - a_t)) { CEN(MT_C2_CUBIC); return a_c; }
+    CEN(MT_C2_SECANT);
     return a_s;
   } else if (fabs(g_t) <= fabs(g_l)) {                      /* case 3 */
     double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
     double w = sqrt(z * z - g_t * g_l);
     double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
     double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
-    double a_n = (fabs(a_c - a_t) < fabs(a_s - a_t)) ? a_c : a_s;
+    const int cubic = fabs(a_c - a_t) < fabs(a_s - a_t);
+    double a_n = cubic ? a_c : a_s;
     double lim = a_t + 0.66 * (a_u - a_t);
-    if (a_t > a_l) return (a_n < lim) ? a_n : lim;          /* std::min(lim, a_n) */
+    /* census: (secant | cubic) x (backward | forward) x (a_n | lim returned) */
+    if (a_t > a_l) {                                        /* std::min(lim, a_n) */
+      g_census[NDT_CEN_MT_C3_SEC_BWD_AN + 4 * cubic + 2 + ((a_n < lim) ? 0 : 1)]++;
+      return (a_n < lim) ? a_n : lim;
+    }
+    g_census[NDT_CEN_MT_C3_SEC_BWD_AN + 4 * cubic + ((lim < a_n) ? 0 : 1)]++;
     return (lim < a_n) ? a_n : lim;                         /* std::max(lim, a_n) */
   } else {                                                  /* case 4 */
     double z = 3 * (f_t - f_u) / (a_t - a_u) - g_t - g_u;
     double w = sqrt(z * z - g_t * g_u);
+    CEN(MT_C4);
     return a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w);
   }
+}
+double ndt_oracle_mt_trial(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u,
+                           double a_t, double f_t, double g_t) {
+  ring_push(0, a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t);
+  const double a = mt_trial_impl(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t);
+  if (a != a) CEN(MT_NAN);
+  return a;
 }
 
 /* updateIntervalMT: cases U1-U3 / a-c; returns 1 when the interval has converged. */
 int ndt_oracle_mt_update(double *a_l, double *f_l, double *g_l, double *a_u, double *f_u,
                          double *g_u, double a_t, double f_t, double g_t) {
-  if (f_t > *f_l) { *a_u = a_t; *f_u = f_t; *g_u = g_t; return 0; }
-  if (g_t * (*a_l - a_t) > 0) { *a_l = a_t; *f_l = f_t; *g_l = g_t; return 0; }
+  ring_push(1, *a_l, *f_l, *g_l, *a_u, *f_u, *g_u, a_t, f_t, g_t);
+  if (f_t > *f_l) { CEN(MU_U1); *a_u = a_t; *f_u = f_t; *g_u = g_t; return 0; }
+  if (g_t * (*a_l - a_t) > 0) { CEN(MU_U2); *a_l = a_t; *f_l = f_t; *g_l = g_t; return 0; }
   if (g_t * (*a_l - a_t) < 0) {
+    CEN(MU_U3);
     *a_u = *a_l; *f_u = *f_l; *g_u = *g_l;
     *a_l = a_t; *f_l = f_t; *g_l = g_t; return 0;
   }
+  CEN(MU_CONVERGED);
   return 1;
 }
 
@@ -605,7 +655,8 @@ static double step_length_mt(align_ctx *cx, const double x[3], double dir[3], do
   double phi_0 = -(*score);
   double d_phi_0 = -(g[0] * dir[0] + g[1] * dir[1] + g[2] * dir[2]);
   if (d_phi_0 >= 0) {
-    if (d_phi_0 == 0) return 0;
+    if (d_phi_0 == 0) { CEN(LS_DPHI0_ZERO); return 0; }
+    CEN(LS_FLIP);
     d_phi_0 *= -1; dir[0] *= -1; dir[1] *= -1; dir[2] *= -1;
   }
   const double mu = prm->mt_mu, nu = prm->mt_nu;
@@ -632,10 +683,13 @@ static double step_length_mt(align_ctx *cx, const double x[3], double dir[3], do
          !(psi_t <= 0 && d_phi_t <= -nu * d_phi_0)) {
     const double a_prev = a_t;                             /* step length of the pass just run */
     if (open_interval) a_t = ndt_oracle_mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
-    else               a_t = ndt_oracle_mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+    else             { a_t = ndt_oracle_mt_trial(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t); CEN(LS_TRIAL_CLOSED); }
+    if (step_max < a_t) CEN(LS_CLAMP_MAX);
     a_t = (step_max < a_t) ? step_max : a_t;
+    if (a_t < step_min) CEN(LS_CLAMP_MIN);
     a_t = (a_t < step_min) ? step_min : a_t;
     x_t[0] = x[0] + dir[0] * a_t; x_t[1] = x[1] + dir[1] * a_t; x_t[2] = x[2] + dir[2] * a_t;
+    if (a_t == a_prev) CEN(LS_REPEAT);
     if (a_t == a_prev) {
       /* the trial of the pass just run, again (the clamp at step_min does this up to mt_max_iter times): the reference
        * transforms the cloud with the same matrix and computes the same derivatives */
@@ -656,6 +710,7 @@ static double step_length_mt(align_ctx *cx, const double x[3], double dir[3], do
     psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
     d_psi_t = d_phi_t - mu * d_phi_0;
     if (open_interval && (psi_t <= 0 && d_psi_t >= 0)) {
+      CEN(LS_OPEN_CLOSES);
       open_interval = 0;
       f_l = f_l + phi_0 - mu * d_phi_0 * a_l; g_l = g_l + mu * d_phi_0;
       f_u = f_u + phi_0 - mu * d_phi_0 * a_u; g_u = g_u + mu * d_phi_0;
@@ -860,12 +915,13 @@ static int align_impl(const ndt_oracle_map *m, const float *scan, size_t n, size
     double mg[3] = {-g[0], -g[1], -g[2]}, dp[3];
     newton_solve(Hf, mg, dp);
     double nrm = sqrt(dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2]);
-    if (nrm == 0 || nrm != nrm) { converged = (nrm == nrm); nan_exit = 1; break; }
+    if (nrm == 0 || nrm != nrm) { if (nrm == nrm) CEN(EXIT_NRM_ZERO); else CEN(EXIT_NRM_NAN); converged = (nrm == nrm); nan_exit = 1; break; }
     dp[0] /= nrm; dp[1] /= nrm; dp[2] /= nrm;
     double a = step_length_mt(&cx, p, dp, nrm, prm->step_size, prm->trans_eps / 2, &score, g, H);
     dp[0] *= a; dp[1] *= a; dp[2] *= a;
     p[0] += dp[0]; p[1] += dp[1]; p[2] += dp[2];
     int over = prm->conv_ge ? (iters >= prm->max_iter) : (iters > prm->max_iter);
+    if (over) CEN(EXIT_MAX_ITER); else if (iters && (fabs(a) < prm->trans_eps)) CEN(EXIT_TRANS_EPS);
     if (over || (iters && (fabs(a) < prm->trans_eps))) converged = 1;
     iters++;
   }

@@ -210,6 +210,43 @@ size_t ndt_oracle_make_map(const float *scans_xy, const size_t *offsets, int n_s
                            int remove_moving, double resol, double thre_neighbor, float *out_xy);
 
 
+/* ---- branch census of the optimiser (tests/optimizer_cases.py) ----
+ * One counter per branch of ndt_oracle_solve3, ndt_oracle_mt_trial, ndt_oracle_mt_update, the line search and the outer
+ * loop, counted wherever those run (a match or a direct call).  Counting changes no result.  Like the hooks below the
+ * census is process-wide and not thread safe: reset, run single-threaded, get.  Names: ndt_oracle.py CENSUS_NAMES. */
+enum {
+  NDT_CEN_S3_ADJ = 0,          /* solve3: adjugate / determinant                                                    */
+  NDT_CEN_S3_NAN,              /*         NaN entry: NaN out                                                        */
+  NDT_CEN_S3_JACOBI,           /*         Jacobi pseudo-inverse entered                                             */
+  NDT_CEN_S3_JACOBI_NONZERO,   /*         ... with a matrix that is not all zero                                    */
+  NDT_CEN_S3_ROT01, NDT_CEN_S3_ROT02, NDT_CEN_S3_ROT12,      /* rotation of pair (p,q) taken, apq != 0              */
+  NDT_CEN_S3_SKIP01, NDT_CEN_S3_SKIP02, NDT_CEN_S3_SKIP12,   /* ... skipped inside a sweep, apq == 0                */
+  NDT_CEN_S3_DROP0, NDT_CEN_S3_DROP1, NDT_CEN_S3_DROP2,      /* eigenvalue k below the threshold: direction dropped */
+  NDT_CEN_MT_C1_CUBIC, NDT_CEN_MT_C1_AVG, NDT_CEN_MT_C2_CUBIC, NDT_CEN_MT_C2_SECANT,
+  /* case 3: a_n = secant | cubic, a_t <= a_l (backward) | a_t > a_l (forward), a_n | lim returned */
+  NDT_CEN_MT_C3_SEC_BWD_AN, NDT_CEN_MT_C3_SEC_BWD_LIM, NDT_CEN_MT_C3_SEC_FWD_AN, NDT_CEN_MT_C3_SEC_FWD_LIM,
+  NDT_CEN_MT_C3_CUB_BWD_AN, NDT_CEN_MT_C3_CUB_BWD_LIM, NDT_CEN_MT_C3_CUB_FWD_AN, NDT_CEN_MT_C3_CUB_FWD_LIM,
+  NDT_CEN_MT_C4,
+  NDT_CEN_MT_NAN,              /* a NaN trial value (negative radicand, 0 / 0)                                      */
+  NDT_CEN_MU_U1, NDT_CEN_MU_U2, NDT_CEN_MU_U3, NDT_CEN_MU_CONVERGED,
+  NDT_CEN_LS_FLIP,             /* line search: dphi0 > 0, direction reversed                                        */
+  NDT_CEN_LS_DPHI0_ZERO,       /*              dphi0 == 0: step length 0                                            */
+  NDT_CEN_LS_OPEN_CLOSES,      /*              the open interval closes                                             */
+  NDT_CEN_LS_TRIAL_CLOSED,     /*              a trial value chosen in the closed interval                          */
+  NDT_CEN_LS_CLAMP_MIN,        /*              an inner trial clamped to trans_eps / 2                              */
+  NDT_CEN_LS_CLAMP_MAX,        /*              an inner trial clamped to step_size                                  */
+  NDT_CEN_LS_REPEAT,           /*              an inner trial at the step length of the pass before it              */
+  NDT_CEN_EXIT_NRM_ZERO, NDT_CEN_EXIT_NRM_NAN,   /* outer loop: zero / NaN Newton step                              */
+  NDT_CEN_EXIT_MAX_ITER, NDT_CEN_EXIT_TRANS_EPS, /*             iteration limit / step below trans_eps              */
+  NDT_CEN_COUNT
+};
+void ndt_oracle_census_reset(void);
+int  ndt_oracle_census_get(int *out, int cap);        /* fills min(cap, NDT_CEN_COUNT) counters; returns NDT_CEN_COUNT */
+/* Bounded ring (the last 8192) of the argument tuples of every ndt_oracle_mt_trial (kind 0) / ndt_oracle_mt_update (kind 1)
+ * call while enabled: rows of 10 doubles {kind, a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t}.  Enabling clears it. */
+void ndt_oracle_ring_enable(int on);
+int  ndt_oracle_ring_get(double *out, int cap_rows);  /* oldest first; returns the rows written */
+
 /* ---- pin points and hooks (tests/test_eigen_pins.py; see the end of ndt_oracle.c) ---- */
 typedef struct ndt_oracle_hooks {
   void (*solve)(const double H[9], const double b[3], double x[3]);   /* replaces ndt_oracle_solve3 in the Newton step */

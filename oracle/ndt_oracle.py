@@ -40,6 +40,15 @@ class MapInfo(C.Structure):
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
 
 
+# ndt_oracle_hooks (oracle/ndt_oracle.h), declared once for every caller of ndt_oracle_set_hooks
+SOLVE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+INITP_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_double))
+
+
+class Hooks(C.Structure):
+    _fields_ = [("solve", SOLVE_FN), ("init_p", INITP_FN)]
+
+
 RESULT_DTYPE = np.dtype([
     ("pose", "f8", 3), ("T00", "f4"), ("T10", "f4"), ("T03", "f4"), ("T13", "f4"),
     ("fitness", "f8"), ("trans_prob", "f8"), ("score", "f8"), ("H", "f8", 9), ("p", "f8", 3),
@@ -118,6 +127,12 @@ def lib():
     L.ndt_oracle_mt_update.argtypes = [dp] * 6 + [C.c_double] * 3
     L.ndt_oracle_gauss.argtypes = [C.POINTER(Params), dp, dp]
     L.ndt_oracle_solve3.argtypes = [dp, dp, dp]
+    L.ndt_oracle_set_hooks.argtypes = [C.POINTER(Hooks)]
+    L.ndt_oracle_census_get.restype = C.c_int
+    L.ndt_oracle_census_get.argtypes = [vp, C.c_int]
+    L.ndt_oracle_ring_enable.argtypes = [C.c_int]
+    L.ndt_oracle_ring_get.restype = C.c_int
+    L.ndt_oracle_ring_get.argtypes = [vp, C.c_int]
     _LIB = L
     return L
 
@@ -251,6 +266,45 @@ def mt_update(a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t):
     v = [C.c_double(x) for x in (a_l, f_l, g_l, a_u, f_u, g_u)]
     r = lib().ndt_oracle_mt_update(*[C.byref(x) for x in v], a_t, f_t, g_t)
     return r, [x.value for x in v]
+
+
+def set_hooks(hooks):
+    """Install a Hooks record (None: none).  The caller keeps the record and its callbacks alive while it is installed."""
+    lib().ndt_oracle_set_hooks(C.byref(hooks) if hooks is not None else None)
+
+
+# ---- branch census of the optimiser (oracle/ndt_oracle.h: the NDT_CEN_* enum, in its order) ----
+CENSUS_NAMES = (
+    "s3_adjugate", "s3_nan", "s3_jacobi", "s3_jacobi_nonzero", "s3_rot01", "s3_rot02", "s3_rot12",
+    "s3_skip01", "s3_skip02", "s3_skip12", "s3_drop0", "s3_drop1", "s3_drop2",
+    "mt_c1_cubic", "mt_c1_average", "mt_c2_cubic", "mt_c2_secant",
+    "mt_c3_secant_bwd_an", "mt_c3_secant_bwd_lim", "mt_c3_secant_fwd_an", "mt_c3_secant_fwd_lim",
+    "mt_c3_cubic_bwd_an", "mt_c3_cubic_bwd_lim", "mt_c3_cubic_fwd_an", "mt_c3_cubic_fwd_lim",
+    "mt_c4", "mt_nan", "mu_u1", "mu_u2", "mu_u3", "mu_converged",
+    "ls_flip", "ls_dphi0_zero", "ls_open_closes", "ls_trial_closed", "ls_clamp_min", "ls_clamp_max", "ls_repeat",
+    "exit_nrm_zero", "exit_nrm_nan", "exit_max_iter", "exit_trans_eps")
+
+
+def census_reset():
+    lib().ndt_oracle_census_reset()
+
+
+def census_get():
+    """-> {name: hits since the last census_reset()}.  Process-wide and not thread safe: run single-threaded in between."""
+    out = np.zeros(len(CENSUS_NAMES), np.int32)
+    n = lib().ndt_oracle_census_get(out.ctypes.data, len(out))
+    assert n == len(CENSUS_NAMES), "CENSUS_NAMES is out of step with the NDT_CEN_* enum"
+    return dict(zip(CENSUS_NAMES, (int(v) for v in out)))
+
+
+def ring_enable(on):
+    lib().ndt_oracle_ring_enable(1 if on else 0)
+
+
+def ring_get(cap=8192):
+    """-> [rows, 10]: {kind (0 mt_trial, 1 mt_update), a_l, f_l, g_l, a_u, f_u, g_u, a_t, f_t, g_t} of the calls since ring_enable(1)."""
+    out = np.zeros((cap, 10))
+    return out[:lib().ndt_oracle_ring_get(out.ctypes.data, cap)].copy()
 
 
 # ---- SURVEY.md 8f row f2 (oracle/ndt_oracle.h) ----

@@ -112,16 +112,10 @@ def oracle_pins():
     L.ndt_oracle_step_matrix.argtypes = [C.POINTER(O.Params), vp, vp]
     L.ndt_oracle_map_override_cells.argtypes = [vp, vp, vp, vp]
     L.ndt_oracle_map_export_sums.argtypes = [vp, vp]
-    L.ndt_oracle_set_hooks.argtypes = [vp]
     return L
 
 
-SOLVE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
-INITP_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_double))
-
-
-class Hooks(C.Structure):
-    _fields_ = [("solve", SOLVE_FN), ("init_p", INITP_FN)]
+SOLVE_FN, INITP_FN, Hooks = O.SOLVE_FN, O.INITP_FN, O.Hooks      # ndt_oracle_hooks, declared once in oracle/ndt_oracle.py
 
 
 def map_sums(M):

@@ -4,7 +4,8 @@
 For a change that touches host code only.  From each library the .hip_fatbin section is taken and its gfx950 code
 object unbundled; then, keyed by symbol name, the disassembly of every function and, keyed by kernel name, every entry of
 the AMDGPU metadata note (registers, LDS, scratch, arguments) are compared.  The code objects as files may differ: where
-a template is first instantiated orders .text, so PC-relative literals are compared by the symbol they reach.  Needs no GPU.  Exit status 0: same names, every body and entry equal.
+a template is first instantiated orders .text, so PC-relative literals are compared by the symbol they reach and the
+alignment padding behind a function's last instruction is left out.  Needs no GPU.  Exit status 0: same names, every body and entry equal.
 """
 import os
 import re
@@ -69,6 +70,13 @@ def functions(co):
             ins = "s_add_u32 %s, %s, <%s>" % (m.group(1), m.group(2), resolve(pc + 4 + (lit - (1 << 32) if lit >> 31 else lit)))
         pc = int(tail.split(":")[0], 16) if ins.startswith("s_getpc_b64") else None
         out[name].append(ins)
+    padded = 0
+    for body in out.values():                          # the padding behind a function's last instruction up to the next
+        n = len(body)                                  # function's alignment: layout, not code
+        while body and body[-1] in ("s_nop 0", "..."):
+            body.pop()
+        padded += len(body) < n
+    print("    %s: trailing padding (s_nop 0 / ...) left out of %d of %d bodies" % (os.path.basename(co), padded, len(out)))
     return out
 
 
