@@ -146,6 +146,24 @@ struct StagedUpload {
   }
 };
 
+constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }      // a: a power of two
+
+// Consecutive regions of one block (a DevBuf of bytes, a pinned staging, or both with the same layout): take() gives the next
+// one's offset, at a multiple of `align` bytes (tables that kernels read as a whole: 256), `end` is the block's size -- what
+// ensure() / reserve() get --, at() a region's typed pointer in a block.  Size and pointers come from the one object.
+struct Regions {
+  size_t end = 0;
+  size_t take(size_t bytes, size_t align = 64) { const size_t o = align_up(end, align); end = o + bytes; return o; }
+  template <typename T, typename B> static T *at(B *base, size_t o) {
+    using Byte = std::conditional_t<std::is_const<B>::value, const char, char>;
+    return reinterpret_cast<T *>(reinterpret_cast<Byte *>(base) + o);
+  }
+};
+
+// offsets[0 .. n] relative to offsets[0]: what a host form uploads beside the points [offsets[0], offsets[n]) alone
+void rel_offsets(const uint64_t *offsets, size_t n, uint64_t *out) { for (size_t i = 0; i <= n; ++i) out[i] = offsets[i] - offsets[0]; }
+std::vector<uint64_t> rel_offsets(const uint64_t *offsets, size_t n) { std::vector<uint64_t> r(n + 1); rel_offsets(offsets, n, r.data()); return r; }
+
 // Run-time booleans as compile-time ones, to pick a kernel's template instance: f(std::true_type / std::false_type).
 template <typename F> void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
@@ -166,20 +184,10 @@ struct LaunchRing {
   bool deferred(unsigned long long k) const { return deferred_[covering(k) % kLen]; }
   // the events of the launch `b` launches before the latest (0: the latest); nullptr if it is not in the ring
   Event *back(int b) { return b < 0 || b >= kLen || (unsigned long long)b >= launches ? nullptr : events(launches - 1 - b); }
-  // Enters the next launch of context `self` as the latest one of that context that reads the maps whose lists of readers
-  // are lists[0 .. n) (ndt_map::readers; one list per distinct map).
+  // Enters the next launch of context `self` as the latest one of that context that reads maps[0 .. n) (each map once), in
+  // their lists of readers (ndt_map::readers).
   // Under g_live_mu: launches and builds on several contexts may come from several host threads.
-  using Readers = std::vector<std::pair<ndt_ctx *, unsigned long long>>;
-  void enter(ndt_ctx *self, Readers *const *lists, int n, bool deferred) {
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    deferred_[launches % kLen] = deferred;
-    for (int i = 0; i < n; ++i) {
-      Readers &readers = *lists[i];
-      auto it = std::find_if(readers.begin(), readers.end(), [&](const auto &r) { return r.first == self; });
-      if (it != readers.end()) it->second = launches; else readers.emplace_back(self, launches);
-    }
-    launches++;
-  }
+  void enter(ndt_ctx *self, const ndt_map *const *maps, int n, bool deferred);
 };
 
 }  // namespace
@@ -274,7 +282,7 @@ struct ndt_ctx {
   Event evb;                          // bounding box of the map build read back
   Stream side;                        // map build: bounding box + centroid fill beside the bucketing chain
   Event ev_fork, ev_join;
-  Event ev_scratch;                   // the scratch bracket (ScratchScope)
+  Event ev_scratch;                   // the scratch bracket (CallFrame)
   Stream fit_stream;                  // NDT_OPT_DEFER_FITNESS (created on first use)
   LaunchRing ring;
   // Occupancy grids: the event behind each of the last kOccEv calls that wrote a grid (integrate, clear, create), recorded on
@@ -324,8 +332,11 @@ int fail(ndt_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
-// The scratch bracket (ndt_ctx::ev_scratch): every entry point that uses the context's scratch opens it before the first and
-// closes it after the last use.
+// The call frame of every entry point that uses the context's scratch or queues one of its launches, opened behind the
+// entry point's refusals and early returns: open() makes the context's device current, picks the stream (the caller's, or the
+// context's for NULL) and opens the scratch bracket on it (ndt_ctx::ev_scratch) before the first use of the scratch; close()
+// closes it after the last.  Everything the call queues lies in between -- a host form's uploads into d_scan / d_off / d_tmp
+// and its read-backs too -- and a host form waits behind close() (close_and_wait).
 // (An event record is a barrier packet between kernels: a call on the context's own / registered stream -- which lives
 // as long as the registration -- records nothing; the event is recorded on that stream when a call on ANOTHER stream
 // arrives.  A call on a foreign stream records at once: the stream may be gone by the time the next call comes.)
@@ -333,12 +344,14 @@ int fail(ndt_ctx *ctx, int code, const std::string &msg) {
 // copy still leaves work on `st` that uses the context's scratch, and a later call on another stream must be ordered behind it
 // (round 5; VERDICT r04: launch_align failing after the match kernel was queued returned without it).  The quiet form (the
 // destructor) keeps the error message of the failure that is being returned.
-struct ScratchScope {
-  ndt_ctx *ctx; hipStream_t st; bool is_open = false;
-  ScratchScope(ndt_ctx *c, hipStream_t s) : ctx(c), st(s) {}
-  ScratchScope(const ScratchScope &) = delete;
-  ScratchScope &operator=(const ScratchScope &) = delete;
-  int open(bool deferred_launch = false) {
+struct CallFrame {
+  ndt_ctx *ctx; hipStream_t st = nullptr; bool is_open = false;
+  explicit CallFrame(ndt_ctx *c) : ctx(c) {}
+  CallFrame(const CallFrame &) = delete;
+  CallFrame &operator=(const CallFrame &) = delete;
+  int open(void *stream = nullptr, bool deferred_launch = false) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = stream ? (hipStream_t)stream : ctx->stream;
     // (NDT_OPT_DEFER_FITNESS) whatever uses the context's scratch next waits for the fitness kernels still running on the
     // context's own stream -- except the next deferred launch, which orders itself (launch_align)
     if (ctx->deferred_pending && !deferred_launch && ctx->ring.launches > 0) {
@@ -358,11 +371,63 @@ struct ScratchScope {
     ctx->scratch_stream = st; ctx->scratch_used = true;
     return NDT_OK;
   }
-  ~ScratchScope() {
+  int close_and_wait() {
+    const int rc = close();
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return NDT_OK;
+  }
+  ~CallFrame() {
     if (!is_open) return;
     const std::string keep = ctx->err, keep_tl = g_last_error;
     (void)close();
     ctx->err = keep; g_last_error = keep_tl;
+  }
+  // the whole frame of a device form: open, body(st), close
+  template <typename Body> static int run(ndt_ctx *ctx, void *stream, Body &&body, bool deferred_launch = false) {
+    CallFrame fr(ctx);
+    int rc = fr.open(stream, deferred_launch);
+    if (rc == NDT_OK) rc = body(fr.st);
+    return rc ? rc : fr.close();
+  }
+};
+
+void LaunchRing::enter(ndt_ctx *self, const ndt_map *const *maps, int n, bool deferred) {
+  std::lock_guard<std::mutex> lk(g_live_mu);
+  deferred_[launches % kLen] = deferred;
+  for (int i = 0; i < n; ++i) {
+    auto &readers = const_cast<ndt_map *>(maps[i])->readers;
+    auto it = std::find_if(readers.begin(), readers.end(), [&](const auto &r) { return r.first == self; });
+    if (it != readers.end()) it->second = launches; else readers.emplace_back(self, launches);
+  }
+  launches++;
+}
+
+// The map-read bracket of a call of `ctx` that queues kernels on st which read maps[0 .. n) (each map once).
+// begin(): st waits for the build of every map built on another stream (once per building context); ev[0 .. 2] are the ring's
+// events for the launch.  entered(code, ...), on EVERY way out once a kernel is queued: the launch has its end event (recorded
+// here unless a dispatch carried it) and its place in the context's ring and in each map's readers, so that a later call on
+// another stream and a build that must wait for it are ordered behind it; returns code (for NDT_OK: the record's failure, as
+// `who`'s).  deferred: work that the stream order of the map's builds does not cover (take_over_from_readers waits for it).
+struct MapRead {
+  ndt_ctx *ctx; hipStream_t st; const ndt_map *const *maps; int n;
+  Event *ev = nullptr;
+  int begin() {
+    std::vector<const ndt_ctx *> waited;
+    for (int i = 0; i < n; ++i) {
+      const ndt_ctx *b = maps[i]->ctx;
+      if (st == b->stream || std::find(waited.begin(), waited.end(), b) != waited.end()) continue;
+      HIP_TRY(ctx, hipStreamWaitEvent(st, b->evm1, 0));
+      waited.push_back(b);
+    }
+    ev = ctx->ring.events(ctx->ring.launches);
+    return NDT_OK;
+  }
+  int entered(int code, bool end_carried, bool deferred, const char *who) {
+    const hipError_t e = end_carried ? hipSuccess : hipEventRecord(ev[2], st);
+    ctx->ring.enter(ctx, maps, n, deferred);
+    if (e != hipSuccess && code == NDT_OK) return fail(ctx, NDT_E_HIP, std::string(who) + ": hipEventRecord: " + hipGetErrorString(e));
+    return code;
   }
 };
 
@@ -469,6 +534,9 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
   LaunchRing &R = ctx->ring;
   const unsigned long long L = R.launches;
+  const ndt_map *const *maps = mm ? mm->distinct.data() : &map;
+  MapRead rd{ctx, st, maps, mm ? (int)mm->distinct.size() : 1};
+  { const int rc = rd.begin(); if (rc) return rc; }
   // NDT_OPT_DEFER_FITNESS: launches take turns on the sets -- the fitness kernels of launch i (the context's own stream) read
   // set i & 1 while the match kernel of launch i + 1 (the caller's stream) fills the other
   ndt_ctx::LaunchSet &set = ctx->sets[defer ? L % ndt_ctx::kDeferSets : 0];
@@ -499,8 +567,10 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const PrepRec *prep = pset ? pset->recs.p : nullptr;
   const unsigned *prep_map = pset ? (const unsigned *)pset->maps.p : nullptr;
   // (every allocation of the launch in front of its first kernel: nothing below can fail for want of memory once work is queued)
-  const size_t far_cnt_bytes = ((size_t)B * 2 * sizeof(unsigned) + 15) & ~(size_t)15;
-  if (shared_scan && (rc = ctx->d_far.ensure(ctx, far_cnt_bytes + slots * sizeof(unsigned) + 16))) return rc;
+  Regions far;                                     // d_far: two counts per match, then the lists (FitJob::far_cnt_bytes: where they start)
+  far.take((size_t)B * 2 * sizeof(unsigned), 16);
+  const size_t far_cnt_bytes = far.take(slots * sizeof(unsigned) + 16, 16);
+  if (shared_scan && (rc = ctx->d_far.ensure(ctx, far.end))) return rc;
   // the chunk sums of the fitness kernels (FitPart, a chunk = 64 points; a match's chunks start at fit_part_of)
   if ((rc = ctx->d_fit_part.ensure(ctx, slots / 64 + (size_t)B + 1))) return rc;
   // control words: zero before every launch -- by the last kernel of the previous launch of this context
@@ -526,7 +596,7 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const int grid = helpers ? ncu : (B < ncu ? B : ncu);
   // timing: the events ride on the kernels' own dispatch packets (hipExtLaunchKernelGGL: start / stop of that kernel) -- an
   // event RECORD is a packet of its own between two kernels, three of them per launch cost the stream 6-10 us
-  Event *evr = R.events(L);
+  Event *evr = rd.ev;
   // (the pair check left out where it cannot fire -- accumulate_pair -- in the preset's own instantiation only)
   const bool chk = !(V.e_hi > 1.0 + 1e-6);
   // The kernel exists in five <SSE, INCL, CHK> instances per MULTI (not eight: it is the largest in the object); a single-map
@@ -545,22 +615,12 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   else if (sse)         match(yes, no, yes);
   else if (incl)        match(no, yes, yes);
   else                  match(no, no, yes);
-  // From here on a kernel that reads the map and the context's scratch is queued: whatever happens below, the launch is
-  // entered in the context's ring (its last event recorded) and in the map's list of readers, so that a later call on another
-  // stream and a build of this map that must wait for it (re-queued, or behind a deferred launch) are ordered behind it.
+  // From here on a kernel that reads the map and the context's scratch is queued (MapRead::entered).  A match launch on a
+  // foreign stream is deferred, to a build, only under NDT_OPT_DEFER_FITNESS: ordering it before a build is the caller's job
+  // (take_over_from_readers).  Its end event rides on fitness_reduce_kernel's dispatch unless that was not made.
   auto entered = [&](int code) {
-    if (code != NDT_OK) { hipError_t e = hipEventRecord(evr[2], st); (void)e; }      // (the dispatch that would have carried it was not made)
-    // this launch reads the map(s): a build must wait for it (ndt_map::readers)
-    if (mm) {
-      std::vector<LaunchRing::Readers *> lists;
-      for (const ndt_map *m : mm->distinct) lists.push_back(&const_cast<ndt_map *>(m)->readers);
-      R.enter(ctx, lists.data(), (int)lists.size(), defer);
-    } else {
-      LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
-      R.enter(ctx, &list, 1, defer);
-    }
     if (pset) pset->reader = (long long)L;
-    return code;
+    return rd.entered(code, /*end_carried=*/code == NDT_OK, defer, "launch_align");
   };
   if (ctx->inject_fault > 0 && --ctx->inject_fault == 0)      // NDT_OPT_INJECT_FAULT (tests): fail with the match kernel queued
     return entered(fail(ctx, NDT_E_HIP, "launch_align: injected fault behind the match kernel's dispatch (NDT_OPT_INJECT_FAULT)"));
@@ -1162,8 +1222,6 @@ static int check_build_batch(ndt_ctx *ctx, const float *const *xy, const size_t 
   return NDT_OK;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // One set of launches for every map: the bounding boxes (one kernel, ONE read-back and host wait), the grids by the rule of
 // the single-map path (grid_of_box, with each map's previous grid), one job-table upload, then each kernel of the chain once.
 // Each map comes out as ndt_map_build_dev would leave it.
@@ -1173,8 +1231,10 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
   const size_t S = (size_t)n_maps, npre = S + 1;
   // staging / device table: [BuildBatch | BoxJob x S | minmax prefixes] [BuildJob x S | prefixes of the other kernels]; the
   // first part goes up ahead of the boxes, the second (the job table proper) once the grids are known
-  const size_t o_box = align256(sizeof(BuildBatch)), o_pre0 = o_box + S * sizeof(BoxJob), o_jobs = align256(o_pre0 + npre * sizeof(unsigned));
-  const size_t o_pre = o_jobs + align256(S * sizeof(BuildJob)), bytes = o_pre + (kBbKernels - 1) * npre * sizeof(unsigned);
+  Regions T;
+  T.take(sizeof(BuildBatch), 256);
+  const size_t o_box = T.take(S * sizeof(BoxJob), 256), o_pre0 = T.take(npre * sizeof(unsigned), alignof(unsigned)),
+               o_jobs = T.take(S * sizeof(BuildJob), 256), o_pre = T.take((kBbKernels - 1) * npre * sizeof(unsigned), 256), bytes = T.end;
   int rc;
   if ((rc = ctx->bb_tab.reserve(ctx, bytes))) return rc;           // (waits for the previous batched build's upload)
   if ((rc = ctx->d_bb.ensure(ctx, bytes))) return rc;
@@ -1324,9 +1384,9 @@ int ndt_map_build_batch(ndt_ctx *ctx, const float *const *xy_host, const size_t 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the clouds, one after another in the context's staging (each at a 256-byte boundary)
   std::vector<size_t> off((size_t)n_maps);
-  size_t tot = 0;
-  for (int s = 0; s < n_maps; ++s) { off[s] = tot; tot += align256(n[s] * stride); }
-  if ((rc = ctx->d_bstage.ensure(ctx, tot))) return rc;
+  Regions C;
+  for (int s = 0; s < n_maps; ++s) off[s] = C.take(n[s] * stride, 256);
+  if ((rc = ctx->d_bstage.ensure(ctx, C.end))) return rc;
   std::vector<const float *> dxy((size_t)n_maps);
   for (int s = 0; s < n_maps; ++s) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bstage.p + off[s], xy_host[s], n[s] * stride, hipMemcpyHostToDevice, ctx->stream));
@@ -1436,11 +1496,12 @@ int ndt_align_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans, co
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!map || !scans || !offsets || !inits || !out || B <= 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: bad arguments");
   if (map->ctx->device != ctx->device) return fail(ctx, NDT_E_ARG, "ndt_align_batch: the map was built on another device");
-  if (total_points == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: total_points = 0");   // (before the scratch bracket opens)
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  // the map build may still be running on the stream of the context that built the map
-  if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  if (total_points == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: total_points = 0");
+  int rc;
+  const bool defer = ctx->defer_fitness != 0;
+  CallFrame fr(ctx);
+  if ((rc = fr.open(stream, defer))) return rc;
+  hipStream_t st = fr.st;
   // a set prepared for exactly this batch against exactly this grid and these parameters?  (A map whose speculative grid turned
   // out wrong has been queued again with another origin -- ndt_map_rebuild_end: NDT_REBUILT --, or a rebuild changed the
   // parameters, or another map took the old one's address, and the set no longer fits: the owners order their scans
@@ -1459,14 +1520,10 @@ int ndt_align_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scans, co
     HIP_TRY(ctx, hipStreamWaitEvent(st, pset->ready, 0));
     pset->valid = false;                           // one launch per prepared set (the caller prepares the next batch)
   }
-  int rc;
-  const bool defer = ctx->defer_fitness != 0;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open(defer))) return rc;
   if ((rc = launch_align(ctx, map, st, scans, (const unsigned long long *)offsets, B, shared_scan, total_points, inits,
                          out, nullptr, 0, nullptr, nullptr, pset, defer)))
-    return rc;                                     // (scope: closed all the same -- kernels may have been queued)
-  return scope.close();
+    return rc;
+  return fr.close();
 }
 
 // ms of the order kernel of the prepared set the context's most recent launches used (0 when none); blocks until it has run
@@ -1491,6 +1548,27 @@ __global__ void __launch_bounds__(256)
 repack_f2_kernel(const float *__restrict__ in, size_t stride, size_t n, float2 *__restrict__ out) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     out[i] = load_pt(in, stride, i);
+}
+
+// A scan of n points (records of `stride` bytes) as packed float2 on the device, inside the caller's frame: from host memory
+// (src_host: uploaded to d_scan, through d_tmp and repacked on the device when stride != 8, e.g. pcl::PointXYZ) or from device
+// memory (src_dev: used in place when stride == 8, else repacked into d_scan).
+int stage_scan_f2(ndt_ctx *ctx, hipStream_t st, const float *src_host, const float *src_dev, size_t n, size_t stride, const float **packed) {
+  if (!src_host && stride == 8) { *packed = src_dev; return NDT_OK; }
+  int rc;
+  if ((rc = ctx->d_scan.ensure(ctx, n * 8))) return rc;
+  if (stride == 8) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, src_host, n * 8, hipMemcpyHostToDevice, st));
+  } else {
+    if (src_host) {
+      if ((rc = ctx->d_tmp.ensure(ctx, n * stride))) return rc;
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp.p, src_host, n * stride, hipMemcpyHostToDevice, st));
+      src_dev = (const float *)ctx->d_tmp.p;
+    }
+    repack_f2_kernel<<<grid_for(n, 256), 256, 0, st>>>(src_dev, stride, n, (float2 *)ctx->d_scan.p);
+  }
+  *packed = (const float *)ctx->d_scan.p;
+  return NDT_OK;
 }
 
 #ifdef NDT_DIAG
@@ -1523,19 +1601,19 @@ void prof_report(const unsigned long long *hp, int B) {
 }
 #endif
 
-// The staged part of a host-pointer match call, from where the scratch bracket opens to where it closes -- the same for
-// one map and for many: scans (records of `stride` bytes, repacked to float2 on the device when stride != 8), offsets, initial
-// guesses and (multi-map calls) map_of go up, `launch(d_map_of, d_trace, d_rows, d_prof)` queues the batch between ev0 and
-// ev1, the records and the trace come back.  Asynchronous: align_host_finish waits.
+// The staged part of a host-pointer match call, its frame on the context's stream -- the same for one map and for many:
+// scans (stage_scan_f2), offsets, initial guesses and (multi-map calls) map_of go up, `launch(st, d_scans, d_map_of, d_trace,
+// d_rows, d_prof)` queues the batch between ev0 and ev1, the records and the trace come back.  Asynchronous:
+// align_host_finish waits.
 template <typename Launch>
-int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t stride, const uint64_t *offsets, int B,
+int align_host_staged(ndt_ctx *ctx, const float *scans, size_t stride, const uint64_t *offsets, int B,
                       int shared_scan, const double *inits, const int *map_of, ndt_result *out, double *trace, int trace_cap,
                       int *trace_rows, Launch &&launch) {
   int rc;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   const size_t nscan = shared_scan ? 1 : (size_t)B, ntot = (size_t)offsets[nscan];
-  if ((rc = ctx->d_scan.ensure(ctx, ntot * 8))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, nscan + 1))) return rc;
   if ((rc = ctx->d_init.ensure(ctx, (size_t)B * 3))) return rc;
   if ((rc = ctx->d_res.ensure(ctx, (size_t)B))) return rc;
@@ -1547,13 +1625,8 @@ int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t s
     HIP_TRY(ctx, hipMemsetAsync(d_trace, 0, (size_t)B * trace_cap * 64, st));
   }
   if (map_of && (rc = ctx->d_map_of.ensure(ctx, (size_t)B))) return rc;
-  if (stride == 8) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scans, ntot * 8, hipMemcpyHostToDevice, st));
-  } else {                                     // e.g. pcl::PointXYZ (16 bytes): strided upload, packed on the device
-    if ((rc = ctx->d_tmp.ensure(ctx, ntot * stride))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp.p, scans, ntot * stride, hipMemcpyHostToDevice, st));
-    repack_f2_kernel<<<grid_for(ntot, 256), 256, 0, st>>>((const float *)ctx->d_tmp.p, stride, ntot, (float2 *)ctx->d_scan.p);
-  }
+  const float *d_scans = nullptr;
+  if ((rc = stage_scan_f2(ctx, st, scans, nullptr, ntot, stride, &d_scans))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off.p, offsets, (nscan + 1) * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_init.p, inits, (size_t)B * 24, hipMemcpyHostToDevice, st));
   if (map_of) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_map_of.p, map_of, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1566,7 +1639,7 @@ int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t s
   if (want_prof) { d_prof = prof_buf.p; HIP_TRY(ctx, hipMemsetAsync(d_prof, 0, prof_bytes, st)); }
 #endif
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, st));
-  if ((rc = launch(map_of ? ctx->d_map_of.p : nullptr, d_trace, d_rows, d_prof))) return rc;
+  if ((rc = launch(st, d_scans, map_of ? ctx->d_map_of.p : nullptr, d_trace, d_rows, d_prof))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, st));
 #ifdef NDT_DIAG
   if (want_prof) {
@@ -1581,47 +1654,43 @@ int align_host_staged(ndt_ctx *ctx, hipStream_t st, const float *scans, size_t s
     HIP_TRY(ctx, hipMemcpyAsync(trace, d_trace, (size_t)B * trace_cap * 64, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(trace_rows, d_rows, (size_t)B * 4, hipMemcpyDeviceToHost, st));
   }
-  return scope.close();
+  return fr.close();
 }
 
-// Host-pointer matches against one map: the refusals, the wait for the map's build, then the staged part.
+// Host-pointer matches against one map: the refusals, then the staged part.
 int align_host_queue(ndt_ctx *ctx, const ndt_map *map, const float *scans, size_t stride, const uint64_t *offsets, int B,
                      int shared_scan, const double *inits, ndt_result *out, double *trace, int trace_cap, int *trace_rows) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!map || !scans || !offsets || !inits || !out || B <= 0 || stride < 8 || (stride & 3))
     return fail(ctx, NDT_E_ARG, "ndt_align_batch: bad arguments");
   if (map->ctx->device != ctx->device) return fail(ctx, NDT_E_ARG, "ndt_align_batch: the map was built on another device");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t nscan = shared_scan ? 1 : (size_t)B;
   const size_t npts = (size_t)(offsets[nscan] - offsets[0]);
   if (npts == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch: empty scans");
   for (size_t b = 0; b < nscan; ++b)
     if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch: offsets not monotone");
-  if (st != map->ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
-  return align_host_staged(ctx, st, scans, stride, offsets, B, shared_scan, inits, nullptr, out, trace, trace_cap, trace_rows,
-                           [&](const int *, double *d_trace, int *d_rows, unsigned long long *d_prof) {
-                             return launch_align(ctx, map, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B,
+  return align_host_staged(ctx, scans, stride, offsets, B, shared_scan, inits, nullptr, out, trace, trace_cap, trace_rows,
+                           [&](hipStream_t st, const float *d_scans, const int *, double *d_trace, int *d_rows, unsigned long long *d_prof) {
+                             return launch_align(ctx, map, st, d_scans, (const unsigned long long *)ctx->d_off.p, B,
                                                  shared_scan, (size_t)offsets[nscan], ctx->d_init.p, ctx->d_res.p, d_trace, trace_cap,
                                                  d_rows, d_prof);
                            });
 }
 
-// The end of a host-pointer wrapper whose result has a length only the device knows: W words come back (w[1]: the count when
-// W > 1, else w[0]), the stream is synchronised, `check(w)` -- the wrapper's own refusal, an NDT code -- looks at them, then
-// that many elements of `elem` bytes are copied and the stream is synchronised again.
+// The end of a host form whose result has a length only the device knows, inside the form's frame: W words come back (w[1]:
+// the count when W > 1, else w[0]) and are waited for, `check(w)` -- the form's own refusal, an NDT code -- looks at them, then
+// that many elements of `elem` bytes are copied, the frame is closed and the stream waited for.
 template <size_t W, typename Check>
-int read_back_counted(ndt_ctx *ctx, hipStream_t st, const uint64_t *d_words, const void *d_out, size_t elem, void *out_host, size_t *n_out,
-                      Check &&check) {
+int read_back_counted(CallFrame &fr, const uint64_t *d_words, const void *d_out, size_t elem, void *out_host, size_t *n_out, Check &&check) {
+  ndt_ctx *ctx = fr.ctx;
   uint64_t w[W] = {};
-  HIP_TRY(ctx, hipMemcpyAsync(w, d_words, sizeof(w), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipMemcpyAsync(w, d_words, sizeof(w), hipMemcpyDeviceToHost, fr.st));
+  HIP_TRY(ctx, hipStreamSynchronize(fr.st));
   if (const int rc = check(w)) return rc;
   const size_t cnt = (size_t)w[W > 1];
   *n_out = cnt;
-  if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_host, d_out, cnt * elem, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  if (cnt) HIP_TRY(ctx, hipMemcpyAsync(out_host, d_out, cnt * elem, hipMemcpyDeviceToHost, fr.st));
+  return fr.close_and_wait();
 }
 int no_check(const uint64_t *) { return NDT_OK; }
 
@@ -1673,20 +1742,6 @@ int check_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_
   return NDT_OK;
 }
 
-// Stream order behind the builds of the maps (each on the stream of the context that built it), then the launch.
-int queue_multi(ndt_ctx *ctx, MultiMaps &mm, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
-                size_t total_points, int shared_scan, const double *inits, ndt_result *out, bool defer,
-                unsigned long long *prof = nullptr) {
-  std::vector<const ndt_ctx *> waited;
-  for (const ndt_map *m : mm.distinct) {
-    if (st == m->ctx->stream || std::find(waited.begin(), waited.end(), m->ctx) != waited.end()) continue;
-    HIP_TRY(ctx, hipStreamWaitEvent(st, m->ctx->evm1, 0));
-    waited.push_back(m->ctx);
-  }
-  return launch_align(ctx, mm.maps[0], st, scans, offsets, B, shared_scan, total_points, inits, out, nullptr, 0, nullptr, prof,
-                      nullptr, defer, &mm);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1700,14 +1755,11 @@ int ndt_align_batch_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_ma
   if (!scans || !offsets || !inits || !out || B <= 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi_dev: bad arguments");
   if (total_points == 0) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi_dev: total_points = 0");
   mm.map_of = map_of_dev;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
   const bool defer = ctx->defer_fitness != 0;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open(defer))) return rc;
-  if ((rc = queue_multi(ctx, mm, st, scans, (const unsigned long long *)offsets, B, total_points, shared_scan, inits, out, defer)))
-    return rc;                                     // (scope: closed all the same -- kernels may have been queued)
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return launch_align(ctx, maps[0], st, scans, (const unsigned long long *)offsets, B, shared_scan, total_points, inits, out, nullptr, 0,
+                        nullptr, nullptr, nullptr, defer, &mm);
+  }, defer);
 }
 
 int ndt_align_batch_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_host,
@@ -1722,13 +1774,11 @@ int ndt_align_batch_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, 
     if (offsets[b + 1] < offsets[b]) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: offsets not monotone");
   const size_t ntot = (size_t)offsets[nscan];
   if (offsets[nscan] == offsets[0]) return fail(ctx, NDT_E_ARG, "ndt_align_batch_multi: empty scans");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  rc = align_host_staged(ctx, st, scans, 8, offsets, B, shared_scan, inits, map_of_host, out, nullptr, 0, nullptr,
-                         [&](const int *d_map_of, double *, int *, unsigned long long *d_prof) {
+  rc = align_host_staged(ctx, scans, 8, offsets, B, shared_scan, inits, map_of_host, out, nullptr, 0, nullptr,
+                         [&](hipStream_t st, const float *d_scans, const int *d_map_of, double *, int *, unsigned long long *d_prof) {
                            mm.map_of = d_map_of;
-                           return queue_multi(ctx, mm, st, (const float *)ctx->d_scan.p, (const unsigned long long *)ctx->d_off.p, B, ntot,
-                                              shared_scan, ctx->d_init.p, ctx->d_res.p, false, d_prof);
+                           return launch_align(ctx, maps[0], st, d_scans, (const unsigned long long *)ctx->d_off.p, B, shared_scan, ntot,
+                                               ctx->d_init.p, ctx->d_res.p, nullptr, 0, nullptr, d_prof, nullptr, false, &mm);
                          });
   return rc ? rc : align_host_finish(ctx);
 }
@@ -1762,8 +1812,7 @@ int ndt_align_batch_sharded(ndt_ctx *const *ctxs, const ndt_map *const *maps, in
     if (shared_scan) {
       rc = align_host_queue(ctxs[r], maps[r], scans, 8, offsets, n, 1, inits + 3 * (size_t)lo, out + lo, nullptr, 0, nullptr);
     } else {
-      offs[r].resize((size_t)n + 1);
-      for (int k = 0; k <= n; ++k) offs[r][k] = offsets[lo + k] - offsets[lo];
+      offs[r] = rel_offsets(offsets + lo, (size_t)n);
       rc = align_host_queue(ctxs[r], maps[r], scans + 2 * (size_t)offsets[lo], 8, offs[r].data(), n, 0, inits + 3 * (size_t)lo,
                             out + lo, nullptr, 0, nullptr);
     }
@@ -1904,31 +1953,46 @@ int ndt_align(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, siz
   return align_host(ctx, map, scan, stride, off, 1, 0, init, out, nullptr, 0, nullptr);
 }
 
+}  // extern "C"
+
+namespace {
+// ndt_eval_at / ndt_fitness_at on the context's stream, synchronous: the scan goes up, st waits for the map's build
+// (MapRead::begin; no ring entry), `launch(st, d_scan, d_part, blocks)` queues the kernel, `words` doubles per block come back.
+template <typename Launch>
+int probe_map(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, size_t stride, int words, std::vector<double> *hp, Launch &&launch) {
+  int rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  if ((rc = MapRead{ctx, st, &map, 1}.begin())) return rc;
+  const int grid = grid_for(n, 256, 1024);
+  hp->resize((size_t)grid * words);
+  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
+  if ((rc = ctx->d_tmp.ensure(ctx, hp->size() * 8))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
+  launch(st, (const float *)ctx->d_scan.p, (double *)ctx->d_tmp.p, grid);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(hp->data(), ctx->d_tmp.p, hp->size() * 8, hipMemcpyDeviceToHost, st));
+  return fr.close_and_wait();
+}
+}  // namespace
+
+extern "C" {
+
 int ndt_eval_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n, size_t stride,
                 const double p[3], double *score, double g[3], double H[9], double *pairs) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!map || !scan || n == 0 || !p || stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, "ndt_eval_at: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const int grid = grid_for(n, 256, 1024);
-  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
-  if ((rc = ctx->d_tmp.ensure(ctx, (size_t)grid * kAcc * 8))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
-  {
-    const MapView &V = map->view; const double sn = map->prm.snap_thresh;
-    const float *ds = (const float *)ctx->d_scan.p; double *dt = (double *)ctx->d_tmp.p;
+  std::vector<double> hp;
+  const int rc = probe_map(ctx, map, scan, n, stride, kAcc, &hp, [&](hipStream_t st, const float *ds, double *dt, int grid) {
     with_bool(map->prm.transform_sse != 0, [&](auto Sse) { with_bool(map->prm.radius_inclusive != 0, [&](auto Incl) {
-      ndt_eval_kernel<decltype(Sse)::value, decltype(Incl)::value><<<grid, 256, 0, st>>>(V, sn, map->prm.libm_f32, ds, stride, (int)n, p[0], p[1], p[2], dt);
+      ndt_eval_kernel<decltype(Sse)::value, decltype(Incl)::value><<<grid, 256, 0, st>>>(map->view, map->prm.snap_thresh, map->prm.libm_f32, ds, stride,
+                                                                                         (int)n, p[0], p[1], p[2], dt);
     }); });
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  std::vector<double> hp((size_t)grid * kAcc);
-  hipError_t e = hipMemcpyAsync(hp.data(), ctx->d_tmp.p, hp.size() * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, hipGetErrorString(e));
+  });
+  if (rc) return rc;
   double t[kAcc] = {0};
-  for (int b = 0; b < grid; ++b) for (int k = 0; k < kAcc; ++k) t[k] += hp[b * kAcc + k];
+  for (size_t b = 0; b < hp.size() / kAcc; ++b) for (int k = 0; k < kAcc; ++k) t[k] += hp[b * kAcc + k];
   const double w = map->view.d1 * map->view.d2;
   if (score) *score = -map->view.d1 * t[0];
   if (g) { g[0] = w * t[1]; g[1] = w * t[2]; g[2] = w * t[3]; }
@@ -1944,23 +2008,13 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n
                    float c, float s, float tx, float ty, double *fitness) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!map || !scan || n == 0 || !fitness || stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, "ndt_fitness_at: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const int grid = grid_for(n, 256, 1024);
-  if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
-  if ((rc = ctx->d_tmp.ensure(ctx, (size_t)grid * 16))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan, n * stride, hipMemcpyHostToDevice, st));
-  Tf32 T = {c, s, tx, ty};
-  ndt_fitness_kernel<<<grid, 256, 0, st>>>(map->view, (const float *)ctx->d_scan.p, stride, (int)n, T,
-                                           (double *)ctx->d_tmp.p);
-  HIP_TRY(ctx, hipGetLastError());
-  std::vector<double> hp((size_t)grid * 2);
-  hipError_t e = hipMemcpyAsync(hp.data(), ctx->d_tmp.p, hp.size() * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, hipGetErrorString(e));
+  std::vector<double> hp;
+  const int rc = probe_map(ctx, map, scan, n, stride, 2, &hp, [&](hipStream_t st, const float *ds, double *dt, int grid) {
+    ndt_fitness_kernel<<<grid, 256, 0, st>>>(map->view, ds, stride, (int)n, Tf32{c, s, tx, ty}, dt);
+  });
+  if (rc) return rc;
   double sum = 0, cnt = 0;
-  for (int b = 0; b < grid; ++b) { sum += hp[2 * b]; cnt += hp[2 * b + 1]; }
+  for (size_t b = 0; b < hp.size() / 2; ++b) { sum += hp[2 * b]; cnt += hp[2 * b + 1]; }
   *fitness = cnt > 0 ? sum / cnt : DBL_MAX;
   return NDT_OK;
 }
@@ -1968,7 +2022,7 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan, size_t n
 }  // extern "C"
 
 namespace {
-// The kernels of the pre-filter over B scans, inside the caller's scratch bracket (ScratchScope).  kTarget
+// The kernels of the pre-filter over B scans, inside the caller's frame (d_pf).  kTarget
 // (ndt_local_map_batch_dev): scan b's filtered points go behind prev[b] (device table, points at prev_stride), which
 // is copied in front of them, and out_offsets is the scan of prev[b].n + count b (of 0 where status[b] != NDT_OK);
 // total_prev_points: the sum of prev[b].n.
@@ -1977,12 +2031,13 @@ int pf_run(ndt_ctx *ctx, const float *raw_xy, size_t stride, const uint64_t *raw
            float leaf, float *out_xy, uint64_t *out_offsets, const PfPrev *prev, size_t prev_stride,
            size_t total_prev_points, const int *status, hipStream_t st) {
   int rc;
-  // filtered points at the raw offsets, then the per-scan counts
-  const size_t tmp_bytes = total_raw_points * sizeof(float2);
-  if ((rc = ctx->d_pf.ensure(ctx, 2 * tmp_bytes + (size_t)B * sizeof(unsigned)))) return rc;
-  float2 *tmp = (float2 *)ctx->d_pf.p;                                   // dense result at the raw offsets
-  float2 *sparse = (float2 *)((char *)ctx->d_pf.p + tmp_bytes);          // step-by-step kernel: flushes at the index of their cause
-  unsigned *counts = (unsigned *)((char *)ctx->d_pf.p + 2 * tmp_bytes);
+  // filtered points at the raw offsets (dense; the step-by-step kernel's flushes at the index of their cause), the per-scan counts
+  Regions R;
+  const size_t o_tmp = R.take(total_raw_points * sizeof(float2)), o_sparse = R.take(total_raw_points * sizeof(float2)),
+               o_counts = R.take((size_t)B * sizeof(unsigned));
+  if ((rc = ctx->d_pf.ensure(ctx, R.end))) return rc;
+  float2 *tmp = R.at<float2>(ctx->d_pf.p, o_tmp), *sparse = R.at<float2>(ctx->d_pf.p, o_sparse);
+  unsigned *counts = R.at<unsigned>(ctx->d_pf.p, o_counts);
   const int grid = B < 8 * ctx->num_cus ? B : 8 * ctx->num_cus;
   // scans of up to kPfSortMax points: ordered by slot, one thread per slot; longer ones: the step-by-step replay
   prefilter_sorted_kernel<<<grid, kPfSortThreads, 0, st>>>(raw_xy, stride, (const unsigned long long *)raw_offsets, B, leaf,
@@ -2007,18 +2062,13 @@ int ndt_prefilter_batch_dev(ndt_ctx *ctx, const float *raw_xy, size_t stride, co
   if (!raw_xy || !raw_offsets || !out_xy || !out_offsets || B <= 0 || total_raw_points == 0 || !(leaf > 0) ||
       stride < 8 || (stride & 7))
     return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  int rc;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  if ((rc = pf_run<false>(ctx, raw_xy, stride, raw_offsets, B, total_raw_points, leaf, out_xy, out_offsets, nullptr, 0, 0, nullptr, st)))
-    return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return pf_run<false>(ctx, raw_xy, stride, raw_offsets, B, total_raw_points, leaf, out_xy, out_offsets, nullptr, 0, 0, nullptr, st);
+  });
 }
 
-// B scans in host memory (raw_offsets[B + 1] in points of raw_xy_host): one upload, ndt_prefilter_batch_dev, the offsets
-// read back, one copy of the result.  out_xy_host needs room for every input point.  Empty scans stay empty.
+// B scans in host memory (raw_offsets[B + 1] in points of raw_xy_host): one upload, the filter, the offsets read back, one
+// copy of the result.  out_xy_host needs room for every input point.  Empty scans stay empty.
 int ndt_prefilter_batch(ndt_ctx *ctx, const float *raw_xy_host, size_t stride, const uint64_t *raw_offsets, int B,
                         float leaf, float *out_xy_host, uint64_t *out_offsets_host) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
@@ -2029,28 +2079,28 @@ int ndt_prefilter_batch(ndt_ctx *ctx, const float *raw_xy_host, size_t stride, c
   for (int b = 0; b < B; ++b)
     if (raw_offsets[b + 1] < raw_offsets[b])
       return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: scan " + std::to_string(b) + ": offsets decrease");
-  const size_t n = (size_t)(raw_offsets[B] - raw_offsets[0]);
+  const size_t n = (size_t)(raw_offsets[B] - raw_offsets[0]), B1 = (size_t)B + 1;
   if (n && (!raw_xy_host || !out_xy_host)) return fail(ctx, NDT_E_ARG, "ndt_prefilter_batch: NULL array (raw_xy or out_xy)");
   if (n == 0) { for (int b = 0; b <= B; ++b) out_offsets_host[b] = 0; return NDT_OK; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   int rc;
-  const size_t ib = (n * stride + 15) & ~(size_t)15;
-  if ((rc = ctx->d_scan.ensure(ctx, ib + n * sizeof(float2)))) return rc;
-  if ((rc = ctx->d_off.ensure(ctx, 2 * ((size_t)B + 1)))) return rc;
-  float *d_in = (float *)ctx->d_scan.p, *d_out = (float *)((char *)ctx->d_scan.p + ib);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions R;
+  const size_t o_in = R.take(n * stride), o_out = R.take(n * sizeof(float2));
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 2 * B1))) return rc;
+  float *d_in = R.at<float>(ctx->d_scan.p, o_in), *d_out = R.at<float>(ctx->d_scan.p, o_out);
   uint64_t *d_offs = ctx->d_off.p;                              // [0 .. B] raw, [B + 1 .. 2 B + 1] filtered
-  std::vector<uint64_t> rel((size_t)B + 1);
-  for (int b = 0; b <= B; ++b) rel[b] = raw_offsets[b] - raw_offsets[0];
+  const std::vector<uint64_t> rel = rel_offsets(raw_offsets, (size_t)B);
   HIP_TRY(ctx, hipMemcpyAsync(d_in, (const char *)raw_xy_host + (size_t)raw_offsets[0] * stride, n * stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_offs, rel.data(), rel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  if ((rc = ndt_prefilter_batch_dev(ctx, d_in, stride, d_offs, B, n, leaf, d_out, d_offs + B + 1, st))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_offsets_host, d_offs + B + 1, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if ((rc = pf_run<false>(ctx, d_in, stride, d_offs, B, n, leaf, d_out, d_offs + B1, nullptr, 0, 0, nullptr, st))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_offsets_host, d_offs + B1, B1 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   const size_t m = (size_t)out_offsets_host[B];
   if (m) HIP_TRY(ctx, hipMemcpyAsync(out_xy_host, d_out, m * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, float leaf, float *out_xy_host,
@@ -2058,19 +2108,11 @@ int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride, f
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!xy_host || n == 0 || !out_xy_host || !n_out || stride < 8 || (stride & 7) || !(leaf > 0))
     return fail(ctx, NDT_E_ARG, "ndt_prefilter: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  if ((rc = ctx->d_scan.ensure(ctx, n * stride + n * sizeof(float2)))) return rc;
-  if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
-  float *d_in = (float *)ctx->d_scan.p;
-  float *d_out = (float *)((char *)ctx->d_scan.p + n * stride);
-  uint64_t *d_offs = ctx->d_off.p;                              // [0..1] raw, [2..3] filtered
-  const uint64_t raw[2] = {0, (uint64_t)n};
-  HIP_TRY(ctx, hipMemcpyAsync(d_in, xy_host, n * stride, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_offs, raw, sizeof(raw), hipMemcpyHostToDevice, st));
-  if ((rc = ndt_prefilter_batch_dev(ctx, d_in, stride, d_offs, 1, n, leaf, d_out, d_offs + 2, st))) return rc;
-  return read_back_counted<2>(ctx, st, d_offs + 2, d_out, sizeof(float2), out_xy_host, n_out, no_check);
+  const uint64_t raw[2] = {0, (uint64_t)n};                     // one scan of the batch form
+  uint64_t filtered[2] = {0, 0};
+  const int rc = ndt_prefilter_batch(ctx, xy_host, stride, raw, 1, leaf, out_xy_host, filtered);
+  if (rc == NDT_OK) *n_out = (size_t)filtered[1];
+  return rc;
 }
 
 namespace {
@@ -2092,33 +2134,35 @@ int ndt_resample_capacity(size_t total_points, double space, double space_thre, 
   return NDT_OK;
 }
 
-int ndt_resample_batch_dev(ndt_ctx *ctx, const double *raw_xy, size_t stride, const uint64_t *raw_offsets, int B,
-                           size_t total_raw_points, double space, double space_thre, double *out_xy64, float *out_xy32,
-                           uint64_t *out_offsets, int *status, void *stream) {
+namespace {
+// What the resampler refuses of either form (the host form names its own refusals first); *cap: ndt_resample_capacity.
+int resample_check(ndt_ctx *ctx, const double *raw_xy, size_t stride, const uint64_t *raw_offsets, int B, size_t total_raw_points,
+                   double space, double space_thre, const void *out_xy64, const void *out_xy32, const uint64_t *out_offsets, size_t *cap) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  size_t cap = 0;
   if (!raw_xy || !raw_offsets || (!out_xy64 && !out_xy32) || !out_offsets || B <= 0 || total_raw_points == 0 ||
-      stride < 16 || (stride & 7) || ndt_resample_capacity(total_raw_points, space, space_thre, &cap))
+      stride < 16 || (stride & 7) || ndt_resample_capacity(total_raw_points, space, space_thre, cap))
     return fail(ctx, NDT_E_ARG, "ndt_resample_batch: bad arguments");
-  const size_t k_max = cap / total_raw_points, N = total_raw_points;
-  if (cap > SIZE_MAX / sizeof(double2) / 2) return fail(ctx, NDT_E_NOMEM, "ndt_resample_batch: scratch too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (*cap > SIZE_MAX / sizeof(double2) / 2) return fail(ctx, NDT_E_NOMEM, "ndt_resample_batch: scratch too large");
+  return NDT_OK;
+}
+
+// The resampler's kernels over B scans on st, inside the caller's frame (d_rs).
+int queue_resample(ndt_ctx *ctx, hipStream_t st, const double *raw_xy, size_t stride, const uint64_t *raw_offsets, int B, size_t N,
+                   double space, double space_thre, size_t cap, double *out_xy64, float *out_xy32, uint64_t *out_offsets, int *status) {
+  const size_t k_max = cap / N;
   int rc;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
   // scratch: walk outputs (k_max slots per raw point) | L | cnt | pos | tot | dist | bad
-  const size_t scr_b = cap * sizeof(double2), l_b = N * sizeof(double), c_b = N * sizeof(unsigned long long),
-               t_b = (size_t)B * sizeof(unsigned long long), d_b = (N * sizeof(unsigned) + 7) & ~(size_t)7;
-  if ((rc = ctx->d_rs.ensure(ctx, scr_b + l_b + 2 * c_b + t_b + d_b + (size_t)B * sizeof(int)))) return rc;
-  char *p = (char *)ctx->d_rs.p;
-  double2 *scr = (double2 *)p;                           p += scr_b;
-  double *L = (double *)p;                               p += l_b;
-  unsigned long long *cnt = (unsigned long long *)p;     p += c_b;
-  unsigned long long *pos = (unsigned long long *)p;     p += c_b;
-  unsigned long long *tot = (unsigned long long *)p;     p += t_b;
-  unsigned *dist = (unsigned *)p;                        p += d_b;
-  int *bad = (int *)p;
+  Regions R;
+  const size_t o_scr = R.take(cap * sizeof(double2)), o_l = R.take(N * sizeof(double)), o_cnt = R.take(N * sizeof(unsigned long long)),
+               o_pos = R.take(N * sizeof(unsigned long long)), o_tot = R.take((size_t)B * sizeof(unsigned long long)),
+               o_dist = R.take(N * sizeof(unsigned)), o_bad = R.take((size_t)B * sizeof(int));
+  if ((rc = ctx->d_rs.ensure(ctx, R.end))) return rc;
+  unsigned char *d = ctx->d_rs.p;
+  double2 *scr = R.at<double2>(d, o_scr);
+  double *L = R.at<double>(d, o_l);
+  unsigned long long *cnt = R.at<unsigned long long>(d, o_cnt), *pos = R.at<unsigned long long>(d, o_pos), *tot = R.at<unsigned long long>(d, o_tot);
+  unsigned *dist = R.at<unsigned>(d, o_dist);
+  int *bad = R.at<int>(d, o_bad);
   const unsigned long long *offs = (const unsigned long long *)raw_offsets;
   const double resync = std::max(space, space_thre);
   const unsigned gx = (unsigned)std::min<size_t>(64, (N / (size_t)B + 255) / 256 + 1), gy = (unsigned)std::min(B, 65535);
@@ -2132,7 +2176,20 @@ int ndt_resample_batch_dev(ndt_ctx *ctx, const double *raw_xy, size_t stride, co
                                                       (const unsigned long long *)out_offsets, (double2 *)out_xy64,
                                                       (float2 *)out_xy32);
   HIP_TRY(ctx, hipGetLastError());
-  return scope.close();
+  return NDT_OK;
+}
+}  // namespace
+
+int ndt_resample_batch_dev(ndt_ctx *ctx, const double *raw_xy, size_t stride, const uint64_t *raw_offsets, int B,
+                           size_t total_raw_points, double space, double space_thre, double *out_xy64, float *out_xy32,
+                           uint64_t *out_offsets, int *status, void *stream) {
+  size_t cap = 0;
+  int rc = resample_check(ctx, raw_xy, stride, raw_offsets, B, total_raw_points, space, space_thre, out_xy64, out_xy32, out_offsets, &cap);
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_resample(ctx, st, raw_xy, stride, raw_offsets, B, total_raw_points, space, space_thre, cap, out_xy64, out_xy32,
+                           out_offsets, status);
+  });
 }
 
 int ndt_resample(ndt_ctx *ctx, const double *xy_host, size_t n, size_t stride, double space, double space_thre,
@@ -2143,21 +2200,23 @@ int ndt_resample(ndt_ctx *ctx, const double *xy_host, size_t n, size_t stride, d
       ndt_resample_capacity(n, space, space_thre, &cap))
     return fail(ctx, NDT_E_ARG, "ndt_resample: bad arguments");
   if (n == 0) { *n_out = 0; return NDT_OK; }           // an empty scan stays empty (src/ScanPointResampler.cpp:7-8)
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  if ((rc = ctx->d_scan.ensure(ctx, n * stride + 15 + cap * sizeof(double2)))) return rc;
-  if ((rc = ctx->d_off.ensure(ctx, 5))) return rc;
-  double *d_in = (double *)ctx->d_scan.p;
-  double *d_out = (double *)((char *)ctx->d_scan.p + ((n * stride + 15) & ~(size_t)15));
-  uint64_t *d_offs = ctx->d_off.p;                              // [0..1] raw, [2..3] resampled, [4] status
   const uint64_t raw[2] = {0, (uint64_t)n};
+  int rc = resample_check(ctx, xy_host, stride, raw, 1, n, space, space_thre, out_xy_host, nullptr, raw, &cap);
+  if (rc) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions R;
+  const size_t o_in = R.take(n * stride), o_out = R.take(cap * sizeof(double2));
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
+  if ((rc = ctx->d_off.ensure(ctx, 5))) return rc;
+  double *d_in = R.at<double>(ctx->d_scan.p, o_in), *d_out = R.at<double>(ctx->d_scan.p, o_out);
+  uint64_t *d_offs = ctx->d_off.p;                              // [0..1] raw, [2..3] resampled, [4] status
   HIP_TRY(ctx, hipMemcpyAsync(d_in, xy_host, n * stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_offs, raw, sizeof(raw), hipMemcpyHostToDevice, st));
-  if ((rc = ndt_resample_batch_dev(ctx, d_in, stride, d_offs, 1, n, space, space_thre, d_out, nullptr, d_offs + 2,
-                                   (int *)(d_offs + 4), st)))
+  if ((rc = queue_resample(ctx, st, d_in, stride, d_offs, 1, n, space, space_thre, cap, d_out, nullptr, d_offs + 2, (int *)(d_offs + 4))))
     return rc;
-  return read_back_counted<3>(ctx, st, d_offs + 2, d_out, sizeof(double2), out_xy_host, n_out, [&](const uint64_t *fo) {
+  return read_back_counted<3>(fr, d_offs + 2, d_out, sizeof(double2), out_xy_host, n_out, [&](const uint64_t *fo) {
     int scan_status = 0;
     memcpy(&scan_status, &fo[2], sizeof(int));
     return scan_status != NDT_OK ? fail(ctx, NDT_E_ARG, "ndt_resample: the scan holds a non-finite coordinate") : NDT_OK;
@@ -2212,51 +2271,68 @@ int ndt_fuse_batch_dev(ndt_ctx *ctx, const ndt_result *results, const double *pr
   return NDT_OK;
 }
 
-int ndt_remove_neighbors_dev(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy,
-                             size_t list_stride, size_t n_list, double thre_neighbor, float *out_xy, uint64_t *n_out,
-                             void *stream) {
+namespace {
+// What the neighbour removal refuses of either form (the host form names its own refusals first).
+int remove_neighbors_check(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy, size_t list_stride,
+                           size_t n_list, const float *out_xy, const void *n_out) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!base_xy || n_base == 0 || n_base > (size_t)INT32_MAX || n_list > (size_t)INT32_MAX || (n_list && !list_xy) ||
       !out_xy || !n_out || base_stride < 8 || (base_stride & 7) || (n_list && (list_stride < 8 || (list_stride & 7))))
     return fail(ctx, NDT_E_ARG, "ndt_remove_neighbors: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  return NDT_OK;
+}
+
+// The three kernels on st, inside the caller's frame (d_rn).
+int queue_remove_neighbors(ndt_ctx *ctx, hipStream_t st, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy,
+                           size_t list_stride, size_t n_list, double thre_neighbor, float *out_xy, uint64_t *n_out) {
   const int nblocks = (int)((n_base + kRnBlock - 1) / kRnBlock);
   int rc;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  if ((rc = ctx->d_rn.ensure(ctx, n_base + (size_t)nblocks * sizeof(int) + 16))) return rc;
-  int *block_count = (int *)ctx->d_rn.p;
-  unsigned char *keep = (unsigned char *)ctx->d_rn.p + (size_t)nblocks * sizeof(int);
+  Regions R;
+  const size_t o_count = R.take((size_t)nblocks * sizeof(int)), o_keep = R.take(n_base + 16);
+  if ((rc = ctx->d_rn.ensure(ctx, R.end))) return rc;
+  int *block_count = R.at<int>(ctx->d_rn.p, o_count);
+  unsigned char *keep = R.at<unsigned char>(ctx->d_rn.p, o_keep);
   remove_neighbors_flag_kernel<<<nblocks, kRnBlock, 0, st>>>(base_xy, base_stride, (int)n_base, list_xy, list_stride,
                                                              (int)n_list, rn_cutoff(thre_neighbor), keep, block_count);
   remove_neighbors_scan_kernel<<<1, 1024, 0, st>>>(block_count, nblocks, (unsigned long long *)n_out);
   remove_neighbors_pack_kernel<<<nblocks, kRnBlock, 0, st>>>(base_xy, base_stride, (int)n_base, keep, block_count,
                                                              (float2 *)out_xy);
   HIP_TRY(ctx, hipGetLastError());
-  return scope.close();
+  return NDT_OK;
+}
+}  // namespace
+
+int ndt_remove_neighbors_dev(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy,
+                             size_t list_stride, size_t n_list, double thre_neighbor, float *out_xy, uint64_t *n_out,
+                             void *stream) {
+  int rc = remove_neighbors_check(ctx, base_xy, base_stride, n_base, list_xy, list_stride, n_list, out_xy, n_out);
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_remove_neighbors(ctx, st, base_xy, base_stride, n_base, list_xy, list_stride, n_list, thre_neighbor, out_xy, n_out);
+  });
 }
 
 int ndt_remove_neighbors(ndt_ctx *ctx, const float *base_xy_host, size_t base_stride, size_t n_base,
                          const float *list_xy_host, size_t list_stride, size_t n_list, double thre_neighbor,
                          float *out_xy_host, size_t *n_out) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!base_xy_host || n_base == 0 || !out_xy_host || !n_out || (n_list && !list_xy_host))
-    return fail(ctx, NDT_E_ARG, "ndt_remove_neighbors: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const size_t bb = n_base * base_stride, lb = n_list * list_stride, ob = n_base * sizeof(float2);
-  if ((rc = ctx->d_scan.ensure(ctx, bb + lb + ob + 64))) return rc;
-  char *d = (char *)ctx->d_scan.p;
-  float *d_base = (float *)d, *d_list = (float *)(d + bb), *d_out = (float *)(d + bb + ((lb + 15) & ~(size_t)15));
+  if (!n_list) list_stride = 8;
+  int rc = remove_neighbors_check(ctx, base_xy_host, base_stride, n_base, list_xy_host, list_stride, n_list, out_xy_host, n_out);
+  if (rc) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  const size_t bb = n_base * base_stride, lb = n_list * list_stride;
+  Regions R;
+  const size_t o_base = R.take(bb), o_list = R.take(lb), o_out = R.take(n_base * sizeof(float2) + 64);
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
+  float *d_base = R.at<float>(ctx->d_scan.p, o_base), *d_list = R.at<float>(ctx->d_scan.p, o_list), *d_out = R.at<float>(ctx->d_scan.p, o_out);
   HIP_TRY(ctx, hipMemcpyAsync(d_base, base_xy_host, bb, hipMemcpyHostToDevice, st));
   if (n_list) HIP_TRY(ctx, hipMemcpyAsync(d_list, list_xy_host, lb, hipMemcpyHostToDevice, st));
-  if ((rc = ndt_remove_neighbors_dev(ctx, d_base, base_stride, n_base, n_list ? d_list : nullptr, n_list ? list_stride : 8,
-                                     n_list, thre_neighbor, d_out, ctx->d_off.p, st)))
+  if ((rc = queue_remove_neighbors(ctx, st, d_base, base_stride, n_base, n_list ? d_list : nullptr, list_stride, n_list, thre_neighbor,
+                                   d_out, ctx->d_off.p)))
     return rc;
-  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, no_check);
+  return read_back_counted<1>(fr, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, no_check);
 }
 
 }  // extern "C"
@@ -2268,13 +2344,6 @@ namespace {
 // ndt_localmap.hip.h.  Device scratch (ctx->d_mm): [jobs][units][submaps][previous clouds], then the chain's own (MmScratch)
 // (the submap and previous-cloud tables only in a batched call, ndt_local_map_batch_dev: the upload ends behind them).
 size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
-size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
-
-// Consecutive regions of one block, each at a multiple of 64 bytes: take() gives the next one's offset, `end` is the block's size
-struct Regions {
-  size_t end = 0;
-  size_t take(size_t bytes) { const size_t o = up64(end); end = o + bytes; return o; }
-};
 
 // The scan triples of a call (of a step of a session set), their jobs still unbound (mm_bind).
 struct MmPlan {
@@ -2364,9 +2433,9 @@ int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, unsigned lo
   Regions R;
   R.take(nj * sizeof(MmJob));
   L.o_units = R.take(nu * sizeof(MmUnit)); L.o_subs = R.take(ns * sizeof(MmSub)); L.o_prev = R.take(ns * sizeof(PfPrev));
-  L.o_up = up64(R.end);
+  L.o_up = align_up(R.end, 64);
   L.x = MmScratch(R, P);
-  int rc;                                            // (the scratch bracket around mm_prepare + mm_run is the caller's: ScratchScope)
+  int rc;                                            // (the frame around mm_prepare + mm_run is the caller's)
   if ((rc = ctx->d_mm.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->mm_tab.reserve(ctx, L.o_up))) return rc;      // (waits for the previous call's upload)
   char *h = (char *)ctx->mm_tab.h.p;
@@ -2424,6 +2493,59 @@ int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t ns, float *cloud_xy, ui
                         (float2 *)cloud_xy, (unsigned long long *)cloud_off, status, st);
 }
 
+// What the difference extraction refuses of either form (the host form names its own refusals first).
+int difference_check(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy, size_t test_stride,
+                     size_t n_test, double resol, const float *out_xy, const void *n_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if ((n_base && !base_xy) || !test_xy || n_test == 0 || n_base + n_test > (size_t)(1u << 30) || !out_xy || !n_out ||
+      base_stride < 8 || (base_stride & 7) || test_stride < 8 || (test_stride & 7) || !(resol > 0.0) || !std::isfinite(resol))
+    return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
+  return NDT_OK;
+}
+
+// One job on st, inside the caller's frame: the difference list goes straight to out_xy, its count to n_out.
+int queue_difference(ndt_ctx *ctx, hipStream_t st, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy,
+                     size_t test_stride, size_t n_test, double resol, float *out_xy, uint64_t *n_out) {
+  MmPlan P;
+  P.sa = base_stride; P.sb = test_stride;
+  P.add(base_xy, base_xy, test_xy, n_base, 0, n_test);
+  MmLayout L;
+  int rc;
+  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, (unsigned long long *)n_out, &L))) return rc;
+  return mm_run(ctx, L, resol, 0.0, nullptr, nullptr, st);
+}
+
+// What the assembly of one submap refuses of either form (the host form names its own refusals first).
+int make_map_check(ndt_ctx *ctx, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans, int remove_moving,
+                   double resol, double thre_neighbor, const float *out_xy, const void *n_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!scans_xy || !offsets || n_scans <= 0 || n_scans > (1 << 20) || !out_xy || !n_out || stride < 8 || (stride & 7) ||
+      (remove_moving && (!(resol > 0.0) || !std::isfinite(resol) || !std::isfinite(thre_neighbor))))
+    return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
+  for (int i = 0; i < n_scans; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)(1u << 29))
+      return fail(ctx, NDT_E_ARG, "ndt_make_map: offsets must be non-decreasing, scans below 2^29 points");
+  return NDT_OK;
+}
+
+// One submap on st, inside the caller's frame; scans_xy is device memory, offsets host memory.
+int queue_make_map(ndt_ctx *ctx, hipStream_t st, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans,
+                   int first_submap, int newest, int remove_moving, double resol, double thre_neighbor, float *out_xy, uint64_t *n_out) {
+  MmPlan P;
+  P.sa = P.sb = stride;
+  // (one submap; its resol and thre_neighbor reach the kernels as arguments, mm_run: the jobs' own copies stay unset)
+  const ndt_submap_desc D = {scans_xy, offsets, n_scans, first_submap, newest, remove_moving, 0.0, 0.0, nullptr, 0};
+  std::vector<MmPiece> pieces;
+  const size_t nu = submap_pieces(D, stride, 0.f, &P, &pieces);
+  P.unit_room = nu;
+  MmLayout L;
+  int rc;
+  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
+  fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
+  if (nu == 0) HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(uint64_t), st));
+  return mm_run(ctx, L, resol, thre_neighbor, out_xy, n_out, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2431,23 +2553,11 @@ extern "C" {
 int ndt_difference_extraction_dev(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base,
                                   const float *test_xy, size_t test_stride, size_t n_test, double resol, float *out_xy,
                                   uint64_t *n_out, void *stream) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if ((n_base && !base_xy) || !test_xy || n_test == 0 || n_base + n_test > (size_t)(1u << 30) || !out_xy || !n_out ||
-      base_stride < 8 || (base_stride & 7) || test_stride < 8 || (test_stride & 7) || !(resol > 0.0) || !std::isfinite(resol))
-    return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  MmPlan P;
-  P.sa = base_stride; P.sb = test_stride;
-  P.add(base_xy, base_xy, test_xy, n_base, 0, n_test);
-  MmLayout L;
-  int rc;
-  // the difference list is written straight to the caller's buffer, its count to the caller's counter
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, (unsigned long long *)n_out, &L))) return rc;
-  if ((rc = mm_run(ctx, L, resol, 0.0, nullptr, nullptr, st))) return rc;
-  return scope.close();
+  int rc = difference_check(ctx, base_xy, base_stride, n_base, test_xy, test_stride, n_test, resol, out_xy, n_out);
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_difference(ctx, st, base_xy, base_stride, n_base, test_xy, test_stride, n_test, resol, out_xy, n_out);
+  });
 }
 
 int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t base_stride, size_t n_base,
@@ -2458,20 +2568,20 @@ int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t ba
       (base_stride & 7) || test_stride < 8 || (test_stride & 7))
     return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
   if (n_test == 0) { *n_out = 0; return NDT_OK; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const size_t bb = (n_base * base_stride + 15) & ~(size_t)15, tb = (n_test * test_stride + 15) & ~(size_t)15;
-  if ((rc = ctx->d_scan.ensure(ctx, bb + tb + n_test * sizeof(float2) + 64))) return rc;
+  int rc = difference_check(ctx, base_xy_host, base_stride, n_base, test_xy_host, test_stride, n_test, resol, out_xy_host, n_out);
+  if (rc) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions R;
+  const size_t o_base = R.take(n_base * base_stride), o_test = R.take(n_test * test_stride), o_out = R.take(n_test * sizeof(float2) + 64);
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
-  char *d = (char *)ctx->d_scan.p;
-  float *d_base = (float *)d, *d_test = (float *)(d + bb), *d_out = (float *)(d + bb + tb);
+  float *d_base = R.at<float>(ctx->d_scan.p, o_base), *d_test = R.at<float>(ctx->d_scan.p, o_test), *d_out = R.at<float>(ctx->d_scan.p, o_out);
   if (n_base) HIP_TRY(ctx, hipMemcpyAsync(d_base, base_xy_host, n_base * base_stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_test, test_xy_host, n_test * test_stride, hipMemcpyHostToDevice, st));
-  if ((rc = ndt_difference_extraction_dev(ctx, d_base, base_stride, n_base, d_test, test_stride, n_test, resol, d_out,
-                                          ctx->d_off.p, st)))
-    return rc;
-  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
+  if ((rc = queue_difference(ctx, st, d_base, base_stride, n_base, d_test, test_stride, n_test, resol, d_out, ctx->d_off.p))) return rc;
+  return read_back_counted<1>(fr, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
     return *cnt == ~0ull ? fail(ctx, NDT_E_ARG, "ndt_difference_extraction: the clouds span more than 2^30 voxels") : NDT_OK;
   });
 }
@@ -2479,31 +2589,12 @@ int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t ba
 int ndt_make_map_dev(ndt_ctx *ctx, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans,
                      int first_submap, int newest, int remove_moving, double resol, double thre_neighbor, float *out_xy,
                      uint64_t *n_out, void *stream) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!scans_xy || !offsets || n_scans <= 0 || n_scans > (1 << 20) || !out_xy || !n_out || stride < 8 || (stride & 7) ||
-      (remove_moving && (!(resol > 0.0) || !std::isfinite(resol) || !std::isfinite(thre_neighbor))))
-    return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
-  for (int i = 0; i < n_scans; ++i)
-    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)(1u << 29))
-      return fail(ctx, NDT_E_ARG, "ndt_make_map: offsets must be non-decreasing, scans below 2^29 points");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  MmPlan P;
-  P.sa = P.sb = stride;
-  // (one submap; its resol and thre_neighbor reach the kernels as arguments, mm_run: the jobs' own copies stay unset)
-  const ndt_submap_desc D = {scans_xy, offsets, n_scans, first_submap, newest, remove_moving, 0.0, 0.0, nullptr, 0};
-  std::vector<MmPiece> pieces;
-  const size_t nu = submap_pieces(D, stride, 0.f, &P, &pieces);
-  P.unit_room = nu;
-  MmLayout L;
-  int rc;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
-  fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
-  if (nu == 0) HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(uint64_t), st));
-  if ((rc = mm_run(ctx, L, resol, thre_neighbor, out_xy, n_out, st))) return rc;
-  return scope.close();
+  int rc = make_map_check(ctx, scans_xy, stride, offsets, n_scans, remove_moving, resol, thre_neighbor, out_xy, n_out);
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_make_map(ctx, st, scans_xy, stride, offsets, n_scans, first_submap, newest, remove_moving, resol, thre_neighbor,
+                           out_xy, n_out);
+  });
 }
 
 int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const uint64_t *offsets, int n_scans,
@@ -2514,23 +2605,24 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
     return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
   const size_t total = (size_t)offsets[n_scans] - (size_t)offsets[0];
   if (total == 0) { *n_out = 0; return NDT_OK; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const size_t ib = (total * stride + 15) & ~(size_t)15;
+  int rc = make_map_check(ctx, scans_xy_host, stride, offsets, n_scans, remove_moving, resol, thre_neighbor, out_xy_host, n_out);
+  if (rc) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   const size_t out_pts = n_scans == 1 ? 2 * total : total;      // a lone scan is appended twice (first + newest)
-  if ((rc = ctx->d_scan.ensure(ctx, ib + out_pts * sizeof(float2) + 64))) return rc;
+  Regions R;
+  const size_t o_in = R.take(total * stride), o_out = R.take(out_pts * sizeof(float2) + 64);
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
-  char *d = (char *)ctx->d_scan.p;
-  float *d_in = (float *)d, *d_out = (float *)(d + ib);
+  float *d_in = R.at<float>(ctx->d_scan.p, o_in), *d_out = R.at<float>(ctx->d_scan.p, o_out);
   HIP_TRY(ctx, hipMemcpyAsync(d_in, (const char *)scans_xy_host + (size_t)offsets[0] * stride, total * stride,
                               hipMemcpyHostToDevice, st));
-  std::vector<uint64_t> rel((size_t)n_scans + 1);
-  for (int i = 0; i <= n_scans; ++i) rel[i] = offsets[i] - offsets[0];
-  if ((rc = ndt_make_map_dev(ctx, d_in, stride, rel.data(), n_scans, first_submap, newest, remove_moving, resol,
-                             thre_neighbor, d_out, ctx->d_off.p, st)))
+  const std::vector<uint64_t> rel = rel_offsets(offsets, (size_t)n_scans);
+  if ((rc = queue_make_map(ctx, st, d_in, stride, rel.data(), n_scans, first_submap, newest, remove_moving, resol, thre_neighbor, d_out,
+                           ctx->d_off.p)))
     return rc;
-  return read_back_counted<1>(ctx, st, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
+  return read_back_counted<1>(fr, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, [&](const uint64_t *cnt) {
     return *cnt == ~0ull ? fail(ctx, NDT_E_ARG, "ndt_make_map: a scan triple spans more than 2^30 voxels") : NDT_OK;
   });
 }
@@ -2576,18 +2668,10 @@ int check_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs,
   return NDT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
-                            float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status,
-                            void *stream) {
-  int rc = check_local_map_batch(ctx, subs, n_subs, stride, leaf, cloud_xy, cloud_off, target_xy, target_off, status,
-                                 "ndt_local_map_batch_dev");
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+// The assembly of every submap (and, with a target, the filter behind it) on st, inside the caller's frame; the scans and
+// previous clouds of `subs` are device memory, its offsets host memory.
+int queue_local_map_batch(ndt_ctx *ctx, hipStream_t st, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
+                          float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status) {
   // the triples (jobs) and the pieces of every submap's cloud
   MmPlan P;
   P.sa = P.sb = stride;
@@ -2610,8 +2694,7 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
     return fail(ctx, NDT_E_ARG, "ndt_local_map_batch_dev: more than 2^31 units of 256 points or scan triples in one call");
   P.unit_room = nu;
   MmLayout L;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
+  int rc;
   if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
   MmUnit *u = L.units;
   for (int s = 0; s < n_subs; ++s) {
@@ -2628,7 +2711,22 @@ int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_sub
                            stride, total_prev, status, st)))
       return rc;
   }
-  return scope.close();
+  return NDT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
+                            float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status,
+                            void *stream) {
+  int rc = check_local_map_batch(ctx, subs, n_subs, stride, leaf, cloud_xy, cloud_off, target_xy, target_off, status,
+                                 "ndt_local_map_batch_dev");
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_local_map_batch(ctx, st, subs, n_subs, stride, leaf, cloud_xy, cloud_off, target_xy, target_off, status);
+  });
 }
 
 int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
@@ -2637,23 +2735,25 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
   int rc = check_local_map_batch(ctx, subs, n_subs, stride, leaf, cloud_xy_host, cloud_off_host, target_xy_host,
                                  target_off_host, status_host, "ndt_local_map_batch");
   if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const bool want_target = target_xy_host != nullptr;
-  // every submap's scans and previous cloud into one host block (each at a 16-byte boundary), uploaded with ONE copy
+  // every submap's scans and previous cloud into one host block, uploaded with ONE copy; the clouds and the targets behind it
   const size_t S = (size_t)n_subs;
   std::vector<size_t> o_scan(S), o_prev(S);
-  size_t in_bytes = 0, cap_cloud = 0, total_prev = 0;
+  Regions R;
+  size_t cap_cloud = 0, total_prev = 0;
   for (size_t s = 0; s < S; ++s) {
     const ndt_submap_desc &D = subs[s];
-    o_scan[s] = in_bytes; in_bytes += ((size_t)(D.offsets[D.n_scans] - D.offsets[0]) * stride + 15) & ~(size_t)15;
-    o_prev[s] = in_bytes; in_bytes += (want_target ? (D.n_prev * stride + 15) & ~(size_t)15 : 0);
+    o_scan[s] = R.take((size_t)(D.offsets[D.n_scans] - D.offsets[0]) * stride);
+    o_prev[s] = R.take(want_target ? D.n_prev * stride : 0);
     cap_cloud += submap_points(D);
     total_prev += D.n_prev;
   }
-  const size_t cap_target = want_target ? cap_cloud + total_prev : 0;
-  const size_t o_cloud = in_bytes + 64, o_target = o_cloud + cap_cloud * sizeof(float2) + 64;
-  if ((rc = ctx->d_scan.ensure(ctx, o_target + cap_target * sizeof(float2) + 64))) return rc;
+  const size_t in_bytes = R.end, cap_target = want_target ? cap_cloud + total_prev : 0;
+  const size_t o_cloud = R.take(cap_cloud * sizeof(float2) + 64), o_target = R.take(cap_target * sizeof(float2) + 64);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, 3 * (S + 1)))) return rc;   // cloud_off | target_off | status (ints)
   std::vector<unsigned char> stage(in_bytes);
   std::vector<ndt_submap_desc> dsubs(subs, subs + S);
@@ -2664,8 +2764,7 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
     const size_t nb = (size_t)(D.offsets[D.n_scans] - D.offsets[0]) * stride;
     if (nb) memcpy(stage.data() + o_scan[s], (const char *)D.scans_xy + (size_t)D.offsets[0] * stride, nb);
     if (want_target && D.n_prev) memcpy(stage.data() + o_prev[s], D.prev_xy, D.n_prev * stride);
-    rel[s].resize((size_t)D.n_scans + 1);
-    for (int i = 0; i <= D.n_scans; ++i) rel[s][i] = D.offsets[i] - D.offsets[0];
+    rel[s] = rel_offsets(D.offsets, (size_t)D.n_scans);
     dsubs[s].scans_xy = (const float *)(d + o_scan[s]);
     dsubs[s].offsets = rel[s].data();
     dsubs[s].prev_xy = want_target && D.n_prev ? (const float *)(d + o_prev[s]) : nullptr;
@@ -2674,8 +2773,8 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
   if (in_bytes) HIP_TRY(ctx, hipMemcpyAsync(d, stage.data(), in_bytes, hipMemcpyHostToDevice, st));
   uint64_t *d_coff = ctx->d_off.p, *d_toff = d_coff + S + 1;
   int *d_status = (int *)(d_toff + S + 1);
-  if ((rc = ndt_local_map_batch_dev(ctx, dsubs.data(), n_subs, stride, leaf, (float *)(d + o_cloud), d_coff,
-                                    want_target ? (float *)(d + o_target) : nullptr, want_target ? d_toff : nullptr, d_status, st))) {
+  if ((rc = queue_local_map_batch(ctx, st, dsubs.data(), n_subs, stride, leaf, (float *)(d + o_cloud), d_coff,
+                                  want_target ? (float *)(d + o_target) : nullptr, want_target ? d_toff : nullptr, d_status))) {
     hipError_t e = hipStreamSynchronize(st); (void)e;          // (the staged block is read by the copy queued above)
     return rc;
   }
@@ -2688,8 +2787,7 @@ int ndt_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, s
   const size_t nc = (size_t)back[S], nt = want_target ? (size_t)back[2 * S + 1] : 0;
   if (nc) HIP_TRY(ctx, hipMemcpyAsync(cloud_xy_host, d + o_cloud, nc * sizeof(float2), hipMemcpyDeviceToHost, st));
   if (nt) HIP_TRY(ctx, hipMemcpyAsync(target_xy_host, d + o_target, nt * sizeof(float2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 }  // extern "C"
@@ -2883,13 +2981,13 @@ int score_check(ndt_ctx *ctx, const ndt_map *map, const void *scan, size_t n, si
   return NDT_OK;
 }
 
-// The sweep on st, inside the caller's scratch bracket: behind the map's build, one kernel, entered in the context's ring as a
-// reader of the map.  A sweep on another stream than the one that carries the map's builds is, to a build, what a deferred
-// launch is -- work its stream order does not cover -- and is entered as one: build_begin waits for its end.
+// The sweep on st, inside the caller's frame: one kernel that reads the map (MapRead).  A sweep on another stream than the one
+// that carries the map's builds is, to a build, what a deferred launch is -- work its stream order does not cover -- and is
+// entered as one.
 int queue_score(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scan, size_t n, size_t stride, const double *poses,
                 const Lattice &L, uint64_t P, double *score, unsigned *pairs) {
-  const bool foreign = st != map->ctx->stream;
-  if (foreign) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  MapRead rd{ctx, st, &map, 1};
+  { const int rc = rd.begin(); if (rc) return rc; }
   const MapView &V = map->view;
   const bool sse = map->prm.transform_sse != 0, incl = map->prm.radius_inclusive != 0;
   const bool chk = !(V.e_hi > 1.0 + 1e-6);            // (launch_align's rule, in the same instances)
@@ -2900,8 +2998,7 @@ int queue_score(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *s
   const uint64_t tiles = (P + kScoreTile - 1) / kScoreTile;
   const uint64_t want = ctx->workgroups > 0 ? (uint64_t)ctx->workgroups : (uint64_t)ctx->num_cus * per_cu;
   const unsigned grid = (unsigned)std::min<uint64_t>(tiles, want);
-  LaunchRing &R = ctx->ring;
-  Event *evr = R.events(R.launches);
+  Event *evr = rd.ev;
   auto sweep = [&](auto S, auto I, auto C) {
     hipExtLaunchKernelGGL((ndt_score_kernel<decltype(S)::value, decltype(I)::value, decltype(C)::value>), dim3(grid), dim3(kScoreBlock),
                           lds, st, evr[0], evr[1], 0, V, map->prm.libm_f32, scan, stride, (int)n, staged, poses, L,
@@ -2915,23 +3012,20 @@ int queue_score(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *s
   else                  sweep(no, no, yes);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_score: ") + hipGetErrorString(e));
-  // the kernel is queued: whatever happens below, the launch has its place in the ring and in the map's readers
-  const hipError_t e2 = hipEventRecord(evr[2], st);
-  LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
-  R.enter(ctx, &list, 1, foreign);
-  if (e2 != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_score: hipEventRecord: ") + hipGetErrorString(e2));
-  return NDT_OK;
+  return rd.entered(NDT_OK, /*end_carried=*/false, /*deferred=*/st != map->ctx->stream, "ndt_score");
 }
 
-// The pick on st, inside the caller's scratch bracket (d_sel).
+// The pick on st, inside the caller's frame (d_sel).
 int queue_select(ndt_ctx *ctx, hipStream_t st, const Lattice &L, uint64_t P, const double *score, const unsigned *pairs, int top_k,
                  int local_max, unsigned long long *cand, int *n_cand) {
   const size_t tiles = (size_t)((P + kSelTile - 1) / kSelTile);
-  const size_t sorted_bytes = align256(tiles * kSelTile * sizeof(unsigned short)), cnt_bytes = align256(tiles * sizeof(unsigned));
+  Regions R;
+  const size_t o_sorted = R.take(tiles * kSelTile * sizeof(unsigned short), 256), o_cnt = R.take(tiles * sizeof(unsigned), 256),
+               o_head = R.take(tiles * sizeof(unsigned), 256);
   int rc;
-  if ((rc = ctx->d_sel.ensure(ctx, sorted_bytes + 2 * cnt_bytes))) return rc;
-  unsigned short *sorted = (unsigned short *)ctx->d_sel.p;
-  unsigned *cnt = (unsigned *)(ctx->d_sel.p + sorted_bytes), *head = (unsigned *)(ctx->d_sel.p + sorted_bytes + cnt_bytes);
+  if ((rc = ctx->d_sel.ensure(ctx, R.end))) return rc;
+  unsigned short *sorted = R.at<unsigned short>(ctx->d_sel.p, o_sorted);
+  unsigned *cnt = R.at<unsigned>(ctx->d_sel.p, o_cnt), *head = R.at<unsigned>(ctx->d_sel.p, o_head);
   const unsigned grid = (unsigned)std::min<size_t>(tiles, (size_t)ctx->num_cus * 2);
   lattice_rank_kernel<<<grid, kSelTile, 0, st>>>(L, (unsigned long long)P, score, pairs, local_max, sorted, cnt, head);
   lattice_merge_kernel<<<1, kSelTile, 0, st>>>((unsigned long long)P, score, sorted, cnt, head, top_k, cand, n_cand);
@@ -2952,38 +3046,24 @@ int relocalize_impl(ndt_ctx *ctx, const ndt_map *map, const float *scan_host, co
   if (!lattice_count(&prm->lattice, &P)) return fail(ctx, NDT_E_ARG, f + ": bad lattice (a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
   const int K = prm->top_k;
   if (K < 1 || K > 1024) return fail(ctx, NDT_E_ARG, f + ": top_k must be in 1 .. 1024");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const Lattice L = lattice_of(prm->lattice);
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   // the volume, the candidates, the guesses and the records: one grow-only allocation
-  const size_t o_pairs = align256((size_t)P * 8), o_cand = o_pairs + align256((size_t)P * 4), o_ncand = o_cand + align256((size_t)K * 8),
-               o_init = o_ncand + 256, o_cscore = o_init + align256((size_t)K * 24), o_off = o_cscore + align256((size_t)K * 8),
-               o_res = o_off + 256, total = o_res + align256((size_t)K * sizeof(ndt_result));
-  if ((rc = ctx->d_rl.ensure(ctx, total))) return rc;
+  Regions R;
+  const size_t o_score = R.take((size_t)P * 8, 256), o_pairs = R.take((size_t)P * 4, 256), o_cand = R.take((size_t)K * 8, 256),
+               o_ncand = R.take(sizeof(int), 256), o_init = R.take((size_t)K * 24, 256), o_cscore = R.take((size_t)K * 8, 256),
+               o_off = R.take(2 * 8, 256), o_res = R.take((size_t)K * sizeof(ndt_result), 256);
+  if ((rc = ctx->d_rl.ensure(ctx, R.end))) return rc;
   unsigned char *base = ctx->d_rl.p;
-  double *d_score = (double *)base; unsigned *d_pairs = (unsigned *)(base + o_pairs);
-  unsigned long long *d_cand = (unsigned long long *)(base + o_cand); int *d_ncand = (int *)(base + o_ncand);
-  double *d_init = (double *)(base + o_init), *d_cscore = (double *)(base + o_cscore);
-  unsigned long long *d_off = (unsigned long long *)(base + o_off); ndt_result *d_res = (ndt_result *)(base + o_res);
+  double *d_score = R.at<double>(base, o_score); unsigned *d_pairs = R.at<unsigned>(base, o_pairs);
+  unsigned long long *d_cand = R.at<unsigned long long>(base, o_cand); int *d_ncand = R.at<int>(base, o_ncand);
+  double *d_init = R.at<double>(base, o_init), *d_cscore = R.at<double>(base, o_cscore);
+  unsigned long long *d_off = R.at<unsigned long long>(base, o_off); ndt_result *d_res = R.at<ndt_result>(base, o_res);
   // the scan, packed: what the match reads (the sweep reads the same copy)
-  const float *scan = scan_dev;
-  if (scan_host || stride != 8) {
-    if ((rc = ctx->d_scan.ensure(ctx, n * 8))) return rc;
-    if (scan_host && stride == 8) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan_host, n * 8, hipMemcpyHostToDevice, st));
-    } else {
-      const float *src = scan_dev;
-      if (scan_host) {
-        if ((rc = ctx->d_tmp.ensure(ctx, n * stride))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tmp.p, scan_host, n * stride, hipMemcpyHostToDevice, st));
-        src = (const float *)ctx->d_tmp.p;
-      }
-      repack_f2_kernel<<<grid_for(n, 256), 256, 0, st>>>(src, stride, n, (float2 *)ctx->d_scan.p);
-    }
-    scan = (const float *)ctx->d_scan.p;
-  }
+  const float *scan = nullptr;
+  if ((rc = stage_scan_f2(ctx, st, scan_host, scan_dev, n, stride, &scan))) return rc;
   const unsigned long long h_off[2] = {0ull, (unsigned long long)n};
   HIP_TRY(ctx, hipMemcpyAsync(d_off, h_off, sizeof(h_off), hipMemcpyHostToDevice, st));
   // sweep, pick, the candidates' poses -- then the call's one host wait before the match: how many there are
@@ -3004,8 +3084,7 @@ int relocalize_impl(ndt_ctx *ctx, const ndt_map *map, const float *scan_host, co
     HIP_TRY(ctx, hipMemcpyAsync(cand_score, d_cscore, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   }
   if (scores_host) HIP_TRY(ctx, hipMemcpyAsync(scores_host, d_score, (size_t)P * 8, hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if ((rc = fr.close_and_wait())) return rc;
   if (nc > 0) HIP_TRY(ctx, hipEventElapsedTime(&ctx->align_ms, ctx->ev0, ctx->ev1));
   // the shim's cost (src/PoseEstimator.cpp:43-46): the fitness of a converged match, else 1e7; lowest first, ties to the lower index
   double best_cost = 0.0;
@@ -3046,12 +3125,9 @@ int ndt_score_poses_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_d
   if (rc) return rc;
   if (!poses_dev || !score_dev) return fail(ctx, NDT_E_ARG, "ndt_score_poses_dev: NULL poses or score");
   if (P < 1 || P > (uint64_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_score_poses_dev: need 1 <= P <= 2^31 - 1 poses");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);                     // (no scratch of its own: the bracket keeps the context's launches in order)
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_score(ctx, map, st, scan_xy_dev, n, stride, poses_dev, Lattice{}, P, score_dev, pairs_dev))) return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {   // (no scratch of its own: the bracket keeps the context's launches in order)
+    return queue_score(ctx, map, st, scan_xy_dev, n, stride, poses_dev, Lattice{}, P, score_dev, pairs_dev);
+  });
 }
 
 int ndt_score_lattice_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_dev, size_t n, size_t stride,
@@ -3062,12 +3138,9 @@ int ndt_score_lattice_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy
   uint64_t P = 0;
   if (!lattice_count(lattice, &P))
     return fail(ctx, NDT_E_ARG, "ndt_score_lattice_dev: bad lattice (NULL, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_score(ctx, map, st, scan_xy_dev, n, stride, nullptr, lattice_of(*lattice), P, score_dev, pairs_dev))) return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_score(ctx, map, st, scan_xy_dev, n, stride, nullptr, lattice_of(*lattice), P, score_dev, pairs_dev);
+  });
 }
 
 int ndt_score_poses(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride, const double *poses_host,
@@ -3076,23 +3149,21 @@ int ndt_score_poses(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host,
   if (rc) return rc;
   if (!poses_host || !score_host) return fail(ctx, NDT_E_ARG, "ndt_score_poses: NULL poses or score");
   if (P < 1 || P > (uint64_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_score_poses: need 1 <= P <= 2^31 - 1 poses");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);
-  if ((rc = scope.open())) return rc;
-  const size_t o_score = align256((size_t)P * 24), o_pairs = o_score + align256((size_t)P * 8);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions R;
+  const size_t o_poses = R.take((size_t)P * 24, 256), o_score = R.take((size_t)P * 8, 256), o_pairs = R.take((size_t)P * 4, 256);
   if ((rc = ctx->d_scan.ensure(ctx, n * stride))) return rc;
-  if ((rc = ctx->d_rl.ensure(ctx, o_pairs + (size_t)P * 4))) return rc;
-  double *d_poses = (double *)ctx->d_rl.p, *d_score = (double *)(ctx->d_rl.p + o_score);
-  unsigned *d_pairs = (unsigned *)(ctx->d_rl.p + o_pairs);
+  if ((rc = ctx->d_rl.ensure(ctx, R.end))) return rc;
+  double *d_poses = R.at<double>(ctx->d_rl.p, o_poses), *d_score = R.at<double>(ctx->d_rl.p, o_score);
+  unsigned *d_pairs = R.at<unsigned>(ctx->d_rl.p, o_pairs);
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_scan.p, scan_xy_host, n * stride, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d_poses, poses_host, (size_t)P * 24, hipMemcpyHostToDevice, st));
   if ((rc = queue_score(ctx, map, st, (const float *)ctx->d_scan.p, n, stride, d_poses, Lattice{}, P, d_score, d_pairs))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(score_host, d_score, (size_t)P * 8, hipMemcpyDeviceToHost, st));
   if (pairs_host) HIP_TRY(ctx, hipMemcpyAsync(pairs_host, d_pairs, (size_t)P * 4, hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 int ndt_lattice_select_dev(ndt_ctx *ctx, const ndt_pose_lattice *lattice, const double *score_dev, const uint32_t *pairs_dev, int top_k,
@@ -3104,14 +3175,9 @@ int ndt_lattice_select_dev(ndt_ctx *ctx, const ndt_pose_lattice *lattice, const 
     return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: bad lattice (NULL, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
   if (top_k < 1 || top_k > 1024) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: top_k must be in 1 .. 1024");
   if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: an ndt_map_rebuild_begin is open on the context");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);
-  int rc;
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_select(ctx, st, lattice_of(*lattice), P, score_dev, pairs_dev, top_k, local_max, (unsigned long long *)cand_index_dev, n_cand_dev)))
-    return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_select(ctx, st, lattice_of(*lattice), P, score_dev, pairs_dev, top_k, local_max, (unsigned long long *)cand_index_dev, n_cand_dev);
+  });
 }
 
 int ndt_relocalize(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, size_t n, size_t stride, const ndt_reloc_params *prm,
@@ -3148,25 +3214,23 @@ int fit_points_check(ndt_ctx *ctx, const ndt_map *map, const void *scans, const 
   return NDT_OK;
 }
 
-// The two kernels on st, inside the caller's scratch bracket (d_fit_pts): behind the map's build, entered in the context's
-// ring as a reader of the map the way the score sweep is (queue_score) -- on another stream than the one that carries the
-// map's builds it is, to a build, what a deferred launch is.  The ring's events ride on the search kernel's dispatch.
+// The two kernels on st, inside the caller's frame (d_fit_pts): they read the map (MapRead), entered the way the score sweep
+// is (queue_score).  The ring's first two events ride on the search kernel's dispatch.
 int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
                      size_t total_points, int shared_scan, const void *tf, size_t tf_stride, double max_d2, float *d2,
                      ndt_fit_stats *stats) {
   int rc;
   const size_t n_parts = shared_scan ? (size_t)B * ((total_points + 63) / 64) : total_points / 64 + (size_t)B + 1;
   if (stats && (rc = ctx->d_fit_pts.ensure(ctx, n_parts))) return rc;        // (the call's one allocation, in front of its first kernel)
-  const bool foreign = st != map->ctx->stream;
-  if (foreign) HIP_TRY(ctx, hipStreamWaitEvent(st, map->ctx->evm1, 0));
+  MapRead rd{ctx, st, &map, 1};
+  if ((rc = rd.begin())) return rc;
   // queue_fitness's grid: workgroup w -> (match, block of the match) in fit_block_of; NDT_OPT_WORKGROUPS bounds it
   const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
   const size_t b8 = ((size_t)B + 7) / 8 * 8;
   size_t gx = std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
   if (ctx->workgroups > 0) gx = std::max<size_t>(1, std::min<size_t>(gx, (size_t)ctx->workgroups / b8));
   FitPtsPart *parts = stats ? ctx->d_fit_pts.p : nullptr;
-  LaunchRing &R = ctx->ring;
-  Event *evr = R.events(R.launches);
+  Event *evr = rd.ev;
   with_bool(map->prm.transform_sse != 0, [&](auto S) {
     hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value>), dim3((unsigned)(gx * b8)), dim3(256), 0, st, evr[0], evr[1], 0, map->view,
                           reinterpret_cast<const float2 *>(scans), offsets, B, shared_scan, (const unsigned char *)tf, tf_stride, max_d2, d2,
@@ -3174,17 +3238,12 @@ int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const flo
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
-  // the search is queued: whatever happens below, the call has its place in the ring and in the map's readers
   if (stats) {
     fit_points_close_kernel<<<dim3((unsigned)(((size_t)B + 3) / 4)), dim3(256), 0, st>>>(offsets, B, shared_scan, parts, stats);
     e = hipGetLastError();
   }
-  const hipError_t e2 = hipEventRecord(evr[2], st);
-  LaunchRing::Readers *list = &const_cast<ndt_map *>(map)->readers;
-  R.enter(ctx, &list, 1, foreign);
-  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: hipEventRecord: ") + hipGetErrorString(e2));
-  return NDT_OK;
+  return rd.entered(e != hipSuccess ? fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e)) : NDT_OK,
+                    /*end_carried=*/false, /*deferred=*/st != map->ctx->stream, "ndt_fit_points");
 }
 
 }  // namespace
@@ -3196,14 +3255,10 @@ int ndt_fit_points_batch_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan
                              float *d2_dev, ndt_fit_stats *stats_dev, void *stream) {
   int rc = fit_points_check(ctx, map, scans_xy_dev, offsets_dev, B, tf_dev, tf_stride_bytes, max_d2, d2_dev, stats_dev, "ndt_fit_points_batch_dev");
   if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_fit_points(ctx, map, st, scans_xy_dev, (const unsigned long long *)offsets_dev, B, total_points, shared_scan, tf_dev,
-                             tf_stride_bytes, max_d2, d2_dev, stats_dev)))
-    return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_fit_points(ctx, map, st, scans_xy_dev, (const unsigned long long *)offsets_dev, B, total_points, shared_scan, tf_dev,
+                             tf_stride_bytes, max_d2, d2_dev, stats_dev);
+  });
 }
 
 int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy_host, const uint64_t *offsets_host, int B,
@@ -3216,12 +3271,13 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
     if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, "ndt_fit_points_batch: offsets not monotone");
   const size_t ntot = (size_t)offsets_host[nscan];
   const size_t n_d2 = shared_scan ? (size_t)B * (size_t)(offsets_host[1] - offsets_host[0]) : ntot;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   // one upload: the offsets, the transforms (packed: 16 bytes each) and the scans, staged in pinned memory
-  const size_t o_tf = align256((nscan + 1) * 8), o_scan = o_tf + align256((size_t)B * 16), bytes = o_scan + ntot * 8;
+  Regions U;
+  U.take((nscan + 1) * 8, 256);
+  const size_t o_tf = U.take((size_t)B * 16, 256), o_scan = U.take(ntot * 8, 256), bytes = U.end;
   if ((rc = ctx->fp_tab.reserve(ctx, bytes))) return rc;
   if ((rc = ctx->d_scan.ensure(ctx, bytes))) return rc;
   if (d2_host && (rc = ctx->d_fit.ensure(ctx, n_d2 + 4))) return rc;
@@ -3238,9 +3294,7 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
     return rc;
   if (d2_host && n_d2) HIP_TRY(ctx, hipMemcpyAsync(d2_host, d_d2, n_d2 * sizeof(float), hipMemcpyDeviceToHost, st));
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, (size_t)B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 }  // extern "C"
@@ -3304,7 +3358,7 @@ struct OccCall {
   const void *origins; size_t origin_stride; double max_range2; ndt_occ_stats *stats;
 };
 
-// The table's upload and the two kernels on st, inside the caller's scratch bracket (d_occ); the grids are entered as written.
+// The table's upload and the two kernels on st, inside the caller's frame (d_occ); the grids are entered as written.
 int queue_occ(ndt_ctx *ctx, hipStream_t st, const OccCall &C) {
   int rc;
   const size_t job_cap = std::min<size_t>(C.total_points / (size_t)kOccRun + (size_t)C.B, (size_t)UINT32_MAX);
@@ -3443,14 +3497,13 @@ int ndt_occ_view(const ndt_occ *o, const uint32_t **cells_dev) {
 int ndt_occ_clear(ndt_ctx *ctx, ndt_occ *occ, void *stream) {
   int rc = occ_one_check(ctx, occ, "ndt_occ_clear");
   if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);                     // (no scratch: the bracket orders the call among the context's)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);   // (no scratch: the bracket orders the call among the context's)
+  if ((rc = fr.open(stream))) return rc;
+  hipStream_t st = fr.st;
   if ((rc = occ_touch(ctx, occ, st))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(occ->cells.p, 0, occ->cells.bytes, st));
   if ((rc = occ_wrote(ctx, &occ, 1, st))) return rc;
-  return scope.close();
+  return fr.close();
 }
 
 int ndt_occ_integrate_dev(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_dev, const float *xy_dev,
@@ -3458,14 +3511,10 @@ int ndt_occ_integrate_dev(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const i
                           size_t origin_stride_bytes, double max_range2, ndt_occ_stats *stats_dev, void *stream) {
   int rc = occ_integrate_check(ctx, occs, n_occ, xy_dev, offsets_dev, B, origins_dev, origin_stride_bytes, max_range2, "ndt_occ_integrate_dev");
   if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_occ(ctx, st, OccCall{occs, n_occ, nullptr, grid_of_dev, xy_dev, (const unsigned long long *)offsets_dev, B, total_points,
-                                       origins_dev, origin_stride_bytes, max_range2, stats_dev})))
-    return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_occ(ctx, st, OccCall{occs, n_occ, nullptr, grid_of_dev, xy_dev, (const unsigned long long *)offsets_dev, B, total_points,
+                                       origins_dev, origin_stride_bytes, max_range2, stats_dev});
+  });
 }
 
 int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *grid_of_host, const float *xy_host,
@@ -3476,10 +3525,9 @@ int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *
   for (int b = 0; b < B; ++b)
     if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, "ndt_occ_integrate: scan " + std::to_string(b) + ": offsets decrease");
   const size_t first = (size_t)offsets_host[0], ntot = (size_t)(offsets_host[B] - offsets_host[0]);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   // one upload: the offsets (relative), grid_of, the origins (packed: 16 bytes each) and the scans, staged in pinned memory
   Regions U;
   const size_t o_off = U.take(((size_t)B + 1) * 8), o_gof = U.take(grid_of_host ? (size_t)B * 4 : 0), o_org = U.take((size_t)B * 16),
@@ -3488,7 +3536,7 @@ int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *
   if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
   if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
   unsigned char *h = ctx->occ_up.h.p, *d = ctx->d_scan.p;
-  for (int b = 0; b <= B; ++b) { const uint64_t v = offsets_host[b] - offsets_host[0]; memcpy(h + o_off + (size_t)b * 8, &v, 8); }
+  rel_offsets(offsets_host, (size_t)B, U.at<uint64_t>(h, o_off));
   if (grid_of_host) memcpy(h + o_gof, grid_of_host, (size_t)B * 4);
   for (int b = 0; b < B; ++b) memcpy(h + o_org + (size_t)b * 16, (const unsigned char *)origins_host + (size_t)b * origin_stride_bytes, 16);
   if (ntot) memcpy(h + o_xy, xy_host + 2 * first, ntot * 8);
@@ -3498,9 +3546,7 @@ int ndt_occ_integrate(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const int *
                                        (const unsigned long long *)(d + o_off), B, ntot, d + o_org, 16, max_range2, d_stats})))
     return rc;
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 int ndt_occ_render_dev(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_dev, void *stream) {
@@ -3508,12 +3554,9 @@ int ndt_occ_render_dev(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out
   if (rc) return rc;
   if (!out_dev) return fail(ctx, NDT_E_ARG, "ndt_occ_render_dev: NULL out");
   if (min_obs < 1) return fail(ctx, NDT_E_ARG, "ndt_occ_render_dev: min_obs below 1");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  ScratchScope scope(ctx, st);                     // (no scratch: the bracket orders the call among the context's)
-  if ((rc = scope.open())) return rc;
-  if ((rc = queue_occ_render(ctx, occ, min_obs, (signed char *)out_dev, st))) return rc;
-  return scope.close();
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {   // (no scratch: the bracket orders the call among the context's)
+    return queue_occ_render(ctx, occ, min_obs, (signed char *)out_dev, st);
+  });
 }
 
 int ndt_occ_render(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_host) {
@@ -3521,16 +3564,13 @@ int ndt_occ_render(ndt_ctx *ctx, ndt_occ *occ, uint32_t min_obs, int8_t *out_hos
   if (rc) return rc;
   if (!out_host) return fail(ctx, NDT_E_ARG, "ndt_occ_render: NULL out");
   if (min_obs < 1) return fail(ctx, NDT_E_ARG, "ndt_occ_render: min_obs below 1");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   if ((rc = ctx->d_tmp.ensure(ctx, occ->n_cells))) return rc;
   if ((rc = queue_occ_render(ctx, occ, min_obs, (signed char *)ctx->d_tmp.p, st))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(out_host, ctx->d_tmp.p, occ->n_cells, hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return NDT_OK;
+  return fr.close_and_wait();
 }
 
 int ndt_occ_counts(ndt_ctx *ctx, ndt_occ *occ, uint32_t *hit_host, uint32_t *pass_host) {
@@ -3578,16 +3618,15 @@ int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsi
     own[(size_t)i].n = Q.scan_off[k + 1] - Q.scan_off[k];
     total += (size_t)own[(size_t)i].n;
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  ScratchScope scope(ctx, st);                     // (every return below closes the bracket)
-  if ((rc = scope.open())) return rc;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
   if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
   ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
   if ((rc = queue_occ(ctx, st, OccCall{taken.data(), S, own.data(), nullptr, nullptr, nullptr, S, total, s->last_pose.p, 24, max_range2, d_stats})))
     return rc;
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
-  if ((rc = scope.close())) return rc;
+  if ((rc = fr.close())) return rc;
   if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
   return NDT_OK;
 }

@@ -327,8 +327,7 @@ int SsStep::front() {
                a_odo = A.take(odo_host ? (size_t)S * 24 : 0);
   SS_TRY(s->tab_a.reserve(ctx, A.end)); SS_TRY(s->d_tab_a.ensure(ctx, A.end));
   unsigned char *h = s->tab_a.h.p;
-  uint64_t *ro = (uint64_t *)(h + a_off);
-  for (int b = 0; b <= S; ++b) ro[b] = raw_offsets[b] - raw_offsets[0];
+  rel_offsets(raw_offsets, (size_t)S, A.at<uint64_t>(h, a_off));
   memcpy(h + a_mode, mode.data(), (size_t)S * 4); memcpy(h + a_mapof, map_of.data(), (size_t)S * 4);
   if (odo_host) memcpy(h + a_odo, odo_host, (size_t)S * 24);
   HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, A.end, st));
@@ -515,12 +514,12 @@ int SsStep::behind() {
   seg_copy_kernel<<<dim3(ss_gx(cap_cloud, S), (unsigned)std::min(4 * S, 65535)), 256, 0, st>>>((const SsCopy *)(db + o_seg), 4 * S);
   HIP_TRY(ctx, hipGetLastError());
   {
-    ScratchScope scope(ctx, st);                  // (the filter's scratch is the context's)
-    SS_TRY(scope.open());
+    CallFrame fr(ctx);                            // (the filter's scratch is the context's)
+    SS_TRY(fr.open(st));
     SS_TRY(pf_run<true>(ctx, (const float *)s->cloud[cur].p, sizeof(float2), s->cloud_off.p, S, std::max<size_t>(cap_cloud, 1), P.leaf,
                         (float *)s->target[cur].p, s->target_off.p, (const PfPrev *)(db + o_prev), sizeof(float2), total_prev,
                         s->status.p, st));
-    SS_TRY(scope.close());
+    SS_TRY(fr.close());
   }
   // host wait 2: the target and cloud offsets, the prefix lengths, the status
   Regions R;
