@@ -128,6 +128,28 @@ __device__ __forceinline__ float2 load_pt(const float *xy, size_t stride, size_t
   return *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(xy) + i * stride);
 }
 
+// The scan of match b in a launch's arrays: n points from point o0 of `scans`.  offsets holds B + 1 prefix offsets, or --
+// shared_scan -- the one scan [offsets[0], offsets[1]) that every match uses.  slot: where match b's own elements start in the
+// launch's per-point arrays (the ordered copies, fit, far_idx, d2): a scan of its own lies where it lies in `scans`, matches that
+// share one have n elements each.  For the fitness kernels; ndt_align_kernel and ndt_order_kernel state the rule themselves
+// (LOG R17.1: taking it out of the match kernel reschedules it).
+struct ScanSpan {
+  unsigned long long o0; int n;
+  __device__ __forceinline__ size_t slot(int shared_scan, int b) const { return shared_scan ? (size_t)b * (size_t)n : (size_t)o0; }
+};
+__device__ __forceinline__ ScanSpan scan_span(const unsigned long long *__restrict__ offsets, int shared_scan, int b) {
+  const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
+  const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
+  return ScanSpan{o0, (int)(o1 - o0)};
+}
+
+// MULTI launches (ndt_align_batch_multi_dev): match b reads the map views[map_of[b]] (map_of null: views[b]); the index of a
+// match is checked before anything is read through it.  -1: outside [0, n_maps), the match has no map.
+__device__ __forceinline__ int map_index_of(const int *__restrict__ map_of, int n_maps, int b) {
+  const int mi = map_of ? map_of[b] : b;
+  return (mi >= 0 && mi < n_maps) ? mi : -1;
+}
+
 // float32 matrix of the fp64 parameter vector (a4): Translation3f(float(p0), float(p1), 0) *
 // AngleAxisf(float(p2), Z); std::cos / std::sin(float): glibc's cosf / sinf (libm_f32) or modelled as correctly rounded.
 __device__ __forceinline__ Tf32 tf_from_p(const double p[3], int libm_f32) {

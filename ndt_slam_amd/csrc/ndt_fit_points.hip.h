@@ -1,18 +1,19 @@
 // ndt_fit_points.hip.h -- ndt_fit_points_batch_dev: the distance of every scan point to its nearest raw map point, in the
 // caller's order, and getFitnessScore(max_range) from them (row a7; src/PoseEstimator.cpp:43 calls it without a range).
 // Part of libndt_mi355x.so: included by ndt_mi355x.hip inside its anonymous namespace behind ndt_fitness.hip.h, whose
-// search (nearest_prep / nearest_home / nearest_ring1_wave / nearest_far: path 2 of tests/test_gpu_fitness_geometry.py)
-// it uses as it is.  Not a standalone header.
+// search (lane_query -- nearest_prep / nearest_home / nearest_ring1_wave -- then nearest_far: path 2 of
+// tests/test_gpu_fitness_geometry.py) it uses as it is.  Not a standalone header.
 
 // ------------------------------------------------------------------------------------------
 // The order of summation.  Chunk k of a match is its points [64k, 64k + 64) in INPUT order -- not the
 // launch's voxel-ordered copy: the caller's indices are the only order that is the same for every way of calling.  A chunk's
 // two sums (every point with a distance / those with (double)d2 <= max_d2) are the wave butterfly over the 64 lanes'
 // (double)d2, 0.0 where the predicate fails; lane l of ONE wave adds the chunks l, l + 64, l + 128 ... in ascending order
-// and the butterfly adds the lanes: fitness_close_match's scheme.  Counts are whole numbers however they are added.  So a
-// match's d2 and ndt_fit_stats depend on (map, scan, transform, max_d2) alone, not on b, B, the other scans, the grid or
-// shared_scan.  A chunk's part is 32 bytes of the context's scratch (ndt_ctx::d_fit_pts), first chunk of match b at
-// fit_part_of: written by the wave that searched the chunk, read by the wave that closes the match.
+// and the butterfly adds the lanes: chunk_part and close_chunks, which fitness_close_match uses too.  Counts are whole
+// numbers however they are added.  So a match's d2 and ndt_fit_stats depend on (map, scan, transform, max_d2) alone, not
+// on b, B, the other scans, the grid or shared_scan.  A chunk's part is 32 bytes of the context's scratch
+// (ndt_ctx::d_fit_pts), first chunk of match b at fit_part_of: written by the wave that searched the chunk, read by the
+// wave that closes the match.
 // ------------------------------------------------------------------------------------------
 struct FitPtsPart { double s_all, s_in, n_dist, n_in; };
 static_assert(sizeof(FitPtsPart) == 32, "one 32-byte part per chunk");
@@ -34,30 +35,21 @@ fit_points_kernel(MapView M, const float2 *__restrict__ scans, const unsigned lo
   __shared__ RingLds ring[256 / 64];
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
-  const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-  const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-  const int n = (int)(o1 - o0);
+  const ScanSpan sp = scan_span(offsets, shared_scan, b);
+  const int n = sp.n;
   const Tf32 T = fit_tf_of(tf, tf_stride, b);
-  const float2 *pts = scans + o0;
-  float *out = d2 ? d2 + (shared_scan ? (size_t)b * (size_t)n : (size_t)o0) : nullptr;
-  FitPtsPart *part = parts ? parts + fit_part_of(b, n, o0, shared_scan) : nullptr;
+  const float2 *pts = scans + sp.o0;
+  float *out = d2 ? d2 + sp.slot(shared_scan, b) : nullptr;
+  FitPtsPart *part = parts ? parts + fit_part_of(sp, shared_scan, b) : nullptr;
   for (int i0 = bx * (int)blockDim.x + (int)(threadIdx.x & ~63u); i0 < n; i0 += gx * (int)blockDim.x) {
     const int i = i0 + (int)(threadIdx.x & 63u);
-    const float2 pt = pts[min(i, n - 1)];
-    float qx, qy;
-    tf_apply_t<SSE>(T, pt.x, pt.y, qx, qy);
-    const bool live = i < n && finite2(qx, qy);
-    if (!live) { qx = 0.f; qy = 0.f; }                           // (any address inside the grid; the result is dropped)
-    NearState S = nearest_home(M, qx, qy, nearest_prep(M, qx, qy));
-    if (!live) { S.more = false; S.rn[0] = S.rn[1] = S.rn[2] = S.rn[3] = 0; }
-    float best = nearest_ring1_wave(M, ring[threadIdx.x >> 6], qx, qy, S);
-    best = nearest_far(M, qx, qy, S, best);
-    if (out && i < n) out[i] = live ? best : INFINITY;
+    const LaneQuery Q = lane_query<SSE>(M, ring[threadIdx.x >> 6], T, pts, i, n);
+    const float best = nearest_far(M, Q.qx, Q.qy, Q.S, Q.best);
+    if (out && i < n) out[i] = Q.live ? best : INFINITY;
     if (part) {                                                  // (uniform) i0 is a multiple of 64: this wave's points are chunk i0 / 64
-      const bool has = live && best < INFINITY, in = has && (double)best <= max_d2;
-      const double sa = wave_sum(has ? (double)best : 0.0), si = wave_sum(in ? (double)best : 0.0);
-      const int ca = __popcll(__ballot(has)), ci = __popcll(__ballot(in));
-      if ((threadIdx.x & 63u) == 0u) part[i0 >> 6] = FitPtsPart{sa, si, (double)ca, (double)ci};
+      const bool has = Q.live && best < INFINITY;
+      const FitPart all = chunk_part(has, best), in = chunk_part(has && (double)best <= max_d2, best);
+      if ((threadIdx.x & 63u) == 0u) part[i0 >> 6] = FitPtsPart{all.sum, in.sum, all.cnt, in.cnt};
     }
   }
 }
@@ -68,28 +60,14 @@ fit_points_close_kernel(const unsigned long long *__restrict__ offsets, int B, i
                         const FitPtsPart *__restrict__ parts, ndt_fit_stats *__restrict__ stats) {
   const int lane = threadIdx.x & 63, b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (b >= B) return;                                            // (whole waves)
-  const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-  const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-  const int n = (int)(o1 - o0), nch = (n + 63) >> 6;
-  const FitPtsPart *part = parts + fit_part_of(b, n, o0, shared_scan);
-  double sa = 0.0, si = 0.0, ca = 0.0, ci = 0.0;
-  for (int k = lane; k < nch; k += 4 * 64) {                     // (four parts of a lane in flight; added in order)
-    double v[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const bool in = k + 64 * u < nch;
-      const FitPtsPart *p = part + (in ? k + 64 * u : k);
-      v[u][0] = gld_d(&p->s_all); v[u][1] = gld_d(&p->s_in); v[u][2] = gld_d(&p->n_dist); v[u][3] = gld_d(&p->n_in);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (k + 64 * u < nch) { sa += v[u][0]; si += v[u][1]; ca += v[u][2]; ci += v[u][3]; }
-  }
-  sa = wave_sum(sa); si = wave_sum(si); ca = wave_sum(ca); ci = wave_sum(ci);
+  const ScanSpan sp = scan_span(offsets, shared_scan, b);
+  double a[4];                                                   // s_all, s_in, n_dist, n_in
+  close_chunks(parts + fit_part_of(sp, shared_scan, b), (sp.n + 63) >> 6, a);
   if (lane == 0) {
     ndt_fit_stats R;
-    R.fitness = ci > 0.0 ? si / ci : DBL_MAX;
-    R.fitness_all = ca > 0.0 ? sa / ca : DBL_MAX;
-    R.n_in = (uint32_t)ci; R.n_dist = (uint32_t)ca; R.n_points = (uint32_t)n; R.reserved = 0u;
+    R.fitness = a[3] > 0.0 ? a[1] / a[3] : DBL_MAX;
+    R.fitness_all = a[2] > 0.0 ? a[0] / a[2] : DBL_MAX;
+    R.n_in = (uint32_t)a[3]; R.n_dist = (uint32_t)a[2]; R.n_points = (uint32_t)sp.n; R.reserved = 0u;
     stats[b] = R;
   }
 }

@@ -54,15 +54,24 @@ __device__ __forceinline__ float scan_bucket(const float2 *__restrict__ pts, int
   return best;
 }
 
+// The home voxel of a query: its own voxel clamped into the grid; inside: nothing was clamped.
+struct HomeVoxel { int cx, cy; bool inside; };
+__device__ __forceinline__ HomeVoxel home_voxel(const MapView &M, float qx, float qy) {
+  const int cx0 = (int)floorf(qx * M.inv_leaf) - M.min_bx, cy0 = (int)floorf(qy * M.inv_leaf) - M.min_by;
+  HomeVoxel H;
+  H.cx = cx0 < 0 ? 0 : (cx0 >= M.div_x ? M.div_x - 1 : cx0);
+  H.cy = cy0 < 0 ? 0 : (cy0 >= M.div_y ? M.div_y - 1 : cy0);
+  H.inside = (H.cx == cx0) && (H.cy == cy0);
+  return H;
+}
+
 // The search in two halves so that a caller can have the next query's offsets in flight while this query's
 // buckets are read: nearest_prep issues the one load everything else depends on.
 struct NearPrep { int cx, cy; bool inside; I4u h, dn, up; };
 __device__ __forceinline__ NearPrep nearest_prep(const MapView &M, float qx, float qy) {
   NearPrep P;
-  const int cx0 = (int)floorf(qx * M.inv_leaf) - M.min_bx, cy0 = (int)floorf(qy * M.inv_leaf) - M.min_by;
-  P.cx = cx0 < 0 ? 0 : (cx0 >= M.div_x ? M.div_x - 1 : cx0);
-  P.cy = cy0 < 0 ? 0 : (cy0 >= M.div_y ? M.div_y - 1 : cy0);
-  P.inside = (P.cx == cx0) && (P.cy == cy0);
+  const HomeVoxel H = home_voxel(M, qx, qy);
+  P.cx = H.cx; P.cy = H.cy; P.inside = H.inside;
   // offsets of (cx-1, cx, cx+1) of the home row in one load: [left, home) [home, right) [right, end)
   const int *row = M.pt_start + ((size_t)P.cy * M.div_x + P.cx) - 1;
   P.h = ld_i4u(row);
@@ -338,49 +347,81 @@ __device__ __forceinline__ float nearest_sq(const MapView &M, float qx, float qy
   return nearest_far(M, qx, qy, S, S.more ? nearest_ring1_lane(M, qx, qy, S) : S.best);
 }
 
+// ndt_fitness_at: one lane per query (nearest_sq) at an explicit transform, with a summation of its own -- grid-stride over
+// the points, one {sum, count} per workgroup, summed on the host in block order.  A path independent of the batch kernels
+// below: the tests compare them with it.
+__global__ void __launch_bounds__(256)
+ndt_fitness_kernel(MapView M, const float *__restrict__ scan, size_t stride, int n, Tf32 T,
+                   double *__restrict__ partial /* grid x 2 */) {
+  __shared__ double sred[(4 + 1) * 2];
+  double fsum = 0.0, fcnt = 0.0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float2 pt = load_pt(scan, stride, i);
+    float qx, qy;
+    tf_apply(T, M.transform_sse, pt.x, pt.y, qx, qy);
+    if (!finite2(qx, qy)) continue;
+    float best = nearest_sq(M, qx, qy);
+    if (best < INFINITY) { fsum += (double)best; fcnt += 1.0; }
+  }
+  block_reduce2(fsum, fcnt, sred, sred + 4 * 2);
+  if (threadIdx.x < 2) partial[blockIdx.x * 2 + threadIdx.x] = sred[4 * 2 + threadIdx.x];
+}
+
 // ------------------------------------------------------------------------------------------
 // a7 for a batch: getFitnessScore of every match (src/PoseEstimator.cpp:43), queued behind the match kernel.
-// Inside the match kernel (one 16-wave workgroup per CU, all registers taken) this search ran at the latency of
-// its dependent loads -- offsets, bucket, neighbouring buckets: ~110 us per 10k-point scan, a quarter of a match.
-// As a kernel of its own it runs at 8 waves per SIMD on the whole chip and is bound by the vector L1 instead.
-// Two steps so that the sum keeps ONE fixed order whatever the grid: the squared distance of every point (in the
-// order the passes read the scan: the cell-ordered copy, so that the lanes of a wave share buckets), then per match
-// the sum in the unit order of the passes (lane -> wave butterfly -> units 0..63).
 // ------------------------------------------------------------------------------------------
-constexpr int kFitOcc = 6;       // workgroups per CU the search kernel is built for (4 .. 8 waves per SIMD measure the same)
-// DEFER (launches whose matches share one scan: hypothesis scoring, configs[4]): the queries that need phase 3 are not
-// finished here but put on their match's list -- those with a point in hand from the front, those without from the back --
-// and fitness_far_kernel finishes them, 64 queries of ONE kind per wave.  With phase 3 inline a wave walks the rings of its
-// farthest lane while the others wait: on configs[4]'s seeds the longest lane of a wave needs 31 rounds of dependent loads,
-// the average lane 8, and less than half the lanes need the phase at all.
 // The mean of a match's distances, and the order it is summed in (round 5; the same for every launch shape and for both
 // forms of the fitness kernels): the match's points in chunks of 64 consecutive points of the ordered copy -- chunk c's
-// sum is the wave butterfly (wave_sum) over its 64 values, points without a distance adding 0 -- then lane l of ONE wave
-// adds the chunks l, l + 64, l + 128 ... one after the other, and the wave butterfly adds the lanes.  Counts are whole
-// numbers however they are added.  A chunk's {sum, count} is 16 bytes in the launch's FitPart array: written by the wave
-// that searched the chunk (fitness_points_kernel, scans of their own) or summed it (fitness_reduce_kernel), read by the
-// wave that closes the match.
+// sum is the wave butterfly (wave_sum) over its 64 values, points without a distance adding 0: chunk_part -- then lane l
+// of ONE wave adds the chunks l, l + 64, l + 128 ... one after the other, and the wave butterfly adds the lanes:
+// close_chunks.  Counts are whole numbers however they are added.  A chunk's {sum, count} is 16 bytes in the launch's
+// FitPart array: written by the wave that searched the chunk (fitness_points_kernel, scans of their own) or summed it
+// (fitness_reduce_kernel), read by the wave that closes the match.
 struct FitPart { double sum, cnt; };
-__device__ __forceinline__ size_t fit_part_of(int b, int n, unsigned long long o0, int shared_scan) {     // first chunk of match b
-  return shared_scan ? (size_t)b * (size_t)((n + 63) >> 6) : (size_t)(o0 >> 6) + (size_t)b;
+// one whole wave, a chunk: the sum of the lanes' d where `in` holds, and how many those are
+__device__ __forceinline__ FitPart chunk_part(bool in, float d) {
+  return FitPart{wave_sum(in ? (double)d : 0.0), (double)__popcll(__ballot(in))};
+}
+// The chunks of a launch: match b's first one, and how many the launch's array holds (scans of their own: match b's
+// chunks end at or before ((o0 + n) >> 6) + b + 1; B + 1 spare for matches that share one scan).
+__device__ __forceinline__ size_t fit_part_of(const ScanSpan &sp, int shared_scan, int b) {
+  return shared_scan ? (size_t)b * (size_t)((sp.n + 63) >> 6) : (size_t)(sp.o0 >> 6) + (size_t)b;
+}
+__host__ __device__ constexpr size_t fit_parts_needed(size_t total_points, size_t B, int shared_scan) {
+  return (shared_scan ? B * ((total_points + 63) >> 6) : total_points >> 6) + B + 1;
+}
+// One whole wave: acc[j] = the sum over a match's nch chunks of double j of the chunk's part (N doubles), in the order
+// stated above: four chunks of a lane in flight, added in ascending order, then the butterfly.  (A slot past the last chunk
+// reads chunk k again; what it read is not added.)
+template <int N, class Part>
+__device__ __forceinline__ void close_chunks(const Part *__restrict__ part, int nch, double (&acc)[N]) {
+  static_assert(sizeof(Part) == N * sizeof(double), "a part is N doubles");
+  const double *p0 = reinterpret_cast<const double *>(part);
+#pragma unroll
+  for (int j = 0; j < N; ++j) acc[j] = 0.0;
+  for (int k = threadIdx.x & 63; k < nch; k += 4 * 64) {
+    double v[4][N];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double *p = p0 + (size_t)N * (size_t)(k + 64 * u < nch ? k + 64 * u : k);
+#pragma unroll
+      for (int j = 0; j < N; ++j) v[u][j] = gld_d(p + j);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k + 64 * u < nch) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[j] += v[u][j];
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) acc[j] = wave_sum(acc[j]);
 }
 // one whole wave: the match's fitness from its chunks
 __device__ __forceinline__ void fitness_close_match(const FitPart *__restrict__ part, int n, ndt_result *R) {
-  const int lane = threadIdx.x & 63, nch = (n + 63) >> 6;
-  double s = 0.0, c = 0.0;
-  for (int k = lane; k < nch; k += 4 * 64) {                    // (four loads of each kind in flight; added in order)
-    double vs[4], vc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const bool in = k + 64 * u < nch;
-      vs[u] = in ? gld_d(&part[k + 64 * u].sum) : 0.0;
-      vc[u] = in ? gld_d(&part[k + 64 * u].cnt) : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (k + 64 * u < nch) { s += vs[u]; c += vc[u]; }
-  }
-  s = wave_sum(s); c = wave_sum(c);
-  if (lane == 0) R->fitness = (n > 0 && c > 0) ? s / c : DBL_MAX;
+  double a[2];                                                   // sum, count
+  close_chunks(part, (n + 63) >> 6, a);
+  if ((threadIdx.x & 63) == 0) R->fitness = (n > 0 && a[1] > 0) ? a[0] / a[1] : DBL_MAX;
 }
 
 // XCD-aware numbering of the fitness kernels' workgroups (round 5).  The dispatcher deals consecutive workgroups out to the
@@ -396,14 +437,37 @@ __device__ __forceinline__ bool fit_block_of(int gx, int B, int &b, int &x) {
   return b < B;
 }
 
-// MULTI launches (ndt_align_batch_multi_dev): the map of match b is views[map_of[b]] (map_of null: views[b]); a match whose
-// index is out of range has no map -- its workgroups return before reading anything through it, and its record keeps the
-// match kernel's fitness (DBL_MAX).  -1 for such a match.
-__device__ __forceinline__ int fit_map_index(const int *__restrict__ map_of, int n_maps, int b) {
-  const int mi = map_of ? map_of[b] : b;
-  return (mi >= 0 && mi < n_maps) ? mi : -1;
+// The map of match b in a fitness kernel: the launch's own (index 0), or -- MULTI launches (ndt_align_batch_multi_dev) --
+// views[map_index_of].  -1: the match has no map -- its workgroups return before reading anything through it, and its
+// record keeps the match kernel's fitness (DBL_MAX; fitness_reduce_kernel skips it by the same index).
+template <bool MULTI>
+__device__ __forceinline__ int match_map_index(const int *__restrict__ map_of, int n_maps, int b) {
+  return MULTI ? map_index_of(map_of, n_maps, b) : 0;
 }
 
+// Phases 1 and 2 for lane's query: point i of the match's n points pts, moved by T.  Whole waves stay together (the ring-1
+// phase is a wave's joint work, in the wave's own R): a lane past the end, or whose point does not stay finite, carries no
+// query -- live is false, it looks at (0, 0) and drops what it finds.
+struct LaneQuery { float qx, qy; bool live; NearState S; float best; };
+template <bool SSE>
+__device__ __forceinline__ LaneQuery lane_query(const MapView &M, RingLds &R, const Tf32 &T, const float2 *pts, int i, int n) {
+  LaneQuery Q;
+  const float2 pt = pts[min(i, n - 1)];
+  tf_apply_t<SSE>(T, pt.x, pt.y, Q.qx, Q.qy);
+  Q.live = i < n && finite2(Q.qx, Q.qy);
+  if (!Q.live) { Q.qx = 0.f; Q.qy = 0.f; }                       // (any address inside the grid; the result is dropped)
+  Q.S = nearest_home(M, Q.qx, Q.qy, nearest_prep(M, Q.qx, Q.qy));
+  if (!Q.live) { Q.S.more = false; Q.S.rn[0] = Q.S.rn[1] = Q.S.rn[2] = Q.S.rn[3] = 0; }
+  Q.best = nearest_ring1_wave(M, R, Q.qx, Q.qy, Q.S);
+  return Q;
+}
+
+// The search as a kernel of its own.  Inside the match kernel (one 16-wave workgroup per CU, all registers taken) it ran at
+// the latency of its dependent loads -- offsets, bucket, neighbouring buckets: ~110 us per 10k-point scan, a quarter of a
+// match.  Here it runs at 8 waves per SIMD on the whole chip and is bound by the vector L1 instead.  Two steps so that the
+// sum keeps ONE fixed order whatever the grid: the squared distance of every point (in the order the passes read the scan:
+// the cell-ordered copy, so that the lanes of a wave share buckets), then per match the sum in the order stated at FitPart.
+constexpr int kFitOcc = 6;       // workgroups per CU the search kernel is built for (4 .. 8 waves per SIMD measure the same)
 template <bool SSE, bool DEFER, bool MULTI = false>
 __global__ void __launch_bounds__(256, kFitOcc)
 fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
@@ -414,33 +478,30 @@ fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsi
   __shared__ RingLds ring[256 / 64];
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
-  int mi = 0;
-  if (MULTI && (mi = fit_map_index(map_of, n_maps, b)) < 0) return;
+  const int mi = match_map_index<MULTI>(map_of, n_maps, b);
+  if (mi < 0) return;
   const MapView M = MULTI ? views[mi] : M_arg;
   {
-    const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-    const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-    const int n = (int)(o1 - o0);
+    const ScanSpan sp = scan_span(offsets, shared_scan, b);
+    const int n = sp.n;
     const ndt_result *R = results + b;
     const Tf32 T = {R->T00, R->T10, R->T03, R->T13};
     const bool use_sorted = sorted != nullptr && !(R->flags & NDT_FLAG_UNSORTED);
-    const size_t slot = shared_scan ? (size_t)b * (size_t)n : (size_t)o0;
-    const float2 *pts = use_sorted ? sorted + slot : reinterpret_cast<const float2 *>(scans) + o0;
+    const size_t slot = sp.slot(shared_scan, b);
+    const float2 *pts = use_sorted ? sorted + slot : reinterpret_cast<const float2 *>(scans) + sp.o0;
     float *out = DEFER ? fit + slot : nullptr;
-    FitPart *part = DEFER ? nullptr : parts + fit_part_of(b, n, o0, shared_scan);
-    // whole waves stay together (the ring-1 phase is a wave's joint work): lanes past the end carry no query
+    FitPart *part = DEFER ? nullptr : parts + fit_part_of(sp, shared_scan, b);
     for (int i0 = bx * (int)blockDim.x + (int)(threadIdx.x & ~63u); i0 < n; i0 += gx * (int)blockDim.x) {
       const int i = i0 + (int)(threadIdx.x & 63u);
-      const float2 pt = pts[min(i, n - 1)];
-      float qx, qy;
-      tf_apply_t<SSE>(T, pt.x, pt.y, qx, qy);
-      const bool live = i < n && finite2(qx, qy);
-      if (!live) { qx = 0.f; qy = 0.f; }                         // (any address inside the grid; the result is dropped)
-      NearState S = nearest_home(M, qx, qy, nearest_prep(M, qx, qy));
-      if (!live) { S.more = false; S.rn[0] = S.rn[1] = S.rn[2] = S.rn[3] = 0; }
-      float best = nearest_ring1_wave(M, ring[threadIdx.x >> 6], qx, qy, S);
+      const LaneQuery Q = lane_query<SSE>(M, ring[threadIdx.x >> 6], T, pts, i, n);
       if (DEFER) {
-        const bool need = live && far_needed(M, S, best), blind = need && !(best < INFINITY);
+        // Launches whose matches share one scan (hypothesis scoring, configs[4]): the queries that need phase 3 are not
+        // finished here but put on their match's list -- those with a point in hand from the front, those without from the
+        // back -- and fitness_far_kernel finishes them, 64 queries of ONE kind per wave.  With phase 3 inline a wave walks
+        // the rings of its farthest lane while the others wait: on configs[4]'s seeds the longest lane of a wave needs 31
+        // rounds of dependent loads, the average lane 8, and less than half the lanes need the phase at all (DESIGN.md 0a
+        // item 4).
+        const bool need = Q.live && far_needed(M, Q.S, Q.best), blind = need && !(Q.best < INFINITY);
         const unsigned long long ma = __ballot(need && !blind), mb = __ballot(blind);
         if (ma | mb) {                                           // (wave-uniform) one atomic per wave and kind
           const int lane = threadIdx.x & 63;
@@ -454,17 +515,12 @@ fitness_points_kernel(MapView M_arg, const float *__restrict__ scans, const unsi
           if (need && !blind) far_idx[slot + base_a + (unsigned)__popcll(ma & below)] = (unsigned)i;
           if (blind) far_idx[slot + (size_t)(n - 1) - (base_b + (unsigned)__popcll(mb & below))] = (unsigned)i;
         }
-      } else {
-        best = nearest_far(M, qx, qy, S, best);
-      }
-      if (DEFER) {
-        if (i < n) out[i] = live ? best : INFINITY;
+        if (i < n) out[i] = Q.live ? Q.best : INFINITY;
       } else {
         // the distances of this chunk of 64 points never leave the wave: their sum and their number do (i0 is a multiple of 64)
-        const bool in = live && best < INFINITY;
-        const double t = wave_sum(in ? (double)best : 0.0);
-        const int c = __popcll(__ballot(in));
-        if ((threadIdx.x & 63u) == 0u) part[i0 >> 6] = FitPart{t, (double)c};
+        const float best = nearest_far(M, Q.qx, Q.qy, Q.S, Q.best);
+        const FitPart p = chunk_part(Q.live && best < INFINITY, best);
+        if ((threadIdx.x & 63u) == 0u) part[i0 >> 6] = p;
       }
     }
   }
@@ -482,20 +538,19 @@ fitness_far_kernel(MapView M_arg, const float *__restrict__ scans, const unsigne
   __shared__ FarLds far_lds;
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
-  int mi = 0;
-  if (MULTI && (mi = fit_map_index(map_of, n_maps, b)) < 0) return;
+  const int mi = match_map_index<MULTI>(map_of, n_maps, b);
+  if (mi < 0) return;
   const MapView M = MULTI ? views[mi] : M_arg;
   {
     const unsigned na = far_n[2 * (size_t)b], nb = far_n[2 * (size_t)b + 1];
     if (na + nb == 0u) return;
-    const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-    const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-    const int n = (int)(o1 - o0);
+    const ScanSpan sp = scan_span(offsets, shared_scan, b);
+    const int n = sp.n;
     const ndt_result *R = results + b;
     const Tf32 T = {R->T00, R->T10, R->T03, R->T13};
     const bool use_sorted = sorted != nullptr && !(R->flags & NDT_FLAG_UNSORTED);
-    const size_t slot = shared_scan ? (size_t)b * (size_t)n : (size_t)o0;
-    const float2 *pts = use_sorted ? sorted + slot : reinterpret_cast<const float2 *>(scans) + o0;
+    const size_t slot = sp.slot(shared_scan, b);
+    const float2 *pts = use_sorted ? sorted + slot : reinterpret_cast<const float2 *>(scans) + sp.o0;
     float *out = fit + slot;
     const unsigned *list = far_idx + slot;
     // whole waves of one kind: the front list rounded up to waves, then the back list
@@ -507,11 +562,10 @@ fitness_far_kernel(MapView M_arg, const float *__restrict__ scans, const unsigne
       const float2 pt = pts[i];
       float qx, qy;
       tf_apply_t<SSE>(T, pt.x, pt.y, qx, qy);
+      const HomeVoxel H = home_voxel(M, qx, qy);
       NearState S;
-      const int cx0 = (int)floorf(qx * M.inv_leaf) - M.min_bx, cy0 = (int)floorf(qy * M.inv_leaf) - M.min_by;
-      S.cx = cx0 < 0 ? 0 : (cx0 >= M.div_x ? M.div_x - 1 : cx0);
-      S.cy = cy0 < 0 ? 0 : (cy0 >= M.div_y ? M.div_y - 1 : cy0);
-      near_walls(M, qx, qy, S.cx, S.cy, (S.cx == cx0) && (S.cy == cy0), S);
+      S.cx = H.cx; S.cy = H.cy;
+      near_walls(M, qx, qy, H.cx, H.cy, H.inside, S);
       S.more = true;
       out[i] = nearest_far_tiles(M, far_lds, qx, qy, S, out[i]);
     }
@@ -534,21 +588,18 @@ fitness_reduce_kernel(const unsigned long long *__restrict__ offsets, int B, int
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (!SUM) {
     for (int b = blockIdx.x * (kFitBlock / 64) + wave; b < B; b += gridDim.x * (kFitBlock / 64)) {
-      if (MULTI && fit_map_index(map_of, n_maps, b) < 0) continue;      // (no map: the record keeps fitness DBL_MAX)
-      const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-      const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-      const int n = (int)(o1 - o0);
-      fitness_close_match(parts + fit_part_of(b, n, o0, shared_scan), n, results + b);
+      if (match_map_index<MULTI>(map_of, n_maps, b) < 0) continue;      // (no map: the record keeps fitness DBL_MAX)
+      const ScanSpan sp = scan_span(offsets, shared_scan, b);
+      fitness_close_match(parts + fit_part_of(sp, shared_scan, b), sp.n, results + b);
     }
     return;
   }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    if (MULTI && fit_map_index(map_of, n_maps, b) < 0) continue;        // (workgroup-uniform)
-    const unsigned long long o0 = shared_scan ? offsets[0] : offsets[b];
-    const unsigned long long o1 = shared_scan ? offsets[1] : offsets[b + 1];
-    const int n = (int)(o1 - o0), nch = (n + 63) >> 6;
-    const float *f = fit + (shared_scan ? (size_t)b * (size_t)n : (size_t)o0);
-    FitPart *part = parts + fit_part_of(b, n, o0, shared_scan);
+    if (match_map_index<MULTI>(map_of, n_maps, b) < 0) continue;        // (workgroup-uniform)
+    const ScanSpan sp = scan_span(offsets, shared_scan, b);
+    const int n = sp.n, nch = (n + 63) >> 6;
+    const float *f = fit + sp.slot(shared_scan, b);
+    FitPart *part = parts + fit_part_of(sp, shared_scan, b);
     for (int c0 = wave; c0 < nch; c0 += 4 * (kFitBlock / 64)) {   // (four chunks of the wave in flight)
       float v[4];
 #pragma unroll
@@ -560,10 +611,8 @@ fitness_reduce_kernel(const unsigned long long *__restrict__ offsets, int B, int
       for (int u = 0; u < 4; ++u) {
         const int c = c0 + u * (kFitBlock / 64);
         if (c < nch) {                                           // (wave-uniform)
-          const bool in = v[u] < INFINITY;
-          const double t = wave_sum(in ? (double)v[u] : 0.0);
-          const int k = __popcll(__ballot(in));
-          if (lane == 0) part[c] = FitPart{t, (double)k};
+          const FitPart p = chunk_part(v[u] < INFINITY, v[u]);
+          if (lane == 0) part[c] = p;
         }
       }
     }

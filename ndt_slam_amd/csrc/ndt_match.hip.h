@@ -1114,12 +1114,6 @@ ndt_order_kernel(MapView M, OptParams P, const float *__restrict__ scans, const 
   }
 }
 
-// MULTI launches (ndt_align_batch_multi_dev): match b reads the map views[map_of[b]] (map_of null: views[b]); the index of a
-// match is checked before anything is read through it.  -1: outside [0, n_maps).
-__device__ __forceinline__ int map_index_of(const int *__restrict__ map_of, int n_maps, int b) {
-  const int mi = map_of ? map_of[b] : b;
-  return (mi >= 0 && mi < n_maps) ? mi : -1;
-}
 // The view into L.M, one word per lane of wave 1 (as the prepared records' optimiser state: a MapView held by value in
 // registers went through scratch memory).  The readers take it from there into SGPRs (pass_units: uniform_*).
 static_assert(sizeof(MapView) % 4 == 0 && sizeof(MapView) / 4 <= 64, "a word of the view per lane of one wave");
@@ -1704,21 +1698,4 @@ ndt_eval_kernel(MapView M, double snap, int libm_f32, const float *__restrict__ 
   }
   block_reduce_acc(A, sred, sred + 4 * kAcc);
   if (threadIdx.x < kAcc) partial[blockIdx.x * kAcc + threadIdx.x] = sred[4 * kAcc + threadIdx.x];
-}
-
-__global__ void __launch_bounds__(256)
-ndt_fitness_kernel(MapView M, const float *__restrict__ scan, size_t stride, int n, Tf32 T,
-                   double *__restrict__ partial /* grid x 2 */) {
-  __shared__ double sred[(4 + 1) * 2];
-  double fsum = 0.0, fcnt = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float2 pt = load_pt(scan, stride, i);
-    float qx, qy;
-    tf_apply(T, M.transform_sse, pt.x, pt.y, qx, qy);
-    if (!finite2(qx, qy)) continue;
-    float best = nearest_sq(M, qx, qy);
-    if (best < INFINITY) { fsum += (double)best; fcnt += 1.0; }
-  }
-  block_reduce2(fsum, fcnt, sred, sred + 4 * 2);
-  if (threadIdx.x < 2) partial[blockIdx.x * 2 + threadIdx.x] = sred[4 * 2 + threadIdx.x];
 }

@@ -480,6 +480,19 @@ int grid_for(size_t n, int block, int cap = 2048) {
   return (int)g;
 }
 
+// The grid of the kernels that search a launch's scans (fitness_points_kernel, fitness_far_kernel, fit_points_kernel): gx
+// workgroups of 256 queries per match, a block per 256 points of the average scan and 64 at the most, for B rounded up to
+// whole rounds of the eight XCDs.  One-dimensional, XCD-aware: workgroup w -> (match, block of the match) in fit_block_of
+// (ndt_fitness.hip.h).  workgroup_bound > 0 (NDT_OPT_WORKGROUPS): no more workgroups than that, while every match keeps one.
+struct FitGrid { unsigned gx, workgroups; };
+FitGrid fit_grid(size_t total_points, int B, int shared_scan, int workgroup_bound = 0) {
+  const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
+  const size_t b8 = ((size_t)B + 7) / 8 * 8;
+  size_t gx = std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
+  if (workgroup_bound > 0) gx = std::max<size_t>(1, std::min<size_t>(gx, (size_t)workgroup_bound / b8));
+  return FitGrid{(unsigned)gx, (unsigned)(gx * b8)};
+}
+
 // The fitness kernels of one launch on stream fs (behind its match kernel there: stream order, or the caller has made fs wait).
 int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   const MapView &V = J.V;
@@ -489,10 +502,9 @@ int queue_fitness(ndt_ctx *ctx, const ndt_ctx::FitJob &J, hipStream_t fs) {
   const size_t zero_bytes = J.zero_bytes, far_cnt_bytes = J.far_cnt_bytes;
   float *fit = ctx->d_fit.p;
   FitPart *parts = ctx->d_fit_part.p;
-  const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
-  const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
-  // one-dimensional, XCD-aware: workgroup w -> (match, block of the match) in fit_block_of (ndt_fitness.hip.h)
-  const dim3 grid(gx * (unsigned)(((size_t)B + 7) / 8 * 8));
+  const FitGrid G = fit_grid(total_points, B, shared_scan);
+  const unsigned gx = G.gx;
+  const dim3 grid(G.workgroups);
   // hypothesis scoring (shared_scan): most seeds end far from the map -- the far phase of the search as a pass of its own over
   // the queries that need it (ndt_fitness.hip.h); scans of their own: the search kernel leaves a {sum, count} per chunk of 64
   // points instead of a distance per point
@@ -572,7 +584,7 @@ int launch_align(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *
   const size_t far_cnt_bytes = far.take(slots * sizeof(unsigned) + 16, 16);
   if (shared_scan && (rc = ctx->d_far.ensure(ctx, far.end))) return rc;
   // the chunk sums of the fitness kernels (FitPart, a chunk = 64 points; a match's chunks start at fit_part_of)
-  if ((rc = ctx->d_fit_part.ensure(ctx, slots / 64 + (size_t)B + 1))) return rc;
+  if ((rc = ctx->d_fit_part.ensure(ctx, fit_parts_needed(total_points, (size_t)B, shared_scan)))) return rc;
   // control words: zero before every launch -- by the last kernel of the previous launch of this context
   // (fitness_reduce_kernel), or by a memset when that did not cover enough
   if (mm && (rc = ctx->views_tab.reserve(ctx, (size_t)mm->n_maps))) return rc;   // (waits for the previous multi-map launch's copy)
@@ -3220,21 +3232,16 @@ int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const flo
                      size_t total_points, int shared_scan, const void *tf, size_t tf_stride, double max_d2, float *d2,
                      ndt_fit_stats *stats) {
   int rc;
-  const size_t n_parts = shared_scan ? (size_t)B * ((total_points + 63) / 64) : total_points / 64 + (size_t)B + 1;
-  if (stats && (rc = ctx->d_fit_pts.ensure(ctx, n_parts))) return rc;        // (the call's one allocation, in front of its first kernel)
+  if (stats && (rc = ctx->d_fit_pts.ensure(ctx, fit_parts_needed(total_points, (size_t)B, shared_scan)))) return rc;   // (the call's one allocation, in front of its first kernel)
   MapRead rd{ctx, st, &map, 1};
   if ((rc = rd.begin())) return rc;
-  // queue_fitness's grid: workgroup w -> (match, block of the match) in fit_block_of; NDT_OPT_WORKGROUPS bounds it
-  const size_t avg = shared_scan ? total_points : (total_points + (size_t)B - 1) / (size_t)B;
-  const size_t b8 = ((size_t)B + 7) / 8 * 8;
-  size_t gx = std::min<size_t>(64, std::max<size_t>(1, (avg + 255) / 256));
-  if (ctx->workgroups > 0) gx = std::max<size_t>(1, std::min<size_t>(gx, (size_t)ctx->workgroups / b8));
+  const FitGrid G = fit_grid(total_points, B, shared_scan, ctx->workgroups);     // (queue_fitness's grid; NDT_OPT_WORKGROUPS bounds it)
   FitPtsPart *parts = stats ? ctx->d_fit_pts.p : nullptr;
   Event *evr = rd.ev;
   with_bool(map->prm.transform_sse != 0, [&](auto S) {
-    hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value>), dim3((unsigned)(gx * b8)), dim3(256), 0, st, evr[0], evr[1], 0, map->view,
+    hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value>), dim3(G.workgroups), dim3(256), 0, st, evr[0], evr[1], 0, map->view,
                           reinterpret_cast<const float2 *>(scans), offsets, B, shared_scan, (const unsigned char *)tf, tf_stride, max_d2, d2,
-                          parts, (int)gx);
+                          parts, (int)G.gx);
   });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
