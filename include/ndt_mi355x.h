@@ -823,6 +823,98 @@ int ndt_occ_counts(ndt_ctx *ctx, ndt_occ *occ, uint32_t *hit_host, uint32_t *pas
 int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, double max_range2,
                                ndt_occ_stats *stats_host);
 
+/* ---- Pose graphs: batched SE(2) optimisation and re-posing of stored clouds -------------------------------------------------
+ * What the reference's commented-out loop closure was for: FrontEnd adds an odometry arc per scan and, on a detected loop, calls
+ * backEnd->adjustPoses(), backEnd->remakeMaps() and smat.remakePoseArray(newPoses) (src/FrontEnd.cpp:21-44);
+ * PointCloudMap::remakeMaps moves every map point from its old scan pose to its new one (src/PointCloudMap.cpp:136-170).  Its
+ * back end (PoseGraph, SlamBackEnd) is absent from the reference tree; these calls are that step for S graphs at once.  Loop
+ * DETECTION is the caller's, with what exists (ndt_align_batch_multi_dev against old submaps' maps, ndt_relocalize,
+ * ndt_fit_points_batch); an ndt_sessions set's own resident state is not rewritten by these calls.
+ *
+ * Conventions are those of the f2 rows: poses are (tx, ty, th[deg]) double triples, covariances and information matrices are
+ * in (m, m, rad), output headings are wrapped into [-180, 180) as MyUtil::add_angle does (src/MyUtil.cpp:4-11).
+ *
+ * Model, in radians internally.  For an arc (i -> j, z, Omega): r_xy = R(th_i)^T (t_j - t_i) - z_xy,
+ * r_th = wrap(th_j - th_i - z_th) into [-pi, pi), F = sum r^T Omega r.  Node 0 of every graph is held fixed: its three doubles
+ * come back bit-identical.
+ *
+ * Method.  Gauss-Newton with analytic Jacobians.  The normal equations H d = -b, node 0's rows and columns removed, are solved
+ * by conjugate gradients preconditioned with the CHAIN matrix T (J^T Omega J in full for every arc with |from - to| = 1, the two
+ * diagonal blocks alone for every other arc: block-tridiagonal, factored once per Gauss-Newton step by a block-Thomas sweep) to
+ * a relative preconditioned residual sqrt(r^T z / r0^T z0) <= cg_rtol, in at most cg_max_iter iterations (0: 6 N).  A step d is
+ * taken only if F does not rise; otherwise it is halved, up to max_halvings times.  converged = 1 when max|d| of an accepted
+ * step is below eps_step (metres and radians alike) -- and when the halving runs out at a step that is already below eps_step:
+ * halving on could only accept a shorter one, so the poses stay (next to the minimiser the change of F along a step of 1e-9
+ * is below the rounding of F itself, and the comparison decides nothing).  converged = 0 at max_iter, at any other step that
+ * cannot be accepted, at a T that is not positive definite to working precision (a pivot of its factor below 1e-13 of its diagonal
+ * entry: a node that nothing ties to node 0) and at a CG breakdown (p^T H p <= 0 or not finite); the poses are then the last accepted ones.
+ * cost_final <= cost_initial always.  iterations counts accepted steps, cg_iterations is the total over the run.  A graph that
+ * took no step keeps its poses' bytes.
+ *
+ * Per-graph faults are found on the device and do not disturb other graphs: an arc index outside the graph, from == to, a
+ * non-finite number in the graph's poses or arcs, an info that is not positive definite (Sylvester's criterion).  Each gives
+ * status = NDT_E_ARG, the other fields 0, that graph's poses untouched.  A graph without arcs: NDT_OK, converged = 1,
+ * iterations = 0, untouched.  A graph in which some node has no path to node 0 is the caller's error: it ends through the
+ * rules above with converged = 0 and finite poses.
+ *
+ * One 256-thread workgroup per graph, one launch for all iterations of all graphs (a batch of one graph uses one CU: the
+ * product is the batch).  A graph's poses and record are a function of its own input alone, to the last bit: not of the
+ * batch, its order, or the schedule.  Graph g's nodes are the pose triples [node_offsets[g], node_offsets[g + 1]), its arcs
+ * edges[edge_offsets[g] .. edge_offsets[g + 1]); both offset arrays (n_graphs + 1 entries) are HOST arrays in either form: the
+ * scratch is sized from them.  _dev is asynchronous on `stream` (NULL = the context's): one table upload, one launch, scratch
+ * inside the context's scratch bracket.  ndt_pg_optimize_batch: host pointers; uploads, the _dev call, poses and records read
+ * back; synchronous.
+ *
+ * Refusals (NDT_E_ARG, synchronous, nothing queued or written): a NULL context ("null context"); NULL arrays; n_graphs < 1;
+ * offsets that decrease; a graph of 2^28 nodes or arcs or more; max_iter outside [1, 10000], eps_step negative or not finite,
+ * cg_max_iter outside [0, 2^30], cg_rtol outside (0, 1), max_halvings outside [0, 60]; an open ndt_map_rebuild_begin on the
+ * context. */
+typedef struct ndt_pg_edge {      /* one arc; DEVICE or HOST memory by entry point; 80 bytes */
+  int32_t from, to;               /* node indices inside the arc's own graph */
+  double  rel[3];                 /* pose of `to` in `from`'s frame: Pose2D::calMotion(to, from) (src/Pose2D.cpp:5-14); th in deg */
+  double  info[6];                /* xx xy xt yy yt tt of the 3x3 information matrix, (m, m, rad) */
+} ndt_pg_edge;
+typedef struct ndt_pg_params { int max_iter; double eps_step; int cg_max_iter; double cg_rtol; int max_halvings; } ndt_pg_params;
+typedef struct ndt_pg_result {    /* one per graph; 32 bytes */
+  double cost_initial, cost_final; int iterations, cg_iterations, converged, status;
+} ndt_pg_result;
+/* 20, 1e-9, 0 (= 6 N), 1e-10, 8: for the pose adjustment called at src/FrontEnd.cpp:37. */
+int ndt_pg_default_params(ndt_pg_params *p);
+/* Host helper, no context: edge->rel = Pose2D::calMotion(to_pose, from_pose) (src/Pose2D.cpp:5-14, the odometry arc of
+ * src/FrontEnd.cpp:61-63); from, to and info are left as they are.  NDT_E_ARG: a NULL pointer, a non-finite pose. */
+int ndt_pg_edge_between(const double from_pose[3], const double to_pose[3], ndt_pg_edge *edge);
+/* Host helper, no context: the information matrix of a world-frame covariance (row-major 3 x 3, (m, m, rad)) seen from the frame
+ * at heading th_deg: C' = R3^T C R3 with R3 = diag(R(th), 1) -- CovarianceCalculator::rotateCovariance(lastPose, fusedCov, cov,
+ * true) of src/FrontEnd.cpp:69 --, then info = C'^-1 as xx xy xt yy yt tt.  The off-diagonal pairs of C are averaged.
+ * NDT_E_ARG: a NULL pointer, a non-finite number, a pair that differs by more than 1e-9 sqrt(C_ii C_jj), a matrix that is not
+ * positive definite by Sylvester's criterion to working precision: a pivot xx, m2 / xx, det / m2 of C' that is not above 1e-12
+ * of the largest diagonal entry of its unit (m^2, rad^2).  A first scan's zero covariance is one, and so is the first matched
+ * scan's, which has 1e-35 m^2 along the motion: give such an arc an information matrix of your own. */
+int ndt_pg_info_from_cov(const double cov_world[9], double th_deg, double info[6]);
+/* SlamBackEnd::adjustPoses (called at src/FrontEnd.cpp:37) for n_graphs graphs at once; device poses, arcs and records. */
+int ndt_pg_optimize_batch_dev(ndt_ctx *ctx, double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                              const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params,
+                              ndt_pg_result *out_dev, void *stream);
+/* The same from host memory (src/FrontEnd.cpp:37); synchronous. */
+int ndt_pg_optimize_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                          const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params,
+                          ndt_pg_result *out_host);
+/* PointCloudMap::remakeMaps' point correction (src/PointCloudMap.cpp:147-154) for clouds stored in ranges.  Segment k covers the
+ * points [seg_offsets[k], seg_offsets[k + 1]) of xy (two float32 at each stride) and has the pose triples old_poses[k] and
+ * new_poses[k]: q = oldPose.relativePoint(p), p' = newPose.globalPoint(q) (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat
+ * builds it, in fp64 without contraction as ndt_scan_to_map_batch_dev does it, rounded once to float32.  A segment whose old and
+ * new pose are bit-equal is copied through unchanged: submaps that a correction does not reach keep their bytes.  out may be
+ * xy itself at the same stride.  Segment ranges are those ndt_sessions_global_map returns in sub_offsets, or per-scan ranges of
+ * a store.  Non-finite poses or points give non-finite points, nothing else.  _dev: asynchronous on `stream` (NULL = the
+ * context's), one launch, no scratch.  Refusals (NDT_E_ARG): a NULL context or array, n_segs < 1, a stride below 8 or not a
+ * multiple of 4, out == xy at another stride; host form: offsets that decrease. */
+int ndt_repose_points_dev(ndt_ctx *ctx, const float *xy_dev, size_t stride_bytes, const uint64_t *seg_offsets_dev, int n_segs,
+                          const double *old_poses_dev, const double *new_poses_dev, float *out_xy_dev, size_t out_stride_bytes,
+                          void *stream);
+/* The same from host memory (src/PointCloudMap.cpp:147-154); synchronous.  Only the points of the segments are read and written. */
+int ndt_repose_points(ndt_ctx *ctx, const float *xy_host, size_t stride_bytes, const uint64_t *seg_offsets_host, int n_segs,
+                      const double *old_poses_host, const double *new_poses_host, float *out_xy_host, size_t out_stride_bytes);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

@@ -133,6 +133,22 @@ class OccStats(C.Structure):
 OCC_STATS_DTYPE = np.dtype([("n_beams", "u8"), ("n_hit", "u8"), ("n_pass", "u8"), ("n_skipped", "u8")], align=True)
 
 
+class PgEdge(C.Structure):
+    """ndt_pg_edge (include/ndt_mi355x.h): one arc of a pose graph."""
+    _fields_ = [("from_", C.c_int32), ("to", C.c_int32), ("rel", C.c_double * 3), ("info", C.c_double * 6)]
+
+
+class PgParams(C.Structure):
+    """ndt_pg_params (include/ndt_mi355x.h)."""
+    _fields_ = [("max_iter", C.c_int), ("eps_step", C.c_double), ("cg_max_iter", C.c_int), ("cg_rtol", C.c_double),
+                ("max_halvings", C.c_int)]
+
+
+PG_EDGE_DTYPE = np.dtype([("from", "i4"), ("to", "i4"), ("rel", "f8", 3), ("info", "f8", 6)], align=True)
+PG_RESULT_DTYPE = np.dtype([("cost_initial", "f8"), ("cost_final", "f8"), ("iterations", "i4"), ("cg_iterations", "i4"),
+                            ("converged", "i4"), ("status", "i4")], align=True)
+
+
 class MapInfo(C.Structure):
     _fields_ = [("min_bx", C.c_int), ("min_by", C.c_int), ("div_x", C.c_int), ("div_y", C.c_int),
                 ("n_cells", C.c_int), ("n_valid", C.c_int), ("n_points", C.c_size_t)]
@@ -170,6 +186,8 @@ EXPORTS = [
     "ndt_occ_cell", "ndt_occ_create", "ndt_occ_destroy", "ndt_occ_clear", "ndt_occ_geometry_get", "ndt_occ_view",
     "ndt_occ_integrate_dev", "ndt_occ_integrate", "ndt_occ_render_dev", "ndt_occ_render", "ndt_occ_counts",
     "ndt_sessions_occ_integrate",
+    "ndt_pg_default_params", "ndt_pg_edge_between", "ndt_pg_info_from_cov", "ndt_pg_optimize_batch_dev", "ndt_pg_optimize_batch",
+    "ndt_repose_points_dev", "ndt_repose_points",
 ]
 
 
@@ -270,6 +288,13 @@ def lib():
     L.ndt_occ_render.argtypes = [vp, vp, C.c_uint32, vp]
     L.ndt_occ_counts.argtypes = [vp, vp, vp, vp]
     L.ndt_sessions_occ_integrate.argtypes = [vp, vp, vp, d, vp]
+    L.ndt_pg_default_params.argtypes = [C.POINTER(PgParams)]
+    L.ndt_pg_edge_between.argtypes = [vp, vp, vp]
+    L.ndt_pg_info_from_cov.argtypes = [vp, d, vp]
+    L.ndt_pg_optimize_batch_dev.argtypes = [vp, vp, vp, vp, vp, i, C.POINTER(PgParams), vp, vp]
+    L.ndt_pg_optimize_batch.argtypes = [vp, vp, vp, vp, vp, i, C.POINTER(PgParams), vp]
+    L.ndt_repose_points_dev.argtypes = [vp, vp, sz, vp, i, vp, vp, vp, sz, vp]
+    L.ndt_repose_points.argtypes = [vp, vp, sz, vp, i, vp, vp, vp, sz]
     for name in EXPORTS:
         if name not in ("ndt_last_error", "ndt_ctx_stream"):
             getattr(L, name).restype = i
@@ -416,6 +441,99 @@ def session_params_from_launch(params):
         fuse_coe_omega=q["coeOmega"], fuse_del_time=q["delTime"], fuse_score_thre=q["score_thre"], space=q["space"],
         space_thre=q["space_thre"], leaf=q["LeafSize"], resol=q["resol"], thre_neighbor=q["thre_neighbor"],
         sep_thre=q["sepThre"], remove_moving=int(bool(q["removeMoving"])))
+
+
+def default_pg_params(**kw):
+    """ndt_pg_default_params, fields overridden by keyword."""
+    p = PgParams()
+    lib().ndt_pg_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _helper_check(rc, what):
+    if rc != 0:
+        raise NdtError("%s failed (%d): %s" % (what, rc, lib().ndt_last_error(None).decode()))
+
+
+def pg_edge_between(from_pose, to_pose):
+    """ndt_pg_edge_between: Pose2D::calMotion(to, from) -> the arc's rel (tx, ty, th[deg])."""
+    a = np.ascontiguousarray(from_pose, dtype=np.float64).reshape(3)
+    b = np.ascontiguousarray(to_pose, dtype=np.float64).reshape(3)
+    e = np.zeros(1, dtype=PG_EDGE_DTYPE)
+    _helper_check(lib().ndt_pg_edge_between(a.ctypes.data, b.ctypes.data, e.ctypes.data), "ndt_pg_edge_between")
+    return e[0]["rel"].copy()
+
+
+def pg_info_from_cov(cov_world, th_deg):
+    """ndt_pg_info_from_cov: a world-frame 3 x 3 covariance seen from the frame at heading th_deg, inverted -> info[6]."""
+    cov = np.ascontiguousarray(cov_world, dtype=np.float64).reshape(9)
+    info = np.zeros(6, dtype=np.float64)
+    _helper_check(lib().ndt_pg_info_from_cov(cov.ctypes.data, float(th_deg), info.ctypes.data), "ndt_pg_info_from_cov")
+    return info
+
+
+def optimize_pose_graphs(ctx, poses, node_offsets, edges, edge_offsets, params=None):
+    """ndt_pg_optimize_batch: graph g = the pose triples [node_offsets[g], node_offsets[g + 1]) of `poses` ([n, 3] float64,
+    th in degrees) and the arcs [edge_offsets[g], edge_offsets[g + 1]) of `edges` (PG_EDGE_DTYPE) -> (new poses, one
+    PG_RESULT_DTYPE record per graph).  `poses` itself is not changed."""
+    out = np.array(poses, dtype=np.float64, order="C").reshape(-1, 3)
+    edges = np.ascontiguousarray(edges, dtype=PG_EDGE_DTYPE)
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    G = len(no) - 1
+    if len(eo) != len(no):
+        raise ValueError("node_offsets and edge_offsets need one entry per graph, plus one")
+    pad_p = out if out.size else np.zeros((1, 3), dtype=np.float64)            # (an address for a batch without nodes)
+    pad_e = edges if edges.size else np.zeros(1, dtype=PG_EDGE_DTYPE)
+    res = np.zeros(max(G, 1), dtype=PG_RESULT_DTYPE)
+    prm = params if params is not None else default_pg_params()
+    ctx.check(lib().ndt_pg_optimize_batch(ctx.h, pad_p.ctypes.data, no.ctypes.data, pad_e.ctypes.data, eo.ctypes.data, G, C.byref(prm),
+                                          res.ctypes.data), "ndt_pg_optimize_batch")
+    return out, res[:G]
+
+
+def optimize_pose_graphs_dev(ctx, poses_ptr, node_offsets, edges_ptr, edge_offsets, out_ptr, params=None, stream=None):
+    """ndt_pg_optimize_batch_dev: device addresses of poses, arcs and records, HOST offset arrays; asynchronous on `stream`."""
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    prm = params if params is not None else default_pg_params()
+    ctx.check(lib().ndt_pg_optimize_batch_dev(ctx.h, poses_ptr, no.ctypes.data, edges_ptr, eo.ctypes.data, len(no) - 1, C.byref(prm),
+                                              out_ptr, stream), "ndt_pg_optimize_batch_dev")
+
+
+def repose_points(ctx, xy, seg_offsets, old_poses, new_poses, out=None):
+    """ndt_repose_points: segment k = the points [seg_offsets[k], seg_offsets[k + 1]) of `xy` ([n, >= 2] float32, the first two
+    of each row), moved from old_poses[k] to new_poses[k] ([K, 3] float64) -> a new array like xy (out=None), or written into
+    `out` (which may be xy itself)."""
+    if not (isinstance(xy, np.ndarray) and xy.dtype == np.float32 and xy.ndim == 2 and xy.shape[1] >= 2 and xy.flags.c_contiguous):
+        xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float32).reshape(len(xy), -1))
+    if out is None:
+        out = xy.copy()
+    if not (out.dtype == np.float32 and out.ndim == 2 and out.shape[1] >= 2 and out.flags.c_contiguous and len(out) == len(xy)):
+        raise ValueError("out needs to be a C-contiguous float32 array with xy's rows")
+    off = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    po = np.ascontiguousarray(old_poses, dtype=np.float64).reshape(-1, 3)
+    pn = np.ascontiguousarray(new_poses, dtype=np.float64).reshape(-1, 3)
+    K = len(off) - 1
+    if len(po) != K or len(pn) != K:
+        raise ValueError("old_poses and new_poses need one row per segment")
+    if K and int(off[-1]) > len(xy):
+        raise ValueError("seg_offsets reach past the points")
+    a = xy if xy.size else np.zeros((1, 2), dtype=np.float32)
+    b = out if out.size else np.zeros((1, 2), dtype=np.float32)
+    ctx.check(lib().ndt_repose_points(ctx.h, a.ctypes.data, a.strides[0], off.ctypes.data, K, po.ctypes.data, pn.ctypes.data, b.ctypes.data,
+                                      b.strides[0]), "ndt_repose_points")
+    return out
+
+
+def repose_points_dev(ctx, xy_ptr, stride, seg_offsets_ptr, n_segs, old_poses_ptr, new_poses_ptr, out_ptr, out_stride, stream=None):
+    """ndt_repose_points_dev: device addresses; asynchronous on `stream` (None: the context's)."""
+    ctx.check(lib().ndt_repose_points_dev(ctx.h, xy_ptr, stride, seg_offsets_ptr, n_segs, old_poses_ptr, new_poses_ptr, out_ptr, out_stride,
+                                          stream), "ndt_repose_points_dev")
 
 
 def _f32c(a):

@@ -53,6 +53,7 @@ thread_local std::string g_last_error;
 #include "ndt_resample.hip.h"
 #include "ndt_score.hip.h"
 #include "ndt_occupancy.hip.h"
+#include "ndt_posegraph.hip.h"
 
 }  // namespace
 
@@ -213,6 +214,8 @@ struct ndt_ctx {
   StagedUpload<unsigned char> fp_tab;                  // ndt_fit_points_batch: offsets, transforms and scans of the call, one upload
   DevBuf<unsigned char> d_occ;                         // ndt_occ_integrate_dev: the call's table of grids, its count of runs and the runs (ndt_occupancy.hip.h)
   StagedUpload<unsigned char> occ_tab, occ_up;         // ... the table's staging; ndt_occ_integrate: offsets, grid_of, origins and scans of the call, one upload
+  DevBuf<unsigned char> d_pg;                          // ndt_pg_optimize_batch_dev: the call's table of graphs, then every graph's scratch (ndt_posegraph.hip.h)
+  StagedUpload<unsigned char> pg_tab;                  // ... the table's staging
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
   DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
@@ -3635,6 +3638,228 @@ int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsi
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
   if ((rc = fr.close())) return rc;
   if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+}  // extern "C"
+
+// ---- ndt_pg_*: pose graphs of many sessions optimised in one launch; ndt_repose_points: stored clouds moved to new poses
+// (kernels in ndt_posegraph.hip.h) ----
+
+namespace {
+
+constexpr uint64_t kPgMax = 1ull << 28;              // nodes or arcs of one graph
+
+// The refusals both forms start with (synchronous, nothing queued or written).
+int pg_check(ndt_ctx *ctx, const void *poses, const uint64_t *node_off, const void *edges, const uint64_t *edge_off, int G,
+             const ndt_pg_params *prm, const void *out, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!poses || !node_off || !edges || !edge_off || !prm || !out) return fail(ctx, NDT_E_ARG, f + ": NULL poses, offsets, edges, params or out");
+  if (G < 1) return fail(ctx, NDT_E_ARG, f + ": need n_graphs >= 1");
+  for (int g = 0; g < G; ++g) {
+    if (node_off[g + 1] < node_off[g] || edge_off[g + 1] < edge_off[g]) return fail(ctx, NDT_E_ARG, f + ": offsets not monotone");
+    if (node_off[g + 1] - node_off[g] >= kPgMax || edge_off[g + 1] - edge_off[g] >= kPgMax)
+      return fail(ctx, NDT_E_ARG, f + ": a graph of 2^28 nodes or arcs or more");
+  }
+  if (prm->max_iter < 1 || prm->max_iter > 10000 || !(prm->eps_step >= 0.0) || !(prm->eps_step <= DBL_MAX) || prm->cg_max_iter < 0 ||
+      prm->cg_max_iter > (1 << 30) || !(prm->cg_rtol > 0.0) || !(prm->cg_rtol < 1.0) || prm->max_halvings < 0 || prm->max_halvings > 60)
+    return fail(ctx, NDT_E_ARG, f + ": parameters out of range");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return NDT_OK;
+}
+
+// The table and the launch on st, inside the caller's frame (d_pg, pg_tab).  node_off / edge_off index poses / edges as given.
+int queue_pg(ndt_ctx *ctx, hipStream_t st, double *poses, const uint64_t *node_off, const ndt_pg_edge *edges, const uint64_t *edge_off,
+             int G, const ndt_pg_params *prm, ndt_pg_result *out) {
+  Regions R;
+  const size_t o_tab = R.take((size_t)G * sizeof(PgRow), 256);
+  int rc;
+  if ((rc = ctx->pg_tab.reserve(ctx, (size_t)G * sizeof(PgRow)))) return rc;
+  PgRow *rows = reinterpret_cast<PgRow *>(ctx->pg_tab.h.p);
+  for (int g = 0; g < G; ++g) {
+    const size_t n = (size_t)(node_off[g + 1] - node_off[g]), m = (size_t)(edge_off[g + 1] - edge_off[g]);
+    size_t n2 = 2;
+    while (n2 < 2 * m) n2 <<= 1;
+    PgRow r{};
+    r.node0 = node_off[g]; r.edge0 = edge_off[g]; r.n = (int)n; r.m = (int)m; r.n2 = (unsigned)n2;
+    r.scratch = m ? R.take(PgLayout(n, m, n2).end * sizeof(double), 256) : 0;   // (a graph without arcs uses none)
+    rows[g] = r;
+  }
+  if ((rc = ctx->d_pg.ensure(ctx, R.end))) return rc;
+  HIP_TRY(ctx, ctx->pg_tab.upload(ctx->d_pg.p + o_tab, 0, (size_t)G * sizeof(PgRow), st));
+  PgParams P{};
+  P.max_iter = prm->max_iter; P.cg_max_iter = prm->cg_max_iter; P.max_halvings = prm->max_halvings;
+  P.eps_step = prm->eps_step; P.cg_rtol = prm->cg_rtol;
+  pg_solve_kernel<<<dim3((unsigned)std::min(G, 1 << 20)), dim3(kPgThreads), 0, st>>>(poses, edges, reinterpret_cast<const PgRow *>(ctx->d_pg.p + o_tab), G,
+                                                                                    P, ctx->d_pg.p, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+int repose_check(ndt_ctx *ctx, const void *xy, size_t stride, const void *off, int n_segs, const void *old_p, const void *new_p,
+                 const void *out, size_t out_stride, const char *fn) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!xy || !off || !old_p || !new_p || !out) return fail(ctx, NDT_E_ARG, f + ": NULL points, offsets, poses or out");
+  if (n_segs < 1) return fail(ctx, NDT_E_ARG, f + ": need n_segs >= 1");
+  if (stride < 8 || (stride & 3) || out_stride < 8 || (out_stride & 3)) return fail(ctx, NDT_E_ARG, f + ": bad stride (need >= 8 and % 4 == 0)");
+  if (out == xy && out_stride != stride) return fail(ctx, NDT_E_ARG, f + ": out is xy at another stride");
+  return NDT_OK;
+}
+
+int queue_repose(ndt_ctx *ctx, hipStream_t st, const void *xy, size_t stride, const uint64_t *off, int n_segs, const double *old_p,
+                 const double *new_p, void *out, size_t out_stride) {
+  const unsigned gy = (unsigned)std::min(n_segs, 65535), gx = std::max(64u, std::min(2048u, 8192u / gy));
+  repose_points_kernel<<<dim3(gx, gy), 256, 0, st>>>((const unsigned char *)xy, stride, (const unsigned long long *)off, n_segs, old_p, new_p,
+                                                      (unsigned char *)out, out_stride);
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+// Pose2D::calRmat's entries (include/ndt_slam/Pose2D.h:43-47)
+void pg_cos_sin(double th_deg, double *c, double *s) { const double a = th_deg * M_PI / 180; *c = std::cos(a); *s = std::sin(a); }
+
+}  // namespace
+
+extern "C" {
+
+int ndt_pg_default_params(ndt_pg_params *p) {
+  if (!p) return NDT_E_ARG;
+  p->max_iter = 20; p->eps_step = 1e-9; p->cg_max_iter = 0; p->cg_rtol = 1e-10; p->max_halvings = 8;
+  return NDT_OK;
+}
+
+int ndt_pg_edge_between(const double from_pose[3], const double to_pose[3], ndt_pg_edge *edge) {
+  if (!from_pose || !to_pose || !edge) return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_between: NULL pointer");
+  for (int k = 0; k < 3; ++k)
+    if (!(std::fabs(from_pose[k]) <= DBL_MAX) || !(std::fabs(to_pose[k]) <= DBL_MAX))
+      return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_between: a pose is not finite");
+  // Pose2D::calMotion(curPose = to, prevPose = from) (src/Pose2D.cpp:5-14)
+  double c, s;
+  pg_cos_sin(from_pose[2], &c, &s);
+  const double dx = to_pose[0] - from_pose[0], dy = to_pose[1] - from_pose[1];
+  edge->rel[0] = c * dx + s * dy;
+  edge->rel[1] = -s * dx + c * dy;
+  double dif = to_pose[2] - from_pose[2];                  // MyUtil::sub_angle (src/MyUtil.cpp:15-23)
+  if (dif < -180) dif += 360; else if (dif >= 180) dif -= 360;
+  edge->rel[2] = dif;
+  return NDT_OK;
+}
+
+int ndt_pg_info_from_cov(const double cov_world[9], double th_deg, double info[6]) {
+  if (!cov_world || !info) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: NULL pointer");
+  for (int k = 0; k < 9; ++k)
+    if (!(std::fabs(cov_world[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not finite");
+  if (!(std::fabs(th_deg) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the heading is not finite");
+  const double *C = cov_world;
+  if (!(C[0] > 0.0) || !(C[4] > 0.0) || !(C[8] > 0.0)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not positive definite");
+  const int pr[3][2] = {{1, 3}, {2, 6}, {5, 7}}, di[3][2] = {{0, 4}, {0, 8}, {4, 8}};
+  for (int k = 0; k < 3; ++k)
+    if (std::fabs(C[pr[k][0]] - C[pr[k][1]]) > 1e-9 * std::sqrt(C[di[k][0]] * C[di[k][1]]))
+      return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not symmetric");
+  const double cxy = 0.5 * (C[1] + C[3]), cxt = 0.5 * (C[2] + C[6]), cyt = 0.5 * (C[5] + C[7]);
+  double c, s;
+  pg_cos_sin(th_deg, &c, &s);
+  // C' = R3^T C R3, R3 = diag(R(th), 1): the xy block R^T Cxy R, the (xy, t) column R^T (cxt, cyt)
+  const double a00 = c * C[0] + s * cxy, a01 = c * cxy + s * C[4];       // rows of R^T Cxy
+  const double a10 = -s * C[0] + c * cxy, a11 = -s * cxy + c * C[4];
+  const double S[9] = {a00 * c + a01 * s, -a00 * s + a01 * c, c * cxt + s * cyt,
+                       0, -a10 * s + a11 * c, -s * cxt + c * cyt,
+                       0, 0, C[8]};
+  const double xx = S[0], xy = S[1], xt = S[2], yy = S[4], yt = S[5], tt = S[8];
+  const double c00 = yy * tt - yt * yt, c01 = yt * xt - xy * tt, c02 = xy * yt - yy * xt;
+  const double m2 = xx * yy - xy * xy, det = xx * c00 + xy * c01 + xt * c02;
+  // Sylvester's criterion to working precision: the pivots xx, m2 / xx, det / m2 against the largest diagonal entry of their
+  // unit (a first matched scan's covariance has 1e-35 m^2 along the motion: positive, and no information anyone can use)
+  const double big = std::max(xx, yy);
+  if (!(xx > 0.0) || !(m2 > 0.0) || !(det > 0.0) || !(det <= DBL_MAX) || !(xx > 1e-12 * big) || !(m2 > 1e-12 * big * xx) ||
+      !(det > 1e-12 * tt * m2))
+    return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not positive definite");
+  info[0] = c00 / det; info[1] = c01 / det; info[2] = c02 / det;
+  info[3] = (xx * tt - xt * xt) / det; info[4] = (xy * xt - xx * yt) / det; info[5] = m2 / det;
+  for (int k = 0; k < 6; ++k)
+    if (!(std::fabs(info[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the inverse is not finite");
+  return NDT_OK;
+}
+
+int ndt_pg_optimize_batch_dev(ndt_ctx *ctx, double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                              const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params, ndt_pg_result *out_dev,
+                              void *stream) {
+  int rc = pg_check(ctx, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, params, out_dev, "ndt_pg_optimize_batch_dev");
+  if (rc) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_pg(ctx, st, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, params, out_dev);
+  });
+}
+
+int ndt_pg_optimize_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                          const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params, ndt_pg_result *out_host) {
+  int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params, out_host, "ndt_pg_optimize_batch");
+  if (rc) return rc;
+  const size_t G = (size_t)n_graphs;
+  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
+  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
+  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions U;
+  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256), o_res = U.take(G * sizeof(ndt_pg_result), 256);
+  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+  unsigned char *d = ctx->d_scan.p;
+  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
+  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
+  if ((rc = queue_pg(ctx, st, (double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs, params,
+                     (ndt_pg_result *)(d + o_res))))
+    return rc;
+  if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, G * sizeof(ndt_pg_result), hipMemcpyDeviceToHost, st));
+  return fr.close_and_wait();
+}
+
+int ndt_repose_points_dev(ndt_ctx *ctx, const float *xy_dev, size_t stride_bytes, const uint64_t *seg_offsets_dev, int n_segs,
+                          const double *old_poses_dev, const double *new_poses_dev, float *out_xy_dev, size_t out_stride_bytes,
+                          void *stream) {
+  int rc = repose_check(ctx, xy_dev, stride_bytes, seg_offsets_dev, n_segs, old_poses_dev, new_poses_dev, out_xy_dev, out_stride_bytes,
+                        "ndt_repose_points_dev");
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  return queue_repose(ctx, st, xy_dev, stride_bytes, seg_offsets_dev, n_segs, old_poses_dev, new_poses_dev, out_xy_dev, out_stride_bytes);
+}
+
+int ndt_repose_points(ndt_ctx *ctx, const float *xy_host, size_t stride_bytes, const uint64_t *seg_offsets_host, int n_segs,
+                      const double *old_poses_host, const double *new_poses_host, float *out_xy_host, size_t out_stride_bytes) {
+  int rc = repose_check(ctx, xy_host, stride_bytes, seg_offsets_host, n_segs, old_poses_host, new_poses_host, out_xy_host, out_stride_bytes,
+                        "ndt_repose_points");
+  if (rc) return rc;
+  const size_t K = (size_t)n_segs;
+  for (size_t k = 0; k < K; ++k)
+    if (seg_offsets_host[k + 1] < seg_offsets_host[k]) return fail(ctx, NDT_E_ARG, "ndt_repose_points: offsets not monotone");
+  const size_t p0 = (size_t)seg_offsets_host[0], np = (size_t)seg_offsets_host[K] - p0;
+  if (np == 0) return NDT_OK;
+  const std::vector<uint64_t> off = rel_offsets(seg_offsets_host, K);
+  // the points packed (8 bytes each) through the call's one staging block; the result comes back into the same place
+  std::vector<float> pk(2 * np);
+  for (size_t i = 0; i < np; ++i) memcpy(&pk[2 * i], (const unsigned char *)xy_host + (p0 + i) * stride_bytes, 8);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions U;
+  const size_t o_off = U.take((K + 1) * 8, 256), o_old = U.take(K * 24, 256), o_new = U.take(K * 24, 256), o_xy = U.take(np * 8, 256);
+  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+  unsigned char *d = ctx->d_scan.p;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_off, off.data(), (K + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_old, old_poses_host, K * 24, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_new, new_poses_host, K * 24, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_xy, pk.data(), np * 8, hipMemcpyHostToDevice, st));
+  if ((rc = queue_repose(ctx, st, d + o_xy, 8, (const uint64_t *)(d + o_off), n_segs, (const double *)(d + o_old), (const double *)(d + o_new),
+                         d + o_xy, 8)))
+    return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(pk.data(), d + o_xy, np * 8, hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close_and_wait())) return rc;
+  for (size_t i = 0; i < np; ++i) memcpy((unsigned char *)out_xy_host + (p0 + i) * out_stride_bytes, &pk[2 * i], 8);
   return NDT_OK;
 }
 

@@ -1,0 +1,532 @@
+// ndt_posegraph.hip.h -- ndt_pg_*: SE(2) pose-graph optimisation of many graphs in one launch, and ndt_repose_points: stored
+// clouds moved from their old scan poses to their new ones (the contract is the header's).  Part of
+// libndt_mi355x.so: included by ndt_mi355x.hip inside its anonymous namespace behind ndt_common.hip.h.  Not a standalone header.
+//
+// One 256-thread workgroup per graph runs every Gauss-Newton iteration of that graph; nothing is shared between workgroups.
+// Node i of a graph belongs to thread i % 256 in every node loop, so the vector updates of the conjugate gradients need no
+// barrier; only H p (reads the neighbours' p), the preconditioner (a serial block-Thomas sweep) and the dot products do.
+// No floating-point atomics: a node sums its arcs' blocks in arc-index order (its list is cut out of a sorted key array),
+// and a dot product is each thread's nodes in index order, a fixed wave tree, then the four waves in order.
+
+constexpr double kPgPi = 3.14159265358979323846;
+constexpr int kPgChunk = 64;                       // nodes of one staged piece of a block-Thomas sweep
+constexpr int kPgThreads = 256;
+
+// One row of a call's table.  scratch: byte offset of the graph's own scratch in the call's block.
+struct PgRow {
+  unsigned long long node0, edge0, scratch;
+  int n, m;                                        // nodes, arcs
+  unsigned n2, pad;                                // length of the key array: a power of two >= 2 m
+};
+static_assert(sizeof(PgRow) == 40, "one 40-byte row per graph");
+
+struct PgParams { int max_iter, cg_max_iter, max_halvings, pad; double eps_step, cg_rtol; };
+
+// An arc linearised at the current poses: cos / sin of the `from` heading, d r_xy / d theta_from = (a, b), the residual.
+struct PgLin { double c, s, a, b, r0, r1, r2, pad; };
+
+// The regions of one graph's scratch, in doubles from its start (host and device agree by calling this one function).
+struct PgLayout {
+  size_t x, xt, g, dl, r, z, p, q, y, D, U, L, Si, W, lin, keys, ptr, end;
+  __host__ __device__ PgLayout(size_t n, size_t m, size_t n2) {
+    size_t o = 0;
+    x = o; o += 3 * n; xt = o; o += 3 * n; g = o; o += 3 * n; dl = o; o += 3 * n; r = o; o += 3 * n; z = o; o += 3 * n;
+    p = o; o += 3 * n; q = o; o += 3 * n; y = o; o += 3 * n;
+    D = o; o += 6 * n; U = o; o += 9 * n; L = o; o += 9 * n; Si = o; o += 6 * n; W = o; o += 9 * n;
+    lin = o; o += 8 * m; keys = o; o += n2; ptr = o; o += (n + 2) / 2 + 1;
+    end = o;
+  }
+};
+
+__device__ __forceinline__ bool pg_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+// into [-pi, pi)
+__device__ __forceinline__ double pg_wrap(double v) {
+  double w = v - 2.0 * kPgPi * floor((v + kPgPi) / (2.0 * kPgPi));
+  if (w >= kPgPi) w -= 2.0 * kPgPi;
+  if (w < -kPgPi) w += 2.0 * kPgPi;
+  return w;
+}
+// degrees into [-180, 180) (MyUtil::add_angle's range, src/MyUtil.cpp:4-11)
+__device__ __forceinline__ double pg_wrap_deg(double v) {
+  double w = v - 360.0 * floor((v + 180.0) / 360.0);
+  if (w >= 180.0) w -= 360.0;
+  if (w < -180.0) w += 360.0;
+  return w;
+}
+
+// Sum over the workgroup in a fixed shape: the wave tree, then the four waves in order.  Every thread gets the same bits.
+__device__ __forceinline__ double pg_block_sum(double v, double *s_w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double t = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  __syncthreads();
+  return t;
+}
+__device__ __forceinline__ double pg_block_max(double v, double *s_w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o));
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double t = fmax(fmax(s_w[0], s_w[1]), fmax(s_w[2], s_w[3]));
+  __syncthreads();
+  return t;
+}
+
+// r = (R(th_i)^T (t_j - t_i) - z_xy, wrap(th_j - th_i - z_th)) of one arc at the poses X (radians)
+__device__ __forceinline__ PgLin pg_linearise(const double *__restrict__ X, const ndt_pg_edge &E) {
+  const double *xi = X + 3 * (size_t)E.from, *xj = X + 3 * (size_t)E.to;
+  PgLin l;
+  l.c = cos(xi[2]); l.s = sin(xi[2]);
+  const double dx = xj[0] - xi[0], dy = xj[1] - xi[1];
+  l.a = -l.s * dx + l.c * dy;
+  l.b = -l.c * dx - l.s * dy;
+  l.r0 = l.c * dx + l.s * dy - E.rel[0];
+  l.r1 = l.a - E.rel[1];
+  l.r2 = pg_wrap(xj[2] - xi[2] - E.rel[2] * (kPgPi / 180.0));
+  l.pad = 0.0;
+  return l;
+}
+
+// w = Omega v, Omega as xx xy xt yy yt tt
+__device__ __forceinline__ void pg_info_mul(const double *__restrict__ I, const double v[3], double w[3]) {
+  w[0] = I[0] * v[0] + I[1] * v[1] + I[2] * v[2];
+  w[1] = I[1] * v[0] + I[3] * v[1] + I[4] * v[2];
+  w[2] = I[2] * v[0] + I[4] * v[1] + I[5] * v[2];
+}
+
+// The Jacobian block of an arc's residual, row-major: side 0 = d r / d x_from, side 1 = d r / d x_to.
+__device__ __forceinline__ void pg_jac(const PgLin &l, int side, double J[9]) {
+  if (side == 0) {
+    J[0] = -l.c; J[1] = -l.s; J[2] = l.a;
+    J[3] = l.s;  J[4] = -l.c; J[5] = l.b;
+    J[6] = 0.0;  J[7] = 0.0;  J[8] = -1.0;
+  } else {
+    J[0] = l.c;  J[1] = l.s;  J[2] = 0.0;
+    J[3] = -l.s; J[4] = l.c;  J[5] = 0.0;
+    J[6] = 0.0;  J[7] = 0.0;  J[8] = 1.0;
+  }
+}
+// out = J^T w
+__device__ __forceinline__ void pg_jt_mul(const double J[9], const double w[3], double out[3]) {
+  out[0] = J[0] * w[0] + J[3] * w[1] + J[6] * w[2];
+  out[1] = J[1] * w[0] + J[4] * w[1] + J[7] * w[2];
+  out[2] = J[2] * w[0] + J[5] * w[1] + J[8] * w[2];
+}
+// out = J v
+__device__ __forceinline__ void pg_j_mul(const double J[9], const double v[3], double out[3]) {
+  out[0] = J[0] * v[0] + J[1] * v[1] + J[2] * v[2];
+  out[1] = J[3] * v[0] + J[4] * v[1] + J[5] * v[2];
+  out[2] = J[6] * v[0] + J[7] * v[1] + J[8] * v[2];
+}
+// M += Ja^T Omega Jb (row-major 3 x 3)
+__device__ __forceinline__ void pg_block_add(const double Ja[9], const double *__restrict__ I, const double Jb[9], double M[9]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double v[3] = {Jb[c], Jb[3 + c], Jb[6 + c]};
+    double w[3], o[3];
+    pg_info_mul(I, v, w);
+    pg_jt_mul(Ja, w, o);
+    M[c] += o[0]; M[3 + c] += o[1]; M[6 + c] += o[2];
+  }
+}
+
+// F = sum r^T Omega r at the poses X: each thread its arcs in index order, then the fixed block sum.
+__device__ double pg_cost(const double *__restrict__ X, const ndt_pg_edge *__restrict__ ed, int m, double *s_w) {
+  double acc = 0.0;
+  for (int e = (int)threadIdx.x; e < m; e += kPgThreads) {
+    const PgLin l = pg_linearise(X, ed[e]);
+    const double r[3] = {l.r0, l.r1, l.r2};
+    double w[3];
+    pg_info_mul(ed[e].info, r, w);
+    acc += (r[0] * w[0] + r[1] * w[1]) + r[2] * w[2];
+  }
+  return pg_block_sum(acc, s_w);
+}
+
+// A pivot of the chain factor counts as positive when it is above this part of its diagonal entry of T: a part of the graph
+// that nothing ties to node 0 leaves pivots at the rounding of the subtraction (1e-16 of the entry, either sign), while the
+// pivots of a connected graph keep a good part of it (0.14 and more on figure-eights up to N = 2000, stars, shuffled numbering).
+constexpr double kPgPivotFloor = 1e-13;
+
+// inverse of a symmetric 3 x 3 (full row-major in, full row-major out); false unless it is finite and positive definite with
+// every pivot S00, m2 / S00, det / m2 above kPgPivotFloor times d0, d1, d2
+__device__ __forceinline__ bool pg_spd_inverse(const double S[9], double d0, double d1, double d2, double Inv[9]) {
+  const double c00 = S[4] * S[8] - S[5] * S[5], c01 = S[5] * S[2] - S[1] * S[8], c02 = S[1] * S[5] - S[4] * S[2];
+  const double m2 = S[0] * S[4] - S[1] * S[1];
+  const double det = (S[0] * c00 + S[1] * c01) + S[2] * c02;
+  if (!(S[0] > kPgPivotFloor * d0) || !(m2 > kPgPivotFloor * d1 * S[0]) || !(det > kPgPivotFloor * d2 * m2) || !(S[0] > 0.0) || !(m2 > 0.0) ||
+      !(det > 0.0) || !pg_finite(det))
+    return false;
+  const double id = 1.0 / det;
+  Inv[0] = c00 * id; Inv[1] = c01 * id; Inv[2] = c02 * id;
+  Inv[4] = (S[0] * S[8] - S[2] * S[2]) * id; Inv[5] = (S[1] * S[2] - S[0] * S[5]) * id;
+  Inv[8] = m2 * id;
+  Inv[3] = Inv[1]; Inv[6] = Inv[2]; Inv[7] = Inv[5];
+  return pg_finite(Inv[0]) && pg_finite(Inv[4]) && pg_finite(Inv[8]);
+}
+
+// Block-Thomas factor of the chain preconditioner T (block-tridiagonal over the nodes 1 .. n-1: D_i on the diagonal, U_i at
+// (i, i + 1)): S_1 = D_1, L_i = U_{i-1}^T S_{i-1}^-1, S_i = D_i - L_i U_{i-1}; kept are L_i, S_i^-1 (six entries) and
+// W_i = S_i^-1 U_i.  The sweep is one lane's; the workgroup stages its input and output through LDS in pieces of kPgChunk
+// nodes so that the lane never waits for global memory.  false: some S_i is not positive definite (pg_spd_inverse).
+__device__ bool pg_factor(const double *__restrict__ D, const double *__restrict__ U, double *__restrict__ L, double *__restrict__ Si,
+                          double *__restrict__ W, int n, double *sh, int *s_ok) {
+  const int tid = (int)threadIdx.x;
+  if (tid == 0) *s_ok = 1;
+  double Sp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i0 = 1; i0 < n; i0 += kPgChunk) {
+    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
+    for (int idx = tid; idx < cn * 15; idx += kPgThreads) {
+      const int a = idx / 15, k = idx % 15, i = i0 + a;
+      sh[a * 30 + k] = k < 6 ? D[6 * (size_t)i + k] : (i > 1 ? U[9 * (size_t)(i - 1) + (k - 6)] : 0.0);
+    }
+    __syncthreads();
+    if (tid == 0 && *s_ok) {
+      for (int a = 0; a < cn; ++a) {
+        const double *d = sh + a * 30, *u = d + 6;
+        double *o = sh + a * 30 + 15;
+        double Lm[9], S[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) Lm[3 * r + c] = (u[r] * Sp[c] + u[3 + r] * Sp[3 + c]) + u[6 + r] * Sp[6 + c];
+        const double Dm[9] = {d[0], d[1], d[2], d[1], d[3], d[4], d[2], d[4], d[5]};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = r; c < 3; ++c) {
+            S[3 * r + c] = Dm[3 * r + c] - ((Lm[3 * r] * u[c] + Lm[3 * r + 1] * u[3 + c]) + Lm[3 * r + 2] * u[6 + c]);
+            S[3 * c + r] = S[3 * r + c];
+          }
+        if (!pg_spd_inverse(S, d[0], d[3], d[5], Sp)) { *s_ok = 0; break; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = Lm[k];
+        o[9] = Sp[0]; o[10] = Sp[1]; o[11] = Sp[2]; o[12] = Sp[4]; o[13] = Sp[5]; o[14] = Sp[8];
+      }
+    }
+    __syncthreads();
+    if (!*s_ok) return false;
+    for (int idx = tid; idx < cn * 15; idx += kPgThreads) {
+      const int a = idx / 15, k = idx % 15, i = i0 + a;
+      const double v = sh[a * 30 + 15 + k];
+      if (k < 9) L[9 * (size_t)i + k] = v; else Si[6 * (size_t)i + (k - 9)] = v;
+    }
+    __syncthreads();
+  }
+  for (int i = 1 + tid; i < n; i += kPgThreads) {
+    const double *s = Si + 6 * (size_t)i, *u = U + 9 * (size_t)i;
+    const double Sm[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        W[9 * (size_t)i + 3 * r + c] = i + 1 < n ? (Sm[3 * r] * u[c] + Sm[3 * r + 1] * u[3 + c]) + Sm[3 * r + 2] * u[6 + c] : 0.0;
+  }
+  __syncthreads();
+  return true;
+}
+
+// z = T^-1 r with the factor above: y_i = r_i - L_i y_{i-1} upwards, v_i = S_i^-1 y_i, z_i = v_i - W_i z_{i+1} downwards.
+// Ends behind a barrier: every thread may read z.
+__device__ void pg_apply(const double *__restrict__ L, const double *__restrict__ Si, const double *__restrict__ W, const double *__restrict__ r,
+                         double *__restrict__ y, double *__restrict__ z, int n, double *sh) {
+  const int tid = (int)threadIdx.x;
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0;             // the lane's carry: y_{i-1}, then z_{i+1}
+  for (int i0 = 1; i0 < n; i0 += kPgChunk) {
+    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
+    for (int idx = tid; idx < cn * 12; idx += kPgThreads) {
+      const int a = idx / 12, k = idx % 12, i = i0 + a;
+      sh[a * 16 + k] = k < 9 ? L[9 * (size_t)i + k] : r[3 * (size_t)i + (k - 9)];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int a = 0; a < cn; ++a) {
+        double *q = sh + a * 16;
+        const double y0 = q[9] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
+        const double y1 = q[10] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
+        const double y2 = q[11] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
+        q[12] = y0; q[13] = y1; q[14] = y2;
+        c0 = y0; c1 = y1; c2 = y2;
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cn * 3; idx += kPgThreads) y[3 * (size_t)(i0 + idx / 3) + idx % 3] = sh[(idx / 3) * 16 + 12 + idx % 3];
+    __syncthreads();
+  }
+  for (int i = 1 + tid; i < n; i += kPgThreads) {
+    const double *s = Si + 6 * (size_t)i;
+    const double a = y[3 * (size_t)i], b = y[3 * (size_t)i + 1], c = y[3 * (size_t)i + 2];
+    y[3 * (size_t)i] = (s[0] * a + s[1] * b) + s[2] * c;
+    y[3 * (size_t)i + 1] = (s[1] * a + s[3] * b) + s[4] * c;
+    y[3 * (size_t)i + 2] = (s[2] * a + s[4] * b) + s[5] * c;
+  }
+  __syncthreads();
+  c0 = c1 = c2 = 0.0;
+  const int chunks = (n - 1 + kPgChunk - 1) / kPgChunk;
+  for (int ch = chunks - 1; ch >= 0; --ch) {
+    const int i0 = 1 + ch * kPgChunk;
+    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
+    for (int idx = tid; idx < cn * 12; idx += kPgThreads) {
+      const int a = idx / 12, k = idx % 12, i = i0 + a;
+      sh[a * 16 + k] = k < 9 ? W[9 * (size_t)i + k] : y[3 * (size_t)i + (k - 9)];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int a = cn - 1; a >= 0; --a) {
+        double *q = sh + a * 16;
+        const double z0 = q[9] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
+        const double z1 = q[10] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
+        const double z2 = q[11] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
+        q[12] = z0; q[13] = z1; q[14] = z2;
+        c0 = z0; c1 = z1; c2 = z2;
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cn * 3; idx += kPgThreads) z[3 * (size_t)(i0 + idx / 3) + idx % 3] = sh[(idx / 3) * 16 + 12 + idx % 3];
+    __syncthreads();
+  }
+}
+
+// All Gauss-Newton iterations of every graph of the call: workgroup w takes the graphs w, w + gridDim.x, ...
+__global__ void __launch_bounds__(kPgThreads)
+pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edges, const PgRow *__restrict__ rows, int n_graphs,
+                PgParams P, unsigned char *__restrict__ scratch, ndt_pg_result *__restrict__ out) {
+  __shared__ double sh[kPgChunk * 30];
+  __shared__ double s_w[4];
+  __shared__ int s_ok;
+  const int tid = (int)threadIdx.x;
+  for (int gi = (int)blockIdx.x; gi < n_graphs; gi += (int)gridDim.x) {
+    const PgRow R = rows[gi];
+    const int n = R.n, m = R.m;
+    double *pose = poses + 3 * R.node0;
+    const ndt_pg_edge *ed = edges + R.edge0;
+    // ---- the graph's own faults: found here, the poses stay as they are ----
+    int bad = 0;
+    for (int i = tid; i < n; i += kPgThreads)
+      if (!pg_finite(pose[3 * (size_t)i]) || !pg_finite(pose[3 * (size_t)i + 1]) || !pg_finite(pose[3 * (size_t)i + 2])) bad = 1;
+    for (int e = tid; e < m; e += kPgThreads) {
+      const ndt_pg_edge E = ed[e];
+      if (E.from < 0 || E.from >= n || E.to < 0 || E.to >= n || E.from == E.to) bad = 1;
+      bool fin = pg_finite(E.rel[0]) && pg_finite(E.rel[1]) && pg_finite(E.rel[2]);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) fin = fin && pg_finite(E.info[k]);
+      const double *I = E.info;
+      const double m2 = I[0] * I[3] - I[1] * I[1];
+      const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
+      if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (bad || m == 0) {
+      if (tid == 0) {
+        ndt_pg_result res;
+        res.cost_initial = 0.0; res.cost_final = 0.0; res.iterations = 0; res.cg_iterations = 0;
+        res.converged = bad ? 0 : 1; res.status = bad ? NDT_E_ARG : NDT_OK;
+        out[gi] = res;
+      }
+      continue;
+    }
+    double *base = reinterpret_cast<double *>(scratch + R.scratch);
+    const PgLayout Y((size_t)n, (size_t)m, (size_t)R.n2);
+    double *x = base + Y.x, *xt = base + Y.xt, *g = base + Y.g, *dl = base + Y.dl, *r = base + Y.r, *z = base + Y.z, *p = base + Y.p,
+           *q = base + Y.q, *y = base + Y.y, *D = base + Y.D, *U = base + Y.U, *L = base + Y.L, *Si = base + Y.Si, *W = base + Y.W;
+    PgLin *lin = reinterpret_cast<PgLin *>(base + Y.lin);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + Y.keys);
+    int *ptr = reinterpret_cast<int *>(base + Y.ptr);
+    // ---- every node's arcs in arc-index order: keys (node, 2 e + side) sorted, then cut at the nodes ----
+    const unsigned n2 = R.n2, m2e = 2u * (unsigned)m;
+    for (unsigned k = (unsigned)tid; k < n2; k += kPgThreads) {
+      unsigned long long key = ~0ull;
+      if (k < m2e) { const ndt_pg_edge &E = ed[k >> 1]; key = ((unsigned long long)(unsigned)((k & 1u) ? E.to : E.from) << 32) | k; }
+      keys[k] = key;
+    }
+    __syncthreads();
+    for (unsigned kk = 2; kk <= n2; kk <<= 1)
+      for (unsigned j = kk >> 1; j > 0; j >>= 1) {
+        for (unsigned i = (unsigned)tid; i < n2; i += kPgThreads) {
+          const unsigned l = i ^ j;
+          if (l > i) {
+            const unsigned long long a = keys[i], b = keys[l];
+            if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
+          }
+        }
+        __syncthreads();
+      }
+    for (unsigned k = (unsigned)tid; k <= m2e; k += kPgThreads) {
+      const int node = k < m2e ? (int)(keys[k] >> 32) : n;
+      const int prev = k > 0 ? (int)(keys[k - 1] >> 32) : -1;
+      for (int v = prev + 1; v <= node; ++v) ptr[v] = (int)k;
+    }
+    // ---- the poses in radians; node 0's entries of the solver's vectors stay zero ----
+    for (int i = tid; i < n; i += kPgThreads) {
+      x[3 * (size_t)i] = pose[3 * (size_t)i]; x[3 * (size_t)i + 1] = pose[3 * (size_t)i + 1];
+      x[3 * (size_t)i + 2] = pose[3 * (size_t)i + 2] * (kPgPi / 180.0);
+    }
+    if (tid < 3) { g[tid] = 0.0; dl[tid] = 0.0; r[tid] = 0.0; z[tid] = 0.0; p[tid] = 0.0; q[tid] = 0.0; y[tid] = 0.0; }
+    __syncthreads();
+    double F = pg_cost(x, ed, m, s_w);
+    const double F0 = F;
+    int iters = 0, cg_total = 0, conv = 0;
+    const int cg_cap = P.cg_max_iter > 0 ? P.cg_max_iter : 6 * n;
+    for (int it = 0; it < P.max_iter; ++it) {
+      // ---- linearise: the arcs, then every node's gradient, diagonal block and chain block ----
+      for (int e = tid; e < m; e += kPgThreads) lin[e] = pg_linearise(x, ed[e]);
+      __syncthreads();
+      for (int i = 1 + tid; i < n; i += kPgThreads) {
+        double gi3[3] = {0, 0, 0}, Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int k = ptr[i]; k < ptr[i + 1]; ++k) {
+          const unsigned slot = (unsigned)keys[k];
+          const int e = (int)(slot >> 1), side = (int)(slot & 1u);
+          const PgLin l = lin[e];
+          const double *I = ed[e].info;
+          const int other = side ? ed[e].from : ed[e].to;
+          double Js[9], Jo[9], w[3], o[3];
+          pg_jac(l, side, Js);
+          const double rr[3] = {l.r0, l.r1, l.r2};
+          pg_info_mul(I, rr, w);
+          pg_jt_mul(Js, w, o);
+          gi3[0] += o[0]; gi3[1] += o[1]; gi3[2] += o[2];
+          pg_block_add(Js, I, Js, Dm);
+          if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add(Js, I, Jo, Um); }
+        }
+        for (int k = 0; k < 3; ++k) { g[3 * (size_t)i + k] = gi3[k]; dl[3 * (size_t)i + k] = 0.0; r[3 * (size_t)i + k] = -gi3[k]; }
+        double *d = D + 6 * (size_t)i;
+        d[0] = Dm[0]; d[1] = Dm[1]; d[2] = Dm[2]; d[3] = Dm[4]; d[4] = Dm[5]; d[5] = Dm[8];
+        for (int k = 0; k < 9; ++k) U[9 * (size_t)i + k] = Um[k];
+      }
+      __syncthreads();
+      if (!pg_factor(D, U, L, Si, W, n, sh, &s_ok)) break;
+      pg_apply(L, Si, W, r, y, z, n, sh);
+      double acc = 0.0;
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+        for (int k = 0; k < 3; ++k) { const double zv = z[3 * (size_t)i + k]; p[3 * (size_t)i + k] = zv; acc += r[3 * (size_t)i + k] * zv; }
+      double rz = pg_block_sum(acc, s_w);
+      if (!(rz >= 0.0) || !pg_finite(rz)) break;
+      bool cg_bad = false;
+      if (rz > 0.0) {
+        const double rz0 = rz;
+        for (int k = 0; k < cg_cap; ++k) {
+          // q = H p, a node's arcs in arc-index order (p of node 0 is zero: its columns are removed)
+          acc = 0.0;
+          for (int i = 1 + tid; i < n; i += kPgThreads) {
+            double qi[3] = {0, 0, 0};
+            const double pi3[3] = {p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]};
+            for (int kk = ptr[i]; kk < ptr[i + 1]; ++kk) {
+              const unsigned slot = (unsigned)keys[kk];
+              const int e = (int)(slot >> 1), side = (int)(slot & 1u);
+              const PgLin l = lin[e];
+              const int other = side ? ed[e].from : ed[e].to;
+              const double po[3] = {p[3 * (size_t)other], p[3 * (size_t)other + 1], p[3 * (size_t)other + 2]};
+              double Js[9], Jo[9], u1[3], u2[3], w[3], o[3];
+              pg_jac(l, side, Js); pg_jac(l, side ^ 1, Jo);
+              pg_j_mul(Js, pi3, u1); pg_j_mul(Jo, po, u2);
+              const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
+              pg_info_mul(ed[e].info, u, w);
+              pg_jt_mul(Js, w, o);
+              qi[0] += o[0]; qi[1] += o[1]; qi[2] += o[2];
+            }
+            for (int c = 0; c < 3; ++c) { q[3 * (size_t)i + c] = qi[c]; acc += pi3[c] * qi[c]; }
+          }
+          const double pq = pg_block_sum(acc, s_w);
+          cg_total++;
+          if (!(pq > 0.0) || !pg_finite(pq)) { cg_bad = true; break; }
+          const double alpha = rz / pq;
+          for (int i = 1 + tid; i < n; i += kPgThreads)
+            for (int c = 0; c < 3; ++c) { dl[3 * (size_t)i + c] += alpha * p[3 * (size_t)i + c]; r[3 * (size_t)i + c] -= alpha * q[3 * (size_t)i + c]; }
+          __syncthreads();
+          pg_apply(L, Si, W, r, y, z, n, sh);
+          acc = 0.0;
+          for (int i = 1 + tid; i < n; i += kPgThreads)
+            for (int c = 0; c < 3; ++c) acc += r[3 * (size_t)i + c] * z[3 * (size_t)i + c];
+          const double rzn = pg_block_sum(acc, s_w);
+          if (!(rzn >= 0.0) || !pg_finite(rzn)) { cg_bad = true; break; }
+          if (sqrt(rzn) <= P.cg_rtol * sqrt(rz0)) break;
+          const double beta = rzn / rz;
+          rz = rzn;
+          for (int i = 1 + tid; i < n; i += kPgThreads)
+            for (int c = 0; c < 3; ++c) p[3 * (size_t)i + c] = z[3 * (size_t)i + c] + beta * p[3 * (size_t)i + c];
+          __syncthreads();
+        }
+      }
+      if (cg_bad) break;
+      // ---- the step: taken only if F does not rise, halved otherwise ----
+      double dmax = 0.0;
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+        for (int c = 0; c < 3; ++c) dmax = fmax(dmax, fabs(dl[3 * (size_t)i + c]));
+      dmax = pg_block_max(dmax, s_w);                            // (NaN entries of d drop out here and fail the cost test)
+      double s = 1.0, Ft = F;
+      bool accepted = false;
+      for (int h = 0; h <= P.max_halvings; ++h) {
+        if (h) s *= 0.5;
+        for (int i = tid; i < n; i += kPgThreads)
+          for (int c = 0; c < 3; ++c) xt[3 * (size_t)i + c] = x[3 * (size_t)i + c] + s * dl[3 * (size_t)i + c];
+        __syncthreads();
+        Ft = pg_cost(xt, ed, m, s_w);
+        if (pg_finite(Ft) && Ft <= F) { accepted = true; break; }
+      }
+      dmax *= s;                                                 // the step taken, or the last one tried
+      if (!accepted) {
+        // the halving ran out below eps_step: halving on could only give a step that is shorter still -- the poses stay
+        if (pg_finite(dmax) && dmax < P.eps_step) conv = 1;
+        break;
+      }
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+        for (int c = 0; c < 3; ++c) x[3 * (size_t)i + c] = xt[3 * (size_t)i + c];
+      __syncthreads();                                           // (the next linearisation reads every node's x)
+      F = Ft;
+      iters++;
+      if (dmax < P.eps_step) { conv = 1; break; }
+    }
+    __syncthreads();
+    // ---- out: the last accepted poses (node 0 and an unmoved graph keep their bytes), the record ----
+    if (iters > 0)
+      for (int i = 1 + tid; i < n; i += kPgThreads) {
+        pose[3 * (size_t)i] = x[3 * (size_t)i]; pose[3 * (size_t)i + 1] = x[3 * (size_t)i + 1];
+        pose[3 * (size_t)i + 2] = pg_wrap_deg(x[3 * (size_t)i + 2] * (180.0 / kPgPi));
+      }
+    if (tid == 0) {
+      ndt_pg_result res;
+      res.cost_initial = F0; res.cost_final = F; res.iterations = iters; res.cg_iterations = cg_total; res.converged = conv; res.status = NDT_OK;
+      out[gi] = res;
+    }
+    __syncthreads();
+  }
+}
+
+// remakeMaps' point correction (src/PointCloudMap.cpp:147-154): q = oldPose.relativePoint(p), p' = newPose.globalPoint(q)
+// (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat builds it, fp64 without contraction, rounded once to float32.  One
+// thread per point; a segment per blockIdx.y, as scan_to_map_kernel takes its scans.  A segment whose poses are bit-equal is
+// copied through (left alone when out is xy itself).
+__global__ void __launch_bounds__(256)
+repose_points_kernel(const unsigned char *__restrict__ xy, size_t stride, const unsigned long long *__restrict__ offsets, int n_segs,
+                     const double *__restrict__ old_poses, const double *__restrict__ new_poses, unsigned char *__restrict__ out,
+                     size_t out_stride) {
+  for (int b = blockIdx.y; b < n_segs; b += gridDim.y) {
+    const unsigned long long r0 = offsets[b], r1 = offsets[b + 1];
+    if (r0 >= r1) continue;
+    const double *po = old_poses + 3 * (size_t)b, *pn = new_poses + 3 * (size_t)b;
+    const bool same = __double_as_longlong(po[0]) == __double_as_longlong(pn[0]) && __double_as_longlong(po[1]) == __double_as_longlong(pn[1]) &&
+                      __double_as_longlong(po[2]) == __double_as_longlong(pn[2]);
+    if (same && out == xy && out_stride == stride) continue;
+    const double tx1 = po[0], ty1 = po[1], a1 = po[2] * M_PI / 180;
+    const double tx2 = pn[0], ty2 = pn[1], a2 = pn[2] * M_PI / 180;
+    const double c1 = cos(a1), s1 = sin(a1), c2 = cos(a2), s2 = sin(a2);
+    const double o00 = c1, o01 = -s1, o10 = s1, o11 = c1;         // oldPose.Rmat
+    const double n00 = c2, n01 = -s2, n10 = s2, n11 = c2;         // newPose.Rmat
+    for (unsigned long long i = r0 + blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < r1;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+      const float *src = reinterpret_cast<const float *>(xy + i * stride);
+      float *dst = reinterpret_cast<float *>(out + i * out_stride);
+      const float fx = src[0], fy = src[1];
+      if (same) { dst[0] = fx; dst[1] = fy; continue; }
+      const double dx = (double)fx - tx1, dy = (double)fy - ty1;
+      const double lx = dx * o00 + dy * o10;
+      const double ly = dx * o01 + dy * o11;
+      const double gx = n00 * lx + n01 * ly + tx2;
+      const double gy = n10 * lx + n11 * ly + ty2;
+      dst[0] = (float)gx; dst[1] = (float)gy;
+    }
+  }
+}
