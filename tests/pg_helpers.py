@@ -2,7 +2,10 @@
 
 oracle_optimize   a dense numpy restatement of the header's model: the same residuals and analytic Jacobians, the normal
                   equations solved by numpy.linalg.solve, full Gauss-Newton steps, no halving.
-figure_eight ...  the graph generators.
+oracle_optimize_halving
+                  the header's whole method, step rule included: "a step d is taken only if F does not rise; otherwise it is
+                  halved, up to max_halvings times", every accepted iterate kept, and how the run ended.
+figure_eight ...  the graph generators; far_start: a figure-eight's arcs from a start metres and tens of degrees away.
 repose_ref        the numpy restatement of ndt_repose_points (fp64, one operation per rounding, then float32).
 """
 import functools
@@ -150,6 +153,61 @@ def oracle_optimize(poses, edges, eps_step=1e-12, max_iter=30):
     return {"poses": out, "costs": costs, "steps": steps, "converged": conv}
 
 
+END_ACCEPTED, END_RUNOUT_BELOW, END_RUNOUT_ABOVE, END_MAX_ITER = "accepted step below eps_step", "run-out below eps_step", \
+    "run-out above eps_step", "max_iter"
+
+
+def oracle_optimize_halving(poses, edges, eps_step=1e-12, max_iter=30, max_halvings=8):
+    """The header's method with a dense solve in place of the conjugate gradients: the Gauss-Newton step d of the normal
+    equations (node 0 fixed), tried at s = 1, 1/2, ... (max_halvings halvings at the most); the first trial whose F is finite
+    and does not rise is taken.  The run ends at an accepted step with max|s d| < eps_step (END_ACCEPTED), at a step that no
+    trial accepts (END_RUNOUT_BELOW / END_RUNOUT_ABOVE by the last trial's max|s d|) or at max_iter.
+    -> dict: poses (deg, wrapped; the last accepted ones), costs (the initial one and one per accepted step), steps (max|s d| of
+    every accepted step), converged, end, and per accepted step iterates (deg, wrapped), halvings, margins (the smallest
+    |Ft - F| / F over the step's trials: how far the closest decision of the step was from a tie); refused: None, or
+    (trials, max|s d| of the last trial, margin) of the step that ran out."""
+    def out_deg(x):
+        out = x.copy()
+        out[:, 2] = wrap_deg(out[:, 2] / DEG)
+        out[0] = poses[0]
+        return out
+
+    x = np.array(poses, np.float64)
+    x[:, 2] *= DEG
+    F = cost(x, edges)
+    costs, steps, iterates, halvings, margins, refused, end = [F], [], [], [], [], None, END_MAX_ITER
+    for _ in range(max_iter):
+        H, b = normal_equations(x, edges)
+        d = np.linalg.solve(H[3:, 3:], -b[3:]).reshape(-1, 3)
+        s, margin, accepted = 1.0, math.inf, False
+        for h in range(max_halvings + 1):
+            if h:
+                s *= 0.5
+            xt = x.copy()
+            xt[1:] += s * d
+            Ft = cost(xt, edges)
+            margin = min(margin, abs(Ft - F) / F) if math.isfinite(Ft) else margin
+            if math.isfinite(Ft) and Ft <= F:
+                accepted = True
+                break
+        dmax = s * float(np.abs(d).max())
+        if not accepted:
+            refused = (h + 1, dmax, margin)
+            end = END_RUNOUT_BELOW if dmax < eps_step else END_RUNOUT_ABOVE
+            break
+        x, F = xt, Ft
+        costs.append(F)
+        steps.append(dmax)
+        iterates.append(out_deg(x))
+        halvings.append(h)
+        margins.append(margin)
+        if dmax < eps_step:
+            end = END_ACCEPTED
+            break
+    return {"poses": out_deg(x), "costs": costs, "steps": steps, "converged": end in (END_ACCEPTED, END_RUNOUT_BELOW), "end": end,
+            "iterates": iterates, "halvings": halvings, "margins": margins, "refused": refused}
+
+
 def iterations_at(res, eps_step):
     """The number of steps the oracle's run takes until one is below eps_step."""
     for k, s in enumerate(res["steps"]):
@@ -230,6 +288,57 @@ def star(N=40):
     return start, make_edges(rows)
 
 
+def far_start(N, sxy, sth, seed):
+    """The arcs of figure_eight(N) from a start that drift has taken away: the nodes 1 .. N-1 moved by normal(0, sxy) metres in
+    x and y, then turned by normal(0, sth) degrees."""
+    poses, edges = figure_eight(N)
+    rng = np.random.default_rng(seed)
+    start = poses.copy()
+    start[1:, :2] += rng.normal(0.0, sxy, (N - 1, 2))
+    start[1:, 2] = wrap_deg(start[1:, 2] + rng.normal(0.0, sth, N - 1))
+    return start, edges
+
+
+def hub(N=300, at=7):
+    """Every node tied to node `at` (every second arc stored towards it), plus every third (j, j + 2); the start is the truth
+    disturbed.  The hub is a free node: its list holds N - 1 arcs."""
+    rng = np.random.default_rng(9000 + N)
+    truth = eight_truth(N)
+    rows = []
+    for j in range(N):
+        if j == at:
+            continue
+        a, b = (j, at) if j % 2 else (at, j)
+        rows.append((a, b, _noisy(between(truth[a], truth[b]), rng, (0.01, 0.01, 0.004)), OMEGA_ODO))
+    rows += [(j, j + 2, _noisy(between(truth[j], truth[j + 2]), rng, (0.002, 0.002, 0.001)), OMEGA_LOOP) for j in range(1, N - 2, 3)]
+    start = truth.copy()
+    start[1:, :2] += rng.normal(0.0, 0.05, (N - 1, 2))
+    start[1:, 2] = wrap_deg(start[1:, 2] + rng.normal(0.0, 0.02, N - 1) / DEG)
+    return start, make_edges(rows)
+
+
+def dense(N, E):
+    """The chain of figure_eight(N) and E - (N - 1) arcs between random pairs, in either direction, pairs repeated."""
+    poses, chain = figure_eight(N, n_loops=0)
+    rng = np.random.default_rng(11000 + 7 * N + E)
+    truth = eight_truth(N)
+    rows = []
+    while len(rows) < E - len(chain):
+        a, b = (int(v) for v in rng.integers(0, N, 2))
+        if a != b:
+            rows.append((a, b, _noisy(between(truth[a], truth[b]), rng, (0.002, 0.002, 0.001)), OMEGA_LOOP))
+    return poses, np.concatenate([chain, make_edges(rows)])
+
+
+def scaled_info(N):
+    """figure_eight(N) with every arc's information scaled by its own 10**uniform(-3, 3)."""
+    poses, edges = figure_eight(N)
+    rng = np.random.default_rng(13000 + N)
+    e = edges.copy()
+    e["info"] *= (10.0 ** rng.uniform(-3.0, 3.0, len(e)))[:, None]
+    return poses, e
+
+
 EIGHT_SIZES = (24, 63, 64, 65, 255, 256, 257, 1000)
 WORKLOADS = {("eight", n): functools.partial(figure_eight, n) for n in EIGHT_SIZES}
 WORKLOADS.update({("eight", 4): functools.partial(figure_eight, 4),
@@ -239,10 +348,52 @@ WORKLOADS.update({("eight", 4): functools.partial(figure_eight, 4),
                   ("reversed", 65): functools.partial(figure_eight, 65, reverse_chain=True)})
 
 
+DENSE_SIZES = ((24, 127), (24, 128), (24, 129), (24, 600), (12, 1025))      # 2 E: 254, 256, 258 around the key array's 256; 2050
+SHAPE_WORKLOADS = {("hub", 300): functools.partial(hub, 300, 7), ("scaled", 24): functools.partial(scaled_info, 24),
+                   ("scaled", 65): functools.partial(scaled_info, 65)}
+SHAPE_WORKLOADS.update({("dense%d_" % n, e): functools.partial(dense, n, e) for n, e in DENSE_SIZES})
+
+# (N, sxy [m], sth [deg], seed) of far_start
+FAR_STARTS = {"far24a": (24, 2.0, 60.0, 2), "far24b": (24, 1.5, 50.0, 2), "far65": (65, 2.0, 60.0, 9),
+              "far257": (257, 2.0, 40.0, 4)}             # (N = 257: the node loops take two trips)
+FAR_STEP_MIN = 1e-6                                    # a step the GPU test compares is longer than this ...
+FAR_MARGIN_MIN = 1e-6                                  # ... and none of its decisions is closer to a tie than this
+# (workload, max_halvings, eps_step, the end, accepted steps): a coarse eps_step between the length of a halved step and that of
+# its full step -- `converged` is judged on the step taken (or the last one tried), not on the full one
+FAR_COARSE_CASES = (("far24a", 8, 18.0, END_ACCEPTED, 2), ("far257", 1, 18.6, END_RUNOUT_BELOW, 2))
+FAR_CAP_NAME = "far24a"
+FAR_CAP_CASES = ((0, 2), (1, 3))                       # (max_halvings, the step of far24a that needs one more)
+
+
+@functools.lru_cache(maxsize=None)
+def far_workload(name):
+    """(start poses, edges, the halving oracle's run to 1e-12 with the default max_halvings, the number of compared steps:
+    those in front of the first one that is not longer than FAR_STEP_MIN) of FAR_STARTS[name], made once per process."""
+    poses, edges = far_start(*FAR_STARTS[name])
+    ref = oracle_optimize_halving(poses, edges, eps_step=1e-12, max_iter=30, max_halvings=8)
+    k = next((i for i, s in enumerate(ref["steps"]) if not s > FAR_STEP_MIN), len(ref["steps"]))
+    poses.setflags(write=False)
+    edges.setflags(write=False)
+    return poses, edges, ref, k
+
+
+def rigid_move(poses, to_xy, turn_deg):
+    """Every pose turned by turn_deg about pose 0's position, then translated so that pose 0 lies at to_xy."""
+    p = np.asarray(poses, np.float64)
+    c, s = math.cos(turn_deg * DEG), math.sin(turn_deg * DEG)
+    d = p[:, :2] - p[0, :2]
+    out = np.empty_like(p)
+    out[:, 0] = c * d[:, 0] - s * d[:, 1] + to_xy[0]
+    out[:, 1] = s * d[:, 0] + c * d[:, 1] + to_xy[1]
+    out[:, 2] = wrap_deg(p[:, 2] + turn_deg)
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def workload(key):
-    """(start poses, edges, the oracle's run to 1e-12) of WORKLOADS[key], made once per process; read-only."""
-    poses, edges = WORKLOADS[key]()
+    """(start poses, edges, the oracle's run to 1e-12) of WORKLOADS[key] or SHAPE_WORKLOADS[key], made once per process;
+    read-only."""
+    poses, edges = (WORKLOADS.get(key) or SHAPE_WORKLOADS[key])()
     ref = oracle_optimize(poses, edges, eps_step=1e-12)
     poses.setflags(write=False)
     edges.setflags(write=False)

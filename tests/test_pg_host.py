@@ -1,5 +1,6 @@
 """Pose graphs without a GPU: the oracle of tests/pg_helpers.py against finite differences and on every workload the GPU
-tests compare with, and the two host helpers of the library (ndt_pg_edge_between, ndt_pg_info_from_cov) against numpy."""
+tests compare with, the halving oracle against the full-step one and the conditions under which its iterates may be compared
+with the device's, and the two host helpers of the library (ndt_pg_edge_between, ndt_pg_info_from_cov) against numpy."""
 import ctypes as C
 import math
 
@@ -79,6 +80,137 @@ def test_oracle_converges_in_full_steps(key):
     assert np.isfinite(ref["poses"]).all()
     assert ref["poses"][0].tobytes() == poses[0].tobytes()
     assert (ref["poses"][:, 2] >= -180).all() and (ref["poses"][:, 2] < 180).all()
+
+
+@pytest.mark.parametrize("key", sorted(H.SHAPE_WORKLOADS), ids=lambda k: "%s%d" % k)
+def test_shape_workloads_are_what_they_claim_and_converge_in_full_steps(key):
+    poses, edges, ref = H.workload(key)
+    N, E = len(poses), len(edges)
+    assert ref["converged"] and 3 <= H.iterations_at(ref, 1e-9) <= 6, ref["steps"]
+    assert np.isfinite(ref["poses"]).all() and ref["poses"][0].tobytes() == poses[0].tobytes()
+    degree = np.bincount(np.concatenate([edges["from"], edges["to"]]), minlength=N)
+    if key[0] == "hub":
+        towards = int((edges["to"] == 7).sum())
+        assert degree[7] >= N - 1 and degree[np.arange(N) != 7].max() <= 4 and abs(2 * towards - (N - 1)) <= 1 and degree[0] >= 1
+    elif key[0].startswith("dense"):
+        assert (N, E) == (int(key[0][5:-1]), key[1]) and (degree > 0).all()
+        assert set(2 * e for _, e in H.DENSE_SIZES) >= {254, 256, 258}         # at and on either side of a key array of 256
+        assert (edges["from"][N - 1:] > edges["to"][N - 1:]).any() and (edges["from"][N - 1:] < edges["to"][N - 1:]).any()
+    else:
+        x = np.array(poses)
+        x[:, 2] *= H.DEG
+        Hm, _ = H.normal_equations(x, edges)
+        scale = edges["info"][:, 0] / H.figure_eight(N)[1]["info"][:, 0]
+        assert np.linalg.cond(Hm[3:, 3:]) >= 1e7 and scale.max() / scale.min() >= 1e5
+
+
+# ---- the halving oracle, and the conditions on the far-start workloads (every one a condition on the reference alone) ----
+
+def test_halving_oracle_takes_the_full_step_oracles_steps():
+    """Where no step raises F the two oracles are the same arithmetic: equal bit for bit in every cost and step length and in
+    the iterate reached, for as long as the steps are longer than 1e-6 (shorter ones are decided by the rounding of F)."""
+    for key in sorted(H.WORKLOADS):
+        poses, edges, ref = H.workload(key)
+        k = next((i for i, s in enumerate(ref["steps"]) if not s > H.FAR_STEP_MIN), len(ref["steps"]))
+        assert k >= 2, (key, ref["steps"])
+        hv = H.oracle_optimize_halving(poses, edges, eps_step=0.0, max_iter=k)
+        assert hv["end"] == H.END_MAX_ITER and hv["halvings"] == [0] * k, (key, hv["halvings"])
+        assert hv["steps"] == ref["steps"][:k] and hv["costs"] == ref["costs"][:k + 1], key
+        full = H.oracle_optimize(poses, edges, eps_step=0.0, max_iter=k)
+        assert hv["poses"].tobytes() == full["poses"].tobytes() == hv["iterates"][-1].tobytes(), key
+
+
+def test_halving_oracle_ends():
+    poses, edges, ref, k = H.far_workload("far24a")
+    assert ref["converged"] and ref["end"] in (H.END_ACCEPTED, H.END_RUNOUT_BELOW)
+    assert len(ref["iterates"]) == len(ref["steps"]) == len(ref["halvings"]) == len(ref["margins"]) == len(ref["costs"]) - 1
+    for a, b in zip(ref["costs"], ref["costs"][1:]):
+        assert b <= a                                                    # the rule itself: nothing that raises F is taken
+    cut = H.oracle_optimize_halving(poses, edges, eps_step=1e-12, max_iter=3)
+    assert cut["end"] == H.END_MAX_ITER and not cut["converged"] and cut["poses"].tobytes() == ref["iterates"][2].tobytes()
+    coarse = H.oracle_optimize_halving(poses, edges, eps_step=1e-3)
+    n = H.iterations_at(ref, 1e-3)
+    assert coarse["end"] == H.END_ACCEPTED and coarse["converged"] and len(coarse["steps"]) == n
+    assert coarse["poses"].tobytes() == ref["iterates"][n - 1].tobytes()
+    for it in ref["iterates"]:
+        assert it[0].tobytes() == poses[0].tobytes() and (it[:, 2] >= -180).all() and (it[:, 2] < 180).all()
+    # a run-out below eps_step: from the minimiser, with an eps_step that every proposed step is below
+    at_min = H.oracle_optimize_halving(ref["poses"], edges, eps_step=1e-3, max_halvings=0)
+    assert at_min["end"] in (H.END_RUNOUT_BELOW, H.END_ACCEPTED) and at_min["converged"]
+
+
+@pytest.mark.parametrize("name", sorted(H.FAR_STARTS))
+def test_far_starts_can_be_compared_iterate_by_iterate(name):
+    """What makes a comparison of iterates with the device mean something: every compared step is longer than 1e-6, none of its
+    decisions (Ft <= F at every trial) is closer to a tie than 1e-6 of F -- the device evaluates F to about 1e-13 of it -- there
+    are six such steps at least, and the run ends in the minimum that the near start of the same arcs reaches."""
+    poses, edges, ref, k = H.far_workload(name)
+    N = H.FAR_STARTS[name][0]
+    print("far start %s: N %d E %d | F %.4g -> %.6f | halvings %s | steps %s | margins %s | %d compared, ends: %s"
+          % (name, N, len(edges), ref["costs"][0], ref["costs"][-1], ref["halvings"], ["%.2g" % s for s in ref["steps"]],
+             ["%.2g" % s for s in ref["margins"]], k, ref["end"]))
+    assert k >= 6, (k, ref["steps"])
+    assert all(s > H.FAR_STEP_MIN for s in ref["steps"][:k])
+    assert all(m >= H.FAR_MARGIN_MIN for m in ref["margins"][:k]), ref["margins"]
+    assert max(ref["halvings"][:k]) >= 1, ref["halvings"]
+    assert ref["converged"], ref["end"]
+    near = H.workload(("eight", N))[2]
+    assert H.pose_error(ref["poses"], near["poses"]) <= (1e-8, 1e-8)
+    assert abs(ref["costs"][-1] - near["costs"][-1]) <= 1e-9 * near["costs"][-1]
+    assert ref["costs"][0] > 1e4 * ref["costs"][-1]                       # a far start indeed
+
+
+def test_far_starts_hold_a_step_of_one_halving_and_a_step_of_two():
+    seen = set()
+    for name in H.FAR_STARTS:
+        _, _, ref, k = H.far_workload(name)
+        seen |= set(ref["halvings"][:k])
+    assert {0, 1, 2} <= seen, seen
+    assert max(H.FAR_STARTS[n][0] for n in H.FAR_STARTS) > 256            # one of them takes the node loops round twice
+
+
+@pytest.mark.parametrize("max_halvings, k", H.FAR_CAP_CASES)
+def test_cap_cases_run_out_above_eps_step(max_halvings, k):
+    """With max_halvings one below what step k of far24a needs, the run ends at that step, refused at every trial, after
+    exactly k - 1 accepted steps; the refused trials are the first ones of the full run's step k, so their margin is its."""
+    poses, edges, ref, n_cmp = H.far_workload(H.FAR_CAP_NAME)
+    assert k <= n_cmp and ref["halvings"][k - 1] == max_halvings + 1, ref["halvings"]
+    cap = H.oracle_optimize_halving(poses, edges, eps_step=1e-9, max_iter=20, max_halvings=max_halvings)
+    assert cap["end"] == H.END_RUNOUT_ABOVE and not cap["converged"]
+    assert len(cap["steps"]) == k - 1 and cap["halvings"] == ref["halvings"][:k - 1]
+    assert cap["poses"].tobytes() == ref["iterates"][k - 2].tobytes()
+    trials, dmax, margin = cap["refused"]
+    assert trials == max_halvings + 1 and dmax > 1.0 and margin >= ref["margins"][k - 1] >= H.FAR_MARGIN_MIN
+
+
+@pytest.mark.parametrize("name, max_halvings, eps_step, end, n_steps", H.FAR_COARSE_CASES)
+def test_coarse_eps_step_cases_end_on_the_length_of_the_halved_step(name, max_halvings, eps_step, end, n_steps):
+    """The run ends `converged` at a step whose halved length is below eps_step and whose full length is above it, by a
+    tenth of eps_step at least on either side; every step in front of it is longer than eps_step by as much."""
+    poses, edges, ref, _ = H.far_workload(name)
+    run = H.oracle_optimize_halving(poses, edges, eps_step=eps_step, max_iter=20, max_halvings=max_halvings)
+    assert run["end"] == end and run["converged"] and len(run["steps"]) == n_steps
+    assert run["poses"].tobytes() == ref["iterates"][n_steps - 1].tobytes()
+    if end == H.END_ACCEPTED:
+        last, halvings, front = run["steps"][-1], run["halvings"][-1], run["steps"][:-1]
+        assert run["margins"][-1] >= H.FAR_MARGIN_MIN
+    else:
+        trials, last, margin = run["refused"]
+        halvings, front = trials - 1, run["steps"]
+        assert margin >= H.FAR_MARGIN_MIN
+    assert halvings >= 1 and last <= 0.9 * eps_step and last * 2 ** halvings >= 1.1 * eps_step, (last, halvings)
+    assert all(s >= 1.1 * eps_step for s in front), front
+
+
+def test_rigid_move_keeps_every_arc():
+    poses, edges, _ = H.workload(("eight", 65))
+    moved = H.rigid_move(poses, (8191.7, -8003.3), 137.0)
+    assert np.abs(moved[0, :2] - (8191.7, -8003.3)).max() == 0.0
+    for e in edges[::7]:
+        a, b = int(e["from"]), int(e["to"])
+        d = H.between(moved[a], moved[b]) - H.between(poses[a], poses[b])
+        assert np.abs(d[:2]).max() <= 1e-11 and abs(H.wrap_deg(d[2])) <= 1e-11      # 8e3 m in fp64: 1e-12
+    assert abs(H.cost_deg(moved, edges) - H.cost_deg(poses, edges)) <= 1e-6 * H.cost_deg(poses, edges)
 
 
 def test_figure_eight_heading_crosses_180():
