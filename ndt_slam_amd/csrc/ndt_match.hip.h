@@ -483,6 +483,7 @@ __device__ __noinline__ void fill_window_fetch(const MapView &M, Lds &L, uint4 *
       const u64 cb = (u64)__double_as_longlong(rc[u].y);
       CellEntry E; E.cent = make_float2(__uint_as_float((unsigned)cb), __uint_as_float((unsigned)(cb >> 32)));
       E.mx = ra[u].x; E.my = ra[u].y; E.i00 = rb[u].x; E.i01 = rb[u].y; E.i11 = rc[u].x;
+      finite_icov(E.i00, E.i01, E.i11);
       ent[nx[u]] = E;
     }
   }

@@ -86,12 +86,23 @@ __device__ __forceinline__ unsigned in_radius(float r2, float xt, float yt, floa
 
 struct CellRec { double mx, my, i00, i01, i11; };
 
+// leaf_finalize's third return (eig_mult 0, exactly collinear points, no identity start) leaves a voxel in the search set
+// whose inverse covariance is not finite: PCL keeps icov_ as computed.  In the reference every pair with such a voxel has a
+// NaN exponent, fails updateDerivatives' check and adds nothing.  Here the pair's e = 0 would meet a non-finite u in the
+// sums (0 * inf), so the record is read as 1e140 * I: e underflows to an exact zero for every |q|^2 above 1e-137 while u and
+// the Hessian term stay finite -- the pair is counted and adds exactly nothing.  Where records are fetched, not per pair
+// in the LDS path.
+__device__ __forceinline__ void finite_icov(double &i00, double &i01, double &i11) {
+  if (!(fabs(i00) + fabs(i01) + fabs(i11) < (double)INFINITY)) { i00 = 1.0e140; i01 = 0.0; i11 = 1.0e140; }
+}
+
 __device__ __forceinline__ CellRec load_rec_global(const MapView &M, size_t base, int k) {
   const int r = (k * 11) >> 5, q = k - 3 * r;                 // k / 3 for k in [0, 9)
   const double *rec = M.rec + (base + (size_t)(r * M.gw + q)) * 8;
   const double2 a = gld_d2(rec);
   const double2 b = gld_d2(rec + 2);
   CellRec c; c.mx = a.x; c.my = a.y; c.i00 = b.x; c.i01 = b.y; c.i11 = gld_d(rec + 4);
+  finite_icov(c.i00, c.i01, c.i11);
   return c;
 }
 

@@ -73,8 +73,12 @@ class Cells:
                     if w[1] < thr:
                         w[1] = thr
                     cov3 = V @ np.diag(w) @ np.linalg.inv(V)
-                ic3 = np.linalg.inv(cov3[:2, :2])
-                ic = np.array([ic3[0, 0], 0.5 * (ic3[0, 1] + ic3[1, 0]), ic3[1, 1]])
+                try:
+                    ic3 = np.linalg.inv(cov3[:2, :2])
+                    ic = np.array([ic3[0, 0], 0.5 * (ic3[0, 1] + ic3[1, 0]), ic3[1, 1]])
+                except np.linalg.LinAlgError:               # exactly singular (collinear points, eig_mult 0): PCL keeps the
+                    ic = np.full(3, np.inf)                 # infinite inverse and drops the voxel from the valid ones
+                    ok = False
             idx.append(int(skey[s])); cent.append(c32); mean.append(mu); icov.append(ic)
             npts.append(n if ok else -n)
         self.idx = np.array(idx, dtype=np.int64)
