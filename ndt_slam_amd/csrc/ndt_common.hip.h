@@ -124,6 +124,106 @@ __device__ __forceinline__ int wave_max_dpp(int x) {
 }
 __device__ __forceinline__ unsigned long long gld_u64(const unsigned long long *p) { return *(const NDT_GLOBAL unsigned long long *)p; }
 
+// ------------------------------------------------------------------------------------------
+// wave and workgroup primitives
+// ------------------------------------------------------------------------------------------
+
+// 64-bit values: the __shfl_up form (DPP moves are 32 bits wide).  int: the DPP form.
+__device__ __forceinline__ int wave_incl_scan(int x) { return (int)wave_incl_scan((unsigned)x); }
+__device__ __forceinline__ unsigned long long wave_incl_scan(unsigned long long x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const unsigned long long u = __shfl_up(x, o, 64); if (lane >= o) x += u; }
+  return x;
+}
+
+// Reductions over the 64 lanes, valid in lane 0.  The tree is fixed -- lane l takes lane l + 32, then + 16, ... + 1 -- and
+// every floating-point sum that is compared bit for bit depends on it (the match, score and fitness sums, the pose graph).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+  return x;
+}
+__device__ __forceinline__ float wave_min(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_down(x, o));
+  return x;
+}
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_down(x, o));
+  return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_down(x, o));
+  return x;
+}
+// The integer minimum with the result in every lane (butterfly).
+__device__ __forceinline__ int wave_min_all(int x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o));
+  return x;
+}
+
+// Inclusive sum over a workgroup of exactly kThreads threads (a multiple of 64, at most 1024), every thread calling it: the
+// wave scan, the waves' totals through sh[kThreads / 64] and wave 0, three barriers.  *total: the sum of all threads'
+// values.  T: unsigned, or unsigned long long.  sh may be used again as soon as the call returns.
+template <int kThreads, typename T>
+__device__ __forceinline__ T block_incl_scan(T v, T *sh, T *total) {
+  constexpr int kWaves = kThreads / 64;
+  static_assert(kThreads % 64 == 0 && kWaves >= 1 && kWaves <= 16, "whole waves, at most 1024 threads");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = wave_incl_scan(v);
+  if (lane == 63) sh[wave] = v;
+  __syncthreads();
+  if (wave == 0) {
+    const T w = wave_incl_scan(lane < kWaves ? sh[lane] : (T)0);
+    if (lane < kWaves) sh[lane] = w;
+  }
+  __syncthreads();
+  const T r = v + (wave ? sh[wave - 1] : (T)0);
+  *total = sh[kWaves - 1];
+  __syncthreads();
+  return r;
+}
+
+// Exclusive offsets of n items by ONE workgroup of kThreads threads, in rounds of kThreads items with a carry: thread t of
+// round r has item i = r kThreads + t, v = load(i), and store(i, sum of the items in front of i, v); returns the sum of all
+// items (in every thread).  load and store are called for i < n only, by the same thread, and all loads of a round come
+// before its stores (a barrier lies between): a caller may keep what load found out in variables that store reads, and may
+// store where it loaded.
+template <int kThreads, typename T, typename I, typename Load, typename Store>
+__device__ __forceinline__ T block_excl_offsets(I n, T *sh, Load load, Store store) {
+  T carry = 0;
+  for (I base = 0; base < n; base += (I)kThreads) {
+    const I i = base + (I)threadIdx.x;
+    const T v = i < n ? load(i) : (T)0;
+    T sum;
+    const T incl = block_incl_scan<kThreads>(v, sh, &sum);
+    if (i < n) store(i, carry + incl - v, v);
+    carry += sum;
+  }
+  return carry;
+}
+
+// Ballot compaction over a workgroup of kThreads threads: the number of flagged threads in front of this one (its place in a
+// packed output that keeps the order) and, in *count, the number of flagged threads.  One barrier; wsum[kThreads / 64] must
+// not be in use by a wave that is still in front of an earlier barrier.
+template <int kThreads>
+__device__ __forceinline__ int block_rank(bool flag, int *wsum, int *count) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(flag);
+  if (lane == 0) wsum[wave] = __builtin_popcountll(b);
+  __syncthreads();
+  int front = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) { const int c = wsum[w]; front += w < wave ? c : 0; all += c; }
+  *count = all;
+  return front + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+}
+
 __device__ __forceinline__ float2 load_pt(const float *xy, size_t stride, size_t i) {
   return *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(xy) + i * stride);
 }
@@ -169,18 +269,24 @@ __device__ __forceinline__ Tf32 tf_from_p(const double p[3], int libm_f32) {
   return t;
 }
 
-// pcl::transformPointCloud on a z = 0 point, float32, no contraction.
-__device__ __forceinline__ void tf_apply(const Tf32 &t, int sse, float x, float y, float &ox,
-                                         float &oy) {
-  float ms = -t.s;
-  float a = t.c * x, b = ms * y, c = t.s * x, d = t.c * y;
-  if (!sse) {
-    float r = a + b; ox = r + t.tx;
-    float q = c + d; oy = q + t.ty;
-  } else {
-    float r = b + t.tx; ox = a + r;
-    float q = d + t.ty; oy = c + q;
-  }
+// pcl::transformPointCloud on a z = 0 point, float32, no contraction.  SSE: the order of the additions of the map's build of PCL
+// (MapView::transform_sse).
+template <bool SSE>
+__device__ __forceinline__ void tf_apply_t(const Tf32 &t, float x, float y, float &ox, float &oy) {
+  const float ms = -t.s;
+  const float a = t.c * x, b = ms * y, c = t.s * x, d = t.c * y;
+  if (!SSE) { const float r = a + b; ox = r + t.tx; const float q = c + d; oy = q + t.ty; }
+  else      { const float r = b + t.tx; ox = a + r; const float q = d + t.ty; oy = c + q; }
+}
+__device__ __forceinline__ void tf_apply(const Tf32 &t, int sse, float x, float y, float &ox, float &oy) {
+  if (sse) tf_apply_t<true>(t, x, y, ox, oy); else tf_apply_t<false>(t, x, y, ox, oy);
+}
+
+// The voxel coordinate of a float: floor(x / leaf) as a float clamped to +-1e9, so that the conversion to int is defined for
+// every input (NaN -> -1e9: outside every grid and window).  The build's grid (grid_of_box on the host, voxel_of) and every
+// lookup of the match, score and fitness kernels go through this one definition: they must agree bit for bit.
+__host__ __device__ __forceinline__ float voxel_coord(float x, float inv_leaf) {
+  return fminf(fmaxf(floorf(x * inv_leaf), -1.0e9f), 1.0e9f);
 }
 
 __device__ __forceinline__ bool finite2(float x, float y) {

@@ -28,10 +28,7 @@ __device__ __forceinline__ float sq_dist(float qx, float qy, float px, float py)
 // The search is bound by the latency of its dependent loads (offsets -> bucket -> next bucket ...), so a bucket is
 // fetched kFitWide 16-byte loads (two points each) at a time, all in flight together; loads past the end of the
 // bucket re-read its last pair and are masked out.
-#ifndef NDT_FIT_WIDE
-#define NDT_FIT_WIDE 6
-#endif
-constexpr int kFitWide = NDT_FIT_WIDE;
+constexpr int kFitWide = 6;
 __device__ __forceinline__ float scan_bucket(const float2 *__restrict__ pts, int s, int se, float qx,
                                              float qy, float best) {
   if (s >= se) return best;
@@ -164,10 +161,7 @@ __device__ __forceinline__ float nearest_ring1_lane(const MapView &M, float qx, 
 // need it put their ranges into LDS and the (query, point) pairs of the whole wave are dealt out to all 64 lanes --
 // the same points, the same float32 expression, the minimum taken with an integer atomic (non-negative floats order
 // like their bit patterns), so the result is the one nearest_ring1_lane gives.
-#ifndef NDT_RING_JOINT_MAX
-#define NDT_RING_JOINT_MAX 12
-#endif
-constexpr int kRingJointMax = NDT_RING_JOINT_MAX;
+constexpr int kRingJointMax = 12;
 struct RingLds {                 // per wave
   int start[64];                 // first item of the query with rank k (k-th lane that needs ring 1)
   float qx[64], qy[64];

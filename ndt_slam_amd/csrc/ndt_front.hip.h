@@ -14,16 +14,10 @@
 // ------------------------------------------------------------------------------------------
 constexpr int kPfSlots = 512;
 struct __attribute__((aligned(8))) PfSlot { int ix, iy, cnt; float cx, cy; int pad; };   // 24 B: one b128 + one b64 LDS read
-#ifndef NDT_PF_SORTED
-#define NDT_PF_SORTED 1   // 0: every scan through the step-by-step replay (A/B)
-#endif
-#ifndef NDT_PF_AHEAD
-#define NDT_PF_AHEAD 8
-#endif
-#ifndef NDT_PF_WAVE_BITS
-#define NDT_PF_WAVE_BITS 3
-#endif
-constexpr int kPfWaveBits = NDT_PF_WAVE_BITS, kPfWaves = 1 << kPfWaveBits, kPfQueue = 128, kPfMaxPoints = 1 << 18;   // bitmap: 32 KiB of LDS
+// The step-by-step replay: scans of more than kPfSortMax points (prefilter_sorted_kernel takes the others).  Eight waves per
+// scan, eight steps of the read pass in flight (LOG: one / four / eight / sixteen waves 0.66 / 0.31 / 0.29 / 0.32 ms; eight
+// steps ahead instead of one 0.29 -> 0.27 ms).
+constexpr int kPfWaveBits = 3, kPfAhead = 8, kPfWaves = 1 << kPfWaveBits, kPfQueue = 128, kPfMaxPoints = 1 << 18;   // bitmap: 32 KiB of LDS
 __global__ void __launch_bounds__(64 * kPfWaves)
 prefilter_mw_kernel(const float *__restrict__ xy, size_t stride, const unsigned long long *__restrict__ offsets, int B,
                     float leaf, float2 *__restrict__ sparse /* at the raw offsets */,
@@ -80,7 +74,6 @@ prefilter_mw_kernel(const float *__restrict__ xy, size_t stride, const unsigned 
       int qn = 0;
       // the read-hash-queue pass over the whole scan: kPfAhead steps of 64 points are in flight (one step ahead left
       // every step waiting for its load: 0.6 us a step, most of the kernel)
-      constexpr int kPfAhead = NDT_PF_AHEAD;
       float2 pnext[kPfAhead];
 #pragma unroll
       for (int u = 0; u < kPfAhead; ++u) {
@@ -128,9 +121,7 @@ prefilter_mw_kernel(const float *__restrict__ xy, size_t stride, const unsigned 
       const int per = (nwords + 64 * kPfWaves - 1) / (64 * kPfWaves);
       const int w0 = min((int)threadIdx.x * per, nwords), w1 = min(w0 + per, nwords);
       for (int k = w0; k < w1; ++k) mine_cnt += __builtin_popcount(fbits[k]);
-      int incl = mine_cnt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+      const int incl = wave_incl_scan(mine_cnt);
       if (lane == 63) wsum[w] = incl;
       __syncthreads();
       int off = incl - mine_cnt;
@@ -232,7 +223,7 @@ prefilter_sorted_kernel(const float *__restrict__ xy, size_t stride, const unsig
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const unsigned long long o0 = offsets[b];
     const int n = (int)(offsets[b + 1] - o0);
-    if (n > kPfSortMax || !NDT_PF_SORTED) continue;            // prefilter_mw_kernel's (uniform over the workgroup)
+    if (n > kPfSortMax) continue;                              // prefilter_mw_kernel's (uniform over the workgroup)
     __syncthreads();
     for (int i = threadIdx.x; i < kPfSortWaves * kPfSlots; i += kPfSortThreads) (&same[0][0])[i] = 0ull;
     auto slot_of = [&](float2 p) {
@@ -312,9 +303,7 @@ prefilter_sorted_kernel(const float *__restrict__ xy, size_t stride, const unsig
         int run = 0;
 #pragma unroll
         for (int k = 0; k < kPfSortWaves; ++k) { const int c = wcount[k][h]; wcount[k][h] = (unsigned short)run; run += c; }
-        int incl = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+        const int incl = wave_incl_scan(run);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         int sb = incl - run;
@@ -362,9 +351,7 @@ prefilter_sorted_kernel(const float *__restrict__ xy, size_t stride, const unsig
       {
         const int twords = (m + 31) / 32;                      // <= 256
         const int mine = (int)threadIdx.x < twords ? __builtin_popcount(fbits[threadIdx.x]) : 0;
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+        const int incl = wave_incl_scan(mine);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         int r = nout + incl - mine;
@@ -408,28 +395,15 @@ template <bool kTarget>
 __global__ void __launch_bounds__(1024)
 prefilter_offsets_kernel(const unsigned *__restrict__ counts, int B, unsigned long long *__restrict__ out_offsets,
                          const PfPrev *__restrict__ prev, const int *__restrict__ status) {
-  __shared__ unsigned long long sh[1024];
-  __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < B; base += 1024) {
-    const int i = base + threadIdx.x;
-    unsigned long long v = i < B ? counts[i] : 0ull;
-    if (kTarget) v = (i < B && status[i] == 0) ? v + prev[i].n : 0ull;
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const unsigned long long t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < B) out_offsets[i] = carry + sh[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out_offsets[B] = carry;
+  __shared__ unsigned long long sh[1024 / 64];
+  const unsigned long long total = block_excl_offsets<1024>(
+      B, sh,
+      [&](int i) -> unsigned long long {
+        if (!kTarget) return counts[i];
+        return status[i] == 0 ? counts[i] + prev[i].n : 0ull;
+      },
+      [&](int i, unsigned long long off, unsigned long long) { out_offsets[i] = off; });
+  if (threadIdx.x == 0) out_offsets[B] = total;
 }
 
 // filtered points from their raw offsets to the packed output.  kTarget: behind prev[b], which is copied in front of them
@@ -652,35 +626,17 @@ remove_neighbors_flag_kernel(const float *__restrict__ base, size_t bstride, int
     }
   }
   if (i < nb) keep[i] = flag ? 1 : 0;
-  const unsigned long long b = __ballot(flag);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __builtin_popcountll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) { int s = 0; for (int w = 0; w < kRnBlock / 64; ++w) s += wsum[w]; block_count[blockIdx.x] = s; }
+  int kept;
+  (void)block_rank<kRnBlock>(flag, wsum, &kept);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = kept;
 }
 // exclusive scan of the block counts (one workgroup), total to *n_out
 __global__ void __launch_bounds__(1024)
 remove_neighbors_scan_kernel(int *__restrict__ block_count, int nblocks, unsigned long long *__restrict__ n_out) {
-  __shared__ int sh[1024];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblocks ? block_count[i] : 0;
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const int t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nblocks) block_count[i] = carry + sh[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *n_out = (unsigned long long)carry;
+  __shared__ unsigned sh[1024 / 64];
+  const unsigned total = block_excl_offsets<1024>(
+      nblocks, sh, [&](int i) { return (unsigned)block_count[i]; }, [&](int i, unsigned off, unsigned) { block_count[i] = (int)off; });
+  if (threadIdx.x == 0) *n_out = (unsigned long long)total;
 }
 __global__ void __launch_bounds__(kRnBlock)
 remove_neighbors_pack_kernel(const float *__restrict__ base, size_t bstride, int nb, const unsigned char *__restrict__ keep,
@@ -688,11 +644,7 @@ remove_neighbors_pack_kernel(const float *__restrict__ base, size_t bstride, int
   __shared__ int wsum[kRnBlock / 64];
   const int i = blockIdx.x * kRnBlock + threadIdx.x;
   const bool flag = i < nb && keep[i];
-  const unsigned long long b = __ballot(flag);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wsum[wv] = __builtin_popcountll(b);
-  __syncthreads();
-  int off = block_off[blockIdx.x];
-  for (int w = 0; w < wv; ++w) off += wsum[w];
-  if (flag) out[off + __builtin_popcountll(b & ((1ull << lane) - 1ull))] = load_pt(base, bstride, (size_t)i);
+  int kept;
+  const int rank = block_rank<kRnBlock>(flag, wsum, &kept);
+  if (flag) out[block_off[blockIdx.x] + rank] = load_pt(base, bstride, (size_t)i);
 }

@@ -174,9 +174,7 @@ make_map_diff_kernel(const MmJob *__restrict__ jobs, double res_arg) {
                            (double)p[k].y < F.miny || (double)p[k].y >= F.maxy);
         myq = viol ? q : myq;
       }
-      int wq = myq;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) wq = min(wq, __shfl_xor(wq, o));
+      const int wq = wave_min_all(myq);
       if (lane == 0 && wq != 0x7fffffff) atomicMin(&F.first, wq);
       __syncthreads();
       const int j = F.first;
@@ -377,39 +375,37 @@ make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ 
       keep = !near;
     }
   }
-  const unsigned long long b = __ballot(keep);
+  const unsigned long long b = __ballot(keep);      // (the ballot itself is stored: block_rank would take it a second time)
   if ((tid & 63) == 0) { keepbits[(size_t)blockIdx.x * (kMmUnit / 64) + (tid >> 6)] = b; wsum[tid >> 6] = __builtin_popcountll(b); }
   __syncthreads();
   if (tid == 0) { int c = 0; for (int w = 0; w < kMmUnit / 64; ++w) c += wsum[w]; unit_cnt[blockIdx.x] = (unsigned)c; }
+}
+
+// Exclusive scan of the counts of units [u0, u1) by one workgroup: unit_off relative to u0; returns the total; *bad (LDS,
+// zero on entry) is set when a unit carries the 0xffffffff of a failed triple -- valid after the call in every thread.
+__device__ __forceinline__ unsigned long long mm_unit_offsets(const unsigned *__restrict__ unit_cnt, unsigned u0, unsigned u1,
+                                                              unsigned long long *__restrict__ unit_off,
+                                                              unsigned long long *sh, int *bad) {
+  return block_excl_offsets<1024>(
+      u1 > u0 ? u1 - u0 : 0u, sh,
+      [&](unsigned k) -> unsigned long long {
+        const unsigned c = unit_cnt[u0 + k];
+        if (c == 0xffffffffu) { *bad = 1; return 0ull; }
+        return c;
+      },
+      [&](unsigned k, unsigned long long off, unsigned long long) { unit_off[u0 + k] = off; });
 }
 
 // exclusive scan of the unit counts (one workgroup); total to *n_out, ~0 when a triple failed
 __global__ void __launch_bounds__(1024)
 make_map_offsets_kernel(const unsigned *__restrict__ unit_cnt, int nu, unsigned long long *__restrict__ unit_off,
                         unsigned long long *__restrict__ n_out) {
-  __shared__ unsigned long long sh[1024];
-  __shared__ unsigned long long carry;
+  __shared__ unsigned long long sh[1024 / 64];
   __shared__ int bad;
-  if (threadIdx.x == 0) { carry = 0ull; bad = 0; }
+  if (threadIdx.x == 0) bad = 0;
   __syncthreads();
-  for (int base = 0; base < nu; base += 1024) {
-    const int i = base + threadIdx.x;
-    unsigned c = i < nu ? unit_cnt[i] : 0u;
-    if (c == 0xffffffffu) { bad = 1; c = 0u; }
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const unsigned long long t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nu) unit_off[i] = carry + sh[threadIdx.x] - c;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *n_out = bad ? kMmEmpty : carry;
+  const unsigned long long total = mm_unit_offsets(unit_cnt, 0u, nu > 0 ? (unsigned)nu : 0u, unit_off, sh, &bad);
+  if (threadIdx.x == 0) *n_out = bad ? kMmEmpty : total;
 }
 
 // Batched calls, first level of the offsets: one workgroup per submap scans the counts of that submap's units
@@ -419,31 +415,14 @@ __global__ void __launch_bounds__(1024)
 make_map_sub_offsets_kernel(const unsigned *__restrict__ unit_cnt, const MmSub *__restrict__ subs,
                             unsigned long long *__restrict__ unit_off, unsigned long long *__restrict__ cloud_off,
                             int *__restrict__ status) {
-  __shared__ unsigned long long sh[1024];
-  __shared__ unsigned long long carry;
+  __shared__ unsigned long long sh[1024 / 64];
   __shared__ int bad;
   const MmSub S = subs[blockIdx.x];
-  if (threadIdx.x == 0) { carry = 0ull; bad = 0; }
+  if (threadIdx.x == 0) bad = 0;
   __syncthreads();
-  for (unsigned base = S.u0; base < S.u1; base += 1024u) {
-    const unsigned i = base + threadIdx.x;
-    unsigned c = i < S.u1 ? unit_cnt[i] : 0u;
-    if (c == 0xffffffffu) { bad = 1; c = 0u; }
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const unsigned long long t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < S.u1) unit_off[i] = carry + sh[threadIdx.x] - c;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
+  const unsigned long long total = mm_unit_offsets(unit_cnt, S.u0, S.u1, unit_off, sh, &bad);
   if (threadIdx.x == 0) {
-    cloud_off[blockIdx.x + 1] = bad ? 0ull : carry;
+    cloud_off[blockIdx.x + 1] = bad ? 0ull : total;
     status[blockIdx.x] = bad ? (int)NDT_E_ARG : (int)NDT_OK;
     if (blockIdx.x == 0) cloud_off[0] = 0ull;
   }
@@ -453,25 +432,10 @@ make_map_sub_offsets_kernel(const unsigned *__restrict__ unit_cnt, const MmSub *
 // a round reads its 1024 entries before it writes them, and the next round's entries lie behind those)
 __global__ void __launch_bounds__(1024)
 make_map_sub_scan_kernel(unsigned long long *__restrict__ cloud_off, int n_subs) {
-  __shared__ unsigned long long sh[1024];
-  __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0ull;
-  __syncthreads();
-  for (int base = 0; base < n_subs; base += 1024) {
-    const int i = base + threadIdx.x;
-    sh[threadIdx.x] = i < n_subs ? cloud_off[i + 1] : 0ull;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const unsigned long long t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n_subs) cloud_off[i + 1] = carry + sh[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
+  __shared__ unsigned long long sh[1024 / 64];
+  (void)block_excl_offsets<1024>(
+      n_subs, sh, [&](int i) { return cloud_off[i + 1]; },
+      [&](int i, unsigned long long front, unsigned long long v) { cloud_off[i + 1] = front + v; });
 }
 
 // kBatch: a unit's place is its submap's start (cloud_off) + its offset in the submap; a unit of a failed

@@ -93,11 +93,7 @@ map_minmax_kernel(const float *__restrict__ xy, size_t stride, size_t n, unsigne
       mny = fminf(mny, p[u].y); mxy = fmaxf(mxy, p[u].y);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mnx = fminf(mnx, __shfl_down(mnx, o)); mny = fminf(mny, __shfl_down(mny, o));
-    mxx = fmaxf(mxx, __shfl_down(mxx, o)); mxy = fmaxf(mxy, __shfl_down(mxy, o));
-  }
+  mnx = wave_min(mnx); mny = wave_min(mny); mxx = wave_max(mxx); mxy = wave_max(mxy);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sh[w][0] = mnx; sh[w][1] = mny; sh[w][2] = mxx; sh[w][3] = mxy; }
   __syncthreads();
@@ -122,7 +118,7 @@ map_minmax_kernel(const float *__restrict__ xy, size_t stride, size_t n, unsigne
 
 __device__ __forceinline__ int voxel_of(const GridDims &G, float2 p) {
   if (!finite2(p.x, p.y)) return -1;
-  const float fx = fminf(fmaxf(floorf(p.x * G.inv_leaf), -1.0e9f), 1.0e9f), fy = fminf(fmaxf(floorf(p.y * G.inv_leaf), -1.0e9f), 1.0e9f);
+  const float fx = voxel_coord(p.x, G.inv_leaf), fy = voxel_coord(p.y, G.inv_leaf);
   const int ix = (int)fx - G.min_bx, iy = (int)fy - G.min_by;
   // never true for the grid of this cloud's own bounding box; a build queued ahead of the bounding
   // box read-back with the previous grid (ndt_map_build_dev) must stay inside its buffers

@@ -246,8 +246,7 @@ __device__ __forceinline__ void region_from_bbox(const MapView &M, const Tf32 &T
           L.clipped = 1;
           const long long w2 = w > 128 ? 128 : w;
           long long h2 = kRegionCells / w2; if (h2 > h) h2 = h;
-          const float sx = fminf(fmaxf(floorf(T0.tx * M.inv_leaf), -1.0e9f), 1.0e9f);    // (NaN -> -1e9, as everywhere)
-          const float sy = fminf(fmaxf(floorf(T0.ty * M.inv_leaf), -1.0e9f), 1.0e9f);
+          const float sx = voxel_coord(T0.tx, M.inv_leaf), sy = voxel_coord(T0.ty, M.inv_leaf);    // (NaN -> -1e9, as everywhere)
           long long cx0 = ((long long)(int)sx - M.min_bx) - w2 / 2, cy0 = ((long long)(int)sy - M.min_by) - h2 / 2;
           cx0 = cx0 < x0 ? x0 : (cx0 > x1 - w2 + 1 ? x1 - w2 + 1 : cx0);
           cy0 = cy0 < y0 ? y0 : (cy0 > y1 - h2 + 1 ? y1 - h2 + 1 : cy0);
@@ -277,8 +276,7 @@ __device__ __noinline__ void compute_region(const MapView &M, const Tf32 &T0, co
     float xt, yt;
     tf_apply_t<SSE>(T0, pt.x, pt.y, xt, yt);
     if (!finite2(xt, yt)) continue;
-    const float fx = fminf(fmaxf(floorf(xt * M.inv_leaf), -1.0e9f), 1.0e9f);
-    const float fy = fminf(fmaxf(floorf(yt * M.inv_leaf), -1.0e9f), 1.0e9f);
+    const float fx = voxel_coord(xt, M.inv_leaf), fy = voxel_coord(yt, M.inv_leaf);
     const int ix = (int)fx - M.min_bx, iy = (int)fy - M.min_by;
     mnx = ix < mnx ? ix : mnx; mxx = ix > mxx ? ix : mxx;
     mny = iy < mny ? iy : mny; mxy = iy > mxy ? iy : mxy;
@@ -523,8 +521,7 @@ __device__ __noinline__ bool sort_points(const MapView &M, const Tf32 &T0, const
     float xt, yt;
     tf_apply_t<SSE>(T0, pt.x, pt.y, xt, yt);
     if (!finite2(xt, yt)) return ncell;
-    const float fx = fminf(fmaxf(floorf(xt * M.inv_leaf), -1.0e9f), 1.0e9f);
-    const float fy = fminf(fmaxf(floorf(yt * M.inv_leaf), -1.0e9f), 1.0e9f);
+    const float fx = voxel_coord(xt, M.inv_leaf), fy = voxel_coord(yt, M.inv_leaf);
     const int lx = (int)fx - M.min_bx - r.x0, ly = (int)fy - M.min_by - r.y0;
     if (lx < 0 || lx >= r.rw || ly < 0 || ly >= r.rh) return ncell;
     return ly * r.rw + lx;
@@ -673,8 +670,7 @@ __device__ __noinline__ void order_scan_regs(const MapView &M, const OptParams &
   auto vox = [&](float2 p, int &ix, int &iy) {
     float xt, yt;
     tf_apply_t<SSE>(T0, p.x, p.y, xt, yt);
-    const float fx = fminf(fmaxf(floorf(xt * M.inv_leaf), -1.0e9f), 1.0e9f);
-    const float fy = fminf(fmaxf(floorf(yt * M.inv_leaf), -1.0e9f), 1.0e9f);
+    const float fx = voxel_coord(xt, M.inv_leaf), fy = voxel_coord(yt, M.inv_leaf);
     ix = (int)fx - M.min_bx; iy = (int)fy - M.min_by;
     return finite2(xt, yt);
   };

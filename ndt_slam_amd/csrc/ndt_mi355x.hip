@@ -1060,7 +1060,7 @@ static int grid_of_box(ndt_ctx *ctx, const unsigned *hb, const ndt_params *prm, 
   const float mnx = ord2f(hb[0]), mny = ord2f(hb[1]), mxx = ord2f(hb[2]), mxy = ord2f(hb[3]);
   GridDims G;
   G.inv_leaf = inv_leaf;
-  auto vox = [&](float x) { return (int)fminf(fmaxf(floorf(x * inv_leaf), -1.0e9f), 1.0e9f); };   // (as voxel_of: a float beyond the int range)
+  auto vox = [&](float x) { return (int)voxel_coord(x, inv_leaf); };   // (voxel_of's own rule: the device's function)
   G.min_bx = vox(mnx); G.min_by = vox(mny);
   long long dx = (long long)vox(mxx) - G.min_bx + 1;
   long long dy = (long long)vox(mxy) - G.min_by + 1;
@@ -2058,7 +2058,7 @@ int pf_run(ndt_ctx *ctx, const float *raw_xy, size_t stride, const uint64_t *raw
   prefilter_sorted_kernel<<<grid, kPfSortThreads, 0, st>>>(raw_xy, stride, (const unsigned long long *)raw_offsets, B, leaf,
                                                            tmp, counts);
   prefilter_mw_kernel<<<grid, 64 * kPfWaves, 0, st>>>(raw_xy, stride, (const unsigned long long *)raw_offsets, B, leaf,
-                                                      sparse, tmp, counts, NDT_PF_SORTED ? kPfSortMax : -1);
+                                                      sparse, tmp, counts, kPfSortMax);
   prefilter_offsets_kernel<kTarget><<<1, 1024, 0, st>>>(counts, B, (unsigned long long *)out_offsets, prev, status);
   const int gx = (int)std::min<size_t>(64, ((total_raw_points + total_prev_points) / (size_t)B + 255) / 256 + 1);
   prefilter_pack_kernel<kTarget><<<dim3((unsigned)gx, (unsigned)std::min(B, 65535)), 256, 0, st>>>(

@@ -41,37 +41,16 @@ __device__ __forceinline__ unsigned long long occ_scan_len(const OccRow *__restr
 __global__ void __launch_bounds__(256)
 occ_jobs_kernel(const OccRow *__restrict__ tab, const unsigned long long *__restrict__ offsets, int B, OccJob *__restrict__ jobs,
                 unsigned job_cap, unsigned *__restrict__ n_jobs, unsigned long long *__restrict__ stats) {
-  __shared__ unsigned long long sh[256];
-  __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0ull;
+  __shared__ unsigned long long sh[256 / 64];
   if (stats && threadIdx.x < 4) stats[threadIdx.x] = 0ull;
-  __syncthreads();
-  for (int base = 0; base < B; base += 256) {
-    const int b = base + (int)threadIdx.x;
-    const unsigned long long n = b < B ? occ_scan_len(tab, offsets, b) : 0ull;
-    const unsigned long long runs = (n + (unsigned long long)kOccRun - 1ull) / (unsigned long long)kOccRun;
-    sh[threadIdx.x] = runs;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const unsigned long long t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    const unsigned long long j0 = carry + sh[threadIdx.x] - runs;
-    for (unsigned long long r = 0; r < runs && j0 + r < (unsigned long long)job_cap; ++r)
-      jobs[j0 + r] = OccJob{b, 0, r * (unsigned long long)kOccRun};
-    __syncthreads();
-    if (threadIdx.x == 255) carry += sh[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *n_jobs = (unsigned)(carry < (unsigned long long)job_cap ? carry : (unsigned long long)job_cap);
-}
-
-__device__ __forceinline__ unsigned long long occ_wave_sum(unsigned long long x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-  return x;
+  const unsigned long long total = block_excl_offsets<256>(
+      B, sh,
+      [&](int b) { return (occ_scan_len(tab, offsets, b) + (unsigned long long)kOccRun - 1ull) / (unsigned long long)kOccRun; },
+      [&](int b, unsigned long long j0, unsigned long long runs) {
+        for (unsigned long long r = 0; r < runs && j0 + r < (unsigned long long)job_cap; ++r)
+          jobs[j0 + r] = OccJob{b, 0, r * (unsigned long long)kOccRun};
+      });
+  if (threadIdx.x == 0) *n_jobs = (unsigned)(total < (unsigned long long)job_cap ? total : (unsigned long long)job_cap);
 }
 
 // no-return relaxed agent-scope integer add; the pointer came out of the call's table and is known to address device
@@ -190,7 +169,7 @@ occ_integrate_kernel(const OccRow *__restrict__ tab, int n_occ, const int *__res
   }
   // ---- the call's stats: per-wave sums, then one atomic per counter and workgroup ----
   if (!stats) return;
-  const unsigned long long v[4] = {occ_wave_sum(c_beams), occ_wave_sum(c_hit), occ_wave_sum(c_pass), occ_wave_sum(c_skip)};
+  const unsigned long long v[4] = {wave_sum(c_beams), wave_sum(c_hit), wave_sum(c_pass), wave_sum(c_skip)};
   if (lane == 0) { s_stat[wave][0] = v[0]; s_stat[wave][1] = v[1]; s_stat[wave][2] = v[2]; s_stat[wave][3] = v[3]; }
   __syncthreads();
   if (tid < 4) {

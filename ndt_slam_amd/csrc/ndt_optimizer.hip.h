@@ -299,9 +299,6 @@ __device__ __forceinline__ void advance(AlignState &S, const OptParams &P, const
     const double a_prev = S.a_t;
     const int ph_prev = S.phase;
     if (advance_step(S, P)) { begin_outer(S, P); return; }
-#ifdef NDT_NO_REPEAT_SKIP
-    return;
-#endif
     // a new trial inside the same line search (same p, same direction) with the step length of the pass just consumed?
     if (S.phase != PH_LS_INNER || ph_prev == PH_INIT || !(S.a_t == a_prev)) return;
     repeat_totals(S, trace, trace_cap, trace_rows);

@@ -32,48 +32,28 @@ struct Window {
 __constant__ double c_exp2_tab[64];
 __device__ __forceinline__ double exp_neg(double x, const double *__restrict__ tab) {
   x = fmax(x, -800.0);
-#ifdef NDT_EXP_RINT
-  const double t = rint(x * 92.332482616893657);            // 64 / ln 2
-  const int n = (int)t;
-#else
   // t = the integer nearest to x * 64 / ln 2, by adding and taking away 1.5 * 2^52 (|x * 64 / ln 2| < 2^17): the sum's low word IS
   // that integer (two's complement), so neither a rounding nor a conversion instruction is needed (round 5: one instruction
   // fewer per pair; the product is rounded once, inside the fma, where rint (x * c) rounded twice -- the two differ only when
   // x * c lies within an ulp of a half-integer, and then by one table step whose result agrees to the last bit or two)
   const double big = 6755399441055744.0;
-  const double sum = __builtin_fma(x, 92.332482616893657, big);
+  const double sum = __builtin_fma(x, 92.332482616893657, big);   // 64 / ln 2
   const double t = sum - big;
   const int n = (int)(unsigned)__double_as_longlong(sum);
-#endif
   const double sc = tab[n & 63];
-#ifndef NDT_NO_EXP_SCHED
   __builtin_amdgcn_sched_barrier(0);                        // issue the table read BEFORE the polynomial (the scheduler put it behind: a full LDS latency exposed per pair)
-#endif
   double r = __builtin_fma(-t, 0x1.62e42fefa0000p-7, x);    // ln2/64, high part (exact product)
   r = __builtin_fma(-t, 0x1.cf79abc9e3b3ap-46, r);          // low part
-#ifdef NDT_EXP_PLAIN
-  double p = __builtin_fma(r, 1.0 / 120.0, 1.0 / 24.0);
-  p = __builtin_fma(r, p, 1.0 / 6.0);
-#else
-  // (the same two fused multiply-adds, spelled as three-address v_fma_f64: left to itself the compiler keeps 1/24 and 1/6 in
+  // (p = fma(r, 1/120, 1/24), then p = fma(r, p, 1/6), spelled as three-address v_fma_f64: left to itself the compiler keeps 1/24 and 1/6 in
   //  registers that share their low word and turns each step into v_mov + v_fmac -- three extra instructions per pair)
   double p, c4 = 1.0 / 24.0, c3 = 1.0 / 6.0, c5 = 1.0 / 120.0;
   //  (1/120 and 1/6 as scalar operands -- one per instruction is allowed -- 1/24 in a vector register: 1/24 and 1/6 in vector
   //   registers share their low word in the compiler's hands, which costs a v_mov per pair to put 1/6 together)
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(r), "s"(c5), "v"(c4));
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(r), "v"(p), "s"(c3));
-#endif
   p = __builtin_fma(r, p, 0.5);
   p = __builtin_fma(p, r * r, r);                           // exp(r) - 1
   return ldexp(__builtin_fma(sc, p, sc), n >> 6);
-}
-
-template <bool SSE>
-__device__ __forceinline__ void tf_apply_t(const Tf32 &t, float x, float y, float &ox, float &oy) {
-  const float ms = -t.s;
-  const float a = t.c * x, b = ms * y, c = t.s * x, d = t.c * y;
-  if (!SSE) { const float r = a + b; ox = r + t.tx; const float q = c + d; oy = q + t.ty; }
-  else      { const float r = b + t.tx; ox = a + r; const float q = d + t.ty; oy = c + q; }
 }
 
 // radius test of flann::L2_Simple<float> on one centroid
@@ -159,6 +139,34 @@ __device__ __forceinline__ void finish_point(float x, float y, double cj, double
   A.htt += tt;
 }
 
+// The pair walk of one transformed point on the global grid: (ix, iy) its voxel in unpadded grid coordinates; the 3 x 3
+// neighbourhood, the radius test on the float32 centroids, accumulate_pair for each hit in ascending neighbour order into S.
+// false: no pair (outside the grid, not finite, nothing in the radius).  eval_point's slow path and score_point.
+template <bool INCL, bool CHK>
+__device__ __forceinline__ bool global_pairs(const MapView &M, const double *__restrict__ etab, float xt, float yt, int ix, int iy,
+                                             PointAcc &S, unsigned &pairs) {
+  const bool ingrid = finite2(xt, yt) & (ix >= -1) & (ix <= M.div_x) & (iy >= -1) & (iy <= M.div_y);
+  if (!ingrid) return false;
+  const size_t base = (size_t)(iy + 1) * M.gw + (ix + 1);     // padded coords of (ix-1, iy-1)
+  const float2 *grow = M.cent + base;
+  unsigned mask = 0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) mask |= in_radius<INCL>(M.r2, xt, yt, gld_f2(grow + (r * M.gw + q))) << (r * 3 + q);
+  if (!mask) return false;
+  pairs += __builtin_popcount(mask);
+  const double XT = (double)xt, YT = (double)yt;
+  const double nd2 = -M.d2, nd2h = nd2 * 0.5;
+#pragma nounroll
+  do {
+    const int k = __builtin_ctz(mask);
+    mask &= mask - 1;
+    accumulate_pair<CHK>(M.e_hi, nd2, nd2h, etab, XT, YT, load_rec_global(M, base, k), S);
+  } while (mask);
+  return true;
+}
+
 // Everything one source point contributes to a derivative pass.
 // Fast path (window holds every occupied voxel, point's 3x3 neighbourhood inside it): slot
 // numbers, centroids and records all come from LDS.  Otherwise the same arithmetic reads the
@@ -169,8 +177,7 @@ __device__ __forceinline__ void eval_point(const MapView &M, const Window &W,
                                            float y, double cj, double sj, double ch, double sh, Acc &A) {
   float xt, yt;
   tf_apply_t<SSE>(T, x, y, xt, yt);
-  const float fx = fminf(fmaxf(floorf(xt * M.inv_leaf), -1.0e9f), 1.0e9f);     // (NaN -> -1e9: outside every window and grid)
-  const float fy = fminf(fmaxf(floorf(yt * M.inv_leaf), -1.0e9f), 1.0e9f);
+  const float fx = voxel_coord(xt, M.inv_leaf), fy = voxel_coord(yt, M.inv_leaf);     // (NaN -> -1e9: outside every window and grid)
   const Region &R = W.R;
   // window coordinates.  Window cells outside the map's grid carry the "outside the search set" slot (fill_window) and a
   // non-finite point lands at -1e9, outside every window: one unsigned comparison per axis decides the fast path.
@@ -190,15 +197,11 @@ __device__ __forceinline__ void eval_point(const MapView &M, const Window &W,
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int q = 0; q < 3; ++q) sl[r * 3 + q] = srow[r * R.rw + q];
-#ifndef NDT_NO_PROBE_SCHED
   __builtin_amdgcn_sched_barrier(0);
-#endif
   float2 cc[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) cc[k] = W.ent[sl[k]].cent;
-#ifndef NDT_NO_PROBE_SCHED
   __builtin_amdgcn_sched_barrier(0);
-#endif
   // (-inf centroids -- occupied voxels without an LDS record -- exist only in a window that spilled: uniform)
   if (R.nspill > 0) {
 #pragma unroll
@@ -226,37 +229,12 @@ __device__ __forceinline__ void eval_point(const MapView &M, const Window &W,
     return;
   }
   // slow path: global centroid grid and record array
-  const int ix = lx + R.x0, iy = ly + R.y0;
-  const bool ingrid = finite2(xt, yt) & (ix >= -1) & (ix <= M.div_x) & (iy >= -1) & (iy <= M.div_y);
-  if (!ingrid) return;
-  const size_t base = (size_t)(iy + 1) * M.gw + (ix + 1);     // padded coords of (ix-1, iy-1)
-  const float2 *grow = M.cent + base;
-  mask = 0;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) mask |= in_radius<INCL>(M.r2, xt, yt, gld_f2(grow + (r * M.gw + q))) << (r * 3 + q);
-  if (!mask) return;
-  A.pairs += __builtin_popcount(mask);
-  const double XT = (double)xt, YT = (double)yt;
   PointAcc S = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma nounroll
-  do {
-    const int k = __builtin_ctz(mask);
-    mask &= mask - 1;
-    accumulate_pair<CHK>(M.e_hi, nd2, nd2h, etab, XT, YT, load_rec_global(M, base, k), S);
-  } while (mask);
-  finish_point(x, y, cj, sj, ch, sh, S, A);
+  if (global_pairs<INCL, CHK>(M, etab, xt, yt, lx + R.x0, ly + R.y0, S, A.pairs)) finish_point(x, y, cj, sj, ch, sh, S, A);
 }
 
-// Fixed-order sums over the workgroup: lanes by shuffle, waves through LDS in wave order.
+// Fixed-order sums over the workgroup: lanes by shuffle (wave_sum, ndt_common.hip.h), waves through LDS in wave order.
 // Totals are left in sred[nw*NV .. nw*NV+NV) (valid for every thread after the call).
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-  return x;
-}
-
 template <int NV>
 __device__ __forceinline__ void block_combine(double *sred, double *out) {
   const int nw = blockDim.x >> 6;

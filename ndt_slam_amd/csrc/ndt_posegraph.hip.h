@@ -57,8 +57,7 @@ __device__ __forceinline__ double pg_wrap_deg(double v) {
 
 // Sum over the workgroup in a fixed shape: the wave tree, then the four waves in order.  Every thread gets the same bits.
 __device__ __forceinline__ double pg_block_sum(double v, double *s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
   __syncthreads();
   const double t = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
@@ -66,8 +65,7 @@ __device__ __forceinline__ double pg_block_sum(double v, double *s_w) {
   return t;
 }
 __device__ __forceinline__ double pg_block_max(double v, double *s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o));
+  v = wave_max(v);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
   __syncthreads();
   const double t = fmax(fmax(s_w[0], s_w[1]), fmax(s_w[2], s_w[3]));

@@ -127,32 +127,6 @@ resample_walk_kernel(const double *__restrict__ xy, size_t stride, const unsigne
   }
 }
 
-// inclusive sum over a workgroup of kRsScanThreads threads; *total = the sum of all threads' values
-__device__ __forceinline__ unsigned long long rs_block_scan(unsigned long long v, unsigned long long *sh, unsigned long long *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) sh[wave] = v;
-  __syncthreads();
-  if (wave == 0) {
-    unsigned long long w = lane < kRsScanThreads / 64 ? sh[lane] : 0ull;
-#pragma unroll
-    for (int o = 1; o < kRsScanThreads / 64; o <<= 1) {
-      const unsigned long long u = __shfl_up(w, o, 64);
-      if (lane >= o) w += u;
-    }
-    if (lane < kRsScanThreads / 64) sh[lane] = w;
-  }
-  __syncthreads();
-  const unsigned long long r = v + (wave ? sh[wave - 1] : 0ull);
-  *total = sh[kRsScanThreads / 64 - 1];
-  __syncthreads();                                      // sh is reused by the next call
-  return r;
-}
-
 // Per scan, one workgroup: where each piece's points go inside the scan's output range (pos, at the piece's
 // start) and the scan's output count (tot; 0 for a failed scan).
 __global__ void __launch_bounds__(kRsScanThreads)
@@ -164,13 +138,14 @@ resample_segscan_kernel(const unsigned long long *__restrict__ offsets, int B, u
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     if (bad[b]) { if (threadIdx.x == 0) tot[b] = 0; continue; }
     const unsigned long long r0 = offsets[b], r1 = offsets[b + 1] < total ? offsets[b + 1] : total;
+    // (the rounds of block_excl_offsets, over raw indices from r0 on: its items count from 0, which costs registers here)
     unsigned long long carry = 0;
     for (unsigned long long base = r0; base < r1; base += kRsScanThreads) {
       const unsigned long long g = base + threadIdx.x;
       const bool start = g < r1 && L[g] >= resync;
       const unsigned long long v = start ? cnt[g] : 0ull;
       unsigned long long sum;
-      const unsigned long long incl = rs_block_scan(v, sh, &sum);
+      const unsigned long long incl = block_incl_scan<kRsScanThreads>(v, sh, &sum);
       if (start) pos[g] = carry + incl - v;
       carry += sum;
     }
@@ -183,19 +158,13 @@ __global__ void __launch_bounds__(kRsScanThreads)
 resample_offsets_kernel(const unsigned long long *__restrict__ tot, const int *__restrict__ bad, int B,
                         unsigned long long *__restrict__ out_offsets, int *__restrict__ status) {
   __shared__ unsigned long long sh[kRsScanThreads / 64];
-  unsigned long long carry = 0;
-  for (int base = 0; base < B; base += kRsScanThreads) {
-    const int b = base + threadIdx.x;
-    const unsigned long long v = b < B ? tot[b] : 0ull;
-    unsigned long long sum;
-    const unsigned long long incl = rs_block_scan(v, sh, &sum);
-    if (b < B) {
-      out_offsets[b] = carry + incl - v;
-      if (status) status[b] = bad[b] ? NDT_E_ARG : NDT_OK;
-    }
-    carry += sum;
-  }
-  if (threadIdx.x == 0) out_offsets[B] = carry;
+  const unsigned long long sum = block_excl_offsets<kRsScanThreads>(
+      B, sh, [&](int b) { return tot[b]; },
+      [&](int b, unsigned long long off, unsigned long long) {
+        out_offsets[b] = off;
+        if (status) status[b] = bad[b] ? NDT_E_ARG : NDT_OK;
+      });
+  if (threadIdx.x == 0) out_offsets[B] = sum;
 }
 
 // The pack, one thread per raw point: the scratch slots [d * k_max, (d + 1) * k_max) of the piece that holds the

@@ -34,36 +34,15 @@ constexpr int kScoreTile = 16;                       // consecutive poses a work
 constexpr int kScoreStagePts = 8000;                 // scans up to this many points are staged in LDS (8 B per point: 62.5 KiB,
                                                      // so that a CU's 160 KiB still holds two workgroups and their exp tables)
 
-// One source point at one pose, the score alone: the pairs eval_point forms on its global path -- float32 transform in the
-// map's order, 3 x 3 neighbourhood, radius test on the float32 centroids -- and accumulate_pair's e for each, in ascending
-// neighbour order, added to S.se.  The other five sums of S are never read: the compiler drops them and what feeds only them.
+// One source point at one pose, the score alone: the pairs eval_point forms on its global path (global_pairs) -- float32
+// transform in the map's order, 3 x 3 neighbourhood, radius test on the float32 centroids -- and accumulate_pair's e for each,
+// in ascending neighbour order, added to S.se.  The other five sums of S are never read: the compiler drops them and what feeds only them.
 template <bool SSE, bool INCL, bool CHK>
 __device__ __forceinline__ void score_point(const MapView &M, const double *__restrict__ etab, const Tf32 &T, float x, float y,
                                             PointAcc &S, unsigned &pairs) {
   float xt, yt;
   tf_apply_t<SSE>(T, x, y, xt, yt);
-  const float fx = fminf(fmaxf(floorf(xt * M.inv_leaf), -1.0e9f), 1.0e9f);     // (NaN -> -1e9: outside every grid)
-  const float fy = fminf(fmaxf(floorf(yt * M.inv_leaf), -1.0e9f), 1.0e9f);
-  const int ix = (int)fx - M.min_bx, iy = (int)fy - M.min_by;
-  const bool ingrid = finite2(xt, yt) & (ix >= -1) & (ix <= M.div_x) & (iy >= -1) & (iy <= M.div_y);
-  if (!ingrid) return;
-  const size_t base = (size_t)(iy + 1) * M.gw + (ix + 1);     // padded coords of (ix-1, iy-1)
-  const float2 *grow = M.cent + base;
-  unsigned mask = 0;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) mask |= in_radius<INCL>(M.r2, xt, yt, gld_f2(grow + (r * M.gw + q))) << (r * 3 + q);
-  if (!mask) return;
-  pairs += __builtin_popcount(mask);
-  const double XT = (double)xt, YT = (double)yt;
-  const double nd2 = -M.d2, nd2h = nd2 * 0.5;
-#pragma nounroll
-  do {
-    const int k = __builtin_ctz(mask);
-    mask &= mask - 1;
-    accumulate_pair<CHK>(M.e_hi, nd2, nd2h, etab, XT, YT, load_rec_global(M, base, k), S);
-  } while (mask);
+  global_pairs<INCL, CHK>(M, etab, xt, yt, (int)voxel_coord(xt, M.inv_leaf) - M.min_bx, (int)voxel_coord(yt, M.inv_leaf) - M.min_by, S, pairs);
 }
 
 // Score and pair count of one scan at P poses: poses[3 p .. 3 p + 3), or (poses == nullptr) the poses of lattice L.
@@ -105,8 +84,7 @@ ndt_score_kernel(MapView M, int libm_f32, const float *__restrict__ scan, size_t
         }
       }
       const double tot = wave_sum(S.se);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) np += __shfl_down(np, o);
+      np = wave_sum(np);
       if (lane == 0) {
         score[pi] = -M.d1 * tot;
         if (pairs_out) pairs_out[pi] = np;

@@ -122,57 +122,45 @@ session_plan_kernel(const SsPlan *__restrict__ plan, int S, const float2 *__rest
                     const unsigned long long *__restrict__ tri_off, const int *__restrict__ tri_status,
                     unsigned long long *__restrict__ plen, float2 *__restrict__ arena,
                     unsigned long long *__restrict__ cloud_off, int *__restrict__ status, SsCopy *__restrict__ seg) {
-  __shared__ unsigned long long sh[1024];
-  __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0ull;
-  __syncthreads();
-  for (int base = 0; base < S; base += 1024) {
-    const int i = base + threadIdx.x;
-    SsPlan P;
-    unsigned long long pl = 0ull, pn = 0ull, nn = 0ull, len = 0ull;
-    const float2 *piece = nullptr;
-    int st = NDT_OK;
-    bool live = false;
-    if (i < S) {
-      P = plan[i];
-      live = P.stepped != 0;
-      if (live) {
-        pl = P.reset ? 0ull : plen[i];
-        piece = P.piece; pn = P.piece_n;
-        if (P.tri >= 0) {
-          if (tri_status[P.tri] != NDT_OK) st = NDT_E_ARG;
-          piece = tri_xy + tri_off[P.tri];
-          pn = tri_off[P.tri + 1] - tri_off[P.tri];
+  __shared__ unsigned long long sh[1024 / 64];
+  // what the load of session i finds out, for its store
+  SsPlan P;
+  unsigned long long pl = 0ull, pn = 0ull, nn = 0ull;
+  const float2 *piece = nullptr;
+  int st = NDT_OK;
+  bool live = false;
+  const unsigned long long total = block_excl_offsets<1024>(
+      S, sh,
+      [&](int i) {
+        unsigned long long len = 0ull;
+        P = plan[i];
+        pl = 0ull; pn = 0ull; nn = 0ull; piece = nullptr; st = NDT_OK;
+        live = P.stepped != 0;
+        if (live) {
+          pl = P.reset ? 0ull : plen[i];
+          piece = P.piece; pn = P.piece_n;
+          if (P.tri >= 0) {
+            if (tri_status[P.tri] != NDT_OK) st = NDT_E_ARG;
+            piece = tri_xy + tri_off[P.tri];
+            pn = tri_off[P.tri + 1] - tri_off[P.tri];
+          }
+          nn = P.with_newest ? P.newest_n : 0ull;
+          if (st != NDT_OK) { pn = 0ull; nn = 0ull; len = 0ull; }
+          else len = pl + pn + nn;
         }
-        nn = P.with_newest ? P.newest_n : 0ull;
-        if (st != NDT_OK) { pn = 0ull; nn = 0ull; len = 0ull; }
-        else len = pl + pn + nn;
-      }
-    }
-    sh[threadIdx.x] = len;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const unsigned long long t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < S) {
-      const unsigned long long off = carry + sh[threadIdx.x] - len;
-      cloud_off[i] = off;
-      status[i] = st;
-      const bool ok = live && st == NDT_OK;
-      seg[4 * i + 0] = SsCopy{piece, ok ? P.prefix + pl : nullptr, ok ? pn : 0ull};
-      seg[4 * i + 1] = SsCopy{ok ? P.prefix : nullptr, arena + off, ok ? pl : 0ull};
-      seg[4 * i + 2] = SsCopy{piece, arena + off + pl, ok ? pn : 0ull};
-      seg[4 * i + 3] = SsCopy{ok ? P.newest : nullptr, arena + off + pl + pn, ok ? nn : 0ull};
-      if (live) plen[i] = st == NDT_OK ? pl + pn : pl;
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) cloud_off[S] = carry;
+        return len;
+      },
+      [&](int i, unsigned long long off, unsigned long long) {
+        cloud_off[i] = off;
+        status[i] = st;
+        const bool ok = live && st == NDT_OK;
+        seg[4 * i + 0] = SsCopy{piece, ok ? P.prefix + pl : nullptr, ok ? pn : 0ull};
+        seg[4 * i + 1] = SsCopy{ok ? P.prefix : nullptr, arena + off, ok ? pl : 0ull};
+        seg[4 * i + 2] = SsCopy{piece, arena + off + pl, ok ? pn : 0ull};
+        seg[4 * i + 3] = SsCopy{ok ? P.newest : nullptr, arena + off + pl + pn, ok ? nn : 0ull};
+        if (live) plen[i] = st == NDT_OK ? pl + pn : pl;
+      });
+  if (threadIdx.x == 0) cloud_off[S] = total;
 }
 
 }  // namespace
