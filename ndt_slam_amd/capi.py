@@ -64,8 +64,7 @@ class SessionsStats(C.Structure):
                 ("triples_run", C.c_int), ("sessions_stepped", C.c_int)]
 
 
-SESSION_STEP_DTYPE = np.dtype([("pose", "f8", 3), ("cov", "f8", 9), ("cost", "f8"), ("stepped", "i4"), ("matched", "i4"),
-                               ("successful", "i4"), ("status", "i4"), ("submap", "i4"), ("split", "i4")], align=True)
+SESSION_STEP_DTYPE = np.dtype(SessionStep)           # (numpy reads a Structure's layout: written once)
 
 
 class PoseLattice(C.Structure):
@@ -77,17 +76,13 @@ class PoseLattice(C.Structure):
     def size(self):
         """ndt_lattice_size (host only); raises NdtError for a lattice the library refuses."""
         n = C.c_uint64()
-        rc = lib().ndt_lattice_size(C.byref(self), C.byref(n))
-        if rc:
-            raise NdtError("ndt_lattice_size -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+        _check(lib().ndt_lattice_size(C.byref(self), C.byref(n)), "ndt_lattice_size")
         return n.value
 
     def pose(self, index):
         """ndt_lattice_pose (host only): the definition of the lattice's poses."""
         p = (C.c_double * 3)()
-        rc = lib().ndt_lattice_pose(C.byref(self), int(index), p)
-        if rc:
-            raise NdtError("ndt_lattice_pose -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+        _check(lib().ndt_lattice_pose(C.byref(self), int(index), p), "ndt_lattice_pose")
         return np.array(p[:])
 
     def poses(self, indices=None):
@@ -107,8 +102,7 @@ class FitStats(C.Structure):
                 ("n_points", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-FIT_STATS_DTYPE = np.dtype([("fitness", "f8"), ("fitness_all", "f8"), ("n_in", "u4"), ("n_dist", "u4"), ("n_points", "u4"),
-                            ("reserved", "u4")], align=True)
+FIT_STATS_DTYPE = np.dtype(FitStats)
 DBL_MAX = float(np.finfo(np.float64).max)
 
 
@@ -119,9 +113,7 @@ class OccGeometry(C.Structure):
     def cell(self, x, y):
         """ndt_occ_cell: the (ix, iy) of a point -- the definition the device follows."""
         ix, iy = C.c_int64(), C.c_int64()
-        rc = lib().ndt_occ_cell(C.byref(self), float(x), float(y), C.byref(ix), C.byref(iy))
-        if rc != 0:
-            raise NdtError("ndt_occ_cell failed (%d): %s" % (rc, lib().ndt_last_error(None).decode()))
+        _check(lib().ndt_occ_cell(C.byref(self), float(x), float(y), C.byref(ix), C.byref(iy)), "ndt_occ_cell")
         return ix.value, iy.value
 
 
@@ -130,7 +122,7 @@ class OccStats(C.Structure):
     _fields_ = [("n_beams", C.c_uint64), ("n_hit", C.c_uint64), ("n_pass", C.c_uint64), ("n_skipped", C.c_uint64)]
 
 
-OCC_STATS_DTYPE = np.dtype([("n_beams", "u8"), ("n_hit", "u8"), ("n_pass", "u8"), ("n_skipped", "u8")], align=True)
+OCC_STATS_DTYPE = np.dtype(OccStats)
 
 
 class PgEdge(C.Structure):
@@ -144,6 +136,7 @@ class PgParams(C.Structure):
                 ("max_halvings", C.c_int)]
 
 
+# (hand-written: the C field is `from`, a Python keyword, so the Structure's is from_)
 PG_EDGE_DTYPE = np.dtype([("from", "i4"), ("to", "i4"), ("rel", "f8", 3), ("info", "f8", 6)], align=True)
 PG_RESULT_DTYPE = np.dtype([("cost_initial", "f8"), ("cost_final", "f8"), ("iterations", "i4"), ("cg_iterations", "i4"),
                             ("converged", "i4"), ("status", "i4")], align=True)
@@ -166,29 +159,106 @@ NDT_OK, NDT_E_ARG, NDT_E_HIP, NDT_E_NO_DEVICE, NDT_E_GRID, NDT_E_NOMEM = 0, -1, 
 OPT_MAX_HELPERS, OPT_WORKGROUPS, OPT_INJECT_FAULT, OPT_DEFER_FITNESS, OPT_SCORE_STAGE = 1, 2, 3, 4, 5     # ndt_ctx_set_option
 SCORE_STAGE_POINTS = 8000            # the score sweep stages scans up to this many points in LDS (kScoreStagePts, ndt_score.hip.h)
 
-EXPORTS = [
-    "ndt_default_params", "ndt_params_pcl110", "ndt_params_pcl18", "ndt_params_pcl_new", "ndt_ctx_create", "ndt_ctx_destroy", "ndt_last_error", "ndt_ctx_stream",
-    "ndt_ctx_set_stream", "ndt_ctx_set_option", "ndt_ctx_wait_launch",
-    "ndt_map_build", "ndt_map_build_dev", "ndt_map_rebuild_begin", "ndt_map_rebuild_end", "ndt_map_destroy", "ndt_map_info_get", "ndt_map_export",
-    "ndt_align", "ndt_align_batch", "ndt_align_batch_dev", "ndt_align_batch_prepare_dev", "ndt_prepare_timing", "ndt_align_batch_trace", "ndt_eval_at",
-    "ndt_fitness_at", "ndt_last_timing", "ndt_kernel_timing", "ndt_launch_interval", "ndt_align_batch_sharded", "ndt_prefilter", "ndt_prefilter_batch_dev",
-    "ndt_fuse_default_params", "ndt_predict_batch_dev", "ndt_fuse_batch_dev",
-    "ndt_remove_neighbors", "ndt_remove_neighbors_dev",
-    "ndt_difference_extraction", "ndt_difference_extraction_dev", "ndt_make_map", "ndt_make_map_dev",
-    "ndt_selftest_libm_f32", "ndt_selftest_optimizer", "ndt_resample_capacity", "ndt_resample_batch_dev", "ndt_resample", "ndt_scan_to_map_batch_dev",
-    "ndt_align_batch_multi", "ndt_align_batch_multi_dev", "ndt_map_build_batch", "ndt_map_build_batch_dev",
-    "ndt_local_map_batch", "ndt_local_map_batch_dev", "ndt_prefilter_batch",
-    "ndt_session_default_params", "ndt_sessions_create", "ndt_sessions_destroy", "ndt_sessions_step", "ndt_sessions_step_dev",
-    "ndt_sessions_local_map", "ndt_sessions_submap_cloud", "ndt_sessions_global_map", "ndt_sessions_get_stats",
-    "ndt_lattice_size", "ndt_lattice_pose", "ndt_score_poses", "ndt_score_poses_dev", "ndt_score_lattice_dev",
-    "ndt_lattice_select_dev", "ndt_relocalize", "ndt_relocalize_dev",
-    "ndt_fit_points_batch", "ndt_fit_points_batch_dev",
-    "ndt_occ_cell", "ndt_occ_create", "ndt_occ_destroy", "ndt_occ_clear", "ndt_occ_geometry_get", "ndt_occ_view",
-    "ndt_occ_integrate_dev", "ndt_occ_integrate", "ndt_occ_render_dev", "ndt_occ_render", "ndt_occ_counts",
-    "ndt_sessions_occ_integrate",
-    "ndt_pg_default_params", "ndt_pg_edge_between", "ndt_pg_info_from_cov", "ndt_pg_optimize_batch_dev", "ndt_pg_optimize_batch",
-    "ndt_repose_points_dev", "ndt_repose_points",
-]
+_vp, _sz, _i, _f, _d, _u32, _u64, _P = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double, C.c_uint32, C.c_uint64, C.POINTER
+
+# Every function of include/ndt_mi355x.h, in the header's order, with its argtypes: the one place a new entry point is
+# declared (tests/test_capi_binding.py holds each entry to the header's declaration).
+PROTOTYPES = {
+    "ndt_default_params": [_P(Params)],
+    "ndt_params_pcl110": [_P(Params)],
+    "ndt_params_pcl18": [_P(Params)],
+    "ndt_params_pcl_new": [_P(Params)],
+    "ndt_ctx_create": [_i, _P(_vp)],
+    "ndt_ctx_destroy": [_vp],
+    "ndt_last_error": [_vp],
+    "ndt_ctx_stream": [_vp],
+    "ndt_ctx_set_option": [_vp, _i, C.c_longlong],
+    "ndt_ctx_set_stream": [_vp, _vp],
+    "ndt_map_build": [_vp, _vp, _sz, _sz, _P(Params), _P(_vp)],
+    "ndt_map_build_dev": [_vp, _vp, _sz, _sz, _P(Params), _P(_vp)],
+    "ndt_map_rebuild_begin": [_vp, _vp, _sz, _sz, _P(Params), _vp],
+    "ndt_map_rebuild_end": [_vp, _vp],
+    "ndt_map_build_batch_dev": [_vp, _vp, _vp, _sz, _i, _vp, _vp],
+    "ndt_map_build_batch": [_vp, _vp, _vp, _sz, _i, _vp, _vp],
+    "ndt_map_destroy": [_vp],
+    "ndt_map_info_get": [_vp, _P(MapInfo)],
+    "ndt_map_export": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "ndt_align": [_vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ndt_align_batch": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "ndt_align_batch_dev": [_vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _vp, _vp],
+    "ndt_align_batch_prepare_dev": [_vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _vp],
+    "ndt_prepare_timing": [_vp, _P(_f)],
+    "ndt_align_batch_multi_dev": [_vp, _vp, _i, _vp, _vp, _vp, _i, _sz, _i, _vp, _vp, _vp],
+    "ndt_align_batch_multi": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "ndt_align_batch_sharded": [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp],
+    "ndt_align_batch_trace": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "ndt_eval_at": [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ndt_fitness_at": [_vp, _vp, _vp, _sz, _sz, _f, _f, _f, _f, _vp],
+    "ndt_prefilter": [_vp, _vp, _sz, _sz, _f, _vp, _P(_sz)],
+    "ndt_prefilter_batch_dev": [_vp, _vp, _sz, _vp, _i, _sz, _f, _vp, _vp, _vp],
+    "ndt_resample_capacity": [_sz, _d, _d, _P(_sz)],
+    "ndt_resample_batch_dev": [_vp, _vp, _sz, _vp, _i, _sz, _d, _d, _vp, _vp, _vp, _vp, _vp],
+    "ndt_resample": [_vp, _vp, _sz, _sz, _d, _d, _vp, _P(_sz)],
+    "ndt_scan_to_map_batch_dev": [_vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp],
+    "ndt_fuse_default_params": [_P(FuseParams)],
+    "ndt_predict_batch_dev": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "ndt_fuse_batch_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _P(FuseParams), _vp, _vp, _vp, _vp],
+    "ndt_remove_neighbors": [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _d, _vp, _P(_sz)],
+    "ndt_remove_neighbors_dev": [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _d, _vp, _vp, _vp],
+    "ndt_difference_extraction": [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _d, _vp, _P(_sz)],
+    "ndt_difference_extraction_dev": [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _d, _vp, _vp, _vp],
+    "ndt_make_map": [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _d, _d, _vp, _P(_sz)],
+    "ndt_make_map_dev": [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp],
+    "ndt_prefilter_batch": [_vp, _vp, _sz, _vp, _i, _f, _vp, _vp],
+    "ndt_local_map_batch_dev": [_vp, _vp, _i, _sz, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ndt_local_map_batch": [_vp, _vp, _i, _sz, _f, _vp, _vp, _vp, _vp, _vp],
+    "ndt_session_default_params": [_P(SessionParams)],
+    "ndt_sessions_create": [_vp, _i, _P(SessionParams), _P(_vp)],
+    "ndt_sessions_destroy": [_vp],
+    "ndt_sessions_step": [_vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ndt_sessions_step_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ndt_sessions_local_map": [_vp, _i, _P(_vp), _P(_sz), _P(_vp)],
+    "ndt_sessions_submap_cloud": [_vp, _i, _P(_vp), _P(_sz)],
+    "ndt_sessions_global_map": [_vp, _i, _vp, _sz, _P(_sz), _vp, _P(_i)],
+    "ndt_sessions_get_stats": [_vp, _P(SessionsStats)],
+    "ndt_lattice_size": [_P(PoseLattice), _P(_u64)],
+    "ndt_lattice_pose": [_P(PoseLattice), _u64, _vp],
+    "ndt_score_poses_dev": [_vp, _vp, _vp, _sz, _sz, _vp, _u64, _vp, _vp, _vp],
+    "ndt_score_lattice_dev": [_vp, _vp, _vp, _sz, _sz, _P(PoseLattice), _vp, _vp, _vp],
+    "ndt_score_poses": [_vp, _vp, _vp, _sz, _sz, _vp, _u64, _vp, _vp],
+    "ndt_lattice_select_dev": [_vp, _P(PoseLattice), _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "ndt_relocalize": [_vp, _vp, _vp, _sz, _sz, _P(RelocParams), _vp, _vp, _vp, _P(_i), _P(_i), _vp],
+    "ndt_relocalize_dev": [_vp, _vp, _vp, _sz, _sz, _P(RelocParams), _vp, _vp, _vp, _P(_i), _P(_i), _vp],
+    "ndt_fit_points_batch_dev": [_vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _sz, _d, _vp, _vp, _vp],
+    "ndt_fit_points_batch": [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _d, _vp, _vp],
+    "ndt_occ_cell": [_P(OccGeometry), _d, _d, _P(C.c_int64), _P(C.c_int64)],
+    "ndt_occ_create": [_vp, _P(OccGeometry), _P(_vp)],
+    "ndt_occ_destroy": [_vp],
+    "ndt_occ_clear": [_vp, _vp, _vp],
+    "ndt_occ_geometry_get": [_vp, _P(OccGeometry)],
+    "ndt_occ_view": [_vp, _P(_vp)],
+    "ndt_occ_integrate_dev": [_vp, _vp, _i, _vp, _vp, _vp, _i, _sz, _vp, _sz, _d, _vp, _vp],
+    "ndt_occ_integrate": [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _d, _vp],
+    "ndt_occ_render_dev": [_vp, _vp, _u32, _vp, _vp],
+    "ndt_occ_render": [_vp, _vp, _u32, _vp],
+    "ndt_occ_counts": [_vp, _vp, _vp, _vp],
+    "ndt_sessions_occ_integrate": [_vp, _vp, _vp, _d, _vp],
+    "ndt_pg_default_params": [_P(PgParams)],
+    "ndt_pg_edge_between": [_vp, _vp, _vp],
+    "ndt_pg_info_from_cov": [_vp, _d, _vp],
+    "ndt_pg_optimize_batch_dev": [_vp, _vp, _vp, _vp, _vp, _i, _P(PgParams), _vp, _vp],
+    "ndt_pg_optimize_batch": [_vp, _vp, _vp, _vp, _vp, _i, _P(PgParams), _vp],
+    "ndt_repose_points_dev": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp],
+    "ndt_repose_points": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz],
+    "ndt_kernel_timing": [_vp, _i, _P(_f), _P(_f)],
+    "ndt_launch_interval": [_vp, _i, _P(_f)],
+    "ndt_ctx_wait_launch": [_vp, _i, _vp],
+    "ndt_last_timing": [_vp, _P(_f), _P(_f)],
+    "ndt_selftest_libm_f32": [_vp, _vp, _sz, _vp, _vp, _vp],
+    "ndt_selftest_optimizer": [_vp] + [_vp, _sz, _vp] * 4,
+}
+RESTYPES = {"ndt_last_error": C.c_char_p, "ndt_ctx_stream": _vp}      # every other function returns an int status
+EXPORTS = list(PROTOTYPES)
 
 
 def lib():
@@ -200,106 +270,77 @@ def lib():
         raise NdtError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    for name in ("ndt_default_params", "ndt_params_pcl110", "ndt_params_pcl18", "ndt_params_pcl_new"):
-        getattr(L, name).argtypes = [C.POINTER(Params)]
-    L.ndt_ctx_create.argtypes = [i, C.POINTER(vp)]
-    L.ndt_ctx_destroy.argtypes = [vp]
-    L.ndt_last_error.restype = C.c_char_p
-    L.ndt_last_error.argtypes = [vp]
-    L.ndt_ctx_stream.restype = vp
-    L.ndt_ctx_stream.argtypes = [vp]
-    L.ndt_ctx_set_stream.argtypes = [vp, vp]
-    L.ndt_ctx_set_option.argtypes = [vp, i, C.c_longlong]
-    L.ndt_ctx_wait_launch.argtypes = [vp, i, vp]
-    L.ndt_map_build.argtypes = [vp, vp, sz, sz, C.POINTER(Params), C.POINTER(vp)]
-    L.ndt_map_build_dev.argtypes = [vp, vp, sz, sz, C.POINTER(Params), C.POINTER(vp)]
-    L.ndt_map_rebuild_begin.argtypes = [vp, vp, sz, sz, C.POINTER(Params), vp]
-    L.ndt_map_rebuild_end.argtypes = [vp, vp]
-    L.ndt_map_destroy.argtypes = [vp]
-    L.ndt_map_info_get.argtypes = [vp, C.POINTER(MapInfo)]
-    L.ndt_map_export.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.ndt_align.argtypes = [vp, vp, vp, sz, sz, vp, vp]
-    L.ndt_align_batch.argtypes = [vp, vp, vp, vp, i, i, vp, vp]
-    L.ndt_align_batch_dev.argtypes = [vp, vp, vp, vp, i, sz, i, vp, vp, vp]
-    L.ndt_align_batch_prepare_dev.argtypes = [vp, vp, vp, vp, i, sz, i, vp, vp]
-    L.ndt_prepare_timing.argtypes = [vp, C.POINTER(C.c_float)]
-    L.ndt_align_batch_trace.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, i, vp]
-    L.ndt_eval_at.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
-    L.ndt_fitness_at.argtypes = [vp, vp, vp, sz, sz, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-    L.ndt_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.ndt_selftest_libm_f32.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
-    L.ndt_selftest_optimizer.argtypes = [vp] + [vp, C.c_size_t, vp] * 4
-    L.ndt_kernel_timing.argtypes = [vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.ndt_launch_interval.argtypes = [vp, i, C.POINTER(C.c_float)]
-    L.ndt_align_batch_sharded.argtypes = [vp, vp, i, vp, vp, i, i, vp, vp]
-    L.ndt_prefilter.argtypes = [vp, vp, sz, sz, C.c_float, vp, C.POINTER(sz)]
-    L.ndt_prefilter_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, C.c_float, vp, vp, vp]
-    L.ndt_fuse_default_params.argtypes = [C.POINTER(FuseParams)]
-    L.ndt_predict_batch_dev.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp]
-    L.ndt_fuse_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, i, C.POINTER(FuseParams), vp, vp, vp, vp]
-    L.ndt_remove_neighbors.argtypes = [vp, vp, sz, sz, vp, sz, sz, C.c_double, vp, C.POINTER(sz)]
-    L.ndt_remove_neighbors_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, C.c_double, vp, vp, vp]
-    L.ndt_difference_extraction.argtypes = [vp, vp, sz, sz, vp, sz, sz, C.c_double, vp, C.POINTER(sz)]
-    L.ndt_difference_extraction_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, C.c_double, vp, vp, vp]
-    L.ndt_make_map.argtypes = [vp, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp,
-                               C.POINTER(sz)]
-    L.ndt_make_map_dev.argtypes = [vp, vp, sz, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
-    L.ndt_resample_capacity.argtypes = [sz, C.c_double, C.c_double, C.POINTER(sz)]
-    L.ndt_resample_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, C.c_double, C.c_double, vp, vp, vp, vp, vp]
-    L.ndt_resample.argtypes = [vp, vp, sz, sz, C.c_double, C.c_double, vp, C.POINTER(sz)]
-    L.ndt_scan_to_map_batch_dev.argtypes = [vp, vp, sz, vp, i, sz, vp, vp, vp]
-    L.ndt_align_batch_multi.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp]
-    L.ndt_align_batch_multi_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, i, vp, vp, vp]
-    L.ndt_map_build_batch.argtypes = [vp, vp, vp, sz, i, vp, vp]
-    L.ndt_map_build_batch_dev.argtypes = [vp, vp, vp, sz, i, vp, vp]
-    L.ndt_local_map_batch.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp]
-    L.ndt_local_map_batch_dev.argtypes = [vp, vp, i, sz, C.c_float, vp, vp, vp, vp, vp, vp]
-    L.ndt_prefilter_batch.argtypes = [vp, vp, sz, vp, i, C.c_float, vp, vp]
-    L.ndt_session_default_params.argtypes = [C.POINTER(SessionParams)]
-    L.ndt_sessions_create.argtypes = [vp, i, C.POINTER(SessionParams), C.POINTER(vp)]
-    L.ndt_sessions_destroy.argtypes = [vp]
-    L.ndt_sessions_step.argtypes = [vp, vp, sz, vp, vp, vp, vp]
-    L.ndt_sessions_step_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
-    L.ndt_sessions_local_map.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
-    L.ndt_sessions_submap_cloud.argtypes = [vp, i, C.POINTER(vp), C.POINTER(sz)]
-    L.ndt_sessions_global_map.argtypes = [vp, i, vp, sz, C.POINTER(sz), vp, C.POINTER(i)]
-    L.ndt_sessions_get_stats.argtypes = [vp, C.POINTER(SessionsStats)]
-    L.ndt_lattice_size.argtypes = [C.POINTER(PoseLattice), C.POINTER(C.c_uint64)]
-    L.ndt_lattice_pose.argtypes = [C.POINTER(PoseLattice), C.c_uint64, vp]
-    L.ndt_score_poses.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp]
-    L.ndt_score_poses_dev.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp, vp]
-    L.ndt_score_lattice_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(PoseLattice), vp, vp, vp]
-    L.ndt_lattice_select_dev.argtypes = [vp, C.POINTER(PoseLattice), vp, vp, i, i, vp, vp, vp]
-    L.ndt_relocalize.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
-    L.ndt_relocalize_dev.argtypes = [vp, vp, vp, sz, sz, C.POINTER(RelocParams), vp, vp, vp, C.POINTER(i), C.POINTER(i), vp]
-    L.ndt_fit_points_batch_dev.argtypes = [vp, vp, vp, vp, i, sz, i, vp, sz, C.c_double, vp, vp, vp]
-    L.ndt_fit_points_batch.argtypes = [vp, vp, vp, vp, i, i, vp, sz, C.c_double, vp, vp]
-    d = C.c_double
-    L.ndt_occ_cell.argtypes = [C.POINTER(OccGeometry), d, d, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.ndt_occ_create.argtypes = [vp, C.POINTER(OccGeometry), C.POINTER(vp)]
-    L.ndt_occ_destroy.argtypes = [vp]
-    L.ndt_occ_clear.argtypes = [vp, vp, vp]
-    L.ndt_occ_geometry_get.argtypes = [vp, C.POINTER(OccGeometry)]
-    L.ndt_occ_view.argtypes = [vp, C.POINTER(vp)]
-    L.ndt_occ_integrate_dev.argtypes = [vp, vp, i, vp, vp, vp, i, sz, vp, sz, d, vp, vp]
-    L.ndt_occ_integrate.argtypes = [vp, vp, i, vp, vp, vp, i, vp, sz, d, vp]
-    L.ndt_occ_render_dev.argtypes = [vp, vp, C.c_uint32, vp, vp]
-    L.ndt_occ_render.argtypes = [vp, vp, C.c_uint32, vp]
-    L.ndt_occ_counts.argtypes = [vp, vp, vp, vp]
-    L.ndt_sessions_occ_integrate.argtypes = [vp, vp, vp, d, vp]
-    L.ndt_pg_default_params.argtypes = [C.POINTER(PgParams)]
-    L.ndt_pg_edge_between.argtypes = [vp, vp, vp]
-    L.ndt_pg_info_from_cov.argtypes = [vp, d, vp]
-    L.ndt_pg_optimize_batch_dev.argtypes = [vp, vp, vp, vp, vp, i, C.POINTER(PgParams), vp, vp]
-    L.ndt_pg_optimize_batch.argtypes = [vp, vp, vp, vp, vp, i, C.POINTER(PgParams), vp]
-    L.ndt_repose_points_dev.argtypes = [vp, vp, sz, vp, i, vp, vp, vp, sz, vp]
-    L.ndt_repose_points.argtypes = [vp, vp, sz, vp, i, vp, vp, vp, sz]
-    for name in EXPORTS:
-        if name not in ("ndt_last_error", "ndt_ctx_stream"):
-            getattr(L, name).restype = i
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, _i)
     _LIB = L
     return L
+
+
+def _error(rc, what, h=None):
+    """The NdtError of a failed call: "<what> -> <rc>: <ndt_last_error of the context h, or of the calling thread>"."""
+    return NdtError("%s -> %d: %s" % (what, rc, lib().ndt_last_error(h).decode()))
+
+
+def _check(rc, what):
+    """Raise for a non-zero return code of a call that takes no context."""
+    if rc:
+        raise _error(rc, what)
+
+
+def _ptr(a):
+    """The address of an array's data, NULL for an empty one."""
+    return a.ctypes.data if len(a) else None
+
+
+def pack_scans(scans, dtype=np.float32, width=2, offsets_dtype=np.uint64):
+    """A list of [n_i, width] arrays (empty ones allowed) -> (points [N, width] `dtype`, C-contiguous; offsets [len + 1]
+    `offsets_dtype`): scan i is points[offsets[i]:offsets[i + 1]].  No scans: a (0, width) array and [0]."""
+    scans = [np.ascontiguousarray(x, dtype=dtype).reshape(-1, width) for x in scans]
+    off = np.zeros(len(scans) + 1, dtype=offsets_dtype)
+    off[1:] = np.cumsum([len(x) for x in scans])
+    return (np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, width), dtype)), off
+
+
+def _batch_args(scans, offsets, inits):
+    """(scans, offsets, inits) of a host align call as contiguous arrays, then B and its zeroed records."""
+    inits = np.ascontiguousarray(inits, dtype=np.float64).reshape(-1, 3)
+    return _f32c(scans), np.ascontiguousarray(offsets, dtype=np.uint64), inits, len(inits), np.zeros(len(inits), dtype=RESULT_DTYPE)
+
+
+def _defaults(struct, fn, kw, nested=()):
+    """struct() as the C function `fn` fills it, fields overridden by keyword (AttributeError for an unknown one).  A
+    keyword <name>_<field> with name in `nested` reaches the struct nested under that name, which itself is not replaced."""
+    p = struct()
+    getattr(lib(), fn)(C.byref(p))
+    for k, v in kw.items():
+        head, _, tail = k.partition("_")
+        obj, field = (getattr(p, head), tail) if head in nested and hasattr(getattr(p, head), tail) else (p, k)
+        if k in nested or not hasattr(obj, field):
+            raise AttributeError(k)
+        setattr(obj, field, v)
+    return p
+
+
+class _Handle:
+    """The owner of a C handle `h` that the library function named `_destroy` frees: close() frees it once, h = C.c_void_p()
+    gives it up without freeing."""
+    _destroy = None
+    h = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        # at interpreter shutdown the HIP runtime may already be gone: leave the handles to the OS
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 PRESETS = {"default": "ndt_default_params", "pcl110": "ndt_params_pcl110", "pcl18": "ndt_params_pcl18",
@@ -308,24 +349,14 @@ PRESETS = {"default": "ndt_default_params", "pcl110": "ndt_params_pcl110", "pcl1
 
 def default_params(preset="default", **kw):
     """ndt_params of a PCL-version preset (include/ndt_mi355x.h), fields overridden by keyword."""
-    p = Params()
-    getattr(lib(), PRESETS[preset])(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _defaults(Params, PRESETS[preset], kw)
 
 
 def align_batch_sharded(maps, scans, offsets, inits, shared_scan=False, partial=False):
     """ndt_align_batch_sharded: `maps` = one Map per device (each with its own Context), the batch on the host.
     `partial`: return (rc, records) instead of raising when a shard failed -- every record of a failed shard carries
     that shard's error in `status`, the others are complete."""
-    scans = _f32c(scans)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    inits = np.ascontiguousarray(inits, dtype=np.float64).reshape(-1, 3)
-    B = len(inits)
-    res = np.zeros(B, dtype=RESULT_DTYPE)
+    scans, offsets, inits, B, res = _batch_args(scans, offsets, inits)
     n = len(maps)
     cx = (C.c_void_p * n)(*[m.ctx.h for m in maps])
     mp = (C.c_void_p * n)(*[m.h for m in maps])
@@ -333,8 +364,7 @@ def align_batch_sharded(maps, scans, offsets, inits, shared_scan=False, partial=
                                        inits.ctypes.data, res.ctypes.data)
     if partial:
         return rc, res
-    if rc:
-        raise NdtError("ndt_align_batch_sharded -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+    _check(rc, "ndt_align_batch_sharded")
     return res
 
 
@@ -348,11 +378,7 @@ def align_batch_multi(ctx, maps, scans, offsets, inits, map_of=None, shared_scan
     """ndt_align_batch_multi: match b against maps[map_of[b]] (map_of None: maps[b], one map per match) in one launch on
     `ctx`; records in the format of Map.align_batch.  A map_of entry outside [0, len(maps)) gives that record alone
     status NDT_E_ARG (zeroed, fitness DBL_MAX)."""
-    scans = _f32c(scans)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    inits = np.ascontiguousarray(inits, dtype=np.float64).reshape(-1, 3)
-    B = len(inits)
-    res = np.zeros(B, dtype=RESULT_DTYPE)
+    scans, offsets, inits, B, res = _batch_args(scans, offsets, inits)
     mp, n = _map_handles(maps)
     mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
     if mo is not None and len(mo) != B:
@@ -391,7 +417,7 @@ def build_maps(ctx, clouds, params, maps=None):
     of launches on `ctx`.  `maps`: a list of Map or None per cloud (None: all new); existing maps are rebuilt in place, new
     ones created.  Returns the list of Map, in the order of `clouds`."""
     clouds = [_f32c(c) for c in clouds]
-    return _build_batch(ctx, "ndt_map_build_batch", [c.ctypes.data if len(c) else None for c in clouds],
+    return _build_batch(ctx, "ndt_map_build_batch", [_ptr(c) for c in clouds],
                         [len(c) for c in clouds], 8, params, maps)
 
 
@@ -399,37 +425,19 @@ def resample_capacity(total_points, space, space_thre):
     """ndt_resample_capacity: the output bound (in points) of the resampler for total_points raw points.  Needs no
     context and no device; raises NdtError on refused parameters."""
     cap = C.c_size_t()
-    rc = lib().ndt_resample_capacity(int(total_points), float(space), float(space_thre), C.byref(cap))
-    if rc:
-        raise NdtError("ndt_resample_capacity -> %d: %s" % (rc, lib().ndt_last_error(None).decode()))
+    _check(lib().ndt_resample_capacity(int(total_points), float(space), float(space_thre), C.byref(cap)), "ndt_resample_capacity")
     return cap.value
 
 
 def default_fuse_params(**kw):
-    p = FuseParams()
-    lib().ndt_fuse_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    """ndt_fuse_default_params, fields overridden by keyword."""
+    return _defaults(FuseParams, "ndt_fuse_default_params", kw)
 
 
 def default_session_params(**kw):
     """ndt_session_default_params (the launch file's values), fields overridden by keyword; match_* and fuse_* reach the
     nested ndt_params / ndt_fuse_params (match_resolution=0.5, fuse_score_thre=1.0)."""
-    p = SessionParams()
-    lib().ndt_session_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k.startswith("match_") and hasattr(p.match, k[6:]):
-            setattr(p.match, k[6:], v)
-        elif k.startswith("fuse_") and hasattr(p.fuse, k[5:]):
-            setattr(p.fuse, k[5:], v)
-        elif hasattr(p, k) and k not in ("match", "fuse"):
-            setattr(p, k, v)
-        else:
-            raise AttributeError(k)
-    return p
+    return _defaults(SessionParams, "ndt_session_default_params", kw, nested=("match", "fuse"))
 
 
 def session_params_from_launch(params):
@@ -445,18 +453,7 @@ def session_params_from_launch(params):
 
 def default_pg_params(**kw):
     """ndt_pg_default_params, fields overridden by keyword."""
-    p = PgParams()
-    lib().ndt_pg_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
-
-
-def _helper_check(rc, what):
-    if rc != 0:
-        raise NdtError("%s failed (%d): %s" % (what, rc, lib().ndt_last_error(None).decode()))
+    return _defaults(PgParams, "ndt_pg_default_params", kw)
 
 
 def pg_edge_between(from_pose, to_pose):
@@ -464,7 +461,7 @@ def pg_edge_between(from_pose, to_pose):
     a = np.ascontiguousarray(from_pose, dtype=np.float64).reshape(3)
     b = np.ascontiguousarray(to_pose, dtype=np.float64).reshape(3)
     e = np.zeros(1, dtype=PG_EDGE_DTYPE)
-    _helper_check(lib().ndt_pg_edge_between(a.ctypes.data, b.ctypes.data, e.ctypes.data), "ndt_pg_edge_between")
+    _check(lib().ndt_pg_edge_between(a.ctypes.data, b.ctypes.data, e.ctypes.data), "ndt_pg_edge_between")
     return e[0]["rel"].copy()
 
 
@@ -472,7 +469,7 @@ def pg_info_from_cov(cov_world, th_deg):
     """ndt_pg_info_from_cov: a world-frame 3 x 3 covariance seen from the frame at heading th_deg, inverted -> info[6]."""
     cov = np.ascontiguousarray(cov_world, dtype=np.float64).reshape(9)
     info = np.zeros(6, dtype=np.float64)
-    _helper_check(lib().ndt_pg_info_from_cov(cov.ctypes.data, float(th_deg), info.ctypes.data), "ndt_pg_info_from_cov")
+    _check(lib().ndt_pg_info_from_cov(cov.ctypes.data, float(th_deg), info.ctypes.data), "ndt_pg_info_from_cov")
     return info
 
 
@@ -565,19 +562,18 @@ def rerank(records, stats):
     return best
 
 
-class Context:
+class Context(_Handle):
     """ndt_ctx: one per process and device."""
+    _destroy = "ndt_ctx_destroy"
 
     def __init__(self, device=0):
         self.h = C.c_void_p()
-        rc = lib().ndt_ctx_create(device, C.byref(self.h))
-        if rc:
-            raise NdtError("ndt_ctx_create(%d) -> %d: %s" % (device, rc, lib().ndt_last_error(None).decode()))
+        _check(lib().ndt_ctx_create(device, C.byref(self.h)), "ndt_ctx_create(%d)" % device)
         self.device = device
 
     def check(self, rc, what):
         if rc:
-            raise NdtError("%s -> %d: %s" % (what, rc, lib().ndt_last_error(self.h).decode()))
+            raise _error(rc, what, self.h)
 
     @property
     def stream(self):
@@ -614,16 +610,13 @@ class Context:
     def prefilter_batch(self, scans, leaf):
         """ndt_prefilter_batch: the pre-filter of every scan of a list ([n_b, 2] float32 each, empty ones allowed) in one
         call -> the list of filtered scans, each what prefilter gives for it."""
-        scans = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in scans]
-        if not scans:
+        allp, off = pack_scans(scans)
+        B = len(off) - 1
+        if not B:
             return []
-        B = len(scans)
-        off = np.zeros(B + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(x) for x in scans])
-        allp = np.ascontiguousarray(np.concatenate(scans))
         out = np.empty((len(allp) + 1, 2), dtype=np.float32)
         ooff = np.zeros(B + 1, dtype=np.uint64)
-        self.check(lib().ndt_prefilter_batch(self.h, allp.ctypes.data if len(allp) else None, 8, off.ctypes.data, B, leaf,
+        self.check(lib().ndt_prefilter_batch(self.h, _ptr(allp), 8, off.ctypes.data, B, leaf,
                                              out.ctypes.data, ooff.ctypes.data), "ndt_prefilter_batch")
         return [out[int(ooff[b]):int(ooff[b + 1])].copy() for b in range(B)]
 
@@ -632,8 +625,7 @@ class Context:
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         out = np.empty((resample_capacity(len(xy), space, space_thre), 2), dtype=np.float64)
         m = C.c_size_t()
-        self.check(lib().ndt_resample(self.h, xy.ctypes.data if len(xy) else None, len(xy), 16, space, space_thre,
-                                      out.ctypes.data if len(out) else None, C.byref(m)), "ndt_resample")
+        self.check(lib().ndt_resample(self.h, _ptr(xy), len(xy), 16, space, space_thre, _ptr(out), C.byref(m)), "ndt_resample")
         return out[:m.value].copy()
 
     def resample_batch_dev(self, raw_ptr, stride, raw_offsets_ptr, B, total_raw_points, space, space_thre, out64_ptr,
@@ -654,8 +646,8 @@ class Context:
         lst = np.ascontiguousarray(point_list, dtype=np.float32).reshape(-1, 2)
         out = np.empty_like(base)
         m = C.c_size_t()
-        self.check(lib().ndt_remove_neighbors(self.h, base.ctypes.data, 8, len(base), lst.ctypes.data if len(lst) else None,
-                                              8, len(lst), thre_neighbor, out.ctypes.data, C.byref(m)),
+        self.check(lib().ndt_remove_neighbors(self.h, base.ctypes.data, 8, len(base), _ptr(lst), 8, len(lst), thre_neighbor,
+                                              out.ctypes.data, C.byref(m)),
                    "ndt_remove_neighbors")
         return out[:m.value].copy()
 
@@ -665,20 +657,17 @@ class Context:
         test = np.ascontiguousarray(test, dtype=np.float32).reshape(-1, 2)
         out = np.empty((len(test) + 1, 2), dtype=np.float32)
         m = C.c_size_t()
-        self.check(lib().ndt_difference_extraction(self.h, base.ctypes.data if len(base) else None, 8, len(base),
-                                                   test.ctypes.data if len(test) else None, 8, len(test), resol,
+        self.check(lib().ndt_difference_extraction(self.h, _ptr(base), 8, len(base), _ptr(test), 8, len(test), resol,
                                                    out.ctypes.data, C.byref(m)), "ndt_difference_extraction")
         return out[:m.value].copy()
 
     def make_map(self, scans, first_submap, newest, remove_moving=True, resol=0.05, thre_neighbor=0.1):
         """Submap::makeMap over a list of (n_i, 2) float32 scans in the map frame -> (n, 2) float32."""
-        scans = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1, 2) for s in scans]
-        off = np.zeros(len(scans) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(s) for s in scans])
-        allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2), np.float32)
-        out = np.empty(((2 if len(scans) == 1 else 1) * len(allp) + 1, 2), dtype=np.float32)
+        allp, off = pack_scans(scans)
+        n_scans = len(off) - 1
+        out = np.empty(((2 if n_scans == 1 else 1) * len(allp) + 1, 2), dtype=np.float32)
         m = C.c_size_t()
-        self.check(lib().ndt_make_map(self.h, allp.ctypes.data, 8, off.ctypes.data, len(scans), int(first_submap),
+        self.check(lib().ndt_make_map(self.h, allp.ctypes.data, 8, off.ctypes.data, n_scans, int(first_submap),
                                       int(newest), int(remove_moving), resol, thre_neighbor, out.ctypes.data,
                                       C.byref(m)), "ndt_make_map")
         return out[:m.value].copy()
@@ -705,17 +694,15 @@ class Context:
         keep = []                                            # the arrays the descriptors point into
         cap_cloud = cap_prev = 0
         for s, (scans, first, newest, remove, resol, thre, prev) in enumerate(items):
-            scans = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in scans]
-            off = np.zeros(len(scans) + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(x) for x in scans])
-            allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2), np.float32)
+            allp, off = pack_scans(scans)
+            n_scans = len(off) - 1
             if len(allp) == 0:
                 allp = np.zeros((1, 2), np.float32)          # (a non-NULL address for a submap without points)
             pv = np.zeros((0, 2), np.float32) if prev is None else np.ascontiguousarray(prev, dtype=np.float32).reshape(-1, 2)
             keep.append((allp, off, pv))
-            descs[s] = SubmapDesc(allp.ctypes.data, off.ctypes.data, len(scans), int(first), int(newest), int(remove),
-                                  float(resol), float(thre), pv.ctypes.data if len(pv) else None, len(pv))
-            cap_cloud += (2 if len(scans) == 1 else 1) * int(off[-1])
+            descs[s] = SubmapDesc(allp.ctypes.data, off.ctypes.data, n_scans, int(first), int(newest), int(remove),
+                                  float(resol), float(thre), _ptr(pv), len(pv))
+            cap_cloud += (2 if n_scans == 1 else 1) * int(off[-1])
             cap_prev += len(pv)
         cloud = np.empty((cap_cloud + 1, 2), dtype=np.float32)
         target = np.empty((cap_cloud + cap_prev + 1, 2), dtype=np.float32)
@@ -817,23 +804,10 @@ class Context:
         self.check(lib().ndt_launch_interval(self.h, back, C.byref(a)), "ndt_launch_interval")
         return a.value
 
-    def close(self):
-        if self.h:
-            lib().ndt_ctx_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        # at interpreter shutdown the HIP runtime may already be gone: leave the handles to the OS
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Sessions:
+class Sessions(_Handle):
     """ndt_sessions: n device-resident SLAM sessions stepped together (include/ndt_mi355x.h)."""
+    _destroy = "ndt_sessions_destroy"
 
     def __init__(self, ctx, n_sessions, params=None):
         self.ctx = ctx
@@ -853,16 +827,13 @@ class Sessions:
     def step(self, scans, odo, active=None):
         """ndt_sessions_step: scans = one [n_i, 2] float64 raw scan per session (empty ones allowed), odo = [S, 3]
         (tx, ty, th[deg]) -> the S records as a numpy array of SESSION_STEP_DTYPE."""
-        scans = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2) for x in scans]
-        if len(scans) != self.n:
+        allp, off = pack_scans(scans, dtype=np.float64)
+        if len(off) - 1 != self.n:
             raise ValueError("step needs one scan per session")
-        off = np.zeros(self.n + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(x) for x in scans])
-        allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2))
         odo = np.ascontiguousarray(odo, dtype=np.float64).reshape(self.n, 3)
         a = self._active(active)
         out = np.zeros(self.n, dtype=SESSION_STEP_DTYPE)
-        self.ctx.check(lib().ndt_sessions_step(self.h, allp.ctypes.data if len(allp) else None, 16, off.ctypes.data,
+        self.ctx.check(lib().ndt_sessions_step(self.h, _ptr(allp), 16, off.ctypes.data,
                                                odo.ctypes.data, None if a is None else a.ctypes.data, out.ctypes.data),
                        "ndt_sessions_step")
         return out
@@ -906,7 +877,7 @@ class Sessions:
         self.ctx.check(lib().ndt_sessions_global_map(self.h, i, None, 0, C.byref(n), None, C.byref(k)), "ndt_sessions_global_map")
         out = np.zeros((n.value, 2), dtype=np.float32)
         off = np.zeros(k.value + 1, dtype=np.uint64)
-        self.ctx.check(lib().ndt_sessions_global_map(self.h, i, out.ctypes.data if n.value else None, n.value, C.byref(n),
+        self.ctx.check(lib().ndt_sessions_global_map(self.h, i, _ptr(out), n.value, C.byref(n),
                                                      off.ctypes.data, C.byref(k)), "ndt_sessions_global_map")
         return out, [out[int(off[j]):int(off[j + 1])] for j in range(k.value)]
 
@@ -928,22 +899,10 @@ class Sessions:
         self.ctx.check(lib().ndt_sessions_get_stats(self.h, C.byref(st)), "ndt_sessions_get_stats")
         return st
 
-    def close(self):
-        if self.h:
-            lib().ndt_sessions_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Map:
+class Map(_Handle):
     """ndt_map: the NDT voxel grid of one target cloud (replaces ndt.setInputTarget)."""
+    _destroy = "ndt_map_destroy"
 
     def __init__(self, ctx, xy=None, params=None, dev_ptr=None, n=None, stride=8):
         self.ctx = ctx
@@ -957,6 +916,10 @@ class Map:
         m = cls.__new__(cls)
         m.ctx, m.params, m.h = ctx, params, C.c_void_p(handle)
         return m
+
+    def _cx(self, ctx):
+        """The context that launches: the caller's, or the map's own."""
+        return ctx if ctx is not None else self.ctx
 
     def rebuild(self, xy=None, dev_ptr=None, n=None, stride=8, params=None):
         """Build the map again in place; `params`: other ndt_params from now on (the resolution may not change)."""
@@ -1005,11 +968,7 @@ class Map:
         return res[0]
 
     def align_batch(self, scans, offsets, inits, shared_scan=False, trace_cap=0):
-        scans = _f32c(scans)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        inits = np.ascontiguousarray(inits, dtype=np.float64).reshape(-1, 3)
-        B = len(inits)
-        res = np.zeros(B, dtype=RESULT_DTYPE)
+        scans, offsets, inits, B, res = _batch_args(scans, offsets, inits)
         if trace_cap:
             trace = np.zeros((B, trace_cap, 8)); rows = np.zeros(B, np.int32)
             self.ctx.check(lib().ndt_align_batch_trace(
@@ -1026,14 +985,14 @@ class Map:
                         stream=None, ctx=None):
         """All pointers are device addresses (e.g. torch.Tensor.data_ptr()); asynchronous.  `ctx`: the context
         whose scratch the launch uses (default: the map's own) -- two contexts keep two batches in flight."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_align_batch_dev(cx.h, self.h, scans_ptr, offsets_ptr, B, total_points,
                                            int(shared_scan), inits_ptr, out_ptr, stream), "ndt_align_batch_dev")
 
     def prepare_batch_dev(self, scans_ptr, offsets_ptr, B, total_points, inits_ptr, shared_scan=False, stream=None, ctx=None):
         """ndt_align_batch_prepare_dev: the optimiser's start, the window geometry and the voxel order of every scan of a batch,
         queued on `stream` ahead of the align_batch_dev call with the same arguments (and the same `ctx`); asynchronous."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_align_batch_prepare_dev(cx.h, self.h, scans_ptr, offsets_ptr, B, total_points,
                                                    int(shared_scan), inits_ptr, stream), "ndt_align_batch_prepare_dev")
 
@@ -1070,20 +1029,20 @@ class Map:
 
     def score_poses_dev(self, scan_ptr, n, poses_ptr, P, score_ptr, pairs_ptr=None, stride=8, stream=None, ctx=None):
         """ndt_score_poses_dev: device addresses; asynchronous.  `ctx`: the context that launches (default: the map's)."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_score_poses_dev(cx.h, self.h, scan_ptr, n, stride, poses_ptr, P, score_ptr, pairs_ptr, stream),
                  "ndt_score_poses_dev")
 
     def score_lattice(self, scan_ptr, n, lattice, score_ptr, pairs_ptr=None, stride=8, stream=None, ctx=None):
         """ndt_score_lattice_dev: the score volume of a PoseLattice; device addresses; asynchronous."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_score_lattice_dev(cx.h, self.h, scan_ptr, n, stride, C.byref(lattice), score_ptr, pairs_ptr, stream),
                  "ndt_score_lattice_dev")
 
     def lattice_select(self, lattice, score_ptr, pairs_ptr, top_k, local_max, cand_ptr, n_cand_ptr, stream=None, ctx=None):
         """ndt_lattice_select_dev: the top_k eligible poses of a score volume (device addresses: uint64 indices, one int32
         count); asynchronous."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_lattice_select_dev(cx.h, C.byref(lattice), score_ptr, pairs_ptr, int(top_k), int(local_max), cand_ptr,
                                               n_cand_ptr, stream), "ndt_lattice_select_dev")
 
@@ -1111,7 +1070,7 @@ class Map:
                        shared_scan=False, stream=None, ctx=None):
         """ndt_fit_points_batch_dev: device addresses (d2_ptr or stats_ptr may be None); asynchronous.  tf_ptr = the address of
         a record's T00 with tf_stride = RESULT_BYTES reads the transforms of a launch's records where they lie."""
-        cx = ctx if ctx is not None else self.ctx
+        cx = self._cx(ctx)
         cx.check(lib().ndt_fit_points_batch_dev(cx.h, self.h, scans_ptr, offsets_ptr, B, total_points, int(shared_scan), tf_ptr,
                                                 tf_stride, float(max_d2), d2_ptr, stats_ptr, stream), "ndt_fit_points_batch_dev")
 
@@ -1149,19 +1108,6 @@ class Map:
                 out["fit_stats"] = st
                 out["best"] = rerank(out["records"], st)
         return out
-
-    def close(self):
-        if self.h:
-            lib().ndt_map_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _occ_handles(grids):
@@ -1201,8 +1147,9 @@ def integrate_occ_dev(ctx, grids, grid_of_ptr, xy_ptr, offsets_ptr, B, total_poi
                                           float(max_range2), stats_ptr, stream), "ndt_occ_integrate_dev")
 
 
-class OccGrid:
+class OccGrid(_Handle):
     """ndt_occ: an occupancy grid of {hit, pass} counters on the device (include/ndt_mi355x.h)."""
+    _destroy = "ndt_occ_destroy"
 
     def __init__(self, ctx, geometry):
         self.ctx = ctx
@@ -1248,16 +1195,3 @@ class OccGrid:
 
     def clear(self, stream=None):
         self.ctx.check(lib().ndt_occ_clear(self.ctx.h, self.h, stream), "ndt_occ_clear")
-
-    def close(self):
-        if self.h:
-            lib().ndt_occ_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,6 +1,8 @@
 """The oracle standing in for a context that provides the batched local-map assembly (tests only)."""
 import numpy as np
 
+from ndt_slam_amd.capi import pack_scans
+
 _EMPTY = np.zeros((0, 2), np.float32)
 
 
@@ -79,10 +81,7 @@ def room_scans(rng, n_scans, n_wall, n_mover, jitter=0.003):
 
 def item_arrays(item):
     """(all points [n, 2] float32, offsets uint64, previous cloud [m, 2] float32) of an item."""
-    scans = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in item[0]]
-    off = np.zeros(len(scans) + 1, np.uint64)
-    off[1:] = np.cumsum([len(x) for x in scans])
-    allp = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2), np.float32)
+    allp, off = pack_scans(item[0])
     prev = _EMPTY if item[6] is None else np.ascontiguousarray(item[6], np.float32).reshape(-1, 2)
     return allp, off, prev
 

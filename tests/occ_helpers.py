@@ -11,6 +11,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from ndt_slam_amd.capi import pack_scans as pack           # [scan] -> (packed float32 [N, 2], uint64 offsets)
 from session_helpers import OracleSessions, to_map_frame
 
 Geometry = namedtuple("Geometry", "x0 y0 res nx ny")
@@ -135,14 +136,6 @@ def stats_tuple(st):
 
 def add_stats(a, b):
     return {k: int(a[k]) + int(b[k]) for k in STATS}
-
-
-def pack(scans):
-    """[scan] -> (packed float32 [N, 2], uint64 offsets)."""
-    scans = [np.asarray(s, np.float32).reshape(-1, 2) for s in scans]
-    off = np.zeros(len(scans) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in scans])
-    return (np.concatenate(scans) if scans else np.zeros((0, 2), np.float32)).astype(np.float32), off
 
 
 class HostGrid:

@@ -20,11 +20,6 @@ if ROOT not in sys.path:
 RAGGED_LENGTHS = (1, 2, 63, 64, 65, 255, 256, 257, 10239, 10240, 0)
 
 
-def _ragged(parts):
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32), off
-
-
 def world():
     """The C3 world (1M-point map, 10k-point scans, 0.5 m voxels) and a second map of another cloud."""
     from ndt_slam_amd import synth
@@ -37,6 +32,7 @@ def world():
 
 def batches(sf):
     """name -> (scans, offsets, inits, shared_scan).  Inputs only: no device needed."""
+    from ndt_slam_amd.capi import pack_scans
     scans, off, _, inits = sf.batch(0, 64)
     out = {"c3_64": (scans, off, inits, False)}
     # ragged: lengths at the set-up's edges, an empty scan, and a scan with NaN points among finite ones
@@ -49,7 +45,7 @@ def batches(sf):
     nan_scan[::97] = np.nan
     nan_scan[5, 1] = np.nan
     parts.append(nan_scan)
-    rs, ro = _ragged(parts)
+    rs, ro = pack_scans(parts)
     out["ragged"] = (rs, ro, inits[:len(parts)], False)
     # dense clusters: ~10k points packed into a handful of voxels (+-4 cm around 3..6 centres, at 0.5 m voxels), so that one
     # wave instruction of the scatter issues hundreds of atomics on the same cell counter
@@ -62,7 +58,7 @@ def batches(sf):
         n = 10240 - 37 * b
         pts = centres[rng.integers(0, k, size=n)] + rng.uniform(-0.04, 0.04, size=(n, 2))
         parts.append(pts.astype(np.float32))
-    ds, do = _ragged(parts)
+    ds, do = pack_scans(parts)
     out["dense"] = (ds, do, inits[48:54], False)
     # 24 scans, fewer than the launch's workgroups: the owners open their scans for joining from inside the set-up (open_ctl)
     s24, o24, _, i24 = sf.batch(100, 24)

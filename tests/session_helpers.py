@@ -172,9 +172,7 @@ class ComposedChain:
         torch, capi, ctx, S, p = self.torch, self.capi, self.ctx, self.S, self.p
         out = step_records(capi, S)
         act = [True] * S if active is None else [bool(a) for a in active]
-        scans = [np.ascontiguousarray(x, np.float64).reshape(-1, 2) for x in scans]
-        off = np.zeros(S + 1, np.int64)
-        off[1:] = np.cumsum([len(x) for x in scans])
+        raw, off = capi.pack_scans(scans, np.float64, offsets_dtype=np.int64)
         N = int(off[-1])
         odo = np.ascontiguousarray(odo, np.float64).reshape(S, 3)
         mode = [0 if not act[i] else (2 if self.started[i] else 1) for i in range(S)]
@@ -197,7 +195,7 @@ class ComposedChain:
         d_mapof = self._t(map_of)
         d_mapxy = torch.zeros((cap, 2), dtype=torch.float32, device=self.dev)
         if N:
-            d_raw, d_off = self._t(np.concatenate(scans)), self._t(off)
+            d_raw, d_off = self._t(raw), self._t(off)
         torch.cuda.synchronize()                      # (the context works on a stream of its own)
         if N:
             ctx.resample_batch_dev(d_raw.data_ptr(), 16, d_off.data_ptr(), S, N, p["space"], p["space_thre"], d_rs64.data_ptr(),

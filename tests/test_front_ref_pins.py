@@ -30,6 +30,7 @@ from ndt_slam_amd import replay                                    # noqa: E402
 from ndt_slam_amd.pose_estimator import RAD2DEG, Pose2D, Scan2D    # noqa: E402
 from test_fuse_oracle import numpy_kalman_update, numpy_odometry_covariance, result_record   # noqa: E402
 import front_ref_bounds as FB                                      # noqa: E402
+from gpu_support import same_bits                                  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden", "front_ref_golden.npz")
 RESTATEMENTS = ("oracle", "twin", "replay")
@@ -38,11 +39,6 @@ RESTATEMENTS = ("oracle", "twin", "replay")
 @pytest.fixture(scope="module")
 def z():
     return np.load(GOLD)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def pose3(p):

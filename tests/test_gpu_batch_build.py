@@ -6,15 +6,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def C1():
@@ -32,15 +26,14 @@ def assert_same_map(a, b, what=""):
 
 def scans_for(n_maps, seed=0):
     """One C1 scan per map (the scan of a C1 world from its own seed, with its initial guess)."""
-    from ndt_slam_amd import synth
+    from ndt_slam_amd import capi, synth
     cfg = C1()
     parts, inits = [], []
     for s in range(n_maps):
         w = synth.make_map(cfg["n_map"], cfg["half"], seed=7000 + seed + s % 5)
         scan, truth, init = synth.ScanFactory(w, cfg["half"], cfg["n_scan"]).make(s)
         parts.append(scan); inits.append(init)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    return np.concatenate(parts), off, np.array(inits)
+    return (*capi.pack_scans(parts), np.array(inits))
 
 
 def records(capi, ctx, maps, scans):
@@ -260,8 +253,8 @@ def test_deferred_fitness_and_a_batched_rebuild_behind_the_launch(gpu):
     for b in range(48):
         scan, truth, init = synth.ScanFactory(clouds[map_of[b]], cfg["half"], cfg["n_scan"]).make(b)
         parts.append(scan); inits.append(init)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans, inits = np.concatenate(parts), np.array(inits)
+    scans, off = capi.pack_scans(parts)
+    inits = np.array(inits)
     dev = torch.device("cuda", 0)
     moved = [torch.from_numpy(np.ascontiguousarray(clouds[k] + np.float32(0.7 * k), dtype=np.float32)).to(dev) for k in (1, 2)]
 

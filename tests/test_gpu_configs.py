@@ -173,8 +173,7 @@ def test_scan_above_the_lds_sort_limit(gpu, oracle, world_1m):
         assert_result_parity(r, om.align(scan, init, run_stats=True))
     # a mixed batch: both set-up routines and the unordered path side by side in one launch
     parts = [synth.ScanFactory(m, cfg["half"], n, radius=40.0).make(5)[:3:2] for n in (9_000, 15_000, 10_240, 10_241, 25_000)]
-    scans = np.concatenate([p[0] for p in parts]); inits = np.stack([p[1] for p in parts])
-    off = np.concatenate([[0], np.cumsum([len(p[0]) for p in parts])]).astype(np.uint64)
+    scans, off = capi.pack_scans([p[0] for p in parts]); inits = np.stack([p[1] for p in parts])
     res = gm.align_batch(scans, off, inits)
     for b in range(len(parts)):
         assert_result_parity(res[b], om.align(parts[b][0], parts[b][1], run_stats=True))

@@ -9,9 +9,11 @@ import numpy as np
 import pytest
 
 import fitness_workloads as W
+from ndt_slam_amd.capi import pack_scans
 from fit_points_helpers import (DBL_MAX, HALF_SCENES, IDENT, describe, half_scene, narrow_pool, ranged_best, ref_stats, stats_tuple,
                                 tf_of_pose)
 from reloc_helpers import LAT, capi_lattice, pose_error, ref_best
+from gpu_support import gpu, sync, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +22,6 @@ LEAVES = (0.05, 0.3, 2.0)
 CASES = [(leaf, off) for leaf in LEAVES for off in W.OFFSETS]
 STILL = dict(max_iter=0, min_pts=1 << 30)                   # (as tests/test_gpu_fitness_geometry.py: only the raw buckets matter)
 SHAPES = (1, 63, 64, 65, 255, 256, 257, 4097, 16385)       # 4097: more than 64 chunks; 16385: more than 256
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def sse_of(leaf, off):
@@ -41,9 +35,8 @@ def build(gpu, w, sse=1):
 
 
 def ragged(parts):
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    allp = np.concatenate([np.asarray(p, dtype=F).reshape(-1, 2) for p in parts]) if parts else np.zeros((0, 2), F)
-    return np.ascontiguousarray(allp if len(allp) else np.zeros((1, 2), F), dtype=F), off
+    allp, off = pack_scans(parts)
+    return (allp if len(allp) else np.zeros((1, 2), F)), off           # (an address for a batch without points)
 
 
 def poses_of(w):
@@ -204,17 +197,6 @@ def test_shared_scan_rows_equal_the_own_scan_form(gpu):
 
 
 # ------------------------------------------------------------------------------------------ 5: against the launch
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(torch.device("cuda", 0))
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
 def test_records_of_a_launch_as_transforms_where_they_lie(gpu, c1_world):
     """align_batch_dev on 8 scans of the C1 world, then fit_points_dev with tf = the address of record 0's T00 and the record
     stride: fitness_all within n 2^-53 of record.fitness, n_dist == n, and n_in at the 0.9 quantile as numpy counts it."""

@@ -21,6 +21,8 @@ import numpy as np
 import pytest
 
 import fitness_workloads as W
+from ndt_slam_amd.capi import pack_scans as ragged
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,14 +34,6 @@ CASES = [(leaf, off) for leaf in W.GPU_LEAVES for off in W.OFFSETS]
 # distribution (min_pts beyond any bucket) there is nothing to step along, and the record's matrix is the seed's.  The
 # buckets of raw points, which are all the fitness search reads, do not depend on min_pts.
 STILL = dict(max_iter=0, min_pts=1 << 30)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def sse_of(leaf, off):
@@ -67,11 +61,6 @@ def build(gpu, w, sse=1):
     assert (i.min_bx, i.min_by, i.div_x, i.div_y) == (G.min_bx, G.min_by, G.div_x, G.div_y), (w.family, w.leaf, w.offset)
     assert i.n_points == len(w.map)
     return gm
-
-
-def ragged(parts):
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    return np.ascontiguousarray(np.concatenate(parts), dtype=F), off
 
 
 def T_of(r):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import front_ref_bounds as FB
+from gpu_support import gpu, same_bits, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
@@ -23,26 +24,8 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "front
 
 
 @pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
-
-
-@pytest.fixture(scope="module")
 def z():
     return np.load(GOLD)
-
-
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def predict_on_device(ctx, cur, prev, last):
@@ -154,8 +137,7 @@ def test_chained_run_on_the_device_step_by_step(gpu, z):
 def resample_on_device(capi, ctx, scans, space, space_thre):
     import torch
     B = len(scans)
-    raw = np.concatenate(scans).reshape(-1, 2)
-    off = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+    raw, off = capi.pack_scans(scans, np.float64, offsets_dtype=np.int64)
     cap = capi.resample_capacity(len(raw), space, space_thre)
     d_raw, d_off = to_dev(raw), to_dev(off)
     d64 = torch.full((cap, 2), -1.0, dtype=torch.float64, device="cuda:0")

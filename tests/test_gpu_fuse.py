@@ -4,21 +4,10 @@ sin/cos (1 ulp), hence a 1e-11 relative tolerance."""
 import numpy as np
 import pytest
 
+from gpu_support import gpu, to_dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
-
-
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def test_predict_and_fuse_match_the_oracle(gpu, oracle):
@@ -97,8 +86,7 @@ def test_whole_front_end_step_on_the_device(gpu, oracle, c1_world):
         d = np.array([[np.cos(al), np.sin(al)], [-np.sin(al), np.cos(al)]]) @ (np.array(init[:2]) - last[:2])   # motion in the robot frame
         cur = np.array([*(prev[:2] + np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]) @ d), prev[2] + 2.0])
         lasts.append(last); prevs.append(prev); curs.append(cur)
-    lens = [len(r) for r in raws]
-    raw_all = np.concatenate(raws).astype(np.float32); raw_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    raw_all, raw_off = capi.pack_scans(raws, offsets_dtype=np.int64)
     last_cov = np.tile(np.eye(3) * 1e-4, (B, 1, 1))
     dev = "cuda:0"
     d_raw, d_roff = to_dev(raw_all), to_dev(raw_off)

@@ -148,9 +148,8 @@ def test_make_map_feeds_the_target_on_the_device(ctx, oracle):
     from ndt_slam_amd import capi
     rng = np.random.default_rng(9)
     scans = submap_scans(rng, 8, 3000, 100)
-    off = np.zeros(len(scans) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in scans])
-    allp = torch.from_numpy(np.concatenate(scans)).cuda()
+    packed, off = capi.pack_scans(scans)
+    allp = torch.from_numpy(packed).cuda()
     out = torch.empty((len(allp) + 1, 2), dtype=torch.float32, device="cuda")
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()

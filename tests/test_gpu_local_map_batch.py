@@ -7,18 +7,11 @@ import numpy as np
 import pytest
 
 from local_map_helpers import CountingOps, DevCall, capacities, host_call, item_arrays, oracle_local_map, room_scans
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 EMPTY = np.zeros((0, 2), np.float32)
 LEAF = 0.05
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def prev_cloud(rng, n):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import map_build_workloads as W
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +21,6 @@ ACCEPTED = ("accept", "raise1", "raise2")
 INFO = ("min_bx", "min_by", "div_x", "div_y", "n_cells", "n_valid", "n_points")
 TABLE = ("idx", "npts", "cent", "mean", "icov")
 T0 = time.time()
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def prm_of(mod, c):

@@ -5,15 +5,9 @@ import math
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def wrap(a):
@@ -65,8 +59,7 @@ def per_map(capi, maps, scans, off, inits, map_of):
     for k in sorted(set(int(x) for x in map_of)):
         idx = [b for b in range(B) if int(map_of[b]) == k]
         parts = [scans[int(off[b]):int(off[b + 1])] for b in idx]
-        o = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-        out[idx] = maps[k].align_batch(np.concatenate(parts), o, inits[idx])
+        out[idx] = maps[k].align_batch(*capi.pack_scans(parts), inits[idx])
     return out
 
 
@@ -117,8 +110,8 @@ def test_mixed_sizes_in_one_launch(gpu, oracle):
             k = (b * 7) % 64
             scan, truth, init = factories[k].make(b)
         parts.append(scan); inits.append(init); map_of.append(k)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans, inits, map_of = np.concatenate(parts), np.array(inits), np.array(map_of, np.int32)
+    scans, off = capi.pack_scans(parts)
+    inits, map_of = np.array(inits), np.array(map_of, np.int32)
     res = multi_dev(capi, ctx, maps, scans, off, inits, map_of)
     assert np.all(res["status"] == 0)
     ref = per_map(capi, maps, scans, off, inits, map_of)
@@ -144,8 +137,8 @@ def test_work_sharing_across_maps(gpu):
     for k in range(8):
         scan, truth, init = synth.ScanFactory(clouds[k], cfg["half"], cfg["n_scan"]).make(k)
         parts.append(scan); inits.append(init)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans, inits = np.concatenate(parts), np.array(inits)
+    scans, off = capi.pack_scans(parts)
+    inits = np.array(inits)
     got = []
     for helpers in (0, None, 15):
         ctx = capi.Context(0)
@@ -196,8 +189,8 @@ def test_bad_map_index_marks_only_its_record(gpu):
         k = int(map_of[b]) if 0 <= map_of[b] < 3 else 0
         scan, truth, init = synth.ScanFactory(clouds[k], cfg["half"], cfg["n_scan"]).make(b)
         parts.append(scan); inits.append(init)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans, inits = np.concatenate(parts), np.array(inits)
+    scans, off = capi.pack_scans(parts)
+    inits = np.array(inits)
     for shared in (False, True):
         o = np.array([0, len(parts[0])], np.uint64) if shared else off
         sc = parts[0] if shared else scans
@@ -313,8 +306,8 @@ def test_deferred_fitness_and_a_rebuild_behind_the_launch(gpu):
     for b in range(48):
         scan, truth, init = synth.ScanFactory(clouds[map_of[b]], cfg["half"], cfg["n_scan"]).make(b)
         parts.append(scan); inits.append(init)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans, inits = np.concatenate(parts), np.array(inits)
+    scans, off = capi.pack_scans(parts)
+    inits = np.array(inits)
     dev = torch.device("cuda", 0)
     moved = torch.from_numpy(np.ascontiguousarray(clouds[1] + np.float32(0.7), dtype=np.float32)).to(dev)
 

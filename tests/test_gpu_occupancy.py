@@ -9,20 +9,13 @@ import pytest
 
 import occ_helpers as H
 from session_helpers import lockstep, same_records, session_logs
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 OFFSET_GEOM = H.Geometry(-1003.3, 707.1, 0.05, 64, 48)        # a world offset of the fitness tests; 0.05 is no short double
 EXACT_GEOM = H.Geometry(0.0, 0.0, 0.25, 300, 300)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def centre(g, ix, iy):

@@ -15,17 +15,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import optimizer_cases as OC      # noqa: E402
+from gpu_support import gpu  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 EPS = OC.EPS
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 @pytest.fixture(scope="module")
@@ -159,8 +152,7 @@ def test_match_list_follows_the_oracle(gpu, oracle, c1_world, omaps):
     n_rows = n_matches = 0
     for pset, items in _batches(c1_world).items():
         gm = capi.Map(ctx, m, capi.default_params(resolution=cfg["resolution"], **OC.PARAM_SETS[pset]))
-        scans = np.concatenate([it[1] for it in items])
-        off = np.concatenate([[0], np.cumsum([len(it[1]) for it in items])]).astype(np.uint64)
+        scans, off = capi.pack_scans([it[1] for it in items])
         inits = np.array([it[2] for it in items])
         res, traces = gm.align_batch(scans, off, inits, trace_cap=512)
         for b, (name, scan, init) in enumerate(items):

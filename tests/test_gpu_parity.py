@@ -7,18 +7,12 @@ import math
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 POSE_TOL_M = 1e-4      # north_star: 1e-4 m
 POSE_TOL_RAD = 1e-4    # north_star: 1e-4 rad
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def wrap(a):
@@ -979,8 +973,7 @@ def test_deferred_fitness_gives_the_same_records(gpu):
     dev = torch.device("cuda", 0)
     scans, off, truths, inits = sf.batch(0, 256)
     parts = [scans[int(off[b]):int(off[b + 1])][:(0 if b == 5 else 1 + (b * 977) % 10000)] for b in range(40)]
-    r_off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    r_scans = np.concatenate(parts)
+    r_scans, r_off = capi.pack_scans(parts)
     batches = []
     for sc, of, ini in ((scans, off, inits), (r_scans, r_off, inits[:40])):
         batches.append((torch.from_numpy(sc).to(dev), torch.from_numpy(of.astype(np.int64)).to(dev), torch.from_numpy(ini).to(dev), len(ini), len(sc)))
@@ -1103,8 +1096,7 @@ def test_a_batch_prepared_ahead_gives_the_same_records(gpu, c1_world):
         if b == 11:
             sc = np.concatenate([sc] * 4)[:11000]                     # beyond kSortRegs = 10240 points: the streaming set-up
         parts.append(sc); inits.append(ini)
-    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
-    scans = np.concatenate(parts); inits = np.array(inits)
+    scans, off = capi.pack_scans(parts); inits = np.array(inits)
     dev = torch.device("cuda", 0)
     prm = capi.default_params(resolution=cfg["resolution"])
     gm = capi.Map(ctx, m, prm)

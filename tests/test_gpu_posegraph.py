@@ -9,20 +9,13 @@ import numpy as np
 import pytest
 
 import pg_helpers as H
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 PARITY_KEYS = [("eight", n) for n in H.EIGHT_SIZES] + [("star", 40), ("star", 120), ("shuffled", 40), ("shuffled", 120),
                                                         ("duplicate", 24), ("reversed", 65)]
 POSE_TOL = 1e-8                                       # metres and radians: the bound the issue derives (see test_parity)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def solve(gpu, graphs, **prm):

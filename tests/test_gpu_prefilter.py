@@ -4,15 +4,9 @@ bit for bit (the filter is order dependent; src/PoseEstimator.cpp:6-10)."""
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def lidar_like(rng, n, radius=30.0):

@@ -8,6 +8,7 @@ import pytest
 
 from reloc_helpers import (LAT, capi_lattice, crafted_volumes, edge_poses, eval_poses, lattice_poses, lattice_size, oracle_scores,
                            pose_error, ref_best, ref_select)
+from gpu_support import gpu, sync, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,29 +16,10 @@ SMALL = dict(x0=-3.0, y0=4.0, yaw0=-0.4, step_x=0.6, step_y=0.45, step_yaw=0.2, 
 
 
 @pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
-
-
-@pytest.fixture(scope="module")
 def maps(gpu, c1_world):
     capi, ctx = gpu
     m, sf, cfg = c1_world
     return capi.Map(ctx, m, capi.default_params(resolution=cfg["resolution"])), sf, cfg
-
-
-def to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(torch.device("cuda", 0))
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
 
 
 def score_dev(gm, scan, poses=None, lattice=None, stride=8, stream=None, ctx=None, want_pairs=True):

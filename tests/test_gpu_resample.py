@@ -11,32 +11,18 @@ import pytest
 from ndt_slam_amd import replay, synth
 from ndt_slam_amd.pose_estimator import Pose2D, Scan2D
 from test_resample_capacity import adversarial_scans
+from gpu_support import gpu, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 LAUNCH = (0.05, 0.25)                      # ndt_mapping.launch: space, space_thre
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
-
-
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def resample_on_device(capi, ctx, scans, space, space_thre):
     """resample_batch_dev on a list of [n_i, 2] float64 scans -> (list of float64 results, list of float32 results,
     out offsets, statuses)."""
     import torch
-    scans = [np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in scans]
     B = len(scans)
-    raw = np.concatenate(scans)
-    off = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+    raw, off = capi.pack_scans(scans, np.float64, offsets_dtype=np.int64)
     cap = capi.resample_capacity(len(raw), space, space_thre)
     d_raw, d_off = to_dev(raw), to_dev(off)
     d64 = torch.full((cap, 2), -1.0, dtype=torch.float64, device="cuda:0")
@@ -226,8 +212,7 @@ def ulp_distance(a, b):
 
 def scan_to_map_on_device(capi, ctx, scans, poses):
     import torch
-    off = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
-    xy = np.concatenate(scans).astype(np.float64)
+    xy, off = capi.pack_scans(scans, np.float64, offsets_dtype=np.int64)
     d_out = torch.full((len(xy), 2), np.nan, dtype=torch.float32, device="cuda:0")
     d_xy, d_off, d_p = to_dev(xy), to_dev(off), to_dev(np.asarray(poses, np.float64).reshape(-1, 3))
     torch.cuda.synchronize()
@@ -280,8 +265,7 @@ def test_whole_matchscan_chain_on_the_device(gpu, oracle, c1_world):
         d = np.array([[np.cos(al), np.sin(al)], [-np.sin(al), np.cos(al)]]) @ (np.array(init[:2]) - last[:2])
         cur = np.array([*(prev[:2] + np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]) @ d), prev[2] + 2.0])
         lasts.append(last); prevs.append(prev); curs.append(cur)
-    raw_all = np.concatenate(raws)
-    raw_off = np.concatenate([[0], np.cumsum([len(r) for r in raws])]).astype(np.int64)
+    raw_all, raw_off = capi.pack_scans(raws, np.float64, offsets_dtype=np.int64)
     cap = capi.resample_capacity(len(raw_all), space, space_thre)
     last_cov = np.tile(np.eye(3) * 1e-4, (B, 1, 1))
     dev = "cuda:0"

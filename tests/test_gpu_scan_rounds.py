@@ -11,18 +11,11 @@ from local_map_helpers import host_call, oracle_local_map, room_scans
 from ndt_slam_amd import replay
 from test_gpu_occupancy import centre, check
 from test_gpu_resample import resample_on_device
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 EMPTY = np.zeros((0, 2), np.float32)
 LEAF = 0.05
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def test_prefilter_batch_of_1100_tiny_scans(gpu, oracle):
@@ -33,9 +26,7 @@ def test_prefilter_batch_of_1100_tiny_scans(gpu, oracle):
     sizes[[0, 5, 1023, 1024, 1099]] = 0                                       # empty scans, on both sides of the round's end
     scans = [(rng.normal(size=(int(n), 2)) * 3.0).astype(np.float32) for n in sizes]
     B = len(scans)
-    off = np.zeros(B + 1, np.uint64)
-    off[1:] = np.cumsum(sizes)
-    allp = np.ascontiguousarray(np.concatenate(scans))
+    allp, off = capi.pack_scans(scans)
     out = np.full((len(allp) + 1, 2), np.float32(-777.0))
     ooff = np.full(B + 1, 7, np.uint64)
     ctx.check(capi.lib().ndt_prefilter_batch(ctx.h, allp.ctypes.data, 8, off.ctypes.data, B, ctypes.c_float(LEAF), out.ctypes.data,

@@ -8,19 +8,12 @@ import numpy as np
 import pytest
 
 from session_helpers import ComposedChain, device_cloud, lockstep, same_records, session_logs
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SPECS = ((33, 14), (34, 9), (35, 12), (36, 7), (37, 10))         # (seed, frames) of the five sessions
 STARTS = [0, 0, 3, 0, 0]                                         # session 2 starts late
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a real MI355X"
-    from ndt_slam_amd import capi
-    return capi, capi.Context(0)
 
 
 def launch_params(**kw):

@@ -54,9 +54,9 @@ class Batch:
 
     def __init__(self, parts, inits, shared=False):
         import torch
+        from ndt_slam_amd.capi import pack_scans
         dev = torch.device("cuda", 0)
-        off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
-        self.scans = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+        self.scans, off = pack_scans(parts, offsets_dtype=np.int64)
         self.inits = np.ascontiguousarray(inits, dtype=np.float64)
         self.d_sc = torch.from_numpy(self.scans).to(dev)
         self.d_off = torch.from_numpy(off).to(dev)

@@ -82,9 +82,8 @@ def test_host_map_mirror_matches_the_python_harness_and_the_oracle(tmp_path, ora
         p = Pose2D(*t)
         reg.append(np.stack([p.Rmat[0][0] * s[:, 0] + p.Rmat[0][1] * s[:, 1] + p.tx,
                              p.Rmat[1][0] * s[:, 0] + p.Rmat[1][1] * s[:, 1] + p.ty], 1))
-    off = np.zeros(len(reg) + 1, np.uint64)
-    off[1:] = np.cumsum([len(r) for r in reg])
-    np.concatenate(reg).astype(np.float64).tofile(tmp_path / "xy.f64")
+    xy, off = capi.pack_scans(reg, np.float64)
+    xy.tofile(tmp_path / "xy.f64")
     off.tofile(tmp_path / "off.u64")
     truth.astype(np.float64).tofile(tmp_path / "poses.f64")
     kw = dict(sepThre=3.0, removeMoving=True, LeafSize=0.05, resol=0.05, thre_neighbor=0.2)
