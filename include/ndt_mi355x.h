@@ -345,7 +345,11 @@ int ndt_fitness_at(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_host, 
  * setLeafSize(LeafSize x3), setInputCloud(source_cloud), filter(*filtered_cloud); SURVEY.md 8a row
  * a1 / 8f row f1) on z = 0 clouds: 512-slot direct-mapped voxel history, flush on collision, the
  * rest flushed in slot order -- same centroids (float32 sums in cloud order), same output order.
- * Single scan, host pointers; out_xy_host needs room for n points; *n_out = points written. */
+ * Single scan, host pointers; out_xy_host needs room for n points; *n_out = points written.
+ * A scan that holds a non-finite coordinate, or one with |x / leaf| >= 2^31, gets an unspecified
+ * result (the reference's float -> int conversion is undefined there), but a deterministic one that
+ * stays within the scan's bounds: 1..n points.  Every other scan of a batch is unaffected
+ * (tests/test_gpu_prefilter_families.py::test_an_undefined_scan_is_isolated). */
 int ndt_prefilter(ndt_ctx *ctx, const float *xy_host, size_t n, size_t stride_bytes, float leaf,
                   float *out_xy_host, size_t *n_out);
 /* Batch of B raw scans resident in device memory (points at stride_bytes, raw_offsets[B+1] in
