@@ -152,8 +152,10 @@ def test_rebuild_chains(gpu, oracle, leaf, off):
 @pytest.mark.parametrize("leaf,off", COMBOS, ids=IDS)
 def test_an_evaluation_on_every_cloud(gpu, oracle, leaf, off):
     """One ndt_eval_at per case at a pose that puts a scan of the cloud's own points a fraction of a voxel beside them: pairs
-    equal, score, gradient and Hessian at the tolerances of test_single_evaluation_matches_oracle -- the cell records the
-    match kernel reads are the ones export showed.
+    equal, score, gradient and Hessian at the tolerances of test_single_evaluation_matches_oracle -- the centroid grid and
+    the record array in HBM are the ones export showed.  (ndt_eval_at's kernel has an empty window: every point reads the HBM
+    tables, global_pairs / load_rec_global.  The 48-byte LDS records the match kernel stages from them, fill_window_fetch, are
+    held by tests/test_gpu_match_window_geometry.py.)
     The `leaves` cases with eig_mult 0 and no identity start hold voxels whose inverse covariance is not finite
     (leaf_finalize's third return; they stay in the search set, as in PCL).  A pair with such a voxel has a NaN exponent and
     is dropped by updateDerivatives' check -- or, for the diagonal line's (inf, -inf, inf) and a point on its far side, an

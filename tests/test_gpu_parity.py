@@ -471,6 +471,8 @@ def test_c1_matches_oracle_with_same_step_sequence(gpu, oracle, c1_world):
         assert len(traces[b]) == len(tr)
         assert traces[b][:, 0] == pytest.approx(tr[:, 0], rel=1e-8, abs=1e-12)     # step lengths
         assert traces[b][:, 1] == pytest.approx(tr[:, 1], rel=1e-10)               # scores
+        for row, want in zip(traces[b], tr):                                       # gradients, at the tolerance of a single evaluation
+            assert row[2:5] == pytest.approx(want[2:5], rel=1e-9, abs=1e-10 * (np.abs(want[2:5]).max() + 1e-300))
         single = gm.align(scan, inits[b])
         assert single.tobytes() == res[b].tobytes()                                # batch == single, deterministic
 
