@@ -567,7 +567,13 @@ typedef struct ndt_session_step {     /* one per session and step, HOST memory *
   int    successful;                  /* matchScan's return value (1 for a first scan) */
   int    status;                      /* NDT_OK, or NDT_E_ARG for a raw scan with a non-finite coordinate: that session alone
                                          skips the step; also NDT_E_ARG (stepped = 1) when the newest scan triple spans more
-                                         than 2^30 voxels: that session's clouds of this step are empty and its map is kept */
+                                         than 2^30 voxels: that session's clouds of this step are empty and its map is kept;
+                                         or the code ndt_map_build_batch_dev gives the session's new local map on its own
+                                         (stepped = 1; NDT_E_GRID: a voxel grid beyond 2^28 cells, NDT_E_ARG: no finite
+                                         point): pose, scans and clouds of the step are as computed, the session's map is
+                                         left exactly as it was (a session without a map stays without one) until a later
+                                         local map builds.  Either way that session alone is concerned: every other
+                                         session steps as in a set without it, and the call returns NDT_OK */
   int    submap;                      /* index of the session's current submap after the step */
   int    split;                       /* 1: this step closed a submap (src/PointCloudMap.cpp:72-90) */
 } ndt_session_step;

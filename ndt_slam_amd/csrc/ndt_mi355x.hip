@@ -1240,8 +1240,12 @@ static int check_build_batch(ndt_ctx *ctx, const float *const *xy, const size_t 
 // One set of launches for every map: the bounding boxes (one kernel, ONE read-back and host wait), the grids by the rule of
 // the single-map path (grid_of_box, with each map's previous grid), one job-table upload, then each kernel of the chain once.
 // Each map comes out as ndt_map_build_dev would leave it.
+// map_status == nullptr (the public entry points): all or nothing -- the first map whose box refuses fails the call with
+// nothing built.  map_status != nullptr (the sessions step): n_maps codes; a map whose box refuses (no finite points, a grid
+// beyond 2^28 cells) gets its code, is left exactly as it was (a NULL maps[s] stays NULL) and owns no workgroup of any kernel
+// behind the boxes; every other map is built in the same launches and the call returns NDT_OK.
 static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, size_t stride, int n_maps, const ndt_params *prm,
-                       ndt_map **maps, const std::string &fn) {
+                       ndt_map **maps, const std::string &fn, int *map_status = nullptr) {
   hipStream_t st = ctx->stream;
   const size_t S = (size_t)n_maps, npre = S + 1;
   // staging / device table: [BuildBatch | BoxJob x S | minmax prefixes] [BuildJob x S | prefixes of the other kernels]; the
@@ -1288,6 +1292,8 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
     hpre[k][S] = (unsigned)tot;
     return NDT_OK;
   };
+  std::vector<char> refused(S, 0);                    // (map_status alone: the maps that take no part behind the boxes)
+  size_t n_refused = 0;
   if ((rc = prefixes(kBbMinmax, 256, [&](size_t s) { return minmax_blocks(n[s]); }))) return rc;
   if ((rc = prefixes(kBbCount, 256, [&](size_t s) { return point_blocks(n[s]); }))) return rc;
   if ((rc = prefixes(kBbScatter, 256, [&](size_t s) { return point_blocks(n[s]); }))) return rc;
@@ -1309,33 +1315,46 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
   for (size_t s = 0; s < S; ++s) {
     const std::string which = fn + ": map " + std::to_string(s);
     const unsigned *hb = ctx->h_boxes.p + 16 * s + 4;
-    if (hb[0] == 0xffffffffu) return fail(ctx, NDT_E_ARG, which + ": no finite points");
     const ndt_map *m = maps[s];
     const bool prev = m && m->have_grid && m->grid.inv_leaf == 1.0f / prm[s].resolution;   // (what ndt_map_rebuild_begin would queue ahead)
     bool same = false;
-    if ((rc = grid_of_box(ctx, hb, &prm[s], prev ? &m->grid : nullptr, &grids[s], &same, which))) return rc;
+    rc = hb[0] == 0xffffffffu ? fail(ctx, NDT_E_ARG, which + ": no finite points")
+                              : grid_of_box(ctx, hb, &prm[s], prev ? &m->grid : nullptr, &grids[s], &same, which);
+    if (map_status) map_status[s] = rc;
+    if (rc) {
+      if (!map_status) return rc;
+      refused[s] = 1; ++n_refused; grids[s] = GridDims{};
+    }
     geom.emplace_back(n[s], grids[s]);
   }
-  if ((rc = prefixes(kBbScan, kScanBlock, [&](size_t s) { return geom[s].ntiles; }))) return rc;
+  if (n_refused == S) return NDT_OK;                   // (map_status: nothing to build, nothing queued)
+  if (n_refused) {                                     // a refused map owns no workgroup: zero-width rows of the prefixes
+    if ((rc = prefixes(kBbCount, 256, [&](size_t s) { return refused[s] ? 0 : point_blocks(n[s]); }))) return rc;
+    if ((rc = prefixes(kBbScatter, 256, [&](size_t s) { return refused[s] ? 0 : point_blocks(n[s]); }))) return rc;
+  }
+  if ((rc = prefixes(kBbScan, kScanBlock, [&](size_t s) { return refused[s] ? 0 : geom[s].ntiles; }))) return rc;
   if ((rc = prefixes(kBbOrder, 256, [&](size_t s) {      // (the big voxels' blocks: no more than the map can need, not kBigBlocks for each)
-         return (size_t)geom[s].small_blocks + std::min<size_t>(kBigBlocks, ((size_t)geom[s].big_cap + kBigWavesPerBlock - 1) / kBigWavesPerBlock); })))
+         return refused[s] ? (size_t)0
+                           : (size_t)geom[s].small_blocks + std::min<size_t>(kBigBlocks, ((size_t)geom[s].big_cap + kBigWavesPerBlock - 1) / kBigWavesPerBlock); })))
     return rc;
-  if ((rc = prefixes(kBbFinalize, 256, [&](size_t s) { return geom[s].finalize_blocks; }))) return rc;
+  if ((rc = prefixes(kBbFinalize, 256, [&](size_t s) { return refused[s] ? 0u : geom[s].finalize_blocks; }))) return rc;
 
   // 3. the maps: new ones created, every one's readers waited for as build_begin does, buffers, jobs
   std::vector<ndt_map *> mp(S, nullptr), made;
   auto failed = [&](int code) {                        // a HIP / allocation failure from here on: as ndt_map_build_dev
     for (size_t s = 0; s < S; ++s)
-      if (maps[s]) { mp[s]->have_grid = false; mp[s]->count_clean = false; }
+      if (maps[s] && !refused[s]) { maps[s]->have_grid = false; maps[s]->count_clean = false; }
     for (ndt_map *m : made) ndt_map_destroy(m);
     return code;
   };
   for (size_t s = 0; s < S; ++s) {
+    if (refused[s]) continue;
     if (maps[s]) { mp[s] = maps[s]; continue; }
     if ((rc = new_map(ctx, &mp[s]))) return failed(rc);
     made.push_back(mp[s]);
   }
   for (size_t s = 0; s < S; ++s) {
+    if (refused[s]) continue;
     ndt_map *m = mp[s];
     const BuildGeom &g = geom[s];
     if ((rc = take_over_from_readers(ctx, m, st))) return failed(rc);
@@ -1353,6 +1372,7 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
     m->count_clean = false;
   }
   if ((rc = prefixes(kBbFill, 256, [&](size_t s) {
+         if (refused[s]) return 0;
          const BuildJob &J = hjob[s];
          return grid_for(std::max(std::max(J.npad, J.ntile8), std::max(J.zero_count, J.zero_state)), 256); })))
     return failed(rc);
@@ -1376,6 +1396,7 @@ static int build_batch(ndt_ctx *ctx, const float *const *xy, const size_t *n, si
 
   // 5. the host side of every map
   for (size_t s = 0; s < S; ++s) {
+    if (refused[s]) continue;
     build_requested(mp[s], xy[s], n[s], stride, &prm[s]);
     build_queued(mp[s], grids[s]);
     maps[s] = mp[s];

@@ -566,9 +566,15 @@ int SsStep::close() {
   // the NDT maps of the new local maps (host wait 3: the bounding boxes)
   if (!bxy.empty()) {
     std::vector<ndt_params> bp(bxy.size(), s->prm.match);
-    const int rc = ndt_map_build_batch_dev(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data());
-    for (size_t k = 0; k < bwho.size(); ++k) s->ses[(size_t)bwho[k]].map = rc == NDT_OK ? bmaps[k] : s->ses[(size_t)bwho[k]].map;
-    if (rc) return rc;
+    // a build refused for one session (NDT_E_GRID: its local map spans more than 2^28 cells) costs that session alone: its
+    // record takes the code, its map stays exactly as it was (none stays none), every other map is built in the same launches
+    std::vector<int> bst(bxy.size(), NDT_OK);
+    SS_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data(), "ndt_map_build_batch_dev"));
+    SS_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data(), "ndt_map_build_batch_dev", bst.data()));
+    for (size_t k = 0; k < bwho.size(); ++k) {
+      if (bst[k] == NDT_OK) s->ses[(size_t)bwho[k]].map = bmaps[k];
+      else out[bwho[k]].status = bst[k];
+    }
   } else {
     HIP_TRY(ctx, hipStreamSynchronize(st));
   }

@@ -4,6 +4,13 @@ OracleSessions   capi.Sessions' interface on the host: the oracle's match, predi
                  PointCloudMap -- what drives replay.run_sessions_resident without a GPU.
 ComposedChain    the same lockstep step made of the existing *_dev entry points (full recomputation of every scan triple,
                  replay.PointCloudMap's bookkeeping on the host): what ndt_sessions_step must reproduce byte for byte.
+DevForm          ndt_sessions_step_dev's arguments from the host form's: the raw scans and the odometry as device tensors at
+                 a chosen stride behind a non-zero first offset, sentinels wherever the step must not read.
+
+Both stand-ins take allow_item_failures (default off: a refused item is an assertion failure, as before).  On, they follow
+ndt_session_step's per-session rules (include/ndt_mi355x.h): a local-map item whose status is non-zero gives that session
+status NDT_E_ARG with empty clouds and its map kept; a refused map build gives the session the build's code and keeps its
+previous map, possibly none.
 """
 import ctypes
 
@@ -29,11 +36,13 @@ def to_map_frame(lps, pose):
 class OracleSessions:
     """n sessions with the interface of capi.Sessions (step, global_map, close), on the host."""
 
-    def __init__(self, oracle, capi, n, p, arith="oracle"):
+    def __init__(self, oracle, capi, n, p, arith="oracle", allow_item_failures=False):
         """arith: "oracle" -- prediction and fusion by oracle.predict / oracle.fuse (C, the reference's expression order,
         what the device kernels restate); "replay" -- by replay's numpy mirrors calMotion / calPredPose / PoseFuser, the
         arithmetic of SlamLauncher itself (the two differ in the last bits of a 3x3 product)."""
         self.o, self.capi, self.n, self.p, self.arith = oracle, capi, n, p, arith
+        self.tolerant = allow_item_failures
+        self.maps = [None] * n                          # (tolerant: the map a session keeps across a refused step)
         self.pcmaps = [replay.PointCloudMap(OracleOps(oracle), sepThre=p["sepThre"], removeMoving=p["removeMoving"],
                                             LeafSize=p["LeafSize"], resol=p["resol"], thre_neighbor=p["thre_neighbor"])
                        for _ in range(n)]
@@ -66,8 +75,13 @@ class OracleSessions:
                 last = pm.getLastPose()
                 motion, pred = o.predict(cur, self.prev_odo[i], (last.tx, last.ty, last.th))
                 filt = o.approx_voxel_filter(lps.astype(np.float32), p["LeafSize"])
-                r = o.Map(np.ascontiguousarray(pm.localMap_cloud, np.float32), self.prm).align(
-                    filt, [pred[0], pred[1], DEG2RAD(pred[2])])
+                if not self.tolerant:
+                    r = o.Map(np.ascontiguousarray(pm.localMap_cloud, np.float32), self.prm).align(
+                        filt, [pred[0], pred[1], DEG2RAD(pred[2])])
+                elif self.maps[i] is None or not len(filt):
+                    r = np.zeros(1, o.RESULT_DTYPE)[0]          # (no map yet, or no points: nothing converged)
+                else:
+                    r = self.maps[i].align(filt, [pred[0], pred[1], DEG2RAD(pred[2])])
                 cost, matched = (float(r["fitness"]) if r["converged"] and r["status"] == 0 else 1e7), 1
                 if self.arith == "oracle":
                     ok, pose, cov = o.fuse(r, pred, motion, (last.tx, last.ty, last.th), self.last_cov[i], self.fprm)
@@ -78,13 +92,37 @@ class OracleSessions:
             n_sub = len(pm.submaps)
             q = Pose2D(*pose)
             pm.addPose(q)
-            pm.addPoints(to_map_frame(lps, pose))
-            pm.setLastPose(q)
-            pm.makeLocalMap()
+            if not self.tolerant:
+                pm.addPoints(to_map_frame(lps, pose))
+                pm.setLastPose(q)
+                pm.makeLocalMap()
+            else:
+                out[i]["status"] = self._tolerant_local_map(pm, i, to_map_frame(lps, pose))
+                pm.setLastPose(q)
             out[i]["pose"], out[i]["cov"], out[i]["cost"] = pose, cov.ravel(), cost
             out[i]["stepped"], out[i]["matched"], out[i]["successful"] = 1, matched, int(ok)
             out[i]["submap"], out[i]["split"] = len(pm.submaps) - 1, int(len(pm.submaps) > n_sub)
         return out
+
+    def _tolerant_local_map(self, pm, i, cloud):
+        """addPoints + makeLocalMap + the map of the new local map, by the per-session rules -> the record's status."""
+        empty = np.zeros((0, 2), np.float32)
+        try:
+            pm.addPoints(cloud)
+        except ValueError:                               # a triple beyond 2^30 voxels: empty clouds, the map kept
+            pm.submaps[-1].setMap(empty, empty)
+            pm.localMap_cloud = empty
+            return self.capi.NDT_E_ARG
+        pm.makeLocalMap()
+        if len(pm.localMap_cloud):
+            try:
+                self.maps[i] = self.o.Map(np.ascontiguousarray(pm.localMap_cloud, np.float32), self.prm)
+            except RuntimeError:                         # a grid beyond 2^28 cells: the map kept
+                return self.capi.NDT_E_GRID
+        return self.capi.NDT_OK
+
+    def has_map(self, i):
+        return self.maps[i] is not None if self.tolerant else len(self.pcmaps[i].localMap_cloud) > 0
 
     def _replay_fuse(self, r, cur, prev, last, last_cov, cost):
         """ScanMatcher.matchScanBegin / matchScanEnd's arithmetic on the record of OracleEstimator's match."""
@@ -145,9 +183,10 @@ class _NoOps:
 class ComposedChain:
     """S sessions stepped through the existing batched *_dev entry points, the arrays in torch tensors."""
 
-    def __init__(self, capi, ctx, S, p):
+    def __init__(self, capi, ctx, S, p, allow_item_failures=False):
         import torch
         self.torch, self.capi, self.ctx, self.S, self.p = torch, capi, ctx, S, p
+        self.tolerant = allow_item_failures
         self.dev = torch.device("cuda", 0)
         self.pcmaps = []
         for _ in range(S):
@@ -256,21 +295,50 @@ class ComposedChain:
         call.run(ctx, p["LeafSize"])
         torch.cuda.synchronize()
         clouds, targets, status = call.results()
-        assert not status.any()
+        if not self.tolerant:
+            assert not status.any()
         toff = call.toff.cpu().numpy()
         ptrs, ns, who = [], [], []
+        empty = np.zeros((0, 2), np.float32)
         for k, i in enumerate(stepped):
+            if status[k]:                                  # this session alone: empty clouds, its map kept
+                out[i]["status"] = capi.NDT_E_ARG
+                self.pcmaps[i].setLocalMap(empty, empty, 0)
+                self.p_cloud[i], self.target[i] = empty, empty
+                continue
             n_prev = 0 if items[k][6] is None else len(items[k][6])
             self.pcmaps[i].setLocalMap(clouds[k], targets[k], n_prev)
             self.p_cloud[i], self.target[i] = clouds[k], targets[k]
             if len(targets[k]):
                 ptrs.append(call.target.data_ptr() + 8 * int(toff[k])); ns.append(len(targets[k])); who.append(i)
         if who:
-            built = ctx.build_maps_dev(ptrs, ns, self.params, [self.maps[i] for i in who])
+            try:
+                built = ctx.build_maps_dev(ptrs, ns, self.params, [self.maps[i] for i in who])
+            except capi.NdtError:
+                if not self.tolerant:
+                    raise
+                built = []
+                for ptr, n, i in zip(ptrs, ns, who):     # the batch is all-or-nothing: each map alone, by the same entry point
+                    rc, m = self._build_alone(ptr, n, self.maps[i])
+                    out[i]["status"] = rc
+                    built.append(m)
             for i, m in zip(who, built):
                 self.maps[i] = m
         torch.cuda.synchronize()
         return out
+
+    def _build_alone(self, ptr, n, m):
+        """ndt_map_build_batch_dev on one map -> (its code, the map: rebuilt, new, or on a refusal the one given)."""
+        capi = self.capi
+        xy, nn, P = (ctypes.c_void_p * 1)(ptr), (ctypes.c_size_t * 1)(n), (capi.Params * 1)(self.params)
+        mp = (ctypes.c_void_p * 1)(m.h if m is not None else None)
+        rc = capi.lib().ndt_map_build_batch_dev(self.ctx.h, xy, nn, 8, 1, P, mp)
+        if rc or m is not None:
+            return rc, m
+        return rc, capi.Map.adopt(self.ctx, mp[0], self.params)
+
+    def has_map(self, i):
+        return self.maps[i] is not None
 
     def global_map(self, i):
         pm = self.pcmaps[i]
@@ -282,6 +350,37 @@ class ComposedChain:
             if m is not None:
                 m.close()
         self.maps = [None] * self.S
+
+
+class DevForm:
+    """The arguments of ndt_sessions_step_dev for one step: every scan's points as rows of stride / 8 doubles in one device
+    tensor, `lead` sentinel rows in front (raw_offsets[0] = lead), a sentinel in every pad column, and sentinel rows in the
+    range of every inactive session; the odometry as a device tensor.  The sentinel is finite and far off (a row read by
+    mistake moves a cloud, a box or a match; it does not just raise a status)."""
+    SENTINEL = 4321.0
+
+    def __init__(self, scans, odo, active, stride=24, lead=5, idle_rows=3):
+        import torch
+        assert stride in (16, 24, 32) and lead > 0
+        S, w = len(scans), stride // 8
+        act = [True] * S if active is None else [bool(a) for a in active]
+        rows = [np.full((lead, w), self.SENTINEL)]
+        off = [lead]
+        for i in range(S):
+            pts = np.asarray(scans[i], np.float64).reshape(-1, 2) if act[i] else np.full((idle_rows, 2), self.SENTINEL)
+            r = np.full((len(pts), w), self.SENTINEL)
+            r[:, :2] = pts
+            rows.append(r)
+            off.append(off[-1] + len(pts))
+        rows.append(np.full((2, w), self.SENTINEL))
+        dev = torch.device("cuda", 0)
+        self.stride, self.offsets = stride, np.array(off, np.uint64)
+        self.raw = torch.from_numpy(np.ascontiguousarray(np.concatenate(rows))).to(dev)
+        self.odo = torch.from_numpy(np.ascontiguousarray(odo, np.float64).reshape(S, 3)).to(dev)
+        torch.cuda.synchronize()
+
+    def step(self, ses, active=None):
+        return ses.step_dev(self.raw.data_ptr(), self.stride, self.offsets, self.odo.data_ptr(), active)
 
 
 RECORD_FIELDS = ("pose", "cov", "cost", "stepped", "matched", "successful", "status", "submap", "split")
