@@ -433,7 +433,9 @@ int ndt_fuse_batch_dev(ndt_ctx *ctx, const ndt_result *results_dev, const double
  * (include/ndt_slam/PCFilter.h:29-56, called from Submap::makeMap, src/PointCloudMap.cpp:27): the points
  * of `base` with no point of `list` closer than thre_neighbor (PCLUtil::distance_points' float32
  * distance, include/ndt_slam/PCLUtil.h:21-23, strict <), in input order, packed as float2.
- * out needs room for n_base points; n_list may be 0. */
+ * out needs room for n_base points; n_list may be 0 (list_xy may then be NULL: every point is kept).
+ * Refusals (NDT_E_ARG, nothing written): a NULL context, base_xy, out_xy or n_out, n_base == 0, n_base or n_list above
+ * INT32_MAX, n_list > 0 with a NULL list, a stride below 8, not a multiple of 8, or above UINT32_MAX. */
 int ndt_remove_neighbors(ndt_ctx *ctx, const float *base_xy_host, size_t base_stride_bytes, size_t n_base,
                          const float *list_xy_host, size_t list_stride_bytes, size_t n_list, double thre_neighbor,
                          float *out_xy_host, size_t *n_out);
@@ -451,7 +453,9 @@ int ndt_remove_neighbors_dev(ndt_ctx *ctx, const float *base_xy_dev, size_t base
  * The points come back in INPUT order, packed as float2; PCL returns the same set in the order of its
  * depth-first leaf walk, which nothing downstream depends on (the list only feeds remove_neighborPoint).
  * out needs room for n_test points; n_base may be 0.  NDT_E_ARG when the two clouds span more than 2^30
- * voxels per axis (PCL's own key width is 32 bits). */
+ * voxels per axis (PCL's own key width is 32 bits).
+ * Refusals (NDT_E_ARG, nothing written): a NULL context or array, more than 2^30 points in all, a resol that is not
+ * positive and finite, a stride below 8, not a multiple of 8, or above UINT32_MAX. */
 int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t base_stride_bytes, size_t n_base,
                               const float *test_xy_host, size_t test_stride_bytes, size_t n_test, double resol,
                               float *out_xy_host, size_t *n_out);
@@ -467,7 +471,10 @@ int ndt_difference_extraction_dev(ndt_ctx *ctx, const float *base_xy_dev, size_t
  * `newest`; without: all scans (first submap) or scans 2.. (later ones).  All triples run side by side, one
  * workgroup each.  out needs room for every input point (twice that for n_scans == 1: the reference then
  * appends the lone scan as the first and again as the newest).  resol / thre_neighbor are PCFilter's `resol` (0.05) and `thre_neighbor` (0.1),
- * include/ndt_slam/PCFilter.h:20-23. */
+ * include/ndt_slam/PCFilter.h:20-23.
+ * Refusals (NDT_E_ARG, nothing written): a NULL context or array, n_scans < 1 or above 2^20, offsets that decrease or a scan
+ * above 2^29 points, remove_moving with a resol that is not positive and finite or a thre_neighbor that is not finite, a
+ * stride below 8, not a multiple of 8, or above UINT32_MAX. */
 int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride_bytes, const uint64_t *offsets, int n_scans,
                  int first_submap, int newest, int remove_moving, double resol, double thre_neighbor,
                  float *out_xy_host, size_t *n_out);
@@ -525,7 +532,7 @@ typedef struct ndt_submap_desc {
  * Refusals (NDT_E_ARG, synchronous, nothing written or queued; the text names the first offending submap): a NULL context
  * ("null context", checked first), n_subs < 1, a NULL array (subs, cloud_xy, cloud_off, status; target_xy without
  * target_off or the reverse), a submap with n_scans < 1 or NULL scans_xy / offsets, offsets that decrease or a scan above
- * 2^29 points, a bad stride, remove_moving with a resol that is not positive and finite, n_prev > 0 with NULL prev_xy, a
+ * 2^29 points, a bad stride (below 8, not a multiple of 8, or above UINT32_MAX), remove_moving with a resol that is not positive and finite, n_prev > 0 with NULL prev_xy, a
  * target with leaf <= 0.  A call in which every submap is empty is valid and gives all-zero offsets. */
 int ndt_local_map_batch_dev(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride_bytes, float leaf,
                             float *cloud_xy_dev, uint64_t *cloud_off_dev, float *target_xy_dev, uint64_t *target_off_dev,

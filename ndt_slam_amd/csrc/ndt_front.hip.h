@@ -573,78 +573,3 @@ fuse_kernel(const ndt_result *__restrict__ res, const double *__restrict__ pred_
   if (successful_out) successful_out[b] = successful;
 }
 
-
-// ------------------------------------------------------------------------------------------
-// f3 (the all-pairs step on its own): PCFilter::remove_neighborPoint (include/ndt_slam/PCFilter.h:29-56) -- keep the points
-// of `base` that have no point of `list` closer than thre_neighbor, in input order.  The
-// reference tests every pair (O(n*m) on the CPU, the largest cost outside NDT when moving
-// objects are removed, src/PointCloudMap.cpp:15-39); here one lane per base point walks the list
-// through LDS tiles.  The distance is PCLUtil::distance_points' float32 expression
-// (include/ndt_slam/PCLUtil.h:21-23) compared with the double threshold (through rn_cutoff), so the
-// kept set is identical; a ballot prefix keeps the order.
-// ------------------------------------------------------------------------------------------
-constexpr int kRnBlock = 256, kRnTile = 1024;
-// The reference's test is (double)sqrtf(d2) < thre with d2 the float32 squared distance.  sqrtf is correctly
-// rounded and monotone, so the test equals d2 < cut with cut the smallest float whose square root reaches
-// thre; rn_cutoff finds it on the host (bisection over the float bit patterns), and the device needs no sqrt.
-inline float rn_cutoff(double thre) {
-  if (!(thre > 0.0)) return 0.0f;                                   // nothing is closer than a non-positive bound
-  if (!((double)sqrtf(FLT_MAX) >= thre)) return INFINITY;           // every finite distance is
-  unsigned lo = 0u, hi = 0x7f7fffffu;                               // float bits: (double)sqrtf(hi) >= thre holds
-  while (lo < hi) {
-    const unsigned mid = lo + (hi - lo) / 2;
-    float f; memcpy(&f, &mid, 4);
-    if ((double)sqrtf(f) >= thre) hi = mid; else lo = mid + 1;
-  }
-  float f; memcpy(&f, &lo, 4);
-  return f;
-}
-__device__ __forceinline__ bool rn_near(float2 p, float2 q, float cut) {
-  const float dx = p.x - q.x, dy = p.y - q.y;
-  const float d2 = dx * dx + dy * dy;            // (+ dz*dz with dz = 0 adds nothing)
-  return d2 < cut;
-}
-__global__ void __launch_bounds__(kRnBlock)
-remove_neighbors_flag_kernel(const float *__restrict__ base, size_t bstride, int nb, const float *__restrict__ list,
-                             size_t lstride, int nl, float cut, unsigned char *__restrict__ keep,
-                             int *__restrict__ block_count) {
-  __shared__ float2 tile[kRnTile];
-  __shared__ int wsum[kRnBlock / 64];
-  const int i = blockIdx.x * kRnBlock + threadIdx.x;
-  float2 p = make_float2(0.f, 0.f);
-  if (i < nb) p = load_pt(base, bstride, (size_t)i);
-  bool flag = i < nb;
-  for (int t0 = 0; t0 < nl; t0 += kRnTile) {
-    const int m = min(kRnTile, nl - t0);
-    __syncthreads();
-    for (int j = threadIdx.x; j < m; j += kRnBlock) tile[j] = load_pt(list, lstride, (size_t)(t0 + j));
-    __syncthreads();
-    if (flag) {                                   // (the reference keeps testing; the outcome is the same)
-      bool near = false;
-      for (int j = 0; j < m; ++j) near = near || rn_near(p, tile[j], cut);
-      flag = !near;
-    }
-  }
-  if (i < nb) keep[i] = flag ? 1 : 0;
-  int kept;
-  (void)block_rank<kRnBlock>(flag, wsum, &kept);
-  if (threadIdx.x == 0) block_count[blockIdx.x] = kept;
-}
-// exclusive scan of the block counts (one workgroup), total to *n_out
-__global__ void __launch_bounds__(1024)
-remove_neighbors_scan_kernel(int *__restrict__ block_count, int nblocks, unsigned long long *__restrict__ n_out) {
-  __shared__ unsigned sh[1024 / 64];
-  const unsigned total = block_excl_offsets<1024>(
-      nblocks, sh, [&](int i) { return (unsigned)block_count[i]; }, [&](int i, unsigned off, unsigned) { block_count[i] = (int)off; });
-  if (threadIdx.x == 0) *n_out = (unsigned long long)total;
-}
-__global__ void __launch_bounds__(kRnBlock)
-remove_neighbors_pack_kernel(const float *__restrict__ base, size_t bstride, int nb, const unsigned char *__restrict__ keep,
-                             const int *__restrict__ block_off, float2 *__restrict__ out) {
-  __shared__ int wsum[kRnBlock / 64];
-  const int i = blockIdx.x * kRnBlock + threadIdx.x;
-  const bool flag = i < nb && keep[i];
-  int kept;
-  const int rank = block_rank<kRnBlock>(flag, wsum, &kept);
-  if (flag) out[block_off[blockIdx.x] + rank] = load_pt(base, bstride, (size_t)i);
-}

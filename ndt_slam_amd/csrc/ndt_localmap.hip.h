@@ -37,19 +37,20 @@ struct MmJob {
   unsigned sa, sb;                     // point strides in bytes
   unsigned tab_mask;                   // hash set capacity - 1 (capacity a power of two >= 2 (n0 + n1) + 2)
   unsigned long long *tab;             // preset to kMmEmpty
-  float2 *diff;                        // points of b in new voxels, input order (room for nb)
-  unsigned long long *n_diff;          // their count; ~0 when the clouds span more than 2^30 voxels
-  double res;                          // batched calls (ndt_local_map_batch_dev): the submap's resol ...
-  float cut;                           // ... and its rn_cutoff(thre_neighbor); the single calls pass both as kernel arguments
-};
+  float2 *diff;                        // points of b in new voxels, input order (room for nb) ...
+  unsigned long long *n_diff;          // ... and their count; ~0 when the clouds span more than 2^30 voxels
+  double res;                          // the submap's resol ...
+  float cut;                           // ... and its rn_cutoff(thre_neighbor)
+  unsigned ls;                         // stride of `diff` in bytes: 8, or that of a caller's list (ndt_remove_neighbors_dev:
+};                                     // a job of the list, its count and cut alone, which make_map_diff_kernel never sees)
 
 struct MmUnit {                        // at most kMmUnit consecutive points of the concatenated result
   const float *src; unsigned stride; unsigned n;
   int job;                             // >= 0: points of that triple's middle scan, to be filtered; < 0: copied whole
-  unsigned sub;                        // batched calls: the submap the unit belongs to
+  unsigned sub;                        // the submap the unit belongs to
 };
 
-struct MmSub { unsigned u0, u1; };     // batched calls: the units of a submap are [u0, u1) of the unit table
+struct MmSub { unsigned u0, u1; };     // the units of a submap are [u0, u1) of the unit table
 
 struct MmFrame {
   double minx, miny, maxx, maxy, minz;
@@ -129,16 +130,15 @@ __device__ inline int mm_append4(const bool flag[kMmPer], const float2 p[kMmPer]
   return run;
 }
 
-// kBatch: the triples of every submap of a batched call, each with its own resol (MmJob::res)
-template <bool kBatch>
+// the triples of every submap of a call, each with its own resol (MmJob::res)
 __global__ void __launch_bounds__(kMmBlock)
-make_map_diff_kernel(const MmJob *__restrict__ jobs, double res_arg) {
+make_map_diff_kernel(const MmJob *__restrict__ jobs) {
   __shared__ MmFrame F;
   __shared__ int wcnt[kMmPer][kMmWaves];
   __shared__ unsigned long long ltab[kMmLdsTab];
   __shared__ int lfill, lover;
   const MmJob J = jobs[blockIdx.x];
-  const double res = kBatch ? J.res : res_arg;
+  const double res = J.res;
   const int tid = threadIdx.x, lane = tid & 63;
   const int nA = (int)(J.n0 + J.n1), N = nA + (int)J.nb;
   if (tid == 0) { F.defined = 0; F.nev = 0; F.err = 0; F.from = 0; F.depth = 0; F.first = 0x7fffffff; }
@@ -343,13 +343,36 @@ make_map_diff_kernel(const MmJob *__restrict__ jobs, double res_arg) {
   if (tid == 0) *J.n_diff = (unsigned long long)nd;
 }
 
-// ---- remove_neighborPoint(test, diff) and the concatenation, spread over the chip: the result is cut into
-// units of at most 256 points -- stretches of a scan that is appended whole, or of a middle scan whose points
-// are tested against their triple's difference list (all pairs, float32 distance, strict <; rn_cutoff).
-// kBatch: the units of every submap of a batched call in one grid, the cut-off per submap (MmJob::cut)
-template <bool kBatch>
+// ---- remove_neighborPoint(test, diff) (PCFilter::remove_neighborPoint, include/ndt_slam/PCFilter.h:29-56) and the
+// concatenation, spread over the chip: the result is cut into units of at most 256 points -- stretches of a scan that
+// is appended whole, or of a middle scan whose points are tested against their triple's difference list: all pairs
+// (O(n m) on the CPU, the reference's largest cost outside NDT when moving objects are removed), one lane per point
+// walking the list through LDS tiles, with PCLUtil::distance_points' float32 expression (include/ndt_slam/PCLUtil.h:21-23)
+// and a strict <, so the kept set is identical; a ballot prefix keeps the order.  ndt_remove_neighbors_dev is this
+// step on its own: units over the caller's base cloud, one job whose list is the caller's.
+// The reference's test is (double)sqrtf(d2) < thre with d2 the float32 squared distance.  sqrtf is correctly
+// rounded and monotone, so the test equals d2 < cut with cut the smallest float whose square root reaches
+// thre; rn_cutoff finds it on the host (bisection over the float bit patterns), and the device needs no sqrt.
+inline float rn_cutoff(double thre) {
+  if (!(thre > 0.0)) return 0.0f;                                   // nothing is closer than a non-positive bound
+  if (!((double)sqrtf(FLT_MAX) >= thre)) return INFINITY;           // every finite distance is
+  unsigned lo = 0u, hi = 0x7f7fffffu;                               // float bits: (double)sqrtf(hi) >= thre holds
+  while (lo < hi) {
+    const unsigned mid = lo + (hi - lo) / 2;
+    float f; memcpy(&f, &mid, 4);
+    if ((double)sqrtf(f) >= thre) hi = mid; else lo = mid + 1;
+  }
+  float f; memcpy(&f, &lo, 4);
+  return f;
+}
+__device__ __forceinline__ bool rn_near(float2 p, float2 q, float cut) {
+  const float dx = p.x - q.x, dy = p.y - q.y;
+  const float d2 = dx * dx + dy * dy;            // (+ dz*dz with dz = 0 adds nothing)
+  return d2 < cut;
+}
+// The units of every submap of a call in one grid, the cut-off per submap (MmJob::cut).
 __global__ void __launch_bounds__(kMmUnit)
-make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ units, float cut_arg,
+make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ units,
                      unsigned long long *__restrict__ keepbits, unsigned *__restrict__ unit_cnt) {
   __shared__ float2 tile[kMmTile];
   __shared__ int wsum[kMmUnit / 64];
@@ -360,14 +383,14 @@ make_map_flag_kernel(const MmJob *__restrict__ jobs, const MmUnit *__restrict__ 
   const unsigned long long ndl = *J.n_diff;
   if (ndl == kMmEmpty) { if (tid == 0) unit_cnt[blockIdx.x] = 0xffffffffu; return; }
   const int nd = (int)ndl;
-  const float cut = kBatch ? J.cut : cut_arg;
+  const float cut = J.cut;
   float2 p = make_float2(0.f, 0.f);
   if (tid < (int)U.n) p = load_pt(U.src, U.stride, (size_t)tid);
   bool keep = tid < (int)U.n;
   for (int t0 = 0; t0 < nd; t0 += kMmTile) {
     const int m = min(kMmTile, nd - t0);
     __syncthreads();
-    for (int j = tid; j < m; j += kMmUnit) tile[j] = J.diff[t0 + j];
+    for (int j = tid; j < m; j += kMmUnit) tile[j] = load_pt((const float *)J.diff, J.ls, (size_t)(t0 + j));
     __syncthreads();
     if (keep) {
       bool near = false;
@@ -396,25 +419,14 @@ __device__ __forceinline__ unsigned long long mm_unit_offsets(const unsigned *__
       [&](unsigned k, unsigned long long off, unsigned long long) { unit_off[u0 + k] = off; });
 }
 
-// exclusive scan of the unit counts (one workgroup); total to *n_out, ~0 when a triple failed
-__global__ void __launch_bounds__(1024)
-make_map_offsets_kernel(const unsigned *__restrict__ unit_cnt, int nu, unsigned long long *__restrict__ unit_off,
-                        unsigned long long *__restrict__ n_out) {
-  __shared__ unsigned long long sh[1024 / 64];
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  const unsigned long long total = mm_unit_offsets(unit_cnt, 0u, nu > 0 ? (unsigned)nu : 0u, unit_off, sh, &bad);
-  if (threadIdx.x == 0) *n_out = bad ? kMmEmpty : total;
-}
-
-// Batched calls, first level of the offsets: one workgroup per submap scans the counts of that submap's units
-// (unit_off: relative to the submap's start) and leaves the submap's total in cloud_off[s + 1] -- 0 and
-// status NDT_E_ARG when one of its triples failed.  Second level: make_map_sub_scan_kernel.
+// First level of the offsets: one workgroup per submap scans the counts of that submap's units (unit_off: relative
+// to the submap's start) and leaves the submap's total in cloud_off[s + 1] -- 0 and status NDT_E_ARG when one of
+// its triples failed.  With one submap cloud_off[0 .. 1] is final; with more, make_map_sub_scan_kernel follows.
+// n_out (a call of one submap; may be NULL): the total once more, ~0 for the failed triple.
 __global__ void __launch_bounds__(1024)
 make_map_sub_offsets_kernel(const unsigned *__restrict__ unit_cnt, const MmSub *__restrict__ subs,
                             unsigned long long *__restrict__ unit_off, unsigned long long *__restrict__ cloud_off,
-                            int *__restrict__ status) {
+                            int *__restrict__ status, unsigned long long *__restrict__ n_out) {
   __shared__ unsigned long long sh[1024 / 64];
   __shared__ int bad;
   const MmSub S = subs[blockIdx.x];
@@ -425,6 +437,7 @@ make_map_sub_offsets_kernel(const unsigned *__restrict__ unit_cnt, const MmSub *
     cloud_off[blockIdx.x + 1] = bad ? 0ull : total;
     status[blockIdx.x] = bad ? (int)NDT_E_ARG : (int)NDT_OK;
     if (blockIdx.x == 0) cloud_off[0] = 0ull;
+    if (n_out) *n_out = bad ? kMmEmpty : total;
   }
 }
 
@@ -438,24 +451,19 @@ make_map_sub_scan_kernel(unsigned long long *__restrict__ cloud_off, int n_subs)
       [&](int i, unsigned long long front, unsigned long long v) { cloud_off[i + 1] = front + v; });
 }
 
-// kBatch: a unit's place is its submap's start (cloud_off) + its offset in the submap; a unit of a failed
-// submap writes nothing (n_out is not read)
-template <bool kBatch>
+// a unit's place is its submap's start (cloud_off) + its offset in the submap; a unit of a failed submap writes nothing
 __global__ void __launch_bounds__(kMmUnit)
 make_map_copy_kernel(const MmUnit *__restrict__ units, const unsigned long long *__restrict__ keepbits,
-                     const unsigned long long *__restrict__ unit_off, const unsigned long long *__restrict__ n_out,
-                     float2 *__restrict__ out, const unsigned long long *__restrict__ cloud_off,
-                     const int *__restrict__ status) {
-  if (!kBatch) { if (*n_out == kMmEmpty) return; }
+                     const unsigned long long *__restrict__ unit_off, float2 *__restrict__ out,
+                     const unsigned long long *__restrict__ cloud_off, const int *__restrict__ status) {
   const MmUnit U = units[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  unsigned long long off = unit_off[blockIdx.x];
-  if (kBatch) {
-    if (status[U.sub] != (int)NDT_OK) return;
-    off += cloud_off[U.sub];
-  }
+  float2 p = make_float2(0.f, 0.f);
+  if (tid < (int)U.n) p = load_pt(U.src, U.stride, (size_t)tid);      // (ahead of the status: both loads in flight together)
+  if (status[U.sub] != (int)NDT_OK) return;
+  unsigned long long off = cloud_off[U.sub] + unit_off[blockIdx.x];
   if (U.job < 0) {
-    if (tid < (int)U.n) out[off + tid] = load_pt(U.src, U.stride, (size_t)tid);
+    if (tid < (int)U.n) out[off + tid] = p;
     return;
   }
   const unsigned long long *kb = keepbits + (size_t)blockIdx.x * (kMmUnit / 64);
@@ -466,6 +474,5 @@ make_map_copy_kernel(const MmUnit *__restrict__ units, const unsigned long long 
     off += w < wv ? (unsigned long long)__builtin_popcountll(b) : 0ull;
     mine = w == wv ? b : mine;
   }
-  if ((mine >> lane) & 1ull)
-    out[off + __builtin_popcountll(mine & ((1ull << lane) - 1ull))] = load_pt(U.src, U.stride, (size_t)tid);
+  if ((mine >> lane) & 1ull) out[off + __builtin_popcountll(mine & ((1ull << lane) - 1ull))] = p;      // (a kept lane is below U.n)
 }

@@ -219,8 +219,7 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
   DevBuf<unsigned char> d_rs;                          // resampler: walk outputs at k_max slots per raw point, lengths, piece counts
-  DevBuf<unsigned char> d_rn;                          // neighbour removal: block offsets + keep flags
-  DevBuf<unsigned char> d_mm;                          // local-map assembly: jobs, pieces, voxel sets, lists
+  DevBuf<unsigned char> d_mm;                          // local-map assembly (and the neighbour removal on its own): jobs, units, voxel sets, lists
   StagedUpload<unsigned char> mm_tab;                  // its job table
   StagedUpload<MapView> views_tab;                     // ndt_align_batch_multi_dev: the launch's table of map views
   // ndt_map_build_batch_dev: the scan's ticket (word 0) and 16 words per map from word 16 (map_minmax's running box, result and
@@ -2307,36 +2306,262 @@ int ndt_fuse_batch_dev(ndt_ctx *ctx, const ndt_result *results, const double *pr
   return NDT_OK;
 }
 
+}  // extern "C"
+
 namespace {
+
+// Local-map assembly, one chain for every caller (ndt_localmap.hip.h): the job table (one entry per scan triple), the unit
+// table (256-point stretches of the result) and the submap table are written into pinned memory and uploaded with one copy.
+// Device scratch (ctx->d_mm): [jobs][units][submaps][previous clouds][one count word], then the chain's own (MmScratch).
+// A call describes 0 submaps (ndt_difference_extraction_dev: one job, no units), 1 (ndt_make_map_dev, ndt_remove_neighbors_dev)
+// or many (ndt_local_map_batch_dev, which alone fills the previous clouds); the sessions' step queues the same chain over
+// tables of its own (SsStep::behind).
+size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
+
+// The rules every entry point of the assembly holds its arguments to (each with its own message):
+// MmUnit::stride and MmJob::sa / sb / ls are 32-bit
+bool mm_stride_ok(size_t stride) { return stride >= 8 && !(stride & 7) && stride <= (size_t)UINT32_MAX; }
+bool mm_scan_count_ok(int n_scans) { return n_scans >= 1 && n_scans <= (1 << 20); }
+bool mm_offsets_ok(const uint64_t *offsets, int n_scans) {      // non-decreasing, scans below 2^29 points
+  for (int i = 0; i < n_scans; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)(1u << 29)) return false;
+  return true;
+}
+
+// The jobs of a call (of a step of a session set), still unbound (mm_bind).
+struct MmPlan {
+  std::vector<MmJob> jobs;
+  size_t sa = 8, sb = 8;     // set before the first add()
+  size_t unit_room = 0;
+  size_t n_subs = 0;         // submaps (the tables of MmSub and PfPrev follow the units)
+  size_t tab_words = 0, list_pts = 0;      // over the jobs: the voxel sets' words, the difference lists' points
+  // One triple: base cloud a0 ++ a1, test cloud b.  The one place that sizes a voxel set.
+  void add(const float *a0, const float *a1, const float *b, size_t n0, size_t n1, size_t nb, double res, float cut) {
+    const size_t cap = pow2_at_least(2 * (n0 + n1) + 2);
+    MmJob J{};
+    J.a0 = a0; J.a1 = a1; J.b = b; J.n0 = (unsigned)n0; J.n1 = (unsigned)n1; J.nb = (unsigned)nb;
+    J.sa = (unsigned)sa; J.sb = (unsigned)sb; J.tab_mask = (unsigned)(cap - 1); J.res = res; J.cut = cut; J.ls = sizeof(float2);
+    jobs.push_back(J);
+    tab_words += cap; list_pts += nb;
+  }
+  // A job that is a list for the flag kernel and nothing else: no clouds, no voxel set (a plan of such jobs has
+  // tab_words == 0, and neither the fill nor make_map_diff_kernel is queued); its list and count are the caller's (mm_bind)
+  void add_list(size_t stride, float cut) {
+    MmJob J{};
+    J.cut = cut; J.ls = (unsigned)stride;
+    jobs.push_back(J);
+  }
+};
+
+// The chain's device-only scratch for P's jobs and P.unit_room units, as offsets into the block the caller lays out (behind the
+// uploaded tables in ctx->d_mm, behind the units in a session set's mm)
+struct MmScratch {
+  size_t ucnt = 0, uoff = 0, keep = 0, cnt = 0, tab = 0, diff = 0, coff = 0, stat = 0, nj = 0, nu = 0, tab_words = 0;
+  MmScratch() = default;
+  MmScratch(Regions &R, const MmPlan &P) : nj(P.jobs.size()), nu(P.unit_room), tab_words(P.tab_words) {
+    ucnt = R.take(nu * 4); uoff = R.take(nu * 8); keep = R.take(nu * (kMmUnit / 64) * 8);      // per unit
+    cnt = R.take(nj * 8 + 8); tab = R.take(tab_words * 8); diff = R.take(P.list_pts * 8 + 64);      // difference counts, voxel sets, lists
+    coff = R.take(2 * 8); stat = R.take(4);      // cloud_off[2] and the status of a call whose one submap reports through n_out alone
+  }
+};
+struct MmLayout {
+  size_t o_units = 0, o_subs = 0, o_prev = 0, o_word = 0, o_up = 0;      // o_up: where the uploaded tables end
+  MmScratch x;
+  size_t ns = 0;
+  MmJob *jobs = nullptr; MmUnit *units = nullptr;      // pinned, valid until the next call on this context
+  MmSub *subs = nullptr; PfPrev *prevs = nullptr;      // pinned; prevs: zero unless the caller fills them
+  unsigned long long *word = nullptr;                  // pinned: the count of a caller's list (add_list), zero otherwise
+};
+
+// Jobs [0, nj) get their voxel sets, difference lists and counters in scratch X of the block at d, one behind the other.
+// diff_override / n_diff_override: every list / counter is the caller's instead (one job).
+void mm_bind(MmJob *jobs, size_t nj, char *d, const MmScratch &X, float2 *diff_override = nullptr, unsigned long long *n_diff_override = nullptr) {
+  size_t tw = 0, lp = 0;
+  for (size_t j = 0; j < nj; ++j) {
+    MmJob &J = jobs[j];
+    J.tab = (unsigned long long *)(d + X.tab) + tw;
+    J.diff = diff_override ? diff_override : (float2 *)(d + X.diff) + lp;
+    J.n_diff = n_diff_override ? n_diff_override : (unsigned long long *)(d + X.cnt) + j;
+    tw += (size_t)J.tab_mask + 1; lp += J.nb;
+  }
+}
+
+// One submap's scan triples (added to P) and the pieces of its cloud (appended to `pieces`) in the order
+// Submap::makeMap appends them -- the rule of the assembly of a whole submap; the sessions' step
+// holds the same branches in their incremental form (SsStep::book, ndt_sessions.hip.h).  cut: rn_cutoff(D.thre_neighbor).
+// Returns the units (stretches of kMmUnit points) the pieces take.
+struct MmPiece { const float *p; size_t n; int job; };      // job: the piece's triple in P.jobs, or -1
+size_t submap_pieces(const ndt_submap_desc &D, size_t stride, float cut, MmPlan *P, std::vector<MmPiece> *pieces) {
+  auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
+  auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
+  size_t nu = 0;
+  auto piece = [&](int i, int job) { pieces->push_back({scan_ptr(i), scan_n(i), job}); nu += (scan_n(i) + kMmUnit - 1) / kMmUnit; };
+  if (D.remove_moving) {
+    if (D.first_submap) piece(0, -1);
+    for (int i = 0; i + 2 < D.n_scans; ++i)
+      if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
+        piece(i + 1, (int)P->jobs.size());
+        P->add(scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut);
+      }
+    if (D.newest) piece(D.n_scans - 1, -1);
+  } else {
+    for (int i = D.first_submap ? 0 : 2; i < D.n_scans; ++i) piece(i, -1);
+  }
+  return nu;
+}
+
+size_t submap_points(const ndt_submap_desc &D) {        // points the submap's cloud may hold (the header's capacity rule)
+  const size_t total = (size_t)(D.offsets[D.n_scans] - D.offsets[0]);
+  return D.n_scans == 1 ? 2 * total : total;            // a lone scan is appended twice (first + newest)
+}
+
+// The units of pieces [first, last), which belong to submap `sub`, written from `units` on; returns the end.
+MmUnit *fill_units(MmUnit *units, const MmPiece *first, const MmPiece *last, size_t stride, unsigned sub) {
+  for (const MmPiece *pc = first; pc != last; ++pc)
+    for (size_t o = 0; o < pc->n; o += kMmUnit)
+      *units++ = MmUnit{(const float *)((const char *)pc->p + o * stride), (unsigned)stride,
+                        (unsigned)std::min<size_t>(kMmUnit, pc->n - o), pc->job, sub};
+  return units;
+}
+
+// Lays out ctx->d_mm and the pinned tables, and writes the jobs, bound.  Queues nothing.
+int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, unsigned long long *n_diff_override, MmLayout *Lo) {
+  const size_t nj = P.jobs.size(), nu = P.unit_room, ns = P.n_subs;
+  MmLayout L;
+  Regions R;
+  R.take(nj * sizeof(MmJob));
+  L.o_units = R.take(nu * sizeof(MmUnit)); L.o_subs = R.take(ns * sizeof(MmSub)); L.o_prev = R.take(ns * sizeof(PfPrev));
+  L.o_word = R.take(8);
+  L.o_up = R.end;
+  L.x = MmScratch(R, P);
+  L.ns = ns;
+  int rc;                                            // (the frame around mm_prepare + mm_upload_queue is the caller's)
+  if ((rc = ctx->d_mm.ensure(ctx, R.end))) return rc;
+  if ((rc = ctx->mm_tab.reserve(ctx, L.o_up))) return rc;      // (waits for the previous call's upload)
+  char *h = (char *)ctx->mm_tab.h.p;
+  L.jobs = (MmJob *)h; L.units = (MmUnit *)(h + L.o_units); L.subs = (MmSub *)(h + L.o_subs); L.prevs = (PfPrev *)(h + L.o_prev);
+  L.word = (unsigned long long *)(h + L.o_word);
+  if (nj) memcpy(L.jobs, P.jobs.data(), nj * sizeof(MmJob));
+  memset(h + L.o_prev, 0, L.o_up - L.o_prev);
+  mm_bind(L.jobs, nj, (char *)ctx->d_mm.p, L.x, diff_override, n_diff_override);
+  *Lo = L;
+  return NDT_OK;
+}
+
+// The chain over tables that are on the device (jobs, units, subs) and scratch X of the block at d, for ns = 0, 1 or many
+// submaps: the fill of the voxel sets and the triples' differences, then every kernel once for all submaps, with a status
+// per submap and the offsets in two levels (per submap; over the submaps when there is more than one -- with one, cloud_off[0 .. 1]
+// is final after the first).  The offsets run even with no units.  n_out (one submap; may be NULL): make_map_sub_offsets_kernel.
+int mm_queue(ndt_ctx *ctx, const MmJob *jobs, const MmUnit *units, const MmSub *subs, char *d, const MmScratch &X, size_t ns,
+             float2 *cloud_xy, unsigned long long *cloud_off, int *status, unsigned long long *n_out, hipStream_t st) {
+  const size_t nu = X.nu;
+  unsigned *ucnt = (unsigned *)(d + X.ucnt);
+  unsigned long long *uoff = (unsigned long long *)(d + X.uoff), *keep = (unsigned long long *)(d + X.keep);
+  if (X.tab_words) {      // (jobs with voxel sets: triples, MmPlan::add)
+    HIP_TRY(ctx, hipMemsetAsync(d + X.tab, 0xff, X.tab_words * 8, st));
+    make_map_diff_kernel<<<(unsigned)X.nj, kMmBlock, 0, st>>>(jobs);
+  }
+  if (nu) make_map_flag_kernel<<<(unsigned)nu, kMmUnit, 0, st>>>(jobs, units, keep, ucnt);
+  if (ns) make_map_sub_offsets_kernel<<<(unsigned)ns, 1024, 0, st>>>(ucnt, subs, uoff, cloud_off, status, n_out);
+  if (ns > 1) make_map_sub_scan_kernel<<<1, 1024, 0, st>>>(cloud_off, (int)ns);
+  if (nu) make_map_copy_kernel<<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, cloud_xy, cloud_off, status);
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+// For the callers that stage through ctx->mm_tab (mm_prepare): ONE upload of the tables, then the chain.  A call of one submap
+// that reports through n_out alone leaves cloud_off and status NULL: they are the scratch's.
+int mm_upload_queue(ndt_ctx *ctx, const MmLayout &L, float *cloud_xy, uint64_t *cloud_off, int *status, uint64_t *n_out, hipStream_t st) {
+  char *d = (char *)ctx->d_mm.p;
+  HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, L.o_up, st));
+  return mm_queue(ctx, (const MmJob *)d, (const MmUnit *)(d + L.o_units), (const MmSub *)(d + L.o_subs), d, L.x, L.ns, (float2 *)cloud_xy,
+                  cloud_off ? (unsigned long long *)cloud_off : (unsigned long long *)(d + L.x.coff), status ? status : (int *)(d + L.x.stat),
+                  (unsigned long long *)n_out, st);
+}
+
 // What the neighbour removal refuses of either form (the host form names its own refusals first).
 int remove_neighbors_check(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy, size_t list_stride,
                            size_t n_list, const float *out_xy, const void *n_out) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
   if (!base_xy || n_base == 0 || n_base > (size_t)INT32_MAX || n_list > (size_t)INT32_MAX || (n_list && !list_xy) ||
-      !out_xy || !n_out || base_stride < 8 || (base_stride & 7) || (n_list && (list_stride < 8 || (list_stride & 7))))
+      !out_xy || !n_out || !mm_stride_ok(base_stride) || (n_list && !mm_stride_ok(list_stride)))
     return fail(ctx, NDT_E_ARG, "ndt_remove_neighbors: bad arguments");
   return NDT_OK;
 }
 
-// The three kernels on st, inside the caller's frame (d_rn).
+// The all-pairs step on its own, on st, inside the caller's frame: one submap of units over the base cloud, one job whose
+// list is the caller's and whose count is the uploaded word.
 int queue_remove_neighbors(ndt_ctx *ctx, hipStream_t st, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy,
                            size_t list_stride, size_t n_list, double thre_neighbor, float *out_xy, uint64_t *n_out) {
-  const int nblocks = (int)((n_base + kRnBlock - 1) / kRnBlock);
+  MmPlan P;
+  P.add_list(n_list ? list_stride : sizeof(float2), rn_cutoff(thre_neighbor));
+  P.unit_room = (n_base + kMmUnit - 1) / kMmUnit;
+  P.n_subs = 1;
+  MmLayout L;
   int rc;
-  Regions R;
-  const size_t o_count = R.take((size_t)nblocks * sizeof(int)), o_keep = R.take(n_base + 16);
-  if ((rc = ctx->d_rn.ensure(ctx, R.end))) return rc;
-  int *block_count = R.at<int>(ctx->d_rn.p, o_count);
-  unsigned char *keep = R.at<unsigned char>(ctx->d_rn.p, o_keep);
-  remove_neighbors_flag_kernel<<<nblocks, kRnBlock, 0, st>>>(base_xy, base_stride, (int)n_base, list_xy, list_stride,
-                                                             (int)n_list, rn_cutoff(thre_neighbor), keep, block_count);
-  remove_neighbors_scan_kernel<<<1, 1024, 0, st>>>(block_count, nblocks, (unsigned long long *)n_out);
-  remove_neighbors_pack_kernel<<<nblocks, kRnBlock, 0, st>>>(base_xy, base_stride, (int)n_base, keep, block_count,
-                                                             (float2 *)out_xy);
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = mm_prepare(ctx, P, (float2 *)list_xy, nullptr, &L))) return rc;
+  L.jobs[0].n_diff = (unsigned long long *)((char *)ctx->d_mm.p + L.o_word);
+  *L.word = n_list;
+  const MmPiece base = {base_xy, n_base, 0};
+  fill_units(L.units, &base, &base + 1, base_stride, 0u);
+  L.subs[0] = MmSub{0u, (unsigned)P.unit_room};
+  return mm_upload_queue(ctx, L, out_xy, nullptr, nullptr, n_out, st);
+}
+
+// What the difference extraction refuses of either form (the host form names its own refusals first).
+int difference_check(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy, size_t test_stride,
+                     size_t n_test, double resol, const float *out_xy, const void *n_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if ((n_base && !base_xy) || !test_xy || n_test == 0 || n_base + n_test > (size_t)(1u << 30) || !out_xy || !n_out ||
+      !mm_stride_ok(base_stride) || !mm_stride_ok(test_stride) || !(resol > 0.0) || !std::isfinite(resol))
+    return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
   return NDT_OK;
 }
+
+// One job on st, inside the caller's frame, no units and no submap: the difference list goes straight to out_xy, its count to n_out.
+int queue_difference(ndt_ctx *ctx, hipStream_t st, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy,
+                     size_t test_stride, size_t n_test, double resol, float *out_xy, uint64_t *n_out) {
+  MmPlan P;
+  P.sa = base_stride; P.sb = test_stride;
+  P.add(base_xy, base_xy, test_xy, n_base, 0, n_test, resol, 0.f);
+  MmLayout L;
+  int rc;
+  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, (unsigned long long *)n_out, &L))) return rc;
+  return mm_upload_queue(ctx, L, nullptr, nullptr, nullptr, nullptr, st);
+}
+
+// What the assembly of one submap refuses of either form (the host form names its own refusals first).
+int make_map_check(ndt_ctx *ctx, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans, int remove_moving,
+                   double resol, double thre_neighbor, const float *out_xy, const void *n_out) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  if (!scans_xy || !offsets || !mm_scan_count_ok(n_scans) || !out_xy || !n_out || !mm_stride_ok(stride) ||
+      (remove_moving && (!(resol > 0.0) || !std::isfinite(resol) || !std::isfinite(thre_neighbor))))
+    return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
+  if (!mm_offsets_ok(offsets, n_scans))
+    return fail(ctx, NDT_E_ARG, "ndt_make_map: offsets must be non-decreasing, scans below 2^29 points");
+  return NDT_OK;
+}
+
+// One submap on st, inside the caller's frame; scans_xy is device memory, offsets host memory.
+int queue_make_map(ndt_ctx *ctx, hipStream_t st, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans,
+                   int first_submap, int newest, int remove_moving, double resol, double thre_neighbor, float *out_xy, uint64_t *n_out) {
+  MmPlan P;
+  P.sa = P.sb = stride;
+  P.n_subs = 1;
+  const ndt_submap_desc D = {scans_xy, offsets, n_scans, first_submap, newest, remove_moving, resol, thre_neighbor, nullptr, 0};
+  std::vector<MmPiece> pieces;
+  P.unit_room = submap_pieces(D, stride, rn_cutoff(thre_neighbor), &P, &pieces);
+  MmLayout L;
+  int rc;
+  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
+  fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
+  L.subs[0] = MmSub{0u, (unsigned)P.unit_room};
+  return mm_upload_queue(ctx, L, out_xy, nullptr, nullptr, n_out, st);
+}
+
 }  // namespace
+
+extern "C" {
 
 int ndt_remove_neighbors_dev(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *list_xy,
                              size_t list_stride, size_t n_list, double thre_neighbor, float *out_xy, uint64_t *n_out,
@@ -2371,221 +2596,6 @@ int ndt_remove_neighbors(ndt_ctx *ctx, const float *base_xy_host, size_t base_st
   return read_back_counted<1>(fr, ctx->d_off.p, d_out, sizeof(float2), out_xy_host, n_out, no_check);
 }
 
-}  // extern "C"
-
-namespace {
-
-// Local-map assembly: the job table (one entry per scan triple) and the unit table (256-point stretches of the
-// result) are written into pinned memory, uploaded with one copy and consumed by the kernels of
-// ndt_localmap.hip.h.  Device scratch (ctx->d_mm): [jobs][units][submaps][previous clouds], then the chain's own (MmScratch)
-// (the submap and previous-cloud tables only in a batched call, ndt_local_map_batch_dev: the upload ends behind them).
-size_t pow2_at_least(size_t v) { size_t c = 64; while (c < v) c <<= 1; return c; }
-
-// The scan triples of a call (of a step of a session set), their jobs still unbound (mm_bind).
-struct MmPlan {
-  std::vector<MmJob> jobs;
-  size_t sa = 8, sb = 8;     // set before the first add()
-  size_t unit_room = 0;
-  size_t n_subs = 0;         // batched calls: submaps (the tables of MmSub and PfPrev follow the units)
-  size_t tab_words = 0, list_pts = 0;      // over the jobs: the voxel sets' words, the difference lists' points
-  // One triple: base cloud a0 ++ a1, test cloud b; res, cut: batched calls.  The one place that sizes a voxel set.
-  void add(const float *a0, const float *a1, const float *b, size_t n0, size_t n1, size_t nb, double res = 0.0, float cut = 0.f) {
-    const size_t cap = pow2_at_least(2 * (n0 + n1) + 2);
-    MmJob J{};
-    J.a0 = a0; J.a1 = a1; J.b = b; J.n0 = (unsigned)n0; J.n1 = (unsigned)n1; J.nb = (unsigned)nb;
-    J.sa = (unsigned)sa; J.sb = (unsigned)sb; J.tab_mask = (unsigned)(cap - 1); J.res = res; J.cut = cut;
-    jobs.push_back(J);
-    tab_words += cap; list_pts += nb;
-  }
-};
-
-// The chain's device-only scratch for P's jobs and P.unit_room units, as offsets into the block the caller lays out (behind the
-// uploaded tables in ctx->d_mm, behind the units in a session set's mm)
-struct MmScratch {
-  size_t ucnt = 0, uoff = 0, keep = 0, cnt = 0, tab = 0, diff = 0, nj = 0, nu = 0, tab_words = 0;
-  MmScratch() = default;
-  MmScratch(Regions &R, const MmPlan &P) : nj(P.jobs.size()), nu(P.unit_room), tab_words(P.tab_words) {
-    ucnt = R.take(nu * 4); uoff = R.take(nu * 8); keep = R.take(nu * (kMmUnit / 64) * 8);      // per unit
-    cnt = R.take(nj * 8 + 8); tab = R.take(tab_words * 8); diff = R.take(P.list_pts * 8 + 64);      // difference counts, voxel sets, lists
-  }
-};
-struct MmLayout {
-  size_t o_units = 0, o_subs = 0, o_prev = 0, o_up = 0;      // o_up: where the uploaded tables end
-  MmScratch x;
-  MmJob *jobs = nullptr; MmUnit *units = nullptr;      // pinned, valid until the next call on this context
-  MmSub *subs = nullptr; PfPrev *prevs = nullptr;      // pinned (batched calls)
-};
-
-// Jobs [0, nj) get their voxel sets, difference lists and counters in scratch X of the block at d, one behind the other.
-// diff_override / n_diff_override: every list / counter is the caller's instead (ndt_difference_extraction_dev: one job).
-void mm_bind(MmJob *jobs, size_t nj, char *d, const MmScratch &X, float2 *diff_override = nullptr, unsigned long long *n_diff_override = nullptr) {
-  size_t tw = 0, lp = 0;
-  for (size_t j = 0; j < nj; ++j) {
-    MmJob &J = jobs[j];
-    J.tab = (unsigned long long *)(d + X.tab) + tw;
-    J.diff = diff_override ? diff_override : (float2 *)(d + X.diff) + lp;
-    J.n_diff = n_diff_override ? n_diff_override : (unsigned long long *)(d + X.cnt) + j;
-    tw += (size_t)J.tab_mask + 1; lp += J.nb;
-  }
-}
-
-// One submap's scan triples (added to P) and the pieces of its cloud (appended to `pieces`) in the order
-// Submap::makeMap appends them -- the rule of the single and the batched assembly, of the whole submap; the sessions' step
-// holds the same branches in their incremental form (SsStep::book, ndt_sessions.hip.h).  cut: rn_cutoff(D.thre_neighbor).
-// Returns the units (stretches of kMmUnit points) the pieces take.
-struct MmPiece { const float *p; size_t n; int job; };      // job: the piece's triple in P.jobs, or -1
-size_t submap_pieces(const ndt_submap_desc &D, size_t stride, float cut, MmPlan *P, std::vector<MmPiece> *pieces) {
-  auto scan_ptr = [&](int i) { return (const float *)((const char *)D.scans_xy + (size_t)D.offsets[i] * stride); };
-  auto scan_n = [&](int i) { return (size_t)(D.offsets[i + 1] - D.offsets[i]); };
-  size_t nu = 0;
-  auto piece = [&](int i, int job) { pieces->push_back({scan_ptr(i), scan_n(i), job}); nu += (scan_n(i) + kMmUnit - 1) / kMmUnit; };
-  if (D.remove_moving) {
-    if (D.first_submap) piece(0, -1);
-    for (int i = 0; i + 2 < D.n_scans; ++i)
-      if (scan_n(i + 1)) {      // an empty middle scan contributes nothing
-        piece(i + 1, (int)P->jobs.size());
-        P->add(scan_ptr(i), scan_ptr(i + 2), scan_ptr(i + 1), scan_n(i), scan_n(i + 2), scan_n(i + 1), D.resol, cut);
-      }
-    if (D.newest) piece(D.n_scans - 1, -1);
-  } else {
-    for (int i = D.first_submap ? 0 : 2; i < D.n_scans; ++i) piece(i, -1);
-  }
-  return nu;
-}
-
-// The units of pieces [first, last), which belong to submap `sub`, written from `units` on; returns the end.
-MmUnit *fill_units(MmUnit *units, const MmPiece *first, const MmPiece *last, size_t stride, unsigned sub) {
-  for (const MmPiece *pc = first; pc != last; ++pc)
-    for (size_t o = 0; o < pc->n; o += kMmUnit)
-      *units++ = MmUnit{(const float *)((const char *)pc->p + o * stride), (unsigned)stride,
-                        (unsigned)std::min<size_t>(kMmUnit, pc->n - o), pc->job, sub};
-  return units;
-}
-
-// Lays out ctx->d_mm and the pinned tables, and writes the jobs, bound.  Queues nothing.
-int mm_prepare(ndt_ctx *ctx, const MmPlan &P, float2 *diff_override, unsigned long long *n_diff_override, MmLayout *Lo) {
-  const size_t nj = P.jobs.size(), nu = P.unit_room, ns = P.n_subs;
-  MmLayout L;
-  Regions R;
-  R.take(nj * sizeof(MmJob));
-  L.o_units = R.take(nu * sizeof(MmUnit)); L.o_subs = R.take(ns * sizeof(MmSub)); L.o_prev = R.take(ns * sizeof(PfPrev));
-  L.o_up = align_up(R.end, 64);
-  L.x = MmScratch(R, P);
-  int rc;                                            // (the frame around mm_prepare + mm_run is the caller's)
-  if ((rc = ctx->d_mm.ensure(ctx, R.end))) return rc;
-  if ((rc = ctx->mm_tab.reserve(ctx, L.o_up))) return rc;      // (waits for the previous call's upload)
-  char *h = (char *)ctx->mm_tab.h.p;
-  L.jobs = (MmJob *)h; L.units = (MmUnit *)(h + L.o_units); L.subs = (MmSub *)(h + L.o_subs); L.prevs = (PfPrev *)(h + L.o_prev);
-  if (nj) memcpy(L.jobs, P.jobs.data(), nj * sizeof(MmJob));
-  mm_bind(L.jobs, nj, (char *)ctx->d_mm.p, L.x, diff_override, n_diff_override);
-  *Lo = L;
-  return NDT_OK;
-}
-
-// fills the voxel sets, uploads jobs + units and queues the kernels; out/n_out are only used when there are units
-int mm_run(ndt_ctx *ctx, const MmLayout &L, double resol, double thre, float *out_xy, uint64_t *n_out, hipStream_t st) {
-  char *d = (char *)ctx->d_mm.p;
-  const size_t nj = L.x.nj, nu = L.x.nu;
-  if (L.x.tab_words) HIP_TRY(ctx, hipMemsetAsync(d + L.x.tab, 0xff, L.x.tab_words * 8, st));
-  const size_t bytes = nu ? L.o_units + nu * sizeof(MmUnit) : nj * sizeof(MmJob);
-  if (bytes) HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, bytes, st));
-  if (nj) make_map_diff_kernel<false><<<(unsigned)nj, kMmBlock, 0, st>>>((const MmJob *)d, resol);
-  if (nu) {
-    const MmUnit *units = (const MmUnit *)(d + L.o_units);
-    unsigned *ucnt = (unsigned *)(d + L.x.ucnt);
-    unsigned long long *uoff = (unsigned long long *)(d + L.x.uoff), *keep = (unsigned long long *)(d + L.x.keep);
-    make_map_flag_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>((const MmJob *)d, units, rn_cutoff(thre), keep, ucnt);
-    make_map_offsets_kernel<<<1, 1024, 0, st>>>(ucnt, (int)nu, uoff, (unsigned long long *)n_out);
-    make_map_copy_kernel<false><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, (const unsigned long long *)n_out,
-                                                                 (float2 *)out_xy, nullptr, nullptr);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return NDT_OK;
-}
-
-// The batched chain over tables that are on the device (jobs, units, subs) and scratch X of the block at d: the fill of
-// the voxel sets, then every kernel once for all submaps, with the offsets in two levels (per submap, then over the
-// submaps) and a status per submap.  The two offset kernels run even with no units.
-int mm_queue_batch(ndt_ctx *ctx, const MmJob *jobs, const MmUnit *units, const MmSub *subs, char *d, const MmScratch &X, size_t ns,
-                   float2 *cloud_xy, unsigned long long *cloud_off, int *status, hipStream_t st) {
-  const size_t nj = X.nj, nu = X.nu;
-  unsigned *ucnt = (unsigned *)(d + X.ucnt);
-  unsigned long long *uoff = (unsigned long long *)(d + X.uoff), *keep = (unsigned long long *)(d + X.keep);
-  if (X.tab_words) HIP_TRY(ctx, hipMemsetAsync(d + X.tab, 0xff, X.tab_words * 8, st));
-  if (nj) make_map_diff_kernel<true><<<(unsigned)nj, kMmBlock, 0, st>>>(jobs, 0.0);
-  if (nu) make_map_flag_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(jobs, units, 0.f, keep, ucnt);
-  make_map_sub_offsets_kernel<<<(unsigned)ns, 1024, 0, st>>>(ucnt, subs, uoff, cloud_off, status);
-  make_map_sub_scan_kernel<<<1, 1024, 0, st>>>(cloud_off, (int)ns);
-  if (nu) make_map_copy_kernel<true><<<(unsigned)nu, kMmUnit, 0, st>>>(units, keep, uoff, nullptr, cloud_xy, cloud_off, status);
-  HIP_TRY(ctx, hipGetLastError());
-  return NDT_OK;
-}
-
-// The batched form (ndt_local_map_batch_dev): ONE upload of jobs + units + the submap tables, then the chain.
-int mm_run_batch(ndt_ctx *ctx, const MmLayout &L, size_t ns, float *cloud_xy, uint64_t *cloud_off, int *status, hipStream_t st) {
-  char *d = (char *)ctx->d_mm.p;
-  HIP_TRY(ctx, ctx->mm_tab.upload(d, 0, L.o_prev + ns * sizeof(PfPrev), st));
-  return mm_queue_batch(ctx, (const MmJob *)d, (const MmUnit *)(d + L.o_units), (const MmSub *)(d + L.o_subs), d, L.x, ns,
-                        (float2 *)cloud_xy, (unsigned long long *)cloud_off, status, st);
-}
-
-// What the difference extraction refuses of either form (the host form names its own refusals first).
-int difference_check(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy, size_t test_stride,
-                     size_t n_test, double resol, const float *out_xy, const void *n_out) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if ((n_base && !base_xy) || !test_xy || n_test == 0 || n_base + n_test > (size_t)(1u << 30) || !out_xy || !n_out ||
-      base_stride < 8 || (base_stride & 7) || test_stride < 8 || (test_stride & 7) || !(resol > 0.0) || !std::isfinite(resol))
-    return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
-  return NDT_OK;
-}
-
-// One job on st, inside the caller's frame: the difference list goes straight to out_xy, its count to n_out.
-int queue_difference(ndt_ctx *ctx, hipStream_t st, const float *base_xy, size_t base_stride, size_t n_base, const float *test_xy,
-                     size_t test_stride, size_t n_test, double resol, float *out_xy, uint64_t *n_out) {
-  MmPlan P;
-  P.sa = base_stride; P.sb = test_stride;
-  P.add(base_xy, base_xy, test_xy, n_base, 0, n_test);
-  MmLayout L;
-  int rc;
-  if ((rc = mm_prepare(ctx, P, (float2 *)out_xy, (unsigned long long *)n_out, &L))) return rc;
-  return mm_run(ctx, L, resol, 0.0, nullptr, nullptr, st);
-}
-
-// What the assembly of one submap refuses of either form (the host form names its own refusals first).
-int make_map_check(ndt_ctx *ctx, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans, int remove_moving,
-                   double resol, double thre_neighbor, const float *out_xy, const void *n_out) {
-  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!scans_xy || !offsets || n_scans <= 0 || n_scans > (1 << 20) || !out_xy || !n_out || stride < 8 || (stride & 7) ||
-      (remove_moving && (!(resol > 0.0) || !std::isfinite(resol) || !std::isfinite(thre_neighbor))))
-    return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
-  for (int i = 0; i < n_scans; ++i)
-    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)(1u << 29))
-      return fail(ctx, NDT_E_ARG, "ndt_make_map: offsets must be non-decreasing, scans below 2^29 points");
-  return NDT_OK;
-}
-
-// One submap on st, inside the caller's frame; scans_xy is device memory, offsets host memory.
-int queue_make_map(ndt_ctx *ctx, hipStream_t st, const float *scans_xy, size_t stride, const uint64_t *offsets, int n_scans,
-                   int first_submap, int newest, int remove_moving, double resol, double thre_neighbor, float *out_xy, uint64_t *n_out) {
-  MmPlan P;
-  P.sa = P.sb = stride;
-  // (one submap; its resol and thre_neighbor reach the kernels as arguments, mm_run: the jobs' own copies stay unset)
-  const ndt_submap_desc D = {scans_xy, offsets, n_scans, first_submap, newest, remove_moving, 0.0, 0.0, nullptr, 0};
-  std::vector<MmPiece> pieces;
-  const size_t nu = submap_pieces(D, stride, 0.f, &P, &pieces);
-  P.unit_room = nu;
-  MmLayout L;
-  int rc;
-  if ((rc = mm_prepare(ctx, P, nullptr, nullptr, &L))) return rc;
-  fill_units(L.units, pieces.data(), pieces.data() + pieces.size(), stride, 0u);
-  if (nu == 0) HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(uint64_t), st));
-  return mm_run(ctx, L, resol, thre_neighbor, out_xy, n_out, st);
-}
-
-}  // namespace
-
-extern "C" {
-
 int ndt_difference_extraction_dev(ndt_ctx *ctx, const float *base_xy, size_t base_stride, size_t n_base,
                                   const float *test_xy, size_t test_stride, size_t n_test, double resol, float *out_xy,
                                   uint64_t *n_out, void *stream) {
@@ -2600,8 +2610,8 @@ int ndt_difference_extraction(ndt_ctx *ctx, const float *base_xy_host, size_t ba
                               const float *test_xy_host, size_t test_stride, size_t n_test, double resol,
                               float *out_xy_host, size_t *n_out) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if ((n_base && !base_xy_host) || (n_test && !test_xy_host) || !out_xy_host || !n_out || base_stride < 8 ||
-      (base_stride & 7) || test_stride < 8 || (test_stride & 7))
+  if ((n_base && !base_xy_host) || (n_test && !test_xy_host) || !out_xy_host || !n_out || !mm_stride_ok(base_stride) ||
+      !mm_stride_ok(test_stride))
     return fail(ctx, NDT_E_ARG, "ndt_difference_extraction: bad arguments");
   if (n_test == 0) { *n_out = 0; return NDT_OK; }
   int rc = difference_check(ctx, base_xy_host, base_stride, n_base, test_xy_host, test_stride, n_test, resol, out_xy_host, n_out);
@@ -2637,7 +2647,7 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
                  int first_submap, int newest, int remove_moving, double resol, double thre_neighbor,
                  float *out_xy_host, size_t *n_out) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
-  if (!scans_xy_host || !offsets || n_scans <= 0 || !out_xy_host || !n_out || stride < 8 || (stride & 7))
+  if (!scans_xy_host || !offsets || n_scans <= 0 || !out_xy_host || !n_out || !mm_stride_ok(stride))
     return fail(ctx, NDT_E_ARG, "ndt_make_map: bad arguments");
   const size_t total = (size_t)offsets[n_scans] - (size_t)offsets[0];
   if (total == 0) { *n_out = 0; return NDT_OK; }
@@ -2646,9 +2656,9 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
   CallFrame fr(ctx);
   if ((rc = fr.open())) return rc;
   hipStream_t st = fr.st;
-  const size_t out_pts = n_scans == 1 ? 2 * total : total;      // a lone scan is appended twice (first + newest)
+  const ndt_submap_desc whole = {scans_xy_host, offsets, n_scans, first_submap, newest, remove_moving, resol, thre_neighbor, nullptr, 0};
   Regions R;
-  const size_t o_in = R.take(total * stride), o_out = R.take(out_pts * sizeof(float2) + 64);
+  const size_t o_in = R.take(total * stride), o_out = R.take(submap_points(whole) * sizeof(float2) + 64);
   if ((rc = ctx->d_scan.ensure(ctx, R.end))) return rc;
   if ((rc = ctx->d_off.ensure(ctx, 4))) return rc;
   float *d_in = R.at<float>(ctx->d_scan.p, o_in), *d_out = R.at<float>(ctx->d_scan.p, o_out);
@@ -2669,11 +2679,6 @@ int ndt_make_map(ndt_ctx *ctx, const float *scans_xy_host, size_t stride, const 
 
 namespace {
 
-size_t submap_points(const ndt_submap_desc &D) {        // points the submap's cloud may hold (the header's capacity rule)
-  const size_t total = (size_t)(D.offsets[D.n_scans] - D.offsets[0]);
-  return D.n_scans == 1 ? 2 * total : total;
-}
-
 // The synchronous refusals of a batched assembly: nothing changed, nothing queued.
 int check_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf, const void *cloud_xy,
                           const void *cloud_off, const void *target_xy, const void *target_off, const void *status,
@@ -2685,13 +2690,12 @@ int check_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs,
   for (int s = 0; s < n_subs; ++s) {
     const ndt_submap_desc &D = subs[s];
     const std::string which = fn + ": submap " + std::to_string(s);
-    if (D.n_scans < 1 || D.n_scans > (1 << 20)) return fail(ctx, NDT_E_ARG, which + ": n_scans < 1 (or above 2^20)");
+    if (!mm_scan_count_ok(D.n_scans)) return fail(ctx, NDT_E_ARG, which + ": n_scans < 1 (or above 2^20)");
     if (!D.scans_xy || !D.offsets) return fail(ctx, NDT_E_ARG, which + ": NULL scans_xy or offsets");
-    for (int i = 0; i < D.n_scans; ++i)
-      if (D.offsets[i + 1] < D.offsets[i] || D.offsets[i + 1] - D.offsets[i] > (uint64_t)(1u << 29))
-        return fail(ctx, NDT_E_ARG, which + ": offsets must be non-decreasing, scans below 2^29 points");
+    if (!mm_offsets_ok(D.offsets, D.n_scans))
+      return fail(ctx, NDT_E_ARG, which + ": offsets must be non-decreasing, scans below 2^29 points");
   }
-  if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, fn + ": bad stride (need stride_bytes >= 8 and % 8 == 0)");
+  if (!mm_stride_ok(stride)) return fail(ctx, NDT_E_ARG, fn + ": bad stride (need stride_bytes >= 8, % 8 == 0 and below 2^32)");
   for (int s = 0; s < n_subs; ++s) {
     const ndt_submap_desc &D = subs[s];
     const std::string which = fn + ": submap " + std::to_string(s);
@@ -2739,7 +2743,7 @@ int queue_local_map_batch(ndt_ctx *ctx, hipStream_t st, const ndt_submap_desc *s
     L.subs[s].u1 = (unsigned)(u - L.units);
     L.prevs[s] = PfPrev{subs[s].n_prev ? subs[s].prev_xy : nullptr, (unsigned long long)subs[s].n_prev};
   }
-  if ((rc = mm_run_batch(ctx, L, (size_t)n_subs, cloud_xy, cloud_off, status, st))) return rc;
+  if ((rc = mm_upload_queue(ctx, L, cloud_xy, cloud_off, status, nullptr, st))) return rc;
   if (target_xy) {
     // Submap::filterPoints of every cloud, behind its previous submap's cloud: cloud_xy / cloud_off are the filter's input form
     const PfPrev *d_prev = (const PfPrev *)((const char *)ctx->d_mm.p + L.o_prev);

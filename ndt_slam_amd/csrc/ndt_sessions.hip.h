@@ -493,8 +493,8 @@ int SsStep::behind() {
     const MmJob *d_jobs = (const MmJob *)(db + o_jobs); const MmSub *d_subs = (const MmSub *)(db + o_subs);
     SS_TRY(s->tri_off.ensure(ctx, nt + 1)); SS_TRY(s->tri_status.ensure(ctx, nt));
     session_units_kernel<<<(unsigned)nt, 256, 0, st>>>(d_jobs, d_subs, (MmUnit *)(dm + m_units));
-    SS_TRY(mm_queue_batch(ctx, d_jobs, (const MmUnit *)(dm + m_units), d_subs, dm, X, nt, s->tri_xy.p,
-                          (unsigned long long *)s->tri_off.p, s->tri_status.p, st));
+    SS_TRY(mm_queue(ctx, d_jobs, (const MmUnit *)(dm + m_units), d_subs, dm, X, nt, s->tri_xy.p,
+                    (unsigned long long *)s->tri_off.p, s->tri_status.p, nullptr, st));
   }
   session_plan_kernel<<<1, 1024, 0, st>>>((const SsPlan *)(db + o_plan), S, s->tri_xy.p, (const unsigned long long *)s->tri_off.p,
                                           s->tri_status.p, s->plen.p, s->cloud[cur].p, (unsigned long long *)s->cloud_off.p,

@@ -198,3 +198,143 @@ def test_make_map_is_repeatable_and_reuses_its_buffers(ctx, oracle):
     for _ in range(2):
         for s, r in zip(sets, refs):
             assert ctx.make_map(s, True, True, True, 0.05, 0.2).tobytes() == r.tobytes()
+
+
+# ---- the device forms' own contract: the count word, nothing behind the count, nothing after a failed triple ----
+
+CANARY = np.float32(-4242.0)
+WORD = 0x5a5a5a5a5a5a            # what a count word holds before a call
+BAD_STRIDE = 2 ** 32 + 8         # strides are 32-bit on the device: refused, not truncated
+
+
+class DevCall:
+    """Device buffers of one ndt_make_map_dev / ndt_difference_extraction_dev call: canaries in the result and a
+    canary in the count word; `points` go up at `stride` bytes per point, the bytes between them filled too."""
+
+    def __init__(self, points, stride, room):
+        import torch
+        host = np.full((max(len(points), 1), stride // 4), CANARY)
+        host[:len(points), :2] = points
+        self.pts = torch.from_numpy(host).cuda()
+        self.out = torch.full((room + 1, 2), float(CANARY), dtype=torch.float32, device="cuda")
+        self.cnt = torch.full((1,), WORD, dtype=torch.int64, device="cuda")
+
+    def result(self):
+        """(count word as int64 -- UINT64_MAX reads -1 --, the points it counts); everything behind them is untouched"""
+        n, out = int(self.cnt.item()), self.out.cpu().numpy()
+        kept = max(n, 0)
+        assert (out[kept:] == CANARY).all()
+        return n, out[:kept]
+
+
+def run_make_map_dev(ctx, scans, first, newest, remove, resol=0.05, thre=0.1, stride=8):
+    import torch
+    from ndt_slam_amd import capi
+    packed, off = capi.pack_scans(scans)
+    call = DevCall(packed, stride, 2 * len(packed))
+    torch.cuda.synchronize()
+    ctx.make_map_dev(call.pts.data_ptr(), stride, off, first, newest, remove, resol, thre, call.out.data_ptr(), call.cnt.data_ptr())
+    torch.cuda.synchronize()
+    return call.result()
+
+
+def test_make_map_dev_beyond_the_span_leaves_nothing_behind(ctx, oracle):
+    rng = np.random.default_rng(61)
+    scans = submap_scans(rng, 3, 55, 5)
+    far = [scans[0], scans[1].copy(), scans[2]]
+    far[1][len(far[1]) // 2] = (1e9, 0.0)
+    n, pts = run_make_map_dev(ctx, far, True, True, True)
+    assert n == -1 and len(pts) == 0                      # UINT64_MAX, no point written
+    n, pts = run_make_map_dev(ctx, scans, True, True, True)
+    ref = oracle.make_map(scans, True, True, True, 0.05, 0.1)
+    assert n == len(ref) and pts.tobytes() == ref.tobytes()
+
+
+def test_make_map_dev_with_no_unit_writes_a_zero_count(ctx):
+    rng = np.random.default_rng(62)
+    empty = np.zeros((0, 2), np.float32)
+    assert run_make_map_dev(ctx, [empty, empty, empty], True, True, True)[0] == 0
+    two = submap_scans(rng, 2, 60, 5)
+    assert run_make_map_dev(ctx, two, False, False, True)[0] == 0
+
+
+@pytest.mark.parametrize("stride", [8, 16])
+def test_difference_extraction_dev_count_word_and_list(ctx, oracle, stride):
+    import torch
+    from ndt_slam_amd import capi
+    rng = np.random.default_rng(63)
+    base, test = scene(rng, 300, 200)
+    far = test.copy()
+    far[100] = (1e9, 0.0)
+    ref = expect_difference(oracle, base, test, 0.05)
+    d_base = DevCall(base, stride, 0)
+    for t, want in ((test, len(ref)), (far, -1)):
+        call = DevCall(t, stride, len(t))
+        torch.cuda.synchronize()
+        ctx.check(capi.lib().ndt_difference_extraction_dev(ctx.h, d_base.pts.data_ptr(), stride, len(base), call.pts.data_ptr(), stride,
+                                                           len(t), 0.05, call.out.data_ptr(), call.cnt.data_ptr(), None),
+                  "ndt_difference_extraction_dev")
+        torch.cuda.synchronize()
+        n = int(call.cnt.item())
+        assert n == want
+        if n >= 0:
+            n, pts = call.result()
+            assert pts.tobytes() == ref.tobytes() and 0 < n < len(t)
+
+
+def test_one_submap_batch_between_two_single_calls(ctx, oracle):
+    """ndt_make_map_dev, ndt_local_map_batch_dev with one submap and no target, ndt_make_map_dev again, queued on the
+    context's stream without a wait in between: they share the chain's scratch and hand the staged tables over."""
+    import torch
+    from ndt_slam_amd import capi
+    rng = np.random.default_rng(64)
+    sets = [submap_scans(rng, n, w, m) for n, w, m in ((4, 300, 12), (5, 520, 20), (3, 150, 6))]
+    refs = [oracle.make_map(s, True, True, True, 0.05, 0.1) for s in sets]
+    packs = [capi.pack_scans(s) for s in sets]
+    calls = [DevCall(p, 8, len(p)) for p, _ in packs]
+    coff = torch.full((2,), WORD, dtype=torch.int64, device="cuda")
+    status = torch.full((1,), 99, dtype=torch.int32, device="cuda")
+    desc = capi.SubmapDesc(calls[1].pts.data_ptr(), packs[1][1].ctypes.data, len(sets[1]), 1, 1, 1, 0.05, 0.1, None, 0)
+    torch.cuda.synchronize()
+
+    def single(k):
+        ctx.make_map_dev(calls[k].pts.data_ptr(), 8, packs[k][1], True, True, True, 0.05, 0.1, calls[k].out.data_ptr(),
+                         calls[k].cnt.data_ptr())
+    single(0)
+    ctx.local_maps_dev([desc], 0.05, calls[1].out.data_ptr(), coff.data_ptr(), None, None, status.data_ptr())
+    single(2)
+    torch.cuda.synchronize()
+    assert coff.tolist() == [0, len(refs[1])] and status.tolist() == [0]
+    calls[1].cnt.fill_(len(refs[1]))                       # (the batched call reports through cloud_off)
+    for call, ref in zip(calls, refs):
+        n, pts = call.result()
+        assert n == len(ref) and pts.tobytes() == ref.tobytes()
+
+
+def test_a_stride_beyond_32_bits_is_refused(ctx):
+    """Every entry point of the assembly, host and device form: NDT_E_ARG, nothing written (host arrays serve both
+    forms: a refusal reads none of them)."""
+    from ndt_slam_amd import capi
+    import ctypes as C
+    L = capi.lib()
+    pts = np.zeros((8, 2), np.float32)
+    off = np.array([0, 3, 6, 8], np.uint64)
+
+    def refused(fn, *args):
+        out, cnt = np.full((20, 2), CANARY), np.full(4, WORD, np.uint64)
+        status = np.full(1, 99, np.int32)
+        mine = {"out": out, "cnt": cnt, "status": status}
+        assert fn(*[mine[a].ctypes.data_as(t) if isinstance(a, str) else a for a, t in zip(args, fn.argtypes)]) == capi.NDT_E_ARG
+        assert (out == CANARY).all() and (cnt == WORD).all() and status[0] == 99
+
+    p = pts.ctypes.data
+    for dev in ((), (None,)):
+        sfx = "_dev" if dev else ""
+        refused(getattr(L, "ndt_make_map" + sfx), ctx.h, p, BAD_STRIDE, off.ctypes.data, 3, 1, 1, 1, 0.05, 0.1, "out", "cnt", *dev)
+        for bs, ts in ((BAD_STRIDE, 8), (8, BAD_STRIDE)):
+            refused(getattr(L, "ndt_difference_extraction" + sfx), ctx.h, p, bs, 4, p, ts, 4, 0.05, "out", "cnt", *dev)
+            refused(getattr(L, "ndt_remove_neighbors" + sfx), ctx.h, p, bs, 4, p, ts, 4, 0.1, "out", "cnt", *dev)
+        descs = (capi.SubmapDesc * 1)(capi.SubmapDesc(p, off.ctypes.data, 3, 1, 1, 1, 0.05, 0.1, None, 0))
+        refused(getattr(L, "ndt_local_map_batch" + sfx), ctx.h, descs, 1, BAD_STRIDE, C.c_float(0.05), "out", "cnt", None, None,
+                "status", *dev)
+        assert "bad stride" in L.ndt_last_error(ctx.h).decode()

@@ -40,7 +40,7 @@ def test_prefilter_batch_of_1100_tiny_scans(gpu, oracle):
 
 
 def test_remove_neighbors_with_more_than_1024_blocks(gpu, oracle):
-    """remove_neighbors_scan_kernel: 1025 blocks of 256 base points."""
+    """make_map_sub_offsets_kernel through ndt_remove_neighbors: 1025 units of 256 base points in its one submap."""
     capi, ctx = gpu
     rng = np.random.default_rng(262145)
     nb = 262145 + 7
@@ -67,7 +67,7 @@ def big_submap(oracle):
 
 
 def test_make_map_of_more_than_1024_units(gpu, big_submap):
-    """make_map_offsets_kernel."""
+    """make_map_sub_offsets_kernel through ndt_make_map: the one submap of a single call (no second level)."""
     capi, ctx = gpu
     item, ref = big_submap
     got = ctx.make_map(*item[:6])
@@ -75,7 +75,7 @@ def test_make_map_of_more_than_1024_units(gpu, big_submap):
 
 
 def test_local_maps_item_of_more_than_1024_units(gpu, oracle, big_submap):
-    """make_map_sub_offsets_kernel: the same submap as one item of a batched call, a small one on either side."""
+    """make_map_sub_offsets_kernel with a second level behind it: the same submap as one item of a batched call, a small one on either side."""
     capi, ctx = gpu
     item, ref = big_submap
     small = (room_scans(np.random.default_rng(5), 4, 300, 15), True, True, True, 0.05, 0.1, None)
