@@ -92,8 +92,8 @@ def capacities(items):
     return cloud, cloud + sum(0 if it[6] is None else len(it[6]) for it in items)
 
 
-def host_call(capi, ctx, items, leaf, want_target=True):
-    """ndt_local_map_batch on host arrays -> (rc, clouds, targets or None, status)."""
+def host_call(capi, ctx, items, leaf, want_target=True, offsets=False):
+    """ndt_local_map_batch on host arrays -> (rc, clouds, targets or None, status); offsets: then (cloud_off, target_off) too."""
     S = len(items)
     descs = (capi.SubmapDesc * S)()
     keep = []
@@ -120,6 +120,8 @@ def host_call(capi, ctx, items, leaf, want_target=True):
     if want_target:
         assert np.all(target[int(toff[S]):] == np.float32(-777.0)) and int(toff[S]) <= tc
         targets = [target[int(toff[s]):int(toff[s + 1])].copy() for s in range(S)]
+    if offsets:
+        return rc, clouds, targets, status, (coff, toff)
     return rc, clouds, targets, status
 
 

@@ -3,6 +3,7 @@ independent numpy statement of the voxel lattice, and Submap::makeMap's bookkeep
 import numpy as np
 import pytest
 
+from local_map_workloads import replay_difference
 from oracle import ndt_oracle as O
 
 
@@ -27,45 +28,6 @@ def test_octree_matches_lattice(seed):
     idx = O.difference_indices(base, test, 0.05)
     assert np.array_equal(np.sort(idx), lattice_difference(base, test, 0.05))
     assert len(np.unique(idx)) == len(idx)
-
-
-def replay_difference(base, test, r):
-    """The octree's voxel lattice by replaying its bounding-box growth point by point (a second, loop-level
-    statement of adoptBoundingBoxToPoint + genOctreeKeyforPoint in three dimensions, z = 0): every point's key is
-    taken in the frame of the moment it is inserted and moved to the final frame by the shifts of the later
-    doublings.  Returns the indices of the test points whose (x, y, z) key no base point has."""
-    eps = float(np.finfo(np.float32).eps)
-    mn = mx = None
-    depth = 0
-    shift = np.zeros(3, np.int64)
-    recs = []                                  # (key in its frame, shift at insertion)
-    for p in list(base) + list(test):
-        p3 = np.array([float(p[0]), float(p[1]), 0.0])
-        if not np.all(np.isfinite(p3)):
-            recs.append(None)
-            continue
-        while True:
-            if mn is None:
-                mn, mx = p3 - r / 2, p3 + r / 2
-                side = 2.0 * r
-                for a in range(3):
-                    over = (side - (mx[a] - mn[a])) / 2.0
-                    if over > eps:
-                        mn[a] -= over; mx[a] += over
-                depth = 1
-            up = p3 >= mx
-            if not (np.any(p3 < mn) or np.any(up)):
-                break
-            side = float(1 << depth) * r
-            for a in range(3):
-                if not up[a]:
-                    mn[a] -= side; shift[a] += 1 << depth
-            depth += 1
-            mx = mn + (float(1 << depth) * r - eps)
-        recs.append((((p3 - mn) / r).astype(np.int64), shift.copy()))
-    keys = [None if q is None else tuple(q[0] + (shift - q[1])) for q in recs]
-    occ = set(k for k in keys[:len(base)] if k is not None)
-    return np.array([i for i, k in enumerate(keys[len(base):]) if k is not None and k not in occ], dtype=np.int64)
 
 
 @pytest.mark.parametrize("resol,span", [(0.05, 5.0), (0.03, 5.0), (0.3, 20.0), (0.02, 40.0), (0.07, 9.0), (0.013, 3.0)])
