@@ -584,7 +584,7 @@ typedef struct ndt_session_step {     /* one per session and step, HOST memory *
   int    submap;                      /* index of the session's current submap after the step */
   int    split;                       /* 1: this step closed a submap (src/PointCloudMap.cpp:72-90) */
 } ndt_session_step;
-typedef struct ndt_sessions_stats {   /* of the most recent step */
+typedef struct ndt_sessions_stats {   /* of the most recent step or ndt_sessions_correct */
   uint64_t h2d_bytes, d2h_bytes;      /* bytes the step copied to and from the device */
   int host_waits;                     /* times the step waited for the device on the host */
   int triples_run;                    /* scan triples the step computed (at most one per stepped session) */
@@ -615,7 +615,7 @@ int ndt_sessions_step(ndt_sessions *s, const double *raw_xy_host, size_t stride_
 int ndt_sessions_step_dev(ndt_sessions *s, const double *raw_xy_dev, size_t stride_bytes,
                           const uint64_t *raw_offsets_host, const double *odo_dev,
                           const unsigned char *active, ndt_session_step *out_host);
-/* Views of the resident state of session i, valid until the next step: the local map (PointCloudMap::localMap_cloud,
+/* Views of the resident state of session i, valid until the next step or ndt_sessions_correct: the local map (PointCloudMap::localMap_cloud,
  * src/PointCloudMap.cpp:119-134; packed float2 in device memory) with the NDT map built from it, and the current submap's
  * cloud (Submap::p_cloud after makeMap, src/PointCloudMap.cpp:15-39).  Before the session's first step: no points, no map. */
 int ndt_sessions_local_map(const ndt_sessions *s, int i, const float **xy_dev, size_t *n, const ndt_map **map);
@@ -846,7 +846,9 @@ int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsi
  * PointCloudMap::remakeMaps moves every map point from its old scan pose to its new one (src/PointCloudMap.cpp:136-170).  Its
  * back end (PoseGraph, SlamBackEnd) is absent from the reference tree; these calls are that step for S graphs at once.  Loop
  * DETECTION is the caller's, with what exists (ndt_align_batch_multi_dev against old submaps' maps, ndt_relocalize,
- * ndt_fit_points_batch); an ndt_sessions set's own resident state is not rewritten by these calls.
+ * ndt_fit_points_batch).  ndt_pg_optimize_batch and ndt_repose_points work on the caller's arrays; an ndt_sessions set's own
+ * resident state takes an adjusted trajectory through ndt_sessions_correct (at the end of this section), and gives the
+ * trajectory a graph is built from through ndt_sessions_trajectory.
  *
  * Conventions are those of the f2 rows: poses are (tx, ty, th[deg]) double triples, covariances and information matrices are
  * in (m, m, rad), output headings are wrapped into [-180, 180) as MyUtil::add_angle does (src/MyUtil.cpp:4-11).
@@ -931,6 +933,45 @@ int ndt_repose_points_dev(ndt_ctx *ctx, const float *xy_dev, size_t stride_bytes
 /* The same from host memory (src/PointCloudMap.cpp:147-154); synchronous.  Only the points of the segments are read and written. */
 int ndt_repose_points(ndt_ctx *ctx, const float *xy_host, size_t stride_bytes, const uint64_t *seg_offsets_host, int n_segs,
                       const double *old_poses_host, const double *new_poses_host, float *out_xy_host, size_t out_stride_bytes);
+
+/* Session i's trajectory as of now (host only, no device work): poses_host[3 * k] = (tx, ty, th[deg]) of its k-th stepped scan
+ * (the step records' `pose`; after ndt_sessions_correct, the corrected ones).  sub_first[m] = cntS of submap m
+ * (src/PointCloudMap.cpp:72-90; n_submaps = closed + 1 entries, the last one the current submap's), sub_anchor[m] = the scan
+ * whose pose pair moves submap m's closed cloud in ndt_sessions_correct: cntS + (cntE - cntS) / 2, with the newest scan as the
+ * current submap's cntE, and cntS for a submap that closed without a scan of its own (cntE < cntS).  *store_first = index of
+ * the first scan held in the current submap's scan store: the store's scans are the tail [store_first, n_scans) of the stepped
+ * scans, the two carried-over scans of a split first (src/PointCloudMap.cpp:80-83).  A call with poses_host == NULL returns
+ * the sizes (*n_scans, *n_submaps, *store_first).  Any other output may be NULL.  capacity in poses.  NDT_E_ARG: a NULL set,
+ * an index outside it, a capacity below n_scans. */
+int ndt_sessions_trajectory(const ndt_sessions *s, int i, double *poses_host, size_t capacity, size_t *n_scans,
+                            int *sub_first, int *sub_anchor, int *n_submaps, size_t *store_first);
+/* PointCloudMap::remakeMaps + ScanMatcher::remakePoseArray (src/PointCloudMap.cpp:136-170, src/FrontEnd.cpp:37-41) for
+ * n_corr sessions of a resident set in one set of launches.  new_poses_host[c]: n_poses[c] x 3 doubles, the whole adjusted
+ * trajectory of session which[c]; n_poses[c] must equal that session's n_scans (a stale trajectory is refused).  For each
+ * of them, with old pose = the stored trajectory and new pose = the argument:
+ *   - every scan of the current submap's store (the carried-over copies included) is moved in place by its own pair, every
+ *     closed submap's cloud by the pair of its anchor scan (sub_anchor above: a closed cloud is a set of voxel centroids
+ *     without a scan id, so it takes one rigid motion) -- ndt_repose_points' arithmetic to the bit, a bit-equal pair leaves
+ *     the bytes alone;
+ *   - the current submap's cloud is computed again from the moved scans, every triple of it, as ndt_local_map_batch_dev
+ *     computes it; the local map is the previous closed cloud (moved) followed by the pre-filter of the new cloud, and the
+ *     NDT map is rebuilt in place from it.  The state is then what the composed chain of ndt_sessions_step's comment holds
+ *     after the same correction, and every later step equals that chain's, byte for byte;
+ *   - the session's last pose becomes new_poses[last] and the stored trajectory the new one; the last covariance, the last
+ *     odometry pose and the travelled distance (atd: the reference does not recompute it) are untouched.
+ * status_host[c]: NDT_OK; NDT_E_GRID / NDT_E_ARG as ndt_map_build_batch_dev gives the new local map on its own (the map is
+ * left as it was, as in a step); NDT_E_ARG when a recomputed triple spans more than 2^30 voxels: both views of that session
+ * are empty, its map is kept, its points and trajectory are moved all the same, and no equality with the chain is claimed
+ * for it afterwards.  Either way the call returns NDT_OK and no other session is concerned.  Sessions not named keep every
+ * byte.  The views of ndt_sessions_local_map / _submap_cloud taken before the call are invalid after it, for every session.
+ * The number of kernels, copies and host waits (two) depends neither on n_corr nor on a submap's length;
+ * ndt_sessions_get_stats then describes this call (sessions_stepped = sessions corrected, triples_run = triples recomputed).
+ * Refusals (NDT_E_ARG, synchronous, nothing changed, the text names the first offending entry): a NULL set ("null session
+ * set"), NULL arrays, n_corr < 1, a session outside the set or one that has not started, the same session twice, a NULL
+ * trajectory, n_poses[c] different from the session's scan count, a non-finite pose (the text names session and scan), an
+ * open ndt_map_rebuild_begin.  NDT_E_HIP: a dead set; a HIP failure inside the call leaves the set dead, as in a step. */
+int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses_host,
+                         const size_t *n_poses, int *status_host);
 
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the

@@ -250,6 +250,8 @@ PROTOTYPES = {
     "ndt_pg_optimize_batch": [_vp, _vp, _vp, _vp, _vp, _i, _P(PgParams), _vp],
     "ndt_repose_points_dev": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp],
     "ndt_repose_points": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz],
+    "ndt_sessions_trajectory": [_vp, _i, _vp, _sz, _P(_sz), _vp, _vp, _P(_i), _P(_sz)],
+    "ndt_sessions_correct": [_vp, _vp, _i, _vp, _vp, _vp],
     "ndt_kernel_timing": [_vp, _i, _P(_f), _P(_f)],
     "ndt_launch_interval": [_vp, _i, _P(_f)],
     "ndt_ctx_wait_launch": [_vp, _i, _vp],
@@ -718,6 +720,16 @@ class Context(_Handle):
         return [(cloud[int(coff[s]):int(coff[s + 1])].copy(), target[int(toff[s]):int(toff[s + 1])].copy(), len(keep[s][2]))
                 for s in range(S)]
 
+    def repose_points(self, clouds, old_poses, new_poses):
+        """ndt_repose_points over a list of [n_k, 2] float32 clouds, cloud k moved from old_poses[k] to new_poses[k] (each
+        (tx, ty, th[deg])) -> the list of moved clouds (new arrays): replay.PointCloudMap.remakeMaps' point move."""
+        clouds = list(clouds)
+        if not clouds:
+            return []
+        allp, off = pack_scans(clouds)
+        moved = repose_points(self, allp, off, old_poses, new_poses)
+        return [moved[int(off[k]):int(off[k + 1])].copy() for k in range(len(clouds))]
+
     def local_maps_dev(self, descs, leaf, cloud_ptr, cloud_off_ptr, target_ptr, target_off_ptr, status_ptr, stride=8,
                        stream=None):
         """ndt_local_map_batch_dev: `descs` a list of SubmapDesc (or a ctypes array of them) whose scans_xy / prev_xy are
@@ -893,6 +905,33 @@ class Sessions(_Handle):
         self.ctx.check(lib().ndt_sessions_occ_integrate(self.h, hs, None if w is None else w.ctypes.data, float(max_range2),
                                                         st.ctypes.data), "ndt_sessions_occ_integrate")
         return st[0]
+
+    def trajectory(self, i):
+        """ndt_sessions_trajectory: (poses [n_scans, 3] float64 (tx, ty, th[deg]), sub_first [n_submaps] int32 -- every
+        submap's first scan --, sub_anchor [n_submaps] int32 -- the scan whose pose pair moves the submap's closed cloud in
+        correct() --, store_first: the current submap's scan store holds the scans [store_first, n_scans))."""
+        n, k, first = C.c_size_t(), C.c_int(), C.c_size_t()
+        self.ctx.check(lib().ndt_sessions_trajectory(self.h, i, None, 0, C.byref(n), None, None, C.byref(k), C.byref(first)),
+                       "ndt_sessions_trajectory")
+        poses = np.zeros((n.value, 3), dtype=np.float64)
+        sub_first, sub_anchor = np.zeros(k.value, dtype=np.int32), np.zeros(k.value, dtype=np.int32)
+        buf = poses if n.value else np.zeros((1, 3))           # (a session that has not started: a non-NULL address all the same)
+        self.ctx.check(lib().ndt_sessions_trajectory(self.h, i, buf.ctypes.data, len(buf), C.byref(n), sub_first.ctypes.data,
+                                                     sub_anchor.ctypes.data, C.byref(k), C.byref(first)), "ndt_sessions_trajectory")
+        return poses, sub_first, sub_anchor, first.value
+
+    def correct(self, new_poses):
+        """ndt_sessions_correct: new_poses = {session index: its whole adjusted trajectory [n_scans, 3] (tx, ty, th[deg])}
+        -> {session index: status} (NDT_OK, or the code that session alone got; include/ndt_mi355x.h)."""
+        who = list(new_poses)
+        arrs = [np.ascontiguousarray(new_poses[i], dtype=np.float64).reshape(-1, 3) for i in who]
+        which = np.array(who, dtype=np.int32)
+        ptrs = (C.c_void_p * max(len(who), 1))(*[a.ctypes.data if len(a) else None for a in arrs])
+        ns = np.array([len(a) for a in arrs], dtype=np.uintp)
+        status = np.zeros(max(len(who), 1), dtype=np.int32)
+        self.ctx.check(lib().ndt_sessions_correct(self.h, which.ctypes.data, len(who), ptrs, ns.ctypes.data, status.ctypes.data),
+                       "ndt_sessions_correct")
+        return {i: int(status[c]) for c, i in enumerate(who)}
 
     def stats(self):
         st = SessionsStats()

@@ -2709,9 +2709,11 @@ int check_local_map_batch(ndt_ctx *ctx, const ndt_submap_desc *subs, int n_subs,
 }
 
 // The assembly of every submap (and, with a target, the filter behind it) on st, inside the caller's frame; the scans and
-// previous clouds of `subs` are device memory, its offsets host memory.
+// previous clouds of `subs` are device memory, its offsets host memory.  up_bytes, n_triples (may be NULL): the size of the
+// call's one table upload and the scan triples it computes (a session set's statistics).
 int queue_local_map_batch(ndt_ctx *ctx, hipStream_t st, const ndt_submap_desc *subs, int n_subs, size_t stride, float leaf,
-                          float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status) {
+                          float *cloud_xy, uint64_t *cloud_off, float *target_xy, uint64_t *target_off, int *status,
+                          size_t *up_bytes = nullptr, size_t *n_triples = nullptr) {
   // the triples (jobs) and the pieces of every submap's cloud
   MmPlan P;
   P.sa = P.sb = stride;
@@ -2743,6 +2745,8 @@ int queue_local_map_batch(ndt_ctx *ctx, hipStream_t st, const ndt_submap_desc *s
     L.subs[s].u1 = (unsigned)(u - L.units);
     L.prevs[s] = PfPrev{subs[s].n_prev ? subs[s].prev_xy : nullptr, (unsigned long long)subs[s].n_prev};
   }
+  if (up_bytes) *up_bytes = L.o_up;
+  if (n_triples) *n_triples = P.jobs.size();
   if ((rc = mm_upload_queue(ctx, L, cloud_xy, cloud_off, status, nullptr, st))) return rc;
   if (target_xy) {
     // Submap::filterPoints of every cloud, behind its previous submap's cloud: cloud_xy / cloud_off are the filter's input form
@@ -2986,6 +2990,60 @@ int ndt_sessions_get_stats(const ndt_sessions *s, ndt_sessions_stats *out) {
   if (!out) return fail(s->ctx, NDT_E_ARG, "ndt_sessions_get_stats: NULL out");
   *out = s->stats;
   return NDT_OK;
+}
+
+int ndt_sessions_trajectory(const ndt_sessions *s, int i, double *poses_host, size_t capacity, size_t *n_scans, int *sub_first,
+                            int *sub_anchor, int *n_submaps, size_t *store_first) {
+  const int rc = check_set(s, i, true, "ndt_sessions_trajectory");
+  if (rc) return rc;
+  const SsSession &Q = s->ses[(size_t)i];
+  const size_t n = (size_t)Q.n_poses;
+  if (poses_host && capacity < n)
+    return fail(s->ctx, NDT_E_ARG, "ndt_sessions_trajectory: session " + std::to_string(i) + ": capacity below the trajectory's " +
+                                       std::to_string(n) + " poses");
+  if (n_scans) *n_scans = n;
+  if (n_submaps) *n_submaps = Q.n_closed + 1;
+  if (store_first) *store_first = n - (Q.scan_off.size() - 1);
+  if (!poses_host) return NDT_OK;
+  if (n) memcpy(poses_host, Q.traj.data(), n * 24);
+  for (int m = 0; m <= Q.n_closed; ++m) {
+    if (sub_first) sub_first[m] = Q.sub_first[(size_t)m];
+    if (sub_anchor) sub_anchor[m] = n ? ss_anchor(Q, m) : 0;
+  }
+  return NDT_OK;
+}
+
+int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses_host, const size_t *n_poses,
+                         int *status_host) {
+  int rc = check_set(s, 0, false, "ndt_sessions_correct");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const std::string f("ndt_sessions_correct");
+  if (!which || !new_poses_host || !n_poses || !status_host) return fail(ctx, NDT_E_ARG, f + ": NULL array (which, new_poses, n_poses or status)");
+  if (n_corr < 1) return fail(ctx, NDT_E_ARG, f + ": n_corr < 1");
+  std::vector<int> entry_of((size_t)s->S, -1);
+  for (int c = 0; c < n_corr; ++c) {
+    const int i = which[c];
+    const std::string who = f + ": entry " + std::to_string(c) + ": session " + std::to_string(i);
+    if (i < 0 || i >= s->S) return fail(ctx, NDT_E_ARG, who + " out of range");
+    const SsSession &Q = s->ses[(size_t)i];
+    if (!Q.started) return fail(ctx, NDT_E_ARG, who + " has not started");
+    if (entry_of[(size_t)i] >= 0) return fail(ctx, NDT_E_ARG, who + " is entry " + std::to_string(entry_of[(size_t)i]) + " again");
+    entry_of[(size_t)i] = c;
+    if (!new_poses_host[c]) return fail(ctx, NDT_E_ARG, who + ": NULL trajectory");
+    if (n_poses[c] != (size_t)Q.n_poses)
+      return fail(ctx, NDT_E_ARG, who + ": " + std::to_string(n_poses[c]) + " poses for a trajectory of " + std::to_string(Q.n_poses) +
+                                      " scans (a stale trajectory)");
+    for (size_t k = 0; k < 3 * n_poses[c]; ++k)
+      if (!(std::fabs(new_poses_host[c][k]) <= DBL_MAX)) return fail(ctx, NDT_E_ARG, who + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
+  }
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  rc = ss_correct(s, which, n_corr, new_poses_host, status_host);
+  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
+    s->dead = true;
+    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -494,9 +494,38 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
 }
 
 // remakeMaps' point correction (src/PointCloudMap.cpp:147-154): q = oldPose.relativePoint(p), p' = newPose.globalPoint(q)
-// (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat builds it, fp64 without contraction, rounded once to float32.  One
-// thread per point; a segment per blockIdx.y, as scan_to_map_kernel takes its scans.  A segment whose poses are bit-equal is
-// copied through (left alone when out is xy itself).
+// (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat builds it, fp64 without contraction, rounded once to float32.
+// ReposeMove: what one (old, new) pose pair gives every point of its segment; repose_point: the per-point body -- the one
+// statement of the arithmetic, for repose_points_kernel and the session set's repose_rows_kernel (ndt_sessions.hip.h).
+struct ReposeMove {
+  double tx1, ty1, o00, o01, o10, o11;             // oldPose and its Rmat
+  double tx2, ty2, n00, n01, n10, n11;             // newPose and its Rmat
+  bool same;                                       // the pair is bit-equal: the segment keeps its bytes
+};
+
+__device__ __forceinline__ ReposeMove repose_move(const double *po, const double *pn) {
+  ReposeMove M;
+  M.same = __double_as_longlong(po[0]) == __double_as_longlong(pn[0]) && __double_as_longlong(po[1]) == __double_as_longlong(pn[1]) &&
+           __double_as_longlong(po[2]) == __double_as_longlong(pn[2]);
+  const double a1 = po[2] * M_PI / 180, a2 = pn[2] * M_PI / 180;
+  const double c1 = cos(a1), s1 = sin(a1), c2 = cos(a2), s2 = sin(a2);
+  M.tx1 = po[0]; M.ty1 = po[1]; M.tx2 = pn[0]; M.ty2 = pn[1];
+  M.o00 = c1; M.o01 = -s1; M.o10 = s1; M.o11 = c1;
+  M.n00 = c2; M.n01 = -s2; M.n10 = s2; M.n11 = c2;
+  return M;
+}
+
+__device__ __forceinline__ float2 repose_point(const ReposeMove &M, float fx, float fy) {
+  const double dx = (double)fx - M.tx1, dy = (double)fy - M.ty1;
+  const double lx = dx * M.o00 + dy * M.o10;
+  const double ly = dx * M.o01 + dy * M.o11;
+  const double gx = M.n00 * lx + M.n01 * ly + M.tx2;
+  const double gy = M.n10 * lx + M.n11 * ly + M.ty2;
+  return make_float2((float)gx, (float)gy);
+}
+
+// One thread per point; a segment per blockIdx.y, as scan_to_map_kernel takes its scans.  A segment whose poses are bit-equal
+// is copied through (left alone when out is xy itself).
 __global__ void __launch_bounds__(256)
 repose_points_kernel(const unsigned char *__restrict__ xy, size_t stride, const unsigned long long *__restrict__ offsets, int n_segs,
                      const double *__restrict__ old_poses, const double *__restrict__ new_poses, unsigned char *__restrict__ out,
@@ -504,27 +533,16 @@ repose_points_kernel(const unsigned char *__restrict__ xy, size_t stride, const 
   for (int b = blockIdx.y; b < n_segs; b += gridDim.y) {
     const unsigned long long r0 = offsets[b], r1 = offsets[b + 1];
     if (r0 >= r1) continue;
-    const double *po = old_poses + 3 * (size_t)b, *pn = new_poses + 3 * (size_t)b;
-    const bool same = __double_as_longlong(po[0]) == __double_as_longlong(pn[0]) && __double_as_longlong(po[1]) == __double_as_longlong(pn[1]) &&
-                      __double_as_longlong(po[2]) == __double_as_longlong(pn[2]);
-    if (same && out == xy && out_stride == stride) continue;
-    const double tx1 = po[0], ty1 = po[1], a1 = po[2] * M_PI / 180;
-    const double tx2 = pn[0], ty2 = pn[1], a2 = pn[2] * M_PI / 180;
-    const double c1 = cos(a1), s1 = sin(a1), c2 = cos(a2), s2 = sin(a2);
-    const double o00 = c1, o01 = -s1, o10 = s1, o11 = c1;         // oldPose.Rmat
-    const double n00 = c2, n01 = -s2, n10 = s2, n11 = c2;         // newPose.Rmat
+    const ReposeMove M = repose_move(old_poses + 3 * (size_t)b, new_poses + 3 * (size_t)b);
+    if (M.same && out == xy && out_stride == stride) continue;
     for (unsigned long long i = r0 + blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < r1;
          i += (unsigned long long)gridDim.x * blockDim.x) {
       const float *src = reinterpret_cast<const float *>(xy + i * stride);
       float *dst = reinterpret_cast<float *>(out + i * out_stride);
       const float fx = src[0], fy = src[1];
-      if (same) { dst[0] = fx; dst[1] = fy; continue; }
-      const double dx = (double)fx - tx1, dy = (double)fy - ty1;
-      const double lx = dx * o00 + dy * o10;
-      const double ly = dx * o01 + dy * o11;
-      const double gx = n00 * lx + n01 * ly + tx2;
-      const double gy = n10 * lx + n11 * ly + ty2;
-      dst[0] = (float)gx; dst[1] = (float)gy;
+      if (M.same) { dst[0] = fx; dst[1] = fy; continue; }
+      const float2 g = repose_point(M, fx, fy);
+      dst[0] = g.x; dst[1] = g.y;
     }
   }
 }

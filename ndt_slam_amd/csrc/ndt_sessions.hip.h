@@ -11,10 +11,19 @@
 //   session_plan_kernel       per session: the cloud's length and offset, the append of the new survivors to the cached
 //                             prefix, and the gather table of prefix ++ survivors ++ newest scan
 //   seg_copy_kernel           every move of a step (carried-over scans, closed clouds, gathers): a table of (src, dst, n)
+// and two for ndt_sessions_correct:
+//   repose_rows_kernel        every stored scan and closed cloud of the corrected sessions moved in place from its old pose
+//                             to its new one: a table of (points, n, old pose, new pose), repose_point's arithmetic
+//   session_refill_kernel     per corrected session: the prefix length and its refill from the recomputed cloud (a segment
+//                             for seg_copy_kernel), and the session's row of last_pose
 
 namespace {
 
 struct SsCopy { const float2 *src; float2 *dst; unsigned long long n; };
+struct SsMove { float2 *p; unsigned long long n; double old_pose[3], new_pose[3]; };
+static_assert(sizeof(SsMove) == 64, "one 64-byte row per moved range");
+// one corrected session: its index in the set, where its prefix lies, what of its cloud is the newest scan, its new last pose
+struct SsFix { int ses, with_newest; unsigned long long newest_n; float2 *prefix; double pose[3]; };
 
 // what the host knows of one session's cloud at a step: Submap::makeMap's branches (src/PointCloudMap.cpp:15-39) with the
 // prefix = [scans[0] of a first submap] ++ the survivors of every triple computed so far (remove_moving), or the scans
@@ -41,6 +50,40 @@ seg_copy_kernel(const SsCopy *__restrict__ tab, int n_seg) {
          j += (unsigned long long)gridDim.x * blockDim.x)
       c.dst[j] = c.src[j];
   }
+}
+
+// seg_copy_kernel's shape over rows that are moved in place (ndt_repose_points' arithmetic: repose_point,
+// ndt_posegraph.hip.h): blockIdx.y strides over the rows, blockIdx.x over a row's points; one sincos pair per row and block.
+// A row whose poses are bit-equal keeps its bytes.
+__global__ void __launch_bounds__(256)
+repose_rows_kernel(const SsMove *__restrict__ tab, int n_rows) {
+  for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
+    const SsMove m = tab[r];
+    if (!m.n) continue;
+    const ReposeMove M = repose_move(m.old_pose, m.new_pose);
+    if (M.same) continue;
+    for (unsigned long long j = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; j < m.n;
+         j += (unsigned long long)gridDim.x * blockDim.x) {
+      const float2 v = m.p[j];
+      m.p[j] = repose_point(M, v.x, v.y);
+    }
+  }
+}
+
+// One lane per corrected session c (row c of the recomputed clouds): the cached prefix is the cloud without its newest scan
+// (Submap::makeMap's branches, SsStep::book), empty when the session's triples failed.
+__global__ void __launch_bounds__(256)
+session_refill_kernel(const SsFix *__restrict__ fix, int n, const unsigned long long *__restrict__ cloud_off,
+                      const int *__restrict__ status, const float2 *__restrict__ arena, unsigned long long *__restrict__ plen,
+                      double *__restrict__ last_pose, SsCopy *__restrict__ seg) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  const SsFix F = fix[c];
+  const unsigned long long len = cloud_off[c + 1] - cloud_off[c], nn = F.with_newest ? F.newest_n : 0ull;
+  const unsigned long long pl = status[c] == NDT_OK && len >= nn ? len - nn : 0ull;
+  plen[F.ses] = pl;
+  for (int k = 0; k < 3; ++k) last_pose[3 * F.ses + k] = F.pose[k];
+  seg[c] = SsCopy{arena + cloud_off[c], F.prefix, pl};
 }
 
 // One lane per session.  mode: kSsNone / kSsFirst / kSsMatch; rs_status: the resampler's (NDT_E_ARG: a non-finite coordinate).
@@ -178,6 +221,10 @@ struct SsSession {
   double atdS = 0.0;                        // of the current submap
   bool first_submap = true;                 // cntS == 0
   int n_closed = 0;
+  // the trajectory (ndt_sessions_trajectory / ndt_sessions_correct): every stepped scan's pose as its record gave it, and per
+  // submap its first scan, per closed submap its last (cntS / cntE, src/PointCloudMap.cpp:72-90)
+  std::vector<double> traj;                 // 3 x n_poses
+  std::vector<int> sub_first{0}, sub_last;  // n_closed + 1, n_closed entries
   // the current submap's scans (map frame, float2), one behind the other in store[cur]; the other store takes the two
   // carried-over scans at a split
   DevBuf<float2> store[2];
@@ -375,7 +422,9 @@ int SsStep::book(int i, size_t n_new) {
   if (Q.n_poses) Q.atd += std::sqrt((tx - Q.last_tx) * (tx - Q.last_tx) + (ty - Q.last_ty) * (ty - Q.last_ty));
   else Q.atd = 0.0;
   Q.n_poses++; Q.last_tx = tx; Q.last_ty = ty; Q.started = true;
+  Q.traj.insert(Q.traj.end(), out[i].pose, out[i].pose + 3);
   if (Q.atd - Q.atdS >= P.sep_thre) {
+    Q.sub_last.push_back(Q.n_poses - 2); Q.sub_first.push_back(Q.n_poses - 1);      // cntE = size - 2, the new cntS = size - 1
     // the current submap closes (src/PointCloudMap.cpp:72-90): its cloud becomes the filtered part of the last local map
     const uint64_t n_tail = Q.has_target ? Q.t_n - Q.n_prev : 0;
     SS_TRY(ss_grow(ctx, Q.closed, (size_t)(Q.closed_off.back() + n_tail), (size_t)Q.closed_off.back()));
@@ -522,14 +571,66 @@ int SsStep::behind() {
   return NDT_OK;
 }
 
+// ---- what the end of a step and the end of a correction share: the carried ranges and the maps ----
+
+// The ranges of the sessions that keep their views across a call that fills the arenas `cur` (a step they did not take part
+// in, a correction that does not name them): each moves behind the call's own ranges, at c_end / t_end.
+struct SsCarry {
+  ndt_sessions *s; int cur; uint64_t c_end, t_end;
+  std::vector<SsCopy> moves;
+  void keep(SsSession &Q) {
+    if (!Q.has_target || Q.buf == cur) return;
+    if (Q.c_n) moves.push_back(SsCopy{s->cloud[Q.buf].p + Q.c_off, s->cloud[cur].p + c_end, Q.c_n});
+    if (Q.t_n) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off, s->target[cur].p + t_end, Q.t_n});
+    Q.c_off = c_end; c_end += Q.c_n; Q.t_off = t_end; t_end += Q.t_n; Q.buf = cur;
+  }
+  // table C, the same size at every call (two carried ranges per session at most), and the copies; `cur` is the set's from here
+  int queue(ndt_sessions_stats &stats) {
+    ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
+    const size_t c_bytes = 2 * (size_t)s->S * sizeof(SsCopy);
+    SS_TRY(s->tab_c.reserve(ctx, c_bytes)); SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
+    memset(s->tab_c.h.p, 0, c_bytes);
+    if (!moves.empty()) memcpy(s->tab_c.h.p, moves.data(), moves.size() * sizeof(SsCopy));
+    HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
+    stats.h2d_bytes += c_bytes;
+    if (!moves.empty())
+      seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(moves.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)moves.size());
+    HIP_TRY(ctx, hipGetLastError());
+    s->cur = cur;
+    return NDT_OK;
+  }
+};
+
+// The NDT maps of the new local maps of the sessions who[k] (xy[k], n[k] points in the target arena), rebuilt in place in one
+// batched build; a host wait: the bounding boxes (without a map to build, the stream).  A build refused for one session
+// (NDT_E_GRID: its local map spans more than 2^28 cells) costs that session alone: code[k] takes the build's code, its map
+// stays exactly as it was (none stays none), every other map is built in the same launches.
+int ss_build_maps(ndt_sessions *s, const std::vector<const float *> &xy, const std::vector<size_t> &n, const std::vector<int> &who,
+                  std::vector<int> *code, ndt_sessions_stats &stats) {
+  ndt_ctx *ctx = s->ctx;
+  code->assign(who.size(), NDT_OK);
+  if (!who.empty()) {
+    std::vector<ndt_params> bp(who.size(), s->prm.match);
+    std::vector<ndt_map *> maps;
+    for (int i : who) maps.push_back(s->ses[(size_t)i].map);
+    SS_TRY(check_build_batch(ctx, xy.data(), n.data(), sizeof(float2), (int)who.size(), bp.data(), maps.data(), "ndt_map_build_batch_dev"));
+    SS_TRY(build_batch(ctx, xy.data(), n.data(), sizeof(float2), (int)who.size(), bp.data(), maps.data(), "ndt_map_build_batch_dev", code->data()));
+    for (size_t k = 0; k < who.size(); ++k)
+      if ((*code)[k] == NDT_OK) s->ses[(size_t)who[k]].map = maps[k];
+  } else {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  stats.host_waits++; stats.d2h_bytes += who.size() * 16 * sizeof(unsigned);
+  return NDT_OK;
+}
+
 // ---- the close: the new views, the carried ranges (table C), the NDT maps of the new local maps (host wait 3) ----
 int SsStep::close() {
   const uint64_t *toff = (const uint64_t *)(s->h_back.p + b_toff), *coff = (const uint64_t *)(s->h_back.p + b_coff),
                  *pl = (const uint64_t *)(s->h_back.p + b_plen);
   const int *stt = (const int *)(s->h_back.p + b_stat);
-  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<ndt_map *> bmaps; std::vector<int> bwho;
-  std::vector<SsCopy> carry;
-  uint64_t c_end = coff[S], t_end = toff[S];
+  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst;
+  SsCarry carry{s, cur, coff[S], toff[S], {}};
   for (int i = 0; i < S; ++i) {
     SsSession &Q = s->ses[(size_t)i];
     if (out[i].stepped) {
@@ -544,41 +645,16 @@ int SsStep::close() {
       Q.c_off = coff[i]; Q.c_n = coff[i + 1] - coff[i];
       Q.t_off = toff[i]; Q.t_n = toff[i + 1] - toff[i];
       Q.n_prev = prevs[(size_t)i].n;
-      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bmaps.push_back(Q.map); bwho.push_back(i); }
-    } else if (Q.has_target && Q.buf != cur) {
-      // a session that did not step keeps its views and its last local map: they move to this step's arenas
-      if (Q.c_n) carry.push_back(SsCopy{s->cloud[Q.buf].p + Q.c_off, s->cloud[cur].p + c_end, Q.c_n});
-      if (Q.t_n) carry.push_back(SsCopy{s->target[Q.buf].p + Q.t_off, s->target[cur].p + t_end, Q.t_n});
-      Q.c_off = c_end; c_end += Q.c_n; Q.t_off = t_end; t_end += Q.t_n; Q.buf = cur;
+      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(i); }
+    } else {
+      carry.keep(Q);      // a session that did not step keeps its views and its last local map: they move to this step's arenas
     }
   }
-  // table C, the same size at every step: two carried ranges per session at most
-  const size_t c_bytes = 2 * (size_t)S * sizeof(SsCopy);
-  SS_TRY(s->tab_c.reserve(ctx, c_bytes)); SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
-  memset(s->tab_c.h.p, 0, c_bytes);
-  if (!carry.empty()) memcpy(s->tab_c.h.p, carry.data(), carry.size() * sizeof(SsCopy));
-  HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
-  stats.h2d_bytes += c_bytes;
-  if (!carry.empty())
-    seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(carry.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)carry.size());
-  HIP_TRY(ctx, hipGetLastError());
-  s->cur = cur;
-  // the NDT maps of the new local maps (host wait 3: the bounding boxes)
-  if (!bxy.empty()) {
-    std::vector<ndt_params> bp(bxy.size(), s->prm.match);
-    // a build refused for one session (NDT_E_GRID: its local map spans more than 2^28 cells) costs that session alone: its
-    // record takes the code, its map stays exactly as it was (none stays none), every other map is built in the same launches
-    std::vector<int> bst(bxy.size(), NDT_OK);
-    SS_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data(), "ndt_map_build_batch_dev"));
-    SS_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)bxy.size(), bp.data(), bmaps.data(), "ndt_map_build_batch_dev", bst.data()));
-    for (size_t k = 0; k < bwho.size(); ++k) {
-      if (bst[k] == NDT_OK) s->ses[(size_t)bwho[k]].map = bmaps[k];
-      else out[bwho[k]].status = bst[k];
-    }
-  } else {
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  stats.host_waits++; stats.d2h_bytes += bxy.size() * 16 * sizeof(unsigned);
+  SS_TRY(carry.queue(stats));
+  // the NDT maps of the new local maps (host wait 3: the bounding boxes); a refused build's code goes into the session's record
+  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
+  for (size_t k = 0; k < bwho.size(); ++k)
+    if (bst[k] != NDT_OK) out[bwho[k]].status = bst[k];
   s->stats = stats;
   return NDT_OK;
 }
@@ -593,6 +669,131 @@ int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev, size
   SS_TRY(T.bookkeeping());
   SS_TRY(T.behind());
   return T.close();
+}
+
+// ---- ndt_sessions_correct: PointCloudMap::remakeMaps for the sessions which[0 .. n_corr) ----
+
+// The scan whose (old, new) pose pair moves submap m's closed cloud: the middle one of the submap's own scans [cntS, cntE].
+// The current submap's cntE is the newest scan; a submap that closed without a scan of its own (cntE < cntS: the empty first
+// submap of sep_thre <= 0) takes cntS.
+int ss_anchor(const SsSession &Q, int m) {
+  const int a = Q.sub_first[(size_t)m], e = m < Q.n_closed ? Q.sub_last[(size_t)m] : Q.n_poses - 1;
+  return e > a ? a + (e - a) / 2 : a;
+}
+
+// The arguments have passed the entry point's refusals.  Three parts around two host waits: (1) the rows of every stored scan
+// and closed cloud moved in place, the current submaps assembled again from the moved scans with the local maps behind them
+// (queue_local_map_batch: every triple, as the composed chain computes them), the prefixes refilled from the clouds; wait 1:
+// offsets and status; (2) the views, the carried ranges of everybody else; (3) the NDT maps (wait 2: the boxes).
+int ss_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses, int *status_out) {
+  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ndt_sessions_stats stats{};
+  const int cur = s->cur ^ 1;
+  const size_t C = (size_t)n_corr, C1 = C + 1;
+  std::vector<SsMove> rows; std::vector<SsFix> fix(C); std::vector<ndt_submap_desc> subs(C);
+  std::vector<unsigned char> named((size_t)S, 0);
+  size_t cap_cloud = 0, total_prev = 0, carry_cloud = 0, carry_target = 0, most_pts = 0;
+  for (size_t c = 0; c < C; ++c) {
+    SsSession &Q = s->ses[(size_t)which[c]];
+    named[(size_t)which[c]] = 1;
+    const double *po = Q.traj.data(), *pn = new_poses[c];
+    const size_t n = Q.scan_off.size() - 1, first = (size_t)Q.n_poses - n;
+    auto row = [&](float2 *p, uint64_t cnt, size_t k) {
+      rows.push_back(SsMove{p, cnt, {po[3 * k], po[3 * k + 1], po[3 * k + 2]}, {pn[3 * k], pn[3 * k + 1], pn[3 * k + 2]}});
+      most_pts = std::max(most_pts, (size_t)cnt);
+    };
+    for (int m = 0; m < Q.n_closed; ++m)
+      row(Q.closed.p + Q.closed_off[(size_t)m], Q.closed_off[(size_t)m + 1] - Q.closed_off[(size_t)m], (size_t)ss_anchor(Q, m));
+    float2 *base = Q.store[Q.cur].p;
+    for (size_t k = 0; k < n; ++k) row(base + Q.scan_off[k], Q.scan_off[k + 1] - Q.scan_off[k], first + k);
+    ndt_submap_desc &D = subs[c];
+    D.scans_xy = (const float *)base; D.offsets = Q.scan_off.data(); D.n_scans = (int)n;
+    D.first_submap = Q.first_submap; D.newest = 1; D.remove_moving = P.remove_moving; D.resol = P.resol; D.thre_neighbor = P.thre_neighbor;
+    D.prev_xy = nullptr; D.n_prev = 0;
+    if (Q.n_closed >= 1) {
+      const uint64_t a = Q.closed_off[(size_t)Q.n_closed - 1], np = Q.closed_off[(size_t)Q.n_closed] - a;
+      if (np) { D.prev_xy = (const float *)(Q.closed.p + a); D.n_prev = (size_t)np; }
+    }
+    cap_cloud += submap_points(D); total_prev += D.n_prev;
+    SS_TRY(ss_grow(ctx, Q.prefix, submap_points(D), 0));      // (refilled whole: nothing of it is kept)
+    const int with_newest = P.remove_moving ? 1 : (Q.first_submap || n - 1 >= 2);
+    fix[c] = SsFix{which[c], with_newest, Q.scan_off[n] - Q.scan_off[n - 1], Q.prefix.p, {pn[3 * (Q.n_poses - 1)], pn[3 * (Q.n_poses - 1) + 1], pn[3 * (Q.n_poses - 1) + 2]}};
+  }
+  for (int i = 0; i < S; ++i) {
+    const SsSession &Q = s->ses[(size_t)i];
+    if (!named[(size_t)i] && Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
+  }
+  SS_TRY(s->cloud[cur].ensure(ctx, cap_cloud + carry_cloud + 64));
+  SS_TRY(s->target[cur].ensure(ctx, cap_cloud + total_prev + carry_target + 64));
+  // table A: the rows | the fixes; the prefix segments of session_refill_kernel lie behind it on the device
+  Regions A;
+  const size_t o_rows = A.take(rows.size() * sizeof(SsMove)), o_fix = A.take(C * sizeof(SsFix)), a_bytes = A.end,
+               o_seg = A.take(C * sizeof(SsCopy));
+  SS_TRY(s->tab_a.reserve(ctx, a_bytes)); SS_TRY(s->d_tab_a.ensure(ctx, A.end));
+  memcpy(s->tab_a.h.p + o_rows, rows.data(), rows.size() * sizeof(SsMove));
+  memcpy(s->tab_a.h.p + o_fix, fix.data(), C * sizeof(SsFix));
+  HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, a_bytes, st));
+  stats.h2d_bytes += a_bytes;
+  unsigned char *da = s->d_tab_a.p;
+  repose_rows_kernel<<<dim3((unsigned)std::min<size_t>(64, most_pts / 256 + 1), (unsigned)std::min<size_t>(rows.size(), 65535)), 256, 0, st>>>(
+      (const SsMove *)(da + o_rows), (int)rows.size());
+  HIP_TRY(ctx, hipGetLastError());
+  size_t up = 0, nt = 0;
+  {
+    CallFrame fr(ctx);                            // (the assembly's and the filter's scratch are the context's)
+    SS_TRY(fr.open(st));
+    SS_TRY(queue_local_map_batch(ctx, st, subs.data(), n_corr, sizeof(float2), P.leaf, (float *)s->cloud[cur].p, s->cloud_off.p,
+                                 (float *)s->target[cur].p, s->target_off.p, s->status.p, &up, &nt));
+    SS_TRY(fr.close());
+  }
+  stats.h2d_bytes += up; stats.triples_run = (int)nt; stats.sessions_stepped = n_corr;
+  session_refill_kernel<<<(n_corr + 255) / 256, 256, 0, st>>>((const SsFix *)(da + o_fix), n_corr, (const unsigned long long *)s->cloud_off.p,
+                                                             s->status.p, s->cloud[cur].p, s->plen.p, s->last_pose.p, (SsCopy *)(da + o_seg));
+  seg_copy_kernel<<<dim3(ss_gx(cap_cloud, n_corr), (unsigned)std::min(n_corr, 65535)), 256, 0, st>>>((const SsCopy *)(da + o_seg), n_corr);
+  HIP_TRY(ctx, hipGetLastError());
+  // host wait 1: the cloud and target offsets, the status
+  Regions R;
+  const size_t b_coff = R.take(C1 * 8), b_toff = R.take(C1 * 8), b_stat = R.take(C * 4);
+  SS_TRY(s->h_back.ensure(ctx, R.end));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_coff, s->cloud_off.p, C1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->target_off.p, C1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->status.p, C * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  stats.d2h_bytes += 2 * C1 * 8 + C * 4; stats.host_waits++;
+  const uint64_t *coff = (const uint64_t *)(s->h_back.p + b_coff), *toff = (const uint64_t *)(s->h_back.p + b_toff);
+  const int *stt = (const int *)(s->h_back.p + b_stat);
+  // the corrected sessions' host state and views; everybody else's ranges move to this call's arenas
+  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst; std::vector<size_t> bentry;
+  for (size_t c = 0; c < C; ++c) {
+    SsSession &Q = s->ses[(size_t)which[c]];
+    Q.traj.assign(new_poses[c], new_poses[c] + 3 * (size_t)Q.n_poses);
+    Q.last_tx = fix[c].pose[0]; Q.last_ty = fix[c].pose[1];
+    Q.buf = cur;
+    status_out[c] = stt[c];
+    if (stt[c] != NDT_OK) {
+      // a recomputed triple spans more than 2^30 voxels: no cloud, no local map and an empty prefix; the map stays as it is
+      Q.has_target = false; Q.c_n = Q.t_n = Q.n_prev = 0; Q.plen = 0;
+      continue;
+    }
+    Q.has_target = true;
+    Q.c_off = coff[c]; Q.c_n = coff[c + 1] - coff[c];
+    Q.t_off = toff[c]; Q.t_n = toff[c + 1] - toff[c];
+    Q.n_prev = subs[c].n_prev;
+    const uint64_t nn = fix[c].with_newest ? fix[c].newest_n : 0;      // (session_refill_kernel's rule)
+    Q.plen = Q.c_n >= nn ? Q.c_n - nn : 0;
+    if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(which[c]); bentry.push_back(c); }
+  }
+  SsCarry carry{s, cur, coff[C], toff[C], {}};
+  for (int i = 0; i < S; ++i)
+    if (!named[(size_t)i]) carry.keep(s->ses[(size_t)i]);
+  SS_TRY(carry.queue(stats));
+  // the NDT maps of the new local maps, by the step's refusal rule (host wait 2: the bounding boxes)
+  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
+  for (size_t k = 0; k < bwho.size(); ++k)
+    if (bst[k] != NDT_OK) status_out[bentry[k]] = bst[k];
+  s->stats = stats;
+  return NDT_OK;
 }
 
 #undef SS_TRY

@@ -10,7 +10,8 @@ Host-side mirrors, same names and argument meaning as the reference:
   * PoseFuser      -- fusePose / calOdometryCovariance (src/PoseFuser.cpp:3-61), Pose2D::calMotion / calPredPose
                       (src/Pose2D.cpp:5-37), MyUtil::add_angle / sub_angle (src/MyUtil.cpp:4-23)
   * Submap / PointCloudMap (include/ndt_slam/PointCloudMap.h:22-151, src/PointCloudMap.cpp:4-134) with PCD ASCII
-                      output (PointCloudMap.h:124-136)
+                      output (PointCloudMap.h:124-136), and remakeMaps (src/PointCloudMap.cpp:136-170, commented out
+                      there) as ndt_sessions_correct applies a pose adjustment: over ops.repose_points
   * FrontEnd::process (src/FrontEnd.cpp:4-47)
 
 What runs on the MI355X: the source pre-filter and NDT match (PoseEstimator -> ndt_prefilter, ndt_map_build,
@@ -359,6 +360,48 @@ class PointCloudMap:
         """The result of that item: the submap's cloud, and the local map = previous submap's cloud + filtered cloud."""
         self.submaps[-1].setMap(p_cloud, target[n_prev:])
         self.localMap_cloud = target
+
+    def storeFirst(self):
+        """Index in `poses` of the first scan the current submap holds: its scans are the tail of the stepped scans, the two
+        carried over at a split first (:80-83)."""
+        return len(self.poses) - len(self.submaps[-1].scans)
+
+    def anchorScan(self, m):
+        """The scan whose (old, new) pose pair moves submap m's closed cloud in remakeMaps: the middle one of the submap's own
+        scans, cntS + (cntE - cntS) / 2 -- the current submap's cntE is the newest scan; a submap that closed without a scan of
+        its own (cntE < cntS) takes cntS."""
+        sub = self.submaps[m]
+        cntE = sub.cntE if m < len(self.submaps) - 1 else len(self.poses) - 1
+        return sub.cntS + (cntE - sub.cntS) // 2 if cntE > sub.cntS else sub.cntS
+
+    def remakeMaps(self, newPoses):                                     # :138-170 (commented out in the reference)
+        """The maps after a pose adjustment, as ndt_sessions_correct makes them on the device: every scan the current submap
+        holds moves from its own old pose to its new one and the submap's cloud is made again from them (the reference moves
+        the points of the cloud by their scan ids; recomputing keeps the cloud what makeMap gives for the scans held); a closed
+        submap's cloud -- voxel centroids without a scan id -- moves as a whole by the pair of its anchor scan (anchorScan).
+        ops.repose_points does the moves.  poses and lastPose are replaced; atd is left as it is (:166-169).  deferred: the
+        makeMap and makeLocalMap are the caller's (localMapItem / setLocalMap), as in addPoints."""
+        newPoses = list(newPoses)
+        if len(newPoses) != len(self.poses):
+            raise ValueError("remakeMaps: %d new poses for %d scans" % (len(newPoses), len(self.poses)))
+        if not newPoses:
+            return
+        cur = self.submaps[-1]
+        first = self.storeFirst()
+        idx = [self.anchorScan(m) for m in range(len(self.submaps) - 1)] + [first + k for k in range(len(cur.scans))]
+        clouds = [s.p_cloud for s in self.submaps[:-1]] + list(cur.scans)
+        moved = self.ops.repose_points(clouds, [(self.poses[i].tx, self.poses[i].ty, self.poses[i].th) for i in idx],
+                                       [(newPoses[i].tx, newPoses[i].ty, newPoses[i].th) for i in idx])
+        n_closed = len(self.submaps) - 1
+        for m in range(n_closed):
+            self.submaps[m].p_cloud = moved[m]
+        cur.scans = list(moved[n_closed:])
+        self.poses = newPoses
+        self.lastPose = newPoses[-1]
+        if not self.deferred:
+            cur.makeMap()
+            self.makeGlobalMap()
+            self.makeLocalMap()
 
     def saveGlobalMap(self, map_name, separated_map_name):              # PointCloudMap.h:124-136
         save_pcd_ascii(map_name, self.globalMap_cloud)
