@@ -696,6 +696,46 @@ int ndt_relocalize_dev(ndt_ctx *ctx, const ndt_map *map, const float *scan_xy_de
                        const ndt_reloc_params *params, uint64_t *cand_index, double *cand_score, ndt_result *records,
                        int *n_cand, int *best, double *scores_host);
 
+/* Many independent (scan, map, lattice) jobs in one sweep launch and one pick launch: what a caller with many sessions to
+ * relocalise -- a loop search over a session set -- would otherwise queue once per session.  Device forms only.
+ *
+ * A job names its map (an index into maps[]), its scan (points [offsets_dev[scan], offsets_dev[scan + 1]) of scans_xy_dev,
+ * packed float2; offsets_dev has n_scans + 1 entries, total_points = the points in scans_xy_dev) and its lattice.  jobs and
+ * vol_offsets_host are HOST arrays, read during the call; vol_offsets_host has n_jobs + 1 entries, in poses, the running sum of
+ * the jobs' lattice sizes from 0.  Jobs may share a scan, a map or both.
+ *
+ * The sweep.  score_dev[vol_offsets[j] + p] and pairs_dev[vol_offsets[j] + p] of job j are the bits ndt_score_lattice_dev
+ * writes for that map, scan and lattice pose: a function of those three alone, which does not depend on j, on the other jobs,
+ * on n_jobs, on NDT_OPT_WORKGROUPS or on NDT_OPT_SCORE_STAGE.  An empty scan range is legal here (a pre-filter may leave
+ * one): every pose of that job gets score 0 and pairs 0.  pairs_dev may be NULL.  Asynchronous on `stream` (NULL = the
+ * context's), behind the maps' builds, one launch whatever n_jobs; the call is entered among the readers of every map of
+ * maps[], as a match launch is.  The kernel instance and the float32 sin / cos are those of maps[0], so every map must have
+ * the match parameters of maps[0] (ndt_align_batch_multi_dev's rule).
+ *
+ * The pick.  cand_index_dev[j * top_k + c], c < n_cand_dev[j], are exactly the list ndt_lattice_select_dev gives on job j's
+ * volume with the same top_k and local_max, as indices inside the job's own lattice; entries from n_cand_dev[j] on are not
+ * written.  One workgroup per job: top_k in 1 .. 16, lattices of at most 2^24 poses (a larger one stays with
+ * ndt_lattice_select_dev).  One launch, no host wait.  A job's map and scan are not read.
+ *
+ * Refusals of both (NDT_E_ARG, synchronous, nothing queued, the text names the first offending job or map): a NULL context
+ * ("null context"), a NULL array (pairs_dev of the sweep excepted), n_jobs < 1, n_scans < 1 or total_points > 2^31 - 1, a job's
+ * map or scan index out of range, a lattice ndt_lattice_size refuses (for the pick: or of more than 2^24 poses), vol_offsets
+ * that are not the running sum of the lattice sizes, more than 2^31 - 1 poses in all, a NULL map, a map never built or of
+ * another device, a map with other match parameters than maps[0], an open ndt_map_rebuild_begin on the context, top_k
+ * outside 1 .. 16. */
+typedef struct ndt_score_job {
+  int map;                            /* index into maps[] */
+  int scan;                           /* index of the job's scan in offsets_dev */
+  ndt_pose_lattice lattice;
+} ndt_score_job;
+int ndt_score_lattice_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const float *scans_xy_dev,
+                                const uint64_t *offsets_dev, int n_scans, size_t total_points, const ndt_score_job *jobs,
+                                int n_jobs, double *score_dev, uint32_t *pairs_dev, const uint64_t *vol_offsets_host,
+                                void *stream);
+int ndt_lattice_select_multi_dev(ndt_ctx *ctx, const ndt_score_job *jobs, int n_jobs, const double *score_dev,
+                                 const uint32_t *pairs_dev, const uint64_t *vol_offsets_host, int top_k, int local_max,
+                                 uint64_t *cand_index_dev, int *n_cand_dev, void *stream);
+
 /* ---- Per-point nearest distances and the ranged fitness ------------------------------------------------------------------
  * ndt_result.fitness is getFitnessScore() as src/PoseEstimator.cpp:43 calls it: PCL's getFitnessScore(max_range) with the
  * default max_range = DBL_MAX, the mean over EVERY scan point.  These calls give what that one number hides: the float32
@@ -845,8 +885,9 @@ int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsi
  * backEnd->adjustPoses(), backEnd->remakeMaps() and smat.remakePoseArray(newPoses) (src/FrontEnd.cpp:21-44);
  * PointCloudMap::remakeMaps moves every map point from its old scan pose to its new one (src/PointCloudMap.cpp:136-170).  Its
  * back end (PoseGraph, SlamBackEnd) is absent from the reference tree; these calls are that step for S graphs at once.  Loop
- * DETECTION is the caller's, with what exists (ndt_align_batch_multi_dev against old submaps' maps, ndt_relocalize,
- * ndt_fit_points_batch).  ndt_pg_optimize_batch and ndt_repose_points work on the caller's arrays; an ndt_sessions set's own
+ * DETECTION between independent maps is the caller's, with what exists (ndt_align_batch_multi_dev against old submaps' maps,
+ * ndt_relocalize, ndt_fit_points_batch); inside a resident session it is ndt_sessions_find_loops, at the end of this section.
+ * ndt_pg_optimize_batch and ndt_repose_points work on the caller's arrays; an ndt_sessions set's own
  * resident state takes an adjusted trajectory through ndt_sessions_correct (at the end of this section), and gives the
  * trajectory a graph is built from through ndt_sessions_trajectory.
  *
@@ -972,6 +1013,105 @@ int ndt_sessions_trajectory(const ndt_sessions *s, int i, double *poses_host, si
  * open ndt_map_rebuild_begin.  NDT_E_HIP: a dead set; a HIP failure inside the call leaves the set dead, as in a step. */
 int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses_host,
                          const size_t *n_poses, int *status_host);
+
+/* ---- Loop search on a session set: lpd.detectLoop of the chain the reference left commented out (src/FrontEnd.cpp:32-43) ----
+ * For every session looked at: has its newest scan come back to a submap it closed long ago?  One call gates candidates on the
+ * host, then sweeps a pose lattice around each candidate's last pose over the old submap's own NDT map, picks the best poses,
+ * refines them with the match and returns a ready ndt_pg_edge per session -- with launches, copies and host waits that do not
+ * grow with the number of sessions.  The edge goes into the graph made of ndt_sessions_trajectory, ndt_pg_optimize_batch
+ * adjusts it and ndt_sessions_correct takes the result back.
+ * Out of scope: more than one candidate submap per session; loops between sessions; a ranged-fitness verification of a
+ * partial overlap (ndt_fit_points_batch stays the caller's tool); keeping the loop maps valid across calls; calling the
+ * optimiser or the correction for the caller.
+ *
+ * Gating (host only, no device work; ndt_sessions_loop_candidates gives exactly what ndt_sessions_find_loops will search).
+ * This is the definition, on what ndt_sessions_trajectory returns (n poses, sub_first, sub_anchor) and the closed clouds'
+ * sizes (ndt_sessions_global_map's sub_offsets):
+ *   - session i is looked at when `which` is NULL or which[i] != 0, it has started and has n_closed >= 2 closed submaps;
+ *   - submap m owns the scans [sub_first[m], sub_first[m + 1] - 1];
+ *   - submap m is eligible when m <= n_closed - 2 (the newest closed submap is already in the local map every step matches
+ *     against), its scan range is not empty, its closed cloud has points, path(m) >= min_path and dist(m) <= radius, where
+ *     path(m) = the sum over k from the submap's last scan to n - 2, in ascending k, of sqrt(dx * dx + dy * dy) between poses
+ *     k and k + 1, and dist(m) = the smallest sqrt(dx * dx + dy * dy) from the last pose (n - 1) to a pose of its scan range;
+ *     fp64, every product, sum and root rounded once;
+ *   - the session's candidate is the eligible submap of smallest dist, ties to the lower m; a session without one has no
+ *     candidate;
+ *   - anchor_scan = sub_anchor[m], the scan whose pose pair moves that cloud in ndt_sessions_correct: the edge made here and a
+ *     correction applied there speak of the same rigid body; newest_scan = n - 1; nearest_scan = the scan of dist(m) (the
+ *     lowest one);
+ *   - the lattice is centred on the last pose (tx, ty, th[deg]): x0 = tx - (double)half_x * step_xy (one rounded multiply, one
+ *     rounded subtraction), y0 likewise, yaw0 = DEG2RAD(th) - (double)half_yaw * step_yaw with DEG2RAD(x) = x * M_PI / 180
+ *     (include/ndt_slam/MyUtil.h:22, as src/PoseEstimator.cpp:22 applies it to the guess); steps (step_xy, step_xy, step_yaw),
+ *     2 half + 1 poses per axis.
+ * Candidates come out in ascending session order; *n_out of them; `out` needs room for n_sessions.
+ * Refusals (NDT_E_ARG, nothing queued): a NULL set ("null session set"), NULL params or outputs, a non-finite or negative
+ * min_path, radius or step, a negative half extent, a lattice above 2^24 poses, top_k outside 1 .. NDT_LOOP_MAX_CAND, a NaN
+ * max_cost.
+ *
+ * The search, for the J candidates (all on the context's stream; synchronous).  (1) One table upload.  (2) Each candidate's
+ * newest stored scan (the one ndt_sessions_occ_integrate takes) goes into the robot frame by ndt_repose_points' arithmetic,
+ * old pose = the session's last pose, new pose = (0, 0, 0), into scratch.  (3) ndt_prefilter_batch_dev's kernels with the set's
+ * leaf: the source a step's match would see.  (4) The J closed clouds are built into NDT maps with the set's match parameters
+ * by the batched build; the set owns these maps (one per session), reuses them from call to call and destroys them; host wait
+ * 1, the bounding boxes.  (5) ndt_score_lattice_multi_dev's launch, (6) ndt_lattice_select_multi_dev's, (7) one kernel that
+ * forms the J x top_k initial guesses and lays each filtered scan out top_k times, (8) ndt_align_batch_multi_dev's launch
+ * with scans of their own, (9) records, candidate indices, scores and counts read back: host wait 2.
+ * The host then takes, per candidate, the record of lowest cost = converged ? fitness : 1e7 (src/PoseEstimator.cpp:43-46), ties
+ * to the lower index, as ndt_relocalize does.
+ *
+ * ndt_loop.  status: NDT_OK, or the code the build gave that candidate's map (NDT_E_GRID, NDT_E_ARG): that candidate alone
+ * then has found = 0 and n_cand = 0.  n_cand records were made (cand_index inside the candidate's lattice, cand_score the
+ * sweep's, cand_cost the rule above; entries from n_cand on are 0); best = the chosen one, -1 for n_cand == 0.  pose = the best
+ * record's (pose[0], pose[1], RAD2DEG(pose[2])), RAD2DEG(x) = x * 180 / M_PI (src/PoseEstimator.cpp:36).  edge: from =
+ * anchor_scan, to = newest_scan, info = params->info, rel by ndt_pg_edge_between(trajectory[anchor_scan], pose); with best == -1
+ * pose and rel are 0.  found = best >= 0 and its cost <= max_cost.  records_host (or NULL): record c of candidate j at
+ * [j * NDT_LOOP_MAX_CAND + c], byte-identical to ndt_align_batch_dev's for that filtered scan alone from that lattice pose.
+ * A candidate's ndt_loop and records do not depend on which other sessions are named.
+ *
+ * The call changes nothing of the set's SLAM state: views taken before it stay valid, and the next step is the step of a set
+ * that never searched.  ndt_sessions_get_stats afterwards describes this call: host_waits 2 (0 with no candidate: the call
+ * then returns NDT_OK with *n_out = 0 and has queued nothing; 0 too when every candidate's newest scan is empty, 1 when no
+ * map could be built: nobody is found), sessions_stepped = J, the bytes of its own tables and read-backs.
+ * Refusals: those of the gating, an open ndt_map_rebuild_begin on the context, more than 2^31 - 1 lattice poses over all
+ * candidates.  NDT_E_HIP on a dead set; a HIP failure inside the call kills the set as in a step. */
+#define NDT_LOOP_MAX_CAND 8
+typedef struct ndt_loop_params {
+  double min_path;                    /* m of trajectory between the candidate submap's last scan and the newest scan */
+  double radius;                      /* m: some scan pose of the candidate submap lies this close to the last pose */
+  double step_xy, step_yaw;           /* m, rad */
+  int    half_x, half_y, half_yaw;    /* lattice of (2 half + 1) per axis, centred on the last pose */
+  int    top_k;                       /* 1 .. NDT_LOOP_MAX_CAND */
+  int    local_max;
+  double max_cost;                    /* found = best cost <= max_cost */
+  double info[6];                     /* copied into every edge: xx xy xt yy yt tt, (m, m, rad) */
+} ndt_loop_params;
+/* min_path 10, radius 2, steps 0.1 m and 1 deg (in rad), halves 10, 10, 6, top_k 4, local_max 1, max_cost 0.02,
+ * info diag(1e4, 1e4, 1e4). */
+int ndt_loop_default_params(ndt_loop_params *p);
+typedef struct ndt_loop_candidate {   /* HOST; what the search of one session will run on */
+  int session, submap, anchor_scan, newest_scan, nearest_scan;
+  double dist, path;
+  ndt_pose_lattice lattice;
+} ndt_loop_candidate;
+/* The gating of ONE trajectory, host only, without a set or a context: the arrays are those ndt_sessions_trajectory (poses,
+ * sub_first, sub_anchor, n_submaps) and ndt_sessions_global_map (sub_offsets, n_submaps + 1 entries) give for a session that has
+ * started.  *has = 1 and *out written (session 0), or *has = 0.  ndt_sessions_loop_candidates is this rule on every session
+ * looked at.  Refusals: those of the parameters, a NULL pointer, n_scans or n_submaps below 1, arrays that are not a set's
+ * layout (sub_first[0] != 0 or decreasing, an index outside the trajectory, decreasing sub_offsets), a pose that is not finite. */
+int ndt_loop_gate(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor, const uint64_t *sub_offsets,
+                  int n_submaps, const ndt_loop_params *p, ndt_loop_candidate *out, int *has);
+int ndt_sessions_loop_candidates(const ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p,
+                                 ndt_loop_candidate *out, int *n_out);
+typedef struct ndt_loop {             /* HOST; one per candidate, in candidate order */
+  ndt_loop_candidate cand;
+  int status, found, n_cand, best;
+  uint64_t cand_index[NDT_LOOP_MAX_CAND];
+  double cand_score[NDT_LOOP_MAX_CAND], cand_cost[NDT_LOOP_MAX_CAND];
+  double pose[3];
+  ndt_pg_edge edge;
+} ndt_loop;
+int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop *out,
+                            int *n_out, ndt_result *records_host);
 
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the

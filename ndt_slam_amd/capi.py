@@ -96,6 +96,20 @@ class RelocParams(C.Structure):
     _fields_ = [("lattice", PoseLattice), ("top_k", C.c_int), ("local_max", C.c_int)]
 
 
+class ScoreJob(C.Structure):
+    """ndt_score_job (include/ndt_mi355x.h): one (map, scan, lattice) of a multi-job sweep or pick."""
+    _fields_ = [("map", C.c_int), ("scan", C.c_int), ("lattice", PoseLattice)]
+
+
+def score_jobs(jobs):
+    """[(map index, scan index, PoseLattice)] -> (ScoreJob array, vol_offsets [len + 1] uint64: the running sum of the
+    lattice sizes, in poses)."""
+    arr = (ScoreJob * len(jobs))(*[ScoreJob(int(m), int(sc), lat) for m, sc, lat in jobs])
+    vol = np.zeros(len(jobs) + 1, dtype=np.uint64)
+    vol[1:] = np.cumsum([lat.size for _, _, lat in jobs], dtype=np.uint64)
+    return arr, vol
+
+
 class FitStats(C.Structure):
     """ndt_fit_stats (include/ndt_mi355x.h): one match's getFitnessScore(max_range) and its counts."""
     _fields_ = [("fitness", C.c_double), ("fitness_all", C.c_double), ("n_in", C.c_uint32), ("n_dist", C.c_uint32),
@@ -135,6 +149,32 @@ class PgParams(C.Structure):
     _fields_ = [("max_iter", C.c_int), ("eps_step", C.c_double), ("cg_max_iter", C.c_int), ("cg_rtol", C.c_double),
                 ("max_halvings", C.c_int)]
 
+
+NDT_LOOP_MAX_CAND = 8
+
+
+class LoopParams(C.Structure):
+    """ndt_loop_params (include/ndt_mi355x.h)."""
+    _fields_ = [("min_path", C.c_double), ("radius", C.c_double), ("step_xy", C.c_double), ("step_yaw", C.c_double),
+                ("half_x", C.c_int), ("half_y", C.c_int), ("half_yaw", C.c_int), ("top_k", C.c_int), ("local_max", C.c_int),
+                ("max_cost", C.c_double), ("info", C.c_double * 6)]
+
+
+class LoopCandidate(C.Structure):
+    """ndt_loop_candidate (include/ndt_mi355x.h): what the search of one session will run on."""
+    _fields_ = [("session", C.c_int), ("submap", C.c_int), ("anchor_scan", C.c_int), ("newest_scan", C.c_int),
+                ("nearest_scan", C.c_int), ("dist", C.c_double), ("path", C.c_double), ("lattice", PoseLattice)]
+
+
+class Loop(C.Structure):
+    """ndt_loop (include/ndt_mi355x.h): one candidate's search result."""
+    _fields_ = [("cand", LoopCandidate), ("status", C.c_int), ("found", C.c_int), ("n_cand", C.c_int), ("best", C.c_int),
+                ("cand_index", C.c_uint64 * NDT_LOOP_MAX_CAND), ("cand_score", C.c_double * NDT_LOOP_MAX_CAND),
+                ("cand_cost", C.c_double * NDT_LOOP_MAX_CAND), ("pose", C.c_double * 3), ("edge", PgEdge)]
+
+
+LOOP_CANDIDATE_DTYPE = np.dtype(LoopCandidate)
+LOOP_DTYPE = np.dtype(Loop)                          # (its edge's first field is from_, as PgEdge's)
 
 # (hand-written: the C field is `from`, a Python keyword, so the Structure's is from_)
 PG_EDGE_DTYPE = np.dtype([("from", "i4"), ("to", "i4"), ("rel", "f8", 3), ("info", "f8", 6)], align=True)
@@ -229,6 +269,8 @@ PROTOTYPES = {
     "ndt_lattice_select_dev": [_vp, _P(PoseLattice), _vp, _vp, _i, _i, _vp, _vp, _vp],
     "ndt_relocalize": [_vp, _vp, _vp, _sz, _sz, _P(RelocParams), _vp, _vp, _vp, _P(_i), _P(_i), _vp],
     "ndt_relocalize_dev": [_vp, _vp, _vp, _sz, _sz, _P(RelocParams), _vp, _vp, _vp, _P(_i), _P(_i), _vp],
+    "ndt_score_lattice_multi_dev": [_vp, _vp, _i, _vp, _vp, _i, _sz, _vp, _i, _vp, _vp, _vp, _vp],
+    "ndt_lattice_select_multi_dev": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "ndt_fit_points_batch_dev": [_vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _sz, _d, _vp, _vp, _vp],
     "ndt_fit_points_batch": [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _d, _vp, _vp],
     "ndt_occ_cell": [_P(OccGeometry), _d, _d, _P(C.c_int64), _P(C.c_int64)],
@@ -252,6 +294,10 @@ PROTOTYPES = {
     "ndt_repose_points": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz],
     "ndt_sessions_trajectory": [_vp, _i, _vp, _sz, _P(_sz), _vp, _vp, _P(_i), _P(_sz)],
     "ndt_sessions_correct": [_vp, _vp, _i, _vp, _vp, _vp],
+    "ndt_loop_default_params": [_P(LoopParams)],
+    "ndt_loop_gate": [_vp, _sz, _vp, _vp, _vp, _i, _P(LoopParams), _P(LoopCandidate), _P(_i)],
+    "ndt_sessions_loop_candidates": [_vp, _vp, _P(LoopParams), _vp, _P(_i)],
+    "ndt_sessions_find_loops": [_vp, _vp, _P(LoopParams), _vp, _P(_i), _vp],
     "ndt_kernel_timing": [_vp, _i, _P(_f), _P(_f)],
     "ndt_launch_interval": [_vp, _i, _P(_f)],
     "ndt_ctx_wait_launch": [_vp, _i, _vp],
@@ -456,6 +502,29 @@ def session_params_from_launch(params):
 def default_pg_params(**kw):
     """ndt_pg_default_params, fields overridden by keyword."""
     return _defaults(PgParams, "ndt_pg_default_params", kw)
+
+
+def default_loop_params(**kw):
+    """ndt_loop_default_params, fields overridden by keyword (info: six numbers)."""
+    info = kw.pop("info", None)
+    p = _defaults(LoopParams, "ndt_loop_default_params", kw)
+    if info is not None:
+        p.info[:] = [float(v) for v in info]
+    return p
+
+
+def loop_gate(poses, sub_first, sub_anchor, sub_offsets, params):
+    """ndt_loop_gate (host only): the candidate of one trajectory -- Sessions.trajectory's poses, sub_first and sub_anchor, the
+    closed clouds' offsets in points (len(sub_first) + 1 entries) -- as a LOOP_CANDIDATE_DTYPE record, or None."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    first, anchor = np.ascontiguousarray(sub_first, dtype=np.int32), np.ascontiguousarray(sub_anchor, dtype=np.int32)
+    off = np.ascontiguousarray(sub_offsets, dtype=np.uint64)
+    if len(anchor) != len(first) or len(off) != len(first) + 1:
+        raise ValueError("loop_gate needs one sub_anchor per submap and one more sub_offsets")
+    out, has = np.zeros(1, dtype=LOOP_CANDIDATE_DTYPE), C.c_int()
+    _check(lib().ndt_loop_gate(_ptr(poses), len(poses), _ptr(first), _ptr(anchor), off.ctypes.data, len(first), C.byref(params),
+                               out.ctypes.data_as(_P(LoopCandidate)), C.byref(has)), "ndt_loop_gate")
+    return out[0] if has.value else None
 
 
 def pg_edge_between(from_pose, to_pose):
@@ -763,6 +832,24 @@ class Context(_Handle):
                                                    int(shared_scan), inits_ptr, out_ptr, stream),
                    "ndt_align_batch_multi_dev")
 
+    def score_lattice_multi_dev(self, maps, scans_ptr, offsets_ptr, n_scans, total_points, jobs, score_ptr, pairs_ptr=None,
+                                stream=None):
+        """ndt_score_lattice_multi_dev: `maps` a list of Map objects, `jobs` a list of (map index, scan index, PoseLattice);
+        every pointer a device address; asynchronous.  Returns vol_offsets (uint64, len(jobs) + 1): job j's volume is
+        score[vol_offsets[j]:vol_offsets[j + 1]]."""
+        mp, n = _map_handles(maps)
+        arr, vol = score_jobs(jobs)
+        self.check(lib().ndt_score_lattice_multi_dev(self.h, mp, n, scans_ptr, offsets_ptr, int(n_scans), int(total_points), arr, len(jobs),
+                                                     score_ptr, pairs_ptr, vol.ctypes.data, stream), "ndt_score_lattice_multi_dev")
+        return vol
+
+    def lattice_select_multi_dev(self, jobs, score_ptr, pairs_ptr, top_k, local_max, cand_ptr, n_cand_ptr, stream=None):
+        """ndt_lattice_select_multi_dev on the volumes of score_lattice_multi_dev's `jobs`: cand_ptr len(jobs) x top_k uint64,
+        n_cand_ptr len(jobs) int32 (device addresses); asynchronous."""
+        arr, vol = score_jobs(jobs)
+        self.check(lib().ndt_lattice_select_multi_dev(self.h, arr, len(jobs), score_ptr, pairs_ptr, vol.ctypes.data, int(top_k),
+                                                      int(local_max), cand_ptr, n_cand_ptr, stream), "ndt_lattice_select_multi_dev")
+
     def build_maps_dev(self, xy_ptrs, ns, params, maps=None, stride=8):
         """ndt_map_build_batch_dev: capi.build_maps with device cloud pointers (xy_ptrs[s], ns[s] points at `stride` bytes);
         asynchronous on this context's stream (the clouds must stay as they are until it has run)."""
@@ -932,6 +1019,25 @@ class Sessions(_Handle):
         self.ctx.check(lib().ndt_sessions_correct(self.h, which.ctypes.data, len(who), ptrs, ns.ctypes.data, status.ctypes.data),
                        "ndt_sessions_correct")
         return {i: int(status[c]) for c, i in enumerate(who)}
+
+    def loop_candidates(self, params, which=None):
+        """ndt_sessions_loop_candidates: the candidates ndt_sessions_find_loops would search, as LOOP_CANDIDATE_DTYPE records
+        (host only, no device work)."""
+        out = np.zeros(self.n, dtype=LOOP_CANDIDATE_DTYPE)
+        n, w = C.c_int(), self._active(which)
+        self.ctx.check(lib().ndt_sessions_loop_candidates(self.h, None if w is None else w.ctypes.data, C.byref(params),
+                                                          out.ctypes.data, C.byref(n)), "ndt_sessions_loop_candidates")
+        return out[:n.value]
+
+    def find_loops(self, params, which=None, want_records=False):
+        """ndt_sessions_find_loops: one LOOP_DTYPE record per candidate; with want_records also the match records, as
+        [candidates, NDT_LOOP_MAX_CAND] RESULT_DTYPE (the first n_cand of a row are written)."""
+        out = np.zeros(self.n, dtype=LOOP_DTYPE)
+        rec = np.zeros((self.n, NDT_LOOP_MAX_CAND), dtype=RESULT_DTYPE) if want_records else None
+        n, w = C.c_int(), self._active(which)
+        self.ctx.check(lib().ndt_sessions_find_loops(self.h, None if w is None else w.ctypes.data, C.byref(params), out.ctypes.data,
+                                                     C.byref(n), None if rec is None else rec.ctypes.data), "ndt_sessions_find_loops")
+        return (out[:n.value], rec[:n.value]) if want_records else out[:n.value]
 
     def stats(self):
         st = SessionsStats()

@@ -231,6 +231,8 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_bstage;                      // ndt_map_build_batch: the host clouds' copies
   DevBuf<unsigned char> d_sel;                         // candidate pick: the sorted lists of the runs, their lengths and heads
   DevBuf<unsigned char> d_rl;                          // score sweep / relocalisation: poses or score volume, pair counts, candidates, guesses, records
+  DevBuf<unsigned char> d_sj, d_pk;                    // multi-job sweep: the call's job table and prefix table of tiles; multi-job pick: its job table
+  StagedUpload<unsigned char> sj_tab, pk_tab;          // ... their stagings (one each: a pick queued behind a sweep does not wait for the sweep's upload)
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
@@ -2925,7 +2927,8 @@ int ndt_sessions_destroy(ndt_sessions *s) {
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)e;
   for (auto &Q : s->ses)
-    if (Q.map) { ndt_map_destroy(Q.map); Q.map = nullptr; }
+    for (ndt_map **m : {&Q.map, &Q.loop_map})
+      if (*m) { ndt_map_destroy(*m); *m = nullptr; }
   delete s;
   return NDT_OK;
 }
@@ -3947,3 +3950,136 @@ int ndt_repose_points(ndt_ctx *ctx, const float *xy_host, size_t stride_bytes, c
 }
 
 }  // extern "C"
+
+// ---- many (scan, map, lattice) jobs in one sweep and one pick (ndt_score_lattice_multi_dev, ndt_lattice_select_multi_dev;
+//      kernels in ndt_score.hip.h) ----
+
+namespace {
+
+// The refusals both calls make of their job list (behind the NULL checks): n_jobs, every job's indices (n_maps, n_scans: -1
+// where the call has none) and lattice, the volume offsets, the pose count.  P[j]: the size of job j's lattice.
+int check_score_jobs(ndt_ctx *ctx, const std::string &f, const ndt_score_job *jobs, int n_jobs, int n_maps, int n_scans,
+                     const uint64_t *vol_offsets, uint64_t max_poses, std::vector<uint64_t> *P) {
+  if (n_jobs < 1) return fail(ctx, NDT_E_ARG, f + ": need n_jobs >= 1");
+  P->resize((size_t)n_jobs);
+  uint64_t run = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const std::string which = f + ": job " + std::to_string(j);
+    if (n_maps >= 0 && (jobs[j].map < 0 || jobs[j].map >= n_maps)) return fail(ctx, NDT_E_ARG, which + ": map index out of range");
+    if (n_scans >= 0 && (jobs[j].scan < 0 || jobs[j].scan >= n_scans)) return fail(ctx, NDT_E_ARG, which + ": scan index out of range");
+    if (!lattice_count(&jobs[j].lattice, &(*P)[j]))
+      return fail(ctx, NDT_E_ARG, which + ": bad lattice (a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
+    if ((*P)[j] > max_poses) return fail(ctx, NDT_E_ARG, which + ": a lattice of more than 2^24 poses (ndt_lattice_select_dev takes it)");
+    if (vol_offsets[j] != run) return fail(ctx, NDT_E_ARG, which + ": vol_offsets is not the running sum of the lattice sizes");
+    run += (*P)[j];
+    if (run > (uint64_t)INT32_MAX) return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 poses in all (at job " + std::to_string(j) + ")");
+  }
+  if (vol_offsets[n_jobs] != run) return fail(ctx, NDT_E_ARG, f + ": vol_offsets[n_jobs] is not the sum of the lattice sizes");
+  return NDT_OK;
+}
+
+// ndt_score_lattice_multi_dev.  longest: no scan of the call has more points (the public call: total_points; the lengths
+// themselves are on the device) -- what the dynamic LDS is sized for.
+int score_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const float *scans_xy_dev, const uint64_t *offsets_dev,
+                int n_scans, size_t total_points, size_t longest, const ndt_score_job *jobs, int n_jobs, double *score_dev,
+                uint32_t *pairs_dev, const uint64_t *vol_offsets_host, void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f("ndt_score_lattice_multi_dev");
+  if (!maps || !scans_xy_dev || !offsets_dev || !jobs || !score_dev || !vol_offsets_host)
+    return fail(ctx, NDT_E_ARG, f + ": NULL maps, scans, offsets, jobs, score or vol_offsets");
+  if (n_scans < 1 || total_points > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, f + ": need n_scans >= 1 and total_points <= 2^31 - 1");
+  std::vector<uint64_t> P;
+  int rc = check_score_jobs(ctx, f, jobs, n_jobs, n_maps < 0 ? 0 : n_maps, n_scans, vol_offsets_host, (uint64_t)INT32_MAX, &P);
+  if (rc) return rc;
+  MultiMaps mm;
+  if ((rc = check_multi(ctx, maps, n_maps, true, 0, f.c_str(), &mm))) return rc;
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    // the table: a row per job (the map's view as it is now), then the prefix of tiles; staged in pinned memory, one copy
+    Regions R;
+    const size_t o_jobs = R.take((size_t)n_jobs * sizeof(ScoreJob), 256), o_tile0 = R.take(((size_t)n_jobs + 1) * 8, 256);
+    int rc2;
+    if ((rc2 = ctx->d_sj.ensure(ctx, R.end)) || (rc2 = ctx->sj_tab.reserve(ctx, R.end))) return rc2;
+    ScoreJob *h_jobs = R.at<ScoreJob>(ctx->sj_tab.h.p, o_jobs);
+    unsigned long long *h_tile0 = R.at<unsigned long long>(ctx->sj_tab.h.p, o_tile0);
+    unsigned long long units = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+      ScoreJob &J = h_jobs[j];
+      J.M = maps[jobs[j].map]->view; J.L = lattice_of(jobs[j].lattice); J.P = P[(size_t)j]; J.vol_off = vol_offsets_host[j]; J.scan = jobs[j].scan;
+      h_tile0[j] = units;
+      units += (P[(size_t)j] + kScoreTile - 1) / kScoreTile;
+    }
+    h_tile0[n_jobs] = units;
+    MapRead rd{ctx, st, mm.distinct.data(), (int)mm.distinct.size()};
+    if ((rc2 = rd.begin())) return rc2;
+    HIP_TRY(ctx, ctx->sj_tab.upload(ctx->d_sj.p, 0, R.end, st));
+    // LDS for the longest scan that can be staged
+    const ndt_map *m0 = maps[0];
+    const bool sse = m0->prm.transform_sse != 0, incl = m0->prm.radius_inclusive != 0;
+    const bool chk = !(m0->view.e_hi > 1.0 + 1e-6);    // (queue_score's instances; check_multi: the same in every map)
+    const unsigned stage_pts = ctx->score_stage ? (unsigned)std::min<size_t>(longest, (size_t)kScoreStagePts) : 0u;
+    const size_t lds = (size_t)stage_pts * sizeof(float2);
+    const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, (size_t)(150 * 1024) / (lds + 1024)));
+    const uint64_t want = ctx->workgroups > 0 ? (uint64_t)ctx->workgroups : (uint64_t)ctx->num_cus * per_cu;
+    const unsigned grid = (unsigned)std::min<uint64_t>(units, want);
+    Event *evr = rd.ev;
+    auto sweep = [&](auto S, auto I, auto C) {
+      hipExtLaunchKernelGGL((ndt_score_multi_kernel<decltype(S)::value, decltype(I)::value, decltype(C)::value>), dim3(grid), dim3(kScoreBlock),
+                            lds, st, evr[0], evr[1], 0, (const ScoreJob *)R.at<ScoreJob>(ctx->d_sj.p, o_jobs),
+                            (const unsigned long long *)R.at<unsigned long long>(ctx->d_sj.p, o_tile0), n_jobs, m0->prm.libm_f32,
+                            (const float2 *)scans_xy_dev, (const unsigned long long *)offsets_dev, stage_pts, score_dev, pairs_dev);
+    };
+    const std::true_type yes; const std::false_type no;
+    if (sse && incl)      sweep(yes, yes, yes);
+    else if (sse && !chk) sweep(yes, no, no);
+    else if (sse)         sweep(yes, no, yes);
+    else if (incl)        sweep(no, yes, yes);
+    else                  sweep(no, no, yes);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, NDT_E_HIP, f + ": " + hipGetErrorString(e));
+    // (queue_score's rule: to a map whose builds another stream carries, this sweep is a deferred launch)
+    const bool deferred = std::any_of(mm.distinct.begin(), mm.distinct.end(), [&](const ndt_map *m) { return st != m->ctx->stream; });
+    return rd.entered(NDT_OK, /*end_carried=*/false, deferred, "ndt_score_lattice_multi_dev");
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndt_score_lattice_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const float *scans_xy_dev,
+                                const uint64_t *offsets_dev, int n_scans, size_t total_points, const ndt_score_job *jobs, int n_jobs,
+                                double *score_dev, uint32_t *pairs_dev, const uint64_t *vol_offsets_host, void *stream) {
+  return score_multi(ctx, maps, n_maps, scans_xy_dev, offsets_dev, n_scans, total_points, total_points, jobs, n_jobs, score_dev, pairs_dev,
+                     vol_offsets_host, stream);
+}
+
+int ndt_lattice_select_multi_dev(ndt_ctx *ctx, const ndt_score_job *jobs, int n_jobs, const double *score_dev, const uint32_t *pairs_dev,
+                                 const uint64_t *vol_offsets_host, int top_k, int local_max, uint64_t *cand_index_dev, int *n_cand_dev,
+                                 void *stream) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f("ndt_lattice_select_multi_dev");
+  if (!jobs || !score_dev || !pairs_dev || !vol_offsets_host || !cand_index_dev || !n_cand_dev) return fail(ctx, NDT_E_ARG, f + ": NULL array");
+  std::vector<uint64_t> P;
+  int rc = check_score_jobs(ctx, f, jobs, n_jobs, -1, -1, vol_offsets_host, (uint64_t)kPickMaxPoses, &P);
+  if (rc) return rc;
+  if (top_k < 1 || top_k > kPickMaxK) return fail(ctx, NDT_E_ARG, f + ": top_k must be in 1 .. 16");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    const size_t bytes = (size_t)n_jobs * sizeof(PickJob);
+    int rc2;
+    if ((rc2 = ctx->d_pk.ensure(ctx, bytes)) || (rc2 = ctx->pk_tab.reserve(ctx, bytes))) return rc2;
+    PickJob *h = reinterpret_cast<PickJob *>(ctx->pk_tab.h.p);
+    for (int j = 0; j < n_jobs; ++j) h[j] = PickJob{lattice_of(jobs[j].lattice), P[(size_t)j], vol_offsets_host[j]};
+    HIP_TRY(ctx, ctx->pk_tab.upload(ctx->d_pk.p, 0, bytes, st));
+    lattice_pick_multi_kernel<<<(unsigned)n_jobs, kPickBlock, (size_t)top_k * kPickBlock * (sizeof(double) + sizeof(unsigned)), st>>>(
+        reinterpret_cast<const PickJob *>(ctx->d_pk.p), score_dev, pairs_dev, top_k, local_max, (unsigned long long *)cand_index_dev, n_cand_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, NDT_E_HIP, f + ": " + hipGetErrorString(e));
+    return (int)NDT_OK;
+  });
+}
+
+}  // extern "C"
+
+#include "ndt_loops.hip.h"

@@ -231,3 +231,140 @@ lattice_cand_kernel(Lattice L, const unsigned long long *__restrict__ cand, cons
   inits[3 * c] = p[0]; inits[3 * c + 1] = p[1]; inits[3 * c + 2] = p[2];
   cand_score[c] = s;
 }
+
+// ------------------------------------------------------------------------------------------
+// many jobs in one launch (ndt_score_lattice_multi_dev, ndt_lattice_select_multi_dev)
+// ------------------------------------------------------------------------------------------
+// A job is one (map, scan, lattice).  Its volume lies at vol_off of the call's score / pairs arrays.
+
+struct ScoreJob {                                    // a row of the sweep's table
+  MapView M;
+  Lattice L;
+  unsigned long long P, vol_off;                     // poses of the lattice; where its volume starts
+  int scan;                                          // points [offsets[scan], offsets[scan + 1]) of the call's scans
+};
+
+// ndt_score_kernel for a table of jobs.  A unit is a tile of kScoreTile consecutive poses of one job; job j owns the units
+// [tile0[j], tile0[j + 1]), every job at least one.  A workgroup takes a contiguous range of the units: it finds the job of its
+// first unit by search in tile0, goes on to the next job when a unit lies behind its job's last, and stages a scan only then.
+// A pose's sums are formed as ndt_score_kernel forms them -- wave w of the workgroup on poses w, w + 4, ... of the tile, lane l
+// on points l, l + 64, ... -- so they depend on the map, the scan and the pose alone.  A scan is staged when it has at most
+// stage_pts points (the call's dynamic LDS; 0: none is); an empty scan gives score 0 (-d1 * 0.0) and pairs 0 at every pose.
+template <bool SSE, bool INCL, bool CHK>
+__global__ void __launch_bounds__(kScoreBlock)
+ndt_score_multi_kernel(const ScoreJob *__restrict__ jobs, const unsigned long long *__restrict__ tile0, int n_jobs, int libm_f32,
+                       const float2 *__restrict__ scans, const unsigned long long *__restrict__ offsets, unsigned stage_pts,
+                       double *__restrict__ score, unsigned *__restrict__ pairs_out) {
+  extern __shared__ float2 s_scan[];                 // stage_pts points
+  __shared__ double etab[64];
+  if (threadIdx.x < 64) etab[threadIdx.x] = c_exp2_tab[threadIdx.x];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long units = tile0[n_jobs];
+  const unsigned long long per = units / gridDim.x, rem = units % gridDim.x;
+  const unsigned long long u0 = blockIdx.x * per + (blockIdx.x < rem ? blockIdx.x : rem), u1 = u0 + per + (blockIdx.x < rem ? 1u : 0u);
+  if (u0 >= u1) return;                              // (uniform)
+  int j = 0;                                         // the last job whose first unit is not behind u0
+  for (int hi = n_jobs - 1; j < hi;) { const int mid = (j + hi + 1) >> 1; if (tile0[mid] <= u0) j = mid; else hi = mid - 1; }
+  j = __builtin_amdgcn_readfirstlane(j) - 1;         // (entered below)
+  MapView M; Lattice L;
+  unsigned long long P = 0, vol = 0, t_first = 0, t_end = 0;
+  const float2 *scan = nullptr; unsigned n = 0; bool staged = false;
+  for (unsigned long long u = u0; u < u1; ++u) {
+    if (u >= t_end) {                                // (uniform) the next job
+      ++j;
+      M = jobs[j].M; L = jobs[j].L; P = jobs[j].P; vol = jobs[j].vol_off;
+      t_first = tile0[j]; t_end = tile0[j + 1];
+      const unsigned long long o0 = offsets[jobs[j].scan], o1 = offsets[jobs[j].scan + 1];
+      scan = scans + o0; n = (unsigned)(o1 - o0);
+      staged = n <= stage_pts;
+      __syncthreads();                               // every wave has left the previous job's points
+      if (staged)
+        for (unsigned i = threadIdx.x; i < n; i += kScoreBlock) s_scan[i] = gld_f2(scan + i);
+      __syncthreads();
+    }
+    const unsigned long long t = u - t_first;
+    for (int r = 0; r < kScoreTile / kScoreWaves; ++r) {
+      const unsigned long long pi = t * kScoreTile + (unsigned)(r * kScoreWaves + wave);   // (wave-uniform)
+      if (pi >= P) break;
+      double p[3];
+      lattice_pose(L, pi, p);
+      PointAcc S = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      unsigned np = 0;
+      // a pose that overflowed to a non-finite component scores nothing (ndt_score_kernel's test)
+      if ((fabs(p[0]) <= DBL_MAX) & (fabs(p[1]) <= DBL_MAX) & (fabs(p[2]) <= DBL_MAX)) {
+        const Tf32 T = tf_from_p(p, libm_f32);
+        if (staged) {
+          for (unsigned i = lane; i < n; i += 64) { const float2 pt = s_scan[i]; score_point<SSE, INCL, CHK>(M, etab, T, pt.x, pt.y, S, np); }
+        } else {
+          for (unsigned i = lane; i < n; i += 64) { const float2 pt = gld_f2(scan + i); score_point<SSE, INCL, CHK>(M, etab, T, pt.x, pt.y, S, np); }
+        }
+      }
+      const double tot = wave_sum(S.se);
+      np = wave_sum(np);
+      if (lane == 0) {
+        score[vol + pi] = -M.d1 * tot;
+        if (pairs_out) pairs_out[vol + pi] = np;
+      }
+    }
+  }
+}
+
+// The pick of every job in one launch: workgroup j on job j's volume.  Every thread keeps the top_k best eligible poses among
+// its own (idx = tid, tid + kPickBlock, ...: ascending, so an equal score never displaces an earlier one) as a sorted list in
+// LDS, slot q of thread t at [q kPickBlock + t]; the workgroup then takes the best of the lists' heads top_k times, as
+// lattice_merge_kernel does.  sel_eligible / sel_beats: the strict total order makes the result ndt_lattice_select_dev's.
+constexpr int kPickBlock = 256;
+constexpr int kPickMaxK = 16;                        // 256 lists x 16 x (8 + 4) B = 48 KiB of LDS
+constexpr unsigned kPickMaxPoses = 1u << 24;
+
+struct PickJob { Lattice L; unsigned long long P, vol_off; };
+
+__global__ void __launch_bounds__(kPickBlock)
+lattice_pick_multi_kernel(const PickJob *__restrict__ jobs, const double *__restrict__ score, const unsigned *__restrict__ pairs,
+                          int top_k, int local_max, unsigned long long *__restrict__ cand, int *__restrict__ n_cand) {
+  extern __shared__ double pk_s[];                   // top_k x kPickBlock scores, then as many pose indices
+  unsigned *pk_i = reinterpret_cast<unsigned *>(pk_s + (size_t)top_k * kPickBlock);
+  __shared__ double ws[kPickBlock / 64];
+  __shared__ unsigned wi[kPickBlock / 64];
+  __shared__ unsigned win_sh;
+  const PickJob J = jobs[blockIdx.x];
+  const double *sc = score + J.vol_off; const unsigned *pr = pairs + J.vol_off;
+  const unsigned P = (unsigned)J.P, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  int m = 0;                                         // length of my list
+  for (unsigned idx = tid; idx < P; idx += kPickBlock) {
+    const double s = gld_d(sc + idx);
+    if (!sel_eligible(J.L, sc, pr, idx, local_max, s)) continue;
+    if (m == top_k && !sel_beats(s, idx, pk_s[(top_k - 1) * kPickBlock + tid], pk_i[(top_k - 1) * kPickBlock + tid])) continue;
+    int at = m < top_k ? m++ : top_k - 1;
+    for (; at > 0 && sel_beats(s, idx, pk_s[(at - 1) * kPickBlock + tid], pk_i[(at - 1) * kPickBlock + tid]); --at) {
+      pk_s[at * kPickBlock + tid] = pk_s[(at - 1) * kPickBlock + tid]; pk_i[at * kPickBlock + tid] = pk_i[(at - 1) * kPickBlock + tid];
+    }
+    pk_s[at * kPickBlock + tid] = s; pk_i[at * kPickBlock + tid] = idx;
+  }
+  constexpr unsigned kNone = ~0u;                    // (P <= 2^24: no pose has this index)
+  int h = 0, r = 0;
+  for (; r < top_k; ++r) {
+    double s = h < m ? pk_s[h * kPickBlock + tid] : 0.0; unsigned i = h < m ? pk_i[h * kPickBlock + tid] : kNone;
+    const unsigned mine = i;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double s2 = __shfl_down(s, o); const unsigned i2 = __shfl_down(i, o);
+      if (i2 != kNone && (i == kNone || sel_beats(s2, i2, s, i))) { s = s2; i = i2; }
+    }
+    if (lane == 0) { ws[wave] = s; wi[wave] = i; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < kPickBlock / 64; ++w)
+        if (wi[w] != kNone && (i == kNone || sel_beats(ws[w], wi[w], s, i))) { s = ws[w]; i = wi[w]; }
+      win_sh = i;
+      if (i != kNone) cand[(size_t)blockIdx.x * top_k + r] = i;
+    }
+    __syncthreads();
+    const unsigned win = win_sh;
+    if (win == kNone) break;                         // (uniform) no eligible pose left
+    if (win == mine) ++h;
+    __syncthreads();                                 // (win_sh, ws, wi are rewritten in the next round)
+  }
+  if (tid == 0) n_cand[blockIdx.x] = r;
+}

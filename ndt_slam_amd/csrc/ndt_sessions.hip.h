@@ -240,6 +240,7 @@ struct SsSession {
   int buf = 0;
   uint64_t c_off = 0, c_n = 0, t_off = 0, t_n = 0, n_prev = 0;
   ndt_map *map = nullptr;
+  ndt_map *loop_map = nullptr;              // ndt_sessions_find_loops: the map of the session's candidate submap, rebuilt by every search
   bool started = false;
 };
 
@@ -272,6 +273,8 @@ struct ndt_sessions {
   DevBuf<uint64_t> cloud_off, target_off;            // S + 1 each
   DevBuf<int> status;
   int cur = 0;                                       // arena of the most recent step
+  // ndt_sessions_find_loops (ndt_loops.hip.h): its table and its scratch -- scans, volumes, candidates, guesses, records
+  StagedUpload<unsigned char> lp_tab; DevBuf<unsigned char> d_lp_tab, lp;
 };
 
 namespace {
