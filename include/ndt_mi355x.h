@@ -1113,6 +1113,56 @@ typedef struct ndt_loop {             /* HOST; one per candidate, in candidate o
 int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop *out,
                             int *n_out, ndt_result *records_host);
 
+/* ---- The scan archive and ndt_sessions_occ_rebuild: occupancy grids that follow a correction -----------------
+ * ndt_sessions_occ_integrate casts a session's newest scan at the pose it had at that step; after ndt_sessions_correct every beam
+ * already in the grid lies where the uncorrected trajectory put it.  A set keeps only the current submap's scans (map frame,
+ * float32), so nothing can be recast from it.  With an ARCHIVE a set keeps every stepped scan -- resampled, robot frame, fp64 --
+ * on the device, and ndt_sessions_occ_rebuild casts the whole archive of any number of sessions into their grids at the poses
+ * the trajectories hold NOW, before or after any number of corrections.
+ *
+ * ndt_sessions_archive_enable.  Off by default: a set without an archive behaves to the last byte and the last
+ * ndt_sessions_stats field as it did before the archive existed.  Legal only while no session of the set has started (after
+ * that NDT_E_ARG, the text names the first started session); idempotent.
+ *
+ * What is archived.  Exactly the scans a step records with stepped = 1: session i's archive always has the n_scans of
+ * ndt_sessions_trajectory, and scan k of it belongs to pose k.  A scan refused with stepped = 0 is not archived; one whose
+ * newest triple fails with the span error is; an empty scan is an empty range.  Stored are the bytes ndt_resample_batch_dev
+ * wrote for the session at that step (double2), copied on the device by the step's own table of moves: with the archive on a
+ * step has no further launch and no further host wait (host_waits stays 3), and uploads one more 24-byte move per session (the
+ * only field of ndt_sessions_stats that differs is h2d_bytes).  Every step record, every view and every later
+ * ndt_sessions_correct / ndt_sessions_find_loops result is byte-identical to a set without the archive.
+ * ndt_sessions_correct does not touch the archive: robot-frame points do not move.  Cost: 16 bytes per resampled point (about
+ * 16 KB per 1000-point scan), grown by doubling, never freed before the set; a failed growth ends the step as a failed growth
+ * of a scan store does (NDT_E_HIP, the set is dead).
+ *
+ * Read-outs.  _info: host only.  _scans: scans [first, first + count) to the host, packed: xy_host takes *n_points double pairs,
+ * offsets count + 1 entries relative to the first; xy_host == NULL returns the sizes (and the offsets).  _view: the device
+ * address of the session's whole archive (NULL while it is empty), valid until the next step.  Refusals (NDT_E_ARG): a NULL
+ * set ("null session set"), an index outside the set, a set without an archive, a range outside the archive, a capacity below
+ * the range's points.
+ *
+ * ndt_sessions_occ_rebuild.  Session i is taken as in ndt_sessions_occ_integrate: (which == NULL or which[i] != 0) and it has
+ * started.  clear != 0 zeroes a taken session's grid first, on the same stream.  Then, for every archived scan k of session i,
+ * the beams of that scan go into occs[i]: a beam's end point is the float32 point ndt_scan_to_map_batch_dev writes for the
+ * archived point and pose k of the trajectory as it is at the call (a = th * M_PI / 180, cos / sin, r00 * lx + r01 * ly + tx,
+ * no contraction, rounded once to float32), its origin (tx, ty) of pose k.  Every other rule is ndt_occ_integrate's: the skips,
+ * the walk, hit and pass, counters modulo 2^32, the stats.  DEFINITION: the grid after the call equals what
+ * ndt_scan_to_map_batch_dev + ndt_occ_integrate_dev give for those scans and poses -- a function of archive, trajectory,
+ * geometry and max_range2 alone; not of the other sessions named, of NDT_OPT_WORKGROUPS, or of anything a step or a correction
+ * did in between.  One fused kernel reads each double2 once: there is no map-frame copy of the archive, the scratch is a table
+ * of at most points / 256 + scans runs and 16 bytes per scan (the pose's cos and sin, computed once per scan).  One table upload (64 bytes per taken session, 32 per scan: the poses come from the
+ * host's trajectory), the clears and two launches whatever the number of sessions and scans; stats_host (may be NULL) is the
+ * one read-back and with it the call's only host wait.  Reads the set's state and changes none of it.  Grids are ordered as by
+ * every ndt_occ_* call.  Refusals (NDT_E_ARG, nothing queued or written): those of ndt_sessions_occ_integrate, a set without an
+ * archive, more than 2^31 - 1 scans or runs of 256 beams over the sessions taken.  NDT_E_HIP: a dead set. */
+int ndt_sessions_archive_enable(ndt_sessions *s);
+int ndt_sessions_archive_info(const ndt_sessions *s, int i, size_t *n_scans, size_t *n_points);
+int ndt_sessions_archive_scans(ndt_sessions *s, int i, size_t first, size_t count, double *xy_host, size_t capacity_points,
+                               uint64_t *offsets, size_t *n_points);
+int ndt_sessions_archive_view(const ndt_sessions *s, int i, const double **xy_dev, size_t *n_points);
+int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
+                             ndt_occ_stats *stats_host);
+
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the
  * match kernel to stop of the last fitness kernel), from HIP events attached to the kernels' own dispatches on the launch's

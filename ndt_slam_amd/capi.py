@@ -298,6 +298,11 @@ PROTOTYPES = {
     "ndt_loop_gate": [_vp, _sz, _vp, _vp, _vp, _i, _P(LoopParams), _P(LoopCandidate), _P(_i)],
     "ndt_sessions_loop_candidates": [_vp, _vp, _P(LoopParams), _vp, _P(_i)],
     "ndt_sessions_find_loops": [_vp, _vp, _P(LoopParams), _vp, _P(_i), _vp],
+    "ndt_sessions_archive_enable": [_vp],
+    "ndt_sessions_archive_info": [_vp, _i, _P(_sz), _P(_sz)],
+    "ndt_sessions_archive_scans": [_vp, _i, _sz, _sz, _vp, _sz, _vp, _P(_sz)],
+    "ndt_sessions_archive_view": [_vp, _i, _P(_vp), _P(_sz)],
+    "ndt_sessions_occ_rebuild": [_vp, _vp, _vp, _i, _d, _vp],
     "ndt_kernel_timing": [_vp, _i, _P(_f), _P(_f)],
     "ndt_launch_interval": [_vp, _i, _P(_f)],
     "ndt_ctx_wait_launch": [_vp, _i, _vp],
@@ -908,12 +913,15 @@ class Sessions(_Handle):
     """ndt_sessions: n device-resident SLAM sessions stepped together (include/ndt_mi355x.h)."""
     _destroy = "ndt_sessions_destroy"
 
-    def __init__(self, ctx, n_sessions, params=None):
+    def __init__(self, ctx, n_sessions, params=None, archive=False):
+        """archive: ndt_sessions_archive_enable -- every stepped scan is kept on the device (robot frame, fp64) for occ_rebuild."""
         self.ctx = ctx
         self.params = params if params is not None else default_session_params()
         self.n = int(n_sessions)
         self.h = C.c_void_p()
         ctx.check(lib().ndt_sessions_create(ctx.h, self.n, C.byref(self.params), C.byref(self.h)), "ndt_sessions_create")
+        if archive:
+            ctx.check(lib().ndt_sessions_archive_enable(self.h), "ndt_sessions_archive_enable")
 
     def _active(self, active):
         if active is None:
@@ -991,6 +999,46 @@ class Sessions(_Handle):
         st = np.zeros(1, dtype=OCC_STATS_DTYPE)
         self.ctx.check(lib().ndt_sessions_occ_integrate(self.h, hs, None if w is None else w.ctypes.data, float(max_range2),
                                                         st.ctypes.data), "ndt_sessions_occ_integrate")
+        return st[0]
+
+    def _grid_handles(self, grids, what):
+        if len(grids) != self.n:
+            raise ValueError("%s needs one grid (or None) per session" % what)
+        return (C.c_void_p * self.n)(*[g.h if g is not None else None for g in grids])
+
+    def archive_info(self, i):
+        """ndt_sessions_archive_info: (scans, points) of session i's scan archive."""
+        n, m = C.c_size_t(), C.c_size_t()
+        self.ctx.check(lib().ndt_sessions_archive_info(self.h, i, C.byref(n), C.byref(m)), "ndt_sessions_archive_info")
+        return n.value, m.value
+
+    def archive_scans(self, i, first=0, count=None):
+        """ndt_sessions_archive_scans: the archived scans [first, first + count) of session i (count None: to the end) as a
+        list of [n, 2] float64 arrays -- the resampled scans in the robot frame, as the steps stored them."""
+        if count is None:
+            count = max(self.archive_info(i)[0] - first, 0)
+        off, n = np.zeros(count + 1, dtype=np.uint64), C.c_size_t()
+        self.ctx.check(lib().ndt_sessions_archive_scans(self.h, i, first, count, None, 0, off.ctypes.data, C.byref(n)),
+                       "ndt_sessions_archive_scans")
+        xy = np.zeros((n.value, 2), dtype=np.float64)
+        self.ctx.check(lib().ndt_sessions_archive_scans(self.h, i, first, count, _ptr(xy), n.value, off.ctypes.data, C.byref(n)),
+                       "ndt_sessions_archive_scans")
+        return [xy[int(off[k]):int(off[k + 1])] for k in range(count)]
+
+    def archive_view(self, i):
+        """ndt_sessions_archive_view: (device address, points) of session i's whole archive; valid until the next step."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self.ctx.check(lib().ndt_sessions_archive_view(self.h, i, C.byref(p), C.byref(n)), "ndt_sessions_archive_view")
+        return p.value, n.value
+
+    def occ_rebuild(self, grids, which=None, clear=True, max_range2=DBL_MAX):
+        """ndt_sessions_occ_rebuild: every taken session's whole scan archive cast into its grid (cleared first with `clear`)
+        at the poses its trajectory holds now -> the call's OCC_STATS_DTYPE record."""
+        hs = self._grid_handles(grids, "occ_rebuild")
+        w = self._active(which)
+        st = np.zeros(1, dtype=OCC_STATS_DTYPE)
+        self.ctx.check(lib().ndt_sessions_occ_rebuild(self.h, hs, None if w is None else w.ctypes.data, 1 if clear else 0,
+                                                      float(max_range2), st.ctypes.data), "ndt_sessions_occ_rebuild")
         return st[0]
 
     def trajectory(self, i):

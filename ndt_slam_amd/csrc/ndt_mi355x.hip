@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <numeric>
 #include <string>
 #include <type_traits>
 #include <mutex>
@@ -2852,6 +2853,14 @@ int check_set(const ndt_sessions *s, int i, bool with_index, const char *fn) {
   return NDT_OK;
 }
 
+// ... and those of the archive's read-outs: check_set's, then a set without an archive
+int check_archive(const ndt_sessions *s, int i, const char *fn) {
+  const int rc = check_set(s, i, true, fn);
+  if (rc) return rc;
+  if (!s->archive) return fail(s->ctx, NDT_E_ARG, std::string(fn) + ": the set has no scan archive (ndt_sessions_archive_enable)");
+  return NDT_OK;
+}
+
 int step_entry(ndt_sessions *s, const double *raw_host, const double *raw_dev, size_t stride, const uint64_t *raw_offsets,
                const double *odo_host, const double *odo_dev, const unsigned char *active, ndt_session_step *out, const char *fn) {
   int rc = check_set(s, 0, false, fn);
@@ -3047,6 +3056,61 @@ int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const do
     hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
   }
   return rc;
+}
+
+// ---- the scan archive (filled by SsStep::book, read by ndt_sessions_occ_rebuild) ----
+
+int ndt_sessions_archive_enable(ndt_sessions *s) {
+  const int rc = check_set(s, 0, false, "ndt_sessions_archive_enable");
+  if (rc) return rc;
+  if (s->archive) return NDT_OK;
+  for (int i = 0; i < s->S; ++i)
+    if (s->ses[(size_t)i].started)
+      return fail(s->ctx, NDT_E_ARG, "ndt_sessions_archive_enable: session " + std::to_string(i) + " has already started");
+  s->archive = true;
+  return NDT_OK;
+}
+
+int ndt_sessions_archive_info(const ndt_sessions *s, int i, size_t *n_scans, size_t *n_points) {
+  const int rc = check_archive(s, i, "ndt_sessions_archive_info");
+  if (rc) return rc;
+  const SsSession &Q = s->ses[(size_t)i];
+  if (n_scans) *n_scans = Q.arch_off.size() - 1;
+  if (n_points) *n_points = (size_t)Q.arch_off.back();
+  return NDT_OK;
+}
+
+int ndt_sessions_archive_scans(ndt_sessions *s, int i, size_t first, size_t count, double *xy_host, size_t capacity_points,
+                               uint64_t *offsets, size_t *n_points) {
+  const int rc = check_archive(s, i, "ndt_sessions_archive_scans");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const SsSession &Q = s->ses[(size_t)i];
+  const size_t have = Q.arch_off.size() - 1;
+  const std::string who = "ndt_sessions_archive_scans: session " + std::to_string(i);
+  if (first > have || count > have - first)
+    return fail(ctx, NDT_E_ARG, who + ": scans [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) +
+                                    ") outside the archive's " + std::to_string(have));
+  const uint64_t p0 = Q.arch_off[first], np = Q.arch_off[first + count] - p0;
+  if (xy_host && capacity_points < np)
+    return fail(ctx, NDT_E_ARG, who + ": capacity below the range's " + std::to_string(np) + " points");
+  if (n_points) *n_points = (size_t)np;
+  if (offsets)
+    for (size_t k = 0; k <= count; ++k) offsets[k] = Q.arch_off[first + k] - p0;
+  if (!xy_host || !np) return NDT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(xy_host, Q.arch.p + p0, (size_t)np * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return NDT_OK;
+}
+
+int ndt_sessions_archive_view(const ndt_sessions *s, int i, const double **xy_dev, size_t *n_points) {
+  const int rc = check_archive(s, i, "ndt_sessions_archive_view");
+  if (rc) return rc;
+  const SsSession &Q = s->ses[(size_t)i];
+  if (xy_dev) *xy_dev = Q.arch_off.back() ? (const double *)Q.arch.p : nullptr;
+  if (n_points) *n_points = (size_t)Q.arch_off.back();
+  return NDT_OK;
 }
 
 }  // extern "C"
@@ -3721,6 +3785,92 @@ int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsi
   ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
   if ((rc = queue_occ(ctx, st, OccCall{taken.data(), S, own.data(), nullptr, nullptr, nullptr, S, total, s->last_pose.p, 24, max_range2, d_stats})))
     return rc;
+  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
+  if ((rc = fr.close())) return rc;
+  if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
+  return NDT_OK;
+}
+
+int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
+                             ndt_occ_stats *stats_host) {
+  int rc = check_set(s, 0, false, "ndt_sessions_occ_rebuild");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const std::string f("ndt_sessions_occ_rebuild");
+  if (!occs) return fail(ctx, NDT_E_ARG, f + ": NULL occs");
+  if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (!s->archive) return fail(ctx, NDT_E_ARG, f + ": the set has no scan archive (ndt_sessions_archive_enable)");
+  // who is taken; the call's scans are the taken sessions' archives one behind the other
+  const int S = s->S;
+  std::vector<ndt_occ *> taken((size_t)S, nullptr);
+  std::vector<int> rows;
+  std::set<const ndt_occ *> seen;
+  uint64_t n_scans = 0, n_runs = 0;
+  for (int i = 0; i < S; ++i) {
+    const SsSession &Q = s->ses[(size_t)i];
+    if ((which && !which[i]) || !Q.started) continue;
+    if (!occs[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": NULL grid");
+    if (occs[i]->ctx != ctx || occs[i]->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": the grid belongs to another context");
+    if (!seen.insert(occs[i]).second) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": its grid is given twice");
+    taken[(size_t)i] = occs[i]; rows.push_back(i);
+    n_scans += Q.arch_off.size() - 1;
+    for (size_t k = 0; k + 1 < Q.arch_off.size(); ++k) n_runs += (Q.arch_off[k + 1] - Q.arch_off[k] + (uint64_t)kOccRun - 1) / (uint64_t)kOccRun;
+    if (n_scans > (uint64_t)INT32_MAX || n_runs > (uint64_t)INT32_MAX)
+      return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 scans or runs of 256 beams over the sessions taken");
+  }
+  if (rows.empty()) {
+    if (stats_host) memset(stats_host, 0, sizeof(*stats_host));
+    return NDT_OK;
+  }
+  const size_t T = rows.size(), Q1 = (size_t)n_scans + 1;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  // the table, one upload: the rows | the scans; behind it on the device the runs and every scan's (cos, sin)
+  Regions R;
+  const size_t o_tab = R.take(T * sizeof(OccRow)), o_scans = R.take(Q1 * sizeof(OccScan)), up_bytes = R.end,
+               o_jobs = R.take((size_t)n_runs * sizeof(OccJob)), o_cs = R.take((size_t)n_scans * sizeof(double2));
+  if ((rc = ctx->occ_tab.reserve(ctx, up_bytes))) return rc;
+  if ((rc = ctx->d_occ.ensure(ctx, R.end))) return rc;
+  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
+  unsigned char *h = ctx->occ_tab.h.p, *d = ctx->d_occ.p;
+  memset(h, 0, up_bytes);
+  OccRow *hr = Regions::at<OccRow>(h, o_tab);
+  OccScan *hs = Regions::at<OccScan>(h, o_scans);
+  uint64_t b = 0, off = 0;
+  for (size_t t = 0; t < T; ++t) {
+    const SsSession &Q = s->ses[(size_t)rows[t]];
+    const ndt_occ &o = *occs[rows[t]];
+    OccRow &r = hr[t];
+    r.cells = o.cells.p; r.x0 = o.g.x0; r.y0 = o.g.y0; r.res = o.g.res; r.nx = o.g.nx; r.ny = o.g.ny;
+    r.pts = reinterpret_cast<const float2 *>(Q.arch.p); r.n = b; r.pad = off;
+    for (size_t k = 0; k + 1 < Q.arch_off.size(); ++k, ++b)
+      hs[b] = OccScan{Q.traj[3 * k], Q.traj[3 * k + 1], Q.traj[3 * k + 2], off + Q.arch_off[k]};
+    off += Q.arch_off.back();
+  }
+  hs[b] = OccScan{0.0, 0.0, 0.0, off};
+  // the runs are dealt with a stride of about one session's runs, coprime to their number (occ_rebuild_kernel)
+  uint64_t stride = std::max<uint64_t>(1, n_runs / T);
+  while (n_runs && std::gcd(stride, n_runs) != 1) ++stride;
+  for (int i : rows) {
+    if ((rc = occ_touch(ctx, occs[i], st))) return rc;
+    if (clear) HIP_TRY(ctx, hipMemsetAsync(occs[i]->cells.p, 0, occs[i]->cells.bytes, st));
+  }
+  HIP_TRY(ctx, ctx->occ_tab.upload(d, 0, up_bytes, st));
+  const OccRow *tab = reinterpret_cast<const OccRow *>(d + o_tab);
+  const OccScan *scans = reinterpret_cast<const OccScan *>(d + o_scans);
+  OccJob *jobs = reinterpret_cast<OccJob *>(d + o_jobs);
+  double2 *cs = reinterpret_cast<double2 *>(d + o_cs);
+  unsigned long long *d_stats = stats_host ? (unsigned long long *)ctx->d_tmp.p : nullptr;
+  occ_rebuild_jobs_kernel<<<1, 256, 0, st>>>(tab, (int)T, scans, (int)n_scans, jobs, (unsigned)n_runs, cs, d_stats);
+  // as many workgroups as there are runs, eight per CU at most (or NDT_OPT_WORKGROUPS): each takes runs in turn
+  const size_t wgs = std::max<size_t>(1, std::min<size_t>((size_t)n_runs, ctx->workgroups > 0 ? (size_t)ctx->workgroups : (size_t)ctx->num_cus * 8));
+  occ_rebuild_kernel<<<dim3((unsigned)wgs), dim3(kOccRun), 0, st>>>(tab, scans, cs, max_range2, jobs, (unsigned)n_runs, (unsigned long long)stride, d_stats);
+  const hipError_t e = hipGetLastError();
+  rc = occ_wrote(ctx, taken.data(), S, st);      // (queued or not: the grids count as written behind this point of st)
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, f + ": " + hipGetErrorString(e));
+  if (rc) return rc;
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
   if ((rc = fr.close())) return rc;
   if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -240,6 +240,10 @@ struct SsSession {
   int buf = 0;
   uint64_t c_off = 0, c_n = 0, t_off = 0, t_n = 0, n_prev = 0;
   ndt_map *map = nullptr;
+  // the scan archive (ndt_sessions_archive_enable): every booked scan as the resampler wrote it -- robot frame,
+  // double2 -- one behind the other; scan k of it belongs to pose k of traj.  Never moved by a correction.
+  DevBuf<double2> arch;
+  std::vector<uint64_t> arch_off{0};        // n_poses + 1 entries
   ndt_map *loop_map = nullptr;              // ndt_sessions_find_loops: the map of the session's candidate submap, rebuilt by every search
   bool started = false;
 };
@@ -251,6 +255,7 @@ struct ndt_sessions {
   int S = 0;
   ndt_session_params prm{};
   bool dead = false;                        // a HIP failure inside a step: every later call returns NDT_E_HIP
+  bool archive = false;                     // ndt_sessions_archive_enable: every booked scan is kept (SsSession::arch)
   std::vector<SsSession> ses;
   ndt_sessions_stats stats{};
   // resident per-session state
@@ -322,7 +327,7 @@ struct SsStep {
   std::vector<uint64_t> rs_off;                    // the front part: the resampled scans' offsets
   // the bookkeeping: table B's contents, the newest triples (unit_room: their units) and the submaps of one triple each
   int cur = 0;                                     // this step's arenas; the last step's are s->cur
-  std::vector<SsCopy> moves;                       // carried-over scans and closed clouds
+  std::vector<SsCopy> moves;                       // carried-over scans and closed clouds, the scan's copy into the archive
   std::vector<float2 *> dst; std::vector<SsPlan> plan; std::vector<PfPrev> prevs;
   MmPlan tri; std::vector<MmSub> subs; float cut = 0.f;      // (cut: rn_cutoff of the set's thre_neighbor)
   size_t cap_cloud = 0, total_prev = 0, carry_cloud = 0, carry_target = 0;
@@ -426,6 +431,13 @@ int SsStep::book(int i, size_t n_new) {
   else Q.atd = 0.0;
   Q.n_poses++; Q.last_tx = tx; Q.last_ty = ty; Q.started = true;
   Q.traj.insert(Q.traj.end(), out[i].pose, out[i].pose + 3);
+  if (s->archive) {
+    // the step's rs64 range of the session, byte for byte: a move of 2 n_new float2
+    SS_TRY(ss_grow(ctx, Q.arch, (size_t)Q.arch_off.back() + n_new, (size_t)Q.arch_off.back()));
+    if (n_new)
+      moves.push_back(SsCopy{(const float2 *)(s->rs64.p + 2 * (size_t)rs_off[(size_t)i]), (float2 *)(Q.arch.p + Q.arch_off.back()), 2ull * n_new});
+    Q.arch_off.push_back(Q.arch_off.back() + n_new);
+  }
   if (Q.atd - Q.atdS >= P.sep_thre) {
     Q.sub_last.push_back(Q.n_poses - 2); Q.sub_first.push_back(Q.n_poses - 1);      // cntE = size - 2, the new cntS = size - 1
     // the current submap closes (src/PointCloudMap.cpp:72-90): its cloud becomes the filtered part of the last local map
@@ -518,12 +530,12 @@ int SsStep::behind() {
   SS_TRY(s->mm.ensure(ctx, M.end));
   char *dm = (char *)s->mm.p;
   mm_bind(tri.jobs.data(), nt, dm, X);
-  // table B, the same size at every step: dst | plan | prevs | jobs | subs | moves (3 per session at most); the segments
+  // table B, the same size at every step: dst | plan | prevs | jobs | subs | moves (3 per session at most, 4 with the archive); the segments
   // of session_plan_kernel lie behind it on the device
   Regions B;
   const size_t o_dst = B.take((size_t)S * 8), o_plan = B.take((size_t)S * sizeof(SsPlan)), o_prev = B.take((size_t)S * sizeof(PfPrev)),
                o_jobs = B.take((size_t)S * sizeof(MmJob)), o_subs = B.take((size_t)S * sizeof(MmSub)),
-               o_moves = B.take(3 * (size_t)S * sizeof(SsCopy)), o_seg = B.take(4 * (size_t)S * sizeof(SsCopy)), b_bytes = o_seg;
+               o_moves = B.take((s->archive ? 4 : 3) * (size_t)S * sizeof(SsCopy)), o_seg = B.take(4 * (size_t)S * sizeof(SsCopy)), b_bytes = o_seg;
   SS_TRY(s->tab_b.reserve(ctx, b_bytes)); SS_TRY(s->d_tab_b.ensure(ctx, B.end));
   unsigned char *h = s->tab_b.h.p;
   memset(h, 0, b_bytes);

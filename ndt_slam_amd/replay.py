@@ -21,6 +21,7 @@ bit-identical to resample_points).  `ops` is the object that provides them (capi
 3x3 filter algebra stay on the host as in the reference.  ROS publishing (tf, PoseArray, RViz clouds)
 is left out: it does not feed back into the estimate.
 """
+import collections
 import math
 import os
 
@@ -659,8 +660,54 @@ def load_occupancy(stem):
     return pix, meta
 
 
+# run_sessions_resident's loop closure: loop = a capi.LoopParams, pg = pose-graph parameters (None: the defaults), odo_info =
+# the six numbers of every odometry arc's information matrix, every = the lockstep steps between two searches, cooldown = the
+# steps a corrected session is not searched again
+LoopClosure = collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")
+
+
+def loop_graph(poses, loop_edge, odo_info):
+    """The pose graph of one trajectory with one loop (host only): one odometry arc per consecutive pair of `poses`
+    ([n, 3], (tx, ty, th[deg])) -- rel by capi.pg_edge_between, info = odo_info (6 numbers) -- then the loop's arc as given
+    (a record with from / from_, to, rel, info: ndt_loop.edge) -> the n arcs as capi.PG_EDGE_DTYPE."""
+    from . import capi
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    n = len(poses)
+    edges = np.zeros(n, dtype=capi.PG_EDGE_DTYPE)
+    for j in range(n - 1):
+        edges[j]["from"], edges[j]["to"] = j, j + 1
+        edges[j]["rel"] = capi.pg_edge_between(poses[j], poses[j + 1])
+        edges[j]["info"] = np.asarray(odo_info, dtype=np.float64).reshape(6)
+    names = getattr(getattr(loop_edge, "dtype", None), "names", None) or ()
+    edges[n - 1]["from"] = loop_edge["from" if "from" in names else "from_"]
+    edges[n - 1]["to"] = loop_edge["to"]
+    edges[n - 1]["rel"], edges[n - 1]["info"] = loop_edge["rel"], loop_edge["info"]
+    return edges
+
+
+def _close_loops(ctx, sessions, lc, which):
+    """One search over the sessions `which`, one batch of pose graphs for the loops found, correct() for the graphs that
+    converged -> the corrected sessions' flags."""
+    from . import capi
+    S = len(which)
+    corrected = np.zeros(S, dtype=np.uint8)
+    found = [l for l in sessions.find_loops(lc.loop, which) if l["status"] == 0 and l["found"]]
+    if not found:
+        return corrected
+    trajs = [sessions.trajectory(int(l["cand"]["session"]))[0] for l in found]
+    graphs = [loop_graph(t, l["edge"], lc.odo_info) for t, l in zip(trajs, found)]
+    off = np.concatenate([[0], np.cumsum([len(t) for t in trajs])]).astype(np.uint64)
+    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(trajs), off, np.concatenate(graphs), off, lc.pg)
+    fix = {int(l["cand"]["session"]): new[int(off[g]):int(off[g + 1])]
+           for g, l in enumerate(found) if res[g]["status"] == 0 and res[g]["converged"]}
+    if fix:
+        for i in sessions.correct(fix):
+            corrected[i] = 1
+    return corrected
+
+
 def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated_map_names=None, sessions=None,
-                          occupancy=None, occupancy_names=None, **params):
+                          occupancy=None, occupancy_names=None, loop_closure=None, **params):
     """run_sessions with every session's state resident on the device: one capi.Sessions set (ndt_sessions_*) over all
     logs, one `step` per lockstep step -- the raw scans and odometry go up, the fused poses come down; scans, submap
     clouds, local maps and NDT maps never leave the device.  The same files and return value as run_sessions
@@ -671,8 +718,16 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
     occupancy: a geometry (x0, y0, res, nx, ny: capi.OccGeometry), or one per log -- one occupancy grid per log
     (capi.OccGrid, or sessions.occ_grid(geometry) where the stand-in has one), every step's scans ray-cast into them
     (sessions.occ_integrate with the records' `stepped` flags), rendered at min_obs = 1 and written with save_occupancy to
-    occupancy_names[i] at the end.  None: no grids, nothing else changes."""
+    occupancy_names[i] at the end.  None: no grids, nothing else changes.
+    loop_closure: None, or an object with LoopClosure's fields.  The set is then created with the scan archive, and behind
+    every `every`-th lockstep step come find_loops over the sessions outside their cooldown, one optimize_pose_graphs batch
+    for the loops found, correct() for the graphs that end with status 0 and converged and, when grids are in use,
+    occ_rebuild(grids, which = corrected, clear = True).  The returned and written poses are then the final trajectories
+    (sessions.trajectory(i)), not the poses as the steps gave them.  A `sessions` object given by the caller must have
+    find_loops (else ValueError) and, for the grids, its archive on."""
     from . import capi
+    if loop_closure is not None and sessions is not None and not hasattr(sessions, "find_loops"):
+        raise ValueError("run_sessions_resident: loop_closure needs a sessions object with find_loops")
     p = dict(LAUNCH_PARAMS)
     p.update(params)
     logs = [list(l) for l in logs]
@@ -681,7 +736,7 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
         return []
     own = sessions is None
     if own:
-        sessions = capi.Sessions(ctx, S, capi.session_params_from_launch(p))
+        sessions = capi.Sessions(ctx, S, capi.session_params_from_launch(p), archive=loop_closure is not None)
     lengths = [min(len(l), p["end_frame"]) for l in logs]
     steps_of = [[k for k in range(lengths[i]) if logs[i][k].sid >= p["start_frame"]] for i in range(S)]
     # FrontEnd::process makes the global map when cnt % keyframe_skip == 0 (cnt: scans processed so far): the last such step
@@ -690,6 +745,7 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
     exported = [(_EMPTY, []) for _ in range(S)]
     empty = np.zeros((0, 2))
     grids, rendered = None, None
+    n_steps, quiet_until = 0, [0] * S
     try:
         if occupancy is not None:
             geoms = [occupancy] * S if hasattr(occupancy, "res") else list(occupancy)
@@ -719,6 +775,16 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
                 if k == last_key[i]:
                     g, parts = sessions.global_map(i)
                     exported[i] = (g.copy(), [m.copy() for m in parts])
+            n_steps += 1
+            if loop_closure is not None and n_steps % loop_closure.every == 0:
+                search = np.array([bool(poses[i]) and n_steps >= quiet_until[i] for i in range(S)], dtype=np.uint8)
+                corrected = _close_loops(ctx, sessions, loop_closure, search) if search.any() else search
+                for i in np.nonzero(corrected)[0]:
+                    quiet_until[i] = n_steps + loop_closure.cooldown
+                if grids is not None and corrected.any():
+                    sessions.occ_rebuild(grids, corrected, True)
+        if loop_closure is not None:
+            poses = [[Pose2D(*[float(v) for v in q]) for q in sessions.trajectory(i)[0]] for i in range(S)]
         if grids is not None:
             rendered = [g.render(1) for g in grids]
     finally:
