@@ -584,7 +584,7 @@ typedef struct ndt_session_step {     /* one per session and step, HOST memory *
   int    submap;                      /* index of the session's current submap after the step */
   int    split;                       /* 1: this step closed a submap (src/PointCloudMap.cpp:72-90) */
 } ndt_session_step;
-typedef struct ndt_sessions_stats {   /* of the most recent step or ndt_sessions_correct */
+typedef struct ndt_sessions_stats {   /* of the most recent step, ndt_sessions_correct or ndt_sessions_remake_closed */
   uint64_t h2d_bytes, d2h_bytes;      /* bytes the step copied to and from the device */
   int host_waits;                     /* times the step waited for the device on the host */
   int triples_run;                    /* scan triples the step computed (at most one per stepped session) */
@@ -1162,6 +1162,46 @@ int ndt_sessions_archive_scans(ndt_sessions *s, int i, size_t first, size_t coun
 int ndt_sessions_archive_view(const ndt_sessions *s, int i, const double **xy_dev, size_t *n_points);
 int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
                              ndt_occ_stats *stats_host);
+/* ndt_sessions_remake_closed: PointCloudMap::remakeMaps for the CLOSED submaps, point by point.
+ * ndt_sessions_correct moves a closed cloud as one rigid body by its anchor scan's pose pair; the reference moves every map
+ * point by its own scan's pair (src/PointCloudMap.cpp:147-154), so the rigid move leaves the drift inside a closed submap where
+ * it was.  With the archive, sessions which[0 .. n_named) get EVERY closed submap's cloud computed again from the archived
+ * scans at the poses the trajectory holds now, and the local map and NDT map refreshed behind that.  Nothing of the
+ * trajectory, of the current submap's scan store, cloud and prefix, or of the archive changes.  Meant to follow
+ * ndt_sessions_correct; legal at any time.
+ * DEFINITION.  Submap m owns the scans [sub_first[m], sub_last[m]], sub_last[m] = sub_first[m + 1] - 1 (ndt_sessions_trajectory).
+ * Its scan list L_m is what its scan store held when it closed: L_0 = its own scans (none for the empty first submap of
+ * sep_thre <= 0); for m >= 1 the last two scans of L_(m-1) -- none when L_(m-1) has fewer than two -- then its own
+ * (src/PointCloudMap.cpp:72-90).  L_m is always a range of the archive, [sub_first[m] - carried_m, sub_last[m]].  Scan k in the
+ * map frame is what ndt_scan_to_map_batch_dev writes for archived scan k and pose k of the trajectory (scan_to_map's
+ * expressions, no contraction, rounded once to float32).  Closed cloud m is the TARGET range ndt_local_map_batch_dev gives one
+ * descriptor with the scans of L_m, first_submap = (sub_first[m] == 0), newest = 1, the set's remove_moving, resol and
+ * thre_neighbor, n_prev = 0, and the set's leaf: filterPoints(makeMap(L_m)), what a split stores.  An empty L_m gives an empty
+ * cloud.  The closed block is rewritten with the new clouds back to back -- their sizes may change -- and
+ * ndt_sessions_global_map's sub_offsets follow.  The local map becomes the new newest closed cloud followed by the filtered
+ * tail of the present one, which keeps its bytes; the NDT map is rebuilt in place from it by the step's per-session refusal
+ * rule.  A session without a local map at the moment gets its closed clouds remade and no local map.  A session without a
+ * closed submap keeps every byte (NDT_OK).  A session's result is a function of its archive, its trajectory and the set's
+ * parameters alone: not of who else is named, of NDT_OPT_WORKGROUPS, or of what steps, corrections or earlier remakes did; a
+ * second call changes no byte.
+ * status_host[c]: NDT_OK; NDT_E_ARG when a scan triple of any remade submap of the session spans more than 2^30 voxels: that
+ * session keeps EVERY byte it had -- closed block, offsets, local map, NDT map (all or nothing per session); otherwise the code
+ * ndt_map_build_batch_dev gives the new local map on its own (the closed clouds are remade, the map is left as it was, as in a
+ * step).  Either way the call returns NDT_OK and no other session is concerned.  Sessions not named keep every byte.  Views
+ * taken before the call are invalid after it, for every session.
+ * Cost: one table upload (48 bytes per archived scan in use, 64 per named session), one kernel that writes each archived scan
+ * in use ONCE into a map-frame scratch (consecutive submaps share it: a descriptor is a slice of the archive's offsets), the
+ * assembly chain of ndt_local_map_batch_dev once over every closed submap of every named session, and TWO host waits (offsets
+ * and status; the bounding boxes), whatever n_named, the number of closed submaps or their lengths.  The scratch holds every
+ * scan in use (8 bytes per point) and every submap's cloud and target at capacity, all at once.  ndt_sessions_get_stats then
+ * describes this call: host_waits 2, sessions_stepped = n_named, triples_run = triples recomputed, the bytes of its own tables
+ * and read-backs.  When no named session has a closed submap that held a point there is nothing to compute: the call queues
+ * nothing and host_waits is 0.
+ * Refusals (NDT_E_ARG, synchronous, nothing changed, the text names the first offending entry): a NULL set ("null session
+ * set"), NULL arrays, n_named < 1, a session outside the set or one that has not started, the same session twice, a set
+ * without an archive, an open ndt_map_rebuild_begin on the context.  NDT_E_HIP: a dead set; a HIP failure inside the call
+ * leaves the set dead, as in a step. */
+int ndt_sessions_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status_host);
 
 /* Durations of the kernels of one of the context's last 64 match launches (`back` = 0: the most recent one):
  * the match kernel (rows a3-a6, a8, a9: start to stop of that kernel) and the fitness kernels behind it (row a7: stop of the

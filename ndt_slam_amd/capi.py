@@ -303,6 +303,7 @@ PROTOTYPES = {
     "ndt_sessions_archive_scans": [_vp, _i, _sz, _sz, _vp, _sz, _vp, _P(_sz)],
     "ndt_sessions_archive_view": [_vp, _i, _P(_vp), _P(_sz)],
     "ndt_sessions_occ_rebuild": [_vp, _vp, _vp, _i, _d, _vp],
+    "ndt_sessions_remake_closed": [_vp, _vp, _i, _vp],
     "ndt_kernel_timing": [_vp, _i, _P(_f), _P(_f)],
     "ndt_launch_interval": [_vp, _i, _P(_f)],
     "ndt_ctx_wait_launch": [_vp, _i, _vp],
@@ -1040,6 +1041,17 @@ class Sessions(_Handle):
         self.ctx.check(lib().ndt_sessions_occ_rebuild(self.h, hs, None if w is None else w.ctypes.data, 1 if clear else 0,
                                                       float(max_range2), st.ctypes.data), "ndt_sessions_occ_rebuild")
         return st[0]
+
+    def remake_closed(self, which):
+        """ndt_sessions_remake_closed: every closed submap's cloud of the sessions `which` (an iterable of session indices)
+        computed again from the scan archive at the poses the trajectories hold now, the local maps and NDT maps behind them
+        -> {session index: status} (NDT_OK, or the code that session alone got; include/ndt_mi355x.h)."""
+        who = [int(i) for i in which]
+        w = np.array(who or [0], dtype=np.int32)          # (nobody named: n_named = 0 with arrays that are not NULL)
+        status = np.zeros(len(w), dtype=np.int32)
+        self.ctx.check(lib().ndt_sessions_remake_closed(self.h, w.ctypes.data, len(who), status.ctypes.data),
+                       "ndt_sessions_remake_closed")
+        return {i: int(status[c]) for c, i in enumerate(who)}
 
     def trajectory(self, i):
         """ndt_sessions_trajectory: (poses [n_scans, 3] float64 (tx, ty, th[deg]), sub_first [n_submaps] int32 -- every

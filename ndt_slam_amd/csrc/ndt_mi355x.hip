@@ -3113,6 +3113,32 @@ int ndt_sessions_archive_view(const ndt_sessions *s, int i, const double **xy_de
   return NDT_OK;
 }
 
+int ndt_sessions_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status_host) {
+  int rc = check_set(s, 0, false, "ndt_sessions_remake_closed");
+  if (rc) return rc;
+  ndt_ctx *ctx = s->ctx;
+  const std::string f("ndt_sessions_remake_closed");
+  if (!which || !status_host) return fail(ctx, NDT_E_ARG, f + ": NULL array (which or status)");
+  if (n_named < 1) return fail(ctx, NDT_E_ARG, f + ": n_named < 1");
+  std::vector<int> entry_of((size_t)s->S, -1);
+  for (int c = 0; c < n_named; ++c) {
+    const int i = which[c];
+    const std::string who = f + ": entry " + std::to_string(c) + ": session " + std::to_string(i);
+    if (i < 0 || i >= s->S) return fail(ctx, NDT_E_ARG, who + " out of range");
+    if (!s->ses[(size_t)i].started) return fail(ctx, NDT_E_ARG, who + " has not started");
+    if (entry_of[(size_t)i] >= 0) return fail(ctx, NDT_E_ARG, who + " is entry " + std::to_string(entry_of[(size_t)i]) + " again");
+    entry_of[(size_t)i] = c;
+  }
+  if (!s->archive) return fail(ctx, NDT_E_ARG, f + ": the set has no scan archive (ndt_sessions_archive_enable)");
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  rc = ss_remake_closed(s, which, n_named, status_host);
+  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
+    s->dead = true;
+    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- relocalisation: score sweep, candidate pick, refinement (ndt_score_*, ndt_lattice_*, ndt_relocalize*; kernels in

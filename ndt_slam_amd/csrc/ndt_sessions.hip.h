@@ -16,6 +16,12 @@
 //                             to its new one: a table of (points, n, old pose, new pose), repose_point's arithmetic
 //   session_refill_kernel     per corrected session: the prefix length and its refill from the recomputed cloud (a segment
 //                             for seg_copy_kernel), and the session's row of last_pose
+// and two for ndt_sessions_remake_closed:
+//   remake_scans_kernel       every archived scan a closed submap of the named sessions held, into the map frame at the pose
+//                             the trajectory holds now: a table of (archive range, pose, destination), scan_to_map_kernel's
+//                             arithmetic
+//   remake_plan_kernel        per named session: the all-or-nothing status over its submaps, its new local map's place in the
+//                             target arena, and the moves into the arenas as segments for seg_copy_kernel
 
 namespace {
 
@@ -39,6 +45,13 @@ struct SsPlan {
   const float2 *newest;
   unsigned long long newest_n;
 };
+
+// one archived scan of a remade session: where it lies in the archive, its pose as the trajectory holds it, where it goes
+struct SsRescan { const double2 *src; float2 *dst; unsigned long long n; double pose[3]; };
+static_assert(sizeof(SsRescan) == 48, "one 48-byte row per archived scan");
+// one named session of a remake: its submaps [d0, d1) among the call's, its present views (old_t: the local map, its first
+// n_prev points the newest closed cloud, `tail` points behind them; old_c: the cloud, c_n points) and where the cloud goes
+struct SsRemake { int d0, d1, has_target, pad; const float2 *old_t, *old_c; float2 *new_c; unsigned long long n_prev, tail, c_n; };
 
 constexpr int kSsNone = 0, kSsFirst = 1, kSsMatch = 2;      // a session's part in a step (SsMode)
 
@@ -84,6 +97,66 @@ session_refill_kernel(const SsFix *__restrict__ fix, int n, const unsigned long 
   plen[F.ses] = pl;
   for (int k = 0; k < 3; ++k) last_pose[3 * F.ses + k] = F.pose[k];
   seg[c] = SsCopy{arena + cloud_off[c], F.prefix, pl};
+}
+
+// scan_to_map_kernel (ndt_resample.hip.h) over rows of packed double2 with a destination each, in repose_rows_kernel's shape:
+// blockIdx.y strides over the rows, blockIdx.x over a row's points; one cos / sin pair per row and block; 16 bytes in and 8 out
+// per point.
+__global__ void __launch_bounds__(256)
+remake_scans_kernel(const SsRescan *__restrict__ tab, int n_rows) {
+  for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
+    const SsRescan R = tab[r];
+    if (!R.n) continue;
+    const double tx = R.pose[0], ty = R.pose[1], a = R.pose[2] * M_PI / 180;
+    const double c = cos(a), sn = sin(a);
+    const double r00 = c, r01 = -sn, r10 = sn, r11 = c;
+    for (unsigned long long g = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; g < R.n;
+         g += (unsigned long long)gridDim.x * blockDim.x) {
+      const double2 p = R.src[g];
+      const double lx = p.x, ly = p.y;
+      const double x = r00 * lx + r01 * ly + tx;
+      const double y = r10 * lx + r11 * ly + ty;
+      R.dst[g] = make_float2((float)x, (float)y);
+    }
+  }
+}
+
+// One workgroup; session c of the call owns the remade submaps [d0, d1): their filtered clouds lie back to back at
+// scr_t + scr_toff[d0 .. d1].  A session is remade when it has a submap and none of them failed (a failed one: NDT_E_ARG, and
+// the session keeps every byte).  Its local map in the target arena: the newest closed cloud -- the remade one, else the one it
+// has -- then the tail it has; a session without a local map gets none.  Writes the exclusive scan of those lengths, the status
+// per session and three segments per session for seg_copy_kernel: the two parts of the local map and the cloud.
+__global__ void __launch_bounds__(1024)
+remake_plan_kernel(const SsRemake *__restrict__ rows, int C, const float2 *__restrict__ scr_t,
+                   const unsigned long long *__restrict__ scr_toff, const int *__restrict__ scr_status, float2 *__restrict__ arena_t,
+                   unsigned long long *__restrict__ ses_toff, int *__restrict__ ses_status, SsCopy *__restrict__ seg) {
+  __shared__ unsigned long long sh[1024 / 64];
+  SsRemake R;
+  const float2 *psrc = nullptr;
+  unsigned long long pn = 0ull, tail = 0ull;
+  int st = NDT_OK;
+  const unsigned long long total = block_excl_offsets<1024>(
+      C, sh,
+      [&](int i) {
+        R = rows[i];
+        st = NDT_OK;
+        for (int d = R.d0; d < R.d1; ++d)
+          if (scr_status[d] != NDT_OK) st = NDT_E_ARG;
+        const bool remade = st == NDT_OK && R.d1 > R.d0;
+        psrc = remade ? scr_t + scr_toff[R.d1 - 1] : R.old_t;
+        pn = remade ? scr_toff[R.d1] - scr_toff[R.d1 - 1] : R.n_prev;
+        tail = R.tail;
+        if (!R.has_target) { pn = 0ull; tail = 0ull; }
+        return pn + tail;
+      },
+      [&](int i, unsigned long long off, unsigned long long) {
+        ses_toff[i] = off;
+        ses_status[i] = st;
+        seg[3 * i + 0] = SsCopy{pn ? psrc : nullptr, arena_t + off, pn};
+        seg[3 * i + 1] = SsCopy{tail ? R.old_t + R.n_prev : nullptr, arena_t + off + pn, tail};
+        seg[3 * i + 2] = SsCopy{R.old_c, R.new_c, R.has_target ? R.c_n : 0ull};
+      });
+  if (threadIdx.x == 0) ses_toff[C] = total;
 }
 
 // One lane per session.  mode: kSsNone / kSsFirst / kSsMatch; rs_status: the resampler's (NDT_E_ARG: a non-finite coordinate).
@@ -280,6 +353,11 @@ struct ndt_sessions {
   int cur = 0;                                       // arena of the most recent step
   // ndt_sessions_find_loops (ndt_loops.hip.h): its table and its scratch -- scans, volumes, candidates, guesses, records
   StagedUpload<unsigned char> lp_tab; DevBuf<unsigned char> d_lp_tab, lp;
+  // ndt_sessions_remake_closed: the archived scans in the map frame, the remade clouds and their filtered forms, one range per
+  // closed submap of the named sessions
+  DevBuf<float2> rm_scan, rm_cloud, rm_target;
+  DevBuf<uint64_t> rm_coff, rm_toff, rm_ses_toff;
+  DevBuf<int> rm_status, rm_ses_status;
 };
 
 namespace {
@@ -800,6 +878,183 @@ int ss_correct(ndt_sessions *s, const int *which, int n_corr, const double *cons
     if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(which[c]); bentry.push_back(c); }
   }
   SsCarry carry{s, cur, coff[C], toff[C], {}};
+  for (int i = 0; i < S; ++i)
+    if (!named[(size_t)i]) carry.keep(s->ses[(size_t)i]);
+  SS_TRY(carry.queue(stats));
+  // the NDT maps of the new local maps, by the step's refusal rule (host wait 2: the bounding boxes)
+  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
+  for (size_t k = 0; k < bwho.size(); ++k)
+    if (bst[k] != NDT_OK) status_out[bentry[k]] = bst[k];
+  s->stats = stats;
+  return NDT_OK;
+}
+
+// ---- ndt_sessions_remake_closed: every closed submap's cloud again from the archive ----
+
+// The archive range [first, first + count) of the scans submap m held when it closed, for every closed submap of Q
+// (SsStep::book's split rule: the last two scans of the store that closed before it, when it held two, then its own).
+void ss_closed_scan_ranges(const SsSession &Q, std::vector<int> *first, std::vector<int> *count) {
+  first->assign((size_t)Q.n_closed, 0); count->assign((size_t)Q.n_closed, 0);
+  int held = 0;
+  for (int m = 0; m < Q.n_closed; ++m) {
+    const int a = Q.sub_first[(size_t)m] - (m >= 1 && held >= 2 ? 2 : 0);
+    held = Q.sub_last[(size_t)m] - a + 1;
+    (*first)[(size_t)m] = a; (*count)[(size_t)m] = held;
+  }
+}
+
+// The arguments have passed the entry point's refusals.  (1) One table: a row per archived scan in use, a row per named
+// session; remake_scans_kernel lays every session's scans out in archive order, so that every submap's scan list is a range of
+// it described by a slice of the archive's own offsets; queue_local_map_batch over every closed submap of every named session;
+// remake_plan_kernel; wait 1: the filtered clouds' offsets, the local maps' offsets, the status.  (2) The closed blocks grown to
+// what they need, the moves into the arenas (seg_copy_kernel), the closed blocks and everybody else's ranges (SsCarry's table).
+// (3) The NDT maps (wait 2: the boxes).  Nothing is committed before wait 1: a session that failed keeps every byte.
+int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status_out) {
+  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ndt_sessions_stats stats{};
+  stats.sessions_stepped = n_named;
+  const size_t C = (size_t)n_named, C1 = C + 1;
+  static const uint64_t no_scan[2] = {0, 0};
+  std::vector<SsRescan> scans; std::vector<SsRemake> rows(C); std::vector<ndt_submap_desc> subs;
+  std::vector<size_t> base(C, 0);                      // where session c's scans start in rm_scan
+  std::vector<unsigned char> named((size_t)S, 0);
+  size_t scan_pts = 0, cap_cloud = 0, most_pts = 0;
+  std::vector<int> first, count;
+  for (size_t c = 0; c < C; ++c) {
+    const SsSession &Q = s->ses[(size_t)which[c]];
+    named[(size_t)which[c]] = 1;
+    rows[c].d0 = (int)subs.size();
+    ss_closed_scan_ranges(Q, &first, &count);
+    base[c] = scan_pts;
+    if (Q.n_closed) scan_pts += (size_t)Q.arch_off[(size_t)(Q.sub_last[(size_t)Q.n_closed - 1] + 1)];
+    for (int m = 0; m < Q.n_closed; ++m) {
+      ndt_submap_desc D{};
+      // (scans_xy: bound below, once rm_scan has its size; a submap that held no scan is one empty scan)
+      D.offsets = count[(size_t)m] ? Q.arch_off.data() + first[(size_t)m] : no_scan;
+      D.n_scans = std::max(count[(size_t)m], 1);
+      D.first_submap = Q.sub_first[(size_t)m] == 0; D.newest = 1;
+      D.remove_moving = P.remove_moving; D.resol = P.resol; D.thre_neighbor = P.thre_neighbor;
+      D.prev_xy = nullptr; D.n_prev = 0;
+      if (D.n_scans > (1 << 20))
+        return fail(ctx, NDT_E_ARG, "ndt_sessions_remake_closed: session " + std::to_string(which[c]) + ": a submap of more than 2^20 scans");
+      cap_cloud += submap_points(D);
+      subs.push_back(D);
+    }
+    rows[c].d1 = (int)subs.size();
+  }
+  const size_t nd = subs.size(), nd1 = nd + 1;
+  if (!cap_cloud) {
+    // no named session has a closed submap that held a point: nothing to compute, nobody changes a byte, nothing is queued
+    for (size_t c = 0; c < C; ++c) status_out[c] = NDT_OK;
+    s->stats = stats;
+    return NDT_OK;
+  }
+  if (nd > (size_t)INT32_MAX / 4 || scan_pts > ((size_t)1 << 40))
+    return fail(ctx, NDT_E_ARG, "ndt_sessions_remake_closed: more than 2^29 closed submaps or 2^40 archived points in one call");
+  const int cur = s->cur ^ 1;
+  SS_TRY(s->rm_scan.ensure(ctx, scan_pts + 64)); SS_TRY(s->rm_cloud.ensure(ctx, cap_cloud + 64)); SS_TRY(s->rm_target.ensure(ctx, cap_cloud + 64));
+  SS_TRY(s->rm_coff.ensure(ctx, nd1)); SS_TRY(s->rm_toff.ensure(ctx, nd1)); SS_TRY(s->rm_status.ensure(ctx, nd));
+  SS_TRY(s->rm_ses_toff.ensure(ctx, C1)); SS_TRY(s->rm_ses_status.ensure(ctx, C));
+  // the arenas: a named session's cloud as it is; its local map with the larger of the two newest closed clouds it may get
+  size_t need_cloud = 0, need_target = 0, carry_cloud = 0, carry_target = 0;
+  for (size_t c = 0; c < C; ++c) {
+    const SsSession &Q = s->ses[(size_t)which[c]];
+    if (!Q.has_target) continue;
+    const size_t newest = rows[c].d1 > rows[c].d0 ? submap_points(subs[(size_t)rows[c].d1 - 1]) : 0;
+    need_cloud += (size_t)Q.c_n; need_target += std::max(newest, (size_t)Q.n_prev) + (size_t)(Q.t_n - Q.n_prev);
+  }
+  for (int i = 0; i < S; ++i) {
+    const SsSession &Q = s->ses[(size_t)i];
+    if (!named[(size_t)i] && Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
+  }
+  SS_TRY(s->cloud[cur].ensure(ctx, need_cloud + carry_cloud + 64));
+  SS_TRY(s->target[cur].ensure(ctx, need_target + carry_target + 64));
+  size_t c_end = 0;
+  for (size_t c = 0; c < C; ++c) {
+    const SsSession &Q = s->ses[(size_t)which[c]];
+    SsRemake &R = rows[c];
+    for (int d = R.d0; d < R.d1; ++d) subs[(size_t)d].scans_xy = (const float *)(s->rm_scan.p + base[c]);
+    if (Q.n_closed) {
+      const int last = Q.sub_last[(size_t)Q.n_closed - 1];      // (-1: one closed submap, the empty first one of sep_thre <= 0)
+      for (size_t k = 0; k < (size_t)(last + 1); ++k) {
+        const uint64_t n = Q.arch_off[k + 1] - Q.arch_off[k];
+        scans.push_back(SsRescan{Q.arch.p + Q.arch_off[k], s->rm_scan.p + base[c] + Q.arch_off[k], n,
+                                 {Q.traj[3 * k], Q.traj[3 * k + 1], Q.traj[3 * k + 2]}});
+        most_pts = std::max(most_pts, (size_t)n);
+      }
+    }
+    R.has_target = Q.has_target; R.pad = 0;
+    R.old_t = Q.has_target ? s->target[Q.buf].p + Q.t_off : nullptr; R.old_c = Q.has_target ? s->cloud[Q.buf].p + Q.c_off : nullptr;
+    R.new_c = s->cloud[cur].p + c_end;
+    R.n_prev = Q.has_target ? Q.n_prev : 0; R.tail = Q.has_target ? Q.t_n - Q.n_prev : 0; R.c_n = Q.has_target ? Q.c_n : 0;
+    c_end += (size_t)R.c_n;
+  }
+  if (scans.size() > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_sessions_remake_closed: more than 2^31 - 1 archived scans in one call");
+  // table A: the scans' rows | the sessions' rows; the segments of remake_plan_kernel lie behind it on the device
+  Regions A;
+  const size_t o_scans = A.take(scans.size() * sizeof(SsRescan)), o_rows = A.take(C * sizeof(SsRemake)), a_bytes = A.end,
+               o_seg = A.take(3 * C * sizeof(SsCopy));
+  SS_TRY(s->tab_a.reserve(ctx, a_bytes)); SS_TRY(s->d_tab_a.ensure(ctx, A.end));
+  memcpy(s->tab_a.h.p + o_scans, scans.data(), scans.size() * sizeof(SsRescan));
+  memcpy(s->tab_a.h.p + o_rows, rows.data(), C * sizeof(SsRemake));
+  HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, a_bytes, st));
+  stats.h2d_bytes += a_bytes;
+  unsigned char *da = s->d_tab_a.p;
+  remake_scans_kernel<<<dim3((unsigned)std::min<size_t>(64, most_pts / 256 + 1), (unsigned)std::min<size_t>(scans.size(), 65535)), 256, 0, st>>>(
+      (const SsRescan *)(da + o_scans), (int)scans.size());
+  HIP_TRY(ctx, hipGetLastError());
+  size_t up = 0, nt = 0;
+  {
+    CallFrame fr(ctx);                            // (the assembly's and the filter's scratch are the context's)
+    SS_TRY(fr.open(st));
+    SS_TRY(queue_local_map_batch(ctx, st, subs.data(), (int)nd, sizeof(float2), P.leaf, (float *)s->rm_cloud.p, s->rm_coff.p,
+                                 (float *)s->rm_target.p, s->rm_toff.p, s->rm_status.p, &up, &nt));
+    SS_TRY(fr.close());
+  }
+  stats.h2d_bytes += up; stats.triples_run = (int)nt;
+  remake_plan_kernel<<<1, 1024, 0, st>>>((const SsRemake *)(da + o_rows), n_named, s->rm_target.p, (const unsigned long long *)s->rm_toff.p,
+                                         s->rm_status.p, s->target[cur].p, (unsigned long long *)s->rm_ses_toff.p, s->rm_ses_status.p,
+                                         (SsCopy *)(da + o_seg));
+  HIP_TRY(ctx, hipGetLastError());
+  // host wait 1: the filtered clouds' offsets, the local maps' offsets, the status
+  Regions R;
+  const size_t b_doff = R.take(nd1 * 8), b_toff = R.take(C1 * 8), b_stat = R.take(C * 4);
+  SS_TRY(s->h_back.ensure(ctx, R.end));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_doff, s->rm_toff.p, nd1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->rm_ses_toff.p, C1 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->rm_ses_status.p, C * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  stats.d2h_bytes += nd1 * 8 + C1 * 8 + C * 4; stats.host_waits++;
+  const uint64_t *doff = (const uint64_t *)(s->h_back.p + b_doff), *toff = (const uint64_t *)(s->h_back.p + b_toff);
+  const int *stt = (const int *)(s->h_back.p + b_stat);
+  // the commit: the moves into the arenas, then the closed blocks (to their exact size) with everybody else's ranges
+  seg_copy_kernel<<<dim3(ss_gx(need_cloud + need_target, 3 * n_named), (unsigned)std::min<size_t>(3 * C, 65535)), 256, 0, st>>>(
+      (const SsCopy *)(da + o_seg), 3 * n_named);
+  HIP_TRY(ctx, hipGetLastError());
+  SsCarry carry{s, cur, c_end, toff[C], {}};
+  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst; std::vector<size_t> bentry;
+  c_end = 0;
+  for (size_t c = 0; c < C; ++c) {
+    SsSession &Q = s->ses[(size_t)which[c]];
+    const SsRemake &W = rows[c];
+    status_out[c] = stt[c];
+    const bool remade = stt[c] == NDT_OK && W.d1 > W.d0;
+    if (remade) {
+      const uint64_t d0 = doff[W.d0], need = doff[W.d1] - d0;
+      SS_TRY(ss_grow(ctx, Q.closed, (size_t)need, 0));      // (rewritten whole: nothing of it is kept)
+      if (need) carry.moves.push_back(SsCopy{s->rm_target.p + d0, Q.closed.p, need});
+      for (int m = 0; m <= Q.n_closed; ++m) Q.closed_off[(size_t)m] = doff[W.d0 + m] - d0;
+    }
+    Q.buf = cur;
+    if (!Q.has_target) continue;
+    Q.c_off = c_end; c_end += (size_t)Q.c_n;
+    Q.t_off = toff[c]; Q.t_n = toff[c + 1] - toff[c];
+    if (remade) {
+      Q.n_prev = doff[W.d1] - doff[W.d1 - 1];
+      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(which[c]); bentry.push_back(c); }
+    }
+  }
   for (int i = 0; i < S; ++i)
     if (!named[(size_t)i]) carry.keep(s->ses[(size_t)i]);
   SS_TRY(carry.queue(stats));

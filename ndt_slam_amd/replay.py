@@ -662,8 +662,32 @@ def load_occupancy(stem):
 
 # run_sessions_resident's loop closure: loop = a capi.LoopParams, pg = pose-graph parameters (None: the defaults), odo_info =
 # the six numbers of every odometry arc's information matrix, every = the lockstep steps between two searches, cooldown = the
-# steps a corrected session is not searched again
-LoopClosure = collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")
+# steps a corrected session is not searched again, remake_closed = behind correct() every corrected session's closed submaps
+# are computed again from the scan archive (sessions.remake_closed) instead of staying rigidly moved
+class LoopClosure(collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")):
+    """The five fields above as a tuple, as before (its _fields, its length and its unpacking are unchanged), and the
+    attribute remake_closed (default False) beside them."""
+
+    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False):
+        self = super().__new__(cls, loop, pg, odo_info, every, cooldown)
+        self.remake_closed = bool(remake_closed)
+        return self
+
+
+def closed_scan_ranges(sub_first, n_closed):
+    """The scans every closed submap held when it closed, as [first, last] index ranges of the stepped scans (host only):
+    sub_first = every submap's first own scan (sessions.trajectory(i)[1]: n_closed + 1 entries, the current submap's last),
+    submap m owns [sub_first[m], sub_first[m + 1] - 1] and held, in front of them, the last two scans of what submap m - 1
+    held -- none when that held fewer than two (addPointsBookkeeping's split rule).  An empty range has last = first - 1."""
+    sub_first = [int(v) for v in sub_first]
+    if n_closed < 0 or n_closed + 1 > len(sub_first):
+        raise ValueError("closed_scan_ranges: %d closed submaps need %d entries of sub_first" % (n_closed, n_closed + 1))
+    out, held = [], 0
+    for m in range(n_closed):
+        first, last = sub_first[m] - (2 if m >= 1 and held >= 2 else 0), sub_first[m + 1] - 1
+        held = last - first + 1
+        out.append([first, last])
+    return out
 
 
 def loop_graph(poses, loop_edge, odo_info):
@@ -721,7 +745,8 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
     occupancy_names[i] at the end.  None: no grids, nothing else changes.
     loop_closure: None, or an object with LoopClosure's fields.  The set is then created with the scan archive, and behind
     every `every`-th lockstep step come find_loops over the sessions outside their cooldown, one optimize_pose_graphs batch
-    for the loops found, correct() for the graphs that end with status 0 and converged and, when grids are in use,
+    for the loops found, correct() for the graphs that end with status 0 and converged, with loop_closure.remake_closed set
+    remake_closed(corrected) -- the corrected sessions' closed submaps again from the archive -- and, when grids are in use,
     occ_rebuild(grids, which = corrected, clear = True).  The returned and written poses are then the final trajectories
     (sessions.trajectory(i)), not the poses as the steps gave them.  A `sessions` object given by the caller must have
     find_loops (else ValueError) and, for the grids, its archive on."""
@@ -781,6 +806,8 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
                 corrected = _close_loops(ctx, sessions, loop_closure, search) if search.any() else search
                 for i in np.nonzero(corrected)[0]:
                     quiet_until[i] = n_steps + loop_closure.cooldown
+                if getattr(loop_closure, "remake_closed", False) and corrected.any():
+                    sessions.remake_closed([int(i) for i in np.nonzero(corrected)[0]])
                 if grids is not None and corrected.any():
                     sessions.occ_rebuild(grids, corrected, True)
         if loop_closure is not None:
