@@ -8,11 +8,11 @@ import numpy as np
 import pytest
 
 import session_workloads as W
-from loops_helpers import FULL_LAP, HALF_LAP, expected_pose, gate_ref, loop_params_dict, loop_workload, pose_gap, same_candidate
-from reloc_helpers import ref_best, ref_cost
-from session_correct_helpers import CorrectedChain, layout
+from loops_helpers import (FULL_LAP, HALF_LAP, assert_composed, chain_layout, compose_loop, expected_pose, gate_ref, loop_bytes,  # noqa: F401
+                           loop_params_dict, loop_workload, pose_gap, same_candidate)
+from session_correct_helpers import CorrectedChain
 from session_helpers import lockstep, same_records, session_logs
-from test_gpu_sessions_correct import chain_poses, same_state, snapshot, same_snapshot
+from test_gpu_sessions_correct import same_state, snapshot, same_snapshot
 from gpu_support import gpu, sync, to_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -45,71 +45,6 @@ def scene(gpu):
     run_lockstep(logs, FULL_LAP, ses, twin, chain)
     yield dict(capi=capi, ctx=ctx, logs=logs, p=p, ses=ses, twin=twin, chain=chain)
     ses.close(); twin.close(); chain.close()
-
-
-def chain_layout(chain, i):
-    """What ndt_sessions_trajectory and ndt_sessions_global_map give for session i, from the chain's bookkeeping."""
-    pm = chain.pcmaps[i]
-    first, anchor, _ = layout(pm)
-    sizes = [len(s.p_cloud) for s in pm.submaps[:-1]]
-    off = np.concatenate([[0], np.cumsum(sizes), [sum(sizes)]]).astype(np.uint64) if sizes else np.zeros(2, np.uint64)
-    return chain_poses(chain, i), first, anchor, off
-
-
-def compose_loop(sc, i, cand, lp):
-    """One candidate's search made of public single-job calls on the chain's own data -> (fields of its ndt_loop, records)."""
-    import torch
-    capi, ctx, chain = sc["capi"], sc["ctx"], sc["chain"]
-    pm, traj = chain.pcmaps[i], chain_poses(chain, i)
-    newest = np.ascontiguousarray(pm.submaps[-1].scans[-1], np.float32).reshape(-1, 2)
-    robot = capi.repose_points(ctx, newest, [0, len(newest)], traj[-1:], np.zeros((1, 3)))
-    src = ctx.prefilter(robot, sc["p"]["LeafSize"])
-    cloud = np.ascontiguousarray(pm.submaps[int(cand["submap"])].p_cloud, np.float32).reshape(-1, 2)
-    gm = capi.Map(ctx, cloud, chain.params)
-    L = capi.PoseLattice.from_buffer_copy(cand["lattice"].tobytes())
-    d_src = to_dev(src)
-    d_s = torch.zeros(L.size, dtype=torch.float64, device=d_src.device)
-    d_p = torch.zeros(L.size, dtype=torch.int32, device=d_src.device)
-    d_c = torch.zeros(lp.top_k, dtype=torch.int64, device=d_src.device)
-    d_n = torch.zeros(1, dtype=torch.int32, device=d_src.device)
-    sync()
-    gm.score_lattice(d_src.data_ptr(), len(src), L, d_s.data_ptr(), d_p.data_ptr())
-    gm.lattice_select(L, d_s.data_ptr(), d_p.data_ptr(), lp.top_k, lp.local_max, d_c.data_ptr(), d_n.data_ptr())
-    sync()
-    n = int(d_n.cpu()[0])
-    idx, score = d_c.cpu().numpy()[:n].astype(np.uint64), d_s.cpu().numpy()
-    recs = np.concatenate([gm.align_batch(src, [0, len(src)], L.pose(int(q)).reshape(1, 3)) for q in idx]) if n else \
-        np.zeros(0, capi.RESULT_DTYPE)
-    gm.close()
-    best = ref_best(recs)
-    out = dict(n_cand=n, best=best, cand_index=idx, cand_score=score[idx.astype(np.int64)], cand_cost=ref_cost(recs))
-    if best >= 0:
-        w = recs[best]["pose"]
-        out["pose"] = np.array([w[0], w[1], w[2] * np.float64(180) / np.float64(np.pi)])
-        out["rel"] = capi.pg_edge_between(traj[int(cand["anchor_scan"])], out["pose"])
-        out["found"] = int(out["cand_cost"][best] <= lp.max_cost)
-    else:
-        out["pose"], out["rel"], out["found"] = np.zeros(3), np.zeros(3), 0
-    return out, recs
-
-
-def loop_bytes(loop, rec):
-    """A candidate's whole ndt_loop and its written records as bytes."""
-    return loop.tobytes() + rec[:int(loop["n_cand"])].tobytes()
-
-
-def assert_composed(sc, loop, rec, lp):
-    ref, recs = compose_loop(sc, int(loop["cand"]["session"]), loop["cand"], lp)
-    n = ref["n_cand"]
-    assert loop["status"] == 0 and loop["n_cand"] == n and loop["best"] == ref["best"] and loop["found"] == ref["found"]
-    for f in ("cand_index", "cand_score", "cand_cost"):
-        assert loop[f][:n].tobytes() == ref[f].tobytes(), f
-        assert not loop[f][n:].any(), f
-    assert rec[:n].tobytes() == recs.tobytes()                              # every record, byte for byte
-    assert loop["pose"].tobytes() == ref["pose"].tobytes()
-    e = loop["edge"]
-    assert (e["from_"], e["to"]) == (loop["cand"]["anchor_scan"], loop["cand"]["newest_scan"])
-    assert e["rel"].tobytes() == ref["rel"].tobytes() and e["info"].tobytes() == np.array(lp.info[:]).tobytes()
 
 
 def test_candidates_are_the_numpy_gating(scene):
