@@ -154,6 +154,34 @@ def test_run_and_prefix_boundaries(gpu):
     assert st["n_skipped"] == 0 and want[1][1][3, 400 + 4999 - 0] >= 1
 
 
+def test_more_scans_than_the_jobs_kernel_has_threads(gpu):
+    """300 scans in one call, their lengths cycling through 0, 1, 255, 256, 257, 3, into three grids: occ_jobs_kernel numbers
+    the runs in rounds of 256 scans and carries the count from one round into the next."""
+    capi, ctx = gpu
+    geoms = [H.Geometry(0.0, 0.0, 0.25, 64, 48), OFFSET_GEOM, H.Geometry(-3.0, -2.0, 0.125, 40, 56)]
+    cells = [(32, 24), (30, 20), (21, 30)]
+    rng = np.random.default_rng(44)
+    lengths = [(0, 1, 255, 256, 257, 3)[b % 6] for b in range(300)]
+    grid_of = rng.integers(0, 3, size=300).astype(np.int32)
+    scans = [centre(geoms[k], cells[k][0] + rng.integers(-12, 13, size=n), cells[k][1] + rng.integers(-12, 13, size=n))
+             for k, n in zip(grid_of, lengths)]
+    origins = np.array([centre(geoms[k], cells[k][0] + rng.integers(-2, 3), cells[k][1] + rng.integers(-2, 3))[0] for k in grid_of], np.float64)
+    runs = np.cumsum([-(-n // 256) for n in lengths])
+    assert runs[255] < runs[256] < runs[-1] and len(set(grid_of[250:262].tolist())) == 3      # runs on both sides of the round's end
+    want, st = check(gpu, geoms, scans, origins, grid_of, what="300 scans")
+    assert st["n_beams"] == sum(lengths) and st["n_skipped"] == 0 and all(w[0].sum() > 0 for w in want)
+    ctx.set_option(2, 1)                                                          # NDT_OPT_WORKGROUPS
+    try:
+        grids, got = run_host(gpu, geoms, scans, origins, grid_of)
+    finally:
+        ctx.set_option(2, 0)
+    assert got == H.stats_tuple(st)
+    for g, w in zip(grids, want):
+        hit, pas = g.counts()
+        assert np.array_equal(hit, w[0]) and np.array_equal(pas, w[1])
+        g.close()
+
+
 # ------------------------------------------------------------------------------------------ 5: contention
 def test_contention_on_the_origin_cell(gpu):
     g = H.Geometry(-6.4, -6.4, 0.05, 256, 256)
