@@ -1065,8 +1065,13 @@ int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const do
  * record's (pose[0], pose[1], RAD2DEG(pose[2])), RAD2DEG(x) = x * 180 / M_PI (src/PoseEstimator.cpp:36).  edge: from =
  * anchor_scan, to = newest_scan, info = params->info, rel by ndt_pg_edge_between(trajectory[anchor_scan], pose); with best == -1
  * pose and rel are 0.  found = best >= 0 and its cost <= max_cost.  records_host (or NULL): record c of candidate j at
- * [j * NDT_LOOP_MAX_CAND + c], byte-identical to ndt_align_batch_dev's for that filtered scan alone from that lattice pose.
+ * [j * NDT_LOOP_MAX_CAND + c], byte-identical to ndt_align_batch_dev's for that filtered scan alone from that lattice pose;
+ * the slots from n_cand on, and every slot behind the *n_out candidates, are not written.
  * A candidate's ndt_loop and records do not depend on which other sessions are named.
+ * A candidate whose newest stored scan has no points (ndt_sessions_step stores a step whose scan is empty as a scan of length
+ * 0) or filters to none, and one whose scan meets no voxel of its map at any lattice pose, is searched like every other and
+ * picks nothing: status NDT_OK, found = 0, n_cand = 0, best = -1, pose and rel 0.  When EVERY candidate's newest scan is
+ * empty the call returns before it builds a map or queues anything: every ndt_loop is that record, with status NDT_OK.
  *
  * The call changes nothing of the set's SLAM state: views taken before it stay valid, and the next step is the step of a set
  * that never searched.  ndt_sessions_get_stats afterwards describes this call: host_waits 2 (0 with no candidate: the call

@@ -5,10 +5,12 @@ robot_frame     a map-frame scan at a pose back in the robot frame, ndt_repose_p
 loop_workload   the issue's workload: the 5 m circle of synth.replay_records, 0.6 m per frame, 181 beams, sepThre 5.
 expected_pose   where the newest scan truly is in the drifted map: traj[anchor] (+) truth[anchor]^-1 (+) truth[newest].
 chain_layout    what ndt_sessions_trajectory and ndt_sessions_global_map give for a session, from a comparison chain.
-compose_loop    one candidate's search made of public single-job calls on a chain's own data; assert_composed holds an
-                ndt_loop and its records to it, loop_bytes is a candidate's whole result as bytes.
+compose_loop    one candidate's search made of public single-job calls on a chain's own data (a refused map: its code and
+                nothing else; an empty filtered scan: nothing scored, nothing picked); assert_loop_is holds an ndt_loop and its
+                records to such a result, assert_composed composes and holds, loop_bytes is a candidate's whole result as bytes.
 """
 import math
+import re
 
 import numpy as np
 
@@ -129,16 +131,32 @@ def chain_layout(chain, i):
     return chain_poses(chain, i), first, anchor, off
 
 
+def _zero_loop(status, n_src=0):
+    return dict(status=status, n_src=n_src, n_cand=0, best=-1, cand_index=np.zeros(0, np.uint64), cand_score=np.zeros(0), cand_cost=np.zeros(0),
+                pose=np.zeros(3), rel=np.zeros(3), found=0)
+
+
 def compose_loop(sc, i, cand, lp):
-    """One candidate's search made of public single-job calls on the chain's own data -> (fields of its ndt_loop, records)."""
+    """One candidate's search made of public single-job calls on the chain's own data -> (fields of its ndt_loop, records).
+    A candidate cloud whose map the single build refuses gives that code as the status and nothing else; a newest scan that
+    filters to no point scores nothing and picks nothing."""
     import torch
     capi, ctx, chain = sc["capi"], sc["ctx"], sc["chain"]
     pm, traj = chain.pcmaps[i], chain_poses(chain, i)
-    newest = np.ascontiguousarray(pm.submaps[-1].scans[-1], np.float32).reshape(-1, 2)
-    robot = capi.repose_points(ctx, newest, [0, len(newest)], traj[-1:], np.zeros((1, 3)))
-    src = ctx.prefilter(robot, sc["p"]["LeafSize"])
+    none = np.zeros(0, capi.RESULT_DTYPE)
     cloud = np.ascontiguousarray(pm.submaps[int(cand["submap"])].p_cloud, np.float32).reshape(-1, 2)
-    gm = capi.Map(ctx, cloud, chain.params)
+    try:
+        gm = capi.Map(ctx, cloud, chain.params)
+    except capi.NdtError as e:
+        return _zero_loop(int(re.search(r"-> (-?\d+):", str(e)).group(1))), none
+    newest = np.ascontiguousarray(pm.submaps[-1].scans[-1], np.float32).reshape(-1, 2)
+    src = newest
+    if len(newest):
+        robot = capi.repose_points(ctx, newest, [0, len(newest)], traj[-1:], np.zeros((1, 3)))
+        src = ctx.prefilter(robot, sc["p"]["LeafSize"])
+    if not len(src):
+        gm.close()
+        return _zero_loop(0), none
     L = capi.PoseLattice.from_buffer_copy(cand["lattice"].tobytes())
     d_src = to_dev(src)
     d_s = torch.zeros(L.size, dtype=torch.float64, device=d_src.device)
@@ -151,11 +169,10 @@ def compose_loop(sc, i, cand, lp):
     sync()
     n = int(d_n.cpu()[0])
     idx, score = d_c.cpu().numpy()[:n].astype(np.uint64), d_s.cpu().numpy()
-    recs = np.concatenate([gm.align_batch(src, [0, len(src)], L.pose(int(q)).reshape(1, 3)) for q in idx]) if n else \
-        np.zeros(0, capi.RESULT_DTYPE)
+    recs = np.concatenate([gm.align_batch(src, [0, len(src)], L.pose(int(q)).reshape(1, 3)) for q in idx]) if n else none
     gm.close()
     best = ref_best(recs)
-    out = dict(n_cand=n, best=best, cand_index=idx, cand_score=score[idx.astype(np.int64)], cand_cost=ref_cost(recs))
+    out = dict(status=0, n_src=len(src), n_cand=n, best=best, cand_index=idx, cand_score=score[idx.astype(np.int64)], cand_cost=ref_cost(recs))
     if best >= 0:
         w = recs[best]["pose"]
         out["pose"] = np.array([w[0], w[1], w[2] * np.float64(180) / np.float64(np.pi)])
@@ -171,10 +188,10 @@ def loop_bytes(loop, rec):
     return loop.tobytes() + rec[:int(loop["n_cand"])].tobytes()
 
 
-def assert_composed(sc, loop, rec, lp):
-    ref, recs = compose_loop(sc, int(loop["cand"]["session"]), loop["cand"], lp)
+def assert_loop_is(loop, rec, ref, recs, lp):
+    """An ndt_loop and its records against compose_loop's result, byte for byte."""
     n = ref["n_cand"]
-    assert loop["status"] == 0 and loop["n_cand"] == n and loop["best"] == ref["best"] and loop["found"] == ref["found"]
+    assert loop["status"] == ref["status"] and loop["n_cand"] == n and loop["best"] == ref["best"] and loop["found"] == ref["found"]
     for f in ("cand_index", "cand_score", "cand_cost"):
         assert loop[f][:n].tobytes() == ref[f].tobytes(), f
         assert not loop[f][n:].any(), f
@@ -183,3 +200,10 @@ def assert_composed(sc, loop, rec, lp):
     e = loop["edge"]
     assert (e["from_"], e["to"]) == (loop["cand"]["anchor_scan"], loop["cand"]["newest_scan"])
     assert e["rel"].tobytes() == ref["rel"].tobytes() and e["info"].tobytes() == np.array(lp.info[:]).tobytes()
+
+
+def assert_composed(sc, loop, rec, lp):
+    """A search that ran (status NDT_OK) against the composition on the chain's session of the same index."""
+    ref, recs = compose_loop(sc, int(loop["cand"]["session"]), loop["cand"], lp)
+    assert loop["status"] == 0
+    assert_loop_is(loop, rec, ref, recs, lp)
