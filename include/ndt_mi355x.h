@@ -795,6 +795,31 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
                          const uint64_t *offsets_host, int B, int shared_scan,
                          const float *tf_host, size_t tf_stride_bytes, double max_d2,
                          float *d2_host, ndt_fit_stats *stats_host);
+/* One map per match.  Match b is searched in maps[map_of[b]]; with map_of == NULL, n_maps must equal B and match b uses
+ * maps[b] (ndt_align_batch_multi_dev's rule).  Every other argument means what it means in ndt_fit_points_batch_dev.
+ * Match b's d2 range and its ndt_fit_stats are, to the last bit, what ndt_fit_points_batch_dev writes for (that map, that
+ * scan, that transform, max_d2), in the order of summation stated above: they do not depend on b, B, the other matches, the
+ * other maps, n_maps, shared_scan against the own-scan form, or NDT_OPT_WORKGROUPS.  Resolutions, grids and every other
+ * parameter but transform_sse may differ between the maps: the kernel reads a view per match, and a view carries its own grid.
+ * A match without a map -- map_of[b] outside [0, n_maps) -- alone gets stats {DBL_MAX, DBL_MAX, 0, 0, n_points, 0} and
+ * +INFINITY in every float of its d2 range; no kernel reads through the index.
+ * One search launch and one close launch, whatever B and n_maps.  The table of the maps' views -- as they are at the call --
+ * goes up once from pinned staging into a table of the call's own inside the context's scratch bracket (not the match
+ * launch's: a match launch queued behind this call does not wait for it); the next ndt_fit_points_multi call waits for the
+ * copy before it rewrites the staging.  The call is entered among the readers of every distinct map, so a rebuild of any of
+ * them, on whatever stream, waits for it.
+ * Refusals (NDT_E_ARG, synchronous, nothing queued or written; the text names the first offending map): maps == NULL or
+ * n_maps < 1; a NULL map, a map never built or built on another device; the refusals of ndt_fit_points_batch_dev; map_of ==
+ * NULL with n_maps != B; maps whose transform_sse differ (the kernel instance depends on it).
+ * ndt_fit_points_multi: the same with host pointers (map_of_host too); one upload; synchronous. */
+int ndt_fit_points_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_dev,
+                             const float *scans_xy_dev, const uint64_t *offsets_dev, int B, size_t total_points,
+                             int shared_scan, const float *tf_dev, size_t tf_stride_bytes, double max_d2,
+                             float *d2_dev, ndt_fit_stats *stats_dev, void *stream);
+int ndt_fit_points_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_host,
+                         const float *scans_xy_host, const uint64_t *offsets_host, int B, int shared_scan,
+                         const float *tf_host, size_t tf_stride_bytes, double max_d2,
+                         float *d2_host, ndt_fit_stats *stats_host);
 
 /* ---- Occupancy grids, ray-cast from scans on the device -----------------------------------------------------------------
  * The reference writes poses and point clouds; it has no counterpart to these calls.  A grid holds, per cell, how many beams
@@ -1020,9 +1045,9 @@ int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const do
  * refines them with the match and returns a ready ndt_pg_edge per session -- with launches, copies and host waits that do not
  * grow with the number of sessions.  The edge goes into the graph made of ndt_sessions_trajectory, ndt_pg_optimize_batch
  * adjusts it and ndt_sessions_correct takes the result back.
- * Out of scope: more than one candidate submap per session; loops between sessions; a ranged-fitness verification of a
- * partial overlap (ndt_fit_points_batch stays the caller's tool); keeping the loop maps valid across calls; calling the
- * optimiser or the correction for the caller.
+ * Several candidate submaps per session and a ranged-fitness verification of a partial overlap: ndt_sessions_find_loops_multi
+ * below.  Out of scope: loops between sessions; keeping the loop maps valid across calls; calling the optimiser or the
+ * correction for the caller.
  *
  * Gating (host only, no device work; ndt_sessions_loop_candidates gives exactly what ndt_sessions_find_loops will search).
  * This is the definition, on what ndt_sessions_trajectory returns (n poses, sub_first, sub_anchor) and the closed clouds'
@@ -1117,6 +1142,71 @@ typedef struct ndt_loop {             /* HOST; one per candidate, in candidate o
 } ndt_loop;
 int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop *out,
                             int *n_out, ndt_result *records_host);
+
+/* ---- Loop search over several old submaps per session, verified by ranged fitness --------------------------
+ * A robot that re-enters a corridor passes several old submaps, and an old submap never covers the whole newest scan: the
+ * points without a counterpart dominate PCL's full-cloud fitness, so ndt_sessions_find_loops rejects a correct pose in a
+ * partly overlapping submap.  These calls search up to NDT_LOOP_MAX_SUBMAPS submaps per session and accept on the fitness of
+ * the points within a range (ndt_fit_points' max_d2), given that enough of the scan lies within it.
+ *
+ * Gating.  Eligibility is exactly the rule above.  A session's candidates are its eligible submaps of smallest dist, at most
+ * max_submaps of them, in ascending (dist, submap index); the sessions come in ascending order; every candidate of a session
+ * has the same lattice, the one the rule above forms.  With max_submaps = 1 the output is byte-identical to
+ * ndt_sessions_loop_candidates / ndt_loop_gate.  `out` needs room for n_sessions * max_submaps (ndt_loop_gate_multi:
+ * max_submaps) candidates.  Refusals: those of the gating above, max_submaps outside 1 .. NDT_LOOP_MAX_SUBMAPS, max_d2 NaN or
+ * negative, min_overlap NaN or outside [0, 1].
+ *
+ * The search is ndt_sessions_find_loops' list over the J candidates of all sessions, with two differences.  Every session's
+ * newest scan is taken to the robot frame and filtered ONCE; all of that session's jobs name it.  Behind the multi-map match
+ * comes one ndt_fit_points_multi_dev stage on the match's own device arrays (the laid-out scans, the slots' maps with -1 for a
+ * dead slot, the records' transforms in place, max_d2; statistics only), whose J * top_k ndt_fit_stats travel back with the
+ * records.  Two host waits; the number of launches, copies and waits depends neither on the number of sessions nor on
+ * max_submaps.  The set owns up to NDT_LOOP_MAX_SUBMAPS loop maps per session, the slot is the candidate's rank, slot 0 is the
+ * map ndt_sessions_find_loops keeps; all are destroyed with the set.  The call changes nothing of the SLAM state.
+ *
+ * The decision, per candidate, on the host.  For slot c < n_cand, st = fit[c], r = record c:
+ *   usable_c = r.converged && st.n_in >= 1 && (double)st.n_in >= min_overlap * (double)st.n_points (one rounded product);
+ *   cand_cost[c] = usable_c ? st.fitness : 1e7;   ok_c = cand_cost[c] <= loop.max_cost;
+ *   best = the slot that is first by: ok before not ok; then the larger (usable_c ? st.n_in : 0); then the lower cand_cost;
+ *   then the lower c.  found = ok_best.  pose and edge come from the best record as ndt_sessions_find_loops forms them; with
+ *   n_cand == 0: best = -1, pose and rel 0.
+ * The inlier count ranks before the cost on purpose (ndt_relocalize's callers rank by ranged fitness alone): an alias that
+ * overlaps less has fewer inliers, each of them tighter, and the lowest ranged fitness alone would pick it.
+ *
+ * Guarantees.  (a) A candidate's loop.cand, status, n_cand, cand_index, cand_score and records are byte-identical to what
+ * ndt_sessions_find_loops gives for the same (session, submap, parameters); they do not depend on the other candidates or
+ * sessions named, nor on max_submaps.  (b) fit[c] is byte-identical to ndt_fit_points_batch on that submap's map, the session's
+ * filtered scan and record c's transform; fit is zero from n_cand on.  (c) A refused map (NDT_E_GRID or NDT_E_ARG from the
+ * build) costs its candidate alone; a session whose newest scan is empty, or filters to nothing, gives the empty record for
+ * each of its candidates; when every scan is empty the call queues nothing.  (d) ndt_sessions_get_stats: host_waits 2 (0 with
+ * no candidate or with all scans empty, 1 when no map could be built), sessions_stepped = J.
+ * Refusals: those of the gating, an open ndt_map_rebuild_begin on the context, more than 2^31 - 1 lattice poses over all
+ * candidates.  NDT_E_HIP on a dead set; a HIP failure inside the call kills the set as in a step.
+ * Out of scope: loops between sessions; keeping the loop maps valid across calls; calling the optimiser for the caller. */
+#define NDT_LOOP_MAX_SUBMAPS 4
+typedef struct ndt_loop_multi_params {
+  ndt_loop_params loop;     /* as for ndt_sessions_find_loops; loop.max_cost is compared with the RANGED cost above */
+  int    max_submaps;       /* 1 .. NDT_LOOP_MAX_SUBMAPS candidate submaps per session */
+  int    reserved;          /* 0 */
+  double max_d2;            /* m^2, inclusive: the range of the verification (ndt_fit_points' max_d2) */
+  double min_overlap;       /* 0 .. 1: share of the filtered scan that must lie within the range */
+} ndt_loop_multi_params;
+/* loop = ndt_loop_default_params, max_submaps 2, reserved 0, max_d2 0.09, min_overlap 0.5. */
+int ndt_loop_multi_default_params(ndt_loop_multi_params *p);
+/* ndt_loop_gate with up to p->max_submaps candidates (session 0) in (dist, submap) order; *n_out of them. */
+int ndt_loop_gate_multi(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor,
+                        const uint64_t *sub_offsets, int n_submaps, const ndt_loop_multi_params *p,
+                        ndt_loop_candidate *out, int *n_out);
+int ndt_sessions_loop_candidates_multi(const ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p,
+                                       ndt_loop_candidate *out, int *n_out);
+typedef struct ndt_loop_multi {        /* HOST; one per candidate, in candidate order */
+  ndt_loop      loop;                  /* every field as ndt_loop; cand_cost, best, found, pose, edge by the rule above */
+  ndt_fit_stats fit[NDT_LOOP_MAX_CAND];/* slot c's ranged statistics at record c's transform; zero from n_cand on */
+  int           rank;                  /* the candidate's place among its session's (0 = nearest) */
+  int           reserved;
+} ndt_loop_multi;
+int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p,
+                                  ndt_loop_multi *out, int *n_out, ndt_result *records_host);
 
 /* ---- The scan archive and ndt_sessions_occ_rebuild: occupancy grids that follow a correction -----------------
  * ndt_sessions_occ_integrate casts a session's newest scan at the pose it had at that step; after ndt_sessions_correct every beam

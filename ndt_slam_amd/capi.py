@@ -173,8 +173,23 @@ class Loop(C.Structure):
                 ("cand_cost", C.c_double * NDT_LOOP_MAX_CAND), ("pose", C.c_double * 3), ("edge", PgEdge)]
 
 
+NDT_LOOP_MAX_SUBMAPS = 4
+
+
+class LoopMultiParams(C.Structure):
+    """ndt_loop_multi_params (include/ndt_mi355x.h): the loop search over several submaps per session."""
+    _fields_ = [("loop", LoopParams), ("max_submaps", C.c_int), ("reserved", C.c_int), ("max_d2", C.c_double),
+                ("min_overlap", C.c_double)]
+
+
+class LoopMulti(C.Structure):
+    """ndt_loop_multi (include/ndt_mi355x.h): one candidate's search result with its slots' ranged statistics."""
+    _fields_ = [("loop", Loop), ("fit", FitStats * NDT_LOOP_MAX_CAND), ("rank", C.c_int), ("reserved", C.c_int)]
+
+
 LOOP_CANDIDATE_DTYPE = np.dtype(LoopCandidate)
 LOOP_DTYPE = np.dtype(Loop)                          # (its edge's first field is from_, as PgEdge's)
+LOOP_MULTI_DTYPE = np.dtype(LoopMulti)
 
 # (hand-written: the C field is `from`, a Python keyword, so the Structure's is from_)
 PG_EDGE_DTYPE = np.dtype([("from", "i4"), ("to", "i4"), ("rel", "f8", 3), ("info", "f8", 6)], align=True)
@@ -273,6 +288,8 @@ PROTOTYPES = {
     "ndt_lattice_select_multi_dev": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "ndt_fit_points_batch_dev": [_vp, _vp, _vp, _vp, _i, _sz, _i, _vp, _sz, _d, _vp, _vp, _vp],
     "ndt_fit_points_batch": [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _d, _vp, _vp],
+    "ndt_fit_points_multi_dev": [_vp, _vp, _i, _vp, _vp, _vp, _i, _sz, _i, _vp, _sz, _d, _vp, _vp, _vp],
+    "ndt_fit_points_multi": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _d, _vp, _vp],
     "ndt_occ_cell": [_P(OccGeometry), _d, _d, _P(C.c_int64), _P(C.c_int64)],
     "ndt_occ_create": [_vp, _P(OccGeometry), _P(_vp)],
     "ndt_occ_destroy": [_vp],
@@ -298,6 +315,10 @@ PROTOTYPES = {
     "ndt_loop_gate": [_vp, _sz, _vp, _vp, _vp, _i, _P(LoopParams), _P(LoopCandidate), _P(_i)],
     "ndt_sessions_loop_candidates": [_vp, _vp, _P(LoopParams), _vp, _P(_i)],
     "ndt_sessions_find_loops": [_vp, _vp, _P(LoopParams), _vp, _P(_i), _vp],
+    "ndt_loop_multi_default_params": [_P(LoopMultiParams)],
+    "ndt_loop_gate_multi": [_vp, _sz, _vp, _vp, _vp, _i, _P(LoopMultiParams), _vp, _P(_i)],
+    "ndt_sessions_loop_candidates_multi": [_vp, _vp, _P(LoopMultiParams), _vp, _P(_i)],
+    "ndt_sessions_find_loops_multi": [_vp, _vp, _P(LoopMultiParams), _vp, _P(_i), _vp],
     "ndt_sessions_archive_enable": [_vp],
     "ndt_sessions_archive_info": [_vp, _i, _P(_sz), _P(_sz)],
     "ndt_sessions_archive_scans": [_vp, _i, _sz, _sz, _vp, _sz, _vp, _P(_sz)],
@@ -533,6 +554,35 @@ def loop_gate(poses, sub_first, sub_anchor, sub_offsets, params):
     return out[0] if has.value else None
 
 
+def default_loop_multi_params(**kw):
+    """ndt_loop_multi_default_params; max_submaps, max_d2 and min_overlap by keyword, every other keyword a field of its
+    `loop` part (info: six numbers)."""
+    own = {k: kw.pop(k) for k in ("max_submaps", "max_d2", "min_overlap") if k in kw}
+    p = _defaults(LoopMultiParams, "ndt_loop_multi_default_params", own)
+    info = kw.pop("info", None)
+    for k, v in kw.items():
+        if not hasattr(p.loop, k):
+            raise AttributeError("ndt_loop_params has no field %r" % k)
+        setattr(p.loop, k, v)
+    if info is not None:
+        p.loop.info[:] = [float(v) for v in info]
+    return p
+
+
+def loop_gate_multi(poses, sub_first, sub_anchor, sub_offsets, params):
+    """ndt_loop_gate_multi (host only): loop_gate with up to params.max_submaps candidates, nearest first, as
+    LOOP_CANDIDATE_DTYPE records (possibly none)."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    first, anchor = np.ascontiguousarray(sub_first, dtype=np.int32), np.ascontiguousarray(sub_anchor, dtype=np.int32)
+    off = np.ascontiguousarray(sub_offsets, dtype=np.uint64)
+    if len(anchor) != len(first) or len(off) != len(first) + 1:
+        raise ValueError("loop_gate_multi needs one sub_anchor per submap and one more sub_offsets")
+    out, n = np.zeros(NDT_LOOP_MAX_SUBMAPS, dtype=LOOP_CANDIDATE_DTYPE), C.c_int()
+    _check(lib().ndt_loop_gate_multi(_ptr(poses), len(poses), _ptr(first), _ptr(anchor), off.ctypes.data, len(first), C.byref(params),
+                                     out.ctypes.data, C.byref(n)), "ndt_loop_gate_multi")
+    return out[:n.value]
+
+
 def pg_edge_between(from_pose, to_pose):
     """ndt_pg_edge_between: Pose2D::calMotion(to, from) -> the arc's rel (tx, ty, th[deg])."""
     a = np.ascontiguousarray(from_pose, dtype=np.float64).reshape(3)
@@ -626,6 +676,30 @@ def _tf4(tf):
     if tf.ndim != 2 or tf.shape[1] != 4:
         raise ValueError("expected a [B, 4] float32 array of (c, s, tx, ty) or a record array")
     return tf
+
+
+def fit_points_multi(ctx, maps, scans, offsets, tf, map_of=None, max_d2=DBL_MAX, shared_scan=False, want_d2=True, want_stats=True):
+    """ndt_fit_points_multi: Map.fit_points with match b searched in maps[map_of[b]] (map_of None: maps[b], one map per match),
+    in one search launch and one close launch on `ctx` -> (d2 float32 or None, stats FIT_STATS_DTYPE [B] or None).  A map_of
+    entry outside [0, len(maps)) gives that match alone +inf distances and stats (DBL_MAX, DBL_MAX, 0, 0, n_points, 0)."""
+    scans = _f32c(scans)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    tf = _tf4(tf)
+    B = len(tf)
+    nscan = 1 if shared_scan else B
+    if len(offsets) != nscan + 1:
+        raise ValueError("offsets needs one entry per scan and one more")
+    mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+    if mo is not None and len(mo) != B:
+        raise ValueError("map_of needs one entry per match")
+    mp, n = _map_handles(maps)
+    n_d2 = B * int(offsets[1] - offsets[0]) if shared_scan else int(offsets[-1])
+    d2 = np.zeros(n_d2, dtype=np.float32) if want_d2 else None
+    stats = np.zeros(B, dtype=FIT_STATS_DTYPE) if want_stats else None
+    ctx.check(lib().ndt_fit_points_multi(ctx.h, mp, n, None if mo is None else mo.ctypes.data, scans.ctypes.data, offsets.ctypes.data,
+                                         B, int(shared_scan), tf.ctypes.data, 16, float(max_d2), d2.ctypes.data if want_d2 else None,
+                                         stats.ctypes.data if want_stats else None), "ndt_fit_points_multi")
+    return d2, stats
 
 
 def rerank(records, stats):
@@ -837,6 +911,15 @@ class Context(_Handle):
         self.check(lib().ndt_align_batch_multi_dev(self.h, mp, n, map_of_ptr, scans_ptr, offsets_ptr, B, total_points,
                                                    int(shared_scan), inits_ptr, out_ptr, stream),
                    "ndt_align_batch_multi_dev")
+
+    def fit_points_multi_dev(self, maps, map_of_ptr, scans_ptr, offsets_ptr, B, total_points, tf_ptr, tf_stride, max_d2, d2_ptr,
+                             stats_ptr, shared_scan=False, stream=None):
+        """ndt_fit_points_multi_dev: `maps` a list of Map objects, map_of_ptr a device array of B int32 or None (match b in
+        maps[b]); every other pointer a device address (d2_ptr or stats_ptr may be None); asynchronous."""
+        mp, n = _map_handles(maps)
+        self.check(lib().ndt_fit_points_multi_dev(self.h, mp, n, map_of_ptr, scans_ptr, offsets_ptr, B, total_points, int(shared_scan),
+                                                  tf_ptr, tf_stride, float(max_d2), d2_ptr, stats_ptr, stream),
+                   "ndt_fit_points_multi_dev")
 
     def score_lattice_multi_dev(self, maps, scans_ptr, offsets_ptr, n_scans, total_points, jobs, score_ptr, pairs_ptr=None,
                                 stream=None):
@@ -1097,6 +1180,27 @@ class Sessions(_Handle):
         n, w = C.c_int(), self._active(which)
         self.ctx.check(lib().ndt_sessions_find_loops(self.h, None if w is None else w.ctypes.data, C.byref(params), out.ctypes.data,
                                                      C.byref(n), None if rec is None else rec.ctypes.data), "ndt_sessions_find_loops")
+        return (out[:n.value], rec[:n.value]) if want_records else out[:n.value]
+
+    def loop_candidates_multi(self, params, which=None):
+        """ndt_sessions_loop_candidates_multi: the candidates ndt_sessions_find_loops_multi would search -- up to
+        params.max_submaps per session, nearest first -- as LOOP_CANDIDATE_DTYPE records (host only)."""
+        out = np.zeros(self.n * NDT_LOOP_MAX_SUBMAPS, dtype=LOOP_CANDIDATE_DTYPE)
+        n, w = C.c_int(), self._active(which)
+        self.ctx.check(lib().ndt_sessions_loop_candidates_multi(self.h, None if w is None else w.ctypes.data, C.byref(params),
+                                                                out.ctypes.data, C.byref(n)), "ndt_sessions_loop_candidates_multi")
+        return out[:n.value]
+
+    def find_loops_multi(self, params, which=None, want_records=False):
+        """ndt_sessions_find_loops_multi: one LOOP_MULTI_DTYPE record per candidate; with want_records also the match records,
+        as [candidates, NDT_LOOP_MAX_CAND] RESULT_DTYPE (the first n_cand of a row are written)."""
+        room = self.n * NDT_LOOP_MAX_SUBMAPS
+        out = np.zeros(room, dtype=LOOP_MULTI_DTYPE)
+        rec = np.zeros((room, NDT_LOOP_MAX_CAND), dtype=RESULT_DTYPE) if want_records else None
+        n, w = C.c_int(), self._active(which)
+        self.ctx.check(lib().ndt_sessions_find_loops_multi(self.h, None if w is None else w.ctypes.data, C.byref(params),
+                                                           out.ctypes.data, C.byref(n), None if rec is None else rec.ctypes.data),
+                       "ndt_sessions_find_loops_multi")
         return (out[:n.value], rec[:n.value]) if want_records else out[:n.value]
 
     def stats(self):

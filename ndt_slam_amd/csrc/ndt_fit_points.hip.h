@@ -1,5 +1,6 @@
 // ndt_fit_points.hip.h -- ndt_fit_points_batch_dev: the distance of every scan point to its nearest raw map point, in the
-// caller's order, and getFitnessScore(max_range) from them (row a7; src/PoseEstimator.cpp:43 calls it without a range).
+// caller's order, and getFitnessScore(max_range) from them (row a7; src/PoseEstimator.cpp:43 calls it without a range);
+// ndt_fit_points_multi_dev: the same with one map per match, through a table of views.
 // Part of libndt_mi355x.so: included by ndt_mi355x.hip inside its anonymous namespace behind ndt_fitness.hip.h, whose
 // search (lane_query -- nearest_prep / nearest_home / nearest_ring1_wave -- then nearest_far: path 2 of
 // tests/test_gpu_fitness_geometry.py) it uses as it is.  Not a standalone header.
@@ -27,20 +28,34 @@ __device__ __forceinline__ Tf32 fit_tf_of(const unsigned char *__restrict__ tf, 
 // fitness_points_kernel<SSE, false> over the scan as the caller laid it out: the same waves (whole, a chunk each, lanes past
 // the end without a query), the same search, the workgroups numbered by fit_block_of.  d2 (may be null): one float per
 // point at the point's own index; parts (may be null): the chunk's sums and counts.
-template <bool SSE>
+// MULTI (ndt_fit_points_multi_dev): match b is searched in views[match_map_index] instead of M_arg, the way
+// fitness_points_kernel<.., MULTI> takes its table -- the view is this workgroup's only difference, so a match's d2 and
+// parts are the single-map instance's.  A match without a map (index -1) reads nothing through the index: its workgroups
+// write +INFINITY per point and empty parts (which close to {DBL_MAX, DBL_MAX, 0, 0, n, 0}) and return.
+template <bool SSE, bool MULTI = false>
 __global__ void __launch_bounds__(256, kFitOcc)
-fit_points_kernel(MapView M, const float2 *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
+fit_points_kernel(MapView M_arg, const float2 *__restrict__ scans, const unsigned long long *__restrict__ offsets, int B,
                   int shared_scan, const unsigned char *__restrict__ tf, size_t tf_stride, double max_d2,
-                  float *__restrict__ d2, FitPtsPart *__restrict__ parts, int gx) {
+                  float *__restrict__ d2, FitPtsPart *__restrict__ parts, int gx, const MapView *__restrict__ views = nullptr,
+                  const int *__restrict__ map_of = nullptr, int n_maps = 0) {
   __shared__ RingLds ring[256 / 64];
   int b, bx;
   if (!fit_block_of(gx, B, b, bx)) return;
+  const int mi = match_map_index<MULTI>(map_of, n_maps, b);
   const ScanSpan sp = scan_span(offsets, shared_scan, b);
   const int n = sp.n;
-  const Tf32 T = fit_tf_of(tf, tf_stride, b);
-  const float2 *pts = scans + sp.o0;
   float *out = d2 ? d2 + sp.slot(shared_scan, b) : nullptr;
   FitPtsPart *part = parts ? parts + fit_part_of(sp, shared_scan, b) : nullptr;
+  if (mi < 0) {                                                    // (workgroup-uniform; MULTI only)
+    for (int i = bx * (int)blockDim.x + (int)threadIdx.x; i < n; i += gx * (int)blockDim.x) {
+      if (out) out[i] = INFINITY;
+      if (part && (i & 63) == 0) part[i >> 6] = FitPtsPart{0.0, 0.0, 0.0, 0.0};
+    }
+    return;
+  }
+  const MapView M = MULTI ? views[mi] : M_arg;
+  const Tf32 T = fit_tf_of(tf, tf_stride, b);
+  const float2 *pts = scans + sp.o0;
   for (int i0 = bx * (int)blockDim.x + (int)(threadIdx.x & ~63u); i0 < n; i0 += gx * (int)blockDim.x) {
     const int i = i0 + (int)(threadIdx.x & 63u);
     const LaneQuery Q = lane_query<SSE>(M, ring[threadIdx.x >> 6], T, pts, i, n);

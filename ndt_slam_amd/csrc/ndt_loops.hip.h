@@ -1,7 +1,8 @@
-// Loop search on a session set (ndt_sessions_loop_candidates, ndt_sessions_find_loops): the host gating of one
-// candidate submap per session, and the search of all candidates in one set of launches -- the newest scans into the robot
-// frame, the pre-filter, the batched build of the old submaps' maps, the multi-job sweep and pick (ndt_score.hip.h), the
-// candidates' guesses, the multi-map match.  Included at the end of ndt_mi355x.hip (one translation unit).  Two kernels of
+// Loop search on a session set (ndt_sessions_loop_candidates, ndt_sessions_find_loops; their _multi forms:
+// 4.19): the host gating of one candidate submap per session, or of several, and the search of all candidates in one set of
+// launches -- the newest scans into the robot frame, the pre-filter, the batched build of the old submaps' maps, the multi-job
+// sweep and pick (ndt_score.hip.h), the candidates' guesses, the multi-map match and, for the _multi form, the multi-map
+// ranged verification (ndt_fit_points.hip.h).  Included at the end of ndt_mi355x.hip (one translation unit).  Two kernels of
 // its own:
 //   loop_scan_kernel     every candidate's newest stored scan from the map frame into the robot frame (repose_point)
 //   loop_guess_kernel    per (candidate, slot): the lattice pose of the slot's pick as initial guess, the candidate's filtered
@@ -10,7 +11,7 @@
 namespace {
 
 struct LpScan { const float2 *src; unsigned long long n, off; double pose[3]; };      // a newest scan, its place in the scratch, the session's last pose
-struct LpJob { Lattice L; unsigned long long vol; };                                  // a candidate's lattice and where its volume starts
+struct LpJob { Lattice L; unsigned long long vol; int scan, pad; };                   // a candidate's lattice, where its volume starts, its newest scan among the call's
 
 // repose_rows_kernel's shape, out of place: new pose (0, 0, 0).  A last pose that is bit-equal to it keeps the points' bytes,
 // as ndt_repose_points does.
@@ -29,15 +30,27 @@ loop_scan_kernel(const LpScan *__restrict__ tab, int n_rows, float2 *__restrict_
   }
 }
 
-// Workgroup b = j K + c: slot c of candidate j.  Scan b of the match launch is candidate j's filtered scan, at
-// rep_off[b] = K * flt_off[j] + c * len(j): the K copies of a scan lie one behind the other, the candidates in order.
+// Workgroup b = j K + c: slot c of candidate j.  Scan b of the match launch is candidate j's filtered scan -- scan jobs[j].scan
+// of the filtered ones, which several candidates may name -- at rep_off[b] = K * (the lengths of the candidates before j) +
+// c * len(j): the K copies of a scan lie one behind the other, the candidates in order.  (The lengths exist on the device
+// only; every workgroup adds up those before its candidate -- whole numbers, in any order.)
 __global__ void __launch_bounds__(256)
 loop_guess_kernel(const LpJob *__restrict__ jobs, int J, int K, const float2 *__restrict__ flt, const unsigned long long *__restrict__ flt_off,
                   const unsigned long long *__restrict__ cand, const int *__restrict__ n_cand, const double *__restrict__ score,
                   float2 *__restrict__ rep, unsigned long long *__restrict__ rep_off, double *__restrict__ inits,
                   double *__restrict__ cand_score, int *__restrict__ map_of) {
+  __shared__ unsigned long long before[256];
   const int b = blockIdx.x, j = b / K, c = b - j * K;
-  const unsigned long long o0 = flt_off[j], len = flt_off[j + 1] - o0, at = (unsigned long long)K * o0 + (unsigned long long)c * len;
+  unsigned long long mine = 0;
+  for (int q = threadIdx.x; q < j; q += blockDim.x) { const int sq = jobs[q].scan; mine += flt_off[sq + 1] - flt_off[sq]; }
+  before[threadIdx.x] = mine;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) before[threadIdx.x] += before[threadIdx.x + w];
+    __syncthreads();
+  }
+  const int sj = jobs[j].scan;
+  const unsigned long long o0 = flt_off[sj], len = flt_off[sj + 1] - o0, at = (unsigned long long)K * before[0] + (unsigned long long)c * len;
   if (threadIdx.x == 0) {
     const LpJob Jb = jobs[j];
     double p[3] = {0.0, 0.0, 0.0}, s = 0.0;
@@ -67,16 +80,17 @@ int loop_check_params(ndt_ctx *ctx, const ndt_loop_params *p, const std::string 
   return NDT_OK;
 }
 
-// The gating of one trajectory as include/ndt_mi355x.h defines it (ndt_loop_gate's arguments, checked by the caller); false:
-// no candidate.  best->session is the caller's to set.
-bool loop_gate_one(const double *T, int n, const int *sub_first, const int *sub_anchor, const uint64_t *closed_off, int n_closed,
-                   const ndt_loop_params &p, ndt_loop_candidate *best) {
-  if (n < 1 || n_closed < 2) return false;
+// The gating of one trajectory as include/ndt_mi355x.h defines it (ndt_loop_gate's arguments, checked by the caller): the
+// eligible submaps of smallest dist, max_k of them at the most, in ascending (dist, submap), appended to *out as candidates of
+// `session`, every one with the session's one lattice.  Returns how many.  The single-candidate gating is max_k = 1.
+int loop_gate_k(const double *T, int n, const int *sub_first, const int *sub_anchor, const uint64_t *closed_off, int n_closed,
+                const ndt_loop_params &p, int session, int max_k, std::vector<ndt_loop_candidate> *out) {
+  if (n < 1 || n_closed < 2) return 0;
   auto dist = [&](int a, int b) {
     const double dx = T[3 * a] - T[3 * b], dy = T[3 * a + 1] - T[3 * b + 1];
     return std::sqrt(dx * dx + dy * dy);
   };
-  bool have = false;
+  const size_t at = out->size();
   for (int m = 0; m <= n_closed - 2; ++m) {
     const int first = sub_first[m], last = sub_first[m + 1] - 1;
     if (last < first || closed_off[m + 1] == closed_off[m]) continue;
@@ -85,22 +99,32 @@ bool loop_gate_one(const double *T, int n, const int *sub_first, const int *sub_
     if (!(path >= p.min_path)) continue;
     double d = dist(n - 1, first); int near = first;
     for (int k = first + 1; k <= last; ++k) { const double dk = dist(n - 1, k); if (dk < d) { d = dk; near = k; } }
-    if (!(d <= p.radius) || (have && !(d < best->dist))) continue;
-    have = true;
-    best->submap = m; best->anchor_scan = sub_anchor[m]; best->newest_scan = n - 1; best->nearest_scan = near;
-    best->dist = d; best->path = path;
+    if (!(d <= p.radius)) continue;
+    // (the eligible ones so far are in (dist, submap) order: this one goes behind every one that is not farther)
+    size_t pos = out->size();
+    while (pos > at && d < (*out)[pos - 1].dist) --pos;
+    if (pos - at >= (size_t)max_k) continue;
+    ndt_loop_candidate c;
+    memset(&c, 0, sizeof(c));
+    c.session = session; c.submap = m; c.anchor_scan = sub_anchor[m]; c.newest_scan = n - 1; c.nearest_scan = near;
+    c.dist = d; c.path = path;
+    out->insert(out->begin() + (ptrdiff_t)pos, c);
+    if (out->size() - at > (size_t)max_k) out->pop_back();
   }
-  if (!have) return false;
+  if (out->size() == at) return 0;
   const double tx = T[3 * (n - 1)], ty = T[3 * (n - 1) + 1], yaw = T[3 * (n - 1) + 2] * M_PI / 180;      // DEG2RAD
-  ndt_pose_lattice &L = best->lattice;
+  ndt_pose_lattice L;
+  memset(&L, 0, sizeof(L));
   L.x0 = tx - (double)p.half_x * p.step_xy; L.y0 = ty - (double)p.half_y * p.step_xy; L.yaw0 = yaw - (double)p.half_yaw * p.step_yaw;
   L.step_x = p.step_xy; L.step_y = p.step_xy; L.step_yaw = p.step_yaw;
   L.nx = 2 * p.half_x + 1; L.ny = 2 * p.half_y + 1; L.nyaw = 2 * p.half_yaw + 1;
-  return true;
+  for (size_t i = at; i < out->size(); ++i) (*out)[i].lattice = L;
+  return (int)(out->size() - at);
 }
 
-// ... of the sessions of a set that `which` names; out: one candidate per session that has one, in session order.
-void loop_gate(const ndt_sessions *s, const unsigned char *which, const ndt_loop_params &p, std::vector<ndt_loop_candidate> *out) {
+// ... of the sessions of a set that `which` names; out: up to max_k candidates per session, the sessions in ascending order.
+void loop_gate(const ndt_sessions *s, const unsigned char *which, const ndt_loop_params &p, std::vector<ndt_loop_candidate> *out,
+               int max_k = 1) {
   out->clear();
   std::vector<int> anchor;
   for (int i = 0; i < s->S; ++i) {
@@ -108,98 +132,132 @@ void loop_gate(const ndt_sessions *s, const unsigned char *which, const ndt_loop
     if ((which && !which[i]) || !Q.started || Q.n_closed < 2) continue;
     anchor.resize((size_t)Q.n_closed);
     for (int m = 0; m < Q.n_closed; ++m) anchor[(size_t)m] = ss_anchor(Q, m);
-    ndt_loop_candidate c{};
-    c.session = i;
-    if (loop_gate_one(Q.traj.data(), Q.n_poses, Q.sub_first.data(), anchor.data(), Q.closed_off.data(), Q.n_closed, p, &c)) out->push_back(c);
+    loop_gate_k(Q.traj.data(), Q.n_poses, Q.sub_first.data(), anchor.data(), Q.closed_off.data(), Q.n_closed, p, i, max_k, out);
   }
 }
 
-// The search of the candidates C (DESIGN.md 4.15's list); the arguments have passed the entry point's refusals.
+// The set's loop map of a session's candidate of rank r (slot 0: the one ndt_sessions_find_loops keeps).
+ndt_map *&loop_map_slot(SsSession &Q, int r) { return r == 0 ? Q.loop_map : Q.loop_map_more[r - 1]; }
+
+// The decision of ndt_sessions_find_loops_multi for one candidate whose records and ranged statistics are in (include/
+// ndt_mi355x.h states the rule): cand_cost and best; returns ok_best.
+bool loop_decide_ranged(const ndt_loop_multi_params &mp, const ndt_result *res, ndt_loop_multi *M) {
+  ndt_loop &L = M->loop;
+  bool best_ok = false; uint32_t best_in = 0;
+  for (int c = 0; c < L.n_cand; ++c) {
+    const ndt_fit_stats &st = M->fit[c];
+    const bool usable = res[c].converged && st.n_in >= 1 && (double)st.n_in >= mp.min_overlap * (double)st.n_points;
+    L.cand_cost[c] = usable ? st.fitness : 1e7;
+    const bool ok = L.cand_cost[c] <= mp.loop.max_cost;
+    const uint32_t in = usable ? st.n_in : 0;
+    const bool first = L.best < 0 || (ok != best_ok ? ok : in != best_in ? in > best_in : L.cand_cost[c] < L.cand_cost[L.best]);
+    if (first) { L.best = c; best_ok = ok; best_in = in; }
+  }
+  return best_ok;
+}
+
+// The search of the candidates C (DESIGN.md 4.15's list; 4.19: mp and mout, ndt_sessions_find_loops_multi -- several candidates
+// of a session in a row, rank by rank, one newest scan per session, the ranged verification behind the match); the arguments
+// have passed the entry point's refusals.  `out` (the single search) or `mout`.
 int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<ndt_loop_candidate> &C, uint64_t P, ndt_loop *out,
-                  ndt_result *records_host) {
+                  ndt_result *records_host, const ndt_loop_multi_params *mp = nullptr, ndt_loop_multi *mout = nullptr) {
   ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ndt_sessions_stats stats{};
   const size_t J = C.size(), K = (size_t)p.top_k, B = J * K;
+  const char *fn = mp ? "ndt_sessions_find_loops_multi" : "ndt_sessions_find_loops";
   stats.sessions_stepped = (int)J;
+  auto loop_of = [&](size_t j) -> ndt_loop & { return mout ? mout[j].loop : out[j]; };
+  // candidate j's newest scan among the call's nS (one per session: the candidates of a session lie in a row) and its rank
+  std::vector<int> scan_of(J), rank(J);
+  size_t nS = 0;
   for (size_t j = 0; j < J; ++j) {
-    memset(&out[j], 0, sizeof(out[j]));
-    out[j].cand = C[j]; out[j].best = -1;
-    out[j].edge.from = C[j].anchor_scan; out[j].edge.to = C[j].newest_scan;
-    memcpy(out[j].edge.info, p.info, sizeof(p.info));
+    const bool same = j > 0 && C[j].session == C[j - 1].session;
+    rank[j] = same ? rank[j - 1] + 1 : 0;
+    scan_of[j] = same ? scan_of[j - 1] : (int)nS++;
+    if (mout) { memset(&mout[j], 0, sizeof(mout[j])); mout[j].rank = rank[j]; }
+    ndt_loop &L = loop_of(j);
+    memset(&L, 0, sizeof(L));
+    L.cand = C[j]; L.best = -1;
+    L.edge.from = C[j].anchor_scan; L.edge.to = C[j].newest_scan;
+    memcpy(L.edge.info, p.info, sizeof(p.info));
   }
-  // (1) the table: the newest scans' rows | their offsets in the scratch, with an empty scan J behind them -- the scan of a
-  // candidate whose map is refused below: its poses then score nothing and nothing is picked | lattices and volume offsets
-  std::vector<LpScan> rows(J); std::vector<uint64_t> raw_off(J + 2, 0), vol(J + 1, 0);
+  // (1) the table: the newest scans' rows | their offsets in the scratch, with an empty scan nS behind them -- the scan of a
+  // candidate whose map is refused below: its poses then score nothing and nothing is picked | lattices, volume offsets, scans
+  std::vector<LpScan> rows(nS); std::vector<uint64_t> raw_off(nS + 2, 0), vol(J + 1, 0);
   std::vector<ndt_score_job> jobs(J);
-  size_t longest = 0;
+  size_t longest = 0, NJ = 0;      // NJ: the points of every candidate's scan, a shared one counted once per candidate
   for (size_t j = 0; j < J; ++j) {
     const SsSession &Q = s->ses[(size_t)C[j].session];
-    const size_t k = Q.scan_off.size() - 2;
+    const size_t k = Q.scan_off.size() - 2, u = (size_t)scan_of[j];
     const uint64_t n = Q.scan_off[k + 1] - Q.scan_off[k];
-    const double *last = Q.traj.data() + 3 * ((size_t)Q.n_poses - 1);
-    rows[j] = LpScan{Q.store[Q.cur].p + Q.scan_off[k], n, raw_off[j], {last[0], last[1], last[2]}};
-    raw_off[j + 1] = raw_off[j] + n;
-    longest = std::max(longest, (size_t)n);
+    if (rank[j] == 0) {
+      const double *last = Q.traj.data() + 3 * ((size_t)Q.n_poses - 1);
+      rows[u] = LpScan{Q.store[Q.cur].p + Q.scan_off[k], n, raw_off[u], {last[0], last[1], last[2]}};
+      raw_off[u + 1] = raw_off[u] + n;
+      longest = std::max(longest, (size_t)n);
+    }
+    NJ += (size_t)n;
     vol[j + 1] = vol[j] + P;
-    jobs[j] = ndt_score_job{(int)j, (int)j, C[j].lattice};
+    jobs[j] = ndt_score_job{(int)j, scan_of[j], C[j].lattice};
   }
-  const size_t N = (size_t)raw_off[J];
-  raw_off[J + 1] = raw_off[J];
+  const size_t N = (size_t)raw_off[nS];
+  raw_off[nS + 1] = raw_off[nS];
   if (N == 0) { s->stats = stats; return NDT_OK; }      // every newest scan is empty: nothing to search with
   Regions A;
-  const size_t a_rows = A.take(J * sizeof(LpScan), 256), a_off = A.take((J + 2) * 8, 256), a_jobs = A.take(J * sizeof(LpJob), 256);
+  const size_t a_rows = A.take(nS * sizeof(LpScan), 256), a_off = A.take((nS + 2) * 8, 256), a_jobs = A.take(J * sizeof(LpJob), 256);
   Regions D;      // the device scratch
-  const size_t d_robot = D.take(N * 8, 256), d_flt = D.take(N * 8, 256), d_foff = D.take((J + 2) * 8, 256), d_score = D.take(J * P * 8, 256),
-               d_pairs = D.take(J * P * 4, 256), d_cand = D.take(B * 8, 256), d_ncand = D.take(J * 4, 256), d_rep = D.take(K * N * 8, 256),
+  const size_t d_robot = D.take(N * 8, 256), d_flt = D.take(N * 8, 256), d_foff = D.take((nS + 2) * 8, 256), d_score = D.take(J * P * 8, 256),
+               d_pairs = D.take(J * P * 4, 256), d_cand = D.take(B * 8, 256), d_ncand = D.take(J * 4, 256), d_rep = D.take(K * NJ * 8, 256),
                d_roff = D.take((B + 1) * 8, 256), d_init = D.take(B * 24, 256), d_cs = D.take(B * 8, 256), d_mapof = D.take(B * 4, 256),
-               d_res = D.take(B * sizeof(ndt_result), 256);
+               d_res = D.take(B * sizeof(ndt_result), 256), d_fit = mp ? D.take(B * sizeof(ndt_fit_stats), 256) : 0;
   Regions R;      // host wait 2's read-back
-  const size_t r_res = R.take(B * sizeof(ndt_result)), r_cand = R.take(B * 8), r_cs = R.take(B * 8), r_ncand = R.take(J * 4);
+  const size_t r_res = R.take(B * sizeof(ndt_result)), r_cand = R.take(B * 8), r_cs = R.take(B * 8), r_ncand = R.take(J * 4),
+               r_fit = mp ? R.take(B * sizeof(ndt_fit_stats)) : 0;
   LP_TRY(s->lp_tab.reserve(ctx, A.end)); LP_TRY(s->d_lp_tab.ensure(ctx, A.end)); LP_TRY(s->lp.ensure(ctx, D.end)); LP_TRY(s->h_back.ensure(ctx, R.end));
   unsigned char *h = s->lp_tab.h.p, *da = s->d_lp_tab.p, *dv = s->lp.p;
-  memcpy(h + a_rows, rows.data(), J * sizeof(LpScan));
-  memcpy(h + a_off, raw_off.data(), (J + 2) * 8);
-  for (size_t j = 0; j < J; ++j) A.at<LpJob>(h, a_jobs)[j] = LpJob{lattice_of(C[j].lattice), vol[j]};
+  memcpy(h + a_rows, rows.data(), nS * sizeof(LpScan));
+  memcpy(h + a_off, raw_off.data(), (nS + 2) * 8);
+  for (size_t j = 0; j < J; ++j) A.at<LpJob>(h, a_jobs)[j] = LpJob{lattice_of(C[j].lattice), vol[j], scan_of[j], 0};
   HIP_TRY(ctx, s->lp_tab.upload(da, 0, A.end, st));
   stats.h2d_bytes += A.end;
   float *robot = D.at<float>(dv, d_robot), *flt = D.at<float>(dv, d_flt);
   uint64_t *flt_off = D.at<uint64_t>(dv, d_foff);
-  // (2) the newest scans in the robot frame, (3) filtered as a step filters its source
-  loop_scan_kernel<<<dim3((unsigned)std::min<size_t>(64, longest / 256 + 1), (unsigned)std::min<size_t>(J, 65535)), 256, 0, st>>>(
-      (const LpScan *)(da + a_rows), (int)J, (float2 *)robot);
+  // (2) the newest scans in the robot frame, (3) filtered as a step filters its source -- each once, whoever names it
+  loop_scan_kernel<<<dim3((unsigned)std::min<size_t>(64, longest / 256 + 1), (unsigned)std::min<size_t>(nS, 65535)), 256, 0, st>>>(
+      (const LpScan *)(da + a_rows), (int)nS, (float2 *)robot);
   HIP_TRY(ctx, hipGetLastError());
-  LP_TRY(ndt_prefilter_batch_dev(ctx, robot, sizeof(float2), (const uint64_t *)(da + a_off), (int)J + 1, N, s->prm.leaf, flt, flt_off, st));
-  // (4) the old submaps' maps, each session's own from call to call (host wait 1: the bounding boxes); a refused build costs
-  // its candidate alone
+  LP_TRY(ndt_prefilter_batch_dev(ctx, robot, sizeof(float2), (const uint64_t *)(da + a_off), (int)nS + 1, N, s->prm.leaf, flt, flt_off, st));
+  // (4) the old submaps' maps, each session's own from call to call, a slot per rank (host wait 1: the bounding boxes); a
+  // refused build costs its candidate alone
   std::vector<const float *> bxy(J); std::vector<size_t> bn(J); std::vector<ndt_params> bp(J, s->prm.match);
   std::vector<ndt_map *> maps(J); std::vector<int> code(J, NDT_OK);
   for (size_t j = 0; j < J; ++j) {
-    const SsSession &Q = s->ses[(size_t)C[j].session];
+    SsSession &Q = s->ses[(size_t)C[j].session];
     const uint64_t a = Q.closed_off[(size_t)C[j].submap];
     bxy[j] = (const float *)(Q.closed.p + a); bn[j] = (size_t)(Q.closed_off[(size_t)C[j].submap + 1] - a);
-    maps[j] = Q.loop_map;
+    maps[j] = loop_map_slot(Q, rank[j]);
   }
-  LP_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), "ndt_sessions_find_loops"));
-  LP_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), "ndt_sessions_find_loops", code.data()));
+  LP_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn));
+  LP_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn, code.data()));
   stats.host_waits++; stats.d2h_bytes += J * 16 * sizeof(unsigned);
   const ndt_map *any = nullptr;
   for (size_t j = 0; j < J; ++j) {
-    out[j].status = code[j];
+    loop_of(j).status = code[j];
     if (code[j] != NDT_OK) continue;
-    s->ses[(size_t)C[j].session].loop_map = maps[j];
+    loop_map_slot(s->ses[(size_t)C[j].session], rank[j]) = maps[j];
     if (!any) any = maps[j];
   }
   if (!any) { s->stats = stats; return NDT_OK; }      // no map at all: nobody is found
   std::vector<const ndt_map *> rd(J);
   for (size_t j = 0; j < J; ++j) {
     rd[j] = code[j] == NDT_OK ? maps[j] : any;
-    if (code[j] != NDT_OK) jobs[j].scan = (int)J;      // (the empty scan)
+    if (code[j] != NDT_OK) jobs[j].scan = (int)nS;      // (the empty scan)
   }
   // (5) the sweep, (6) the pick, (7) the guesses and the scans' copies, (8) the match
   double *score = D.at<double>(dv, d_score); uint32_t *pairs = D.at<uint32_t>(dv, d_pairs);
   uint64_t *cand = D.at<uint64_t>(dv, d_cand); int *n_cand = D.at<int>(dv, d_ncand);
-  LP_TRY(score_multi(ctx, rd.data(), (int)J, flt, flt_off, (int)J + 1, N, longest, jobs.data(), (int)J, score, pairs, vol.data(), st));
+  LP_TRY(score_multi(ctx, rd.data(), (int)J, flt, flt_off, (int)nS + 1, N, longest, jobs.data(), (int)J, score, pairs, vol.data(), st));
   LP_TRY(ndt_lattice_select_multi_dev(ctx, jobs.data(), (int)J, score, pairs, vol.data(), p.top_k, p.local_max, cand, n_cand, st));
   stats.h2d_bytes += J * (sizeof(ScoreJob) + sizeof(PickJob)) + (J + 1) * 8;
   loop_guess_kernel<<<(unsigned)B, 256, 0, st>>>((const LpJob *)(da + a_jobs), (int)J, (int)K, (const float2 *)flt, (const unsigned long long *)flt_off,
@@ -208,35 +266,49 @@ int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<n
                                                 D.at<int>(dv, d_mapof));
   HIP_TRY(ctx, hipGetLastError());
   LP_TRY(ndt_align_batch_multi_dev(ctx, rd.data(), (int)J, D.at<int>(dv, d_mapof), D.at<float>(dv, d_rep), D.at<uint64_t>(dv, d_roff), (int)B,
-                                   K * N, 0, D.at<double>(dv, d_init), D.at<ndt_result>(dv, d_res), st));
+                                   K * NJ, 0, D.at<double>(dv, d_init), D.at<ndt_result>(dv, d_res), st));
+  // (8b) the ranged verification on the match's own arrays: every slot's statistics at its record's transform, no d2; a dead
+  // slot (map_of -1) reads no map
+  if (mp) {
+    LP_TRY(ndt_fit_points_multi_dev(ctx, rd.data(), (int)J, D.at<int>(dv, d_mapof), D.at<float>(dv, d_rep), D.at<uint64_t>(dv, d_roff), (int)B,
+                                    K * NJ, 0, &D.at<ndt_result>(dv, d_res)->T00, sizeof(ndt_result), mp->max_d2, nullptr,
+                                    D.at<ndt_fit_stats>(dv, d_fit), st));
+    stats.h2d_bytes += J * sizeof(MapView);
+  }
   // (9) host wait 2
   unsigned char *hb = s->h_back.p;
   HIP_TRY(ctx, hipMemcpyAsync(hb + r_res, dv + d_res, B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(hb + r_cand, dv + d_cand, B * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(hb + r_cs, dv + d_cs, B * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(hb + r_ncand, dv + d_ncand, J * 4, hipMemcpyDeviceToHost, st));
+  if (mp) HIP_TRY(ctx, hipMemcpyAsync(hb + r_fit, dv + d_fit, B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.host_waits++; stats.d2h_bytes += B * (sizeof(ndt_result) + 16) + J * 4;
+  stats.host_waits++; stats.d2h_bytes += B * (sizeof(ndt_result) + 16 + (mp ? sizeof(ndt_fit_stats) : 0)) + J * 4;
   const ndt_result *res = R.at<ndt_result>(hb, r_res);
   const uint64_t *h_cand = R.at<uint64_t>(hb, r_cand); const double *h_cs = R.at<double>(hb, r_cs); const int *h_n = R.at<int>(hb, r_ncand);
   for (size_t j = 0; j < J; ++j) {
-    ndt_loop &L = out[j];
+    ndt_loop &L = loop_of(j);
     if (L.status != NDT_OK) continue;
     L.n_cand = h_n[j];
-    double best_cost = 0.0;
+    bool ok = false;
     for (int c = 0; c < L.n_cand; ++c) {
       const ndt_result &r = res[j * K + (size_t)c];
       L.cand_index[c] = h_cand[j * K + (size_t)c]; L.cand_score[c] = h_cs[j * K + (size_t)c];
-      L.cand_cost[c] = r.converged ? r.fitness : 1e7;      // (src/PoseEstimator.cpp:43-46, as relocalize_impl)
-      if (L.best < 0 || L.cand_cost[c] < best_cost) { L.best = c; best_cost = L.cand_cost[c]; }
+      if (mp) mout[j].fit[c] = R.at<ndt_fit_stats>(hb, r_fit)[j * K + (size_t)c];
+      else {
+        L.cand_cost[c] = r.converged ? r.fitness : 1e7;      // (src/PoseEstimator.cpp:43-46, as relocalize_impl)
+        if (L.best < 0 || L.cand_cost[c] < L.cand_cost[L.best]) L.best = c;
+      }
       if (records_host) records_host[j * NDT_LOOP_MAX_CAND + (size_t)c] = r;
     }
+    if (mp) ok = loop_decide_ranged(*mp, res + j * K, &mout[j]);
     if (L.best < 0) continue;
+    if (!mp) ok = L.cand_cost[L.best] <= p.max_cost;
     const ndt_result &w = res[j * K + (size_t)L.best];
     L.pose[0] = w.pose[0]; L.pose[1] = w.pose[1]; L.pose[2] = w.pose[2] * 180 / M_PI;      // RAD2DEG
     const SsSession &Q = s->ses[(size_t)C[j].session];
     // (a pose that is not finite leaves rel at 0: the cost rule keeps such a record from being found)
-    if (ndt_pg_edge_between(Q.traj.data() + 3 * (size_t)C[j].anchor_scan, L.pose, &L.edge) == NDT_OK) L.found = best_cost <= p.max_cost;
+    if (ndt_pg_edge_between(Q.traj.data() + 3 * (size_t)C[j].anchor_scan, L.pose, &L.edge) == NDT_OK) L.found = ok;
   }
   s->stats = stats;
   return NDT_OK;
@@ -248,6 +320,68 @@ int loop_entry_checks(const ndt_sessions *s, const ndt_loop_params *p, const voi
   const std::string f(fn);
   if (!p || !out || !n_out) return fail(s->ctx, NDT_E_ARG, f + ": NULL params or outputs");
   return loop_check_params(s->ctx, p, f, P);
+}
+
+// The refusals ndt_loop_multi_params adds to those of its `loop` part.
+int loop_check_multi_params(ndt_ctx *ctx, const ndt_loop_multi_params *p, const std::string &f, uint64_t *P) {
+  const int rc = loop_check_params(ctx, &p->loop, f, P);
+  if (rc) return rc;
+  if (p->max_submaps < 1 || p->max_submaps > NDT_LOOP_MAX_SUBMAPS)
+    return fail(ctx, NDT_E_ARG, f + ": max_submaps must be in 1 .. " + std::to_string(NDT_LOOP_MAX_SUBMAPS));
+  if (!(p->max_d2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_d2 is NaN or negative");
+  if (!(p->min_overlap >= 0.0 && p->min_overlap <= 1.0)) return fail(ctx, NDT_E_ARG, f + ": min_overlap is NaN or outside [0, 1]");
+  return NDT_OK;
+}
+
+int loop_multi_entry_checks(const ndt_sessions *s, const ndt_loop_multi_params *p, const void *out, const int *n_out, const char *fn,
+                            uint64_t *P) {
+  const int rc = check_set(s, 0, false, fn);
+  if (rc) return rc;
+  const std::string f(fn);
+  if (!p || !out || !n_out) return fail(s->ctx, NDT_E_ARG, f + ": NULL params or outputs");
+  return loop_check_multi_params(s->ctx, p, f, P);
+}
+
+// Both searches behind their parameters' refusals: the remaining refusals, the gating, the search; a HIP failure kills the set.
+int loop_search_entry(ndt_sessions *s, const unsigned char *which, const ndt_loop_params &p, uint64_t P, const char *fn, ndt_loop *out,
+                      const ndt_loop_multi_params *mp, ndt_loop_multi *mout, int *n_out, ndt_result *records_host) {
+  ndt_ctx *ctx = s->ctx;
+  const std::string f(fn);
+  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  std::vector<ndt_loop_candidate> C;
+  loop_gate(s, which, p, &C, mp ? mp->max_submaps : 1);
+  if (C.size() * P > (uint64_t)INT32_MAX)
+    return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
+  *n_out = (int)C.size();
+  if (C.empty()) { s->stats = ndt_sessions_stats{}; return NDT_OK; }
+  const int rc = ss_find_loops(s, p, C, P, out, records_host, mp, mout);
+  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
+    s->dead = true;
+    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
+  }
+  return rc;
+}
+
+// The gating of one trajectory behind the NULL checks (ndt_loop_gate; mp: ndt_loop_gate_multi, whose `loop` part p is): the
+// refusals of the arrays, then of the parameters, then the candidates (session 0).
+int loop_gate_arrays(const char *fn, const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor,
+                     const uint64_t *sub_offsets, int n_submaps, const ndt_loop_params &p, const ndt_loop_multi_params *mp,
+                     std::vector<ndt_loop_candidate> *C) {
+  const std::string f(fn);
+  if (n_scans < 1 || n_scans > (size_t)INT32_MAX || n_submaps < 1) return fail(nullptr, NDT_E_ARG, f + ": need 1 <= n_scans <= 2^31 - 1 and n_submaps >= 1");
+  for (int m = 0; m < n_submaps; ++m) {
+    const bool ordered = m == 0 ? sub_first[0] == 0 : sub_first[m] >= sub_first[m - 1];
+    if (!ordered || sub_first[m] < 0 || (size_t)sub_first[m] >= n_scans || sub_anchor[m] < 0 || (size_t)sub_anchor[m] >= n_scans ||
+        sub_offsets[m + 1] < sub_offsets[m])
+      return fail(nullptr, NDT_E_ARG, f + ": submap " + std::to_string(m) + ": sub_first, sub_anchor or sub_offsets is not a set's layout");
+  }
+  for (size_t k = 0; k < 3 * n_scans; ++k)
+    if (!(std::fabs(poses[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, f + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
+  uint64_t P = 0;
+  const int rc = mp ? loop_check_multi_params(nullptr, mp, f, &P) : loop_check_params(nullptr, &p, f, &P);
+  if (rc) return rc;
+  loop_gate_k(poses, (int)n_scans, sub_first, sub_anchor, sub_offsets, n_submaps - 1, p, 0, mp ? mp->max_submaps : 1, C);
+  return NDT_OK;
 }
 
 #undef LP_TRY
@@ -265,25 +399,45 @@ int ndt_loop_default_params(ndt_loop_params *p) {
   return NDT_OK;
 }
 
+int ndt_loop_multi_default_params(ndt_loop_multi_params *p) {
+  if (!p) return NDT_E_ARG;
+  memset(p, 0, sizeof(*p));
+  ndt_loop_default_params(&p->loop);
+  p->max_submaps = 2; p->max_d2 = 0.09; p->min_overlap = 0.5;
+  return NDT_OK;
+}
+
 int ndt_loop_gate(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor, const uint64_t *sub_offsets,
                   int n_submaps, const ndt_loop_params *p, ndt_loop_candidate *out, int *has) {
-  const std::string f("ndt_loop_gate");
-  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !has) return fail(nullptr, NDT_E_ARG, f + ": NULL pointer");
-  if (n_scans < 1 || n_scans > (size_t)INT32_MAX || n_submaps < 1) return fail(nullptr, NDT_E_ARG, f + ": need 1 <= n_scans <= 2^31 - 1 and n_submaps >= 1");
-  for (int m = 0; m < n_submaps; ++m) {
-    const bool ordered = m == 0 ? sub_first[0] == 0 : sub_first[m] >= sub_first[m - 1];
-    if (!ordered || sub_first[m] < 0 || (size_t)sub_first[m] >= n_scans || sub_anchor[m] < 0 || (size_t)sub_anchor[m] >= n_scans ||
-        sub_offsets[m + 1] < sub_offsets[m])
-      return fail(nullptr, NDT_E_ARG, f + ": submap " + std::to_string(m) + ": sub_first, sub_anchor or sub_offsets is not a set's layout");
-  }
-  for (size_t k = 0; k < 3 * n_scans; ++k)
-    if (!(std::fabs(poses[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, f + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
-  uint64_t P = 0;
-  const int rc = loop_check_params(nullptr, p, f, &P);
+  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !has) return fail(nullptr, NDT_E_ARG, "ndt_loop_gate: NULL pointer");
+  std::vector<ndt_loop_candidate> C;
+  const int rc = loop_gate_arrays("ndt_loop_gate", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, *p, nullptr, &C);
   if (rc) return rc;
-  ndt_loop_candidate c{};
-  *has = loop_gate_one(poses, (int)n_scans, sub_first, sub_anchor, sub_offsets, n_submaps - 1, *p, &c) ? 1 : 0;
-  if (*has) *out = c;
+  *has = C.empty() ? 0 : 1;
+  if (*has) *out = C[0];
+  return NDT_OK;
+}
+
+int ndt_loop_gate_multi(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor, const uint64_t *sub_offsets,
+                        int n_submaps, const ndt_loop_multi_params *p, ndt_loop_candidate *out, int *n_out) {
+  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !n_out) return fail(nullptr, NDT_E_ARG, "ndt_loop_gate_multi: NULL pointer");
+  std::vector<ndt_loop_candidate> C;
+  const int rc = loop_gate_arrays("ndt_loop_gate_multi", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, p->loop, p, &C);
+  if (rc) return rc;
+  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(ndt_loop_candidate));
+  *n_out = (int)C.size();
+  return NDT_OK;
+}
+
+int ndt_sessions_loop_candidates_multi(const ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p,
+                                       ndt_loop_candidate *out, int *n_out) {
+  uint64_t P = 0;
+  const int rc = loop_multi_entry_checks(s, p, out, n_out, "ndt_sessions_loop_candidates_multi", &P);
+  if (rc) return rc;
+  std::vector<ndt_loop_candidate> C;
+  loop_gate(s, which, p->loop, &C, p->max_submaps);
+  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(ndt_loop_candidate));
+  *n_out = (int)C.size();
   return NDT_OK;
 }
 
@@ -302,22 +456,17 @@ int ndt_sessions_loop_candidates(const ndt_sessions *s, const unsigned char *whi
 int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop *out, int *n_out,
                             ndt_result *records_host) {
   uint64_t P = 0;
-  int rc = loop_entry_checks(s, p, out, n_out, "ndt_sessions_find_loops", &P);
+  const int rc = loop_entry_checks(s, p, out, n_out, "ndt_sessions_find_loops", &P);
   if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_sessions_find_loops: an ndt_map_rebuild_begin is open on the context");
-  std::vector<ndt_loop_candidate> C;
-  loop_gate(s, which, *p, &C);
-  if (C.size() * P > (uint64_t)INT32_MAX)
-    return fail(ctx, NDT_E_ARG, "ndt_sessions_find_loops: more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
-  *n_out = (int)C.size();
-  if (C.empty()) { s->stats = ndt_sessions_stats{}; return NDT_OK; }
-  rc = ss_find_loops(s, *p, C, P, out, records_host);
-  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
-    s->dead = true;
-    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
-  }
-  return rc;
+  return loop_search_entry(s, which, *p, P, "ndt_sessions_find_loops", out, nullptr, nullptr, n_out, records_host);
+}
+
+int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p, ndt_loop_multi *out,
+                                  int *n_out, ndt_result *records_host) {
+  uint64_t P = 0;
+  const int rc = loop_multi_entry_checks(s, p, out, n_out, "ndt_sessions_find_loops_multi", &P);
+  if (rc) return rc;
+  return loop_search_entry(s, which, p->loop, P, "ndt_sessions_find_loops_multi", nullptr, p, out, n_out, records_host);
 }
 
 }  // extern "C"

@@ -223,6 +223,8 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_mm;                          // local-map assembly (and the neighbour removal on its own): jobs, units, voxel sets, lists
   StagedUpload<unsigned char> mm_tab;                  // its job table
   StagedUpload<MapView> views_tab;                     // ndt_align_batch_multi_dev: the launch's table of map views
+  DevBuf<MapView> d_fp_views;                          // ndt_fit_points_multi_dev: the call's table of map views ...
+  StagedUpload<MapView> fpv_tab;                       // ... and its staging
   // ndt_map_build_batch_dev: the scan's ticket (word 0) and 16 words per map from word 16 (map_minmax's running box, result and
   // done-counter, set to their start values when the table grows), their read-back, the job table and its staging
   DevBuf<unsigned> d_boxes;
@@ -2936,8 +2938,9 @@ int ndt_sessions_destroy(ndt_sessions *s) {
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)e;
   for (auto &Q : s->ses)
-    for (ndt_map **m : {&Q.map, &Q.loop_map})
+    for (ndt_map **m : {&Q.map, &Q.loop_map, &Q.loop_map_more[0], &Q.loop_map_more[1], &Q.loop_map_more[2]})
       if (*m) { ndt_map_destroy(*m); *m = nullptr; }
+  static_assert(NDT_LOOP_MAX_SUBMAPS == 4, "every loop map of a session is destroyed above");
   delete s;
   return NDT_OK;
 }
@@ -3407,21 +3410,34 @@ int fit_points_check(ndt_ctx *ctx, const ndt_map *map, const void *scans, const 
 
 // The two kernels on st, inside the caller's frame (d_fit_pts): they read the map (MapRead), entered the way the score sweep
 // is (queue_score).  The ring's first two events ride on the search kernel's dispatch.
+// mm (ndt_fit_points_multi_dev): match b reads mm->maps[map_of[b]]; `map` is then mm->maps[0], whose transform_sse every map
+// has (fit_points_multi_check).  The views as they are now go up once, staged in pinned memory, into a table of the call's
+// own (ndt_ctx::d_fp_views / fpv_tab -- not views_tab, which lives in a match launch's workspace): the scratch bracket
+// orders the copy behind the previous call's kernels, reserve() waits for the previous call's copy.
 int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const float *scans, const unsigned long long *offsets, int B,
                      size_t total_points, int shared_scan, const void *tf, size_t tf_stride, double max_d2, float *d2,
-                     ndt_fit_stats *stats) {
+                     ndt_fit_stats *stats, const MultiMaps *mm = nullptr) {
   int rc;
   if (stats && (rc = ctx->d_fit_pts.ensure(ctx, fit_parts_needed(total_points, (size_t)B, shared_scan)))) return rc;   // (the call's one allocation, in front of its first kernel)
-  MapRead rd{ctx, st, &map, 1};
+  if (mm && ((rc = ctx->d_fp_views.ensure(ctx, (size_t)mm->n_maps)) || (rc = ctx->fpv_tab.reserve(ctx, (size_t)mm->n_maps)))) return rc;
+  const ndt_map *const *maps = mm ? mm->distinct.data() : &map;
+  const int n_read = mm ? (int)mm->distinct.size() : 1;
+  MapRead rd{ctx, st, maps, n_read};
   if ((rc = rd.begin())) return rc;
+  if (mm) {
+    for (int i = 0; i < mm->n_maps; ++i) ctx->fpv_tab.h.p[i] = mm->maps[i]->view;
+    HIP_TRY(ctx, ctx->fpv_tab.upload(ctx->d_fp_views.p, 0, (size_t)mm->n_maps, st));
+  }
+  const MapView *views = mm ? ctx->d_fp_views.p : nullptr;
+  const int *map_of = mm ? mm->map_of : nullptr; const int n_maps = mm ? mm->n_maps : 0;
   const FitGrid G = fit_grid(total_points, B, shared_scan, ctx->workgroups);     // (queue_fitness's grid; NDT_OPT_WORKGROUPS bounds it)
   FitPtsPart *parts = stats ? ctx->d_fit_pts.p : nullptr;
   Event *evr = rd.ev;
-  with_bool(map->prm.transform_sse != 0, [&](auto S) {
-    hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value>), dim3(G.workgroups), dim3(256), 0, st, evr[0], evr[1], 0, map->view,
-                          reinterpret_cast<const float2 *>(scans), offsets, B, shared_scan, (const unsigned char *)tf, tf_stride, max_d2, d2,
-                          parts, (int)G.gx);
-  });
+  with_bool(map->prm.transform_sse != 0, [&](auto S) { with_bool(mm != nullptr, [&](auto M) {
+    hipExtLaunchKernelGGL((fit_points_kernel<decltype(S)::value, decltype(M)::value>), dim3(G.workgroups), dim3(256), 0, st, evr[0], evr[1], 0,
+                          map->view, reinterpret_cast<const float2 *>(scans), offsets, B, shared_scan, (const unsigned char *)tf, tf_stride,
+                          max_d2, d2, parts, (int)G.gx, views, map_of, n_maps);
+  }); });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e));
   if (stats) {
@@ -3429,7 +3445,75 @@ int queue_fit_points(ndt_ctx *ctx, const ndt_map *map, hipStream_t st, const flo
     e = hipGetLastError();
   }
   return rd.entered(e != hipSuccess ? fail(ctx, NDT_E_HIP, std::string("ndt_fit_points: ") + hipGetErrorString(e)) : NDT_OK,
-                    /*end_carried=*/false, /*deferred=*/st != map->ctx->stream, "ndt_fit_points");
+                    /*end_carried=*/false,
+                    /*deferred=*/std::any_of(maps, maps + n_read, [&](const ndt_map *m) { return st != m->ctx->stream; }), "ndt_fit_points");
+}
+
+// The refusals of the multi-map forms: the maps first (the text names the first offending one), then those of the single-map
+// call, then what ties the maps to the matches and to one kernel instance.  Fills mm on success (map_of is the caller's to set).
+int fit_points_multi_check(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, bool have_map_of, const void *scans, const void *offsets,
+                           int B, const void *tf, size_t tf_stride, double max_d2, const void *d2, const void *stats, const char *fn,
+                           MultiMaps *mm) {
+  if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
+  const std::string f(fn);
+  if (!maps || n_maps < 1) return fail(ctx, NDT_E_ARG, f + ": no maps (maps == NULL or n_maps < 1)");
+  for (int i = 0; i < n_maps; ++i) {
+    const ndt_map *m = maps[i];
+    const std::string which = f + ": map " + std::to_string(i);
+    if (!m) return fail(ctx, NDT_E_ARG, which + " is NULL");
+    if (!m->ctx || !m->view.cent) return fail(ctx, NDT_E_ARG, which + " was never built");
+    if (m->device != ctx->device) return fail(ctx, NDT_E_ARG, which + " was built on another device");
+  }
+  const int rc = fit_points_check(ctx, maps[0], scans, offsets, B, tf, tf_stride, max_d2, d2, stats, fn);
+  if (rc) return rc;
+  if (!have_map_of && n_maps != B) return fail(ctx, NDT_E_ARG, f + ": map_of == NULL needs n_maps == B");
+  for (int i = 1; i < n_maps; ++i)
+    if ((maps[i]->prm.transform_sse != 0) != (maps[0]->prm.transform_sse != 0))
+      return fail(ctx, NDT_E_ARG, f + ": map " + std::to_string(i) + " has another transform_sse than map 0 (the kernel instance depends on it)");
+  mm->maps = maps; mm->n_maps = n_maps; mm->map_of = nullptr;
+  mm->distinct.assign(maps, maps + n_maps);
+  std::sort(mm->distinct.begin(), mm->distinct.end());
+  mm->distinct.erase(std::unique(mm->distinct.begin(), mm->distinct.end()), mm->distinct.end());
+  return NDT_OK;
+}
+
+// The host forms behind their refusals: one upload (the offsets, the transforms packed to 16 bytes each, the multi-map form's
+// map_of and the scans, staged in pinned memory), the two kernels, the read-backs, one wait.
+int fit_points_host(ndt_ctx *ctx, const ndt_map *map, MultiMaps *mm, const int *map_of_host, const float *scans_xy_host,
+                    const uint64_t *offsets_host, int B, int shared_scan, const float *tf_host, size_t tf_stride_bytes, double max_d2,
+                    float *d2_host, ndt_fit_stats *stats_host, const char *fn) {
+  int rc;
+  const size_t nscan = shared_scan ? 1 : (size_t)B;
+  for (size_t b = 0; b < nscan; ++b)
+    if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, std::string(fn) + ": offsets not monotone");
+  const size_t ntot = (size_t)offsets_host[nscan];
+  const size_t n_d2 = shared_scan ? (size_t)B * (size_t)(offsets_host[1] - offsets_host[0]) : ntot;
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions U;
+  U.take((nscan + 1) * 8, 256);
+  const size_t o_tf = U.take((size_t)B * 16, 256), o_mapof = map_of_host ? U.take((size_t)B * sizeof(int), 256) : 0,
+               o_scan = U.take(ntot * 8, 256), bytes = U.end;
+  if ((rc = ctx->fp_tab.reserve(ctx, bytes))) return rc;
+  if ((rc = ctx->d_scan.ensure(ctx, bytes))) return rc;
+  if (d2_host && (rc = ctx->d_fit.ensure(ctx, n_d2 + 4))) return rc;
+  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, (size_t)B * sizeof(ndt_fit_stats)))) return rc;
+  unsigned char *h = ctx->fp_tab.h.p, *d = ctx->d_scan.p;
+  memcpy(h, offsets_host, (nscan + 1) * 8);
+  for (int b = 0; b < B; ++b) memcpy(h + o_tf + (size_t)b * 16, (const unsigned char *)tf_host + (size_t)b * tf_stride_bytes, 16);
+  if (map_of_host) memcpy(h + o_mapof, map_of_host, (size_t)B * sizeof(int));
+  if (ntot) memcpy(h + o_scan, scans_xy_host, ntot * 8);
+  HIP_TRY(ctx, ctx->fp_tab.upload(d, 0, bytes, st));
+  if (mm) mm->map_of = map_of_host ? (const int *)(d + o_mapof) : nullptr;
+  float *d_d2 = d2_host ? ctx->d_fit.p : nullptr;
+  ndt_fit_stats *d_stats = stats_host ? (ndt_fit_stats *)ctx->d_tmp.p : nullptr;
+  if ((rc = queue_fit_points(ctx, map, st, (const float *)(d + o_scan), (const unsigned long long *)d, B, ntot, shared_scan, d + o_tf, 16,
+                             max_d2, d_d2, d_stats, mm)))
+    return rc;
+  if (d2_host && n_d2) HIP_TRY(ctx, hipMemcpyAsync(d2_host, d_d2, n_d2 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, (size_t)B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
+  return fr.close_and_wait();
 }
 
 }  // namespace
@@ -3452,35 +3536,33 @@ int ndt_fit_points_batch(ndt_ctx *ctx, const ndt_map *map, const float *scans_xy
                          ndt_fit_stats *stats_host) {
   int rc = fit_points_check(ctx, map, scans_xy_host, offsets_host, B, tf_host, tf_stride_bytes, max_d2, d2_host, stats_host, "ndt_fit_points_batch");
   if (rc) return rc;
-  const size_t nscan = shared_scan ? 1 : (size_t)B;
-  for (size_t b = 0; b < nscan; ++b)
-    if (offsets_host[b + 1] < offsets_host[b]) return fail(ctx, NDT_E_ARG, "ndt_fit_points_batch: offsets not monotone");
-  const size_t ntot = (size_t)offsets_host[nscan];
-  const size_t n_d2 = shared_scan ? (size_t)B * (size_t)(offsets_host[1] - offsets_host[0]) : ntot;
-  CallFrame fr(ctx);
-  if ((rc = fr.open())) return rc;
-  hipStream_t st = fr.st;
-  // one upload: the offsets, the transforms (packed: 16 bytes each) and the scans, staged in pinned memory
-  Regions U;
-  U.take((nscan + 1) * 8, 256);
-  const size_t o_tf = U.take((size_t)B * 16, 256), o_scan = U.take(ntot * 8, 256), bytes = U.end;
-  if ((rc = ctx->fp_tab.reserve(ctx, bytes))) return rc;
-  if ((rc = ctx->d_scan.ensure(ctx, bytes))) return rc;
-  if (d2_host && (rc = ctx->d_fit.ensure(ctx, n_d2 + 4))) return rc;
-  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, (size_t)B * sizeof(ndt_fit_stats)))) return rc;
-  unsigned char *h = ctx->fp_tab.h.p, *d = ctx->d_scan.p;
-  memcpy(h, offsets_host, (nscan + 1) * 8);
-  for (int b = 0; b < B; ++b) memcpy(h + o_tf + (size_t)b * 16, (const unsigned char *)tf_host + (size_t)b * tf_stride_bytes, 16);
-  if (ntot) memcpy(h + o_scan, scans_xy_host, ntot * 8);
-  HIP_TRY(ctx, ctx->fp_tab.upload(d, 0, bytes, st));
-  float *d_d2 = d2_host ? ctx->d_fit.p : nullptr;
-  ndt_fit_stats *d_stats = stats_host ? (ndt_fit_stats *)ctx->d_tmp.p : nullptr;
-  if ((rc = queue_fit_points(ctx, map, st, (const float *)(d + o_scan), (const unsigned long long *)d, B, ntot, shared_scan, d + o_tf, 16,
-                             max_d2, d_d2, d_stats)))
-    return rc;
-  if (d2_host && n_d2) HIP_TRY(ctx, hipMemcpyAsync(d2_host, d_d2, n_d2 * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, (size_t)B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
-  return fr.close_and_wait();
+  return fit_points_host(ctx, map, nullptr, nullptr, scans_xy_host, offsets_host, B, shared_scan, tf_host, tf_stride_bytes, max_d2, d2_host,
+                         stats_host, "ndt_fit_points_batch");
+}
+
+int ndt_fit_points_multi_dev(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_dev, const float *scans_xy_dev,
+                             const uint64_t *offsets_dev, int B, size_t total_points, int shared_scan, const float *tf_dev,
+                             size_t tf_stride_bytes, double max_d2, float *d2_dev, ndt_fit_stats *stats_dev, void *stream) {
+  MultiMaps mm;
+  int rc = fit_points_multi_check(ctx, maps, n_maps, map_of_dev != nullptr, scans_xy_dev, offsets_dev, B, tf_dev, tf_stride_bytes, max_d2,
+                                  d2_dev, stats_dev, "ndt_fit_points_multi_dev", &mm);
+  if (rc) return rc;
+  mm.map_of = map_of_dev;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_fit_points(ctx, maps[0], st, scans_xy_dev, (const unsigned long long *)offsets_dev, B, total_points, shared_scan, tf_dev,
+                             tf_stride_bytes, max_d2, d2_dev, stats_dev, &mm);
+  });
+}
+
+int ndt_fit_points_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const int *map_of_host, const float *scans_xy_host,
+                         const uint64_t *offsets_host, int B, int shared_scan, const float *tf_host, size_t tf_stride_bytes,
+                         double max_d2, float *d2_host, ndt_fit_stats *stats_host) {
+  MultiMaps mm;
+  int rc = fit_points_multi_check(ctx, maps, n_maps, map_of_host != nullptr, scans_xy_host, offsets_host, B, tf_host, tf_stride_bytes, max_d2,
+                                  d2_host, stats_host, "ndt_fit_points_multi", &mm);
+  if (rc) return rc;
+  return fit_points_host(ctx, maps[0], &mm, map_of_host, scans_xy_host, offsets_host, B, shared_scan, tf_host, tf_stride_bytes, max_d2,
+                         d2_host, stats_host, "ndt_fit_points_multi");
 }
 
 }  // extern "C"

@@ -318,6 +318,7 @@ struct SsSession {
   DevBuf<double2> arch;
   std::vector<uint64_t> arch_off{0};        // n_poses + 1 entries
   ndt_map *loop_map = nullptr;              // ndt_sessions_find_loops: the map of the session's candidate submap, rebuilt by every search
+  ndt_map *loop_map_more[NDT_LOOP_MAX_SUBMAPS - 1] = {};      // ndt_sessions_find_loops_multi: those of its candidates of rank 1 and up
   bool started = false;
 };
 

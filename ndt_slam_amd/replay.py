@@ -663,14 +663,17 @@ def load_occupancy(stem):
 # run_sessions_resident's loop closure: loop = a capi.LoopParams, pg = pose-graph parameters (None: the defaults), odo_info =
 # the six numbers of every odometry arc's information matrix, every = the lockstep steps between two searches, cooldown = the
 # steps a corrected session is not searched again, remake_closed = behind correct() every corrected session's closed submaps
-# are computed again from the scan archive (sessions.remake_closed) instead of staying rigidly moved
+# are computed again from the scan archive (sessions.remake_closed) instead of staying rigidly moved, multi = None or a
+# capi.LoopMultiParams: the search is then sessions.find_loops_multi with it (several old submaps per session, accepted on
+# ranged fitness; its `loop` part replaces `loop`) and every edge found for a session goes into that session's one graph
 class LoopClosure(collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")):
     """The five fields above as a tuple, as before (its _fields, its length and its unpacking are unchanged), and the
-    attribute remake_closed (default False) beside them."""
+    attributes remake_closed (default False) and multi (default None) beside them."""
 
-    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False):
+    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None):
         self = super().__new__(cls, loop, pg, odo_info, every, cooldown)
         self.remake_closed = bool(remake_closed)
+        self.multi = multi
         return self
 
 
@@ -690,40 +693,54 @@ def closed_scan_ranges(sub_first, n_closed):
     return out
 
 
-def loop_graph(poses, loop_edge, odo_info):
-    """The pose graph of one trajectory with one loop (host only): one odometry arc per consecutive pair of `poses`
-    ([n, 3], (tx, ty, th[deg])) -- rel by capi.pg_edge_between, info = odo_info (6 numbers) -- then the loop's arc as given
-    (a record with from / from_, to, rel, info: ndt_loop.edge) -> the n arcs as capi.PG_EDGE_DTYPE."""
+def loops_graph(poses, loop_edges, odo_info):
+    """The pose graph of one trajectory with any number of loops (host only): one odometry arc per consecutive pair of
+    `poses` ([n, 3], (tx, ty, th[deg])) -- rel by capi.pg_edge_between, info = odo_info (6 numbers) -- then every loop's arc
+    as given and in the given order (records with from / from_, to, rel, info: ndt_loop.edge) -> the n - 1 + len(loop_edges)
+    arcs as capi.PG_EDGE_DTYPE."""
     from . import capi
     poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
     n = len(poses)
-    edges = np.zeros(n, dtype=capi.PG_EDGE_DTYPE)
+    edges = np.zeros(n - 1 + len(loop_edges), dtype=capi.PG_EDGE_DTYPE)
     for j in range(n - 1):
         edges[j]["from"], edges[j]["to"] = j, j + 1
         edges[j]["rel"] = capi.pg_edge_between(poses[j], poses[j + 1])
         edges[j]["info"] = np.asarray(odo_info, dtype=np.float64).reshape(6)
-    names = getattr(getattr(loop_edge, "dtype", None), "names", None) or ()
-    edges[n - 1]["from"] = loop_edge["from" if "from" in names else "from_"]
-    edges[n - 1]["to"] = loop_edge["to"]
-    edges[n - 1]["rel"], edges[n - 1]["info"] = loop_edge["rel"], loop_edge["info"]
+    for k, loop_edge in enumerate(loop_edges):
+        names = getattr(getattr(loop_edge, "dtype", None), "names", None) or ()
+        e = edges[n - 1 + k]
+        e["from"] = loop_edge["from" if "from" in names else "from_"]
+        e["to"] = loop_edge["to"]
+        e["rel"], e["info"] = loop_edge["rel"], loop_edge["info"]
     return edges
 
 
+def loop_graph(poses, loop_edge, odo_info):
+    """loops_graph with one loop: the n arcs of a trajectory of n poses."""
+    return loops_graph(poses, [loop_edge], odo_info)
+
+
 def _close_loops(ctx, sessions, lc, which):
-    """One search over the sessions `which`, one batch of pose graphs for the loops found, correct() for the graphs that
-    converged -> the corrected sessions' flags."""
+    """One search over the sessions `which`, one batch of pose graphs for the loops found -- a graph per session, with every
+    edge found for it (lc.multi: several) --, correct() for the graphs that converged -> the corrected sessions' flags."""
     from . import capi
     S = len(which)
     corrected = np.zeros(S, dtype=np.uint8)
-    found = [l for l in sessions.find_loops(lc.loop, which) if l["status"] == 0 and l["found"]]
-    if not found:
+    multi = getattr(lc, "multi", None)
+    loops = sessions.find_loops(lc.loop, which) if multi is None else sessions.find_loops_multi(multi, which)["loop"]
+    by_session = collections.OrderedDict()
+    for l in loops:
+        if l["status"] == 0 and l["found"]:
+            by_session.setdefault(int(l["cand"]["session"]), []).append(l["edge"])
+    if not by_session:
         return corrected
-    trajs = [sessions.trajectory(int(l["cand"]["session"]))[0] for l in found]
-    graphs = [loop_graph(t, l["edge"], lc.odo_info) for t, l in zip(trajs, found)]
+    who = list(by_session)
+    trajs = [sessions.trajectory(i)[0] for i in who]
+    graphs = [loops_graph(t, by_session[i], lc.odo_info) for t, i in zip(trajs, who)]
     off = np.concatenate([[0], np.cumsum([len(t) for t in trajs])]).astype(np.uint64)
-    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(trajs), off, np.concatenate(graphs), off, lc.pg)
-    fix = {int(l["cand"]["session"]): new[int(off[g]):int(off[g + 1])]
-           for g, l in enumerate(found) if res[g]["status"] == 0 and res[g]["converged"]}
+    eoff = np.concatenate([[0], np.cumsum([len(g) for g in graphs])]).astype(np.uint64)
+    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(trajs), off, np.concatenate(graphs), eoff, lc.pg)
+    fix = {i: new[int(off[g]):int(off[g + 1])] for g, i in enumerate(who) if res[g]["status"] == 0 and res[g]["converged"]}
     if fix:
         for i in sessions.correct(fix):
             corrected[i] = 1

@@ -157,7 +157,93 @@ def summary(x):
     return dict(median=float(np.median(x)), min=float(min(x)), max=float(max(x)))
 
 
-out = dict(sessions=S, candidates=J, reps=REPS, lattice_poses=int(P), filtered_points=int(np.mean([d["nf"] for d in per])),
+# ---- the search over several submaps (ndt_sessions_find_loops_multi; LOG.md R40.1): S sessions x 2 submaps in one call, against
+# what a caller composes today -- ndt_sessions_find_loops for the nearest submap, then per extra submap and session a build,
+# the single-job sweep, pick and match (ndt_relocalize_dev), and one ndt_fit_points_batch_dev per map (the nearest submaps' maps
+# are the set's own, so the caller builds those again for its verification).  Beside them the one call at 1, 2 and 4 submaps
+# and ndt_sessions_find_loops with the same gating.
+MULTI = dict(radius=4.0, max_d2=0.09, min_overlap=0.5)
+mp2 = capi.default_loop_multi_params(max_submaps=2, **MULTI)
+cands2 = ses.loop_candidates_multi(mp2)
+assert len(cands2) == 2 * S, "every session has two old submaps within 4 m"
+extra = []
+for c in cands2:
+    i = int(c["session"])
+    cloud = np.ascontiguousarray(ses.global_map(i)[1][int(c["submap"])])
+    d = per[[int(x["session"]) for x in cands].index(i)]
+    e = dict(base=d, session=i, cloud=torch.from_numpy(cloud).to(dev), n_cloud=len(cloud), lattice=capi.PoseLattice.from_buffer_copy(c["lattice"].tobytes()),
+             nearest=int(c["submap"]) == int(cands2[cands2["session"] == i][0]["submap"]),
+             stats=torch.zeros(capi.NDT_LOOP_MAX_CAND * 32, dtype=torch.uint8, device=dev))
+    extra.append(e)
+torch.cuda.synchronize()
+for e in extra:
+    e["map"] = capi.Map(ctx, params=params, dev_ptr=e["cloud"].data_ptr(), n=e["n_cloud"])
+torch.cuda.synchronize()
+TF_AT = capi.RESULT_DTYPE.fields["T00"][1]
+
+
+def composed():
+    t0 = time.perf_counter()
+    loops, recs = ses.find_loops(mp2.loop, want_records=True)
+    row = {int(l["cand"]["session"]): j for j, l in enumerate(loops)}
+    for e in extra:
+        d = e["base"]
+        e["map"].rebuild(dev_ptr=e["cloud"].data_ptr(), n=e["n_cloud"])
+        if e["nearest"]:
+            j = row[e["session"]]
+            rec = recs[j][:int(loops[j]["n_cand"])]
+        else:
+            rec = e["map"].relocalize(None, e["lattice"], top_k=lp.top_k, local_max=bool(lp.local_max), dev_ptr=d["filt"].data_ptr(),
+                                      n=d["nf"], stride=8)["records"]
+        if len(rec):
+            d_rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8)).to(dev)
+            e["map"].fit_points_dev(d["filt"].data_ptr(), d["foff"].data_ptr(), len(rec), d["nf"], d_rec.data_ptr() + TF_AT, capi.RESULT_BYTES,
+                                    mp2.max_d2, None, e["stats"].data_ptr(), shared_scan=True)
+            e["st"] = e["stats"].cpu()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def multi_call(prm):
+    t0 = time.perf_counter()
+    loops = ses.find_loops_multi(prm)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, len(loops), int(loops["loop"]["found"].sum())
+
+
+def single_call(prm):
+    t0 = time.perf_counter()
+    ses.find_loops(prm)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+forms = {"multi_x1": capi.default_loop_multi_params(max_submaps=1, **MULTI), "multi_x2": mp2,
+         "multi_x4": capi.default_loop_multi_params(max_submaps=4, **dict(MULTI, radius=10.0))}
+for _ in range(2):
+    composed()
+    single_call(mp2.loop)
+    for prm in forms.values():
+        multi_call(prm)
+t_comp, t_single, t_multi = [], [], {k: [] for k in forms}
+for _ in range(REPS):
+    t_comp.append(composed())
+    t_single.append(single_call(mp2.loop))
+    for k, prm in forms.items():
+        t_multi[k].append(multi_call(prm))
+mstats = {}
+for k, prm in forms.items():
+    ses.find_loops_multi(prm)
+    q = ses.stats()
+    mstats[k] = dict(host_waits=q.host_waits, candidates=q.sessions_stepped, h2d_bytes=int(q.h2d_bytes), d2h_bytes=int(q.d2h_bytes))
+multi_out = dict(composed_x2_ms=summary(t_comp), find_loops_radius4_ms=summary(t_single),
+                 **{k + "_ms": summary([t for t, _, _ in v]) for k, v in t_multi.items()},
+                 **{k + "_found": v[-1][2] for k, v in t_multi.items()}, stats=mstats)
+for e in extra:
+    e["map"].close()
+
+out = dict(find_loops_multi=multi_out,
+sessions=S, candidates=J, reps=REPS, lattice_poses=int(P), filtered_points=int(np.mean([d["nf"] for d in per])),
            cloud_points=int(np.mean([d["n_cloud"] for d in per])),
            find_loops_ms=summary([t for t, _ in a]), per_session_ms=summary([t for t, _ in b]),
            found=dict(find_loops=a[-1][1], per_session=b[-1][1]),
