@@ -1046,8 +1046,8 @@ int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const do
  * grow with the number of sessions.  The edge goes into the graph made of ndt_sessions_trajectory, ndt_pg_optimize_batch
  * adjusts it and ndt_sessions_correct takes the result back.
  * Several candidate submaps per session and a ranged-fitness verification of a partial overlap: ndt_sessions_find_loops_multi
- * below.  Out of scope: loops between sessions; keeping the loop maps valid across calls; calling the optimiser or the
- * correction for the caller.
+ * below; loops between the sessions of a set: ndt_sessions_find_cross_loops behind it.  Out of scope: keeping the loop maps
+ * valid across calls; calling the optimiser or the correction for the caller.
  *
  * Gating (host only, no device work; ndt_sessions_loop_candidates gives exactly what ndt_sessions_find_loops will search).
  * This is the definition, on what ndt_sessions_trajectory returns (n poses, sub_first, sub_anchor) and the closed clouds'
@@ -1182,7 +1182,8 @@ int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const n
  * no candidate or with all scans empty, 1 when no map could be built), sessions_stepped = J.
  * Refusals: those of the gating, an open ndt_map_rebuild_begin on the context, more than 2^31 - 1 lattice poses over all
  * candidates.  NDT_E_HIP on a dead set; a HIP failure inside the call kills the set as in a step.
- * Out of scope: loops between sessions; keeping the loop maps valid across calls; calling the optimiser for the caller. */
+ * Out of scope: keeping the loop maps valid across calls; calling the optimiser for the caller.  (Loops between sessions:
+ * the next section.) */
 #define NDT_LOOP_MAX_SUBMAPS 4
 typedef struct ndt_loop_multi_params {
   ndt_loop_params loop;     /* as for ndt_sessions_find_loops; loop.max_cost is compared with the RANGED cost above */
@@ -1207,6 +1208,78 @@ typedef struct ndt_loop_multi {        /* HOST; one per candidate, in candidate 
 } ndt_loop_multi;
 int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p,
                                   ndt_loop_multi *out, int *n_out, ndt_result *records_host);
+
+/* ---- Loops between the sessions of a set -------------------------------------------------------------------
+ * Has session a just driven into a place that session b mapped -- several robots in one building, several logs of one site?
+ * The sessions must share a map frame: a session's frame is its first odometry pose (src/ScanMatcher.cpp:9-22), so the caller
+ * feeds odometry that starts at the robot's known pose.  Finding an unknown offset between frames is out of scope.
+ *
+ * The cross gate.  Every searcher against every closed submap of every other track: a product, so it has a device form
+ * (ndt_cross_gate_batch) beside the host definition (ndt_cross_gate); the two agree to the byte.  The rule is defined on the
+ * SQUARED distance and takes no root.  For a searcher with last pose L = (x, y, th[deg]), track t and submap m of t:
+ *   - t != own and m in 0 .. n_submaps - 2: every closed submap, the newest closed one included (the searcher's local map
+ *     holds nothing of another session); own = -1: no track is the searcher's;
+ *   - submap m owns the scans [sub_first[m], sub_first[m + 1] - 1];
+ *   - d2(t, m) = the smallest, over the poses T[k] of that range, of dx * dx + dy * dy with dx = L.x - T[k].x, dy = L.y -
+ *     T[k].y: fp64, each subtraction, product and the sum rounded once, no fused multiply-add; nearest_scan = the lowest k
+ *     that attains it;
+ *   - (t, m) is eligible when its scan range is not empty, its closed cloud has points (sub_offsets[m + 1] > sub_offsets[m])
+ *     and d2 <= radius * radius (one rounded product);
+ *   - the searcher's candidates are its max_submaps eligible (t, m) of smallest d2, in ascending (d2, t, m);
+ *   - the lattice is the one ndt_loop_gate forms around L;
+ *   - min_path is not read; every other field of ndt_loop_multi_params means what it means above.
+ * ndt_cross_candidate: cand.session = the searcher (ndt_cross_gate: 0; the batch: its index), cand.submap = m, cand.anchor_scan
+ * = sub_anchor[m] and cand.nearest_scan in track t's numbering, cand.newest_scan as given, cand.dist = sqrt(d2) (host), cand.path
+ * = 0; map_session = t; rank = the candidate's place among its searcher's; padding bytes are 0.
+ * Refusals (NDT_E_ARG): those of ndt_loop_gate_multi for every track, the text naming the track ("track 3: ..."); a NULL
+ * pointer, n_tracks < 1; a last pose that is not finite; own outside [-1, n_tracks); more than 2^28 (searcher, closed submap)
+ * pairs.
+ * ndt_cross_gate_batch: n_search searchers (last_poses 3 doubles each) in one table upload, two launches and one read-back,
+ * whatever n_search and n_tracks are; synchronous, on the context's stream.  out[i * max_submaps + r] is candidate r of
+ * searcher i for r < n_out[i]; the records from n_out[i] on are zero.  out and n_out are byte-identical to n_search calls of
+ * ndt_cross_gate (with cand.session = i).
+ *
+ * ndt_sessions_cross_candidates / ndt_sessions_find_cross_loops.  Searchers: the sessions with which[i] (NULL: all) that have
+ * started.  Tracks: the sessions with against[i] (NULL: all) that have started and have at least one closed submap, in
+ * ascending session order.  The candidates are what ndt_cross_gate gives for each searcher on the tracks' ndt_sessions_trajectory
+ * and ndt_sessions_global_map arrays, own = the searcher's own place among the tracks (-1 when it is none), with cand.session
+ * and map_session given as SESSION indices; the searchers in ascending order, each one's candidates in a row; *n_out of them;
+ * `out` needs room for n_sessions * max_submaps.  They are computed by the device gate (one host wait).
+ * The search is ndt_sessions_find_loops_multi's, stage for stage, with one difference: a candidate's closed cloud and anchor
+ * pose are map_session's, not the searcher's.  The map slots are the searcher's loop maps (slot = rank); each searcher's newest
+ * scan is taken to the robot frame and filtered once.  m is filled as ndt_sessions_find_loops_multi fills it: m.loop.edge.from =
+ * the anchor scan in map_session's trajectory, edge.to = the searcher's newest scan, rel = ndt_pg_edge_between(trajectory of
+ * map_session [anchor], pose) -- an arc between two trajectories, for a joint graph of both.
+ * Guarantees.  (a) A candidate's status, n_cand, cand_index, cand_score, records and fit are byte-identical to the same search
+ * made of public calls on that cloud and that scan.  (b) They depend neither on the other searchers, nor on the other tracks
+ * beyond eligibility, nor on max_submaps.  (c) A refused map costs its candidate alone; an empty newest scan gives the empty
+ * record; a set of one session, or no eligible pair, gives *n_out = 0 and NDT_OK with nothing queued behind the gate.  (d) The
+ * SLAM state is untouched.  (e) ndt_sessions_get_stats: host_waits 3 (the gate, the boxes, the records), 1 when the gate finds
+ * nothing (0 when there is no searcher or no track: the gate is not run), sessions_stepped = J; launches, copies and waits do
+ * not depend on the number of sessions.
+ * Refusals: those of ndt_sessions_find_loops_multi; NDT_E_HIP on a dead set.
+ * Out of scope: an unknown offset between the sessions' frames; keeping cross edges from one search to the next; loop maps
+ * that stay valid across calls; a robust back end. */
+typedef struct ndt_cross_track {        /* HOST: one trajectory whose closed submaps may be searched */
+  const double   *poses;  size_t n_scans;               /* ndt_sessions_trajectory */
+  const int      *sub_first, *sub_anchor;               /* n_submaps entries each */
+  const uint64_t *sub_offsets;  int n_submaps;          /* ndt_sessions_global_map: n_submaps + 1 entries */
+} ndt_cross_track;
+typedef struct ndt_cross_candidate {
+  ndt_loop_candidate cand;
+  int map_session, rank;
+  double d2;
+} ndt_cross_candidate;
+int ndt_cross_gate(const double last_pose[3], int newest_scan, int own, const ndt_cross_track *tracks, int n_tracks,
+                   const ndt_loop_multi_params *p, ndt_cross_candidate *out, int *n_out);
+int ndt_cross_gate_batch(ndt_ctx *ctx, const double *last_poses, const int *newest_scan, const int *own, int n_search,
+                         const ndt_cross_track *tracks, int n_tracks, const ndt_loop_multi_params *p,
+                         ndt_cross_candidate *out, int *n_out);
+typedef struct ndt_cross_loop { ndt_loop_multi m; int map_session, reserved; } ndt_cross_loop;
+int ndt_sessions_cross_candidates(ndt_sessions *s, const unsigned char *which, const unsigned char *against,
+                                  const ndt_loop_multi_params *p, ndt_cross_candidate *out, int *n_out);
+int ndt_sessions_find_cross_loops(ndt_sessions *s, const unsigned char *which, const unsigned char *against,
+                                  const ndt_loop_multi_params *p, ndt_cross_loop *out, int *n_out, ndt_result *records_host);
 
 /* ---- The scan archive and ndt_sessions_occ_rebuild: occupancy grids that follow a correction -----------------
  * ndt_sessions_occ_integrate casts a session's newest scan at the pose it had at that step; after ndt_sessions_correct every beam

@@ -187,7 +187,25 @@ class LoopMulti(C.Structure):
     _fields_ = [("loop", Loop), ("fit", FitStats * NDT_LOOP_MAX_CAND), ("rank", C.c_int), ("reserved", C.c_int)]
 
 
+class CrossTrack(C.Structure):
+    """ndt_cross_track (include/ndt_mi355x.h): one trajectory whose closed submaps may be searched."""
+    _fields_ = [("poses", C.c_void_p), ("n_scans", C.c_size_t), ("sub_first", C.c_void_p), ("sub_anchor", C.c_void_p),
+                ("sub_offsets", C.c_void_p), ("n_submaps", C.c_int)]
+
+
+class CrossCandidate(C.Structure):
+    """ndt_cross_candidate (include/ndt_mi355x.h): a closed submap of another track that a searcher's newest scan is near."""
+    _fields_ = [("cand", LoopCandidate), ("map_session", C.c_int), ("rank", C.c_int), ("d2", C.c_double)]
+
+
+class CrossLoop(C.Structure):
+    """ndt_cross_loop (include/ndt_mi355x.h): one cross candidate's search result."""
+    _fields_ = [("m", LoopMulti), ("map_session", C.c_int), ("reserved", C.c_int)]
+
+
 LOOP_CANDIDATE_DTYPE = np.dtype(LoopCandidate)
+CROSS_CANDIDATE_DTYPE = np.dtype(CrossCandidate)
+CROSS_LOOP_DTYPE = np.dtype(CrossLoop)
 LOOP_DTYPE = np.dtype(Loop)                          # (its edge's first field is from_, as PgEdge's)
 LOOP_MULTI_DTYPE = np.dtype(LoopMulti)
 
@@ -319,6 +337,10 @@ PROTOTYPES = {
     "ndt_loop_gate_multi": [_vp, _sz, _vp, _vp, _vp, _i, _P(LoopMultiParams), _vp, _P(_i)],
     "ndt_sessions_loop_candidates_multi": [_vp, _vp, _P(LoopMultiParams), _vp, _P(_i)],
     "ndt_sessions_find_loops_multi": [_vp, _vp, _P(LoopMultiParams), _vp, _P(_i), _vp],
+    "ndt_cross_gate": [_vp, _i, _i, _vp, _i, _P(LoopMultiParams), _vp, _P(_i)],
+    "ndt_cross_gate_batch": [_vp, _vp, _vp, _vp, _i, _vp, _i, _P(LoopMultiParams), _vp, _vp],
+    "ndt_sessions_cross_candidates": [_vp, _vp, _vp, _P(LoopMultiParams), _vp, _P(_i)],
+    "ndt_sessions_find_cross_loops": [_vp, _vp, _vp, _P(LoopMultiParams), _vp, _P(_i), _vp],
     "ndt_sessions_archive_enable": [_vp],
     "ndt_sessions_archive_info": [_vp, _i, _P(_sz), _P(_sz)],
     "ndt_sessions_archive_scans": [_vp, _i, _sz, _sz, _vp, _sz, _vp, _P(_sz)],
@@ -581,6 +603,46 @@ def loop_gate_multi(poses, sub_first, sub_anchor, sub_offsets, params):
     _check(lib().ndt_loop_gate_multi(_ptr(poses), len(poses), _ptr(first), _ptr(anchor), off.ctypes.data, len(first), C.byref(params),
                                      out.ctypes.data, C.byref(n)), "ndt_loop_gate_multi")
     return out[:n.value]
+
+
+def _cross_tracks(tracks):
+    """Tracks given as (poses, sub_first, sub_anchor, sub_offsets) -> (the CrossTrack array, the arrays it points into)."""
+    keep, arr = [], (CrossTrack * max(len(tracks), 1))()
+    for t, (poses, sub_first, sub_anchor, sub_offsets) in enumerate(tracks):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        first, anchor = np.ascontiguousarray(sub_first, dtype=np.int32), np.ascontiguousarray(sub_anchor, dtype=np.int32)
+        off = np.ascontiguousarray(sub_offsets, dtype=np.uint64)
+        if len(anchor) != len(first) or len(off) != len(first) + 1:
+            raise ValueError("track %d needs one sub_anchor per submap and one more sub_offsets" % t)
+        keep.append((poses, first, anchor, off))
+        arr[t] = CrossTrack(poses.ctypes.data, len(poses), first.ctypes.data, anchor.ctypes.data, off.ctypes.data, len(first))
+    return arr, keep
+
+
+def cross_gate(last_pose, newest_scan, own, tracks, params):
+    """ndt_cross_gate (host only): the closed submaps of the other tracks -- each (poses, sub_first, sub_anchor, sub_offsets) as
+    loop_gate takes them -- that lie within params.loop.radius of last_pose, nearest first, as CROSS_CANDIDATE_DTYPE records."""
+    last = np.ascontiguousarray(last_pose, dtype=np.float64).reshape(3)
+    arr, keep = _cross_tracks(tracks)
+    out, n = np.zeros(NDT_LOOP_MAX_SUBMAPS, dtype=CROSS_CANDIDATE_DTYPE), C.c_int()
+    _check(lib().ndt_cross_gate(last.ctypes.data, int(newest_scan), int(own), C.addressof(arr), len(tracks), C.byref(params),
+                                out.ctypes.data, C.byref(n)), "ndt_cross_gate")
+    return out[:n.value]
+
+
+def cross_gate_batch(ctx, last_poses, newest_scan, own, tracks, params):
+    """ndt_cross_gate_batch: cross_gate for many searchers in one upload, two launches and one read-back -> a list with one
+    array of CROSS_CANDIDATE_DTYPE records per searcher (cand.session = the searcher's index), byte for byte cross_gate's."""
+    last = np.ascontiguousarray(last_poses, dtype=np.float64).reshape(-1, 3)
+    newest, own = np.ascontiguousarray(newest_scan, dtype=np.int32), np.ascontiguousarray(own, dtype=np.int32)
+    if len(newest) != len(last) or len(own) != len(last):
+        raise ValueError("cross_gate_batch needs one newest_scan and one own per searcher")
+    arr, keep = _cross_tracks(tracks)
+    K = params.max_submaps if 1 <= params.max_submaps <= NDT_LOOP_MAX_SUBMAPS else NDT_LOOP_MAX_SUBMAPS
+    out, n = np.zeros((max(len(last), 1), K), dtype=CROSS_CANDIDATE_DTYPE), np.zeros(max(len(last), 1), dtype=np.int32)
+    ctx.check(lib().ndt_cross_gate_batch(ctx.h, _ptr(last), _ptr(newest), _ptr(own), len(last), C.addressof(arr), len(tracks),
+                                         C.byref(params), out.ctypes.data, n.ctypes.data), "ndt_cross_gate_batch")
+    return [out[i, :n[i]] for i in range(len(last))]
 
 
 def pg_edge_between(from_pose, to_pose):
@@ -1190,6 +1252,30 @@ class Sessions(_Handle):
         self.ctx.check(lib().ndt_sessions_loop_candidates_multi(self.h, None if w is None else w.ctypes.data, C.byref(params),
                                                                 out.ctypes.data, C.byref(n)), "ndt_sessions_loop_candidates_multi")
         return out[:n.value]
+
+    def _cross(self, fn, dtype, params, which, against, want_records):
+        """Both cross calls: `dtype` records for up to n * NDT_LOOP_MAX_SUBMAPS candidates.  want_records: None for the call
+        that takes no record array (the candidates), else whether to pass one and return it beside the records."""
+        room = self.n * NDT_LOOP_MAX_SUBMAPS
+        out = np.zeros(room, dtype=dtype)
+        rec = np.zeros((room, NDT_LOOP_MAX_CAND), dtype=RESULT_DTYPE) if want_records else None
+        w, a, n = self._active(which), self._active(against), C.c_int()
+        args = [self.h, None if w is None else w.ctypes.data, None if a is None else a.ctypes.data, C.byref(params), out.ctypes.data, C.byref(n)]
+        if want_records is not None:
+            args.append(None if rec is None else rec.ctypes.data)
+        self.ctx.check(getattr(lib(), fn)(*args), fn)
+        return (out[:n.value], rec[:n.value]) if want_records else out[:n.value]
+
+    def cross_candidates(self, params, which=None, against=None):
+        """ndt_sessions_cross_candidates: the candidates ndt_sessions_find_cross_loops would search -- for every searcher
+        (`which`) up to params.max_submaps closed submaps of the OTHER sessions (`against`), nearest first -- as
+        CROSS_CANDIDATE_DTYPE records (the device gate: one host wait)."""
+        return self._cross("ndt_sessions_cross_candidates", CROSS_CANDIDATE_DTYPE, params, which, against, None)
+
+    def find_cross_loops(self, params, which=None, against=None, want_records=False):
+        """ndt_sessions_find_cross_loops: one CROSS_LOOP_DTYPE record per cross candidate; with want_records also the match
+        records, as [candidates, NDT_LOOP_MAX_CAND] RESULT_DTYPE (the first n_cand of a row are written)."""
+        return self._cross("ndt_sessions_find_cross_loops", CROSS_LOOP_DTYPE, params, which, against, bool(want_records))
 
     def find_loops_multi(self, params, which=None, want_records=False):
         """ndt_sessions_find_loops_multi: one LOOP_MULTI_DTYPE record per candidate; with want_records also the match records,

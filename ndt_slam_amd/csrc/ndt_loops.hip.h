@@ -2,8 +2,9 @@
 // 4.19): the host gating of one candidate submap per session, or of several, and the search of all candidates in one set of
 // launches -- the newest scans into the robot frame, the pre-filter, the batched build of the old submaps' maps, the multi-job
 // sweep and pick (ndt_score.hip.h), the candidates' guesses, the multi-map match and, for the _multi form, the multi-map
-// ranged verification (ndt_fit_points.hip.h).  Included at the end of ndt_mi355x.hip (one translation unit).  Two kernels of
-// its own:
+// ranged verification (ndt_fit_points.hip.h).  The same search serves the loops between sessions (ndt_cross.hip.h, included
+// behind this file): a candidate's cloud and anchor pose may be another session's.  Included at the end of ndt_mi355x.hip (one
+// translation unit).  Two kernels of its own:
 //   loop_scan_kernel     every candidate's newest stored scan from the map frame into the robot frame (repose_point)
 //   loop_guess_kernel    per (candidate, slot): the lattice pose of the slot's pick as initial guess, the candidate's filtered
 //                        scan laid out once more behind a device-built offset, and the slot's map (-1: no pick in that slot)
@@ -80,6 +81,17 @@ int loop_check_params(ndt_ctx *ctx, const ndt_loop_params *p, const std::string 
   return NDT_OK;
 }
 
+// The lattice of the gating rule around a last pose (tx, ty, th[deg]).
+ndt_pose_lattice loop_lattice_around(const ndt_loop_params &p, const double *last) {
+  const double tx = last[0], ty = last[1], yaw = last[2] * M_PI / 180;      // DEG2RAD
+  ndt_pose_lattice L;
+  memset(&L, 0, sizeof(L));
+  L.x0 = tx - (double)p.half_x * p.step_xy; L.y0 = ty - (double)p.half_y * p.step_xy; L.yaw0 = yaw - (double)p.half_yaw * p.step_yaw;
+  L.step_x = p.step_xy; L.step_y = p.step_xy; L.step_yaw = p.step_yaw;
+  L.nx = 2 * p.half_x + 1; L.ny = 2 * p.half_y + 1; L.nyaw = 2 * p.half_yaw + 1;
+  return L;
+}
+
 // The gating of one trajectory as include/ndt_mi355x.h defines it (ndt_loop_gate's arguments, checked by the caller): the
 // eligible submaps of smallest dist, max_k of them at the most, in ascending (dist, submap), appended to *out as candidates of
 // `session`, every one with the session's one lattice.  Returns how many.  The single-candidate gating is max_k = 1.
@@ -112,12 +124,7 @@ int loop_gate_k(const double *T, int n, const int *sub_first, const int *sub_anc
     if (out->size() - at > (size_t)max_k) out->pop_back();
   }
   if (out->size() == at) return 0;
-  const double tx = T[3 * (n - 1)], ty = T[3 * (n - 1) + 1], yaw = T[3 * (n - 1) + 2] * M_PI / 180;      // DEG2RAD
-  ndt_pose_lattice L;
-  memset(&L, 0, sizeof(L));
-  L.x0 = tx - (double)p.half_x * p.step_xy; L.y0 = ty - (double)p.half_y * p.step_xy; L.yaw0 = yaw - (double)p.half_yaw * p.step_yaw;
-  L.step_x = p.step_xy; L.step_y = p.step_xy; L.step_yaw = p.step_yaw;
-  L.nx = 2 * p.half_x + 1; L.ny = 2 * p.half_y + 1; L.nyaw = 2 * p.half_yaw + 1;
+  const ndt_pose_lattice L = loop_lattice_around(p, T + 3 * (size_t)(n - 1));
   for (size_t i = at; i < out->size(); ++i) (*out)[i].lattice = L;
   return (int)(out->size() - at);
 }
@@ -158,14 +165,17 @@ bool loop_decide_ranged(const ndt_loop_multi_params &mp, const ndt_result *res, 
 
 // The search of the candidates C (DESIGN.md 4.15's list; 4.19: mp and mout, ndt_sessions_find_loops_multi -- several candidates
 // of a session in a row, rank by rank, one newest scan per session, the ranged verification behind the match); the arguments
-// have passed the entry point's refusals.  `out` (the single search) or `mout`.
+// have passed the entry point's refusals.  `out` (the single search) or `mout`.  owner (ndt_sessions_find_cross_loops, 4.20):
+// the session whose closed cloud and trajectory candidate j's submap and anchor scan are numbered in; nullptr: the candidate's own.
 int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<ndt_loop_candidate> &C, uint64_t P, ndt_loop *out,
-                  ndt_result *records_host, const ndt_loop_multi_params *mp = nullptr, ndt_loop_multi *mout = nullptr) {
+                  ndt_result *records_host, const ndt_loop_multi_params *mp = nullptr, ndt_loop_multi *mout = nullptr,
+                  const int *owner = nullptr) {
   ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ndt_sessions_stats stats{};
   const size_t J = C.size(), K = (size_t)p.top_k, B = J * K;
-  const char *fn = mp ? "ndt_sessions_find_loops_multi" : "ndt_sessions_find_loops";
+  const char *fn = owner ? "ndt_sessions_find_cross_loops" : mp ? "ndt_sessions_find_loops_multi" : "ndt_sessions_find_loops";
+  auto owner_of = [&](size_t j) -> SsSession & { return s->ses[(size_t)(owner ? owner[j] : C[j].session)]; };
   stats.sessions_stepped = (int)J;
   auto loop_of = [&](size_t j) -> ndt_loop & { return mout ? mout[j].loop : out[j]; };
   // candidate j's newest scan among the call's nS (one per session: the candidates of a session lie in a row) and its rank
@@ -233,10 +243,10 @@ int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<n
   std::vector<const float *> bxy(J); std::vector<size_t> bn(J); std::vector<ndt_params> bp(J, s->prm.match);
   std::vector<ndt_map *> maps(J); std::vector<int> code(J, NDT_OK);
   for (size_t j = 0; j < J; ++j) {
-    SsSession &Q = s->ses[(size_t)C[j].session];
+    const SsSession &Q = owner_of(j);
     const uint64_t a = Q.closed_off[(size_t)C[j].submap];
     bxy[j] = (const float *)(Q.closed.p + a); bn[j] = (size_t)(Q.closed_off[(size_t)C[j].submap + 1] - a);
-    maps[j] = loop_map_slot(Q, rank[j]);
+    maps[j] = loop_map_slot(s->ses[(size_t)C[j].session], rank[j]);
   }
   LP_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn));
   LP_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn, code.data()));
@@ -306,7 +316,7 @@ int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<n
     if (!mp) ok = L.cand_cost[L.best] <= p.max_cost;
     const ndt_result &w = res[j * K + (size_t)L.best];
     L.pose[0] = w.pose[0]; L.pose[1] = w.pose[1]; L.pose[2] = w.pose[2] * 180 / M_PI;      // RAD2DEG
-    const SsSession &Q = s->ses[(size_t)C[j].session];
+    const SsSession &Q = owner_of(j);
     // (a pose that is not finite leaves rel at 0: the cost rule keeps such a record from being found)
     if (ndt_pg_edge_between(Q.traj.data() + 3 * (size_t)C[j].anchor_scan, L.pose, &L.edge) == NDT_OK) L.found = ok;
   }
@@ -362,23 +372,31 @@ int loop_search_entry(ndt_sessions *s, const unsigned char *which, const ndt_loo
   return rc;
 }
 
+// The refusals of one trajectory's arrays (f: the function, and for the cross gate the track).
+int loop_check_arrays(ndt_ctx *ctx, const std::string &f, const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor,
+                      const uint64_t *sub_offsets, int n_submaps) {
+  if (n_scans < 1 || n_scans > (size_t)INT32_MAX || n_submaps < 1) return fail(ctx, NDT_E_ARG, f + ": need 1 <= n_scans <= 2^31 - 1 and n_submaps >= 1");
+  for (int m = 0; m < n_submaps; ++m) {
+    const bool ordered = m == 0 ? sub_first[0] == 0 : sub_first[m] >= sub_first[m - 1];
+    if (!ordered || sub_first[m] < 0 || (size_t)sub_first[m] >= n_scans || sub_anchor[m] < 0 || (size_t)sub_anchor[m] >= n_scans ||
+        sub_offsets[m + 1] < sub_offsets[m])
+      return fail(ctx, NDT_E_ARG, f + ": submap " + std::to_string(m) + ": sub_first, sub_anchor or sub_offsets is not a set's layout");
+  }
+  for (size_t k = 0; k < 3 * n_scans; ++k)
+    if (!(std::fabs(poses[k]) <= DBL_MAX)) return fail(ctx, NDT_E_ARG, f + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
+  return NDT_OK;
+}
+
 // The gating of one trajectory behind the NULL checks (ndt_loop_gate; mp: ndt_loop_gate_multi, whose `loop` part p is): the
 // refusals of the arrays, then of the parameters, then the candidates (session 0).
 int loop_gate_arrays(const char *fn, const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor,
                      const uint64_t *sub_offsets, int n_submaps, const ndt_loop_params &p, const ndt_loop_multi_params *mp,
                      std::vector<ndt_loop_candidate> *C) {
   const std::string f(fn);
-  if (n_scans < 1 || n_scans > (size_t)INT32_MAX || n_submaps < 1) return fail(nullptr, NDT_E_ARG, f + ": need 1 <= n_scans <= 2^31 - 1 and n_submaps >= 1");
-  for (int m = 0; m < n_submaps; ++m) {
-    const bool ordered = m == 0 ? sub_first[0] == 0 : sub_first[m] >= sub_first[m - 1];
-    if (!ordered || sub_first[m] < 0 || (size_t)sub_first[m] >= n_scans || sub_anchor[m] < 0 || (size_t)sub_anchor[m] >= n_scans ||
-        sub_offsets[m + 1] < sub_offsets[m])
-      return fail(nullptr, NDT_E_ARG, f + ": submap " + std::to_string(m) + ": sub_first, sub_anchor or sub_offsets is not a set's layout");
-  }
-  for (size_t k = 0; k < 3 * n_scans; ++k)
-    if (!(std::fabs(poses[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, f + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
+  int rc = loop_check_arrays(nullptr, f, poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps);
+  if (rc) return rc;
   uint64_t P = 0;
-  const int rc = mp ? loop_check_multi_params(nullptr, mp, f, &P) : loop_check_params(nullptr, &p, f, &P);
+  rc = mp ? loop_check_multi_params(nullptr, mp, f, &P) : loop_check_params(nullptr, &p, f, &P);
   if (rc) return rc;
   loop_gate_k(poses, (int)n_scans, sub_first, sub_anchor, sub_offsets, n_submaps - 1, p, 0, mp ? mp->max_submaps : 1, C);
   return NDT_OK;

@@ -236,6 +236,9 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_rl;                          // score sweep / relocalisation: poses or score volume, pair counts, candidates, guesses, records
   DevBuf<unsigned char> d_sj, d_pk;                    // multi-job sweep: the call's job table and prefix table of tiles; multi-job pick: its job table
   StagedUpload<unsigned char> sj_tab, pk_tab;          // ... their stagings (one each: a pick queued behind a sweep does not wait for the sweep's upload)
+  DevBuf<unsigned char> d_cg;                          // ndt_cross_gate_batch: the call's table (rows, packed poses, searchers), the (searcher x row) minima, the picks (ndt_cross.hip.h)
+  StagedUpload<unsigned char> cg_tab;                  // ... the table's staging
+  PinnedBuf<unsigned char> h_cg;                       // ... the picks' read-back
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
@@ -4341,3 +4344,4 @@ int ndt_lattice_select_multi_dev(ndt_ctx *ctx, const ndt_score_job *jobs, int n_
 }  // extern "C"
 
 #include "ndt_loops.hip.h"
+#include "ndt_cross.hip.h"

@@ -665,15 +665,18 @@ def load_occupancy(stem):
 # steps a corrected session is not searched again, remake_closed = behind correct() every corrected session's closed submaps
 # are computed again from the scan archive (sessions.remake_closed) instead of staying rigidly moved, multi = None or a
 # capi.LoopMultiParams: the search is then sessions.find_loops_multi with it (several old submaps per session, accepted on
-# ranged fitness; its `loop` part replaces `loop`) and every edge found for a session goes into that session's one graph
+# ranged fitness; its `loop` part replaces `loop`) and every edge found for a session goes into that session's one graph,
+# cross = None or a capi.LoopMultiParams: behind the closing inside the sessions comes one sessions.find_cross_loops with it
+# (the sessions must share a map frame), one joint graph per group of sessions that its edges tie together, and one correct()
 class LoopClosure(collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")):
     """The five fields above as a tuple, as before (its _fields, its length and its unpacking are unchanged), and the
-    attributes remake_closed (default False) and multi (default None) beside them."""
+    attributes remake_closed (default False), multi (default None) and cross (default None) beside them."""
 
-    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None):
+    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None, cross=None):
         self = super().__new__(cls, loop, pg, odo_info, every, cooldown)
         self.remake_closed = bool(remake_closed)
         self.multi = multi
+        self.cross = cross
         return self
 
 
@@ -718,6 +721,78 @@ def loops_graph(poses, loop_edges, odo_info):
 def loop_graph(poses, loop_edge, odo_info):
     """loops_graph with one loop: the n arcs of a trajectory of n poses."""
     return loops_graph(poses, [loop_edge], odo_info)
+
+
+def cross_graph(trajs, loop_edges_per_session, cross_edges, odo_info):
+    """The joint pose graph of a group of sessions (host only).  The nodes are the trajectories `trajs` ([n_i, 3] each, in
+    ascending session order) back to back: node offset[i] + k is scan k of trajectory i.  The arcs: per trajectory, in order,
+    what loops_graph(trajs[i], loop_edges_per_session[i], odo_info) makes, its indices shifted by offset[i]; then every cross
+    edge (a, b, edge) -- `edge` found by a searcher that is trajectory b in a closed submap of trajectory a (ndt_cross_loop:
+    edge.from a scan of a, edge.to a scan of b) -- with from shifted by offset[a] and to by offset[b], in the given order.
+    -> (the nodes [sum n_i, 3], the arcs as capi.PG_EDGE_DTYPE, offset)."""
+    from . import capi
+    trajs = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3) for t in trajs]
+    if len(loop_edges_per_session) != len(trajs):
+        raise ValueError("cross_graph needs one list of loop edges per trajectory")
+    offset = np.concatenate([[0], np.cumsum([len(t) for t in trajs])]).astype(np.int64)
+    parts = []
+    for i, t in enumerate(trajs):
+        g = loops_graph(t, loop_edges_per_session[i], odo_info)
+        g["from"] += int(offset[i])
+        g["to"] += int(offset[i])
+        parts.append(g)
+    tail = np.zeros(len(cross_edges), dtype=capi.PG_EDGE_DTYPE)
+    for k, (a, b, edge) in enumerate(cross_edges):
+        if not (0 <= a < len(trajs) and 0 <= b < len(trajs)) or a == b:
+            raise ValueError("cross_graph: cross edge %d does not tie two trajectories of the group" % k)
+        names = getattr(getattr(edge, "dtype", None), "names", None) or ()
+        tail[k]["from"] = int(edge["from" if "from" in names else "from_"]) + int(offset[a])
+        tail[k]["to"] = int(edge["to"]) + int(offset[b])
+        tail[k]["rel"], tail[k]["info"] = edge["rel"], edge["info"]
+    return np.concatenate(trajs), np.concatenate(parts + [tail]), offset
+
+
+def _close_cross(ctx, sessions, lc, which):
+    """One cross search of the sessions `which` against all, the sessions grouped by the edges found, one batch with a joint
+    graph per group, correct() for every session of a group whose graph converged -> the corrected sessions' flags."""
+    from . import capi
+    S = len(which)
+    corrected = np.zeros(S, dtype=np.uint8)
+    found = [l for l in sessions.find_cross_loops(lc.cross, which) if l["m"]["loop"]["status"] == 0 and l["m"]["loop"]["found"]]
+    if not found:
+        return corrected
+    root = list(range(S))
+
+    def find(i):
+        while root[i] != i:
+            root[i] = root[root[i]]
+            i = root[i]
+        return i
+    for l in found:
+        a, b = find(int(l["map_session"])), find(int(l["m"]["loop"]["cand"]["session"]))
+        root[max(a, b)] = min(a, b)
+    groups = collections.OrderedDict()
+    for i in sorted({int(l["map_session"]) for l in found} | {int(l["m"]["loop"]["cand"]["session"]) for l in found}):
+        groups.setdefault(find(i), []).append(i)
+    nodes, arcs, noff, eoff, offsets = [], [], [0], [0], []
+    for members in groups.values():
+        place = {i: k for k, i in enumerate(members)}
+        cross = [(place[int(l["map_session"])], place[int(l["m"]["loop"]["cand"]["session"])], l["m"]["loop"]["edge"])
+                 for l in found if int(l["map_session"]) in place]
+        n, e, off = cross_graph([sessions.trajectory(i)[0] for i in members], [[] for _ in members], cross, lc.odo_info)
+        nodes.append(n); arcs.append(e); offsets.append(off)
+        noff.append(noff[-1] + len(n)); eoff.append(eoff[-1] + len(e))
+    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(nodes), np.array(noff, dtype=np.uint64), np.concatenate(arcs),
+                                         np.array(eoff, dtype=np.uint64), lc.pg)
+    fix = {}
+    for g, members in enumerate(groups.values()):
+        if res[g]["status"] == 0 and res[g]["converged"]:
+            for k, i in enumerate(members):
+                fix[i] = new[noff[g] + int(offsets[g][k]):noff[g] + int(offsets[g][k + 1])]
+    if fix:
+        for i in sessions.correct(fix):
+            corrected[i] = 1
+    return corrected
 
 
 def _close_loops(ctx, sessions, lc, which):
@@ -765,7 +840,11 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
     for the loops found, correct() for the graphs that end with status 0 and converged, with loop_closure.remake_closed set
     remake_closed(corrected) -- the corrected sessions' closed submaps again from the archive -- and, when grids are in use,
     occ_rebuild(grids, which = corrected, clear = True).  The returned and written poses are then the final trajectories
-    (sessions.trajectory(i)), not the poses as the steps gave them.  A `sessions` object given by the caller must have
+    (sessions.trajectory(i)), not the poses as the steps gave them.  With loop_closure.cross set, behind that closing of every
+    search comes one find_cross_loops (the searched sessions against all; the logs must then share a map frame), one
+    optimize_pose_graphs batch with a joint graph (cross_graph) per group of sessions its edges tie together and one correct()
+    for every session of a converged group; remake_closed and occ_rebuild then take the sessions either closing corrected.
+    A `sessions` object given by the caller must have
     find_loops (else ValueError) and, for the grids, its archive on."""
     from . import capi
     if loop_closure is not None and sessions is not None and not hasattr(sessions, "find_loops"):
@@ -821,6 +900,8 @@ def run_sessions_resident(ctx, logs, poses_names=None, map_names=None, separated
             if loop_closure is not None and n_steps % loop_closure.every == 0:
                 search = np.array([bool(poses[i]) and n_steps >= quiet_until[i] for i in range(S)], dtype=np.uint8)
                 corrected = _close_loops(ctx, sessions, loop_closure, search) if search.any() else search
+                if getattr(loop_closure, "cross", None) is not None and search.any():
+                    corrected = corrected | _close_cross(ctx, sessions, loop_closure, search)
                 for i in np.nonzero(corrected)[0]:
                     quiet_until[i] = n_steps + loop_closure.cooldown
                 if getattr(loop_closure, "remake_closed", False) and corrected.any():
