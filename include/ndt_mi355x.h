@@ -1162,14 +1162,19 @@ int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const n
  * dead slot, the records' transforms in place, max_d2; statistics only), whose J * top_k ndt_fit_stats travel back with the
  * records.  Two host waits; the number of launches, copies and waits depends neither on the number of sessions nor on
  * max_submaps.  The set owns up to NDT_LOOP_MAX_SUBMAPS loop maps per session, the slot is the candidate's rank, slot 0 is the
- * map ndt_sessions_find_loops keeps; all are destroyed with the set.  The call changes nothing of the SLAM state.
+ * map ndt_sessions_find_loops keeps; all are destroyed with the set.  A slot is rebuilt in place by every search that has a
+ * candidate of that rank for the session -- the three searches share the slots, and a cross search builds ANOTHER session's
+ * cloud into the searcher's slot -- and no result depends on what a slot held before.  The call changes nothing of the SLAM
+ * state.
  *
  * The decision, per candidate, on the host.  For slot c < n_cand, st = fit[c], r = record c:
  *   usable_c = r.converged && st.n_in >= 1 && (double)st.n_in >= min_overlap * (double)st.n_points (one rounded product);
  *   cand_cost[c] = usable_c ? st.fitness : 1e7;   ok_c = cand_cost[c] <= loop.max_cost;
  *   best = the slot that is first by: ok before not ok; then the larger (usable_c ? st.n_in : 0); then the lower cand_cost;
  *   then the lower c.  found = ok_best.  pose and edge come from the best record as ndt_sessions_find_loops forms them; with
- *   n_cand == 0: best = -1, pose and rel 0.
+ *   n_cand == 0: best = -1, pose and rel 0.  ok_c is the plain comparison also for a slot that is not usable: with
+ *   loop.max_cost = +inf every candidate with a record is found (cost 1e7), with -inf none is; the caller that wants a
+ *   verified loop keeps max_cost finite.
  * The inlier count ranks before the cost on purpose (ndt_relocalize's callers rank by ranged fitness alone): an alias that
  * overlaps less has fewer inliers, each of them tighter, and the lowest ranged fitness alone would pick it.
  *
@@ -1255,8 +1260,9 @@ int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, c
  * beyond eligibility, nor on max_submaps.  (c) A refused map costs its candidate alone; an empty newest scan gives the empty
  * record; a set of one session, or no eligible pair, gives *n_out = 0 and NDT_OK with nothing queued behind the gate.  (d) The
  * SLAM state is untouched.  (e) ndt_sessions_get_stats: host_waits 3 (the gate, the boxes, the records), 1 when the gate finds
- * nothing (0 when there is no searcher or no track: the gate is not run), sessions_stepped = J; launches, copies and waits do
- * not depend on the number of sessions.
+ * nothing (0 when there is no searcher or no track: the gate is not run), 1 also when every searcher that has a candidate has
+ * an empty newest scan (the candidates are given, each with the empty record, and nothing is queued behind the gate), 2 when
+ * no map could be built; sessions_stepped = J; launches, copies and waits do not depend on the number of sessions.
  * Refusals: those of ndt_sessions_find_loops_multi; NDT_E_HIP on a dead set.
  * Out of scope: an unknown offset between the sessions' frames; keeping cross edges from one search to the next; loop maps
  * that stay valid across calls; a robust back end. */

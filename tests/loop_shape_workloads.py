@@ -72,8 +72,10 @@ def _logs(specs, n_beams=BEAMS):
     return [([x.copy() for x in _DRIVES[(spec, n_beams)][0]], _DRIVES[(spec, n_beams)][1].copy()) for spec in specs]
 
 
-def _call(k, lp_, which, tag=""):
-    return dict(k=k, lp=lp_, which=list(which), tag=tag)
+def _call(k, lp_, which, tag="", **more):
+    """more (tests/loop_multi_shape_workloads.py): kind "multi" or "cross", mp (the ndt_loop_multi_params fields beside `loop`),
+    against (a flag per session of the set, cross only); a call without them is a single search."""
+    return dict(k=k, lp=lp_, which=list(which), tag=tag, **more)
 
 
 def _family(name, logs, calls, cls=None, starts=None, tolerant=False, **more):

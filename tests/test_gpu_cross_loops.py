@@ -20,6 +20,7 @@ from session_correct_helpers import CorrectedChain
 from session_helpers import lockstep, same_records, session_logs
 from test_gpu_loops import params, run_lockstep
 from test_gpu_loops_multi import assert_decision, field_rows
+from test_gpu_posegraph import POSE_TOL
 from test_gpu_sessions_correct import chain_poses, same_snapshot, snapshot
 from gpu_support import gpu, sync, to_dev  # noqa: F401
 
@@ -304,6 +305,10 @@ def test_two_chains_joined_by_one_edge_converge(gpu):
           % (res[0]["status"], res[0]["converged"], res[0]["iterations"], res[0]["cg_iterations"], res[0]["cost_initial"], res[0]["cost_final"],
              len(ref["steps"]), ref["costs"][-1], gap))
     assert res[0]["status"] == 0 and res[0]["converged"] == 1
+    # the same poses: metres and degrees both under the bound in metres and radians (a degree is the larger number); the optimum
+    # has zero residuals, so the cost is held as test_gpu_posegraph holds its zero-residual case, not relative to the oracle's
+    assert gap <= POSE_TOL, gap
+    assert res[0]["cost_final"] <= 1e-18 * res[0]["cost_initial"], (res[0]["cost_final"], res[0]["cost_initial"], ref["costs"][-1])
 
 
 # ------------------------------------------------------------------------------------------ replay

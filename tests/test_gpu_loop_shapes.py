@@ -129,9 +129,11 @@ def search(sc, ses, fam, call):
         c: len(chain.pcmaps[c].submaps[int(gates[c]["submap"])].p_cloud) for c in gates if gates[c] is not None})
 
 
-def run_family(capi, ctx, fam):
+def run_family(capi, ctx, fam, search=None):
     """The family's set beside the chain (one chain session per class), a twin set that never searches where the family asks
-    for one -> the result of every call."""
+    for one -> the result of every call.  search: another search(sc, ses, fam, call) than this module's
+    (tests/test_gpu_loop_multi_shapes.py)."""
+    search = search or globals()["search"]
     cls, p = fam["cls"], fam["p"]
     S = len(cls)
     ses = capi.Sessions(ctx, S, capi.session_params_from_launch(p))
