@@ -1,7 +1,7 @@
 // Loops between the sessions of a set (ndt_cross_gate, ndt_cross_gate_batch, ndt_sessions_cross_candidates,
 // ndt_sessions_find_cross_loops): the cross gate -- every searcher against every closed submap of every other
 // track -- as a host definition and as a device form that equals it to the bit, and the search of its candidates by
-// ss_find_loops (ndt_loops.hip.h) with the candidate's cloud and anchor taken from the track.  Included behind ndt_loops.hip.h
+// LpSearch (ndt_loops.hip.h) with the candidate's cloud and anchor taken from the track.  Included behind ndt_loops.hip.h
 // (one translation unit).  Two kernels of its own:
 //   cross_dist_kernel    per (row, searcher): the smallest squared distance from the searcher's last pose to a pose of the row
 //                        (a closed submap's scan range, staged in LDS), and the first scan that attains it
@@ -268,11 +268,10 @@ int cross_gate_dev(ndt_ctx *ctx, const double *last_poses, const int *newest_sca
 }
 
 // Who searches and who is searched in a set (include/ndt_mi355x.h), and the device gate on them: the candidates of all
-// searchers in a row, cand.session and map_session as session indices.  *gated: the gate ran (one host wait).
+// searchers in a row, cand.session and map_session as session indices.  A gate that ran adds its one host wait to *stats.
 int cross_gate_set(ndt_sessions *s, const unsigned char *which, const unsigned char *against, const ndt_loop_multi_params &p, const char *fn,
-                   std::vector<ndt_cross_candidate> *C, bool *gated, ndt_sessions_stats *stats) {
+                   std::vector<ndt_cross_candidate> *C, ndt_sessions_stats *stats) {
   C->clear();
-  *gated = false;
   std::vector<int> track_ses, track_of((size_t)s->S, -1);
   std::vector<std::vector<int>> anchors;
   std::vector<ndt_cross_track> tr;
@@ -307,7 +306,6 @@ int cross_gate_set(ndt_sessions *s, const unsigned char *which, const unsigned c
   size_t h2d = 0, d2h = 0;
   CG_TRY(cross_gate_dev(s->ctx, last.data(), newest.data(), own.data(), who.data(), (int)who.size(), tr.data(), (int)tr.size(), p, all.data(),
                         n.data(), fn, &h2d, &d2h));
-  *gated = true;
   stats->host_waits++; stats->h2d_bytes += h2d; stats->d2h_bytes += d2h;
   for (size_t i = 0; i < who.size(); ++i)
     for (int r = 0; r < n[i]; ++r) {
@@ -318,42 +316,38 @@ int cross_gate_set(ndt_sessions *s, const unsigned char *which, const unsigned c
   return NDT_OK;
 }
 
-// Both set calls: the refusals, the gate, and for out_loops the search.  A HIP failure kills the set as in a step.
+// Both set calls: the bracket, the refusals, the gate, and for out_loops the search.  The set's stats -- the gate's part and
+// the search's -- are written once; behind a search that failed they hold the gate's part alone.
 int cross_set_entry(ndt_sessions *s, const unsigned char *which, const unsigned char *against, const ndt_loop_multi_params *p,
                     ndt_cross_candidate *out_cand, ndt_cross_loop *out_loops, int *n_out, ndt_result *records_host, const char *fn) {
+  SetCall call{s, fn};
   uint64_t P = 0;
-  CG_TRY(loop_multi_entry_checks(s, p, out_cand ? (const void *)out_cand : (const void *)out_loops, n_out, fn, &P));
-  ndt_ctx *ctx = s->ctx;
-  const std::string f(fn);
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  auto dies = [&](int rc) {
-    if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) { s->dead = true; hipError_t e = hipStreamSynchronize(ctx->stream); (void)e; }
-    return rc;
-  };
-  std::vector<ndt_cross_candidate> C;
-  bool gated = false;
-  ndt_sessions_stats gate_stats{};
-  CG_TRY(dies(cross_gate_set(s, which, against, *p, fn, &C, &gated, &gate_stats)));
-  if (C.size() * P > (uint64_t)INT32_MAX)
-    return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
-  *n_out = (int)C.size();
-  s->stats = gate_stats;
-  if (out_cand) {
-    if (!C.empty()) memcpy(out_cand, C.data(), C.size() * sizeof(ndt_cross_candidate));
-    return NDT_OK;
-  }
-  if (C.empty()) return NDT_OK;
-  std::vector<ndt_loop_candidate> lc(C.size());
-  std::vector<int> owner(C.size());
-  std::vector<ndt_loop_multi> M(C.size());
-  for (size_t j = 0; j < C.size(); ++j) { lc[j] = C[j].cand; owner[j] = C[j].map_session; }
-  memset(out_loops, 0, C.size() * sizeof(ndt_cross_loop));
-  const int rc = dies(ss_find_loops(s, p->loop, lc, P, nullptr, records_host, p, M.data(), owner.data()));
-  // (ss_find_loops has set the set's stats to its own part on every way out that got as far as its table)
-  s->stats.host_waits += gate_stats.host_waits; s->stats.h2d_bytes += gate_stats.h2d_bytes; s->stats.d2h_bytes += gate_stats.d2h_bytes;
-  if (rc) return rc;
-  for (size_t j = 0; j < C.size(); ++j) { out_loops[j].m = M[j]; out_loops[j].map_session = C[j].map_session; }
-  return NDT_OK;
+  int rc = call.enter();
+  if (rc || (rc = loop_entry_checks(call.ctx, call.f, p ? &p->loop : nullptr, p, out_cand ? (void *)out_cand : (void *)out_loops, n_out, &P))) return rc;
+  return call.run([&] {
+    std::vector<ndt_cross_candidate> C;
+    ndt_sessions_stats stats{};
+    CG_TRY(cross_gate_set(s, which, against, *p, fn, &C, &stats));
+    if (C.size() * P > (uint64_t)INT32_MAX)
+      return call.refuse("more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
+    *n_out = (int)C.size();
+    int found = NDT_OK;
+    if (out_cand) give_candidates(C, out_cand, n_out);
+    else if (!C.empty()) {
+      const ndt_sessions_stats gate = stats;
+      std::vector<ndt_loop_candidate> lc(C.size());
+      std::vector<ndt_loop_multi> M(C.size());
+      for (size_t j = 0; j < C.size(); ++j) lc[j] = C[j].cand;
+      memset(out_loops, 0, C.size() * sizeof(ndt_cross_loop));
+      LpSearch T{s, p->loop, lc, P, records_host, stats};
+      T.ranged(p, M.data(), fn);
+      for (size_t j = 0; j < C.size(); ++j) T.owner[j] = C[j].map_session;
+      if ((found = T.run())) stats = gate;
+      else for (size_t j = 0; j < C.size(); ++j) { out_loops[j].m = M[j]; out_loops[j].map_session = C[j].map_session; }
+    }
+    s->stats = stats;
+    return found;
+  });
 }
 
 #undef CG_TRY

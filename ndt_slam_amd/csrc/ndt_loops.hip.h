@@ -81,6 +81,17 @@ int loop_check_params(ndt_ctx *ctx, const ndt_loop_params *p, const std::string 
   return NDT_OK;
 }
 
+// The refusals ndt_loop_multi_params adds to those of its `loop` part.
+int loop_check_multi_params(ndt_ctx *ctx, const ndt_loop_multi_params *p, const std::string &f, uint64_t *P) {
+  const int rc = loop_check_params(ctx, &p->loop, f, P);
+  if (rc) return rc;
+  if (p->max_submaps < 1 || p->max_submaps > NDT_LOOP_MAX_SUBMAPS)
+    return fail(ctx, NDT_E_ARG, f + ": max_submaps must be in 1 .. " + std::to_string(NDT_LOOP_MAX_SUBMAPS));
+  if (!(p->max_d2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_d2 is NaN or negative");
+  if (!(p->min_overlap >= 0.0 && p->min_overlap <= 1.0)) return fail(ctx, NDT_E_ARG, f + ": min_overlap is NaN or outside [0, 1]");
+  return NDT_OK;
+}
+
 // The lattice of the gating rule around a last pose (tx, ty, th[deg]).
 ndt_pose_lattice loop_lattice_around(const ndt_loop_params &p, const double *last) {
   const double tx = last[0], ty = last[1], yaw = last[2] * M_PI / 180;      // DEG2RAD
@@ -143,9 +154,6 @@ void loop_gate(const ndt_sessions *s, const unsigned char *which, const ndt_loop
   }
 }
 
-// The set's loop map of a session's candidate of rank r (slot 0: the one ndt_sessions_find_loops keeps).
-ndt_map *&loop_map_slot(SsSession &Q, int r) { return r == 0 ? Q.loop_map : Q.loop_map_more[r - 1]; }
-
 // The decision of ndt_sessions_find_loops_multi for one candidate whose records and ranged statistics are in (include/
 // ndt_mi355x.h states the rule): cand_cost and best; returns ok_best.
 bool loop_decide_ranged(const ndt_loop_multi_params &mp, const ndt_result *res, ndt_loop_multi *M) {
@@ -163,40 +171,55 @@ bool loop_decide_ranged(const ndt_loop_multi_params &mp, const ndt_result *res, 
   return best_ok;
 }
 
-// The search of the candidates C (DESIGN.md 4.15's list; 4.19: mp and mout, ndt_sessions_find_loops_multi -- several candidates
-// of a session in a row, rank by rank, one newest scan per session, the ranged verification behind the match); the arguments
-// have passed the entry point's refusals.  `out` (the single search) or `mout`.  owner (ndt_sessions_find_cross_loops, 4.20):
-// the session whose closed cloud and trajectory candidate j's submap and anchor scan are numbered in; nullptr: the candidate's own.
-int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<ndt_loop_candidate> &C, uint64_t P, ndt_loop *out,
-                  ndt_result *records_host, const ndt_loop_multi_params *mp = nullptr, ndt_loop_multi *mout = nullptr,
-                  const int *owner = nullptr) {
-  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ndt_sessions_stats stats{};
-  const size_t J = C.size(), K = (size_t)p.top_k, B = J * K;
-  const char *fn = owner ? "ndt_sessions_find_cross_loops" : mp ? "ndt_sessions_find_loops_multi" : "ndt_sessions_find_loops";
-  auto owner_of = [&](size_t j) -> SsSession & { return s->ses[(size_t)(owner ? owner[j] : C[j].session)]; };
+// The search of the candidates C (DESIGN.md 4.15's list; 4.19: the ranged verification; 4.20: the loops between sessions); the
+// arguments have passed the entry point's refusals.  What its three callers differ in is set up once, by single() or ranged()
+// (and `owner`, which the cross search overwrites): the function's name in messages; where record j is written (loop[j], and
+// multi[j] with its slots' ranged statistics); whether the ranged verification runs, and with it the rule that decides best and
+// found (mp); the session whose closed cloud and trajectory candidate j's submap and anchor scan are numbered in (owner[j]).
+// The parts add to `stats`, which the entry owns.
+struct LpSearch {
+  ndt_sessions *s; const ndt_loop_params &p; const std::vector<ndt_loop_candidate> &C; uint64_t P; ndt_result *records_host;
+  ndt_sessions_stats &stats;
+  const char *fn = "ndt_sessions_find_loops"; const ndt_loop_multi_params *mp = nullptr;
+  std::vector<ndt_loop *> loop; std::vector<ndt_loop_multi *> multi; std::vector<int> owner;
+  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const size_t J = C.size(), K = (size_t)p.top_k, B = J * K;
+  std::vector<int> scan_of, rank;                  // candidate j's newest scan among the call's nS (one per session) and its rank
+  size_t nS = 0, longest = 0, NJ = 0, N = 0;       // NJ: the points of every candidate's scan, a shared one counted once per candidate
+  std::vector<LpScan> rows; std::vector<uint64_t> raw_off, vol; std::vector<ndt_score_job> jobs;
+  Regions A, D;                                    // the table; the device scratch
+  size_t a_rows = 0, a_off = 0, a_jobs = 0, d_robot = 0, d_flt = 0, d_foff = 0, d_score = 0, d_pairs = 0, d_cand = 0, d_ncand = 0, d_rep = 0,
+         d_roff = 0, d_init = 0, d_cs = 0, d_mapof = 0, d_res = 0, d_fit = 0;
+  SsBack back{s}; size_t r_res = 0, r_cand = 0, r_cs = 0, r_ncand = 0, r_fit = 0;      // host wait 2's read-back
+  std::vector<const ndt_map *> rd; const ndt_map *first = nullptr;      // the map every candidate's slots read; the first one built
+  template <typename T> T *dev(size_t o) const { return Regions::at<T>(s->lp.p, o); }
+
+  void single(ndt_loop *out) { for (size_t j = 0; j < J; ++j) { loop.push_back(out + j); owner.push_back(C[j].session); } }
+  void ranged(const ndt_loop_multi_params *m, ndt_loop_multi *mout, const char *name) {
+    mp = m; fn = name;
+    for (size_t j = 0; j < J; ++j) { loop.push_back(&mout[j].loop); multi.push_back(mout + j); owner.push_back(C[j].session); }
+  }
+  int plan(); int scans(); int maps(); int match(); void decide(); int run();      // the parts, in this order, and the search
+};
+
+// (1) the plan: the records' fixed part, every candidate's scan and rank (the candidates of a session lie in a row), the newest
+// scans' rows with an empty scan nS behind them -- the scan of a candidate whose map is refused: its poses then score nothing and
+// nothing is picked --, volume offsets and jobs (N = 0: every newest scan is empty, nothing to search with); (2) the table: the
+// rows | their offsets in the scratch | lattices, volume offsets, scans; the layouts of the device scratch and of the read-back
+int LpSearch::plan() {
   stats.sessions_stepped = (int)J;
-  auto loop_of = [&](size_t j) -> ndt_loop & { return mout ? mout[j].loop : out[j]; };
-  // candidate j's newest scan among the call's nS (one per session: the candidates of a session lie in a row) and its rank
-  std::vector<int> scan_of(J), rank(J);
-  size_t nS = 0;
+  scan_of.resize(J); rank.resize(J); jobs.resize(J); vol.assign(J + 1, 0);
   for (size_t j = 0; j < J; ++j) {
     const bool same = j > 0 && C[j].session == C[j - 1].session;
     rank[j] = same ? rank[j - 1] + 1 : 0;
     scan_of[j] = same ? scan_of[j - 1] : (int)nS++;
-    if (mout) { memset(&mout[j], 0, sizeof(mout[j])); mout[j].rank = rank[j]; }
-    ndt_loop &L = loop_of(j);
+    if (mp) { memset(multi[j], 0, sizeof(*multi[j])); multi[j]->rank = rank[j]; }
+    ndt_loop &L = *loop[j];
     memset(&L, 0, sizeof(L));
     L.cand = C[j]; L.best = -1;
     L.edge.from = C[j].anchor_scan; L.edge.to = C[j].newest_scan;
     memcpy(L.edge.info, p.info, sizeof(p.info));
   }
-  // (1) the table: the newest scans' rows | their offsets in the scratch, with an empty scan nS behind them -- the scan of a
-  // candidate whose map is refused below: its poses then score nothing and nothing is picked | lattices, volume offsets, scans
-  std::vector<LpScan> rows(nS); std::vector<uint64_t> raw_off(nS + 2, 0), vol(J + 1, 0);
-  std::vector<ndt_score_job> jobs(J);
-  size_t longest = 0, NJ = 0;      // NJ: the points of every candidate's scan, a shared one counted once per candidate
+  rows.resize(nS); raw_off.assign(nS + 2, 0);
   for (size_t j = 0; j < J; ++j) {
     const SsSession &Q = s->ses[(size_t)C[j].session];
     const size_t k = Q.scan_off.size() - 2, u = (size_t)scan_of[j];
@@ -211,165 +234,177 @@ int ss_find_loops(ndt_sessions *s, const ndt_loop_params &p, const std::vector<n
     vol[j + 1] = vol[j] + P;
     jobs[j] = ndt_score_job{(int)j, scan_of[j], C[j].lattice};
   }
-  const size_t N = (size_t)raw_off[nS];
+  N = (size_t)raw_off[nS];
   raw_off[nS + 1] = raw_off[nS];
-  if (N == 0) { s->stats = stats; return NDT_OK; }      // every newest scan is empty: nothing to search with
-  Regions A;
-  const size_t a_rows = A.take(nS * sizeof(LpScan), 256), a_off = A.take((nS + 2) * 8, 256), a_jobs = A.take(J * sizeof(LpJob), 256);
-  Regions D;      // the device scratch
-  const size_t d_robot = D.take(N * 8, 256), d_flt = D.take(N * 8, 256), d_foff = D.take((nS + 2) * 8, 256), d_score = D.take(J * P * 8, 256),
-               d_pairs = D.take(J * P * 4, 256), d_cand = D.take(B * 8, 256), d_ncand = D.take(J * 4, 256), d_rep = D.take(K * NJ * 8, 256),
-               d_roff = D.take((B + 1) * 8, 256), d_init = D.take(B * 24, 256), d_cs = D.take(B * 8, 256), d_mapof = D.take(B * 4, 256),
-               d_res = D.take(B * sizeof(ndt_result), 256), d_fit = mp ? D.take(B * sizeof(ndt_fit_stats), 256) : 0;
-  Regions R;      // host wait 2's read-back
-  const size_t r_res = R.take(B * sizeof(ndt_result)), r_cand = R.take(B * 8), r_cs = R.take(B * 8), r_ncand = R.take(J * 4),
-               r_fit = mp ? R.take(B * sizeof(ndt_fit_stats)) : 0;
-  LP_TRY(s->lp_tab.reserve(ctx, A.end)); LP_TRY(s->d_lp_tab.ensure(ctx, A.end)); LP_TRY(s->lp.ensure(ctx, D.end)); LP_TRY(s->h_back.ensure(ctx, R.end));
-  unsigned char *h = s->lp_tab.h.p, *da = s->d_lp_tab.p, *dv = s->lp.p;
+  if (!N) return NDT_OK;
+  a_rows = A.take(nS * sizeof(LpScan), 256); a_off = A.take((nS + 2) * 8, 256); a_jobs = A.take(J * sizeof(LpJob), 256);
+  d_robot = D.take(N * 8, 256); d_flt = D.take(N * 8, 256); d_foff = D.take((nS + 2) * 8, 256); d_score = D.take(J * P * 8, 256);
+  d_pairs = D.take(J * P * 4, 256); d_cand = D.take(B * 8, 256); d_ncand = D.take(J * 4, 256); d_rep = D.take(K * NJ * 8, 256);
+  d_roff = D.take((B + 1) * 8, 256); d_init = D.take(B * 24, 256); d_cs = D.take(B * 8, 256); d_mapof = D.take(B * 4, 256);
+  d_res = D.take(B * sizeof(ndt_result), 256); d_fit = mp ? D.take(B * sizeof(ndt_fit_stats), 256) : 0;
+  LP_TRY(s->lp_tab.reserve(ctx, A.end)); LP_TRY(s->d_lp_tab.ensure(ctx, A.end)); LP_TRY(s->lp.ensure(ctx, D.end));
+  r_res = back.add(dev<ndt_result>(d_res), B); r_cand = back.add(dev<uint64_t>(d_cand), B); r_cs = back.add(dev<double>(d_cs), B);
+  r_ncand = back.add(dev<int>(d_ncand), J);
+  if (mp) r_fit = back.add(dev<ndt_fit_stats>(d_fit), B);
+  LP_TRY(back.reserve());
+  unsigned char *h = s->lp_tab.h.p;
   memcpy(h + a_rows, rows.data(), nS * sizeof(LpScan));
   memcpy(h + a_off, raw_off.data(), (nS + 2) * 8);
   for (size_t j = 0; j < J; ++j) A.at<LpJob>(h, a_jobs)[j] = LpJob{lattice_of(C[j].lattice), vol[j], scan_of[j], 0};
-  HIP_TRY(ctx, s->lp_tab.upload(da, 0, A.end, st));
+  HIP_TRY(ctx, s->lp_tab.upload(s->d_lp_tab.p, 0, A.end, st));
   stats.h2d_bytes += A.end;
-  float *robot = D.at<float>(dv, d_robot), *flt = D.at<float>(dv, d_flt);
-  uint64_t *flt_off = D.at<uint64_t>(dv, d_foff);
-  // (2) the newest scans in the robot frame, (3) filtered as a step filters its source -- each once, whoever names it
+  return NDT_OK;
+}
+
+// (3) the newest scans in the robot frame, filtered as a step filters its source -- each once, whoever names it
+int LpSearch::scans() {
+  const unsigned char *da = s->d_lp_tab.p;
   loop_scan_kernel<<<dim3((unsigned)std::min<size_t>(64, longest / 256 + 1), (unsigned)std::min<size_t>(nS, 65535)), 256, 0, st>>>(
-      (const LpScan *)(da + a_rows), (int)nS, (float2 *)robot);
+      (const LpScan *)(da + a_rows), (int)nS, dev<float2>(d_robot));
   HIP_TRY(ctx, hipGetLastError());
-  LP_TRY(ndt_prefilter_batch_dev(ctx, robot, sizeof(float2), (const uint64_t *)(da + a_off), (int)nS + 1, N, s->prm.leaf, flt, flt_off, st));
-  // (4) the old submaps' maps, each session's own from call to call, a slot per rank (host wait 1: the bounding boxes); a
-  // refused build costs its candidate alone
+  return ndt_prefilter_batch_dev(ctx, dev<float>(d_robot), sizeof(float2), (const uint64_t *)(da + a_off), (int)nS + 1, N, s->prm.leaf,
+                                 dev<float>(d_flt), dev<uint64_t>(d_foff), st);
+}
+
+// (4) the old submaps' maps, each searcher's own from call to call, a slot per rank (host wait 1: the bounding boxes); a
+// refused build costs its candidate alone.  first stays nullptr: no map at all -- nobody is found
+int LpSearch::maps() {
   std::vector<const float *> bxy(J); std::vector<size_t> bn(J); std::vector<ndt_params> bp(J, s->prm.match);
-  std::vector<ndt_map *> maps(J); std::vector<int> code(J, NDT_OK);
+  std::vector<ndt_map *> built(J); std::vector<int> code(J, NDT_OK);
   for (size_t j = 0; j < J; ++j) {
-    const SsSession &Q = owner_of(j);
+    const SsSession &Q = s->ses[(size_t)owner[j]];
     const uint64_t a = Q.closed_off[(size_t)C[j].submap];
     bxy[j] = (const float *)(Q.closed.p + a); bn[j] = (size_t)(Q.closed_off[(size_t)C[j].submap + 1] - a);
-    maps[j] = loop_map_slot(s->ses[(size_t)C[j].session], rank[j]);
+    built[j] = s->ses[(size_t)C[j].session].loop_maps[rank[j]];
   }
-  LP_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn));
-  LP_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), maps.data(), fn, code.data()));
+  LP_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), built.data(), fn));
+  LP_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)J, bp.data(), built.data(), fn, code.data()));
   stats.host_waits++; stats.d2h_bytes += J * 16 * sizeof(unsigned);
-  const ndt_map *any = nullptr;
   for (size_t j = 0; j < J; ++j) {
-    loop_of(j).status = code[j];
+    loop[j]->status = code[j];
     if (code[j] != NDT_OK) continue;
-    loop_map_slot(s->ses[(size_t)C[j].session], rank[j]) = maps[j];
-    if (!any) any = maps[j];
+    s->ses[(size_t)C[j].session].loop_maps[rank[j]] = built[j];
+    if (!first) first = built[j];
   }
-  if (!any) { s->stats = stats; return NDT_OK; }      // no map at all: nobody is found
-  std::vector<const ndt_map *> rd(J);
+  rd.resize(J);
   for (size_t j = 0; j < J; ++j) {
-    rd[j] = code[j] == NDT_OK ? maps[j] : any;
+    rd[j] = code[j] == NDT_OK ? built[j] : first;
     if (code[j] != NDT_OK) jobs[j].scan = (int)nS;      // (the empty scan)
   }
-  // (5) the sweep, (6) the pick, (7) the guesses and the scans' copies, (8) the match
-  double *score = D.at<double>(dv, d_score); uint32_t *pairs = D.at<uint32_t>(dv, d_pairs);
-  uint64_t *cand = D.at<uint64_t>(dv, d_cand); int *n_cand = D.at<int>(dv, d_ncand);
+  return NDT_OK;
+}
+
+// (5) the sweep, (6) the pick, (7) the guesses and the scans' copies, (8) the match and, for the ranged search, the verification
+// on the match's own arrays: every slot's statistics at its record's transform, no d2; a dead slot (map_of -1) reads no map
+int LpSearch::match() {
+  const float *flt = dev<float>(d_flt); const uint64_t *flt_off = dev<uint64_t>(d_foff);
+  double *score = dev<double>(d_score); uint32_t *pairs = dev<uint32_t>(d_pairs);
+  uint64_t *cand = dev<uint64_t>(d_cand); int *n_cand = dev<int>(d_ncand);
   LP_TRY(score_multi(ctx, rd.data(), (int)J, flt, flt_off, (int)nS + 1, N, longest, jobs.data(), (int)J, score, pairs, vol.data(), st));
   LP_TRY(ndt_lattice_select_multi_dev(ctx, jobs.data(), (int)J, score, pairs, vol.data(), p.top_k, p.local_max, cand, n_cand, st));
   stats.h2d_bytes += J * (sizeof(ScoreJob) + sizeof(PickJob)) + (J + 1) * 8;
-  loop_guess_kernel<<<(unsigned)B, 256, 0, st>>>((const LpJob *)(da + a_jobs), (int)J, (int)K, (const float2 *)flt, (const unsigned long long *)flt_off,
-                                                (const unsigned long long *)cand, n_cand, score, D.at<float2>(dv, d_rep),
-                                                D.at<unsigned long long>(dv, d_roff), D.at<double>(dv, d_init), D.at<double>(dv, d_cs),
-                                                D.at<int>(dv, d_mapof));
+  loop_guess_kernel<<<(unsigned)B, 256, 0, st>>>((const LpJob *)(s->d_lp_tab.p + a_jobs), (int)J, (int)K, (const float2 *)flt,
+                                                (const unsigned long long *)flt_off, (const unsigned long long *)cand, n_cand, score,
+                                                dev<float2>(d_rep), dev<unsigned long long>(d_roff), dev<double>(d_init), dev<double>(d_cs),
+                                                dev<int>(d_mapof));
   HIP_TRY(ctx, hipGetLastError());
-  LP_TRY(ndt_align_batch_multi_dev(ctx, rd.data(), (int)J, D.at<int>(dv, d_mapof), D.at<float>(dv, d_rep), D.at<uint64_t>(dv, d_roff), (int)B,
-                                   K * NJ, 0, D.at<double>(dv, d_init), D.at<ndt_result>(dv, d_res), st));
-  // (8b) the ranged verification on the match's own arrays: every slot's statistics at its record's transform, no d2; a dead
-  // slot (map_of -1) reads no map
-  if (mp) {
-    LP_TRY(ndt_fit_points_multi_dev(ctx, rd.data(), (int)J, D.at<int>(dv, d_mapof), D.at<float>(dv, d_rep), D.at<uint64_t>(dv, d_roff), (int)B,
-                                    K * NJ, 0, &D.at<ndt_result>(dv, d_res)->T00, sizeof(ndt_result), mp->max_d2, nullptr,
-                                    D.at<ndt_fit_stats>(dv, d_fit), st));
-    stats.h2d_bytes += J * sizeof(MapView);
-  }
-  // (9) host wait 2
-  unsigned char *hb = s->h_back.p;
-  HIP_TRY(ctx, hipMemcpyAsync(hb + r_res, dv + d_res, B * sizeof(ndt_result), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(hb + r_cand, dv + d_cand, B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(hb + r_cs, dv + d_cs, B * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(hb + r_ncand, dv + d_ncand, J * 4, hipMemcpyDeviceToHost, st));
-  if (mp) HIP_TRY(ctx, hipMemcpyAsync(hb + r_fit, dv + d_fit, B * sizeof(ndt_fit_stats), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.host_waits++; stats.d2h_bytes += B * (sizeof(ndt_result) + 16 + (mp ? sizeof(ndt_fit_stats) : 0)) + J * 4;
-  const ndt_result *res = R.at<ndt_result>(hb, r_res);
-  const uint64_t *h_cand = R.at<uint64_t>(hb, r_cand); const double *h_cs = R.at<double>(hb, r_cs); const int *h_n = R.at<int>(hb, r_ncand);
+  LP_TRY(ndt_align_batch_multi_dev(ctx, rd.data(), (int)J, dev<int>(d_mapof), dev<float>(d_rep), dev<uint64_t>(d_roff), (int)B, K * NJ, 0,
+                                   dev<double>(d_init), dev<ndt_result>(d_res), st));
+  if (!mp) return NDT_OK;
+  LP_TRY(ndt_fit_points_multi_dev(ctx, rd.data(), (int)J, dev<int>(d_mapof), dev<float>(d_rep), dev<uint64_t>(d_roff), (int)B, K * NJ, 0,
+                                  &dev<ndt_result>(d_res)->T00, sizeof(ndt_result), mp->max_d2, nullptr, dev<ndt_fit_stats>(d_fit), st));
+  stats.h2d_bytes += J * sizeof(MapView);
+  return NDT_OK;
+}
+
+// (9) the decision, behind host wait 2: the slots' records, costs (ranged: statistics), best and found, the pose and the edge
+void LpSearch::decide() {
+  const ndt_result *res = back.at<ndt_result>(r_res);
+  const uint64_t *h_cand = back.at<uint64_t>(r_cand); const double *h_cs = back.at<double>(r_cs); const int *h_n = back.at<int>(r_ncand);
   for (size_t j = 0; j < J; ++j) {
-    ndt_loop &L = loop_of(j);
+    ndt_loop &L = *loop[j];
     if (L.status != NDT_OK) continue;
     L.n_cand = h_n[j];
-    bool ok = false;
     for (int c = 0; c < L.n_cand; ++c) {
       const ndt_result &r = res[j * K + (size_t)c];
       L.cand_index[c] = h_cand[j * K + (size_t)c]; L.cand_score[c] = h_cs[j * K + (size_t)c];
-      if (mp) mout[j].fit[c] = R.at<ndt_fit_stats>(hb, r_fit)[j * K + (size_t)c];
+      if (mp) multi[j]->fit[c] = back.at<ndt_fit_stats>(r_fit)[j * K + (size_t)c];
       else {
         L.cand_cost[c] = r.converged ? r.fitness : 1e7;      // (src/PoseEstimator.cpp:43-46, as relocalize_impl)
         if (L.best < 0 || L.cand_cost[c] < L.cand_cost[L.best]) L.best = c;
       }
       if (records_host) records_host[j * NDT_LOOP_MAX_CAND + (size_t)c] = r;
     }
-    if (mp) ok = loop_decide_ranged(*mp, res + j * K, &mout[j]);
+    const bool ranged_ok = mp && loop_decide_ranged(*mp, res + j * K, multi[j]);
     if (L.best < 0) continue;
-    if (!mp) ok = L.cand_cost[L.best] <= p.max_cost;
+    const bool ok = mp ? ranged_ok : L.cand_cost[L.best] <= p.max_cost;
     const ndt_result &w = res[j * K + (size_t)L.best];
     L.pose[0] = w.pose[0]; L.pose[1] = w.pose[1]; L.pose[2] = w.pose[2] * 180 / M_PI;      // RAD2DEG
-    const SsSession &Q = owner_of(j);
     // (a pose that is not finite leaves rel at 0: the cost rule keeps such a record from being found)
-    if (ndt_pg_edge_between(Q.traj.data() + 3 * (size_t)C[j].anchor_scan, L.pose, &L.edge) == NDT_OK) L.found = ok;
+    const double *anchor = s->ses[(size_t)owner[j]].traj.data() + 3 * (size_t)C[j].anchor_scan;
+    if (ndt_pg_edge_between(anchor, L.pose, &L.edge) == NDT_OK) L.found = ok;
   }
-  s->stats = stats;
+}
+
+int LpSearch::run() {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  LP_TRY(plan());
+  if (!N) return NDT_OK;
+  LP_TRY(scans());
+  LP_TRY(maps());
+  if (!first) return NDT_OK;
+  LP_TRY(match());
+  LP_TRY(back.wait(stats));
+  decide();
   return NDT_OK;
 }
 
-int loop_entry_checks(const ndt_sessions *s, const ndt_loop_params *p, const void *out, const int *n_out, const char *fn, uint64_t *P) {
-  const int rc = check_set(s, 0, false, fn);
-  if (rc) return rc;
-  const std::string f(fn);
-  if (!p || !out || !n_out) return fail(s->ctx, NDT_E_ARG, f + ": NULL params or outputs");
-  return loop_check_params(s->ctx, p, f, P);
+// The refusals of a set's loop calls behind check_set: the NULL arguments and the parameters -- p, or mp whose `loop` part p is
+// (the _multi and the cross calls); *P: the poses of every candidate's lattice.
+int loop_entry_checks(ndt_ctx *ctx, const std::string &f, const ndt_loop_params *p, const ndt_loop_multi_params *mp, const void *out,
+                      const int *n_out, uint64_t *P) {
+  if (!p || !out || !n_out) return fail(ctx, NDT_E_ARG, f + ": NULL params or outputs");
+  return mp ? loop_check_multi_params(ctx, mp, f, P) : loop_check_params(ctx, p, f, P);
 }
 
-// The refusals ndt_loop_multi_params adds to those of its `loop` part.
-int loop_check_multi_params(ndt_ctx *ctx, const ndt_loop_multi_params *p, const std::string &f, uint64_t *P) {
-  const int rc = loop_check_params(ctx, &p->loop, f, P);
-  if (rc) return rc;
-  if (p->max_submaps < 1 || p->max_submaps > NDT_LOOP_MAX_SUBMAPS)
-    return fail(ctx, NDT_E_ARG, f + ": max_submaps must be in 1 .. " + std::to_string(NDT_LOOP_MAX_SUBMAPS));
-  if (!(p->max_d2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_d2 is NaN or negative");
-  if (!(p->min_overlap >= 0.0 && p->min_overlap <= 1.0)) return fail(ctx, NDT_E_ARG, f + ": min_overlap is NaN or outside [0, 1]");
-  return NDT_OK;
-}
-
-int loop_multi_entry_checks(const ndt_sessions *s, const ndt_loop_multi_params *p, const void *out, const int *n_out, const char *fn,
-                            uint64_t *P) {
-  const int rc = check_set(s, 0, false, fn);
-  if (rc) return rc;
-  const std::string f(fn);
-  if (!p || !out || !n_out) return fail(s->ctx, NDT_E_ARG, f + ": NULL params or outputs");
-  return loop_check_multi_params(s->ctx, p, f, P);
-}
-
-// Both searches behind their parameters' refusals: the remaining refusals, the gating, the search; a HIP failure kills the set.
-int loop_search_entry(ndt_sessions *s, const unsigned char *which, const ndt_loop_params &p, uint64_t P, const char *fn, ndt_loop *out,
-                      const ndt_loop_multi_params *mp, ndt_loop_multi *mout, int *n_out, ndt_result *records_host) {
-  ndt_ctx *ctx = s->ctx;
-  const std::string f(fn);
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  std::vector<ndt_loop_candidate> C;
-  loop_gate(s, which, p, &C, mp ? mp->max_submaps : 1);
-  if (C.size() * P > (uint64_t)INT32_MAX)
-    return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
+// The candidates of a gate into the caller's array.
+template <typename T> int give_candidates(const std::vector<T> &C, T *out, int *n_out) {
+  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(T));
   *n_out = (int)C.size();
-  if (C.empty()) { s->stats = ndt_sessions_stats{}; return NDT_OK; }
-  const int rc = ss_find_loops(s, p, C, P, out, records_host, mp, mout);
-  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
-    s->dead = true;
-    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
-  }
-  return rc;
+  return NDT_OK;
+}
+
+// The candidates of a set's host gate (mp: up to max_submaps per session).
+int loop_candidates_entry(const ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, const ndt_loop_multi_params *mp,
+                          ndt_loop_candidate *out, int *n_out, const char *fn) {
+  uint64_t P = 0;
+  int rc = check_set(s, 0, false, fn);
+  if (rc || (rc = loop_entry_checks(s->ctx, fn, p, mp, out, n_out, &P))) return rc;
+  std::vector<ndt_loop_candidate> C;
+  loop_gate(s, which, *p, &C, mp ? mp->max_submaps : 1);
+  return give_candidates(C, out, n_out);
+}
+
+// Both searches (mp and mout: the ranged one): the bracket, the refusals, the gating, the search, the set's stats.
+int loop_search_entry(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, const ndt_loop_multi_params *mp, ndt_loop *out,
+                      ndt_loop_multi *mout, int *n_out, ndt_result *records_host, const char *fn) {
+  SetCall call{s, fn};
+  uint64_t P = 0;
+  int rc = call.enter();
+  if (rc || (rc = loop_entry_checks(call.ctx, call.f, p, mp, mp ? (const void *)mout : (const void *)out, n_out, &P))) return rc;
+  return call.run([&] {
+    std::vector<ndt_loop_candidate> C;
+    loop_gate(s, which, *p, &C, mp ? mp->max_submaps : 1);
+    if (C.size() * P > (uint64_t)INT32_MAX)
+      return call.refuse("more than 2^31 - 1 lattice poses over the " + std::to_string(C.size()) + " candidates");
+    *n_out = (int)C.size();
+    ndt_sessions_stats stats{};
+    LpSearch T{s, *p, C, P, records_host, stats};
+    if (mp) T.ranged(mp, mout, fn); else T.single(out);
+    const int found = C.empty() ? NDT_OK : T.run();
+    if (!found) s->stats = stats;
+    return found;
+  });
 }
 
 // The refusals of one trajectory's arrays (f: the function, and for the cross gate the track).
@@ -387,19 +422,21 @@ int loop_check_arrays(ndt_ctx *ctx, const std::string &f, const double *poses, s
   return NDT_OK;
 }
 
-// The gating of one trajectory behind the NULL checks (ndt_loop_gate; mp: ndt_loop_gate_multi, whose `loop` part p is): the
-// refusals of the arrays, then of the parameters, then the candidates (session 0).
+// The gating of one trajectory (ndt_loop_gate; mp: ndt_loop_gate_multi, whose `loop` part p is): the NULL checks, the refusals of
+// the arrays, then of the parameters, then the candidates (session 0) into out[0 .. *n_out).
 int loop_gate_arrays(const char *fn, const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor,
-                     const uint64_t *sub_offsets, int n_submaps, const ndt_loop_params &p, const ndt_loop_multi_params *mp,
-                     std::vector<ndt_loop_candidate> *C) {
+                     const uint64_t *sub_offsets, int n_submaps, const ndt_loop_params *p, const ndt_loop_multi_params *mp,
+                     ndt_loop_candidate *out, int *n_out) {
   const std::string f(fn);
+  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !n_out) return fail(nullptr, NDT_E_ARG, f + ": NULL pointer");
   int rc = loop_check_arrays(nullptr, f, poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps);
   if (rc) return rc;
   uint64_t P = 0;
-  rc = mp ? loop_check_multi_params(nullptr, mp, f, &P) : loop_check_params(nullptr, &p, f, &P);
+  rc = mp ? loop_check_multi_params(nullptr, mp, f, &P) : loop_check_params(nullptr, p, f, &P);
   if (rc) return rc;
-  loop_gate_k(poses, (int)n_scans, sub_first, sub_anchor, sub_offsets, n_submaps - 1, p, 0, mp ? mp->max_submaps : 1, C);
-  return NDT_OK;
+  std::vector<ndt_loop_candidate> C;
+  loop_gate_k(poses, (int)n_scans, sub_first, sub_anchor, sub_offsets, n_submaps - 1, *p, 0, mp ? mp->max_submaps : 1, &C);
+  return give_candidates(C, out, n_out);
 }
 
 #undef LP_TRY
@@ -426,65 +463,33 @@ int ndt_loop_multi_default_params(ndt_loop_multi_params *p) {
 }
 
 int ndt_loop_gate(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor, const uint64_t *sub_offsets,
-                  int n_submaps, const ndt_loop_params *p, ndt_loop_candidate *out, int *has) {
-  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !has) return fail(nullptr, NDT_E_ARG, "ndt_loop_gate: NULL pointer");
-  std::vector<ndt_loop_candidate> C;
-  const int rc = loop_gate_arrays("ndt_loop_gate", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, *p, nullptr, &C);
-  if (rc) return rc;
-  *has = C.empty() ? 0 : 1;
-  if (*has) *out = C[0];
-  return NDT_OK;
+                  int n_submaps, const ndt_loop_params *p, ndt_loop_candidate *out, int *has) {      // (*has: one candidate at the most)
+  return loop_gate_arrays("ndt_loop_gate", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, p, nullptr, out, has);
 }
 
 int ndt_loop_gate_multi(const double *poses, size_t n_scans, const int *sub_first, const int *sub_anchor, const uint64_t *sub_offsets,
                         int n_submaps, const ndt_loop_multi_params *p, ndt_loop_candidate *out, int *n_out) {
-  if (!poses || !sub_first || !sub_anchor || !sub_offsets || !p || !out || !n_out) return fail(nullptr, NDT_E_ARG, "ndt_loop_gate_multi: NULL pointer");
-  std::vector<ndt_loop_candidate> C;
-  const int rc = loop_gate_arrays("ndt_loop_gate_multi", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, p->loop, p, &C);
-  if (rc) return rc;
-  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(ndt_loop_candidate));
-  *n_out = (int)C.size();
-  return NDT_OK;
+  return loop_gate_arrays("ndt_loop_gate_multi", poses, n_scans, sub_first, sub_anchor, sub_offsets, n_submaps, p ? &p->loop : nullptr, p, out, n_out);
 }
 
 int ndt_sessions_loop_candidates_multi(const ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p,
                                        ndt_loop_candidate *out, int *n_out) {
-  uint64_t P = 0;
-  const int rc = loop_multi_entry_checks(s, p, out, n_out, "ndt_sessions_loop_candidates_multi", &P);
-  if (rc) return rc;
-  std::vector<ndt_loop_candidate> C;
-  loop_gate(s, which, p->loop, &C, p->max_submaps);
-  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(ndt_loop_candidate));
-  *n_out = (int)C.size();
-  return NDT_OK;
+  return loop_candidates_entry(s, which, p ? &p->loop : nullptr, p, out, n_out, "ndt_sessions_loop_candidates_multi");
 }
 
 int ndt_sessions_loop_candidates(const ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop_candidate *out,
                                  int *n_out) {
-  uint64_t P = 0;
-  const int rc = loop_entry_checks(s, p, out, n_out, "ndt_sessions_loop_candidates", &P);
-  if (rc) return rc;
-  std::vector<ndt_loop_candidate> C;
-  loop_gate(s, which, *p, &C);
-  if (!C.empty()) memcpy(out, C.data(), C.size() * sizeof(ndt_loop_candidate));
-  *n_out = (int)C.size();
-  return NDT_OK;
+  return loop_candidates_entry(s, which, p, nullptr, out, n_out, "ndt_sessions_loop_candidates");
 }
 
 int ndt_sessions_find_loops(ndt_sessions *s, const unsigned char *which, const ndt_loop_params *p, ndt_loop *out, int *n_out,
                             ndt_result *records_host) {
-  uint64_t P = 0;
-  const int rc = loop_entry_checks(s, p, out, n_out, "ndt_sessions_find_loops", &P);
-  if (rc) return rc;
-  return loop_search_entry(s, which, *p, P, "ndt_sessions_find_loops", out, nullptr, nullptr, n_out, records_host);
+  return loop_search_entry(s, which, p, nullptr, out, nullptr, n_out, records_host, "ndt_sessions_find_loops");
 }
 
 int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, const ndt_loop_multi_params *p, ndt_loop_multi *out,
                                   int *n_out, ndt_result *records_host) {
-  uint64_t P = 0;
-  const int rc = loop_multi_entry_checks(s, p, out, n_out, "ndt_sessions_find_loops_multi", &P);
-  if (rc) return rc;
-  return loop_search_entry(s, which, p->loop, P, "ndt_sessions_find_loops_multi", nullptr, p, out, n_out, records_host);
+  return loop_search_entry(s, which, p ? &p->loop : nullptr, p, nullptr, out, n_out, records_host, "ndt_sessions_find_loops_multi");
 }
 
 }  // extern "C"

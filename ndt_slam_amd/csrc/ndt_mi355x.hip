@@ -342,6 +342,9 @@ int fail(ndt_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
+// The refusal of a call `f` that would use the context while an ndt_map_rebuild_begin waits for its _end (the one sentence).
+int refuse_pending(ndt_ctx *ctx, const std::string &f) { return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context"); }
+
 // The call frame of every entry point that uses the context's scratch or queues one of its launches, opened behind the
 // entry point's refusals and early returns: open() makes the context's device current, picks the stream (the caller's, or the
 // context's for NULL) and opens the scratch bracket on it (ndt_ctx::ev_scratch) before the first use of the scratch; close()
@@ -2858,32 +2861,56 @@ int check_set(const ndt_sessions *s, int i, bool with_index, const char *fn) {
   return NDT_OK;
 }
 
+// a set without an archive, to a call that reads it (the one sentence)
+int refuse_no_archive(const ndt_sessions *s, const std::string &f) { return fail(s->ctx, NDT_E_ARG, f + ": the set has no scan archive (ndt_sessions_archive_enable)"); }
+
 // ... and those of the archive's read-outs: check_set's, then a set without an archive
 int check_archive(const ndt_sessions *s, int i, const char *fn) {
   const int rc = check_set(s, i, true, fn);
-  if (rc) return rc;
-  if (!s->archive) return fail(s->ctx, NDT_E_ARG, std::string(fn) + ": the set has no scan archive (ndt_sessions_archive_enable)");
+  return rc || s->archive ? rc : refuse_no_archive(s, fn);
+}
+
+// The bracket of every call that changes or searches a set, in CallFrame's manner: enter() holds check_set's refusals; the call's
+// own refusals follow in the call's own order (refuse(): one under the call's name); run() refuses while an ndt_map_rebuild_begin
+// is open on the context, runs the body and, on NDT_E_HIP / NDT_E_NOMEM, marks the set dead and drains the stream (the context
+// stays usable: nothing of the set is in flight).  kills = false, ndt_sessions_occ_integrate and ndt_sessions_occ_rebuild: their
+// scratch is the context's, taken through CallFrame, and they write grids, nothing of the set: it stays as usable as it was.
+struct SetCall {
+  ndt_sessions *s; const char *fn; bool kills = true;
+  ndt_ctx *ctx = nullptr; std::string f;
+  int enter() { const int rc = check_set(s, 0, false, fn); if (!rc) { ctx = s->ctx; f = fn; } return rc; }
+  int refuse(const std::string &what) const { return fail(ctx, NDT_E_ARG, f + ": " + what); }
+  template <typename Body> int run(Body &&body) {
+    if (ctx->pending_map) return refuse_pending(ctx, f);
+    const int rc = body();
+    if (kills && (rc == NDT_E_HIP || rc == NDT_E_NOMEM)) { s->dead = true; hipError_t e = hipStreamSynchronize(ctx->stream); (void)e; }
+    return rc;
+  }
+};
+
+// Entry c of a named-session list: out of range, not started, named twice (entry_of: S entries, -1 before the first); *who: the
+// entry's name, for the caller's own refusals of it.
+int check_named(const SetCall &call, const int *which, int c, std::vector<int> &entry_of, std::string *who) {
+  const int i = which[c];
+  *who = "entry " + std::to_string(c) + ": session " + std::to_string(i);
+  if (i < 0 || i >= call.s->S) return call.refuse(*who + " out of range");
+  if (!call.s->ses[(size_t)i].started) return call.refuse(*who + " has not started");
+  if (entry_of[(size_t)i] >= 0) return call.refuse(*who + " is entry " + std::to_string(entry_of[(size_t)i]) + " again");
+  entry_of[(size_t)i] = c;
   return NDT_OK;
 }
 
 int step_entry(ndt_sessions *s, const double *raw_host, const double *raw_dev, size_t stride, const uint64_t *raw_offsets,
                const double *odo_host, const double *odo_dev, const unsigned char *active, ndt_session_step *out, const char *fn) {
-  int rc = check_set(s, 0, false, fn);
+  SetCall call{s, fn};
+  const int rc = call.enter();
   if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  const std::string f(fn);
-  if (!raw_offsets || !out || (!odo_host && !odo_dev)) return fail(ctx, NDT_E_ARG, f + ": NULL array (raw_offsets, odo or out)");
-  if (stride < 16 || (stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad stride (need stride_bytes >= 16 and % 8 == 0)");
+  if (!raw_offsets || !out || (!odo_host && !odo_dev)) return call.refuse("NULL array (raw_offsets, odo or out)");
+  if (stride < 16 || (stride & 7)) return call.refuse("bad stride (need stride_bytes >= 16 and % 8 == 0)");
   for (int i = 0; i < s->S; ++i)
-    if (raw_offsets[i + 1] < raw_offsets[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": offsets decrease");
-  if (raw_offsets[s->S] > raw_offsets[0] && !raw_host && !raw_dev) return fail(ctx, NDT_E_ARG, f + ": NULL array (raw_xy)");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  rc = ss_step(s, raw_host, raw_dev, stride, raw_offsets, odo_host, odo_dev, active, out);
-  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
-    s->dead = true;
-    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;      // (the context stays usable: nothing of the set is in flight)
-  }
-  return rc;
+    if (raw_offsets[i + 1] < raw_offsets[i]) return call.refuse("session " + std::to_string(i) + ": offsets decrease");
+  if (raw_offsets[s->S] > raw_offsets[0] && !raw_host && !raw_dev) return call.refuse("NULL array (raw_xy)");
+  return call.run([&] { return SsStep{s, raw_host, raw_dev, stride, raw_offsets, odo_host, odo_dev, active, out}.run(); });
 }
 
 }  // namespace
@@ -2909,7 +2936,7 @@ int ndt_sessions_create(ndt_ctx *ctx, int n_sessions, const ndt_session_params *
   if (!prm || !out) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: NULL argument (prm or out)");
   int rc = ss_check_params(ctx, *prm);
   if (rc) return rc;
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, "ndt_sessions_create");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ndt_sessions *s = new (std::nothrow) ndt_sessions;
   if (!s) return fail(ctx, NDT_E_NOMEM, "ndt_sessions_create: out of memory");
@@ -2940,10 +2967,11 @@ int ndt_sessions_destroy(ndt_sessions *s) {
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)e;
-  for (auto &Q : s->ses)
-    for (ndt_map **m : {&Q.map, &Q.loop_map, &Q.loop_map_more[0], &Q.loop_map_more[1], &Q.loop_map_more[2]})
-      if (*m) { ndt_map_destroy(*m); *m = nullptr; }
-  static_assert(NDT_LOOP_MAX_SUBMAPS == 4, "every loop map of a session is destroyed above");
+  for (auto &Q : s->ses) {
+    if (Q.map) ndt_map_destroy(Q.map);
+    for (ndt_map *m : Q.loop_maps)
+      if (m) ndt_map_destroy(m);
+  }
   delete s;
   return NDT_OK;
 }
@@ -3033,35 +3061,23 @@ int ndt_sessions_trajectory(const ndt_sessions *s, int i, double *poses_host, si
 
 int ndt_sessions_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses_host, const size_t *n_poses,
                          int *status_host) {
-  int rc = check_set(s, 0, false, "ndt_sessions_correct");
+  SetCall call{s, "ndt_sessions_correct"};
+  int rc = call.enter();
   if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  const std::string f("ndt_sessions_correct");
-  if (!which || !new_poses_host || !n_poses || !status_host) return fail(ctx, NDT_E_ARG, f + ": NULL array (which, new_poses, n_poses or status)");
-  if (n_corr < 1) return fail(ctx, NDT_E_ARG, f + ": n_corr < 1");
+  if (!which || !new_poses_host || !n_poses || !status_host) return call.refuse("NULL array (which, new_poses, n_poses or status)");
+  if (n_corr < 1) return call.refuse("n_corr < 1");
   std::vector<int> entry_of((size_t)s->S, -1);
+  std::string who;
   for (int c = 0; c < n_corr; ++c) {
-    const int i = which[c];
-    const std::string who = f + ": entry " + std::to_string(c) + ": session " + std::to_string(i);
-    if (i < 0 || i >= s->S) return fail(ctx, NDT_E_ARG, who + " out of range");
-    const SsSession &Q = s->ses[(size_t)i];
-    if (!Q.started) return fail(ctx, NDT_E_ARG, who + " has not started");
-    if (entry_of[(size_t)i] >= 0) return fail(ctx, NDT_E_ARG, who + " is entry " + std::to_string(entry_of[(size_t)i]) + " again");
-    entry_of[(size_t)i] = c;
-    if (!new_poses_host[c]) return fail(ctx, NDT_E_ARG, who + ": NULL trajectory");
-    if (n_poses[c] != (size_t)Q.n_poses)
-      return fail(ctx, NDT_E_ARG, who + ": " + std::to_string(n_poses[c]) + " poses for a trajectory of " + std::to_string(Q.n_poses) +
-                                      " scans (a stale trajectory)");
+    if ((rc = check_named(call, which, c, entry_of, &who))) return rc;
+    const int have = s->ses[(size_t)which[c]].n_poses;
+    if (!new_poses_host[c]) return call.refuse(who + ": NULL trajectory");
+    if (n_poses[c] != (size_t)have)
+      return call.refuse(who + ": " + std::to_string(n_poses[c]) + " poses for a trajectory of " + std::to_string(have) + " scans (a stale trajectory)");
     for (size_t k = 0; k < 3 * n_poses[c]; ++k)
-      if (!(std::fabs(new_poses_host[c][k]) <= DBL_MAX)) return fail(ctx, NDT_E_ARG, who + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
+      if (!(std::fabs(new_poses_host[c][k]) <= DBL_MAX)) return call.refuse(who + ": scan " + std::to_string(k / 3) + ": a pose is not finite");
   }
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  rc = ss_correct(s, which, n_corr, new_poses_host, status_host);
-  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
-    s->dead = true;
-    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
-  }
-  return rc;
+  return call.run([&] { return SsCorrect{s, which, n_corr, new_poses_host, status_host}.run(); });
 }
 
 // ---- the scan archive (filled by SsStep::book, read by ndt_sessions_occ_rebuild) ----
@@ -3120,29 +3136,17 @@ int ndt_sessions_archive_view(const ndt_sessions *s, int i, const double **xy_de
 }
 
 int ndt_sessions_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status_host) {
-  int rc = check_set(s, 0, false, "ndt_sessions_remake_closed");
+  SetCall call{s, "ndt_sessions_remake_closed"};
+  int rc = call.enter();
   if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  const std::string f("ndt_sessions_remake_closed");
-  if (!which || !status_host) return fail(ctx, NDT_E_ARG, f + ": NULL array (which or status)");
-  if (n_named < 1) return fail(ctx, NDT_E_ARG, f + ": n_named < 1");
+  if (!which || !status_host) return call.refuse("NULL array (which or status)");
+  if (n_named < 1) return call.refuse("n_named < 1");
   std::vector<int> entry_of((size_t)s->S, -1);
-  for (int c = 0; c < n_named; ++c) {
-    const int i = which[c];
-    const std::string who = f + ": entry " + std::to_string(c) + ": session " + std::to_string(i);
-    if (i < 0 || i >= s->S) return fail(ctx, NDT_E_ARG, who + " out of range");
-    if (!s->ses[(size_t)i].started) return fail(ctx, NDT_E_ARG, who + " has not started");
-    if (entry_of[(size_t)i] >= 0) return fail(ctx, NDT_E_ARG, who + " is entry " + std::to_string(entry_of[(size_t)i]) + " again");
-    entry_of[(size_t)i] = c;
-  }
-  if (!s->archive) return fail(ctx, NDT_E_ARG, f + ": the set has no scan archive (ndt_sessions_archive_enable)");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  rc = ss_remake_closed(s, which, n_named, status_host);
-  if (rc == NDT_E_HIP || rc == NDT_E_NOMEM) {
-    s->dead = true;
-    hipError_t e = hipStreamSynchronize(ctx->stream); (void)e;
-  }
-  return rc;
+  std::string who;
+  for (int c = 0; c < n_named; ++c)
+    if ((rc = check_named(call, which, c, entry_of, &who))) return rc;
+  if (!s->archive) return refuse_no_archive(s, call.f);
+  return call.run([&] { return SsRemakeCall{s, which, n_named, status_host}.run(); });
 }
 
 }  // extern "C"
@@ -3174,7 +3178,7 @@ int score_check(ndt_ctx *ctx, const ndt_map *map, const void *scan, size_t n, si
   if (map->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the map was built on another device");
   if (n == 0 || n > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, f + ": need 1 <= n <= 2^31 - 1 scan points");
   if (stride < 8 || (stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad stride (need stride_bytes >= 8 and % 8 == 0)");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return NDT_OK;
 }
 
@@ -3371,7 +3375,7 @@ int ndt_lattice_select_dev(ndt_ctx *ctx, const ndt_pose_lattice *lattice, const 
   if (!lattice_count(lattice, &P))
     return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: bad lattice (NULL, a dimension below 1, a non-finite origin or step, or more than 2^31 - 1 poses)");
   if (top_k < 1 || top_k > 1024) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: top_k must be in 1 .. 1024");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_lattice_select_dev: an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, "ndt_lattice_select_dev");
   return CallFrame::run(ctx, stream, [&](hipStream_t st) {
     return queue_select(ctx, st, lattice_of(*lattice), P, score_dev, pairs_dev, top_k, local_max, (unsigned long long *)cand_index_dev, n_cand_dev);
   });
@@ -3407,7 +3411,7 @@ int fit_points_check(ndt_ctx *ctx, const ndt_map *map, const void *scans, const 
   if (map->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the map was built on another device");
   if (tf_stride < 16 || (tf_stride & 3)) return fail(ctx, NDT_E_ARG, f + ": bad tf_stride_bytes (need >= 16 and % 4 == 0)");
   if (!(max_d2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_d2 is NaN or negative");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return NDT_OK;
 }
 
@@ -3682,7 +3686,7 @@ int occ_integrate_check(ndt_ctx *ctx, ndt_occ *const *occs, int n_occ, const voi
   }
   if (origin_stride < 16 || (origin_stride & 7)) return fail(ctx, NDT_E_ARG, f + ": bad origin_stride_bytes (need >= 16 and % 8 == 0)");
   if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return NDT_OK;
 }
 
@@ -3692,7 +3696,7 @@ int occ_one_check(ndt_ctx *ctx, const ndt_occ *occ, const char *fn) {
   const std::string f(fn);
   if (!occ) return fail(ctx, NDT_E_ARG, f + ": NULL grid");
   if (occ->ctx != ctx || occ->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": the grid belongs to another context");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return NDT_OK;
 }
 
@@ -3726,7 +3730,7 @@ int ndt_occ_create(ndt_ctx *ctx, const ndt_occ_geometry *g, ndt_occ **out) {
   if (!out) return fail(ctx, NDT_E_ARG, "ndt_occ_create: NULL out");
   int rc = occ_geometry_check(ctx, g, "ndt_occ_create");
   if (rc) return rc;
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, "ndt_occ_create: an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, "ndt_occ_create");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ndt_occ *o = new (std::nothrow) ndt_occ;
   if (!o) return fail(ctx, NDT_E_NOMEM, "ndt_occ_create: out of memory");
@@ -3862,57 +3866,59 @@ int ndt_occ_counts(ndt_ctx *ctx, ndt_occ *occ, uint32_t *hit_host, uint32_t *pas
   return NDT_OK;
 }
 
-int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, double max_range2,
-                               ndt_occ_stats *stats_host) {
-  int rc = check_set(s, 0, false, "ndt_sessions_occ_integrate");
-  if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  const std::string f("ndt_sessions_occ_integrate");
-  if (!occs) return fail(ctx, NDT_E_ARG, f + ": NULL occs");
-  if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  // who is taken: the newest scan is the last range of scan_off in store[cur]
-  const int S = s->S;
-  std::vector<ndt_occ *> taken((size_t)S, nullptr);
-  std::vector<OccRow> own((size_t)S);
-  std::set<const ndt_occ *> seen;
-  size_t total = 0;
-  for (int i = 0; i < S; ++i) {
-    const SsSession &Q = s->ses[(size_t)i];
-    if ((which && !which[i]) || !Q.started || Q.scan_off.size() < 2) continue;
-    if (!occs[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": NULL grid");
-    if (occs[i]->ctx != ctx || occs[i]->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": the grid belongs to another context");
-    if (!seen.insert(occs[i]).second) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": its grid is given twice");
-    const size_t k = Q.scan_off.size() - 2;
-    taken[(size_t)i] = occs[i];
-    own[(size_t)i].pts = Q.store[Q.cur].p + Q.scan_off[k];
-    own[(size_t)i].n = Q.scan_off[k + 1] - Q.scan_off[k];
-    total += (size_t)own[(size_t)i].n;
-  }
-  CallFrame fr(ctx);
-  if ((rc = fr.open())) return rc;
-  hipStream_t st = fr.st;
-  if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
-  ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
-  if ((rc = queue_occ(ctx, st, OccCall{taken.data(), S, own.data(), nullptr, nullptr, nullptr, S, total, s->last_pose.p, 24, max_range2, d_stats})))
-    return rc;
-  if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
-  if ((rc = fr.close())) return rc;
-  if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
+// Session i's grid, to a call that takes it: NULL, another context's, given twice (seen: the grids taken so far).
+static int check_grid(const SetCall &call, ndt_occ *const *occs, int i, std::set<const ndt_occ *> &seen) {
+  const std::string who = "session " + std::to_string(i);
+  if (!occs[i]) return call.refuse(who + ": NULL grid");
+  if (occs[i]->ctx != call.ctx || occs[i]->device != call.ctx->device) return call.refuse(who + ": the grid belongs to another context");
+  if (!seen.insert(occs[i]).second) return call.refuse(who + ": its grid is given twice");
   return NDT_OK;
 }
 
-int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
-                             ndt_occ_stats *stats_host) {
-  int rc = check_set(s, 0, false, "ndt_sessions_occ_rebuild");
+int ndt_sessions_occ_integrate(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, double max_range2,
+                               ndt_occ_stats *stats_host) {
+  SetCall call{s, "ndt_sessions_occ_integrate", false};
+  int rc = call.enter();
   if (rc) return rc;
-  ndt_ctx *ctx = s->ctx;
-  const std::string f("ndt_sessions_occ_rebuild");
-  if (!occs) return fail(ctx, NDT_E_ARG, f + ": NULL occs");
-  if (!(max_range2 >= 0.0)) return fail(ctx, NDT_E_ARG, f + ": max_range2 is NaN or negative");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
-  if (!s->archive) return fail(ctx, NDT_E_ARG, f + ": the set has no scan archive (ndt_sessions_archive_enable)");
-  // who is taken; the call's scans are the taken sessions' archives one behind the other
+  ndt_ctx *ctx = call.ctx;
+  if (!occs) return call.refuse("NULL occs");
+  if (!(max_range2 >= 0.0)) return call.refuse("max_range2 is NaN or negative");
+  return call.run([&]() -> int {      // who is taken: the newest scan is the last range of scan_off in store[cur]
+    const int S = s->S;
+    std::vector<ndt_occ *> taken((size_t)S, nullptr);
+    std::vector<OccRow> own((size_t)S);
+    std::set<const ndt_occ *> seen;
+    size_t total = 0;
+    for (int i = 0; i < S; ++i) {
+      const SsSession &Q = s->ses[(size_t)i];
+      if ((which && !which[i]) || !Q.started || Q.scan_off.size() < 2) continue;
+      if ((rc = check_grid(call, occs, i, seen))) return rc;
+      const size_t k = Q.scan_off.size() - 2;
+      taken[(size_t)i] = occs[i];
+      own[(size_t)i].pts = Q.store[Q.cur].p + Q.scan_off[k];
+      own[(size_t)i].n = Q.scan_off[k + 1] - Q.scan_off[k];
+      total += (size_t)own[(size_t)i].n;
+    }
+    CallFrame fr(ctx);
+    if ((rc = fr.open())) return rc;
+    hipStream_t st = fr.st;
+    if (stats_host && (rc = ctx->d_tmp.ensure(ctx, sizeof(ndt_occ_stats)))) return rc;
+    ndt_occ_stats *d_stats = stats_host ? (ndt_occ_stats *)ctx->d_tmp.p : nullptr;
+    if ((rc = queue_occ(ctx, st, OccCall{taken.data(), S, own.data(), nullptr, nullptr, nullptr, S, total, s->last_pose.p, 24, max_range2, d_stats})))
+      return rc;
+    if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
+    if ((rc = fr.close())) return rc;
+    if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
+    return NDT_OK;
+  });
+}
+
+// ndt_sessions_occ_rebuild behind its bracket.  Who is taken; the call's scans are the taken sessions' archives one behind the other.
+static int ss_occ_rebuild(const SetCall &call, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
+                          ndt_occ_stats *stats_host) {
+  ndt_sessions *s = call.s; ndt_ctx *ctx = call.ctx;
+  if (!s->archive) return refuse_no_archive(s, call.f);
+  int rc = NDT_OK;
   const int S = s->S;
   std::vector<ndt_occ *> taken((size_t)S, nullptr);
   std::vector<int> rows;
@@ -3921,14 +3927,12 @@ int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsign
   for (int i = 0; i < S; ++i) {
     const SsSession &Q = s->ses[(size_t)i];
     if ((which && !which[i]) || !Q.started) continue;
-    if (!occs[i]) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": NULL grid");
-    if (occs[i]->ctx != ctx || occs[i]->device != ctx->device) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": the grid belongs to another context");
-    if (!seen.insert(occs[i]).second) return fail(ctx, NDT_E_ARG, f + ": session " + std::to_string(i) + ": its grid is given twice");
+    if ((rc = check_grid(call, occs, i, seen))) return rc;
     taken[(size_t)i] = occs[i]; rows.push_back(i);
     n_scans += Q.arch_off.size() - 1;
     for (size_t k = 0; k + 1 < Q.arch_off.size(); ++k) n_runs += (Q.arch_off[k + 1] - Q.arch_off[k] + (uint64_t)kOccRun - 1) / (uint64_t)kOccRun;
     if (n_scans > (uint64_t)INT32_MAX || n_runs > (uint64_t)INT32_MAX)
-      return fail(ctx, NDT_E_ARG, f + ": more than 2^31 - 1 scans or runs of 256 beams over the sessions taken");
+      return call.refuse("more than 2^31 - 1 scans or runs of 256 beams over the sessions taken");
   }
   if (rows.empty()) {
     if (stats_host) memset(stats_host, 0, sizeof(*stats_host));
@@ -3980,12 +3984,22 @@ int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsign
   occ_rebuild_kernel<<<dim3((unsigned)wgs), dim3(kOccRun), 0, st>>>(tab, scans, cs, max_range2, jobs, (unsigned)n_runs, (unsigned long long)stride, d_stats);
   const hipError_t e = hipGetLastError();
   rc = occ_wrote(ctx, taken.data(), S, st);      // (queued or not: the grids count as written behind this point of st)
-  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, f + ": " + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(ctx, NDT_E_HIP, call.f + ": " + hipGetErrorString(e));
   if (rc) return rc;
   if (stats_host) HIP_TRY(ctx, hipMemcpyAsync(stats_host, d_stats, sizeof(ndt_occ_stats), hipMemcpyDeviceToHost, st));
   if ((rc = fr.close())) return rc;
   if (stats_host) HIP_TRY(ctx, hipStreamSynchronize(st));
   return NDT_OK;
+}
+
+int ndt_sessions_occ_rebuild(ndt_sessions *s, ndt_occ *const *occs, const unsigned char *which, int clear, double max_range2,
+                             ndt_occ_stats *stats_host) {
+  SetCall call{s, "ndt_sessions_occ_rebuild", false};
+  const int rc = call.enter();
+  if (rc) return rc;
+  if (!occs) return call.refuse("NULL occs");
+  if (!(max_range2 >= 0.0)) return call.refuse("max_range2 is NaN or negative");
+  return call.run([&] { return ss_occ_rebuild(call, occs, which, clear, max_range2, stats_host); });
 }
 
 }  // extern "C"
@@ -4012,7 +4026,7 @@ int pg_check(ndt_ctx *ctx, const void *poses, const uint64_t *node_off, const vo
   if (prm->max_iter < 1 || prm->max_iter > 10000 || !(prm->eps_step >= 0.0) || !(prm->eps_step <= DBL_MAX) || prm->cg_max_iter < 0 ||
       prm->cg_max_iter > (1 << 30) || !(prm->cg_rtol > 0.0) || !(prm->cg_rtol < 1.0) || prm->max_halvings < 0 || prm->max_halvings > 60)
     return fail(ctx, NDT_E_ARG, f + ": parameters out of range");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return NDT_OK;
 }
 
@@ -4254,7 +4268,7 @@ int score_multi(ndt_ctx *ctx, const ndt_map *const *maps, int n_maps, const floa
   if (rc) return rc;
   MultiMaps mm;
   if ((rc = check_multi(ctx, maps, n_maps, true, 0, f.c_str(), &mm))) return rc;
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return CallFrame::run(ctx, stream, [&](hipStream_t st) {
     // the table: a row per job (the map's view as it is now), then the prefix of tiles; staged in pinned memory, one copy
     Regions R;
@@ -4325,7 +4339,7 @@ int ndt_lattice_select_multi_dev(ndt_ctx *ctx, const ndt_score_job *jobs, int n_
   int rc = check_score_jobs(ctx, f, jobs, n_jobs, -1, -1, vol_offsets_host, (uint64_t)kPickMaxPoses, &P);
   if (rc) return rc;
   if (top_k < 1 || top_k > kPickMaxK) return fail(ctx, NDT_E_ARG, f + ": top_k must be in 1 .. 16");
-  if (ctx->pending_map) return fail(ctx, NDT_E_ARG, f + ": an ndt_map_rebuild_begin is open on the context");
+  if (ctx->pending_map) return refuse_pending(ctx, f);
   return CallFrame::run(ctx, stream, [&](hipStream_t st) {
     const size_t bytes = (size_t)n_jobs * sizeof(PickJob);
     int rc2;

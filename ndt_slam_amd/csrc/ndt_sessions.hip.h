@@ -317,8 +317,9 @@ struct SsSession {
   // double2 -- one behind the other; scan k of it belongs to pose k of traj.  Never moved by a correction.
   DevBuf<double2> arch;
   std::vector<uint64_t> arch_off{0};        // n_poses + 1 entries
-  ndt_map *loop_map = nullptr;              // ndt_sessions_find_loops: the map of the session's candidate submap, rebuilt by every search
-  ndt_map *loop_map_more[NDT_LOOP_MAX_SUBMAPS - 1] = {};      // ndt_sessions_find_loops_multi: those of its candidates of rank 1 and up
+  // the loop searches (ndt_loops.hip.h): the map of the session's candidate of rank r, rebuilt by every search (rank 0: the one
+  // ndt_sessions_find_loops keeps)
+  ndt_map *loop_maps[NDT_LOOP_MAX_SUBMAPS] = {};
   bool started = false;
 };
 
@@ -380,6 +381,29 @@ int ss_grow(ndt_ctx *ctx, DevBuf<T> &b, size_t need, size_t keep) {
   return NDT_OK;
 }
 
+// One read-back into the set's h_back and its host wait: add() registers n elements at a device address (the array's number),
+// wait() lays the registered arrays out, queues their copies, waits and counts the wait and the bytes it copied; at(k) is array
+// k's host copy, good until the set's next read-back.
+struct SsBack {
+  ndt_sessions *s;
+  struct Part { const void *src; size_t bytes, off; };
+  std::vector<Part> parts; Regions R;
+  template <typename T> size_t add(const T *src, size_t n) { parts.push_back(Part{src, n * sizeof(T), R.take(n * sizeof(T))}); return parts.size() - 1; }
+  template <typename T> const T *at(size_t k) const { return (const T *)(s->h_back.p + parts[k].off); }
+  int reserve() { return s->h_back.ensure(s->ctx, R.end); }
+  int wait(ndt_sessions_stats &stats) {
+    ndt_ctx *ctx = s->ctx;
+    SS_TRY(reserve());
+    for (const Part &p : parts) {
+      HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + p.off, p.src, p.bytes, hipMemcpyDeviceToHost, ctx->stream));
+      stats.d2h_bytes += p.bytes;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    stats.host_waits++;
+    return NDT_OK;
+  }
+};
+
 int ss_check_params(ndt_ctx *ctx, const ndt_session_params &p) {
   size_t cap = 0;
   if (!(p.leaf > 0)) return fail(ctx, NDT_E_ARG, "ndt_sessions_create: leaf <= 0");
@@ -395,23 +419,114 @@ int ss_check_params(ndt_ctx *ctx, const ndt_session_params &p) {
 
 unsigned ss_gx(size_t total, int B) { return (unsigned)std::min<size_t>(64, (total / (size_t)std::max(B, 1) + 255) / 256 + 1); }
 
+// ---- what the end of a step, of a correction and of a remake share: the commit ----
+
+// The commit of a call that fills the arenas `cur` and counts in `stats`: who is named (the sessions the call computes; everybody
+// else keeps its views across the call -- a step it did not take part in, a correction that does not name it -- and is carried),
+// the call's own moves that ride in the carried ranges' table, which new local maps want an NDT map, and the tail.  The call itself
+// states the named sessions' new views.
+struct SsCommit {
+  ndt_sessions *s; const int cur = s->cur ^ 1; ndt_sessions_stats stats{};
+  std::vector<unsigned char> named = std::vector<unsigned char>((size_t)s->S, 0);
+  std::vector<SsCopy> moves;
+  std::vector<const float *> bxy; std::vector<size_t> bn, bentry; std::vector<int> bwho;
+  // the points everybody else carries into this call's arenas: part of the arenas' sizes
+  void carried(size_t *cloud, size_t *target) const {
+    for (int i = 0; i < s->S; ++i) {
+      const SsSession &Q = s->ses[(size_t)i];
+      if (!named[(size_t)i] && Q.has_target && Q.buf != cur) { *cloud += Q.c_n; *target += Q.t_n; }
+    }
+  }
+  // Named session i behind the call's wait, range `entry` of the read-back offsets: its views and its wish for a map, or (ok
+  // false: a triple of its cloud spans more than 2^30 voxels) no cloud and no local map; the map stays as it is.
+  void view(int i, size_t entry, bool ok, const uint64_t *coff, const uint64_t *toff, uint64_t n_prev) {
+    SsSession &Q = s->ses[(size_t)i];
+    Q.buf = cur; Q.has_target = ok; Q.c_n = Q.t_n = Q.n_prev = 0;
+    if (!ok) return;
+    Q.c_off = coff[entry]; Q.c_n = coff[entry + 1] - coff[entry];
+    Q.t_off = toff[entry]; Q.t_n = toff[entry + 1] - toff[entry];
+    Q.n_prev = n_prev;
+    wants_map(i, entry);
+  }
+  // session i's new local map (its view is set) wants an NDT map; a refused build's code goes to the caller's status `entry`
+  void wants_map(int i, size_t entry) {
+    const SsSession &Q = s->ses[(size_t)i];
+    if (!Q.t_n) return;
+    bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(i); bentry.push_back(entry);
+  }
+  // The tail.  (1) Everybody else's ranges move behind the call's own, which end at (c_end, t_end): with the call's moves table C, the
+  // same size at every call (two carried ranges per session at most), and the copies; `cur` is the set's from here.  (2) The NDT maps
+  // of the new local maps, rebuilt in place in one batched build; a host wait: the bounding boxes (without a map to build, the stream).
+  // A build refused for one session (NDT_E_GRID: its local map spans more than 2^28 cells) costs that session alone: status(entry) takes
+  // the build's code, its map stays exactly as it was (none stays none), every other map is built all the same.  (3) The set's stats.
+  template <typename Status> int finish(uint64_t c_end, uint64_t t_end, Status &&status) {
+    ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
+    for (int i = 0; i < s->S; ++i) {
+      SsSession &Q = s->ses[(size_t)i];
+      if (named[(size_t)i] || !Q.has_target || Q.buf == cur) continue;
+      if (Q.c_n) moves.push_back(SsCopy{s->cloud[Q.buf].p + Q.c_off, s->cloud[cur].p + c_end, Q.c_n});
+      if (Q.t_n) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off, s->target[cur].p + t_end, Q.t_n});
+      Q.c_off = c_end; c_end += Q.c_n; Q.t_off = t_end; t_end += Q.t_n; Q.buf = cur;
+    }
+    const size_t c_bytes = 2 * (size_t)s->S * sizeof(SsCopy), nb = bwho.size();
+    SS_TRY(s->tab_c.reserve(ctx, c_bytes)); SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
+    memset(s->tab_c.h.p, 0, c_bytes);
+    if (!moves.empty()) memcpy(s->tab_c.h.p, moves.data(), moves.size() * sizeof(SsCopy));
+    HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
+    stats.h2d_bytes += c_bytes;
+    if (!moves.empty())
+      seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(moves.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)moves.size());
+    HIP_TRY(ctx, hipGetLastError());
+    s->cur = cur;
+    if (nb) {
+      std::vector<ndt_params> bp(nb, s->prm.match);
+      std::vector<ndt_map *> maps;
+      std::vector<int> code(nb, NDT_OK);
+      for (int i : bwho) maps.push_back(s->ses[(size_t)i].map);
+      SS_TRY(check_build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)nb, bp.data(), maps.data(), "ndt_map_build_batch_dev"));
+      SS_TRY(build_batch(ctx, bxy.data(), bn.data(), sizeof(float2), (int)nb, bp.data(), maps.data(), "ndt_map_build_batch_dev", code.data()));
+      for (size_t k = 0; k < nb; ++k)
+        if (code[k] == NDT_OK) s->ses[(size_t)bwho[k]].map = maps[k]; else status(bentry[k]) = code[k];
+    } else {
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    stats.host_waits++; stats.d2h_bytes += nb * 16 * sizeof(unsigned);
+    s->stats = stats;
+    return NDT_OK;
+  }
+};
+
+// queue_local_map_batch over `subs` on the set's stream, in a call frame of its own (the assembly's and the filter's scratch are
+// the context's); its upload and its triples go to the stats.
+int ss_local_maps(ndt_sessions *s, const std::vector<ndt_submap_desc> &subs, float2 *cloud, DevBuf<uint64_t> &cloud_off, float2 *target,
+                  DevBuf<uint64_t> &target_off, DevBuf<int> &status, ndt_sessions_stats &stats) {
+  ndt_ctx *ctx = s->ctx;
+  size_t up = 0, nt = 0;
+  CallFrame fr(ctx);
+  SS_TRY(fr.open(ctx->stream));
+  SS_TRY(queue_local_map_batch(ctx, ctx->stream, subs.data(), (int)subs.size(), sizeof(float2), s->prm.leaf, (float *)cloud, cloud_off.p,
+                               (float *)target, target_off.p, status.p, &up, &nt));
+  SS_TRY(fr.close());
+  stats.h2d_bytes += up; stats.triples_run = (int)nt;
+  return NDT_OK;
+}
+
 // What passes between the parts of one step (DESIGN.md 4.10's list), in the order the parts fill it.
 struct SsStep {
   // the call; raw_dev / odo_dev: the device form (then raw_host / odo_host are NULL)
   ndt_sessions *s; const double *raw_host, *raw_dev; size_t stride; const uint64_t *raw_offsets; const double *odo_host, *odo_dev;
   const unsigned char *active; ndt_session_step *out;
   ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
-  ndt_sessions_stats stats{};
+  SsCommit commit{s}; ndt_sessions_stats &stats = commit.stats; const int cur = commit.cur;      // (named: who stepped; cur: this step's arenas)
   std::vector<int> mode, map_of; std::vector<const ndt_map *> maps;      // who steps
   std::vector<uint64_t> rs_off;                    // the front part: the resampled scans' offsets
   // the bookkeeping: table B's contents, the newest triples (unit_room: their units) and the submaps of one triple each
-  int cur = 0;                                     // this step's arenas; the last step's are s->cur
   std::vector<SsCopy> moves;                       // carried-over scans and closed clouds, the scan's copy into the archive
   std::vector<float2 *> dst; std::vector<SsPlan> plan; std::vector<PfPrev> prevs;
   MmPlan tri; std::vector<MmSub> subs; float cut = 0.f;      // (cut: rn_cutoff of the set's thre_neighbor)
   size_t cap_cloud = 0, total_prev = 0, carry_cloud = 0, carry_target = 0;
-  size_t b_toff = 0, b_coff = 0, b_plen = 0, b_stat = 0;      // the part behind it: where wait 2's read-back lies in h_back
-  bool who_steps(); int front(); int bookkeeping(); int behind(); int close();      // the parts, in this order
+  SsBack back{s}; size_t b_toff = 0, b_coff = 0, b_plen = 0, b_stat = 0;      // the part behind it: wait 2's read-back
+  bool who_steps(); int front(); int bookkeeping(); int behind(); int close(); int run();      // the parts, in this order, and the step
   int book(int i, size_t n_new);
 };
 
@@ -485,15 +600,11 @@ int SsStep::front() {
                                                          S, s->last_pose.p, s->last_cov.p, s->prev_odo.p, s->rec.p);
   HIP_TRY(ctx, hipGetLastError());
   // host wait 1: the resampled counts and the records
-  Regions B;
-  const size_t b_rs = B.take(S1 * 8), b_rec = B.take((size_t)S * sizeof(ndt_session_step));
-  SS_TRY(s->h_back.ensure(ctx, B.end));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rs, s->rs_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_rec, s->rec.p, (size_t)S * sizeof(ndt_session_step), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += S1 * 8 + (size_t)S * sizeof(ndt_session_step); stats.host_waits++;
-  rs_off.assign((const uint64_t *)(s->h_back.p + b_rs), (const uint64_t *)(s->h_back.p + b_rs) + S1);
-  memcpy(out, s->h_back.p + b_rec, (size_t)S * sizeof(ndt_session_step));
+  SsBack B{s};
+  const size_t b_rs = B.add(s->rs_off.p, S1), b_rec = B.add(s->rec.p, (size_t)S);
+  SS_TRY(B.wait(stats));
+  rs_off.assign(B.at<uint64_t>(b_rs), B.at<uint64_t>(b_rs) + S1);
+  memcpy(out, B.at<ndt_session_step>(b_rec), (size_t)S * sizeof(ndt_session_step));
   return NDT_OK;
 }
 
@@ -582,7 +693,6 @@ int SsStep::book(int i, size_t n_new) {
 
 // ---- the host bookkeeping: table B's rows, the moves and the newest triples of the sessions that stepped (book) ----
 int SsStep::bookkeeping() {
-  cur = s->cur ^ 1;
   dst.assign((size_t)S, nullptr); prevs.assign((size_t)S, PfPrev{nullptr, 0ull});
   plan.assign((size_t)S, SsPlan{nullptr, nullptr, 0ull, -1, 0, 0, 0, nullptr, 0ull});
   tri.sa = tri.sb = sizeof(float2);
@@ -590,9 +700,10 @@ int SsStep::bookkeeping() {
   for (int i = 0; i < S; ++i) {
     const SsSession &Q = s->ses[(size_t)i];
     out[i].submap = Q.n_closed;
+    commit.named[(size_t)i] = out[i].stepped != 0;
     if (out[i].stepped) SS_TRY(book(i, (size_t)(rs_off[(size_t)i + 1] - rs_off[(size_t)i])));
-    else if (Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
   }
+  commit.carried(&carry_cloud, &carry_target);
   stats.triples_run = (int)tri.jobs.size();
   return NDT_OK;
 }
@@ -653,116 +764,32 @@ int SsStep::behind() {
     SS_TRY(fr.close());
   }
   // host wait 2: the target and cloud offsets, the prefix lengths, the status
-  Regions R;
-  b_toff = R.take(S1 * 8); b_coff = R.take(S1 * 8); b_plen = R.take((size_t)S * 8); b_stat = R.take((size_t)S * 4);
-  SS_TRY(s->h_back.ensure(ctx, R.end));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->target_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_coff, s->cloud_off.p, S1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_plen, s->plen.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->status.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += 2 * S1 * 8 + (size_t)S * 12; stats.host_waits++;
-  return NDT_OK;
+  b_toff = back.add(s->target_off.p, S1); b_coff = back.add(s->cloud_off.p, S1); b_plen = back.add(s->plen.p, (size_t)S);
+  b_stat = back.add(s->status.p, (size_t)S);
+  return back.wait(stats);
 }
 
-// ---- what the end of a step and the end of a correction share: the carried ranges and the maps ----
-
-// The ranges of the sessions that keep their views across a call that fills the arenas `cur` (a step they did not take part
-// in, a correction that does not name them): each moves behind the call's own ranges, at c_end / t_end.
-struct SsCarry {
-  ndt_sessions *s; int cur; uint64_t c_end, t_end;
-  std::vector<SsCopy> moves;
-  void keep(SsSession &Q) {
-    if (!Q.has_target || Q.buf == cur) return;
-    if (Q.c_n) moves.push_back(SsCopy{s->cloud[Q.buf].p + Q.c_off, s->cloud[cur].p + c_end, Q.c_n});
-    if (Q.t_n) moves.push_back(SsCopy{s->target[Q.buf].p + Q.t_off, s->target[cur].p + t_end, Q.t_n});
-    Q.c_off = c_end; c_end += Q.c_n; Q.t_off = t_end; t_end += Q.t_n; Q.buf = cur;
-  }
-  // table C, the same size at every call (two carried ranges per session at most), and the copies; `cur` is the set's from here
-  int queue(ndt_sessions_stats &stats) {
-    ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream;
-    const size_t c_bytes = 2 * (size_t)s->S * sizeof(SsCopy);
-    SS_TRY(s->tab_c.reserve(ctx, c_bytes)); SS_TRY(s->d_tab_c.ensure(ctx, c_bytes));
-    memset(s->tab_c.h.p, 0, c_bytes);
-    if (!moves.empty()) memcpy(s->tab_c.h.p, moves.data(), moves.size() * sizeof(SsCopy));
-    HIP_TRY(ctx, s->tab_c.upload(s->d_tab_c.p, 0, c_bytes, st));
-    stats.h2d_bytes += c_bytes;
-    if (!moves.empty())
-      seg_copy_kernel<<<dim3(16, (unsigned)std::min<size_t>(moves.size(), 65535)), 256, 0, st>>>((const SsCopy *)s->d_tab_c.p, (int)moves.size());
-    HIP_TRY(ctx, hipGetLastError());
-    s->cur = cur;
-    return NDT_OK;
-  }
-};
-
-// The NDT maps of the new local maps of the sessions who[k] (xy[k], n[k] points in the target arena), rebuilt in place in one
-// batched build; a host wait: the bounding boxes (without a map to build, the stream).  A build refused for one session
-// (NDT_E_GRID: its local map spans more than 2^28 cells) costs that session alone: code[k] takes the build's code, its map
-// stays exactly as it was (none stays none), every other map is built in the same launches.
-int ss_build_maps(ndt_sessions *s, const std::vector<const float *> &xy, const std::vector<size_t> &n, const std::vector<int> &who,
-                  std::vector<int> *code, ndt_sessions_stats &stats) {
-  ndt_ctx *ctx = s->ctx;
-  code->assign(who.size(), NDT_OK);
-  if (!who.empty()) {
-    std::vector<ndt_params> bp(who.size(), s->prm.match);
-    std::vector<ndt_map *> maps;
-    for (int i : who) maps.push_back(s->ses[(size_t)i].map);
-    SS_TRY(check_build_batch(ctx, xy.data(), n.data(), sizeof(float2), (int)who.size(), bp.data(), maps.data(), "ndt_map_build_batch_dev"));
-    SS_TRY(build_batch(ctx, xy.data(), n.data(), sizeof(float2), (int)who.size(), bp.data(), maps.data(), "ndt_map_build_batch_dev", code->data()));
-    for (size_t k = 0; k < who.size(); ++k)
-      if ((*code)[k] == NDT_OK) s->ses[(size_t)who[k]].map = maps[k];
-  } else {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  stats.host_waits++; stats.d2h_bytes += who.size() * 16 * sizeof(unsigned);
-  return NDT_OK;
-}
-
-// ---- the close: the new views, the carried ranges (table C), the NDT maps of the new local maps (host wait 3) ----
+// ---- the close: the new views of who stepped; the commit (table C; the NDT maps, host wait 3: a refused build's code goes into the record) ----
 int SsStep::close() {
-  const uint64_t *toff = (const uint64_t *)(s->h_back.p + b_toff), *coff = (const uint64_t *)(s->h_back.p + b_coff),
-                 *pl = (const uint64_t *)(s->h_back.p + b_plen);
-  const int *stt = (const int *)(s->h_back.p + b_stat);
-  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst;
-  SsCarry carry{s, cur, coff[S], toff[S], {}};
+  const uint64_t *toff = back.at<uint64_t>(b_toff), *coff = back.at<uint64_t>(b_coff), *pl = back.at<uint64_t>(b_plen);
+  const int *stt = back.at<int>(b_stat);
   for (int i = 0; i < S; ++i) {
-    SsSession &Q = s->ses[(size_t)i];
-    if (out[i].stepped) {
-      Q.plen = pl[i];
-      if (stt[i] != NDT_OK) {
-        // the newest triple spans more than 2^30 voxels: no cloud and no local map this step; the map stays as it is
-        out[i].status = NDT_E_ARG;
-        Q.has_target = false; Q.c_n = Q.t_n = Q.n_prev = 0; Q.buf = cur;
-        continue;
-      }
-      Q.buf = cur; Q.has_target = true;
-      Q.c_off = coff[i]; Q.c_n = coff[i + 1] - coff[i];
-      Q.t_off = toff[i]; Q.t_n = toff[i + 1] - toff[i];
-      Q.n_prev = prevs[(size_t)i].n;
-      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(i); }
-    } else {
-      carry.keep(Q);      // a session that did not step keeps its views and its last local map: they move to this step's arenas
-    }
+    if (!out[i].stepped) continue;      // (it keeps its views and its last local map: they move to this step's arenas)
+    s->ses[(size_t)i].plen = pl[i];
+    if (stt[i] != NDT_OK) out[i].status = NDT_E_ARG;
+    commit.view(i, (size_t)i, stt[i] == NDT_OK, coff, toff, prevs[(size_t)i].n);
   }
-  SS_TRY(carry.queue(stats));
-  // the NDT maps of the new local maps (host wait 3: the bounding boxes); a refused build's code goes into the session's record
-  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
-  for (size_t k = 0; k < bwho.size(); ++k)
-    if (bst[k] != NDT_OK) out[bwho[k]].status = bst[k];
-  s->stats = stats;
-  return NDT_OK;
+  return commit.finish(coff[S], toff[S], [&](size_t i) -> int & { return out[i].status; });
 }
 
 // The step: DESIGN.md 4.10's list.  Every return with a HIP error leaves the set dead (the caller marks it).
-int ss_step(ndt_sessions *s, const double *raw_host, const double *raw_dev, size_t stride, const uint64_t *raw_offsets,
-            const double *odo_host, const double *odo_dev, const unsigned char *active, ndt_session_step *out) {
-  HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
-  SsStep T{s, raw_host, raw_dev, stride, raw_offsets, odo_host, odo_dev, active, out};
-  if (!T.who_steps()) return NDT_OK;
-  SS_TRY(T.front());
-  SS_TRY(T.bookkeeping());
-  SS_TRY(T.behind());
-  return T.close();
+int SsStep::run() {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!who_steps()) return NDT_OK;
+  SS_TRY(front());
+  SS_TRY(bookkeeping());
+  SS_TRY(behind());
+  return close();
 }
 
 // ---- ndt_sessions_correct: PointCloudMap::remakeMaps for the sessions which[0 .. n_corr) ----
@@ -775,26 +802,29 @@ int ss_anchor(const SsSession &Q, int m) {
   return e > a ? a + (e - a) / 2 : a;
 }
 
-// The arguments have passed the entry point's refusals.  Three parts around two host waits: (1) the rows of every stored scan
-// and closed cloud moved in place, the current submaps assembled again from the moved scans with the local maps behind them
-// (queue_local_map_batch: every triple, as the composed chain computes them), the prefixes refilled from the clouds; wait 1:
-// offsets and status; (2) the views, the carried ranges of everybody else; (3) the NDT maps (wait 2: the boxes).
-int ss_correct(ndt_sessions *s, const int *which, int n_corr, const double *const *new_poses, int *status_out) {
-  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ndt_sessions_stats stats{};
-  const int cur = s->cur ^ 1;
-  const size_t C = (size_t)n_corr, C1 = C + 1;
-  std::vector<SsMove> rows; std::vector<SsFix> fix(C); std::vector<ndt_submap_desc> subs(C);
-  std::vector<unsigned char> named((size_t)S, 0);
-  size_t cap_cloud = 0, total_prev = 0, carry_cloud = 0, carry_target = 0, most_pts = 0;
+// The arguments have passed the entry point's refusals.  rows(): the rows of every stored scan and closed cloud moved in place, the
+// current submaps as queue_local_map_batch takes them.  run(): the moves, the current submaps assembled again from the moved scans
+// with the local maps behind them (every triple, as the composed chain computes them), the prefixes refilled from the clouds; wait
+// 1: offsets and status; the corrected sessions' views, then SsCommit's tail (everybody else's ranges, the NDT maps; wait 2).
+struct SsCorrect {
+  ndt_sessions *s; const int *which; int n_corr; const double *const *new_poses; int *status_out;
+  ndt_ctx *ctx = s->ctx; const ndt_session_params &P = s->prm; const size_t C = (size_t)n_corr;
+  SsCommit commit{s}; ndt_sessions_stats &stats = commit.stats; const int cur = commit.cur;
+  std::vector<SsMove> moved; std::vector<SsFix> fix; std::vector<ndt_submap_desc> subs;
+  size_t cap_cloud = 0, total_prev = 0, most_pts = 0;
+  int rows(); int run();
+};
+
+int SsCorrect::rows() {
+  fix.resize(C); subs.resize(C);
+  stats.sessions_stepped = n_corr;
   for (size_t c = 0; c < C; ++c) {
     SsSession &Q = s->ses[(size_t)which[c]];
-    named[(size_t)which[c]] = 1;
+    commit.named[(size_t)which[c]] = 1;
     const double *po = Q.traj.data(), *pn = new_poses[c];
     const size_t n = Q.scan_off.size() - 1, first = (size_t)Q.n_poses - n;
     auto row = [&](float2 *p, uint64_t cnt, size_t k) {
-      rows.push_back(SsMove{p, cnt, {po[3 * k], po[3 * k + 1], po[3 * k + 2]}, {pn[3 * k], pn[3 * k + 1], pn[3 * k + 2]}});
+      moved.push_back(SsMove{p, cnt, {po[3 * k], po[3 * k + 1], po[3 * k + 2]}, {pn[3 * k], pn[3 * k + 1], pn[3 * k + 2]}});
       most_pts = std::max(most_pts, (size_t)cnt);
     };
     for (int m = 0; m < Q.n_closed; ++m)
@@ -812,82 +842,55 @@ int ss_correct(ndt_sessions *s, const int *which, int n_corr, const double *cons
     cap_cloud += submap_points(D); total_prev += D.n_prev;
     SS_TRY(ss_grow(ctx, Q.prefix, submap_points(D), 0));      // (refilled whole: nothing of it is kept)
     const int with_newest = P.remove_moving ? 1 : (Q.first_submap || n - 1 >= 2);
-    fix[c] = SsFix{which[c], with_newest, Q.scan_off[n] - Q.scan_off[n - 1], Q.prefix.p, {pn[3 * (Q.n_poses - 1)], pn[3 * (Q.n_poses - 1) + 1], pn[3 * (Q.n_poses - 1) + 2]}};
+    const double *last = pn + 3 * ((size_t)Q.n_poses - 1);
+    fix[c] = SsFix{which[c], with_newest, Q.scan_off[n] - Q.scan_off[n - 1], Q.prefix.p, {last[0], last[1], last[2]}};
   }
-  for (int i = 0; i < S; ++i) {
-    const SsSession &Q = s->ses[(size_t)i];
-    if (!named[(size_t)i] && Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
-  }
+  return NDT_OK;
+}
+
+int SsCorrect::run() {
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SS_TRY(rows());
+  size_t carry_cloud = 0, carry_target = 0;
+  commit.carried(&carry_cloud, &carry_target);
   SS_TRY(s->cloud[cur].ensure(ctx, cap_cloud + carry_cloud + 64));
   SS_TRY(s->target[cur].ensure(ctx, cap_cloud + total_prev + carry_target + 64));
   // table A: the rows | the fixes; the prefix segments of session_refill_kernel lie behind it on the device
   Regions A;
-  const size_t o_rows = A.take(rows.size() * sizeof(SsMove)), o_fix = A.take(C * sizeof(SsFix)), a_bytes = A.end,
+  const size_t o_rows = A.take(moved.size() * sizeof(SsMove)), o_fix = A.take(C * sizeof(SsFix)), a_bytes = A.end,
                o_seg = A.take(C * sizeof(SsCopy));
   SS_TRY(s->tab_a.reserve(ctx, a_bytes)); SS_TRY(s->d_tab_a.ensure(ctx, A.end));
-  memcpy(s->tab_a.h.p + o_rows, rows.data(), rows.size() * sizeof(SsMove));
+  memcpy(s->tab_a.h.p + o_rows, moved.data(), moved.size() * sizeof(SsMove));
   memcpy(s->tab_a.h.p + o_fix, fix.data(), C * sizeof(SsFix));
   HIP_TRY(ctx, s->tab_a.upload(s->d_tab_a.p, 0, a_bytes, st));
   stats.h2d_bytes += a_bytes;
   unsigned char *da = s->d_tab_a.p;
-  repose_rows_kernel<<<dim3((unsigned)std::min<size_t>(64, most_pts / 256 + 1), (unsigned)std::min<size_t>(rows.size(), 65535)), 256, 0, st>>>(
-      (const SsMove *)(da + o_rows), (int)rows.size());
+  repose_rows_kernel<<<dim3((unsigned)std::min<size_t>(64, most_pts / 256 + 1), (unsigned)std::min<size_t>(moved.size(), 65535)), 256, 0, st>>>(
+      (const SsMove *)(da + o_rows), (int)moved.size());
   HIP_TRY(ctx, hipGetLastError());
-  size_t up = 0, nt = 0;
-  {
-    CallFrame fr(ctx);                            // (the assembly's and the filter's scratch are the context's)
-    SS_TRY(fr.open(st));
-    SS_TRY(queue_local_map_batch(ctx, st, subs.data(), n_corr, sizeof(float2), P.leaf, (float *)s->cloud[cur].p, s->cloud_off.p,
-                                 (float *)s->target[cur].p, s->target_off.p, s->status.p, &up, &nt));
-    SS_TRY(fr.close());
-  }
-  stats.h2d_bytes += up; stats.triples_run = (int)nt; stats.sessions_stepped = n_corr;
+  SS_TRY(ss_local_maps(s, subs, s->cloud[cur].p, s->cloud_off, s->target[cur].p, s->target_off, s->status, stats));
   session_refill_kernel<<<(n_corr + 255) / 256, 256, 0, st>>>((const SsFix *)(da + o_fix), n_corr, (const unsigned long long *)s->cloud_off.p,
                                                              s->status.p, s->cloud[cur].p, s->plen.p, s->last_pose.p, (SsCopy *)(da + o_seg));
   seg_copy_kernel<<<dim3(ss_gx(cap_cloud, n_corr), (unsigned)std::min(n_corr, 65535)), 256, 0, st>>>((const SsCopy *)(da + o_seg), n_corr);
   HIP_TRY(ctx, hipGetLastError());
   // host wait 1: the cloud and target offsets, the status
-  Regions R;
-  const size_t b_coff = R.take(C1 * 8), b_toff = R.take(C1 * 8), b_stat = R.take(C * 4);
-  SS_TRY(s->h_back.ensure(ctx, R.end));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_coff, s->cloud_off.p, C1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->target_off.p, C1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->status.p, C * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += 2 * C1 * 8 + C * 4; stats.host_waits++;
-  const uint64_t *coff = (const uint64_t *)(s->h_back.p + b_coff), *toff = (const uint64_t *)(s->h_back.p + b_toff);
-  const int *stt = (const int *)(s->h_back.p + b_stat);
+  SsBack back{s};
+  const size_t b_coff = back.add(s->cloud_off.p, C + 1), b_toff = back.add(s->target_off.p, C + 1), b_stat = back.add(s->status.p, C);
+  SS_TRY(back.wait(stats));
+  const uint64_t *coff = back.at<uint64_t>(b_coff), *toff = back.at<uint64_t>(b_toff);
+  const int *stt = back.at<int>(b_stat);
   // the corrected sessions' host state and views; everybody else's ranges move to this call's arenas
-  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst; std::vector<size_t> bentry;
   for (size_t c = 0; c < C; ++c) {
     SsSession &Q = s->ses[(size_t)which[c]];
     Q.traj.assign(new_poses[c], new_poses[c] + 3 * (size_t)Q.n_poses);
     Q.last_tx = fix[c].pose[0]; Q.last_ty = fix[c].pose[1];
-    Q.buf = cur;
     status_out[c] = stt[c];
-    if (stt[c] != NDT_OK) {
-      // a recomputed triple spans more than 2^30 voxels: no cloud, no local map and an empty prefix; the map stays as it is
-      Q.has_target = false; Q.c_n = Q.t_n = Q.n_prev = 0; Q.plen = 0;
-      continue;
-    }
-    Q.has_target = true;
-    Q.c_off = coff[c]; Q.c_n = coff[c + 1] - coff[c];
-    Q.t_off = toff[c]; Q.t_n = toff[c + 1] - toff[c];
-    Q.n_prev = subs[c].n_prev;
-    const uint64_t nn = fix[c].with_newest ? fix[c].newest_n : 0;      // (session_refill_kernel's rule)
+    commit.view(which[c], c, stt[c] == NDT_OK, coff, toff, subs[c].n_prev);
+    const uint64_t nn = fix[c].with_newest ? fix[c].newest_n : 0;      // (session_refill_kernel's rule; a failed cloud: an empty prefix)
     Q.plen = Q.c_n >= nn ? Q.c_n - nn : 0;
-    if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(which[c]); bentry.push_back(c); }
   }
-  SsCarry carry{s, cur, coff[C], toff[C], {}};
-  for (int i = 0; i < S; ++i)
-    if (!named[(size_t)i]) carry.keep(s->ses[(size_t)i]);
-  SS_TRY(carry.queue(stats));
-  // the NDT maps of the new local maps, by the step's refusal rule (host wait 2: the bounding boxes)
-  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
-  for (size_t k = 0; k < bwho.size(); ++k)
-    if (bst[k] != NDT_OK) status_out[bentry[k]] = bst[k];
-  s->stats = stats;
-  return NDT_OK;
+  return commit.finish(coff[C], toff[C], [&](size_t c) -> int & { return status_out[c]; });
 }
 
 // ---- ndt_sessions_remake_closed: every closed submap's cloud again from the archive ----
@@ -904,27 +907,30 @@ void ss_closed_scan_ranges(const SsSession &Q, std::vector<int> *first, std::vec
   }
 }
 
-// The arguments have passed the entry point's refusals.  (1) One table: a row per archived scan in use, a row per named
-// session; remake_scans_kernel lays every session's scans out in archive order, so that every submap's scan list is a range of
-// it described by a slice of the archive's own offsets; queue_local_map_batch over every closed submap of every named session;
-// remake_plan_kernel; wait 1: the filtered clouds' offsets, the local maps' offsets, the status.  (2) The closed blocks grown to
-// what they need, the moves into the arenas (seg_copy_kernel), the closed blocks and everybody else's ranges (SsCarry's table).
-// (3) The NDT maps (wait 2: the boxes).  Nothing is committed before wait 1: a session that failed keeps every byte.
-int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status_out) {
-  ndt_ctx *ctx = s->ctx; hipStream_t st = ctx->stream; const int S = s->S; const ndt_session_params &P = s->prm;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ndt_sessions_stats stats{};
-  stats.sessions_stepped = n_named;
-  const size_t C = (size_t)n_named, C1 = C + 1;
+// The arguments have passed the entry point's refusals.  plan(): every closed submap of every named session as queue_local_map_batch
+// takes it -- its scan list a slice of the archive's own offsets, the session's scans laid out in archive order; the arenas'
+// sizes, a row per archived scan in use, a row per named session.  run(): the one table, remake_scans_kernel, the assembly
+// over every submap, remake_plan_kernel; wait 1: the filtered clouds' offsets, the local maps' offsets, the status; the moves into
+// the arenas (seg_copy_kernel), the closed blocks grown to what they need and their moves beside everybody else's ranges (SsCommit's
+// tail; the NDT maps, wait 2).  Nothing is committed before wait 1: a session that failed keeps every byte.
+struct SsRemakeCall {
+  ndt_sessions *s; const int *which; int n_named; int *status_out;
+  ndt_ctx *ctx = s->ctx; const ndt_session_params &P = s->prm; const size_t C = (size_t)n_named;
+  SsCommit commit{s}; ndt_sessions_stats &stats = commit.stats; const int cur = commit.cur;
+  std::vector<SsRescan> scans; std::vector<SsRemake> rows; std::vector<ndt_submap_desc> subs;
+  std::vector<size_t> base;                            // where session c's scans start in rm_scan
+  size_t scan_pts = 0, cap_cloud = 0, most_pts = 0, need_cloud = 0, need_target = 0, c_end = 0;
+  int plan(); int run();
+};
+
+int SsRemakeCall::plan() {
   static const uint64_t no_scan[2] = {0, 0};
-  std::vector<SsRescan> scans; std::vector<SsRemake> rows(C); std::vector<ndt_submap_desc> subs;
-  std::vector<size_t> base(C, 0);                      // where session c's scans start in rm_scan
-  std::vector<unsigned char> named((size_t)S, 0);
-  size_t scan_pts = 0, cap_cloud = 0, most_pts = 0;
+  stats.sessions_stepped = n_named;
+  rows.resize(C); base.assign(C, 0);
   std::vector<int> first, count;
   for (size_t c = 0; c < C; ++c) {
     const SsSession &Q = s->ses[(size_t)which[c]];
-    named[(size_t)which[c]] = 1;
+    commit.named[(size_t)which[c]] = 1;
     rows[c].d0 = (int)subs.size();
     ss_closed_scan_ranges(Q, &first, &count);
     base[c] = scan_pts;
@@ -944,34 +950,24 @@ int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status
     }
     rows[c].d1 = (int)subs.size();
   }
-  const size_t nd = subs.size(), nd1 = nd + 1;
-  if (!cap_cloud) {
-    // no named session has a closed submap that held a point: nothing to compute, nobody changes a byte, nothing is queued
-    for (size_t c = 0; c < C; ++c) status_out[c] = NDT_OK;
-    s->stats = stats;
-    return NDT_OK;
-  }
+  const size_t nd = subs.size();
+  if (!cap_cloud) return NDT_OK;      // (nothing to compute)
   if (nd > (size_t)INT32_MAX / 4 || scan_pts > ((size_t)1 << 40))
     return fail(ctx, NDT_E_ARG, "ndt_sessions_remake_closed: more than 2^29 closed submaps or 2^40 archived points in one call");
-  const int cur = s->cur ^ 1;
   SS_TRY(s->rm_scan.ensure(ctx, scan_pts + 64)); SS_TRY(s->rm_cloud.ensure(ctx, cap_cloud + 64)); SS_TRY(s->rm_target.ensure(ctx, cap_cloud + 64));
-  SS_TRY(s->rm_coff.ensure(ctx, nd1)); SS_TRY(s->rm_toff.ensure(ctx, nd1)); SS_TRY(s->rm_status.ensure(ctx, nd));
-  SS_TRY(s->rm_ses_toff.ensure(ctx, C1)); SS_TRY(s->rm_ses_status.ensure(ctx, C));
+  SS_TRY(s->rm_coff.ensure(ctx, nd + 1)); SS_TRY(s->rm_toff.ensure(ctx, nd + 1)); SS_TRY(s->rm_status.ensure(ctx, nd));
+  SS_TRY(s->rm_ses_toff.ensure(ctx, C + 1)); SS_TRY(s->rm_ses_status.ensure(ctx, C));
   // the arenas: a named session's cloud as it is; its local map with the larger of the two newest closed clouds it may get
-  size_t need_cloud = 0, need_target = 0, carry_cloud = 0, carry_target = 0;
+  size_t carry_cloud = 0, carry_target = 0;
   for (size_t c = 0; c < C; ++c) {
     const SsSession &Q = s->ses[(size_t)which[c]];
     if (!Q.has_target) continue;
     const size_t newest = rows[c].d1 > rows[c].d0 ? submap_points(subs[(size_t)rows[c].d1 - 1]) : 0;
     need_cloud += (size_t)Q.c_n; need_target += std::max(newest, (size_t)Q.n_prev) + (size_t)(Q.t_n - Q.n_prev);
   }
-  for (int i = 0; i < S; ++i) {
-    const SsSession &Q = s->ses[(size_t)i];
-    if (!named[(size_t)i] && Q.has_target && Q.buf != cur) { carry_cloud += Q.c_n; carry_target += Q.t_n; }
-  }
+  commit.carried(&carry_cloud, &carry_target);
   SS_TRY(s->cloud[cur].ensure(ctx, need_cloud + carry_cloud + 64));
   SS_TRY(s->target[cur].ensure(ctx, need_target + carry_target + 64));
-  size_t c_end = 0;
   for (size_t c = 0; c < C; ++c) {
     const SsSession &Q = s->ses[(size_t)which[c]];
     SsRemake &R = rows[c];
@@ -992,6 +988,19 @@ int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status
     c_end += (size_t)R.c_n;
   }
   if (scans.size() > (size_t)INT32_MAX) return fail(ctx, NDT_E_ARG, "ndt_sessions_remake_closed: more than 2^31 - 1 archived scans in one call");
+  return NDT_OK;
+}
+
+int SsRemakeCall::run() {
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SS_TRY(plan());
+  if (!cap_cloud) {
+    // no named session has a closed submap that held a point: nothing to compute, nobody changes a byte, nothing is queued
+    for (size_t c = 0; c < C; ++c) status_out[c] = NDT_OK;
+    s->stats = stats;
+    return NDT_OK;
+  }
   // table A: the scans' rows | the sessions' rows; the segments of remake_plan_kernel lie behind it on the device
   Regions A;
   const size_t o_scans = A.take(scans.size() * sizeof(SsRescan)), o_rows = A.take(C * sizeof(SsRemake)), a_bytes = A.end,
@@ -1005,37 +1014,22 @@ int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status
   remake_scans_kernel<<<dim3((unsigned)std::min<size_t>(64, most_pts / 256 + 1), (unsigned)std::min<size_t>(scans.size(), 65535)), 256, 0, st>>>(
       (const SsRescan *)(da + o_scans), (int)scans.size());
   HIP_TRY(ctx, hipGetLastError());
-  size_t up = 0, nt = 0;
-  {
-    CallFrame fr(ctx);                            // (the assembly's and the filter's scratch are the context's)
-    SS_TRY(fr.open(st));
-    SS_TRY(queue_local_map_batch(ctx, st, subs.data(), (int)nd, sizeof(float2), P.leaf, (float *)s->rm_cloud.p, s->rm_coff.p,
-                                 (float *)s->rm_target.p, s->rm_toff.p, s->rm_status.p, &up, &nt));
-    SS_TRY(fr.close());
-  }
-  stats.h2d_bytes += up; stats.triples_run = (int)nt;
+  SS_TRY(ss_local_maps(s, subs, s->rm_cloud.p, s->rm_coff, s->rm_target.p, s->rm_toff, s->rm_status, stats));
   remake_plan_kernel<<<1, 1024, 0, st>>>((const SsRemake *)(da + o_rows), n_named, s->rm_target.p, (const unsigned long long *)s->rm_toff.p,
                                          s->rm_status.p, s->target[cur].p, (unsigned long long *)s->rm_ses_toff.p, s->rm_ses_status.p,
                                          (SsCopy *)(da + o_seg));
   HIP_TRY(ctx, hipGetLastError());
   // host wait 1: the filtered clouds' offsets, the local maps' offsets, the status
-  Regions R;
-  const size_t b_doff = R.take(nd1 * 8), b_toff = R.take(C1 * 8), b_stat = R.take(C * 4);
-  SS_TRY(s->h_back.ensure(ctx, R.end));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_doff, s->rm_toff.p, nd1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_toff, s->rm_ses_toff.p, C1 * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_back.p + b_stat, s->rm_ses_status.p, C * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.d2h_bytes += nd1 * 8 + C1 * 8 + C * 4; stats.host_waits++;
-  const uint64_t *doff = (const uint64_t *)(s->h_back.p + b_doff), *toff = (const uint64_t *)(s->h_back.p + b_toff);
-  const int *stt = (const int *)(s->h_back.p + b_stat);
+  SsBack back{s};
+  const size_t b_doff = back.add(s->rm_toff.p, subs.size() + 1), b_toff = back.add(s->rm_ses_toff.p, C + 1), b_stat = back.add(s->rm_ses_status.p, C);
+  SS_TRY(back.wait(stats));
+  const uint64_t *doff = back.at<uint64_t>(b_doff), *toff = back.at<uint64_t>(b_toff);
+  const int *stt = back.at<int>(b_stat);
   // the commit: the moves into the arenas, then the closed blocks (to their exact size) with everybody else's ranges
   seg_copy_kernel<<<dim3(ss_gx(need_cloud + need_target, 3 * n_named), (unsigned)std::min<size_t>(3 * C, 65535)), 256, 0, st>>>(
       (const SsCopy *)(da + o_seg), 3 * n_named);
   HIP_TRY(ctx, hipGetLastError());
-  SsCarry carry{s, cur, c_end, toff[C], {}};
-  std::vector<const float *> bxy; std::vector<size_t> bn; std::vector<int> bwho, bst; std::vector<size_t> bentry;
-  c_end = 0;
+  uint64_t c_at = 0;
   for (size_t c = 0; c < C; ++c) {
     SsSession &Q = s->ses[(size_t)which[c]];
     const SsRemake &W = rows[c];
@@ -1044,27 +1038,19 @@ int ss_remake_closed(ndt_sessions *s, const int *which, int n_named, int *status
     if (remade) {
       const uint64_t d0 = doff[W.d0], need = doff[W.d1] - d0;
       SS_TRY(ss_grow(ctx, Q.closed, (size_t)need, 0));      // (rewritten whole: nothing of it is kept)
-      if (need) carry.moves.push_back(SsCopy{s->rm_target.p + d0, Q.closed.p, need});
+      if (need) commit.moves.push_back(SsCopy{s->rm_target.p + d0, Q.closed.p, need});
       for (int m = 0; m <= Q.n_closed; ++m) Q.closed_off[(size_t)m] = doff[W.d0 + m] - d0;
     }
     Q.buf = cur;
     if (!Q.has_target) continue;
-    Q.c_off = c_end; c_end += (size_t)Q.c_n;
+    Q.c_off = c_at; c_at += Q.c_n;
     Q.t_off = toff[c]; Q.t_n = toff[c + 1] - toff[c];
     if (remade) {
       Q.n_prev = doff[W.d1] - doff[W.d1 - 1];
-      if (Q.t_n) { bxy.push_back((const float *)(s->target[cur].p + Q.t_off)); bn.push_back((size_t)Q.t_n); bwho.push_back(which[c]); bentry.push_back(c); }
+      commit.wants_map(which[c], c);
     }
   }
-  for (int i = 0; i < S; ++i)
-    if (!named[(size_t)i]) carry.keep(s->ses[(size_t)i]);
-  SS_TRY(carry.queue(stats));
-  // the NDT maps of the new local maps, by the step's refusal rule (host wait 2: the bounding boxes)
-  SS_TRY(ss_build_maps(s, bxy, bn, bwho, &bst, stats));
-  for (size_t k = 0; k < bwho.size(); ++k)
-    if (bst[k] != NDT_OK) status_out[bentry[k]] = bst[k];
-  s->stats = stats;
-  return NDT_OK;
+  return commit.finish(c_end, toff[C], [&](size_t c) -> int & { return status_out[c]; });
 }
 
 #undef SS_TRY

@@ -1,4 +1,4 @@
-"""Workloads that walk ndt_sessions_find_loops_multi and ndt_sessions_find_cross_loops through what they added to ss_find_loops
+"""Workloads that walk ndt_sessions_find_loops_multi and ndt_sessions_find_cross_loops through what they added to the search (LpSearch)
 (ndt_slam_amd/csrc/ndt_loops.hip.h; tests only): several candidates of a session in a row behind one newest scan (rank, scan_of),
 a resident map slot per rank, another session's closed cloud, trajectory and anchor pose (owner_of), the ranged verification
 and the host decision behind it.  tests/loop_shape_workloads.py's machinery and settings: 181 beams, score_thre -1, sepThre 1,

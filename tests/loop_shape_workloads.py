@@ -1,6 +1,6 @@
 """Workloads that walk ndt_sessions_find_loops (ndt_slam_amd/csrc/ndt_loops.hip.h) through its own layout arithmetic (tests
 only): named families of small session sets, the searches made on them, and per family a certificate that says which branch
-of ss_find_loops / loop_scan_kernel / loop_guess_kernel it reaches.  tests/test_loop_shapes_host.py checks every certificate
+of LpSearch / loop_scan_kernel / loop_guess_kernel it reaches.  tests/test_loop_shapes_host.py checks every certificate
 that needs no device; tests/test_gpu_loop_shapes.py holds the device byte for byte to the composed chain on every family and
 checks the certificates that are statements about picks (n_cand), on the composed reference.
 
