@@ -984,6 +984,68 @@ int ndt_pg_optimize_batch_dev(ndt_ctx *ctx, double *poses_dev, const uint64_t *n
 int ndt_pg_optimize_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
                           const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params,
                           ndt_pg_result *out_host);
+/* ---- Pose graphs that reject false loop arcs: graduated non-convexity on Geman-McClure arcs ----
+ * ndt_pg_optimize_batch takes every arc at face value; a loop search verifies that two clouds fit, not that the place is the
+ * same, and one false arc bends a whole trajectory.  These calls are that optimiser with a robust cost on the arcs the caller
+ * marks, by graduated non-convexity (Yang, Antonante, Tzoumas, Carlone: "Graduated Non-Convexity for Robust Spatial Perception",
+ * RA-L 2020, the Geman-McClure form): a plain redescending kernel started at a drifted chain would reject the true loops too,
+ * whose first chi-square is large precisely because of the drift they are meant to remove.
+ *
+ * Model.  Arcs, poses, the residual r_e, Omega_e and node 0 held fixed are exactly those of ndt_pg_optimize_batch.  Every arc
+ * also carries phi_e >= 0 (phi[e], indexed like edges; phi == NULL: all 0).  phi_e == 0: a plain arc, never down-weighted
+ * (odometry arcs).  phi_e > 0: a robust arc.  With c_e = r_e^T Omega_e r_e and a level mu >= 1: a plain arc has rho = c_e,
+ * w_e = 1; a robust arc has sigma = mu phi_e, rho = sigma c_e / (sigma + c_e), w_e = (sigma / (sigma + c_e))^2;
+ * F_mu = sum_e rho.  At mu = 1 an arc with c_e = phi_e has weight 1/4: phi is the chi-square beyond which an arc counts as
+ * rejected.
+ *
+ * Method.  One TRIP at the current mu: linearise at x, every arc's w_e at x, (sum w_e J^T Omega J) d = -(sum w_e J^T Omega r)
+ * by the same preconditioned conjugate gradients (the chain matrix T from the weighted blocks), then the same step rule on
+ * F_mu: s = 1, 1/2, ..., the first trial whose F_mu is finite and does not rise, at most max_halvings halvings.  max_iter bounds
+ * the TRIPS, accepted or not, over all levels; iterations counts accepted steps.  Levels: mu starts at mu0; mu0 = 0 in the
+ * parameters means max(1, 2 max_e c_e(x0) / phi_e) over the graph's robust arcs, clipped to 1e12; a graph without a robust arc
+ * starts at 1 whatever mu0 says.  A level with mu > 1 ends when an accepted step has max|s d| < eps_level, when the halving runs
+ * out, or when the level has taken level_iter accepted steps; then mu = max(1, mu / factor) and F is evaluated again at the
+ * same poses.  At mu == 1 the ending rules of ndt_pg_optimize_batch hold unchanged (eps_step, the run-out below eps_step, the
+ * CG breakdown, the pivot floor, `converged`); converged can only become 1 at mu == 1.  A T that is not positive definite and a
+ * CG breakdown end the run at any level, with converged = 0 and the last accepted poses: a component whose only tie to node 0
+ * is a robust arc ends so once that arc's weight has fallen below the pivot floor.  cost_initial and cost_final are F_1 at the
+ * first and the last poses; cost_final <= cost_initial is promised only for runs that spend every trip at mu == 1 (a level
+ * above 1 lowers F_mu, not F_1).  factor = 1.4 is the paper's; level_iter = 3 and eps_level = 1e-3 come from a numpy prototype
+ * on drifted figure-eights of 24 and 65 nodes (tests/pg_robust_helpers.py), not from a device measurement.
+ *
+ * Outputs per arc (optional arrays indexed like edges): weight_out[e] = w_e at mu = 1 at the final poses, 1.0 for a plain
+ * arc; chi2_out[e] = c_e there.  An arc counts as REJECTED when it is robust and its final c_e > phi_e (weight below 1/4);
+ * n_rejected counts them, n_robust the arcs with phi_e > 0.  mu0 in the record is the value the graph started at, levels the
+ * number of levels visited (1 for a graph that starts at mu == 1).  For a graph that ends with status != NDT_OK the arc
+ * outputs and the record's other fields are 0.  A graph without arcs: NDT_OK, converged = 1, mu0 = 1, levels = 1.
+ *
+ * Per-graph faults are those of ndt_pg_optimize_batch, found on the device in the same way, and a phi_e that is negative or
+ * not finite: status = NDT_E_ARG for that graph alone.
+ *
+ * A graph with no robust arc (phi == NULL, or all zeros) comes back with poses and the `pg` part of its record byte-identical
+ * to what ndt_pg_optimize_batch gives for the same input and ndt_pg_params; its weights are exactly 1.0.  Resources are those of
+ * ndt_pg_optimize_batch: the same table and scratch, one launch; a graph's bytes are a function of its own input alone.
+ *
+ * Refusals (NDT_E_ARG, synchronous, nothing queued or written): those of ndt_pg_optimize_batch (on params->pg); mu0 that is
+ * neither 0 nor in [1, 1e12]; factor outside [1.05, 1e6]; eps_level negative or not finite; level_iter outside [1, 10000]. */
+typedef struct ndt_pg_robust_params { ndt_pg_params pg; double mu0, factor, eps_level; int level_iter; } ndt_pg_robust_params;
+typedef struct ndt_pg_robust_result {   /* one per graph; 56 bytes */
+  ndt_pg_result pg; double mu0; int levels, n_robust, n_rejected, pad;
+} ndt_pg_robust_result;
+/* pg as ndt_pg_default_params but max_iter = 200 (the trips of every level); mu0 = 0 (automatic), factor = 1.4,
+ * eps_level = 1e-3, level_iter = 3. */
+int ndt_pg_robust_default_params(ndt_pg_robust_params *p);
+/* Device poses, arcs, phi (may be NULL), records and arc outputs (each may be NULL); HOST offset arrays; asynchronous on
+ * `stream` (NULL = the context's). */
+int ndt_pg_optimize_robust_batch_dev(ndt_ctx *ctx, double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                                     const uint64_t *edge_offsets_host, int n_graphs, const double *phi_dev,
+                                     const ndt_pg_robust_params *params, ndt_pg_robust_result *out_dev, double *weight_out_dev,
+                                     double *chi2_out_dev, void *stream);
+/* The same from host memory; synchronous. */
+int ndt_pg_optimize_robust_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                                 const uint64_t *edge_offsets_host, int n_graphs, const double *phi_host,
+                                 const ndt_pg_robust_params *params, ndt_pg_robust_result *out_host, double *weight_out_host,
+                                 double *chi2_out_host);
 /* PointCloudMap::remakeMaps' point correction (src/PointCloudMap.cpp:147-154) for clouds stored in ranges.  Segment k covers the
  * points [seg_offsets[k], seg_offsets[k + 1]) of xy (two float32 at each stride) and has the pose triples old_poses[k] and
  * new_poses[k]: q = oldPose.relativePoint(p), p' = newPose.globalPoint(q) (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat

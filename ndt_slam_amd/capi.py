@@ -150,6 +150,11 @@ class PgParams(C.Structure):
                 ("max_halvings", C.c_int)]
 
 
+class PgRobustParams(C.Structure):
+    """ndt_pg_robust_params (include/ndt_mi355x.h): the pose-graph parameters and the level schedule."""
+    _fields_ = [("pg", PgParams), ("mu0", C.c_double), ("factor", C.c_double), ("eps_level", C.c_double), ("level_iter", C.c_int)]
+
+
 NDT_LOOP_MAX_CAND = 8
 
 
@@ -213,6 +218,8 @@ LOOP_MULTI_DTYPE = np.dtype(LoopMulti)
 PG_EDGE_DTYPE = np.dtype([("from", "i4"), ("to", "i4"), ("rel", "f8", 3), ("info", "f8", 6)], align=True)
 PG_RESULT_DTYPE = np.dtype([("cost_initial", "f8"), ("cost_final", "f8"), ("iterations", "i4"), ("cg_iterations", "i4"),
                             ("converged", "i4"), ("status", "i4")], align=True)
+PG_ROBUST_RESULT_DTYPE = np.dtype([("pg", PG_RESULT_DTYPE), ("mu0", "f8"), ("levels", "i4"), ("n_robust", "i4"), ("n_rejected", "i4"),
+                                   ("pad", "i4")], align=True)
 
 
 class MapInfo(C.Structure):
@@ -325,6 +332,9 @@ PROTOTYPES = {
     "ndt_pg_info_from_cov": [_vp, _d, _vp],
     "ndt_pg_optimize_batch_dev": [_vp, _vp, _vp, _vp, _vp, _i, _P(PgParams), _vp, _vp],
     "ndt_pg_optimize_batch": [_vp, _vp, _vp, _vp, _vp, _i, _P(PgParams), _vp],
+    "ndt_pg_robust_default_params": [_P(PgRobustParams)],
+    "ndt_pg_optimize_robust_batch_dev": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _P(PgRobustParams), _vp, _vp, _vp, _vp],
+    "ndt_pg_optimize_robust_batch": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _P(PgRobustParams), _vp, _vp, _vp],
     "ndt_repose_points_dev": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp],
     "ndt_repose_points": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz],
     "ndt_sessions_trajectory": [_vp, _i, _vp, _sz, _P(_sz), _vp, _vp, _P(_i), _P(_sz)],
@@ -553,6 +563,12 @@ def default_pg_params(**kw):
     return _defaults(PgParams, "ndt_pg_default_params", kw)
 
 
+def default_pg_robust_params(**kw):
+    """ndt_pg_robust_default_params; mu0, factor, eps_level and level_iter by keyword, pg_<field> reaches the nested
+    ndt_pg_params (pg_max_iter=50)."""
+    return _defaults(PgRobustParams, "ndt_pg_robust_default_params", kw, nested=("pg",))
+
+
 def default_loop_params(**kw):
     """ndt_loop_default_params, fields overridden by keyword (info: six numbers)."""
     info = kw.pop("info", None)
@@ -689,6 +705,44 @@ def optimize_pose_graphs_dev(ctx, poses_ptr, node_offsets, edges_ptr, edge_offse
     prm = params if params is not None else default_pg_params()
     ctx.check(lib().ndt_pg_optimize_batch_dev(ctx.h, poses_ptr, no.ctypes.data, edges_ptr, eo.ctypes.data, len(no) - 1, C.byref(prm),
                                               out_ptr, stream), "ndt_pg_optimize_batch_dev")
+
+
+def optimize_pose_graphs_robust(ctx, poses, node_offsets, edges, edge_offsets, phi=None, params=None):
+    """ndt_pg_optimize_robust_batch: optimize_pose_graphs with a robust cost on the arcs whose `phi` (one float64 per arc, None:
+    no robust arc) is above 0 -> (new poses, one PG_ROBUST_RESULT_DTYPE record per graph, every arc's weight at mu = 1 at the
+    final poses, every arc's chi-square there).  A robust arc is rejected when its chi2 is above its phi (weight below 1/4)."""
+    out = np.array(poses, dtype=np.float64, order="C").reshape(-1, 3)
+    edges = np.ascontiguousarray(edges, dtype=PG_EDGE_DTYPE)
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    G = len(no) - 1
+    if len(eo) != len(no):
+        raise ValueError("node_offsets and edge_offsets need one entry per graph, plus one")
+    if phi is not None:
+        phi = np.ascontiguousarray(phi, dtype=np.float64).reshape(-1)
+        if len(phi) != len(edges):
+            raise ValueError("phi needs one entry per arc")
+    pad_p = out if out.size else np.zeros((1, 3), dtype=np.float64)            # (an address for a batch without nodes)
+    pad_e = edges if edges.size else np.zeros(1, dtype=PG_EDGE_DTYPE)
+    res = np.zeros(max(G, 1), dtype=PG_ROBUST_RESULT_DTYPE)
+    w, c = np.zeros(max(len(edges), 1), dtype=np.float64), np.zeros(max(len(edges), 1), dtype=np.float64)
+    prm = params if params is not None else default_pg_robust_params()
+    ctx.check(lib().ndt_pg_optimize_robust_batch(ctx.h, pad_p.ctypes.data, no.ctypes.data, pad_e.ctypes.data, eo.ctypes.data, G,
+                                                 phi.ctypes.data if phi is not None and len(phi) else None, C.byref(prm),
+                                                 res.ctypes.data, w.ctypes.data, c.ctypes.data), "ndt_pg_optimize_robust_batch")
+    return out, res[:G], w[:len(edges)], c[:len(edges)]
+
+
+def optimize_pose_graphs_robust_dev(ctx, poses_ptr, node_offsets, edges_ptr, edge_offsets, out_ptr, phi_ptr=None, weight_ptr=None,
+                                    chi2_ptr=None, params=None, stream=None):
+    """ndt_pg_optimize_robust_batch_dev: device addresses of poses, arcs, records and (each or None) phi, weights and chi2; HOST
+    offset arrays; asynchronous on `stream`."""
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    prm = params if params is not None else default_pg_robust_params()
+    ctx.check(lib().ndt_pg_optimize_robust_batch_dev(ctx.h, poses_ptr, no.ctypes.data, edges_ptr, eo.ctypes.data, len(no) - 1, phi_ptr,
+                                                     C.byref(prm), out_ptr, weight_ptr, chi2_ptr, stream),
+              "ndt_pg_optimize_robust_batch_dev")
 
 
 def repose_points(ctx, xy, seg_offsets, old_poses, new_poses, out=None):

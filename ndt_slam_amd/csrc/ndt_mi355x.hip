@@ -4030,9 +4030,20 @@ int pg_check(ndt_ctx *ctx, const void *poses, const uint64_t *node_off, const vo
   return NDT_OK;
 }
 
-// The table and the launch on st, inside the caller's frame (d_pg, pg_tab).  node_off / edge_off index poses / edges as given.
+// The robust form's own refusals, behind pg_check on params->pg.
+int pg_robust_check(ndt_ctx *ctx, const ndt_pg_robust_params *rp, const char *fn) {
+  if (!((rp->mu0 == 0.0) || (rp->mu0 >= 1.0 && rp->mu0 <= kPgMuMax)) || !(rp->factor >= 1.05) || !(rp->factor <= 1e6) ||
+      !(rp->eps_level >= 0.0) || !(rp->eps_level <= DBL_MAX) || rp->level_iter < 1 || rp->level_iter > 10000)
+    return fail(ctx, NDT_E_ARG, std::string(fn) + ": robust parameters out of range");
+  return NDT_OK;
+}
+
+// The table and the launch on st, inside the caller's frame (d_pg, pg_tab).  node_off / edge_off index poses / edges as given
+// (and phi, weight_out, chi2_out as edges).  rp == NULL: the plain form, out holds ndt_pg_result; else the robust one, out
+// holds ndt_pg_robust_result.
 int queue_pg(ndt_ctx *ctx, hipStream_t st, double *poses, const uint64_t *node_off, const ndt_pg_edge *edges, const uint64_t *edge_off,
-             int G, const ndt_pg_params *prm, ndt_pg_result *out) {
+             int G, const ndt_pg_params *prm, void *out, const ndt_pg_robust_params *rp = nullptr, const double *phi = nullptr,
+             double *weight_out = nullptr, double *chi2_out = nullptr) {
   Regions R;
   const size_t o_tab = R.take((size_t)G * sizeof(PgRow), 256);
   int rc;
@@ -4052,8 +4063,16 @@ int queue_pg(ndt_ctx *ctx, hipStream_t st, double *poses, const uint64_t *node_o
   PgParams P{};
   P.max_iter = prm->max_iter; P.cg_max_iter = prm->cg_max_iter; P.max_halvings = prm->max_halvings;
   P.eps_step = prm->eps_step; P.cg_rtol = prm->cg_rtol;
-  pg_solve_kernel<<<dim3((unsigned)std::min(G, 1 << 20)), dim3(kPgThreads), 0, st>>>(poses, edges, reinterpret_cast<const PgRow *>(ctx->d_pg.p + o_tab), G,
-                                                                                    P, ctx->d_pg.p, out);
+  const PgRow *d_rows = reinterpret_cast<const PgRow *>(ctx->d_pg.p + o_tab);
+  const dim3 grid((unsigned)std::min(G, 1 << 20));
+  if (!rp) {
+    pg_solve_kernel<false><<<grid, dim3(kPgThreads), 0, st>>>(poses, edges, d_rows, G, P, ctx->d_pg.p, static_cast<ndt_pg_result *>(out));
+  } else {
+    PgExtra<true> X{};
+    X.RP.mu0 = rp->mu0; X.RP.factor = rp->factor; X.RP.eps_level = rp->eps_level; X.RP.level_iter = rp->level_iter;
+    X.phi = phi; X.weight_out = weight_out; X.chi2_out = chi2_out;
+    pg_solve_kernel<true><<<grid, dim3(kPgThreads), 0, st>>>(poses, edges, d_rows, G, P, ctx->d_pg.p, static_cast<ndt_pg_robust_result *>(out), X);
+  }
   HIP_TRY(ctx, hipGetLastError());
   return NDT_OK;
 }
@@ -4176,6 +4195,61 @@ int ndt_pg_optimize_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node
     return rc;
   if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, G * sizeof(ndt_pg_result), hipMemcpyDeviceToHost, st));
+  return fr.close_and_wait();
+}
+
+int ndt_pg_robust_default_params(ndt_pg_robust_params *p) {
+  if (!p) return NDT_E_ARG;
+  ndt_pg_default_params(&p->pg);
+  p->pg.max_iter = 200;
+  p->mu0 = 0.0; p->factor = 1.4; p->eps_level = 1e-3; p->level_iter = 3;
+  return NDT_OK;
+}
+
+int ndt_pg_optimize_robust_batch_dev(ndt_ctx *ctx, double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                                     const uint64_t *edge_offsets_host, int n_graphs, const double *phi_dev,
+                                     const ndt_pg_robust_params *params, ndt_pg_robust_result *out_dev, double *weight_out_dev,
+                                     double *chi2_out_dev, void *stream) {
+  const char *fn = "ndt_pg_optimize_robust_batch_dev";
+  int rc = pg_check(ctx, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, params ? &params->pg : nullptr, out_dev, fn);
+  if (rc || (rc = pg_robust_check(ctx, params, fn))) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_pg(ctx, st, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, &params->pg, out_dev, params, phi_dev,
+                    weight_out_dev, chi2_out_dev);
+  });
+}
+
+int ndt_pg_optimize_robust_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                                 const uint64_t *edge_offsets_host, int n_graphs, const double *phi_host,
+                                 const ndt_pg_robust_params *params, ndt_pg_robust_result *out_host, double *weight_out_host,
+                                 double *chi2_out_host) {
+  const char *fn = "ndt_pg_optimize_robust_batch";
+  int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params ? &params->pg : nullptr, out_host, fn);
+  if (rc || (rc = pg_robust_check(ctx, params, fn))) return rc;
+  const size_t G = (size_t)n_graphs;
+  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
+  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
+  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions U;
+  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256),
+               o_res = U.take(G * sizeof(ndt_pg_robust_result), 256), o_phi = U.take(ne * 8 + 8, 256), o_w = U.take(ne * 8 + 8, 256),
+               o_c = U.take(ne * 8 + 8, 256);
+  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+  unsigned char *d = ctx->d_scan.p;
+  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
+  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
+  if (ne && phi_host) HIP_TRY(ctx, hipMemcpyAsync(d + o_phi, phi_host + e0, ne * 8, hipMemcpyHostToDevice, st));
+  if ((rc = queue_pg(ctx, st, (double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs, &params->pg,
+                     d + o_res, params, phi_host ? (const double *)(d + o_phi) : nullptr, weight_out_host ? (double *)(d + o_w) : nullptr,
+                     chi2_out_host ? (double *)(d + o_c) : nullptr)))
+    return rc;
+  if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, G * sizeof(ndt_pg_robust_result), hipMemcpyDeviceToHost, st));
+  if (ne && weight_out_host) HIP_TRY(ctx, hipMemcpyAsync(weight_out_host + e0, d + o_w, ne * 8, hipMemcpyDeviceToHost, st));
+  if (ne && chi2_out_host) HIP_TRY(ctx, hipMemcpyAsync(chi2_out_host + e0, d + o_c, ne * 8, hipMemcpyDeviceToHost, st));
   return fr.close_and_wait();
 }
 

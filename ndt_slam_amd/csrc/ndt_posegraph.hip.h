@@ -21,8 +21,12 @@ struct PgRow {
 static_assert(sizeof(PgRow) == 40, "one 40-byte row per graph");
 
 struct PgParams { int max_iter, cg_max_iter, max_halvings, pad; double eps_step, cg_rtol; };
+// The level schedule of the robust form (ndt_pg_robust_params without its pg part); unread by the plain one.
+struct PgRobust { double mu0, factor, eps_level; int level_iter, pad; };
+constexpr double kPgMuMax = 1e12;
 
 // An arc linearised at the current poses: cos / sin of the `from` heading, d r_xy / d theta_from = (a, b), the residual.
+// pad: the robust form keeps the arc's weight at those poses there (1.0 for a plain arc); the plain form leaves it 0 and unread.
 struct PgLin { double c, s, a, b, r0, r1, r2, pad; };
 
 // The regions of one graph's scratch, in doubles from its start (host and device agree by calling this one function).
@@ -119,27 +123,49 @@ __device__ __forceinline__ void pg_j_mul(const double J[9], const double v[3], d
   out[1] = J[3] * v[0] + J[4] * v[1] + J[5] * v[2];
   out[2] = J[6] * v[0] + J[7] * v[1] + J[8] * v[2];
 }
-// M += Ja^T Omega Jb (row-major 3 x 3)
-__device__ __forceinline__ void pg_block_add(const double Ja[9], const double *__restrict__ I, const double Jb[9], double M[9]) {
+// M += Ja^T Omega Jb (row-major 3 x 3); ROBUST: M += wt Ja^T Omega Jb, and a wt of exactly 1.0 adds the same bits
+template <bool ROBUST>
+__device__ __forceinline__ void pg_block_add(const double Ja[9], const double *__restrict__ I, const double Jb[9], double wt, double M[9]) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double v[3] = {Jb[c], Jb[3 + c], Jb[6 + c]};
     double w[3], o[3];
     pg_info_mul(I, v, w);
     pg_jt_mul(Ja, w, o);
-    M[c] += o[0]; M[3 + c] += o[1]; M[6 + c] += o[2];
+    if constexpr (ROBUST) { M[c] += wt * o[0]; M[3 + c] += wt * o[1]; M[6 + c] += wt * o[2]; }
+    else { M[c] += o[0]; M[3 + c] += o[1]; M[6 + c] += o[2]; }
   }
 }
 
-// F = sum r^T Omega r at the poses X: each thread its arcs in index order, then the fixed block sum.
-__device__ double pg_cost(const double *__restrict__ X, const ndt_pg_edge *__restrict__ ed, int m, double *s_w) {
+// c = r^T Omega r of a linearised arc
+__device__ __forceinline__ double pg_chi2(const PgLin &l, const double *__restrict__ I) {
+  const double r[3] = {l.r0, l.r1, l.r2};
+  double w[3];
+  pg_info_mul(I, r, w);
+  return (r[0] * w[0] + r[1] * w[1]) + r[2] * w[2];
+}
+// Geman-McClure at sigma = mu phi, written with q = c / sigma so that a huge sigma gives the plain arc and not inf / inf:
+// rho = sigma c / (sigma + c) = c / (1 + q), w = (sigma / (sigma + c))^2 = (1 / (1 + q))^2
+__device__ __forceinline__ double pg_rho(double c, double sigma) { return c / (1.0 + c / sigma); }
+__device__ __forceinline__ double pg_weight(double c, double sigma) { const double t = 1.0 / (1.0 + c / sigma); return t * t; }
+
+// F = sum r^T Omega r at the poses X: each thread its arcs in index order, then the fixed block sum.  ROBUST: F_mu, an arc with
+// phi[e] > 0 adds rho at sigma = mu phi[e] in place of c (phi: the graph's own, or NULL for none).
+template <bool ROBUST>
+__device__ double pg_cost(const double *__restrict__ X, const ndt_pg_edge *__restrict__ ed, int m, double *s_w, const double *__restrict__ phi,
+                          double mu) {
   double acc = 0.0;
   for (int e = (int)threadIdx.x; e < m; e += kPgThreads) {
     const PgLin l = pg_linearise(X, ed[e]);
     const double r[3] = {l.r0, l.r1, l.r2};
     double w[3];
     pg_info_mul(ed[e].info, r, w);
-    acc += (r[0] * w[0] + r[1] * w[1]) + r[2] * w[2];
+    if constexpr (ROBUST) {
+      const double c = (r[0] * w[0] + r[1] * w[1]) + r[2] * w[2], ph = phi ? phi[e] : 0.0;
+      acc += ph > 0.0 ? pg_rho(c, mu * ph) : c;
+    } else {
+      acc += (r[0] * w[0] + r[1] * w[1]) + r[2] * w[2];
+    }
   }
   return pg_block_sum(acc, s_w);
 }
@@ -288,10 +314,26 @@ __device__ void pg_apply(const double *__restrict__ L, const double *__restrict_
   }
 }
 
-// All Gauss-Newton iterations of every graph of the call: workgroup w takes the graphs w, w + gridDim.x, ...
+// What the robust form's launch carries beside the plain one's arguments, and the record either form writes.
+template <bool ROBUST> struct PgExtra;
+template <> struct PgExtra<false> { typedef ndt_pg_result Record; };
+template <> struct PgExtra<true> {
+  typedef ndt_pg_robust_result Record;
+  PgRobust RP;
+  const double *phi;                               // indexed like edges, as the two outputs; each may be NULL
+  double *weight_out, *chi2_out;
+};
+
+// All Gauss-Newton iterations of every graph of the call: workgroup w takes the graphs w, w + gridDim.x, ...  One body for both
+// forms.  ROBUST = false is ndt_pg_optimize_batch: no extra argument, X is empty and out holds ndt_pg_result.  ROBUST = true is
+// ndt_pg_optimize_robust_batch (graduated non-convexity, the header's contract): out holds ndt_pg_robust_result.  Every level decision is taken from
+// block sums and maxima, which every thread holds with the same bits: control flow stays uniform around the barriers.
+template <bool ROBUST, typename... Extra>
 __global__ void __launch_bounds__(kPgThreads)
 pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edges, const PgRow *__restrict__ rows, int n_graphs,
-                PgParams P, unsigned char *__restrict__ scratch, ndt_pg_result *__restrict__ out) {
+                PgParams P, unsigned char *__restrict__ scratch, typename PgExtra<ROBUST>::Record *__restrict__ out, Extra... extra) {
+  static_assert(sizeof...(Extra) == (ROBUST ? 1 : 0), "the robust form takes one PgExtra<true>, the plain form nothing");
+  const PgExtra<ROBUST> X{extra...};                 // (the plain form's argument list is ndt_pg_optimize_batch's own, unchanged)
   __shared__ double sh[kPgChunk * 30];
   __shared__ double s_w[4];
   __shared__ int s_ok;
@@ -301,6 +343,9 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
     const int n = R.n, m = R.m;
     double *pose = poses + 3 * R.node0;
     const ndt_pg_edge *ed = edges + R.edge0;
+    const double *gphi = nullptr;                              // the graph's own phi, as ed its arcs
+    double *weight_out = nullptr, *chi2_out = nullptr;
+    if constexpr (ROBUST) { gphi = X.phi ? X.phi + R.edge0 : nullptr; weight_out = X.weight_out; chi2_out = X.chi2_out; }
     // ---- the graph's own faults: found here, the poses stay as they are ----
     int bad = 0;
     for (int i = tid; i < n; i += kPgThreads)
@@ -315,10 +360,24 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
       const double m2 = I[0] * I[3] - I[1] * I[1];
       const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
       if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
+      if constexpr (ROBUST)
+        if (gphi && (!(gphi[e] >= 0.0) || !pg_finite(gphi[e]))) bad = 1;
     }
     bad = __syncthreads_or(bad);
     if (bad || m == 0) {
-      if (tid == 0) {
+      if constexpr (ROBUST) {
+        for (int e = tid; e < m; e += kPgThreads) {            // (a faulted graph's arc outputs are 0)
+          if (weight_out) weight_out[R.edge0 + e] = 0.0;
+          if (chi2_out) chi2_out[R.edge0 + e] = 0.0;
+        }
+        if (tid == 0) {
+          ndt_pg_robust_result res;
+          res.pg.cost_initial = 0.0; res.pg.cost_final = 0.0; res.pg.iterations = 0; res.pg.cg_iterations = 0;
+          res.pg.converged = bad ? 0 : 1; res.pg.status = bad ? NDT_E_ARG : NDT_OK;
+          res.mu0 = bad ? 0.0 : 1.0; res.levels = bad ? 0 : 1; res.n_robust = 0; res.n_rejected = 0; res.pad = 0;
+          out[gi] = res;
+        }
+      } else if (tid == 0) {
         ndt_pg_result res;
         res.cost_initial = 0.0; res.cost_final = 0.0; res.iterations = 0; res.cg_iterations = 0;
         res.converged = bad ? 0 : 1; res.status = bad ? NDT_E_ARG : NDT_OK;
@@ -364,13 +423,37 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
     }
     if (tid < 3) { g[tid] = 0.0; dl[tid] = 0.0; r[tid] = 0.0; z[tid] = 0.0; p[tid] = 0.0; q[tid] = 0.0; y[tid] = 0.0; }
     __syncthreads();
-    double F = pg_cost(x, ed, m, s_w);
+    // ---- the robust form's start: the robust arcs counted, mu0 = max(1, 2 max c_e / phi_e) over them unless it is given ----
+    double mu = 1.0, mu_start = 1.0;
+    int levels = 1, in_level = 0, n_robust = 0;
+    if constexpr (ROBUST) {
+      double cnt = 0.0, mx = 0.0;
+      if (gphi)
+        for (int e = tid; e < m; e += kPgThreads) {
+          const double ph = gphi[e];
+          if (ph > 0.0) { cnt += 1.0; mx = fmax(mx, pg_chi2(pg_linearise(x, ed[e]), ed[e].info) / ph); }
+        }
+      n_robust = (int)pg_block_sum(cnt, s_w);                    // (a sum of small whole numbers: exact in any order)
+      mx = pg_block_max(mx, s_w);
+      if (n_robust > 0) mu_start = X.RP.mu0 != 0.0 ? X.RP.mu0 : fmin(kPgMuMax, fmax(1.0, 2.0 * mx));
+      mu = mu_start;
+    }
+    double F = pg_cost<ROBUST>(x, ed, m, s_w, gphi, 1.0);
     const double F0 = F;
+    if constexpr (ROBUST)
+      if (mu > 1.0) F = pg_cost<true>(x, ed, m, s_w, gphi, mu);
     int iters = 0, cg_total = 0, conv = 0;
     const int cg_cap = P.cg_max_iter > 0 ? P.cg_max_iter : 6 * n;
     for (int it = 0; it < P.max_iter; ++it) {
       // ---- linearise: the arcs, then every node's gradient, diagonal block and chain block ----
-      for (int e = tid; e < m; e += kPgThreads) lin[e] = pg_linearise(x, ed[e]);
+      for (int e = tid; e < m; e += kPgThreads) {
+        PgLin l = pg_linearise(x, ed[e]);
+        if constexpr (ROBUST) {
+          const double ph = gphi ? gphi[e] : 0.0;
+          l.pad = ph > 0.0 ? pg_weight(pg_chi2(l, ed[e].info), mu * ph) : 1.0;
+        }
+        lin[e] = l;
+      }
       __syncthreads();
       for (int i = 1 + tid; i < n; i += kPgThreads) {
         double gi3[3] = {0, 0, 0}, Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -385,9 +468,10 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
           const double rr[3] = {l.r0, l.r1, l.r2};
           pg_info_mul(I, rr, w);
           pg_jt_mul(Js, w, o);
-          gi3[0] += o[0]; gi3[1] += o[1]; gi3[2] += o[2];
-          pg_block_add(Js, I, Js, Dm);
-          if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add(Js, I, Jo, Um); }
+          if constexpr (ROBUST) { gi3[0] += l.pad * o[0]; gi3[1] += l.pad * o[1]; gi3[2] += l.pad * o[2]; }
+          else { gi3[0] += o[0]; gi3[1] += o[1]; gi3[2] += o[2]; }
+          pg_block_add<ROBUST>(Js, I, Js, l.pad, Dm);
+          if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add<ROBUST>(Js, I, Jo, l.pad, Um); }
         }
         for (int k = 0; k < 3; ++k) { g[3 * (size_t)i + k] = gi3[k]; dl[3 * (size_t)i + k] = 0.0; r[3 * (size_t)i + k] = -gi3[k]; }
         double *d = D + 6 * (size_t)i;
@@ -423,7 +507,8 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
               const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
               pg_info_mul(ed[e].info, u, w);
               pg_jt_mul(Js, w, o);
-              qi[0] += o[0]; qi[1] += o[1]; qi[2] += o[2];
+              if constexpr (ROBUST) { qi[0] += l.pad * o[0]; qi[1] += l.pad * o[1]; qi[2] += l.pad * o[2]; }
+              else { qi[0] += o[0]; qi[1] += o[1]; qi[2] += o[2]; }
             }
             for (int c = 0; c < 3; ++c) { q[3 * (size_t)i + c] = qi[c]; acc += pi3[c] * qi[c]; }
           }
@@ -461,10 +546,32 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
         for (int i = tid; i < n; i += kPgThreads)
           for (int c = 0; c < 3; ++c) xt[3 * (size_t)i + c] = x[3 * (size_t)i + c] + s * dl[3 * (size_t)i + c];
         __syncthreads();
-        Ft = pg_cost(xt, ed, m, s_w);
+        Ft = pg_cost<ROBUST>(xt, ed, m, s_w, gphi, mu);
         if (pg_finite(Ft) && Ft <= F) { accepted = true; break; }
       }
       dmax *= s;                                                 // the step taken, or the last one tried
+      if constexpr (ROBUST)
+        if (mu > 1.0) {
+          // a level above 1 never ends the run: it ends on a short accepted step, on level_iter of them, or where the halving
+          // runs out; the next level starts from the same poses with F evaluated again at its own mu
+          bool end_level = true;
+          if (accepted) {
+            for (int i = 1 + tid; i < n; i += kPgThreads)
+              for (int c = 0; c < 3; ++c) x[3 * (size_t)i + c] = xt[3 * (size_t)i + c];
+            __syncthreads();
+            F = Ft;
+            iters++;
+            in_level++;
+            end_level = dmax < X.RP.eps_level || in_level >= X.RP.level_iter;
+          }
+          if (end_level) {
+            mu = fmax(1.0, mu / X.RP.factor);
+            levels++;
+            in_level = 0;
+            F = pg_cost<true>(x, ed, m, s_w, gphi, mu);
+          }
+          continue;
+        }
       if (!accepted) {
         // the halving ran out below eps_step: halving on could only give a step that is shorter still -- the poses stay
         if (pg_finite(dmax) && dmax < P.eps_step) conv = 1;
@@ -484,7 +591,25 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
         pose[3 * (size_t)i] = x[3 * (size_t)i]; pose[3 * (size_t)i + 1] = x[3 * (size_t)i + 1];
         pose[3 * (size_t)i + 2] = pg_wrap_deg(x[3 * (size_t)i + 2] * (180.0 / kPgPi));
       }
-    if (tid == 0) {
+    if constexpr (ROBUST) {
+      // ---- the final pass: every arc's c and weight at mu = 1 at the last poses, the rejected arcs counted, F_1 there ----
+      double cnt = 0.0;
+      for (int e = tid; e < m; e += kPgThreads) {
+        const double c = pg_chi2(pg_linearise(x, ed[e]), ed[e].info), ph = gphi ? gphi[e] : 0.0;
+        if (ph > 0.0 && c > ph) cnt += 1.0;
+        if (weight_out) weight_out[R.edge0 + e] = ph > 0.0 ? pg_weight(c, ph) : 1.0;
+        if (chi2_out) chi2_out[R.edge0 + e] = c;
+      }
+      const int n_rejected = (int)pg_block_sum(cnt, s_w);
+      if (mu > 1.0) F = pg_cost<true>(x, ed, m, s_w, gphi, 1.0);     // (the run ended inside a level)
+      if (tid == 0) {
+        ndt_pg_robust_result res;
+        res.pg.cost_initial = F0; res.pg.cost_final = F; res.pg.iterations = iters; res.pg.cg_iterations = cg_total; res.pg.converged = conv;
+        res.pg.status = NDT_OK;
+        res.mu0 = mu_start; res.levels = levels; res.n_robust = n_robust; res.n_rejected = n_rejected; res.pad = 0;
+        out[gi] = res;
+      }
+    } else if (tid == 0) {
       ndt_pg_result res;
       res.cost_initial = F0; res.cost_final = F; res.iterations = iters; res.cg_iterations = cg_total; res.converged = conv; res.status = NDT_OK;
       out[gi] = res;

@@ -667,17 +667,57 @@ def load_occupancy(stem):
 # capi.LoopMultiParams: the search is then sessions.find_loops_multi with it (several old submaps per session, accepted on
 # ranged fitness; its `loop` part replaces `loop`) and every edge found for a session goes into that session's one graph,
 # cross = None or a capi.LoopMultiParams: behind the closing inside the sessions comes one sessions.find_cross_loops with it
-# (the sessions must share a map frame), one joint graph per group of sessions that its edges tie together, and one correct()
+# (the sessions must share a map frame), one joint graph per group of sessions that its edges tie together, and one correct(),
+# robust = None or an object with `params` (a capi.PgRobustParams, None: the defaults) and `phi` (the chi-square beyond which a
+# loop or cross arc counts as rejected): the graphs then go through capi.optimize_pose_graphs_robust with phi on the loop and
+# cross arcs and 0 on the odometry arcs, `pg` is not used, and a graph's sessions are corrected only when robust_keep says so
 class LoopClosure(collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")):
     """The five fields above as a tuple, as before (its _fields, its length and its unpacking are unchanged), and the
-    attributes remake_closed (default False), multi (default None) and cross (default None) beside them."""
+    attributes remake_closed (default False), multi (default None), cross (default None) and robust (default None) beside
+    them."""
 
-    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None, cross=None):
+    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None, cross=None, robust=None):
         self = super().__new__(cls, loop, pg, odo_info, every, cooldown)
         self.remake_closed = bool(remake_closed)
         self.multi = multi
         self.cross = cross
+        self.robust = robust
         return self
+
+
+RobustClosure = collections.namedtuple("RobustClosure", "params phi")      # what LoopClosure.robust is set to
+
+
+def robust_keep(records, chi2, phi, edge_offsets):
+    """Which graphs of a robust batch may correct their sessions (host only): graph g when its record ends with status 0 and
+    converged and at least one of its robust arcs (phi > 0) is kept, that is has chi2 <= phi.  records: PG_ROBUST_RESULT_DTYPE
+    (or anything with ["pg"]["status"] and ["pg"]["converged"] per graph); chi2 and phi one number per arc; edge_offsets the
+    batch's.  -> a bool array, one per graph."""
+    chi2, phi = np.asarray(chi2, dtype=np.float64).reshape(-1), np.asarray(phi, dtype=np.float64).reshape(-1)
+    if len(chi2) != len(phi) or len(edge_offsets) != len(records) + 1:
+        raise ValueError("robust_keep needs one chi2 and one phi per arc and one more edge offset than graphs")
+    keep = np.zeros(len(records), dtype=bool)
+    for g in range(len(records)):
+        a, b = int(edge_offsets[g]), int(edge_offsets[g + 1])
+        kept = (phi[a:b] > 0) & (chi2[a:b] <= phi[a:b])
+        keep[g] = int(records[g]["pg"]["status"]) == 0 and bool(records[g]["pg"]["converged"]) and bool(kept.any())
+    return keep
+
+
+def _optimize_closing(ctx, lc, poses, node_offsets, edges, edge_offsets, n_loop_arcs):
+    """The batch of a closing through the optimiser lc asks for -> (new poses, one flag per graph: correct its sessions).
+    n_loop_arcs[g]: the loop or cross arcs of graph g, which lie at the END of its arc list (loops_graph, cross_graph without
+    loops inside the trajectories)."""
+    from . import capi
+    robust = getattr(lc, "robust", None)
+    if robust is None:
+        new, res = capi.optimize_pose_graphs(ctx, poses, node_offsets, edges, edge_offsets, lc.pg)
+        return new, np.array([r["status"] == 0 and bool(r["converged"]) for r in res], dtype=bool)
+    phi = np.zeros(len(edges), dtype=np.float64)
+    for g, k in enumerate(n_loop_arcs):
+        phi[int(edge_offsets[g + 1]) - k:int(edge_offsets[g + 1])] = float(robust.phi)
+    new, res, _, chi2 = capi.optimize_pose_graphs_robust(ctx, poses, node_offsets, edges, edge_offsets, phi, robust.params)
+    return new, robust_keep(res, chi2, phi, edge_offsets)
 
 
 def closed_scan_ranges(sub_first, n_closed):
@@ -774,19 +814,19 @@ def _close_cross(ctx, sessions, lc, which):
     groups = collections.OrderedDict()
     for i in sorted({int(l["map_session"]) for l in found} | {int(l["m"]["loop"]["cand"]["session"]) for l in found}):
         groups.setdefault(find(i), []).append(i)
-    nodes, arcs, noff, eoff, offsets = [], [], [0], [0], []
+    nodes, arcs, noff, eoff, offsets, n_cross = [], [], [0], [0], [], []
     for members in groups.values():
         place = {i: k for k, i in enumerate(members)}
         cross = [(place[int(l["map_session"])], place[int(l["m"]["loop"]["cand"]["session"])], l["m"]["loop"]["edge"])
                  for l in found if int(l["map_session"]) in place]
         n, e, off = cross_graph([sessions.trajectory(i)[0] for i in members], [[] for _ in members], cross, lc.odo_info)
-        nodes.append(n); arcs.append(e); offsets.append(off)
+        nodes.append(n); arcs.append(e); offsets.append(off); n_cross.append(len(cross))
         noff.append(noff[-1] + len(n)); eoff.append(eoff[-1] + len(e))
-    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(nodes), np.array(noff, dtype=np.uint64), np.concatenate(arcs),
-                                         np.array(eoff, dtype=np.uint64), lc.pg)
+    new, good = _optimize_closing(ctx, lc, np.concatenate(nodes), np.array(noff, dtype=np.uint64), np.concatenate(arcs),
+                                  np.array(eoff, dtype=np.uint64), n_cross)
     fix = {}
     for g, members in enumerate(groups.values()):
-        if res[g]["status"] == 0 and res[g]["converged"]:
+        if good[g]:
             for k, i in enumerate(members):
                 fix[i] = new[noff[g] + int(offsets[g][k]):noff[g] + int(offsets[g][k + 1])]
     if fix:
@@ -814,8 +854,8 @@ def _close_loops(ctx, sessions, lc, which):
     graphs = [loops_graph(t, by_session[i], lc.odo_info) for t, i in zip(trajs, who)]
     off = np.concatenate([[0], np.cumsum([len(t) for t in trajs])]).astype(np.uint64)
     eoff = np.concatenate([[0], np.cumsum([len(g) for g in graphs])]).astype(np.uint64)
-    new, res = capi.optimize_pose_graphs(ctx, np.concatenate(trajs), off, np.concatenate(graphs), eoff, lc.pg)
-    fix = {i: new[int(off[g]):int(off[g + 1])] for g, i in enumerate(who) if res[g]["status"] == 0 and res[g]["converged"]}
+    new, good = _optimize_closing(ctx, lc, np.concatenate(trajs), off, np.concatenate(graphs), eoff, [len(by_session[i]) for i in who])
+    fix = {i: new[int(off[g]):int(off[g + 1])] for g, i in enumerate(who) if good[g]}
     if fix:
         for i in sessions.correct(fix):
             corrected[i] = 1
