@@ -1046,6 +1046,68 @@ int ndt_pg_optimize_robust_batch(ndt_ctx *ctx, double *poses_host, const uint64_
                                  const uint64_t *edge_offsets_host, int n_graphs, const double *phi_host,
                                  const ndt_pg_robust_params *params, ndt_pg_robust_result *out_host, double *weight_out_host,
                                  double *chi2_out_host);
+/* ---- Pose covariances from the pose graph: blocks of H^-1, and the consistency of a candidate loop arc ----
+ * The optimisers above return poses and chi-squares; these calls answer how well pose b is known relative to pose a, and
+ * whether a candidate loop arc agrees with the odometry in between -- a Mahalanobis distance on that answer, which needs no
+ * true loop beside a false one and so belongs in front of ndt_pg_optimize_robust_batch.
+ *
+ * Model.  H = sum_e w_e J_e^T Omega_e J_e at the poses GIVEN (no step is taken, the poses are only read), node 0's rows and
+ * columns removed, exactly as ndt_pg_optimize_robust_batch forms it; Sigma = H^-1 is the covariance relative to node 0, in
+ * (m, m, rad).  weight (one double per arc, indexed like edges) may be NULL: every w_e = 1, and the result is byte-identical
+ * to passing an array of 1.0.  It is meant to take weight_out of the robust call, so that a rejected arc does not count;
+ * w_e >= 0 and finite is required, and an arc with w_e == 0 contributes nothing.
+ *
+ * Query (graph, a, b): Saa and Sbb are the diagonal blocks of the nodes a and b, each off-diagonal pair replaced by
+ * 0.5 (upper + lower); Sab[3 r + c] = Sigma[3 a + r, 3 b + c], taken from the solves of node b's unit columns.  a == b is
+ * legal: three columns are solved and Sab = Sbb = Saa.  A block that involves node 0 is exactly 0.0.
+ *
+ * Method.  For each unit column, H x = e by the conjugate gradients and the chain factor of the optimisers, to
+ * sqrt(r^T z / r0^T z0) <= cg_rtol in at most cg_max_iter iterations (0: 6 N).  Of ndt_pg_params only cg_max_iter and cg_rtol
+ * are used (the others are held to ndt_pg_optimize_batch's ranges and otherwise ignored).  The three or six columns of a query
+ * share every walk over the arcs and every sweep of the factor, each with its own step lengths and its own stop.
+ * cg_iterations is the largest count over the query's columns, converged = 1 when every column met the rule.  converged = 0
+ * gives all three blocks as 0 -- nobody gets a half-solved covariance --: the iteration cap, a pivot of T below 1e-13 of its
+ * diagonal entry (a node that nothing ties to node 0, also through arcs of weight 0), a CG breakdown.  On a graph that is a
+ * pure chain T = H and a column takes one or two iterations.
+ *
+ * status = NDT_E_ARG with everything else 0, for that query alone: a per-graph fault as ndt_pg_optimize_batch defines it, a
+ * weight of the graph that is negative or not finite, graph, a or b out of range, a graph without arcs when a or b is not 0.
+ *
+ * A column's solution is a function of (graph, weights, node, column) alone, to the last bit: not of the batch, the order of
+ * the queries, the other node of the query or the place of the column in it.  Saa of (a, b), Saa of (a, a) and Sbb of (c, a)
+ * are the same bytes.
+ *
+ * One 256-thread workgroup per query at a time, at most 1024 workgroups, one launch; the scratch is one slot per workgroup
+ * for the largest queried graph, inside the context's scratch bracket: it does not grow with n_queries beyond that.  queries
+ * and both offset arrays are HOST arrays in either form.  _dev is asynchronous on `stream` (NULL = the context's).
+ *
+ * Refusals (NDT_E_ARG, synchronous, nothing queued or written): those of ndt_pg_optimize_batch; NULL queries or out;
+ * n_queries < 1. */
+typedef struct ndt_pg_query    { int32_t graph, a, b, pad; } ndt_pg_query;
+typedef struct ndt_pg_marginal {  /* one per query; 232 bytes */
+  double Saa[9], Sab[9], Sbb[9];  /* row-major 3x3, (m, m, rad) */
+  int cg_iterations, converged, status, pad;
+} ndt_pg_marginal;
+/* Device poses, arcs, weights (may be NULL) and records; HOST offsets and queries. */
+int ndt_pg_marginals_batch_dev(ndt_ctx *ctx, const double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                               const uint64_t *edge_offsets_host, int n_graphs, const double *weight_dev,
+                               const ndt_pg_query *queries_host, int n_queries, const ndt_pg_params *params,
+                               ndt_pg_marginal *out_dev, void *stream);
+/* The same from host memory; synchronous. */
+int ndt_pg_marginals_batch(ndt_ctx *ctx, const double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                           const uint64_t *edge_offsets_host, int n_graphs, const double *weight_host,
+                           const ndt_pg_query *queries_host, int n_queries, const ndt_pg_params *params,
+                           ndt_pg_marginal *out_host);
+/* Host helper, no context: the first-order covariance of "b in a's frame" (the arc residual's own variable), row-major 3 x 3 in
+ * (m, m, rad): C = Ja Saa Ja^T + Ja Sab Jb^T + Jb Sab^T Ja^T + Jb Sbb Jb^T with Ja = d r / d x_a and Jb = d r / d x_b of the
+ * residual above at (pose_a, pose_b), poses as (tx, ty, th[deg]).  NDT_E_ARG: a NULL pointer, a non-finite number, a C that is
+ * not positive definite (Sylvester's criterion; the zero blocks of a query that did not converge end here). */
+int ndt_pg_relative_cov(const double pose_a[3], const double pose_b[3], const ndt_pg_marginal *m, double cov[9]);
+/* Host helper, no context: d2 = r^T (rel_cov + Omega^-1)^-1 r for an arc from pose_a to pose_b, r its residual at the two poses
+ * and Omega its information (edge->from and edge->to are not read); rel_cov's off-diagonal pairs are averaged.  Under the model
+ * d2 of a true arc follows chi-square with 3 degrees of freedom.  NDT_E_ARG: a NULL pointer, a non-finite number, an Omega or
+ * a rel_cov + Omega^-1 that is not positive definite. */
+int ndt_pg_edge_chi2(const double pose_a[3], const double pose_b[3], const ndt_pg_edge *edge, const double rel_cov[9], double *d2);
 /* PointCloudMap::remakeMaps' point correction (src/PointCloudMap.cpp:147-154) for clouds stored in ranges.  Segment k covers the
  * points [seg_offsets[k], seg_offsets[k + 1]) of xy (two float32 at each stride) and has the pose triples old_poses[k] and
  * new_poses[k]: q = oldPose.relativePoint(p), p' = newPose.globalPoint(q) (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat

@@ -220,6 +220,9 @@ PG_RESULT_DTYPE = np.dtype([("cost_initial", "f8"), ("cost_final", "f8"), ("iter
                             ("converged", "i4"), ("status", "i4")], align=True)
 PG_ROBUST_RESULT_DTYPE = np.dtype([("pg", PG_RESULT_DTYPE), ("mu0", "f8"), ("levels", "i4"), ("n_robust", "i4"), ("n_rejected", "i4"),
                                    ("pad", "i4")], align=True)
+PG_QUERY_DTYPE = np.dtype([("graph", "i4"), ("a", "i4"), ("b", "i4"), ("pad", "i4")], align=True)
+PG_MARGINAL_DTYPE = np.dtype([("Saa", "f8", 9), ("Sab", "f8", 9), ("Sbb", "f8", 9), ("cg_iterations", "i4"), ("converged", "i4"),
+                              ("status", "i4"), ("pad", "i4")], align=True)
 
 
 class MapInfo(C.Structure):
@@ -335,6 +338,10 @@ PROTOTYPES = {
     "ndt_pg_robust_default_params": [_P(PgRobustParams)],
     "ndt_pg_optimize_robust_batch_dev": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _P(PgRobustParams), _vp, _vp, _vp, _vp],
     "ndt_pg_optimize_robust_batch": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _P(PgRobustParams), _vp, _vp, _vp],
+    "ndt_pg_marginals_batch_dev": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _P(PgParams), _vp, _vp],
+    "ndt_pg_marginals_batch": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _P(PgParams), _vp],
+    "ndt_pg_relative_cov": [_vp, _vp, _vp, _vp],
+    "ndt_pg_edge_chi2": [_vp, _vp, _vp, _vp, _vp],
     "ndt_repose_points_dev": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp],
     "ndt_repose_points": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _sz],
     "ndt_sessions_trajectory": [_vp, _i, _vp, _sz, _P(_sz), _vp, _vp, _P(_i), _P(_sz)],
@@ -743,6 +750,76 @@ def optimize_pose_graphs_robust_dev(ctx, poses_ptr, node_offsets, edges_ptr, edg
     ctx.check(lib().ndt_pg_optimize_robust_batch_dev(ctx.h, poses_ptr, no.ctypes.data, edges_ptr, eo.ctypes.data, len(no) - 1, phi_ptr,
                                                      C.byref(prm), out_ptr, weight_ptr, chi2_ptr, stream),
               "ndt_pg_optimize_robust_batch_dev")
+
+
+def pg_queries(queries):
+    """(graph, a, b) rows, or PG_QUERY_DTYPE records -> a contiguous PG_QUERY_DTYPE array."""
+    if isinstance(queries, np.ndarray) and queries.dtype == PG_QUERY_DTYPE:
+        return np.ascontiguousarray(queries)
+    rows = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    q = np.zeros(len(rows), dtype=PG_QUERY_DTYPE)
+    q["graph"], q["a"], q["b"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return q
+
+
+def pose_graph_marginals(ctx, poses, node_offsets, edges, edge_offsets, queries, weight=None, params=None):
+    """ndt_pg_marginals_batch: blocks of the covariance H^-1 (node 0 fixed) of the graphs as optimize_pose_graphs takes them, at
+    the poses given.  queries: (graph, a, b) rows or PG_QUERY_DTYPE; weight: one float64 per arc (optimize_pose_graphs_robust's
+    weights), None: all 1 -> one PG_MARGINAL_DTYPE record per query (Saa, Sab, Sbb row-major 3 x 3 in (m, m, rad))."""
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    edges = np.ascontiguousarray(edges, dtype=PG_EDGE_DTYPE)
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    if len(eo) != len(no):
+        raise ValueError("node_offsets and edge_offsets need one entry per graph, plus one")
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        if len(weight) != len(edges):
+            raise ValueError("weight needs one entry per arc")
+    q = pg_queries(queries)
+    pad_p = poses if poses.size else np.zeros((1, 3), dtype=np.float64)        # (an address for a batch without nodes)
+    pad_e = edges if edges.size else np.zeros(1, dtype=PG_EDGE_DTYPE)
+    out = np.zeros(max(len(q), 1), dtype=PG_MARGINAL_DTYPE)
+    prm = params if params is not None else default_pg_params()
+    ctx.check(lib().ndt_pg_marginals_batch(ctx.h, pad_p.ctypes.data, no.ctypes.data, pad_e.ctypes.data, eo.ctypes.data, len(no) - 1,
+                                           weight.ctypes.data if weight is not None and len(weight) else None, _ptr(q), len(q),
+                                           C.byref(prm), out.ctypes.data), "ndt_pg_marginals_batch")
+    return out[:len(q)]
+
+
+def pose_graph_marginals_dev(ctx, poses_ptr, node_offsets, edges_ptr, edge_offsets, queries, out_ptr, weight_ptr=None, params=None,
+                             stream=None):
+    """ndt_pg_marginals_batch_dev: device addresses of poses, arcs, records and (or None) weights; HOST offsets and queries;
+    asynchronous on `stream`."""
+    no = np.ascontiguousarray(node_offsets, dtype=np.uint64)
+    eo = np.ascontiguousarray(edge_offsets, dtype=np.uint64)
+    q = pg_queries(queries)
+    prm = params if params is not None else default_pg_params()
+    ctx.check(lib().ndt_pg_marginals_batch_dev(ctx.h, poses_ptr, no.ctypes.data, edges_ptr, eo.ctypes.data, len(no) - 1, weight_ptr,
+                                               _ptr(q), len(q), C.byref(prm), out_ptr, stream), "ndt_pg_marginals_batch_dev")
+
+
+def pg_relative_cov(pose_a, pose_b, marginal):
+    """ndt_pg_relative_cov: the first-order covariance of pose_b in pose_a's frame from a query's record -> [3, 3]."""
+    a = np.ascontiguousarray(pose_a, dtype=np.float64).reshape(3)
+    b = np.ascontiguousarray(pose_b, dtype=np.float64).reshape(3)
+    m = np.zeros(1, dtype=PG_MARGINAL_DTYPE)
+    m[0] = marginal
+    cov = np.zeros(9, dtype=np.float64)
+    _check(lib().ndt_pg_relative_cov(a.ctypes.data, b.ctypes.data, m.ctypes.data, cov.ctypes.data), "ndt_pg_relative_cov")
+    return cov.reshape(3, 3)
+
+
+def pg_edge_chi2(pose_a, pose_b, edge, rel_cov):
+    """ndt_pg_edge_chi2: r^T (rel_cov + Omega^-1)^-1 r of an arc (a record with rel and info) from pose_a to pose_b."""
+    a = np.ascontiguousarray(pose_a, dtype=np.float64).reshape(3)
+    b = np.ascontiguousarray(pose_b, dtype=np.float64).reshape(3)
+    e = np.zeros(1, dtype=PG_EDGE_DTYPE)
+    e[0]["rel"], e[0]["info"] = edge["rel"], edge["info"]
+    cov = np.ascontiguousarray(rel_cov, dtype=np.float64).reshape(9)
+    d2 = C.c_double()
+    _check(lib().ndt_pg_edge_chi2(a.ctypes.data, b.ctypes.data, e.ctypes.data, cov.ctypes.data, C.byref(d2)), "ndt_pg_edge_chi2")
+    return d2.value
 
 
 def repose_points(ctx, xy, seg_offsets, old_poses, new_poses, out=None):

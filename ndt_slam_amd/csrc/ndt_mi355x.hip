@@ -215,7 +215,7 @@ struct ndt_ctx {
   StagedUpload<unsigned char> fp_tab;                  // ndt_fit_points_batch: offsets, transforms and scans of the call, one upload
   DevBuf<unsigned char> d_occ;                         // ndt_occ_integrate_dev: the call's table of grids, its count of runs and the runs (ndt_occupancy.hip.h)
   StagedUpload<unsigned char> occ_tab, occ_up;         // ... the table's staging; ndt_occ_integrate: offsets, grid_of, origins and scans of the call, one upload
-  DevBuf<unsigned char> d_pg;                          // ndt_pg_optimize_batch_dev: the call's table of graphs, then every graph's scratch (ndt_posegraph.hip.h)
+  DevBuf<unsigned char> d_pg;                          // ndt_pg_*_batch_dev: the call's table of graphs (and queries), then every graph's or workgroup's scratch (ndt_posegraph.hip.h)
   StagedUpload<unsigned char> pg_tab;                  // ... the table's staging
   DevBuf<unsigned char> d_far;                         // deferred far phase of the fitness search: per match two counts, then the lists
   DevBuf<unsigned char> d_pf;                          // pre-filter: filtered points at the raw offsets + counts
@@ -4077,6 +4077,88 @@ int queue_pg(ndt_ctx *ctx, hipStream_t st, double *poses, const uint64_t *node_o
   return NDT_OK;
 }
 
+constexpr int kPgMarginalGrid = 1024;                // workgroups of one marginals launch at the most: one scratch slot each
+
+// ndt_pg_marginals_batch*: the table of graphs and the queries in one upload, one scratch slot per workgroup sized for the
+// largest graph that a query names, the launch on st; inside the caller's frame (d_pg, pg_tab).  Offsets index poses / edges /
+// weight as given.
+int queue_pg_marginals(ndt_ctx *ctx, hipStream_t st, const double *poses, const uint64_t *node_off, const ndt_pg_edge *edges,
+                       const uint64_t *edge_off, int G, const double *weight, const ndt_pg_query *queries, int Q, const ndt_pg_params *prm,
+                       ndt_pg_marginal *out) {
+  Regions R;
+  const size_t o_tab = R.take((size_t)G * sizeof(PgRow), 256), o_qry = R.take((size_t)Q * sizeof(ndt_pg_query), 256), tab_end = R.end;
+  int rc;
+  if ((rc = ctx->pg_tab.reserve(ctx, tab_end))) return rc;
+  PgRow *rows = Regions::at<PgRow>(ctx->pg_tab.h.p, o_tab);
+  for (int g = 0; g < G; ++g) {
+    const size_t n = (size_t)(node_off[g + 1] - node_off[g]), m = (size_t)(edge_off[g + 1] - edge_off[g]);
+    size_t n2 = 2;
+    while (n2 < 2 * m) n2 <<= 1;
+    PgRow r{};
+    r.node0 = node_off[g]; r.edge0 = edge_off[g]; r.n = (int)n; r.m = (int)m; r.n2 = (unsigned)n2;
+    rows[g] = r;                                             // (scratch: unused, the slot is the workgroup's)
+  }
+  std::memcpy(Regions::at<ndt_pg_query>(ctx->pg_tab.h.p, o_qry), queries, (size_t)Q * sizeof(ndt_pg_query));
+  size_t slot = 0;
+  for (int k = 0; k < Q; ++k) {
+    const int g = queries[k].graph;
+    if (g < 0 || g >= G) continue;                           // (the kernel gives that query NDT_E_ARG)
+    slot = std::max(slot, PgMLayout((size_t)rows[g].n, (size_t)rows[g].m, (size_t)rows[g].n2).end * sizeof(double));
+  }
+  slot = align_up(slot, 256);
+  const int grid = std::min(Q, kPgMarginalGrid);
+  const size_t o_slots = R.take((size_t)grid * slot, 256);
+  if ((rc = ctx->d_pg.ensure(ctx, R.end))) return rc;
+  HIP_TRY(ctx, ctx->pg_tab.upload(ctx->d_pg.p + o_tab, 0, tab_end, st));
+  pg_marginal_kernel<<<dim3((unsigned)grid), dim3(kPgThreads), 0, st>>>(
+      poses, edges, Regions::at<const PgRow>(ctx->d_pg.p, o_tab), G, weight, Regions::at<const ndt_pg_query>(ctx->d_pg.p, o_qry), Q,
+      prm->cg_max_iter, prm->cg_rtol, ctx->d_pg.p + o_slots, (unsigned long long)slot, out);
+  HIP_TRY(ctx, hipGetLastError());
+  return NDT_OK;
+}
+
+int pg_marginals_check(ndt_ctx *ctx, const void *queries, int Q, const char *fn) {
+  if (!queries) return fail(ctx, NDT_E_ARG, std::string(fn) + ": NULL queries");
+  if (Q < 1) return fail(ctx, NDT_E_ARG, std::string(fn) + ": need n_queries >= 1");
+  return NDT_OK;
+}
+
+// The residual of an arc with the measurement rel between two poses (tx, ty, th[deg]) and its two Jacobian blocks, as
+// pg_linearise and pg_jac (ndt_posegraph.hip.h) state them; rel == NULL: the Jacobians alone.
+void pg_host_arc(const double pa[3], const double pb[3], const double *rel, double r[3], double Ja[9], double Jb[9]) {
+  const double ta = pa[2] * (M_PI / 180.0), tb = pb[2] * (M_PI / 180.0);
+  const double c = std::cos(ta), s = std::sin(ta), dx = pb[0] - pa[0], dy = pb[1] - pa[1];
+  const double a = -s * dx + c * dy, b = -c * dx - s * dy;
+  const double A[9] = {-c, -s, a, s, -c, b, 0, 0, -1}, B[9] = {c, s, 0, -s, c, 0, 0, 0, 1};
+  std::copy(A, A + 9, Ja); std::copy(B, B + 9, Jb);
+  if (!rel) return;
+  r[0] = c * dx + s * dy - rel[0];
+  r[1] = a - rel[1];
+  double w = tb - ta - rel[2] * (M_PI / 180.0);
+  w -= 2.0 * M_PI * std::floor((w + M_PI) / (2.0 * M_PI));
+  if (w >= M_PI) w -= 2.0 * M_PI;
+  if (w < -M_PI) w += 2.0 * M_PI;
+  r[2] = w;
+}
+
+// The inverse of a symmetric 3 x 3 given as xx xy xt yy yt tt; false unless it is finite and positive definite (Sylvester).
+bool pg_host_spd_inverse(const double S[6], double Inv[6]) {
+  const double c00 = S[3] * S[5] - S[4] * S[4], c01 = S[4] * S[2] - S[1] * S[5], c02 = S[1] * S[4] - S[3] * S[2];
+  const double m2 = S[0] * S[3] - S[1] * S[1], det = S[0] * c00 + S[1] * c01 + S[2] * c02;
+  if (!(S[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0) || !(det <= DBL_MAX)) return false;
+  Inv[0] = c00 / det; Inv[1] = c01 / det; Inv[2] = c02 / det;
+  Inv[3] = (S[0] * S[5] - S[2] * S[2]) / det; Inv[4] = (S[1] * S[2] - S[0] * S[4]) / det; Inv[5] = m2 / det;
+  for (int k = 0; k < 6; ++k)
+    if (!(std::fabs(Inv[k]) <= DBL_MAX)) return false;
+  return true;
+}
+
+bool pg_host_finite(const double *v, int n) {
+  for (int k = 0; k < n; ++k)
+    if (!(std::fabs(v[k]) <= DBL_MAX)) return false;
+  return true;
+}
+
 int repose_check(ndt_ctx *ctx, const void *xy, size_t stride, const void *off, int n_segs, const void *old_p, const void *new_p,
                  const void *out, size_t out_stride, const char *fn) {
   if (!ctx) return fail(nullptr, NDT_E_ARG, "null context");
@@ -4251,6 +4333,105 @@ int ndt_pg_optimize_robust_batch(ndt_ctx *ctx, double *poses_host, const uint64_
   if (ne && weight_out_host) HIP_TRY(ctx, hipMemcpyAsync(weight_out_host + e0, d + o_w, ne * 8, hipMemcpyDeviceToHost, st));
   if (ne && chi2_out_host) HIP_TRY(ctx, hipMemcpyAsync(chi2_out_host + e0, d + o_c, ne * 8, hipMemcpyDeviceToHost, st));
   return fr.close_and_wait();
+}
+
+int ndt_pg_marginals_batch_dev(ndt_ctx *ctx, const double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
+                               const uint64_t *edge_offsets_host, int n_graphs, const double *weight_dev,
+                               const ndt_pg_query *queries_host, int n_queries, const ndt_pg_params *params,
+                               ndt_pg_marginal *out_dev, void *stream) {
+  const char *fn = "ndt_pg_marginals_batch_dev";
+  int rc = pg_check(ctx, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, params, out_dev, fn);
+  if (rc || (rc = pg_marginals_check(ctx, queries_host, n_queries, fn))) return rc;
+  return CallFrame::run(ctx, stream, [&](hipStream_t st) {
+    return queue_pg_marginals(ctx, st, poses_dev, node_offsets_host, edges_dev, edge_offsets_host, n_graphs, weight_dev, queries_host,
+                              n_queries, params, out_dev);
+  });
+}
+
+int ndt_pg_marginals_batch(ndt_ctx *ctx, const double *poses_host, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_host,
+                           const uint64_t *edge_offsets_host, int n_graphs, const double *weight_host,
+                           const ndt_pg_query *queries_host, int n_queries, const ndt_pg_params *params,
+                           ndt_pg_marginal *out_host) {
+  const char *fn = "ndt_pg_marginals_batch";
+  int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params, out_host, fn);
+  if (rc || (rc = pg_marginals_check(ctx, queries_host, n_queries, fn))) return rc;
+  const size_t G = (size_t)n_graphs, Q = (size_t)n_queries;
+  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
+  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
+  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
+  CallFrame fr(ctx);
+  if ((rc = fr.open())) return rc;
+  hipStream_t st = fr.st;
+  Regions U;
+  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256), o_w = U.take(ne * 8 + 8, 256),
+               o_res = U.take(Q * sizeof(ndt_pg_marginal), 256);
+  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+  unsigned char *d = ctx->d_scan.p;
+  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
+  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
+  if (ne && weight_host) HIP_TRY(ctx, hipMemcpyAsync(d + o_w, weight_host + e0, ne * 8, hipMemcpyHostToDevice, st));
+  if ((rc = queue_pg_marginals(ctx, st, (const double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs,
+                               weight_host ? (const double *)(d + o_w) : nullptr, queries_host, n_queries, params,
+                               (ndt_pg_marginal *)(d + o_res))))
+    return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, Q * sizeof(ndt_pg_marginal), hipMemcpyDeviceToHost, st));
+  return fr.close_and_wait();
+}
+
+int ndt_pg_relative_cov(const double pose_a[3], const double pose_b[3], const ndt_pg_marginal *m, double cov[9]) {
+  if (!pose_a || !pose_b || !m || !cov) return fail(nullptr, NDT_E_ARG, "ndt_pg_relative_cov: NULL pointer");
+  if (!pg_host_finite(pose_a, 3) || !pg_host_finite(pose_b, 3) || !pg_host_finite(m->Saa, 9) || !pg_host_finite(m->Sab, 9) ||
+      !pg_host_finite(m->Sbb, 9))
+    return fail(nullptr, NDT_E_ARG, "ndt_pg_relative_cov: a number is not finite");
+  double Ja[9], Jb[9];
+  pg_host_arc(pose_a, pose_b, nullptr, nullptr, Ja, Jb);
+  // M = [Ja Jb] [[Saa Sab] [Sab^T Sbb]] [Ja Jb]^T, term by term
+  const auto mul3 = [](const double *X, const double *Y, bool y_transposed, double *Z) {
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        for (int k = 0; k < 3; ++k) v += X[3 * r + k] * (y_transposed ? Y[3 * c + k] : Y[3 * k + c]);
+        Z[3 * r + c] = v;
+      }
+  };
+  double T1[9], T2[9], C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const double *J[2] = {Ja, Jb};
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j) {
+      double Sab_t[9];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Sab_t[3 * r + c] = m->Sab[3 * c + r];
+      const double *S = i == 0 ? (j == 0 ? m->Saa : m->Sab) : (j == 0 ? Sab_t : m->Sbb);
+      mul3(J[i], S, false, T1);
+      mul3(T1, J[j], true, T2);
+      for (int k = 0; k < 9; ++k) C[k] += T2[k];
+    }
+  const double S6[6] = {C[0], 0.5 * (C[1] + C[3]), 0.5 * (C[2] + C[6]), C[4], 0.5 * (C[5] + C[7]), C[8]};
+  double inv[6];
+  if (!pg_host_finite(C, 9) || !pg_host_spd_inverse(S6, inv))
+    return fail(nullptr, NDT_E_ARG, "ndt_pg_relative_cov: the covariance is not positive definite");
+  cov[0] = S6[0]; cov[1] = S6[1]; cov[2] = S6[2]; cov[3] = S6[1]; cov[4] = S6[3]; cov[5] = S6[4]; cov[6] = S6[2]; cov[7] = S6[4]; cov[8] = S6[5];
+  return NDT_OK;
+}
+
+int ndt_pg_edge_chi2(const double pose_a[3], const double pose_b[3], const ndt_pg_edge *edge, const double rel_cov[9], double *d2) {
+  if (!pose_a || !pose_b || !edge || !rel_cov || !d2) return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_chi2: NULL pointer");
+  if (!pg_host_finite(pose_a, 3) || !pg_host_finite(pose_b, 3) || !pg_host_finite(edge->rel, 3) || !pg_host_finite(edge->info, 6) ||
+      !pg_host_finite(rel_cov, 9))
+    return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_chi2: a number is not finite");
+  double r[3], Ja[9], Jb[9], om_inv[6], inv[6];
+  pg_host_arc(pose_a, pose_b, edge->rel, r, Ja, Jb);
+  if (!pg_host_spd_inverse(edge->info, om_inv)) return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_chi2: the information is not positive definite");
+  const double *C = rel_cov;
+  const double S[6] = {C[0] + om_inv[0], 0.5 * (C[1] + C[3]) + om_inv[1], 0.5 * (C[2] + C[6]) + om_inv[2], C[4] + om_inv[3],
+                       0.5 * (C[5] + C[7]) + om_inv[4], C[8] + om_inv[5]};
+  if (!pg_host_spd_inverse(S, inv)) return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_chi2: rel_cov + Omega^-1 is not positive definite");
+  const double w[3] = {inv[0] * r[0] + inv[1] * r[1] + inv[2] * r[2], inv[1] * r[0] + inv[3] * r[1] + inv[4] * r[2],
+                       inv[2] * r[0] + inv[4] * r[1] + inv[5] * r[2]};
+  const double v = r[0] * w[0] + r[1] * w[1] + r[2] * w[2];
+  if (!(std::fabs(v) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_edge_chi2: the distance is not finite");
+  *d2 = v;
+  return NDT_OK;
 }
 
 int ndt_repose_points_dev(ndt_ctx *ctx, const float *xy_dev, size_t stride_bytes, const uint64_t *seg_offsets_dev, int n_segs,

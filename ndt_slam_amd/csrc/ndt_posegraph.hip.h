@@ -618,6 +618,375 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
   }
 }
 
+// ---- ndt_pg_marginals_batch: blocks of H^-1 at the poses given (the contract is the header's) ----
+// A query (graph, a, b) is the three unit columns of each of its free nodes solved against the one factor: K = 3 or 6
+// right-hand sides that share every H p walk and every block-Thomas sweep.  The vectors are laid out [node][column][3]; a
+// column's arithmetic is the same instructions in every slot and touches no other column's numbers, so its solution is a
+// function of (graph, weights, node, column) alone.
+
+constexpr int kPgCols = 6;                         // columns of one query at the most: two free nodes
+constexpr int kPgMStride = 9 + 3 * kPgCols;        // doubles of one staged node of pg_apply_multi: L_i or W_i, then K triples
+static_assert(kPgMStride <= 30, "pg_apply_multi stages in the LDS that pg_factor uses");
+
+// The regions of one workgroup's scratch slot, in doubles from its start: the vectors are sized for kPgCols columns.
+struct PgMLayout {
+  size_t xr, r, z, p, q, y, x, D, U, L, Si, W, lin, keys, ptr, end;
+  __host__ __device__ PgMLayout(size_t n, size_t m, size_t n2) {
+    const size_t v = 3 * (size_t)kPgCols * n;
+    size_t o = 0;
+    xr = o; o += 3 * n; r = o; o += v; z = o; o += v; p = o; o += v; q = o; o += v; y = o; o += v; x = o; o += v;
+    D = o; o += 6 * n; U = o; o += 9 * n; L = o; o += 9 * n; Si = o; o += 6 * n; W = o; o += 9 * n;
+    lin = o; o += 8 * m; keys = o; o += n2; ptr = o; o += (n + 2) / 2 + 1;
+    end = o;
+  }
+};
+
+// pg_block_sum for kPgCols values at once: each value goes through the same tree, and every thread gets the same bits.
+__device__ __forceinline__ void pg_block_sum_cols(double v[kPgCols], double *s_wk) {
+#pragma unroll
+  for (int k = 0; k < kPgCols; ++k) {
+    const double t = wave_sum(v[k]);
+    if ((threadIdx.x & 63) == 0) s_wk[(threadIdx.x >> 6) * kPgCols + k] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kPgCols; ++k) v[k] = ((s_wk[k] + s_wk[kPgCols + k]) + s_wk[2 * kPgCols + k]) + s_wk[3 * kPgCols + k];
+  __syncthreads();
+}
+
+// pg_apply for K columns ([node][column][3] vectors): lane k of wave 0 carries column k through the forward and the backward
+// sweep, every lane reads the same L_i / W_i from LDS (a broadcast), so one trip up and one trip down serve all K columns.
+// Staged in pieces of kPgChunk nodes as pg_apply stages them; a column's arithmetic is pg_apply's.  Ends behind a barrier.
+__device__ void pg_apply_multi(const double *__restrict__ L, const double *__restrict__ Si, const double *__restrict__ W,
+                               const double *__restrict__ r, double *__restrict__ y, double *__restrict__ z, int n, int K, double *sh) {
+  const int tid = (int)threadIdx.x, K3 = 3 * K, per = 9 + K3;
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0;             // the lane's carry: y_{i-1} of its column, then z_{i+1}
+  for (int i0 = 1; i0 < n; i0 += kPgChunk) {
+    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
+    for (int idx = tid; idx < cn * per; idx += kPgThreads) {
+      const int a = idx / per, k = idx % per, i = i0 + a;
+      sh[a * kPgMStride + k] = k < 9 ? L[9 * (size_t)i + k] : r[(size_t)K3 * i + (k - 9)];
+    }
+    __syncthreads();
+    if (tid < K) {
+      for (int a = 0; a < cn; ++a) {
+        const double *q = sh + a * kPgMStride;
+        double *v = sh + a * kPgMStride + 9 + 3 * tid;
+        const double y0 = v[0] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
+        const double y1 = v[1] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
+        const double y2 = v[2] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
+        v[0] = y0; v[1] = y1; v[2] = y2;
+        c0 = y0; c1 = y1; c2 = y2;
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cn * K3; idx += kPgThreads) y[(size_t)K3 * (i0 + idx / K3) + idx % K3] = sh[(idx / K3) * kPgMStride + 9 + idx % K3];
+    __syncthreads();
+  }
+  for (int idx = tid; idx < (n - 1) * K; idx += kPgThreads) {
+    const int i = 1 + idx / K;
+    const double *s = Si + 6 * (size_t)i;
+    double *v = y + (size_t)K3 * i + 3 * (idx % K);
+    const double a = v[0], b = v[1], c = v[2];
+    v[0] = (s[0] * a + s[1] * b) + s[2] * c;
+    v[1] = (s[1] * a + s[3] * b) + s[4] * c;
+    v[2] = (s[2] * a + s[4] * b) + s[5] * c;
+  }
+  __syncthreads();
+  c0 = c1 = c2 = 0.0;
+  const int chunks = (n - 1 + kPgChunk - 1) / kPgChunk;
+  for (int ch = chunks - 1; ch >= 0; --ch) {
+    const int i0 = 1 + ch * kPgChunk;
+    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
+    for (int idx = tid; idx < cn * per; idx += kPgThreads) {
+      const int a = idx / per, k = idx % per, i = i0 + a;
+      sh[a * kPgMStride + k] = k < 9 ? W[9 * (size_t)i + k] : y[(size_t)K3 * i + (k - 9)];
+    }
+    __syncthreads();
+    if (tid < K) {
+      for (int a = cn - 1; a >= 0; --a) {
+        const double *q = sh + a * kPgMStride;
+        double *v = sh + a * kPgMStride + 9 + 3 * tid;
+        const double z0 = v[0] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
+        const double z1 = v[1] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
+        const double z2 = v[2] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
+        v[0] = z0; v[1] = z1; v[2] = z2;
+        c0 = z0; c1 = z1; c2 = z2;
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < cn * K3; idx += kPgThreads) z[(size_t)K3 * (i0 + idx / K3) + idx % K3] = sh[(idx / K3) * kPgMStride + 9 + idx % K3];
+    __syncthreads();
+  }
+}
+
+// One query's record: the blocks as given (NULL: zeros), the counters.
+__device__ void pg_marginal_write(ndt_pg_marginal *__restrict__ o, const double *Saa, const double *Sab, const double *Sbb, int cg_iterations,
+                                  int converged, int status) {
+  for (int k = 0; k < 9; ++k) { o->Saa[k] = Saa ? Saa[k] : 0.0; o->Sab[k] = Sab ? Sab[k] : 0.0; o->Sbb[k] = Sbb ? Sbb[k] : 0.0; }
+  o->cg_iterations = cg_iterations; o->converged = converged; o->status = status; o->pad = 0;
+}
+// The diagonal block of node `node` from the solves of its own columns (slot: its first column): every pair averaged.
+__device__ void pg_marginal_diag(const double *__restrict__ x, int K, int node, int slot, double S[9]) {
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) S[3 * r + c] = x[((size_t)node * K + slot + c) * 3 + r];
+  S[1] = S[3] = 0.5 * (S[1] + S[3]); S[2] = S[6] = 0.5 * (S[2] + S[6]); S[5] = S[7] = 0.5 * (S[5] + S[7]);
+}
+
+// Workgroup w takes the queries w, w + gridDim.x, ... in its own scratch slot (slot_bytes each, for the largest queried graph).
+// The set-up of a query is pg_solve_kernel<true>'s at the poses given, the arc weights in PgLin::pad; the conjugate gradients
+// are its loop with one alpha, beta, r^T z and stop flag per column.  A column that has stopped is frozen; every decision is
+// taken from block sums, which every thread holds with the same bits: control flow stays uniform around the barriers.
+__global__ void __launch_bounds__(kPgThreads)
+pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restrict__ edges, const PgRow *__restrict__ rows, int n_graphs,
+                   const double *__restrict__ weight, const ndt_pg_query *__restrict__ queries, int n_queries, int cg_max_iter, double cg_rtol,
+                   unsigned char *__restrict__ scratch, unsigned long long slot_bytes, ndt_pg_marginal *__restrict__ out) {
+  __shared__ double sh[kPgChunk * 30];
+  __shared__ double s_wk[4 * kPgCols];
+  __shared__ int s_ok;
+  const int tid = (int)threadIdx.x;
+  double *base = reinterpret_cast<double *>(scratch + (unsigned long long)blockIdx.x * slot_bytes);
+  for (int qi = (int)blockIdx.x; qi < n_queries; qi += (int)gridDim.x) {
+    const ndt_pg_query Q = queries[qi];
+    if (Q.graph < 0 || Q.graph >= n_graphs) {
+      if (tid == 0) pg_marginal_write(out + qi, nullptr, nullptr, nullptr, 0, 0, NDT_E_ARG);
+      continue;
+    }
+    const PgRow R = rows[Q.graph];
+    const int n = R.n, m = R.m;
+    const double *pose = poses + 3 * R.node0;
+    const ndt_pg_edge *ed = edges + R.edge0;
+    const double *gw = weight ? weight + R.edge0 : nullptr;
+    // ---- the query's and the graph's own faults (pg_solve_kernel's, and a weight that is negative or not finite) ----
+    int bad = (Q.a < 0 || Q.a >= n || Q.b < 0 || Q.b >= n) ? 1 : 0;
+    for (int i = tid; i < n; i += kPgThreads)
+      if (!pg_finite(pose[3 * (size_t)i]) || !pg_finite(pose[3 * (size_t)i + 1]) || !pg_finite(pose[3 * (size_t)i + 2])) bad = 1;
+    for (int e = tid; e < m; e += kPgThreads) {
+      const ndt_pg_edge E = ed[e];
+      if (E.from < 0 || E.from >= n || E.to < 0 || E.to >= n || E.from == E.to) bad = 1;
+      bool fin = pg_finite(E.rel[0]) && pg_finite(E.rel[1]) && pg_finite(E.rel[2]);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) fin = fin && pg_finite(E.info[k]);
+      const double *I = E.info;
+      const double m2 = I[0] * I[3] - I[1] * I[1];
+      const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
+      if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
+      if (gw && (!(gw[e] >= 0.0) || !pg_finite(gw[e]))) bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    if (!bad && m == 0 && (Q.a != 0 || Q.b != 0)) bad = 1;       // (nothing ties the node to node 0)
+    // ---- the free nodes whose columns are solved: a, then b unless it is a again; a block with node 0 is exactly 0 ----
+    const int na = Q.a != 0 ? 1 : 0, nb = (Q.b != 0 && Q.b != Q.a) ? 1 : 0;
+    const int K = 3 * (na + nb);
+    if (bad || K == 0) {
+      if (tid == 0) pg_marginal_write(out + qi, nullptr, nullptr, nullptr, 0, bad ? 0 : 1, bad ? NDT_E_ARG : NDT_OK);
+      continue;
+    }
+    const int node0 = na ? Q.a : Q.b, node1 = Q.b;             // the node of the columns 0 .. 2, of the columns 3 .. 5
+    const int K3 = 3 * K;
+    const PgMLayout Y((size_t)n, (size_t)m, (size_t)R.n2);
+    double *xr = base + Y.xr, *r = base + Y.r, *z = base + Y.z, *p = base + Y.p, *q = base + Y.q, *y = base + Y.y, *x = base + Y.x,
+           *D = base + Y.D, *U = base + Y.U, *L = base + Y.L, *Si = base + Y.Si, *W = base + Y.W;
+    PgLin *lin = reinterpret_cast<PgLin *>(base + Y.lin);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + Y.keys);
+    int *ptr = reinterpret_cast<int *>(base + Y.ptr);
+    // ---- every node's arcs in arc-index order: keys (node, 2 e + side) sorted, then cut at the nodes ----
+    const unsigned n2 = R.n2, m2e = 2u * (unsigned)m;
+    for (unsigned k = (unsigned)tid; k < n2; k += kPgThreads) {
+      unsigned long long key = ~0ull;
+      if (k < m2e) { const ndt_pg_edge &E = ed[k >> 1]; key = ((unsigned long long)(unsigned)((k & 1u) ? E.to : E.from) << 32) | k; }
+      keys[k] = key;
+    }
+    __syncthreads();
+    for (unsigned kk = 2; kk <= n2; kk <<= 1)
+      for (unsigned j = kk >> 1; j > 0; j >>= 1) {
+        for (unsigned i = (unsigned)tid; i < n2; i += kPgThreads) {
+          const unsigned l = i ^ j;
+          if (l > i) {
+            const unsigned long long a = keys[i], b = keys[l];
+            if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
+          }
+        }
+        __syncthreads();
+      }
+    for (unsigned k = (unsigned)tid; k <= m2e; k += kPgThreads) {
+      const int node = k < m2e ? (int)(keys[k] >> 32) : n;
+      const int prev = k > 0 ? (int)(keys[k - 1] >> 32) : -1;
+      for (int v = prev + 1; v <= node; ++v) ptr[v] = (int)k;
+    }
+    // ---- the poses in radians (read only), the arcs linearised there with their weights, every node's D and U ----
+    for (int i = tid; i < n; i += kPgThreads) {
+      xr[3 * (size_t)i] = pose[3 * (size_t)i]; xr[3 * (size_t)i + 1] = pose[3 * (size_t)i + 1];
+      xr[3 * (size_t)i + 2] = pose[3 * (size_t)i + 2] * (kPgPi / 180.0);
+    }
+    __syncthreads();
+    for (int e = tid; e < m; e += kPgThreads) {
+      PgLin l = pg_linearise(xr, ed[e]);
+      l.pad = gw ? gw[e] : 1.0;
+      lin[e] = l;
+    }
+    __syncthreads();
+    for (int i = 1 + tid; i < n; i += kPgThreads) {
+      double Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int k = ptr[i]; k < ptr[i + 1]; ++k) {
+        const unsigned slot = (unsigned)keys[k];
+        const int e = (int)(slot >> 1), side = (int)(slot & 1u);
+        const PgLin l = lin[e];
+        const double *I = ed[e].info;
+        const int other = side ? ed[e].from : ed[e].to;
+        double Js[9], Jo[9];
+        pg_jac(l, side, Js);
+        pg_block_add<true>(Js, I, Js, l.pad, Dm);
+        if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add<true>(Js, I, Jo, l.pad, Um); }
+      }
+      double *d = D + 6 * (size_t)i;
+      d[0] = Dm[0]; d[1] = Dm[1]; d[2] = Dm[2]; d[3] = Dm[4]; d[4] = Dm[5]; d[5] = Dm[8];
+      for (int k = 0; k < 9; ++k) U[9 * (size_t)i + k] = Um[k];
+    }
+    __syncthreads();
+    if (!pg_factor(D, U, L, Si, W, n, sh, &s_ok)) {
+      if (tid == 0) pg_marginal_write(out + qi, nullptr, nullptr, nullptr, 0, 0, NDT_OK);
+      __syncthreads();
+      continue;
+    }
+    // ---- the right-hand sides: column k is the unit vector of entry k % 3 of its node; node 0's entries stay zero ----
+    for (int i = tid; i < n; i += kPgThreads)
+      for (int k = 0; k < K; ++k) {
+        const int node = k < 3 ? node0 : node1;
+        for (int c = 0; c < 3; ++c) {
+          const size_t at = ((size_t)i * K + k) * 3 + c;
+          r[at] = (i == node && c == k % 3) ? 1.0 : 0.0;
+          x[at] = 0.0;
+          if (i == 0) { z[at] = 0.0; p[at] = 0.0; q[at] = 0.0; y[at] = 0.0; }
+        }
+      }
+    __syncthreads();
+    pg_apply_multi(L, Si, W, r, y, z, n, K, sh);
+    double rz[kPgCols], rz0[kPgCols], coef[kPgCols], acc[kPgCols];
+    bool act[kPgCols], ok[kPgCols];
+    int its[kPgCols];
+#pragma unroll
+    for (int k = 0; k < kPgCols; ++k) acc[k] = 0.0;
+    for (int i = 1 + tid; i < n; i += kPgThreads)
+#pragma unroll
+      for (int k = 0; k < kPgCols; ++k)
+        if (k < K)
+          for (int c = 0; c < 3; ++c) {
+            const size_t at = ((size_t)i * K + k) * 3 + c;
+            const double zv = z[at];
+            p[at] = zv; acc[k] += r[at] * zv;
+          }
+    pg_block_sum_cols(acc, s_wk);
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < kPgCols; ++k) {
+      rz[k] = acc[k]; rz0[k] = acc[k]; coef[k] = 0.0; its[k] = 0;
+      ok[k] = k >= K || (rz[k] > 0.0 && pg_finite(rz[k]));      // (T is positive definite: r0^T z0 of a unit column is above 0)
+      act[k] = k < K && ok[k];
+      any = any || act[k];
+    }
+    const int cg_cap = cg_max_iter > 0 ? cg_max_iter : 6 * n;
+    for (int it = 0; it < cg_cap && any; ++it) {
+      // q = H p of the columns still running: a node's arcs in arc-index order, each arc's Jacobians applied to every column
+#pragma unroll
+      for (int k = 0; k < kPgCols; ++k) acc[k] = 0.0;
+      for (int i = 1 + tid; i < n; i += kPgThreads) {
+        double qv[kPgCols][3];
+#pragma unroll
+        for (int k = 0; k < kPgCols; ++k) { qv[k][0] = 0.0; qv[k][1] = 0.0; qv[k][2] = 0.0; }
+        const double *pi = p + (size_t)i * K3;
+        for (int kk = ptr[i]; kk < ptr[i + 1]; ++kk) {
+          const unsigned slot = (unsigned)keys[kk];
+          const int e = (int)(slot >> 1), side = (int)(slot & 1u);
+          const PgLin l = lin[e];
+          const double *I = ed[e].info;
+          const int other = side ? ed[e].from : ed[e].to;
+          const double *po = p + (size_t)other * K3;
+          double Js[9], Jo[9];
+          pg_jac(l, side, Js); pg_jac(l, side ^ 1, Jo);
+#pragma unroll
+          for (int k = 0; k < kPgCols; ++k)
+            if (act[k]) {
+              const double pi3[3] = {pi[3 * k], pi[3 * k + 1], pi[3 * k + 2]}, po3[3] = {po[3 * k], po[3 * k + 1], po[3 * k + 2]};
+              double u1[3], u2[3], w[3], o[3];
+              pg_j_mul(Js, pi3, u1); pg_j_mul(Jo, po3, u2);
+              const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
+              pg_info_mul(I, u, w);
+              pg_jt_mul(Js, w, o);
+              qv[k][0] += l.pad * o[0]; qv[k][1] += l.pad * o[1]; qv[k][2] += l.pad * o[2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPgCols; ++k)
+          if (act[k])
+            for (int c = 0; c < 3; ++c) { q[(size_t)i * K3 + 3 * k + c] = qv[k][c]; acc[k] += pi[3 * k + c] * qv[k][c]; }
+      }
+      pg_block_sum_cols(acc, s_wk);
+#pragma unroll
+      for (int k = 0; k < kPgCols; ++k)
+        if (act[k]) {
+          its[k]++;
+          if (!(acc[k] > 0.0) || !pg_finite(acc[k])) { act[k] = false; ok[k] = false; }     // (a CG breakdown)
+          else coef[k] = rz[k] / acc[k];
+        }
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+#pragma unroll
+        for (int k = 0; k < kPgCols; ++k)
+          if (act[k])
+            for (int c = 0; c < 3; ++c) {
+              const size_t at = (size_t)i * K3 + 3 * k + c;
+              x[at] += coef[k] * p[at]; r[at] -= coef[k] * q[at];
+            }
+      __syncthreads();
+      pg_apply_multi(L, Si, W, r, y, z, n, K, sh);
+#pragma unroll
+      for (int k = 0; k < kPgCols; ++k) acc[k] = 0.0;
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+#pragma unroll
+        for (int k = 0; k < kPgCols; ++k)
+          if (act[k])
+            for (int c = 0; c < 3; ++c) { const size_t at = (size_t)i * K3 + 3 * k + c; acc[k] += r[at] * z[at]; }
+      pg_block_sum_cols(acc, s_wk);
+      any = false;
+#pragma unroll
+      for (int k = 0; k < kPgCols; ++k)
+        if (act[k]) {
+          if (!(acc[k] >= 0.0) || !pg_finite(acc[k])) { act[k] = false; ok[k] = false; }
+          else if (sqrt(acc[k]) <= cg_rtol * sqrt(rz0[k])) act[k] = false;                    // (the column has met the rule)
+          else { coef[k] = acc[k] / rz[k]; rz[k] = acc[k]; any = true; }
+        }
+      for (int i = 1 + tid; i < n; i += kPgThreads)
+#pragma unroll
+        for (int k = 0; k < kPgCols; ++k)
+          if (act[k])
+            for (int c = 0; c < 3; ++c) { const size_t at = (size_t)i * K3 + 3 * k + c; p[at] = z[at] + coef[k] * p[at]; }
+      __syncthreads();
+    }
+    // ---- out: all three blocks or none -- every column has to have met the rule ----
+    int conv = 1, cg_most = 0;
+#pragma unroll
+    for (int k = 0; k < kPgCols; ++k) {
+      if (!ok[k] || act[k]) conv = 0;
+      cg_most = its[k] > cg_most ? its[k] : cg_most;
+    }
+    if (tid == 0) {
+      if (!conv) {
+        pg_marginal_write(out + qi, nullptr, nullptr, nullptr, cg_most, 0, NDT_OK);
+      } else {
+        double Saa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Sab[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Sbb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const int slot_b = (na && nb) ? 3 : 0;                   // b's first column (a's is 0)
+        if (na) pg_marginal_diag(x, K, Q.a, 0, Saa);
+        if (Q.b != 0) pg_marginal_diag(x, K, Q.b, slot_b, Sbb);
+        if (na && Q.b != 0)
+          for (int rr = 0; rr < 3; ++rr)
+            for (int c = 0; c < 3; ++c) Sab[3 * rr + c] = Q.a == Q.b ? Saa[3 * rr + c] : x[((size_t)Q.a * K + slot_b + c) * 3 + rr];
+        pg_marginal_write(out + qi, Saa, Sab, Sbb, cg_most, 1, NDT_OK);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // remakeMaps' point correction (src/PointCloudMap.cpp:147-154): q = oldPose.relativePoint(p), p' = newPose.globalPoint(q)
 // (src/Pose2D.cpp:46-59) with Rmat as Pose2D::calRmat builds it, fp64 without contraction, rounded once to float32.
 // ReposeMove: what one (old, new) pose pair gives every point of its segment; repose_point: the per-point body -- the one

@@ -670,18 +670,23 @@ def load_occupancy(stem):
 # (the sessions must share a map frame), one joint graph per group of sessions that its edges tie together, and one correct(),
 # robust = None or an object with `params` (a capi.PgRobustParams, None: the defaults) and `phi` (the chi-square beyond which a
 # loop or cross arc counts as rejected): the graphs then go through capi.optimize_pose_graphs_robust with phi on the loop and
-# cross arcs and 0 on the odometry arcs, `pg` is not used, and a graph's sessions are corrected only when robust_keep says so
+# cross arcs and 0 on the odometry arcs, `pg` is not used, and a graph's sessions are corrected only when robust_keep says so,
+# consistency = None or a chi-square bound (11.34: 99 % at 3 degrees of freedom): a loop edge found inside a session whose
+# loop_consistency against that session's odometry is above the bound is dropped before the graph is built (cross edges, which
+# no single trajectory's odometry spans, are not gated)
 class LoopClosure(collections.namedtuple("LoopClosure", "loop pg odo_info every cooldown")):
     """The five fields above as a tuple, as before (its _fields, its length and its unpacking are unchanged), and the
-    attributes remake_closed (default False), multi (default None), cross (default None) and robust (default None) beside
-    them."""
+    attributes remake_closed (default False), multi (default None), cross (default None), robust (default None) and
+    consistency (default None) beside them."""
 
-    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None, cross=None, robust=None):
+    def __new__(cls, loop, pg, odo_info, every, cooldown, remake_closed=False, multi=None, cross=None, robust=None,
+                consistency=None):
         self = super().__new__(cls, loop, pg, odo_info, every, cooldown)
         self.remake_closed = bool(remake_closed)
         self.multi = multi
         self.cross = cross
         self.robust = robust
+        self.consistency = consistency
         return self
 
 
@@ -756,6 +761,30 @@ def loops_graph(poses, loop_edges, odo_info):
         e["to"] = loop_edge["to"]
         e["rel"], e["info"] = loop_edge["rel"], loop_edge["info"]
     return edges
+
+
+def loop_consistency(ctx, poses, odo_info, loop_edges):
+    """How far every candidate loop arc of one trajectory lies from what the odometry in between allows -> d2[], one squared
+    Mahalanobis distance per arc (chi-square with 3 degrees of freedom for a true one).  The graph is the odometry alone,
+    loops_graph(poses, [], odo_info); one query (0, from, to) per arc in one capi.pose_graph_marginals call, then
+    capi.pg_relative_cov and capi.pg_edge_chi2 at the trajectory's poses."""
+    from . import capi
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    if not len(loop_edges):
+        return np.zeros(0, dtype=np.float64)
+    ends = []
+    for e in loop_edges:
+        names = getattr(getattr(e, "dtype", None), "names", None) or ()
+        ends.append((int(e["from" if "from" in names else "from_"]), int(e["to"])))
+    odo = loops_graph(poses, [], odo_info)
+    marg = capi.pose_graph_marginals(ctx, poses, [0, len(poses)], odo, [0, len(odo)], [(0, a, b) for a, b in ends])
+    d2 = np.zeros(len(ends), dtype=np.float64)
+    for k, ((a, b), e) in enumerate(zip(ends, loop_edges)):
+        if marg[k]["status"] != 0 or not marg[k]["converged"]:
+            raise capi.NdtError("loop_consistency: no covariance for the arc %d -> %d (status %d, converged %d)"
+                                % (a, b, marg[k]["status"], marg[k]["converged"]))
+        d2[k] = capi.pg_edge_chi2(poses[a], poses[b], e, capi.pg_relative_cov(poses[a], poses[b], marg[k]))
+    return d2
 
 
 def loop_graph(poses, loop_edge, odo_info):
@@ -847,6 +876,13 @@ def _close_loops(ctx, sessions, lc, which):
     for l in loops:
         if l["status"] == 0 and l["found"]:
             by_session.setdefault(int(l["cand"]["session"]), []).append(l["edge"])
+    bound = getattr(lc, "consistency", None)
+    if bound is not None:                              # the gate: an edge the odometry in between contradicts never reaches a graph
+        for i in list(by_session):
+            d2 = loop_consistency(ctx, sessions.trajectory(i)[0], lc.odo_info, by_session[i])
+            by_session[i] = [e for e, d in zip(by_session[i], d2) if d <= bound]
+            if not by_session[i]:
+                del by_session[i]
     if not by_session:
         return corrected
     who = list(by_session)
