@@ -4038,6 +4038,16 @@ int pg_robust_check(ndt_ctx *ctx, const ndt_pg_robust_params *rp, const char *fn
   return NDT_OK;
 }
 
+// Graph g's row of a call's table but for its scratch offset: where its nodes and arcs start, how many, the key array's length.
+PgRow pg_row(const uint64_t *node_off, const uint64_t *edge_off, int g) {
+  PgRow r{};
+  r.node0 = node_off[g]; r.edge0 = edge_off[g];
+  r.n = (int)(node_off[g + 1] - node_off[g]); r.m = (int)(edge_off[g + 1] - edge_off[g]);
+  r.n2 = 2;
+  while (r.n2 < 2 * (size_t)r.m) r.n2 <<= 1;
+  return r;
+}
+
 // The table and the launch on st, inside the caller's frame (d_pg, pg_tab).  node_off / edge_off index poses / edges as given
 // (and phi, weight_out, chi2_out as edges).  rp == NULL: the plain form, out holds ndt_pg_result; else the robust one, out
 // holds ndt_pg_robust_result.
@@ -4050,12 +4060,8 @@ int queue_pg(ndt_ctx *ctx, hipStream_t st, double *poses, const uint64_t *node_o
   if ((rc = ctx->pg_tab.reserve(ctx, (size_t)G * sizeof(PgRow)))) return rc;
   PgRow *rows = reinterpret_cast<PgRow *>(ctx->pg_tab.h.p);
   for (int g = 0; g < G; ++g) {
-    const size_t n = (size_t)(node_off[g + 1] - node_off[g]), m = (size_t)(edge_off[g + 1] - edge_off[g]);
-    size_t n2 = 2;
-    while (n2 < 2 * m) n2 <<= 1;
-    PgRow r{};
-    r.node0 = node_off[g]; r.edge0 = edge_off[g]; r.n = (int)n; r.m = (int)m; r.n2 = (unsigned)n2;
-    r.scratch = m ? R.take(PgLayout(n, m, n2).end * sizeof(double), 256) : 0;   // (a graph without arcs uses none)
+    PgRow r = pg_row(node_off, edge_off, g);
+    r.scratch = r.m ? R.take(PgLayout((size_t)r.n, (size_t)r.m, (size_t)r.n2).end * sizeof(double), 256) : 0;   // (a graph without arcs uses none)
     rows[g] = r;
   }
   if ((rc = ctx->d_pg.ensure(ctx, R.end))) return rc;
@@ -4090,14 +4096,7 @@ int queue_pg_marginals(ndt_ctx *ctx, hipStream_t st, const double *poses, const 
   int rc;
   if ((rc = ctx->pg_tab.reserve(ctx, tab_end))) return rc;
   PgRow *rows = Regions::at<PgRow>(ctx->pg_tab.h.p, o_tab);
-  for (int g = 0; g < G; ++g) {
-    const size_t n = (size_t)(node_off[g + 1] - node_off[g]), m = (size_t)(edge_off[g + 1] - edge_off[g]);
-    size_t n2 = 2;
-    while (n2 < 2 * m) n2 <<= 1;
-    PgRow r{};
-    r.node0 = node_off[g]; r.edge0 = edge_off[g]; r.n = (int)n; r.m = (int)m; r.n2 = (unsigned)n2;
-    rows[g] = r;                                             // (scratch: unused, the slot is the workgroup's)
-  }
+  for (int g = 0; g < G; ++g) rows[g] = pg_row(node_off, edge_off, g);     // (scratch: unused, the slot is the workgroup's)
   std::memcpy(Regions::at<ndt_pg_query>(ctx->pg_tab.h.p, o_qry), queries, (size_t)Q * sizeof(ndt_pg_query));
   size_t slot = 0;
   for (int k = 0; k < Q; ++k) {
@@ -4123,6 +4122,51 @@ int pg_marginals_check(ndt_ctx *ctx, const void *queries, int Q, const char *fn)
   return NDT_OK;
 }
 
+// The bracket of a host-pointer entry point: offsets relative to the first graph's, the call frame, the call's block of d_scan
+// (poses, arcs, then the regions that the entry point takes before open()) and the copies on the frame's stream.  An array of one
+// double per arc is optional on either side: a NULL host pointer copies nothing and gives the kernel NULL.
+struct PgStage {
+  ndt_ctx *ctx;
+  CallFrame fr;
+  Regions U;
+  const size_t G, n0, nn, e0, ne;                      // graphs; first node, nodes, first arc, arcs of the call
+  const std::vector<uint64_t> noff, eoff;
+  const size_t o_pose, o_edge;
+  unsigned char *d = nullptr;
+  PgStage(ndt_ctx *c, const uint64_t *node_off, const uint64_t *edge_off, int n_graphs)
+      : ctx(c), fr(c), G((size_t)n_graphs), n0((size_t)node_off[0]), nn((size_t)node_off[G] - n0), e0((size_t)edge_off[0]),
+        ne((size_t)edge_off[G] - e0), noff(rel_offsets(node_off, G)), eoff(rel_offsets(edge_off, G)), o_pose(U.take(nn * 24 + 8, 256)),
+        o_edge(U.take(ne * sizeof(ndt_pg_edge) + 8, 256)) {}
+  size_t take_arcs() { return U.take(ne * 8 + 8, 256); }
+  int open(const double *poses_host, const ndt_pg_edge *edges_host) {
+    int rc;
+    if ((rc = fr.open()) || (rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
+    d = ctx->d_scan.p;
+    if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, fr.st));
+    if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, fr.st));
+    return NDT_OK;
+  }
+  double *poses() const { return Regions::at<double>(d, o_pose); }
+  const ndt_pg_edge *edges() const { return Regions::at<const ndt_pg_edge>(d, o_edge); }
+  double *arcs(size_t o, const double *host) const { return host ? Regions::at<double>(d, o) : nullptr; }
+  int up_arcs(size_t o, const double *host) {
+    if (ne && host) HIP_TRY(ctx, hipMemcpyAsync(d + o, host + e0, ne * 8, hipMemcpyHostToDevice, fr.st));
+    return NDT_OK;
+  }
+  int down_arcs(size_t o, double *host) {
+    if (ne && host) HIP_TRY(ctx, hipMemcpyAsync(host + e0, d + o, ne * 8, hipMemcpyDeviceToHost, fr.st));
+    return NDT_OK;
+  }
+  int down_poses(double *poses_host) {
+    if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, fr.st));
+    return NDT_OK;
+  }
+  int down(size_t o, void *host, size_t bytes) {
+    HIP_TRY(ctx, hipMemcpyAsync(host, d + o, bytes, hipMemcpyDeviceToHost, fr.st));
+    return NDT_OK;
+  }
+};
+
 // The residual of an arc with the measurement rel between two poses (tx, ty, th[deg]) and its two Jacobian blocks, as
 // pg_linearise and pg_jac (ndt_posegraph.hip.h) state them; rel == NULL: the Jacobians alone.
 void pg_host_arc(const double pa[3], const double pb[3], const double *rel, double r[3], double Ja[9], double Jb[9]) {
@@ -4134,11 +4178,7 @@ void pg_host_arc(const double pa[3], const double pb[3], const double *rel, doub
   if (!rel) return;
   r[0] = c * dx + s * dy - rel[0];
   r[1] = a - rel[1];
-  double w = tb - ta - rel[2] * (M_PI / 180.0);
-  w -= 2.0 * M_PI * std::floor((w + M_PI) / (2.0 * M_PI));
-  if (w >= M_PI) w -= 2.0 * M_PI;
-  if (w < -M_PI) w += 2.0 * M_PI;
-  r[2] = w;
+  r[2] = pg_wrap(tb - ta - rel[2] * (M_PI / 180.0));
 }
 
 // The inverse of a symmetric 3 x 3 given as xx xy xt yy yt tt; false unless it is finite and positive definite (Sylvester).
@@ -4211,9 +4251,8 @@ int ndt_pg_edge_between(const double from_pose[3], const double to_pose[3], ndt_
 
 int ndt_pg_info_from_cov(const double cov_world[9], double th_deg, double info[6]) {
   if (!cov_world || !info) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: NULL pointer");
-  for (int k = 0; k < 9; ++k)
-    if (!(std::fabs(cov_world[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not finite");
-  if (!(std::fabs(th_deg) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the heading is not finite");
+  if (!pg_host_finite(cov_world, 9)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not finite");
+  if (!pg_host_finite(&th_deg, 1)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the heading is not finite");
   const double *C = cov_world;
   if (!(C[0] > 0.0) || !(C[4] > 0.0) || !(C[8] > 0.0)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not positive definite");
   const int pr[3][2] = {{1, 3}, {2, 6}, {5, 7}}, di[3][2] = {{0, 4}, {0, 8}, {4, 8}};
@@ -4240,8 +4279,7 @@ int ndt_pg_info_from_cov(const double cov_world[9], double th_deg, double info[6
     return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the covariance is not positive definite");
   info[0] = c00 / det; info[1] = c01 / det; info[2] = c02 / det;
   info[3] = (xx * tt - xt * xt) / det; info[4] = (xy * xt - xx * yt) / det; info[5] = m2 / det;
-  for (int k = 0; k < 6; ++k)
-    if (!(std::fabs(info[k]) <= DBL_MAX)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the inverse is not finite");
+  if (!pg_host_finite(info, 6)) return fail(nullptr, NDT_E_ARG, "ndt_pg_info_from_cov: the inverse is not finite");
   return NDT_OK;
 }
 
@@ -4259,25 +4297,13 @@ int ndt_pg_optimize_batch(ndt_ctx *ctx, double *poses_host, const uint64_t *node
                           const uint64_t *edge_offsets_host, int n_graphs, const ndt_pg_params *params, ndt_pg_result *out_host) {
   int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params, out_host, "ndt_pg_optimize_batch");
   if (rc) return rc;
-  const size_t G = (size_t)n_graphs;
-  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
-  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
-  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
-  CallFrame fr(ctx);
-  if ((rc = fr.open())) return rc;
-  hipStream_t st = fr.st;
-  Regions U;
-  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256), o_res = U.take(G * sizeof(ndt_pg_result), 256);
-  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
-  unsigned char *d = ctx->d_scan.p;
-  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
-  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
-  if ((rc = queue_pg(ctx, st, (double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs, params,
-                     (ndt_pg_result *)(d + o_res))))
+  PgStage S(ctx, node_offsets_host, edge_offsets_host, n_graphs);
+  const size_t res_bytes = S.G * sizeof(ndt_pg_result), o_res = S.U.take(res_bytes, 256);
+  if ((rc = S.open(poses_host, edges_host)) ||
+      (rc = queue_pg(ctx, S.fr.st, S.poses(), S.noff.data(), S.edges(), S.eoff.data(), n_graphs, params, S.d + o_res)) ||
+      (rc = S.down_poses(poses_host)) || (rc = S.down(o_res, out_host, res_bytes)))
     return rc;
-  if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, G * sizeof(ndt_pg_result), hipMemcpyDeviceToHost, st));
-  return fr.close_and_wait();
+  return S.fr.close_and_wait();
 }
 
 int ndt_pg_robust_default_params(ndt_pg_robust_params *p) {
@@ -4308,31 +4334,16 @@ int ndt_pg_optimize_robust_batch(ndt_ctx *ctx, double *poses_host, const uint64_
   const char *fn = "ndt_pg_optimize_robust_batch";
   int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params ? &params->pg : nullptr, out_host, fn);
   if (rc || (rc = pg_robust_check(ctx, params, fn))) return rc;
-  const size_t G = (size_t)n_graphs;
-  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
-  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
-  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
-  CallFrame fr(ctx);
-  if ((rc = fr.open())) return rc;
-  hipStream_t st = fr.st;
-  Regions U;
-  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256),
-               o_res = U.take(G * sizeof(ndt_pg_robust_result), 256), o_phi = U.take(ne * 8 + 8, 256), o_w = U.take(ne * 8 + 8, 256),
-               o_c = U.take(ne * 8 + 8, 256);
-  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
-  unsigned char *d = ctx->d_scan.p;
-  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
-  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
-  if (ne && phi_host) HIP_TRY(ctx, hipMemcpyAsync(d + o_phi, phi_host + e0, ne * 8, hipMemcpyHostToDevice, st));
-  if ((rc = queue_pg(ctx, st, (double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs, &params->pg,
-                     d + o_res, params, phi_host ? (const double *)(d + o_phi) : nullptr, weight_out_host ? (double *)(d + o_w) : nullptr,
-                     chi2_out_host ? (double *)(d + o_c) : nullptr)))
+  PgStage S(ctx, node_offsets_host, edge_offsets_host, n_graphs);
+  const size_t res_bytes = S.G * sizeof(ndt_pg_robust_result), o_res = S.U.take(res_bytes, 256), o_phi = S.take_arcs(), o_w = S.take_arcs(),
+               o_c = S.take_arcs();
+  if ((rc = S.open(poses_host, edges_host)) || (rc = S.up_arcs(o_phi, phi_host)) ||
+      (rc = queue_pg(ctx, S.fr.st, S.poses(), S.noff.data(), S.edges(), S.eoff.data(), n_graphs, &params->pg, S.d + o_res, params,
+                     S.arcs(o_phi, phi_host), S.arcs(o_w, weight_out_host), S.arcs(o_c, chi2_out_host))) ||
+      (rc = S.down_poses(poses_host)) || (rc = S.down(o_res, out_host, res_bytes)) || (rc = S.down_arcs(o_w, weight_out_host)) ||
+      (rc = S.down_arcs(o_c, chi2_out_host)))
     return rc;
-  if (nn) HIP_TRY(ctx, hipMemcpyAsync(poses_host + 3 * n0, d + o_pose, nn * 24, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, G * sizeof(ndt_pg_robust_result), hipMemcpyDeviceToHost, st));
-  if (ne && weight_out_host) HIP_TRY(ctx, hipMemcpyAsync(weight_out_host + e0, d + o_w, ne * 8, hipMemcpyDeviceToHost, st));
-  if (ne && chi2_out_host) HIP_TRY(ctx, hipMemcpyAsync(chi2_out_host + e0, d + o_c, ne * 8, hipMemcpyDeviceToHost, st));
-  return fr.close_and_wait();
+  return S.fr.close_and_wait();
 }
 
 int ndt_pg_marginals_batch_dev(ndt_ctx *ctx, const double *poses_dev, const uint64_t *node_offsets_host, const ndt_pg_edge *edges_dev,
@@ -4355,27 +4366,14 @@ int ndt_pg_marginals_batch(ndt_ctx *ctx, const double *poses_host, const uint64_
   const char *fn = "ndt_pg_marginals_batch";
   int rc = pg_check(ctx, poses_host, node_offsets_host, edges_host, edge_offsets_host, n_graphs, params, out_host, fn);
   if (rc || (rc = pg_marginals_check(ctx, queries_host, n_queries, fn))) return rc;
-  const size_t G = (size_t)n_graphs, Q = (size_t)n_queries;
-  const size_t n0 = (size_t)node_offsets_host[0], nn = (size_t)node_offsets_host[G] - n0;
-  const size_t e0 = (size_t)edge_offsets_host[0], ne = (size_t)edge_offsets_host[G] - e0;
-  const std::vector<uint64_t> noff = rel_offsets(node_offsets_host, G), eoff = rel_offsets(edge_offsets_host, G);
-  CallFrame fr(ctx);
-  if ((rc = fr.open())) return rc;
-  hipStream_t st = fr.st;
-  Regions U;
-  const size_t o_pose = U.take(nn * 24 + 8, 256), o_edge = U.take(ne * sizeof(ndt_pg_edge) + 8, 256), o_w = U.take(ne * 8 + 8, 256),
-               o_res = U.take(Q * sizeof(ndt_pg_marginal), 256);
-  if ((rc = ctx->d_scan.ensure(ctx, U.end))) return rc;
-  unsigned char *d = ctx->d_scan.p;
-  if (nn) HIP_TRY(ctx, hipMemcpyAsync(d + o_pose, poses_host + 3 * n0, nn * 24, hipMemcpyHostToDevice, st));
-  if (ne) HIP_TRY(ctx, hipMemcpyAsync(d + o_edge, edges_host + e0, ne * sizeof(ndt_pg_edge), hipMemcpyHostToDevice, st));
-  if (ne && weight_host) HIP_TRY(ctx, hipMemcpyAsync(d + o_w, weight_host + e0, ne * 8, hipMemcpyHostToDevice, st));
-  if ((rc = queue_pg_marginals(ctx, st, (const double *)(d + o_pose), noff.data(), (const ndt_pg_edge *)(d + o_edge), eoff.data(), n_graphs,
-                               weight_host ? (const double *)(d + o_w) : nullptr, queries_host, n_queries, params,
-                               (ndt_pg_marginal *)(d + o_res))))
+  PgStage S(ctx, node_offsets_host, edge_offsets_host, n_graphs);
+  const size_t o_w = S.take_arcs(), res_bytes = (size_t)n_queries * sizeof(ndt_pg_marginal), o_res = S.U.take(res_bytes, 256);
+  if ((rc = S.open(poses_host, edges_host)) || (rc = S.up_arcs(o_w, weight_host)) ||
+      (rc = queue_pg_marginals(ctx, S.fr.st, S.poses(), S.noff.data(), S.edges(), S.eoff.data(), n_graphs, S.arcs(o_w, weight_host),
+                               queries_host, n_queries, params, Regions::at<ndt_pg_marginal>(S.d, o_res))) ||
+      (rc = S.down(o_res, out_host, res_bytes)))
     return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_host, d + o_res, Q * sizeof(ndt_pg_marginal), hipMemcpyDeviceToHost, st));
-  return fr.close_and_wait();
+  return S.fr.close_and_wait();
 }
 
 int ndt_pg_relative_cov(const double pose_a[3], const double pose_b[3], const ndt_pg_marginal *m, double cov[9]) {

@@ -7,6 +7,9 @@
 // barrier; only H p (reads the neighbours' p), the preconditioner (a serial block-Thomas sweep) and the dot products do.
 // No floating-point atomics: a node sums its arcs' blocks in arc-index order (its list is cut out of a sorted key array),
 // and a dot product is each thread's nodes in index order, a fixed wave tree, then the four waves in order.
+// The solver (pg_solve_kernel, plain and robust) and the marginals (pg_marginal_kernel) share every step but
+// their conjugate-gradient loops: pg_graph_bad, pg_arc_order, pg_radians, pg_node_blocks, pg_arc_hp, pg_factor, pg_apply<K>,
+// pg_block_sum_cols<N>, and the tail of the scratch (PgTail, PgWork).
 
 constexpr double kPgPi = 3.14159265358979323846;
 constexpr int kPgChunk = 64;                       // nodes of one staged piece of a block-Thomas sweep
@@ -26,26 +29,49 @@ struct PgRobust { double mu0, factor, eps_level; int level_iter, pad; };
 constexpr double kPgMuMax = 1e12;
 
 // An arc linearised at the current poses: cos / sin of the `from` heading, d r_xy / d theta_from = (a, b), the residual.
-// pad: the robust form keeps the arc's weight at those poses there (1.0 for a plain arc); the plain form leaves it 0 and unread.
-struct PgLin { double c, s, a, b, r0, r1, r2, pad; };
+// wt: the arc's weight (the robust form: at those poses, 1.0 for a plain arc; the marginals: as given); the plain form leaves it 0
+// and unread.
+struct PgLin { double c, s, a, b, r0, r1, r2, wt; };
 
-// The regions of one graph's scratch, in doubles from its start (host and device agree by calling this one function).
-struct PgLayout {
-  size_t x, xt, g, dl, r, z, p, q, y, D, U, L, Si, W, lin, keys, ptr, end;
+// What every scratch ends with, in doubles from the scratch's start: the linear system's blocks, the chain factor, the
+// linearised arcs and the arc order.  `o`: where it starts, behind the vectors that a layout puts in front of it.
+struct PgTail {
+  size_t D, U, L, Si, W, lin, keys, ptr, end;
+  __host__ __device__ static PgTail at(size_t o, size_t n, size_t m, size_t n2) {
+    PgTail t;
+    t.D = o; o += 6 * n; t.U = o; o += 9 * n; t.L = o; o += 9 * n; t.Si = o; o += 6 * n; t.W = o; o += 9 * n;
+    t.lin = o; o += 8 * m; t.keys = o; o += n2; t.ptr = o; o += (n + 2) / 2 + 1;
+    t.end = o;
+    return t;
+  }
+};
+
+// The regions of one graph's scratch (host and device agree by calling this one function).
+struct PgLayout : PgTail {
+  size_t x, xt, g, dl, r, z, p, q, y;
   __host__ __device__ PgLayout(size_t n, size_t m, size_t n2) {
     size_t o = 0;
     x = o; o += 3 * n; xt = o; o += 3 * n; g = o; o += 3 * n; dl = o; o += 3 * n; r = o; o += 3 * n; z = o; o += 3 * n;
     p = o; o += 3 * n; q = o; o += 3 * n; y = o; o += 3 * n;
-    D = o; o += 6 * n; U = o; o += 9 * n; L = o; o += 9 * n; Si = o; o += 6 * n; W = o; o += 9 * n;
-    lin = o; o += 8 * m; keys = o; o += n2; ptr = o; o += (n + 2) / 2 + 1;
-    end = o;
+    static_cast<PgTail &>(*this) = PgTail::at(o, n, m, n2);
   }
+};
+
+// The tail's regions of the scratch at `base` as pointers.
+struct PgWork {
+  double *D, *U, *L, *Si, *W;
+  PgLin *lin;
+  unsigned long long *keys;
+  int *ptr;
+  __device__ PgWork(double *base, const PgTail &T)
+      : D(base + T.D), U(base + T.U), L(base + T.L), Si(base + T.Si), W(base + T.W), lin(reinterpret_cast<PgLin *>(base + T.lin)),
+        keys(reinterpret_cast<unsigned long long *>(base + T.keys)), ptr(reinterpret_cast<int *>(base + T.ptr)) {}
 };
 
 __device__ __forceinline__ bool pg_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // into [-pi, pi)
-__device__ __forceinline__ double pg_wrap(double v) {
+__host__ __device__ __forceinline__ double pg_wrap(double v) {
   double w = v - 2.0 * kPgPi * floor((v + kPgPi) / (2.0 * kPgPi));
   if (w >= kPgPi) w -= 2.0 * kPgPi;
   if (w < -kPgPi) w += 2.0 * kPgPi;
@@ -59,14 +85,23 @@ __device__ __forceinline__ double pg_wrap_deg(double v) {
   return w;
 }
 
-// Sum over the workgroup in a fixed shape: the wave tree, then the four waves in order.  Every thread gets the same bits.
+// Sums over the workgroup in a fixed shape, N values at once (s_w: 4 N doubles of LDS): each value goes through the wave tree,
+// then the four waves in order.  Every thread gets the same bits.  Two barriers: called under block-uniform conditions only.
+template <int N>
+__device__ __forceinline__ void pg_block_sum_cols(double v[N], double *s_w) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double t = wave_sum(v[k]);
+    if ((threadIdx.x & 63) == 0) s_w[(threadIdx.x >> 6) * N + k] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = ((s_w[k] + s_w[N + k]) + s_w[2 * N + k]) + s_w[3 * N + k];
+  __syncthreads();
+}
 __device__ __forceinline__ double pg_block_sum(double v, double *s_w) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double t = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-  __syncthreads();
-  return t;
+  pg_block_sum_cols<1>(&v, s_w);
+  return v;
 }
 __device__ __forceinline__ double pg_block_max(double v, double *s_w) {
   v = wave_max(v);
@@ -88,7 +123,7 @@ __device__ __forceinline__ PgLin pg_linearise(const double *__restrict__ X, cons
   l.r0 = l.c * dx + l.s * dy - E.rel[0];
   l.r1 = l.a - E.rel[1];
   l.r2 = pg_wrap(xj[2] - xi[2] - E.rel[2] * (kPgPi / 180.0));
-  l.pad = 0.0;
+  l.wt = 0.0;
   return l;
 }
 
@@ -253,65 +288,179 @@ __device__ bool pg_factor(const double *__restrict__ D, const double *__restrict
   return true;
 }
 
-// z = T^-1 r with the factor above: y_i = r_i - L_i y_{i-1} upwards, v_i = S_i^-1 y_i, z_i = v_i - W_i z_{i+1} downwards.
-// Ends behind a barrier: every thread may read z.
-__device__ void pg_apply(const double *__restrict__ L, const double *__restrict__ Si, const double *__restrict__ W, const double *__restrict__ r,
-                         double *__restrict__ y, double *__restrict__ z, int n, double *sh) {
+// One staged piece of a sweep of pg_apply: the nodes i0 .. i0 + cn - 1 of M (L or W) and of `in` into LDS, lane k of wave 0
+// takes column k through them (upwards, or downwards for DOWN) as v_i = in_i - M_i c with c the value before, `out` from LDS.
+template <int K, bool DOWN>
+__device__ __forceinline__ void pg_sweep_chunk(const double *__restrict__ M, const double *in, double *out, int i0, int cn, double c[3],
+                                               double *sh) {
+  constexpr int K3 = 3 * K, per = 9 + K3;          // doubles of one staged node: M_i, then K triples
+  static_assert(per <= 30, "staged in the LDS that pg_factor uses");
   const int tid = (int)threadIdx.x;
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0;             // the lane's carry: y_{i-1}, then z_{i+1}
-  for (int i0 = 1; i0 < n; i0 += kPgChunk) {
-    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
-    for (int idx = tid; idx < cn * 12; idx += kPgThreads) {
-      const int a = idx / 12, k = idx % 12, i = i0 + a;
-      sh[a * 16 + k] = k < 9 ? L[9 * (size_t)i + k] : r[3 * (size_t)i + (k - 9)];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (int a = 0; a < cn; ++a) {
-        double *q = sh + a * 16;
-        const double y0 = q[9] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
-        const double y1 = q[10] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
-        const double y2 = q[11] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
-        q[12] = y0; q[13] = y1; q[14] = y2;
-        c0 = y0; c1 = y1; c2 = y2;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < cn * 3; idx += kPgThreads) y[3 * (size_t)(i0 + idx / 3) + idx % 3] = sh[(idx / 3) * 16 + 12 + idx % 3];
-    __syncthreads();
-  }
-  for (int i = 1 + tid; i < n; i += kPgThreads) {
-    const double *s = Si + 6 * (size_t)i;
-    const double a = y[3 * (size_t)i], b = y[3 * (size_t)i + 1], c = y[3 * (size_t)i + 2];
-    y[3 * (size_t)i] = (s[0] * a + s[1] * b) + s[2] * c;
-    y[3 * (size_t)i + 1] = (s[1] * a + s[3] * b) + s[4] * c;
-    y[3 * (size_t)i + 2] = (s[2] * a + s[4] * b) + s[5] * c;
+  for (int idx = tid; idx < cn * per; idx += kPgThreads) {
+    const int k = idx % per, i = i0 + idx / per;
+    sh[idx] = k < 9 ? M[9 * (size_t)i + k] : in[(size_t)K3 * i + (k - 9)];
   }
   __syncthreads();
-  c0 = c1 = c2 = 0.0;
-  const int chunks = (n - 1 + kPgChunk - 1) / kPgChunk;
-  for (int ch = chunks - 1; ch >= 0; --ch) {
-    const int i0 = 1 + ch * kPgChunk;
-    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
-    for (int idx = tid; idx < cn * 12; idx += kPgThreads) {
-      const int a = idx / 12, k = idx % 12, i = i0 + a;
-      sh[a * 16 + k] = k < 9 ? W[9 * (size_t)i + k] : y[3 * (size_t)i + (k - 9)];
+  if (tid < K) {
+    for (int t = 0; t < cn; ++t) {
+      const double *q = sh + (DOWN ? cn - 1 - t : t) * per;
+      double *v = sh + (DOWN ? cn - 1 - t : t) * per + 9 + 3 * tid;
+      const double v0 = v[0] - ((q[0] * c[0] + q[1] * c[1]) + q[2] * c[2]);
+      const double v1 = v[1] - ((q[3] * c[0] + q[4] * c[1]) + q[5] * c[2]);
+      const double v2 = v[2] - ((q[6] * c[0] + q[7] * c[1]) + q[8] * c[2]);
+      v[0] = v0; v[1] = v1; v[2] = v2;
+      c[0] = v0; c[1] = v1; c[2] = v2;
     }
-    __syncthreads();
-    if (tid == 0) {
-      for (int a = cn - 1; a >= 0; --a) {
-        double *q = sh + a * 16;
-        const double z0 = q[9] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
-        const double z1 = q[10] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
-        const double z2 = q[11] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
-        q[12] = z0; q[13] = z1; q[14] = z2;
-        c0 = z0; c1 = z1; c2 = z2;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < cn * 3; idx += kPgThreads) z[3 * (size_t)(i0 + idx / 3) + idx % 3] = sh[(idx / 3) * 16 + 12 + idx % 3];
-    __syncthreads();
   }
+  __syncthreads();
+  for (int idx = tid; idx < cn * K3; idx += kPgThreads) out[(size_t)K3 * (i0 + idx / K3) + idx % K3] = sh[(idx / K3) * per + 9 + idx % K3];
+  __syncthreads();
+}
+
+// z = T^-1 r with the factor above for K right-hand sides, laid out [node][column][3] (K = 1: the solver's [node][3]):
+// y_i = r_i - L_i y_{i-1} upwards, v_i = S_i^-1 y_i, z_i = v_i - W_i z_{i+1} downwards.  Lane k of wave 0 carries column k; every
+// lane reads the same L_i / W_i from LDS (a broadcast), so one trip up and one trip down serve all K columns, and a column's
+// arithmetic is the same at every K.  Contains barriers: called under block-uniform conditions only.  Ends behind a barrier:
+// every thread may read z.
+template <int K>
+__device__ void pg_apply(const PgWork &Wk, const double *__restrict__ r, double *__restrict__ y, double *__restrict__ z, int n, double *sh) {
+  const int tid = (int)threadIdx.x;
+  double c[3] = {0.0, 0.0, 0.0};                   // the lane's carry: y_{i-1} of its column, then z_{i+1}
+  for (int i0 = 1; i0 < n; i0 += kPgChunk) pg_sweep_chunk<K, false>(Wk.L, r, y, i0, n - i0 < kPgChunk ? n - i0 : kPgChunk, c, sh);
+  for (int idx = tid; idx < (n - 1) * K; idx += kPgThreads) {
+    const double *s = Wk.Si + 6 * (size_t)(1 + idx / K);
+    double *v = y + 3 * ((size_t)K + idx);         // (node 1 + idx / K, column idx % K)
+    const double a = v[0], b = v[1], d = v[2];
+    v[0] = (s[0] * a + s[1] * b) + s[2] * d;
+    v[1] = (s[1] * a + s[3] * b) + s[4] * d;
+    v[2] = (s[2] * a + s[4] * b) + s[5] * d;
+  }
+  __syncthreads();
+  c[0] = c[1] = c[2] = 0.0;
+  for (int i0 = 1 + (n - 2) / kPgChunk * kPgChunk; i0 >= 1; i0 -= kPgChunk)
+    pg_sweep_chunk<K, true>(Wk.W, y, z, i0, n - i0 < kPgChunk ? n - i0 : kPgChunk, c, sh);
+}
+
+// ---- what the solver and the marginals share of a graph's set-up and of H p.  The functions that contain a barrier are called
+// under block-uniform conditions only: every decision of either kernel comes from the launch's arguments or from block sums
+// that all threads hold with the same bits. ----
+
+// The graph's own faults: a pose, rel or info that is not finite, an arc end out of range or a loop on one node, an info that is
+// not positive definite, an entry of arc_scalar (the graph's phi or weight, indexed like ed; NULL: none) that is negative or
+// not finite.  Nonzero in every thread if any thread found one.  Contains a barrier.
+__device__ __forceinline__ int pg_graph_bad(const double *__restrict__ pose, const ndt_pg_edge *__restrict__ ed, int n, int m,
+                                            const double *__restrict__ arc_scalar) {
+  const int tid = (int)threadIdx.x;
+  int bad = 0;
+  for (int i = tid; i < n; i += kPgThreads)
+    if (!pg_finite(pose[3 * (size_t)i]) || !pg_finite(pose[3 * (size_t)i + 1]) || !pg_finite(pose[3 * (size_t)i + 2])) bad = 1;
+  for (int e = tid; e < m; e += kPgThreads) {
+    const ndt_pg_edge E = ed[e];
+    if (E.from < 0 || E.from >= n || E.to < 0 || E.to >= n || E.from == E.to) bad = 1;
+    bool fin = pg_finite(E.rel[0]) && pg_finite(E.rel[1]) && pg_finite(E.rel[2]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fin = fin && pg_finite(E.info[k]);
+    const double *I = E.info;
+    const double m2 = I[0] * I[3] - I[1] * I[1];
+    const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
+    if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
+    if (arc_scalar && (!(arc_scalar[e] >= 0.0) || !pg_finite(arc_scalar[e]))) bad = 1;
+  }
+  return __syncthreads_or(bad);
+}
+
+// Every node's arcs in arc-index order: the keys (node, 2 e + side) of the 2 m arc ends, padded to n2, sorted, then cut at the
+// nodes -- node i's arc ends are keys[ptr[i] .. ptr[i + 1]).  Contains barriers (the sort's).  Ends behind none: ptr is written
+// last, and the barrier behind the caller's pg_radians is the one that lets every thread read it.
+__device__ __forceinline__ void pg_arc_order(const ndt_pg_edge *__restrict__ ed, int n, int m, unsigned n2, unsigned long long *keys, int *ptr) {
+  const unsigned tid = threadIdx.x, m2e = 2u * (unsigned)m;
+  for (unsigned k = tid; k < n2; k += kPgThreads) {
+    unsigned long long key = ~0ull;
+    if (k < m2e) { const ndt_pg_edge &E = ed[k >> 1]; key = ((unsigned long long)(unsigned)((k & 1u) ? E.to : E.from) << 32) | k; }
+    keys[k] = key;
+  }
+  __syncthreads();
+  for (unsigned kk = 2; kk <= n2; kk <<= 1)
+    for (unsigned j = kk >> 1; j > 0; j >>= 1) {
+      for (unsigned i = tid; i < n2; i += kPgThreads) {
+        const unsigned l = i ^ j;
+        if (l > i) {
+          const unsigned long long a = keys[i], b = keys[l];
+          if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  for (unsigned k = tid; k <= m2e; k += kPgThreads) {
+    const int node = k < m2e ? (int)(keys[k] >> 32) : n;
+    const int prev = k > 0 ? (int)(keys[k - 1] >> 32) : -1;
+    for (int v = prev + 1; v <= node; ++v) ptr[v] = (int)k;
+  }
+}
+
+// x = the poses with the heading in radians.  No barrier: the caller's follows.
+__device__ __forceinline__ void pg_radians(const double *__restrict__ pose, double *__restrict__ x, int n) {
+  for (int i = (int)threadIdx.x; i < n; i += kPgThreads) {
+    x[3 * (size_t)i] = pose[3 * (size_t)i]; x[3 * (size_t)i + 1] = pose[3 * (size_t)i + 1];
+    x[3 * (size_t)i + 2] = pose[3 * (size_t)i + 2] * (kPgPi / 180.0);
+  }
+}
+
+// Node i's diagonal block D_i (six entries) and chain block U_i of H from its arc list, the arcs as linearised in Wk.lin; GRAD:
+// g3 = its entries of the gradient, summed in the same walk.  ROBUST: every term times the arc's weight (pg_block_add).
+template <bool ROBUST, bool GRAD>
+__device__ __forceinline__ void pg_node_blocks(const PgWork &Wk, const ndt_pg_edge *__restrict__ ed, int i, double g3[3]) {
+  double Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (GRAD) { g3[0] = 0.0; g3[1] = 0.0; g3[2] = 0.0; }
+  for (int k = Wk.ptr[i]; k < Wk.ptr[i + 1]; ++k) {
+    const unsigned slot = (unsigned)Wk.keys[k];
+    const int e = (int)(slot >> 1), side = (int)(slot & 1u);
+    const PgLin l = Wk.lin[e];
+    const double *I = ed[e].info;
+    const int other = side ? ed[e].from : ed[e].to;
+    double Js[9], Jo[9];
+    pg_jac(l, side, Js);
+    if constexpr (GRAD) {
+      const double rr[3] = {l.r0, l.r1, l.r2};
+      double w[3], o[3];
+      pg_info_mul(I, rr, w);
+      pg_jt_mul(Js, w, o);
+      if constexpr (ROBUST) { g3[0] += l.wt * o[0]; g3[1] += l.wt * o[1]; g3[2] += l.wt * o[2]; }
+      else { g3[0] += o[0]; g3[1] += o[1]; g3[2] += o[2]; }
+    }
+    pg_block_add<ROBUST>(Js, I, Js, l.wt, Dm);
+    if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add<ROBUST>(Js, I, Jo, l.wt, Um); }
+  }
+  double *d = Wk.D + 6 * (size_t)i;
+  d[0] = Dm[0]; d[1] = Dm[1]; d[2] = Dm[2]; d[3] = Dm[4]; d[4] = Dm[5]; d[5] = Dm[8];
+  for (int k = 0; k < 9; ++k) Wk.U[9 * (size_t)i + k] = Um[k];
+}
+
+// One arc's term of H p at the node whose Jacobian block is Js: q += [wt] Js^T Omega (Js p_i + Jo p_other)
+template <bool ROBUST>
+__device__ __forceinline__ void pg_arc_hp(const double Js[9], const double Jo[9], const double *__restrict__ I, double wt, const double pi3[3],
+                                          const double po3[3], double q[3]) {
+  double u1[3], u2[3], w[3], o[3];
+  pg_j_mul(Js, pi3, u1); pg_j_mul(Jo, po3, u2);
+  const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
+  pg_info_mul(I, u, w);
+  pg_jt_mul(Js, w, o);
+  if constexpr (ROBUST) { q[0] += wt * o[0]; q[1] += wt * o[1]; q[2] += wt * o[2]; }
+  else { q[0] += o[0]; q[1] += o[1]; q[2] += o[2]; }
+}
+
+// The record of one graph; the robust record nests it.
+__device__ __forceinline__ ndt_pg_result pg_record(double cost_initial, double cost_final, int iterations, int cg_iterations, int converged,
+                                                   int status) {
+  ndt_pg_result res;
+  res.cost_initial = cost_initial; res.cost_final = cost_final; res.iterations = iterations; res.cg_iterations = cg_iterations;
+  res.converged = converged; res.status = status;
+  return res;
+}
+__device__ __forceinline__ ndt_pg_robust_result pg_robust_record(const ndt_pg_result &pg, double mu0, int levels, int n_robust, int n_rejected) {
+  ndt_pg_robust_result res;
+  res.pg = pg; res.mu0 = mu0; res.levels = levels; res.n_robust = n_robust; res.n_rejected = n_rejected; res.pad = 0;
+  return res;
 }
 
 // What the robust form's launch carries beside the plain one's arguments, and the record either form writes.
@@ -347,80 +496,31 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
     double *weight_out = nullptr, *chi2_out = nullptr;
     if constexpr (ROBUST) { gphi = X.phi ? X.phi + R.edge0 : nullptr; weight_out = X.weight_out; chi2_out = X.chi2_out; }
     // ---- the graph's own faults: found here, the poses stay as they are ----
-    int bad = 0;
-    for (int i = tid; i < n; i += kPgThreads)
-      if (!pg_finite(pose[3 * (size_t)i]) || !pg_finite(pose[3 * (size_t)i + 1]) || !pg_finite(pose[3 * (size_t)i + 2])) bad = 1;
-    for (int e = tid; e < m; e += kPgThreads) {
-      const ndt_pg_edge E = ed[e];
-      if (E.from < 0 || E.from >= n || E.to < 0 || E.to >= n || E.from == E.to) bad = 1;
-      bool fin = pg_finite(E.rel[0]) && pg_finite(E.rel[1]) && pg_finite(E.rel[2]);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) fin = fin && pg_finite(E.info[k]);
-      const double *I = E.info;
-      const double m2 = I[0] * I[3] - I[1] * I[1];
-      const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
-      if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
-      if constexpr (ROBUST)
-        if (gphi && (!(gphi[e] >= 0.0) || !pg_finite(gphi[e]))) bad = 1;
-    }
-    bad = __syncthreads_or(bad);
+    const int bad = pg_graph_bad(pose, ed, n, m, gphi);
     if (bad || m == 0) {
-      if constexpr (ROBUST) {
-        for (int e = tid; e < m; e += kPgThreads) {            // (a faulted graph's arc outputs are 0)
+      if constexpr (ROBUST)
+        for (int e = tid; e < m; e += kPgThreads) {              // (a faulted graph's arc outputs are 0)
           if (weight_out) weight_out[R.edge0 + e] = 0.0;
           if (chi2_out) chi2_out[R.edge0 + e] = 0.0;
         }
-        if (tid == 0) {
-          ndt_pg_robust_result res;
-          res.pg.cost_initial = 0.0; res.pg.cost_final = 0.0; res.pg.iterations = 0; res.pg.cg_iterations = 0;
-          res.pg.converged = bad ? 0 : 1; res.pg.status = bad ? NDT_E_ARG : NDT_OK;
-          res.mu0 = bad ? 0.0 : 1.0; res.levels = bad ? 0 : 1; res.n_robust = 0; res.n_rejected = 0; res.pad = 0;
-          out[gi] = res;
-        }
-      } else if (tid == 0) {
-        ndt_pg_result res;
-        res.cost_initial = 0.0; res.cost_final = 0.0; res.iterations = 0; res.cg_iterations = 0;
-        res.converged = bad ? 0 : 1; res.status = bad ? NDT_E_ARG : NDT_OK;
-        out[gi] = res;
+      if (tid == 0) {
+        const ndt_pg_result res = pg_record(0.0, 0.0, 0, 0, bad ? 0 : 1, bad ? NDT_E_ARG : NDT_OK);
+        if constexpr (ROBUST) out[gi] = pg_robust_record(res, bad ? 0.0 : 1.0, bad ? 0 : 1, 0, 0);
+        else out[gi] = res;
       }
       continue;
     }
     double *base = reinterpret_cast<double *>(scratch + R.scratch);
     const PgLayout Y((size_t)n, (size_t)m, (size_t)R.n2);
     double *x = base + Y.x, *xt = base + Y.xt, *g = base + Y.g, *dl = base + Y.dl, *r = base + Y.r, *z = base + Y.z, *p = base + Y.p,
-           *q = base + Y.q, *y = base + Y.y, *D = base + Y.D, *U = base + Y.U, *L = base + Y.L, *Si = base + Y.Si, *W = base + Y.W;
-    PgLin *lin = reinterpret_cast<PgLin *>(base + Y.lin);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + Y.keys);
-    int *ptr = reinterpret_cast<int *>(base + Y.ptr);
-    // ---- every node's arcs in arc-index order: keys (node, 2 e + side) sorted, then cut at the nodes ----
-    const unsigned n2 = R.n2, m2e = 2u * (unsigned)m;
-    for (unsigned k = (unsigned)tid; k < n2; k += kPgThreads) {
-      unsigned long long key = ~0ull;
-      if (k < m2e) { const ndt_pg_edge &E = ed[k >> 1]; key = ((unsigned long long)(unsigned)((k & 1u) ? E.to : E.from) << 32) | k; }
-      keys[k] = key;
-    }
-    __syncthreads();
-    for (unsigned kk = 2; kk <= n2; kk <<= 1)
-      for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-        for (unsigned i = (unsigned)tid; i < n2; i += kPgThreads) {
-          const unsigned l = i ^ j;
-          if (l > i) {
-            const unsigned long long a = keys[i], b = keys[l];
-            if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    for (unsigned k = (unsigned)tid; k <= m2e; k += kPgThreads) {
-      const int node = k < m2e ? (int)(keys[k] >> 32) : n;
-      const int prev = k > 0 ? (int)(keys[k - 1] >> 32) : -1;
-      for (int v = prev + 1; v <= node; ++v) ptr[v] = (int)k;
-    }
-    // ---- the poses in radians; node 0's entries of the solver's vectors stay zero ----
-    for (int i = tid; i < n; i += kPgThreads) {
-      x[3 * (size_t)i] = pose[3 * (size_t)i]; x[3 * (size_t)i + 1] = pose[3 * (size_t)i + 1];
-      x[3 * (size_t)i + 2] = pose[3 * (size_t)i + 2] * (kPgPi / 180.0);
-    }
+           *q = base + Y.q, *y = base + Y.y;
+    const PgWork Wk(base, Y);
+    const unsigned long long *keys = Wk.keys;
+    const int *ptr = Wk.ptr;
+    PgLin *lin = Wk.lin;
+    // ---- every node's arcs in arc-index order, the poses in radians; node 0's entries of the solver's vectors stay zero ----
+    pg_arc_order(ed, n, m, R.n2, Wk.keys, Wk.ptr);
+    pg_radians(pose, x, n);
     if (tid < 3) { g[tid] = 0.0; dl[tid] = 0.0; r[tid] = 0.0; z[tid] = 0.0; p[tid] = 0.0; q[tid] = 0.0; y[tid] = 0.0; }
     __syncthreads();
     // ---- the robust form's start: the robust arcs counted, mu0 = max(1, 2 max c_e / phi_e) over them unless it is given ----
@@ -450,37 +550,19 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
         PgLin l = pg_linearise(x, ed[e]);
         if constexpr (ROBUST) {
           const double ph = gphi ? gphi[e] : 0.0;
-          l.pad = ph > 0.0 ? pg_weight(pg_chi2(l, ed[e].info), mu * ph) : 1.0;
+          l.wt = ph > 0.0 ? pg_weight(pg_chi2(l, ed[e].info), mu * ph) : 1.0;
         }
         lin[e] = l;
       }
       __syncthreads();
       for (int i = 1 + tid; i < n; i += kPgThreads) {
-        double gi3[3] = {0, 0, 0}, Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = ptr[i]; k < ptr[i + 1]; ++k) {
-          const unsigned slot = (unsigned)keys[k];
-          const int e = (int)(slot >> 1), side = (int)(slot & 1u);
-          const PgLin l = lin[e];
-          const double *I = ed[e].info;
-          const int other = side ? ed[e].from : ed[e].to;
-          double Js[9], Jo[9], w[3], o[3];
-          pg_jac(l, side, Js);
-          const double rr[3] = {l.r0, l.r1, l.r2};
-          pg_info_mul(I, rr, w);
-          pg_jt_mul(Js, w, o);
-          if constexpr (ROBUST) { gi3[0] += l.pad * o[0]; gi3[1] += l.pad * o[1]; gi3[2] += l.pad * o[2]; }
-          else { gi3[0] += o[0]; gi3[1] += o[1]; gi3[2] += o[2]; }
-          pg_block_add<ROBUST>(Js, I, Js, l.pad, Dm);
-          if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add<ROBUST>(Js, I, Jo, l.pad, Um); }
-        }
+        double gi3[3];
+        pg_node_blocks<ROBUST, true>(Wk, ed, i, gi3);
         for (int k = 0; k < 3; ++k) { g[3 * (size_t)i + k] = gi3[k]; dl[3 * (size_t)i + k] = 0.0; r[3 * (size_t)i + k] = -gi3[k]; }
-        double *d = D + 6 * (size_t)i;
-        d[0] = Dm[0]; d[1] = Dm[1]; d[2] = Dm[2]; d[3] = Dm[4]; d[4] = Dm[5]; d[5] = Dm[8];
-        for (int k = 0; k < 9; ++k) U[9 * (size_t)i + k] = Um[k];
       }
       __syncthreads();
-      if (!pg_factor(D, U, L, Si, W, n, sh, &s_ok)) break;
-      pg_apply(L, Si, W, r, y, z, n, sh);
+      if (!pg_factor(Wk.D, Wk.U, Wk.L, Wk.Si, Wk.W, n, sh, &s_ok)) break;
+      pg_apply<1>(Wk, r, y, z, n, sh);
       double acc = 0.0;
       for (int i = 1 + tid; i < n; i += kPgThreads)
         for (int k = 0; k < 3; ++k) { const double zv = z[3 * (size_t)i + k]; p[3 * (size_t)i + k] = zv; acc += r[3 * (size_t)i + k] * zv; }
@@ -501,14 +583,9 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
               const PgLin l = lin[e];
               const int other = side ? ed[e].from : ed[e].to;
               const double po[3] = {p[3 * (size_t)other], p[3 * (size_t)other + 1], p[3 * (size_t)other + 2]};
-              double Js[9], Jo[9], u1[3], u2[3], w[3], o[3];
+              double Js[9], Jo[9];
               pg_jac(l, side, Js); pg_jac(l, side ^ 1, Jo);
-              pg_j_mul(Js, pi3, u1); pg_j_mul(Jo, po, u2);
-              const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
-              pg_info_mul(ed[e].info, u, w);
-              pg_jt_mul(Js, w, o);
-              if constexpr (ROBUST) { qi[0] += l.pad * o[0]; qi[1] += l.pad * o[1]; qi[2] += l.pad * o[2]; }
-              else { qi[0] += o[0]; qi[1] += o[1]; qi[2] += o[2]; }
+              pg_arc_hp<ROBUST>(Js, Jo, ed[e].info, l.wt, pi3, po, qi);
             }
             for (int c = 0; c < 3; ++c) { q[3 * (size_t)i + c] = qi[c]; acc += pi3[c] * qi[c]; }
           }
@@ -519,7 +596,7 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
           for (int i = 1 + tid; i < n; i += kPgThreads)
             for (int c = 0; c < 3; ++c) { dl[3 * (size_t)i + c] += alpha * p[3 * (size_t)i + c]; r[3 * (size_t)i + c] -= alpha * q[3 * (size_t)i + c]; }
           __syncthreads();
-          pg_apply(L, Si, W, r, y, z, n, sh);
+          pg_apply<1>(Wk, r, y, z, n, sh);
           acc = 0.0;
           for (int i = 1 + tid; i < n; i += kPgThreads)
             for (int c = 0; c < 3; ++c) acc += r[3 * (size_t)i + c] * z[3 * (size_t)i + c];
@@ -602,17 +679,9 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
       }
       const int n_rejected = (int)pg_block_sum(cnt, s_w);
       if (mu > 1.0) F = pg_cost<true>(x, ed, m, s_w, gphi, 1.0);     // (the run ended inside a level)
-      if (tid == 0) {
-        ndt_pg_robust_result res;
-        res.pg.cost_initial = F0; res.pg.cost_final = F; res.pg.iterations = iters; res.pg.cg_iterations = cg_total; res.pg.converged = conv;
-        res.pg.status = NDT_OK;
-        res.mu0 = mu_start; res.levels = levels; res.n_robust = n_robust; res.n_rejected = n_rejected; res.pad = 0;
-        out[gi] = res;
-      }
+      if (tid == 0) out[gi] = pg_robust_record(pg_record(F0, F, iters, cg_total, conv, NDT_OK), mu_start, levels, n_robust, n_rejected);
     } else if (tid == 0) {
-      ndt_pg_result res;
-      res.cost_initial = F0; res.cost_final = F; res.iterations = iters; res.cg_iterations = cg_total; res.converged = conv; res.status = NDT_OK;
-      out[gi] = res;
+      out[gi] = pg_record(F0, F, iters, cg_total, conv, NDT_OK);
     }
     __syncthreads();
   }
@@ -620,104 +689,26 @@ pg_solve_kernel(double *__restrict__ poses, const ndt_pg_edge *__restrict__ edge
 
 // ---- ndt_pg_marginals_batch: blocks of H^-1 at the poses given (the contract is the header's) ----
 // A query (graph, a, b) is the three unit columns of each of its free nodes solved against the one factor: K = 3 or 6
-// right-hand sides that share every H p walk and every block-Thomas sweep.  The vectors are laid out [node][column][3]; a
-// column's arithmetic is the same instructions in every slot and touches no other column's numbers, so its solution is a
-// function of (graph, weights, node, column) alone.
+// right-hand sides that share every H p walk and every block-Thomas sweep (pg_apply<K>).  The vectors are laid out
+// [node][column][3]; a column's arithmetic is the same instructions in every slot and touches no other column's numbers, so its
+// solution is a function of (graph, weights, node, column) alone.
 
 constexpr int kPgCols = 6;                         // columns of one query at the most: two free nodes
-constexpr int kPgMStride = 9 + 3 * kPgCols;        // doubles of one staged node of pg_apply_multi: L_i or W_i, then K triples
-static_assert(kPgMStride <= 30, "pg_apply_multi stages in the LDS that pg_factor uses");
 
-// The regions of one workgroup's scratch slot, in doubles from its start: the vectors are sized for kPgCols columns.
-struct PgMLayout {
-  size_t xr, r, z, p, q, y, x, D, U, L, Si, W, lin, keys, ptr, end;
+// The regions of one workgroup's scratch slot: the vectors are sized for kPgCols columns.
+struct PgMLayout : PgTail {
+  size_t xr, r, z, p, q, y, x;
   __host__ __device__ PgMLayout(size_t n, size_t m, size_t n2) {
     const size_t v = 3 * (size_t)kPgCols * n;
     size_t o = 0;
     xr = o; o += 3 * n; r = o; o += v; z = o; o += v; p = o; o += v; q = o; o += v; y = o; o += v; x = o; o += v;
-    D = o; o += 6 * n; U = o; o += 9 * n; L = o; o += 9 * n; Si = o; o += 6 * n; W = o; o += 9 * n;
-    lin = o; o += 8 * m; keys = o; o += n2; ptr = o; o += (n + 2) / 2 + 1;
-    end = o;
+    static_cast<PgTail &>(*this) = PgTail::at(o, n, m, n2);
   }
 };
 
-// pg_block_sum for kPgCols values at once: each value goes through the same tree, and every thread gets the same bits.
-__device__ __forceinline__ void pg_block_sum_cols(double v[kPgCols], double *s_wk) {
-#pragma unroll
-  for (int k = 0; k < kPgCols; ++k) {
-    const double t = wave_sum(v[k]);
-    if ((threadIdx.x & 63) == 0) s_wk[(threadIdx.x >> 6) * kPgCols + k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kPgCols; ++k) v[k] = ((s_wk[k] + s_wk[kPgCols + k]) + s_wk[2 * kPgCols + k]) + s_wk[3 * kPgCols + k];
-  __syncthreads();
-}
-
-// pg_apply for K columns ([node][column][3] vectors): lane k of wave 0 carries column k through the forward and the backward
-// sweep, every lane reads the same L_i / W_i from LDS (a broadcast), so one trip up and one trip down serve all K columns.
-// Staged in pieces of kPgChunk nodes as pg_apply stages them; a column's arithmetic is pg_apply's.  Ends behind a barrier.
-__device__ void pg_apply_multi(const double *__restrict__ L, const double *__restrict__ Si, const double *__restrict__ W,
-                               const double *__restrict__ r, double *__restrict__ y, double *__restrict__ z, int n, int K, double *sh) {
-  const int tid = (int)threadIdx.x, K3 = 3 * K, per = 9 + K3;
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0;             // the lane's carry: y_{i-1} of its column, then z_{i+1}
-  for (int i0 = 1; i0 < n; i0 += kPgChunk) {
-    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
-    for (int idx = tid; idx < cn * per; idx += kPgThreads) {
-      const int a = idx / per, k = idx % per, i = i0 + a;
-      sh[a * kPgMStride + k] = k < 9 ? L[9 * (size_t)i + k] : r[(size_t)K3 * i + (k - 9)];
-    }
-    __syncthreads();
-    if (tid < K) {
-      for (int a = 0; a < cn; ++a) {
-        const double *q = sh + a * kPgMStride;
-        double *v = sh + a * kPgMStride + 9 + 3 * tid;
-        const double y0 = v[0] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
-        const double y1 = v[1] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
-        const double y2 = v[2] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
-        v[0] = y0; v[1] = y1; v[2] = y2;
-        c0 = y0; c1 = y1; c2 = y2;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < cn * K3; idx += kPgThreads) y[(size_t)K3 * (i0 + idx / K3) + idx % K3] = sh[(idx / K3) * kPgMStride + 9 + idx % K3];
-    __syncthreads();
-  }
-  for (int idx = tid; idx < (n - 1) * K; idx += kPgThreads) {
-    const int i = 1 + idx / K;
-    const double *s = Si + 6 * (size_t)i;
-    double *v = y + (size_t)K3 * i + 3 * (idx % K);
-    const double a = v[0], b = v[1], c = v[2];
-    v[0] = (s[0] * a + s[1] * b) + s[2] * c;
-    v[1] = (s[1] * a + s[3] * b) + s[4] * c;
-    v[2] = (s[2] * a + s[4] * b) + s[5] * c;
-  }
-  __syncthreads();
-  c0 = c1 = c2 = 0.0;
-  const int chunks = (n - 1 + kPgChunk - 1) / kPgChunk;
-  for (int ch = chunks - 1; ch >= 0; --ch) {
-    const int i0 = 1 + ch * kPgChunk;
-    const int cn = n - i0 < kPgChunk ? n - i0 : kPgChunk;
-    for (int idx = tid; idx < cn * per; idx += kPgThreads) {
-      const int a = idx / per, k = idx % per, i = i0 + a;
-      sh[a * kPgMStride + k] = k < 9 ? W[9 * (size_t)i + k] : y[(size_t)K3 * i + (k - 9)];
-    }
-    __syncthreads();
-    if (tid < K) {
-      for (int a = cn - 1; a >= 0; --a) {
-        const double *q = sh + a * kPgMStride;
-        double *v = sh + a * kPgMStride + 9 + 3 * tid;
-        const double z0 = v[0] - ((q[0] * c0 + q[1] * c1) + q[2] * c2);
-        const double z1 = v[1] - ((q[3] * c0 + q[4] * c1) + q[5] * c2);
-        const double z2 = v[2] - ((q[6] * c0 + q[7] * c1) + q[8] * c2);
-        v[0] = z0; v[1] = z1; v[2] = z2;
-        c0 = z0; c1 = z1; c2 = z2;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < cn * K3; idx += kPgThreads) z[(size_t)K3 * (i0 + idx / K3) + idx % K3] = sh[(idx / K3) * kPgMStride + 9 + idx % K3];
-    __syncthreads();
-  }
+// pg_apply at the query's column count (block-uniform).
+__device__ __forceinline__ void pg_apply_cols(int K, const PgWork &Wk, const double *r, double *y, double *z, int n, double *sh) {
+  if (K == 3) pg_apply<3>(Wk, r, y, z, n, sh); else pg_apply<kPgCols>(Wk, r, y, z, n, sh);
 }
 
 // One query's record: the blocks as given (NULL: zeros), the counters.
@@ -734,8 +725,9 @@ __device__ void pg_marginal_diag(const double *__restrict__ x, int K, int node, 
 }
 
 // Workgroup w takes the queries w, w + gridDim.x, ... in its own scratch slot (slot_bytes each, for the largest queried graph).
-// The set-up of a query is pg_solve_kernel<true>'s at the poses given, the arc weights in PgLin::pad; the conjugate gradients
-// are its loop with one alpha, beta, r^T z and stop flag per column.  A column that has stopped is frozen; every decision is
+// The set-up of a query is the solver's own functions at the poses given (pg_graph_bad, pg_arc_order, pg_radians,
+// pg_node_blocks<true, no gradient>), the arc weights as given in PgLin::wt; the conjugate gradients are the solver's loop
+// around pg_arc_hp and pg_apply<K> with one alpha, beta, r^T z and stop flag per column.  A column that has stopped is frozen; every decision is
 // taken from block sums, which every thread holds with the same bits: control flow stays uniform around the barriers.
 __global__ void __launch_bounds__(kPgThreads)
 pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restrict__ edges, const PgRow *__restrict__ rows, int n_graphs,
@@ -757,23 +749,9 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
     const double *pose = poses + 3 * R.node0;
     const ndt_pg_edge *ed = edges + R.edge0;
     const double *gw = weight ? weight + R.edge0 : nullptr;
-    // ---- the query's and the graph's own faults (pg_solve_kernel's, and a weight that is negative or not finite) ----
-    int bad = (Q.a < 0 || Q.a >= n || Q.b < 0 || Q.b >= n) ? 1 : 0;
-    for (int i = tid; i < n; i += kPgThreads)
-      if (!pg_finite(pose[3 * (size_t)i]) || !pg_finite(pose[3 * (size_t)i + 1]) || !pg_finite(pose[3 * (size_t)i + 2])) bad = 1;
-    for (int e = tid; e < m; e += kPgThreads) {
-      const ndt_pg_edge E = ed[e];
-      if (E.from < 0 || E.from >= n || E.to < 0 || E.to >= n || E.from == E.to) bad = 1;
-      bool fin = pg_finite(E.rel[0]) && pg_finite(E.rel[1]) && pg_finite(E.rel[2]);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) fin = fin && pg_finite(E.info[k]);
-      const double *I = E.info;
-      const double m2 = I[0] * I[3] - I[1] * I[1];
-      const double det = (I[0] * (I[3] * I[5] - I[4] * I[4]) + I[1] * (I[4] * I[2] - I[1] * I[5])) + I[2] * (I[1] * I[4] - I[3] * I[2]);
-      if (!fin || !(I[0] > 0.0) || !(m2 > 0.0) || !(det > 0.0)) bad = 1;
-      if (gw && (!(gw[e] >= 0.0) || !pg_finite(gw[e]))) bad = 1;
-    }
-    bad = __syncthreads_or(bad);
+    // ---- the query's own faults and the graph's (a weight that is negative or not finite among them) ----
+    int bad = pg_graph_bad(pose, ed, n, m, gw);
+    if (Q.a < 0 || Q.a >= n || Q.b < 0 || Q.b >= n) bad = 1;
     if (!bad && m == 0 && (Q.a != 0 || Q.b != 0)) bad = 1;       // (nothing ties the node to node 0)
     // ---- the free nodes whose columns are solved: a, then b unless it is a again; a block with node 0 is exactly 0 ----
     const int na = Q.a != 0 ? 1 : 0, nb = (Q.b != 0 && Q.b != Q.a) ? 1 : 0;
@@ -785,66 +763,24 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
     const int node0 = na ? Q.a : Q.b, node1 = Q.b;             // the node of the columns 0 .. 2, of the columns 3 .. 5
     const int K3 = 3 * K;
     const PgMLayout Y((size_t)n, (size_t)m, (size_t)R.n2);
-    double *xr = base + Y.xr, *r = base + Y.r, *z = base + Y.z, *p = base + Y.p, *q = base + Y.q, *y = base + Y.y, *x = base + Y.x,
-           *D = base + Y.D, *U = base + Y.U, *L = base + Y.L, *Si = base + Y.Si, *W = base + Y.W;
-    PgLin *lin = reinterpret_cast<PgLin *>(base + Y.lin);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(base + Y.keys);
-    int *ptr = reinterpret_cast<int *>(base + Y.ptr);
-    // ---- every node's arcs in arc-index order: keys (node, 2 e + side) sorted, then cut at the nodes ----
-    const unsigned n2 = R.n2, m2e = 2u * (unsigned)m;
-    for (unsigned k = (unsigned)tid; k < n2; k += kPgThreads) {
-      unsigned long long key = ~0ull;
-      if (k < m2e) { const ndt_pg_edge &E = ed[k >> 1]; key = ((unsigned long long)(unsigned)((k & 1u) ? E.to : E.from) << 32) | k; }
-      keys[k] = key;
-    }
-    __syncthreads();
-    for (unsigned kk = 2; kk <= n2; kk <<= 1)
-      for (unsigned j = kk >> 1; j > 0; j >>= 1) {
-        for (unsigned i = (unsigned)tid; i < n2; i += kPgThreads) {
-          const unsigned l = i ^ j;
-          if (l > i) {
-            const unsigned long long a = keys[i], b = keys[l];
-            if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    for (unsigned k = (unsigned)tid; k <= m2e; k += kPgThreads) {
-      const int node = k < m2e ? (int)(keys[k] >> 32) : n;
-      const int prev = k > 0 ? (int)(keys[k - 1] >> 32) : -1;
-      for (int v = prev + 1; v <= node; ++v) ptr[v] = (int)k;
-    }
-    // ---- the poses in radians (read only), the arcs linearised there with their weights, every node's D and U ----
-    for (int i = tid; i < n; i += kPgThreads) {
-      xr[3 * (size_t)i] = pose[3 * (size_t)i]; xr[3 * (size_t)i + 1] = pose[3 * (size_t)i + 1];
-      xr[3 * (size_t)i + 2] = pose[3 * (size_t)i + 2] * (kPgPi / 180.0);
-    }
+    double *xr = base + Y.xr, *r = base + Y.r, *z = base + Y.z, *p = base + Y.p, *q = base + Y.q, *y = base + Y.y, *x = base + Y.x;
+    const PgWork Wk(base, Y);
+    const unsigned long long *keys = Wk.keys;
+    const int *ptr = Wk.ptr;
+    PgLin *lin = Wk.lin;
+    // ---- the arc order, the poses in radians (read only), the arcs linearised there with their weights, every node's D and U ----
+    pg_arc_order(ed, n, m, R.n2, Wk.keys, Wk.ptr);
+    pg_radians(pose, xr, n);
     __syncthreads();
     for (int e = tid; e < m; e += kPgThreads) {
       PgLin l = pg_linearise(xr, ed[e]);
-      l.pad = gw ? gw[e] : 1.0;
+      l.wt = gw ? gw[e] : 1.0;
       lin[e] = l;
     }
     __syncthreads();
-    for (int i = 1 + tid; i < n; i += kPgThreads) {
-      double Dm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Um[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for (int k = ptr[i]; k < ptr[i + 1]; ++k) {
-        const unsigned slot = (unsigned)keys[k];
-        const int e = (int)(slot >> 1), side = (int)(slot & 1u);
-        const PgLin l = lin[e];
-        const double *I = ed[e].info;
-        const int other = side ? ed[e].from : ed[e].to;
-        double Js[9], Jo[9];
-        pg_jac(l, side, Js);
-        pg_block_add<true>(Js, I, Js, l.pad, Dm);
-        if (other == i + 1) { pg_jac(l, side ^ 1, Jo); pg_block_add<true>(Js, I, Jo, l.pad, Um); }
-      }
-      double *d = D + 6 * (size_t)i;
-      d[0] = Dm[0]; d[1] = Dm[1]; d[2] = Dm[2]; d[3] = Dm[4]; d[4] = Dm[5]; d[5] = Dm[8];
-      for (int k = 0; k < 9; ++k) U[9 * (size_t)i + k] = Um[k];
-    }
+    for (int i = 1 + tid; i < n; i += kPgThreads) pg_node_blocks<true, false>(Wk, ed, i, nullptr);
     __syncthreads();
-    if (!pg_factor(D, U, L, Si, W, n, sh, &s_ok)) {
+    if (!pg_factor(Wk.D, Wk.U, Wk.L, Wk.Si, Wk.W, n, sh, &s_ok)) {
       if (tid == 0) pg_marginal_write(out + qi, nullptr, nullptr, nullptr, 0, 0, NDT_OK);
       __syncthreads();
       continue;
@@ -861,7 +797,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
         }
       }
     __syncthreads();
-    pg_apply_multi(L, Si, W, r, y, z, n, K, sh);
+    pg_apply_cols(K, Wk, r, y, z, n, sh);
     double rz[kPgCols], rz0[kPgCols], coef[kPgCols], acc[kPgCols];
     bool act[kPgCols], ok[kPgCols];
     int its[kPgCols];
@@ -876,7 +812,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
             const double zv = z[at];
             p[at] = zv; acc[k] += r[at] * zv;
           }
-    pg_block_sum_cols(acc, s_wk);
+    pg_block_sum_cols<kPgCols>(acc, s_wk);
     bool any = false;
 #pragma unroll
     for (int k = 0; k < kPgCols; ++k) {
@@ -908,12 +844,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
           for (int k = 0; k < kPgCols; ++k)
             if (act[k]) {
               const double pi3[3] = {pi[3 * k], pi[3 * k + 1], pi[3 * k + 2]}, po3[3] = {po[3 * k], po[3 * k + 1], po[3 * k + 2]};
-              double u1[3], u2[3], w[3], o[3];
-              pg_j_mul(Js, pi3, u1); pg_j_mul(Jo, po3, u2);
-              const double u[3] = {u1[0] + u2[0], u1[1] + u2[1], u1[2] + u2[2]};
-              pg_info_mul(I, u, w);
-              pg_jt_mul(Js, w, o);
-              qv[k][0] += l.pad * o[0]; qv[k][1] += l.pad * o[1]; qv[k][2] += l.pad * o[2];
+              pg_arc_hp<true>(Js, Jo, I, l.wt, pi3, po3, qv[k]);
             }
         }
 #pragma unroll
@@ -921,7 +852,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
           if (act[k])
             for (int c = 0; c < 3; ++c) { q[(size_t)i * K3 + 3 * k + c] = qv[k][c]; acc[k] += pi[3 * k + c] * qv[k][c]; }
       }
-      pg_block_sum_cols(acc, s_wk);
+      pg_block_sum_cols<kPgCols>(acc, s_wk);
 #pragma unroll
       for (int k = 0; k < kPgCols; ++k)
         if (act[k]) {
@@ -938,7 +869,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
               x[at] += coef[k] * p[at]; r[at] -= coef[k] * q[at];
             }
       __syncthreads();
-      pg_apply_multi(L, Si, W, r, y, z, n, K, sh);
+      pg_apply_cols(K, Wk, r, y, z, n, sh);
 #pragma unroll
       for (int k = 0; k < kPgCols; ++k) acc[k] = 0.0;
       for (int i = 1 + tid; i < n; i += kPgThreads)
@@ -946,7 +877,7 @@ pg_marginal_kernel(const double *__restrict__ poses, const ndt_pg_edge *__restri
         for (int k = 0; k < kPgCols; ++k)
           if (act[k])
             for (int c = 0; c < 3; ++c) { const size_t at = (size_t)i * K3 + 3 * k + c; acc[k] += r[at] * z[at]; }
-      pg_block_sum_cols(acc, s_wk);
+      pg_block_sum_cols<kPgCols>(acc, s_wk);
       any = false;
 #pragma unroll
       for (int k = 0; k < kPgCols; ++k)
