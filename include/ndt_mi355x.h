@@ -1341,7 +1341,7 @@ int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, c
 /* ---- Loops between the sessions of a set -------------------------------------------------------------------
  * Has session a just driven into a place that session b mapped -- several robots in one building, several logs of one site?
  * The sessions must share a map frame: a session's frame is its first odometry pose (src/ScanMatcher.cpp:9-22), so the caller
- * feeds odometry that starts at the robot's known pose.  Finding an unknown offset between frames is out of scope.
+ * feeds odometry that starts at the robot's known pose.  An unknown offset between frames: the place section below.
  *
  * The cross gate.  Every searcher against every closed submap of every other track: a product, so it has a device form
  * (ndt_cross_gate_batch) beside the host definition (ndt_cross_gate); the two agree to the byte.  The rule is defined on the
@@ -1388,8 +1388,8 @@ int ndt_sessions_find_loops_multi(ndt_sessions *s, const unsigned char *which, c
  * an empty newest scan (the candidates are given, each with the empty record, and nothing is queued behind the gate), 2 when
  * no map could be built; sessions_stepped = J; launches, copies and waits do not depend on the number of sessions.
  * Refusals: those of ndt_sessions_find_loops_multi; NDT_E_HIP on a dead set.
- * Out of scope: an unknown offset between the sessions' frames; keeping cross edges from one search to the next; loop maps
- * that stay valid across calls; a robust back end. */
+ * Out of scope: keeping cross edges from one search to the next; loop maps that stay valid across calls; a robust back end.
+ * (An unknown offset between the sessions' frames: ndt_sessions_place_candidates below.) */
 typedef struct ndt_cross_track {        /* HOST: one trajectory whose closed submaps may be searched */
   const double   *poses;  size_t n_scans;               /* ndt_sessions_trajectory */
   const int      *sub_first, *sub_anchor;               /* n_submaps entries each */
@@ -1410,6 +1410,111 @@ int ndt_sessions_cross_candidates(ndt_sessions *s, const unsigned char *which, c
                                   const ndt_loop_multi_params *p, ndt_cross_candidate *out, int *n_out);
 int ndt_sessions_find_cross_loops(ndt_sessions *s, const unsigned char *which, const unsigned char *against,
                                   const ndt_loop_multi_params *p, ndt_cross_loop *out, int *n_out, ndt_result *records_host);
+
+/* ---- Place recognition: where two sessions overlap without a shared frame ---------------------------------
+ * The gates above are distance gates around the last pose: they need the searcher and the map in one frame.  Two robots started
+ * somewhere in one building, two logs of one site, or a session whose drift exceeds `radius` have none.  This section gives a
+ * ROTATION-INVARIANT DESCRIPTOR of a cloud about a centre and an all-pairs match of descriptors that returns, per query, a few
+ * candidates (item, descriptor, rotation) with no pose prior; the candidates then go through the verification that exists
+ * (ndt_score_lattice_multi_dev .. ndt_fit_points_multi_dev).  Integer work throughout: every device result
+ * is byte-identical to the host definition.
+ *
+ * THE DESCRIPTOR of a cloud about the centre (cx, cy) is n_rings uint64_t words: bit s of word r says that cell (ring r, sector
+ * s) holds at least min_pts points.  The axes are the cloud's own: no heading, no trigonometry.  For a float32 point (x, y),
+ * every operation fp64 and rounded once, no fused multiply-add:
+ *   dx = (double)x - cx, dy = (double)y - cy, r2 = dx * dx + dy * dy;
+ *   the point is skipped when r2 is not finite, r2 < r_min * r_min, or r2 >= edge2[n_rings], with
+ *   edge2[j] = (j * ring_width) * (j * ring_width), j = 1 .. n_rings (two rounded products);
+ *   ring = the number of j in 1 .. n_rings with r2 >= edge2[j];
+ *   ax = |dx|, ay = |dy|, a = max(ax, ay), b = min(ax, ay); sub = the number of j in 1 .. 7 with b >= T[j] * a (one rounded
+ *   product), T = NDT_PLACE_TAN below: the fp64 nearest to tan(j pi / 32); s16 = (ay > ax) ? 15 - sub : sub;
+ *   sector = dx >= 0 ? (dy >= 0 ? s16 : 63 - s16) : (dy >= 0 ? 31 - s16 : 32 + s16).
+ * The counts are integers: the descriptor does not depend on the order of the points.  An empty cloud gives zero words.
+ * ndt_place_describe is the definition (host, no context, no device).  ndt_place_describe_batch_dev: n_desc descriptors in one
+ * table upload and one launch, whatever n_desc; descriptor k is of cloud cloud_of[k] -- the points [offsets[c], offsets[c + 1]) of
+ * xy_dev, stride_bytes apart (8 or 16) -- about centres[2k], centres[2k + 1]; several centres may name one cloud; desc_dev[k *
+ * n_rings + r].  Every descriptor is byte-identical to ndt_place_describe and depends neither on the other descriptors, nor on
+ * NDT_OPT_WORKGROUPS, nor on the stride.  ndt_place_describe_batch: the same with host pointers, synchronous.
+ *
+ * THE KEY of a query Q against an entry D (n_rings words each) at the shift s in 0 .. 63:
+ *   c(s) = sum over r of popcount(Q_r & rotl64(D_r, s)), na = sum popcount(Q_r), nb = sum popcount(D_r), den = na + nb - c(s),
+ *   key(s) = den == 0 ? 0 : (c(s) * 65536) / den (unsigned 32-bit division): the Jaccard overlap of the two cell sets in 1/65536.
+ * A direction theta in the query's axes is the direction theta - s * 5.625 deg in the entry's axes.  The best shift of an entry
+ * is the one of largest key, ties to the smallest s.  Entries are grouped into ITEMS: item i = the descriptors [item_first[i],
+ * item_first[i + 1]) -- one submap described about several poses.  An item's hit = its descriptor of largest key, ties to the
+ * lowest descriptor.  An item is skipped for a query when q_group >= 0 && q_group == item_group[i] (its own session) or when it
+ * has no descriptor.  A query's result = its at most top_k items with key >= min_key, in descending key, ties to the lower item.
+ * ndt_place_key: one (Q, D, s) (host).  ndt_place_match_host: the definition (host, no context).  ndt_place_match_dev: one table
+ * upload and two launches (match, pick), no host wait.  out[q * top_k + j] is hit j of query q for j < n_out[q]; the records
+ * from n_out[q] on are zero.  table (may be NULL): table[q * n_items + i] = (key << 32) | (0xFFFFFFFF - (desc << 6 | shift)) of
+ * item i's hit, 0 when the item is skipped -- the ordering rules are one unsigned maximum.  out, n_out and table are
+ * byte-identical to ndt_place_match_host; a query's bytes depend neither on the other queries nor on NDT_OPT_WORKGROUPS.
+ * ndt_place_match: the same with host pointers, synchronous.  ndt_place_hit: desc counts from the first descriptor of the call;
+ * overlap = c(shift), n_query = na, n_entry = nb; rank = j.
+ *
+ * Refusals (NDT_E_ARG, nothing queued or written): a NULL context ("null context") or pointer; a parameter outside the range
+ * given beside it below, the text naming it ("ring_width", ...); a stride other than 8 or 16; n_clouds, n_desc, n_q or n_items
+ * below 0; offsets that decrease; a cloud of more than 2^32 - 1 points; a non-finite centre; cloud_of outside [0, n_clouds);
+ * item_first that does not start at 0 or decreases; more than 2^26 descriptors; n_q * n_items above 2^31 - 1.  Nothing to do
+ * (n_desc, n_q == 0): NDT_OK.
+ *
+ * ndt_sessions_place_candidates.  Searchers and tracks are chosen as in ndt_sessions_cross_candidates.  A searcher's query is its
+ * local map (the ndt_sessions_local_map points) about its last pose; its group is its session; a searcher without local-map
+ * points gets no candidates.  Item (t, m) = closed submap m of track t with a non-empty cloud (as ndt_sessions_global_map returns
+ * it) and a non-empty scan range, described about the trajectory poses of the scans sub_first[m] + j * centre_stride inside its
+ * range; its group is the track's session; the items in ascending (t, m).  A candidate: session = the searcher, map_session and
+ * submap = the item, centre_scan = the hit descriptor's scan in map_session's trajectory, shift .. rank as in ndt_place_hit,
+ * guess = the searcher's newest pose in map_session's frame as the hit reads it: (centre.x, centre.y, last.th - shift * 5.625)
+ * in (m, m, deg), not wrapped.  The searchers in ascending order, each one's candidates in a row; *n_out of them; `out` needs
+ * room for n_sessions * top_k.  Guarantees: the candidates are byte-identical to ndt_place_describe_batch on those views followed
+ * by ndt_place_match; they depend neither on the other searchers nor on top_k beyond truncation.  One table upload, one describe
+ * launch for entries and queries together, the two match launches and one read-back as the only host wait (ndt_sessions_get_stats:
+ * host_waits 1; 0 when there is no query or no item: nothing is queued), whatever the number of sessions.  The SLAM state is
+ * untouched.  Descriptors are computed afresh on every call.  Refusals: a NULL set ("null session set"), a NULL pointer, a
+ * parameter outside its range (the text names it), more descriptors or pairs than above, an open ndt_map_rebuild_begin on the
+ * context.  NDT_E_HIP: a dead set.
+ * Out of scope: descriptors kept across calls (ndt_sessions_correct and _remake_closed change the closed clouds); yaw finer
+ * than a sector; mirrored maps. */
+#define NDT_PLACE_SECTORS   64
+#define NDT_PLACE_MAX_RINGS 32
+#define NDT_PLACE_MAX_TOP_K 16
+#define NDT_PLACE_TAN { 0x1.936bb8c5b2da2p-4, 0x1.975f5e0553158p-3, 0x1.36a08355c63dcp-2, 0x1.a827999fcef32p-2, 0x1.11ab7190834ebp-1, 0x1.561b82ab7f990p-1, 0x1.a43002ae4284fp-1 }
+typedef struct ndt_place_params {
+  double ring_width;    /* m, finite, > 0                          default 0.5  */
+  double r_min;         /* m, finite, >= 0: nearer points skipped  default 0.25 */
+  int    n_rings;       /* 1 .. 32                                 default 20   */
+  int    min_pts;       /* >= 1: points a cell needs to count      default 1    */
+  int    min_key;       /* 1 .. 65536: weaker hits are dropped     default 1    */
+  int    top_k;         /* 1 .. 16                                 default 4    */
+  int    centre_stride; /* >= 1 (ndt_sessions_place_candidates)    default 1    */
+  int    reserved;      /* 0 */
+} ndt_place_params;
+typedef struct ndt_place_hit { int item, desc, shift, key, overlap, n_query, n_entry, rank; } ndt_place_hit;   /* 32 bytes */
+typedef struct ndt_place_candidate {
+  int session, map_session, submap, centre_scan, shift, key, overlap, n_query, n_entry, rank;
+  double guess[3];
+} ndt_place_candidate;
+int ndt_place_default_params(ndt_place_params *p);
+int ndt_place_describe(const float *xy_host, size_t n, size_t stride_bytes, double cx, double cy, const ndt_place_params *p,
+                       uint64_t *desc_host);
+int ndt_place_describe_batch_dev(ndt_ctx *ctx, const float *xy_dev, size_t stride_bytes, const uint64_t *offsets_host, int n_clouds,
+                                 const double *centres_host, const int *cloud_of_host, int n_desc, const ndt_place_params *p,
+                                 uint64_t *desc_dev, void *stream);
+int ndt_place_describe_batch(ndt_ctx *ctx, const float *xy_host, size_t stride_bytes, const uint64_t *offsets_host, int n_clouds,
+                             const double *centres_host, const int *cloud_of_host, int n_desc, const ndt_place_params *p,
+                             uint64_t *desc_host);
+int ndt_place_key(const uint64_t *q_desc, const uint64_t *d_desc, int n_rings, int shift, int *key, int *overlap);
+int ndt_place_match_host(const uint64_t *q_desc, const int *q_group, int n_q, const uint64_t *d_desc, const int *item_first,
+                         const int *item_group, int n_items, const ndt_place_params *p, uint64_t *table, ndt_place_hit *out,
+                         int *n_out);
+int ndt_place_match_dev(ndt_ctx *ctx, const uint64_t *q_desc_dev, const int *q_group_host, int n_q, const uint64_t *d_desc_dev,
+                        const int *item_first_host, const int *item_group_host, int n_items, const ndt_place_params *p,
+                        uint64_t *table_dev, ndt_place_hit *out_dev, int *n_out_dev, void *stream);
+int ndt_place_match(ndt_ctx *ctx, const uint64_t *q_desc_host, const int *q_group_host, int n_q, const uint64_t *d_desc_host,
+                    const int *item_first_host, const int *item_group_host, int n_items, const ndt_place_params *p,
+                    uint64_t *table_host, ndt_place_hit *out_host, int *n_out_host);
+int ndt_sessions_place_candidates(ndt_sessions *s, const unsigned char *which, const unsigned char *against,
+                                  const ndt_place_params *p, ndt_place_candidate *out, int *n_out);
 
 /* ---- The scan archive and ndt_sessions_occ_rebuild: occupancy grids that follow a correction -----------------
  * ndt_sessions_occ_integrate casts a session's newest scan at the pose it had at that step; after ndt_sessions_correct every beam

@@ -208,6 +208,26 @@ class CrossLoop(C.Structure):
     _fields_ = [("m", LoopMulti), ("map_session", C.c_int), ("reserved", C.c_int)]
 
 
+class PlaceParams(C.Structure):
+    """ndt_place_params (include/ndt_mi355x.h): the place descriptor's geometry and the match's selection."""
+    _fields_ = [("ring_width", C.c_double), ("r_min", C.c_double), ("n_rings", C.c_int), ("min_pts", C.c_int), ("min_key", C.c_int),
+                ("top_k", C.c_int), ("centre_stride", C.c_int), ("reserved", C.c_int)]
+
+
+class PlaceHit(C.Structure):
+    """ndt_place_hit (include/ndt_mi355x.h): one item a query's descriptor matched, at its best descriptor and shift."""
+    _fields_ = [(n, C.c_int) for n in ("item", "desc", "shift", "key", "overlap", "n_query", "n_entry", "rank")]
+
+
+class PlaceCandidate(C.Structure):
+    """ndt_place_candidate (include/ndt_mi355x.h): a closed submap of another session that a searcher's local map resembles."""
+    _fields_ = [(n, C.c_int) for n in ("session", "map_session", "submap", "centre_scan", "shift", "key", "overlap", "n_query",
+                                       "n_entry", "rank")] + [("guess", C.c_double * 3)]
+
+
+NDT_PLACE_SECTORS, NDT_PLACE_MAX_RINGS, NDT_PLACE_MAX_TOP_K = 64, 32, 16
+PLACE_HIT_DTYPE = np.dtype(PlaceHit)
+PLACE_CANDIDATE_DTYPE = np.dtype(PlaceCandidate)
 LOOP_CANDIDATE_DTYPE = np.dtype(LoopCandidate)
 CROSS_CANDIDATE_DTYPE = np.dtype(CrossCandidate)
 CROSS_LOOP_DTYPE = np.dtype(CrossLoop)
@@ -358,6 +378,15 @@ PROTOTYPES = {
     "ndt_cross_gate_batch": [_vp, _vp, _vp, _vp, _i, _vp, _i, _P(LoopMultiParams), _vp, _vp],
     "ndt_sessions_cross_candidates": [_vp, _vp, _vp, _P(LoopMultiParams), _vp, _P(_i)],
     "ndt_sessions_find_cross_loops": [_vp, _vp, _vp, _P(LoopMultiParams), _vp, _P(_i), _vp],
+    "ndt_place_default_params": [_P(PlaceParams)],
+    "ndt_place_describe": [_vp, _sz, _sz, _d, _d, _P(PlaceParams), _vp],
+    "ndt_place_describe_batch_dev": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _i, _P(PlaceParams), _vp, _vp],
+    "ndt_place_describe_batch": [_vp, _vp, _sz, _vp, _i, _vp, _vp, _i, _P(PlaceParams), _vp],
+    "ndt_place_key": [_vp, _vp, _i, _i, _P(_i), _P(_i)],
+    "ndt_place_match_host": [_vp, _vp, _i, _vp, _vp, _vp, _i, _P(PlaceParams), _vp, _vp, _vp],
+    "ndt_place_match_dev": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _P(PlaceParams), _vp, _vp, _vp, _vp],
+    "ndt_place_match": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _P(PlaceParams), _vp, _vp, _vp],
+    "ndt_sessions_place_candidates": [_vp, _vp, _vp, _P(PlaceParams), _vp, _P(_i)],
     "ndt_sessions_archive_enable": [_vp],
     "ndt_sessions_archive_info": [_vp, _i, _P(_sz), _P(_sz)],
     "ndt_sessions_archive_scans": [_vp, _i, _sz, _sz, _vp, _sz, _vp, _P(_sz)],
@@ -666,6 +695,106 @@ def cross_gate_batch(ctx, last_poses, newest_scan, own, tracks, params):
     ctx.check(lib().ndt_cross_gate_batch(ctx.h, _ptr(last), _ptr(newest), _ptr(own), len(last), C.addressof(arr), len(tracks),
                                          C.byref(params), out.ctypes.data, n.ctypes.data), "ndt_cross_gate_batch")
     return [out[i, :n[i]] for i in range(len(last))]
+
+
+def default_place_params(**kw):
+    """ndt_place_default_params, fields overridden by keyword."""
+    return _defaults(PlaceParams, "ndt_place_default_params", kw)
+
+
+def _place_clouds(clouds, stride):
+    """Clouds ([n_i, 2] float32 each, empty ones allowed) packed `stride` bytes apart (8, or 16 with two unused floats per
+    point) -> (the packed array, offsets in points)."""
+    pts, off = pack_scans(clouds)
+    if stride == 16:
+        wide = np.zeros((len(pts), 4), dtype=np.float32)
+        wide[:, :2] = pts
+        pts = wide
+    return pts, off
+
+
+def _place_centres(centres, cloud_of):
+    centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 2)
+    cloud_of = np.ascontiguousarray(cloud_of, dtype=np.int32)
+    if len(cloud_of) != len(centres):
+        raise ValueError("one cloud_of per centre")
+    return centres, cloud_of
+
+
+def place_describe(xy, centre, params, stride=8):
+    """ndt_place_describe (host only, the definition): the descriptor of one cloud about `centre` -> [n_rings] uint64."""
+    pts, _ = _place_clouds([xy], stride)
+    desc = np.zeros(max(params.n_rings, 1), dtype=np.uint64)
+    _check(lib().ndt_place_describe(_ptr(pts), len(pts), stride, float(centre[0]), float(centre[1]), C.byref(params), desc.ctypes.data),
+           "ndt_place_describe")
+    return desc
+
+
+def place_describe_batch(ctx, clouds, centres, cloud_of, params, stride=8):
+    """ndt_place_describe_batch: descriptor k of clouds[cloud_of[k]] about centres[k], in one upload and one launch ->
+    [n_desc, n_rings] uint64, byte for byte place_describe's."""
+    pts, off = _place_clouds(clouds, stride)
+    centres, cloud_of = _place_centres(centres, cloud_of)
+    desc = np.zeros((len(centres), max(params.n_rings, 1)), dtype=np.uint64)
+    ctx.check(lib().ndt_place_describe_batch(ctx.h, _ptr(pts), stride, off.ctypes.data, len(off) - 1, _ptr(centres), _ptr(cloud_of),
+                                             len(centres), C.byref(params), _ptr(desc)), "ndt_place_describe_batch")
+    return desc
+
+
+def place_describe_batch_dev(ctx, xy_ptr, stride, offsets, centres, cloud_of, params, desc_ptr, stream=None):
+    """ndt_place_describe_batch_dev: device addresses of the points and of the descriptors; offsets, centres and cloud_of host
+    arrays."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    centres, cloud_of = _place_centres(centres, cloud_of)
+    ctx.check(lib().ndt_place_describe_batch_dev(ctx.h, xy_ptr, stride, off.ctypes.data, len(off) - 1, _ptr(centres), _ptr(cloud_of),
+                                                 len(centres), C.byref(params), desc_ptr, stream), "ndt_place_describe_batch_dev")
+
+
+def place_key(q_desc, d_desc, shift):
+    """ndt_place_key (host only): (key, overlap) of a query descriptor against an entry at one shift."""
+    q, d = np.ascontiguousarray(q_desc, dtype=np.uint64), np.ascontiguousarray(d_desc, dtype=np.uint64)
+    if q.shape != d.shape or q.ndim != 1:
+        raise ValueError("place_key needs two descriptors of one length")
+    key, c = C.c_int(), C.c_int()
+    _check(lib().ndt_place_key(_ptr(q), _ptr(d), len(q), int(shift), C.byref(key), C.byref(c)), "ndt_place_key")
+    return key.value, c.value
+
+
+def _place_match_args(q_desc, q_group, d_desc, item_first, item_group, params):
+    R = params.n_rings if 1 <= params.n_rings <= NDT_PLACE_MAX_RINGS else 1        # (outside: the library refuses)
+    q, d =np.ascontiguousarray(q_desc, dtype=np.uint64).reshape(-1, R), np.ascontiguousarray(d_desc, dtype=np.uint64).reshape(-1, R)
+    qg, first = np.ascontiguousarray(q_group, dtype=np.int32), np.ascontiguousarray(item_first, dtype=np.int32)
+    group = np.ascontiguousarray(item_group, dtype=np.int32)
+    if len(qg) != len(q) or len(first) != len(group) + 1 or (len(first) and int(first[-1]) > len(d)):
+        raise ValueError("place match: one group per query, one more item_first than items, item_first within the descriptors")
+    K = params.top_k if 1 <= params.top_k <= NDT_PLACE_MAX_TOP_K else NDT_PLACE_MAX_TOP_K
+    table = np.zeros((len(q), len(group)), dtype=np.uint64)
+    out, n = np.zeros((max(len(q), 1), K), dtype=PLACE_HIT_DTYPE), np.zeros(max(len(q), 1), dtype=np.int32)
+    return q, qg, d, first, group, table, out, n
+
+
+def place_match_host(q_desc, q_group, d_desc, item_first, item_group, params):
+    """ndt_place_match_host (host only, the definition) -> (hits [n_q, top_k] PLACE_HIT_DTYPE, n [n_q], table [n_q, n_items])."""
+    q, qg, d, first, group, table, out, n = _place_match_args(q_desc, q_group, d_desc, item_first, item_group, params)
+    _check(lib().ndt_place_match_host(_ptr(q), _ptr(qg), len(q), _ptr(d), first.ctypes.data, _ptr(group), len(group), C.byref(params),
+                                      _ptr(table.reshape(-1)), out.ctypes.data, n.ctypes.data), "ndt_place_match_host")
+    return out[:len(q)], n[:len(q)], table
+
+
+def place_match(ctx, q_desc, q_group, d_desc, item_first, item_group, params):
+    """ndt_place_match: place_match_host on the device (one table upload, two launches), byte for byte."""
+    q, qg, d, first, group, table, out, n = _place_match_args(q_desc, q_group, d_desc, item_first, item_group, params)
+    ctx.check(lib().ndt_place_match(ctx.h, _ptr(q), _ptr(qg), len(q), _ptr(d), first.ctypes.data, _ptr(group), len(group), C.byref(params),
+                                    _ptr(table.reshape(-1)), out.ctypes.data, n.ctypes.data), "ndt_place_match")
+    return out[:len(q)], n[:len(q)], table
+
+
+def place_match_dev(ctx, q_desc_ptr, q_group, d_desc_ptr, item_first, item_group, params, out_ptr, n_out_ptr, table_ptr=None, stream=None):
+    """ndt_place_match_dev: device addresses of the descriptors and the outputs; the groups and item_first host arrays."""
+    qg, first = np.ascontiguousarray(q_group, dtype=np.int32), np.ascontiguousarray(item_first, dtype=np.int32)
+    group = np.ascontiguousarray(item_group, dtype=np.int32)
+    ctx.check(lib().ndt_place_match_dev(ctx.h, q_desc_ptr, _ptr(qg), len(qg), d_desc_ptr, first.ctypes.data, _ptr(group), len(group),
+                                        C.byref(params), table_ptr, out_ptr, n_out_ptr, stream), "ndt_place_match_dev")
 
 
 def pg_edge_between(from_pose, to_pose):
@@ -1407,6 +1536,17 @@ class Sessions(_Handle):
         """ndt_sessions_find_cross_loops: one CROSS_LOOP_DTYPE record per cross candidate; with want_records also the match
         records, as [candidates, NDT_LOOP_MAX_CAND] RESULT_DTYPE (the first n_cand of a row are written)."""
         return self._cross("ndt_sessions_find_cross_loops", CROSS_LOOP_DTYPE, params, which, against, bool(want_records))
+
+    def place_candidates(self, params, which=None, against=None):
+        """ndt_sessions_place_candidates: for every searcher (`which`) up to params.top_k closed submaps of the OTHER sessions
+        (`against`) whose place descriptor resembles the searcher's local map, best first, with a pose guess in the other
+        session's frame -- no shared frame needed -- as PLACE_CANDIDATE_DTYPE records (one host wait)."""
+        K = params.top_k if 1 <= params.top_k <= NDT_PLACE_MAX_TOP_K else NDT_PLACE_MAX_TOP_K
+        out = np.zeros(self.n * K, dtype=PLACE_CANDIDATE_DTYPE)
+        w, a, n = self._active(which), self._active(against), C.c_int()
+        self.ctx.check(lib().ndt_sessions_place_candidates(self.h, None if w is None else w.ctypes.data, None if a is None else a.ctypes.data,
+                                                           C.byref(params), out.ctypes.data, C.byref(n)), "ndt_sessions_place_candidates")
+        return out[:n.value]
 
     def find_loops_multi(self, params, which=None, want_records=False):
         """ndt_sessions_find_loops_multi: one LOOP_MULTI_DTYPE record per candidate; with want_records also the match records,

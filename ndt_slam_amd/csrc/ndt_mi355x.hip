@@ -239,6 +239,10 @@ struct ndt_ctx {
   DevBuf<unsigned char> d_cg;                          // ndt_cross_gate_batch: the call's table (rows, packed poses, searchers), the (searcher x row) minima, the picks (ndt_cross.hip.h)
   StagedUpload<unsigned char> cg_tab;                  // ... the table's staging
   PinnedBuf<unsigned char> h_cg;                       // ... the picks' read-back
+  DevBuf<unsigned char> d_pld, d_plm;                  // ndt_place_describe_batch_dev: the call's table (edges, rows); ndt_place_match_dev: its table (groups, items) and scratch (ndt_place.hip.h)
+  StagedUpload<unsigned char> pld_tab, plm_tab;        // ... their stagings (one each: a match queued behind a describe does not wait for the describe's upload)
+  DevBuf<unsigned char> d_pl_host;                     // the host forms' copies of clouds, descriptors and results
+  PinnedBuf<unsigned char> h_pl;                       // ndt_sessions_place_candidates: the hits' read-back
   int num_cus = 0;
   int helpers = -1;                                    // NDT_OPT_MAX_HELPERS: helper workgroups per scan (0: no work sharing; -1: by the size of the launch)
   int workgroups = 0;                                  // NDT_OPT_WORKGROUPS: workgroups of a match launch (0: one per CU)
@@ -4612,3 +4616,4 @@ int ndt_lattice_select_multi_dev(ndt_ctx *ctx, const ndt_score_job *jobs, int n_
 
 #include "ndt_loops.hip.h"
 #include "ndt_cross.hip.h"
+#include "ndt_place.hip.h"

@@ -821,6 +821,118 @@ def cross_graph(trajs, loop_edges_per_session, cross_edges, odo_info):
     return np.concatenate(trajs), np.concatenate(parts + [tail]), offset
 
 
+def place_verify(ctx, sessions, candidates, loop_params):
+    """Sessions.place_candidates' `candidates` through the stages of the multi-submap loop search, made of public calls: a map
+    of every candidate's closed cloud (capi.build_maps), the searcher's newest scan -- from the set's archive, robot frame,
+    pre-filtered at the set's leaf --, a lattice of loop_params.loop's steps and half extents around the candidate's guess (wide
+    enough when the half extents cover one ring width and one sector, +-3 deg), then ndt_score_lattice_multi_dev ->
+    ndt_lattice_select_multi_dev -> ndt_align_batch_multi_dev -> ndt_fit_points_multi_dev over all candidates at once.  A
+    candidate is accepted by ndt_sessions_find_loops_multi's rule (include/ndt_mi355x.h: a pick is usable when it converged with
+    n_in >= 1 and n_in >= min_overlap * n_points, its cost the ranged fitness; the best pick is the accepted one of largest n_in,
+    then lowest cost; accepted when its cost <= max_cost).  -> [(candidate index, edge)] of the accepted candidates: edge a
+    capi.PG_EDGE_DTYPE record from the candidate's centre scan in map_session's trajectory to the searcher's newest scan, rel =
+    ndt_pg_edge_between(that scan's pose, the matched pose), info = loop_params.loop.info."""
+    import torch
+
+    from . import capi
+    lp, K = loop_params.loop, loop_params.loop.top_k
+    cands = list(candidates)
+    if not cands:
+        return []
+    dev = torch.device("cuda", ctx.device)
+    trajs = {i: sessions.trajectory(i)[0] for c in cands for i in (int(c["session"]), int(c["map_session"]))}
+    closed = {i: sessions.global_map(i)[1] for i in {int(c["map_session"]) for c in cands}}
+    searchers = sorted({int(c["session"]) for c in cands})
+    leaf = sessions.params.leaf
+    scans = [ctx.prefilter(np.asarray(sessions.archive_scans(i, len(trajs[i]) - 1, 1)[0], np.float32), leaf) for i in searchers]
+    if any(len(s) == 0 for s in scans):
+        raise ValueError("place_verify: a searcher's newest scan is empty")
+    maps = capi.build_maps(ctx, [closed[int(c["map_session"])][int(c["submap"])] for c in cands], sessions.params.match)
+    try:
+        jobs = []
+        for j, c in enumerate(cands):
+            g = c["guess"]
+            lat = capi.PoseLattice(x0=g[0] - lp.half_x * lp.step_xy, y0=g[1] - lp.half_y * lp.step_xy,
+                                   yaw0=DEG2RAD(g[2]) - lp.half_yaw * lp.step_yaw, step_x=lp.step_xy, step_y=lp.step_xy,
+                                   step_yaw=lp.step_yaw, nx=2 * lp.half_x + 1, ny=2 * lp.half_y + 1, nyaw=2 * lp.half_yaw + 1)
+            jobs.append((j, searchers.index(int(c["session"])), lat))
+        pts, off = capi.pack_scans(scans)
+        d_pts, d_off = torch.from_numpy(pts).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev)
+        total = sum(lat.size for _, _, lat in jobs)
+        d_score = torch.zeros(total, dtype=torch.float64, device=dev)
+        d_pairs = torch.zeros(total, dtype=torch.int32, device=dev)
+        d_cand = torch.zeros(len(jobs) * K, dtype=torch.int64, device=dev)
+        d_n = torch.zeros(len(jobs), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.score_lattice_multi_dev(maps, d_pts.data_ptr(), d_off.data_ptr(), len(scans), len(pts), jobs, d_score.data_ptr(), d_pairs.data_ptr())
+        ctx.lattice_select_multi_dev(jobs, d_score.data_ptr(), d_pairs.data_ptr(), K, lp.local_max, d_cand.data_ptr(), d_n.data_ptr())
+        torch.cuda.synchronize(dev)
+        picks, n_pick = d_cand.cpu().numpy().reshape(len(jobs), K), d_n.cpu().numpy()
+        rows = [(j, int(q)) for j in range(len(jobs)) for q in picks[j, :n_pick[j]]]
+        if not rows:
+            return []
+        inits = np.array([jobs[j][2].pose(q) for j, q in rows], np.float64).reshape(-1, 3)
+        m_pts, m_off = capi.pack_scans([scans[jobs[j][1]] for j, _ in rows])
+        d_mp, d_mo = torch.from_numpy(m_pts).to(dev), torch.from_numpy(m_off.astype(np.int64)).to(dev)
+        d_map_of = torch.tensor([j for j, _ in rows], dtype=torch.int32, device=dev)
+        d_init = torch.from_numpy(inits).to(dev)
+        d_res = torch.zeros(len(rows) * capi.RESULT_BYTES, dtype=torch.uint8, device=dev)
+        d_fit = torch.zeros(len(rows) * capi.FIT_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.align_batch_multi_dev(maps, d_map_of.data_ptr(), d_mp.data_ptr(), d_mo.data_ptr(), len(rows), len(m_pts), d_init.data_ptr(),
+                                  d_res.data_ptr())
+        ctx.fit_points_multi_dev(maps, d_map_of.data_ptr(), d_mp.data_ptr(), d_mo.data_ptr(), len(rows), len(m_pts),
+                                 d_res.data_ptr() + capi.RESULT_DTYPE.fields["T00"][1], capi.RESULT_BYTES, loop_params.max_d2, None, d_fit.data_ptr())
+        torch.cuda.synchronize(dev)
+        res = d_res.cpu().numpy().view(capi.RESULT_DTYPE)
+        fit = d_fit.cpu().numpy().view(capi.FIT_STATS_DTYPE)
+    finally:
+        for m in maps:
+            m.close()
+    out = []
+    for j, c in enumerate(cands):
+        best, best_key = -1, None
+        for r, (jj, _) in enumerate(rows):
+            if jj != j:
+                continue
+            usable = bool(res[r]["converged"]) and fit[r]["n_in"] >= 1 and float(fit[r]["n_in"]) >= loop_params.min_overlap * float(fit[r]["n_points"])
+            cost = float(fit[r]["fitness"]) if usable else 1e7
+            key = (not cost <= lp.max_cost, -(int(fit[r]["n_in"]) if usable else 0), cost)
+            if best_key is None or key < best_key:
+                best, best_key = r, key
+        if best < 0 or best_key[0]:
+            continue
+        pose = np.array([res[best]["pose"][0], res[best]["pose"][1], RAD2DEG(res[best]["pose"][2])])
+        edge = np.zeros(1, dtype=capi.PG_EDGE_DTYPE)[0]
+        edge["from"], edge["to"] = int(c["centre_scan"]), len(trajs[int(c["session"])]) - 1
+        edge["rel"] = capi.pg_edge_between(trajs[int(c["map_session"])][int(c["centre_scan"])], pose)
+        edge["info"] = lp.info[:]
+        out.append((j, edge))
+    return out
+
+
+def align_frames(traj_b, edge, traj_a):
+    """B's trajectory expressed in A's frame from one accepted place edge (edge.from a scan of A, edge.to a scan of B, rel the
+    pose of B's scan seen from A's): the rigid motion that carries traj_b[edge.to] onto traj_a[edge.from] (+) rel, applied to
+    every pose of B -> [n, 3] (tx, ty, th[deg], headings wrapped as Pose2D does).  A usable start for cross_graph."""
+    traj_a = np.asarray(traj_a, np.float64).reshape(-1, 3)
+    traj_b = np.asarray(traj_b, np.float64).reshape(-1, 3)
+    names = getattr(getattr(edge, "dtype", None), "names", None) or ()
+    a = traj_a[int(edge["from" if "from" in names else "from_"])]
+    b = traj_b[int(edge["to"])]
+    rel = np.asarray(edge["rel"], np.float64)
+    ca, sa = math.cos(DEG2RAD(a[2])), math.sin(DEG2RAD(a[2]))
+    want = np.array([a[0] + ca * rel[0] - sa * rel[1], a[1] + sa * rel[0] + ca * rel[1], add_angle(a[2], rel[2])])     # (calPredPose's composition)
+    dth = sub_angle(want[2], b[2])
+    c, s = math.cos(DEG2RAD(dth)), math.sin(DEG2RAD(dth))
+    out = np.empty_like(traj_b)
+    dx, dy = traj_b[:, 0] - b[0], traj_b[:, 1] - b[1]
+    out[:, 0] = want[0] + c * dx - s * dy
+    out[:, 1] = want[1] + s * dx + c * dy
+    out[:, 2] = [add_angle(t, dth) for t in traj_b[:, 2]]
+    return out
+
+
 def _close_cross(ctx, sessions, lc, which):
     """One cross search of the sessions `which` against all, the sessions grouped by the edges found, one batch with a joint
     graph per group, correct() for every session of a group whose graph converged -> the corrected sessions' flags."""
